@@ -8,8 +8,14 @@ the timed region; one call returns only ~40 B per trajectory.  With N > 1 GPUs e
 B trajectories (weak scaling, no data-path collective) and one tiny all_gather of energy-ranked
 records closes the step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision mfma16|f16|fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision mfma16|f16|fp32] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (the `roofline` of the timed launches included: it comes from
+the same steps and from committed counter files).  The secondary records that take runs of their own - the fp32 engine
+(`fp32_engine`), C5 (`c5`), C4 (`c4`, `c4_sharded`) and the CPU baseline (`cpu_baseline`) - run only with --full.
+--dump-outputs DIR writes what the last timed step returned on rank 0 (dfm_sample's arrays and the gathered records) as float32
+DIR/<name>.npy; the inputs depend on the arguments alone, so two builds can be compared output for output.
 
 `python bench.py --gpus N` with no RANK in the environment starts the N ranks itself (one process per GPU, rendezvous on
 127.0.0.1) and still prints ONE JSON line.  The record gather runs over RCCL ("nccl") when every rank's RCCL probe succeeds,
@@ -299,6 +305,25 @@ def c4_sharded_line(model, precision, num_steps, rank, world, backend):
 FLOP_PER_NODE_EVAL = 59.2e6
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as float32 DIR/<name>.npy.  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the rows
+    (trajectories, records) is kept - the same rows of every array with the same leading size."""
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = DUMP_LIMIT_BYTES / total
+        for k, a in arrays.items():
+            n = a.shape[0]
+            keep = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * frac)), replace=False))
+            arrays[k] = a[keep]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def workload_label(a):
     shape = f"synthetic {a.R}+{a.L}-residue complex, batch={a.batch} trajectories/GPU, {a.num_steps} steps ({a.num_steps + 1} score evaluations + energy head)"
     if (a.R, a.L, a.batch, a.num_steps) == (300, 300, 256, 40):
@@ -362,12 +387,18 @@ def main():
                     help="mfma16: the 16-bit MFMA engine as shipped (DFM_F_MFMA16: fp16 operands, fp32 accumulation; dfm_config_string() "
                          "in the JSON line says what that is; reported as dtype f16); f16: the same with fp32 A_i; fp32: exact; "
                          "bf16: deprecated ALIAS of mfma16 kept for BASELINE's wording - the operands are fp16, not bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary records (fp32 engine, C5, C4 / c4_sharded, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned (rank 0) as float32 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-l0-table", action="store_true", help="A/B: layer 0 evaluated edge by edge (DFM_F_NO_L0_TABLE)")
-    ap.add_argument("--no-fp32-line", action="store_true", help="skip the secondary measurement of the fp32 engine (one more batched call)")
-    ap.add_argument("--no-c5-line", action="store_true", help="skip the secondary C5 record (1000+1000 residues, batch 32: one timed call)")
-    ap.add_argument("--no-c4-line", action="store_true", help="skip the secondary C4 record (24 DB5-sized complexes x 40 trajectories through driver.run_set, three drivers)")
+    ap.add_argument("--no-fp32-line", action="store_true", help="with --full: skip the secondary measurement of the fp32 engine (one more batched call)")
+    ap.add_argument("--no-c5-line", action="store_true", help="with --full: skip the secondary C5 record (1000+1000 residues, batch 32: one timed call)")
+    ap.add_argument("--no-c4-line", action="store_true", help="with --full: skip the secondary C4 record (24 DB5-sized complexes x 40 trajectories through driver.run_set, three drivers)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -419,9 +450,9 @@ def main():
     edge_ms, edge_launches, edge_rows, lig_launches, lig_ms = 0.0, 0, 0, 0, 0.0
     clk_cycles = clk_ticks = 0.0      # the message kernel's own clock stamps (dfm_profile::edge_shader_cycles / edge_ref_ticks)
     l0 = dict(l0_evals=0, l0_edges=0, l0_miss_rows=0, l0_rows_ms=0.0, l0_gather_ms=0.0)
-    allrec = None
+    last = allrec = None
     for it in range(args.steps):
-        _, allrec = one_step(args.warmup + it, profile=True)
+        last, allrec = one_step(args.warmup + it, profile=True)
         p = gx.profile()
         edge_ms += p["edge_kernel_ms"]
         edge_launches += p["edge_kernel_launches"]
@@ -436,12 +467,14 @@ def main():
     elapsed = time.perf_counter() - t0
     per_rank = D.allgather_scalars([elapsed, float(dev)])      # max over ranks of the time; which device every rank ran on
     elapsed = float(per_rank[:, 0].max())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(last, records=allrec))
     headline = (args.R, args.L, args.batch, args.num_steps) == (300, 300, 256, 40)
     c4s = None
-    if world > 1 and headline and not args.no_c4_line:      # every rank takes part (outside the timed C3 region)
+    if args.full and world > 1 and headline and not args.no_c4_line:      # every rank takes part (outside the timed C3 region)
         c4s = c4_sharded_line(model, args.precision, args.num_steps, rank, world, grp.backend)
     fp32_line = None
-    if rank == 0 and world == 1 and mfma16 and not args.no_fp32_line:
+    if args.full and rank == 0 and world == 1 and mfma16 and not args.no_fp32_line:
         # secondary record: the fp32 engine - the reference's own arithmetic - on the same workload, one batched call
         gx.sample(B=B, num_steps=2, seed=7, l0_table=not args.no_l0_table)      # (builds the fp32 engine's own layer-0 table)
         torch.cuda.synchronize()
@@ -568,13 +601,13 @@ def main():
                                    "gather_tbps": 512 * l0["l0_edges"] / max(l0["l0_gather_ms"], 1e-9) / 1e9,
                                    "note": "per evaluation: k_edge_msg<1,1,1> over the row list (inter-chain edges + bin mismatches) and "
                                            "k_l0_gather (K rows of 512 B per node, out of L2 / the Infinity Cache) replace one full message launch"}
-        if world == 1 and mfma16 and headline and not args.no_c5_line:
+        if args.full and world == 1 and mfma16 and headline and not args.no_c5_line:
             out["c5"] = c5_line(engine, model, pk, args.num_steps)
-        if world == 1 and headline and not args.no_c4_line:
+        if args.full and world == 1 and headline and not args.no_c4_line:
             out["c4"] = c4_line(engine, model, args.precision, args.num_steps)
-        if world > 1 and headline and not args.no_c4_line:
+        if args.full and world > 1 and headline and not args.no_c4_line:
             out["c4_sharded"] = c4s      # measured by every rank below the timed C3 region (collectives inside), reported by rank 0
-        if not args.no_cpu_baseline and world == 1:     # reported baseline: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:     # reported baseline: rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(blob, cx, args.num_steps)
         print(json.dumps(out), flush=True)
     D.shutdown()

@@ -220,14 +220,14 @@ def test_bench_eight_ranks_oversubscribed_on_one_gpu():
 
 def test_bench_c4_sharded_record_on_two_ranks(tmp_path):
     """BASELINE config 4 is DEFINED as a sharded run (24 DB5-sized complexes x 40 trajectories over the ranks of one node, one gather
-    of the ranked energy records; the loop it replaces: src/inference_mlsb.py:415-439).  `bench.py --gpus N` puts it on the line as
+    of the ranked energy records; the loop it replaces: src/inference_mlsb.py:415-439).  `bench.py --gpus N --full` puts it on the line as
     `c4_sharded`.  Two ranks on the one GPU of the test box: 960 records with 960 distinct (complex,
     trajectory) ids reach every rank, both ranks took complexes, and the sharded CSV is byte-identical to the one-rank CSV of the
     same call (a trajectory is a pure function of seed, complex and index)."""
     env = dict(os.environ, DFM_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -275,13 +275,13 @@ def test_bench_c4_sharded_record_on_two_ranks(tmp_path):
 
 
 def test_bench_eight_ranks_headline_shape_carries_c4_sharded():
-    """The driver's 8-GPU command at the HEADLINE shape (no size overrides) on the 1-GPU box: eight self-spawned ranks share GPU 0.  After the weak-scaling C3
+    """The driver's 8-GPU command at the HEADLINE shape (no size overrides, --full) on the 1-GPU box: eight self-spawned ranks share GPU 0.  After the weak-scaling C3
     step (8 x 256 trajectories) the line must carry BASELINE config 4 as `c4_sharded`: 24 DB5-sized complexes x 40 trajectories sharded three per rank by the
     cost model, 960 distinct (complex, trajectory) ids in ONE gather (the loop it replaces: src/inference_mlsb.py:415-439).  No scaling claim."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "DFM_DIST_BACKEND"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]

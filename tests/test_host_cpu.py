@@ -509,3 +509,25 @@ def test_bench_c4_set_is_the_db5_fixtures(monkeypatch, tmp_path):
     monkeypatch.setattr(bench.os.path, "abspath", lambda p: str(tmp_path / "bench.py"))      # no tests/golden next to it
     syn, what2 = bench.c4_complexes()
     assert len(syn) == 24 and "synthetic" in what2 and sorted((c["rec_x"].shape[0], c["lig_x"].shape[0]) for c in syn) == sorted(bench.DB5_SIZES)
+
+
+def test_bench_dump_outputs_float32_and_bounded(monkeypatch, tmp_path):
+    """bench.py --dump-outputs: every array as float32 <name>.npy; above the size limit a fixed seeded sample of the rows, the same
+    rows of every array with the same leading size, and the same sample on every call."""
+    import bench
+    rng = np.random.default_rng(0)
+    arrays = {"lig_pos": rng.standard_normal((64, 30, 3, 3)).astype(np.float32), "num_clashes": np.arange(64, dtype=np.int32),
+              "records": rng.standard_normal((64, 10)).astype(np.float32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for k, a in arrays.items():
+        b = np.load(tmp_path / "all" / (k + ".npy"))
+        assert b.dtype == np.float32 and b.shape == a.shape and (b == a).all()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", sum(a.size for a in arrays.values()))      # a quarter of the float32 bytes
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {k: np.load(tmp_path / "s1" / (k + ".npy")) for k in arrays}
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT_BYTES and 0 < got["num_clashes"].shape[0] < 64
+    keep = got["num_clashes"].astype(np.int64)                      # the rows kept, in order
+    assert (np.diff(keep) > 0).all() and (got["lig_pos"] == arrays["lig_pos"][keep]).all() and (got["records"] == arrays["records"][keep]).all()
+    for k in arrays:
+        assert (np.load(tmp_path / "s2" / (k + ".npy")) == got[k]).all()

@@ -1,5 +1,4 @@
 """Host-side I/O of the drivers against values produced by the reference's own functions."""
-import os
 
 import numpy as np
 import pytest
@@ -84,9 +83,57 @@ def test_apply_pose_matches_sampler_convention():
     np.testing.assert_allclose(a, b, atol=2e-4)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/data/db5_test/4POU.pt"), reason="reference data not mounted")
-def test_db5_pt_reader_shapes():
+def _write_hetero_data_pt(path, cid, parts, monkeypatch):
+    """A torch.save file laid out like the reference's data/db5_test/<id>.pt (a pickled torch_geometric HeteroData: `_global_store`
+    = BaseStorage{_mapping: {name}}, `_node_store_dict` = {receptor, ligand: NodeStorage{_mapping: {x [n,1280] f32, pos [n,3,3]
+    f32, seq}, _parent, _key}}, `_edge_store_dict` = {}), written through stand-in classes under torch_geometric's module paths - the same pickle opcodes
+    (GLOBAL + NEWOBJ + BUILD of the instance dict, tensors as persistent storages) without torch_geometric."""
+    import sys
+    import types
+    import torch
+
+    def cls(module, name):
+        c = type(name, (), {"__module__": module})
+        c.__qualname__ = name
+        return c
+    mods = {m: types.ModuleType(m) for m in ("torch_geometric", "torch_geometric.data", "torch_geometric.data.hetero_data",
+                                             "torch_geometric.data.storage")}
+    Hetero, Base, Node = cls("torch_geometric.data.hetero_data", "HeteroData"), cls("torch_geometric.data.storage", "BaseStorage"), \
+        cls("torch_geometric.data.storage", "NodeStorage")
+    mods["torch_geometric.data.hetero_data"].HeteroData = Hetero
+    mods["torch_geometric.data.storage"].BaseStorage, mods["torch_geometric.data.storage"].NodeStorage = Base, Node
+    for m, mod in mods.items():
+        monkeypatch.setitem(sys.modules, m, mod)
+    data = Hetero()
+    g = Base()
+    g.__dict__.update(_mapping={"name": cid}, _parent=data)
+    stores = {}
+    for key, (x, pos, seq) in parts.items():
+        n = Node()
+        n.__dict__.update(_mapping={"x": torch.from_numpy(x), "pos": torch.from_numpy(pos), "seq": seq}, _parent=data, _key=key)
+        stores[key] = n
+    data.__dict__.update(_global_store=g, _node_store_dict=stores, _edge_store_dict={})
+    torch.save(data, path)
+
+
+def test_db5_pt_reader_shapes(tmp_path, monkeypatch):
+    """dfmdock_amd.db5.load_db5_pt on a file in the layout of the reference's data/db5_test/4POU.pt, built from the committed 4POU
+    arrays (backbone + sequence: db5_backbones.npz; ESM-2 block: esm_db5_q8.npz, dequantised)."""
     from dfmdock_amd.db5 import load_db5_pt
-    d = load_db5_pt("/root/reference/data/db5_test/4POU.pt")
+    bb, q8 = load_golden("db5_backbones.npz"), load_golden("esm_db5_q8.npz")
+    esm = q8["4POU_q"].astype(np.float32) * q8["4POU_s"].astype(np.float32)[:, None]
+    R = len(str(bb["4POU_rec_seq"]))
+    parts = {"receptor": (esm[:R], bb["4POU_rec_pos"].astype(np.float32), str(bb["4POU_rec_seq"])),
+             "ligand": (esm[R:], bb["4POU_lig_pos"].astype(np.float32), str(bb["4POU_lig_seq"]))}
+    path = str(tmp_path / "4POU.pt")
+    _write_hetero_data_pt(path, "4POU", parts, monkeypatch)
+    monkeypatch.undo()      # the reader must not need the stand-ins
+    d = load_db5_pt(path)
     assert d["rec_x"].shape == (120, 1301) and d["lig_x"].shape == (120, 1301) and d["rec_pos"].shape == (120, 3, 3)
     assert (d["rec_x"][:, 1280:].sum(1) == 1).all() and len(d["rec_seq"]) == 120
+    assert d["id"] == "4POU"
+    for side, key in (("rec", "receptor"), ("lig", "ligand")):
+        x, pos, seq = parts[key]
+        assert d[side + "_seq"] == seq
+        np.testing.assert_array_equal(d[side + "_x"][:, :1280], x)
+        np.testing.assert_array_equal(d[side + "_pos"], pos)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-end evidence run on the GPU box (every step under its own timeout, outputs under gpurun_out/final/, copied into profiles/ by
 # tools/copy_evidence.sh):
-#   full GPU test suite | default bench line (with cpu_baseline and the fp32 secondary line) | rocprofv3 --kernel-trace --stats of the
+#   full GPU test suite | full bench line (--full: cpu_baseline, the fp32 / C5 / C4 secondary records) | rocprofv3 --kernel-trace --stats of the
 #   same bench command | kernel profiles at B = 1 and B = 8 | counters of EVERY kernel of the step evaluation in one set of passes (FETCH_SIZE / WRITE_SIZE in separate
 #   --pmc passes, SQ busy counters; no trace domains) -> traffic JSON that bench.py replays (per launch type of the message kernel,
 #   per-kernel table) | counters of k_knn_sample at C5 | C5 kernel stats | second model family | tolerance report | size sweeps
@@ -28,7 +28,7 @@ prof bench_prof python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-fp32-lin
 pmc pmc_all 'k_edge_msg|k_l0_gather|k_gemm_split|k_edge_coord|k_knn_sample|k_edge_feat|k_heads' --batch 256 --num-steps 3
 python tools/make_traffic_json.py $OUT > $OUT/traffic_summary.txt 2>&1; cat $OUT/traffic_summary.txt
 cp $OUT/traffic.json profiles/r06_traffic.json      # so that the bench line below replays THIS run's counters
-timeout 900 python bench.py > $OUT/bench.log 2>&1; tail -1 $OUT/bench.log | cut -c1-400
+timeout 900 python bench.py --full > $OUT/bench.log 2>&1; tail -1 $OUT/bench.log | cut -c1-400
 pmc pmc_knn_c5 'k_knn_sample' --R 1000 --L 1000 --batch 32 --num-steps 3; grep -E "INSTS_VALU |ACTIVE_INST_VALU|GRBM" $OUT/pmc_knn_c5.txt
 prof c5 python $GRAFT_REPO_ROOT/bench.py --R 1000 --L 1000 --batch 32 --steps 1 --warmup 1 --no-cpu-baseline --no-fp32-line; tail -1 $OUT/c5.log | cut -c1-200; head -8 $OUT/c5_kernel_stats.csv | cut -c1-160
 prof pair python $GRAFT_REPO_ROOT/tools/pair_bench.py 256; tail -4 $OUT/pair.log; head -6 $OUT/pair_kernel_stats.csv | cut -c1-160

@@ -5,7 +5,7 @@ timeout 2400 python -m pytest tests -m gpu -q -s -p no:cacheprovider > $OUT/pyte
 grep -E "chi-square|KS D|P\(energy" $OUT/pytest_gpu.log | cut -c1-400
 timeout 600 python tools/c4_run.py > $OUT/c4_syn.txt 2> $OUT/c4_syn.err; cat $OUT/c4_syn.txt
 timeout 600 python tools/c4_run.py --db5 > $OUT/c4_db5.txt 2> $OUT/c4_db5.err; cat $OUT/c4_db5.txt; grep selfcheck $OUT/c4_db5.err | head -30 > $OUT/selfcheck_db5.txt
-timeout 900 python bench.py > $OUT/bench.log 2> $OUT/bench.err; tail -1 $OUT/bench.log | cut -c1-600; tail -3 $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/bench.log 2> $OUT/bench.err; tail -1 $OUT/bench.log | cut -c1-600; tail -3 $OUT/bench.err
 python - <<'PY'
 import json,os
 l=open(os.environ["GRAFT_REPO_ROOT"]+"/gpurun_out/r05_1/bench.log").read().strip().splitlines()[-1]

@@ -4,7 +4,7 @@ timeout 2400 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/pytest_
 timeout 600 python tools/selfcheck_db5.py > $OUT/selfcheck_db5.txt 2>&1; cut -c1-330 $OUT/selfcheck_db5.txt
 timeout 600 python tools/c4_run.py > $OUT/c4_syn.txt 2> $OUT/c4_syn.err; grep -v "^SYN\|^id," $OUT/c4_syn.txt | cut -c1-330
 timeout 600 python tools/c4_run.py --db5 > $OUT/c4_db5.txt 2> $OUT/c4_db5.err; grep -v "^1AVX\|^id," $OUT/c4_db5.txt | cut -c1-330
-timeout 900 python bench.py > $OUT/bench.log 2> $OUT/bench.err; tail -2 $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/bench.log 2> $OUT/bench.err; tail -2 $OUT/bench.err
 python - <<'PY'
 import json,os
 l=open(os.environ["GRAFT_REPO_ROOT"]+"/gpurun_out/r05_2/bench.log").read().strip().splitlines()[-1]
