@@ -30,12 +30,14 @@ DFM_F_DIST = 1 << 10
 DFM_F_L0_TABLE = 1 << 11       # dfm_score: layer 0 through the per-complex message table
 DFM_F_NO_L0_TABLE = 1 << 12    # dfm_sample: layer 0 evaluated directly
 DFM_F_GRAPH = 1 << 13          # dfm_sample: replay one captured step as a hipGraph (opt-in)
+DFM_F_RESTRAINTS = 1 << 14     # dfm_sample: the interface restraint step (dfm_complex_set_restraints)
 
 EXPORTS = [
     "dfm_last_error", "dfm_config_string", "dfm_device_count", "dfm_set_device", "dfm_default_hparams", "dfm_param_count",
     "dfm_model_create", "dfm_model_destroy", "dfm_complex_create", "dfm_complex_destroy", "dfm_complex_degree",
     "dfm_complex_set_pose", "dfm_complex_set_homomer",
     "dfm_score", "dfm_sample", "dfm_get_profile", "dfm_diffusion_coef", "dfm_complex_selfcheck", "dfm_trim_cache",
+    "dfm_complex_set_restraints", "dfm_restraint_eval",
 ]
 
 
@@ -82,6 +84,10 @@ class SelfcheckC(C.Structure):
                 ("saturated", C.c_int64), ("range_ok", C.c_int), ("dev_ok", C.c_int), ("ok", C.c_int)]
 
 
+class RestraintParamsC(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("k_tr", "k_rot", "max_tr", "max_rot", "t_start")]
+
+
 _lib = None
 
 
@@ -119,6 +125,8 @@ def lib():
                              C.POINTER(InjectC), C.POINTER(TrajOutC)]
     L.dfm_get_profile.argtypes = [C.c_void_p, C.POINTER(ProfileC)]
     L.dfm_complex_selfcheck.argtypes = [C.c_void_p, C.c_int, F32P, C.c_uint64, C.c_uint32, C.POINTER(SelfcheckC)]
+    L.dfm_complex_set_restraints.argtypes = [C.c_void_p, C.c_int, I32P, I32P, F32P, F32P, C.POINTER(RestraintParamsC)]
+    L.dfm_restraint_eval.argtypes = [C.c_void_p, C.c_int, F32P, F32P, I32P, F32P]
     L.dfm_trim_cache.argtypes = [C.c_int]
     L.dfm_trim_cache.restype = C.c_longlong
     L.dfm_diffusion_coef.argtypes = [C.POINTER(HParamsC), C.c_int, C.c_double, C.POINTER(C.c_double),

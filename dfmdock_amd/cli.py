@@ -3,6 +3,8 @@
     python -m dfmdock_amd dock REC.pdb LIG.pdb --ckpt model_0.ckpt --features F.npz [--num-samples 120] [--out output.pdb]
     python -m dfmdock_amd sweep --db5 data/db5_test --ckpt model_0.ckpt [--num-samples 40] [--out-csv results.csv]
     python -m dfmdock_amd selfcheck REC.pdb LIG.pdb --ckpt model_0.ckpt --features F.npz
+    python -m dfmdock_amd dock ... --restraints FILE [--restraint-rank satisfied|energy]
+    python -m dfmdock_amd sweep ... --native-restraints K [--restraint-cutoff 8.0]
 
   dock       <- src/inference_single.py:1-12 -> inference() (src/inference_base.py:601-670): num_samples (120) trajectories of
                 num_steps (40), the minimum-energy one applied to the all-atom ligand, `output.pdb` written, {"energy": E} printed.
@@ -13,6 +15,10 @@
   sweep      <- inference_mlsb.Sampler.run_sampling over PPIDataset('db5_test') (src/inference_mlsb.py:188-262,
                 src/datasets/ppi_dataset.py:224-329): every `<id>.pt` of --db5 (ids from `test.txt` when present), the
                 reference-schema CSV (src/inference_base.py:495-499) and the DockQ success-rate table.
+  restraints no reference counterpart: interface distance restraints applied in the sampler (dfmdock_amd/restraints.py; file
+             format there and in INTEGRATION.md).  `dock --restraints` keeps the minimum-energy trajectory among those satisfying the
+             most groups (`--restraint-rank energy`: the plain minimum-energy rule); `sweep --native-restraints K` restrains every
+             complex with K seeded native CA-CA contacts (< --restraint-cutoff A), the usual evaluation of guided docking.
   selfcheck  no reference counterpart: dfm_complex_selfcheck on the pair (what `dock` and `sweep` run once per complex anyway).
 
 --ckpt takes the Lightning checkpoint the reference loads (src/inference_base.py:611-616; read without Lightning / omegaconf by
@@ -54,6 +60,10 @@ def build_parser():
     d.add_argument("--num-samples", type=int, default=120)
     d.add_argument("--out", default="output.pdb")
     d.add_argument("--json", default=None, help="also write the result line to this file")
+    d.add_argument("--restraints", default=None, help="interface restraint file: REC_RESIDUES LIG_RESIDUES UPPER [WEIGHT] per line")
+    d.add_argument("--restraint-rank", default="satisfied", choices=["satisfied", "energy"],
+                   help="with --restraints: keep the minimum energy among the trajectories satisfying the most groups (default) "
+                        "or the plain minimum energy")
     _add_common(d)
     s = sub.add_parser("sweep", help="sample every complex of a DB5-style directory (inference_mlsb.py run_sampling)")
     s.add_argument("--db5", required=True, help="directory of <id>.pt files (+ optional test.txt with the ids to run)")
@@ -63,6 +73,9 @@ def build_parser():
     s.add_argument("--traj-dir", default=None, help="write one multi-MODEL PDB per trajectory (save_trj)")
     s.add_argument("--no-global-rotation", action="store_true", help="skip the loader's random rotation (ppi_dataset.py:309)")
     s.add_argument("--limit", type=int, default=None, help="first N ids only")
+    s.add_argument("--native-restraints", type=int, default=None, metavar="K",
+                   help="restrain every complex with K seeded native CA-CA contacts (adds restraint columns to the CSV)")
+    s.add_argument("--restraint-cutoff", type=float, default=8.0, help="contact cutoff and upper bound of --native-restraints (A)")
     _add_common(s)
     c = sub.add_parser("selfcheck", help="fp32-vs-16-bit check + fp16 range telemetry of one pair")
     c.add_argument("pdb_1")
@@ -129,6 +142,19 @@ def success_table(rows):
     return per, table
 
 
+def restraint_summary(rows, restraints_by_id):
+    """Per complex: the number of restraint groups, the trajectories satisfying all of them, and the mean number satisfied."""
+    out = {}
+    for cid, groups in sorted(restraints_by_id.items()):
+        rs = [r for r in rows if r["id"] == cid]
+        if not rs:
+            continue
+        sat = [int(r["restraints_satisfied"]) for r in rs]
+        out[cid] = {"groups": len(groups), "all_satisfied": sum(s == len(groups) for s in sat), "n": len(rs),
+                    "mean_satisfied": float(np.mean(sat))}
+    return out
+
+
 def format_table(per, table):
     lines = [f"{'id':8s} {'n':>4s} {'top1 DockQ':>11s} {'best DockQ':>11s} {'top1 energy':>12s}"]
     for cid, p in per.items():
@@ -143,16 +169,26 @@ def cmd_dock(args):
     from . import driver
     model, _ = load_model(args)
     rec, lig, rec_x, lig_x = load_pair(args.pdb_1, args.pdb_2, args.features, model.hp.lm_embed_dim)
+    kw = {}
+    if args.restraints:
+        from .restraints import read_restraints
+        kw = dict(restraints=read_restraints(args.restraints, rec, lig), restraint_rank=args.restraint_rank)
     res = driver.dock_pair(model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                            precision=args.precision, out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
-                           on_selfcheck_fail=args.on_selfcheck_fail)
+                           on_selfcheck_fail=args.on_selfcheck_fail, **kw)
     line = {"energy": res["energy"], "output": os.path.abspath(args.out), "num_samples": args.num_samples, "precision": res["precision"],
             "rot_update": [float(v) for v in res["rot_update"]], "tr_update": [float(v) for v in res["tr_update"]],
             "selfcheck_ok": None if res["selfcheck"] is None else bool(res["selfcheck"]["ok"])}
+    if args.restraints:
+        line.update(restraints=res["restraints"], restraints_satisfied=res["restraints_satisfied"],
+                    restraint_energy=res["restraint_energy"], restraint_rank=res["restraint_rank"], index=res["index"])
     print(json.dumps(line), flush=True)
     if args.json:
+        extra = {}
+        if args.restraints:
+            extra["trajectories"] = {k: [float(x) for x in v] for k, v in res["trajectories"].items()}
         with open(args.json, "w") as f:
-            json.dump(dict(line, selfcheck=res["selfcheck"]), f, default=float)
+            json.dump(dict(line, selfcheck=res["selfcheck"], **extra), f, default=float)
     return 0
 
 
@@ -184,19 +220,28 @@ def cmd_sweep(args):
     if not cxs:
         raise SystemExit(f"sweep: no <id>.pt under {args.db5}")
     checks = []
+    rkw = {}
+    if args.native_restraints is not None:
+        from .restraints import native_contact_groups
+        rkw["restraints_by_id"] = {c["id"]: native_contact_groups(c["rec_pos"], c["lig_pos"], args.native_restraints,
+                                                                  cutoff=args.restraint_cutoff, seed=args.seed) for c in cxs}
     rows, _ = driver.run_set(model, cxs, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                              precision=args.precision, global_rotation=not args.no_global_rotation, out_csv=args.out_csv,
                              traj_dir=args.traj_dir, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
-                             on_selfcheck_fail=args.on_selfcheck_fail, checks_out=checks)
+                             on_selfcheck_fail=args.on_selfcheck_fail, checks_out=checks, **rkw)
     all_rows = driver._gather_rows(rows, world)
     all_checks = [c for part in D.gather_objects(checks) for c in part] if world > 1 else checks
     if rank == 0:
         per, table = success_table(all_rows)
         print(format_table(per, table), flush=True)
+        extra = {}
+        if rkw:
+            extra["restraints"] = restraint_summary(all_rows, rkw["restraints_by_id"])
+            print(json.dumps({"restraints": extra["restraints"]}), flush=True)
         if args.summary:
             with open(args.summary, "w") as f:
                 json.dump({"csv": os.path.abspath(args.out_csv), "complexes": per, "success": table, "selfcheck": all_checks,
-                           "world": world, "backend": grp.backend if grp else "single"}, f, default=float, indent=1)
+                           "world": world, "backend": grp.backend if grp else "single", **extra}, f, default=float, indent=1)
     if world > 1:
         D.shutdown()
     return 0

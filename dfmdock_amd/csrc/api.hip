@@ -317,6 +317,12 @@ struct dfm_complex {
     uint64_t step_key = 0;       // (B, engine flags) the graph was captured for
     uint64_t buf_gen = 0;        // bumped whenever a buffer a captured launch points into is re-allocated (workspace, message table)
     uint64_t step_gen = ~0ull;   // buf_gen at capture
+    // interface restraints (dfm_complex_set_restraints): the set in its own pool, replaced as a whole
+    DevPool rs_pool;
+    int32_t *rs_gstart = nullptr, *rs_pairs = nullptr, *rs_big = nullptr;
+    float *rs_upper = nullptr, *rs_weight = nullptr;
+    int rs_G = 0, rs_nbig = 0;
+    dfm_restraint_params rs_par = {};
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -715,7 +721,7 @@ extern "C" dfm_complex *dfm_complex_create(dfm_model *m, const float *rec_x, con
     bool ok = hipStreamCreateWithFlags(&cx->stream, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipEventCreate(&cx->ev_total[0]) == hipSuccess && hipEventCreate(&cx->ev_total[1]) == hipSuccess;
     float *x = nullptr;
-    cx->pool.bind(cx->stream); cx->ws.pool.bind(cx->stream); cx->l0_pool.bind(cx->stream); cx->l0_pool32.bind(cx->stream);
+    cx->pool.bind(cx->stream); cx->rs_pool.bind(cx->stream); cx->ws.pool.bind(cx->stream); cx->l0_pool.bind(cx->stream); cx->l0_pool32.bind(cx->stream);
     DevPool tmp;      // staging of the raw node features: a cached block (hipMalloc / hipFree would drain the device)
     tmp.bind(cx->stream);
     ok = ok && tmp.alloc(&x, (size_t)N * lm) == hipSuccess;
@@ -760,6 +766,7 @@ extern "C" void dfm_complex_destroy(dfm_complex *cx)
     if (cx->stream) drained = hipStreamSynchronize(cx->stream) == hipSuccess;
     // every block of the handle was only ever touched by its own stream, which is drained now: no device-wide wait
     cx->ws.pool.release(drained); cx->ws.tpool.release(drained); cx->l0_pool.release(drained); cx->l0_pool32.release(drained); cx->pool.release(drained);
+    cx->rs_pool.release(drained);
     if (cx->stream) (void)hipStreamDestroy(cx->stream);
     if (cx->step_exec) (void)hipGraphExecDestroy(cx->step_exec);
     for (hipEvent_t e : cx->ev) (void)hipEventDestroy(e);
@@ -801,6 +808,102 @@ extern "C" int dfm_complex_set_homomer(dfm_complex *cx, int flag)
         (void)project_layer0(cx);                      // best effort: put the old projection back
         (void)hipStreamSynchronize(cx->stream);
         return fail(DFM_E_HIP, hipGetErrorString(e));
+    }
+    return DFM_OK;
+}
+
+// defaults of dfm_restraint_params, tuned on four DB5 fixtures
+static dfm_restraint_params default_restraint_params() { return dfm_restraint_params{0.25f, 3e-3f, 10.0f, 0.3f, 1.0f}; }
+
+extern "C" int dfm_complex_set_restraints(dfm_complex *cx, int G, const int32_t *gstart, const int32_t *pairs, const float *upper,
+                                          const float *weight, const dfm_restraint_params *par)
+{
+    if (!cx) return fail(DFM_E_INVALID, "NULL argument");
+    if (G < 0 || G > RS_MAX_GROUPS) return fail(DFM_E_INVALID, "restraints: need 0 <= n_groups <= " + std::to_string(RS_MAX_GROUPS));
+    dfm_restraint_params pr = par ? *par : default_restraint_params();
+    if (!(pr.k_tr >= 0.f) || !(pr.k_rot >= 0.f) || !(pr.max_tr >= 0.f) || !(pr.max_rot >= 0.f) || !std::isfinite(pr.k_tr) ||
+        !std::isfinite(pr.k_rot) || !std::isfinite(pr.max_tr) || !std::isfinite(pr.max_rot) || std::isnan(pr.t_start))
+        return fail(DFM_E_INVALID, "restraints: k_tr, k_rot, max_tr, max_rot must be finite and >= 0, t_start a number");
+    std::vector<int32_t> big;
+    if (G > 0) {
+        if (!gstart || !pairs || !upper || !weight) return fail(DFM_E_INVALID, "restraints: NULL array");
+        if (gstart[0] != 0) return fail(DFM_E_INVALID, "restraints: group_start[0] must be 0");
+        for (int g = 0; g < G; ++g) {
+            const long long n = (long long)gstart[g + 1] - gstart[g];
+            if (n < 1) return fail(DFM_E_INVALID, "restraints: group " + std::to_string(g) + " is empty (group_start must increase)");
+            if (gstart[g + 1] > RS_MAX_PAIRS) return fail(DFM_E_INVALID, "restraints: more than " + std::to_string(RS_MAX_PAIRS) + " pairs");
+            if (n > RS_SMALL) big.push_back(g);
+            if (!(upper[g] > 0.f) || !std::isfinite(upper[g]))
+                return fail(DFM_E_INVALID, "restraints: group " + std::to_string(g) + ": upper bound must be finite and > 0");
+            if (!(weight[g] >= 0.f) || !std::isfinite(weight[g]))
+                return fail(DFM_E_INVALID, "restraints: group " + std::to_string(g) + ": weight must be finite and >= 0");
+        }
+        for (int q = 0; q < gstart[G]; ++q) {
+            if (pairs[q * 2] < 0 || pairs[q * 2] >= cx->R || pairs[q * 2 + 1] < 0 || pairs[q * 2 + 1] >= cx->L)
+                return fail(DFM_E_INVALID, "restraints: pair " + std::to_string(q) + " = (" + std::to_string(pairs[q * 2]) + ", " +
+                                               std::to_string(pairs[q * 2 + 1]) + ") outside [0, R) x [0, L) = [0, " + std::to_string(cx->R) +
+                                               ") x [0, " + std::to_string(cx->L) + ")");
+        }
+    }
+    DEVICE_SCOPE(cx->device);
+    HIPCHK(hipStreamSynchronize(cx->stream));      // nothing in flight reads the old set any more
+    DevPool np;
+    np.bind(cx->stream);
+    int32_t *d_gs = nullptr, *d_pairs = nullptr, *d_big = nullptr;
+    float *d_up = nullptr, *d_w = nullptr;
+    if (G > 0) {
+        const size_t P = (size_t)gstart[G];
+        hipError_t e = np.upload_async(&d_gs, gstart, (size_t)G + 1, cx->stream);
+        if (e == hipSuccess) e = np.upload_async(&d_pairs, pairs, P * 2, cx->stream);
+        if (e == hipSuccess) e = np.upload_async(&d_up, upper, (size_t)G, cx->stream);
+        if (e == hipSuccess) e = np.upload_async(&d_w, weight, (size_t)G, cx->stream);
+        if (e == hipSuccess && !big.empty()) e = np.upload_async(&d_big, big.data(), big.size(), cx->stream);
+        const hipError_t es = hipStreamSynchronize(cx->stream);
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) { np.release(es == hipSuccess); return fail(DFM_E_HIP, std::string("restraints upload: ") + hipGetErrorString(e)); }
+    }
+    std::swap(cx->rs_pool.ptrs, np.ptrs);
+    np.release(true);      // the old set
+    cx->rs_gstart = d_gs; cx->rs_pairs = d_pairs; cx->rs_big = d_big; cx->rs_upper = d_up; cx->rs_weight = d_w;
+    cx->rs_G = G; cx->rs_nbig = (int)big.size(); cx->rs_par = pr;
+    // the captured step graph holds the old set's pointers and parameters by value: capture again on the next call
+    if (cx->step_exec) { (void)hipGraphExecDestroy(cx->step_exec); cx->step_exec = nullptr; }
+    return DFM_OK;
+}
+
+static RestraintArgs restraint_args(const dfm_complex *cx, float *lig)
+{
+    RestraintArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.rec_pos = cx->rec_pos; a.R = cx->R; a.L = cx->L; a.all_atoms = cx->m->hp.family == 1;
+    a.gstart = cx->rs_gstart; a.pairs = cx->rs_pairs; a.upper = cx->rs_upper; a.weight = cx->rs_weight; a.big = cx->rs_big;
+    a.G = cx->rs_G; a.n_big = cx->rs_nbig;
+    a.k_tr = cx->rs_par.k_tr; a.k_rot = cx->rs_par.k_rot; a.max_tr = cx->rs_par.max_tr; a.max_rot = cx->rs_par.max_rot;
+    a.t_start = cx->rs_par.t_start;
+    a.lig = lig;
+    return a;
+}
+
+extern "C" int dfm_restraint_eval(dfm_complex *cx, int B, const float *lig_pos, float *energy, int32_t *n_satisfied, float *step)
+{
+    if (!cx || !lig_pos || !energy || !n_satisfied) return fail(DFM_E_INVALID, "NULL argument");
+    if (B < 1) return fail(DFM_E_INVALID, "need B >= 1");
+    DEVICE_SCOPE(cx->device);
+    DevPool tmp;
+    tmp.bind(cx->stream);
+    float *lig = nullptr, *o = nullptr;
+    HIPCHK(tmp.upload_async(&lig, lig_pos, (size_t)B * cx->L * 9, cx->stream));
+    HIPCHK(tmp.alloc(&o, (size_t)B * 8));
+    RestraintArgs a = restraint_args(cx, lig);
+    a.out = o;
+    HIPCHK(launch_restraint(a, B, cx->stream));
+    std::vector<float> h((size_t)B * 8);
+    HIPCHK(hipMemcpyAsync(h.data(), o, h.size() * 4, hipMemcpyDeviceToHost, cx->stream));
+    HIPCHK(hipStreamSynchronize(cx->stream));
+    for (int b = 0; b < B; ++b) {
+        energy[b] = h[(size_t)b * 8];
+        n_satisfied[b] = (int32_t)h[(size_t)b * 8 + 1];
+        if (step) std::memcpy(step + (size_t)b * 6, &h[(size_t)b * 8 + 2], 6 * sizeof(float));
     }
     return DFM_OK;
 }
@@ -1575,6 +1678,16 @@ extern "C" int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, floa
     // the pose a step produces is prepared for the next evaluation by that step's k_heads (one dependent launch less per step) unless
     // something still moves it afterwards (clash force) or the step is a captured graph (whose first launch is the preparation)
     const bool fuse_prep = !use_graph && !(flags & DFM_F_CLASH_FORCE);
+    // the restraint step (DFM_F_RESTRAINTS with a set stored): after k_heads, before the clash force.  Without the clash force it is the
+    // last kernel that moves the pose and takes over k_heads' preparation of it - the flag adds no dependent launch per step
+    const bool restr = (flags & DFM_F_RESTRAINTS) && cx->rs_G > 0;
+    auto restraint_step = [&](int i, const uint32_t *ctl) {
+        RestraintArgs ra = restraint_args(cx, W.lig_cur);
+        ra.apply = 1; ra.tr_update = W.tr_update; ra.rot_update = W.rot_update;
+        ra.t_dev = W.t_dev; ra.step = (uint32_t)i; ra.ctl = ctl;
+        if (fuse_prep) { ra.prep_next = 1; ra.prep_pos = W.pos; ra.prep_ca4 = W.ca4; ra.prep_cb4 = W.cb4; }
+        return launch_restraint(ra, B, s);
+    };
     if (use_graph) {
         std::vector<StepParams> sp(S);
         for (int i = 0; i < num_steps; ++i) {
@@ -1587,7 +1700,7 @@ extern "C" int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, floa
         HIPCHK(hipMemcpyAsync(W.step_ctl, ctl_h, sizeof(ctl_h), hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));      // (pageable sources: the copies have read them)
         const uint64_t key = ((uint64_t)(uint32_t)B << 32) | (uint64_t)(flags & (DFM_F_MFMA16 | DFM_F_F16 | DFM_F_BF16_OPS | DFM_F_CLASH_FORCE | DFM_F_ODE | DFM_F_NO_L0_TABLE))
-                             | (l0 ? 1ull << 31 : 0ull);
+                             | (l0 ? 1ull << 31 : 0ull) | (restr ? (uint64_t)DFM_F_RESTRAINTS : 0ull);
         if (!cx->step_exec || cx->step_key != key || cx->step_gen != cx->buf_gen) {
             if (cx->step_exec) { (void)hipGraphExecDestroy(cx->step_exec); cx->step_exec = nullptr; }
             hipGraph_t graph = nullptr;
@@ -1599,6 +1712,7 @@ extern "C" int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, floa
                 step_head_args(0, ha);
                 ha.hid_base = W.hid_base; ha.step_params = W.step_params; ha.ctl = W.step_ctl;
                 hipError_t e = launch_heads(ha, s);
+                if (e == hipSuccess && restr) e = restraint_step(0, W.step_ctl);
                 if (e == hipSuccess && (flags & DFM_F_CLASH_FORCE)) e = launch_clash_force(cx->rec_pos, B, cx->R, cx->L, W.lig_cur, W.tr_update, s);
                 if (e != hipSuccess) crc = fail(DFM_E_HIP, hipGetErrorString(e));
             }
@@ -1623,13 +1737,13 @@ extern "C" int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, floa
         if (rc) return rc;
         HeadArgs ha;
         step_head_args(i, ha);
-        if (fuse_prep) { ha.prep_next = 1; ha.rec_pos = cx->rec_pos; ha.prep_pos = W.pos; ha.prep_ca4 = W.ca4; ha.prep_cb4 = W.cb4; }
+        if (fuse_prep && !restr) { ha.prep_next = 1; ha.rec_pos = cx->rec_pos; ha.prep_pos = W.pos; ha.prep_ca4 = W.ca4; ha.prep_cb4 = W.cb4; }
         HIPCHK(launch_heads(ha, s));
-        if (flags & DFM_F_CLASH_FORCE) {   // inference_base.py:458-461
+        if (restr) HIPCHK(restraint_step(i, nullptr));
+        if (flags & DFM_F_CLASH_FORCE)   // inference_base.py:458-461
             HIPCHK(launch_clash_force(cx->rec_pos, B, cx->R, cx->L, W.lig_cur, W.tr_update, s));
-            if (tp_d) HIPCHK(hipMemcpy2DAsync(tp_d + (size_t)i * L * 9, S * L * 9 * 4, W.lig_cur, L * 9 * 4, L * 9 * 4, B,
-                                              hipMemcpyDeviceToDevice, s));
-        }
+        if (tp_d && (restr || (flags & DFM_F_CLASH_FORCE)))      // the trace holds the pose after the whole step
+            HIPCHK(hipMemcpy2DAsync(tp_d + (size_t)i * L * 9, S * L * 9 * 4, W.lig_cur, L * 9 * 4, L * 9 * 4, B, hipMemcpyDeviceToDevice, s));
     }
     // final evaluation of the last pose, with the energy head (inference_base.py:463-466); same t as the last step
     o.edges_dev = ed_d ? ed_d + (size_t)num_steps * N * K : nullptr;

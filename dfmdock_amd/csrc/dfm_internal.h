@@ -331,4 +331,30 @@ hipError_t launch_init_pose(const float *rec_pos, const float *lig0, int B, int 
 hipError_t launch_clash_force(const float *rec_pos, int B, int R, int L, float *lig_cur, float *tr_update,
                               hipStream_t s);
 
+// interface distance restraints (kernels_geom.hip: k_restraint; include/dfmdock_amd.h: dfm_complex_set_restraints)
+constexpr int RS_MAX_GROUPS = 4096;       // per-group arg-min in LDS (12 B per group)
+constexpr int RS_MAX_PAIRS = 1 << 20;
+constexpr int RS_SMALL = 16;              // groups of up to RS_SMALL pairs: one lane each; larger ones (listed in `big`): one wave each
+struct RestraintArgs {
+    const float *rec_pos;       // [R][9]  the receptor as the sampler sees it (the clash force's coordinates)
+    int R, L, all_atoms;        // all_atoms: rotate about the all-backbone-atom centroid (second family, as k_heads)
+    const int32_t *gstart;      // [G+1]
+    const int32_t *pairs;       // [P][2]  (receptor index, ligand index)
+    const float *upper, *weight;   // [G]
+    const int32_t *big;         // [n_big] the groups with more than RS_SMALL pairs
+    int G, n_big;
+    float k_tr, k_rot, max_tr, max_rot, t_start;
+    float *lig;                 // [B][L][9]  pose (moved in place when apply)
+    int apply;                  // sampler: move the pose and the bookkeeping; 0: evaluation only (dfm_restraint_eval)
+    float *tr_update, *rot_update;   // [B][3] (apply)
+    // sampler: step i runs only when t_dev[i] <= t_start; i = step, or ctl[0] - 1 in the replayed step graph.  t_dev == nullptr: always
+    const float *t_dev;
+    uint32_t step;
+    const uint32_t *ctl;
+    float *out;                 // [B][8] energy, satisfied groups, dtau[3], domega[3] (or nullptr)
+    int prep_next;              // prepare the pose for the next evaluation (what k_prep_pose writes), as k_heads' prep_next
+    float4 *prep_pos, *prep_ca4, *prep_cb4;
+};
+hipError_t launch_restraint(const RestraintArgs &a, int B, hipStream_t s);
+
 }  // namespace dfm

@@ -572,4 +572,164 @@ hipError_t launch_clash_force(const float *rec_pos, int B, int R, int L, float *
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Interface distance restraints (include/dfmdock_amd.h: dfm_complex_set_restraints; the numpy form in dfmdock_amd/restraints.py is the
+// spec).  Group g: d_g = min over its pairs (i, j) of |x_j - y_i| (CA atoms; the first minimal pair in list order), v_g = max(0, d_g - u_g),
+// U = sum_g w_g v_g^2; the gradient 2 w_g v_g (x_j* - y_i*) / d_g acts on x_j* alone.  F = -sum grad, T = sum (x_j* - c) x (-grad) about the
+// ligand centroid c the sampler rotates about; dtau = clip(k_tr F, max_tr), domega = clip(k_rot T, max_rot); applied like the
+// Euler-Maruyama step (modify_coords + bookkeeping, inference_base.py:453-456).
+// One 256-thread workgroup per trajectory (the shape of k_prep_pose, so that this kernel can prepare the pose it produces for the next
+// evaluation with the same code and the same bits).  Phase 1: groups of at most RS_SMALL pairs are one lane each (serial loop: a
+// restraint set is mostly single pairs), larger groups one wave each (pairs strided over the lanes, lane-local then butterfly arg-min,
+// ties to the lower pair index); each group's (d^2, arg-min pair) goes to LDS.  Phase 2: lane t folds groups t, t + 256, ... in order,
+// then the block sums the lanes in a fixed order - a trajectory's bits do not depend on B or on its place in the batch.  d^2 and every
+// sum are float64 (a group near its bound cancels d - u); the pose update is float32 with k_heads' expressions.
+__global__ __launch_bounds__(256) void k_restraint(RestraintArgs p)
+{
+    __shared__ double s_d2[RS_MAX_GROUPS];
+    __shared__ int s_arg[RS_MAX_GROUPS];
+    __shared__ double dscr[4 * 10];
+    __shared__ float s_upd[16], s_center[3];
+    __shared__ int s_go;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, L = p.L, G = p.G;
+    float *lig = p.lig + (size_t)b * L * 9;
+    bool go = true;
+    if (p.t_dev) {      // sampler: only from t_start on (step i's time; the replayed step graph reads i from its control word)
+        const uint32_t idx = p.ctl ? p.ctl[0] - 1u : p.step;
+        go = p.t_dev[idx] <= p.t_start;
+    }
+    if (go) {
+        // centre the sampler rotates about: ligand CA centroid (all backbone atoms for the second family, as k_heads)
+        double c[3] = {0, 0, 0};
+        if (p.all_atoms) {
+            for (int q = tid; q < L * 3; q += blockDim.x) { c[0] += lig[q * 3]; c[1] += lig[q * 3 + 1]; c[2] += lig[q * 3 + 2]; }
+        } else {
+            for (int q = tid; q < L; q += blockDim.x) { c[0] += lig[q * 9 + 3]; c[1] += lig[q * 9 + 4]; c[2] += lig[q * 9 + 5]; }
+        }
+        // phase 1a: small groups, one lane each
+        for (int g = tid; g < G; g += blockDim.x) {
+            const int q0 = p.gstart[g], q1 = p.gstart[g + 1];
+            if (q1 - q0 > RS_SMALL) continue;
+            double best = 0; int arg = -1;
+            for (int q = q0; q < q1; ++q) {
+                const int i = p.pairs[q * 2], j = p.pairs[q * 2 + 1];
+                const double dx = (double)lig[j * 9 + 3] - (double)p.rec_pos[i * 9 + 3];
+                const double dy = (double)lig[j * 9 + 4] - (double)p.rec_pos[i * 9 + 4];
+                const double dz = (double)lig[j * 9 + 5] - (double)p.rec_pos[i * 9 + 5];
+                const double d2 = dx * dx + dy * dy + dz * dz;
+                if (arg < 0 || d2 < best) { best = d2; arg = q; }
+            }
+            s_d2[g] = best; s_arg[g] = arg;
+        }
+        // phase 1b: large groups, one wave each
+        for (int k = wave; k < p.n_big; k += (int)(blockDim.x >> 6)) {
+            const int g = p.big[k], q0 = p.gstart[g], q1 = p.gstart[g + 1];
+            double best = 0; int arg = 0x7fffffff;
+            for (int q = q0 + lane; q < q1; q += 64) {
+                const int i = p.pairs[q * 2], j = p.pairs[q * 2 + 1];
+                const double dx = (double)lig[j * 9 + 3] - (double)p.rec_pos[i * 9 + 3];
+                const double dy = (double)lig[j * 9 + 4] - (double)p.rec_pos[i * 9 + 4];
+                const double dz = (double)lig[j * 9 + 5] - (double)p.rec_pos[i * 9 + 5];
+                const double d2 = dx * dx + dy * dy + dz * dz;
+                if (arg == 0x7fffffff || d2 < best) { best = d2; arg = q; }
+            }
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) {
+                const double ob = __shfl_xor(best, m, 64);
+                const int oa = __shfl_xor(arg, m, 64);
+                // lexicographic (d^2, pair index) minimum; a lane without pairs (arg = INT_MAX) loses to any lane with one
+                if (oa != 0x7fffffff && (arg == 0x7fffffff || ob < best || (ob == best && oa < arg))) { best = ob; arg = oa; }
+            }
+            if (lane == 0) { s_d2[g] = best; s_arg[g] = arg; }
+        }
+        double cs[3] = {c[0], c[1], c[2]};
+        {
+            double v3[3] = {c[0], c[1], c[2]};
+            // (block_sum over the centroid partials; its barriers also publish s_d2 / s_arg)
+            for (int k = 0; k < 3; ++k) v3[k] = wave_sum_d(v3[k]);
+            __syncthreads();
+            if (lane == 0) { dscr[wave * 3] = v3[0]; dscr[wave * 3 + 1] = v3[1]; dscr[wave * 3 + 2] = v3[2]; }
+            __syncthreads();
+            const int ncen = p.all_atoms ? L * 3 : L;
+            for (int k = 0; k < 3; ++k) cs[k] = (((dscr[k] + dscr[3 + k]) + dscr[6 + k]) + dscr[9 + k]) / ncen;
+        }
+        // phase 2: energy, satisfied count, force, torque
+        double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int g = tid; g < G; g += blockDim.x) {
+            const double d = sqrt(s_d2[g]), v = d - (double)p.upper[g];
+            if (v <= 0.0) { a[7] += 1.0; continue; }
+            const double w = p.weight[g];
+            a[0] += w * v * v;
+            if (w == 0.0 || d == 0.0) continue;
+            const int q = s_arg[g], i = p.pairs[q * 2], j = p.pairs[q * 2 + 1];
+            const double x0 = lig[j * 9 + 3], x1 = lig[j * 9 + 4], x2 = lig[j * 9 + 5];
+            const double s = -2.0 * w * v / d;      // force on x_j* = s (x_j* - y_i*)
+            const double f0 = s * (x0 - (double)p.rec_pos[i * 9 + 3]), f1 = s * (x1 - (double)p.rec_pos[i * 9 + 4]),
+                         f2 = s * (x2 - (double)p.rec_pos[i * 9 + 5]);
+            const double r0 = x0 - cs[0], r1 = x1 - cs[1], r2 = x2 - cs[2];
+            a[1] += f0; a[2] += f1; a[3] += f2;
+            a[4] += r1 * f2 - r2 * f1; a[5] += r2 * f0 - r0 * f2; a[6] += r0 * f1 - r1 * f0;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a[k] = wave_sum_d(a[k]);
+        __syncthreads();
+        if (lane == 0) for (int k = 0; k < 8; ++k) dscr[wave * 8 + k] = a[k];
+        __syncthreads();
+        if (tid == 0) {
+            for (int k = 0; k < 8; ++k) a[k] = ((dscr[k] + dscr[8 + k]) + dscr[16 + k]) + dscr[24 + k];
+            double st[6] = {p.k_tr * a[1], p.k_tr * a[2], p.k_tr * a[3], p.k_rot * a[4], p.k_rot * a[5], p.k_rot * a[6]};
+            for (int h = 0; h < 2; ++h) {      // clip(v, m) = v min(1, m / |v|)
+                const double n = sqrt(st[h * 3] * st[h * 3] + st[h * 3 + 1] * st[h * 3 + 1] + st[h * 3 + 2] * st[h * 3 + 2]);
+                const double m = h ? p.max_rot : p.max_tr;
+                if (n > m) for (int k = 0; k < 3; ++k) st[h * 3 + k] *= m / n;
+            }
+            float tr[3], rot[3];
+            for (int k = 0; k < 3; ++k) { tr[k] = (float)st[k]; rot[k] = (float)st[3 + k]; }
+            if (p.out) {
+                float *o = p.out + (size_t)b * 8;
+                o[0] = (float)a[0]; o[1] = (float)a[7];
+                for (int k = 0; k < 3; ++k) { o[2 + k] = tr[k]; o[5 + k] = rot[k]; }
+            }
+            const bool moves = p.apply && (tr[0] != 0.f || tr[1] != 0.f || tr[2] != 0.f || rot[0] != 0.f || rot[1] != 0.f || rot[2] != 0.f);
+            s_go = moves;
+            if (moves) {
+                float Rm[9];
+                aa_to_mat(rot, Rm);
+                for (int k = 0; k < 9; ++k) s_upd[k] = Rm[k];
+                for (int k = 0; k < 3; ++k) { s_upd[9 + k] = tr[k]; s_upd[12 + k] = (float)cs[k]; }
+                float ru[3] = {p.rot_update[b * 3], p.rot_update[b * 3 + 1], p.rot_update[b * 3 + 2]}, rn[3];
+                rot_compose(ru, rot, rn);
+                for (int k = 0; k < 3; ++k) {
+                    p.tr_update[b * 3 + k] += tr[k];
+                    p.rot_update[b * 3 + k] = rn[k];
+                }
+            }
+        }
+        __syncthreads();
+        if (s_go) {      // modify_coords (inference_base.py:342-352) with k_heads' expressions
+            for (int at = tid; at < L * 3; at += blockDim.x) {
+                const float v0 = lig[at * 3] - s_upd[12], v1 = lig[at * 3 + 1] - s_upd[13], v2 = lig[at * 3 + 2] - s_upd[14];
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    float s = 0;
+                    s += v0 * s_upd[r * 3]; s += v1 * s_upd[r * 3 + 1]; s += v2 * s_upd[r * 3 + 2];
+                    lig[at * 3 + r] = (s + s_upd[12 + r]) + s_upd[9 + r];
+                }
+            }
+        }
+    }
+    if (p.prep_next) {      // the last kernel that moves the pose prepares it for the next evaluation (k_heads does not, then)
+        __syncthreads();
+        const int N = p.R + L;
+        prep_pose_block(p.rec_pos, lig, p.R, L, p.all_atoms, p.prep_pos + (size_t)b * N, p.prep_ca4 + (size_t)b * N, p.prep_cb4 + (size_t)b * N,
+                        dscr, s_center);
+    }
+}
+
+hipError_t launch_restraint(const RestraintArgs &a, int B, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_restraint, dim3(B), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace dfm

@@ -26,6 +26,7 @@ from . import engine, pdbio
 from .metrics import NativeContext, compute_metrics
 
 CSV_FIELDS = ["id", "index", "c_rmsd", "i_rmsd", "l_rmsd", "fnat", "DockQ", "energy", "num_clashes"]
+RESTRAINT_FIELDS = ["restraint_energy", "restraints_satisfied"]      # appended to the rows only when restraints are given
 
 
 def rotate_complex(rec_pos, lig_pos, Rm):
@@ -71,10 +72,11 @@ def checked_precision(gx: engine.Complex, precision: str, name: str, selfcheck=T
 
 class _Prepared:
     """One complex ready to sample: its handle, the pose it was created on and everything derived from that pose alone."""
-    __slots__ = ("ci", "c", "gx", "N", "rec_pos", "lig_pos", "native", "precision", "check", "ms")
+    __slots__ = ("ci", "c", "gx", "N", "rec_pos", "lig_pos", "native", "precision", "check", "ms", "restraints")
 
 
-def _prepare(model, c, ci, rot_seed, global_rotation, precision, selfcheck, on_selfcheck_fail, seed, log=None) -> _Prepared:
+def _prepare(model, c, ci, rot_seed, global_rotation, precision, selfcheck, on_selfcheck_fail, seed, log=None,
+             restraints=None) -> _Prepared:
     """Stage 1 of run_set (host + a little device work on the new handle's own stream): loader semantics, handle, self-check."""
     import time
     t0 = time.perf_counter()
@@ -86,6 +88,9 @@ def _prepare(model, c, ci, rot_seed, global_rotation, precision, selfcheck, on_s
     p.rec_pos, p.lig_pos = rec_pos, lig_pos
     p.gx = engine.Complex(model, c["rec_x"], c["lig_x"], rec_pos, lig_pos)
     p.N = p.gx.N
+    p.restraints = restraints      # residue indices: unchanged by the global rotation
+    if restraints is not None:
+        p.gx.set_restraints(restraints)
     p.native = NativeContext((rec_pos, lig_pos))
     p.precision, p.check = checked_precision(p.gx, precision, str(c.get("id", ci)), selfcheck, on_selfcheck_fail, log=log, seed=seed)
     p.ms = {"prepare": (time.perf_counter() - t0) * 1e3}
@@ -103,7 +108,10 @@ def _sample(p: _Prepared, t_lo, t_hi, num_steps, seed, max_batch, trace, sampler
         while done < t_hi:
             b = min(max_batch, t_hi - done)
             r = p.gx.sample(B=b, num_steps=num_steps, seed=seed * 100003 + p.ci * 1009 + done, trace=trace,
-                            **engine.precision_kwargs(p.precision), **sampler_kw)
+                            restraints=p.restraints is not None, **engine.precision_kwargs(p.precision), **sampler_kw)
+            if p.restraints is not None:      # the restraint terms of the final poses, on the sampler's own kernel
+                ev = p.gx.restraint_eval(r["lig_pos"])
+                r["restraint_energy"], r["restraints_satisfied"] = ev["energy"], ev["n_satisfied"]
             batches.append((done, b, r))
             done += b
     finally:
@@ -123,6 +131,8 @@ def _post(p: _Prepared, batches, traj_dir):
             m = compute_metrics((p.rec_pos, r["lig_pos"][k]), (p.rec_pos, p.lig_pos), p.native)
             rows.append({"id": c.get("id", str(p.ci)), "index": str(done + k), **m, "energy": float(r["energy"][k]),
                          "num_clashes": int(r["num_clashes"][k])})
+            if p.restraints is not None:
+                rows[-1].update(restraint_energy=float(r["restraint_energy"][k]), restraints_satisfied=int(r["restraints_satisfied"][k]))
             if traj_dir is not None and "rec_seq" in c:
                 os.makedirs(traj_dir, exist_ok=True)
                 frames = r["trace_pose"][k]
@@ -135,7 +145,7 @@ def _post(p: _Prepared, batches, traj_dir):
 
 def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0, precision="mfma16", global_rotation=True,
             out_csv=None, traj_dir=None, max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", checks_out=None,
-            overlap=True, samplers=2, timings_out=None, log=None, canary=True, canary_out=None, **sampler_kw):
+            overlap=True, samplers=2, timings_out=None, log=None, canary=True, canary_out=None, restraints_by_id=None, **sampler_kw):
     """Sample `num_samples` trajectories for every complex dict (id, rec_x, lig_x, rec_pos, lig_pos[, rec_seq, lig_seq]);
     returns the metric rows of this rank's share; rank 0 writes the gathered CSV when `out_csv` is given.  Every complex is
     self-checked first (checked_precision); `checks_out` (a list) collects {id, precision used, check dict}.
@@ -153,7 +163,12 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
     running at once (profiles/r05_concurrency.txt; tests/test_gpu_concurrency.py holds the shipped build to 0 deviations).  As a
     run-time tripwire on whatever box / ROCm this runs on, the cheapest complex that sampled with others in flight is sampled AGAIN
     after the pipeline has drained, alone, and compared bit for bit; on a mismatch the whole share is re-run by the serial driver and
-    those rows are returned (`canary_out`, a dict, receives {checked, id, ok, reran_serial})."""
+    those rows are returned (`canary_out`, a dict, receives {checked, id, ok, reran_serial}).
+
+    `restraints_by_id` ({complex id: [restraints.RestraintGroup]}): the listed complexes sample with their interface restraints
+    (DFM_F_RESTRAINTS; every rank holds the set, the canary re-sample uses it too) and every row gains `restraint_energy` and
+    `restraints_satisfied` of its final pose (complexes without an entry: 0 groups, both 0).  Without it the rows and the CSV keep
+    the reference schema."""
     rank, _, world = D.dist_env()
     complexes = list(complexes)
     split_trajectories = world > 1 and len(complexes) < 2 * world
@@ -170,8 +185,14 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
         share = []
     trace = traj_dir is not None
 
+    def restraints_of(ci):      # keyword arguments of _prepare: none without restraints
+        if restraints_by_id is None:
+            return {}
+        return {"restraints": list(restraints_by_id.get(complexes[ci].get("id", str(ci)), []))}
+
     def prep(ci):
-        return _prepare(model, complexes[ci], ci, rots[ci], global_rotation, precision, selfcheck, on_selfcheck_fail, seed, log)
+        return _prepare(model, complexes[ci], ci, rots[ci], global_rotation, precision, selfcheck, on_selfcheck_fail, seed, log,
+                        **restraints_of(ci))
 
     def samp(p):
         return _sample(p, t_lo, t_hi, num_steps, seed, max_batch, trace, sampler_kw)
@@ -228,7 +249,7 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
                 raise
         if canary_ci is not None and "batches" in canary_ref:
             again = _prepare(model, complexes[canary_ci], canary_ci, rots[canary_ci], global_rotation, canary_ref["precision"], False,
-                             on_selfcheck_fail, seed, log)
+                             on_selfcheck_fail, seed, log, **restraints_of(canary_ci))
             solo = samp(again)
             same = len(solo) == len(canary_ref["batches"]) and all(
                 all(np.array_equal(ra[k], rb[k]) for k in ("lig_pos", "energy", "num_clashes", "rot_update", "tr_update"))
@@ -262,7 +283,7 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
         if rank == 0:
             os.makedirs(os.path.dirname(os.path.abspath(out_csv)), exist_ok=True)
             with open(out_csv, "w", newline="") as f:
-                w = csv.DictWriter(f, fieldnames=CSV_FIELDS)
+                w = csv.DictWriter(f, fieldnames=CSV_FIELDS + (RESTRAINT_FIELDS if restraints_by_id is not None else []))
                 w.writeheader()
                 for row in sorted(all_rows, key=lambda x: (x["id"], int(x["index"]))):
                     w.writerow(row)
@@ -276,13 +297,24 @@ def _gather_rows(rows, world):
 
 
 def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_steps=40, seed=0, precision="mfma16",
-              out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", **sampler_kw):
+              out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", restraints=None,
+              restraint_rank="satisfied", restraint_params=None, **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
     pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
     the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
-    rot_noise_scale, ode)."""
+    rot_noise_scale, ode).
+
+    `restraints` ([restraints.RestraintGroup]): sample with the interface restraint step (DFM_F_RESTRAINTS, `restraint_params` or the
+    defaults) and keep, by `restraint_rank`, the minimum-energy trajectory among those satisfying the most groups ("satisfied") or the
+    reference's plain minimum-energy one ("energy"); the result gains `restraint_energy`, `restraints_satisfied` of the kept pose and
+    `trajectories` (per-trajectory energy, restraint_energy, restraints_satisfied)."""
+    if restraints is not None and restraint_rank not in ("satisfied", "energy"):
+        raise ValueError(f"restraint_rank must be 'satisfied' or 'energy', got {restraint_rank!r}")
     gx = engine.Complex(model, rec_x, lig_x, rec["bb_coords"], lig["bb_coords"])
     precision, chk = checked_precision(gx, precision, "pair", selfcheck, on_selfcheck_fail, seed=seed)
+    if restraints is not None:
+        return _dock_pair_restrained(gx, model, rec, lig, restraints, restraint_rank, restraint_params, num_samples, num_steps, seed,
+                                     precision, chk, out_pdb, max_batch, sampler_kw)
     best = None
     done = 0
     while done < num_samples:
@@ -300,3 +332,31 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         pdbio.write_complex_pdb(out_pdb, rec_atoms, lig["atoms"], lig_aa)
     return {"energy": best[0], "rot_update": best[1], "tr_update": best[2], "lig_aa_coords": lig_aa, "precision": precision,
             "selfcheck": chk}
+
+
+def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_samples, num_steps, seed, precision, chk, out_pdb, max_batch,
+                          sampler_kw):
+    from . import restraints as RS
+    gx.set_restraints(restraints, params)
+    cols = {k: [] for k in ("energy", "restraint_energy", "restraints_satisfied", "rot_update", "tr_update")}
+    done = 0
+    while done < num_samples:
+        b = min(max_batch, num_samples - done)
+        r = gx.sample(B=b, num_steps=num_steps, seed=seed + done, restraints=True, **engine.precision_kwargs(precision), **sampler_kw)
+        ev = gx.restraint_eval(r["lig_pos"])
+        for k, v in (("energy", r["energy"]), ("restraint_energy", ev["energy"]), ("restraints_satisfied", ev["n_satisfied"]),
+                     ("rot_update", r["rot_update"]), ("tr_update", r["tr_update"])):
+            cols[k].append(v)
+        done += b
+    gx.close()
+    cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
+    k = RS.rank_key(cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else int(np.argmin(cols["energy"]))
+    lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k],
+                                       center="all_atoms" if model.hp.family == 1 else "ca")
+    if out_pdb:
+        pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa)
+    return {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
+            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, "index": k, "restraints": len(restraints),
+            "restraint_rank": rank, "restraint_energy": float(cols["restraint_energy"][k]),
+            "restraints_satisfied": int(cols["restraints_satisfied"][k]),
+            "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}

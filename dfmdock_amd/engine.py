@@ -131,6 +131,7 @@ class Complex:
         if not self._h:
             L.check(-2, "dfm_complex_create")
         self.K = L.lib().dfm_complex_degree(self._h)
+        self.n_restraints = 0
         self.lig_pos0 = lig_pos.reshape(self.L, 3, 3).copy()
 
     def close(self):
@@ -158,6 +159,31 @@ class Complex:
     def set_homomer(self, flag: bool):
         """Value of the 67th ("sym") position channel (positional_embed_dim = 67 models only)."""
         L.check(L.lib().dfm_complex_set_homomer(self._h, int(bool(flag))), "dfm_complex_set_homomer")
+
+    def set_restraints(self, groups, params=None):
+        """Store interface restraints (restraints.RestraintGroup list; None or [] clears them) and the step's parameters
+        (restraints.RestraintParams, None: the defaults) - dfm_complex_set_restraints.  `sample(restraints=True)` applies them."""
+        from .restraints import pack
+        gs, pairs, up, w = pack(groups or [], self.R, self.L)
+        par = None if params is None else params.to_c()
+        rc = L.lib().dfm_complex_set_restraints(self._h, len(up), _p(gs, L.I32P), _p(pairs, L.I32P), _p(up), _p(w),
+                                                C.byref(par) if par is not None else None)
+        L.check(rc, "dfm_complex_set_restraints")
+        self.n_restraints = len(up)
+
+    def restraint_eval(self, lig_pos):
+        """The stored restraints at poses lig_pos [B,L,3,3] (or [L,3,3]) on the GPU, with the sampler's own kernel
+        (dfm_restraint_eval): {energy [B], n_satisfied [B], step [B,6] = dtau, domega}."""
+        lp = _f32(lig_pos)
+        if lp.ndim == 3:
+            lp = lp[None]
+        B = lp.shape[0]
+        if lp.shape[1:] != (self.L, 3, 3):
+            raise ValueError(f"lig_pos must be [B,{self.L},3,3]")
+        o = dict(energy=np.zeros(B, np.float32), n_satisfied=np.zeros(B, np.int32), step=np.zeros((B, 6), np.float32))
+        L.check(L.lib().dfm_restraint_eval(self._h, B, _p(lp), _p(o["energy"]), _p(o["n_satisfied"], L.I32P), _p(o["step"])),
+                "dfm_restraint_eval")
+        return o
 
     def score(self, lig_pos, t, edges=None, seed=0, mfma16=False, energy=True, debug=False, profile=False, f16=False,
               ires=False, return_edges=False, bf16_ops=False, dist=False, bf16=False, l0_table=False):
@@ -212,13 +238,14 @@ class Complex:
 
     def sample(self, B=1, num_steps=40, eps=1e-3, tr_noise_scale=0.5, rot_noise_scale=0.5, noise_annealing=False,
                use_clash_force=False, ode=False, seed=0, mfma16=False, inject=None, trace=False, profile=False, f16=False, bf16_ops=False,
-               bf16=False, l0_table=True, graph=False, step_energy=None):
+               bf16=False, l0_table=True, graph=False, step_energy=None, restraints=False):
         """B independent Euler-Maruyama trajectories (inference_base.py:390-468 batched).  l0_table=False: DFM_F_NO_L0_TABLE
         (layer 0 evaluated edge by edge even where the per-complex message table applies).  graph=True: DFM_F_GRAPH (one captured
         step replayed as a hipGraph instead of every launch enqueued by the host; bitwise the same results, no faster on MI355X).
         trace=True returns the pose after every step and the scores of every evaluation; by default it also asks for the energy
         head on every step (DFM_F_STEP_ENERGY - the step evaluations then run their last layer in full); step_energy=False keeps
-        the step evaluations exactly as an untraced call runs them (ligand-only last layer, no energy in trace_scores[:, :-1])."""
+        the step evaluations exactly as an untraced call runs them (ligand-only last layer, no energy in trace_scores[:, :-1]).
+        restraints=True: DFM_F_RESTRAINTS (the restraint step of set_restraints after every update; nothing without a stored set)."""
         mfma16 = mfma16 or bf16
         if step_energy is None:
             step_energy = bool(trace)
@@ -251,7 +278,7 @@ class Complex:
                 (L.DFM_F_CLASH_FORCE if use_clash_force else 0) | (L.DFM_F_ODE if ode else 0) | \
                 (L.DFM_F_PROFILE if profile else 0) | (L.DFM_F_STEP_ENERGY if step_energy else 0) | (L.DFM_F_F16 if f16 else 0) | \
                 (L.DFM_F_BF16_OPS if bf16_ops else 0) | (0 if l0_table else L.DFM_F_NO_L0_TABLE) | \
-                (L.DFM_F_GRAPH if graph else 0)
+                (L.DFM_F_GRAPH if graph else 0) | (L.DFM_F_RESTRAINTS if restraints else 0)
         rc = L.lib().dfm_sample(self._h, int(B), S, float(eps), float(tr_noise_scale), float(rot_noise_scale), flags,
                                 int(seed), C.byref(inj) if inj is not None else None, C.byref(out))
         L.check(rc, "dfm_sample")

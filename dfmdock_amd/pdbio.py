@@ -43,7 +43,7 @@ def read_pdb(path):
 
 def backbone_from_atoms(atoms):
     """get_info_from_pdb semantics: drop HETATM; a residue (keyed by res_id, as the reference does) is kept when
-    it has N, CA and C; seq via 3->1 (unknown -> X); bb_coords [n,3,3] float64 in file order."""
+    it has N, CA and C; seq via 3->1 (unknown -> X); bb_coords [n,3,3] float64 in file order; residues [n] their keys."""
     atoms = [a for a in atoms if not a["hetero"]]
     names_by_res = {}
     for a in atoms:
@@ -63,7 +63,8 @@ def backbone_from_atoms(atoms):
         raise ValueError("backbone atom counts do not match the residue count (duplicate residue ids?)")
     bb = np.stack([n, ca, c], axis=1)
     aa = np.array([a["coord"] for a in atoms], dtype=np.float64)
-    return {"atoms": atoms, "seq": "".join(seq), "aa_coords": aa, "bb_coords": bb}
+    # residues: the (chain, res_id, ins, res_name) key of every kept residue, in bb_coords order (restraint files name residues by it)
+    return {"atoms": atoms, "seq": "".join(seq), "aa_coords": aa, "bb_coords": bb, "residues": order}
 
 
 def axis_angle_to_matrix(aa):

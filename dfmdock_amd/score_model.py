@@ -248,17 +248,20 @@ class DFMDock(Score_Model):
 
 def Euler_Maruyama_sampler(model: Score_Model, batch, num_steps=40, device="cpu", batch_size=1, eps=1e-3,
                            use_clash_force=False, noise_annealing=False, tr_noise_scale=0.5, rot_noise_scale=0.5,
-                           seed=None):
+                           seed=None, restraints=None):
     """One trajectory, reference signature and return tuple (inference_base.py:390-468):
     (rec_pos, lig_pos [L,3,3], rot_update [1,3], tr_update [1,3], output dict).  The whole 40-step loop runs
-    inside one dfm_sample call on the GPU."""
+    inside one dfm_sample call on the GPU.  restraints ([restraints.RestraintGroup], optional): interface restraints applied
+    after every step (DFM_F_RESTRAINTS); None samples as the reference does."""
     import torch
     if batch_size != 1:
         raise ValueError("batch_size must be 1 (as in the reference); use sample_trajectories for batches")
     cx = model.complex_for(batch)
     model._calls += 1
+    if restraints is not None:
+        cx.set_restraints(restraints)
     r = cx.sample(B=1, num_steps=num_steps, eps=eps, tr_noise_scale=tr_noise_scale, rot_noise_scale=rot_noise_scale,
-                  noise_annealing=noise_annealing, use_clash_force=use_clash_force,
+                  noise_annealing=noise_annealing, use_clash_force=use_clash_force, restraints=restraints is not None,
                   seed=(model.seed + model._calls) if seed is None else seed, **engine.precision_kwargs(model.precision))
     output = {"energy": torch.tensor(float(r["energy"][0])), "num_clashes": torch.tensor(int(r["num_clashes"][0])),
               "tr_score": torch.from_numpy(r["final_scores"][:, 0:3].copy()),

@@ -128,6 +128,9 @@ enum {
                                         complex alone (R^2 + L^2 <= 8 M pairs), never on B: a batch whose per-edge buffers (532 B per edge)
                                         do not fit fails with DFM_E_OOM instead of changing the arithmetic.                       */
     DFM_F_NO_L0_TABLE = 1u << 12,    /* dfm_sample: evaluate layer 0 directly                                            */
+    DFM_F_RESTRAINTS = 1u << 14,     /* dfm_sample: apply the interface restraint step (dfm_complex_set_restraints) after every step's
+                                        Euler-Maruyama update with t_i <= t_start, before the clash force.  With no set stored the flag
+                                        does nothing: the results are bitwise those of the unflagged call                   */
     DFM_F_GRAPH = 1u << 13           /* dfm_sample: capture ONE step (score evaluation + heads + update) as a hipGraph and replay it
                                         num_steps times instead of enqueueing every launch (ignored when anything is injected,
                                         traced or profiled).  Same kernels and arguments - the per-step / per-call scalars are
@@ -137,6 +140,15 @@ enum {
                                         measures 0.2 - 1.9 % SLOWER at B = 1 ... 120 (profiles/r04_graph_ab.txt); it is there
                                         for hosts that cannot keep a stream fed (DFM_GRAPH=1 in the environment: default on) */
 };
+
+/* Parameters of the restraint step (dfm_complex_set_restraints).  Defaults (p_or_null = NULL): DESIGN.md "Interface restraints". */
+typedef struct {
+    float k_tr;       /* A per unit of force (U in A^2, F in A):           dtau   = clip(k_tr F, max_tr)      default 0.25   */
+    float k_rot;      /* rad per unit of torque (A^2):                     domega = clip(k_rot T, max_rot)    default 3e-3   */
+    float max_tr;     /* A, largest translation of one restraint step                                         default 10.0   */
+    float max_rot;    /* rad, largest rotation of one restraint step                                          default 0.3    */
+    float t_start;    /* the step runs on step i when t_i <= t_start (1.0: every step)                         default 1.0    */
+} dfm_restraint_params;
 
 /* Output of dfm_score.  Required: tr_score, rot_score.  Any other pointer may be NULL. */
 typedef struct {
@@ -274,6 +286,23 @@ int dfm_complex_set_pose(dfm_complex *cx, const float *rec_pos_or_null, const fl
  * [relpos one-hot 66 | flag], the same constant on every residue pair.  A checkpoint trained with another layout of that
  * channel needs this entry point revisited. */
 int dfm_complex_set_homomer(dfm_complex *cx, int flag);
+/* Interface distance restraints of the complex: n_groups groups, group g = pairs[group_start[g] .. group_start[g+1]) of (receptor residue
+ * i in [0, R), ligand residue j in [0, L)), an upper bound upper[g] > 0 (A) and a weight weight[g] >= 0.  With receptor CA y_i as the
+ * sampler sees it (the stored rec_pos, as the clash force) and ligand CA x_j of a trajectory: d_g = min over the group of |x_j - y_i|
+ * (the first minimal pair in list order: a group of many pairs is an ambiguous restraint), v_g = max(0, d_g - u_g),
+ * U = sum_g w_g v_g^2.  The restraint step of DFM_F_RESTRAINTS moves the ligand rigidly down U: F = -dU/dx summed over the arg-min
+ * residues, T = sum (x_j* - c) x F_g about the centroid c the sampler rotates about (ligand CA; all backbone atoms for family 1),
+ * dtau = clip(k_tr F, max_tr), domega = clip(k_rot T, max_rot) with clip(v, m) = v min(1, m / |v|), applied as the Euler-Maruyama step
+ * is (modify_coords and the rot_update / tr_update bookkeeping, src/inference_base.py:453-456), in the clash force's slot right before
+ * it (:458-461), so dfm_traj_out's rot_update / tr_update still describe the final pose.  A step with dtau = domega = 0 leaves every bit
+ * of the pose alone.  Uploaded on the handle's stream; n_groups = 0 clears the set.  Limits: 1 <= n_groups <= 4096, at most 2^20 pairs
+ * in all, no empty group; bad input returns DFM_E_INVALID and keeps the stored set.  A captured step graph (DFM_F_GRAPH) is invalidated:
+ * the next call captures again.  p_or_null = NULL: the defaults (dfm_restraint_params).  No reference call has a counterpart. */
+int dfm_complex_set_restraints(dfm_complex *cx, int n_groups, const int32_t *group_start /*[G+1]*/, const int32_t *pairs /*[P,2]*/,
+                               const float *upper /*[G]*/, const float *weight /*[G]*/, const dfm_restraint_params *p_or_null);
+/* The restraint terms at B poses lig_pos [B,L,9]: energy U [B], the number of groups with v_g = 0 [B] and (step_or_null) the step the
+ * sampler would take there [B,6] = dtau, domega.  Runs the sampler's kernel (k_restraint) in its evaluation mode.  No set stored: zeros. */
+int dfm_restraint_eval(dfm_complex *cx, int B, const float *lig_pos, float *energy, int32_t *n_satisfied, float *step_or_null);
 /* edges per node for this complex: min(N,20) + min(40, N-20) */
 int dfm_complex_degree(const dfm_complex *cx);
 /* Device blocks released by destroyed handles are parked per device for the next handle (a set driver creates and destroys a
