@@ -32,12 +32,15 @@ DFM_F_NO_L0_TABLE = 1 << 12    # dfm_sample: layer 0 evaluated directly
 DFM_F_GRAPH = 1 << 13          # dfm_sample: replay one captured step as a hipGraph (opt-in)
 DFM_F_RESTRAINTS = 1 << 14     # dfm_sample: the interface restraint step (dfm_complex_set_restraints)
 
+DFM_CLUSTER_ENERGY = 0         # dfm_pose_cluster rules
+DFM_CLUSTER_SIZE = 1
+
 EXPORTS = [
     "dfm_last_error", "dfm_config_string", "dfm_device_count", "dfm_set_device", "dfm_default_hparams", "dfm_param_count",
     "dfm_model_create", "dfm_model_destroy", "dfm_complex_create", "dfm_complex_destroy", "dfm_complex_degree",
     "dfm_complex_set_pose", "dfm_complex_set_homomer",
     "dfm_score", "dfm_sample", "dfm_get_profile", "dfm_diffusion_coef", "dfm_complex_selfcheck", "dfm_trim_cache",
-    "dfm_complex_set_restraints", "dfm_restraint_eval",
+    "dfm_complex_set_restraints", "dfm_restraint_eval", "dfm_pose_rmsd", "dfm_pose_cluster", "dfm_pose_last_timing",
 ]
 
 
@@ -127,6 +130,10 @@ def lib():
     L.dfm_complex_selfcheck.argtypes = [C.c_void_p, C.c_int, F32P, C.c_uint64, C.c_uint32, C.POINTER(SelfcheckC)]
     L.dfm_complex_set_restraints.argtypes = [C.c_void_p, C.c_int, I32P, I32P, F32P, F32P, C.POINTER(RestraintParamsC)]
     L.dfm_restraint_eval.argtypes = [C.c_void_p, C.c_int, F32P, F32P, I32P, F32P]
+    L.dfm_pose_rmsd.argtypes = [C.c_void_p, C.c_int, C.c_int, F32P, I32P, C.c_int, F32P]
+    L.dfm_pose_cluster.argtypes = [C.c_void_p, C.c_int, C.c_int, F32P, I32P, C.c_int, F32P, C.c_float, C.c_int, C.c_int, I32P, I32P, I32P,
+                                   I32P]
+    L.dfm_pose_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_trim_cache.argtypes = [C.c_int]
     L.dfm_trim_cache.restype = C.c_longlong
     L.dfm_diffusion_coef.argtypes = [C.POINTER(HParamsC), C.c_int, C.c_double, C.POINTER(C.c_double),

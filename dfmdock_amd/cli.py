@@ -5,6 +5,8 @@
     python -m dfmdock_amd selfcheck REC.pdb LIG.pdb --ckpt model_0.ckpt --features F.npz
     python -m dfmdock_amd dock ... --restraints FILE [--restraint-rank satisfied|energy]
     python -m dfmdock_amd sweep ... --native-restraints K [--restraint-cutoff 8.0]
+    python -m dfmdock_amd dock ... --top-k K [--cluster-radius 4.0] [--cluster-rule energy|size]
+    python -m dfmdock_amd sweep ... --cluster-radius R [--top-k 10] [--cluster-rule energy|size]
 
   dock       <- src/inference_single.py:1-12 -> inference() (src/inference_base.py:601-670): num_samples (120) trajectories of
                 num_steps (40), the minimum-energy one applied to the all-atom ligand, `output.pdb` written, {"energy": E} printed.
@@ -19,6 +21,10 @@
              format there and in INTEGRATION.md).  `dock --restraints` keeps the minimum-energy trajectory among those satisfying the
              most groups (`--restraint-rank energy`: the plain minimum-energy rule); `sweep --native-restraints K` restrains every
              complex with K seeded native CA-CA contacts (< --restraint-cutoff A), the usual evaluation of guided docking.
+  clustering no reference counterpart: trajectories grouped by ligand RMSD on the GPU (dfmdock_amd/cluster.py, dfm_pose_cluster).
+             `dock --top-k K` writes the centres of the first K clusters as <out stem>_1.pdb ... <out stem>_K.pdb (model 1 of rule
+             energy is output.pdb) and lists them under `models`; `sweep --cluster-radius R` adds `cluster` / `is_center` to the CSV and
+             a top{K} success rate (any of the first K cluster centres reaches the DockQ threshold).
   selfcheck  no reference counterpart: dfm_complex_selfcheck on the pair (what `dock` and `sweep` run once per complex anyway).
 
 --ckpt takes the Lightning checkpoint the reference loads (src/inference_base.py:611-616; read without Lightning / omegaconf by
@@ -64,6 +70,11 @@ def build_parser():
     d.add_argument("--restraint-rank", default="satisfied", choices=["satisfied", "energy"],
                    help="with --restraints: keep the minimum energy among the trajectories satisfying the most groups (default) "
                         "or the plain minimum energy")
+    d.add_argument("--top-k", type=int, default=None, metavar="K",
+                   help="cluster the trajectories and write the first K cluster centres as <out stem>_1.pdb ... _K.pdb")
+    d.add_argument("--cluster-radius", type=float, default=4.0, help="with --top-k: ligand RMSD radius of a cluster (A)")
+    d.add_argument("--cluster-rule", default="energy", choices=["energy", "size"],
+                   help="with --top-k: leader clustering in key order (default) or greedy by cluster size")
     _add_common(d)
     s = sub.add_parser("sweep", help="sample every complex of a DB5-style directory (inference_mlsb.py run_sampling)")
     s.add_argument("--db5", required=True, help="directory of <id>.pt files (+ optional test.txt with the ids to run)")
@@ -76,6 +87,10 @@ def build_parser():
     s.add_argument("--native-restraints", type=int, default=None, metavar="K",
                    help="restrain every complex with K seeded native CA-CA contacts (adds restraint columns to the CSV)")
     s.add_argument("--restraint-cutoff", type=float, default=8.0, help="contact cutoff and upper bound of --native-restraints (A)")
+    s.add_argument("--cluster-radius", type=float, default=None, metavar="R",
+                   help="cluster every complex's trajectories by ligand RMSD (adds cluster / is_center to the CSV and a top-K success rate)")
+    s.add_argument("--top-k", type=int, default=10, metavar="K", help="with --cluster-radius: clusters per complex (default 10)")
+    s.add_argument("--cluster-rule", default="energy", choices=["energy", "size"], help="with --cluster-radius: clustering rule")
     _add_common(s)
     c = sub.add_parser("selfcheck", help="fp32-vs-16-bit check + fp16 range telemetry of one pair")
     c.add_argument("pdb_1")
@@ -125,9 +140,10 @@ def load_pair(pdb_1, pdb_2, features, lm_embed_dim=1301):
     return rec, lig, xs[0], xs[1]
 
 
-def success_table(rows):
+def success_table(rows, top_k=None):
     """Per complex: DockQ of the minimum-energy trajectory (what inference() keeps) and the best DockQ among its trajectories;
-    success rates at the CAPRI thresholds."""
+    success rates at the CAPRI thresholds.  `top_k` (rows with cluster columns): also the best DockQ among the centres of the first
+    top_k clusters and the `top{K}` success rate."""
     by = {}
     for r in rows:
         by.setdefault(r["id"], []).append(r)
@@ -136,9 +152,16 @@ def success_table(rows):
         top = min(rs, key=lambda r: (r["energy"], int(r["index"])))
         per[cid] = {"n": len(rs), "top1_DockQ": float(top["DockQ"]), "top1_energy": float(top["energy"]),
                     "best_DockQ": float(max(r["DockQ"] for r in rs)), "mean_DockQ": float(np.mean([r["DockQ"] for r in rs]))}
+        if top_k is not None:
+            cen = [float(r["DockQ"]) for r in rs if int(r["is_center"]) and 0 <= int(r["cluster"]) < top_k]
+            per[cid][f"top{top_k}_DockQ"] = max(cen) if cen else float("nan")
+            per[cid]["clusters"] = len(cen)
     n = max(len(per), 1)
     table = {name: {"threshold": thr, "top1": sum(p["top1_DockQ"] >= thr for p in per.values()) / n,
                     "best_of_n": sum(p["best_DockQ"] >= thr for p in per.values()) / n} for name, thr in DOCKQ_THRESHOLDS}
+    if top_k is not None:
+        for name, thr in DOCKQ_THRESHOLDS:
+            table[name][f"top{top_k}"] = sum(p[f"top{top_k}_DockQ"] >= thr for p in per.values()) / n
     return per, table
 
 
@@ -155,13 +178,28 @@ def restraint_summary(rows, restraints_by_id):
     return out
 
 
-def format_table(per, table):
+def format_table(per, table, top_k=None):
+    if top_k is not None:
+        return _format_table_clustered(per, table, top_k)
     lines = [f"{'id':8s} {'n':>4s} {'top1 DockQ':>11s} {'best DockQ':>11s} {'top1 energy':>12s}"]
     for cid, p in per.items():
         lines.append(f"{cid:8s} {p['n']:4d} {p['top1_DockQ']:11.4f} {p['best_DockQ']:11.4f} {p['top1_energy']:12.4f}")
     lines.append(f"success rate over {len(per)} complexes (DockQ of the minimum-energy trajectory | best of the trajectories):")
     for name, t in table.items():
         lines.append(f"  {name:10s} DockQ >= {t['threshold']:.2f}: {100 * t['top1']:5.1f} % | {100 * t['best_of_n']:5.1f} %")
+    return "\n".join(lines)
+
+
+def _format_table_clustered(per, table, top_k):
+    tk = f"top{top_k}"
+    lines = [f"{'id':8s} {'n':>4s} {'top1 DockQ':>11s} {tk + ' DockQ':>11s} {'best DockQ':>11s} {'top1 energy':>12s}"]
+    for cid, p in per.items():
+        lines.append(f"{cid:8s} {p['n']:4d} {p['top1_DockQ']:11.4f} {p[tk + '_DockQ']:11.4f} {p['best_DockQ']:11.4f} {p['top1_energy']:12.4f}")
+    lines.append(f"success rate over {len(per)} complexes (DockQ of the minimum-energy trajectory | best of the first {top_k} cluster "
+                 "centres | best of the trajectories):")
+    for name, t in table.items():
+        lines.append(f"  {name:10s} DockQ >= {t['threshold']:.2f}: {100 * t['top1']:5.1f} % | {100 * t[tk]:5.1f} % | "
+                     f"{100 * t['best_of_n']:5.1f} %")
     return "\n".join(lines)
 
 
@@ -173,6 +211,8 @@ def cmd_dock(args):
     if args.restraints:
         from .restraints import read_restraints
         kw = dict(restraints=read_restraints(args.restraints, rec, lig), restraint_rank=args.restraint_rank)
+    if args.top_k is not None:
+        kw.update(top_k=args.top_k, cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule)
     res = driver.dock_pair(model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                            precision=args.precision, out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
                            on_selfcheck_fail=args.on_selfcheck_fail, **kw)
@@ -182,6 +222,9 @@ def cmd_dock(args):
     if args.restraints:
         line.update(restraints=res["restraints"], restraints_satisfied=res["restraints_satisfied"],
                     restraint_energy=res["restraint_energy"], restraint_rank=res["restraint_rank"], index=res["index"])
+    if args.top_k is not None:
+        line.update(models=[dict(m, path=os.path.abspath(driver.model_path(args.out, m["rank"]))) for m in res["models"]],
+                    cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule)
     print(json.dumps(line), flush=True)
     if args.json:
         extra = {}
@@ -225,6 +268,10 @@ def cmd_sweep(args):
         from .restraints import native_contact_groups
         rkw["restraints_by_id"] = {c["id"]: native_contact_groups(c["rec_pos"], c["lig_pos"], args.native_restraints,
                                                                   cutoff=args.restraint_cutoff, seed=args.seed) for c in cxs}
+    top_k = None
+    if args.cluster_radius is not None:
+        top_k = args.top_k
+        rkw.update(cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule, top_k=top_k)
     rows, _ = driver.run_set(model, cxs, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                              precision=args.precision, global_rotation=not args.no_global_rotation, out_csv=args.out_csv,
                              traj_dir=args.traj_dir, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
@@ -232,10 +279,10 @@ def cmd_sweep(args):
     all_rows = driver._gather_rows(rows, world)
     all_checks = [c for part in D.gather_objects(checks) for c in part] if world > 1 else checks
     if rank == 0:
-        per, table = success_table(all_rows)
-        print(format_table(per, table), flush=True)
+        per, table = success_table(all_rows, top_k)
+        print(format_table(per, table, top_k), flush=True)
         extra = {}
-        if rkw:
+        if "restraints_by_id" in rkw:
             extra["restraints"] = restraint_summary(all_rows, rkw["restraints_by_id"])
             print(json.dumps({"restraints": extra["restraints"]}), flush=True)
         if args.summary:

@@ -1,6 +1,8 @@
 // api.hip - C ABI of the engine (include/dfmdock_amd.h): handles, weight packing, the per-evaluation
 // kernel schedule and the Euler-Maruyama loop.  Everything runs on one HIP stream per complex handle;
 // the host only enqueues (no sync inside the 40-step loop).
+#include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -905,6 +907,168 @@ extern "C" int dfm_restraint_eval(dfm_complex *cx, int B, const float *lig_pos, 
         n_satisfied[b] = (int32_t)h[(size_t)b * 8 + 1];
         if (step) std::memcpy(step + (size_t)b * 6, &h[(size_t)b * 8 + 2], 6 * sizeof(float));
     }
+    return DFM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Pose clustering (kernels_cluster.hip).  Bound to the model handle: the drivers close a complex right after sampling, and clustering
+// runs later, on the post-processing thread.  Every call owns a non-blocking stream and its temporaries (block cache), so calls from
+// several host threads, and next to that model's complex handles, do not share any state.
+static thread_local double g_cluster_ms[2] = {0.0, 0.0};      // k_pose_dist, the clustering kernels of this thread's last call
+
+static int check_pose_args(int B, int L, const float *lig_pos, const int32_t *residues, int n_res, std::vector<int32_t> *res_out)
+{
+    if (!lig_pos) return fail(DFM_E_INVALID, "lig_pos is NULL");
+    if (B < 1 || L < 1) return fail(DFM_E_INVALID, "need B >= 1 and L >= 1");
+    if (B > CL_MAX_POSES) return fail(DFM_E_INVALID, "at most " + std::to_string(CL_MAX_POSES) + " poses per call");
+    if ((int64_t)L * 9 > INT32_MAX / 2) return fail(DFM_E_INVALID, "L too large");
+    res_out->clear();
+    if (residues) {
+        if (n_res < 1 || n_res > L) return fail(DFM_E_INVALID, "need 1 <= n_res <= L");
+        std::vector<char> seen((size_t)L, 0);
+        for (int i = 0; i < n_res; ++i) {
+            const int r = residues[i];
+            if (r < 0 || r >= L) return fail(DFM_E_INVALID, "residue " + std::to_string(r) + " outside [0, " + std::to_string(L) + ")");
+            if (seen[(size_t)r]) return fail(DFM_E_INVALID, "residue " + std::to_string(r) + " listed twice");
+            seen[(size_t)r] = 1;
+        }
+        res_out->assign(residues, residues + n_res);
+    }
+    return DFM_OK;
+}
+
+// the call's stream and temporaries; the pool goes back to the block cache after the stream has drained
+struct PoseCall {
+    hipStream_t s = nullptr;
+    DevPool tmp;
+    hipEvent_t ev[4] = {};
+    ~PoseCall()
+    {
+        if (s) (void)hipStreamSynchronize(s);
+        tmp.release(true);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (s) (void)hipStreamDestroy(s);
+    }
+    hipError_t open()
+    {
+        hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        if (e != hipSuccess) { s = nullptr; return e; }
+        tmp.bind(s);
+        for (hipEvent_t &v : ev)
+            if ((e = hipEventCreate(&v)) != hipSuccess) { v = nullptr; return e; }
+        return hipSuccess;
+    }
+    // uploads lig_pos and the subset; radius > 0 with rmsd == nullptr: the bitmask
+    hipError_t dist(int B, int L, const float *lig_pos, const std::vector<int32_t> &res, float radius, float *rmsd, uint32_t **mask)
+    {
+        float *X = nullptr;
+        int32_t *r = nullptr;
+        hipError_t e = tmp.upload_async(&X, lig_pos, (size_t)B * L * 9, s);
+        if (e == hipSuccess && !res.empty()) e = tmp.upload_async(&r, res.data(), res.size(), s);
+        const int W = (B + 31) / 32;
+        if (e == hipSuccess && !rmsd) e = tmp.alloc(mask, (size_t)B * W);
+        if (e == hipSuccess) e = hipEventRecord(ev[0], s);
+        if (e == hipSuccess) e = launch_pose_dist(X, B, L * 9, r, res.empty() ? L : (int)res.size(), radius, rmsd, rmsd ? nullptr : *mask, s);
+        if (e == hipSuccess) e = hipEventRecord(ev[1], s);
+        return e;
+    }
+};
+
+extern "C" int dfm_pose_rmsd(dfm_model *m, int B, int L, const float *lig_pos, const int32_t *residues, int n_res, float *rmsd)
+{
+    if (!m || !rmsd) return fail(DFM_E_INVALID, "NULL argument");
+    std::vector<int32_t> res;
+    if (int rc = check_pose_args(B, L, lig_pos, residues, n_res, &res)) return rc;
+    DEVICE_SCOPE(m->device);
+    PoseCall c;
+    HIPCHK(c.open());
+    float *d = nullptr;
+    HIPCHK(c.tmp.alloc(&d, (size_t)B * B));
+    HIPCHK(c.dist(B, L, lig_pos, res, 1.0f, d, nullptr));
+    HIPCHK(hipMemcpyAsync(rmsd, d, (size_t)B * B * sizeof(float), hipMemcpyDeviceToHost, c.s));
+    HIPCHK(hipStreamSynchronize(c.s));
+    float ms = 0.f;
+    g_cluster_ms[0] = hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess ? ms : -1.0;
+    g_cluster_ms[1] = 0.0;
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_cluster(dfm_model *m, int B, int L, const float *lig_pos, const int32_t *residues, int n_res, const float *key,
+                                float radius, int rule, int max_clusters, int32_t *n_clusters, int32_t *center, int32_t *size,
+                                int32_t *cluster_of)
+{
+    if (!m || !n_clusters || !center || !size || !cluster_of) return fail(DFM_E_INVALID, "NULL argument");
+    std::vector<int32_t> res;
+    if (int rc = check_pose_args(B, L, lig_pos, residues, n_res, &res)) return rc;
+    if (!(radius > 0.f) || !std::isfinite(radius)) return fail(DFM_E_INVALID, "radius must be finite and > 0");
+    if (rule != DFM_CLUSTER_ENERGY && rule != DFM_CLUSTER_SIZE) return fail(DFM_E_INVALID, "rule must be 0 (energy) or 1 (size)");
+    if (max_clusters < 1) return fail(DFM_E_INVALID, "max_clusters must be >= 1");
+    const int maxc = max_clusters < B ? max_clusters : B;
+    // key order on the host: lower key first, ties to the lower index, NaN last (dfmdock_amd/cluster.py: rank_order)
+    std::vector<int32_t> order((size_t)B), pos((size_t)B);
+    for (int i = 0; i < B; ++i) order[(size_t)i] = i;
+    if (key) {
+        std::stable_sort(order.begin(), order.end(), [key](int32_t a, int32_t b) {
+            const bool na = std::isnan(key[a]), nb = std::isnan(key[b]);
+            if (na != nb) return nb;
+            return !na && key[a] < key[b];
+        });
+    }
+    for (int i = 0; i < B; ++i) pos[(size_t)order[(size_t)i]] = i;
+    DEVICE_SCOPE(m->device);
+    PoseCall c;
+    HIPCHK(c.open());
+    uint32_t *mask = nullptr;
+    int32_t *d_order = nullptr, *d_out = nullptr;
+    const size_t out_n = (size_t)B + 2 * (size_t)maxc + 4;      // cluster_of | center | size | state
+    HIPCHK(c.tmp.upload_async(&d_order, order.data(), order.size(), c.s));
+    HIPCHK(c.tmp.alloc(&d_out, out_n));
+    HIPCHK(c.dist(B, L, lig_pos, res, radius, nullptr, &mask));
+    int32_t *d_of = d_out, *d_center = d_out + B, *d_size = d_center + maxc, *d_state = d_size + maxc;
+    if (rule == DFM_CLUSTER_ENERGY) {
+        HIPCHK(launch_cluster_leader(mask, B, d_order, maxc, d_of, d_center, d_size, d_state, c.s));
+    } else {
+        int32_t *d_pos = nullptr, *counts = nullptr, *mlist = nullptr;
+        uint32_t *U = nullptr;
+        HIPCHK(c.tmp.upload_async(&d_pos, pos.data(), pos.size(), c.s));
+        HIPCHK(c.tmp.alloc(&counts, (size_t)B));
+        HIPCHK(c.tmp.alloc(&mlist, (size_t)B));
+        HIPCHK(c.tmp.alloc(&U, (size_t)(B + 31) / 32));
+        HIPCHK(launch_cluster_count(mask, B, counts, U, d_of, d_state, c.s));
+        // one pick + decrement per cluster; the steps after the last pose is assigned return at once.  Every 64 clusters the host
+        // looks at the done flag, so a run that ends early does not enqueue max_clusters steps.
+        int32_t st[3] = {0, 0, 0};
+        for (int k = 0; k < maxc; ++k) {
+            HIPCHK(launch_cluster_step(mask, B, counts, d_pos, d_order, U, d_of, d_center, d_size, mlist, d_state, c.s));
+            if ((k & 63) == 63 && k + 1 < maxc) {
+                HIPCHK(hipMemcpyAsync(st, d_state, sizeof(st), hipMemcpyDeviceToHost, c.s));
+                HIPCHK(hipStreamSynchronize(c.s));
+                if (st[1]) break;
+            }
+        }
+    }
+    HIPCHK(hipEventRecord(c.ev[2], c.s));
+    std::vector<int32_t> h(out_n);
+    HIPCHK(hipMemcpyAsync(h.data(), d_out, out_n * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+    HIPCHK(hipStreamSynchronize(c.s));
+    const int n = h[(size_t)B + 2 * maxc];
+    if (n < 0 || n > maxc) return fail(DFM_E_HIP, "clustering kernel returned " + std::to_string(n) + " clusters");
+    *n_clusters = n;
+    std::memcpy(cluster_of, h.data(), (size_t)B * sizeof(int32_t));
+    std::memcpy(center, h.data() + B, (size_t)n * sizeof(int32_t));
+    std::memcpy(size, h.data() + B + maxc, (size_t)n * sizeof(int32_t));
+    float ms = 0.f;
+    g_cluster_ms[0] = hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess ? ms : -1.0;
+    g_cluster_ms[1] = hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess ? ms : -1.0;
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_last_timing(double *dist_ms, double *cluster_ms)
+{
+    if (!dist_ms || !cluster_ms) return fail(DFM_E_INVALID, "NULL argument");
+    *dist_ms = g_cluster_ms[0];
+    *cluster_ms = g_cluster_ms[1];
     return DFM_OK;
 }
 

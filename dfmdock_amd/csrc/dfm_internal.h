@@ -357,4 +357,17 @@ struct RestraintArgs {
 };
 hipError_t launch_restraint(const RestraintArgs &a, int B, hipStream_t s);
 
+// pose clustering (kernels_cluster.hip; include/dfmdock_amd.h: dfm_pose_rmsd / dfm_pose_cluster).  X [B][L9] pose rows, res [n_res] the
+// residue subset or nullptr (n_res = L); rmsd [B][B] (evaluation) or, when rmsd is nullptr, mask [B][ceil(B/32)] (bit: rmsd <= radius)
+constexpr int CL_MAX_POSES = 65536;
+hipError_t launch_pose_dist(const float *X, int B, int L9, const int32_t *res, int n_res, float radius, float *rmsd, uint32_t *mask,
+                            hipStream_t s);
+// rule 0: leader clustering in key order (one launch)
+hipError_t launch_cluster_leader(const uint32_t *mask, int B, const int32_t *order, int max_clusters, int32_t *cluster_of, int32_t *center,
+                                 int32_t *size, int32_t *n_out, hipStream_t s);
+// rule 1: counts / state set-up, then one step per cluster (state = {clusters formed, done, members of the last cluster})
+hipError_t launch_cluster_count(const uint32_t *mask, int B, int32_t *counts, uint32_t *U, int32_t *cluster_of, int32_t *state, hipStream_t s);
+hipError_t launch_cluster_step(const uint32_t *mask, int B, int32_t *counts, const int32_t *pos, const int32_t *order, uint32_t *U,
+                               int32_t *cluster_of, int32_t *center, int32_t *size, int32_t *mlist, int32_t *state, hipStream_t s);
+
 }  // namespace dfm

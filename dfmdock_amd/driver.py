@@ -27,6 +27,7 @@ from .metrics import NativeContext, compute_metrics
 
 CSV_FIELDS = ["id", "index", "c_rmsd", "i_rmsd", "l_rmsd", "fnat", "DockQ", "energy", "num_clashes"]
 RESTRAINT_FIELDS = ["restraint_energy", "restraints_satisfied"]      # appended to the rows only when restraints are given
+CLUSTER_FIELDS = ["cluster", "is_center"]      # appended to the rows only when clustering is asked for
 
 
 def rotate_complex(rec_pos, lig_pos, Rm):
@@ -47,6 +48,23 @@ def random_rotation(rec_pos, lig_pos, rng):
                    [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
                    [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
     return rotate_complex(rec_pos, lig_pos, Rm)
+
+
+def input_pose(c, rot_seed, global_rotation):
+    """The (receptor, ligand) backbone a complex is sampled from: the loader's random rotation applied when `global_rotation`."""
+    rec_pos, lig_pos = np.asarray(c["rec_pos"], np.float32), np.asarray(c["lig_pos"], np.float32)
+    if global_rotation:
+        rec_pos, lig_pos = random_rotation(rec_pos, lig_pos, np.random.default_rng(rot_seed))
+    return rec_pos, lig_pos
+
+
+def cluster_trajectories(model: engine.Model, lig_pos0, rot_update, tr_update, key, radius, rule="energy", max_clusters=None):
+    """Cluster trajectories on the GPU (dfm_pose_cluster) by the ligand backbone rebuilt from their final (rot_update, tr_update) on
+    the input backbone lig_pos0 (cluster.rebuild_backbone): a function of those records alone, so every world size and sharding gives
+    the same clusters.  `key` [n]: lower = better.  Returns the dict of Model.pose_cluster."""
+    from .cluster import rebuild_backbone
+    poses = rebuild_backbone(lig_pos0, rot_update, tr_update, model.hp.family)
+    return model.pose_cluster(poses, radius, key=key, rule=rule, max_clusters=max_clusters)
 
 
 def checked_precision(gx: engine.Complex, precision: str, name: str, selfcheck=True, on_fail="fp32", log=None, seed=0):
@@ -82,9 +100,7 @@ def _prepare(model, c, ci, rot_seed, global_rotation, precision, selfcheck, on_s
     t0 = time.perf_counter()
     p = _Prepared()
     p.ci, p.c = ci, c
-    rec_pos, lig_pos = np.asarray(c["rec_pos"], np.float32), np.asarray(c["lig_pos"], np.float32)
-    if global_rotation:
-        rec_pos, lig_pos = random_rotation(rec_pos, lig_pos, np.random.default_rng(rot_seed))
+    rec_pos, lig_pos = input_pose(c, rot_seed, global_rotation)
     p.rec_pos, p.lig_pos = rec_pos, lig_pos
     p.gx = engine.Complex(model, c["rec_x"], c["lig_x"], rec_pos, lig_pos)
     p.N = p.gx.N
@@ -145,7 +161,8 @@ def _post(p: _Prepared, batches, traj_dir):
 
 def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0, precision="mfma16", global_rotation=True,
             out_csv=None, traj_dir=None, max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", checks_out=None,
-            overlap=True, samplers=2, timings_out=None, log=None, canary=True, canary_out=None, restraints_by_id=None, **sampler_kw):
+            overlap=True, samplers=2, timings_out=None, log=None, canary=True, canary_out=None, restraints_by_id=None,
+            cluster_radius=None, cluster_rule="energy", top_k=10, **sampler_kw):
     """Sample `num_samples` trajectories for every complex dict (id, rec_x, lig_x, rec_pos, lig_pos[, rec_seq, lig_seq]);
     returns the metric rows of this rank's share; rank 0 writes the gathered CSV when `out_csv` is given.  Every complex is
     self-checked first (checked_precision); `checks_out` (a list) collects {id, precision used, check dict}.
@@ -168,7 +185,14 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
     `restraints_by_id` ({complex id: [restraints.RestraintGroup]}): the listed complexes sample with their interface restraints
     (DFM_F_RESTRAINTS; every rank holds the set, the canary re-sample uses it too) and every row gains `restraint_energy` and
     `restraints_satisfied` of its final pose (complexes without an entry: 0 groups, both 0).  Without it the rows and the CSV keep
-    the reference schema."""
+    the reference schema.
+
+    `cluster_radius` (A): the trajectories of every complex are clustered by ligand RMSD (cluster_trajectories; key: energy, rule
+    `cluster_rule`, at most `top_k` clusters) and every row gains `cluster` (-1: in none of them) and `is_center`.  This runs where all
+    trajectories of a complex are present: on the owning rank when complexes are sharded, on rank 0 after the record gather when
+    trajectories are split (the assignment then reaches every rank's rows)."""
+    if cluster_radius is not None and cluster_rule not in ("energy", "size"):
+        raise ValueError(f"cluster_rule must be 'energy' or 'size', got {cluster_rule!r}")
     rank, _, world = D.dist_env()
     complexes = list(complexes)
     split_trajectories = world > 1 and len(complexes) < 2 * world
@@ -277,13 +301,34 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
         if timings_out is not None:
             timings_out.append({"id": p.c.get("id", str(p.ci)), "N": p.N, **p.ms})
     recs = np.concatenate(records, 0) if records else np.zeros((0, D.RECORD_WIDTH), np.float32)
-    ranked = D.rank_by_energy(D.gather_records(recs)) if world > 1 or len(recs) else {}
+    gathered = D.gather_records(recs) if world > 1 or len(recs) else recs
+    ranked = D.rank_by_energy(gathered) if world > 1 or len(recs) else {}
+    if cluster_radius is not None:
+        mine = list(range(len(complexes))) if split_trajectories else [p.ci for p, _, _ in done]
+        assign = {}
+        if not split_trajectories or rank == 0:
+            for ci in mine:
+                r = gathered[gathered[:, 0] == ci]
+                if not len(r):
+                    continue
+                r = r[np.argsort(r[:, 1], kind="stable")]
+                lig0 = input_pose(complexes[ci], rots[ci], global_rotation)[1]
+                cl = cluster_trajectories(model, lig0, r[:, 4:7], r[:, 7:10], r[:, 2], cluster_radius, cluster_rule, top_k)
+                centers = set(int(r[c, 1]) for c in cl["center"])
+                cid = complexes[ci].get("id", str(ci))
+                for t, k in zip(r[:, 1].astype(int), cl["cluster_of"]):
+                    assign[f"{cid}/{t}"] = (int(k), int(t in centers))
+        if split_trajectories and world > 1:
+            assign = D.gather_objects(assign)[0]
+        for row in rows:
+            row["cluster"], row["is_center"] = assign[f"{row['id']}/{row['index']}"]
     if out_csv is not None:
         all_rows = _gather_rows(rows, world)
         if rank == 0:
             os.makedirs(os.path.dirname(os.path.abspath(out_csv)), exist_ok=True)
             with open(out_csv, "w", newline="") as f:
-                w = csv.DictWriter(f, fieldnames=CSV_FIELDS + (RESTRAINT_FIELDS if restraints_by_id is not None else []))
+                w = csv.DictWriter(f, fieldnames=CSV_FIELDS + (RESTRAINT_FIELDS if restraints_by_id is not None else []) +
+                                   (CLUSTER_FIELDS if cluster_radius is not None else []))
                 w.writeheader()
                 for row in sorted(all_rows, key=lambda x: (x["id"], int(x["index"]))):
                     w.writerow(row)
@@ -298,7 +343,7 @@ def _gather_rows(rows, world):
 
 def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_steps=40, seed=0, precision="mfma16",
               out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", restraints=None,
-              restraint_rank="satisfied", restraint_params=None, **sampler_kw):
+              restraint_rank="satisfied", restraint_params=None, top_k=None, cluster_radius=4.0, cluster_rule="energy", **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
     pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
     the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
@@ -307,35 +352,77 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     `restraints` ([restraints.RestraintGroup]): sample with the interface restraint step (DFM_F_RESTRAINTS, `restraint_params` or the
     defaults) and keep, by `restraint_rank`, the minimum-energy trajectory among those satisfying the most groups ("satisfied") or the
     reference's plain minimum-energy one ("energy"); the result gains `restraint_energy`, `restraints_satisfied` of the kept pose and
-    `trajectories` (per-trajectory energy, restraint_energy, restraints_satisfied)."""
+    `trajectories` (per-trajectory energy, restraint_energy, restraints_satisfied).
+
+    `top_k`: also cluster the trajectories by ligand RMSD (cluster_trajectories: `cluster_radius` A, rule `cluster_rule`) with the key
+    that picks output.pdb - energy, or under restraint_rank "satisfied" the most satisfied groups and then energy - and return up to
+    top_k cluster centres as `models` [{rank, index, energy, cluster_size}], written as <out_pdb stem>_<rank>.pdb.  Under rule "energy"
+    model 1 is the output.pdb pose."""
     if restraints is not None and restraint_rank not in ("satisfied", "energy"):
         raise ValueError(f"restraint_rank must be 'satisfied' or 'energy', got {restraint_rank!r}")
+    if top_k is not None:
+        if int(top_k) < 1:
+            raise ValueError("top_k must be >= 1")
+        if cluster_rule not in ("energy", "size"):
+            raise ValueError(f"cluster_rule must be 'energy' or 'size', got {cluster_rule!r}")
+        if not (np.isfinite(cluster_radius) and cluster_radius > 0):
+            raise ValueError("cluster_radius must be finite and > 0")
+    clu = None if top_k is None else (int(top_k), float(cluster_radius), cluster_rule)
     gx = engine.Complex(model, rec_x, lig_x, rec["bb_coords"], lig["bb_coords"])
     precision, chk = checked_precision(gx, precision, "pair", selfcheck, on_selfcheck_fail, seed=seed)
     if restraints is not None:
         return _dock_pair_restrained(gx, model, rec, lig, restraints, restraint_rank, restraint_params, num_samples, num_steps, seed,
-                                     precision, chk, out_pdb, max_batch, sampler_kw)
+                                     precision, chk, out_pdb, max_batch, sampler_kw, clu)
     best = None
     done = 0
+    cols = {k: [] for k in ("energy", "rot_update", "tr_update")}
     while done < num_samples:
         b = min(max_batch, num_samples - done)
         r = gx.sample(B=b, num_steps=num_steps, seed=seed + done, **engine.precision_kwargs(precision), **sampler_kw)
         k = int(np.argmin(r["energy"]))
         if best is None or r["energy"][k] < best[0]:     # strict <: the first minimum wins, as in the reference
             best = (float(r["energy"][k]), r["rot_update"][k].copy(), r["tr_update"][k].copy())
+        if clu is not None:
+            for c in cols:
+                cols[c].append(r[c])
         done += b
+    lig0 = gx.lig_pos0
     gx.close()
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], best[1], best[2],
                                        center="all_atoms" if model.hp.family == 1 else "ca")
     if out_pdb:
         rec_atoms = [a for a in rec["atoms"]]
         pdbio.write_complex_pdb(out_pdb, rec_atoms, lig["atoms"], lig_aa)
-    return {"energy": best[0], "rot_update": best[1], "tr_update": best[2], "lig_aa_coords": lig_aa, "precision": precision,
-            "selfcheck": chk}
+    res = {"energy": best[0], "rot_update": best[1], "tr_update": best[2], "lig_aa_coords": lig_aa, "precision": precision,
+           "selfcheck": chk}
+    if clu is not None:
+        cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
+        res.update(_top_models(model, rec, lig, lig0, cols, cols["energy"], clu, out_pdb))
+    return res
+
+
+def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb):
+    """dock_pair's `models`: the centres of up to top_k clusters in cluster order, each written as <out_pdb stem>_<rank>.pdb."""
+    top_k, radius, rule = clu
+    cl = cluster_trajectories(model, lig0, cols["rot_update"], cols["tr_update"], key, radius, rule, top_k)
+    models = []
+    for k, (c, n) in enumerate(zip(cl["center"], cl["size"])):
+        c = int(c)
+        models.append({"rank": k + 1, "index": c, "energy": float(cols["energy"][c]), "cluster_size": int(n)})
+        if out_pdb:
+            aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c],
+                                           center="all_atoms" if model.hp.family == 1 else "ca")
+            pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa)
+    return {"models": models, "cluster_of": cl["cluster_of"]}
+
+
+def model_path(out_pdb, rank):
+    """<stem>_<rank>.pdb next to out_pdb."""
+    return os.path.splitext(out_pdb)[0] + f"_{rank}.pdb"
 
 
 def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_samples, num_steps, seed, precision, chk, out_pdb, max_batch,
-                          sampler_kw):
+                          sampler_kw, clu=None):
     from . import restraints as RS
     gx.set_restraints(restraints, params)
     cols = {k: [] for k in ("energy", "restraint_energy", "restraints_satisfied", "rot_update", "tr_update")}
@@ -348,6 +435,7 @@ def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_sam
                      ("rot_update", r["rot_update"]), ("tr_update", r["tr_update"])):
             cols[k].append(v)
         done += b
+    lig0 = gx.lig_pos0
     gx.close()
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
     k = RS.rank_key(cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else int(np.argmin(cols["energy"]))
@@ -355,8 +443,13 @@ def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_sam
                                        center="all_atoms" if model.hp.family == 1 else "ca")
     if out_pdb:
         pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa)
-    return {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
-            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, "index": k, "restraints": len(restraints),
-            "restraint_rank": rank, "restraint_energy": float(cols["restraint_energy"][k]),
-            "restraints_satisfied": int(cols["restraints_satisfied"][k]),
-            "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
+    res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
+           "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, "index": k, "restraints": len(restraints),
+           "restraint_rank": rank, "restraint_energy": float(cols["restraint_energy"][k]),
+           "restraints_satisfied": int(cols["restraints_satisfied"][k]),
+           "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
+    if clu is not None:
+        from .cluster import satisfied_key
+        key = satisfied_key(cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else cols["energy"]
+        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb))
+    return res

@@ -114,6 +114,54 @@ class Model:
             pass
 
 
+    # ------------------------------------------------------------------
+    def _poses(self, lig_pos, residues):
+        lp = _f32(lig_pos)
+        if lp.ndim == 4:
+            lp = lp.reshape(lp.shape[0], lp.shape[1], 9)
+        if lp.ndim != 3 or lp.shape[2] != 9:
+            raise ValueError(f"lig_pos must be [B,L,9] or [B,L,3,3], got {np.shape(lig_pos)}")
+        res = None if residues is None else np.ascontiguousarray(np.asarray(residues).reshape(-1), dtype=np.int32)
+        return lp, res, 0 if res is None else res.size
+
+    def pose_rmsd(self, lig_pos, residues=None):
+        """[B,B] float32 pairwise ligand RMSD without superposition over the backbone atoms of `residues` (None: all) on the GPU
+        (dfm_pose_rmsd; the float64 definition is cluster.pose_rmsd)."""
+        lp, res, n_res = self._poses(lig_pos, residues)
+        B, Lg = lp.shape[0], lp.shape[1]
+        out = np.empty((B, B), np.float32)
+        L.check(L.lib().dfm_pose_rmsd(self._h, B, Lg, _p(lp), _p(res, L.I32P), n_res, _p(out)), "dfm_pose_rmsd")
+        return out
+
+    def pose_cluster(self, lig_pos, radius, key=None, rule="energy", max_clusters=None, residues=None):
+        """Cluster B poses on the GPU (dfm_pose_cluster; the definition is cluster.cluster_poses): neighbours within `radius` A ligand
+        RMSD, `key` [B] lower = better (None: index order), rule "energy" (leader) or "size" (greedy), at most `max_clusters` (None: B).
+        Returns {n_clusters, center, size, cluster_of} as int32 arrays."""
+        from .cluster import RULES
+        if rule not in RULES:
+            raise ValueError(f"rule must be one of {RULES}, got {rule!r}")
+        lp, res, n_res = self._poses(lig_pos, residues)
+        B, Lg = lp.shape[0], lp.shape[1]
+        maxc = B if max_clusters is None else int(max_clusters)
+        k = None if key is None else _f32(key).reshape(-1)
+        if k is not None and k.size != B:
+            raise ValueError(f"key must have {B} entries")
+        n = C.c_int32(0)
+        cap = max(1, min(maxc, B))
+        center, size, cluster_of = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(B, np.int32)
+        rc = L.lib().dfm_pose_cluster(self._h, B, Lg, _p(lp), _p(res, L.I32P), n_res, _p(k), float(radius), RULES.index(rule), maxc,
+                                      C.byref(n), _p(center, L.I32P), _p(size, L.I32P), _p(cluster_of, L.I32P))
+        L.check(rc, "dfm_pose_cluster")
+        return {"n_clusters": int(n.value), "center": center[: n.value].copy(), "size": size[: n.value].copy(), "cluster_of": cluster_of}
+
+
+def pose_last_timing():
+    """(k_pose_dist ms, clustering kernels ms) of this thread's last pose_rmsd / pose_cluster call (dfm_pose_last_timing)."""
+    a, b = C.c_double(0), C.c_double(0)
+    L.check(L.lib().dfm_pose_last_timing(C.byref(a), C.byref(b)), "dfm_pose_last_timing")
+    return a.value, b.value
+
+
 class Complex:
     """One receptor/ligand pair resident on the GPU (dfm_complex)."""
 
