@@ -550,7 +550,6 @@ extern "C" dfm_model *dfm_model_create(const float *blob, size_t n_floats, const
         const double S = (double)SILU_S;
         std::vector<uint16_t> T2b((size_t)NTAB2 * H);
         double tmax[2] = {0, 0};      // range telemetry of dfm_complex_selfcheck
-#if DFM_TAB_MERGE
         for (int om = 0; om < 24; ++om)
             for (int th = 0; th < 24; ++th)
                 for (int ph = 0; ph < 12; ++ph) {
@@ -565,17 +564,6 @@ extern "C" dfm_model *dfm_model_create(const float *blob, size_t n_floats, const
                 for (int c = 0; c < H; ++c) { const double v = S * (a[c] + b[c]); tmax[1] = std::fmax(tmax[1], std::fabs(v)); row[c] = f2h((float)v); }
             }
         m->tab_max[l][0] = (float)tmax[0]; m->tab_max[l][1] = (float)tmax[1];
-#else
-        for (int c = 0; c < H; ++c) {
-            for (int om = 0; om < 24; ++om)
-                for (int th = 0; th < 24; ++th)
-                    T2b[(size_t)(om * 24 + th) * H + c] = f2h((float)(S * (Td[(size_t)(40 + om) * H + c] + Td[(size_t)(64 + th) * H + c])));
-            for (int ph = 0; ph < 12; ++ph)
-                for (int d = 0; d < 40; ++d)
-                    T2b[(size_t)(576 + ph * 40 + d) * H + c] = f2h((float)(S * (Td[(size_t)(88 + ph) * H + c] + Td[(size_t)d * H + c])));
-            for (int rp = 0; rp < 66; ++rp) T2b[(size_t)(1056 + rp) * H + c] = f2h((float)(S * Td[(size_t)(100 + rp) * H + c]));
-        }
-#endif
         {
             std::vector<float> wrs(H), babs(2 * H), wc2s(H);
             for (int c = 0; c < H; ++c) wrs[c] = SILU_S * w_r[c];
@@ -1271,9 +1259,8 @@ extern "C" const char *dfm_config_string(void)
         c += "three-term split-bf16";
         c += ", fp32 accumulate / geometry / GraphNorm statistics / heads / SDE step";
         c += "; layer 0 through the per-complex message table in dfm_sample (DFM_F_NO_L0_TABLE: direct), on request in dfm_score (DFM_F_L0_TABLE)";
-        c += "; build: TAB_MERGE=" + std::to_string((int)DFM_TAB_MERGE);
         std::string env;
-        for (const char *k : {"DFM_EDGE_SPLIT", "DFM_GEMM_NARROW_MAXWG", "DFM_GEMM_QUARTER_MAXWG", "DFM_L0_TABLE", "DFM_GRAPH", "DFM_EDGE_F32_SCALAR", "DFM_GEMM_F32_SCALAR", "DFM_PAIR_HEAD_VALU", "DFM_PAIR_HEAD_M32", "DFM_ALLOC_CACHE", "DFM_ALLOC_CACHE_FRAC", "DFM_ALLOC_POISON", "DFM_ALLOC_GUARD", "DFM_LIB"}) {
+        for (const char *k : {"DFM_EDGE_SPLIT", "DFM_GEMM_NARROW_MAXWG", "DFM_GEMM_QUARTER_MAXWG", "DFM_L0_TABLE", "DFM_GRAPH", "DFM_ALLOC_CACHE", "DFM_ALLOC_CACHE_FRAC", "DFM_ALLOC_POISON", "DFM_ALLOC_GUARD", "DFM_LIB"}) {
             const char *e = getenv(k);
             if (e) env += std::string(env.empty() ? "" : " ") + k + "=" + e;
         }
@@ -1490,14 +1477,11 @@ static int enqueue_forward(dfm_complex *cx, int B, const FwdOpts &o)
     if (pair_family) {
         // egnn_net.py:430-470: pair heads on cat[h_r, h_l, D].  Per head: one GEMM projects every node through the stacked
         // halves of Linear(513 -> 256) (reusing the A / Bm buffers), then the elementwise pair kernel.
-        static const bool pair_valu = [] { const char *e = getenv("DFM_PAIR_HEAD_VALU"); return e && atoi(e) != 0; }();      // A/B: r02-r03 kernel
         // 16-bit engines: k_pair_head_m (LayerNorm statistics from fp32 row moments + a dot product, 1-ulp hardware exp2 / rcp).
         // The fp32 engine - the baseline of dfm_complex_selfcheck and the fallback when a check fails - keeps the three-pass
-        // LayerNorm, expf and IEEE division of k_pair_head<EXACT>: z = P + Q + w_d * D with D up to hundreds of Angstroms, so
+        // LayerNorm, expf and IEEE division of k_pair_head: z = P + Q + w_d * D with D up to hundreds of Angstroms, so
         // E[z^2] - mean^2 loses digits to cancellation exactly when a trained checkpoint has a large mean / std ratio, which no
-        // synthetic draw shows.  DFM_PAIR_HEAD_M32=1 opts the fp32 engine into the matrix-pipe kernel (+10 %).
-        static const bool pair_m32 = [] { const char *e = getenv("DFM_PAIR_HEAD_M32"); return e && atoi(e) != 0; }();
-        const bool pair_m = !pair_valu && (o.bf16 || pair_m32);
+        // synthetic draw shows.
         auto run_head = [&](int q, int mode) -> int {
             const PairHeadDev &Ph = m->pair[q];
             GemmArgs g;
@@ -1508,9 +1492,9 @@ static int enqueue_forward(dfm_complex *cx, int B, const FwdOpts &o)
             PairArgs a;
             std::memset(&a, 0, sizeof(a));
             a.P = W.A; a.Q = W.Bm; a.ca4 = W.ca4; a.B = B; a.R = R; a.L = L; a.w_d = Ph.w_d; a.ln_w = Ph.ln_w; a.ln_b = Ph.ln_b;
-            a.w3 = Ph.w3; a.mode = mode; a.exact = o.bf16 ? 0 : 1; a.cut_off = m->hp.cut_off; a.fpart = W.fpart;
+            a.w3 = Ph.w3; a.mode = mode; a.cut_off = m->hp.cut_off; a.fpart = W.fpart;
             a.spart = mode == 1 ? W.en_part : W.cpart; a.clash_part = W.clash_part;
-            if (pair_m) {      // 16-bit engines: s(r, l) with the rank-4 part on the matrix pipe, then this head's reductions
+            if (o.bf16) {      // 16-bit engines: s(r, l) with the rank-4 part on the matrix pipe, then this head's reductions
                 a.S = W.pair_s; a.Rp = (R + 31) / 32 * 32;
                 HIPCHK(launch_pair_head_m(a, s));
                 HIPCHK(launch_pair_finish_s(a, 4 * ((R + 63) / 64), m->hp.agg_mean ? 1.0f / (float)R : 1.0f, W.fvec, W.conf, s));
@@ -1525,7 +1509,7 @@ static int enqueue_forward(dfm_complex *cx, int B, const FwdOpts &o)
             if ((rc = run_head(1, 1)) != DFM_OK) return rc;
             if ((rc = run_head(2, 2)) != DFM_OK) return rc;
         }
-        if (!pair_m)
+        if (!o.bf16)
             HIPCHK(launch_pair_finish(W.fpart, B, R, L, m->hp.agg_mean ? 1.0f / (float)R : 1.0f, W.fvec, W.cpart,
                                       o.want_energy ? W.conf : nullptr, s));
     } else if (o.want_energy) {

@@ -29,19 +29,11 @@ __host__ __device__ inline uint32_t pack_code(int d, int om, int th, int ph, int
 // channel handled by (k-step kk, lane-half h, element e) of the bf16 MFMA operands (natural order)
 __host__ __device__ inline int frag_channel(int kk, int h, int e) { return kk * 16 + h * 8 + e; }
 
-// merged edge-feature tables of the 16-bit MFMA kernel (stored as fp16): row gathers per edge and 32-channel chunk instead of 5.
-// DFM_TAB_MERGE 1 (two gathers; 4.9 MB per layer, but the angle bins are zeroed beyond 22 A and most sequence offsets saturate,
-// so the rows actually touched are few):
+// merged edge-feature tables of the 16-bit MFMA kernel (stored as fp16): two row gathers per edge and 32-channel chunk instead of 5
+// (4.9 MB per layer, but the angle bins are zeroed beyond 22 A and most sequence offsets saturate, so the rows actually touched are few):
 //   [0, 6912)     (omega*24 + theta)*12 + phi   = T[40+omega] + T[64+theta] + T[88+phi]
 //   [6912, 9552)  6912 + relpos*40 + d          = T[100+relpos] + T[d]
-// DFM_TAB_MERGE 0 (three gathers, 574 KiB per layer):
-//   [0, 576)      omega*24 + theta              = T[40+omega] + T[64+theta]
-//   [576, 1056)   576 + phi*40 + d              = T[88+phi]   + T[d]
-//   [1056, 1122)  1056 + relpos                 = T[100+relpos]
-#ifndef DFM_TAB_MERGE
-#define DFM_TAB_MERGE 1
-#endif
-constexpr int NTAB2 = DFM_TAB_MERGE ? 6912 + 2640 : 576 + 480 + 66;
+constexpr int NTAB2 = 6912 + 2640;
 
 struct LayerDev {
     float *Wab;       // [512][256]   rows 0..255 = edge_mlp.0.weight[:, 0:256] (h_i), 256..511 = [:, 256:512] (h_j)
@@ -252,7 +244,6 @@ struct PairArgs {
     int B, R, L;
     const float *w_d, *ln_w, *ln_b, *w3;
     int mode;                // 0 force (+ clashes), 1 energy, 2 confidence
-    int exact;               // fp32 engine: three-pass LayerNorm, expf
     float cut_off;
     float *fpart;            // [B][ceil(R/64)][L][3]
     float *spart;            // [B][ceil(R/64)*4][2]

@@ -249,11 +249,10 @@ __global__ __launch_bounds__(256) void k_gemm_f32v(GemmArgs a)
 hipError_t launch_gemm_f32(const GemmArgs &a, hipStream_t s)
 {
     const dim3 grid((a.M + BM - 1) / BM, (a.Nout + BN - 1) / BN);
-    static const bool scalar_env = [] { const char *e = getenv("DFM_GEMM_F32_SCALAR"); return e && atoi(e) != 0; }();      // A/B: the r01-r04 kernel
     const bool aligned = a.K % BK == 0 && a.lda % 4 == 0 && a.ldw % 4 == 0 && (a.pro != 1 || (a.K / 2) % 4 == 0) &&
                          ((uintptr_t)a.A0 % 16 == 0) && ((uintptr_t)a.W % 16 == 0) && (a.pro != 1 || (uintptr_t)a.A1 % 16 == 0);
-    if (aligned && !scalar_env) hipLaunchKernelGGL(k_gemm_f32v, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_gemm_f32, grid, dim3(256), 0, s, a);
+    if (aligned) hipLaunchKernelGGL(k_gemm_f32v, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_gemm_f32, grid, dim3(256), 0, s, a);      // unaligned operands
     return hipGetLastError();
 }
 

@@ -7,7 +7,8 @@
 // lookup table (one-hot -> Linear == row gather).  Every node has exactly K out-edges stored
 // contiguously, so scatter_add is a dense K-row reduction: no atomics anywhere.
 //
-//   k_edge_f32  : exact fp32 (VALU) - the parity-reference precision of the engine.
+//   k_edge_f32m : fp32 products and accumulation on v_mfma_f32_32x32x2_f32 - the parity-reference precision of the engine
+//                 (itself checked against the tests' CPU reference model).
 //   k_edge_msg / k_edge_coord : 256x256 contraction on v_mfma_f32_32x32x16_{bf16,f16}, fp32 accumulate; A-fragments are
 //                 built in registers straight from the gathers, the weight matrix lives in LDS for the
 //                 whole (persistent) workgroup.
@@ -20,13 +21,8 @@
 
 #include "dfm_device.h"
 #include "dfm_internal.h"
-#include "dfm_edge_knobs.h"
 
 namespace dfm {
-
-// =================================================================================================
-// fp32 kernel: one 256-thread workgroup per (trajectory, node); thread = channel.
-constexpr int KF = 60;   // accumulator rows held in registers (K <= 60 always: knn 20 + sample 40)
 
 struct EdgeKArgs {
     const float *A, *Bm;
@@ -58,7 +54,7 @@ struct EdgeKArgs {
     int no_agg;                  // message kernels: nobody reads agg after this launch (ligand-only last layer): no segment-sum store, no atomics, no memset
     int node0, nodes;            // message kernels: the tasks cover nodes node0 .. node0 + nodes - 1 of every trajectory (all of them, or - last
                                  // layer when nobody reads the node outputs - the ligand nodes only: EdgeArgs::lig_only)
-    uint32_t *range;             // k_edge_f32, dfm_complex_selfcheck only: [0] max |pre-activation of edge_mlp.0|, [1] of edge_mlp.2, as float bits
+    uint32_t *range;             // k_edge_f32m, dfm_complex_selfcheck only: [0] max |pre-activation of edge_mlp.0|, [1] of edge_mlp.2, as float bits
     // k_edge_msg<1, 1, 1> (row-list form, layer 0 only: A / Bm are the complex's own, pose-independent operands): the tasks are 32-row
     // tiles of a flat list of edges (i, j, code, radial bits); the gated messages go out row-major as fp16 [row][256]
     const uint4 *rows;
@@ -70,145 +66,6 @@ struct EdgeKArgs {
                                  // zero at launch (the last wave out of a workgroup zeroes its pair again) - the waves of a workgroup take the
                                  // workgroup's tasks in order from here instead of by a fixed stride ("dynamic tasks" in the kernel), or nullptr
 };
-
-__device__ inline void row_dot(const float *lds_rows /*[KF][256]*/, const float *__restrict__ Wt /*[256][256]*/,
-                               int c, float bias, float (&acc)[KF])
-{
-#pragma unroll
-    for (int s = 0; s < KF; ++s) acc[s] = bias;
-    for (int k = 0; k < H; k += 4) {
-        const float w0 = Wt[(size_t)(k + 0) * H + c], w1 = Wt[(size_t)(k + 1) * H + c],
-                    w2 = Wt[(size_t)(k + 2) * H + c], w3 = Wt[(size_t)(k + 3) * H + c];
-#pragma unroll
-        for (int s = 0; s < KF; ++s) {
-            const float4 a = *reinterpret_cast<const float4 *>(lds_rows + s * H + k);   // broadcast read
-            float t = acc[s];
-            t = fmaf(a.x, w0, t); t = fmaf(a.y, w1, t); t = fmaf(a.z, w2, t); t = fmaf(a.w, w3, t);
-            acc[s] = t;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_edge_f32(EdgeKArgs p)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float *rows = reinterpret_cast<float *>(smem);            // [KF][256]
-    float *s_rad = rows + KF * H;                             // [64]
-    float *s_gate = s_rad + 64;                               // [64]
-    int *s_j = reinterpret_cast<int *>(s_gate + 64);          // [64]
-    uint32_t *s_code = reinterpret_cast<uint32_t *>(s_j + 64);   // [64]
-
-    const int c = threadIdx.x, lane = c & 63, wave = c >> 6;
-    const long long node = blockIdx.x;
-    const int b = (int)(node / p.N), i = (int)(node % p.N), K = p.K;
-    if (i < p.node0) return;      // lig_only: receptor nodes are not needed (block-uniform)
-    const size_t ebase = (size_t)node * K;
-    if (c < 64) {
-        const bool v = c < K;
-        s_j[c] = v ? p.edges[ebase + c] : i;
-        s_code[c] = v ? p.codes[ebase + c] : 0u;
-        s_rad[c] = v ? p.radial[ebase + c] : 0.f;
-    }
-    __syncthreads();
-    const size_t ab = (size_t)b * p.ab_bstride;
-    const float Ai = p.A[ab + (size_t)i * H + c];
-    const float wr = p.w_r[c];
-    // edge_mlp.0 + SiLU  (egnn.py:95-101)
-    float pre_max = 0.f;      // range telemetry (p.range): largest |pre-activation| this thread saw
-    for (int s = 0; s < KF; ++s) {
-        float v = 0.f;
-        if (s < K) {
-            const uint32_t code = s_code[s];
-            const int j = s_j[s];
-            float pre = Ai + p.Bm[ab + (size_t)j * H + c];
-            pre += wr * s_rad[s];
-            pre += p.T[(size_t)(code & 63u) * H + c];
-            pre += p.T[(size_t)(40u + ((code >> 6) & 31u)) * H + c];
-            pre += p.T[(size_t)(64u + ((code >> 11) & 31u)) * H + c];
-            pre += p.T[(size_t)(88u + ((code >> 16) & 15u)) * H + c];
-            pre += p.T[(size_t)(100u + ((code >> 20) & 127u)) * H + c];
-            pre_max = fmaxf(pre_max, fabsf(pre));
-            v = silu_exact(pre);
-        }
-        rows[s * H + c] = v;
-    }
-    __syncthreads();
-    // edge_mlp.2 + SiLU
-    float acc[KF];
-    row_dot(rows, p.W2t, c, p.b2[c], acc);
-    __syncthreads();
-    if (p.range) {      // non-negative floats order like their bit patterns: one atomicMax per wave and quantity
-        float acc_max = 0.f;
-#pragma unroll
-        for (int s = 0; s < KF; ++s) acc_max = s < K ? fmaxf(acc_max, fabsf(acc[s])) : acc_max;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            pre_max = fmaxf(pre_max, __shfl_xor(pre_max, m, 64));
-            acc_max = fmaxf(acc_max, __shfl_xor(acc_max, m, 64));
-        }
-        if (lane == 0) { atomicMax(p.range, __float_as_uint(pre_max)); atomicMax(p.range + 1, __float_as_uint(acc_max)); }
-    }
-#pragma unroll
-    for (int s = 0; s < KF; ++s) {
-        acc[s] = silu_exact(acc[s]);
-        rows[s * H + c] = acc[s];
-    }
-    __syncthreads();
-    // attention gate (egnn.py:102-104): sigmoid(att_w . m + att_b) per edge
-    for (int s = wave; s < KF; s += 4) {
-        const float4 m4 = *reinterpret_cast<const float4 *>(rows + s * H + lane * 4);
-        const float4 w4 = *reinterpret_cast<const float4 *>(p.att_w + lane * 4);
-        float t = m4.x * w4.x + m4.y * w4.y + m4.z * w4.z + m4.w * w4.w;
-        t = wave_sum(t);
-        if (lane == 0) s_gate[s] = (s < K) ? sigmoid_exact(t + p.att_b) : 0.f;
-    }
-    __syncthreads();
-    float sum = 0.f;
-#pragma unroll
-    for (int s = 0; s < KF; ++s) {
-        acc[s] *= s_gate[s];
-        sum += acc[s];   // unsorted_segment_sum over this node's edges, in edge order
-    }
-    p.agg[(size_t)node * H + c] = sum;
-
-    if (p.last && i >= p.R) {
-        // coord_model (egnn.py:118-137) for ligand nodes (lig_mask)
-#pragma unroll
-        for (int s = 0; s < KF; ++s) rows[s * H + c] = acc[s];
-        __syncthreads();
-        float cacc[KF];
-        row_dot(rows, p.Wc1t, c, p.bc1[c], cacc);
-        __syncthreads();
-        const float w2 = p.wc2[c];
-#pragma unroll
-        for (int s = 0; s < KF; ++s) rows[s * H + c] = silu_exact(cacc[s]) * w2;
-        __syncthreads();
-        for (int s = wave; s < KF; s += 4) {
-            const float4 m4 = *reinterpret_cast<const float4 *>(rows + s * H + lane * 4);
-            float t = (m4.x + m4.y) + (m4.z + m4.w);
-            t = wave_sum(t);
-            if (lane == 0) s_gate[s] = fminf(fmaxf(t, -2.0f), 2.0f);   // clamp_(-2, 2)
-        }
-        __syncthreads();
-        if (c < 3) {
-            const float4 *ca = p.ca4 + (size_t)b * p.N;
-            const float4 xi = ca[i];
-            const float xi_d = c == 0 ? xi.x : (c == 1 ? xi.y : xi.z);
-            float a = 0.f;
-            for (int s = 0; s < K; ++s) {
-                const float4 xj = ca[s_j[s]];
-                const float dx = xi.x - xj.x, dy = xi.y - xj.y, dz = xi.z - xj.z;
-                const float r2 = (dx * dx + dy * dy) + dz * dz;
-                const float nrm = sqrtf(r2 + 1e-8f) + 1.0f;      // coord2radial, normalize=True
-                const float dd = (c == 0 ? dx : (c == 1 ? dy : dz)) / nrm;
-                a += dd * s_gate[s];
-            }
-            a = a / (float)(K > 1 ? K : 1);                        // unsorted_segment_mean
-            const float moved = xi_d + a;                          // coord + agg * lig_mask
-            p.fout[((size_t)b * p.L + (i - p.R)) * 3 + c] = moved - xi_d;   // f = pos_out - r
-        }
-    }
-}
 
 // =================================================================================================
 // 16-bit MFMA kernel (bf16 or fp16 operands).
@@ -234,19 +91,8 @@ union H8 { uint4 u; __half2 h[4]; };   // eight fp16 values of one gathered 16-b
 
 constexpr int LDS_WF_BYTES = 16 * 8 * 64 * 16;     // 131072: bf16 B-fragments of one 256x256 matrix
 constexpr int LDS_STAGE_BYTES = 32 * 64 * 2;       // 4096 per wave: 32 rows x 64 channels bf16
-constexpr int EDGE_WAVES = DFM_EDGE_WAVES;         // waves per workgroup: 8 = two per SIMD (256 registers each), 4 = one per SIMD (512)
+constexpr int EDGE_WAVES = 8;                      // waves per workgroup: two per SIMD, 256 registers each (one per SIMD: slower, profiles/r06_clock.txt)
 constexpr int LDS_EDGE_BYTES = LDS_WF_BYTES + EDGE_WAVES * LDS_STAGE_BYTES;   // 163840 = the whole CU with 8 waves
-// Diagnostic build (WRONG RESULTS BY DESIGN, r06): DFM_EDGE_HALF = the per-wave work of a kernel in which TWO waves share a 32-row tile
-// (each: 16 of the 32 producer rows, 128 of the 256 output columns = 64 accumulators) without the pair's hand-shakes; DFM_MSG_WAVES waves
-// per workgroup run it (12 = three per SIMD at <= 168 registers; staging areas of waves >= 8 alias those of waves 0..3: timing only).
-#ifndef DFM_EDGE_HALF
-#define DFM_EDGE_HALF 0
-#endif
-#ifndef DFM_MSG_WAVES
-#define DFM_MSG_WAVES DFM_EDGE_WAVES
-#endif
-constexpr int MSG_WAVES = DFM_MSG_WAVES;
-constexpr int MSG_NT = DFM_EDGE_HALF ? 4 : 8;      // n-tiles (32 columns) of the output a wave owns
 
 typedef float f2 __attribute__((ext_vector_type(2)));   // packed fp32 pair -> v_pk_{mul,add,fma}_f32 (2 results / instr)
 // a + (float)half of a packed fp16 pair in ONE plain-rate instruction (v_fma_mix_f32: f16 source 0 times 1.0 plus f32 source 2);
@@ -337,23 +183,12 @@ __device__ inline float half_reduce_scatter(const float (&v)[16], int lane)
 
 // make every earlier LDS access of this wave visible/ordered before later ones (wave-private staging tile)
 __device__ inline void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-// Transposing stores (last layer's gated messages, row-list form): the staging area is wave-private and a wave's LDS instructions execute in order, so neither
-// the reads after the ds_write_b16 nor the next n-tile's writes after the reads need the counter drained - DFM_EDGE_MSTORE_NOFENCE keeps the compiler's order only
-__device__ inline void mstore_fence() { if constexpr (DFM_EDGE_MSTORE_NOFENCE) asm volatile("" ::: "memory"); else wave_lds_fence(); }
 
-#if DFM_TAB_MERGE
 struct RawP { uint4 bm, t0, t1; };            // gathered fp16 operands of one producer pass (8 channels of one row)
-#else
-struct RawP { uint4 bm, t0, t1, t2; };
-#endif
 
 // one MFMA step on bf16 (F16 = 0) or fp16 (F16 = 1) operands, fp32 accumulate - same rate on gfx950
 template <int F16> __device__ inline f32x16 mfma16(const Frag &a, const Frag &b, f32x16 c)
 {
-#if DFM_EDGE_KO & 1      // knock-out build (wrong results): no matrix instruction, operands still read
-    asm volatile("" : "+v"(c) : "v"(a.u.x), "v"(a.u.w), "v"(b.u.x), "v"(b.u.w));      // (opaque: the epilogue is not folded away)
-    return c;
-#endif
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(a.f, b.f, c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.b, b.b, c, 0, 0, 0);
 }
@@ -367,11 +202,7 @@ __device__ inline uint32_t pack_f16_sat_lo(float a, float b)
     v = __builtin_elementwise_max(v, lo);
     return __builtin_bit_cast(uint32_t, v);
 }
-template <int F16> __device__ inline uint16_t to16(float x)
-{
-    if constexpr (F16) return __builtin_bit_cast(uint16_t, (_Float16)fminf(fmaxf(x, -65504.f), 65504.f));
-    else return __builtin_bit_cast(uint16_t, (__bf16)x);
-}
+__device__ inline uint16_t bf16_bits(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
 
 // Every input of a SiLU on this path is carried pre-multiplied by SILU_S = -log2(e): silu(x) = x * sigmoid(x) with
 // x' = SILU_S * x is (x' / SILU_S) / (1 + exp2(x')), i.e. exp2 -> +1 -> rcp -> mul on x' and a constant factor 1 / SILU_S
@@ -398,7 +229,7 @@ __device__ inline float4 bload16f(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint
 }
 // Streams that pass through once (A_i rows, edge data, agg / message stores) carry the non-temporal hint, so that they do not
 // push the lookup tables and the re-gathered Bm rows out of the XCD's 4 MiB L2 (cache-policy bit 1 of the buffer instructions)
-constexpr int AUX_STREAM = DFM_EDGE_NT ? 2 : 0;
+constexpr int AUX_STREAM = 2;
 __device__ inline float4 bload16f_stream(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff)
 {
     const u32x4v v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, (int)soff, AUX_STREAM);
@@ -406,19 +237,16 @@ __device__ inline float4 bload16f_stream(__amdgpu_buffer_rsrc_t rs, uint32_t vof
 }
 __device__ inline void store_stream(float *p, float v)
 {
-    if constexpr (DFM_EDGE_NT) __builtin_nontemporal_store(v, p); else *p = v;
+    __builtin_nontemporal_store(v, p);
 }
 __device__ inline void store_stream(uint4 *p, uint4 v)
 {
-    if constexpr (DFM_EDGE_NT) __builtin_nontemporal_store((u32x4v){v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4v *>(p)); else *p = v;
+    __builtin_nontemporal_store((u32x4v){v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4v *>(p));
 }
 __device__ inline __amdgpu_buffer_rsrc_t make_rsrc(const void *base)
 {   // raw buffer (stride 0), 2 GiB window, dword-format descriptor word 3 of gfx9
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0x7fffffff, 0x00027000);
 }
-// knock-out builds (DFM_EDGE_KO; WRONG results by design): bit 0 no MFMA, bit 1 no producer transcendentals, bit 2 no epilogue transcendentals
-template <int KO> __device__ inline float ko_exp2(float x) { if constexpr (KO) return x; else return __builtin_amdgcn_exp2f(x); }
-template <int KO> __device__ inline float ko_rcp(float x) { if constexpr (KO) return x; else return __builtin_amdgcn_rcpf(x); }
 // SiLU of two pre-scaled values (see SILU_S): 2 v_exp_f32 + 2 v_rcp_f32 + 2 packed ops
 __device__ inline f2 silu2s(f2 x)
 {
@@ -429,7 +257,7 @@ __device__ inline f2 silu2s(f2 x)
 }
 
 // =================================================================================================
-// fp32 engine on the matrix pipe: the same algebra as k_edge_f32, the two 256 x 256 contractions on v_mfma_f32_32x32x2_f32 (exact
+// fp32 engine on the matrix pipe: the edge model's algebra in fp32, the two 256 x 256 contractions on v_mfma_f32_32x32x2_f32 (exact
 // fp32 products and accumulation - the reference's own arithmetic, src/models/egnn.py:95-137 - at 16x the scalar-FMA rate of one
 // lane).  fp32 weights do not fit the LDS (256 KiB), so the kernel is a synchronous tiled GEMM with the edge model fused around it:
 //
@@ -442,8 +270,8 @@ __device__ inline f2 silu2s(f2 x)
 //   last layer, ligand nodes: the coordinate MLP as a second K loop whose A operand is the gated message tile, transposed chunk by
 //   chunk through the wave's rows of the staging buffer; clamp, normalised differences, mean -> f
 //
-// Summation order differs from k_edge_f32 (MFMA k order, tree reductions) at the 1e-7 level; DFM_EDGE_F32_SCALAR=1 selects the
-// scalar kernel (A/B timing, profiles/r04_fp32_engine.txt).
+// This is the engine's fp32 reference precision, checked against the tests' CPU reference model; its summation order (MFMA k order,
+// tree reductions) is not the CPU model's, so the two agree to rounding, not bitwise.
 constexpr int FM_LD = 129;                       // floats per k-row of the m1 staging ([k][128 rows] + 1)
 constexpr int FM_W_FLOATS = 32 * 256;            // one weight chunk
 constexpr int FM_M_FLOATS = 32 * FM_LD;          // one staging chunk
@@ -470,6 +298,10 @@ template <int ROWS> __global__ __launch_bounds__(256, 1) void k_edge_f32m(EdgeKA
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l31 = lane & 31;
     const int K = p.K;
+    // Diagnostic builds of this file (tools/build_variant.sh; same results, extra output through EdgeKArgs::stamp; never in the product):
+    //   -DDFM_F32M_STAMP   s_memtime stamps of this kernel's phases (tools/f32m_stamp_run.py)
+    //   -DDFM_EDGE_STAMP   per-phase cycle sums of k_edge_msg's tiles (tools/edge_phases.py)
+    //   -DDFM_EDGE_TRACE   raw wave timelines of k_edge_msg's workgroup 0, written to $DFM_EDGE_TRACE_FILE (tools/edge_trace.py)
 #ifdef DFM_F32M_STAMP
     unsigned long long st[6]; int sti = 0;
 #define FSTAMP() { __builtin_amdgcn_sched_barrier(0); st[sti++] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
@@ -563,8 +395,8 @@ template <int ROWS> __global__ __launch_bounds__(256, 1) void k_edge_f32m(EdgeKA
 #pragma unroll
         for (int j = 0; j < NOPS; ++j) fetch_op1(c, j);
     };
-    // edge_mlp.0 + SiLU (egnn.py:95-101) of element e of this thread's row `it`, same association as k_edge_f32; in two slices so that
-    // it can be laid between MFMAs (a slice must stay below the 64 cycles an MFMA occupies the pipe)
+    // edge_mlp.0 + SiLU (egnn.py:95-101) of element e of this thread's row `it`, summed as (A_i + Bm_j) + w_r r^2, then the five table
+    // rows in order; in two slices so that it can be laid between MFMAs (a slice must stay below the 64 cycles an MFMA occupies the pipe)
     float pre_e = 0.f;
     auto build_slice = [&](int buf, int it, int e, int part) {
         if (part == 0) {
@@ -811,7 +643,7 @@ template <int ROWS> __global__ __launch_bounds__(256, 1) void k_edge_f32m(EdgeKA
 // (i, j, code, radial), A_i is gathered per row like Bm_j, and instead of the segment sum the gated messages are stored row-major
 // as fp16 (S * gate * m, the unit of the last layer's message buffer).  Rows are independent in the contraction, so a row's result
 // does not depend on which other rows share its tile.
-template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVES * 64) void k_edge_msg(EdgeKArgs p)
+template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(EDGE_WAVES * 64) void k_edge_msg(EdgeKArgs p)
 {
     static_assert(!ROWS || (F16 && AW16), "the row-list form exists for the shipped 16-bit plan only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -843,7 +675,7 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
     const int U = p.B * nsplit;
     const int nb_x = U > xcd ? (U - xcd + 7) >> 3 : 0;
     const unsigned ntask = ROWS ? n_row_tiles : (unsigned)nb_x * (unsigned)NTc;
-    const unsigned tstride = ROWS ? gridDim.x * MSG_WAVES : (unsigned)wg_per_xcd * MSG_WAVES;
+    const unsigned tstride = ROWS ? gridDim.x * EDGE_WAVES : (unsigned)wg_per_xcd * EDGE_WAVES;
     auto task_tile = [&](unsigned tt, int &b, int &i, int &mt) -> bool {      // first tile of task tt
         if constexpr (ROWS) { b = 0; i = (int)tt; mt = 0; return true; }      // row-list form: "node" i = the tile of the list
         const unsigned tq = tt / (unsigned)NTc, tr = tt - tq * (unsigned)NTc;
@@ -900,7 +732,7 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
         if (lane == 0) v = __hip_atomic_fetch_add(p.task_ctr + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return v;
     };
-    auto dyn_index = [&](uint32_t pos) -> uint32_t { return (uint32_t)slot + (uint32_t)wg_per_xcd * ((uint32_t)MSG_WAVES + pos); };
+    auto dyn_index = [&](uint32_t pos) -> uint32_t { return (uint32_t)slot + (uint32_t)wg_per_xcd * ((uint32_t)EDGE_WAVES + pos); };
     if (dyn && has_task && ntile == 1) dyn_next = dyn_index((uint32_t)__builtin_amdgcn_readfirstlane((int)fetch_task()));      // one-tile tasks: needed at once
 
     // raw edge data of the tile in lookahead (rows past K read the node's last edge and are masked in set_tile)
@@ -928,9 +760,6 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
     };
     // producer state: gather offsets / resources of the tile whose operands are being REQUESTED, radial of the tile being BUILT
     uint32_t obm[2], ot0[2], ot1[2];
-#if !DFM_TAB_MERGE
-    uint32_t ot2[2];
-#endif
     uint32_t oa[2] = {0u, 0u};      // row-list form: byte offset of the row's own A_i
     float radq[2], radq_nx[2];
     __amdgpu_buffer_rsrc_t rs_bm = rs_t, rs_a = rs_t;
@@ -942,41 +771,19 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
 #pragma unroll
         for (int q = 0; q < 2; ++q) {      // masked rows (>= K; row-list form: past the end of the list): self edge, zero features -> finite values, gate forced to 0
             const bool v = ROWS ? (uint32_t)ti * 32u + (uint32_t)(q * 16 + r16) < n_rows : tm * 32 + q * 16 + r16 < K;
-            const int j = v ? jqn[q] : (DFM_EDGE_PAD0 || ROWS ? 0 : ti);
+            const int j = v ? jqn[q] : (ROWS ? 0 : ti);
             const uint32_t code = v ? codeqn[q] : 0u;
             radq_nx[q] = v ? radqn[q] : 0.f;
             if constexpr (ROWS) oa[q] = (uint32_t)(v ? iqn[q] : 0) * (H * 2) + c4 * 16;
             obm[q] = (uint32_t)j * (H * 2) + c4 * 16;
-#if DFM_TAB_MERGE
             ot0[q] = ((((code >> 6) & 31u) * 24u + ((code >> 11) & 31u)) * 12u + ((code >> 16) & 15u)) * (H * 2) + c4 * 16;
             ot1[q] = (6912u + ((code >> 20) & 127u) * 40u + (code & 63u)) * (H * 2) + c4 * 16;
-#else
-            ot0[q] = (((code >> 6) & 31u) * 24u + ((code >> 11) & 31u)) * (H * 2) + c4 * 16;
-            ot1[q] = (576u + ((code >> 16) & 15u) * 40u + (code & 63u)) * (H * 2) + c4 * 16;
-            ot2[q] = (1056u + ((code >> 20) & 127u)) * (H * 2) + c4 * 16;
-#endif
-#ifdef DFM_EDGE_SAMEROW      // diagnostic builds: rows gather row 0 (wrong results; loads issued, L1 hits): 1 everything, 2 Bm only, 3 tables only
-            if (DFM_EDGE_SAMEROW != 3) obm[q] = (obm[q] & 1u) + c4 * 16;
-            if (DFM_EDGE_SAMEROW != 2) {
-                ot0[q] = (ot0[q] & 1u) + c4 * 16; ot1[q] = (ot1[q] & 1u) + c4 * 16;
-#if !DFM_TAB_MERGE
-                ot2[q] = (ot2[q] & 1u) + c4 * 16;
-#endif
-            }
-#endif
         }
     };
     float4 a0, a1, w0, w1;      // fp32 A_i / w_r of this lane's 8 channels (AW16: a0 holds the 8 fp16 values of A_i, a1 unused)
-#ifdef DFM_EDGE_NOGATHER      // diagnostic build: the gathered operands are whatever the registers hold (wrong results, no instruction
-                              // issued for them) - the kernel's time with no gather in it
-#define FAKE4(v) asm volatile("" : "=v"((v).x), "=v"((v).y), "=v"((v).z), "=v"((v).w))
-    auto gather_chunk = [&](int) { FAKE4(a0); FAKE4(w0); FAKE4(w1); if constexpr (!AW16) FAKE4(a1); };
-    auto gather = [&](int, int, RawP &r) { FAKE4(r.bm); FAKE4(r.t0); FAKE4(r.t1); };
-#undef FAKE4
-#else
     auto gather_chunk = [&](int c) {
         if constexpr (ROWS) { a0 = bload16f(rs_a, oa[0], c * 64); a1 = bload16f(rs_a, oa[1], c * 64); }      // a row of A per pass
-        else if constexpr (AW16) a0 = DFM_EDGE_A_NT ? bload16f_stream(rs_a, c4 * 16, c * 64) : bload16f(rs_a, c4 * 16, c * 64);
+        else if constexpr (AW16) a0 = bload16f(rs_a, c4 * 16, c * 64);
         else { a0 = bload16f_stream(rs_a, oc4, c * 128); a1 = bload16f_stream(rs_a, oc4, c * 128 + 16); }
         w0 = bload16f(rs_w, oc4, c * 128); w1 = bload16f(rs_w, oc4, c * 128 + 16);
     };
@@ -984,14 +791,9 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
         r.bm = bload16(rs_bm, obm[q], c * 64);
         r.t0 = bload16(rs_t, ot0[q], c * 64);
         r.t1 = bload16(rs_t, ot1[q], c * 64);
-#if !DFM_TAB_MERGE
-        r.t2 = bload16(rs_t, ot2[q], c * 64);
-#endif
     };
-#endif
     H8 pt[2], pbm;
     f2 pv[2][4];
-    f2 pex[2];      // DFM_EDGE_SKEW: exp2 of the pair in flight, issued at the end of the pair's pre-activation slice
     Frag pf[2];
     // The producer arithmetic of one pass (8 channels of one row per lane) cut into eight slices, so that it can be laid between
     // MFMAs in program order: even slice 2e = pre-activation of channel pair e, odd slice 2e + 1 = its SiLU + conversion; slice 7
@@ -1001,16 +803,9 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
         if (k == 0) {
             H8 t1;
             pt[q].u = r.t0; t1.u = r.t1; pbm.u = r.bm;
-#if !DFM_TAB_MERGE
-            H8 t2;
-            t2.u = r.t2;
-#endif
 #pragma unroll
             for (int x = 0; x < 4; ++x) {
                 pt[q].h[x] = __hadd2(pt[q].h[x], t1.h[x]);
-#if !DFM_TAB_MERGE
-                pt[q].h[x] = __hadd2(pt[q].h[x], t2.h[x]);
-#endif
                 pt[q].h[x] = __hadd2(pt[q].h[x], pbm.h[x]);      // Bm_j joins the table rows in the packed fp16 sum (one add for two channels)
             }
         }
@@ -1026,7 +821,6 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
                 pv[q][e] = wv * rad2 + av;
             }
             pv[q][e] = add_half2(pv[q][e], pt[q].h[e]);
-            if constexpr (DFM_EDGE_SKEW && F16) pex[q] = (f2){ko_exp2<DFM_EDGE_KO & 2>(pv[q][e].x), ko_exp2<DFM_EDGE_KO & 2>(pv[q][e].y)};
         } else {
             if constexpr (F16) {
                 // fp16 operand from ONE v_cvt_pkrtz per pair: truncation saturates for free (no separate clamp), and the reciprocal
@@ -1034,11 +828,9 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
                 // within (-0.625, 0.375) ulp of the exact one: round-to-nearest-like (RMS 0.315 vs 0.289 ulp).  Same-box A/B with the
                 // packed fp16 sum above: 2.211 vs 2.251 ms per launch, deviations unchanged (profiles/r03_exp_edge_trims.txt)
                 const f2 x = pv[q][e];
-                f2 ex;
-                if constexpr (DFM_EDGE_SKEW) ex = pex[q];
-                else ex = (f2){ko_exp2<DFM_EDGE_KO & 2>(x.x), ko_exp2<DFM_EDGE_KO & 2>(x.y)};
+                f2 ex = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
                 ex = ex * (f2){0.999755859375f, 0.999755859375f} + (f2){0.999755859375f, 0.999755859375f};
-                const f2 r = {ko_rcp<DFM_EDGE_KO & 2>(ex.x), ko_rcp<DFM_EDGE_KO & 2>(ex.y)};
+                const f2 r = {__builtin_amdgcn_rcpf(ex.x), __builtin_amdgcn_rcpf(ex.y)};
                 const f2 m = x * r;
                 (&pf[q].u.x)[e] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(m.x, m.y));
             } else {
@@ -1048,9 +840,6 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
             if (k == 7) {
                 const int row = q * 16 + r16;
                 *reinterpret_cast<uint4 *>(buf + ((c4 * 32 + (row ^ (4 * c4))) << 4)) = pf[q].u;
-#if DFM_EDGE_HALF      // (rows 16..31 belong to the partner wave of the pair form: filled with a copy so that the wrong results stay finite)
-                *reinterpret_cast<uint4 *>(buf + ((c4 * 32 + ((row + 16) ^ (4 * c4))) << 4)) = pf[q].u;
-#endif
             }
         }
     };
@@ -1092,22 +881,21 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
         radq[0] = radq_nx[0]; radq[1] = radq_nx[1];
         gather_chunk(0);
         gather(0, 0, r0);
-        if constexpr (!DFM_EDGE_HALF) gather(0, 1, r1);
+        gather(0, 1, r1);
     }
     // The workgroup's weight fragments, global -> LDS, with the first tile's index loads and gathers already in flight: a launch with
     // one round of tiles (small batches, the row-list launches) otherwise pays the two dependent round trips of its prologue AFTER
     // the 128 KiB fill instead of under it.
-    for (int q = tid; q < LDS_WF_BYTES / 16; q += MSG_WAVES * 64) Wf[q] = p.Wf[q];
+    for (int q = tid; q < LDS_WF_BYTES / 16; q += EDGE_WAVES * 64) Wf[q] = p.Wf[q];
     __syncthreads();
     if (!has_task) return;
-    if constexpr (DFM_EDGE_PRIO) { if (wave >= EDGE_WAVES / 2) __builtin_amdgcn_s_setprio(DFM_EDGE_PRIO); }      // the second wave of every SIMD
     compute_store(0, r0, stage); gather(1, 0, r0);
-    if constexpr (!DFM_EDGE_HALF) { compute_store(1, r1, stage); gather(1, 1, r1); }
+    compute_store(1, r1, stage); gather(1, 1, r1);
     gather_chunk(1);
 
-    float colsum[MSG_NT];
+    float colsum[8];
 #pragma unroll
-    for (int nt = 0; nt < MSG_NT; ++nt) colsum[nt] = 0.f;
+    for (int nt = 0; nt < 8; ++nt) colsum[nt] = 0.f;
     const float *dot_v = p.att_w;
 
     while (true) {
@@ -1128,72 +916,43 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
         }
         if (!have_next) { nb = b; ni = i; nmt = mt; }
 
-        f32x16 acc[MSG_NT];
-        Frag af0c, bq0c;      // DFM_EDGE_EARLYA: k-step 0's A fragment / first weight fragment of the next chunk, carried over the chunk boundary
-        float dv[MSG_NT];
-        uint32_t bp[MSG_NT];
+        f32x16 acc[8];
+        float dv[8];
+        uint32_t bp[8];
         // one chunk: 16 MFMAs of chunk c; PRODUCE: the arithmetic of the next chunk (chunk 7: chunk 0 of the next tile), one slice after
-        // every MFMA; the loads of the chunk after that go out at the slots DFM_EDGE_G0 / GC / G1; FIRST: opens the accumulators;
-        // LAST: the epilogue's bias operand is requested instead of the (already built) staging being idle
+        // every MFMA; the loads of the chunk after that go out at the slots G0 / GC / G1; FIRST: opens the accumulators; LAST: the
+        // epilogue's bias operand is requested instead of the (already built) staging being idle, and the rest of the next tile's chunk 1
+        // is requested after the epilogue instead (outside its register budget).  A scheduling barrier after every slot keeps the slices
+        // where they are (one every 2nd or 4th slot: no faster, profiles/r06_exp_edge_sched.txt).
+        // The vector-memory counter completes in order, so a wait for the YOUNGEST load a slot needs also waits for everything issued
+        // before it: the per-chunk constants (A_i, w_r: L1 hits, used from slot 0 of the next chunk) go out BEFORE the second pass's
+        // gathers (L2 hits, used from slot 8), and both gathers as early as their registers are dead.
+        constexpr int BD = 2;       // weight-fragment buffers: each LDS read one slot ahead of its MFMA (two ahead: no faster, r06)
+        constexpr int G0 = 7;       // first pass's gathers: behind the pass's eight slices
+        constexpr int GC = 14;      // per-chunk constants A_i / w_r: ahead of the second pass's gathers
+        constexpr int G1 = 15;      // second pass's gathers: last, behind the constants
         auto chunk = [&](int c, auto first, auto last) {
             char *bufc = stage + (c & 1) * 2048, *bufn = stage + ((c + 1) & 1) * 2048;
             const int cg = (c + 2) & 7;
-            // (the staging area is wave-private and a wave's LDS instructions execute in order: the fragment reads below see the producer's
-            // ds_write without waiting for it to complete - DFM_EDGE_NOFENCE keeps only the compiler from reordering them)
-            if constexpr (DFM_EDGE_NOFENCE) asm volatile("" ::: "memory"); else wave_lds_fence();
+            // (the staging area is wave-private and a wave's LDS instructions execute in order, so the fragment reads below would see the
+            // producer's ds_write without this wait too; dropping it measured no faster: profiles/r06_exp_edge_sched.txt)
+            wave_lds_fence();
             Frag af[2];
-            constexpr bool carried = DFM_EDGE_EARLYA && !decltype(first)::value;      // k-step 0's fragments were requested at the end of the chunk before
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 const int un = ks * 2 + h;
-                if (ks == 0 && carried) af[0] = af0c;
-                else af[ks].u = *reinterpret_cast<const uint4 *>(bufc + ((un * 32 + (l31 ^ (4 * un))) << 4));
+                af[ks].u = *reinterpret_cast<const uint4 *>(bufc + ((un * 32 + (l31 ^ (4 * un))) << 4));
             }
             const uint4 *wq = Wf + (size_t)c * 16 * 64 + lane;
-#if DFM_EDGE_HALF
-            {
-                Frag bq[2];
-                bq[0].u = wq[0];
-#pragma unroll
-                for (int sl = 0; sl < 8; ++sl) {      // 8 slots: k-step sl >> 2, n-tile sl & 3; one producer slice of the wave's ONE pass after each
-                    if (sl < 7) bq[(sl + 1) & 1].u = wq[((((sl + 1) >> 2) * 8) + ((sl + 1) & 3)) * 64];
-                    if constexpr (decltype(first)::value) {
-                        if (sl < 4) acc[sl] = mfma16<F16>(af[0], bq[sl & 1], zero16);
-                        else acc[sl & 3] = mfma16<F16>(af[1], bq[sl & 1], acc[sl & 3]);
-                    } else {
-                        acc[sl & 3] = mfma16<F16>(af[sl >> 2], bq[sl & 1], acc[sl & 3]);
-                    }
-                    if constexpr (decltype(last)::value) { if (sl < 4) bp[sl] = p.biasp[sl * 64 + lane]; }
-                    slice(0, sl, r0, bufn);
-                    if (sl == 3) gather(cg, 0, r0);
-                    if constexpr (!decltype(last)::value || DFM_EDGE_DEFER < 1) { if (sl == 4) gather_chunk(cg); }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                return;
-            }
-#endif
-            constexpr int BD = DFM_EDGE_BD;
             Frag bq[BD];
 #pragma unroll
-            for (int d = 0; d < BD - 1; ++d) { if (d == 0 && carried) bq[0] = bq0c; else bq[d].u = wq[d * 64]; }
+            for (int d = 0; d < BD - 1; ++d) bq[d].u = wq[d * 64];
 #pragma unroll
             for (int m = 0; m < 16; ++m) {
-#if DFM_EDGE_KO & 8      // knock-out build (wrong results): ONE weight-fragment read per chunk instead of sixteen - what the 128 KiB of LDS reads per tile cost
-                if (m + BD - 1 < 16) asm volatile("" : "+v"(bq[(m + BD - 1) % BD].u.x), "+v"(bq[(m + BD - 1) % BD].u.y), "+v"(bq[(m + BD - 1) % BD].u.z), "+v"(bq[(m + BD - 1) % BD].u.w));
-#else
                 if (m + BD - 1 < 16) bq[(m + BD - 1) % BD].u = wq[(m + BD - 1) * 64];
-#endif
-                auto do_slice = [&]() {
-                    if constexpr (DFM_EDGE_ILV) { if (m & 1) slice(1, m >> 1, r1, bufn); else slice(0, m >> 1, r0, bufn); }      // passes interleaved slot by slot
-                    else { if (m < 8) slice(0, m & 7, r0, bufn); else slice(1, m & 7, r1, bufn); }
-                    if constexpr (DFM_EDGE_EARLYA && !decltype(last)::value) {
-                        if (m == 15) {      // the next chunk is complete in bufn: its k-step 0 operands go out now, one MFMA (and the loop's back edge) ahead of their use
-                            af0c.u = *reinterpret_cast<const uint4 *>(bufn + ((h * 32 + (l31 ^ (4 * h))) << 4));
-                            bq0c.u = wq[16 * 64];
-                        }
-                    }
-                };
-                if constexpr (DFM_EDGE_ROT) do_slice();      // slice BEFORE the slot's MFMA: the fragment reads at the top of the chunk fly under slice 0
+                // this slot's producer slice: pass m >> 3, slice m & 7 (a lambda called below the MFMA: written out in place, the same code
+                // comes out of hipcc with a different register assignment)
+                auto produce = [&]() { if (m < 8) slice(0, m & 7, r0, bufn); else slice(1, m & 7, r1, bufn); };
                 if constexpr (decltype(first)::value) {
                     if (m < 8) acc[m] = mfma16<F16>(af[0], bq[m % BD], zero16);
                     else acc[m & 7] = mfma16<F16>(af[1], bq[m % BD], acc[m & 7]);
@@ -1203,11 +962,13 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
                 if constexpr (decltype(last)::value) {
                     if (m < 8) bp[m] = p.biasp[m * 64 + lane];      // older than this chunk's gathers: the bias step does not wait for them
                 }
-                if constexpr (!DFM_EDGE_ROT) do_slice();
-                if (m == DFM_EDGE_G0) gather(cg, 0, r0);
-                if constexpr (!decltype(last)::value || DFM_EDGE_DEFER < 1) { if (m == DFM_EDGE_GC) gather_chunk(cg); }
-                if constexpr (!decltype(last)::value || DFM_EDGE_DEFER < 2) { if (m == DFM_EDGE_G1) gather(cg, 1, r1); }
-                if ((m + 1) % DFM_EDGE_SB == 0) __builtin_amdgcn_sched_barrier(0);
+                produce();
+                if (m == G0) gather(cg, 0, r0);
+                if constexpr (!decltype(last)::value) {
+                    if (m == GC) gather_chunk(cg);
+                    if (m == G1) gather(cg, 1, r1);
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
         };
         chunk(0, std::true_type{}, std::false_type{});
@@ -1220,10 +981,10 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
         radq[0] = radq_nx[0]; radq[1] = radq_nx[1];
         chunk(7, std::false_type{}, std::true_type{});      // builds chunk 0 of the next tile, requests its chunk 1
 #pragma unroll
-        for (int nt = 0; nt < MSG_NT; ++nt) dv[nt] = dot_v[nt * 32 + l31];
+        for (int nt = 0; nt < 8; ++nt) dv[nt] = dot_v[nt * 32 + l31];
         // bias k-step: acc += 1 * hi + 1 * lo (the accumulators were opened with C = 0)
 #pragma unroll
-        for (int nt = 0; nt < MSG_NT; ++nt) {
+        for (int nt = 0; nt < 8; ++nt) {
             Frag bb;
             bb.u = make_uint4(bp[nt], 0u, 0u, 0u);
             acc[nt] = mfma16<F16>(onef, bb, acc[nt]);
@@ -1246,13 +1007,11 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
 #pragma unroll
             for (int q = 0; q < 8; ++q) part2[q] = (f2){0.f, 0.f};
 #pragma unroll
-            for (int nt = 0; nt < MSG_NT; ++nt) {
+            for (int nt = 0; nt < 8; ++nt) {
                 const f2 vv = {dv[nt], dv[nt]};
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    f2 m;
-                    if constexpr (DFM_EDGE_KO & 4) m = (f2){acc[nt][2 * q], acc[nt][2 * q + 1]} * (f2){0.5f, 0.5f};      // knock-out: no transcendentals
-                    else m = silu2s((f2){acc[nt][2 * q], acc[nt][2 * q + 1]});
+                    const f2 m = silu2s((f2){acc[nt][2 * q], acc[nt][2 * q + 1]});
                     acc[nt][2 * q] = m.x; acc[nt][2 * q + 1] = m.y;
                     part2[q] = m * vv + part2[q];
                 }
@@ -1292,16 +1051,16 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
                 wr[k2] = row * 32 + uu;
             }
 #pragma unroll
-            for (int nt = 0; nt < MSG_NT; ++nt) {
+            for (int nt = 0; nt < 8; ++nt) {
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
                     const uint32_t pk = pack_f16_sat_lo(acc[nt][r] * part[r], acc[nt][r + 1] * part[r + 1]);
                     *reinterpret_cast<uint16_t *>(tb + wbase[r & 3] + (r >> 2) * 128) = (uint16_t)pk;
                     *reinterpret_cast<uint16_t *>(tb + wbase[(r + 1) & 3] + (r >> 2) * 128) = (uint16_t)(pk >> 16);
                 }
-                mstore_fence();
+                wave_lds_fence();
                 const uint4 v0 = *reinterpret_cast<const uint4 *>(tb + rd[0]), v1 = *reinterpret_cast<const uint4 *>(tb + rd[1]);
-                mstore_fence();      // the reads have returned before the next n-tile overwrites the buffer
+                wave_lds_fence();      // the reads have returned before the next n-tile overwrites the buffer
                 Rout[wr[0] + nt * 4] = v0;
                 Rout[wr[1] + nt * 4] = v1;
             }
@@ -1312,7 +1071,6 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
             // channel of 16 rows, so direct stores are 128 two-byte stores per tile (~100 cycles of issue each); instead every n-tile
             // goes through the wave's free staging buffer (buffer 1: chunk 7 has consumed it, buffer 0 already holds the next tile's
             // chunk 0): 16 ds_write_b16 (unit u, row ^ u: conflict-free), then two 16-byte reads + fully coalesced 16-byte stores.
-#if DFM_EDGE_MSTORE_LDS
             char *tb = stage + 2048;
             uint4 *Mout = reinterpret_cast<uint4 *>(p.mbuf + (((size_t)b * p.L + (i - p.R)) * 2 + mt) * (32 * H));
             const int u = l31 >> 3;
@@ -1331,38 +1089,26 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
 #pragma unroll
             for (int r = 0; r < 16; ++r) { ps[r] = part[r]; asm volatile("" : "+v"(ps[r])); }
 #pragma unroll
-            for (int nt = 0; nt < MSG_NT; ++nt) {
+            for (int nt = 0; nt < 8; ++nt) {
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
                     const float g0 = acc[nt][r] * ps[r], g1 = acc[nt][r + 1] * ps[r + 1];
                     uint32_t pk;
                     if constexpr (F16) pk = pack_f16_sat_lo(g0, g1);
-                    else pk = (uint32_t)to16<0>(g0) | ((uint32_t)to16<0>(g1) << 16);
+                    else pk = (uint32_t)bf16_bits(g0) | ((uint32_t)bf16_bits(g1) << 16);
                     *reinterpret_cast<uint16_t *>(tb + wbase[r & 3] + (r >> 2) * 128) = (uint16_t)pk;
                     *reinterpret_cast<uint16_t *>(tb + wbase[(r + 1) & 3] + (r >> 2) * 128) = (uint16_t)(pk >> 16);
                 }
-                mstore_fence();
+                wave_lds_fence();
                 const uint4 v0 = *reinterpret_cast<const uint4 *>(tb + rd[0]), v1 = *reinterpret_cast<const uint4 *>(tb + rd[1]);
-                mstore_fence();      // the reads have returned before the next n-tile overwrites the buffer
+                wave_lds_fence();      // the reads have returned before the next n-tile overwrites the buffer
                 store_stream(Mout + nt * 128 + lane, v0);
                 store_stream(Mout + nt * 128 + 64 + lane, v1);
             }
-#else
-            uint16_t *Mout = p.mbuf + (((size_t)b * p.L + (i - p.R)) * 2 + mt) * (32 * H);
-#pragma unroll
-            for (int nt = 0; nt < MSG_NT; ++nt) {
-                const int cbase = (((nt * 2 + (l31 >> 4)) * 2 + ((l31 >> 3) & 1)) * 32) * 8 + (l31 & 7);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int rowin = (r & 3) + 8 * (r >> 2) + 4 * h;
-                    Mout[cbase + rowin * 8] = to16<F16>(acc[nt][r] * part[r]);
-                }
-            }
-#endif
         }
         if (!p.no_agg) {      // (the ligand-only last layer has no reader for the segment sums: its launches skip them, r06)
 #pragma unroll
-        for (int nt = 0; nt < MSG_NT; ++nt) {
+        for (int nt = 0; nt < 8; ++nt) {
             f2 cs = {0.f, 0.f};
 #pragma unroll
             for (int q = 0; q < 8; ++q) cs = (f2){acc[nt][2 * q], acc[nt][2 * q + 1]} * (f2){part[2 * q], part[2 * q + 1]} + cs;
@@ -1385,7 +1131,7 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
             asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0" : "=v"(le));
             float *out = p.agg + ((size_t)b * p.N + i) * H + le;
 #pragma unroll
-            for (int nt = 0; nt < MSG_NT; ++nt) {
+            for (int nt = 0; nt < 8; ++nt) {
                 if (h == 0 && !p.no_agg) {
                     if (split) atomicAdd(out + nt * 32, colsum[nt]); else store_stream(out + nt * 32, colsum[nt]);
                 }
@@ -1402,13 +1148,13 @@ template <int F16, int AW16, int ROWS = 0> __global__ __launch_bounds__(MSG_WAVE
             dyn_next = dyn_index(got);
         }
         // the rest of the next tile's chunk 1 (kept out of the epilogue's register budget): the second pass is first used at slot 8
-        if constexpr (DFM_EDGE_DEFER >= 2 && !DFM_EDGE_HALF) gather(1, 1, r1);
-        if constexpr (DFM_EDGE_DEFER >= 1) gather_chunk(1);
+        gather(1, 1, r1);
+        gather_chunk(1);
         tt = ntt; b = nb; i = ni; mt = nmt;
     }
     if (dyn && lane == 0) {      // count this wave out; the last of the workgroup's waves that had a task leaves the counters zeroed for the next launch
         uint32_t active = 0;      // waves of this workgroup whose static first task exists
-        for (int w = 0; w < MSG_WAVES; ++w) active += (uint32_t)w * (uint32_t)wg_per_xcd + (uint32_t)slot < ntask ? 1u : 0u;
+        for (int w = 0; w < EDGE_WAVES; ++w) active += (uint32_t)w * (uint32_t)wg_per_xcd + (uint32_t)slot < ntask ? 1u : 0u;
         const uint32_t gone = __hip_atomic_fetch_add(p.task_ctr + TASK_CTR_WGS + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (gone + 1u == active) {
             __hip_atomic_store(p.task_ctr + blockIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1480,8 +1226,7 @@ __global__ __launch_bounds__(EDGE_WAVES * 64) void k_edge_coord(EdgeKArgs p)
     auto load_tile = [&](const uint4 *Mt, uint4 (&a)[16]) {      // read once: non-temporal, like the stores that wrote them
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {
-            const u32x4v v = DFM_EDGE_NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4v *>(Mt + kk * 64))
-                                         : *reinterpret_cast<const u32x4v *>(Mt + kk * 64);
+            const u32x4v v = __builtin_nontemporal_load(reinterpret_cast<const u32x4v *>(Mt + kk * 64));
             a[kk] = make_uint4(v.x, v.y, v.z, v.w);
         }
     };
@@ -1565,8 +1310,7 @@ __global__ __launch_bounds__(EDGE_WAVES * 64) void k_edge_coord(EdgeKArgs p)
                     if (m < 4) acc[m] = mfma16<F16>(af, bq[m % CDEPTH], zero16);
                     else acc[m & 3] = mfma16<F16>(af, bq[m % CDEPTH], acc[m & 3]);
                     if (hf == 1 && (m & 3) == 3) {      // k-step m >> 2 of this tile is done: its register takes the next tile's
-                        const u32x4v v = DFM_EDGE_NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4v *>(Mn + (m >> 2) * 64))
-                                                     : *reinterpret_cast<const u32x4v *>(Mn + (m >> 2) * 64);
+                        const u32x4v v = __builtin_nontemporal_load(reinterpret_cast<const u32x4v *>(Mn + (m >> 2) * 64));
                         cur[m >> 2] = make_uint4(v.x, v.y, v.z, v.w);
                     }
                 }
@@ -1672,24 +1416,12 @@ static EdgeKArgs to_kargs_mfma(const EdgeArgs &a, int mode)
 
 hipError_t launch_edge_f32(const EdgeArgs &a, hipStream_t s)
 {
-    static const bool scalar = [] { const char *e = getenv("DFM_EDGE_F32_SCALAR"); return e && atoi(e) != 0; }();      // diagnostics: the r01-r03 kernel
-    if (!scalar) {
-        static std::atomic<bool> attr_m[MAX_DEVICES];
-        hipError_t e = ensure_lds_attr(reinterpret_cast<const void *>(k_edge_f32m<0>), LDS_F32M_BYTES, attr_m);
-        if (e != hipSuccess) return e;
-        const EdgeKArgs k = to_kargs(a);
-        const long long tasks = (long long)a.B * k.nodes;
-        hipLaunchKernelGGL(k_edge_f32m<0>, dim3((unsigned)((tasks + 1) / 2)), dim3(256), LDS_F32M_BYTES, s, k);
-        return hipGetLastError();
-    }
     static std::atomic<bool> attr_done[MAX_DEVICES];
-    const int lds = KF * H * 4 + 4 * 64 * 4;
-    {
-        hipError_t e = ensure_lds_attr(reinterpret_cast<const void *>(k_edge_f32), lds, attr_done);
-        if (e != hipSuccess) return e;
-    }
+    hipError_t e = ensure_lds_attr(reinterpret_cast<const void *>(k_edge_f32m<0>), LDS_F32M_BYTES, attr_done);
+    if (e != hipSuccess) return e;
     const EdgeKArgs k = to_kargs(a);
-    hipLaunchKernelGGL(k_edge_f32, dim3((unsigned)((long long)a.B * a.N)), dim3(256), lds, s, k);
+    const long long tasks = (long long)a.B * k.nodes;
+    hipLaunchKernelGGL(k_edge_f32m<0>, dim3((unsigned)((tasks + 1) / 2)), dim3(256), LDS_F32M_BYTES, s, k);
     return hipGetLastError();
 }
 
@@ -1709,7 +1441,7 @@ template <int F16, int AW16> static hipError_t launch_msg_t(const EdgeKArgs &k, 
         hipError_t e = ensure_lds_attr(reinterpret_cast<const void *>(k_edge_msg<F16, AW16>), LDS_EDGE_BYTES, attr_done);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_edge_msg<F16, AW16>), dim3(persistent_grid(wave_tasks)), dim3(MSG_WAVES * 64), LDS_EDGE_BYTES, s, k);
+    hipLaunchKernelGGL((k_edge_msg<F16, AW16>), dim3(persistent_grid(wave_tasks)), dim3(EDGE_WAVES * 64), LDS_EDGE_BYTES, s, k);
     return hipGetLastError();
 }
 template <int F16> static hipError_t launch_coord_t(const EdgeKArgs &k, long long wave_tasks, hipStream_t s)
@@ -1749,7 +1481,7 @@ hipError_t launch_edge_bf16(const EdgeArgs &a, hipStream_t s)
             if (e != hipSuccess) return e;
         }
     }
-    else if (a.task_ctr && a.B >= 8 && tasks >= 2 * (long long)device_cus() * MSG_WAVES) {
+    else if (a.task_ctr && a.B >= 8 && tasks >= 2 * (long long)device_cus() * EDGE_WAVES) {
         // node tasks, more tasks than waves: every wave's tasks after its first come from the per-XCD counters (dynamic tasks, k_edge_msg)
         static const bool off = [] { const char *e = getenv("DFM_EDGE_DYNAMIC"); return e && atoi(e) == 0; }();      // diagnostics: the fixed stride of r01-r05
         if (!off && device_cus() <= TASK_CTR_WGS) k.task_ctr = a.task_ctr;      // zero at allocation, zeroed again by the last wave of every launch
@@ -1890,7 +1622,7 @@ hipError_t launch_edge_rows(const EdgeArgs &a, const uint4 *rows, const uint32_t
     static std::atomic<bool> attr_done[MAX_DEVICES];
     hipError_t e = ensure_lds_attr(reinterpret_cast<const void *>(k_edge_msg<1, 1, 1>), LDS_EDGE_BYTES, attr_done);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_edge_msg<1, 1, 1>), dim3(persistent_grid(((long long)n_rows_cap + 31) / 32)), dim3(MSG_WAVES * 64), LDS_EDGE_BYTES, s, k);
+    hipLaunchKernelGGL((k_edge_msg<1, 1, 1>), dim3(persistent_grid(((long long)n_rows_cap + 31) / 32)), dim3(EDGE_WAVES * 64), LDS_EDGE_BYTES, s, k);
     return hipGetLastError();
 }
 

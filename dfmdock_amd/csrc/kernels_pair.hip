@@ -32,7 +32,11 @@ struct PairKArgs {
     int32_t *clash_part;       // mode 0: [B][RT*4]
 };
 
-template <int EXACT>   // 1: three-pass LayerNorm, expf/division (fp32 engine); 0: sum / sum-of-squares, fast SiLU
+// The fp32 engine's pair head, k_pair_head<1>: three-pass LayerNorm, expf / IEEE division.  EXACT = 0 (LayerNorm from row moments,
+// fast SiLU: the r02-r03 head of the 16-bit engines) is no longer instantiated.  Its code stays for now: the two w_d reductions after
+// the staging loop (sum_w, sum_w2), read by EXACT = 0 only, still execute in k_pair_head<1>, so removing them changes that kernel's
+// machine code - a change to be measured on its own.
+template <int EXACT>
 __global__ __launch_bounds__(256) void k_pair_head(PairKArgs p)
 {
     extern __shared__ float Pt[];
@@ -151,8 +155,8 @@ __global__ __launch_bounds__(256) void k_pair_head(PairKArgs p)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The pair head of every engine (r04; fp32 throughout): the rank-4 part of the pre-activation on the matrix pipe.  (DFM_PAIR_HEAD_VALU=1 selects
-// k_pair_head<EXACT> above: all-VALU, three-pass LayerNorm + expf / division for the fp32 engine.)
+// The pair head of the 16-bit engines (r04; fp32 throughout): the rank-4 part of the pre-activation on the matrix pipe.  (The fp32 engine
+// runs k_pair_head<1> above: all-VALU, three-pass LayerNorm + expf / division.)
 // With S = -log2(e) folded in (SiLU as exp2 -> +1 -> rcp -> mul, see SILU_S in kernels_edge.hip) the LayerNorm output of pair (r, l) is
 //     y'_c = rstd P''[r][c]  +  [rstd D] wd''_c + [rstd] Q''[l][c] + [-mean rstd] lnw''_c + [1] lnb''_c          ('' = times S ln_w_c; lnb'' = S ln_b)
 // i.e. a per-row scaling of the resident P'' tile plus a K = 4 outer product of per-pair scalars (rstd D, rstd, -mean rstd, 1) with four
@@ -471,18 +475,16 @@ hipError_t launch_pair_dist(const float *P, const float *Q, const float4 *ca4, i
 
 hipError_t launch_pair_head(const PairArgs &a, hipStream_t s)
 {
-    static std::atomic<bool> done0[MAX_DEVICES], done1[MAX_DEVICES];
+    static std::atomic<bool> attr_done[MAX_DEVICES];
     {
-        hipError_t e = a.exact ? ensure_lds_attr(reinterpret_cast<const void *>(k_pair_head<1>), PAIR_LDS_BYTES, done1)
-                               : ensure_lds_attr(reinterpret_cast<const void *>(k_pair_head<0>), PAIR_LDS_BYTES, done0);
+        hipError_t e = ensure_lds_attr(reinterpret_cast<const void *>(k_pair_head<1>), PAIR_LDS_BYTES, attr_done);
         if (e != hipSuccess) return e;
     }
     PairKArgs k;
     k.P = a.P; k.Q = a.Q; k.ca4 = a.ca4; k.R = a.R; k.L = a.L; k.w_d = a.w_d; k.ln_w = a.ln_w; k.ln_b = a.ln_b; k.w3 = a.w3;
     k.mode = a.mode; k.cut_off = a.cut_off; k.fpart = a.fpart; k.spart = a.spart; k.clash_part = a.clash_part;
     const dim3 grid((a.R + 63) / 64, a.B);
-    if (a.exact) hipLaunchKernelGGL(k_pair_head<1>, grid, dim3(256), PAIR_LDS_BYTES, s, k);
-    else hipLaunchKernelGGL(k_pair_head<0>, grid, dim3(256), PAIR_LDS_BYTES, s, k);
+    hipLaunchKernelGGL(k_pair_head<1>, grid, dim3(256), PAIR_LDS_BYTES, s, k);
     return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build a variant of the engine that differs from the product build in kernels_edge.hip (and api.hip for -DDFM_EDGE_TRACE / _STAMP)
 # only; the other objects are the product's.  Output: tools/variants/NAME.so (git-ignored, travels with gpurun) + a resource line.
-#   bash tools/build_edge_variant.sh ilv_sb2 "-DDFM_EDGE_ILV=1 -DDFM_EDGE_SB=2 -DDFM_EDGE_G0=2 -DDFM_EDGE_G1=3"
+#   bash tools/build_edge_variant.sh trace "-DDFM_EDGE_TRACE"      (the diagnostic builds are listed in kernels_edge.hip, k_edge_f32m)
 set -e
 NAME=$1; EXTRA=$2
 ROOT=$(cd $(dirname $0)/.. && pwd); SRC=$ROOT/dfmdock_amd/csrc; OBJ=/tmp/dfm_ev_$NAME; mkdir -p $OBJ $ROOT/tools/variants

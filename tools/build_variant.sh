@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a variant of the engine next to the product library for same-box A/B runs (tools/ab_lib.sh, DFM_LIB):
-#   bash tools/build_variant.sh libdfm_stamp "-DDFM_EDGE_STAMP"
+#   bash tools/build_variant.sh libdfm_stamp "-DDFM_EDGE_STAMP"      (or -DDFM_EDGE_TRACE, -DDFM_F32M_STAMP, -DDFM_GEMM_STAMP)
 set -e
 NAME=$1; EXTRA=$2
 SRC=$(cd $(dirname $0)/../dfmdock_amd/csrc && pwd); OBJ=/tmp/dfm_variant_$NAME; mkdir -p $OBJ

@@ -1,6 +1,6 @@
 #!/bin/bash
 # HBM traffic and pipe occupancy of the node GEMM (k_gemm_split) at the bench configuration: separate --pmc passes, no trace domains.
-#   DFM_GEMM_TERMS=3 bash tools/pmc_gemm.sh   -> the three-term split-bf16 form for comparison
+#   bash tools/pmc_gemm.sh   (on the GPU box)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/pmc_gemm; rm -rf $OUT; mkdir -p $OUT
 CMD="python bench.py --steps 1 --warmup 0 --batch 256 --num-steps 2 --no-cpu-baseline"

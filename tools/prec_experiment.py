@@ -1,4 +1,4 @@
-"""Print bf16-path deviations from the reference's golden vectors (set DFM_GATHER_PREC=0..3 to compare variants)."""
+"""Print the 16-bit engine's deviations from the reference's golden vectors (argument f16: the engine with fp32 A_i)."""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
