@@ -91,10 +91,17 @@ __device__ inline float bfhi(uint32_t packed) { return __uint_as_float(packed & 
 // two fp32 -> packed fp16 on the hardware converter (round to nearest even), saturating at +-65504 like f2h (NaN stays NaN).
 // f2h above is bit manipulation for host AND device (~30 instructions and several branches per value): fine for one-off uploads,
 // not for a GEMM epilogue - the [Wa|Wb] projection spent half its time in it (profiles/r03_exp_gemm_variants.txt)
+// The clamp alone is not NaN-safe: med3 of a NaN and the two bounds returns a bound (-65504), so a NaN is passed around it
+// (tests/test_gpu_dense_kernels.py::test_fp16_outputs_follow_f2h).
+__device__ inline float sat_h(float x)
+{
+    const float c = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
+    return x != x ? x : c;
+}
 __device__ inline uint32_t pack_h2_sat(float a, float b)
 {
     typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-    const h2_t v = {(_Float16)__builtin_amdgcn_fmed3f(a, -65504.f, 65504.f), (_Float16)__builtin_amdgcn_fmed3f(b, -65504.f, 65504.f)};
+    const h2_t v = {(_Float16)sat_h(a), (_Float16)sat_h(b)};
     return __builtin_bit_cast(uint32_t, v);
 }
 __device__ inline uint32_t pack_bf2(float lo, float hi) { return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16); }

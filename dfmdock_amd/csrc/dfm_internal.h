@@ -140,8 +140,8 @@ struct GemmArgs {
     uint16_t *C2b;        // [M][256]  fp16 copy of C2 (epi 2), may be nullptr
     uint16_t *Cb;         // [M][256]  epi 2: when set, the first 256 columns go here as fp16 INSTEAD of C (k_gemm_split only)
     // optional (k_gemm_split, 64-row tiles, Nout = 256): row tiles aligned to the trajectories (rows_per_graph rows each) and
-    // per-tile column statistics of the output for GraphNorm, [M / rows_per_graph][tiles per trajectory][256][2] =
-    // (mean, sum of squared deviations) of the tile's rows; merged in the prologue of the consuming GEMM (gn_part)
+    // column statistics of the output for GraphNorm per 32-row half of a tile, [M / rows_per_graph][ceil(rows_per_graph / 32)][256][2] =
+    // (mean, sum of squared deviations) of the half's rows; merged in the prologue of the consuming GEMM (gn_part)
     float *stat_part;
     // optional (k_gemm_split, pro 2): the GraphNorm statistics are finished INSIDE the prologue - every workgroup merges the per-tile
     // (mean, M2) pairs of its trajectory (gn_part, written by the previous launch's stat_part) exactly as k_gn_finish does, so small
@@ -156,8 +156,9 @@ struct GemmArgs {
     int a0_period, r_period;
 };
 hipError_t launch_gemm_f32(const GemmArgs &a, hipStream_t s);
-// split-bf16 (hi/lo) variant, ~1e-5 relative error; Whi/Wlo = pre-split weights [Nout][ldw] bf16
-// W16 non-null: the two-term fp16 form (weights as ONE fp16 tile in the same [K/32][4][Nout][8] order); else three bf16 terms
+// split-bf16 (hi/lo) variant: three bf16 MFMA terms a_hi w_hi + a_hi w_lo + a_lo w_hi, ~1e-5 relative error (bound 2^-15 |A||W|^T:
+// tests/test_gpu_dense_kernels.py); Whi / Wlo = the pre-split weights as bf16 tiles [K/32][4][Nout][8] (split_bf16 in api.hip), a.W
+// and a.ldw unused.  Needs K % 32 == 0, Nout % 256 == 0, lda and ldc multiples of 4 (else hipErrorInvalidValue before any launch)
 hipError_t launch_gemm_split(const GemmArgs &a, const uint16_t *Whi, const uint16_t *Wlo, hipStream_t s);
 int gemm_rows_per_tile();   // 64: the row tile of k_gemm_split (tiles of the fused GraphNorm statistics)
 
