@@ -193,14 +193,22 @@ template <int F16> __device__ inline f32x16 mfma16(const Frag &a, const Frag &b,
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.b, b.b, c, 0, 0, 0);
 }
 // two fp32 -> packed fp16 (round to nearest even), -inf / below -65504 clamped to -65504 by ONE packed max on the converted pair
-// (the values on this path are S * silu(.) [* gate]: bounded above by 0.41, unbounded below; no NaN from finite inputs)
+// (the values on this path are S * silu(.) [* gate]: bounded above by 0.41, unbounded below; no NaN from finite inputs).  The max
+// is IEEE maximum (NaN-propagating, v_pk_maximum3_f16): a NaN stays NaN like in the bf16 form and the fp32 engine - maxNum
+// (v_pk_max_f16) would return -65504 for it and hand the coordinate update a finite message
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 __device__ inline uint32_t pack_f16_sat_lo(float a, float b)
 {
     f16x2 v = {(_Float16)a, (_Float16)b};
     const f16x2 lo = {(_Float16)-65504.f, (_Float16)-65504.f};
-    v = __builtin_elementwise_max(v, lo);
+    v = __builtin_elementwise_maximum(v, lo);
     return __builtin_bit_cast(uint32_t, v);
+}
+// clamp_(-2, 2) of the coordinate MLP's output (egnn.py:135) that keeps a NaN, like torch.clamp: med3 alone returns a bound for it
+__device__ inline float clamp2_keep_nan(float w)
+{
+    const float c = __builtin_amdgcn_fmed3f(w, -2.0f, 2.0f);
+    return w != w ? w : c;
 }
 __device__ inline uint16_t bf16_bits(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
 
@@ -544,7 +552,7 @@ template <int ROWS> __global__ __launch_bounds__(256, 1) void k_edge_f32m(EdgeKA
         if (h == 0) s_part[wave * 256 + nt * 32 + l31] = cs;
     }
     __syncthreads();
-    if (mt == 0 && wvalid) {
+    if (mt == 0 && wvalid && !p.no_agg) {      // (ligand-only last layer: nobody reads agg, as in k_edge_msg)
         float *out = p.agg + ((size_t)wb * p.N + wi) * H;
 #pragma unroll
         for (int q = 0; q < 4; ++q) out[q * 64 + lane] = s_part[wave * 256 + q * 64 + lane] + s_part[(wave + 1) * 256 + q * 64 + lane];
@@ -609,7 +617,7 @@ template <int ROWS> __global__ __launch_bounds__(256, 1) void k_edge_f32m(EdgeKA
     const float4 xi = ca[wi];
     if (l31 < 16 && lrow < K) {
         const float4 xj = ca[s_j[(wave >> 1) * 64 + lrow]];
-        w = fminf(fmaxf(w, -2.0f), 2.0f);                                       // clamp_(-2, 2)
+        w = clamp2_keep_nan(w);                                                 // clamp_(-2, 2)
         const float dx = xi.x - xj.x, dy = xi.y - xj.y, dz = xi.z - xj.z;
         const float nrm = sqrtf((dx * dx + dy * dy) + dz * dz + 1e-8f) + 1.0f;   // coord2radial, normalize=True
         c0 = dx / nrm * w; c1 = dy / nrm * w; c2 = dz / nrm * w;
@@ -1352,7 +1360,7 @@ __global__ __launch_bounds__(EDGE_WAVES * 64) void k_edge_coord(EdgeKArgs p)
         for (int r = 1; r < 16; ++r) w = l31 == r ? part[r] : w;
         if (l31 < 16 && lrow < K) {
             const float4 xi = c_xi, xj = c_xj;
-            w = fminf(fmaxf(w, -2.0f), 2.0f);
+            w = clamp2_keep_nan(w);
             const float dx = xi.x - xj.x, dy = xi.y - xj.y, dz = xi.z - xj.z;
             const float nrm = sqrtf(dx * dx + dy * dy + dz * dz + 1e-8f) + 1.0f;
             cacc0 += dx / nrm * w; cacc1 += dy / nrm * w; cacc2 += dz / nrm * w;
@@ -1414,8 +1422,19 @@ static EdgeKArgs to_kargs_mfma(const EdgeArgs &a, int mode)
     return k;
 }
 
+// Shapes the node-task kernels run correctly, refused with hipErrorInvalidValue before any HIP call: 1 <= K <= 60 (the degree the
+// model allows, dfm_model_create; a node's two 32-row tiles hold up to 64 rows, K = 61 .. 64 is untested), at least one trajectory and
+// node, 0 <= R <= N, and a ligand node whenever the launch reads or writes ligand outputs (coordinate update, last layer, ligand-only).
+constexpr int EDGE_K_MAX = 60;
+static bool edge_shape_ok(const EdgeArgs &a, bool coord)
+{
+    if (a.K < 1 || a.K > EDGE_K_MAX || a.B < 1 || a.N < 1 || a.R < 0 || a.R > a.N) return false;
+    return !((coord || a.last || a.lig_only) && a.R >= a.N);
+}
+
 hipError_t launch_edge_f32(const EdgeArgs &a, hipStream_t s)
 {
+    if (!edge_shape_ok(a, false)) return hipErrorInvalidValue;
     static std::atomic<bool> attr_done[MAX_DEVICES];
     hipError_t e = ensure_lds_attr(reinterpret_cast<const void *>(k_edge_f32m<0>), LDS_F32M_BYTES, attr_done);
     if (e != hipSuccess) return e;
@@ -1472,6 +1491,7 @@ bool edge_msg_tile_tasks(int B, int N /* nodes with a task per trajectory */, in
 
 hipError_t launch_edge_bf16(const EdgeArgs &a, hipStream_t s)
 {
+    if (!edge_shape_ok(a, false)) return hipErrorInvalidValue;
     EdgeKArgs k = to_kargs_mfma(a, 0);
     long long tasks = (long long)a.B * k.nodes;
     if (edge_msg_tile_tasks(a.B, k.nodes, a.K)) {
@@ -1492,6 +1512,7 @@ hipError_t launch_edge_bf16(const EdgeArgs &a, hipStream_t s)
 
 hipError_t launch_coord_bf16(const EdgeArgs &a, hipStream_t s)
 {
+    if (!edge_shape_ok(a, true)) return hipErrorInvalidValue;
     EdgeKArgs k = to_kargs_mfma(a, 1);
     const long long tasks = (long long)a.B * (a.N - a.R);
     static const bool off = [] { const char *e = getenv("DFM_EDGE_DYNAMIC"); return e && atoi(e) == 0; }();
