@@ -41,6 +41,7 @@ EXPORTS = [
     "dfm_complex_set_pose", "dfm_complex_set_homomer",
     "dfm_score", "dfm_sample", "dfm_get_profile", "dfm_diffusion_coef", "dfm_complex_selfcheck", "dfm_trim_cache",
     "dfm_complex_set_restraints", "dfm_restraint_eval", "dfm_pose_rmsd", "dfm_pose_cluster", "dfm_pose_last_timing",
+    "dfm_refine", "dfm_forward_marginal", "dfm_igso3_table",
 ]
 
 
@@ -66,6 +67,14 @@ class TrajOutC(C.Structure):
     _fields_ = [("lig_pos", F32P), ("rot_update", F32P), ("tr_update", F32P), ("energy", F32P),
                 ("num_clashes", I32P), ("final_scores", F32P), ("trace_pose", F32P), ("trace_scores", F32P),
                 ("init_pose", F32P)]
+
+
+class RefineParamsC(C.Structure):
+    _fields_ = [("t_begin", C.c_float), ("perturb", C.c_int), ("start_pos", F32P)]
+
+
+class RefineInjectC(C.Structure):
+    _fields_ = [("u_angle", F32P), ("axis_draw", F32P), ("tr_draw", F32P)]
 
 
 class ProfileC(C.Structure):
@@ -126,6 +135,10 @@ def lib():
     L.dfm_score.argtypes = [C.c_void_p, C.c_int, F32P, F32P, I32P, C.c_uint64, C.c_uint32, C.POINTER(ScoreOutC)]
     L.dfm_sample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint64,
                              C.POINTER(InjectC), C.POINTER(TrajOutC)]
+    L.dfm_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint64,
+                             C.POINTER(RefineParamsC), C.POINTER(InjectC), C.POINTER(RefineInjectC), C.POINTER(TrajOutC)]
+    L.dfm_forward_marginal.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.POINTER(RefineInjectC), F32P, F32P]
+    L.dfm_igso3_table.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_get_profile.argtypes = [C.c_void_p, C.POINTER(ProfileC)]
     L.dfm_complex_selfcheck.argtypes = [C.c_void_p, C.c_int, F32P, C.c_uint64, C.c_uint32, C.POINTER(SelfcheckC)]
     L.dfm_complex_set_restraints.argtypes = [C.c_void_p, C.c_int, I32P, I32P, F32P, F32P, C.POINTER(RestraintParamsC)]

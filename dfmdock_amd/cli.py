@@ -7,6 +7,8 @@
     python -m dfmdock_amd sweep ... --native-restraints K [--restraint-cutoff 8.0]
     python -m dfmdock_amd dock ... --top-k K [--cluster-radius 4.0] [--cluster-rule energy|size]
     python -m dfmdock_amd sweep ... --cluster-radius R [--top-k 10] [--cluster-rule energy|size]
+    python -m dfmdock_amd refine REC.pdb LIG.pdb --ckpt model_0.ckpt --features F.npz --t-begin 0.1 [--num-samples 32] [--no-perturb]
+    python -m dfmdock_amd dock ... --top-k K --refine-t T [--refine-samples 8]
 
   dock       <- src/inference_single.py:1-12 -> inference() (src/inference_base.py:601-670): num_samples (120) trajectories of
                 num_steps (40), the minimum-energy one applied to the all-atom ligand, `output.pdb` written, {"energy": E} printed.
@@ -25,6 +27,10 @@
              `dock --top-k K` writes the centres of the first K clusters as <out stem>_1.pdb ... <out stem>_K.pdb (model 1 of rule
              energy is output.pdb) and lists them under `models`; `sweep --cluster-radius R` adds `cluster` / `is_center` to the CSV and
              a top{K} success rate (any of the first K cluster centres reaches the DockQ threshold).
+  refine     no reference counterpart as a command; the forward process is the reference's training-step noising (dfmdock_amd/refine.py):
+             the pose the two PDB files are in is noised at --t-begin and the sampler runs down from there (dfm_refine); same output
+             contract as `dock`.  `dock --top-k K --refine-t T` refines the K cluster centres in one batched call; <out stem>_k.pdb is
+             then the minimum-energy refined pose of centre k and `models` carries both energies.
   selfcheck  no reference counterpart: dfm_complex_selfcheck on the pair (what `dock` and `sweep` run once per complex anyway).
 
 --ckpt takes the Lightning checkpoint the reference loads (src/inference_base.py:611-616; read without Lightning / omegaconf by
@@ -75,7 +81,21 @@ def build_parser():
     d.add_argument("--cluster-radius", type=float, default=4.0, help="with --top-k: ligand RMSD radius of a cluster (A)")
     d.add_argument("--cluster-rule", default="energy", choices=["energy", "size"],
                    help="with --top-k: leader clustering in key order (default) or greedy by cluster size")
+    d.add_argument("--refine-t", type=float, default=None, metavar="T",
+                   help="with --top-k: refine every cluster centre locally from t_begin = T (one batched call)")
+    d.add_argument("--refine-samples", type=int, default=8, metavar="n", help="with --refine-t: trajectories per cluster centre")
     _add_common(d)
+    r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)")
+    r.add_argument("pdb_1", help="receptor PDB")
+    r.add_argument("pdb_2", help="ligand PDB, in the pose to refine")
+    r.add_argument("--features", required=True, help=".npz with rec_esm / lig_esm [n,1280] (or rec_x / lig_x [n,1301])")
+    r.add_argument("--t-begin", type=float, default=0.1, help="time the forward process noises the pose to (eps < t <= 1)")
+    r.add_argument("--num-samples", type=int, default=32)
+    r.add_argument("--no-perturb", action="store_true", help="start every trajectory at the pose itself")
+    r.add_argument("--out", default="output.pdb")
+    r.add_argument("--json", default=None, help="also write the result line to this file")
+    r.add_argument("--restraints", default=None, help="interface restraint file (as for dock)")
+    _add_common(r)
     s = sub.add_parser("sweep", help="sample every complex of a DB5-style directory (inference_mlsb.py run_sampling)")
     s.add_argument("--db5", required=True, help="directory of <id>.pt files (+ optional test.txt with the ids to run)")
     s.add_argument("--num-samples", type=int, default=40)
@@ -99,6 +119,14 @@ def build_parser():
     c.add_argument("--n-eval", type=int, default=4)
     _add_common(c)
     return ap
+
+
+def parse_args(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.cmd == "dock" and args.refine_t is not None and args.top_k is None:
+        ap.error("--refine-t refines the cluster centres: it needs --top-k")
+    return args
 
 
 def load_model(args):
@@ -213,6 +241,8 @@ def cmd_dock(args):
         kw = dict(restraints=read_restraints(args.restraints, rec, lig), restraint_rank=args.restraint_rank)
     if args.top_k is not None:
         kw.update(top_k=args.top_k, cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule)
+    if args.refine_t is not None:
+        kw.update(refine_t=args.refine_t, refine_samples=args.refine_samples)
     res = driver.dock_pair(model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                            precision=args.precision, out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
                            on_selfcheck_fail=args.on_selfcheck_fail, **kw)
@@ -225,6 +255,8 @@ def cmd_dock(args):
     if args.top_k is not None:
         line.update(models=[dict(m, path=os.path.abspath(driver.model_path(args.out, m["rank"]))) for m in res["models"]],
                     cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule)
+    if args.refine_t is not None:
+        line.update(refine_t=args.refine_t, refine_samples=args.refine_samples)
     print(json.dumps(line), flush=True)
     if args.json:
         extra = {}
@@ -232,6 +264,28 @@ def cmd_dock(args):
             extra["trajectories"] = {k: [float(x) for x in v] for k, v in res["trajectories"].items()}
         with open(args.json, "w") as f:
             json.dump(dict(line, selfcheck=res["selfcheck"], **extra), f, default=float)
+    return 0
+
+
+def cmd_refine(args):
+    from . import driver
+    model, _ = load_model(args)
+    rec, lig, rec_x, lig_x = load_pair(args.pdb_1, args.pdb_2, args.features, model.hp.lm_embed_dim)
+    kw = {}
+    if args.restraints:
+        from .restraints import read_restraints
+        kw = dict(restraints=read_restraints(args.restraints, rec, lig))
+    res = driver.refine_pair(model, rec, lig, rec_x, lig_x, t_begin=args.t_begin, num_samples=args.num_samples, num_steps=args.num_steps,
+                             seed=args.seed, precision=args.precision, out_pdb=args.out, max_batch=args.max_batch,
+                             selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, perturb=not args.no_perturb, **kw)
+    line = {"energy": res["energy"], "output": os.path.abspath(args.out), "num_samples": args.num_samples, "precision": res["precision"],
+            "t_begin": res["t_begin"], "perturb": not args.no_perturb, "index": res["index"],
+            "rot_update": [float(v) for v in res["rot_update"]], "tr_update": [float(v) for v in res["tr_update"]],
+            "selfcheck_ok": None if res["selfcheck"] is None else bool(res["selfcheck"]["ok"])}
+    print(json.dumps(line), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(dict(line, selfcheck=res["selfcheck"], energies=[float(e) for e in res["trajectories"]["energy"]]), f, default=float)
     return 0
 
 
@@ -307,5 +361,5 @@ def cmd_selfcheck(args):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    return {"dock": cmd_dock, "sweep": cmd_sweep, "selfcheck": cmd_selfcheck}[args.cmd](args)
+    args = parse_args(argv)
+    return {"dock": cmd_dock, "sweep": cmd_sweep, "selfcheck": cmd_selfcheck, "refine": cmd_refine}[args.cmd](args)

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -254,7 +255,9 @@ struct dfm_model {
     PairHeadDev pair[3];             // family 1: 0 to_force, 1 to_energy, 2 to_confidence
     PairHeadDev dist;                // family 1: to_dist (fp32 only; w3 = [256][64], transposed)
     float *ir0_w = nullptr, *ir0_b = nullptr, *ir2_w = nullptr, *ir2_b = nullptr, *ir4_w = nullptr, *ir4_b = nullptr;   // to_ires
-    float tab_max[8][2] = {};        // per layer: largest |entry| of the two merged lookup tables as stored (log2e-scaled; before the fp16 clamp)
+    float tab_max[8][2] = {};        // per layer: largest |entry| of the two merged lookup tables as stored (log2e-scaled; before the fp16 clamp)    // local refinement: IGSO(3) cdf tables by sigma index (k_igso3_cdf, 8 KB each in `pool`), built on first use and never changed
+    std::mutex ig_m;
+    std::map<int, double *> ig_tab;
 };
 
 struct Workspace {
@@ -1259,6 +1262,7 @@ extern "C" const char *dfm_config_string(void)
         c += "three-term split-bf16";
         c += ", fp32 accumulate / geometry / GraphNorm statistics / heads / SDE step";
         c += "; layer 0 through the per-complex message table in dfm_sample (DFM_F_NO_L0_TABLE: direct), on request in dfm_score (DFM_F_L0_TABLE)";
+        c += "; dfm_refine: start from a given pose at t_begin (IGSO(3) cdf tables in float64, cached per sigma index), then dfm_sample's steps";
         std::string env;
         for (const char *k : {"DFM_EDGE_SPLIT", "DFM_GEMM_NARROW_MAXWG", "DFM_GEMM_QUARTER_MAXWG", "DFM_L0_TABLE", "DFM_GRAPH", "DFM_ALLOC_CACHE", "DFM_ALLOC_CACHE_FRAC", "DFM_ALLOC_POISON", "DFM_ALLOC_GUARD", "DFM_LIB"}) {
             const char *e = getenv(k);
@@ -1728,8 +1732,12 @@ extern "C" int dfm_score(dfm_complex *cx, int B, const float *lig_pos, const flo
 }
 
 // ------------------------------------------------------------------------------------------------
-extern "C" int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, float tr_noise_scale, float rot_noise_scale,
-                          uint32_t flags, uint64_t seed, const dfm_inject *inj, dfm_traj_out *out)
+// The sampler behind dfm_sample and dfm_refine: the time grid linspace(t_first, eps, num_steps) and `start`, which fills ws.lig_cur /
+// tr_update / rot_update with the start poses on the handle's stream (per-call device buffers from `tmp`).  Everything after the
+// start - noise scales, last step without noise, annealing, ODE, clash force, restraint step, final evaluation - is shared.
+using StartFn = std::function<int(DevPool &tmp)>;
+static int sample_impl(dfm_complex *cx, int B, int num_steps, float eps, float tr_noise_scale, float rot_noise_scale,
+                       uint32_t flags, uint64_t seed, const dfm_inject *inj, dfm_traj_out *out, float t_first, const StartFn &start)
 {
     if (!cx || !out) return fail(DFM_E_INVALID, "NULL argument");
     if (B < 1 || num_steps < 2) return fail(DFM_E_INVALID, "need B >= 1 and num_steps >= 2");
@@ -1758,12 +1766,12 @@ extern "C" int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, floa
         HIPCHK(hipMemsetAsync(W.l0_miss_total, 0, sizeof(unsigned long long), s));
     }
 
-    // time grid: torch.linspace(1, eps, num_steps) in float32; dt = t[0] - t[1]   (inference_base.py:404-405)
+    // time grid: torch.linspace(t_first, eps, num_steps) in float32; dt = t[0] - t[1]   (inference_base.py:404-405 with t_first = 1)
     std::vector<float> ts(S);
     {
-        const float step = (eps - 1.0f) / (float)(num_steps - 1);
+        const float step = (eps - t_first) / (float)(num_steps - 1);
         for (int i = 0; i < num_steps; ++i)
-            ts[i] = i < num_steps / 2 ? 1.0f + step * (float)i : eps - step * (float)(num_steps - 1 - i);
+            ts[i] = i < num_steps / 2 ? t_first + step * (float)i : eps - step * (float)(num_steps - 1 - i);
     }
     const float dt = ts[0] - ts[1];
     std::vector<double> gr(S), gt(S);
@@ -1775,12 +1783,9 @@ extern "C" int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, floa
 
     DevPool tmp;   // per-call device buffers (injections, traces)
     tmp.bind(cx->stream);
-    float *R0_d = nullptr, *trd_d = nullptr, *zr_d = nullptr, *zt_d = nullptr, *tp_d = nullptr, *tsc_d = nullptr,
-          *ip_d = nullptr;
+    float *zr_d = nullptr, *zt_d = nullptr, *tp_d = nullptr, *tsc_d = nullptr, *ip_d = nullptr;
     int32_t *ed_d = nullptr;
     if (inj) {
-        if (inj->R0) HIPCHK(tmp.upload(&R0_d, inj->R0, (size_t)B * 9));
-        if (inj->tr_draw) HIPCHK(tmp.upload(&trd_d, inj->tr_draw, (size_t)B * 3));
         if (inj->z_rot) HIPCHK(tmp.upload(&zr_d, inj->z_rot, (size_t)B * S * 3));
         if (inj->z_tr) HIPCHK(tmp.upload(&zt_d, inj->z_tr, (size_t)B * S * 3));
         if (inj->edges) HIPCHK(tmp.upload(&ed_d, inj->edges, (size_t)B * (S + 1) * N * K));
@@ -1792,8 +1797,7 @@ extern "C" int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, floa
     HIPCHK(hipMemcpyAsync(W.t_dev, ts.data(), S * sizeof(float), hipMemcpyHostToDevice, s));
     HIPCHK(launch_time_embed(W.t_dev, num_steps, &cx->m->heads, W.hid_base, s));
     HIPCHK(hipEventRecord(cx->ev_total[0], s));
-    HIPCHK(launch_init_pose(cx->rec_pos, cx->lig0, B, cx->R, cx->L, hp.family == 1, R0_d, trd_d, seed, W.lig_cur, W.tr_update,
-                            W.rot_update, s));
+    if ((rc = start(tmp)) != DFM_OK) return rc;
     if (out->init_pose) {
         HIPCHK(tmp.alloc(&ip_d, (size_t)B * L * 9));
         HIPCHK(hipMemcpyAsync(ip_d, W.lig_cur, (size_t)B * L * 9 * 4, hipMemcpyDeviceToDevice, s));
@@ -1922,6 +1926,140 @@ extern "C" int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, floa
     }
     if (o.profile) return finish_profile(cx);
     return DFM_OK;
+}
+
+extern "C" int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, float tr_noise_scale, float rot_noise_scale,
+                          uint32_t flags, uint64_t seed, const dfm_inject *inj, dfm_traj_out *out)
+{
+    // randomize_pose (inference_base.py:318-340) at t = 1
+    const StartFn start = [&](DevPool &tmp) -> int {
+        float *R0_d = nullptr, *trd_d = nullptr;
+        if (inj && inj->R0) HIPCHK(tmp.upload(&R0_d, inj->R0, (size_t)B * 9));
+        if (inj && inj->tr_draw) HIPCHK(tmp.upload(&trd_d, inj->tr_draw, (size_t)B * 3));
+        HIPCHK(launch_init_pose(cx->rec_pos, cx->lig0, B, cx->R, cx->L, cx->m->hp.family == 1, R0_d, trd_d, seed, cx->ws.lig_cur,
+                                cx->ws.tr_update, cx->ws.rot_update, cx->stream));
+        return DFM_OK;
+    };
+    return sample_impl(cx, B, num_steps, eps, tr_noise_scale, rot_noise_scale, flags, seed, inj, out, 1.0f, start);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Local refinement (include/dfmdock_amd.h: dfm_refine; definition: dfmdock_amd/refine.py).
+// The sigma index of time t on the reference's grid (so3_diffuser.py:199-206: digitize(sigma(t), sigma(linspace(0, 1, 1000))) - 1), the
+// grid sigma, and the device table of that index - built on `s` and waited for on first use, then shared by every handle of the model.
+static int igso3_table(dfm_model *m, double t, hipStream_t s, int *idx_out, double *sigma_out, const double **dev_out)
+{
+    double st = 0.0;
+    int rc = dfm_diffusion_coef(&m->hp, 1, t, nullptr, &st);
+    if (rc) return rc;
+    int idx = -1;
+    double sg = 0.0;
+    for (int i = 0; i < IGSO3_N; ++i) {      // the grid is increasing: idx = #(grid <= sigma(t)) - 1
+        const double ti = i == IGSO3_N - 1 ? 1.0 : (double)i * (1.0 / (double)(IGSO3_N - 1));      // np.linspace(0, 1, 1000)
+        double si = 0.0;
+        dfm_diffusion_coef(&m->hp, 1, ti, nullptr, &si);
+        if (si <= st) { idx = i; sg = si; } else break;
+    }
+    if (idx < 0) return fail(DFM_E_INVALID, "sigma(t) below the sigma grid");
+    std::lock_guard<std::mutex> g(m->ig_m);
+    auto it = m->ig_tab.find(idx);
+    if (it == m->ig_tab.end()) {
+        double *d = nullptr;
+        HIPCHK(m->pool.alloc(&d, (size_t)IGSO3_N));
+        HIPCHK(launch_igso3_cdf(sg, d, s));
+        HIPCHK(hipStreamSynchronize(s));
+        it = m->ig_tab.emplace(idx, d).first;
+    }
+    if (idx_out) *idx_out = idx;
+    if (sigma_out) *sigma_out = sg;
+    if (dev_out) *dev_out = it->second;
+    return DFM_OK;
+}
+
+extern "C" int dfm_igso3_table(dfm_model *m, double t, int *sigma_idx, double *sigma, double *cdf)
+{
+    if (!m) return fail(DFM_E_INVALID, "NULL argument");
+    DEVICE_SCOPE(m->device);
+    const double *dev = nullptr;
+    int rc = igso3_table(m, t, nullptr, sigma_idx, sigma, &dev);
+    if (rc) return rc;
+    if (cdf) HIPCHK(hipMemcpy(cdf, dev, (size_t)IGSO3_N * sizeof(double), hipMemcpyDeviceToHost));
+    return DFM_OK;
+}
+
+static int fill_start_args(dfm_complex *cx, int B, float t, uint64_t seed, const dfm_refine_inject *rinj, DevPool &tmp, const double *cdf,
+                           StartArgs *a)
+{
+    std::memset(a, 0, sizeof(*a));
+    a->start = cx->lig0; a->start_bstride = 0;
+    a->L = cx->L; a->all_atoms = cx->m->hp.family == 1; a->perturb = 1;
+    a->cdf = cdf;
+    dfm_diffusion_coef(&cx->m->hp, 0, (double)t, nullptr, &a->sigma_r3);
+    a->seed_lo = (uint32_t)seed; a->seed_hi = (uint32_t)(seed >> 32);
+    if (rinj) {
+        float *u = nullptr, *ax = nullptr, *tr = nullptr;
+        if (rinj->u_angle) HIPCHK(tmp.upload(&u, rinj->u_angle, (size_t)B));
+        if (rinj->axis_draw) HIPCHK(tmp.upload(&ax, rinj->axis_draw, (size_t)B * 3));
+        if (rinj->tr_draw) HIPCHK(tmp.upload(&tr, rinj->tr_draw, (size_t)B * 3));
+        a->u_inj = u; a->axis_inj = ax; a->tr_inj = tr;
+    }
+    return DFM_OK;
+}
+
+extern "C" int dfm_forward_marginal(dfm_complex *cx, int B, float t, uint64_t seed, const dfm_refine_inject *rinj, float *rot, float *tr)
+{
+    if (!cx || !rot || !tr) return fail(DFM_E_INVALID, "NULL argument");
+    if (B < 1) return fail(DFM_E_INVALID, "need B >= 1");
+    if (!(t >= 0.0f && t <= 1.0f)) return fail(DFM_E_INVALID, "Invalid t (need 0 <= t <= 1)");
+    DEVICE_SCOPE(cx->device);
+    hipStream_t s = cx->stream;
+    const double *cdf = nullptr;
+    int rc = igso3_table(cx->m, (double)t, s, nullptr, nullptr, &cdf);
+    if (rc) return rc;
+    DevPool tmp;
+    tmp.bind(s);
+    StartArgs a;
+    if ((rc = fill_start_args(cx, B, t, seed, rinj, tmp, cdf, &a)) != DFM_OK) return rc;
+    float *o = nullptr;
+    HIPCHK(tmp.alloc(&o, (size_t)B * 6));
+    a.rot_update = o; a.tr_update = o + (size_t)B * 3;      // lig_cur stays NULL: the updates only
+    HIPCHK(launch_start_pose(a, B, s));
+    HIPCHK(hipMemcpyAsync(rot, a.rot_update, (size_t)B * 3 * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(tr, a.tr_update, (size_t)B * 3 * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return DFM_OK;
+}
+
+extern "C" int dfm_refine(dfm_complex *cx, int B, int num_steps, float eps, float tr_noise_scale, float rot_noise_scale, uint32_t flags,
+                          uint64_t seed, const dfm_refine_params *p, const dfm_inject *inj, const dfm_refine_inject *rinj, dfm_traj_out *out)
+{
+    if (!cx || !out || !p) return fail(DFM_E_INVALID, "NULL argument");
+    if (B < 1 || num_steps < 2) return fail(DFM_E_INVALID, "need B >= 1 and num_steps >= 2");
+    if (num_steps > (1 << 24)) return fail(DFM_E_INVALID, "num_steps above 2^24");
+    if (!(p->t_begin > eps && p->t_begin <= 1.0f)) return fail(DFM_E_INVALID, "need eps < t_begin <= 1");
+    if (inj && (inj->R0 || inj->tr_draw))
+        return fail(DFM_E_INVALID, "dfm_inject.R0 / tr_draw belong to randomize_pose: inject the start of dfm_refine through dfm_refine_inject");
+    DEVICE_SCOPE(cx->device);
+    const double *cdf = nullptr;
+    if (p->perturb) {
+        int rc = igso3_table(cx->m, (double)p->t_begin, cx->stream, nullptr, nullptr, &cdf);
+        if (rc) return rc;
+    }
+    const StartFn start = [&](DevPool &tmp) -> int {
+        StartArgs a;
+        int rc = fill_start_args(cx, B, p->t_begin, seed, p->perturb ? rinj : nullptr, tmp, cdf, &a);
+        if (rc) return rc;
+        a.perturb = p->perturb ? 1 : 0;
+        if (p->start_pos) {
+            float *sp = nullptr;
+            HIPCHK(tmp.upload(&sp, p->start_pos, (size_t)B * cx->L * 9));
+            a.start = sp; a.start_bstride = (int64_t)cx->L * 9;
+        }
+        a.lig_cur = cx->ws.lig_cur; a.tr_update = cx->ws.tr_update; a.rot_update = cx->ws.rot_update;
+        HIPCHK(launch_start_pose(a, B, cx->stream));
+        return DFM_OK;
+    };
+    return sample_impl(cx, B, num_steps, eps, tr_noise_scale, rot_noise_scale, flags, seed, inj, out, p->t_begin, start);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -29,7 +29,7 @@ __host__ __device__ inline u32x4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c
 __host__ __device__ inline float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 // RNG stream ids (counter word 3)
-enum : uint32_t { RNG_EDGES = 1, RNG_NOISE = 2, RNG_INIT = 3 };
+enum : uint32_t { RNG_EDGES = 1, RNG_NOISE = 2, RNG_INIT = 3, RNG_START = 4 };
 
 // ---- bf16 <-> f32 (round to nearest even) -----------------------------------------------------------
 __host__ __device__ inline uint16_t f2bf(float f)

@@ -323,6 +323,22 @@ hipError_t launch_init_pose(const float *rec_pos, const float *lig0, int B, int 
 hipError_t launch_clash_force(const float *rec_pos, int B, int R, int L, float *lig_cur, float *tr_update,
                               hipStream_t s);
 
+// local refinement (kernels_geom.hip: k_igso3_cdf / k_start_pose; include/dfmdock_amd.h: dfm_refine)
+constexpr int IGSO3_N = 1000;      // entries of an IGSO(3) cdf table = sigma grid points = truncation of the expansion (the reference's 1000 / 1000 / 1000)
+hipError_t launch_igso3_cdf(double sigma, double *cdf /*[IGSO3_N]*/, hipStream_t s);
+struct StartArgs {
+    const float *start;         // the start pose(s): [L][9] with start_bstride 0 (the stored ligand pose) or [B][L][9]
+    int64_t start_bstride;
+    int L, all_atoms, perturb;
+    const double *cdf;          // [IGSO3_N] table of the sigma index of t_begin (unused when perturb == 0)
+    double sigma_r3;            // sigma of the R^3 diffuser at t_begin
+    const float *u_inj, *axis_inj, *tr_inj;      // [B], [B][3], [B][3] injected draws or nullptr (Philox stream RNG_START)
+    uint32_t seed_lo, seed_hi;
+    float *lig_cur;             // [B][L][9] or nullptr: evaluation mode (the updates only)
+    float *tr_update, *rot_update;      // [B][3] the noise translation / rotation (axis-angle)
+};
+hipError_t launch_start_pose(const StartArgs &a, int B, hipStream_t s);
+
 // interface distance restraints (kernels_geom.hip: k_restraint; include/dfmdock_amd.h: dfm_complex_set_restraints)
 constexpr int RS_MAX_GROUPS = 4096;       // per-group arg-min in LDS (12 B per group)
 constexpr int RS_MAX_PAIRS = 1 << 20;

@@ -494,6 +494,148 @@ hipError_t launch_init_pose(const float *rec_pos, const float *lig0, int B, int 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Local refinement (include/dfmdock_amd.h: dfm_refine; definition: dfmdock_amd/refine.py).
+//
+// k_igso3_cdf: the reference's 1000-entry cdf of the IGSO(3) rotation angle at one sigma (so3_diffuser.py:24-85,:165-177), float64:
+// omega_k = k pi / 1000, expansion = sum_{l<1000} (2l+1) exp(-l(l+1) sigma^2 / 2) sin((l+1/2) omega) / sin(omega / 2),
+// pdf = expansion (1 - cos omega) / pi, cdf = cumsum(pdf) / 1000 * pi.  One workgroup: the 1000 factors of l go to LDS once, thread k
+// sums its omega_k over l in ascending order, then a block scan.  10^6 float64 sines per NEW sigma index (the table is cached on the
+// model handle), on no per-step path.
+__global__ __launch_bounds__(1024) void k_igso3_cdf(double sigma, double *__restrict__ cdf)
+{
+    __shared__ double s_coef[IGSO3_N];
+    __shared__ double s_wave[16];
+    const int k = threadIdx.x, lane = k & 63, w = k >> 6;
+    if (k < IGSO3_N) {
+        const double l = (double)k;
+        s_coef[k] = (2.0 * l + 1.0) * exp((-l * (l + 1.0)) * (sigma * sigma) / 2.0);
+    }
+    __syncthreads();
+    double x = 0.0;
+    if (k < IGSO3_N) {
+        const double pi = 3.14159265358979323846;
+        const double om = k == IGSO3_N - 1 ? pi : (double)(k + 1) * (pi / (double)IGSO3_N);      // np.linspace(0, pi, 1001)[1:]
+        const double lo = sin(om / 2.0);
+        double e = 0.0;
+#pragma unroll 1
+        for (int l = 0; l < IGSO3_N; ++l) e += s_coef[l] * sin(om * ((double)l + 0.5)) / lo;
+        x = e * (1.0 - cos(om)) / pi;
+    }
+    // inclusive scan: within the wave, then the totals of the waves before
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double v = __shfl_up(x, d, 64);
+        if (lane >= d) x += v;
+    }
+    if (lane == 63) s_wave[w] = x;
+    __syncthreads();
+    double base = 0.0;
+    for (int i = 0; i < w; ++i) base += s_wave[i];
+    if (k < IGSO3_N) cdf[k] = (base + x) / (double)IGSO3_N * 3.14159265358979323846;
+}
+
+hipError_t launch_igso3_cdf(double sigma, double *cdf, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_igso3_cdf, dim3(1), dim3(1024), 0, s, sigma, cdf);
+    return hipGetLastError();
+}
+
+// k_start_pose, the sibling of k_init_pose: the forward marginal of a given pose at t_begin (score_model_mlsb.py:65-94).  One workgroup
+// per trajectory.  Rotation angle: inverse cdf by the first-crossing rule (k = the first index with cdf[k] >= u; 0 -> omega_1; none ->
+// pi; else linear between the two entries) - every thread tests its entries and the workgroup keeps the smallest index, which is the
+// rule itself also where the table's tail is not monotone; axis: a normalised N(0, I) draw; translation: sigma_r3(t) z.  Draws: Philox
+// stream RNG_START (or injected).  Applied like a step of the sampler (k_heads): x = ((x - c) R^T + c) + tr about the CA centroid (all
+// backbone atoms: second family).  lig_cur == nullptr: evaluation mode, the updates only (dfm_forward_marginal).  perturb == 0: the
+// pose is copied bit for bit and the updates are zero.
+__global__ __launch_bounds__(256) void k_start_pose(StartArgs p)
+{
+    __shared__ double scratch[8];
+    __shared__ float sh[16];      // c[3], tr[3], R[9]
+    __shared__ float s_draw[8];   // u, axis[3], z[3]
+    __shared__ int s_first;
+    const int b = blockIdx.x, L = p.L;
+    const float *src = p.start + (size_t)b * p.start_bstride;
+    float *out = p.lig_cur ? p.lig_cur + (size_t)b * L * 9 : nullptr;
+    if (!p.perturb) {
+        if (out) for (int a = threadIdx.x; a < L * 9; a += blockDim.x) out[a] = src[a];
+        if (threadIdx.x < 3) { p.tr_update[b * 3 + threadIdx.x] = 0.0f; p.rot_update[b * 3 + threadIdx.x] = 0.0f; }
+        return;
+    }
+    if (threadIdx.x == 0) {
+        const u32x4 r1 = philox4x32((uint32_t)b, 0u, 0u, RNG_START, p.seed_lo, p.seed_hi);
+        const u32x4 r2 = philox4x32((uint32_t)b, 1u, 0u, RNG_START, p.seed_lo, p.seed_hi);
+        const u32x4 r3 = philox4x32((uint32_t)b, 2u, 0u, RNG_START, p.seed_lo, p.seed_hi);
+        const u32x4 r4 = philox4x32((uint32_t)b, 3u, 0u, RNG_START, p.seed_lo, p.seed_hi);
+        s_draw[0] = p.u_inj ? p.u_inj[b] : u01(r1.x);
+        s_draw[1] = p.axis_inj ? p.axis_inj[b * 3] : normal_from(r2.x, r2.y);
+        s_draw[2] = p.axis_inj ? p.axis_inj[b * 3 + 1] : normal_from(r2.z, r2.w);
+        s_draw[3] = p.axis_inj ? p.axis_inj[b * 3 + 2] : normal_from(r3.x, r3.y);
+        s_draw[4] = p.tr_inj ? p.tr_inj[b * 3] : normal_from(r3.z, r3.w);
+        s_draw[5] = p.tr_inj ? p.tr_inj[b * 3 + 1] : normal_from(r4.x, r4.y);
+        s_draw[6] = p.tr_inj ? p.tr_inj[b * 3 + 2] : normal_from(r4.z, r4.w);
+        s_first = IGSO3_N;
+    }
+    __syncthreads();
+    const double u = (double)s_draw[0];
+    int first = IGSO3_N;
+    for (int k = threadIdx.x; k < IGSO3_N; k += blockDim.x)
+        if (p.cdf[k] >= u) { first = k; break; }
+    if (first < IGSO3_N) atomicMin(&s_first, first);
+    double l0 = 0, l1 = 0, l2 = 0;
+    if (out) {
+        if (p.all_atoms) {
+            for (int q = threadIdx.x; q < L * 3; q += blockDim.x) { l0 += src[q * 3]; l1 += src[q * 3 + 1]; l2 += src[q * 3 + 2]; }
+        } else {
+            for (int q = threadIdx.x; q < L; q += blockDim.x) { l0 += src[q * 9 + 3]; l1 += src[q * 9 + 4]; l2 += src[q * 9 + 5]; }
+        }
+        l0 = block_sum_d(l0, scratch); l1 = block_sum_d(l1, scratch); l2 = block_sum_d(l2, scratch);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double pi = 3.14159265358979323846, dw = pi / (double)IGSO3_N;
+        const int k = s_first;
+        double ang;
+        if (k >= IGSO3_N) ang = pi;
+        else if (k == 0) ang = dw;
+        else {
+            const double w0 = (double)k * dw, w1 = k == IGSO3_N - 1 ? pi : (double)(k + 1) * dw, c0 = p.cdf[k - 1], c1 = p.cdf[k];
+            ang = (w1 - w0) / (c1 - c0) * (u - c0) + w0;
+        }
+        const double ax = s_draw[1], ay = s_draw[2], az = s_draw[3];
+        const double n = sqrt(ax * ax + ay * ay + az * az);
+        const float rot[3] = {(float)(ax / n * ang), (float)(ay / n * ang), (float)(az / n * ang)};
+        const int nl = p.all_atoms ? L * 3 : L;
+        float Rm[9];
+        aa_to_mat(rot, Rm);
+        for (int q = 0; q < 9; ++q) sh[6 + q] = Rm[q];
+        sh[0] = (float)(l0 / nl); sh[1] = (float)(l1 / nl); sh[2] = (float)(l2 / nl);
+        for (int q = 0; q < 3; ++q) {
+            const float tr = (float)(p.sigma_r3 * (double)s_draw[4 + q]);
+            sh[3 + q] = tr;
+            p.tr_update[b * 3 + q] = tr;
+            p.rot_update[b * 3 + q] = rot[q];
+        }
+    }
+    if (!out) return;
+    __syncthreads();
+    for (int a = threadIdx.x; a < L * 3; a += blockDim.x) {
+        const float v0 = src[a * 3] - sh[0], v1 = src[a * 3 + 1] - sh[1], v2 = src[a * 3 + 2] - sh[2];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            float s = 0;
+            s += v0 * sh[6 + r * 3]; s += v1 * sh[6 + r * 3 + 1]; s += v2 * sh[6 + r * 3 + 2];
+            out[a * 3 + r] = (s + sh[r]) + sh[3 + r];
+        }
+    }
+}
+
+hipError_t launch_start_pose(const StartArgs &a, int B, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_start_pose, dim3(B), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // get_clash_force (inference_base.py:366-384), closed form of the reference's autograd:
 // E = -5 * sum_{d<4} (4-d)^1.5 / (0.75 d) over all backbone-atom pairs; the ligand is shifted rigidly
 // by the mean over its 3L atoms of dE/dx.

@@ -343,7 +343,8 @@ def _gather_rows(rows, world):
 
 def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_steps=40, seed=0, precision="mfma16",
               out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", restraints=None,
-              restraint_rank="satisfied", restraint_params=None, top_k=None, cluster_radius=4.0, cluster_rule="energy", **sampler_kw):
+              restraint_rank="satisfied", restraint_params=None, top_k=None, cluster_radius=4.0, cluster_rule="energy", refine_t=None,
+              refine_samples=8, **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
     pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
     the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
@@ -357,7 +358,14 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     `top_k`: also cluster the trajectories by ligand RMSD (cluster_trajectories: `cluster_radius` A, rule `cluster_rule`) with the key
     that picks output.pdb - energy, or under restraint_rank "satisfied" the most satisfied groups and then energy - and return up to
     top_k cluster centres as `models` [{rank, index, energy, cluster_size}], written as <out_pdb stem>_<rank>.pdb.  Under rule "energy"
-    model 1 is the output.pdb pose."""
+    model 1 is the output.pdb pose.
+
+    `refine_t` (needs top_k): the centres are then refined locally from t_begin = refine_t, `refine_samples` trajectories each, in one
+    batched call (refine_models); the models gain `refined_energy` and their files hold the refined poses.  output.pdb is unchanged."""
+    if refine_t is not None and top_k is None:
+        raise ValueError("refine_t refines the cluster centres: it needs top_k")
+    if refine_t is not None and int(refine_samples) < 1:
+        raise ValueError("refine_samples must be >= 1")
     if restraints is not None and restraint_rank not in ("satisfied", "energy"):
         raise ValueError(f"restraint_rank must be 'satisfied' or 'energy', got {restraint_rank!r}")
     if top_k is not None:
@@ -372,7 +380,8 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     precision, chk = checked_precision(gx, precision, "pair", selfcheck, on_selfcheck_fail, seed=seed)
     if restraints is not None:
         return _dock_pair_restrained(gx, model, rec, lig, restraints, restraint_rank, restraint_params, num_samples, num_steps, seed,
-                                     precision, chk, out_pdb, max_batch, sampler_kw, clu)
+                                     precision, chk, out_pdb, max_batch, sampler_kw, clu,
+                                     None if refine_t is None else (float(refine_t), int(refine_samples)))
     best = None
     done = 0
     cols = {k: [] for k in ("energy", "rot_update", "tr_update")}
@@ -387,7 +396,8 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
                 cols[c].append(r[c])
         done += b
     lig0 = gx.lig_pos0
-    gx.close()
+    if refine_t is None:
+        gx.close()
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], best[1], best[2],
                                        center="all_atoms" if model.hp.family == 1 else "ca")
     if out_pdb:
@@ -398,7 +408,64 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     if clu is not None:
         cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
         res.update(_top_models(model, rec, lig, lig0, cols, cols["energy"], clu, out_pdb))
+        if refine_t is not None:
+            refine_models(model, gx, rec, lig, lig0, cols, res["models"], float(refine_t), int(refine_samples), num_steps, seed, precision,
+                          out_pdb, **sampler_kw)
+            gx.close()
     return res
+
+
+def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
+                out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", perturb=True, restraints=None,
+                restraint_params=None, **sampler_kw):
+    """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories
+    start from that pose noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps
+    down from t_begin; like dock_pair the minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns
+    dock_pair's dict plus `t_begin`, `index` and `trajectories` (every trajectory's energy, rot_update, tr_update).  `restraints`
+    ([restraints.RestraintGroup]) turns the restraint step on (DFM_F_RESTRAINTS)."""
+    gx = engine.Complex(model, rec_x, lig_x, rec["bb_coords"], lig["bb_coords"])
+    precision, chk = checked_precision(gx, precision, "pair", selfcheck, on_selfcheck_fail, seed=seed)
+    if restraints is not None:
+        gx.set_restraints(restraints, restraint_params)
+    cols = {k: [] for k in ("energy", "rot_update", "tr_update")}
+    done = 0
+    while done < num_samples:
+        b = min(max_batch, num_samples - done)
+        r = gx.refine(B=b, t_begin=t_begin, perturb=perturb, num_steps=num_steps, seed=seed + done, restraints=restraints is not None,
+                      **engine.precision_kwargs(precision), **sampler_kw)
+        for c in cols:
+            cols[c].append(r[c])
+        done += b
+    gx.close()
+    cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
+    k = int(np.argmin(cols["energy"]))      # the first minimum wins, as in dock_pair
+    lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k],
+                                       center="all_atoms" if model.hp.family == 1 else "ca")
+    if out_pdb:
+        pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa)
+    return {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
+            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, "index": k, "t_begin": float(t_begin), "trajectories": cols}
+
+
+def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps, seed, precision, out_pdb, restraints=False, **sampler_kw):
+    """dock_pair's second stage (`refine_t`): the K cluster centres of `models` refined in ONE dfm_refine call - B = K n trajectories,
+    start_pos = each centre's backbone n times.  Every model gains `refined_energy` (the minimum over its n trajectories) and
+    `refined_index`; <out_pdb stem>_<rank>.pdb becomes that refined pose (the centre's rigid motion, then the refinement's)."""
+    from .cluster import rebuild_backbone
+    K = len(models)
+    cen = [m["index"] for m in models]
+    start = rebuild_backbone(lig0, cols["rot_update"][cen], cols["tr_update"][cen], model.hp.family)      # [K,L,3,3]
+    r = gx.refine(B=K * n, t_begin=t_begin, start_pos=np.repeat(start, n, 0), num_steps=num_steps, seed=seed, restraints=restraints,
+                  **engine.precision_kwargs(precision), **sampler_kw)
+    center = "all_atoms" if model.hp.family == 1 else "ca"
+    for k, m in enumerate(models):
+        j = k * n + int(np.argmin(r["energy"][k * n:(k + 1) * n]))
+        m.update(refined_energy=float(r["energy"][j]), refined_index=j - k * n)
+        if out_pdb:
+            aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][cen[k]], cols["tr_update"][cen[k]], center=center)
+            aa = pdbio.apply_pose_all_atom(aa, start[k], r["rot_update"][j], r["tr_update"][j], center=center)
+            pdbio.write_complex_pdb(model_path(out_pdb, m["rank"]), list(rec["atoms"]), lig["atoms"], aa)
+    return models
 
 
 def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb):
@@ -422,7 +489,7 @@ def model_path(out_pdb, rank):
 
 
 def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_samples, num_steps, seed, precision, chk, out_pdb, max_batch,
-                          sampler_kw, clu=None):
+                          sampler_kw, clu=None, refine=None):
     from . import restraints as RS
     gx.set_restraints(restraints, params)
     cols = {k: [] for k in ("energy", "restraint_energy", "restraints_satisfied", "rot_update", "tr_update")}
@@ -436,7 +503,8 @@ def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_sam
             cols[k].append(v)
         done += b
     lig0 = gx.lig_pos0
-    gx.close()
+    if refine is None:
+        gx.close()
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
     k = RS.rank_key(cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else int(np.argmin(cols["energy"]))
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k],
@@ -452,4 +520,8 @@ def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_sam
         from .cluster import satisfied_key
         key = satisfied_key(cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else cols["energy"]
         res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb))
+        if refine is not None:
+            refine_models(model, gx, rec, lig, lig0, cols, res["models"], refine[0], refine[1], num_steps, seed, precision, out_pdb,
+                          restraints=True, **sampler_kw)
+            gx.close()
     return res

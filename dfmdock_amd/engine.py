@@ -155,6 +155,16 @@ class Model:
         return {"n_clusters": int(n.value), "center": center[: n.value].copy(), "size": size[: n.value].copy(), "cluster_of": cluster_of}
 
 
+    def igso3_table(self, t):
+        """The IGSO(3) table `refine` looks rotation angles up in at time t (dfm_igso3_table; definition: refine.sigma_index /
+        refine.igso3_cdf): {sigma_idx, sigma, cdf [1000] float64}, computed on the GPU once per sigma index."""
+        idx, sg = C.c_int(0), C.c_double(0)
+        cdf = np.zeros(1000, np.float64)
+        L.check(L.lib().dfm_igso3_table(self._h, float(t), C.byref(idx), C.byref(sg), cdf.ctypes.data_as(C.POINTER(C.c_double))),
+                "dfm_igso3_table")
+        return {"sigma_idx": idx.value, "sigma": sg.value, "cdf": cdf}
+
+
 def pose_last_timing():
     """(k_pose_dist ms, clustering kernels ms) of this thread's last pose_rmsd / pose_cluster call (dfm_pose_last_timing)."""
     a, b = C.c_double(0), C.c_double(0)
@@ -294,7 +304,12 @@ class Complex:
         head on every step (DFM_F_STEP_ENERGY - the step evaluations then run their last layer in full); step_energy=False keeps
         the step evaluations exactly as an untraced call runs them (ligand-only last layer, no energy in trace_scores[:, :-1]).
         restraints=True: DFM_F_RESTRAINTS (the restraint step of set_restraints after every update; nothing without a stored set)."""
-        mfma16 = mfma16 or bf16
+        return self._trajectories(None, B, num_steps, eps, tr_noise_scale, rot_noise_scale, noise_annealing, use_clash_force, ode, seed,
+                                  mfma16 or bf16, inject, trace, profile, f16, bf16_ops, l0_table, graph, step_energy, restraints)
+
+    def _trajectories(self, refine, B, num_steps, eps, tr_noise_scale, rot_noise_scale, noise_annealing, use_clash_force, ode, seed, mfma16,
+                      inject, trace, profile, f16, bf16_ops, l0_table, graph, step_energy, restraints):
+        """dfm_sample (refine None) or dfm_refine (refine = (RefineParamsC, RefineInjectC or None, arrays to keep alive))."""
         if step_energy is None:
             step_energy = bool(trace)
         Lg, N, K, S = self.L, self.N, self.K, int(num_steps)
@@ -327,9 +342,62 @@ class Complex:
                 (L.DFM_F_PROFILE if profile else 0) | (L.DFM_F_STEP_ENERGY if step_energy else 0) | (L.DFM_F_F16 if f16 else 0) | \
                 (L.DFM_F_BF16_OPS if bf16_ops else 0) | (0 if l0_table else L.DFM_F_NO_L0_TABLE) | \
                 (L.DFM_F_GRAPH if graph else 0) | (L.DFM_F_RESTRAINTS if restraints else 0)
+        if refine is not None:
+            par, rinj, _alive = refine
+            rc = L.lib().dfm_refine(self._h, int(B), S, float(eps), float(tr_noise_scale), float(rot_noise_scale), flags, int(seed),
+                                    C.byref(par), C.byref(inj) if inj is not None else None,
+                                    C.byref(rinj) if rinj is not None else None, C.byref(out))
+            L.check(rc, "dfm_refine")
+            return o
         rc = L.lib().dfm_sample(self._h, int(B), S, float(eps), float(tr_noise_scale), float(rot_noise_scale), flags,
                                 int(seed), C.byref(inj) if inj is not None else None, C.byref(out))
         L.check(rc, "dfm_sample")
+        return o
+
+    @staticmethod
+    def _refine_inject(refine_inject, B):
+        if not refine_inject:
+            return None, []
+        rinj, keep = L.RefineInjectC(), []
+        for k, shp in {"u_angle": (B,), "axis_draw": (B, 3), "tr_draw": (B, 3)}.items():
+            if refine_inject.get(k) is not None:
+                a = _f32(refine_inject[k]).reshape(shp)
+                keep.append(a)
+                setattr(rinj, k, _p(a))
+        return rinj, keep
+
+    def refine(self, B=1, t_begin=0.1, start_pos=None, perturb=True, num_steps=40, eps=1e-3, tr_noise_scale=0.5, rot_noise_scale=0.5,
+               noise_annealing=False, use_clash_force=False, ode=False, seed=0, mfma16=False, inject=None, refine_inject=None, trace=False,
+               profile=False, f16=False, bf16_ops=False, bf16=False, l0_table=True, graph=False, step_energy=None, restraints=False):
+        """Local refinement (dfm_refine; definition: dfmdock_amd/refine.py): B trajectories that start from `start_pos` [B,L,3,3] (one
+        pose per trajectory; [L,3,3]: the same for all; None: the stored ligand pose), noised with the reference's forward process at
+        `t_begin` (perturb=False: the pose itself), and run `sample`'s steps over linspace(t_begin, eps, num_steps).  Keywords and the
+        returned dict are `sample`'s; rot_update / tr_update map each trajectory's START pose onto its final pose.  `inject`: z_rot,
+        z_tr, edges as for `sample` (R0 / tr_draw are randomize_pose's: ValueError); `refine_inject`: u_angle [B], axis_draw [B,3],
+        tr_draw [B,3] of the start."""
+        par, keep = L.RefineParamsC(), []
+        par.t_begin, par.perturb = float(t_begin), int(bool(perturb))
+        if start_pos is not None:
+            sp = _f32(start_pos)
+            if sp.shape in ((self.L, 3, 3), (self.L, 9)):
+                sp = np.repeat(sp.reshape(1, self.L, 9), B, 0)
+            if sp.size != B * self.L * 9:
+                raise ValueError(f"start_pos must be [B,{self.L},3,3] (or one [{self.L},3,3] pose)")
+            sp = np.ascontiguousarray(sp.reshape(B, self.L, 9))
+            keep.append(sp)
+            par.start_pos = _p(sp)
+        rinj, k2 = self._refine_inject(refine_inject, B)
+        return self._trajectories((par, rinj, keep + k2), B, num_steps, eps, tr_noise_scale, rot_noise_scale, noise_annealing,
+                                  use_clash_force, ode, seed, mfma16 or bf16, inject, trace, profile, f16, bf16_ops, l0_table, graph,
+                                  step_energy, restraints)
+
+    def forward_marginal(self, B, t, seed=0, refine_inject=None):
+        """The draws `refine` starts from at t_begin = t (dfm_forward_marginal, the start kernel in evaluation mode): {rot [B,3]
+        axis-angle, tr [B,3]}."""
+        rinj, keep = self._refine_inject(refine_inject, B)
+        o = dict(rot=np.zeros((B, 3), np.float32), tr=np.zeros((B, 3), np.float32))
+        L.check(L.lib().dfm_forward_marginal(self._h, int(B), float(t), int(seed), C.byref(rinj) if rinj is not None else None,
+                                             _p(o["rot"]), _p(o["tr"])), "dfm_forward_marginal")
         return o
 
     def selfcheck(self, n_eval=4, t=None, seed=0, precision="mfma16", bf16_ops=False):

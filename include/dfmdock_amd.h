@@ -193,6 +193,22 @@ typedef struct {
     float *init_pose;     /* [B,L,9]        pose after randomize_pose                    */
 } dfm_traj_out;
 
+/* Local refinement (dfm_refine): where the trajectories start.  The pose is noised with the reference's forward process at t_begin
+ * (score_model_mlsb.py:65-94: IGSO(3) rotation about the ligand centroid + N(0, sigma_r3(t_begin)^2) translation; dfmdock_amd/refine.py
+ * is the float64 definition) and the reverse SDE runs over linspace(t_begin, eps, num_steps). */
+typedef struct {
+    float t_begin;            /* eps < t_begin <= 1                                                    */
+    int perturb;              /* 1: forward marginal at t_begin (default); 0: start at the pose itself  */
+    const float *start_pos;   /* [B,L,9] one start pose per trajectory, or NULL: the stored ligand pose */
+} dfm_refine_params;
+
+/* Injected draws of the start of dfm_refine / dfm_forward_marginal (every pointer may be NULL = draw natively with Philox) */
+typedef struct {
+    const float *u_angle;     /* [B]   uniform draw of the rotation angle                               */
+    const float *axis_draw;   /* [B,3] N(0,1) draws of the axis (normalised by the kernel)              */
+    const float *tr_draw;     /* [B,3] N(0,1) draws of the translation                                  */
+} dfm_refine_inject;
+
 typedef struct {
     double edge_kernel_ms;    /* summed HIP-event time of the per-edge message kernel     */
     int64_t edge_kernel_launches;
@@ -346,6 +362,25 @@ int dfm_score(dfm_complex *cx, int B, const float *lig_pos, const float *t, cons
 /* B independent trajectories of the Euler-Maruyama sampler */
 int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, float tr_noise_scale, float rot_noise_scale,
                uint32_t flags, uint64_t seed, const dfm_inject *inj_or_null, dfm_traj_out *out);
+
+/* Local refinement: B trajectories that start from a given pose instead of randomize_pose.  Trajectory b starts from
+ * p->start_pos[b] (NULL: the stored ligand pose of the complex), noised with the forward marginal at p->t_begin unless p->perturb is 0,
+ * and runs dfm_sample's steps over linspace(t_begin, eps, num_steps) (t_begin = 1: dfm_sample's grid bit for bit); flags, the noise
+ * scales and inj->z_rot / z_tr / edges mean what they mean for dfm_sample.  rot_update / tr_update start as the noise rotation /
+ * translation and are composed as in dfm_sample: they map the START pose of a trajectory onto its final pose; init_pose is the pose
+ * after the start.  A start_pos[b] that is a rigid motion of the stored ligand pose hits the layer-0 message table; any other conformer
+ * misses edge by edge and goes through the edge model (the rule of DFM_F_L0_TABLE).  DFM_E_INVALID, nothing enqueued: p NULL, t_begin
+ * NaN, <= eps or > 1, num_steps < 2, inj->R0 or inj->tr_draw set (they belong to randomize_pose; the start is injected through rinj). */
+int dfm_refine(dfm_complex *cx, int B, int num_steps, float eps, float tr_noise_scale, float rot_noise_scale, uint32_t flags,
+               uint64_t seed, const dfm_refine_params *p, const dfm_inject *inj_or_null, const dfm_refine_inject *rinj_or_null,
+               dfm_traj_out *out);
+/* The draws dfm_refine starts from at t_begin = t, by the same kernel: rotation vectors rot [B,3] (axis-angle) and translations
+ * tr [B,3] of B trajectories with `seed` (or the injected draws).  0 <= t <= 1. */
+int dfm_forward_marginal(dfm_complex *cx, int B, float t, uint64_t seed, const dfm_refine_inject *rinj_or_null, float *rot, float *tr);
+/* The IGSO(3) table dfm_refine looks rotation angles up in at time t: the index of sigma_so3(t) on the reference's 1000-point sigma
+ * grid (the grid value below it, so3_diffuser.py:199-206), that sigma, and the cdf [1000] over omega_k = k pi / 1000 (float64, computed
+ * on the device once per index and cached on the model handle).  Any output pointer may be NULL. */
+int dfm_igso3_table(dfm_model *m, double t, int *sigma_idx, double *sigma, double *cdf);
 
 int dfm_get_profile(const dfm_complex *cx, dfm_profile *p);
 
