@@ -42,6 +42,7 @@ EXPORTS = [
     "dfm_score", "dfm_sample", "dfm_get_profile", "dfm_diffusion_coef", "dfm_complex_selfcheck", "dfm_trim_cache",
     "dfm_complex_set_restraints", "dfm_restraint_eval", "dfm_pose_rmsd", "dfm_pose_cluster", "dfm_pose_last_timing",
     "dfm_refine", "dfm_forward_marginal", "dfm_igso3_table",
+    "dfm_native_create", "dfm_native_destroy", "dfm_native_info", "dfm_pose_metrics", "dfm_metrics_last_timing",
 ]
 
 
@@ -100,6 +101,10 @@ class RestraintParamsC(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("k_tr", "k_rot", "max_tr", "max_rot", "t_start")]
 
 
+class MetricsOutC(C.Structure):
+    _fields_ = [(n, C.POINTER(C.c_double)) for n in ("c_rmsd", "i_rmsd", "l_rmsd", "fnat", "dockq")] + [("n_recovered", I32P)]
+
+
 _lib = None
 
 
@@ -147,6 +152,13 @@ def lib():
     L.dfm_pose_cluster.argtypes = [C.c_void_p, C.c_int, C.c_int, F32P, I32P, C.c_int, F32P, C.c_float, C.c_int, C.c_int, I32P, I32P, I32P,
                                    I32P]
     L.dfm_pose_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_native_create.argtypes = [C.c_void_p, F32P, F32P, C.c_int, C.c_int, C.c_float, C.c_float]
+    L.dfm_native_create.restype = C.c_void_p
+    L.dfm_native_destroy.argtypes = [C.c_void_p]
+    L.dfm_native_destroy.restype = None
+    L.dfm_native_info.argtypes = [C.c_void_p, I32P, I32P, I32P, I32P, I32P, I32P]
+    L.dfm_pose_metrics.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.POINTER(MetricsOutC)]
+    L.dfm_metrics_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_trim_cache.argtypes = [C.c_int]
     L.dfm_trim_cache.restype = C.c_longlong
     L.dfm_diffusion_coef.argtypes = [C.POINTER(HParamsC), C.c_int, C.c_double, C.POINTER(C.c_double),

@@ -9,6 +9,8 @@
     python -m dfmdock_amd sweep ... --cluster-radius R [--top-k 10] [--cluster-rule energy|size]
     python -m dfmdock_amd refine REC.pdb LIG.pdb --ckpt model_0.ckpt --features F.npz --t-begin 0.1 [--num-samples 32] [--no-perturb]
     python -m dfmdock_amd dock ... --top-k K --refine-t T [--refine-samples 8]
+    python -m dfmdock_amd dock|refine ... --native NATIVE_REC.pdb NATIVE_LIG.pdb
+    python -m dfmdock_amd sweep ... --metrics gpu [--step-metrics steps.csv]
 
   dock       <- src/inference_single.py:1-12 -> inference() (src/inference_base.py:601-670): num_samples (120) trajectories of
                 num_steps (40), the minimum-energy one applied to the all-atom ligand, `output.pdb` written, {"energy": E} printed.
@@ -31,6 +33,13 @@
              the pose the two PDB files are in is noised at --t-begin and the sampler runs down from there (dfm_refine); same output
              contract as `dock`.  `dock --top-k K --refine-t T` refines the K cluster centres in one batched call; <out stem>_k.pdb is
              then the minimum-energy refined pose of centre k and `models` carries both energies.
+  metrics    c_rmsd, i_rmsd, l_rmsd, fnat and DockQ as the reference's compute_metrics defines them (src/utils/metrics.py:3-121), batched
+             on the GPU (dfm_pose_metrics).  `dock / refine --native REC.pdb LIG.pdb` add the metrics of the kept pose (of every --top-k
+             model, and of each centre before and after --refine-t) to the result line; the native is matched to the input residue by
+             residue and may be in any frame.  `sweep --metrics gpu` evaluates the final poses on the GPU instead of the host (same
+             definition; the CSV differs from the host's in the last digits), `sweep --step-metrics FILE.csv` (implies --metrics gpu)
+             writes the metrics after EVERY step of every trajectory and adds, per complex, the step at which the minimum-energy
+             trajectory first reaches DockQ >= 0.23 and the best DockQ seen along any trajectory to the summary.
   selfcheck  no reference counterpart: dfm_complex_selfcheck on the pair (what `dock` and `sweep` run once per complex anyway).
 
 --ckpt takes the Lightning checkpoint the reference loads (src/inference_base.py:611-616; read without Lightning / omegaconf by
@@ -47,6 +56,11 @@ import sys
 import numpy as np
 
 DOCKQ_THRESHOLDS = (("acceptable", 0.23), ("medium", 0.49), ("high", 0.80))      # CAPRI classes by DockQ
+
+
+def _add_native(p):
+    p.add_argument("--native", nargs=2, default=None, metavar=("REC.pdb", "LIG.pdb"),
+                   help="native complex (same residues as the input, any frame): add c_rmsd / i_rmsd / l_rmsd / fnat / DockQ to the result")
 
 
 def _add_common(p):
@@ -84,6 +98,7 @@ def build_parser():
     d.add_argument("--refine-t", type=float, default=None, metavar="T",
                    help="with --top-k: refine every cluster centre locally from t_begin = T (one batched call)")
     d.add_argument("--refine-samples", type=int, default=8, metavar="n", help="with --refine-t: trajectories per cluster centre")
+    _add_native(d)
     _add_common(d)
     r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)")
     r.add_argument("pdb_1", help="receptor PDB")
@@ -95,6 +110,7 @@ def build_parser():
     r.add_argument("--out", default="output.pdb")
     r.add_argument("--json", default=None, help="also write the result line to this file")
     r.add_argument("--restraints", default=None, help="interface restraint file (as for dock)")
+    _add_native(r)
     _add_common(r)
     s = sub.add_parser("sweep", help="sample every complex of a DB5-style directory (inference_mlsb.py run_sampling)")
     s.add_argument("--db5", required=True, help="directory of <id>.pt files (+ optional test.txt with the ids to run)")
@@ -111,6 +127,10 @@ def build_parser():
                    help="cluster every complex's trajectories by ligand RMSD (adds cluster / is_center to the CSV and a top-K success rate)")
     s.add_argument("--top-k", type=int, default=10, metavar="K", help="with --cluster-radius: clusters per complex (default 10)")
     s.add_argument("--cluster-rule", default="energy", choices=["energy", "size"], help="with --cluster-radius: clustering rule")
+    s.add_argument("--metrics", default="host", choices=["host", "gpu"],
+                   help="where the final poses are scored: host (default, numpy) or gpu (dfm_pose_metrics, one call per complex)")
+    s.add_argument("--step-metrics", default=None, metavar="FILE.csv",
+                   help="also write the metrics after every step of every trajectory (implies --metrics gpu)")
     _add_common(s)
     c = sub.add_parser("selfcheck", help="fp32-vs-16-bit check + fp16 range telemetry of one pair")
     c.add_argument("pdb_1")
@@ -126,6 +146,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.cmd == "dock" and args.refine_t is not None and args.top_k is None:
         ap.error("--refine-t refines the cluster centres: it needs --top-k")
+    if args.cmd == "sweep" and args.step_metrics is not None:
+        args.metrics = "gpu"
     return args
 
 
@@ -166,6 +188,30 @@ def load_pair(pdb_1, pdb_2, features, lm_embed_dim=1301):
             raise ValueError(f"{features}: {side}_seq does not match the sequence read from the PDB")
         xs.append(x)
     return rec, lig, xs[0], xs[1]
+
+
+def load_native(paths):
+    """--native REC.pdb LIG.pdb -> (receptor [R,3,3], ligand [L,3,3]) backbones, residues as pdbio.backbone_from_atoms keeps them."""
+    from . import pdbio
+    return tuple(np.asarray(pdbio.backbone_from_atoms(pdbio.read_pdb(p))["bb_coords"], np.float32) for p in paths)
+
+
+def step_summary(step_rows, rows, threshold=0.23):
+    """Per complex, from the long table of run_set(step_metrics=True): the step at which the minimum-energy trajectory (what inference()
+    keeps) first reaches DockQ >= threshold (None: never) and the best DockQ seen after any step of any trajectory."""
+    top = {}
+    for r in rows:
+        if r["id"] not in top or (r["energy"], int(r["index"])) < (top[r["id"]]["energy"], int(top[r["id"]]["index"])):
+            top[r["id"]] = r
+    out = {}
+    for s in sorted(step_rows, key=lambda x: (x["id"], int(x["index"]), int(x["step"]))):
+        o = out.setdefault(s["id"], {"top1_first_acceptable_step": None, "best_DockQ_any_step": float("-inf")})
+        if float(s["DockQ"]) > o["best_DockQ_any_step"]:
+            o["best_DockQ_any_step"] = float(s["DockQ"])
+        if s["id"] in top and str(s["index"]) == str(top[s["id"]]["index"]) and o["top1_first_acceptable_step"] is None \
+                and float(s["DockQ"]) >= threshold:
+            o["top1_first_acceptable_step"] = int(s["step"])
+    return out
 
 
 def success_table(rows, top_k=None):
@@ -243,6 +289,8 @@ def cmd_dock(args):
         kw.update(top_k=args.top_k, cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule)
     if args.refine_t is not None:
         kw.update(refine_t=args.refine_t, refine_samples=args.refine_samples)
+    if args.native:
+        kw.update(native=load_native(args.native))
     res = driver.dock_pair(model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                            precision=args.precision, out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
                            on_selfcheck_fail=args.on_selfcheck_fail, **kw)
@@ -257,6 +305,8 @@ def cmd_dock(args):
                     cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule)
     if args.refine_t is not None:
         line.update(refine_t=args.refine_t, refine_samples=args.refine_samples)
+    if args.native:
+        line.update(metrics=res["metrics"])
     print(json.dumps(line), flush=True)
     if args.json:
         extra = {}
@@ -275,6 +325,8 @@ def cmd_refine(args):
     if args.restraints:
         from .restraints import read_restraints
         kw = dict(restraints=read_restraints(args.restraints, rec, lig))
+    if args.native:
+        kw.update(native=load_native(args.native))
     res = driver.refine_pair(model, rec, lig, rec_x, lig_x, t_begin=args.t_begin, num_samples=args.num_samples, num_steps=args.num_steps,
                              seed=args.seed, precision=args.precision, out_pdb=args.out, max_batch=args.max_batch,
                              selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, perturb=not args.no_perturb, **kw)
@@ -282,6 +334,8 @@ def cmd_refine(args):
             "t_begin": res["t_begin"], "perturb": not args.no_perturb, "index": res["index"],
             "rot_update": [float(v) for v in res["rot_update"]], "tr_update": [float(v) for v in res["tr_update"]],
             "selfcheck_ok": None if res["selfcheck"] is None else bool(res["selfcheck"]["ok"])}
+    if args.native:
+        line.update(metrics=res["metrics"], start_metrics=res["start_metrics"])
     print(json.dumps(line), flush=True)
     if args.json:
         with open(args.json, "w") as f:
@@ -326,11 +380,17 @@ def cmd_sweep(args):
     if args.cluster_radius is not None:
         top_k = args.top_k
         rkw.update(cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule, top_k=top_k)
+    steps = []
+    if args.metrics != "host":
+        rkw.update(metrics=args.metrics)
+    if args.step_metrics is not None:
+        rkw.update(step_csv=args.step_metrics, steps_out=steps)
     rows, _ = driver.run_set(model, cxs, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                              precision=args.precision, global_rotation=not args.no_global_rotation, out_csv=args.out_csv,
                              traj_dir=args.traj_dir, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
                              on_selfcheck_fail=args.on_selfcheck_fail, checks_out=checks, **rkw)
     all_rows = driver._gather_rows(rows, world)
+    all_steps = driver._gather_rows(steps, world) if args.step_metrics is not None else []
     all_checks = [c for part in D.gather_objects(checks) for c in part] if world > 1 else checks
     if rank == 0:
         per, table = success_table(all_rows, top_k)
@@ -339,6 +399,9 @@ def cmd_sweep(args):
         if "restraints_by_id" in rkw:
             extra["restraints"] = restraint_summary(all_rows, rkw["restraints_by_id"])
             print(json.dumps({"restraints": extra["restraints"]}), flush=True)
+        if args.step_metrics is not None:
+            extra["step_metrics"] = step_summary(all_steps, all_rows)
+            extra["step_csv"] = os.path.abspath(args.step_metrics)
         if args.summary:
             with open(args.summary, "w") as f:
                 json.dump({"csv": os.path.abspath(args.out_csv), "complexes": per, "success": table, "selfcheck": all_checks,

@@ -1063,6 +1063,200 @@ extern "C" int dfm_pose_last_timing(double *dist_ms, double *cluster_ms)
     return DFM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Docking metrics (kernels_metrics.hip).  A dfm_native holds what the native alone fixes and is read-only after creation; like the
+// clustering calls it is bound to the model handle's device only, and every dfm_pose_metrics call owns its stream and temporaries.
+constexpr size_t METRICS_CHUNK_BYTES = (size_t)64 << 20;      // poses uploaded and evaluated per chunk of a call
+static thread_local double g_metrics_ms[2] = {0.0, 0.0};      // host-to-device copies, kernels of this thread's last dfm_pose_metrics
+
+struct dfm_native {
+    int device = 0, R = 0, L = 0;
+    DevPool pool;      // unbound: released under a device-wide wait, like a model's
+    float *rec = nullptr, *lig = nullptr;
+    uint8_t *frec = nullptr, *flig = nullptr;
+    int32_t *contacts = nullptr;
+    double *rec_const = nullptr;      // the receptor's sums with the native receptor as its own model (k_metrics_reduce)
+    MetricsConst mc = {};
+    std::vector<int32_t> iface_rec, iface_lig, pairs;
+};
+
+extern "C" void dfm_native_destroy(dfm_native *nat)
+{
+    if (!nat) return;
+    DeviceScope ds(nat->device);
+    nat->pool.release();
+    delete nat;
+}
+
+extern "C" dfm_native *dfm_native_create(dfm_model *m, const float *rec_pos, const float *lig_pos, int R, int L, float iface_cutoff,
+                                         float contact_cutoff)
+{
+    auto bad = [](int code, const std::string &msg) -> dfm_native * { (void)fail(code, msg); return nullptr; };
+    if (!m || !rec_pos || !lig_pos) return bad(DFM_E_INVALID, "NULL argument");
+    if (R < 1 || L < 1) return bad(DFM_E_INVALID, "need R >= 1 and L >= 1");
+    if ((int64_t)R * L > ((int64_t)1 << 27)) return bad(DFM_E_INVALID, "R x L exceeds 2^27 residue pairs");
+    if (!std::isfinite(iface_cutoff) || !std::isfinite(contact_cutoff)) return bad(DFM_E_INVALID, "cutoffs must be finite");
+    DeviceScope ds(m->device);
+    if (ds.err != hipSuccess) return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err));
+    dfm_native *nat = new dfm_native;
+    nat->device = m->device; nat->R = R; nat->L = L;
+    hipError_t e = hipSuccess;
+    {
+        PoseCall c;
+        uint8_t *d_pairs = nullptr;
+        std::vector<uint8_t> pm((size_t)R * L);
+        e = c.open();
+        if (e == hipSuccess) e = nat->pool.upload_async(&nat->rec, rec_pos, (size_t)R * 9, c.s);
+        if (e == hipSuccess) e = nat->pool.upload_async(&nat->lig, lig_pos, (size_t)L * 9, c.s);
+        if (e == hipSuccess) e = c.tmp.alloc(&d_pairs, pm.size());
+        if (e == hipSuccess) e = launch_native_pairs(nat->rec, nat->lig, R, L, (double)iface_cutoff, (double)contact_cutoff, d_pairs, c.s);
+        if (e == hipSuccess) e = hipMemcpyAsync(pm.data(), d_pairs, pm.size(), hipMemcpyDeviceToHost, c.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
+        std::vector<uint8_t> fr((size_t)R, 0), fl((size_t)L, 0);
+        MetricsConst &mc = nat->mc;
+        if (e == hipSuccess) {
+            for (int i = 0; i < R; ++i)
+                for (int j = 0; j < L; ++j) {
+                    const uint8_t b = pm[(size_t)i * L + j];
+                    if (b & 1) { fr[(size_t)i] = 1; fl[(size_t)j] = 1; }
+                    if (b & 2) { nat->pairs.push_back(i); nat->pairs.push_back(j); }
+                }
+            for (int i = 0; i < R; ++i) if (fr[(size_t)i]) nat->iface_rec.push_back(i);
+            for (int j = 0; j < L; ++j) if (fl[(size_t)j]) nat->iface_lig.push_back(j);
+            // the shift: the all-atom centroid rounded to fp32 (p - o is then exact in fp64 for every fp32 coordinate near the complex)
+            double cen[3] = {0.0, 0.0, 0.0};
+            for (int i = 0; i < R * 9; ++i) cen[i % 3] += (double)rec_pos[i];
+            for (int i = 0; i < L * 9; ++i) cen[i % 3] += (double)lig_pos[i];
+            for (int k = 0; k < 3; ++k) {
+                const float of = (float)(cen[k] / (3.0 * ((double)R + (double)L)));
+                mc.o[k] = std::isfinite(of) ? (double)of : 0.0;
+            }
+            for (int i = 0; i < R; ++i)
+                for (int k = 0; k < 9; ++k) {
+                    const double q = (double)rec_pos[(size_t)i * 9 + k] - mc.o[k % 3];
+                    mc.T_rec[k % 3] += q;
+                    if (fr[(size_t)i]) mc.T_rec_iface[k % 3] += q;
+                }
+            for (int j = 0; j < L; ++j)
+                for (int k = 0; k < 9; ++k) {
+                    const double q = (double)lig_pos[(size_t)j * 9 + k] - mc.o[k % 3];
+                    mc.T_lig[k % 3] += q;
+                    if (fl[(size_t)j]) mc.T_lig_iface[k % 3] += q;
+                }
+            mc.n_rec = R; mc.n_lig = L;
+            mc.n_rec_iface = (int)nat->iface_rec.size(); mc.n_lig_iface = (int)nat->iface_lig.size();
+            mc.n_contacts = (int)(nat->pairs.size() / 2);
+            mc.rec_moves = 0;
+            mc.contact_cutoff = (double)contact_cutoff;
+            e = nat->pool.upload_async(&nat->frec, fr.data(), fr.size(), c.s);
+        }
+        if (e == hipSuccess) e = nat->pool.upload_async(&nat->flig, fl.data(), fl.size(), c.s);
+        if (e == hipSuccess) e = nat->pool.upload_async(&nat->contacts, nat->pairs.data(), nat->pairs.size(), c.s);
+        if (e == hipSuccess) e = nat->pool.alloc(&nat->rec_const, 24);
+        if (e == hipSuccess) {
+            const MetricsChain rc = {nat->rec, nat->rec, nat->frec, R};
+            e = launch_metrics_reduce(rc, rc, 1, 1, mc, nat->rec_const, c.s);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
+    }      // the call's stream has drained: the host vectors it read may go
+    if (e != hipSuccess) {
+        nat->pool.release();
+        delete nat;
+        return bad(e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP, std::string("dfm_native_create: ") + hipGetErrorString(e));
+    }
+    return nat;
+}
+
+extern "C" int dfm_native_info(const dfm_native *nat, int32_t *n_iface_rec, int32_t *n_iface_lig, int32_t *n_contacts, int32_t *iface_rec,
+                               int32_t *iface_lig, int32_t *contacts)
+{
+    if (!nat) return fail(DFM_E_INVALID, "NULL argument");
+    if (n_iface_rec) *n_iface_rec = (int32_t)nat->iface_rec.size();
+    if (n_iface_lig) *n_iface_lig = (int32_t)nat->iface_lig.size();
+    if (n_contacts) *n_contacts = (int32_t)(nat->pairs.size() / 2);
+    if (iface_rec && !nat->iface_rec.empty()) std::memcpy(iface_rec, nat->iface_rec.data(), nat->iface_rec.size() * sizeof(int32_t));
+    if (iface_lig && !nat->iface_lig.empty()) std::memcpy(iface_lig, nat->iface_lig.data(), nat->iface_lig.size() * sizeof(int32_t));
+    if (contacts && !nat->pairs.empty()) std::memcpy(contacts, nat->pairs.data(), nat->pairs.size() * sizeof(int32_t));
+    return DFM_OK;
+}
+
+// Python's round(x, 6): the correctly rounded six-decimal string, read back
+static double round6(double x)
+{
+    if (!std::isfinite(x)) return x;
+    char buf[64];
+    snprintf(buf, sizeof(buf), "%.6f", x);
+    return strtod(buf, nullptr);
+}
+// libm's pow through a pointer the compiler cannot fold: metrics.py's `** 2` is that call, and the results are compared bit for bit
+static double (*volatile g_pow)(double, double) = static_cast<double (*)(double, double)>(std::pow);
+
+extern "C" int dfm_pose_metrics(dfm_native *nat, int P, const float *lig_pos, const float *rec_pos, dfm_metrics_out *out)
+{
+    if (!nat || !out) return fail(DFM_E_INVALID, "NULL argument");
+    if (!lig_pos) return fail(DFM_E_INVALID, "lig_pos is NULL");
+    if (P < 1) return fail(DFM_E_INVALID, "need P >= 1");
+    DEVICE_SCOPE(nat->device);
+    PoseCall c;
+    HIPCHK(c.open());
+    const int R = nat->R, L = nat->L, chains = rec_pos ? 2 : 1;
+    const size_t lig_n = (size_t)L * 9, rec_n = (size_t)R * 9, per_pose = (lig_n + (rec_pos ? rec_n : 0)) * sizeof(float);
+    const int Pc = (int)std::min<size_t>((size_t)P, std::max<size_t>(1, METRICS_CHUNK_BYTES / per_pose));
+    float *X = nullptr, *Xr = nullptr;
+    double *sums = nullptr, *xf = nullptr, *d_rmsd = nullptr;
+    int32_t *d_cnt = nullptr;
+    HIPCHK(c.tmp.alloc(&X, (size_t)Pc * lig_n));
+    if (rec_pos) HIPCHK(c.tmp.alloc(&Xr, (size_t)Pc * rec_n));
+    HIPCHK(c.tmp.alloc(&sums, (size_t)Pc * chains * 24));
+    HIPCHK(c.tmp.alloc(&xf, (size_t)Pc * 36));
+    HIPCHK(c.tmp.alloc(&d_rmsd, (size_t)Pc * 3));
+    HIPCHK(c.tmp.alloc(&d_cnt, (size_t)Pc));
+    MetricsConst mc = nat->mc;
+    mc.rec_moves = rec_pos ? 1 : 0;
+    const MetricsChain lig = {X, nat->lig, nat->flig, L}, rec = {rec_pos ? Xr : nat->rec, nat->rec, nat->frec, R};
+    std::vector<double> h_rmsd((size_t)P * 3);
+    std::vector<int32_t> h_cnt((size_t)P);
+    double copy_ms = 0.0, kernel_ms = 0.0;
+    for (int p0 = 0; p0 < P; p0 += Pc) {
+        const int n = std::min(Pc, P - p0);
+        HIPCHK(hipEventRecord(c.ev[0], c.s));
+        HIPCHK(hipMemcpyAsync(X, lig_pos + (size_t)p0 * lig_n, (size_t)n * lig_n * sizeof(float), hipMemcpyHostToDevice, c.s));
+        if (rec_pos) HIPCHK(hipMemcpyAsync(Xr, rec_pos + (size_t)p0 * rec_n, (size_t)n * rec_n * sizeof(float), hipMemcpyHostToDevice, c.s));
+        HIPCHK(hipEventRecord(c.ev[1], c.s));
+        HIPCHK(launch_metrics_reduce(lig, rec, chains, n, mc, sums, c.s));
+        HIPCHK(launch_metrics_finish(lig, rec, sums, chains, nat->rec_const, mc, nat->contacts, n, xf, d_rmsd, d_cnt, c.s));
+        HIPCHK(hipEventRecord(c.ev[2], c.s));
+        HIPCHK(hipMemcpyAsync(h_rmsd.data() + (size_t)p0 * 3, d_rmsd, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(hipMemcpyAsync(h_cnt.data() + p0, d_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(hipStreamSynchronize(c.s));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) copy_ms += ms;
+        if (hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess) kernel_ms += ms;
+    }
+    g_metrics_ms[0] = copy_ms;
+    g_metrics_ms[1] = kernel_ms;
+    const double nc = (double)mc.n_contacts;
+    for (int p = 0; p < P; ++p) {
+        const double cr = h_rmsd[(size_t)p * 3], ir = h_rmsd[(size_t)p * 3 + 1], lr = h_rmsd[(size_t)p * 3 + 2];
+        const double fnat = round6((double)h_cnt[(size_t)p] / (nc + 1e-6));
+        if (out->c_rmsd) out->c_rmsd[p] = cr;
+        if (out->i_rmsd) out->i_rmsd[p] = ir;
+        if (out->l_rmsd) out->l_rmsd[p] = lr;
+        if (out->fnat) out->fnat[p] = fnat;
+        if (out->dockq) out->dockq[p] = (fnat + 1.0 / (1.0 + g_pow(ir / 1.5, 2.0)) + 1.0 / (1.0 + g_pow(lr / 8.5, 2.0))) / 3.0;
+        if (out->n_recovered) out->n_recovered[p] = h_cnt[(size_t)p];
+    }
+    return DFM_OK;
+}
+
+extern "C" int dfm_metrics_last_timing(double *copy_ms, double *kernel_ms)
+{
+    if (!copy_ms || !kernel_ms) return fail(DFM_E_INVALID, "NULL argument");
+    *copy_ms = g_metrics_ms[0];
+    *kernel_ms = g_metrics_ms[1];
+    return DFM_OK;
+}
+
 extern "C" int dfm_complex_degree(const dfm_complex *cx) { return cx ? cx->K : -1; }
 
 extern "C" long long dfm_trim_cache(int device)

@@ -378,4 +378,32 @@ hipError_t launch_cluster_count(const uint32_t *mask, int B, int32_t *counts, ui
 hipError_t launch_cluster_step(const uint32_t *mask, int B, int32_t *counts, const int32_t *pos, const int32_t *order, uint32_t *U,
                                int32_t *cluster_of, int32_t *center, int32_t *size, int32_t *mlist, int32_t *state, hipStream_t s);
 
+// docking metrics (kernels_metrics.hip; include/dfmdock_amd.h: dfm_native_create / dfm_pose_metrics).  One chain of a batch of poses:
+// model [P][n][9] (pose stride n * 9), native [n][9], iface [n] (1: interface residue of the native)
+struct MetricsChain {
+    const float *model;
+    const float *native;
+    const uint8_t *iface;
+    int n;
+};
+// what the native alone fixes: residue counts, T = sum of the native's shifted coordinates q' = q - o per group (over atoms), the shift
+struct MetricsConst {
+    int n_rec, n_lig, n_rec_iface, n_lig_iface, n_contacts;
+    int rec_moves;              // 1: every pose brings its own receptor; 0: the native receptor in every pose
+    double T_rec[3], T_lig[3], T_rec_iface[3], T_lig_iface[3];
+    double o[3];
+    double contact_cutoff;
+};
+// out [R][L]: bit 0 = min backbone-atom distance < iface_cutoff, bit 1 = < contact_cutoff
+hipError_t launch_native_pairs(const float *rec, const float *lig, int R, int L, double iface_cutoff, double contact_cutoff, uint8_t *out,
+                               hipStream_t s);
+// sums [P][chains][24] of chain c0 (and c1 when chains = 2)
+hipError_t launch_metrics_reduce(const MetricsChain &c0, const MetricsChain &c1, int chains, int P, const MetricsConst &mc, double *sums,
+                                 hipStream_t s);
+// the three fits (xf [P][36] scratch) and their residuals: rmsd [P][3] = c, i, l; recovered [P] native contacts.  rec_const [24]: the
+// receptor's sums when chains = 1
+hipError_t launch_metrics_finish(const MetricsChain &lig, const MetricsChain &rec, const double *sums, int chains, const double *rec_const,
+                                 const MetricsConst &mc, const int32_t *contacts, int P, double *xf, double *rmsd, int32_t *recovered,
+                                 hipStream_t s);
+
 }  // namespace dfm

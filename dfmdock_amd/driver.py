@@ -28,6 +28,8 @@ from .metrics import NativeContext, compute_metrics
 CSV_FIELDS = ["id", "index", "c_rmsd", "i_rmsd", "l_rmsd", "fnat", "DockQ", "energy", "num_clashes"]
 RESTRAINT_FIELDS = ["restraint_energy", "restraints_satisfied"]      # appended to the rows only when restraints are given
 CLUSTER_FIELDS = ["cluster", "is_center"]      # appended to the rows only when clustering is asked for
+STEP_FIELDS = ["id", "index", "step", "t", "c_rmsd", "i_rmsd", "l_rmsd", "fnat", "DockQ"]      # the long table of run_set(step_metrics=True)
+METRIC_FIELDS = ["c_rmsd", "i_rmsd", "l_rmsd", "fnat", "DockQ"]
 
 
 def rotate_complex(rec_pos, lig_pos, Rm):
@@ -137,14 +139,33 @@ def _sample(p: _Prepared, t_lo, t_hi, num_steps, seed, max_batch, trace, sampler
     return batches
 
 
-def _post(p: _Prepared, batches, traj_dir):
-    """Stage 3 (host only): per-trajectory metrics against the native pose (inference_mlsb.py:232-262), trajectory PDBs, records."""
+def _post(p: _Prepared, batches, traj_dir, model=None, metrics="host", step_metrics=False, eps=1e-3):
+    """Stage 3: per-trajectory metrics against the native pose (inference_mlsb.py:232-262), trajectory PDBs, records.  metrics "host":
+    one compute_metrics per final pose (numpy, the reference's arithmetic); "gpu": the final poses of the complex in ONE
+    dfm_pose_metrics call, and with `step_metrics` every frame of every trace in one call per batch (returned as the third value)."""
     import time
     t0 = time.perf_counter()
-    c, rows, records = p.c, [], []
+    c, rows, records, steps = p.c, [], [], []
+    gm = None
+    if metrics == "gpu" and batches:
+        with model.native(p.rec_pos, p.lig_pos) as nat:
+            gm = nat.metrics(np.concatenate([r["lig_pos"] for _, _, r in batches], 0))
+            if step_metrics:
+                for done, b, r in batches:
+                    S = r["trace_pose"].shape[1]
+                    sm = nat.metrics(r["trace_pose"].reshape(b * S, -1, 3, 3))
+                    ts = np.linspace(1.0, eps, S)
+                    for k in range(b):
+                        for st in range(S):
+                            steps.append({"id": c.get("id", str(p.ci)), "index": str(done + k), "step": st, "t": float(ts[st]),
+                                          **{f: float(sm[f][k * S + st]) for f in METRIC_FIELDS}})
+    at = 0
     for done, b, r in batches:
         for k in range(b):
-            m = compute_metrics((p.rec_pos, r["lig_pos"][k]), (p.rec_pos, p.lig_pos), p.native)
+            if gm is not None:
+                m = {f: float(gm[f][at + k]) for f in METRIC_FIELDS}
+            else:
+                m = compute_metrics((p.rec_pos, r["lig_pos"][k]), (p.rec_pos, p.lig_pos), p.native)
             rows.append({"id": c.get("id", str(p.ci)), "index": str(done + k), **m, "energy": float(r["energy"][k]),
                          "num_clashes": int(r["num_clashes"][k])})
             if p.restraints is not None:
@@ -154,15 +175,19 @@ def _post(p: _Prepared, batches, traj_dir):
                 frames = r["trace_pose"][k]
                 pdbio.write_trajectory_pdb(os.path.join(traj_dir, f"{c.get('id', p.ci)}_p{done + k}.pdb"),
                                            [p.rec_pos] * len(frames), frames, c["rec_seq"], c["lig_seq"])
+        at += b
         records.append(D.make_records(p.ci, np.arange(done, done + b), r))
     p.ms["post"] = (time.perf_counter() - t0) * 1e3
+    if step_metrics:
+        return rows, records, steps
     return rows, records
 
 
 def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0, precision="mfma16", global_rotation=True,
             out_csv=None, traj_dir=None, max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", checks_out=None,
             overlap=True, samplers=2, timings_out=None, log=None, canary=True, canary_out=None, restraints_by_id=None,
-            cluster_radius=None, cluster_rule="energy", top_k=10, **sampler_kw):
+            cluster_radius=None, cluster_rule="energy", top_k=10, metrics="host", step_metrics=False, step_csv=None, steps_out=None,
+            **sampler_kw):
     """Sample `num_samples` trajectories for every complex dict (id, rec_x, lig_x, rec_pos, lig_pos[, rec_seq, lig_seq]);
     returns the metric rows of this rank's share; rank 0 writes the gathered CSV when `out_csv` is given.  Every complex is
     self-checked first (checked_precision); `checks_out` (a list) collects {id, precision used, check dict}.
@@ -190,7 +215,19 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
     `cluster_radius` (A): the trajectories of every complex are clustered by ligand RMSD (cluster_trajectories; key: energy, rule
     `cluster_rule`, at most `top_k` clusters) and every row gains `cluster` (-1: in none of them) and `is_center`.  This runs where all
     trajectories of a complex are present: on the owning rank when complexes are sharded, on rank 0 after the record gather when
-    trajectories are split (the assignment then reaches every rank's rows)."""
+    trajectories are split (the assignment then reaches every rank's rows).
+
+    `metrics`: "host" (default; one numpy compute_metrics per final pose, the CSV of every earlier version byte for byte) or "gpu" (the
+    final poses of a complex in one dfm_pose_metrics call: the same definition evaluated in fp64 on the device, equal to the host's
+    values to ~1e-12 relative, so the CSV differs in the last printed digits).  `step_metrics=True` (needs metrics="gpu"; takes the
+    trace) evaluates the pose after EVERY step of every trajectory: the long table {id, index, step, t, c_rmsd, i_rmsd, l_rmsd, fnat,
+    DockQ} (t = the time of the step taken, linspace(1, eps, num_steps)[step]) is appended to `steps_out` (a list; this rank's share)
+    and written to `step_csv` by rank 0."""
+    if metrics not in ("host", "gpu"):
+        raise ValueError(f"metrics must be 'host' or 'gpu', got {metrics!r}")
+    step_metrics = bool(step_metrics) or step_csv is not None
+    if step_metrics and metrics != "gpu":
+        raise ValueError("step_metrics evaluates num_samples x num_steps poses per complex: it needs metrics='gpu'")
     if cluster_radius is not None and cluster_rule not in ("energy", "size"):
         raise ValueError(f"cluster_rule must be 'energy' or 'size', got {cluster_rule!r}")
     rank, _, world = D.dist_env()
@@ -207,7 +244,18 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
     rots = [rng.integers(0, 2 ** 31) for _ in complexes]      # per-complex streams, identical on every rank
     if t_hi <= t_lo:
         share = []
-    trace = traj_dir is not None
+    trace = traj_dir is not None or step_metrics
+    if step_metrics and traj_dir is None:      # the trace is taken for its poses alone: the step evaluations stay those of an untraced run
+        sampler_kw.setdefault("step_energy", False)
+    step_rows = []
+
+    def post(p, batches):
+        if metrics == "host":
+            return _post(p, batches, traj_dir)      # the path of every earlier version, untouched
+        out = _post(p, batches, traj_dir, model, metrics, step_metrics, float(sampler_kw.get("eps", 1e-3)))
+        if step_metrics:
+            step_rows.extend(out[2])
+        return out[0], out[1]
 
     def restraints_of(ci):      # keyword arguments of _prepare: none without restraints
         if restraints_by_id is None:
@@ -225,7 +273,7 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
     if not overlap or len(share) < 2:
         for ci in share:
             p = prep(ci)
-            rows_c, recs_c = _post(p, samp(p), traj_dir)
+            rows_c, recs_c = post(p, samp(p))
             done.append((p, rows_c, recs_c))
     else:
         import threading
@@ -254,7 +302,7 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
             p, batches = fs.result()
             if p.ci == canary_ci:
                 canary_ref["batches"], canary_ref["precision"] = batches, p.precision
-            rows_c, recs_c = _post(p, batches, traj_dir)
+            rows_c, recs_c = post(p, batches)
             return p, rows_c, recs_c
 
         with ThreadPoolExecutor(1, thread_name_prefix="dfm-prep") as ex_prep, \
@@ -285,9 +333,10 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
                     f"run_set canary: complex {info['id']} sampled next to other handles differs from the same complex sampled alone - "
                     "concurrent handles are NOT independent on this system; re-running this rank's share serially")
                 done = []
+                del step_rows[:]
                 for ci in share:
                     p = prep(ci)
-                    rows_c, recs_c = _post(p, samp(p), traj_dir)
+                    rows_c, recs_c = post(p, samp(p))
                     done.append((p, rows_c, recs_c))
                 info["reran_serial"] = True
             if canary_out is not None:
@@ -332,6 +381,17 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
                 w.writeheader()
                 for row in sorted(all_rows, key=lambda x: (x["id"], int(x["index"]))):
                     w.writerow(row)
+    if steps_out is not None:
+        steps_out.extend(step_rows)
+    if step_csv is not None:
+        all_steps = _gather_rows(step_rows, world)
+        if rank == 0:
+            os.makedirs(os.path.dirname(os.path.abspath(step_csv)), exist_ok=True)
+            with open(step_csv, "w", newline="") as f:
+                w = csv.DictWriter(f, fieldnames=STEP_FIELDS)
+                w.writeheader()
+                for row in sorted(all_steps, key=lambda x: (x["id"], int(x["index"]), x["step"])):
+                    w.writerow(row)
     return rows, ranked
 
 
@@ -341,10 +401,42 @@ def _gather_rows(rows, world):
     return [r for part in D.gather_objects(rows) for r in part]
 
 
+def native_metrics(model: engine.Model, native, rec_bb, lig_poses):
+    """Docking metrics of ligand poses lig_poses [P,L,3,3] of a pair whose receptor backbone is rec_bb [R,3,3], against `native` =
+    (receptor [R,3,3], ligand [L,3,3]) given in ANY frame: the pair's receptor travels with every pose (rec_pos of dfm_pose_metrics), so
+    the fits take care of the frame.  The native is matched to the pair by residue order.  Returns one {c_rmsd, ..., DockQ} per pose."""
+    nr, nl = (np.asarray(x, np.float32).reshape(-1, 3, 3) for x in native)
+    rec_bb, lig_poses = np.asarray(rec_bb, np.float32).reshape(-1, 3, 3), np.asarray(lig_poses, np.float32)
+    lig_poses = lig_poses.reshape(lig_poses.shape[0], -1, 3, 3)
+    if nr.shape[0] != rec_bb.shape[0] or nl.shape[0] != lig_poses.shape[1]:
+        raise ValueError(f"the native has {nr.shape[0]} receptor / {nl.shape[0]} ligand residues, the input pair "
+                         f"{rec_bb.shape[0]} / {lig_poses.shape[1]}: they must match residue by residue")
+    with model.native(nr, nl) as nat:
+        m = nat.metrics(lig_poses, np.repeat(rec_bb[None], lig_poses.shape[0], 0))
+    return [{k: float(m[k][p]) for k in METRIC_FIELDS} for p in range(lig_poses.shape[0])]
+
+
+def _check_native(native, rec, lig):
+    """Before any sampling: the native must have the input's residue counts."""
+    nr, nl = (np.asarray(x).reshape(-1, 3, 3) for x in native)
+    if nr.shape[0] != len(rec["bb_coords"]) or nl.shape[0] != len(lig["bb_coords"]):
+        raise ValueError(f"the native has {nr.shape[0]} receptor / {nl.shape[0]} ligand residues, the input pair "
+                         f"{len(rec['bb_coords'])} / {len(lig['bb_coords'])}: they must match residue by residue")
+
+
+def _selected_metrics(model, native, rec, lig0, res):
+    """`metrics` of the pose a pair driver keeps (its rot_update / tr_update on the input backbone), when a native is given."""
+    if native is not None:
+        from .cluster import rebuild_backbone
+        res["metrics"] = native_metrics(model, native, rec["bb_coords"],
+                                        rebuild_backbone(lig0, res["rot_update"][None], res["tr_update"][None], model.hp.family))[0]
+    return res
+
+
 def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_steps=40, seed=0, precision="mfma16",
               out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", restraints=None,
               restraint_rank="satisfied", restraint_params=None, top_k=None, cluster_radius=4.0, cluster_rule="energy", refine_t=None,
-              refine_samples=8, **sampler_kw):
+              refine_samples=8, native=None, **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
     pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
     the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
@@ -361,7 +453,13 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     model 1 is the output.pdb pose.
 
     `refine_t` (needs top_k): the centres are then refined locally from t_begin = refine_t, `refine_samples` trajectories each, in one
-    batched call (refine_models); the models gain `refined_energy` and their files hold the refined poses.  output.pdb is unchanged."""
+    batched call (refine_models); the models gain `refined_energy` and their files hold the refined poses.  output.pdb is unchanged.
+
+    `native` ((receptor [R,3,3], ligand [L,3,3]) backbones of the native complex, any frame, same residues as the input): the result
+    gains `metrics` (c_rmsd, i_rmsd, l_rmsd, fnat, DockQ of the kept pose, on the GPU: native_metrics), every model `metrics` and, after
+    refinement, `refined_metrics`."""
+    if native is not None:
+        _check_native(native, rec, lig)
     if refine_t is not None and top_k is None:
         raise ValueError("refine_t refines the cluster centres: it needs top_k")
     if refine_t is not None and int(refine_samples) < 1:
@@ -381,7 +479,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     if restraints is not None:
         return _dock_pair_restrained(gx, model, rec, lig, restraints, restraint_rank, restraint_params, num_samples, num_steps, seed,
                                      precision, chk, out_pdb, max_batch, sampler_kw, clu,
-                                     None if refine_t is None else (float(refine_t), int(refine_samples)))
+                                     None if refine_t is None else (float(refine_t), int(refine_samples)), native)
     best = None
     done = 0
     cols = {k: [] for k in ("energy", "rot_update", "tr_update")}
@@ -405,24 +503,28 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         pdbio.write_complex_pdb(out_pdb, rec_atoms, lig["atoms"], lig_aa)
     res = {"energy": best[0], "rot_update": best[1], "tr_update": best[2], "lig_aa_coords": lig_aa, "precision": precision,
            "selfcheck": chk}
+    _selected_metrics(model, native, rec, lig0, res)
     if clu is not None:
         cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
-        res.update(_top_models(model, rec, lig, lig0, cols, cols["energy"], clu, out_pdb))
+        res.update(_top_models(model, rec, lig, lig0, cols, cols["energy"], clu, out_pdb, native))
         if refine_t is not None:
             refine_models(model, gx, rec, lig, lig0, cols, res["models"], float(refine_t), int(refine_samples), num_steps, seed, precision,
-                          out_pdb, **sampler_kw)
+                          out_pdb, native=native, **sampler_kw)
             gx.close()
     return res
 
 
 def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
                 out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", perturb=True, restraints=None,
-                restraint_params=None, **sampler_kw):
+                restraint_params=None, native=None, **sampler_kw):
     """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories
     start from that pose noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps
     down from t_begin; like dock_pair the minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns
     dock_pair's dict plus `t_begin`, `index` and `trajectories` (every trajectory's energy, rot_update, tr_update).  `restraints`
-    ([restraints.RestraintGroup]) turns the restraint step on (DFM_F_RESTRAINTS)."""
+    ([restraints.RestraintGroup]) turns the restraint step on (DFM_F_RESTRAINTS).  `native` (as for dock_pair): the result gains
+    `metrics` of the kept pose and `start_metrics` of the pose the refinement started from."""
+    if native is not None:
+        _check_native(native, rec, lig)
     gx = engine.Complex(model, rec_x, lig_x, rec["bb_coords"], lig["bb_coords"])
     precision, chk = checked_precision(gx, precision, "pair", selfcheck, on_selfcheck_fail, seed=seed)
     if restraints is not None:
@@ -443,11 +545,16 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
                                        center="all_atoms" if model.hp.family == 1 else "ca")
     if out_pdb:
         pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa)
-    return {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
-            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, "index": k, "t_begin": float(t_begin), "trajectories": cols}
+    res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
+           "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, "index": k, "t_begin": float(t_begin), "trajectories": cols}
+    if native is not None:
+        _selected_metrics(model, native, rec, gx.lig_pos0, res)
+        res["start_metrics"] = native_metrics(model, native, rec["bb_coords"], gx.lig_pos0[None])[0]
+    return res
 
 
-def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps, seed, precision, out_pdb, restraints=False, **sampler_kw):
+def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps, seed, precision, out_pdb, restraints=False, native=None,
+                  **sampler_kw):
     """dock_pair's second stage (`refine_t`): the K cluster centres of `models` refined in ONE dfm_refine call - B = K n trajectories,
     start_pos = each centre's backbone n times.  Every model gains `refined_energy` (the minimum over its n trajectories) and
     `refined_index`; <out_pdb stem>_<rank>.pdb becomes that refined pose (the centre's rigid motion, then the refinement's)."""
@@ -458,8 +565,12 @@ def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps
     r = gx.refine(B=K * n, t_begin=t_begin, start_pos=np.repeat(start, n, 0), num_steps=num_steps, seed=seed, restraints=restraints,
                   **engine.precision_kwargs(precision), **sampler_kw)
     center = "all_atoms" if model.hp.family == 1 else "ca"
+    kept = [k * n + int(np.argmin(r["energy"][k * n:(k + 1) * n])) for k in range(K)]
+    if native is not None:      # every centre after its refinement (before: the model's `metrics`, _top_models)
+        for m, rm in zip(models, native_metrics(model, native, rec["bb_coords"], r["lig_pos"][kept])):
+            m["refined_metrics"] = rm
     for k, m in enumerate(models):
-        j = k * n + int(np.argmin(r["energy"][k * n:(k + 1) * n]))
+        j = kept[k]
         m.update(refined_energy=float(r["energy"][j]), refined_index=j - k * n)
         if out_pdb:
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][cen[k]], cols["tr_update"][cen[k]], center=center)
@@ -468,7 +579,7 @@ def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps
     return models
 
 
-def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb):
+def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None):
     """dock_pair's `models`: the centres of up to top_k clusters in cluster order, each written as <out_pdb stem>_<rank>.pdb."""
     top_k, radius, rule = clu
     cl = cluster_trajectories(model, lig0, cols["rot_update"], cols["tr_update"], key, radius, rule, top_k)
@@ -480,6 +591,12 @@ def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb):
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c],
                                            center="all_atoms" if model.hp.family == 1 else "ca")
             pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa)
+    if native is not None and models:
+        from .cluster import rebuild_backbone
+        cen = [m["index"] for m in models]
+        poses = rebuild_backbone(lig0, cols["rot_update"][cen], cols["tr_update"][cen], model.hp.family)
+        for m, pm in zip(models, native_metrics(model, native, rec["bb_coords"], poses)):
+            m["metrics"] = pm
     return {"models": models, "cluster_of": cl["cluster_of"]}
 
 
@@ -489,7 +606,7 @@ def model_path(out_pdb, rank):
 
 
 def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_samples, num_steps, seed, precision, chk, out_pdb, max_batch,
-                          sampler_kw, clu=None, refine=None):
+                          sampler_kw, clu=None, refine=None, native=None):
     from . import restraints as RS
     gx.set_restraints(restraints, params)
     cols = {k: [] for k in ("energy", "restraint_energy", "restraints_satisfied", "rot_update", "tr_update")}
@@ -516,12 +633,13 @@ def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_sam
            "restraint_rank": rank, "restraint_energy": float(cols["restraint_energy"][k]),
            "restraints_satisfied": int(cols["restraints_satisfied"][k]),
            "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
+    _selected_metrics(model, native, rec, lig0, res)
     if clu is not None:
         from .cluster import satisfied_key
         key = satisfied_key(cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else cols["energy"]
-        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb))
+        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native))
         if refine is not None:
             refine_models(model, gx, rec, lig, lig0, cols, res["models"], refine[0], refine[1], num_steps, seed, precision, out_pdb,
-                          restraints=True, **sampler_kw)
+                          restraints=True, native=native, **sampler_kw)
             gx.close()
     return res

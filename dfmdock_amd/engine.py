@@ -165,6 +165,86 @@ class Model:
         return {"sigma_idx": idx.value, "sigma": sg.value, "cdf": cdf}
 
 
+    def native(self, rec_pos, lig_pos, iface_cutoff=10.0, contact_cutoff=5.5):
+        """The native pose (receptor [R,3,3], ligand [L,3,3]) prepared for batched docking metrics on the GPU (dfm_native_create):
+        a Native whose `.metrics(lig_pos[, rec_pos])` evaluates P poses in one call.  The cutoffs are the reference's."""
+        return Native(self, rec_pos, lig_pos, iface_cutoff, contact_cutoff)
+
+
+class Native:
+    """A native pose resident on the model's GPU (dfm_native): interface residues, native contacts and the receptor's share of the
+    Kabsch sums, computed once.  Read-only after creation: `metrics` may be called from several threads at once."""
+
+    def __init__(self, model: Model, rec_pos, lig_pos, iface_cutoff=10.0, contact_cutoff=5.5):
+        rp, lp = _f32(rec_pos).reshape(-1, 9), _f32(lig_pos).reshape(-1, 9)
+        self.model, self.R, self.L = model, rp.shape[0], lp.shape[0]
+        self._h = L.lib().dfm_native_create(model._h, _p(rp), _p(lp), self.R, self.L, float(iface_cutoff), float(contact_cutoff))
+        if not self._h:
+            msg = L.lib().dfm_last_error()
+            L.check(-2 if msg.startswith((b"dfm_native_create", b"hipSetDevice")) else -1, "dfm_native_create")      # else: bad argument
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().dfm_native_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{n_iface_rec, n_iface_lig, n_contacts, iface_rec, iface_lig (ascending residue indices), contacts [n,2] (receptor, ligand)}:
+        what metrics.NativeContext calls r1, r2 and act."""
+        n = [C.c_int32(0) for _ in range(3)]
+        L.check(L.lib().dfm_native_info(self._h, C.byref(n[0]), C.byref(n[1]), C.byref(n[2]), None, None, None), "dfm_native_info")
+        r1, r2, act = np.zeros(n[0].value, np.int32), np.zeros(n[1].value, np.int32), np.zeros((n[2].value, 2), np.int32)
+        L.check(L.lib().dfm_native_info(self._h, None, None, None, _p(r1, L.I32P), _p(r2, L.I32P), _p(act, L.I32P)), "dfm_native_info")
+        return {"n_iface_rec": n[0].value, "n_iface_lig": n[1].value, "n_contacts": n[2].value, "iface_rec": r1, "iface_lig": r2,
+                "contacts": act}
+
+    def metrics(self, lig_pos, rec_pos=None):
+        """Docking metrics of P poses (dfm_pose_metrics; the float64 definition is metrics.compute_metrics): lig_pos [P,L,3,3] (or one
+        [L,3,3] pose), rec_pos [P,R,3,3] or None = the native receptor in every pose.  Returns float64 arrays [P] under the reference's
+        keys c_rmsd, i_rmsd, l_rmsd, fnat, DockQ, plus n_recovered (int32: the native contacts found in the pose)."""
+        lp = _f32(lig_pos)
+        if lp.size and lp.size == self.L * 9:
+            lp = lp.reshape(1, self.L, 9)
+        if lp.ndim < 2 or lp.shape[0] < 1 or lp.size != lp.shape[0] * self.L * 9:
+            raise ValueError(f"lig_pos must be [P,{self.L},3,3] with P >= 1, got {np.shape(lig_pos)}")
+        P = lp.shape[0]
+        rp = None
+        if rec_pos is not None:
+            rp = _f32(rec_pos)
+            if rp.size == self.R * 9 and P > 1:
+                rp = np.ascontiguousarray(np.broadcast_to(rp.reshape(1, self.R, 9), (P, self.R, 9)))
+            if rp.size != P * self.R * 9:
+                raise ValueError(f"rec_pos must be [P,{self.R},3,3] with P = {P}, got {np.shape(rec_pos)}")
+        o = {k: np.zeros(P, np.float64) for k in ("c_rmsd", "i_rmsd", "l_rmsd", "fnat", "DockQ")}
+        o["n_recovered"] = np.zeros(P, np.int32)
+        out = L.MetricsOutC()
+        dp = C.POINTER(C.c_double)
+        out.c_rmsd, out.i_rmsd, out.l_rmsd = (o[k].ctypes.data_as(dp) for k in ("c_rmsd", "i_rmsd", "l_rmsd"))
+        out.fnat, out.dockq, out.n_recovered = o["fnat"].ctypes.data_as(dp), o["DockQ"].ctypes.data_as(dp), _p(o["n_recovered"], L.I32P)
+        L.check(L.lib().dfm_pose_metrics(self._h, P, _p(lp), _p(rp), C.byref(out)), "dfm_pose_metrics")
+        return o
+
+
+def metrics_last_timing():
+    """(host-to-device copy ms, kernel ms) of this thread's last Native.metrics call (dfm_metrics_last_timing)."""
+    a, b = C.c_double(0), C.c_double(0)
+    L.check(L.lib().dfm_metrics_last_timing(C.byref(a), C.byref(b)), "dfm_metrics_last_timing")
+    return a.value, b.value
+
+
 def pose_last_timing():
     """(k_pose_dist ms, clustering kernels ms) of this thread's last pose_rmsd / pose_cluster call (dfm_pose_last_timing)."""
     a, b = C.c_double(0), C.c_double(0)

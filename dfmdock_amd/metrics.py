@@ -72,3 +72,27 @@ def compute_metrics(model, native, ctx: NativeContext | None = None):
     fnat = round(int((pred < 5.5).sum()) / (len(act[0]) + 1e-6), 6)
     dockq = (fnat + 1.0 / (1.0 + (i_rmsd / 1.5) ** 2) + 1.0 / (1.0 + (l_rmsd / 8.5) ** 2)) / 3
     return {"c_rmsd": c_rmsd, "i_rmsd": i_rmsd, "l_rmsd": l_rmsd, "fnat": fnat, "DockQ": dockq}
+
+
+METRIC_KEYS = ("c_rmsd", "i_rmsd", "l_rmsd", "fnat", "DockQ")
+
+
+def compute_metrics_batch(models_lig, native, ctx: NativeContext | None = None, models_rec=None):
+    """compute_metrics over P poses: models_lig [P,L,3,3], models_rec [P,R,3,3] or None = the native receptor in every pose (what
+    the drivers produce).  Returns float64 arrays [P] under compute_metrics' keys plus `n_recovered` (int32: native contacts whose
+    minimum backbone-atom distance in the pose is below 5.5 A).  This loop is the definition the batched GPU call
+    (engine.Native.metrics, dfm_pose_metrics) is tested against."""
+    ctx = ctx or NativeContext(native)
+    lig = np.asarray(models_lig, np.float32)
+    lig = lig.reshape(lig.shape[0], -1, 3, 3)
+    rec = None if models_rec is None else np.asarray(models_rec, np.float32).reshape(lig.shape[0], -1, 3, 3)
+    out = {k: np.zeros(lig.shape[0], np.float64) for k in METRIC_KEYS}
+    out["n_recovered"] = np.zeros(lig.shape[0], np.int32)
+    for p in range(lig.shape[0]):
+        mr = native[0] if rec is None else rec[p]
+        m = compute_metrics((mr, lig[p]), native, ctx)
+        for k in METRIC_KEYS:
+            out[k][p] = m[k]
+        pred = _min_dist_pairs(np.asarray(mr, np.float32).astype(np.float64), lig[p].astype(np.float64), ctx.act[0], ctx.act[1])
+        out["n_recovered"][p] = int((pred < 5.5).sum())
+    return out

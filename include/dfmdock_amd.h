@@ -58,6 +58,7 @@ extern "C" {
 
 typedef struct dfm_model dfm_model;
 typedef struct dfm_complex dfm_complex;
+typedef struct dfm_native dfm_native;
 
 typedef enum {
     DFM_OK = 0,
@@ -346,6 +347,41 @@ int dfm_pose_cluster(dfm_model *m, int B, int L, const float *lig_pos, const int
 /* GPU milliseconds of the calling thread's last dfm_pose_rmsd / dfm_pose_cluster: the distance kernel (k_pose_dist) and the clustering
  * kernels after it (0 for dfm_pose_rmsd) - tools/cluster_bench.py */
 int dfm_pose_last_timing(double *dist_ms, double *cluster_ms);
+/* Docking metrics of P model poses against one native pose: c_rmsd, i_rmsd, l_rmsd, fnat and DockQ as the reference's compute_metrics
+ * defines them (src/utils/metrics.py:3-121; dfmdock_amd/metrics.py is the float64 definition this call is tested against), batched on
+ * the GPU.  Backbones are [n,9] = (N, CA, C) per residue, dfm_traj_out's layout.
+ *   dfm_native_create: the native receptor rec_pos [R,9] and ligand lig_pos [L,9].  Precomputes on the GPU what depends on the native
+ *     alone: the interface residues (minimum backbone-atom distance to the other chain < iface_cutoff; the reference uses 10.0), the
+ *     native contacts (residue pairs with that distance < contact_cutoff; 5.5) and the receptor's share of the fits' sums.  NULL on
+ *     failure (dfm_last_error): NULL pointers, R or L < 1, R x L > 2^27 pairs, cutoffs not finite.  Lives on the MODEL handle's device,
+ *     needs the model only for that - the drivers close a complex right after sampling and evaluate later.
+ *   dfm_native_info: counts and, where the pointer is not NULL, the interface residue indices (ascending; [n_iface_rec], [n_iface_lig])
+ *     and the contact pairs [n_contacts,2] = (receptor residue, ligand residue) in row-major order of the R x L matrix.
+ *   dfm_pose_metrics: P >= 1 poses, ligand lig_pos [P,L,9]; receptor rec_pos_or_null [P,R,9], or NULL = the native receptor in every
+ *     pose (what every driver of this engine produces: the receptor never moves).  Per pose: three Kabsch fits in fp64 - all 3 (R + L)
+ *     atoms (c_rmsd), the interface atoms (i_rmsd), the receptor atoms with the fit applied to the ligand (l_rmsd) - each the RMSD of
+ *     the explicitly transformed points; n_recovered = native contact pairs whose minimum backbone-atom distance in the pose is below
+ *     contact_cutoff; fnat = round(n_recovered / (n_contacts + 1e-6), 6) and DockQ = (fnat + 1 / (1 + (i_rmsd / 1.5)^2) +
+ *     1 / (1 + (l_rmsd / 8.5)^2)) / 3 are finished in double on the host.  No interface residue: i_rmsd and dockq NaN; no native
+ *     contact: fnat 0.  A pose with NaN coordinates gets NaN where the definition gives NaN and leaves the other poses alone.  A pose's
+ *     outputs depend on that pose and the native alone - not on P, its index, or how the call splits P into chunks (64 MiB of poses
+ *     each).  Every output pointer of dfm_metrics_out may be NULL.  DFM_E_INVALID: NULL handle / lig_pos / out, P < 1.
+ * A dfm_native is read-only after creation: any number of host threads may call dfm_pose_metrics on it at once, next to sampling
+ * handles; every call owns a non-blocking stream and its device temporaries.  No reference call is batched: the reference evaluates one
+ * pose per compute_metrics call on the host (src/inference_mlsb.py:232-262). */
+dfm_native *dfm_native_create(dfm_model *m, const float *rec_pos /*[R,9]*/, const float *lig_pos /*[L,9]*/, int R, int L,
+                              float iface_cutoff, float contact_cutoff);
+void dfm_native_destroy(dfm_native *nat);
+int dfm_native_info(const dfm_native *nat, int32_t *n_iface_rec, int32_t *n_iface_lig, int32_t *n_contacts, int32_t *iface_rec_or_null,
+                    int32_t *iface_lig_or_null, int32_t *contacts_or_null /*[n_contacts,2]*/);
+typedef struct {
+    double *c_rmsd, *i_rmsd, *l_rmsd, *fnat, *dockq;   /* [P] each, or NULL */
+    int32_t *n_recovered;                              /* [P] or NULL       */
+} dfm_metrics_out;
+int dfm_pose_metrics(dfm_native *nat, int P, const float *lig_pos, const float *rec_pos_or_null, dfm_metrics_out *out);
+/* GPU milliseconds of the calling thread's last dfm_pose_metrics, summed over its chunks: the host-to-device copies of the poses and
+ * the three kernels (k_metrics_reduce, k_metrics_solve, k_metrics_resid) - tools/metrics_bench.py */
+int dfm_metrics_last_timing(double *copy_ms, double *kernel_ms);
 /* edges per node for this complex: min(N,20) + min(40, N-20) */
 int dfm_complex_degree(const dfm_complex *cx);
 /* Device blocks released by destroyed handles are parked per device for the next handle (a set driver creates and destroys a

@@ -1,0 +1,398 @@
+"""Docking metrics on the GPU (dfm_native_create / dfm_pose_metrics, kernels_metrics.hip) against their float64 definition
+dfmdock_amd/metrics.py (compute_metrics, which tests/test_host_cpu.py pins to values captured from the reference), and through the
+drivers and the command line.
+
+Tolerances.  RMSDs: rel = 2e-5, abs = 2e-5 - what tests/test_host_cpu.py grants between metrics.py and the reference's own fp32
+evaluation.  n_recovered: equal, except that a native contact pair whose float64 distance in the pose lies within 1e-3 A of the cutoff
+may count either way; such pairs may be at most 0.5 % of all contact evaluations of the parity test.  fnat and DockQ follow from the
+GPU's own count and RMSDs exactly (same formula, same libm)."""
+import csv
+import json
+import os
+import subprocess
+import sys
+import threading
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, complex_for, db5_complex, db5_ids, load_golden
+
+pytestmark = pytest.mark.gpu
+
+RMSD_KEYS = ("c_rmsd", "i_rmsd", "l_rmsd")
+SCALES = (0.0, 0.02, 0.05, 0.1, 0.3, 1.0)
+TOL = dict(rel=2e-5, abs=2e-5)
+BORDER = 1e-3
+
+
+def rotvec_matrix(v):
+    th = float(np.linalg.norm(v))
+    if th == 0.0:
+        return np.eye(3)
+    k = np.asarray(v, np.float64) / th
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+
+
+def perturbations(lig_pos, rng, n=16):
+    """n rigid perturbations of the ligand [L,3,3]: pose k has scale s = SCALES[k % 6], rotation vector s N(0,1)^3 about the CA centroid,
+    translation N(0, (10 s)^2) A per axis; s = 0 is the native itself.  float32."""
+    lig = np.asarray(lig_pos, np.float64)
+    cen = lig[:, 1].mean(0)
+    out = np.zeros((n,) + lig.shape, np.float32)
+    for k in range(n):
+        s = SCALES[k % len(SCALES)]
+        Rm, tr = rotvec_matrix(s * rng.standard_normal(3)), 10.0 * s * rng.standard_normal(3)
+        out[k] = ((lig - cen) @ Rm.T + cen + tr).astype(np.float32) if s else lig.astype(np.float32)
+    return out
+
+
+def recompute(o, n_contacts):
+    """fnat and DockQ from the call's own n_recovered and RMSDs, as metrics.compute_metrics finishes them."""
+    fnat = np.array([round(int(n) / (n_contacts + 1e-6), 6) for n in o["n_recovered"]])
+    with np.errstate(invalid="ignore"):
+        dockq = np.array([(f + 1.0 / (1.0 + (float(i) / 1.5) ** 2) + 1.0 / (1.0 + (float(l) / 8.5) ** 2)) / 3
+                          for f, i, l in zip(fnat, o["i_rmsd"], o["l_rmsd"])])
+    return fnat, dockq
+
+
+def check_against_definition(got, want, ctx, rec_poses, lig_poses, label=""):
+    """Gate 1 on a batch; returns (contact evaluations, borderline ones)."""
+    from dfmdock_amd.metrics import _min_dist_pairs
+    n_eval = n_border = 0
+    for p in range(len(lig_poses)):
+        for k in RMSD_KEYS:
+            print(f"{label} pose {p} {k}: gpu {got[k][p]:.9g} definition {want[k][p]:.9g}")
+            assert got[k][p] == pytest.approx(want[k][p], nan_ok=True, **TOL), (label, p, k)
+        d = _min_dist_pairs(np.asarray(rec_poses[p], np.float32).astype(np.float64), np.asarray(lig_poses[p], np.float32).astype(np.float64),
+                            ctx.act[0], ctx.act[1])
+        border = int((np.abs(d - 5.5) < BORDER).sum())
+        sure = int(((d < 5.5) & (np.abs(d - 5.5) >= BORDER)).sum())
+        n_eval += len(d)
+        n_border += border
+        print(f"{label} pose {p} n_recovered: gpu {got['n_recovered'][p]} definition {want['n_recovered'][p]} borderline {border}")
+        assert sure <= got["n_recovered"][p] <= sure + border, (label, p)
+    fnat, dockq = recompute(got, len(ctx.act[0]))
+    np.testing.assert_array_equal(got["fnat"], fnat)
+    np.testing.assert_array_equal(got["DockQ"], dockq)
+    return n_eval, n_border
+
+
+@pytest.fixture(scope="module")
+def model(blob):
+    from dfmdock_amd import engine
+    engine.set_device(0)
+    m = engine.Model(blob)
+    yield m
+    m.close()
+
+
+def test_parity_with_the_definition_on_db5(model):
+    """Gate 1.  24 DB5 backbones x 16 seeded rigid perturbations of the native ligand (numpy default_rng(0), one stream over the complexes
+    in fixture order).  With this recipe the definition alone has 5 of 5 744 contact evaluations (0.09 %) within 1e-3 A of the cutoff
+    (counted on the CPU); the cap is 0.5 %."""
+    from dfmdock_amd.metrics import NativeContext, compute_metrics_batch
+    rng = np.random.default_rng(0)
+    n_eval = n_border = 0
+    for cid in db5_ids():
+        c = db5_complex(cid)
+        native = (c["rec_pos"], c["lig_pos"])
+        ctx = NativeContext(native)
+        poses = perturbations(c["lig_pos"], rng)
+        want = compute_metrics_batch(poses, native, ctx)
+        with model.native(*native) as nat:
+            info = nat.info()
+            np.testing.assert_array_equal(info["iface_rec"], ctx.r1)
+            np.testing.assert_array_equal(info["iface_lig"], ctx.r2)
+            np.testing.assert_array_equal(info["contacts"], np.stack(ctx.act, 1))
+            got = nat.metrics(poses)
+        e, b = check_against_definition(got, want, ctx, [c["rec_pos"]] * len(poses), poses, cid)
+        n_eval += e
+        n_border += b
+    print(f"contact evaluations {n_eval}, borderline {n_border}")
+    assert n_eval == 5744 and n_border <= 0.005 * n_eval
+
+
+def test_reference_values_7cei(model):
+    """Gate 2: the cases of tests/test_host_cpu.py::test_compute_metrics_matches_reference through the GPU call."""
+    g, cx = load_golden("metrics_7CEI.npz"), load_golden("cx_7CEI.npz")
+    keys = [str(k) for k in g["keys"]]
+    sh = cx["lig_pos"].copy()
+    sh[..., 0] += 5.0
+    with model.native(cx["rec_pos"], cx["lig_pos"]) as nat:
+        o = nat.metrics(np.stack([cx["lig_pos"], sh, g["noised_lig"]]))
+    print({k: v.tolist() for k, v in o.items()})
+    assert o["fnat"][0] == 1.0 and abs(o["DockQ"][0] - 1.0) < 1e-6 and o["l_rmsd"][0] < 1e-4
+    for p, ref in ((1, g["shifted"]), (2, g["noised"])):
+        for k, v in zip(keys, ref):
+            assert o[k][p] == pytest.approx(float(v), rel=2e-5, abs=2e-5), (p, k)
+    assert o["DockQ"][1] == pytest.approx(0.4223329224, abs=1e-5)
+
+
+def test_moving_receptor_and_reflection(model):
+    """Gate 3: with rec_pos given, one rigid motion of the whole model leaves the metrics alone; a mirrored native is not a fit."""
+    from dfmdock_amd.metrics import NativeContext, compute_metrics_batch
+    rng = np.random.default_rng(3)
+    for cid in db5_ids()[:6]:
+        c = db5_complex(cid)
+        native = (c["rec_pos"], c["lig_pos"])
+        ctx = NativeContext(native)
+        poses = perturbations(c["lig_pos"], rng, 12)
+        want = compute_metrics_batch(poses, native, ctx)
+        moved_r, moved_l = np.zeros((12,) + c["rec_pos"].shape, np.float32), np.zeros_like(poses)
+        cen = np.asarray(c["rec_pos"], np.float64).reshape(-1, 3).mean(0)
+        for p in range(12):
+            Rm, tr = rotvec_matrix(2.0 * rng.standard_normal(3)), 10.0 * rng.standard_normal(3)
+            moved_r[p] = ((np.asarray(c["rec_pos"], np.float64) - cen) @ Rm.T + cen + tr).astype(np.float32)
+            moved_l[p] = ((poses[p].astype(np.float64) - cen) @ Rm.T + cen + tr).astype(np.float32)
+        with model.native(*native) as nat:
+            still = nat.metrics(poses, np.repeat(np.asarray(c["rec_pos"], np.float32)[None], 12, 0))
+            got = nat.metrics(moved_l, moved_r)
+            fixed = nat.metrics(poses)
+            mirror = nat.metrics((c["lig_pos"] * np.float32([-1, 1, 1]))[None], (c["rec_pos"] * np.float32([-1, 1, 1]))[None])
+        check_against_definition(still, want, ctx, [c["rec_pos"]] * 12, poses, cid + " unmoved")
+        check_against_definition(got, compute_metrics_batch(moved_l, native, ctx, moved_r), ctx, moved_r, moved_l, cid + " moved")
+        for k in RMSD_KEYS:      # invariance: the moved model against the unmoved one, and the receptor given against the receptor implied
+            for p in range(12):
+                assert got[k][p] == pytest.approx(want[k][p], **TOL), (cid, p, k)
+                assert still[k][p] == pytest.approx(fixed[k][p], **TOL), (cid, p, k)
+        np.testing.assert_array_equal(still["n_recovered"], fixed["n_recovered"])
+        wm = compute_metrics_batch((c["lig_pos"] * np.float32([-1, 1, 1]))[None], native, ctx, (c["rec_pos"] * np.float32([-1, 1, 1]))[None])
+        print(cid, "mirrored c_rmsd gpu", mirror["c_rmsd"][0], "definition", wm["c_rmsd"][0])
+        assert mirror["c_rmsd"][0] > 1.0 and mirror["c_rmsd"][0] == pytest.approx(wm["c_rmsd"][0], **TOL)
+
+
+def _same(a, b, idx_a, idx_b):
+    for k in a:
+        assert a[k][idx_a].tobytes() == b[k][idx_b].tobytes(), k
+
+
+def test_batch_invariance_and_threads(model, blob):
+    """Gate 4: a pose's outputs do not depend on P, on its index, on the call's chunking (64 MiB of poses per chunk: 116 508 poses of a
+    16-residue ligand) or on other host threads calling at once next to a sampling handle."""
+    from dfmdock_amd import engine
+    cx = complex_for("fwd_syn_24_16")
+    rng = np.random.default_rng(11)
+    probe = perturbations(cx["lig_pos"], rng, 6)[3]
+    with model.native(cx["rec_pos"], cx["lig_pos"]) as nat:
+        one = nat.metrics(probe[None])
+        assert np.isfinite(one["c_rmsd"][0]) and one["c_rmsd"][0] > 0
+        mid = (cx["lig_pos"][None] + rng.standard_normal((1000, 16, 3, 3)).astype(np.float32)).astype(np.float32)
+        mid[500] = probe
+        _same(one, nat.metrics(mid), 0, 500)
+        P = 120000      # two chunks
+        big = np.empty((P, 16, 3, 3), np.float32)
+        big[:] = cx["lig_pos"][None]
+        big += rng.standard_normal((P, 1, 1, 3)).astype(np.float32)
+        for i in (0, 116507, 116508, P - 1):
+            big[i] = probe
+        ob = nat.metrics(big)
+        for i in (0, 116507, 116508, P - 1):
+            _same(one, ob, 0, i)
+        _same(nat.metrics(big[1000:1200]), ob, slice(None), slice(1000, 1200))
+        # moving receptor too
+        recs = np.repeat(np.asarray(cx["rec_pos"], np.float32)[None], 1000, 0)
+        _same(nat.metrics(probe[None], recs[:1]), nat.metrics(mid, recs), 0, 500)
+        # two threads at once, next to a sampling handle
+        a, b = mid, big[:20000]
+        serial = [nat.metrics(a), nat.metrics(b)]
+        gx = engine.Complex(model, cx["rec_x"], cx["lig_x"], cx["rec_pos"], cx["lig_pos"])
+        ref_s = gx.sample(B=8, num_steps=6, seed=2, mfma16=True)
+        res, errs = [None, None], []
+
+        def work(i, x):
+            try:
+                res[i] = [nat.metrics(x) for _ in range(4)]
+            except BaseException as e:      # noqa: BLE001
+                errs.append(e)
+        th = [threading.Thread(target=work, args=(i, x)) for i, x in enumerate((a, b))]
+        for t in th:
+            t.start()
+        s = gx.sample(B=8, num_steps=6, seed=2, mfma16=True)
+        for t in th:
+            t.join()
+        gx.close()
+        assert not errs, errs
+        assert np.array_equal(s["lig_pos"], ref_s["lig_pos"])
+        for i in range(2):
+            for r in res[i]:
+                _same(r, serial[i], slice(None), slice(None))
+
+
+def test_degenerate_and_bad_input(model):
+    """Gate 5."""
+    import ctypes as C
+    from dfmdock_amd import _lib as L
+    cx = complex_for("fwd_syn_24_16")
+    far = (cx["lig_pos"] + np.float32([100.0, 0, 0])).astype(np.float32)
+    rng = np.random.default_rng(5)
+    with model.native(cx["rec_pos"], far) as nat:
+        info = nat.info()
+        assert info["n_iface_rec"] == info["n_iface_lig"] == info["n_contacts"] == 0
+        o = nat.metrics(perturbations(far, rng, 6))
+        assert np.isnan(o["i_rmsd"]).all() and np.isnan(o["DockQ"]).all() and (o["fnat"] == 0).all() and (o["n_recovered"] == 0).all()
+        assert np.isfinite(o["c_rmsd"]).all() and np.isfinite(o["l_rmsd"]).all() and o["l_rmsd"][3] > 0.1
+    native = (cx["rec_pos"], cx["lig_pos"])
+    poses = perturbations(cx["lig_pos"], rng, 12)
+    with model.native(*native) as nat:
+        clean = nat.metrics(poses)
+        dirty = poses.copy()
+        dirty[5] = np.nan
+        o = nat.metrics(dirty)
+        # (metrics.py itself raises on a NaN pose - numpy's SVD does not converge - so the expectation is stated here: NaN RMSDs and DockQ,
+        # no contact found)
+        for k in RMSD_KEYS + ("DockQ",):
+            assert np.isnan(o[k][5]), k
+        assert o["fnat"][5] == 0.0 and o["n_recovered"][5] == 0
+        keep = np.arange(12) != 5
+        for k in o:
+            assert o[k][keep].tobytes() == clean[k][keep].tobytes(), k
+        # bad arguments: DFM_E_INVALID (-1) and a message, nothing launched
+        lib, h = L.lib(), nat._h
+        lp = np.ascontiguousarray(poses.reshape(12, -1))
+        out = L.MetricsOutC()
+        f = lambda a: a.ctypes.data_as(L.F32P)
+        for args in ((h, 0, f(lp), None, C.byref(out)), (h, -3, f(lp), None, C.byref(out)), (h, 12, None, None, C.byref(out)),
+                     (None, 12, f(lp), None, C.byref(out)), (h, 12, f(lp), None, None)):
+            assert lib.dfm_pose_metrics(*args) == -1 and lib.dfm_last_error()
+        with pytest.raises(ValueError):
+            nat.metrics(poses[:, :5])
+    rp, lg = (np.ascontiguousarray(x, np.float32).reshape(-1, 9) for x in native)
+    for args in ((model._h, f(rp), f(lg), 24, 16, float("nan"), 5.5), (model._h, f(rp), f(lg), 24, 16, 10.0, float("inf")),
+                 (model._h, None, f(lg), 24, 16, 10.0, 5.5), (model._h, f(rp), f(lg), 0, 16, 10.0, 5.5), (None, f(rp), f(lg), 24, 16, 10.0, 5.5)):
+        assert not lib.dfm_native_create(*args) and lib.dfm_last_error()
+    with pytest.raises(ValueError):
+        model.native(cx["rec_pos"], cx["lig_pos"], iface_cutoff=float("nan"))
+    assert lib.dfm_native_info(None, None, None, None, None, None, None) == -1
+
+
+# ---- gate 6: drivers and command line ---------------------------------------------------------------------------------------------
+def _fixture_set():
+    cxs = []
+    for name, case in (("SYN1", "fwd_syn_24_16"), ("SYN2", "fwd_syn_64_48_p0"), ("7CEI", "fwd_7CEI_p0")):
+        c = dict(complex_for(case))
+        c["id"] = name
+        cxs.append(c)
+    return cxs
+
+
+RUN_KW = dict(num_samples=12, num_steps=6, seed=1, max_batch=8, log=lambda m: None)
+METRIC_COLS = ("c_rmsd", "i_rmsd", "l_rmsd", "fnat", "DockQ")
+
+
+def test_run_set_gpu_metrics_and_step_table(model, tmp_path):
+    from dfmdock_amd import driver
+    from dfmdock_amd.metrics import NativeContext, compute_metrics
+    cxs = _fixture_set()
+    h0, _ = driver.run_set(model, cxs, out_csv=str(tmp_path / "default.csv"), **RUN_KW)
+    h1, _ = driver.run_set(model, cxs, out_csv=str(tmp_path / "host.csv"), metrics="host", **RUN_KW)
+    assert open(tmp_path / "default.csv", "rb").read() == open(tmp_path / "host.csv", "rb").read()
+    assert list(csv.DictReader(open(tmp_path / "default.csv")))[0].keys() == set(driver.CSV_FIELDS) and h0 == h1
+    g, _ = driver.run_set(model, cxs, out_csv=str(tmp_path / "gpu.csv"), metrics="gpu", **RUN_KW)
+    assert len(g) == len(h0) == 36
+    for a, b in zip(sorted(h0, key=lambda r: (r["id"], int(r["index"]))), sorted(g, key=lambda r: (r["id"], int(r["index"])))):
+        assert a.keys() == b.keys()
+        for k in a:
+            if k in RMSD_KEYS or k == "DockQ":
+                print(a["id"], a["index"], k, "host", a[k], "gpu", b[k])
+                assert b[k] == pytest.approx(a[k], **TOL), (a["id"], a["index"], k)
+            else:      # fnat included: the trajectories of this seeded run have no contact pair within 1e-3 A of the cutoff
+                assert a[k] == b[k], (a["id"], a["index"], k)
+    assert list(csv.DictReader(open(tmp_path / "gpu.csv")))[0].keys() == set(driver.CSV_FIELDS)
+    # every step of every trajectory
+    steps = []
+    gs, _ = driver.run_set(model, cxs, metrics="gpu", step_metrics=True, steps_out=steps, step_csv=str(tmp_path / "steps.csv"), **RUN_KW)
+    assert gs == g      # the rows of the final poses do not change with the trace
+    assert len(steps) == 3 * 12 * 6
+    table = list(csv.DictReader(open(tmp_path / "steps.csv")))
+    assert len(table) == len(steps) and list(table[0]) == driver.STEP_FIELDS
+    ts = np.linspace(1.0, 1e-3, 6)
+    assert all(float(r["t"]) == float(ts[int(r["step"])]) for r in table)
+    # one complex stage by stage, with its poses in hand
+    rots = [np.random.default_rng(1).integers(0, 2 ** 31)]
+    c = cxs[2]
+    p = driver._prepare(model, c, 0, rots[0], True, "mfma16", False, "fp32", 1)
+    batches = driver._sample(p, 0, 12, 6, 1, 8, True, {"step_energy": False})
+    rows, _, st = driver._post(p, batches, None, model, "gpu", True)
+    ctx = NativeContext((p.rec_pos, p.lig_pos))
+    by = {(r["index"], r["step"]): r for r in st}
+    cells, rng = [], np.random.default_rng(9)
+    for done, b, r in batches:
+        assert np.array_equal(r["trace_pose"][:, -1], r["lig_pos"])      # the trace's last frame IS the final pose, bit for bit
+        for k in range(b):
+            row = next(x for x in rows if x["index"] == str(done + k))
+            for f in METRIC_COLS:
+                a, bb = by[(str(done + k), 5)][f], row[f]
+                assert a == bb or (np.isnan(a) and np.isnan(bb)), (done + k, f)
+            cells += [(r, k, done + k, s) for s in range(6)]
+    for r, k, idx, s in [cells[i] for i in rng.choice(len(cells), 64, replace=False)]:
+        want = compute_metrics((p.rec_pos, r["trace_pose"][k, s]), (p.rec_pos, p.lig_pos), ctx)
+        for f in RMSD_KEYS + ("DockQ", "fnat"):
+            print("7CEI", idx, s, f, "gpu", by[(str(idx), s)][f], "definition", want[f])
+            assert by[(str(idx), s)][f] == pytest.approx(want[f], **TOL), (idx, s, f)
+
+
+def _run(args, cwd):
+    return subprocess.run([sys.executable, "-m", "dfmdock_amd"] + args, cwd=cwd, capture_output=True, text=True, timeout=900,
+                          env=dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", "")))
+
+
+def test_cli_dock_and_refine_with_native(tmp_path):
+    """`dock --native` / `refine --native` on 7CEI with a seeded checkpoint.  The metrics on the result line equal compute_metrics of
+    the kept pose: within gate 1 for the backbone rebuilt from the line's own rot_update / tr_update, and within 1e-3 A for the backbone
+    read back from the written PDB - its coordinates carry three decimals, each is off by at most 5e-4 A, and an RMSD (a norm of the
+    coordinate differences, minimised over the fit) moves by at most the RMS of the coordinate changes, sqrt(3) x 5e-4 < 1e-3."""
+    from cli_fixtures import golden_7cei, write_ckpt, write_pair
+    from dfmdock_amd import pdbio
+    from dfmdock_amd.cluster import rebuild_backbone
+    from dfmdock_amd.metrics import compute_metrics
+    cx, rs, ls = golden_7cei()
+    rec_pdb, lig_pdb, feat = write_pair(str(tmp_path), cx, rs, ls)
+    ck = str(tmp_path / "model_0.ckpt")
+    write_ckpt(ck, seed=0)
+    rec = pdbio.backbone_from_atoms(pdbio.read_pdb(rec_pdb))
+    lig = pdbio.backbone_from_atoms(pdbio.read_pdb(lig_pdb))
+    native = (np.asarray(rec["bb_coords"], np.float32), np.asarray(lig["bb_coords"], np.float32))
+    R = len(rec["bb_coords"])
+
+    def check(m, pose, label, tol):
+        want = compute_metrics((native[0], pose), native)
+        assert set(m) == set(METRIC_COLS)
+        for k in RMSD_KEYS:
+            print(label, k, "line", m[k], "definition", want[k])
+            assert m[k] == pytest.approx(want[k], **tol), (label, k)
+        return want
+
+    for cmd, extra in (("dock", ["--num-samples", "8", "--top-k", "2", "--cluster-radius", "2.0", "--refine-t", "0.1", "--refine-samples", "2"]),
+                       ("refine", ["--num-samples", "4", "--t-begin", "0.1"])):
+        d = tmp_path / cmd
+        d.mkdir()
+        base = [cmd, rec_pdb, lig_pdb, "--ckpt", ck, "--features", feat, "--seed", "3", "--max-batch", "8"] + extra
+        p0 = _run(base, cwd=str(d))
+        assert p0.returncode == 0, p0.stdout + p0.stderr
+        plain = json.loads(p0.stdout.strip().splitlines()[-1])
+        plain_pdb = open(d / "output.pdb", "rb").read()
+        p = _run(base + ["--native", rec_pdb, lig_pdb], cwd=str(d))
+        assert p.returncode == 0, p.stdout + p.stderr
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert open(d / "output.pdb", "rb").read() == plain_pdb
+        assert "metrics" not in plain and set(line["metrics"]) == set(METRIC_COLS)
+        strip = lambda o: {k: ([{a: b for a, b in m.items() if "metrics" not in a} for m in v] if k == "models" else v)
+                           for k, v in o.items() if "metrics" not in k}
+        assert strip(line) == plain      # everything else on the line is what it was
+        pose = rebuild_backbone(native[1], np.float32(line["rot_update"])[None], np.float32(line["tr_update"])[None])[0]
+        want = check(line["metrics"], pose, cmd, TOL)
+        assert line["metrics"]["fnat"] == want["fnat"] and line["metrics"]["DockQ"] == pytest.approx(want["DockQ"], **TOL)
+        written = pdbio.backbone_from_atoms(pdbio.read_pdb(str(d / "output.pdb")))["bb_coords"][R:]
+        check(line["metrics"], np.asarray(written, np.float32), cmd + " (PDB)", dict(rel=0, abs=1e-3))
+        if cmd == "dock":
+            assert len(line["models"]) >= 1
+            for m in line["models"]:
+                assert set(m["metrics"]) == set(m["refined_metrics"]) == set(METRIC_COLS)
+                wr = pdbio.backbone_from_atoms(pdbio.read_pdb(m["path"]))["bb_coords"][R:]
+                check(m["refined_metrics"], np.asarray(wr, np.float32), f"model {m['rank']} refined (PDB)", dict(rel=0, abs=1e-3))
+        else:
+            assert line["start_metrics"]["fnat"] == 1.0 and line["start_metrics"]["l_rmsd"] < 1e-4      # the input pose is the native
+    bad = _run(["dock", rec_pdb, lig_pdb, "--ckpt", ck, "--features", feat, "--num-samples", "4", "--native", lig_pdb, rec_pdb], cwd=str(tmp_path))
+    assert bad.returncode != 0 and f"{len(lig['bb_coords'])} receptor / {R} ligand residues" in bad.stderr
