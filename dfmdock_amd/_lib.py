@@ -43,6 +43,7 @@ EXPORTS = [
     "dfm_complex_set_restraints", "dfm_restraint_eval", "dfm_pose_rmsd", "dfm_pose_cluster", "dfm_pose_last_timing",
     "dfm_refine", "dfm_forward_marginal", "dfm_igso3_table",
     "dfm_native_create", "dfm_native_destroy", "dfm_native_info", "dfm_pose_metrics", "dfm_metrics_last_timing",
+    "dfm_pose_consensus", "dfm_consensus_chunk_poses", "dfm_consensus_last_timing",
 ]
 
 
@@ -105,6 +106,11 @@ class MetricsOutC(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_double)) for n in ("c_rmsd", "i_rmsd", "l_rmsd", "fnat", "dockq")] + [("n_recovered", I32P)]
 
 
+class ConsensusOutC(C.Structure):
+    _fields_ = [("count", I32P), ("rec_count", I32P), ("lig_count", I32P), ("n_contacts", I32P), ("score_sum", C.POINTER(C.c_int64)),
+                ("bits", C.POINTER(C.c_uint64))]
+
+
 _lib = None
 
 
@@ -159,6 +165,10 @@ def lib():
     L.dfm_native_info.argtypes = [C.c_void_p, I32P, I32P, I32P, I32P, I32P, I32P]
     L.dfm_pose_metrics.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.POINTER(MetricsOutC)]
     L.dfm_metrics_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_pose_consensus.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, F32P, F32P, C.POINTER(C.c_uint8), C.c_float,
+                                     C.POINTER(ConsensusOutC)]
+    L.dfm_consensus_chunk_poses.argtypes = [C.c_int, C.c_int]
+    L.dfm_consensus_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_trim_cache.argtypes = [C.c_int]
     L.dfm_trim_cache.restype = C.c_longlong
     L.dfm_diffusion_coef.argtypes = [C.POINTER(HParamsC), C.c_int, C.c_double, C.POINTER(C.c_double),

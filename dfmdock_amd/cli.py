@@ -11,6 +11,9 @@
     python -m dfmdock_amd dock ... --top-k K --refine-t T [--refine-samples 8]
     python -m dfmdock_amd dock|refine ... --native NATIVE_REC.pdb NATIVE_LIG.pdb
     python -m dfmdock_amd sweep ... --metrics gpu [--step-metrics steps.csv]
+    python -m dfmdock_amd dock|refine ... --consensus [--rank consensus] [--consensus-top 0.5] [--contact-map map.npz]
+    python -m dfmdock_amd dock|refine ... --write-restraints consensus.txt --restraint-top 10 [--restraint-upper 8.0]
+    python -m dfmdock_amd sweep ... --consensus [--consensus-top 0.5]
 
   dock       <- src/inference_single.py:1-12 -> inference() (src/inference_base.py:601-670): num_samples (120) trajectories of
                 num_steps (40), the minimum-energy one applied to the all-atom ligand, `output.pdb` written, {"energy": E} printed.
@@ -40,6 +43,15 @@
              definition; the CSV differs from the host's in the last digits), `sweep --step-metrics FILE.csv` (implies --metrics gpu)
              writes the metrics after EVERY step of every trajectory and adds, per complex, the step at which the minimum-energy
              trajectory first reaches DockQ >= 0.23 and the best DockQ seen along any trajectory to the summary.
+  consensus  no reference counterpart: CONSRANK-style consensus contact scoring of the trajectories on the GPU (dfmdock_amd/consensus.py,
+             dfm_pose_consensus) - a ranking that needs neither a native nor the energy head.  `dock / refine --consensus` add the
+             consensus score, consensus rank and contact count of the kept pose to the result line; `--rank consensus` keeps the pose
+             with the highest consensus instead of the minimum energy (and makes that order the clustering key of --top-k);
+             `--contact-map FILE.npz` writes the R x L contact counts and frequencies, the per-residue interface counts and the residue
+             labels; `--write-restraints FILE --restraint-top N` writes the N most frequent contacts as a restraint file for a second,
+             guided run (`dock --restraints FILE`).  `--consensus-top FRAC`: only the best FRAC of the trajectories by energy are members
+             of the ensemble (all are scored).  `sweep --consensus` appends `consensus` and `n_contacts` to the CSV and adds the DockQ
+             success rates of the consensus-selected trajectory to the table.
   selfcheck  no reference counterpart: dfm_complex_selfcheck on the pair (what `dock` and `sweep` run once per complex anyway).
 
 --ckpt takes the Lightning checkpoint the reference loads (src/inference_base.py:611-616; read without Lightning / omegaconf by
@@ -61,6 +73,22 @@ DOCKQ_THRESHOLDS = (("acceptable", 0.23), ("medium", 0.49), ("high", 0.80))     
 def _add_native(p):
     p.add_argument("--native", nargs=2, default=None, metavar=("REC.pdb", "LIG.pdb"),
                    help="native complex (same residues as the input, any frame): add c_rmsd / i_rmsd / l_rmsd / fnat / DockQ to the result")
+
+
+def _add_consensus(p):
+    p.add_argument("--consensus", action="store_true",
+                   help="score the trajectories by consensus contacts (adds a `consensus` object to the result line)")
+    p.add_argument("--rank", default="energy", choices=["energy", "consensus"],
+                   help="which trajectory is kept: the minimum energy (default) or the highest consensus score (implies --consensus)")
+    p.add_argument("--consensus-top", type=float, default=None, metavar="FRAC",
+                   help="with --consensus: members of the ensemble are the best FRAC of the trajectories by energy (default 1.0: all)")
+    p.add_argument("--contact-map", default=None, metavar="FILE.npz",
+                   help="write the consensus contact map: count, freq, rec_count, lig_count, M, cutoff, residue labels (implies --consensus)")
+    p.add_argument("--write-restraints", default=None, metavar="FILE",
+                   help="write the --restraint-top most frequent consensus contacts as a restraint file (implies --consensus)")
+    p.add_argument("--restraint-top", type=int, default=None, metavar="N", help="with --write-restraints: number of contacts (default 10)")
+    p.add_argument("--restraint-upper", type=float, default=None, metavar="U",
+                   help="with --write-restraints: upper bound on the CA-CA distance of every written contact (A, default 8.0)")
 
 
 def _add_common(p):
@@ -99,6 +127,7 @@ def build_parser():
                    help="with --top-k: refine every cluster centre locally from t_begin = T (one batched call)")
     d.add_argument("--refine-samples", type=int, default=8, metavar="n", help="with --refine-t: trajectories per cluster centre")
     _add_native(d)
+    _add_consensus(d)
     _add_common(d)
     r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)")
     r.add_argument("pdb_1", help="receptor PDB")
@@ -111,6 +140,7 @@ def build_parser():
     r.add_argument("--json", default=None, help="also write the result line to this file")
     r.add_argument("--restraints", default=None, help="interface restraint file (as for dock)")
     _add_native(r)
+    _add_consensus(r)
     _add_common(r)
     s = sub.add_parser("sweep", help="sample every complex of a DB5-style directory (inference_mlsb.py run_sampling)")
     s.add_argument("--db5", required=True, help="directory of <id>.pt files (+ optional test.txt with the ids to run)")
@@ -131,6 +161,11 @@ def build_parser():
                    help="where the final poses are scored: host (default, numpy) or gpu (dfm_pose_metrics, one call per complex)")
     s.add_argument("--step-metrics", default=None, metavar="FILE.csv",
                    help="also write the metrics after every step of every trajectory (implies --metrics gpu)")
+    s.add_argument("--consensus", action="store_true",
+                   help="consensus contact score of every trajectory within its complex (adds consensus / n_contacts to the CSV and the "
+                        "success rates of the consensus-selected trajectory to the table)")
+    s.add_argument("--consensus-top", type=float, default=None, metavar="FRAC",
+                   help="with --consensus: members of the ensemble are the best FRAC of a complex's trajectories by energy")
     _add_common(s)
     c = sub.add_parser("selfcheck", help="fp32-vs-16-bit check + fp16 range telemetry of one pair")
     c.add_argument("pdb_1")
@@ -148,6 +183,23 @@ def parse_args(argv=None):
         ap.error("--refine-t refines the cluster centres: it needs --top-k")
     if args.cmd == "sweep" and args.step_metrics is not None:
         args.metrics = "gpu"
+    if args.cmd in ("dock", "refine"):
+        if args.rank == "consensus" or args.contact_map or args.write_restraints:
+            args.consensus = True
+        if not args.write_restraints and (args.restraint_top is not None or args.restraint_upper is not None):
+            ap.error("--restraint-top / --restraint-upper describe the file of --write-restraints: they need it")
+        args.restraint_top = 10 if args.restraint_top is None else args.restraint_top
+        args.restraint_upper = 8.0 if args.restraint_upper is None else args.restraint_upper
+        if args.restraint_top < 1:
+            ap.error("--restraint-top must be >= 1")
+        if not (args.restraint_upper > 0 and np.isfinite(args.restraint_upper)):
+            ap.error("--restraint-upper must be finite and > 0")
+    if args.cmd in ("dock", "refine", "sweep"):
+        if args.consensus_top is not None and not args.consensus:
+            ap.error("--consensus-top selects the members of the consensus ensemble: it needs --consensus")
+        args.consensus_top = 1.0 if args.consensus_top is None else args.consensus_top
+        if not (0.0 < args.consensus_top <= 1.0):
+            ap.error("--consensus-top must be in (0, 1]")
     return args
 
 
@@ -212,6 +264,65 @@ def step_summary(step_rows, rows, threshold=0.23):
                 and float(s["DockQ"]) >= threshold:
             o["top1_first_acceptable_step"] = int(s["step"])
     return out
+
+
+def residue_labels(chain):
+    """`chain:resnum[icode]` of every residue of a pdbio.backbone_from_atoms dict, the names restraint files use."""
+    return np.array([f"{k[0]}:{int(k[1])}{k[2] if k[2] != ' ' else ''}" for k in chain["residues"]])
+
+
+def consensus_kwargs(args):
+    """Driver keyword arguments of the consensus flags of dock / refine: none without them."""
+    if not args.consensus:
+        return {}
+    return dict(consensus=True, rank=args.rank, consensus_top=args.consensus_top)
+
+
+def consensus_outputs(args, res, rec, lig, line):
+    """The consensus part of a dock / refine result: the `consensus` object of the line, --contact-map and --write-restraints."""
+    if not args.consensus:
+        return
+    from . import consensus as CS
+    cd = res["consensus_data"]
+    line.update(consensus=res["consensus"], index=res["index"])
+    if args.contact_map:
+        np.savez(args.contact_map, count=cd["count"], freq=cd["freq"], rec_count=cd["rec_count"], lig_count=cd["lig_count"],
+                 M=np.int64(cd["M"]), cutoff=np.float64(cd["cutoff"]), rec_residues=residue_labels(rec), lig_residues=residue_labels(lig))
+        line.update(contact_map=os.path.abspath(args.contact_map))
+    if args.write_restraints:
+        groups = CS.contact_groups(cd["count"], cd["M"], args.restraint_top, upper=args.restraint_upper)
+        CS.write_restraints(args.write_restraints, groups, rec, lig,
+                            header=f"top {len(groups)} consensus contacts of {len(cd['consensus'])} trajectories ({cd['M']} members, "
+                                   f"contact cutoff {cd['cutoff']:g} A): REC LIG UPPER WEIGHT(= contact frequency)")
+        line.update(restraints_written=os.path.abspath(args.write_restraints), restraints_written_n=len(groups))
+
+
+def consensus_table(rows):
+    """Per complex the trajectory consensus ranking keeps (highest consensus, ties: lower energy, lower index; no contact anywhere: the
+    minimum energy) with its DockQ, and the success rates of that choice at the CAPRI thresholds."""
+    from . import consensus as CS
+    by = {}
+    for r in rows:
+        by.setdefault(r["id"], []).append(r)
+    per = {}
+    for cid, rs in sorted(by.items()):
+        rs = sorted(rs, key=lambda r: int(r["index"]))
+        k = CS.pick([float(r["consensus"]) for r in rs], [float(r["energy"]) for r in rs])
+        top = rs[k] if k is not None else min(rs, key=lambda r: (r["energy"], int(r["index"])))
+        per[cid] = {"index": int(top["index"]), "consensus": float(top["consensus"]), "n_contacts": int(top["n_contacts"]),
+                    "DockQ": float(top["DockQ"]), "energy": float(top["energy"]), "fallback": k is None}
+    n = max(len(per), 1)
+    return per, {name: {"threshold": thr, "consensus_top1": sum(p["DockQ"] >= thr for p in per.values()) / n} for name, thr in DOCKQ_THRESHOLDS}
+
+
+def format_consensus_table(per, table, energy_table):
+    lines = [f"consensus-selected trajectory ({sum(p['fallback'] for p in per.values())} of {len(per)} complexes without any contact: energy pick):"]
+    for cid, p in per.items():
+        lines.append(f"{cid:8s} index {p['index']:4d} consensus {p['consensus']:8.4f} contacts {p['n_contacts']:5d} DockQ {p['DockQ']:8.4f}")
+    for name, t in table.items():
+        lines.append(f"  {name:10s} DockQ >= {t['threshold']:.2f}: consensus pick {100 * t['consensus_top1']:5.1f} % | energy pick "
+                     f"{100 * energy_table[name]['top1']:5.1f} %")
+    return "\n".join(lines)
 
 
 def success_table(rows, top_k=None):
@@ -291,6 +402,7 @@ def cmd_dock(args):
         kw.update(refine_t=args.refine_t, refine_samples=args.refine_samples)
     if args.native:
         kw.update(native=load_native(args.native))
+    kw.update(consensus_kwargs(args))
     res = driver.dock_pair(model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                            precision=args.precision, out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
                            on_selfcheck_fail=args.on_selfcheck_fail, **kw)
@@ -307,6 +419,7 @@ def cmd_dock(args):
         line.update(refine_t=args.refine_t, refine_samples=args.refine_samples)
     if args.native:
         line.update(metrics=res["metrics"])
+    consensus_outputs(args, res, rec, lig, line)
     print(json.dumps(line), flush=True)
     if args.json:
         extra = {}
@@ -327,6 +440,7 @@ def cmd_refine(args):
         kw = dict(restraints=read_restraints(args.restraints, rec, lig))
     if args.native:
         kw.update(native=load_native(args.native))
+    kw.update(consensus_kwargs(args))
     res = driver.refine_pair(model, rec, lig, rec_x, lig_x, t_begin=args.t_begin, num_samples=args.num_samples, num_steps=args.num_steps,
                              seed=args.seed, precision=args.precision, out_pdb=args.out, max_batch=args.max_batch,
                              selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, perturb=not args.no_perturb, **kw)
@@ -336,6 +450,7 @@ def cmd_refine(args):
             "selfcheck_ok": None if res["selfcheck"] is None else bool(res["selfcheck"]["ok"])}
     if args.native:
         line.update(metrics=res["metrics"], start_metrics=res["start_metrics"])
+    consensus_outputs(args, res, rec, lig, line)
     print(json.dumps(line), flush=True)
     if args.json:
         with open(args.json, "w") as f:
@@ -385,6 +500,8 @@ def cmd_sweep(args):
         rkw.update(metrics=args.metrics)
     if args.step_metrics is not None:
         rkw.update(step_csv=args.step_metrics, steps_out=steps)
+    if args.consensus:
+        rkw.update(consensus=True, consensus_top=args.consensus_top)
     rows, _ = driver.run_set(model, cxs, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                              precision=args.precision, global_rotation=not args.no_global_rotation, out_csv=args.out_csv,
                              traj_dir=args.traj_dir, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
@@ -402,6 +519,10 @@ def cmd_sweep(args):
         if args.step_metrics is not None:
             extra["step_metrics"] = step_summary(all_steps, all_rows)
             extra["step_csv"] = os.path.abspath(args.step_metrics)
+        if args.consensus:
+            cper, ctable = consensus_table(all_rows)
+            print(format_consensus_table(cper, ctable, table), flush=True)
+            extra["consensus"] = {"complexes": cper, "success": ctable, "members_fraction": args.consensus_top}
         if args.summary:
             with open(args.summary, "w") as f:
                 json.dump({"csv": os.path.abspath(args.out_csv), "complexes": per, "success": table, "selfcheck": all_checks,

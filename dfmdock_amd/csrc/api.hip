@@ -1257,6 +1257,111 @@ extern "C" int dfm_metrics_last_timing(double *copy_ms, double *kernel_ms)
     return DFM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Consensus contact scoring (kernels_consensus.hip).  Bound to the model handle's device only, like the clustering calls; every call owns
+// its stream and temporaries.  A chunk holds its poses and their contact bits; a call of one chunk keeps the bits between the counting
+// and the scoring pass, a longer call uploads and evaluates every chunk again in the scoring pass.
+constexpr size_t CONSENSUS_CHUNK_BYTES = (size_t)256 << 20;
+constexpr int CONSENSUS_MAX_POSES = 65536;
+static thread_local double g_consensus_ms[2] = {0.0, 0.0};      // host-to-device copies, kernels of this thread's last dfm_pose_consensus
+
+extern "C" int dfm_consensus_chunk_poses(int R, int L)
+{
+    if (R < 1 || L < 1) return 0;
+    const size_t per_pose = (size_t)L * 9 * sizeof(float) + (size_t)R * (size_t)((L + 63) / 64) * sizeof(uint64_t);
+    return (int)std::min<size_t>(32768, std::max<size_t>(1, CONSENSUS_CHUNK_BYTES / per_pose));      // (a launch takes 65535 poses)
+}
+
+extern "C" int dfm_pose_consensus(dfm_model *m, int P, int R, int L, const float *rec_pos, const float *lig_pos, const uint8_t *member,
+                                  float cutoff, dfm_consensus_out *out)
+{
+    if (!m) return fail(DFM_E_INVALID, "m is NULL");
+    if (!rec_pos) return fail(DFM_E_INVALID, "rec_pos is NULL");
+    if (!lig_pos) return fail(DFM_E_INVALID, "lig_pos is NULL");
+    if (!out) return fail(DFM_E_INVALID, "out is NULL");
+    if (P < 1 || P > CONSENSUS_MAX_POSES) return fail(DFM_E_INVALID, "P must be in 1 .. " + std::to_string(CONSENSUS_MAX_POSES));
+    if (R < 1 || L < 1) return fail(DFM_E_INVALID, "need R >= 1 and L >= 1");
+    if ((int64_t)R * L > ((int64_t)1 << 27)) return fail(DFM_E_INVALID, "R x L exceeds 2^27 residue pairs");
+    if (!std::isfinite(cutoff) || !(cutoff > 0.f)) return fail(DFM_E_INVALID, "cutoff must be finite and > 0");
+    std::vector<uint8_t> mem((size_t)P, 1);
+    if (member) {
+        size_t M = 0;
+        for (int p = 0; p < P; ++p) M += (mem[(size_t)p] = member[p] ? 1 : 0);
+        if (M == 0) return fail(DFM_E_INVALID, "member: no pose is a member");
+    }
+    DEVICE_SCOPE(m->device);
+    PoseCall c;
+    HIPCHK(c.open());
+    const int W = (L + 63) / 64, Pc = std::min(P, dfm_consensus_chunk_poses(R, L));
+    const size_t lig_n = (size_t)L * 9, words = (size_t)W * R, RL = (size_t)R * L;
+    const bool one_chunk = Pc >= P, want_count = out->count || out->rec_count || out->lig_count || out->score_sum;
+    const bool want_pose = out->n_contacts || out->score_sum;
+    float *d_rec = nullptr, *X = nullptr;
+    uint8_t *d_mem = nullptr;
+    uint64_t *d_bits = nullptr;
+    int32_t *d_count = nullptr, *d_marg = nullptr, *d_n = nullptr;
+    int64_t *d_sum = nullptr;
+    HIPCHK(c.tmp.upload_async(&d_rec, rec_pos, (size_t)R * 9, c.s));
+    HIPCHK(c.tmp.upload_async(&d_mem, mem.data(), mem.size(), c.s));
+    HIPCHK(c.tmp.alloc(&X, (size_t)Pc * lig_n));
+    HIPCHK(c.tmp.alloc(&d_bits, (size_t)Pc * words));
+    HIPCHK(c.tmp.alloc(&d_count, RL));
+    HIPCHK(c.tmp.alloc(&d_marg, (size_t)R + L));      // rec_count | lig_count
+    HIPCHK(c.tmp.alloc(&d_n, (size_t)Pc));
+    HIPCHK(c.tmp.alloc(&d_sum, (size_t)Pc));
+    HIPCHK(hipMemsetAsync(d_count, 0, RL * sizeof(int32_t), c.s));
+    HIPCHK(hipMemsetAsync(d_marg, 0, ((size_t)R + L) * sizeof(int32_t), c.s));
+    std::vector<uint64_t> h_bits(out->bits ? (size_t)Pc * words : 0);
+    double copy_ms = 0.0, kernel_ms = 0.0;
+    // pass 0: bits and counts of every chunk; pass 1: per-pose sums against the finished counts
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1 && !want_pose) break;
+        for (int p0 = 0; p0 < P; p0 += Pc) {
+            const int n = std::min(Pc, P - p0);
+            HIPCHK(hipEventRecord(c.ev[0], c.s));
+            if (pass == 0 || !one_chunk)
+                HIPCHK(hipMemcpyAsync(X, lig_pos + (size_t)p0 * lig_n, (size_t)n * lig_n * sizeof(float), hipMemcpyHostToDevice, c.s));
+            HIPCHK(hipEventRecord(c.ev[1], c.s));
+            if (pass == 0 || !one_chunk) HIPCHK(launch_contact_bits(d_rec, X, n, R, L, cutoff, d_bits, c.s));
+            if (pass == 0 && want_count) HIPCHK(launch_contact_count(d_bits, d_mem + p0, n, R, L, d_count, d_marg, d_marg + R, c.s));
+            if (pass == 1) HIPCHK(launch_contact_score(d_bits, d_count, n, R, L, d_n, d_sum, c.s));
+            HIPCHK(hipEventRecord(c.ev[2], c.s));
+            if (pass == 0 && out->bits)
+                HIPCHK(hipMemcpyAsync(h_bits.data(), d_bits, (size_t)n * words * sizeof(uint64_t), hipMemcpyDeviceToHost, c.s));
+            if (pass == 1 && out->n_contacts)
+                HIPCHK(hipMemcpyAsync(out->n_contacts + p0, d_n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+            if (pass == 1 && out->score_sum)
+                HIPCHK(hipMemcpyAsync(out->score_sum + p0, d_sum, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
+            HIPCHK(hipStreamSynchronize(c.s));
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) copy_ms += ms;
+            if (hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess) kernel_ms += ms;
+            if (pass == 0 && out->bits)      // device [n][W][R] -> the ABI's [P][R][W]
+                for (int p = 0; p < n; ++p)
+                    for (int w = 0; w < W; ++w) {
+                        const uint64_t *src = h_bits.data() + ((size_t)p * W + w) * R;
+                        uint64_t *dst = out->bits + (size_t)(p0 + p) * words + w;
+                        for (int i = 0; i < R; ++i) dst[(size_t)i * W] = src[i];
+                    }
+        }
+    }
+    if (out->count) HIPCHK(hipMemcpyAsync(out->count, d_count, RL * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+    if (out->rec_count) HIPCHK(hipMemcpyAsync(out->rec_count, d_marg, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+    if (out->lig_count) HIPCHK(hipMemcpyAsync(out->lig_count, d_marg + R, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+    HIPCHK(hipStreamSynchronize(c.s));
+    g_consensus_ms[0] = copy_ms;
+    g_consensus_ms[1] = kernel_ms;
+    return DFM_OK;
+}
+
+extern "C" int dfm_consensus_last_timing(double *copy_ms, double *kernel_ms)
+{
+    if (!copy_ms || !kernel_ms) return fail(DFM_E_INVALID, "NULL argument");
+    *copy_ms = g_consensus_ms[0];
+    *kernel_ms = g_consensus_ms[1];
+    return DFM_OK;
+}
+
 extern "C" int dfm_complex_degree(const dfm_complex *cx) { return cx ? cx->K : -1; }
 
 extern "C" long long dfm_trim_cache(int device)

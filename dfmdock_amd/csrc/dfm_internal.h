@@ -406,4 +406,15 @@ hipError_t launch_metrics_finish(const MetricsChain &lig, const MetricsChain &re
                                  const MetricsConst &mc, const int32_t *contacts, int P, double *xf, double *rmsd, int32_t *recovered,
                                  hipStream_t s);
 
+// consensus contact scoring (kernels_consensus.hip; include/dfmdock_amd.h: dfm_pose_consensus).  n poses of one chunk: rec [R][9],
+// lig [n][L][9]; bits [n][W][R] uint64 with W = ceil(L / 64): bit j % 64 of word (p, j / 64, i) = contact (i, j) of pose p, unused high
+// bits 0 (the transpose of the C ABI's [P][R][W]).  member [n]: 1 = the pose counts.  count [R][L], rec_count [R], lig_count [L] are
+// ADDED to (zero them before the first chunk).
+hipError_t launch_contact_bits(const float *rec, const float *lig, int n, int R, int L, float cutoff, uint64_t *bits, hipStream_t s);
+hipError_t launch_contact_count(const uint64_t *bits, const uint8_t *member, int n, int R, int L, int32_t *count, int32_t *rec_count,
+                                int32_t *lig_count, hipStream_t s);
+// per pose, members or not: n_contacts [n] and score_sum [n] = sum of count over the pose's contacts
+hipError_t launch_contact_score(const uint64_t *bits, const int32_t *count, int n, int R, int L, int32_t *n_contacts, int64_t *score_sum,
+                                hipStream_t s);
+
 }  // namespace dfm

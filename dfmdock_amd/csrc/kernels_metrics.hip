@@ -18,6 +18,7 @@
 //   k_native_pairs    dfm_native_create: per residue pair of the native, bit 0 = min distance < interface cutoff, bit 1 = < contact cutoff.
 //
 // Built with -ffp-contract=off: the distance arithmetic rounds like numpy's; the sums use explicit fma.
+#include "dfm_contact.h"      // min_dist9
 #include "dfm_internal.h"
 
 namespace dfm {
@@ -30,25 +31,6 @@ __device__ inline double wave_sum(double v)
 {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
-}
-
-// minimum over the 9 atom pairs of |a_i - b_j| (a, b: one residue each, 9 floats), as metrics._min_dist_pairs
-__device__ inline double min_dist9(const float *__restrict__ a, const float *__restrict__ b)
-{
-    double av[9], bv[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { av[k] = (double)a[k]; bv[k] = (double)b[k]; }
-    double best = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const double dx = av[3 * i] - bv[3 * j], dy = av[3 * i + 1] - bv[3 * j + 1], dz = av[3 * i + 2] - bv[3 * j + 2];
-            const double d = sqrt((dx * dx + dy * dy) + dz * dz);
-            // numpy's min propagates NaN
-            best = (i == 0 && j == 0) ? d : ((d < best || d != d) ? d : best);
-        }
-    return best;
 }
 
 // one Jacobi rotation of the symmetric 4 x 4 matrix a in the (p, q) plane; v collects the eigenvectors as columns

@@ -30,6 +30,7 @@ RESTRAINT_FIELDS = ["restraint_energy", "restraints_satisfied"]      # appended 
 CLUSTER_FIELDS = ["cluster", "is_center"]      # appended to the rows only when clustering is asked for
 STEP_FIELDS = ["id", "index", "step", "t", "c_rmsd", "i_rmsd", "l_rmsd", "fnat", "DockQ"]      # the long table of run_set(step_metrics=True)
 METRIC_FIELDS = ["c_rmsd", "i_rmsd", "l_rmsd", "fnat", "DockQ"]
+CONSENSUS_FIELDS = ["consensus", "n_contacts"]      # appended to the rows only when consensus scoring is asked for
 
 
 def rotate_complex(rec_pos, lig_pos, Rm):
@@ -67,6 +68,49 @@ def cluster_trajectories(model: engine.Model, lig_pos0, rot_update, tr_update, k
     from .cluster import rebuild_backbone
     poses = rebuild_backbone(lig_pos0, rot_update, tr_update, model.hp.family)
     return model.pose_cluster(poses, radius, key=key, rule=rule, max_clusters=max_clusters)
+
+
+def ensemble_consensus(model: engine.Model, rec_bb, lig0, rot_update, tr_update, energy, cutoff=5.5, top=1.0):
+    """Consensus contact scoring of trajectories on the GPU (dfm_pose_consensus) on the ligand backbone rebuilt from their final
+    (rot_update, tr_update) on the input backbone lig0 (cluster.rebuild_backbone, as cluster_trajectories does).  Members: the best `top`
+    fraction by energy (consensus.energy_members); every trajectory is scored.  Returns the dict of Model.consensus plus `members`."""
+    from . import consensus as CS
+    from .cluster import rebuild_backbone
+    poses = rebuild_backbone(lig0, rot_update, tr_update, model.hp.family)
+    members = CS.energy_members(energy, top)
+    out = model.consensus(rec_bb, poses, cutoff=cutoff, members=members)
+    out["members"] = members
+    return out
+
+
+def _check_rank(rank, consensus_top):
+    if rank not in ("energy", "consensus"):
+        raise ValueError(f"rank must be 'energy' or 'consensus', got {rank!r}")
+    if not (0.0 < float(consensus_top) <= 1.0):
+        raise ValueError(f"consensus_top must be in (0, 1], got {consensus_top}")
+
+
+def _with_consensus(model, rec, lig0, cols, k, key, opts):
+    """The consensus part of a pair driver.  opts = None (off) or (rank, cutoff, top); k / key: the pose and the clustering key the
+    driver's own rule gives.  Returns (k, key, extra result entries): under rank "consensus" k is the pose consensus.pick keeps and key
+    its order (consensus.rank_positions) - unless no pose has any contact, when both stay and `fallback` says so."""
+    if opts is None:
+        return k, key, {}
+    from . import consensus as CS
+    from .cluster import rank_order
+    rank, cutoff, top = opts
+    cd = ensemble_consensus(model, rec["bb_coords"], lig0, cols["rot_update"], cols["tr_update"], cols["energy"], cutoff, top)
+    ranked_by = "energy"
+    if rank == "consensus":
+        k2 = CS.pick(cd["consensus"], cols["energy"])
+        if k2 is not None:
+            k, key, ranked_by = k2, CS.rank_positions(cd["consensus"], cols["energy"]), "consensus"
+    n = len(cd["consensus"])
+    s = float(cd["consensus"][k])
+    summary = {"score": None if np.isnan(s) else s, "rank": int(np.nonzero(rank_order(-cd["consensus"], n) == k)[0][0]) + 1,
+               "n_contacts": int(cd["n_contacts"][k]), "M": int(cd["M"]), "cutoff": float(cd["cutoff"]), "ranked_by": ranked_by,
+               "fallback": rank == "consensus" and ranked_by != "consensus"}
+    return k, key, {"consensus": summary, "consensus_data": cd, "index": int(k)}
 
 
 def checked_precision(gx: engine.Complex, precision: str, name: str, selfcheck=True, on_fail="fp32", log=None, seed=0):
@@ -187,7 +231,7 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
             out_csv=None, traj_dir=None, max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", checks_out=None,
             overlap=True, samplers=2, timings_out=None, log=None, canary=True, canary_out=None, restraints_by_id=None,
             cluster_radius=None, cluster_rule="energy", top_k=10, metrics="host", step_metrics=False, step_csv=None, steps_out=None,
-            **sampler_kw):
+            consensus=False, consensus_top=1.0, consensus_cutoff=5.5, **sampler_kw):
     """Sample `num_samples` trajectories for every complex dict (id, rec_x, lig_x, rec_pos, lig_pos[, rec_seq, lig_seq]);
     returns the metric rows of this rank's share; rank 0 writes the gathered CSV when `out_csv` is given.  Every complex is
     self-checked first (checked_precision); `checks_out` (a list) collects {id, precision used, check dict}.
@@ -222,7 +266,13 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
     values to ~1e-12 relative, so the CSV differs in the last printed digits).  `step_metrics=True` (needs metrics="gpu"; takes the
     trace) evaluates the pose after EVERY step of every trajectory: the long table {id, index, step, t, c_rmsd, i_rmsd, l_rmsd, fnat,
     DockQ} (t = the time of the step taken, linspace(1, eps, num_steps)[step]) is appended to `steps_out` (a list; this rank's share)
-    and written to `step_csv` by rank 0."""
+    and written to `step_csv` by rank 0.
+
+    `consensus`: every row gains `consensus` (the consensus contact score of the trajectory within its complex's ensemble, NaN without
+    a contact) and `n_contacts` (ensemble_consensus: contacts below `consensus_cutoff` A, members = the best `consensus_top` fraction by
+    energy).  Like clustering it runs where all trajectories of a complex are present."""
+    if consensus:
+        _check_rank("energy", consensus_top)
     if metrics not in ("host", "gpu"):
         raise ValueError(f"metrics must be 'host' or 'gpu', got {metrics!r}")
     step_metrics = bool(step_metrics) or step_csv is not None
@@ -371,13 +421,31 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
             assign = D.gather_objects(assign)[0]
         for row in rows:
             row["cluster"], row["is_center"] = assign[f"{row['id']}/{row['index']}"]
+    if consensus:
+        mine = list(range(len(complexes))) if split_trajectories else [p.ci for p, _, _ in done]
+        scored = {}
+        if not split_trajectories or rank == 0:
+            for ci in mine:
+                r = gathered[gathered[:, 0] == ci]
+                if not len(r):
+                    continue
+                r = r[np.argsort(r[:, 1], kind="stable")]
+                rec0, lig0 = input_pose(complexes[ci], rots[ci], global_rotation)
+                cd = ensemble_consensus(model, rec0, lig0, r[:, 4:7], r[:, 7:10], r[:, 2], consensus_cutoff, consensus_top)
+                cid = complexes[ci].get("id", str(ci))
+                for t, sc, nc in zip(r[:, 1].astype(int), cd["consensus"], cd["n_contacts"]):
+                    scored[f"{cid}/{t}"] = (float(sc), int(nc))
+        if split_trajectories and world > 1:
+            scored = D.gather_objects(scored)[0]
+        for row in rows:
+            row["consensus"], row["n_contacts"] = scored[f"{row['id']}/{row['index']}"]
     if out_csv is not None:
         all_rows = _gather_rows(rows, world)
         if rank == 0:
             os.makedirs(os.path.dirname(os.path.abspath(out_csv)), exist_ok=True)
             with open(out_csv, "w", newline="") as f:
                 w = csv.DictWriter(f, fieldnames=CSV_FIELDS + (RESTRAINT_FIELDS if restraints_by_id is not None else []) +
-                                   (CLUSTER_FIELDS if cluster_radius is not None else []))
+                                   (CLUSTER_FIELDS if cluster_radius is not None else []) + (CONSENSUS_FIELDS if consensus else []))
                 w.writeheader()
                 for row in sorted(all_rows, key=lambda x: (x["id"], int(x["index"]))):
                     w.writerow(row)
@@ -436,7 +504,7 @@ def _selected_metrics(model, native, rec, lig0, res):
 def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_steps=40, seed=0, precision="mfma16",
               out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", restraints=None,
               restraint_rank="satisfied", restraint_params=None, top_k=None, cluster_radius=4.0, cluster_rule="energy", refine_t=None,
-              refine_samples=8, native=None, **sampler_kw):
+              refine_samples=8, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
     pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
     the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
@@ -457,7 +525,17 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
 
     `native` ((receptor [R,3,3], ligand [L,3,3]) backbones of the native complex, any frame, same residues as the input): the result
     gains `metrics` (c_rmsd, i_rmsd, l_rmsd, fnat, DockQ of the kept pose, on the GPU: native_metrics), every model `metrics` and, after
-    refinement, `refined_metrics`."""
+    refinement, `refined_metrics`.
+
+    `consensus`: the trajectories are also scored by consensus contacts (ensemble_consensus: contacts below `consensus_cutoff` A, members =
+    the best `consensus_top` fraction by energy) and the result gains `consensus` ({score, rank, n_contacts} of the kept pose - rank: its
+    position in consensus order - plus M, cutoff, ranked_by, fallback), `consensus_data` (the arrays of Model.consensus and `members`),
+    `index` and `trajectories` (every trajectory's energy, rot_update, tr_update, as refine_pair returns them; with restraints: the
+    restrained path's own `trajectories`).  rank="consensus" (implies consensus) keeps the pose with the highest consensus instead (ties: lower energy, then lower
+    index; it overrides restraint_rank) and makes that order the clustering key of `top_k`; when no trajectory has any contact the
+    driver's own rule stays and `fallback` is true."""
+    _check_rank(rank, consensus_top)
+    cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
     if native is not None:
         _check_native(native, rec, lig)
     if refine_t is not None and top_k is None:
@@ -479,7 +557,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     if restraints is not None:
         return _dock_pair_restrained(gx, model, rec, lig, restraints, restraint_rank, restraint_params, num_samples, num_steps, seed,
                                      precision, chk, out_pdb, max_batch, sampler_kw, clu,
-                                     None if refine_t is None else (float(refine_t), int(refine_samples)), native)
+                                     None if refine_t is None else (float(refine_t), int(refine_samples)), native, cons)
     best = None
     done = 0
     cols = {k: [] for k in ("energy", "rot_update", "tr_update")}
@@ -489,13 +567,23 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         k = int(np.argmin(r["energy"]))
         if best is None or r["energy"][k] < best[0]:     # strict <: the first minimum wins, as in the reference
             best = (float(r["energy"][k]), r["rot_update"][k].copy(), r["tr_update"][k].copy())
-        if clu is not None:
+        if clu is not None or cons is not None:
             for c in cols:
                 cols[c].append(r[c])
         done += b
     lig0 = gx.lig_pos0
     if refine_t is None:
         gx.close()
+    key, extra = None, {}
+    if clu is not None or cons is not None:
+        cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
+        key = cols["energy"]
+    if cons is not None:
+        k0 = int(np.argmin(cols["energy"]))      # the first minimum: the pose `best` holds
+        k, key, extra = _with_consensus(model, rec, lig0, cols, k0, key, cons)
+        if k != k0:
+            best = (float(cols["energy"][k]), cols["rot_update"][k].copy(), cols["tr_update"][k].copy())
+        extra["trajectories"] = {c: cols[c] for c in ("energy", "rot_update", "tr_update")}
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], best[1], best[2],
                                        center="all_atoms" if model.hp.family == 1 else "ca")
     if out_pdb:
@@ -503,10 +591,10 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         pdbio.write_complex_pdb(out_pdb, rec_atoms, lig["atoms"], lig_aa)
     res = {"energy": best[0], "rot_update": best[1], "tr_update": best[2], "lig_aa_coords": lig_aa, "precision": precision,
            "selfcheck": chk}
+    res.update(extra)
     _selected_metrics(model, native, rec, lig0, res)
     if clu is not None:
-        cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
-        res.update(_top_models(model, rec, lig, lig0, cols, cols["energy"], clu, out_pdb, native))
+        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native))
         if refine_t is not None:
             refine_models(model, gx, rec, lig, lig0, cols, res["models"], float(refine_t), int(refine_samples), num_steps, seed, precision,
                           out_pdb, native=native, **sampler_kw)
@@ -516,13 +604,16 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
 
 def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
                 out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", perturb=True, restraints=None,
-                restraint_params=None, native=None, **sampler_kw):
+                restraint_params=None, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, **sampler_kw):
     """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories
     start from that pose noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps
     down from t_begin; like dock_pair the minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns
     dock_pair's dict plus `t_begin`, `index` and `trajectories` (every trajectory's energy, rot_update, tr_update).  `restraints`
     ([restraints.RestraintGroup]) turns the restraint step on (DFM_F_RESTRAINTS).  `native` (as for dock_pair): the result gains
-    `metrics` of the kept pose and `start_metrics` of the pose the refinement started from."""
+    `metrics` of the kept pose and `start_metrics` of the pose the refinement started from.  `consensus` / `rank` / `consensus_top` /
+    `consensus_cutoff`: as for dock_pair."""
+    _check_rank(rank, consensus_top)
+    cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
     if native is not None:
         _check_native(native, rec, lig)
     gx = engine.Complex(model, rec_x, lig_x, rec["bb_coords"], lig["bb_coords"])
@@ -541,12 +632,14 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
     gx.close()
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
     k = int(np.argmin(cols["energy"]))      # the first minimum wins, as in dock_pair
+    k, _, extra = _with_consensus(model, rec, gx.lig_pos0, cols, k, None, cons)
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k],
                                        center="all_atoms" if model.hp.family == 1 else "ca")
     if out_pdb:
         pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa)
     res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, "index": k, "t_begin": float(t_begin), "trajectories": cols}
+    res.update(extra)
     if native is not None:
         _selected_metrics(model, native, rec, gx.lig_pos0, res)
         res["start_metrics"] = native_metrics(model, native, rec["bb_coords"], gx.lig_pos0[None])[0]
@@ -606,7 +699,7 @@ def model_path(out_pdb, rank):
 
 
 def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_samples, num_steps, seed, precision, chk, out_pdb, max_batch,
-                          sampler_kw, clu=None, refine=None, native=None):
+                          sampler_kw, clu=None, refine=None, native=None, cons=None):
     from . import restraints as RS
     gx.set_restraints(restraints, params)
     cols = {k: [] for k in ("energy", "restraint_energy", "restraints_satisfied", "rot_update", "tr_update")}
@@ -624,6 +717,11 @@ def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_sam
         gx.close()
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
     k = RS.rank_key(cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else int(np.argmin(cols["energy"]))
+    key, extra = None, {}
+    if clu is not None:
+        from .cluster import satisfied_key
+        key = satisfied_key(cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else cols["energy"]
+    k, key, extra = _with_consensus(model, rec, lig0, cols, k, key, cons)
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k],
                                        center="all_atoms" if model.hp.family == 1 else "ca")
     if out_pdb:
@@ -633,10 +731,9 @@ def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_sam
            "restraint_rank": rank, "restraint_energy": float(cols["restraint_energy"][k]),
            "restraints_satisfied": int(cols["restraints_satisfied"][k]),
            "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
+    res.update(extra)
     _selected_metrics(model, native, rec, lig0, res)
     if clu is not None:
-        from .cluster import satisfied_key
-        key = satisfied_key(cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else cols["energy"]
         res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native))
         if refine is not None:
             refine_models(model, gx, rec, lig, lig0, cols, res["models"], refine[0], refine[1], num_steps, seed, precision, out_pdb,

@@ -170,6 +170,40 @@ class Model:
         a Native whose `.metrics(lig_pos[, rec_pos])` evaluates P poses in one call.  The cutoffs are the reference's."""
         return Native(self, rec_pos, lig_pos, iface_cutoff, contact_cutoff)
 
+    def consensus(self, rec_pos, lig_pos, cutoff=5.5, members=None, bits=False):
+        """Consensus contact scoring of P poses on the GPU (dfm_pose_consensus; the float64 definition is consensus.consensus): rec_pos
+        [R,3,3], lig_pos [P,L,3,3], `members` bool [P] (None: every pose).  Returns {count [R,L], rec_count [R], lig_count [L], n_contacts
+        [P] (int32), score_sum [P] (int64), M, cutoff, freq = count / M, consensus [P] = score_sum / (M n_contacts), NaN without a
+        contact (consensus.finish)} and, with `bits`, the contacts themselves as uint64 [P,R,ceil(L/64)] (consensus.unpack_bits)."""
+        from . import consensus as CS
+        rp = _f32(rec_pos).reshape(-1, 9)
+        lp = _f32(lig_pos)
+        if lp.ndim == 4:
+            lp = lp.reshape(lp.shape[0], lp.shape[1], 9)
+        if lp.ndim != 3 or lp.shape[2] != 9:
+            raise ValueError(f"lig_pos must be [P,L,9] or [P,L,3,3], got {np.shape(lig_pos)}")
+        P, Lg, R = lp.shape[0], lp.shape[1], rp.shape[0]
+        mem = None
+        if members is not None:
+            mem = np.ascontiguousarray(np.asarray(members).reshape(-1).astype(bool), dtype=np.uint8)
+            if mem.size != P:
+                raise ValueError(f"members must have {P} entries, got {mem.size}")
+        o = {"count": np.zeros((R, Lg), np.int32), "rec_count": np.zeros(R, np.int32), "lig_count": np.zeros(Lg, np.int32),
+             "n_contacts": np.zeros(P, np.int32), "score_sum": np.zeros(P, np.int64)}
+        out = L.ConsensusOutC()
+        out.count, out.rec_count, out.lig_count, out.n_contacts = (_p(o[k], L.I32P) for k in ("count", "rec_count", "lig_count", "n_contacts"))
+        out.score_sum = o["score_sum"].ctypes.data_as(C.POINTER(C.c_int64))
+        if bits:
+            o["bits"] = np.zeros((P, R, (Lg + 63) // 64), np.uint64)
+            out.bits = o["bits"].ctypes.data_as(C.POINTER(C.c_uint64))
+        L.check(L.lib().dfm_pose_consensus(self._h, P, R, Lg, _p(rp), _p(lp), _p(mem, C.POINTER(C.c_uint8)), float(cutoff), C.byref(out)),
+                "dfm_pose_consensus")
+        o["M"] = P if mem is None else int(mem.sum())
+        o["cutoff"] = float(np.float32(cutoff))
+        o["freq"] = o["count"].astype(np.float64) / o["M"]
+        o["consensus"] = CS.finish(o["score_sum"], o["n_contacts"], o["M"])
+        return o
+
 
 class Native:
     """A native pose resident on the model's GPU (dfm_native): interface residues, native contacts and the receptor's share of the
@@ -243,6 +277,18 @@ def metrics_last_timing():
     a, b = C.c_double(0), C.c_double(0)
     L.check(L.lib().dfm_metrics_last_timing(C.byref(a), C.byref(b)), "dfm_metrics_last_timing")
     return a.value, b.value
+
+
+def consensus_last_timing():
+    """(host-to-device copy ms, kernel ms) of this thread's last Model.consensus call (dfm_consensus_last_timing)."""
+    a, b = C.c_double(0), C.c_double(0)
+    L.check(L.lib().dfm_consensus_last_timing(C.byref(a), C.byref(b)), "dfm_consensus_last_timing")
+    return a.value, b.value
+
+
+def consensus_chunk_poses(R: int, Lg: int) -> int:
+    """Poses per chunk of a Model.consensus call on an R + L complex (dfm_consensus_chunk_poses)."""
+    return int(L.lib().dfm_consensus_chunk_poses(int(R), int(Lg)))
 
 
 def pose_last_timing():

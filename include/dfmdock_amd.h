@@ -382,6 +382,41 @@ int dfm_pose_metrics(dfm_native *nat, int P, const float *lig_pos, const float *
 /* GPU milliseconds of the calling thread's last dfm_pose_metrics, summed over its chunks: the host-to-device copies of the poses and
  * the three kernels (k_metrics_reduce, k_metrics_solve, k_metrics_resid) - tools/metrics_bench.py */
 int dfm_metrics_last_timing(double *copy_ms, double *kernel_ms);
+/* Consensus contact scoring of P ligand poses of one complex (CONSRANK style): which inter-residue contacts the ensemble agrees on, and
+ * how well every pose agrees with the ensemble - a ranking that needs neither a native nor the energy head.  dfmdock_amd/consensus.py
+ * is the float64 definition this call is tested against.  rec_pos [R,9] (N, CA, C per residue; the receptor is the same in every pose),
+ * lig_pos [P,L,9], member_or_null [P] (non-zero: the pose is a member of the ensemble; NULL: every pose; M = number of members).
+ *   contact (p,i,j): the minimum over the 9 backbone-atom pairs of sqrt((dx*dx + dy*dy) + dz*dz), in fp64 on the fp32 inputs, is
+ *     < cutoff (strict; the cutoff is widened to double; 5.5 is what dfm_native_create's callers use).  A NaN distance is no contact.
+ *   count [R,L]: member poses with the contact.  rec_count [R] / lig_count [L]: member poses in which the residue has a contact.
+ *   per pose, member or not: n_contacts [P], and score_sum [P] = the sum of count over the pose's contacts (a member's own contacts are
+ *     part of count).  The consensus score score_sum / (M n_contacts) is finished by the caller (consensus.finish).
+ *   bits [P,R,ceil(L/64)]: the contacts themselves, bit j % 64 of word j / 64 = contact (i,j); unused high bits are 0.
+ * Every output pointer may be NULL.  All results are integers: apart from pairs whose distance rounds onto the cutoff they equal the
+ * definition exactly, and they do not depend on the order of the poses or on how the call splits P into chunks
+ * (dfm_consensus_chunk_poses poses each; a call of more than one chunk evaluates the contact bits twice - once to count, once to score -
+ * instead of keeping them).  A pose with NaN coordinates has no contact there and disturbs no other pose.
+ * DFM_E_INVALID, nothing enqueued: NULL m / rec_pos / lig_pos / out, P < 1 or > 65536 (count stays an int32), R or L < 1,
+ * R x L > 2^27, cutoff not finite or <= 0, no member.  DFM_E_OOM when the poses, the bits of a chunk or the R x L counts do not fit.
+ * Within these limits the cost is proportional to P x R x L, except that lig_count takes R / 64 serial steps of one wave per pose and
+ * 64 ligand residues: sized for protein chains (R, L up to a few thousand), slow for a receptor of millions of residues.
+ * Takes the MODEL handle for its device only.  Every call owns a non-blocking stream and its device temporaries, so calls may run from
+ * several host threads at once and next to that model's sampling handles.  No reference call has a counterpart. */
+typedef struct {
+    int32_t *count;        /* [R,L]  or NULL */
+    int32_t *rec_count;    /* [R]    or NULL */
+    int32_t *lig_count;    /* [L]    or NULL */
+    int32_t *n_contacts;   /* [P]    or NULL */
+    int64_t *score_sum;    /* [P]    or NULL */
+    uint64_t *bits;        /* [P,R,ceil(L/64)] or NULL: bit j%64 of word j/64 = contact (i,j); unused high bits 0 */
+} dfm_consensus_out;
+int dfm_pose_consensus(dfm_model *m, int P, int R, int L, const float *rec_pos, const float *lig_pos,
+                       const uint8_t *member_or_null, float cutoff, dfm_consensus_out *out);
+/* poses per chunk of a dfm_pose_consensus call on an R + L complex (host arithmetic; < 1 for R or L < 1) */
+int dfm_consensus_chunk_poses(int R, int L);
+/* GPU milliseconds of the calling thread's last dfm_pose_consensus, summed over its chunks and passes: the host-to-device copies of the
+ * poses and the kernels (k_contact_bits, k_contact_count, k_contact_marginals, k_contact_score) - tools/consensus_bench.py */
+int dfm_consensus_last_timing(double *copy_ms, double *kernel_ms);
 /* edges per node for this complex: min(N,20) + min(40, N-20) */
 int dfm_complex_degree(const dfm_complex *cx);
 /* Device blocks released by destroyed handles are parked per device for the next handle (a set driver creates and destroys a
