@@ -44,6 +44,8 @@ EXPORTS = [
     "dfm_refine", "dfm_forward_marginal", "dfm_igso3_table",
     "dfm_native_create", "dfm_native_destroy", "dfm_native_info", "dfm_pose_metrics", "dfm_metrics_last_timing",
     "dfm_pose_consensus", "dfm_consensus_chunk_poses", "dfm_consensus_last_timing",
+    "dfm_atoms_create", "dfm_atoms_destroy", "dfm_atoms_info", "dfm_pose_sterics", "dfm_pose_sterics_chunked", "dfm_sterics_last_timing",
+    "dfm_sterics_exit_counts",
 ]
 
 
@@ -111,6 +113,14 @@ class ConsensusOutC(C.Structure):
                 ("bits", C.POINTER(C.c_uint64))]
 
 
+class StericsParamsC(C.Structure):
+    _fields_ = [("clash_cutoff", C.c_float), ("contact_cutoff", C.c_float), ("chunk_poses", C.c_int)]
+
+
+class StericsOutC(C.Structure):
+    _fields_ = [("n_clash", I32P), ("n_contact", I32P), ("min_dist", C.POINTER(C.c_double)), ("lig_clash", I32P), ("lig_contact", I32P)]
+
+
 _lib = None
 
 
@@ -169,6 +179,15 @@ def lib():
                                      C.POINTER(ConsensusOutC)]
     L.dfm_consensus_chunk_poses.argtypes = [C.c_int, C.c_int]
     L.dfm_consensus_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_atoms_create.argtypes = [C.c_void_p, C.c_int, F32P, C.c_int, F32P, F32P, C.POINTER(StericsParamsC)]
+    L.dfm_atoms_create.restype = C.c_void_p
+    L.dfm_atoms_destroy.argtypes = [C.c_void_p]
+    L.dfm_atoms_destroy.restype = None
+    L.dfm_atoms_info.argtypes = [C.c_void_p, I32P, I32P, F32P]
+    L.dfm_pose_sterics.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.POINTER(StericsOutC)]
+    L.dfm_pose_sterics_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(StericsOutC)]
+    L.dfm_sterics_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_sterics_exit_counts.argtypes = [C.c_int, C.POINTER(C.c_uint64)]
     L.dfm_trim_cache.argtypes = [C.c_int]
     L.dfm_trim_cache.restype = C.c_longlong
     L.dfm_diffusion_coef.argtypes = [C.POINTER(HParamsC), C.c_int, C.c_double, C.POINTER(C.c_double),

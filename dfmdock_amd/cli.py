@@ -14,6 +14,7 @@
     python -m dfmdock_amd dock|refine ... --consensus [--rank consensus] [--consensus-top 0.5] [--contact-map map.npz]
     python -m dfmdock_amd dock|refine ... --write-restraints consensus.txt --restraint-top 10 [--restraint-upper 8.0]
     python -m dfmdock_amd sweep ... --consensus [--consensus-top 0.5]
+    python -m dfmdock_amd dock|refine ... --clash-screen [--clash-filter] [--clash-cutoff 3.0] [--contact-cutoff 5.0] [--clash-residues FILE]
 
   dock       <- src/inference_single.py:1-12 -> inference() (src/inference_base.py:601-670): num_samples (120) trajectories of
                 num_steps (40), the minimum-energy one applied to the all-atom ligand, `output.pdb` written, {"energy": E} printed.
@@ -52,6 +53,13 @@
              guided run (`dock --restraints FILE`).  `--consensus-top FRAC`: only the best FRAC of the trajectories by energy are members
              of the ensemble (all are scored).  `sweep --consensus` appends `consensus` and `n_contacts` to the CSV and adds the DockQ
              success rates of the consensus-selected trajectory to the table.
+  sterics    no reference counterpart: the all-atom clash / contact screen of every trajectory on the GPU (dfmdock_amd/sterics.py,
+             dfm_pose_sterics) - the only step that reads the side chains.  CAPRI's rule: a clash is a pair of heavy atoms of the two
+             chains closer than --clash-cutoff (3.0 A), the interface size the pairs closer than --contact-cutoff (5.0 A), and a model
+             whose clash count exceeds the ensemble's mean by more than two standard deviations is flagged.  `dock / refine
+             --clash-screen` add a `sterics` object for the kept pose (and for every --top-k model) to the result line and a REMARK line
+             with the counts to every written model; `--clash-filter` removes the flagged trajectories before the selection, the
+             consensus ranking and the clustering; `--clash-residues FILE` lists the kept model's counts per ligand residue.
   selfcheck  no reference counterpart: dfm_complex_selfcheck on the pair (what `dock` and `sweep` run once per complex anyway).
 
 --ckpt takes the Lightning checkpoint the reference loads (src/inference_base.py:611-616; read without Lightning / omegaconf by
@@ -91,6 +99,18 @@ def _add_consensus(p):
                    help="with --write-restraints: upper bound on the CA-CA distance of every written contact (A, default 8.0)")
 
 
+def _add_sterics(p):
+    p.add_argument("--clash-screen", action="store_true",
+                   help="all-atom clash / contact screen of every trajectory (adds a `sterics` object to the result line, a REMARK to the models)")
+    p.add_argument("--clash-filter", action="store_true",
+                   help="remove the trajectories CAPRI's rule flags (clashes > ensemble mean + 2 std) before any selection (implies --clash-screen)")
+    p.add_argument("--clash-cutoff", type=float, default=None, metavar="A", help="with --clash-screen: heavy-atom distance of a clash (default 3.0)")
+    p.add_argument("--contact-cutoff", type=float, default=None, metavar="A",
+                   help="with --clash-screen: heavy-atom distance of an interface contact (default 5.0, >= --clash-cutoff)")
+    p.add_argument("--clash-residues", default=None, metavar="FILE",
+                   help="write the kept model's clash / contact counts per ligand residue (implies --clash-screen)")
+
+
 def _add_common(p):
     p.add_argument("--ckpt", required=True, help="Lightning checkpoint or bare state_dict (torch.save)")
     p.add_argument("--num-steps", type=int, default=40)
@@ -128,6 +148,7 @@ def build_parser():
     d.add_argument("--refine-samples", type=int, default=8, metavar="n", help="with --refine-t: trajectories per cluster centre")
     _add_native(d)
     _add_consensus(d)
+    _add_sterics(d)
     _add_common(d)
     r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)")
     r.add_argument("pdb_1", help="receptor PDB")
@@ -141,6 +162,7 @@ def build_parser():
     r.add_argument("--restraints", default=None, help="interface restraint file (as for dock)")
     _add_native(r)
     _add_consensus(r)
+    _add_sterics(r)
     _add_common(r)
     s = sub.add_parser("sweep", help="sample every complex of a DB5-style directory (inference_mlsb.py run_sampling)")
     s.add_argument("--db5", required=True, help="directory of <id>.pt files (+ optional test.txt with the ids to run)")
@@ -194,6 +216,15 @@ def parse_args(argv=None):
             ap.error("--restraint-top must be >= 1")
         if not (args.restraint_upper > 0 and np.isfinite(args.restraint_upper)):
             ap.error("--restraint-upper must be finite and > 0")
+    if args.cmd in ("dock", "refine"):
+        if args.clash_filter or args.clash_residues:
+            args.clash_screen = True
+        if not args.clash_screen and (args.clash_cutoff is not None or args.contact_cutoff is not None):
+            ap.error("--clash-cutoff / --contact-cutoff are the cutoffs of --clash-screen: they need it")
+        args.clash_cutoff = 3.0 if args.clash_cutoff is None else args.clash_cutoff
+        args.contact_cutoff = 5.0 if args.contact_cutoff is None else args.contact_cutoff
+        if not (np.isfinite(args.clash_cutoff) and np.isfinite(args.contact_cutoff) and 0 < args.clash_cutoff <= args.contact_cutoff):
+            ap.error("need 0 < --clash-cutoff <= --contact-cutoff, both finite")
     if args.cmd in ("dock", "refine", "sweep"):
         if args.consensus_top is not None and not args.consensus:
             ap.error("--consensus-top selects the members of the consensus ensemble: it needs --consensus")
@@ -295,6 +326,26 @@ def consensus_outputs(args, res, rec, lig, line):
                             header=f"top {len(groups)} consensus contacts of {len(cd['consensus'])} trajectories ({cd['M']} members, "
                                    f"contact cutoff {cd['cutoff']:g} A): REC LIG UPPER WEIGHT(= contact frequency)")
         line.update(restraints_written=os.path.abspath(args.write_restraints), restraints_written_n=len(groups))
+
+
+def sterics_kwargs(args):
+    """Driver keyword arguments of the screen flags of dock / refine: none without them."""
+    if not args.clash_screen:
+        return {}
+    return dict(clash_screen=True, clash_filter=args.clash_filter, clash_cutoff=args.clash_cutoff, contact_cutoff=args.contact_cutoff)
+
+
+def sterics_outputs(args, model, res, rec, lig, line):
+    """The screen's part of a dock / refine result: the `sterics` object of the line and --clash-residues."""
+    if not args.clash_screen:
+        return
+    line.update(sterics=res["sterics"], index=res["index"])
+    if args.clash_residues:
+        from . import driver
+        from .sterics import write_clash_residues
+        keys, clash, contact = driver.residue_sterics(model, rec, lig, res["rot_update"], res["tr_update"], args.clash_cutoff, args.contact_cutoff)
+        write_clash_residues(args.clash_residues, keys, clash, contact)
+        line.update(clash_residues=os.path.abspath(args.clash_residues))
 
 
 def consensus_table(rows):
@@ -403,6 +454,7 @@ def cmd_dock(args):
     if args.native:
         kw.update(native=load_native(args.native))
     kw.update(consensus_kwargs(args))
+    kw.update(sterics_kwargs(args))
     res = driver.dock_pair(model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                            precision=args.precision, out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
                            on_selfcheck_fail=args.on_selfcheck_fail, **kw)
@@ -420,6 +472,7 @@ def cmd_dock(args):
     if args.native:
         line.update(metrics=res["metrics"])
     consensus_outputs(args, res, rec, lig, line)
+    sterics_outputs(args, model, res, rec, lig, line)
     print(json.dumps(line), flush=True)
     if args.json:
         extra = {}
@@ -441,6 +494,7 @@ def cmd_refine(args):
     if args.native:
         kw.update(native=load_native(args.native))
     kw.update(consensus_kwargs(args))
+    kw.update(sterics_kwargs(args))
     res = driver.refine_pair(model, rec, lig, rec_x, lig_x, t_begin=args.t_begin, num_samples=args.num_samples, num_steps=args.num_steps,
                              seed=args.seed, precision=args.precision, out_pdb=args.out, max_batch=args.max_batch,
                              selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, perturb=not args.no_perturb, **kw)
@@ -451,6 +505,7 @@ def cmd_refine(args):
     if args.native:
         line.update(metrics=res["metrics"], start_metrics=res["start_metrics"])
     consensus_outputs(args, res, rec, lig, line)
+    sterics_outputs(args, model, res, rec, lig, line)
     print(json.dumps(line), flush=True)
     if args.json:
         with open(args.json, "w") as f:

@@ -1362,6 +1362,300 @@ extern "C" int dfm_consensus_last_timing(double *copy_ms, double *kernel_ms)
     return DFM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// All-atom clash / contact screen (kernels_sterics.hip).  A dfm_atoms holds what the two atom sets and the rotation centre fix - the
+// receptor's cell grid, the ligand in blocks of 64 neighbours - and is read-only after creation; like a dfm_native it is bound to the
+// model handle's device only, and every dfm_pose_sterics call owns its stream and temporaries.
+constexpr size_t STERICS_CHUNK_BYTES = (size_t)64 << 20;      // per-atom output of one chunk of a call
+constexpr int STERICS_MAX_CHUNK = 32768;                      // poses per launch (gridDim.y)
+constexpr int STERICS_MAX_ATOMS = 1 << 24, STERICS_MAX_CELLS = 1 << 24;
+static thread_local double g_sterics_ms[2] = {0.0, 0.0};      // host-to-device copies, kernels of this thread's last dfm_pose_sterics
+static thread_local int g_sterics_count = 0;                  // dfm_sterics_exit_counts: count the early exits of this thread's calls
+static thread_local uint64_t g_sterics_exits[3] = {0, 0, 0};  // waves, left at the sphere test, left at the box test
+
+struct dfm_atoms {
+    int device = 0, Ar = 0, Al = 0, n_cells = 0, max_cell_atoms = 0;
+    int chunk_poses = 0, default_chunk = 0;      // the creator's chunk (0: none given); poses whose per-atom output fills STERICS_CHUNK_BYTES
+    float cell_edge = 0.f;
+    DevPool pool;      // unbound: released under a device-wide wait, like a model's
+    float *rec = nullptr, *lig = nullptr, *sphere = nullptr;
+    int32_t *cell_start = nullptr, *lig_index = nullptr;
+    StericsConst sc = {};
+};
+
+extern "C" void dfm_atoms_destroy(dfm_atoms *a)
+{
+    if (!a) return;
+    DeviceScope ds(a->device);
+    a->pool.release();
+    delete a;
+}
+
+// 21 bits of each cell coordinate interleaved
+static uint64_t morton3(uint32_t x, uint32_t y, uint32_t z)
+{
+    auto spread = [](uint64_t v) {
+        v &= 0x1fffff;
+        v = (v | v << 32) & 0x1f00000000ffffull;
+        v = (v | v << 16) & 0x1f0000ff0000ffull;
+        v = (v | v << 8) & 0x100f00f00f00f00full;
+        v = (v | v << 4) & 0x10c30c30c30c30c3ull;
+        v = (v | v << 2) & 0x1249249249249249ull;
+        return v;
+    };
+    return spread(x) | spread(y) << 1 | spread(z) << 2;
+}
+
+extern "C" dfm_atoms *dfm_atoms_create(dfm_model *m, int Ar, const float *rec_atoms, int Al, const float *lig_atoms, const float center[3],
+                                       const dfm_sterics_params *p_or_null)
+{
+    auto bad = [](int code, const std::string &msg) -> dfm_atoms * { (void)fail(code, msg); return nullptr; };
+    if (!m) return bad(DFM_E_INVALID, "m is NULL");
+    if (!rec_atoms) return bad(DFM_E_INVALID, "rec_atoms is NULL");
+    if (!lig_atoms) return bad(DFM_E_INVALID, "lig_atoms is NULL");
+    if (!center) return bad(DFM_E_INVALID, "center is NULL");
+    if (Ar < 1 || Al < 1) return bad(DFM_E_INVALID, "need Ar >= 1 and Al >= 1");
+    if (Ar > STERICS_MAX_ATOMS || Al > STERICS_MAX_ATOMS) return bad(DFM_E_INVALID, "Ar or Al exceeds 2^24 atoms");
+    dfm_sterics_params prm = {3.0f, 5.0f, 0};
+    if (p_or_null) prm = *p_or_null;
+    if (!std::isfinite(prm.clash_cutoff) || !std::isfinite(prm.contact_cutoff) || !(prm.clash_cutoff > 0.f) || !(prm.contact_cutoff > 0.f))
+        return bad(DFM_E_INVALID, "cutoffs must be finite and > 0");
+    if (prm.contact_cutoff < prm.clash_cutoff) return bad(DFM_E_INVALID, "contact_cutoff must be >= clash_cutoff");
+    if (prm.chunk_poses < 0) return bad(DFM_E_INVALID, "chunk_poses must be >= 0");
+    for (size_t i = 0; i < (size_t)Ar * 3; ++i)
+        if (!std::isfinite(rec_atoms[i])) return bad(DFM_E_INVALID, "rec_atoms: atom " + std::to_string(i / 3) + " is not finite");
+    for (size_t i = 0; i < (size_t)Al * 3; ++i)
+        if (!std::isfinite(lig_atoms[i])) return bad(DFM_E_INVALID, "lig_atoms: atom " + std::to_string(i / 3) + " is not finite");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(center[k])) return bad(DFM_E_INVALID, "center is not finite");
+    // the receptor's grid: origin = the bounding box's low corner, edge = the contact cutoff
+    StericsConst sc = {};
+    sc.edge = sc.contact = (double)prm.contact_cutoff;
+    sc.clash = (double)prm.clash_cutoff;
+    for (int k = 0; k < 3; ++k) { sc.lo[k] = sc.hi[k] = (double)rec_atoms[k]; sc.center[k] = (double)center[k]; }
+    for (int i = 1; i < Ar; ++i)
+        for (int k = 0; k < 3; ++k) {
+            const double v = (double)rec_atoms[(size_t)i * 3 + k];
+            sc.lo[k] = std::min(sc.lo[k], v);
+            sc.hi[k] = std::max(sc.hi[k], v);
+        }
+    double dims[3], cells = 1.0, maxabs = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        dims[k] = std::floor((sc.hi[k] - sc.lo[k]) / sc.edge) + 1.0;
+        cells *= dims[k];
+        maxabs = std::max(maxabs, std::max(std::fabs(sc.lo[k]), std::fabs(sc.hi[k])));
+    }
+    if (!(cells <= (double)STERICS_MAX_CELLS)) return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells of the contact cutoff");
+    sc.nx = (int)dims[0]; sc.ny = (int)dims[1]; sc.nz = (int)dims[2];
+    maxabs += 2.0 * sc.contact + 1.0;
+    // the fp32 reject threshold (kernels_sterics.hip): contact * 1.0001 + max(1e-3, 2.5e-7 maxabs)
+    const float slack = std::max(1e-3f, (float)(2.5e-7 * maxabs)), thr = prm.contact_cutoff * 1.0001f + slack;
+    sc.reject2 = thr * thr;
+    sc.grow = (double)thr;
+    if (!std::isfinite(sc.reject2)) return bad(DFM_E_INVALID, "cutoffs must be finite and > 0");
+    const int n_cells = sc.nx * sc.ny * sc.nz;
+    auto cell1 = [&](double x, int k, int n) {
+        double c = std::floor((x - sc.lo[k]) / sc.edge);
+        c = c < 0.0 ? 0.0 : (c > (double)(n - 1) ? (double)(n - 1) : c);
+        return (int)c;
+    };
+    // counting sort of the receptor atoms by cell
+    std::vector<int32_t> start((size_t)n_cells + 1, 0), cell_of((size_t)Ar);
+    for (int i = 0; i < Ar; ++i) {
+        const float *x = rec_atoms + (size_t)i * 3;
+        const int c = (cell1((double)x[2], 2, sc.nz) * sc.ny + cell1((double)x[1], 1, sc.ny)) * sc.nx + cell1((double)x[0], 0, sc.nx);
+        cell_of[(size_t)i] = c;
+        ++start[(size_t)c + 1];
+    }
+    int max_cell = 0;
+    for (int c = 0; c < n_cells; ++c) {
+        max_cell = std::max(max_cell, (int)start[(size_t)c + 1]);
+        start[(size_t)c + 1] += start[(size_t)c];
+    }
+    std::vector<float> rec4((size_t)Ar * 4, 0.f);
+    {
+        std::vector<int32_t> at(start.begin(), start.end() - 1);
+        for (int i = 0; i < Ar; ++i) {
+            float *dst = rec4.data() + (size_t)at[(size_t)cell_of[(size_t)i]]++ * 4;
+            for (int k = 0; k < 3; ++k) dst[k] = rec_atoms[(size_t)i * 3 + k];
+        }
+    }
+    // the ligand in Morton order of its own cells (ties: the caller's order), and a bounding sphere per block of 64
+    double llo[3] = {(double)lig_atoms[0], (double)lig_atoms[1], (double)lig_atoms[2]};
+    for (int i = 1; i < Al; ++i)
+        for (int k = 0; k < 3; ++k) llo[k] = std::min(llo[k], (double)lig_atoms[(size_t)i * 3 + k]);
+    std::vector<std::pair<uint64_t, int32_t>> order((size_t)Al);
+    for (int i = 0; i < Al; ++i) {
+        uint32_t c[3];
+        for (int k = 0; k < 3; ++k) {
+            const double v = std::floor(((double)lig_atoms[(size_t)i * 3 + k] - llo[k]) / sc.edge);
+            c[k] = (uint32_t)(v < 0.0 ? 0.0 : (v > 2097151.0 ? 2097151.0 : v));
+        }
+        order[(size_t)i] = {morton3(c[0], c[1], c[2]), i};
+    }
+    std::sort(order.begin(), order.end());
+    const int nblk = (Al + 63) / 64;
+    std::vector<float> lig4((size_t)Al * 4, 0.f), sph((size_t)nblk * 4, 0.f);
+    std::vector<int32_t> lig_index((size_t)Al);
+    for (int i = 0; i < Al; ++i) {
+        const int32_t src = order[(size_t)i].second;
+        lig_index[(size_t)i] = src;
+        for (int k = 0; k < 3; ++k) lig4[(size_t)i * 4 + k] = lig_atoms[(size_t)src * 3 + k];
+    }
+    for (int b = 0; b < nblk; ++b) {
+        const int i0 = b * 64, i1 = std::min(Al, i0 + 64);
+        double lo[3], hi[3];
+        for (int k = 0; k < 3; ++k) lo[k] = hi[k] = (double)lig4[(size_t)i0 * 4 + k];
+        for (int i = i0 + 1; i < i1; ++i)
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = std::min(lo[k], (double)lig4[(size_t)i * 4 + k]);
+                hi[k] = std::max(hi[k], (double)lig4[(size_t)i * 4 + k]);
+            }
+        // the centre as the fp32 the kernel reads, the radius measured from THAT point and rounded up
+        float c[3];
+        for (int k = 0; k < 3; ++k) c[k] = (float)(0.5 * (lo[k] + hi[k]) - sc.center[k]);
+        double r2 = 0.0;
+        for (int i = i0; i < i1; ++i) {
+            double d2 = 0.0;
+            for (int k = 0; k < 3; ++k) {
+                const double d = ((double)lig4[(size_t)i * 4 + k] - sc.center[k]) - (double)c[k];
+                d2 += d * d;
+            }
+            r2 = std::max(r2, d2);
+        }
+        for (int k = 0; k < 3; ++k) sph[(size_t)b * 4 + k] = c[k];
+        sph[(size_t)b * 4 + 3] = std::nextafter((float)(std::sqrt(r2) * (1.0 + 1e-6) + 1e-6), INFINITY);
+    }
+    for (size_t i = 0; i < sph.size(); ++i)
+        if (!std::isfinite(sph[i])) return bad(DFM_E_INVALID, "lig_atoms / center: the ligand's extent about the centre overflows fp32");
+    DeviceScope ds(m->device);
+    if (ds.err != hipSuccess) return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err));
+    dfm_atoms *a = new dfm_atoms;
+    a->device = m->device; a->Ar = Ar; a->Al = Al; a->sc = sc; a->n_cells = n_cells; a->max_cell_atoms = max_cell;
+    a->cell_edge = prm.contact_cutoff;
+    a->chunk_poses = prm.chunk_poses;
+    a->default_chunk = (int)std::min<size_t>(STERICS_MAX_CHUNK, std::max<size_t>(1, STERICS_CHUNK_BYTES / ((size_t)Al * 2 * sizeof(int32_t))));
+    hipError_t e = hipSuccess;
+    {
+        PoseCall c;
+        e = c.open();
+        if (e == hipSuccess) e = a->pool.upload_async(&a->rec, rec4.data(), rec4.size(), c.s);
+        if (e == hipSuccess) e = a->pool.upload_async(&a->cell_start, start.data(), start.size(), c.s);
+        if (e == hipSuccess) e = a->pool.upload_async(&a->lig, lig4.data(), lig4.size(), c.s);
+        if (e == hipSuccess) e = a->pool.upload_async(&a->sphere, sph.data(), sph.size(), c.s);
+        if (e == hipSuccess) e = a->pool.upload_async(&a->lig_index, lig_index.data(), lig_index.size(), c.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
+    }      // the call's stream has drained: the host vectors it read may go
+    if (e != hipSuccess) {
+        a->pool.release();
+        delete a;
+        return bad(e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP, std::string("dfm_atoms_create: ") + hipGetErrorString(e));
+    }
+    return a;
+}
+
+extern "C" int dfm_atoms_info(const dfm_atoms *a, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge)
+{
+    if (!a) return fail(DFM_E_INVALID, "NULL argument");
+    if (n_cells) *n_cells = a->n_cells;
+    if (max_cell_atoms) *max_cell_atoms = a->max_cell_atoms;
+    if (cell_edge) *cell_edge = a->cell_edge;
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_sterics_chunked(dfm_atoms *a, int P, const float *rot, const float *tr, int chunk_poses, dfm_sterics_out *out)
+{
+    if (!a) return fail(DFM_E_INVALID, "a is NULL");
+    if (!rot) return fail(DFM_E_INVALID, "rot is NULL");
+    if (!tr) return fail(DFM_E_INVALID, "tr is NULL");
+    if (!out) return fail(DFM_E_INVALID, "out is NULL");
+    if (P < 1) return fail(DFM_E_INVALID, "need P >= 1");
+    if (chunk_poses < 0) return fail(DFM_E_INVALID, "chunk_poses must be >= 0");
+    DEVICE_SCOPE(a->device);
+    PoseCall c;
+    HIPCHK(c.open());
+    const bool per_atom = out->lig_clash || out->lig_contact;
+    // the call's chunk, else the creator's, else the default: without per-atom output a chunk is bounded by the launch alone
+    const int want = chunk_poses > 0 ? chunk_poses : a->chunk_poses;
+    const int Pc = std::min(P, want > 0 ? std::min(want, STERICS_MAX_CHUNK) : (per_atom ? a->default_chunk : STERICS_MAX_CHUNK));
+    const size_t Al = (size_t)a->Al;
+    float *d_rot = nullptr, *d_tr = nullptr;
+    double *T = nullptr;
+    int32_t *d_cnt = nullptr, *d_lc = nullptr, *d_lt = nullptr;
+    uint64_t *d_min = nullptr, *d_exits = nullptr;
+    HIPCHK(c.tmp.alloc(&d_rot, (size_t)Pc * 3));
+    HIPCHK(c.tmp.alloc(&d_tr, (size_t)Pc * 3));
+    HIPCHK(c.tmp.alloc(&T, (size_t)Pc * 12));
+    HIPCHK(c.tmp.alloc(&d_cnt, (size_t)Pc * 2));      // n_clash | n_contact
+    HIPCHK(c.tmp.alloc(&d_min, (size_t)Pc));
+    if (out->lig_clash) HIPCHK(c.tmp.alloc(&d_lc, (size_t)Pc * Al));
+    if (out->lig_contact) HIPCHK(c.tmp.alloc(&d_lt, (size_t)Pc * Al));
+    if (g_sterics_count) {
+        HIPCHK(c.tmp.alloc(&d_exits, 2));
+        HIPCHK(hipMemsetAsync(d_exits, 0, 2 * sizeof(uint64_t), c.s));
+    }
+    const StericsAtoms at = {a->rec, a->lig, a->sphere, a->cell_start, a->lig_index, a->sc, a->Ar, a->Al};
+    std::vector<int32_t> h_cnt((size_t)Pc * 2);
+    std::vector<uint64_t> h_min((size_t)Pc);
+    double copy_ms = 0.0, kernel_ms = 0.0;
+    for (int p0 = 0; p0 < P; p0 += Pc) {
+        const int n = std::min(Pc, P - p0);
+        HIPCHK(hipEventRecord(c.ev[0], c.s));
+        HIPCHK(hipMemcpyAsync(d_rot, rot + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s));
+        HIPCHK(hipMemcpyAsync(d_tr, tr + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s));
+        HIPCHK(hipEventRecord(c.ev[1], c.s));
+        if (d_lc) HIPCHK(hipMemsetAsync(d_lc, 0, (size_t)n * Al * sizeof(int32_t), c.s));
+        if (d_lt) HIPCHK(hipMemsetAsync(d_lt, 0, (size_t)n * Al * sizeof(int32_t), c.s));
+        HIPCHK(launch_sterics_pose(d_rot, d_tr, n, T, d_cnt, d_cnt + Pc, d_min, c.s));
+        HIPCHK(launch_sterics(at, T, n, d_cnt, d_cnt + Pc, d_min, d_lc, d_lt, d_exits, c.s));
+        HIPCHK(hipEventRecord(c.ev[2], c.s));
+        HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)Pc * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(hipMemcpyAsync(h_min.data(), d_min, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, c.s));
+        if (d_lc) HIPCHK(hipMemcpyAsync(out->lig_clash + (size_t)p0 * Al, d_lc, (size_t)n * Al * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        if (d_lt) HIPCHK(hipMemcpyAsync(out->lig_contact + (size_t)p0 * Al, d_lt, (size_t)n * Al * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(hipStreamSynchronize(c.s));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) copy_ms += ms;
+        if (hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess) kernel_ms += ms;
+        for (int p = 0; p < n; ++p) {
+            if (out->n_clash) out->n_clash[p0 + p] = h_cnt[(size_t)p];
+            if (out->n_contact) out->n_contact[p0 + p] = h_cnt[(size_t)Pc + p];
+            if (out->min_dist) std::memcpy(out->min_dist + p0 + p, &h_min[(size_t)p], sizeof(double));
+        }
+    }
+    if (d_exits) {
+        uint64_t h[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(h, d_exits, sizeof(h), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(hipStreamSynchronize(c.s));
+        g_sterics_exits[0] = (uint64_t)P * (uint64_t)((a->Al + 63) / 64);
+        g_sterics_exits[1] = h[0];
+        g_sterics_exits[2] = h[1];
+    }
+    g_sterics_ms[0] = copy_ms;
+    g_sterics_ms[1] = kernel_ms;
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_sterics(dfm_atoms *a, int P, const float *rot, const float *tr, dfm_sterics_out *out)
+{
+    return dfm_pose_sterics_chunked(a, P, rot, tr, 0, out);
+}
+
+extern "C" int dfm_sterics_last_timing(double *copy_ms, double *kernel_ms)
+{
+    if (!copy_ms || !kernel_ms) return fail(DFM_E_INVALID, "NULL argument");
+    *copy_ms = g_sterics_ms[0];
+    *kernel_ms = g_sterics_ms[1];
+    return DFM_OK;
+}
+
+extern "C" int dfm_sterics_exit_counts(int enable, uint64_t *counts_or_null)
+{
+    if (counts_or_null) std::memcpy(counts_or_null, g_sterics_exits, sizeof(g_sterics_exits));
+    g_sterics_count = enable ? 1 : 0;
+    return DFM_OK;
+}
+
 extern "C" int dfm_complex_degree(const dfm_complex *cx) { return cx ? cx->K : -1; }
 
 extern "C" long long dfm_trim_cache(int device)

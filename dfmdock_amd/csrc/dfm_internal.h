@@ -417,4 +417,31 @@ hipError_t launch_contact_count(const uint64_t *bits, const uint8_t *member, int
 hipError_t launch_contact_score(const uint64_t *bits, const int32_t *count, int n, int R, int L, int32_t *n_contacts, int64_t *score_sum,
                                 hipStream_t s);
 
+// all-atom clash / contact screen (kernels_sterics.hip; include/dfmdock_amd.h: dfm_atoms_create / dfm_pose_sterics).  What the atoms alone
+// fix: the receptor's bounding box lo / hi (= the grid's origin and extent), the grid of nx x ny x nz cells of edge `edge` (the contact
+// cutoff), the rotation centre, the cutoffs widened to double, the fp32 reject threshold squared and `grow` = that threshold as a double
+// (the cutoff plus the rounding slack derived in kernels_sterics.hip), by which every box test is widened.
+struct StericsConst {
+    double lo[3], hi[3], center[3];
+    double edge, clash, contact, grow;
+    float reject2;
+    int nx, ny, nz;
+};
+// device arrays of a dfm_atoms: rec [Ar] float4 sorted by cell (w unused), cell_start [nx ny nz + 1], lig [Al] float4 in Morton order of the
+// ligand's own cells, lig_index [Al] = each sorted atom's index in the caller's order, sphere [ceil(Al / 64)] float4 = centre (relative to
+// the rotation centre) and radius of each block of 64 sorted ligand atoms
+struct StericsAtoms {
+    const float *rec, *lig, *sphere;
+    const int32_t *cell_start, *lig_index;
+    StericsConst sc;
+    int Ar, Al;
+};
+// T [n][12]: R(rot) row-major and tr as doubles; also sets n_clash = n_contact = 0 and min_bits = the bits of +inf for the n poses
+hipError_t launch_sterics_pose(const float *rot, const float *tr, int n, double *T, int32_t *n_clash, int32_t *n_contact, uint64_t *min_bits,
+                               hipStream_t s);
+// n <= 65535 poses.  lig_clash / lig_contact [n][Al] (caller's atom order) or nullptr: written by the waves that reach the cell walk only,
+// so zero them first.  exits [2] or nullptr: += waves that left at the sphere test, at the box test
+hipError_t launch_sterics(const StericsAtoms &at, const double *T, int n, int32_t *n_clash, int32_t *n_contact, uint64_t *min_bits,
+                          int32_t *lig_clash, int32_t *lig_contact, uint64_t *exits, hipStream_t s);
+
 }  // namespace dfm

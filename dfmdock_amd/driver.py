@@ -83,6 +83,94 @@ def ensemble_consensus(model: engine.Model, rec_bb, lig0, rot_update, tr_update,
     return out
 
 
+def sterics_inputs(rec, lig, family):
+    """What the all-atom screen takes from two pdbio.backbone_from_atoms dicts: the heavy atoms of both chains (sterics.heavy_atoms,
+    float32 [n,3]) and the centre pdbio.apply_pose_all_atom rotates the ligand about for this model family, as float32."""
+    from . import sterics as ST
+    ra = np.asarray(rec["aa_coords"], np.float32)[ST.heavy_atoms(rec["atoms"])]
+    la = np.asarray(lig["aa_coords"], np.float32)[ST.heavy_atoms(lig["atoms"])]
+    cen = np.asarray(lig["aa_coords"], np.float64).reshape(-1, 3).mean(0) if family == 1 else np.asarray(lig["bb_coords"], np.float64)[:, 1].mean(0)
+    return ra, la, cen.astype(np.float32)
+
+
+def ensemble_sterics(model: engine.Model, rec, lig, rot_update, tr_update, clash_cutoff=3.0, contact_cutoff=5.0, per_atom=False):
+    """All-atom clash / contact screen of trajectories on the GPU (dfm_pose_sterics) from their final (rot_update, tr_update) alone: the
+    heavy atoms of the two parsed PDB chains, the ligand moved as pdbio.apply_pose_all_atom moves it.  Returns the dict of Atoms.sterics
+    (n_clash, n_contact, min_dist, flags, threshold, ensemble_mean, ensemble_std) plus the cutoffs."""
+    ra, la, cen = sterics_inputs(rec, lig, model.hp.family)
+    with model.atoms(ra, la, cen, clash_cutoff, contact_cutoff) as at:
+        out = at.sterics(np.asarray(rot_update, np.float32).reshape(-1, 3), np.asarray(tr_update, np.float32).reshape(-1, 3), per_atom=per_atom)
+        out.update(clash_cutoff=at.clash_cutoff, contact_cutoff=at.contact_cutoff)
+    return out
+
+
+def residue_sterics(model: engine.Model, rec, lig, rot, tr, clash_cutoff=3.0, contact_cutoff=5.0):
+    """Per ligand residue of ONE pose: (keys, clash pairs, contact pairs) - the per-atom counts of the screen summed over each residue's
+    heavy atoms (sterics.residue_of_atoms)."""
+    from . import sterics as ST
+    sd = ensemble_sterics(model, rec, lig, np.asarray(rot).reshape(1, 3), np.asarray(tr).reshape(1, 3), clash_cutoff, contact_cutoff, per_atom=True)
+    keys, res = ST.residue_of_atoms(lig["atoms"], ST.heavy_atoms(lig["atoms"]))
+    return keys, ST.residue_counts(sd["lig_clash"][0], res, len(keys)), ST.residue_counts(sd["lig_contact"][0], res, len(keys))
+
+
+def _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff):
+    """None (off) or (filter, clash cutoff, contact cutoff) of a pair driver's screen options."""
+    if not (clash_screen or clash_filter):
+        return None
+    from .sterics import check_cutoffs
+    cc, ct = check_cutoffs(clash_cutoff, contact_cutoff)
+    return bool(clash_filter), cc, ct
+
+
+def _screen(model, rec, lig, cols, opts):
+    """The screen of a pair driver's trajectories.  Returns (sterics data or None, bad): bad [n] bool = the poses --clash-filter removes
+    (CAPRI's flags), or None when nothing is removed - the filter is off, nothing is flagged, or every pose would go (`fallback`)."""
+    if opts is None:
+        return None, None
+    sd = ensemble_sterics(model, rec, lig, cols["rot_update"], cols["tr_update"], opts[1], opts[2])
+    sd["filtered"], sd["fallback"] = opts[0], bool(opts[0] and sd["flags"].all())
+    bad = sd["flags"].copy() if opts[0] and sd["flags"].any() and not sd["fallback"] else None
+    return sd, bad
+
+
+def _kept(pick, bad, *cols):
+    """pick(*cols) -> index, over the poses that are not `bad`."""
+    if bad is None:
+        return int(pick(*cols))
+    idx = np.nonzero(~bad)[0]
+    return int(idx[int(pick(*(np.asarray(c)[idx] for c in cols)))])
+
+
+def _nan_key(key, bad):
+    """The clustering key with NaN on the removed poses (cluster.rank_order sorts NaN last)."""
+    return key if bad is None or key is None else np.where(bad, np.nan, np.asarray(key, np.float64))
+
+
+def _pose_sterics(sd, k):
+    m = float(sd["min_dist"][k])
+    return {"n_clash": int(sd["n_clash"][k]), "n_contact": int(sd["n_contact"][k]), "min_dist": m if np.isfinite(m) else None,
+            "flagged": bool(sd["flags"][k])}
+
+
+def _sterics_result(sd, k):
+    """The `sterics` entries of a pair driver's result for the kept pose k: none without the screen."""
+    if sd is None:
+        return {}
+    fin = lambda v: float(v) if np.isfinite(v) else None
+    return {"sterics": dict(_pose_sterics(sd, k), threshold=fin(sd["threshold"]), ensemble_mean=fin(sd["ensemble_mean"]),
+                            ensemble_std=fin(sd["ensemble_std"]), clash_cutoff=sd["clash_cutoff"], contact_cutoff=sd["contact_cutoff"],
+                            filtered=sd["filtered"], fallback=sd["fallback"]),
+            "sterics_data": sd, "index": int(k)}
+
+
+def _remarks(sd, k):
+    """The REMARK line of a written model: none without the screen."""
+    if sd is None:
+        return None
+    return [f"dfmdock_amd sterics n_clash {int(sd['n_clash'][k])} n_contact {int(sd['n_contact'][k])} "
+            f"(heavy-atom pairs below {sd['clash_cutoff']:g} / {sd['contact_cutoff']:g} A)"]
+
+
 def _check_rank(rank, consensus_top):
     if rank not in ("energy", "consensus"):
         raise ValueError(f"rank must be 'energy' or 'consensus', got {rank!r}")
@@ -90,7 +178,7 @@ def _check_rank(rank, consensus_top):
         raise ValueError(f"consensus_top must be in (0, 1], got {consensus_top}")
 
 
-def _with_consensus(model, rec, lig0, cols, k, key, opts):
+def _with_consensus(model, rec, lig0, cols, k, key, opts, bad=None):
     """The consensus part of a pair driver.  opts = None (off) or (rank, cutoff, top); k / key: the pose and the clustering key the
     driver's own rule gives.  Returns (k, key, extra result entries): under rank "consensus" k is the pose consensus.pick keeps and key
     its order (consensus.rank_positions) - unless no pose has any contact, when both stay and `fallback` says so."""
@@ -100,6 +188,8 @@ def _with_consensus(model, rec, lig0, cols, k, key, opts):
     from .cluster import rank_order
     rank, cutoff, top = opts
     cd = ensemble_consensus(model, rec["bb_coords"], lig0, cols["rot_update"], cols["tr_update"], cols["energy"], cutoff, top)
+    if bad is not None:      # poses the clash filter removed: no score, so never picked and last in consensus order
+        cd["consensus"] = np.where(bad, np.nan, cd["consensus"])
     ranked_by = "energy"
     if rank == "consensus":
         k2 = CS.pick(cd["consensus"], cols["energy"])
@@ -504,7 +594,8 @@ def _selected_metrics(model, native, rec, lig0, res):
 def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_steps=40, seed=0, precision="mfma16",
               out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", restraints=None,
               restraint_rank="satisfied", restraint_params=None, top_k=None, cluster_radius=4.0, cluster_rule="energy", refine_t=None,
-              refine_samples=8, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, **sampler_kw):
+              refine_samples=8, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
+              clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
     pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
     the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
@@ -533,9 +624,17 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     `index` and `trajectories` (every trajectory's energy, rot_update, tr_update, as refine_pair returns them; with restraints: the
     restrained path's own `trajectories`).  rank="consensus" (implies consensus) keeps the pose with the highest consensus instead (ties: lower energy, then lower
     index; it overrides restraint_rank) and makes that order the clustering key of `top_k`; when no trajectory has any contact the
-    driver's own rule stays and `fallback` is true."""
+    driver's own rule stays and `fallback` is true.
+
+    `clash_screen`: the all-atom clash / contact screen of every trajectory (ensemble_sterics: heavy-atom pairs below `clash_cutoff` /
+    `contact_cutoff` A, CAPRI's mean + 2 std rule over the ensemble).  The result gains `sterics` ({n_clash, n_contact, min_dist, flagged}
+    of the kept pose, threshold, ensemble_mean, ensemble_std, the cutoffs, filtered, fallback), `sterics_data` (the arrays), `index` and
+    `trajectories`; every model of `top_k` gains `sterics`, and every written file a REMARK line with its counts.  `clash_filter` (implies
+    the screen): flagged poses are removed before the selection, the consensus ranking and the clustering - they can neither be kept nor
+    become a model; were every pose flagged, nothing is removed and `fallback` is true."""
     _check_rank(rank, consensus_top)
     cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
+    ster = _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff)
     if native is not None:
         _check_native(native, rec, lig)
     if refine_t is not None and top_k is None:
@@ -557,7 +656,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     if restraints is not None:
         return _dock_pair_restrained(gx, model, rec, lig, restraints, restraint_rank, restraint_params, num_samples, num_steps, seed,
                                      precision, chk, out_pdb, max_batch, sampler_kw, clu,
-                                     None if refine_t is None else (float(refine_t), int(refine_samples)), native, cons)
+                                     None if refine_t is None else (float(refine_t), int(refine_samples)), native, cons, ster)
     best = None
     done = 0
     cols = {k: [] for k in ("energy", "rot_update", "tr_update")}
@@ -567,34 +666,38 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         k = int(np.argmin(r["energy"]))
         if best is None or r["energy"][k] < best[0]:     # strict <: the first minimum wins, as in the reference
             best = (float(r["energy"][k]), r["rot_update"][k].copy(), r["tr_update"][k].copy())
-        if clu is not None or cons is not None:
+        if clu is not None or cons is not None or ster is not None:
             for c in cols:
                 cols[c].append(r[c])
         done += b
     lig0 = gx.lig_pos0
     if refine_t is None:
         gx.close()
-    key, extra = None, {}
-    if clu is not None or cons is not None:
+    key, extra, sd, bad = None, {}, None, None
+    if clu is not None or cons is not None or ster is not None:
         cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
         key = cols["energy"]
-    if cons is not None:
+    if cons is not None or ster is not None:
         k0 = int(np.argmin(cols["energy"]))      # the first minimum: the pose `best` holds
-        k, key, extra = _with_consensus(model, rec, lig0, cols, k0, key, cons)
+        sd, bad = _screen(model, rec, lig, cols, ster)
+        k = _kept(np.argmin, bad, cols["energy"])
+        k, key, extra = _with_consensus(model, rec, lig0, cols, k, _nan_key(key, bad), cons, bad)
+        key = _nan_key(key, bad)
         if k != k0:
             best = (float(cols["energy"][k]), cols["rot_update"][k].copy(), cols["tr_update"][k].copy())
+        extra.update(_sterics_result(sd, k))
         extra["trajectories"] = {c: cols[c] for c in ("energy", "rot_update", "tr_update")}
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], best[1], best[2],
                                        center="all_atoms" if model.hp.family == 1 else "ca")
     if out_pdb:
         rec_atoms = [a for a in rec["atoms"]]
-        pdbio.write_complex_pdb(out_pdb, rec_atoms, lig["atoms"], lig_aa)
+        pdbio.write_complex_pdb(out_pdb, rec_atoms, lig["atoms"], lig_aa, **({} if sd is None else {"remarks": _remarks(sd, k)}))
     res = {"energy": best[0], "rot_update": best[1], "tr_update": best[2], "lig_aa_coords": lig_aa, "precision": precision,
            "selfcheck": chk}
     res.update(extra)
     _selected_metrics(model, native, rec, lig0, res)
     if clu is not None:
-        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native))
+        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad))
         if refine_t is not None:
             refine_models(model, gx, rec, lig, lig0, cols, res["models"], float(refine_t), int(refine_samples), num_steps, seed, precision,
                           out_pdb, native=native, **sampler_kw)
@@ -604,18 +707,26 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
 
 def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
                 out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", perturb=True, restraints=None,
-                restraint_params=None, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, **sampler_kw):
+                restraint_params=None, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
+                clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, start_shift=None, **sampler_kw):
     """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories
     start from that pose noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps
     down from t_begin; like dock_pair the minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns
     dock_pair's dict plus `t_begin`, `index` and `trajectories` (every trajectory's energy, rot_update, tr_update).  `restraints`
     ([restraints.RestraintGroup]) turns the restraint step on (DFM_F_RESTRAINTS).  `native` (as for dock_pair): the result gains
     `metrics` of the kept pose and `start_metrics` of the pose the refinement started from.  `consensus` / `rank` / `consensus_top` /
-    `consensus_cutoff`: as for dock_pair."""
+    `consensus_cutoff`: as for dock_pair.  `clash_screen` / `clash_filter` / `clash_cutoff` / `contact_cutoff`: as for dock_pair.
+    `start_shift` ([num_samples,3]): trajectory i starts from the input pose translated by start_shift[i] (the engine's start_pos); the
+    shift is added to its tr_update, so (rot_update, tr_update) keep mapping the INPUT pose onto the final one."""
     _check_rank(rank, consensus_top)
     cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
+    ster = _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff)
     if native is not None:
         _check_native(native, rec, lig)
+    if start_shift is not None:
+        start_shift = np.asarray(start_shift, np.float32).reshape(-1, 3)
+        if start_shift.shape[0] != num_samples:
+            raise ValueError(f"start_shift must be [{num_samples},3], got {start_shift.shape}")
     gx = engine.Complex(model, rec_x, lig_x, rec["bb_coords"], lig["bb_coords"])
     precision, chk = checked_precision(gx, precision, "pair", selfcheck, on_selfcheck_fail, seed=seed)
     if restraints is not None:
@@ -624,19 +735,26 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
     done = 0
     while done < num_samples:
         b = min(max_batch, num_samples - done)
+        skw = dict(sampler_kw)
+        if start_shift is not None:      # a translation commutes with the rotation about the (equally translated) centre
+            skw["start_pos"] = gx.lig_pos0[None] + start_shift[done:done + b, None, None, :]
         r = gx.refine(B=b, t_begin=t_begin, perturb=perturb, num_steps=num_steps, seed=seed + done, restraints=restraints is not None,
-                      **engine.precision_kwargs(precision), **sampler_kw)
+                      **engine.precision_kwargs(precision), **skw)
+        if start_shift is not None:
+            r["tr_update"] = (r["tr_update"] + start_shift[done:done + b]).astype(np.float32)
         for c in cols:
             cols[c].append(r[c])
         done += b
     gx.close()
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
-    k = int(np.argmin(cols["energy"]))      # the first minimum wins, as in dock_pair
-    k, _, extra = _with_consensus(model, rec, gx.lig_pos0, cols, k, None, cons)
+    sd, bad = _screen(model, rec, lig, cols, ster)
+    k = _kept(np.argmin, bad, cols["energy"])      # the first minimum wins, as in dock_pair
+    k, _, extra = _with_consensus(model, rec, gx.lig_pos0, cols, k, None, cons, bad)
+    extra.update(_sterics_result(sd, k))
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k],
                                        center="all_atoms" if model.hp.family == 1 else "ca")
     if out_pdb:
-        pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa)
+        pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa, **({} if sd is None else {"remarks": _remarks(sd, k)}))
     res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, "index": k, "t_begin": float(t_begin), "trajectories": cols}
     res.update(extra)
@@ -672,18 +790,26 @@ def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps
     return models
 
 
-def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None):
-    """dock_pair's `models`: the centres of up to top_k clusters in cluster order, each written as <out_pdb stem>_<rank>.pdb."""
+def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=None, bad=None):
+    """dock_pair's `models`: the centres of up to top_k clusters in cluster order, each written as <out_pdb stem>_<rank>.pdb.  sd: the
+    screen's data (every model gains `sterics`, every file a REMARK line); bad: poses the clash filter removed - their key is NaN, so they
+    come last, and a cluster one of them would lead is left out."""
     top_k, radius, rule = clu
     cl = cluster_trajectories(model, lig0, cols["rot_update"], cols["tr_update"], key, radius, rule, top_k)
     models = []
-    for k, (c, n) in enumerate(zip(cl["center"], cl["size"])):
+    for c, n in zip(cl["center"], cl["size"]):
         c = int(c)
+        if bad is not None and bad[c]:
+            continue
+        k = len(models)
         models.append({"rank": k + 1, "index": c, "energy": float(cols["energy"][c]), "cluster_size": int(n)})
+        if sd is not None:
+            models[-1]["sterics"] = _pose_sterics(sd, c)
         if out_pdb:
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c],
                                            center="all_atoms" if model.hp.family == 1 else "ca")
-            pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa)
+            pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa,
+                                    **({} if sd is None else {"remarks": _remarks(sd, c)}))
     if native is not None and models:
         from .cluster import rebuild_backbone
         cen = [m["index"] for m in models]
@@ -699,7 +825,7 @@ def model_path(out_pdb, rank):
 
 
 def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_samples, num_steps, seed, precision, chk, out_pdb, max_batch,
-                          sampler_kw, clu=None, refine=None, native=None, cons=None):
+                          sampler_kw, clu=None, refine=None, native=None, cons=None, ster=None):
     from . import restraints as RS
     gx.set_restraints(restraints, params)
     cols = {k: [] for k in ("energy", "restraint_energy", "restraints_satisfied", "rot_update", "tr_update")}
@@ -716,16 +842,19 @@ def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_sam
     if refine is None:
         gx.close()
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
-    k = RS.rank_key(cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else int(np.argmin(cols["energy"]))
+    sd, bad = _screen(model, rec, lig, cols, ster)
+    k = _kept(RS.rank_key, bad, cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else _kept(np.argmin, bad, cols["energy"])
     key, extra = None, {}
     if clu is not None:
         from .cluster import satisfied_key
         key = satisfied_key(cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else cols["energy"]
-    k, key, extra = _with_consensus(model, rec, lig0, cols, k, key, cons)
+    k, key, extra = _with_consensus(model, rec, lig0, cols, k, _nan_key(key, bad), cons, bad)
+    key = _nan_key(key, bad)
+    extra.update(_sterics_result(sd, k))
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k],
                                        center="all_atoms" if model.hp.family == 1 else "ca")
     if out_pdb:
-        pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa)
+        pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa, **({} if sd is None else {"remarks": _remarks(sd, k)}))
     res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, "index": k, "restraints": len(restraints),
            "restraint_rank": rank, "restraint_energy": float(cols["restraint_energy"][k]),
@@ -734,7 +863,7 @@ def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_sam
     res.update(extra)
     _selected_metrics(model, native, rec, lig0, res)
     if clu is not None:
-        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native))
+        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad))
         if refine is not None:
             refine_models(model, gx, rec, lig, lig0, cols, res["models"], refine[0], refine[1], num_steps, seed, precision, out_pdb,
                           restraints=True, native=native, **sampler_kw)

@@ -205,6 +205,13 @@ class Model:
         return o
 
 
+    def atoms(self, rec_atoms, lig_atoms, center, clash_cutoff=3.0, contact_cutoff=5.0):
+        """The heavy atoms of a pair prepared for the all-atom clash / contact screen on the GPU (dfm_atoms_create): rec_atoms [Ar,3],
+        lig_atoms [Al,3], center [3] = the point the sampler's (rot, tr) rotate the ligand about.  Returns an Atoms whose
+        `.sterics(rot, tr)` screens P poses in one call."""
+        return Atoms(self, rec_atoms, lig_atoms, center, clash_cutoff, contact_cutoff)
+
+
 class Native:
     """A native pose resident on the model's GPU (dfm_native): interface residues, native contacts and the receptor's share of the
     Kabsch sums, computed once.  Read-only after creation: `metrics` may be called from several threads at once."""
@@ -270,6 +277,83 @@ class Native:
         out.fnat, out.dockq, out.n_recovered = o["fnat"].ctypes.data_as(dp), o["DockQ"].ctypes.data_as(dp), _p(o["n_recovered"], L.I32P)
         L.check(L.lib().dfm_pose_metrics(self._h, P, _p(lp), _p(rp), C.byref(out)), "dfm_pose_metrics")
         return o
+
+
+class Atoms:
+    """The heavy atoms of a receptor / ligand pair resident on the model's GPU (dfm_atoms): the receptor binned into a cell grid, the
+    ligand in blocks of neighbours.  Read-only after creation: `sterics` may be called from several threads at once."""
+
+    def __init__(self, model: Model, rec_atoms, lig_atoms, center, clash_cutoff=3.0, contact_cutoff=5.0):
+        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _f32(center).reshape(-1)
+        if cen.size != 3:
+            raise ValueError(f"center must have 3 entries, got {np.shape(center)}")
+        self.model, self.Ar, self.Al = model, ra.shape[0], la.shape[0]
+        self.clash_cutoff, self.contact_cutoff = float(np.float32(clash_cutoff)), float(np.float32(contact_cutoff))
+        prm = L.StericsParamsC(float(clash_cutoff), float(contact_cutoff), 0)
+        self._h = L.lib().dfm_atoms_create(model._h, self.Ar, _p(ra), self.Al, _p(la), _p(cen), C.byref(prm))
+        if not self._h:
+            msg = L.lib().dfm_last_error()
+            L.check(-2 if msg.startswith((b"dfm_atoms_create", b"hipSetDevice")) else -1, "dfm_atoms_create")      # else: bad argument
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().dfm_atoms_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{n_cells, max_cell_atoms, cell_edge} of the receptor's grid (dfm_atoms_info)."""
+        n, mx, e = C.c_int32(0), C.c_int32(0), C.c_float(0)
+        L.check(L.lib().dfm_atoms_info(self._h, C.byref(n), C.byref(mx), C.byref(e)), "dfm_atoms_info")
+        return {"n_cells": n.value, "max_cell_atoms": mx.value, "cell_edge": e.value}
+
+    def sterics(self, rot, tr, per_atom=False, chunk_poses=0, members=None):
+        """Clash / contact screen of P poses (dfm_pose_sterics; the float64 definition is sterics.sterics): rot [P,3] axis-angle and tr
+        [P,3] as rot_update / tr_update hold them.  Returns {n_clash, n_contact (int32 [P]), min_dist (float64 [P], +inf without a
+        contact)}, with `per_atom` lig_clash / lig_contact (int32 [P,Al], the caller's atom order), and CAPRI's rule over `members`
+        (bool [P]; None: every pose) from sterics.capri_flags: flags (bool [P]), threshold, ensemble_mean, ensemble_std."""
+        from . import sterics as ST
+        r, t = _f32(rot).reshape(-1, 3), _f32(tr).reshape(-1, 3)
+        if r.shape != t.shape or r.shape[0] < 1:
+            raise ValueError(f"rot and tr must both be [P,3] with P >= 1, got {np.shape(rot)} and {np.shape(tr)}")
+        P = r.shape[0]
+        o = {"n_clash": np.zeros(P, np.int32), "n_contact": np.zeros(P, np.int32), "min_dist": np.zeros(P, np.float64)}
+        out = L.StericsOutC()
+        out.n_clash, out.n_contact = _p(o["n_clash"], L.I32P), _p(o["n_contact"], L.I32P)
+        out.min_dist = o["min_dist"].ctypes.data_as(C.POINTER(C.c_double))
+        if per_atom:
+            o["lig_clash"], o["lig_contact"] = np.zeros((P, self.Al), np.int32), np.zeros((P, self.Al), np.int32)
+            out.lig_clash, out.lig_contact = _p(o["lig_clash"], L.I32P), _p(o["lig_contact"], L.I32P)
+        L.check(L.lib().dfm_pose_sterics_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_sterics")
+        o["flags"], o["threshold"], o["ensemble_mean"], o["ensemble_std"] = ST.capri_flags(o["n_clash"], members)
+        return o
+
+
+def sterics_last_timing():
+    """(host-to-device copy ms, kernel ms) of this thread's last Atoms.sterics call (dfm_sterics_last_timing)."""
+    a, b = C.c_double(0), C.c_double(0)
+    L.check(L.lib().dfm_sterics_last_timing(C.byref(a), C.byref(b)), "dfm_sterics_last_timing")
+    return a.value, b.value
+
+
+def sterics_exit_counts(enable):
+    """Diagnostic (dfm_sterics_exit_counts): (waves, left at the sphere test, left at the box test) of this thread's last counted
+    Atoms.sterics call; `enable` switches the counting of this thread's next calls."""
+    n = (C.c_uint64 * 3)()
+    L.check(L.lib().dfm_sterics_exit_counts(int(bool(enable)), n), "dfm_sterics_exit_counts")
+    return int(n[0]), int(n[1]), int(n[2])
 
 
 def metrics_last_timing():

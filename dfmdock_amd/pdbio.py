@@ -91,9 +91,11 @@ def apply_pose_all_atom(aa_coords, bb_coords, rot, tr, center="ca"):
     return (np.asarray(aa_coords, np.float64) - center) @ R.T + center + np.asarray(tr, np.float64).reshape(3)
 
 
-def write_complex_pdb(path, rec_atoms, lig_atoms, lig_coords):
-    """Receptor atoms as read + ligand atoms at `lig_coords`, one PDB model."""
+def write_complex_pdb(path, rec_atoms, lig_atoms, lig_coords, remarks=None):
+    """Receptor atoms as read + ligand atoms at `lig_coords`, one PDB model.  `remarks`: lines written as REMARK records on top."""
     with open(path, "w") as f:
+        for r in remarks or ():
+            f.write("REMARK " + r + "\n")
         k = 0
         for atoms, coords in ((rec_atoms, None), (lig_atoms, lig_coords)):
             for idx, a in enumerate(atoms):

@@ -417,6 +417,52 @@ int dfm_consensus_chunk_poses(int R, int L);
 /* GPU milliseconds of the calling thread's last dfm_pose_consensus, summed over its chunks and passes: the host-to-device copies of the
  * poses and the kernels (k_contact_bits, k_contact_count, k_contact_marginals, k_contact_score) - tools/consensus_bench.py */
 int dfm_consensus_last_timing(double *copy_ms, double *kernel_ms);
+/* All-atom clash and contact screen of P rigid poses of one ligand (CAPRI's steric rule): the only calls that read atoms beyond the
+ * backbone.  dfmdock_amd/sterics.py is the float64 definition these calls are tested against.  rec_atoms [Ar,3] and lig_atoms [Al,3] are
+ * heavy atoms (the caller filters hydrogens); center [3] is the point the sampler rotates the ligand about (the CA centroid for the
+ * first model family, the all-atom mean for the second); a pose is (rot [3] axis-angle, tr [3]) = dfm_traj_out.rot_update / tr_update.
+ *   pose p of ligand atom a: (a - center) R(rot_p)^T + center + tr_p in fp64 on the fp32 inputs, R as the host's axis_angle_to_matrix
+ *     (small-angle branch below 1e-6 rad); distance of a pair: sqrt((dx*dx + dy*dy) + dz*dz) in fp64.
+ *   n_clash [P]: pairs (receptor atom, ligand atom) closer than clash_cutoff (strict; default 3.0).  n_contact [P]: pairs closer than
+ *     contact_cutoff (default 5.0, >= clash_cutoff).  min_dist [P]: the smallest distance among the pairs below contact_cutoff, +inf
+ *     without one.  lig_clash / lig_contact [P,Al]: the same counts per ligand atom, in the caller's atom order.
+ *   A NaN distance is neither: a pose with a NaN or infinite rot / tr gets 0, 0 and +inf and disturbs no other pose (not an error).
+ * dfm_atoms_create bins the receptor atoms into a uniform grid whose cell edge is contact_cutoff (a counting sort on the host, once),
+ * sorts the ligand atoms spatially into blocks of 64 and uploads both; the handle is read-only afterwards.  dfm_atoms_info: the number
+ * of cells, the most atoms in one cell, the cell edge.
+ * Every output pointer may be NULL.  Counts are integers and min_dist a minimum: apart from pairs whose distance rounds onto a cutoff
+ * the results equal the definition, and none depends on P, on a pose's index, on the order of the poses or on the chunks of a call.
+ * Per-atom output is produced chunk_poses poses at a time (0: as many as fill 64 MiB of it; without per-atom output: 32768, the launch
+ * limit); dfm_pose_sterics_chunked overrides the creator's chunk_poses for one call.
+ * DFM_E_INVALID / NULL, nothing enqueued: NULL m / rec_atoms / lig_atoms / center (a / rot / tr / out), Ar or Al < 1 or > 2^24, a cutoff
+ * not finite or <= 0, contact_cutoff < clash_cutoff, chunk_poses < 0, a non-finite receptor atom, ligand atom or centre, a receptor
+ * bounding box of more than 2^24 cells, P < 1.  Counts are int32: a pose may have at most 2^31 - 1 pairs below the contact cutoff.
+ * DFM_E_OOM when the atoms or a chunk's per-atom output do not fit.
+ * Takes the MODEL handle for its device only.  Every call owns a non-blocking stream and its device temporaries, so calls on one handle
+ * may run from several host threads at once and next to that model's sampling handles.  No reference call has a counterpart. */
+typedef struct dfm_atoms dfm_atoms;
+typedef struct {
+    float clash_cutoff, contact_cutoff;
+    int chunk_poses;       /* 0: default */
+} dfm_sterics_params;
+typedef struct {
+    int32_t *n_clash, *n_contact;      /* [P]    or NULL */
+    double *min_dist;                  /* [P]    or NULL */
+    int32_t *lig_clash, *lig_contact;  /* [P,Al] or NULL */
+} dfm_sterics_out;
+dfm_atoms *dfm_atoms_create(dfm_model *m, int Ar, const float *rec_atoms, int Al, const float *lig_atoms, const float center[3],
+                            const dfm_sterics_params *p_or_null);
+void dfm_atoms_destroy(dfm_atoms *a);
+int dfm_atoms_info(const dfm_atoms *a, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge);
+int dfm_pose_sterics(dfm_atoms *a, int P, const float *rot, const float *tr, dfm_sterics_out *out);
+int dfm_pose_sterics_chunked(dfm_atoms *a, int P, const float *rot, const float *tr, int chunk_poses, dfm_sterics_out *out);
+/* GPU milliseconds of the calling thread's last dfm_pose_sterics, summed over its chunks: the host-to-device copies of the poses and
+ * the kernels (k_sterics_pose, k_sterics, the memsets of the per-atom output) - tools/sterics_bench.py */
+int dfm_sterics_last_timing(double *copy_ms, double *kernel_ms);
+/* diagnostic (tools/sterics_bench.py): counts_or_null [3] receives, of the calling thread's last counted dfm_pose_sterics, the waves
+ * launched (poses x blocks of 64 ligand atoms), those that left at the block's sphere test and those that left at its box test;
+ * `enable` != 0 makes this thread's next calls count (one atomic per leaving wave: not for timing) */
+int dfm_sterics_exit_counts(int enable, uint64_t *counts_or_null);
 /* edges per node for this complex: min(N,20) + min(40, N-20) */
 int dfm_complex_degree(const dfm_complex *cx);
 /* Device blocks released by destroyed handles are parked per device for the next handle (a set driver creates and destroys a
