@@ -127,9 +127,10 @@ def _screen(model, rec, lig, cols, opts):
     (CAPRI's flags), or None when nothing is removed - the filter is off, nothing is flagged, or every pose would go (`fallback`)."""
     if opts is None:
         return None, None
-    sd = ensemble_sterics(model, rec, lig, cols["rot_update"], cols["tr_update"], opts[1], opts[2])
-    sd["filtered"], sd["fallback"] = opts[0], bool(opts[0] and sd["flags"].all())
-    bad = sd["flags"].copy() if opts[0] and sd["flags"].any() and not sd["fallback"] else None
+    filtered, clash_cutoff, contact_cutoff = opts
+    sd = ensemble_sterics(model, rec, lig, cols["rot_update"], cols["tr_update"], clash_cutoff, contact_cutoff)
+    sd["filtered"], sd["fallback"] = filtered, bool(filtered and sd["flags"].all())
+    bad = sd["flags"].copy() if filtered and sd["flags"].any() and not sd["fallback"] else None
     return sd, bad
 
 
@@ -492,64 +493,62 @@ def run_set(model: engine.Model, complexes, num_samples=40, num_steps=40, seed=0
     recs = np.concatenate(records, 0) if records else np.zeros((0, D.RECORD_WIDTH), np.float32)
     gathered = D.gather_records(recs) if world > 1 or len(recs) else recs
     ranked = D.rank_by_energy(gathered) if world > 1 or len(recs) else {}
-    if cluster_radius is not None:
+
+    def per_complex(fields, fn):
+        """Every row's columns `fields` from fn(ci, trajectory indices, energy, rot_update, tr_update) -> one tuple of values per trajectory,
+        given all trajectories of complex ci in index order.  fn runs where they are all present: on the owning rank when complexes are
+        sharded, on rank 0 after the record gather when trajectories are split (the values then reach every rank's rows)."""
         mine = list(range(len(complexes))) if split_trajectories else [p.ci for p, _, _ in done]
-        assign = {}
+        values = {}
         if not split_trajectories or rank == 0:
             for ci in mine:
                 r = gathered[gathered[:, 0] == ci]
                 if not len(r):
                     continue
                 r = r[np.argsort(r[:, 1], kind="stable")]
-                lig0 = input_pose(complexes[ci], rots[ci], global_rotation)[1]
-                cl = cluster_trajectories(model, lig0, r[:, 4:7], r[:, 7:10], r[:, 2], cluster_radius, cluster_rule, top_k)
-                centers = set(int(r[c, 1]) for c in cl["center"])
+                t = r[:, 1].astype(int)      # D.make_records: complex, trajectory, energy, num_clashes, rot_update[3], tr_update[3]
                 cid = complexes[ci].get("id", str(ci))
-                for t, k in zip(r[:, 1].astype(int), cl["cluster_of"]):
-                    assign[f"{cid}/{t}"] = (int(k), int(t in centers))
+                for ti, v in zip(t, fn(ci, t, r[:, 2], r[:, 4:7], r[:, 7:10])):
+                    values[f"{cid}/{ti}"] = v
         if split_trajectories and world > 1:
-            assign = D.gather_objects(assign)[0]
+            values = D.gather_objects(values)[0]
         for row in rows:
-            row["cluster"], row["is_center"] = assign[f"{row['id']}/{row['index']}"]
-    if consensus:
-        mine = list(range(len(complexes))) if split_trajectories else [p.ci for p, _, _ in done]
-        scored = {}
-        if not split_trajectories or rank == 0:
-            for ci in mine:
-                r = gathered[gathered[:, 0] == ci]
-                if not len(r):
-                    continue
-                r = r[np.argsort(r[:, 1], kind="stable")]
-                rec0, lig0 = input_pose(complexes[ci], rots[ci], global_rotation)
-                cd = ensemble_consensus(model, rec0, lig0, r[:, 4:7], r[:, 7:10], r[:, 2], consensus_cutoff, consensus_top)
-                cid = complexes[ci].get("id", str(ci))
-                for t, sc, nc in zip(r[:, 1].astype(int), cd["consensus"], cd["n_contacts"]):
-                    scored[f"{cid}/{t}"] = (float(sc), int(nc))
-        if split_trajectories and world > 1:
-            scored = D.gather_objects(scored)[0]
-        for row in rows:
-            row["consensus"], row["n_contacts"] = scored[f"{row['id']}/{row['index']}"]
-    if out_csv is not None:
-        all_rows = _gather_rows(rows, world)
+            row.update(zip(fields, values[f"{row['id']}/{row['index']}"]))
+
+    def clusters(ci, t, energy, rot_update, tr_update):
+        lig0 = input_pose(complexes[ci], rots[ci], global_rotation)[1]
+        cl = cluster_trajectories(model, lig0, rot_update, tr_update, energy, cluster_radius, cluster_rule, top_k)
+        centers = set(int(t[c]) for c in cl["center"])
+        return [(int(k), int(ti in centers)) for ti, k in zip(t, cl["cluster_of"])]
+
+    def consensus_scores(ci, t, energy, rot_update, tr_update):
+        rec0, lig0 = input_pose(complexes[ci], rots[ci], global_rotation)
+        cd = ensemble_consensus(model, rec0, lig0, rot_update, tr_update, energy, consensus_cutoff, consensus_top)
+        return [(float(sc), int(nc)) for sc, nc in zip(cd["consensus"], cd["n_contacts"])]
+
+    def write_csv(path, table, fields, order):
+        """Rank 0 writes the rows of every rank in `order`."""
+        table = _gather_rows(table, world)
         if rank == 0:
-            os.makedirs(os.path.dirname(os.path.abspath(out_csv)), exist_ok=True)
-            with open(out_csv, "w", newline="") as f:
-                w = csv.DictWriter(f, fieldnames=CSV_FIELDS + (RESTRAINT_FIELDS if restraints_by_id is not None else []) +
-                                   (CLUSTER_FIELDS if cluster_radius is not None else []) + (CONSENSUS_FIELDS if consensus else []))
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w", newline="") as f:
+                w = csv.DictWriter(f, fieldnames=fields)
                 w.writeheader()
-                for row in sorted(all_rows, key=lambda x: (x["id"], int(x["index"]))):
+                for row in sorted(table, key=order):
                     w.writerow(row)
+
+    if cluster_radius is not None:
+        per_complex(CLUSTER_FIELDS, clusters)
+    if consensus:
+        per_complex(CONSENSUS_FIELDS, consensus_scores)
+    if out_csv is not None:
+        write_csv(out_csv, rows, CSV_FIELDS + (RESTRAINT_FIELDS if restraints_by_id is not None else []) +
+                  (CLUSTER_FIELDS if cluster_radius is not None else []) + (CONSENSUS_FIELDS if consensus else []),
+                  lambda x: (x["id"], int(x["index"])))
     if steps_out is not None:
         steps_out.extend(step_rows)
     if step_csv is not None:
-        all_steps = _gather_rows(step_rows, world)
-        if rank == 0:
-            os.makedirs(os.path.dirname(os.path.abspath(step_csv)), exist_ok=True)
-            with open(step_csv, "w", newline="") as f:
-                w = csv.DictWriter(f, fieldnames=STEP_FIELDS)
-                w.writeheader()
-                for row in sorted(all_steps, key=lambda x: (x["id"], int(x["index"]), x["step"])):
-                    w.writerow(row)
+        write_csv(step_csv, step_rows, STEP_FIELDS, lambda x: (x["id"], int(x["index"]), x["step"]))
     return rows, ranked
 
 
@@ -588,6 +587,42 @@ def _selected_metrics(model, native, rec, lig0, res):
         from .cluster import rebuild_backbone
         res["metrics"] = native_metrics(model, native, rec["bb_coords"],
                                         rebuild_backbone(lig0, res["rot_update"][None], res["tr_update"][None], model.hp.family))[0]
+    return res
+
+
+def _center(model):
+    """The centre pdbio.apply_pose_all_atom rotates the ligand about for this model family."""
+    return "all_atoms" if model.hp.family == 1 else "ca"
+
+
+def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native=None, cons=None, ster=None, clu=None, refine=None):
+    """What every pair driver does with its sampled trajectories: the kept pose, its files and the result.  cols: every trajectory's
+    energy, rot_update, tr_update (and the driver's own columns).  pick = (rule, *column names): the driver's own choice, rule(*columns) ->
+    index; key: the clustering key that goes with it.  entries(k): the driver's own result entries for the kept pose k.  cons / ster / clu:
+    None or the options of _with_consensus / _screen / _top_models; refine: None or the keyword arguments of refine_models - only then
+    does the handle outlive the sampling."""
+    lig0 = gx.lig_pos0
+    if refine is None:      # the columns are host arrays: the handle (and its ~GB of device workspace) goes before any post-processing
+        gx.close()
+    sd, bad = _screen(model, rec, lig, cols, ster)
+    k = _kept(pick[0], bad, *(cols[c] for c in pick[1:]))
+    k, key, extra = _with_consensus(model, rec, lig0, cols, k, _nan_key(key, bad), cons, bad)
+    key = _nan_key(key, bad)      # again: rank "consensus" has replaced the key by consensus.rank_positions
+    extra.update(_sterics_result(sd, k))
+    lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k], center=_center(model))
+    if out_pdb:
+        pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa, remarks=_remarks(sd, k))
+    res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
+           "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, **entries(k)}
+    res.update(extra)
+    if cons is not None or ster is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
+        res.setdefault("trajectories", {c: cols[c] for c in ("energy", "rot_update", "tr_update")})
+    _selected_metrics(model, native, rec, lig0, res)
+    if clu is not None:
+        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad))
+        if refine is not None:
+            refine_models(model, gx, rec, lig, lig0, cols, res["models"], precision=precision, out_pdb=out_pdb, native=native, **refine)
+            gx.close()
     return res
 
 
@@ -651,58 +686,42 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         if not (np.isfinite(cluster_radius) and cluster_radius > 0):
             raise ValueError("cluster_radius must be finite and > 0")
     clu = None if top_k is None else (int(top_k), float(cluster_radius), cluster_rule)
+    refine = None if refine_t is None else dict(t_begin=float(refine_t), n=int(refine_samples), num_steps=num_steps, seed=seed,
+                                                restraints=restraints is not None, **sampler_kw)
     gx = engine.Complex(model, rec_x, lig_x, rec["bb_coords"], lig["bb_coords"])
     precision, chk = checked_precision(gx, precision, "pair", selfcheck, on_selfcheck_fail, seed=seed)
-    if restraints is not None:
-        return _dock_pair_restrained(gx, model, rec, lig, restraints, restraint_rank, restraint_params, num_samples, num_steps, seed,
-                                     precision, chk, out_pdb, max_batch, sampler_kw, clu,
-                                     None if refine_t is None else (float(refine_t), int(refine_samples)), native, cons, ster)
-    best = None
-    done = 0
-    cols = {k: [] for k in ("energy", "rot_update", "tr_update")}
+    restrained = restraints is not None
+    if restrained:
+        gx.set_restraints(restraints, restraint_params)
+    cols = {c: [] for c in ("energy", "rot_update", "tr_update") + (("restraint_energy", "restraints_satisfied") if restrained else ())}
+    best, k0, done = None, None, 0
     while done < num_samples:
         b = min(max_batch, num_samples - done)
-        r = gx.sample(B=b, num_steps=num_steps, seed=seed + done, **engine.precision_kwargs(precision), **sampler_kw)
+        r = gx.sample(B=b, num_steps=num_steps, seed=seed + done, restraints=restrained, **engine.precision_kwargs(precision), **sampler_kw)
+        if restrained:      # the restraint terms of the final poses, on the sampler's own kernel
+            ev = gx.restraint_eval(r["lig_pos"])
+            r["restraint_energy"], r["restraints_satisfied"] = ev["energy"], ev["n_satisfied"]
         k = int(np.argmin(r["energy"]))
-        if best is None or r["energy"][k] < best[0]:     # strict <: the first minimum wins, as in the reference
-            best = (float(r["energy"][k]), r["rot_update"][k].copy(), r["tr_update"][k].copy())
-        if clu is not None or cons is not None or ster is not None:
-            for c in cols:
-                cols[c].append(r[c])
+        if k0 is None or r["energy"][k] < best:     # strict <: the first minimum wins, as in the reference
+            best, k0 = r["energy"][k], done + k
+        for c in cols:
+            cols[c].append(r[c])
         done += b
-    lig0 = gx.lig_pos0
-    if refine_t is None:
-        gx.close()
-    key, extra, sd, bad = None, {}, None, None
-    if clu is not None or cons is not None or ster is not None:
-        cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
-        key = cols["energy"]
-    if cons is not None or ster is not None:
-        k0 = int(np.argmin(cols["energy"]))      # the first minimum: the pose `best` holds
-        sd, bad = _screen(model, rec, lig, cols, ster)
-        k = _kept(np.argmin, bad, cols["energy"])
-        k, key, extra = _with_consensus(model, rec, lig0, cols, k, _nan_key(key, bad), cons, bad)
-        key = _nan_key(key, bad)
-        if k != k0:
-            best = (float(cols["energy"][k]), cols["rot_update"][k].copy(), cols["tr_update"][k].copy())
-        extra.update(_sterics_result(sd, k))
-        extra["trajectories"] = {c: cols[c] for c in ("energy", "rot_update", "tr_update")}
-    lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], best[1], best[2],
-                                       center="all_atoms" if model.hp.family == 1 else "ca")
-    if out_pdb:
-        rec_atoms = [a for a in rec["atoms"]]
-        pdbio.write_complex_pdb(out_pdb, rec_atoms, lig["atoms"], lig_aa, **({} if sd is None else {"remarks": _remarks(sd, k)}))
-    res = {"energy": best[0], "rot_update": best[1], "tr_update": best[2], "lig_aa_coords": lig_aa, "precision": precision,
-           "selfcheck": chk}
-    res.update(extra)
-    _selected_metrics(model, native, rec, lig0, res)
-    if clu is not None:
-        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad))
-        if refine_t is not None:
-            refine_models(model, gx, rec, lig, lig0, cols, res["models"], float(refine_t), int(refine_samples), num_steps, seed, precision,
-                          out_pdb, native=native, **sampler_kw)
-            gx.close()
-    return res
+    cols = {c: np.concatenate(v, 0) for c, v in cols.items()}
+    if not restrained:
+        # the loop's own minimum; consensus and the screen choose among all trajectories at once (the first minimum: the same pose)
+        pick = (np.argmin if cons is not None or ster is not None else (lambda energy: k0), "energy")
+        key, entries = cols["energy"], lambda k: {}
+    else:
+        from . import restraints as RS
+        from .cluster import satisfied_key
+        by_satisfied = restraint_rank == "satisfied"
+        pick = (RS.rank_key, "energy", "restraints_satisfied") if by_satisfied else (np.argmin, "energy")
+        key = satisfied_key(cols["energy"], cols["restraints_satisfied"]) if by_satisfied else cols["energy"]
+        entries = lambda k: {"index": k, "restraints": len(restraints), "restraint_rank": restraint_rank,
+                             "restraint_energy": float(cols["restraint_energy"][k]), "restraints_satisfied": int(cols["restraints_satisfied"][k]),
+                             "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
+    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine)
 
 
 def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
@@ -745,21 +764,10 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
         for c in cols:
             cols[c].append(r[c])
         done += b
-    gx.close()
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
-    sd, bad = _screen(model, rec, lig, cols, ster)
-    k = _kept(np.argmin, bad, cols["energy"])      # the first minimum wins, as in dock_pair
-    k, _, extra = _with_consensus(model, rec, gx.lig_pos0, cols, k, None, cons, bad)
-    extra.update(_sterics_result(sd, k))
-    lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k],
-                                       center="all_atoms" if model.hp.family == 1 else "ca")
-    if out_pdb:
-        pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa, **({} if sd is None else {"remarks": _remarks(sd, k)}))
-    res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
-           "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, "index": k, "t_begin": float(t_begin), "trajectories": cols}
-    res.update(extra)
+    res = _finish(model, gx, rec, lig, cols, (np.argmin, "energy"), None,      # the first minimum wins, as in dock_pair
+                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster)
     if native is not None:
-        _selected_metrics(model, native, rec, gx.lig_pos0, res)
         res["start_metrics"] = native_metrics(model, native, rec["bb_coords"], gx.lig_pos0[None])[0]
     return res
 
@@ -775,7 +783,7 @@ def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps
     start = rebuild_backbone(lig0, cols["rot_update"][cen], cols["tr_update"][cen], model.hp.family)      # [K,L,3,3]
     r = gx.refine(B=K * n, t_begin=t_begin, start_pos=np.repeat(start, n, 0), num_steps=num_steps, seed=seed, restraints=restraints,
                   **engine.precision_kwargs(precision), **sampler_kw)
-    center = "all_atoms" if model.hp.family == 1 else "ca"
+    center = _center(model)
     kept = [k * n + int(np.argmin(r["energy"][k * n:(k + 1) * n])) for k in range(K)]
     if native is not None:      # every centre after its refinement (before: the model's `metrics`, _top_models)
         for m, rm in zip(models, native_metrics(model, native, rec["bb_coords"], r["lig_pos"][kept])):
@@ -806,10 +814,8 @@ def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=
         if sd is not None:
             models[-1]["sterics"] = _pose_sterics(sd, c)
         if out_pdb:
-            aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c],
-                                           center="all_atoms" if model.hp.family == 1 else "ca")
-            pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa,
-                                    **({} if sd is None else {"remarks": _remarks(sd, c)}))
+            aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c], center=_center(model))
+            pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa, remarks=_remarks(sd, c))
     if native is not None and models:
         from .cluster import rebuild_backbone
         cen = [m["index"] for m in models]
@@ -822,50 +828,3 @@ def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=
 def model_path(out_pdb, rank):
     """<stem>_<rank>.pdb next to out_pdb."""
     return os.path.splitext(out_pdb)[0] + f"_{rank}.pdb"
-
-
-def _dock_pair_restrained(gx, model, rec, lig, restraints, rank, params, num_samples, num_steps, seed, precision, chk, out_pdb, max_batch,
-                          sampler_kw, clu=None, refine=None, native=None, cons=None, ster=None):
-    from . import restraints as RS
-    gx.set_restraints(restraints, params)
-    cols = {k: [] for k in ("energy", "restraint_energy", "restraints_satisfied", "rot_update", "tr_update")}
-    done = 0
-    while done < num_samples:
-        b = min(max_batch, num_samples - done)
-        r = gx.sample(B=b, num_steps=num_steps, seed=seed + done, restraints=True, **engine.precision_kwargs(precision), **sampler_kw)
-        ev = gx.restraint_eval(r["lig_pos"])
-        for k, v in (("energy", r["energy"]), ("restraint_energy", ev["energy"]), ("restraints_satisfied", ev["n_satisfied"]),
-                     ("rot_update", r["rot_update"]), ("tr_update", r["tr_update"])):
-            cols[k].append(v)
-        done += b
-    lig0 = gx.lig_pos0
-    if refine is None:
-        gx.close()
-    cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
-    sd, bad = _screen(model, rec, lig, cols, ster)
-    k = _kept(RS.rank_key, bad, cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else _kept(np.argmin, bad, cols["energy"])
-    key, extra = None, {}
-    if clu is not None:
-        from .cluster import satisfied_key
-        key = satisfied_key(cols["energy"], cols["restraints_satisfied"]) if rank == "satisfied" else cols["energy"]
-    k, key, extra = _with_consensus(model, rec, lig0, cols, k, _nan_key(key, bad), cons, bad)
-    key = _nan_key(key, bad)
-    extra.update(_sterics_result(sd, k))
-    lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k],
-                                       center="all_atoms" if model.hp.family == 1 else "ca")
-    if out_pdb:
-        pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa, **({} if sd is None else {"remarks": _remarks(sd, k)}))
-    res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
-           "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, "index": k, "restraints": len(restraints),
-           "restraint_rank": rank, "restraint_energy": float(cols["restraint_energy"][k]),
-           "restraints_satisfied": int(cols["restraints_satisfied"][k]),
-           "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
-    res.update(extra)
-    _selected_metrics(model, native, rec, lig0, res)
-    if clu is not None:
-        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad))
-        if refine is not None:
-            refine_models(model, gx, rec, lig, lig0, cols, res["models"], refine[0], refine[1], num_steps, seed, precision, out_pdb,
-                          restraints=True, native=native, **sampler_kw)
-            gx.close()
-    return res
