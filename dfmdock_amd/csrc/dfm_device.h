@@ -25,7 +25,9 @@ __host__ __device__ inline u32x4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c
     }
     return u32x4{c0, c1, c2, c3};
 }
-// uniform in (0,1): never 0 or 1
+// uniform in (0, 1]: never 0 (the smallest value is 2^-25), but EXACTLY 1.0f for x >> 8 == 0xFFFFFF (16777215.5 is not representable
+// and rounds to 2^24; from 2^23 on neighbouring inputs merge).  Consumers must accept log(u) == 0 (tests/test_geom_harness_cpu.py).
+// Changing the expression would change every native stream.
 __host__ __device__ inline float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 // RNG stream ids (counter word 3)

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void k_knn_sample(const float4 *__restrict__ c
             if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);      // (NPL ballots hoisted to the top spill scalar registers)
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // same wave: the writes above are visible to the reads below
-        const uint32_t myk = sh_key[w][lane & 31], myj = sh_j[w][lane & 31];      // knn <= 20
+        const uint32_t myk = sh_key[w][lane], myj = sh_j[w][lane];      // knn <= 60 < 64: lane e ranks winner e (lanes >= knn read unused rows and write nothing)
         int rank = 0;
         for (int e = 0; e < knn; ++e) {
             const uint32_t ke = sh_key[w][e], je = sh_j[w][e];
@@ -191,7 +191,10 @@ __global__ __launch_bounds__(256) void k_knn_sample(const float4 *__restrict__ c
                 float k2 = __builtin_inff();
                 if (!((near >> r) & 1) && d != __builtin_inff()) {   // not taken by kNN, j < N
                     d = d < 1e-10f ? 1e-10f : d;
-                    k2 = -__builtin_amdgcn_logf(u01(rr[e])) * ((d * d) * d);      // v_log_f32 (log2): a common factor ln 2 does not change the race
+                    // v_log_f32 (log2): a common factor ln 2 does not change the race.  |log2 u| and not -log2 u: u01 can return exactly 1.0f, and
+                    // -log2(1) d^3 = -0.0f has the sign bit set - as a word it would order ABOVE every key in the selection below, so the
+                    // candidate that wins with certainty could never be drawn (and with nsamp = all candidates a slot stayed unwritten)
+                    k2 = fabsf(__builtin_amdgcn_logf(u01(rr[e]))) * ((d * d) * d);
                 }
                 key[r] = __float_as_uint(k2);
             }
@@ -215,6 +218,9 @@ __global__ __launch_bounds__(256) void k_knn_sample(const float4 *__restrict__ c
 hipError_t launch_knn_sample(const float4 *ca4, int B, int N, int knn, int nsamp, uint64_t seed, uint32_t stream_id,
                              int32_t *edges, const uint32_t *ctl, hipStream_t s)
 {
+    // the widest instantiation holds 4 * 64 * (64 / 4) = 4096 candidates per node: a longer chain would silently lose the rest
+    static_assert(MAX_NODES == 4 * 64 * (64 / 4), "k_knn_sample<64> covers exactly MAX_NODES candidates");
+    if (N > MAX_NODES) return hipErrorInvalidValue;
     const long long nodes = (long long)B * N;
     const dim3 grid((unsigned)((nodes + 3) / 4)), block(256);
     const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
