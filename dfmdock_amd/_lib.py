@@ -46,6 +46,7 @@ EXPORTS = [
     "dfm_pose_consensus", "dfm_consensus_chunk_poses", "dfm_consensus_last_timing",
     "dfm_atoms_create", "dfm_atoms_destroy", "dfm_atoms_info", "dfm_pose_sterics", "dfm_pose_sterics_chunked", "dfm_sterics_last_timing",
     "dfm_sterics_exit_counts",
+    "dfm_surface_create", "dfm_surface_destroy", "dfm_surface_info", "dfm_pose_bsa", "dfm_pose_bsa_chunked", "dfm_bsa_last_timing",
 ]
 
 
@@ -121,6 +122,15 @@ class StericsOutC(C.Structure):
     _fields_ = [("n_clash", I32P), ("n_contact", I32P), ("min_dist", C.POINTER(C.c_double)), ("lig_clash", I32P), ("lig_contact", I32P)]
 
 
+class SurfaceParamsC(C.Structure):
+    _fields_ = [("probe", C.c_float), ("K", C.c_int), ("dirs", F32P), ("chunk_poses", C.c_int)]
+
+
+class BsaOutC(C.Structure):
+    _fields_ = [("lig_buried", I32P), ("rec_buried", I32P), ("lig_points", I32P), ("rec_points", I32P), ("class_points", I32P),
+                ("bsa", C.POINTER(C.c_double))]
+
+
 _lib = None
 
 
@@ -188,6 +198,14 @@ def lib():
     L.dfm_pose_sterics_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(StericsOutC)]
     L.dfm_sterics_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_sterics_exit_counts.argtypes = [C.c_int, C.POINTER(C.c_uint64)]
+    L.dfm_surface_create.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, F32P, F32P, F32P, C.POINTER(SurfaceParamsC)]
+    L.dfm_surface_create.restype = C.c_void_p
+    L.dfm_surface_destroy.argtypes = [C.c_void_p]
+    L.dfm_surface_destroy.restype = None
+    L.dfm_surface_info.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), I32P, I32P, I32P, F32P, I32P, I32P, F32P]
+    L.dfm_pose_bsa.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.POINTER(BsaOutC)]
+    L.dfm_pose_bsa_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(BsaOutC)]
+    L.dfm_bsa_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_trim_cache.argtypes = [C.c_int]
     L.dfm_trim_cache.restype = C.c_longlong
     L.dfm_diffusion_coef.argtypes = [C.POINTER(HParamsC), C.c_int, C.c_double, C.POINTER(C.c_double),

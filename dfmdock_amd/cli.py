@@ -111,6 +111,18 @@ def _add_sterics(p):
                    help="write the kept model's clash / contact counts per ligand residue (implies --clash-screen)")
 
 
+def _add_surface(p):
+    p.add_argument("--bsa", action="store_true",
+                   help="buried solvent-accessible surface area of every trajectory (adds bsa, bsa_rec, bsa_lig in A^2 to the result line and to every model)")
+    p.add_argument("--min-bsa", type=float, default=None, metavar="A",
+                   help="with --top-k: cluster centres that bury less than A A^2 do not become a model (implies --bsa)")
+    p.add_argument("--interface-residues", default=None, metavar="FILE",
+                   help="write the kept model's buried area per residue of both chains (implies --bsa)")
+    p.add_argument("--probe", type=float, default=None, metavar="A", help="with --bsa: probe radius (default 1.4)")
+    p.add_argument("--sphere-points", type=int, default=None, metavar="K",
+                   help="with --bsa: sphere points per atom, a multiple of 64 in 64 .. 256 (default 128)")
+
+
 def _add_common(p):
     p.add_argument("--ckpt", required=True, help="Lightning checkpoint or bare state_dict (torch.save)")
     p.add_argument("--num-steps", type=int, default=40)
@@ -149,6 +161,7 @@ def build_parser():
     _add_native(d)
     _add_consensus(d)
     _add_sterics(d)
+    _add_surface(d)
     _add_common(d)
     r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)")
     r.add_argument("pdb_1", help="receptor PDB")
@@ -163,6 +176,7 @@ def build_parser():
     _add_native(r)
     _add_consensus(r)
     _add_sterics(r)
+    _add_surface(r)
     _add_common(r)
     s = sub.add_parser("sweep", help="sample every complex of a DB5-style directory (inference_mlsb.py run_sampling)")
     s.add_argument("--db5", required=True, help="directory of <id>.pt files (+ optional test.txt with the ids to run)")
@@ -225,6 +239,19 @@ def parse_args(argv=None):
         args.contact_cutoff = 5.0 if args.contact_cutoff is None else args.contact_cutoff
         if not (np.isfinite(args.clash_cutoff) and np.isfinite(args.contact_cutoff) and 0 < args.clash_cutoff <= args.contact_cutoff):
             ap.error("need 0 < --clash-cutoff <= --contact-cutoff, both finite")
+    if args.cmd in ("dock", "refine"):
+        if args.min_bsa is not None or args.interface_residues:
+            args.bsa = True
+        if not args.bsa and (args.probe is not None or args.sphere_points is not None):
+            ap.error("--probe / --sphere-points describe the surface of --bsa: they need it")
+        args.probe = 1.4 if args.probe is None else args.probe
+        args.sphere_points = 128 if args.sphere_points is None else args.sphere_points
+        if not (np.isfinite(args.probe) and args.probe > 0):
+            ap.error("--probe must be finite and > 0")
+        if args.sphere_points < 64 or args.sphere_points > 256 or args.sphere_points % 64:
+            ap.error("--sphere-points must be a multiple of 64 in 64 .. 256")
+        if args.min_bsa is not None and not np.isfinite(args.min_bsa):
+            ap.error("--min-bsa must be finite")
     if args.cmd in ("dock", "refine", "sweep"):
         if args.consensus_top is not None and not args.consensus:
             ap.error("--consensus-top selects the members of the consensus ensemble: it needs --consensus")
@@ -348,6 +375,31 @@ def sterics_outputs(args, model, res, rec, lig, line):
         line.update(clash_residues=os.path.abspath(args.clash_residues))
 
 
+def surface_kwargs(args):
+    """Driver keyword arguments of the surface flags of dock / refine: none without them."""
+    if not args.bsa:
+        return {}
+    return dict(bsa=True, min_bsa=args.min_bsa, probe=args.probe, sphere_points=args.sphere_points)
+
+
+def surface_outputs(args, model, res, rec, lig, line):
+    """The surface part of a dock / refine result: the areas of the line and --interface-residues."""
+    if not args.bsa:
+        return
+    line.update(bsa=res["bsa"], bsa_rec=res["bsa_rec"], bsa_lig=res["bsa_lig"], probe=res["probe"], sphere_points=res["sphere_points"],
+                index=res["index"])
+    if args.min_bsa is not None:
+        line.update(min_bsa=args.min_bsa)
+        if "bsa_dropped" in res:
+            line.update(bsa_dropped=res["bsa_dropped"])
+    if args.interface_residues:
+        from . import driver
+        from .surface import write_interface_residues
+        keys, area = driver.residue_surface(model, rec, lig, res["rot_update"], res["tr_update"], args.probe, args.sphere_points)
+        write_interface_residues(args.interface_residues, keys, area)
+        line.update(interface_residues=os.path.abspath(args.interface_residues))
+
+
 def consensus_table(rows):
     """Per complex the trajectory consensus ranking keeps (highest consensus, ties: lower energy, lower index; no contact anywhere: the
     minimum energy) with its DockQ, and the success rates of that choice at the CAPRI thresholds."""
@@ -455,6 +507,7 @@ def cmd_dock(args):
         kw.update(native=load_native(args.native))
     kw.update(consensus_kwargs(args))
     kw.update(sterics_kwargs(args))
+    kw.update(surface_kwargs(args))
     res = driver.dock_pair(model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                            precision=args.precision, out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
                            on_selfcheck_fail=args.on_selfcheck_fail, **kw)
@@ -473,6 +526,7 @@ def cmd_dock(args):
         line.update(metrics=res["metrics"])
     consensus_outputs(args, res, rec, lig, line)
     sterics_outputs(args, model, res, rec, lig, line)
+    surface_outputs(args, model, res, rec, lig, line)
     print(json.dumps(line), flush=True)
     if args.json:
         extra = {}
@@ -495,6 +549,7 @@ def cmd_refine(args):
         kw.update(native=load_native(args.native))
     kw.update(consensus_kwargs(args))
     kw.update(sterics_kwargs(args))
+    kw.update(surface_kwargs(args))
     res = driver.refine_pair(model, rec, lig, rec_x, lig_x, t_begin=args.t_begin, num_samples=args.num_samples, num_steps=args.num_steps,
                              seed=args.seed, precision=args.precision, out_pdb=args.out, max_batch=args.max_batch,
                              selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, perturb=not args.no_perturb, **kw)
@@ -506,6 +561,7 @@ def cmd_refine(args):
         line.update(metrics=res["metrics"], start_metrics=res["start_metrics"])
     consensus_outputs(args, res, rec, lig, line)
     sterics_outputs(args, model, res, rec, lig, line)
+    surface_outputs(args, model, res, rec, lig, line)
     print(json.dumps(line), flush=True)
     if args.json:
         with open(args.json, "w") as f:

@@ -1656,6 +1656,368 @@ extern "C" int dfm_sterics_exit_counts(int enable, uint64_t *counts_or_null)
     return DFM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Buried surface area (kernels_surface.hip).  A dfm_surface holds what the two atom sets, their radii, the probe, the sphere points and
+// the rotation centre fix - the receptor's cell grid, the ligand in blocks of 64 neighbours, every atom's isolated exposure mask - and is
+// read-only after creation; every dfm_pose_bsa call owns its stream and temporaries.
+constexpr size_t SURFACE_CHUNK_BYTES = (size_t)64 << 20;      // receptor masks and per-atom output of one chunk of a call
+static thread_local double g_bsa_ms[2] = {0.0, 0.0};          // host-to-device copies, kernels of this thread's last dfm_pose_bsa
+
+struct dfm_surface {
+    int device = 0, Ar = 0, Al = 0, K = 0, n_classes = 0, n_cells = 0, max_cell_atoms = 0, chunk_poses = 0;
+    float probe = 0.f, cell_edge = 0.f, class_radius[16] = {};
+    double sasa[2] = {0.0, 0.0};
+    std::vector<int32_t> exposed[2];      // exposed points per atom, caller's order: receptor, ligand
+    DevPool pool;
+    float *rec = nullptr, *lig = nullptr, *sphere = nullptr, *dirs = nullptr;
+    int32_t *cell_start = nullptr, *rec_index = nullptr, *lig_index = nullptr, *rec_class = nullptr, *lig_class = nullptr;
+    uint64_t *rec_exp = nullptr, *lig_exp = nullptr;
+    SurfaceConst sc = {};
+};
+
+extern "C" void dfm_surface_destroy(dfm_surface *s)
+{
+    if (!s) return;
+    DeviceScope ds(s->device);
+    s->pool.release();
+    delete s;
+}
+
+// the atoms of one chain sorted by cell of a grid of the given edge over their bounding box (a stable counting sort): lo / hi / dims,
+// start [cells + 1], order [n] = atom indices by cell.  false: more than 2^24 cells
+struct SurfaceGrid {
+    double lo[3], hi[3];
+    int dims[3], max_cell = 0;
+    std::vector<int32_t> start, order;
+};
+static bool surface_grid(int n, const float *xyz, double edge, SurfaceGrid &g)
+{
+    for (int k = 0; k < 3; ++k) g.lo[k] = g.hi[k] = (double)xyz[k];
+    for (int i = 1; i < n; ++i)
+        for (int k = 0; k < 3; ++k) {
+            const double v = (double)xyz[(size_t)i * 3 + k];
+            g.lo[k] = std::min(g.lo[k], v);
+            g.hi[k] = std::max(g.hi[k], v);
+        }
+    double cells = 1.0;
+    for (int k = 0; k < 3; ++k) {
+        const double d = std::floor((g.hi[k] - g.lo[k]) / edge) + 1.0;
+        cells *= d;
+        if (!(cells <= (double)STERICS_MAX_CELLS)) return false;
+        g.dims[k] = (int)d;
+    }
+    const int n_cells = g.dims[0] * g.dims[1] * g.dims[2];
+    auto cell1 = [&](double x, int k) {
+        double c = std::floor((x - g.lo[k]) / edge);
+        c = c < 0.0 ? 0.0 : (c > (double)(g.dims[k] - 1) ? (double)(g.dims[k] - 1) : c);
+        return (int)c;
+    };
+    std::vector<int32_t> cell((size_t)n);
+    g.start.assign((size_t)n_cells + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        const float *x = xyz + (size_t)i * 3;
+        cell[(size_t)i] = (cell1((double)x[2], 2) * g.dims[1] + cell1((double)x[1], 1)) * g.dims[0] + cell1((double)x[0], 0);
+        ++g.start[(size_t)cell[(size_t)i] + 1];
+    }
+    g.max_cell = 0;
+    for (int c = 0; c < n_cells; ++c) {
+        g.max_cell = std::max(g.max_cell, (int)g.start[(size_t)c + 1]);
+        g.start[(size_t)c + 1] += g.start[(size_t)c];
+    }
+    g.order.resize((size_t)n);
+    std::vector<int32_t> at(g.start.begin(), g.start.end() - 1);
+    for (int i = 0; i < n; ++i) g.order[(size_t)at[(size_t)cell[(size_t)i]]++] = i;
+    return true;
+}
+
+extern "C" dfm_surface *dfm_surface_create(dfm_model *m, int Ar, const float *rec_atoms, const float *rec_radius, int Al,
+                                           const float *lig_atoms, const float *lig_radius, const float center[3],
+                                           const dfm_surface_params *p_or_null)
+{
+    auto bad = [](int code, const std::string &msg) -> dfm_surface * { (void)fail(code, msg); return nullptr; };
+    if (!m) return bad(DFM_E_INVALID, "m is NULL");
+    if (!rec_atoms) return bad(DFM_E_INVALID, "rec_atoms is NULL");
+    if (!rec_radius) return bad(DFM_E_INVALID, "rec_radius is NULL");
+    if (!lig_atoms) return bad(DFM_E_INVALID, "lig_atoms is NULL");
+    if (!lig_radius) return bad(DFM_E_INVALID, "lig_radius is NULL");
+    if (!center) return bad(DFM_E_INVALID, "center is NULL");
+    if (Ar < 1 || Al < 1) return bad(DFM_E_INVALID, "need Ar >= 1 and Al >= 1");
+    if (Ar > STERICS_MAX_ATOMS || Al > STERICS_MAX_ATOMS) return bad(DFM_E_INVALID, "Ar or Al exceeds 2^24 atoms");
+    dfm_surface_params prm = {1.4f, 128, nullptr, 0};
+    if (p_or_null) prm = *p_or_null;
+    if (!std::isfinite(prm.probe) || !(prm.probe > 0.f)) return bad(DFM_E_INVALID, "probe must be finite and > 0");
+    if (prm.K < 64 || prm.K > 256 || prm.K % 64) return bad(DFM_E_INVALID, "K must be a multiple of 64 in 64 .. 256");
+    if (prm.chunk_poses < 0) return bad(DFM_E_INVALID, "chunk_poses must be >= 0");
+    const int K = prm.K, G = K / 64;
+    std::vector<float> dirs((size_t)K * 3);
+    for (int k = 0; k < K; ++k) {
+        if (prm.dirs) {
+            for (int c = 0; c < 3; ++c) dirs[(size_t)k * 3 + c] = prm.dirs[(size_t)k * 3 + c];
+        } else {
+            const double z = 1.0 - (2.0 * k + 1.0) / K, r = std::sqrt(1.0 - z * z), phi = k * (M_PI * (3.0 - std::sqrt(5.0)));
+            dirs[(size_t)k * 3] = (float)(r * std::cos(phi)); dirs[(size_t)k * 3 + 1] = (float)(r * std::sin(phi)); dirs[(size_t)k * 3 + 2] = (float)z;
+        }
+    }
+    for (float v : dirs)
+        if (!std::isfinite(v)) return bad(DFM_E_INVALID, "dirs is not finite");
+    for (size_t i = 0; i < (size_t)Ar * 3; ++i)
+        if (!std::isfinite(rec_atoms[i])) return bad(DFM_E_INVALID, "rec_atoms: atom " + std::to_string(i / 3) + " is not finite");
+    for (size_t i = 0; i < (size_t)Al * 3; ++i)
+        if (!std::isfinite(lig_atoms[i])) return bad(DFM_E_INVALID, "lig_atoms: atom " + std::to_string(i / 3) + " is not finite");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(center[k])) return bad(DFM_E_INVALID, "center is not finite");
+    // the radius classes: the distinct fp32 values of both chains in ascending order (positive floats order like their bit patterns)
+    std::vector<float> values;
+    for (int side = 0; side < 2; ++side) {
+        const float *rad = side ? lig_radius : rec_radius;
+        for (int i = 0; i < (side ? Al : Ar); ++i) {
+            if (!std::isfinite(rad[i]) || !(rad[i] > 0.f))
+                return bad(DFM_E_INVALID, std::string(side ? "lig_radius" : "rec_radius") + ": atom " + std::to_string(i) + " is not finite and > 0");
+            if (std::find(values.begin(), values.end(), rad[i]) == values.end()) {
+                if (values.size() == 16) return bad(DFM_E_INVALID, "more than 16 radius classes");
+                values.push_back(rad[i]);
+            }
+        }
+    }
+    std::sort(values.begin(), values.end());
+    auto class_of = [&](float v) { return (int32_t)(std::lower_bound(values.begin(), values.end(), v) - values.begin()); };
+    const double probe = (double)prm.probe, Rmax = (double)values.back() + probe;
+    // one grid edge for the receptor's device grid and both host exposure grids: at least 2 Rmax, grown as kernels_sterics.hip grows
+    // its cutoff - by the factor 1.0001 and slack = max(1e-3, 2.5e-7 maxabs) - which is also the fp32 pair test's allowance
+    double maxabs = 0.0;
+    for (size_t i = 0; i < (size_t)Ar * 3; ++i) maxabs = std::max(maxabs, std::fabs((double)rec_atoms[i]));
+    for (size_t i = 0; i < (size_t)Al * 3; ++i) maxabs = std::max(maxabs, std::fabs((double)lig_atoms[i]));
+    maxabs += 4.0 * Rmax + 1.0;
+    const float slack = std::max(1e-3f, (float)(2.5e-7 * maxabs)), thr = (float)(2.0 * Rmax) * 1.0001f + slack;
+    if (!std::isfinite(thr)) return bad(DFM_E_INVALID, "radii and probe must be finite and > 0");
+    const double edge = (double)thr, pad = 1e-6 + 1e-12 * maxabs;
+    SurfaceGrid gr, gl;
+    if (!surface_grid(Ar, rec_atoms, edge, gr)) return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells");
+    if (!surface_grid(Al, lig_atoms, edge, gl)) return bad(DFM_E_INVALID, "the ligand's bounding box needs more than 2^24 cells");
+    std::vector<uint64_t> rexp((size_t)Ar * G), lexp((size_t)Al * G);
+    surface_exposure(Ar, rec_atoms, rec_radius, probe, K, dirs.data(), gr.lo, gr.dims, edge, pad, gr.start.data(), gr.order.data(), rexp.data());
+    surface_exposure(Al, lig_atoms, lig_radius, probe, K, dirs.data(), gl.lo, gl.dims, edge, pad, gl.start.data(), gl.order.data(), lexp.data());
+    dfm_surface *sf = new dfm_surface;
+    sf->device = m->device; sf->Ar = Ar; sf->Al = Al; sf->K = K; sf->probe = prm.probe; sf->chunk_poses = prm.chunk_poses;
+    sf->n_classes = (int)values.size();
+    for (size_t c = 0; c < values.size(); ++c) sf->class_radius[c] = values[c];
+    sf->n_cells = gr.dims[0] * gr.dims[1] * gr.dims[2]; sf->max_cell_atoms = gr.max_cell; sf->cell_edge = thr;
+    // exposed points per atom and the isolated SASA: class sums in ascending order, left to right
+    for (int side = 0; side < 2; ++side) {
+        const int n = side ? Al : Ar;
+        const float *rad = side ? lig_radius : rec_radius;
+        const std::vector<uint64_t> &ex = side ? lexp : rexp;
+        int64_t per_class[16] = {};
+        sf->exposed[side].resize((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            int c = 0;
+            for (int g = 0; g < G; ++g) c += __builtin_popcountll(ex[(size_t)i * G + g]);
+            sf->exposed[side][(size_t)i] = c;
+            per_class[class_of(rad[i])] += c;
+        }
+        double s = 0.0;
+        for (size_t c = 0; c < values.size(); ++c) {
+            const double R = (double)values[c] + probe;
+            s = s + (double)per_class[c] * (4.0 * M_PI * R * R / K);
+        }
+        sf->sasa[side] = s;
+    }
+    SurfaceConst sc = {};
+    for (int k = 0; k < 3; ++k) { sc.lo[k] = gr.lo[k]; sc.hi[k] = gr.hi[k]; sc.center[k] = (double)center[k]; }
+    sc.edge = edge; sc.grow = edge; sc.probe = probe; sc.slack = slack;
+    sc.nx = gr.dims[0]; sc.ny = gr.dims[1]; sc.nz = gr.dims[2]; sc.G = G;
+    sf->sc = sc;
+    // the receptor in cell order
+    std::vector<float> rec4((size_t)Ar * 4);
+    std::vector<int32_t> rec_class((size_t)Ar);
+    std::vector<uint64_t> rexp_s((size_t)Ar * G);
+    for (int q = 0; q < Ar; ++q) {
+        const int32_t src = gr.order[(size_t)q];
+        for (int k = 0; k < 3; ++k) rec4[(size_t)q * 4 + k] = rec_atoms[(size_t)src * 3 + k];
+        rec4[(size_t)q * 4 + 3] = rec_radius[src];
+        rec_class[(size_t)q] = class_of(rec_radius[src]);
+        for (int g = 0; g < G; ++g) rexp_s[(size_t)q * G + g] = rexp[(size_t)src * G + g];
+    }
+    // the ligand in Morton order of its own cells (ties: the caller's order), and a bounding sphere per block of 64 (dfm_atoms_create)
+    std::vector<std::pair<uint64_t, int32_t>> order((size_t)Al);
+    for (int i = 0; i < Al; ++i) {
+        uint32_t c[3];
+        for (int k = 0; k < 3; ++k) {
+            const double v = std::floor(((double)lig_atoms[(size_t)i * 3 + k] - gl.lo[k]) / edge);
+            c[k] = (uint32_t)(v < 0.0 ? 0.0 : (v > 2097151.0 ? 2097151.0 : v));
+        }
+        order[(size_t)i] = {morton3(c[0], c[1], c[2]), i};
+    }
+    std::sort(order.begin(), order.end());
+    const int nblk = (Al + 63) / 64;
+    std::vector<float> lig4((size_t)Al * 4), sph((size_t)nblk * 4, 0.f);
+    std::vector<int32_t> lig_index((size_t)Al), lig_class((size_t)Al);
+    std::vector<uint64_t> lexp_s((size_t)Al * G);
+    for (int q = 0; q < Al; ++q) {
+        const int32_t src = order[(size_t)q].second;
+        lig_index[(size_t)q] = src;
+        for (int k = 0; k < 3; ++k) lig4[(size_t)q * 4 + k] = lig_atoms[(size_t)src * 3 + k];
+        lig4[(size_t)q * 4 + 3] = lig_radius[src];
+        lig_class[(size_t)q] = class_of(lig_radius[src]);
+        for (int g = 0; g < G; ++g) lexp_s[(size_t)q * G + g] = lexp[(size_t)src * G + g];
+    }
+    for (int b = 0; b < nblk; ++b) {
+        const int i0 = b * 64, i1 = std::min(Al, i0 + 64);
+        double lo[3], hi[3];
+        for (int k = 0; k < 3; ++k) lo[k] = hi[k] = (double)lig4[(size_t)i0 * 4 + k];
+        for (int i = i0 + 1; i < i1; ++i)
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = std::min(lo[k], (double)lig4[(size_t)i * 4 + k]);
+                hi[k] = std::max(hi[k], (double)lig4[(size_t)i * 4 + k]);
+            }
+        // the centre as the fp32 the kernel reads, the radius measured from THAT point and rounded up
+        float c[3];
+        for (int k = 0; k < 3; ++k) c[k] = (float)(0.5 * (lo[k] + hi[k]) - sc.center[k]);
+        double r2 = 0.0;
+        for (int i = i0; i < i1; ++i) {
+            double d2 = 0.0;
+            for (int k = 0; k < 3; ++k) {
+                const double d = ((double)lig4[(size_t)i * 4 + k] - sc.center[k]) - (double)c[k];
+                d2 += d * d;
+            }
+            r2 = std::max(r2, d2);
+        }
+        for (int k = 0; k < 3; ++k) sph[(size_t)b * 4 + k] = c[k];
+        sph[(size_t)b * 4 + 3] = std::nextafter((float)(std::sqrt(r2) * (1.0 + 1e-6) + 1e-6), INFINITY);
+    }
+    for (size_t i = 0; i < sph.size(); ++i)
+        if (!std::isfinite(sph[i])) { delete sf; return bad(DFM_E_INVALID, "lig_atoms / center: the ligand's extent about the centre overflows fp32"); }
+    DeviceScope ds(m->device);
+    if (ds.err != hipSuccess) { delete sf; return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err)); }
+    hipError_t e = hipSuccess;
+    {
+        PoseCall c;
+        e = c.open();
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->rec, rec4.data(), rec4.size(), c.s);
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->cell_start, gr.start.data(), gr.start.size(), c.s);
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->rec_index, gr.order.data(), gr.order.size(), c.s);
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->rec_class, rec_class.data(), rec_class.size(), c.s);
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->rec_exp, rexp_s.data(), rexp_s.size(), c.s);
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig, lig4.data(), lig4.size(), c.s);
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->sphere, sph.data(), sph.size(), c.s);
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig_index, lig_index.data(), lig_index.size(), c.s);
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig_class, lig_class.data(), lig_class.size(), c.s);
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig_exp, lexp_s.data(), lexp_s.size(), c.s);
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->dirs, dirs.data(), dirs.size(), c.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
+    }      // the call's stream has drained: the host vectors it read may go
+    if (e != hipSuccess) {
+        sf->pool.release();
+        delete sf;
+        return bad(e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP, std::string("dfm_surface_create: ") + hipGetErrorString(e));
+    }
+    return sf;
+}
+
+extern "C" int dfm_surface_info(const dfm_surface *s, double *sasa_rec, double *sasa_lig, int32_t *rec_exposed, int32_t *lig_exposed,
+                                int32_t *n_classes, float *class_radius, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge)
+{
+    if (!s) return fail(DFM_E_INVALID, "NULL argument");
+    if (sasa_rec) *sasa_rec = s->sasa[0];
+    if (sasa_lig) *sasa_lig = s->sasa[1];
+    if (rec_exposed) std::memcpy(rec_exposed, s->exposed[0].data(), (size_t)s->Ar * sizeof(int32_t));
+    if (lig_exposed) std::memcpy(lig_exposed, s->exposed[1].data(), (size_t)s->Al * sizeof(int32_t));
+    if (n_classes) *n_classes = s->n_classes;
+    if (class_radius) std::memcpy(class_radius, s->class_radius, sizeof(s->class_radius));
+    if (n_cells) *n_cells = s->n_cells;
+    if (max_cell_atoms) *max_cell_atoms = s->max_cell_atoms;
+    if (cell_edge) *cell_edge = s->cell_edge;
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_bsa_chunked(dfm_surface *sf, int P, const float *rot, const float *tr, int chunk_poses, dfm_bsa_out *out)
+{
+    if (!sf) return fail(DFM_E_INVALID, "s is NULL");
+    if (!rot) return fail(DFM_E_INVALID, "rot is NULL");
+    if (!tr) return fail(DFM_E_INVALID, "tr is NULL");
+    if (!out) return fail(DFM_E_INVALID, "out is NULL");
+    if (P < 1) return fail(DFM_E_INVALID, "need P >= 1");
+    if (chunk_poses < 0) return fail(DFM_E_INVALID, "chunk_poses must be >= 0");
+    DEVICE_SCOPE(sf->device);
+    PoseCall c;
+    HIPCHK(c.open());
+    const size_t Ar = (size_t)sf->Ar, Al = (size_t)sf->Al, G = (size_t)sf->sc.G;
+    // the call's chunk, else the creator's, else as many poses as fill SURFACE_CHUNK_BYTES of masks and per-atom output
+    const size_t per_pose = Ar * G * sizeof(uint64_t) + (out->lig_buried ? Al * sizeof(int32_t) : 0) + (out->rec_buried ? Ar * sizeof(int32_t) : 0);
+    const int want = chunk_poses > 0 ? chunk_poses : sf->chunk_poses;
+    const int fill = (int)std::min<size_t>(STERICS_MAX_CHUNK, std::max<size_t>(1, SURFACE_CHUNK_BYTES / per_pose));
+    const int Pc = std::min(P, want > 0 ? std::min(want, STERICS_MAX_CHUNK) : fill);
+    float *d_rot = nullptr, *d_tr = nullptr;
+    double *T = nullptr;
+    int32_t *d_cls = nullptr, *d_lb = nullptr, *d_rb = nullptr;
+    uint64_t *d_mask = nullptr;
+    HIPCHK(c.tmp.alloc(&d_rot, (size_t)Pc * 3));
+    HIPCHK(c.tmp.alloc(&d_tr, (size_t)Pc * 3));
+    HIPCHK(c.tmp.alloc(&T, (size_t)Pc * 12));
+    HIPCHK(c.tmp.alloc(&d_cls, (size_t)Pc * 32));
+    HIPCHK(c.tmp.alloc(&d_mask, (size_t)Pc * Ar * G));
+    if (out->lig_buried) HIPCHK(c.tmp.alloc(&d_lb, (size_t)Pc * Al));
+    if (out->rec_buried) HIPCHK(c.tmp.alloc(&d_rb, (size_t)Pc * Ar));
+    const SurfaceAtoms at = {sf->rec, sf->lig, sf->sphere, sf->dirs, sf->cell_start, sf->rec_index, sf->lig_index, sf->rec_class, sf->lig_class,
+                             sf->rec_exp, sf->lig_exp, sf->sc, sf->Ar, sf->Al};
+    std::vector<int32_t> h_cls((size_t)Pc * 32);
+    double area[16] = {};
+    for (int k = 0; k < sf->n_classes; ++k) {
+        const double R = (double)sf->class_radius[k] + (double)sf->probe;
+        area[k] = 4.0 * M_PI * R * R / sf->K;
+    }
+    double copy_ms = 0.0, kernel_ms = 0.0;
+    for (int p0 = 0; p0 < P; p0 += Pc) {
+        const int n = std::min(Pc, P - p0);
+        HIPCHK(hipEventRecord(c.ev[0], c.s));
+        HIPCHK(hipMemcpyAsync(d_rot, rot + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s));
+        HIPCHK(hipMemcpyAsync(d_tr, tr + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s));
+        HIPCHK(hipEventRecord(c.ev[1], c.s));
+        HIPCHK(hipMemsetAsync(d_mask, 0, (size_t)n * Ar * G * sizeof(uint64_t), c.s));
+        if (d_lb) HIPCHK(hipMemsetAsync(d_lb, 0, (size_t)n * Al * sizeof(int32_t), c.s));
+        HIPCHK(launch_surface_pose(d_rot, d_tr, n, T, d_cls, c.s));
+        HIPCHK(launch_surface(at, T, n, d_mask, d_lb, d_rb, d_cls, c.s));
+        HIPCHK(hipEventRecord(c.ev[2], c.s));
+        HIPCHK(hipMemcpyAsync(h_cls.data(), d_cls, (size_t)n * 32 * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        if (d_lb) HIPCHK(hipMemcpyAsync(out->lig_buried + (size_t)p0 * Al, d_lb, (size_t)n * Al * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        if (d_rb) HIPCHK(hipMemcpyAsync(out->rec_buried + (size_t)p0 * Ar, d_rb, (size_t)n * Ar * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(hipStreamSynchronize(c.s));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) copy_ms += ms;
+        if (hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess) kernel_ms += ms;
+        for (int p = 0; p < n; ++p) {
+            const int32_t *cp = h_cls.data() + (size_t)p * 32;
+            int32_t side[2] = {0, 0};
+            double s = 0.0;
+            for (int ch = 0; ch < 2; ++ch)
+                for (int k = 0; k < sf->n_classes; ++k) {
+                    side[ch] += cp[ch * 16 + k];
+                    s = s + (double)cp[ch * 16 + k] * area[k];
+                }
+            if (out->rec_points) out->rec_points[p0 + p] = side[0];
+            if (out->lig_points) out->lig_points[p0 + p] = side[1];
+            if (out->class_points) std::memcpy(out->class_points + (size_t)(p0 + p) * 32, cp, 32 * sizeof(int32_t));
+            if (out->bsa) out->bsa[p0 + p] = s;
+        }
+    }
+    g_bsa_ms[0] = copy_ms;
+    g_bsa_ms[1] = kernel_ms;
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_bsa(dfm_surface *s, int P, const float *rot, const float *tr, dfm_bsa_out *out)
+{
+    return dfm_pose_bsa_chunked(s, P, rot, tr, 0, out);
+}
+
+extern "C" int dfm_bsa_last_timing(double *copy_ms, double *kernel_ms)
+{
+    if (!copy_ms || !kernel_ms) return fail(DFM_E_INVALID, "NULL argument");
+    *copy_ms = g_bsa_ms[0];
+    *kernel_ms = g_bsa_ms[1];
+    return DFM_OK;
+}
+
 extern "C" int dfm_complex_degree(const dfm_complex *cx) { return cx ? cx->K : -1; }
 
 extern "C" long long dfm_trim_cache(int device)

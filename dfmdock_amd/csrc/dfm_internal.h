@@ -444,4 +444,34 @@ hipError_t launch_sterics_pose(const float *rot, const float *tr, int n, double 
 hipError_t launch_sterics(const StericsAtoms &at, const double *T, int n, int32_t *n_clash, int32_t *n_contact, uint64_t *min_bits,
                           int32_t *lig_clash, int32_t *lig_contact, uint64_t *exits, hipStream_t s);
 
+// buried surface area (kernels_surface.hip; include/dfmdock_amd.h: dfm_surface_create / dfm_pose_bsa).  What the atoms alone fix: the
+// receptor's bounding box lo / hi (= the grid's origin and extent), the grid of nx x ny x nz cells of edge `edge` (at least the largest
+// R_a + R_b), the rotation centre, the probe widened to double, `slack` of the fp32 pair test d2 > ((R_a + R_b) 1.0001 + slack)^2 and
+// `grow` = that threshold for the largest radii as a double, by which every box test is widened; G = K / 64 groups of sphere points.
+struct SurfaceConst {
+    double lo[3], hi[3], center[3];
+    double edge, grow, probe;
+    float slack;
+    int nx, ny, nz, G;
+};
+// device arrays of a dfm_surface: rec [Ar] float4 sorted by cell (w = radius), cell_start [nx ny nz + 1], lig [Al] float4 in Morton order
+// of the ligand's own cells (w = radius), sphere [ceil(Al / 64)] float4 as in StericsAtoms; per sorted atom its index in the caller's
+// order, its radius class and its exposure mask [G] (bit l of word g = point 64 g + l is exposed in isolation); dirs [K][3]
+struct SurfaceAtoms {
+    const float *rec, *lig, *sphere, *dirs;
+    const int32_t *cell_start, *rec_index, *lig_index, *rec_class, *lig_class;
+    const uint64_t *rec_exp, *lig_exp;
+    SurfaceConst sc;
+    int Ar, Al;
+};
+// T [n][12]: R(rot) row-major and tr as doubles; also zeroes class_points [n][2][16]
+hipError_t launch_surface_pose(const float *rot, const float *tr, int n, double *T, int32_t *class_points, hipStream_t s);
+// n <= 65535 poses.  rec_bur [n][Ar][G]: zero it first.  lig_buried [n][Al] / rec_buried [n][Ar] (caller's atom order) or nullptr;
+// lig_buried is written by the waves that reach the cell walk only, so zero it first.  class_points [n][2][16] is added to.
+hipError_t launch_surface(const SurfaceAtoms &at, const double *T, int n, uint64_t *rec_bur, int32_t *lig_buried, int32_t *rec_buried,
+                          int32_t *class_points, hipStream_t s);
+// isolated exposure of one chain on the host, as the definition takes it (kernels_surface.hip)
+void surface_exposure(int n, const float *xyz, const float *radius, double probe, int K, const float *dirs, const double lo[3],
+                      const int dims[3], double edge, double pad, const int32_t *start, const int32_t *order, uint64_t *mask);
+
 }  // namespace dfm

@@ -113,6 +113,64 @@ def residue_sterics(model: engine.Model, rec, lig, rot, tr, clash_cutoff=3.0, co
     return keys, ST.residue_counts(sd["lig_clash"][0], res, len(keys)), ST.residue_counts(sd["lig_contact"][0], res, len(keys))
 
 
+def surface_inputs(rec, lig, family):
+    """What the buried-surface call takes from two pdbio.backbone_from_atoms dicts: sterics_inputs plus the van der Waals radius of every
+    heavy atom (surface.element_radius, float32 [n])."""
+    from . import sterics as ST
+    from . import surface as SF
+    ra, la, cen = sterics_inputs(rec, lig, family)
+    return ra, SF.atom_radii(rec["atoms"], ST.heavy_atoms(rec["atoms"])), la, SF.atom_radii(lig["atoms"], ST.heavy_atoms(lig["atoms"])), cen
+
+
+def ensemble_surface(model: engine.Model, rec, lig, rot_update, tr_update, probe=1.4, sphere_points=128, per_atom=False):
+    """Buried solvent-accessible surface area of trajectories on the GPU (dfm_pose_bsa) from their final (rot_update, tr_update) alone:
+    the heavy atoms of the two parsed PDB chains with their element radii, the ligand moved as pdbio.apply_pose_all_atom moves it.
+    Returns the dict of Surface.bsa plus probe, sphere_points and the two radius arrays."""
+    ra, rr, la, lr, cen = surface_inputs(rec, lig, model.hp.family)
+    with model.surface(ra, rr, la, lr, cen, probe, sphere_points) as sf:
+        out = sf.bsa(np.asarray(rot_update, np.float32).reshape(-1, 3), np.asarray(tr_update, np.float32).reshape(-1, 3), per_atom=per_atom)
+        out.update(probe=sf.probe, sphere_points=sf.K, rec_radius=rr, lig_radius=lr)
+    return out
+
+
+def residue_surface(model: engine.Model, rec, lig, rot, tr, probe=1.4, sphere_points=128):
+    """Per residue of ONE pose: ((receptor keys, ligand keys), (receptor areas, ligand areas)) - the buried points of each residue's heavy
+    atoms as areas in A^2 (surface.residue_bsa)."""
+    from . import sterics as ST
+    from . import surface as SF
+    bd = ensemble_surface(model, rec, lig, np.asarray(rot).reshape(1, 3), np.asarray(tr).reshape(1, 3), probe, sphere_points, per_atom=True)
+    keys, area = [], []
+    for chain, buried, radius in ((rec, bd["rec_buried"][0], bd["rec_radius"]), (lig, bd["lig_buried"][0], bd["lig_radius"])):
+        k, res = ST.residue_of_atoms(chain["atoms"], ST.heavy_atoms(chain["atoms"]))
+        keys.append(k)
+        area.append(SF.residue_bsa(buried, radius, res, len(k), bd["probe"], bd["sphere_points"]))
+    return keys, area
+
+
+def _check_surface(bsa, min_bsa, probe, sphere_points):
+    """None (off) or (min_bsa or None, probe, sphere points) of a pair driver's surface options; min_bsa implies bsa."""
+    if not bsa and min_bsa is None:
+        return None
+    from . import surface as SF
+    if min_bsa is not None and not np.isfinite(min_bsa):
+        raise ValueError(f"min_bsa must be finite, got {min_bsa}")
+    return (None if min_bsa is None else float(min_bsa)), SF.check_probe(probe), SF.check_points(sphere_points)
+
+
+def _pose_bsa(bd, k):
+    return {"bsa": float(bd["bsa"][k]), "bsa_rec": float(bd["bsa_rec"][k]), "bsa_lig": float(bd["bsa_lig"][k])}
+
+
+def _surface_result(bd, k, opts):
+    """The surface entries of a pair driver's result for the kept pose k: none without the option."""
+    if bd is None:
+        return {}
+    out = dict(_pose_bsa(bd, k), bsa_data=bd, probe=bd["probe"], sphere_points=bd["sphere_points"], index=int(k))
+    if opts[0] is not None:
+        out["min_bsa"] = opts[0]
+    return out
+
+
 def _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff):
     """None (off) or (filter, clash cutoff, contact cutoff) of a pair driver's screen options."""
     if not (clash_screen or clash_filter):
@@ -595,11 +653,12 @@ def _center(model):
     return "all_atoms" if model.hp.family == 1 else "ca"
 
 
-def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native=None, cons=None, ster=None, clu=None, refine=None):
+def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native=None, cons=None, ster=None, clu=None, refine=None,
+            surf=None):
     """What every pair driver does with its sampled trajectories: the kept pose, its files and the result.  cols: every trajectory's
     energy, rot_update, tr_update (and the driver's own columns).  pick = (rule, *column names): the driver's own choice, rule(*columns) ->
     index; key: the clustering key that goes with it.  entries(k): the driver's own result entries for the kept pose k.  cons / ster / clu:
-    None or the options of _with_consensus / _screen / _top_models; refine: None or the keyword arguments of refine_models - only then
+    None or the options of _with_consensus / _screen / _top_models; surf: None or the options of _check_surface; refine: None or the keyword arguments of refine_models - only then
     does the handle outlive the sampling."""
     lig0 = gx.lig_pos0
     if refine is None:      # the columns are host arrays: the handle (and its ~GB of device workspace) goes before any post-processing
@@ -609,17 +668,19 @@ def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_p
     k, key, extra = _with_consensus(model, rec, lig0, cols, k, _nan_key(key, bad), cons, bad)
     key = _nan_key(key, bad)      # again: rank "consensus" has replaced the key by consensus.rank_positions
     extra.update(_sterics_result(sd, k))
+    bd = None if surf is None else ensemble_surface(model, rec, lig, cols["rot_update"], cols["tr_update"], surf[1], surf[2])
+    extra.update(_surface_result(bd, k, surf))
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k], center=_center(model))
     if out_pdb:
         pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa, remarks=_remarks(sd, k))
     res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, **entries(k)}
     res.update(extra)
-    if cons is not None or ster is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
+    if cons is not None or ster is not None or surf is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
         res.setdefault("trajectories", {c: cols[c] for c in ("energy", "rot_update", "tr_update")})
     _selected_metrics(model, native, rec, lig0, res)
     if clu is not None:
-        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad))
+        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad, bd, None if surf is None else surf[0]))
         if refine is not None:
             refine_models(model, gx, rec, lig, lig0, cols, res["models"], precision=precision, out_pdb=out_pdb, native=native, **refine)
             gx.close()
@@ -630,7 +691,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
               out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", restraints=None,
               restraint_rank="satisfied", restraint_params=None, top_k=None, cluster_radius=4.0, cluster_rule="energy", refine_t=None,
               refine_samples=8, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
-              clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, **sampler_kw):
+              clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, bsa=False, min_bsa=None, probe=1.4, sphere_points=128, **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
     pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
     the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
@@ -666,10 +727,17 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     of the kept pose, threshold, ensemble_mean, ensemble_std, the cutoffs, filtered, fallback), `sterics_data` (the arrays), `index` and
     `trajectories`; every model of `top_k` gains `sterics`, and every written file a REMARK line with its counts.  `clash_filter` (implies
     the screen): flagged poses are removed before the selection, the consensus ranking and the clustering - they can neither be kept nor
-    become a model; were every pose flagged, nothing is removed and `fallback` is true."""
+    become a model; were every pose flagged, nothing is removed and `fallback` is true.
+
+    `bsa`: the buried solvent-accessible surface area of every trajectory (ensemble_surface: Shrake-Rupley with `sphere_points` points per
+    heavy atom and a probe of `probe` A).  The result gains `bsa`, `bsa_rec`, `bsa_lig` (A^2 of the kept pose: both sides, each side),
+    `bsa_data` (the arrays), `probe`, `sphere_points`, `index` and `trajectories`; every model of `top_k` gains the three areas.  `min_bsa`
+    (implies bsa): cluster centres that bury less than min_bsa A^2 do not become a model of `top_k`; `bsa_dropped` counts them.  It
+    composes with `clash_filter`; the kept pose is not affected."""
     _check_rank(rank, consensus_top)
     cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
     ster = _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff)
+    surf = _check_surface(bsa, min_bsa, probe, sphere_points)
     if native is not None:
         _check_native(native, rec, lig)
     if refine_t is not None and top_k is None:
@@ -710,7 +778,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     cols = {c: np.concatenate(v, 0) for c, v in cols.items()}
     if not restrained:
         # the loop's own minimum; consensus and the screen choose among all trajectories at once (the first minimum: the same pose)
-        pick = (np.argmin if cons is not None or ster is not None else (lambda energy: k0), "energy")
+        pick = (np.argmin if cons is not None or ster is not None or surf is not None else (lambda energy: k0), "energy")
         key, entries = cols["energy"], lambda k: {}
     else:
         from . import restraints as RS
@@ -721,13 +789,14 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         entries = lambda k: {"index": k, "restraints": len(restraints), "restraint_rank": restraint_rank,
                              "restraint_energy": float(cols["restraint_energy"][k]), "restraints_satisfied": int(cols["restraints_satisfied"][k]),
                              "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
-    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine)
+    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine, surf)
 
 
 def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
                 out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", perturb=True, restraints=None,
                 restraint_params=None, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
-                clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, start_shift=None, **sampler_kw):
+                clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, start_shift=None, bsa=False, min_bsa=None, probe=1.4,
+                sphere_points=128, **sampler_kw):
     """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories
     start from that pose noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps
     down from t_begin; like dock_pair the minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns
@@ -735,11 +804,13 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
     ([restraints.RestraintGroup]) turns the restraint step on (DFM_F_RESTRAINTS).  `native` (as for dock_pair): the result gains
     `metrics` of the kept pose and `start_metrics` of the pose the refinement started from.  `consensus` / `rank` / `consensus_top` /
     `consensus_cutoff`: as for dock_pair.  `clash_screen` / `clash_filter` / `clash_cutoff` / `contact_cutoff`: as for dock_pair.
+    `bsa` / `min_bsa` / `probe` / `sphere_points`: as for dock_pair (there are no models here, so min_bsa only turns bsa on).
     `start_shift` ([num_samples,3]): trajectory i starts from the input pose translated by start_shift[i] (the engine's start_pos); the
     shift is added to its tr_update, so (rot_update, tr_update) keep mapping the INPUT pose onto the final one."""
     _check_rank(rank, consensus_top)
     cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
     ster = _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff)
+    surf = _check_surface(bsa, min_bsa, probe, sphere_points)
     if native is not None:
         _check_native(native, rec, lig)
     if start_shift is not None:
@@ -766,7 +837,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
         done += b
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
     res = _finish(model, gx, rec, lig, cols, (np.argmin, "energy"), None,      # the first minimum wins, as in dock_pair
-                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster)
+                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster, surf=surf)
     if native is not None:
         res["start_metrics"] = native_metrics(model, native, rec["bb_coords"], gx.lig_pos0[None])[0]
     return res
@@ -798,21 +869,27 @@ def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps
     return models
 
 
-def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=None, bad=None):
+def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=None, bad=None, bd=None, min_bsa=None):
     """dock_pair's `models`: the centres of up to top_k clusters in cluster order, each written as <out_pdb stem>_<rank>.pdb.  sd: the
     screen's data (every model gains `sterics`, every file a REMARK line); bad: poses the clash filter removed - their key is NaN, so they
-    come last, and a cluster one of them would lead is left out."""
+    come last, and a cluster one of them would lead is left out.  bd: the surface data (every model gains bsa, bsa_rec, bsa_lig); min_bsa:
+    a centre that buries less is left out as well, and `bsa_dropped` counts those."""
     top_k, radius, rule = clu
     cl = cluster_trajectories(model, lig0, cols["rot_update"], cols["tr_update"], key, radius, rule, top_k)
-    models = []
+    models, dropped = [], 0
     for c, n in zip(cl["center"], cl["size"]):
         c = int(c)
         if bad is not None and bad[c]:
+            continue
+        if bd is not None and min_bsa is not None and bd["bsa"][c] < min_bsa:
+            dropped += 1
             continue
         k = len(models)
         models.append({"rank": k + 1, "index": c, "energy": float(cols["energy"][c]), "cluster_size": int(n)})
         if sd is not None:
             models[-1]["sterics"] = _pose_sterics(sd, c)
+        if bd is not None:
+            models[-1].update(_pose_bsa(bd, c))
         if out_pdb:
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c], center=_center(model))
             pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa, remarks=_remarks(sd, c))
@@ -822,7 +899,7 @@ def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=
         poses = rebuild_backbone(lig0, cols["rot_update"][cen], cols["tr_update"][cen], model.hp.family)
         for m, pm in zip(models, native_metrics(model, native, rec["bb_coords"], poses)):
             m["metrics"] = pm
-    return {"models": models, "cluster_of": cl["cluster_of"]}
+    return {"models": models, "cluster_of": cl["cluster_of"], **({"bsa_dropped": dropped} if bd is not None and min_bsa is not None else {})}
 
 
 def model_path(out_pdb, rank):

@@ -211,6 +211,12 @@ class Model:
         `.sterics(rot, tr)` screens P poses in one call."""
         return Atoms(self, rec_atoms, lig_atoms, center, clash_cutoff, contact_cutoff)
 
+    def surface(self, rec_atoms, rec_radius, lig_atoms, lig_radius, center, probe=1.4, points=128):
+        """The heavy atoms of a pair and their van der Waals radii prepared for the buried-surface-area call on the GPU
+        (dfm_surface_create): `points` sphere points per atom (surface.sphere_points), a probe of `probe` A.  Returns a Surface whose
+        `.bsa(rot, tr)` takes P poses in one call."""
+        return Surface(self, rec_atoms, rec_radius, lig_atoms, lig_radius, center, probe, points)
+
 
 class Native:
     """A native pose resident on the model's GPU (dfm_native): interface residues, native contacts and the receptor's share of the
@@ -339,6 +345,88 @@ class Atoms:
         L.check(L.lib().dfm_pose_sterics_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_sterics")
         o["flags"], o["threshold"], o["ensemble_mean"], o["ensemble_std"] = ST.capri_flags(o["n_clash"], members)
         return o
+
+
+class Surface:
+    """The heavy atoms of a receptor / ligand pair with their isolated exposure masks resident on the model's GPU (dfm_surface).
+    Read-only after creation: `bsa` may be called from several threads at once."""
+
+    def __init__(self, model: Model, rec_atoms, rec_radius, lig_atoms, lig_radius, center, probe=1.4, points=128):
+        from . import surface as SF
+        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _f32(center).reshape(-1)
+        rr, lr = _f32(rec_radius).reshape(-1), _f32(lig_radius).reshape(-1)
+        if cen.size != 3:
+            raise ValueError(f"center must have 3 entries, got {np.shape(center)}")
+        if rr.size != ra.shape[0] or lr.size != la.shape[0]:
+            raise ValueError(f"one radius per atom: {ra.shape[0]} / {rr.size} receptor, {la.shape[0]} / {lr.size} ligand")
+        self.model, self.Ar, self.Al = model, ra.shape[0], la.shape[0]
+        self.K, self.probe = SF.check_points(points), float(np.float32(probe))
+        dirs = SF.sphere_points(self.K)
+        prm = L.SurfaceParamsC(float(probe), self.K, _p(dirs), 0)
+        self._h = L.lib().dfm_surface_create(model._h, self.Ar, _p(ra), _p(rr), self.Al, _p(la), _p(lr), _p(cen), C.byref(prm))
+        if not self._h:
+            msg = L.lib().dfm_last_error()
+            L.check(-2 if msg.startswith((b"dfm_surface_create", b"hipSetDevice")) else -1, "dfm_surface_create")      # else: bad argument
+        self.class_radius = self.info()["class_radius"]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().dfm_surface_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{sasa_rec, sasa_lig (A^2 in isolation), rec_exposed [Ar], lig_exposed [Al] (exposed points per atom), class_radius (float32,
+        ascending), n_cells, max_cell_atoms, cell_edge} (dfm_surface_info)."""
+        sr, sl = C.c_double(0), C.c_double(0)
+        re, le = np.zeros(self.Ar, np.int32), np.zeros(self.Al, np.int32)
+        nc, n, mx, e = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_float(0)
+        cr = np.zeros(16, np.float32)
+        L.check(L.lib().dfm_surface_info(self._h, C.byref(sr), C.byref(sl), _p(re, L.I32P), _p(le, L.I32P), C.byref(nc), _p(cr), C.byref(n),
+                                         C.byref(mx), C.byref(e)), "dfm_surface_info")
+        return {"sasa_rec": sr.value, "sasa_lig": sl.value, "rec_exposed": re, "lig_exposed": le, "class_radius": cr[:nc.value].copy(),
+                "n_cells": n.value, "max_cell_atoms": mx.value, "cell_edge": e.value}
+
+    def bsa(self, rot, tr, per_atom=False, chunk_poses=0):
+        """Buried surface of P poses (dfm_pose_bsa; the float64 definition is surface.bsa): rot [P,3] axis-angle and tr [P,3] as
+        rot_update / tr_update hold them.  Returns {bsa (float64 [P], A^2, both sides), lig_points, rec_points (int32 [P]), class_points
+        (int32 [P,2,16])}, with `per_atom` lig_buried [P,Al] / rec_buried [P,Ar] (int32 points, the caller's atom order), and
+        bsa_rec / bsa_lig (float64 [P]): the two sides (surface.side_areas)."""
+        from . import surface as SF
+        r, t = _f32(rot).reshape(-1, 3), _f32(tr).reshape(-1, 3)
+        if r.shape != t.shape or r.shape[0] < 1:
+            raise ValueError(f"rot and tr must both be [P,3] with P >= 1, got {np.shape(rot)} and {np.shape(tr)}")
+        P = r.shape[0]
+        o = {"bsa": np.zeros(P, np.float64), "lig_points": np.zeros(P, np.int32), "rec_points": np.zeros(P, np.int32),
+             "class_points": np.zeros((P, 2, 16), np.int32)}
+        out = L.BsaOutC()
+        out.bsa = o["bsa"].ctypes.data_as(C.POINTER(C.c_double))
+        out.lig_points, out.rec_points, out.class_points = (_p(o[k], L.I32P) for k in ("lig_points", "rec_points", "class_points"))
+        if per_atom:
+            o["lig_buried"], o["rec_buried"] = np.zeros((P, self.Al), np.int32), np.zeros((P, self.Ar), np.int32)
+            out.lig_buried, out.rec_buried = _p(o["lig_buried"], L.I32P), _p(o["rec_buried"], L.I32P)
+        L.check(L.lib().dfm_pose_bsa_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_bsa")
+        o["bsa_rec"], o["bsa_lig"] = SF.side_areas(o["class_points"], self.class_radius, self.probe, self.K)
+        return o
+
+
+def bsa_last_timing():
+    """(host-to-device copy ms, kernel ms) of this thread's last Surface.bsa call (dfm_bsa_last_timing)."""
+    a, b = C.c_double(0), C.c_double(0)
+    L.check(L.lib().dfm_bsa_last_timing(C.byref(a), C.byref(b)), "dfm_bsa_last_timing")
+    return a.value, b.value
 
 
 def sterics_last_timing():

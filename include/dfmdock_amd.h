@@ -463,6 +463,60 @@ int dfm_sterics_last_timing(double *copy_ms, double *kernel_ms);
  * launched (poses x blocks of 64 ligand atoms), those that left at the block's sphere test and those that left at its box test;
  * `enable` != 0 makes this thread's next calls count (one atomic per leaving wave: not for timing) */
 int dfm_sterics_exit_counts(int enable, uint64_t *counts_or_null);
+/* Buried solvent-accessible surface area (Shrake-Rupley) of P rigid poses of one ligand.  dfmdock_amd/surface.py is the float64
+ * definition these calls are tested against.  Atoms, centre and poses as for dfm_atoms_create / dfm_pose_sterics; rec_radius [Ar] and
+ * lig_radius [Al] are van der Waals radii.
+ *   sphere points: dirs [K,3], K a multiple of 64 in 64 .. 256 (default 128).  The definition's table is the golden spiral z_k =
+ *     1 - (2k+1)/K, r_k = sqrt(1 - z_k^2), phi_k = k pi (3 - sqrt 5), u_k = (r cos phi, r sin phi, z) rounded to fp32; dirs == NULL
+ *     computes it with the C library, whose cos / sin may round differently from another one's (the Python wrapper passes its table).
+ *   R_i = (double)radius_i + (double)probe (default 1.4).  Both chains together hold at most 16 distinct radius values (fp32 bit
+ *     patterns); the class of an atom is the index of its value in their ascending list.
+ *   distance: d = sqrt((dx*dx + dy*dy) + dz*dz) in fp64.  Point k of atom i of a chain in its input frame is c_i + R_i u_k (fp64,
+ *     component-wise); it is exposed iff no OTHER atom j of that chain has d < R_j (strict).  Taken once, at creation.
+ *   pose p: x_a as dfm_pose_sterics moves ligand atom a; w_k = (R[:,0] u0 + R[:,1] u1) + R[:,2] u2 with R = R(rot_p); the ligand point
+ *     is x_a + R_a w_k, the receptor point c_b + R_b u_k.  A point is buried in pose p iff it is exposed and some atom j of the OTHER
+ *     chain has d < R_j (strict).  A NaN distance buries nothing: a pose with a NaN or infinite rot / tr gets all zeros (not an error).
+ *   lig_buried [P,Al], rec_buried [P,Ar]: buried points per atom, in the caller's atom order; lig_points, rec_points [P]: their sums;
+ *     class_points [P,2,16]: the sums per chain (receptor = 0) and radius class; bsa [P] = sum over chain (receptor first) and class
+ *     (ascending) of count * (4.0 pi R_c R_c / K), left to right, on the host: equal counts give bitwise equal areas.  bsa is the
+ *     total over both sides; the "interface area" is half of it.
+ * dfm_surface_info (every pointer may be NULL): the isolated SASA of each chain (class sums in the same order), the exposed points per
+ * atom (rec_exposed [Ar], lig_exposed [Al]), the number of radius classes and their values (class_radius [16]), the receptor grid's
+ * cells, the most atoms in one cell and the cell edge.
+ * Every output pointer may be NULL.  Counts are integers: apart from points whose distance rounds onto a radius the results equal the
+ * definition, and none depends on P, on a pose's index, on the order of the poses or on the chunks of a call.  A call works through
+ * chunk_poses poses at a time (0: as many as fill 64 MiB of receptor masks - Ar K / 8 bytes per pose - and per-atom output, at most
+ * 32768); dfm_pose_bsa_chunked overrides the creator's chunk_poses for one call.
+ * DFM_E_INVALID / NULL, nothing enqueued: NULL m / rec_atoms / rec_radius / lig_atoms / lig_radius / center (s / rot / tr / out), Ar or
+ * Al < 1 or > 2^24, a non-finite atom, radius, centre, probe or direction, a radius or probe <= 0, K not a multiple of 64 in 64 .. 256,
+ * more than 16 radius classes, chunk_poses < 0, a bounding box of either chain of more than 2^24 grid cells, P < 1.
+ * DFM_E_OOM when the atoms or a chunk do not fit.
+ * Takes the MODEL handle for its device only.  The handle is read-only after creation; every call owns a non-blocking stream and its
+ * device temporaries, so calls on one handle may run from several host threads at once.  No reference call has a counterpart. */
+typedef struct dfm_surface dfm_surface;
+typedef struct {
+    float probe;           /* > 0 */
+    int K;                 /* sphere points per atom */
+    const float *dirs;     /* [K,3] or NULL */
+    int chunk_poses;       /* 0: default */
+} dfm_surface_params;
+typedef struct {
+    int32_t *lig_buried;               /* [P,Al]   or NULL */
+    int32_t *rec_buried;               /* [P,Ar]   or NULL */
+    int32_t *lig_points, *rec_points;  /* [P]      or NULL */
+    int32_t *class_points;             /* [P,2,16] or NULL */
+    double *bsa;                       /* [P]      or NULL */
+} dfm_bsa_out;
+dfm_surface *dfm_surface_create(dfm_model *m, int Ar, const float *rec_atoms, const float *rec_radius, int Al, const float *lig_atoms,
+                                const float *lig_radius, const float center[3], const dfm_surface_params *p_or_null);
+void dfm_surface_destroy(dfm_surface *s);
+int dfm_surface_info(const dfm_surface *s, double *sasa_rec, double *sasa_lig, int32_t *rec_exposed, int32_t *lig_exposed,
+                     int32_t *n_classes, float *class_radius, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge);
+int dfm_pose_bsa(dfm_surface *s, int P, const float *rot, const float *tr, dfm_bsa_out *out);
+int dfm_pose_bsa_chunked(dfm_surface *s, int P, const float *rot, const float *tr, int chunk_poses, dfm_bsa_out *out);
+/* GPU milliseconds of the calling thread's last dfm_pose_bsa, summed over its chunks: the host-to-device copies of the poses and the
+ * kernels (k_surface_pose, k_surface, k_surface_finish, the memsets of the masks and of the per-atom output) - tools/surface_bench.py */
+int dfm_bsa_last_timing(double *copy_ms, double *kernel_ms);
 /* edges per node for this complex: min(N,20) + min(40, N-20) */
 int dfm_complex_degree(const dfm_complex *cx);
 /* Device blocks released by destroyed handles are parked per device for the next handle (a set driver creates and destroys a
