@@ -14,6 +14,7 @@
 
 #include "dfm_device.h"
 #include "dfm_internal.h"
+#include "dfm_poseprep.h"
 
 using namespace dfm;
 
@@ -905,7 +906,24 @@ extern "C" int dfm_restraint_eval(dfm_complex *cx, int B, const float *lig_pos, 
 // Pose clustering (kernels_cluster.hip).  Bound to the model handle: the drivers close a complex right after sampling, and clustering
 // runs later, on the post-processing thread.  Every call owns a non-blocking stream and its temporaries (block cache), so calls from
 // several host threads, and next to that model's complex handles, do not share any state.
-static thread_local double g_cluster_ms[2] = {0.0, 0.0};      // k_pose_dist, the clustering kernels of this thread's last call
+// the two millisecond figures of this thread's last call of each kind, behind the dfm_*_last_timing getters: k_pose_dist and the
+// clustering kernels for MS_CLUSTER, host-to-device copies and kernels for the others
+enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_KINDS };
+static thread_local double g_last_ms[MS_KINDS][2] = {};
+
+static void set_last_ms(int kind, double a, double b)
+{
+    g_last_ms[kind][0] = a;
+    g_last_ms[kind][1] = b;
+}
+
+static int last_timing(int kind, double *a, double *b)
+{
+    if (!a || !b) return fail(DFM_E_INVALID, "NULL argument");
+    *a = g_last_ms[kind][0];
+    *b = g_last_ms[kind][1];
+    return DFM_OK;
+}
 
 static int check_pose_args(int B, int L, const float *lig_pos, const int32_t *residues, int n_res, std::vector<int32_t> *res_out)
 {
@@ -966,6 +984,41 @@ struct PoseCall {
     }
 };
 
+// the chunk loop of the rigid-pose calls (dfm_pose_sterics, dfm_pose_bsa): the chunk's (rot, tr) on the device, their transforms T, and
+// the call's copy / kernel milliseconds from the call's own events.  Per chunk: upload, the caller's memsets and launches, kernels_done,
+// the caller's downloads, finish
+struct PoseChunks {
+    PoseCall &c;
+    const float *rot, *tr;
+    float *d_rot = nullptr, *d_tr = nullptr;
+    double *T = nullptr;
+    double copy_ms = 0.0, kernel_ms = 0.0;
+    hipError_t open(int Pc)
+    {
+        hipError_t e = c.tmp.alloc(&d_rot, (size_t)Pc * 3);
+        if (e == hipSuccess) e = c.tmp.alloc(&d_tr, (size_t)Pc * 3);
+        if (e == hipSuccess) e = c.tmp.alloc(&T, (size_t)Pc * 12);
+        return e;
+    }
+    hipError_t upload(int p0, int n)
+    {
+        hipError_t e = hipEventRecord(c.ev[0], c.s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_rot, rot + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_tr, tr + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s);
+        if (e == hipSuccess) e = hipEventRecord(c.ev[1], c.s);
+        return e;
+    }
+    hipError_t kernels_done() { return hipEventRecord(c.ev[2], c.s); }
+    hipError_t finish()
+    {
+        const hipError_t e = hipStreamSynchronize(c.s);
+        float ms = 0.f;
+        if (e == hipSuccess && hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) copy_ms += ms;
+        if (e == hipSuccess && hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess) kernel_ms += ms;
+        return e;
+    }
+};
+
 extern "C" int dfm_pose_rmsd(dfm_model *m, int B, int L, const float *lig_pos, const int32_t *residues, int n_res, float *rmsd)
 {
     if (!m || !rmsd) return fail(DFM_E_INVALID, "NULL argument");
@@ -980,8 +1033,7 @@ extern "C" int dfm_pose_rmsd(dfm_model *m, int B, int L, const float *lig_pos, c
     HIPCHK(hipMemcpyAsync(rmsd, d, (size_t)B * B * sizeof(float), hipMemcpyDeviceToHost, c.s));
     HIPCHK(hipStreamSynchronize(c.s));
     float ms = 0.f;
-    g_cluster_ms[0] = hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess ? ms : -1.0;
-    g_cluster_ms[1] = 0.0;
+    set_last_ms(MS_CLUSTER, hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess ? ms : -1.0, 0.0);
     return DFM_OK;
 }
 
@@ -1050,24 +1102,20 @@ extern "C" int dfm_pose_cluster(dfm_model *m, int B, int L, const float *lig_pos
     std::memcpy(center, h.data() + B, (size_t)n * sizeof(int32_t));
     std::memcpy(size, h.data() + B + maxc, (size_t)n * sizeof(int32_t));
     float ms = 0.f;
-    g_cluster_ms[0] = hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess ? ms : -1.0;
-    g_cluster_ms[1] = hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess ? ms : -1.0;
+    const double dist_ms = hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess ? ms : -1.0;
+    set_last_ms(MS_CLUSTER, dist_ms, hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess ? ms : -1.0);
     return DFM_OK;
 }
 
 extern "C" int dfm_pose_last_timing(double *dist_ms, double *cluster_ms)
 {
-    if (!dist_ms || !cluster_ms) return fail(DFM_E_INVALID, "NULL argument");
-    *dist_ms = g_cluster_ms[0];
-    *cluster_ms = g_cluster_ms[1];
-    return DFM_OK;
+    return last_timing(MS_CLUSTER, dist_ms, cluster_ms);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Docking metrics (kernels_metrics.hip).  A dfm_native holds what the native alone fixes and is read-only after creation; like the
 // clustering calls it is bound to the model handle's device only, and every dfm_pose_metrics call owns its stream and temporaries.
 constexpr size_t METRICS_CHUNK_BYTES = (size_t)64 << 20;      // poses uploaded and evaluated per chunk of a call
-static thread_local double g_metrics_ms[2] = {0.0, 0.0};      // host-to-device copies, kernels of this thread's last dfm_pose_metrics
 
 struct dfm_native {
     int device = 0, R = 0, L = 0;
@@ -1233,8 +1281,7 @@ extern "C" int dfm_pose_metrics(dfm_native *nat, int P, const float *lig_pos, co
         if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) copy_ms += ms;
         if (hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess) kernel_ms += ms;
     }
-    g_metrics_ms[0] = copy_ms;
-    g_metrics_ms[1] = kernel_ms;
+    set_last_ms(MS_METRICS, copy_ms, kernel_ms);
     const double nc = (double)mc.n_contacts;
     for (int p = 0; p < P; ++p) {
         const double cr = h_rmsd[(size_t)p * 3], ir = h_rmsd[(size_t)p * 3 + 1], lr = h_rmsd[(size_t)p * 3 + 2];
@@ -1251,10 +1298,7 @@ extern "C" int dfm_pose_metrics(dfm_native *nat, int P, const float *lig_pos, co
 
 extern "C" int dfm_metrics_last_timing(double *copy_ms, double *kernel_ms)
 {
-    if (!copy_ms || !kernel_ms) return fail(DFM_E_INVALID, "NULL argument");
-    *copy_ms = g_metrics_ms[0];
-    *kernel_ms = g_metrics_ms[1];
-    return DFM_OK;
+    return last_timing(MS_METRICS, copy_ms, kernel_ms);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1263,7 +1307,6 @@ extern "C" int dfm_metrics_last_timing(double *copy_ms, double *kernel_ms)
 // and the scoring pass, a longer call uploads and evaluates every chunk again in the scoring pass.
 constexpr size_t CONSENSUS_CHUNK_BYTES = (size_t)256 << 20;
 constexpr int CONSENSUS_MAX_POSES = 65536;
-static thread_local double g_consensus_ms[2] = {0.0, 0.0};      // host-to-device copies, kernels of this thread's last dfm_pose_consensus
 
 extern "C" int dfm_consensus_chunk_poses(int R, int L)
 {
@@ -1349,17 +1392,13 @@ extern "C" int dfm_pose_consensus(dfm_model *m, int P, int R, int L, const float
     if (out->rec_count) HIPCHK(hipMemcpyAsync(out->rec_count, d_marg, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
     if (out->lig_count) HIPCHK(hipMemcpyAsync(out->lig_count, d_marg + R, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
     HIPCHK(hipStreamSynchronize(c.s));
-    g_consensus_ms[0] = copy_ms;
-    g_consensus_ms[1] = kernel_ms;
+    set_last_ms(MS_CONSENSUS, copy_ms, kernel_ms);
     return DFM_OK;
 }
 
 extern "C" int dfm_consensus_last_timing(double *copy_ms, double *kernel_ms)
 {
-    if (!copy_ms || !kernel_ms) return fail(DFM_E_INVALID, "NULL argument");
-    *copy_ms = g_consensus_ms[0];
-    *kernel_ms = g_consensus_ms[1];
-    return DFM_OK;
+    return last_timing(MS_CONSENSUS, copy_ms, kernel_ms);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1368,8 +1407,6 @@ extern "C" int dfm_consensus_last_timing(double *copy_ms, double *kernel_ms)
 // model handle's device only, and every dfm_pose_sterics call owns its stream and temporaries.
 constexpr size_t STERICS_CHUNK_BYTES = (size_t)64 << 20;      // per-atom output of one chunk of a call
 constexpr int STERICS_MAX_CHUNK = 32768;                      // poses per launch (gridDim.y)
-constexpr int STERICS_MAX_ATOMS = 1 << 24, STERICS_MAX_CELLS = 1 << 24;
-static thread_local double g_sterics_ms[2] = {0.0, 0.0};      // host-to-device copies, kernels of this thread's last dfm_pose_sterics
 static thread_local int g_sterics_count = 0;                  // dfm_sterics_exit_counts: count the early exits of this thread's calls
 static thread_local uint64_t g_sterics_exits[3] = {0, 0, 0};  // waves, left at the sphere test, left at the box test
 
@@ -1391,147 +1428,43 @@ extern "C" void dfm_atoms_destroy(dfm_atoms *a)
     delete a;
 }
 
-// 21 bits of each cell coordinate interleaved
-static uint64_t morton3(uint32_t x, uint32_t y, uint32_t z)
-{
-    auto spread = [](uint64_t v) {
-        v &= 0x1fffff;
-        v = (v | v << 32) & 0x1f00000000ffffull;
-        v = (v | v << 16) & 0x1f0000ff0000ffull;
-        v = (v | v << 8) & 0x100f00f00f00f00full;
-        v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-        v = (v | v << 2) & 0x1249249249249249ull;
-        return v;
-    };
-    return spread(x) | spread(y) << 1 | spread(z) << 2;
-}
-
 extern "C" dfm_atoms *dfm_atoms_create(dfm_model *m, int Ar, const float *rec_atoms, int Al, const float *lig_atoms, const float center[3],
                                        const dfm_sterics_params *p_or_null)
 {
     auto bad = [](int code, const std::string &msg) -> dfm_atoms * { (void)fail(code, msg); return nullptr; };
     if (!m) return bad(DFM_E_INVALID, "m is NULL");
-    if (!rec_atoms) return bad(DFM_E_INVALID, "rec_atoms is NULL");
-    if (!lig_atoms) return bad(DFM_E_INVALID, "lig_atoms is NULL");
-    if (!center) return bad(DFM_E_INVALID, "center is NULL");
-    if (Ar < 1 || Al < 1) return bad(DFM_E_INVALID, "need Ar >= 1 and Al >= 1");
-    if (Ar > STERICS_MAX_ATOMS || Al > STERICS_MAX_ATOMS) return bad(DFM_E_INVALID, "Ar or Al exceeds 2^24 atoms");
+    if (const std::string msg = check_atom_sets(Ar, rec_atoms, Al, lig_atoms, center); !msg.empty()) return bad(DFM_E_INVALID, msg);
     dfm_sterics_params prm = {3.0f, 5.0f, 0};
     if (p_or_null) prm = *p_or_null;
     if (!std::isfinite(prm.clash_cutoff) || !std::isfinite(prm.contact_cutoff) || !(prm.clash_cutoff > 0.f) || !(prm.contact_cutoff > 0.f))
         return bad(DFM_E_INVALID, "cutoffs must be finite and > 0");
     if (prm.contact_cutoff < prm.clash_cutoff) return bad(DFM_E_INVALID, "contact_cutoff must be >= clash_cutoff");
     if (prm.chunk_poses < 0) return bad(DFM_E_INVALID, "chunk_poses must be >= 0");
-    for (size_t i = 0; i < (size_t)Ar * 3; ++i)
-        if (!std::isfinite(rec_atoms[i])) return bad(DFM_E_INVALID, "rec_atoms: atom " + std::to_string(i / 3) + " is not finite");
-    for (size_t i = 0; i < (size_t)Al * 3; ++i)
-        if (!std::isfinite(lig_atoms[i])) return bad(DFM_E_INVALID, "lig_atoms: atom " + std::to_string(i / 3) + " is not finite");
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(center[k])) return bad(DFM_E_INVALID, "center is not finite");
     // the receptor's grid: origin = the bounding box's low corner, edge = the contact cutoff
+    CellGrid gr;
+    if (!build_cell_grid(Ar, rec_atoms, (double)prm.contact_cutoff, gr))
+        return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells of the contact cutoff");
+    double maxabs = 0.0;
+    for (int k = 0; k < 3; ++k) maxabs = std::max(maxabs, std::max(std::fabs(gr.lo[k]), std::fabs(gr.hi[k])));
+    maxabs += 2.0 * (double)prm.contact_cutoff + 1.0;
+    // the fp32 reject threshold (dfm_posewalk.h): contact * 1.0001 + slack
+    const float thr = prm.contact_cutoff * 1.0001f + pose_slack(maxabs);
     StericsConst sc = {};
-    sc.edge = sc.contact = (double)prm.contact_cutoff;
+    sc.g = walk_grid(gr, (double)prm.contact_cutoff, (double)thr, center);
+    sc.contact = (double)prm.contact_cutoff;
     sc.clash = (double)prm.clash_cutoff;
-    for (int k = 0; k < 3; ++k) { sc.lo[k] = sc.hi[k] = (double)rec_atoms[k]; sc.center[k] = (double)center[k]; }
-    for (int i = 1; i < Ar; ++i)
-        for (int k = 0; k < 3; ++k) {
-            const double v = (double)rec_atoms[(size_t)i * 3 + k];
-            sc.lo[k] = std::min(sc.lo[k], v);
-            sc.hi[k] = std::max(sc.hi[k], v);
-        }
-    double dims[3], cells = 1.0, maxabs = 0.0;
-    for (int k = 0; k < 3; ++k) {
-        dims[k] = std::floor((sc.hi[k] - sc.lo[k]) / sc.edge) + 1.0;
-        cells *= dims[k];
-        maxabs = std::max(maxabs, std::max(std::fabs(sc.lo[k]), std::fabs(sc.hi[k])));
-    }
-    if (!(cells <= (double)STERICS_MAX_CELLS)) return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells of the contact cutoff");
-    sc.nx = (int)dims[0]; sc.ny = (int)dims[1]; sc.nz = (int)dims[2];
-    maxabs += 2.0 * sc.contact + 1.0;
-    // the fp32 reject threshold (kernels_sterics.hip): contact * 1.0001 + max(1e-3, 2.5e-7 maxabs)
-    const float slack = std::max(1e-3f, (float)(2.5e-7 * maxabs)), thr = prm.contact_cutoff * 1.0001f + slack;
     sc.reject2 = thr * thr;
-    sc.grow = (double)thr;
     if (!std::isfinite(sc.reject2)) return bad(DFM_E_INVALID, "cutoffs must be finite and > 0");
-    const int n_cells = sc.nx * sc.ny * sc.nz;
-    auto cell1 = [&](double x, int k, int n) {
-        double c = std::floor((x - sc.lo[k]) / sc.edge);
-        c = c < 0.0 ? 0.0 : (c > (double)(n - 1) ? (double)(n - 1) : c);
-        return (int)c;
-    };
-    // counting sort of the receptor atoms by cell
-    std::vector<int32_t> start((size_t)n_cells + 1, 0), cell_of((size_t)Ar);
-    for (int i = 0; i < Ar; ++i) {
-        const float *x = rec_atoms + (size_t)i * 3;
-        const int c = (cell1((double)x[2], 2, sc.nz) * sc.ny + cell1((double)x[1], 1, sc.ny)) * sc.nx + cell1((double)x[0], 0, sc.nx);
-        cell_of[(size_t)i] = c;
-        ++start[(size_t)c + 1];
-    }
-    int max_cell = 0;
-    for (int c = 0; c < n_cells; ++c) {
-        max_cell = std::max(max_cell, (int)start[(size_t)c + 1]);
-        start[(size_t)c + 1] += start[(size_t)c];
-    }
-    std::vector<float> rec4((size_t)Ar * 4, 0.f);
-    {
-        std::vector<int32_t> at(start.begin(), start.end() - 1);
-        for (int i = 0; i < Ar; ++i) {
-            float *dst = rec4.data() + (size_t)at[(size_t)cell_of[(size_t)i]]++ * 4;
-            for (int k = 0; k < 3; ++k) dst[k] = rec_atoms[(size_t)i * 3 + k];
-        }
-    }
-    // the ligand in Morton order of its own cells (ties: the caller's order), and a bounding sphere per block of 64
     double llo[3] = {(double)lig_atoms[0], (double)lig_atoms[1], (double)lig_atoms[2]};
     for (int i = 1; i < Al; ++i)
         for (int k = 0; k < 3; ++k) llo[k] = std::min(llo[k], (double)lig_atoms[(size_t)i * 3 + k]);
-    std::vector<std::pair<uint64_t, int32_t>> order((size_t)Al);
-    for (int i = 0; i < Al; ++i) {
-        uint32_t c[3];
-        for (int k = 0; k < 3; ++k) {
-            const double v = std::floor(((double)lig_atoms[(size_t)i * 3 + k] - llo[k]) / sc.edge);
-            c[k] = (uint32_t)(v < 0.0 ? 0.0 : (v > 2097151.0 ? 2097151.0 : v));
-        }
-        order[(size_t)i] = {morton3(c[0], c[1], c[2]), i};
-    }
-    std::sort(order.begin(), order.end());
-    const int nblk = (Al + 63) / 64;
-    std::vector<float> lig4((size_t)Al * 4, 0.f), sph((size_t)nblk * 4, 0.f);
-    std::vector<int32_t> lig_index((size_t)Al);
-    for (int i = 0; i < Al; ++i) {
-        const int32_t src = order[(size_t)i].second;
-        lig_index[(size_t)i] = src;
-        for (int k = 0; k < 3; ++k) lig4[(size_t)i * 4 + k] = lig_atoms[(size_t)src * 3 + k];
-    }
-    for (int b = 0; b < nblk; ++b) {
-        const int i0 = b * 64, i1 = std::min(Al, i0 + 64);
-        double lo[3], hi[3];
-        for (int k = 0; k < 3; ++k) lo[k] = hi[k] = (double)lig4[(size_t)i0 * 4 + k];
-        for (int i = i0 + 1; i < i1; ++i)
-            for (int k = 0; k < 3; ++k) {
-                lo[k] = std::min(lo[k], (double)lig4[(size_t)i * 4 + k]);
-                hi[k] = std::max(hi[k], (double)lig4[(size_t)i * 4 + k]);
-            }
-        // the centre as the fp32 the kernel reads, the radius measured from THAT point and rounded up
-        float c[3];
-        for (int k = 0; k < 3; ++k) c[k] = (float)(0.5 * (lo[k] + hi[k]) - sc.center[k]);
-        double r2 = 0.0;
-        for (int i = i0; i < i1; ++i) {
-            double d2 = 0.0;
-            for (int k = 0; k < 3; ++k) {
-                const double d = ((double)lig4[(size_t)i * 4 + k] - sc.center[k]) - (double)c[k];
-                d2 += d * d;
-            }
-            r2 = std::max(r2, d2);
-        }
-        for (int k = 0; k < 3; ++k) sph[(size_t)b * 4 + k] = c[k];
-        sph[(size_t)b * 4 + 3] = std::nextafter((float)(std::sqrt(r2) * (1.0 + 1e-6) + 1e-6), INFINITY);
-    }
-    for (size_t i = 0; i < sph.size(); ++i)
-        if (!std::isfinite(sph[i])) return bad(DFM_E_INVALID, "lig_atoms / center: the ligand's extent about the centre overflows fp32");
+    const LigandBlocks lb = build_ligand_blocks(Al, lig_atoms, llo, sc.g.edge, sc.g.center);
+    if (!lb.finite) return bad(DFM_E_INVALID, "lig_atoms / center: the ligand's extent about the centre overflows fp32");
+    const std::vector<float> rec4 = gather4(gr.order, rec_atoms, nullptr), lig4 = gather4(lb.index, lig_atoms, nullptr);
     DeviceScope ds(m->device);
     if (ds.err != hipSuccess) return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err));
     dfm_atoms *a = new dfm_atoms;
-    a->device = m->device; a->Ar = Ar; a->Al = Al; a->sc = sc; a->n_cells = n_cells; a->max_cell_atoms = max_cell;
+    a->device = m->device; a->Ar = Ar; a->Al = Al; a->sc = sc; a->n_cells = sc.g.nx * sc.g.ny * sc.g.nz; a->max_cell_atoms = gr.max_cell;
     a->cell_edge = prm.contact_cutoff;
     a->chunk_poses = prm.chunk_poses;
     a->default_chunk = (int)std::min<size_t>(STERICS_MAX_CHUNK, std::max<size_t>(1, STERICS_CHUNK_BYTES / ((size_t)Al * 2 * sizeof(int32_t))));
@@ -1540,10 +1473,10 @@ extern "C" dfm_atoms *dfm_atoms_create(dfm_model *m, int Ar, const float *rec_at
         PoseCall c;
         e = c.open();
         if (e == hipSuccess) e = a->pool.upload_async(&a->rec, rec4.data(), rec4.size(), c.s);
-        if (e == hipSuccess) e = a->pool.upload_async(&a->cell_start, start.data(), start.size(), c.s);
+        if (e == hipSuccess) e = a->pool.upload_async(&a->cell_start, gr.start.data(), gr.start.size(), c.s);
         if (e == hipSuccess) e = a->pool.upload_async(&a->lig, lig4.data(), lig4.size(), c.s);
-        if (e == hipSuccess) e = a->pool.upload_async(&a->sphere, sph.data(), sph.size(), c.s);
-        if (e == hipSuccess) e = a->pool.upload_async(&a->lig_index, lig_index.data(), lig_index.size(), c.s);
+        if (e == hipSuccess) e = a->pool.upload_async(&a->sphere, lb.sphere.data(), lb.sphere.size(), c.s);
+        if (e == hipSuccess) e = a->pool.upload_async(&a->lig_index, lb.index.data(), lb.index.size(), c.s);
         if (e == hipSuccess) e = hipStreamSynchronize(c.s);
     }      // the call's stream has drained: the host vectors it read may go
     if (e != hipSuccess) {
@@ -1579,13 +1512,10 @@ extern "C" int dfm_pose_sterics_chunked(dfm_atoms *a, int P, const float *rot, c
     const int want = chunk_poses > 0 ? chunk_poses : a->chunk_poses;
     const int Pc = std::min(P, want > 0 ? std::min(want, STERICS_MAX_CHUNK) : (per_atom ? a->default_chunk : STERICS_MAX_CHUNK));
     const size_t Al = (size_t)a->Al;
-    float *d_rot = nullptr, *d_tr = nullptr;
-    double *T = nullptr;
+    PoseChunks ch{c, rot, tr};
     int32_t *d_cnt = nullptr, *d_lc = nullptr, *d_lt = nullptr;
     uint64_t *d_min = nullptr, *d_exits = nullptr;
-    HIPCHK(c.tmp.alloc(&d_rot, (size_t)Pc * 3));
-    HIPCHK(c.tmp.alloc(&d_tr, (size_t)Pc * 3));
-    HIPCHK(c.tmp.alloc(&T, (size_t)Pc * 12));
+    HIPCHK(ch.open(Pc));
     HIPCHK(c.tmp.alloc(&d_cnt, (size_t)Pc * 2));      // n_clash | n_contact
     HIPCHK(c.tmp.alloc(&d_min, (size_t)Pc));
     if (out->lig_clash) HIPCHK(c.tmp.alloc(&d_lc, (size_t)Pc * Al));
@@ -1597,26 +1527,19 @@ extern "C" int dfm_pose_sterics_chunked(dfm_atoms *a, int P, const float *rot, c
     const StericsAtoms at = {a->rec, a->lig, a->sphere, a->cell_start, a->lig_index, a->sc, a->Ar, a->Al};
     std::vector<int32_t> h_cnt((size_t)Pc * 2);
     std::vector<uint64_t> h_min((size_t)Pc);
-    double copy_ms = 0.0, kernel_ms = 0.0;
     for (int p0 = 0; p0 < P; p0 += Pc) {
         const int n = std::min(Pc, P - p0);
-        HIPCHK(hipEventRecord(c.ev[0], c.s));
-        HIPCHK(hipMemcpyAsync(d_rot, rot + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s));
-        HIPCHK(hipMemcpyAsync(d_tr, tr + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s));
-        HIPCHK(hipEventRecord(c.ev[1], c.s));
+        HIPCHK(ch.upload(p0, n));
         if (d_lc) HIPCHK(hipMemsetAsync(d_lc, 0, (size_t)n * Al * sizeof(int32_t), c.s));
         if (d_lt) HIPCHK(hipMemsetAsync(d_lt, 0, (size_t)n * Al * sizeof(int32_t), c.s));
-        HIPCHK(launch_sterics_pose(d_rot, d_tr, n, T, d_cnt, d_cnt + Pc, d_min, c.s));
-        HIPCHK(launch_sterics(at, T, n, d_cnt, d_cnt + Pc, d_min, d_lc, d_lt, d_exits, c.s));
-        HIPCHK(hipEventRecord(c.ev[2], c.s));
+        HIPCHK(launch_sterics_pose(ch.d_rot, ch.d_tr, n, ch.T, d_cnt, d_cnt + Pc, d_min, c.s));
+        HIPCHK(launch_sterics(at, ch.T, n, d_cnt, d_cnt + Pc, d_min, d_lc, d_lt, d_exits, c.s));
+        HIPCHK(ch.kernels_done());
         HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)Pc * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
         HIPCHK(hipMemcpyAsync(h_min.data(), d_min, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, c.s));
         if (d_lc) HIPCHK(hipMemcpyAsync(out->lig_clash + (size_t)p0 * Al, d_lc, (size_t)n * Al * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
         if (d_lt) HIPCHK(hipMemcpyAsync(out->lig_contact + (size_t)p0 * Al, d_lt, (size_t)n * Al * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        HIPCHK(hipStreamSynchronize(c.s));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) copy_ms += ms;
-        if (hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess) kernel_ms += ms;
+        HIPCHK(ch.finish());
         for (int p = 0; p < n; ++p) {
             if (out->n_clash) out->n_clash[p0 + p] = h_cnt[(size_t)p];
             if (out->n_contact) out->n_contact[p0 + p] = h_cnt[(size_t)Pc + p];
@@ -1631,8 +1554,7 @@ extern "C" int dfm_pose_sterics_chunked(dfm_atoms *a, int P, const float *rot, c
         g_sterics_exits[1] = h[0];
         g_sterics_exits[2] = h[1];
     }
-    g_sterics_ms[0] = copy_ms;
-    g_sterics_ms[1] = kernel_ms;
+    set_last_ms(MS_STERICS, ch.copy_ms, ch.kernel_ms);
     return DFM_OK;
 }
 
@@ -1643,10 +1565,7 @@ extern "C" int dfm_pose_sterics(dfm_atoms *a, int P, const float *rot, const flo
 
 extern "C" int dfm_sterics_last_timing(double *copy_ms, double *kernel_ms)
 {
-    if (!copy_ms || !kernel_ms) return fail(DFM_E_INVALID, "NULL argument");
-    *copy_ms = g_sterics_ms[0];
-    *kernel_ms = g_sterics_ms[1];
-    return DFM_OK;
+    return last_timing(MS_STERICS, copy_ms, kernel_ms);
 }
 
 extern "C" int dfm_sterics_exit_counts(int enable, uint64_t *counts_or_null)
@@ -1661,7 +1580,6 @@ extern "C" int dfm_sterics_exit_counts(int enable, uint64_t *counts_or_null)
 // the rotation centre fix - the receptor's cell grid, the ligand in blocks of 64 neighbours, every atom's isolated exposure mask - and is
 // read-only after creation; every dfm_pose_bsa call owns its stream and temporaries.
 constexpr size_t SURFACE_CHUNK_BYTES = (size_t)64 << 20;      // receptor masks and per-atom output of one chunk of a call
-static thread_local double g_bsa_ms[2] = {0.0, 0.0};          // host-to-device copies, kernels of this thread's last dfm_pose_bsa
 
 struct dfm_surface {
     int device = 0, Ar = 0, Al = 0, K = 0, n_classes = 0, n_cells = 0, max_cell_atoms = 0, chunk_poses = 0;
@@ -1683,66 +1601,15 @@ extern "C" void dfm_surface_destroy(dfm_surface *s)
     delete s;
 }
 
-// the atoms of one chain sorted by cell of a grid of the given edge over their bounding box (a stable counting sort): lo / hi / dims,
-// start [cells + 1], order [n] = atom indices by cell.  false: more than 2^24 cells
-struct SurfaceGrid {
-    double lo[3], hi[3];
-    int dims[3], max_cell = 0;
-    std::vector<int32_t> start, order;
-};
-static bool surface_grid(int n, const float *xyz, double edge, SurfaceGrid &g)
-{
-    for (int k = 0; k < 3; ++k) g.lo[k] = g.hi[k] = (double)xyz[k];
-    for (int i = 1; i < n; ++i)
-        for (int k = 0; k < 3; ++k) {
-            const double v = (double)xyz[(size_t)i * 3 + k];
-            g.lo[k] = std::min(g.lo[k], v);
-            g.hi[k] = std::max(g.hi[k], v);
-        }
-    double cells = 1.0;
-    for (int k = 0; k < 3; ++k) {
-        const double d = std::floor((g.hi[k] - g.lo[k]) / edge) + 1.0;
-        cells *= d;
-        if (!(cells <= (double)STERICS_MAX_CELLS)) return false;
-        g.dims[k] = (int)d;
-    }
-    const int n_cells = g.dims[0] * g.dims[1] * g.dims[2];
-    auto cell1 = [&](double x, int k) {
-        double c = std::floor((x - g.lo[k]) / edge);
-        c = c < 0.0 ? 0.0 : (c > (double)(g.dims[k] - 1) ? (double)(g.dims[k] - 1) : c);
-        return (int)c;
-    };
-    std::vector<int32_t> cell((size_t)n);
-    g.start.assign((size_t)n_cells + 1, 0);
-    for (int i = 0; i < n; ++i) {
-        const float *x = xyz + (size_t)i * 3;
-        cell[(size_t)i] = (cell1((double)x[2], 2) * g.dims[1] + cell1((double)x[1], 1)) * g.dims[0] + cell1((double)x[0], 0);
-        ++g.start[(size_t)cell[(size_t)i] + 1];
-    }
-    g.max_cell = 0;
-    for (int c = 0; c < n_cells; ++c) {
-        g.max_cell = std::max(g.max_cell, (int)g.start[(size_t)c + 1]);
-        g.start[(size_t)c + 1] += g.start[(size_t)c];
-    }
-    g.order.resize((size_t)n);
-    std::vector<int32_t> at(g.start.begin(), g.start.end() - 1);
-    for (int i = 0; i < n; ++i) g.order[(size_t)at[(size_t)cell[(size_t)i]]++] = i;
-    return true;
-}
-
 extern "C" dfm_surface *dfm_surface_create(dfm_model *m, int Ar, const float *rec_atoms, const float *rec_radius, int Al,
                                            const float *lig_atoms, const float *lig_radius, const float center[3],
                                            const dfm_surface_params *p_or_null)
 {
     auto bad = [](int code, const std::string &msg) -> dfm_surface * { (void)fail(code, msg); return nullptr; };
     if (!m) return bad(DFM_E_INVALID, "m is NULL");
-    if (!rec_atoms) return bad(DFM_E_INVALID, "rec_atoms is NULL");
+    if (const std::string msg = check_atom_sets(Ar, rec_atoms, Al, lig_atoms, center); !msg.empty()) return bad(DFM_E_INVALID, msg);
     if (!rec_radius) return bad(DFM_E_INVALID, "rec_radius is NULL");
-    if (!lig_atoms) return bad(DFM_E_INVALID, "lig_atoms is NULL");
     if (!lig_radius) return bad(DFM_E_INVALID, "lig_radius is NULL");
-    if (!center) return bad(DFM_E_INVALID, "center is NULL");
-    if (Ar < 1 || Al < 1) return bad(DFM_E_INVALID, "need Ar >= 1 and Al >= 1");
-    if (Ar > STERICS_MAX_ATOMS || Al > STERICS_MAX_ATOMS) return bad(DFM_E_INVALID, "Ar or Al exceeds 2^24 atoms");
     dfm_surface_params prm = {1.4f, 128, nullptr, 0};
     if (p_or_null) prm = *p_or_null;
     if (!std::isfinite(prm.probe) || !(prm.probe > 0.f)) return bad(DFM_E_INVALID, "probe must be finite and > 0");
@@ -1760,12 +1627,6 @@ extern "C" dfm_surface *dfm_surface_create(dfm_model *m, int Ar, const float *re
     }
     for (float v : dirs)
         if (!std::isfinite(v)) return bad(DFM_E_INVALID, "dirs is not finite");
-    for (size_t i = 0; i < (size_t)Ar * 3; ++i)
-        if (!std::isfinite(rec_atoms[i])) return bad(DFM_E_INVALID, "rec_atoms: atom " + std::to_string(i / 3) + " is not finite");
-    for (size_t i = 0; i < (size_t)Al * 3; ++i)
-        if (!std::isfinite(lig_atoms[i])) return bad(DFM_E_INVALID, "lig_atoms: atom " + std::to_string(i / 3) + " is not finite");
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(center[k])) return bad(DFM_E_INVALID, "center is not finite");
     // the radius classes: the distinct fp32 values of both chains in ascending order (positive floats order like their bit patterns)
     std::vector<float> values;
     for (int side = 0; side < 2; ++side) {
@@ -1782,18 +1643,18 @@ extern "C" dfm_surface *dfm_surface_create(dfm_model *m, int Ar, const float *re
     std::sort(values.begin(), values.end());
     auto class_of = [&](float v) { return (int32_t)(std::lower_bound(values.begin(), values.end(), v) - values.begin()); };
     const double probe = (double)prm.probe, Rmax = (double)values.back() + probe;
-    // one grid edge for the receptor's device grid and both host exposure grids: at least 2 Rmax, grown as kernels_sterics.hip grows
-    // its cutoff - by the factor 1.0001 and slack = max(1e-3, 2.5e-7 maxabs) - which is also the fp32 pair test's allowance
+    // one grid edge for the receptor's device grid and both host exposure grids: at least 2 Rmax, grown as dfm_posewalk.h grows a
+    // reach - by the factor 1.0001 and the slack - which is also the fp32 pair test's allowance
     double maxabs = 0.0;
     for (size_t i = 0; i < (size_t)Ar * 3; ++i) maxabs = std::max(maxabs, std::fabs((double)rec_atoms[i]));
     for (size_t i = 0; i < (size_t)Al * 3; ++i) maxabs = std::max(maxabs, std::fabs((double)lig_atoms[i]));
     maxabs += 4.0 * Rmax + 1.0;
-    const float slack = std::max(1e-3f, (float)(2.5e-7 * maxabs)), thr = (float)(2.0 * Rmax) * 1.0001f + slack;
+    const float slack = pose_slack(maxabs), thr = (float)(2.0 * Rmax) * 1.0001f + slack;
     if (!std::isfinite(thr)) return bad(DFM_E_INVALID, "radii and probe must be finite and > 0");
     const double edge = (double)thr, pad = 1e-6 + 1e-12 * maxabs;
-    SurfaceGrid gr, gl;
-    if (!surface_grid(Ar, rec_atoms, edge, gr)) return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells");
-    if (!surface_grid(Al, lig_atoms, edge, gl)) return bad(DFM_E_INVALID, "the ligand's bounding box needs more than 2^24 cells");
+    CellGrid gr, gl;
+    if (!build_cell_grid(Ar, rec_atoms, edge, gr)) return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells");
+    if (!build_cell_grid(Al, lig_atoms, edge, gl)) return bad(DFM_E_INVALID, "the ligand's bounding box needs more than 2^24 cells");
     std::vector<uint64_t> rexp((size_t)Ar * G), lexp((size_t)Al * G);
     surface_exposure(Ar, rec_atoms, rec_radius, probe, K, dirs.data(), gr.lo, gr.dims, edge, pad, gr.start.data(), gr.order.data(), rexp.data());
     surface_exposure(Al, lig_atoms, lig_radius, probe, K, dirs.data(), gl.lo, gl.dims, edge, pad, gl.start.data(), gl.order.data(), lexp.data());
@@ -1823,70 +1684,25 @@ extern "C" dfm_surface *dfm_surface_create(dfm_model *m, int Ar, const float *re
         sf->sasa[side] = s;
     }
     SurfaceConst sc = {};
-    for (int k = 0; k < 3; ++k) { sc.lo[k] = gr.lo[k]; sc.hi[k] = gr.hi[k]; sc.center[k] = (double)center[k]; }
-    sc.edge = edge; sc.grow = edge; sc.probe = probe; sc.slack = slack;
-    sc.nx = gr.dims[0]; sc.ny = gr.dims[1]; sc.nz = gr.dims[2]; sc.G = G;
+    sc.g = walk_grid(gr, edge, edge, center);
+    sc.probe = probe; sc.slack = slack; sc.G = G;
     sf->sc = sc;
-    // the receptor in cell order
-    std::vector<float> rec4((size_t)Ar * 4);
-    std::vector<int32_t> rec_class((size_t)Ar);
-    std::vector<uint64_t> rexp_s((size_t)Ar * G);
+    // the ligand in blocks of 64 neighbours; both chains' per-atom arrays in their device order
+    const LigandBlocks lb = build_ligand_blocks(Al, lig_atoms, gl.lo, edge, sc.g.center);
+    if (!lb.finite) { delete sf; return bad(DFM_E_INVALID, "lig_atoms / center: the ligand's extent about the centre overflows fp32"); }
+    const std::vector<float> rec4 = gather4(gr.order, rec_atoms, rec_radius), lig4 = gather4(lb.index, lig_atoms, lig_radius);
+    std::vector<int32_t> rec_class((size_t)Ar), lig_class((size_t)Al);
+    std::vector<uint64_t> rexp_s((size_t)Ar * G), lexp_s((size_t)Al * G);
     for (int q = 0; q < Ar; ++q) {
         const int32_t src = gr.order[(size_t)q];
-        for (int k = 0; k < 3; ++k) rec4[(size_t)q * 4 + k] = rec_atoms[(size_t)src * 3 + k];
-        rec4[(size_t)q * 4 + 3] = rec_radius[src];
         rec_class[(size_t)q] = class_of(rec_radius[src]);
         for (int g = 0; g < G; ++g) rexp_s[(size_t)q * G + g] = rexp[(size_t)src * G + g];
     }
-    // the ligand in Morton order of its own cells (ties: the caller's order), and a bounding sphere per block of 64 (dfm_atoms_create)
-    std::vector<std::pair<uint64_t, int32_t>> order((size_t)Al);
-    for (int i = 0; i < Al; ++i) {
-        uint32_t c[3];
-        for (int k = 0; k < 3; ++k) {
-            const double v = std::floor(((double)lig_atoms[(size_t)i * 3 + k] - gl.lo[k]) / edge);
-            c[k] = (uint32_t)(v < 0.0 ? 0.0 : (v > 2097151.0 ? 2097151.0 : v));
-        }
-        order[(size_t)i] = {morton3(c[0], c[1], c[2]), i};
-    }
-    std::sort(order.begin(), order.end());
-    const int nblk = (Al + 63) / 64;
-    std::vector<float> lig4((size_t)Al * 4), sph((size_t)nblk * 4, 0.f);
-    std::vector<int32_t> lig_index((size_t)Al), lig_class((size_t)Al);
-    std::vector<uint64_t> lexp_s((size_t)Al * G);
     for (int q = 0; q < Al; ++q) {
-        const int32_t src = order[(size_t)q].second;
-        lig_index[(size_t)q] = src;
-        for (int k = 0; k < 3; ++k) lig4[(size_t)q * 4 + k] = lig_atoms[(size_t)src * 3 + k];
-        lig4[(size_t)q * 4 + 3] = lig_radius[src];
+        const int32_t src = lb.index[(size_t)q];
         lig_class[(size_t)q] = class_of(lig_radius[src]);
         for (int g = 0; g < G; ++g) lexp_s[(size_t)q * G + g] = lexp[(size_t)src * G + g];
     }
-    for (int b = 0; b < nblk; ++b) {
-        const int i0 = b * 64, i1 = std::min(Al, i0 + 64);
-        double lo[3], hi[3];
-        for (int k = 0; k < 3; ++k) lo[k] = hi[k] = (double)lig4[(size_t)i0 * 4 + k];
-        for (int i = i0 + 1; i < i1; ++i)
-            for (int k = 0; k < 3; ++k) {
-                lo[k] = std::min(lo[k], (double)lig4[(size_t)i * 4 + k]);
-                hi[k] = std::max(hi[k], (double)lig4[(size_t)i * 4 + k]);
-            }
-        // the centre as the fp32 the kernel reads, the radius measured from THAT point and rounded up
-        float c[3];
-        for (int k = 0; k < 3; ++k) c[k] = (float)(0.5 * (lo[k] + hi[k]) - sc.center[k]);
-        double r2 = 0.0;
-        for (int i = i0; i < i1; ++i) {
-            double d2 = 0.0;
-            for (int k = 0; k < 3; ++k) {
-                const double d = ((double)lig4[(size_t)i * 4 + k] - sc.center[k]) - (double)c[k];
-                d2 += d * d;
-            }
-            r2 = std::max(r2, d2);
-        }
-        for (int k = 0; k < 3; ++k) sph[(size_t)b * 4 + k] = c[k];
-        sph[(size_t)b * 4 + 3] = std::nextafter((float)(std::sqrt(r2) * (1.0 + 1e-6) + 1e-6), INFINITY);
-    }
-    for (size_t i = 0; i < sph.size(); ++i)
-        if (!std::isfinite(sph[i])) { delete sf; return bad(DFM_E_INVALID, "lig_atoms / center: the ligand's extent about the centre overflows fp32"); }
     DeviceScope ds(m->device);
     if (ds.err != hipSuccess) { delete sf; return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err)); }
     hipError_t e = hipSuccess;
@@ -1899,8 +1715,8 @@ extern "C" dfm_surface *dfm_surface_create(dfm_model *m, int Ar, const float *re
         if (e == hipSuccess) e = sf->pool.upload_async(&sf->rec_class, rec_class.data(), rec_class.size(), c.s);
         if (e == hipSuccess) e = sf->pool.upload_async(&sf->rec_exp, rexp_s.data(), rexp_s.size(), c.s);
         if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig, lig4.data(), lig4.size(), c.s);
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->sphere, sph.data(), sph.size(), c.s);
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig_index, lig_index.data(), lig_index.size(), c.s);
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->sphere, lb.sphere.data(), lb.sphere.size(), c.s);
+        if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig_index, lb.index.data(), lb.index.size(), c.s);
         if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig_class, lig_class.data(), lig_class.size(), c.s);
         if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig_exp, lexp_s.data(), lexp_s.size(), c.s);
         if (e == hipSuccess) e = sf->pool.upload_async(&sf->dirs, dirs.data(), dirs.size(), c.s);
@@ -1947,13 +1763,10 @@ extern "C" int dfm_pose_bsa_chunked(dfm_surface *sf, int P, const float *rot, co
     const int want = chunk_poses > 0 ? chunk_poses : sf->chunk_poses;
     const int fill = (int)std::min<size_t>(STERICS_MAX_CHUNK, std::max<size_t>(1, SURFACE_CHUNK_BYTES / per_pose));
     const int Pc = std::min(P, want > 0 ? std::min(want, STERICS_MAX_CHUNK) : fill);
-    float *d_rot = nullptr, *d_tr = nullptr;
-    double *T = nullptr;
+    PoseChunks ch{c, rot, tr};
     int32_t *d_cls = nullptr, *d_lb = nullptr, *d_rb = nullptr;
     uint64_t *d_mask = nullptr;
-    HIPCHK(c.tmp.alloc(&d_rot, (size_t)Pc * 3));
-    HIPCHK(c.tmp.alloc(&d_tr, (size_t)Pc * 3));
-    HIPCHK(c.tmp.alloc(&T, (size_t)Pc * 12));
+    HIPCHK(ch.open(Pc));
     HIPCHK(c.tmp.alloc(&d_cls, (size_t)Pc * 32));
     HIPCHK(c.tmp.alloc(&d_mask, (size_t)Pc * Ar * G));
     if (out->lig_buried) HIPCHK(c.tmp.alloc(&d_lb, (size_t)Pc * Al));
@@ -1966,25 +1779,18 @@ extern "C" int dfm_pose_bsa_chunked(dfm_surface *sf, int P, const float *rot, co
         const double R = (double)sf->class_radius[k] + (double)sf->probe;
         area[k] = 4.0 * M_PI * R * R / sf->K;
     }
-    double copy_ms = 0.0, kernel_ms = 0.0;
     for (int p0 = 0; p0 < P; p0 += Pc) {
         const int n = std::min(Pc, P - p0);
-        HIPCHK(hipEventRecord(c.ev[0], c.s));
-        HIPCHK(hipMemcpyAsync(d_rot, rot + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s));
-        HIPCHK(hipMemcpyAsync(d_tr, tr + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s));
-        HIPCHK(hipEventRecord(c.ev[1], c.s));
+        HIPCHK(ch.upload(p0, n));
         HIPCHK(hipMemsetAsync(d_mask, 0, (size_t)n * Ar * G * sizeof(uint64_t), c.s));
         if (d_lb) HIPCHK(hipMemsetAsync(d_lb, 0, (size_t)n * Al * sizeof(int32_t), c.s));
-        HIPCHK(launch_surface_pose(d_rot, d_tr, n, T, d_cls, c.s));
-        HIPCHK(launch_surface(at, T, n, d_mask, d_lb, d_rb, d_cls, c.s));
-        HIPCHK(hipEventRecord(c.ev[2], c.s));
+        HIPCHK(launch_surface_pose(ch.d_rot, ch.d_tr, n, ch.T, d_cls, c.s));
+        HIPCHK(launch_surface(at, ch.T, n, d_mask, d_lb, d_rb, d_cls, c.s));
+        HIPCHK(ch.kernels_done());
         HIPCHK(hipMemcpyAsync(h_cls.data(), d_cls, (size_t)n * 32 * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
         if (d_lb) HIPCHK(hipMemcpyAsync(out->lig_buried + (size_t)p0 * Al, d_lb, (size_t)n * Al * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
         if (d_rb) HIPCHK(hipMemcpyAsync(out->rec_buried + (size_t)p0 * Ar, d_rb, (size_t)n * Ar * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        HIPCHK(hipStreamSynchronize(c.s));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) copy_ms += ms;
-        if (hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess) kernel_ms += ms;
+        HIPCHK(ch.finish());
         for (int p = 0; p < n; ++p) {
             const int32_t *cp = h_cls.data() + (size_t)p * 32;
             int32_t side[2] = {0, 0};
@@ -2000,8 +1806,7 @@ extern "C" int dfm_pose_bsa_chunked(dfm_surface *sf, int P, const float *rot, co
             if (out->bsa) out->bsa[p0 + p] = s;
         }
     }
-    g_bsa_ms[0] = copy_ms;
-    g_bsa_ms[1] = kernel_ms;
+    set_last_ms(MS_BSA, ch.copy_ms, ch.kernel_ms);
     return DFM_OK;
 }
 
@@ -2012,10 +1817,7 @@ extern "C" int dfm_pose_bsa(dfm_surface *s, int P, const float *rot, const float
 
 extern "C" int dfm_bsa_last_timing(double *copy_ms, double *kernel_ms)
 {
-    if (!copy_ms || !kernel_ms) return fail(DFM_E_INVALID, "NULL argument");
-    *copy_ms = g_bsa_ms[0];
-    *kernel_ms = g_bsa_ms[1];
-    return DFM_OK;
+    return last_timing(MS_BSA, copy_ms, kernel_ms);
 }
 
 extern "C" int dfm_complex_degree(const dfm_complex *cx) { return cx ? cx->K : -1; }

@@ -8,6 +8,7 @@
 #include <atomic>
 
 #include "../../include/dfmdock_amd.h"
+#include "dfm_walkgrid.h"
 
 namespace dfm {
 
@@ -418,14 +419,12 @@ hipError_t launch_contact_score(const uint64_t *bits, const int32_t *count, int 
                                 hipStream_t s);
 
 // all-atom clash / contact screen (kernels_sterics.hip; include/dfmdock_amd.h: dfm_atoms_create / dfm_pose_sterics).  What the atoms alone
-// fix: the receptor's bounding box lo / hi (= the grid's origin and extent), the grid of nx x ny x nz cells of edge `edge` (the contact
-// cutoff), the rotation centre, the cutoffs widened to double, the fp32 reject threshold squared and `grow` = that threshold as a double
-// (the cutoff plus the rounding slack derived in kernels_sterics.hip), by which every box test is widened.
+// fix: the receptor's grid of cells of the contact cutoff (dfm_walkgrid.h: WalkGrid), the cutoffs widened to double and the fp32 reject
+// threshold squared; g.grow is that threshold as a double (the cutoff plus the rounding slack derived in dfm_posewalk.h).
 struct StericsConst {
-    double lo[3], hi[3], center[3];
-    double edge, clash, contact, grow;
+    WalkGrid g;
+    double clash, contact;
     float reject2;
-    int nx, ny, nz;
 };
 // device arrays of a dfm_atoms: rec [Ar] float4 sorted by cell (w unused), cell_start [nx ny nz + 1], lig [Al] float4 in Morton order of the
 // ligand's own cells, lig_index [Al] = each sorted atom's index in the caller's order, sphere [ceil(Al / 64)] float4 = centre (relative to
@@ -445,14 +444,14 @@ hipError_t launch_sterics(const StericsAtoms &at, const double *T, int n, int32_
                           int32_t *lig_clash, int32_t *lig_contact, uint64_t *exits, hipStream_t s);
 
 // buried surface area (kernels_surface.hip; include/dfmdock_amd.h: dfm_surface_create / dfm_pose_bsa).  What the atoms alone fix: the
-// receptor's bounding box lo / hi (= the grid's origin and extent), the grid of nx x ny x nz cells of edge `edge` (at least the largest
-// R_a + R_b), the rotation centre, the probe widened to double, `slack` of the fp32 pair test d2 > ((R_a + R_b) 1.0001 + slack)^2 and
-// `grow` = that threshold for the largest radii as a double, by which every box test is widened; G = K / 64 groups of sphere points.
+// receptor's grid (dfm_walkgrid.h: WalkGrid) of cells whose edge is at least the largest R_a + R_b, the probe widened to double and
+// `slack` of the fp32 pair test d2 > ((R_a + R_b) 1.0001 + slack)^2; g.grow is that threshold for the largest radii as a double;
+// G = K / 64 groups of sphere points.
 struct SurfaceConst {
-    double lo[3], hi[3], center[3];
-    double edge, grow, probe;
+    WalkGrid g;
+    double probe;
     float slack;
-    int nx, ny, nz, G;
+    int G;
 };
 // device arrays of a dfm_surface: rec [Ar] float4 sorted by cell (w = radius), cell_start [nx ny nz + 1], lig [Al] float4 in Morton order
 // of the ligand's own cells (w = radius), sphere [ceil(Al / 64)] float4 as in StericsAtoms; per sorted atom its index in the caller's

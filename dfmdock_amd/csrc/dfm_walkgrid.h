@@ -1,0 +1,33 @@
+// dfm_walkgrid.h - the receptor's cell grid of the per-pose all-atom calls and its binning formula, in plain C++: the host builds the
+// grid with them (dfm_poseprep.h), the kernels walk it (dfm_posewalk.h).
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#define DFM_HOST_DEVICE __host__ __device__
+#else
+#define DFM_HOST_DEVICE
+#endif
+
+namespace dfm {
+
+// the receptor's bounding box lo / hi (= the grid's origin and extent), the rotation centre, the grid of nx x ny x nz cells of edge
+// `edge`, and `grow`, by which every box test is widened
+struct WalkGrid {
+    double lo[3], hi[3], center[3];
+    double edge, grow;
+    int nx, ny, nz;
+};
+
+// cell coordinate of x along one axis, clamped to the grid: the one binning formula of host and device
+DFM_HOST_DEVICE inline int cell_of(double x, double origin, double edge, int n)
+{
+    double c = floor((x - origin) / edge);
+    c = c < 0.0 ? 0.0 : (c > (double)(n - 1) ? (double)(n - 1) : c);
+    return (int)c;
+}
+
+}  // namespace dfm

@@ -13,11 +13,11 @@
 // least the largest R_a + R_b, with the cell starts, each sorted atom's index in the caller's order, radius class and K-bit exposure mask;
 // the ligand atoms sorted by the Morton code of their cell, in blocks of 64 with a bounding sphere each, with the same per-atom arrays.
 //
-//   k_surface_pose    one lane per pose: R(rot) and tr as 12 doubles (k_sterics_pose's arithmetic), zeroes the pose's class counters.
-//   k_surface         one wave per (pose, block of 64 ligand atoms); the early exits and the receptor cell walk of k_sterics.
+//   k_surface_pose    one lane per pose: the pose as 12 doubles (dfm_posewalk.h: pose_transform), zeroes the pose's class counters.
+//   k_surface         one wave per (pose, block of 64 ligand atoms); the early exits and the staged receptor cell walk of dfm_posewalk.h.
 //                     phase A  lanes are ATOMS.  Each receptor atom of the block's cell range, staged through LDS, is tested against the
 //                              lane's atom in fp32: a pair passes unless d2 > ((R_a + R_b) 1.0001 + slack)^2.  A point of a lies R_a from
-//                              x_a, so b can hold it only when |x_a - c_b| < R_a + R_b; slack (kernels_sterics.hip derives it: max(1e-3,
+//                              x_a, so b can hold it only when |x_a - c_b| < R_a + R_b; slack (dfm_posewalk.h derives it: max(1e-3,
 //                              2.5e-7 maxabs)) and the factor cover the fp32 rounding, so no pair that buries anything is dropped.
 //                              Passing pairs (a, b) go to an LDS queue through a ballot and a prefix count.
 //                     phase B  when the queue is nearly full and at the end: lanes are POINTS.  For each queued pair and each group of 64
@@ -29,6 +29,7 @@
 //                     the end  lanes are atoms again: popcount of the block's masks -> lig_buried, integer atomics per radius class.
 //   k_surface_finish  one lane per (pose, receptor atom): popcount of its mask -> rec_buried, integer atomics per radius class.
 #include "dfm_internal.h"
+#include "dfm_posewalk.h"
 
 #include <algorithm>
 #include <cmath>
@@ -39,32 +40,6 @@ namespace dfm {
 namespace {
 
 constexpr int QCAP = 512;      // queue entries; drained when fewer than 64 are free
-
-__device__ inline double wave_min(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        const double w = __shfl_xor(v, o);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
-__device__ inline double wave_max(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        const double w = __shfl_xor(v, o);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
-// cell coordinate of x along one axis, clamped to the grid: the host's binning formula
-__device__ inline int cell_of(double x, double origin, double edge, int n)
-{
-    double c = floor((x - origin) / edge);
-    c = c < 0.0 ? 0.0 : (c > (double)(n - 1) ? (double)(n - 1) : c);
-    return (int)c;
-}
 
 // phase B for the qn queued pairs of pose p.  s_x: X | Y | Z | R of the block's 64 atoms, s_w / s_u: the rotated and the plain sphere
 // points as x | y | z rows of 256, s_bur [64][4]: the block's buried masks.  Wave-uniform control flow throughout.
@@ -108,16 +83,7 @@ __global__ __launch_bounds__(64) void k_surface_pose(const float *__restrict__ r
 {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= n) return;
-    const double x = (double)rot[3 * p], y = (double)rot[3 * p + 1], z = (double)rot[3 * p + 2];
-    const double ang = sqrt((x * x + y * y) + z * z);
-    const double s = fabs(ang) < 1e-6 ? 0.5 - ang * ang / 48.0 : sin(0.5 * ang) / ang;
-    const double r = cos(0.5 * ang), i = x * s, j = y * s, k = z * s;
-    const double two_s = 2.0 / (((r * r + i * i) + j * j) + k * k);
-    double *__restrict__ t = T + (int64_t)p * 12;
-    t[0] = 1.0 - two_s * (j * j + k * k); t[1] = two_s * (i * j - k * r);       t[2] = two_s * (i * k + j * r);
-    t[3] = two_s * (i * j + k * r);       t[4] = 1.0 - two_s * (i * i + k * k); t[5] = two_s * (j * k - i * r);
-    t[6] = two_s * (i * k - j * r);       t[7] = two_s * (j * k + i * r);       t[8] = 1.0 - two_s * (i * i + j * j);
-    t[9] = (double)tr[3 * p]; t[10] = (double)tr[3 * p + 1]; t[11] = (double)tr[3 * p + 2];
+    pose_transform(rot, tr, p, T);
     for (int c = 0; c < 32; ++c) class_points[(int64_t)p * 32 + c] = 0;
 }
 
@@ -133,44 +99,12 @@ __global__ __launch_bounds__(64) void k_surface(SurfaceAtoms at, const double *_
     __shared__ unsigned long long s_bur[64 * 4];
     __shared__ uint32_t s_q[QCAP];
     const SurfaceConst &sc = at.sc;
-    const int lane = threadIdx.x, blk = blockIdx.x, p = blockIdx.y, Al = at.Al, G = sc.G;
-    double t[12], chk = 0.0;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-        t[k] = T[(int64_t)p * 12 + k];
-        chk += t[k] * 0.0;
-    }
-    if (chk != chk) return;      // a NaN or infinite transform: nothing is buried
-    {
-        const float4 bs = reinterpret_cast<const float4 *>(at.sphere)[blk];
-        const double qx = (double)bs.x, qy = (double)bs.y, qz = (double)bs.z, reach = (double)bs.w + sc.grow;
-        const double cx = ((qx * t[0] + qy * t[1]) + qz * t[2]) + sc.center[0] + t[9];
-        const double cy = ((qx * t[3] + qy * t[4]) + qz * t[5]) + sc.center[1] + t[10];
-        const double cz = ((qx * t[6] + qy * t[7]) + qz * t[8]) + sc.center[2] + t[11];
-        const double ex = cx < sc.lo[0] ? sc.lo[0] - cx : (cx > sc.hi[0] ? cx - sc.hi[0] : 0.0);
-        const double ey = cy < sc.lo[1] ? sc.lo[1] - cy : (cy > sc.hi[1] ? cy - sc.hi[1] : 0.0);
-        const double ez = cz < sc.lo[2] ? sc.lo[2] - cz : (cz > sc.hi[2] ? cz - sc.hi[2] : 0.0);
-        if ((ex * ex + ey * ey) + ez * ez > reach * reach) return;
-    }
-    const int a = blk * 64 + lane;
-    const bool valid = a < Al;
-    const float4 l4 = reinterpret_cast<const float4 *>(at.lig)[valid ? a : Al - 1];
-    const double qx = (double)l4.x - sc.center[0], qy = (double)l4.y - sc.center[1], qz = (double)l4.z - sc.center[2];
-    const double X = ((qx * t[0] + qy * t[1]) + qz * t[2]) + sc.center[0] + t[9];
-    const double Y = ((qx * t[3] + qy * t[4]) + qz * t[5]) + sc.center[1] + t[10];
-    const double Z = ((qx * t[6] + qy * t[7]) + qz * t[8]) + sc.center[2] + t[11];
-    const double Ra = (double)l4.w + sc.probe;
-    // (the lanes past Al repeat the last atom: they change no minimum or maximum)
-    const double x0 = wave_min(X) - sc.grow, x1 = wave_max(X) + sc.grow;
-    const double y0 = wave_min(Y) - sc.grow, y1 = wave_max(Y) + sc.grow;
-    const double z0 = wave_min(Z) - sc.grow, z1 = wave_max(Z) + sc.grow;
-    if (x0 > sc.hi[0] || x1 < sc.lo[0] || y0 > sc.hi[1] || y1 < sc.lo[1] || z0 > sc.hi[2] || z1 < sc.lo[2]) return;
-    const int cx0 = __builtin_amdgcn_readfirstlane(cell_of(x0, sc.lo[0], sc.edge, sc.nx));
-    const int cx1 = __builtin_amdgcn_readfirstlane(cell_of(x1, sc.lo[0], sc.edge, sc.nx));
-    const int cy0 = __builtin_amdgcn_readfirstlane(cell_of(y0, sc.lo[1], sc.edge, sc.ny));
-    const int cy1 = __builtin_amdgcn_readfirstlane(cell_of(y1, sc.lo[1], sc.edge, sc.ny));
-    const int cz0 = __builtin_amdgcn_readfirstlane(cell_of(z0, sc.lo[2], sc.edge, sc.nz));
-    const int cz1 = __builtin_amdgcn_readfirstlane(cell_of(z1, sc.lo[2], sc.edge, sc.nz));
+    const int lane = threadIdx.x, blk = blockIdx.x, p = blockIdx.y, Al = at.Al, G = sc.G, a = blk * 64 + lane;
+    WalkBlock w;
+    // a NaN or infinite transform, a block out of reach of the receptor: nothing is buried
+    if (!walk_front(sc.g, T, reinterpret_cast<const float4 *>(at.sphere), reinterpret_cast<const float4 *>(at.lig), Al, nullptr, w)) return;
+    const bool valid = w.valid;
+    const double *t = w.t, X = w.X, Y = w.Y, Z = w.Z, Ra = (double)w.l4.w + sc.probe;
     // the block's atoms and the pose's sphere points, for the lanes-are-points phase
     s_x[lane] = X; s_x[64 + lane] = Y; s_x[128 + lane] = Z; s_x[192 + lane] = Ra;
     for (int g = 0; g < 4; ++g) s_bur[lane * 4 + g] = 0ull;
@@ -184,34 +118,22 @@ __global__ __launch_bounds__(64) void k_surface(SurfaceAtoms at, const double *_
     }
     const float xf = (float)X, yf = (float)Y, zf = (float)Z, raf = (float)Ra, probef = (float)sc.probe;
     int qn = 0;
-    for (int cz = cz0; cz <= cz1; ++cz)
-        for (int cy = cy0; cy <= cy1; ++cy) {
-            const int row = (cz * sc.ny + cy) * sc.nx;
-            const int b0 = at.cell_start[row + cx0], b1 = at.cell_start[row + cx1 + 1];
-            for (int base = b0; base < b1; base += 64) {
-                const int cnt = b1 - base < 64 ? b1 - base : 64;
-                __syncthreads();      // the previous batch has been read
-                if (lane < cnt) s_rec[lane] = reinterpret_cast<const float4 *>(at.rec)[base + lane];
-                __syncthreads();
-                for (int j = 0; j < cnt; ++j) {
-                    const float4 r = s_rec[j];
-                    const float dx = r.x - xf, dy = r.y - yf, dz = r.z - zf;
-                    const float d2 = (dx * dx + dy * dy) + dz * dz;
-                    const float lim = (raf + (r.w + probef)) * 1.0001f + sc.slack;
-                    const bool close_by = valid && !(d2 > lim * lim);
-                    const unsigned long long m = __ballot(close_by);
-                    if (m) {
-                        const int at_q = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                        if (close_by) s_q[at_q] = ((uint32_t)lane << 24) | (uint32_t)(base + j);
-                        qn += __popcll(m);
-                        if (qn > QCAP - 64) {
-                            drain(at, G, blk, (int64_t)p, lane, qn, s_q, s_x, s_w, s_u, s_bur, rec_bur);
-                            qn = 0;
-                        }
-                    }
-                }
+    walk_rows(sc.g, w, at.cell_start, reinterpret_cast<const float4 *>(at.rec), s_rec, [&](int b, const float4 r) {
+        const float dx = r.x - xf, dy = r.y - yf, dz = r.z - zf;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        const float lim = (raf + (r.w + probef)) * 1.0001f + sc.slack;
+        const bool close_by = valid && !(d2 > lim * lim);
+        const unsigned long long m = __ballot(close_by);
+        if (m) {
+            const int at_q = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            if (close_by) s_q[at_q] = ((uint32_t)lane << 24) | (uint32_t)b;
+            qn += __popcll(m);
+            if (qn > QCAP - 64) {
+                drain(at, G, blk, (int64_t)p, lane, qn, s_q, s_x, s_w, s_u, s_bur, rec_bur);
+                qn = 0;
             }
         }
+    });
     drain(at, G, blk, (int64_t)p, lane, qn, s_q, s_x, s_w, s_u, s_bur, rec_bur);
     if (valid) {
         int n = 0;
@@ -263,11 +185,7 @@ void surface_exposure(int n, const float *xyz, const float *radius, double probe
                       const int dims[3], double edge, double pad, const int32_t *start, const int32_t *order, uint64_t *mask)
 {
     const int G = K / 64;
-    auto cell1 = [&](double x, int k) {
-        double c = std::floor((x - lo[k]) / edge);
-        c = c < 0.0 ? 0.0 : (c > (double)(dims[k] - 1) ? (double)(dims[k] - 1) : c);
-        return (int)c;
-    };
+    auto cell1 = [&](double x, int k) { return cell_of(x, lo[k], edge, dims[k]); };
     std::vector<std::pair<double, int>> cand;
     for (int i = 0; i < n; ++i) {
         const double cx = (double)xyz[(size_t)i * 3], cy = (double)xyz[(size_t)i * 3 + 1], cz = (double)xyz[(size_t)i * 3 + 2];

@@ -218,21 +218,19 @@ class Model:
         return Surface(self, rec_atoms, rec_radius, lig_atoms, lig_radius, center, probe, points)
 
 
-class Native:
-    """A native pose resident on the model's GPU (dfm_native): interface residues, native contacts and the receptor's share of the
-    Kabsch sums, computed once.  Read-only after creation: `metrics` may be called from several threads at once."""
+class _Handle:
+    """What Native, Atoms and Surface share: a handle `_h` made by dfm_<_kind>_create and freed by dfm_<_kind>_destroy - close(), a context
+    manager, closed when collected."""
+    _kind = None
 
-    def __init__(self, model: Model, rec_pos, lig_pos, iface_cutoff=10.0, contact_cutoff=5.5):
-        rp, lp = _f32(rec_pos).reshape(-1, 9), _f32(lig_pos).reshape(-1, 9)
-        self.model, self.R, self.L = model, rp.shape[0], lp.shape[0]
-        self._h = L.lib().dfm_native_create(model._h, _p(rp), _p(lp), self.R, self.L, float(iface_cutoff), float(contact_cutoff))
+    def _created(self):
         if not self._h:
-            msg = L.lib().dfm_last_error()
-            L.check(-2 if msg.startswith((b"dfm_native_create", b"hipSetDevice")) else -1, "dfm_native_create")      # else: bad argument
+            name = f"dfm_{self._kind}_create"
+            L.check(-2 if L.lib().dfm_last_error().startswith((name.encode(), b"hipSetDevice")) else -1, name)      # else: bad argument
 
     def close(self):
         if getattr(self, "_h", None):
-            L.lib().dfm_native_destroy(self._h)
+            getattr(L.lib(), f"dfm_{self._kind}_destroy")(self._h)
             self._h = None
 
     def __enter__(self):
@@ -247,6 +245,26 @@ class Native:
             self.close()
         except Exception:
             pass
+
+
+def _rigid_poses(rot, tr):
+    """rot, tr as float32 [P,3] and P: the poses of Atoms.sterics and Surface.bsa."""
+    r, t = _f32(rot).reshape(-1, 3), _f32(tr).reshape(-1, 3)
+    if r.shape != t.shape or r.shape[0] < 1:
+        raise ValueError(f"rot and tr must both be [P,3] with P >= 1, got {np.shape(rot)} and {np.shape(tr)}")
+    return r, t, r.shape[0]
+
+
+class Native(_Handle):
+    """A native pose resident on the model's GPU (dfm_native): interface residues, native contacts and the receptor's share of the
+    Kabsch sums, computed once.  Read-only after creation: `metrics` may be called from several threads at once."""
+    _kind = "native"
+
+    def __init__(self, model: Model, rec_pos, lig_pos, iface_cutoff=10.0, contact_cutoff=5.5):
+        rp, lp = _f32(rec_pos).reshape(-1, 9), _f32(lig_pos).reshape(-1, 9)
+        self.model, self.R, self.L = model, rp.shape[0], lp.shape[0]
+        self._h = L.lib().dfm_native_create(model._h, _p(rp), _p(lp), self.R, self.L, float(iface_cutoff), float(contact_cutoff))
+        self._created()
 
     def info(self):
         """{n_iface_rec, n_iface_lig, n_contacts, iface_rec, iface_lig (ascending residue indices), contacts [n,2] (receptor, ligand)}:
@@ -285,9 +303,10 @@ class Native:
         return o
 
 
-class Atoms:
+class Atoms(_Handle):
     """The heavy atoms of a receptor / ligand pair resident on the model's GPU (dfm_atoms): the receptor binned into a cell grid, the
     ligand in blocks of neighbours.  Read-only after creation: `sterics` may be called from several threads at once."""
+    _kind = "atoms"
 
     def __init__(self, model: Model, rec_atoms, lig_atoms, center, clash_cutoff=3.0, contact_cutoff=5.0):
         ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _f32(center).reshape(-1)
@@ -297,27 +316,7 @@ class Atoms:
         self.clash_cutoff, self.contact_cutoff = float(np.float32(clash_cutoff)), float(np.float32(contact_cutoff))
         prm = L.StericsParamsC(float(clash_cutoff), float(contact_cutoff), 0)
         self._h = L.lib().dfm_atoms_create(model._h, self.Ar, _p(ra), self.Al, _p(la), _p(cen), C.byref(prm))
-        if not self._h:
-            msg = L.lib().dfm_last_error()
-            L.check(-2 if msg.startswith((b"dfm_atoms_create", b"hipSetDevice")) else -1, "dfm_atoms_create")      # else: bad argument
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib().dfm_atoms_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._created()
 
     def info(self):
         """{n_cells, max_cell_atoms, cell_edge} of the receptor's grid (dfm_atoms_info)."""
@@ -331,10 +330,7 @@ class Atoms:
         contact)}, with `per_atom` lig_clash / lig_contact (int32 [P,Al], the caller's atom order), and CAPRI's rule over `members`
         (bool [P]; None: every pose) from sterics.capri_flags: flags (bool [P]), threshold, ensemble_mean, ensemble_std."""
         from . import sterics as ST
-        r, t = _f32(rot).reshape(-1, 3), _f32(tr).reshape(-1, 3)
-        if r.shape != t.shape or r.shape[0] < 1:
-            raise ValueError(f"rot and tr must both be [P,3] with P >= 1, got {np.shape(rot)} and {np.shape(tr)}")
-        P = r.shape[0]
+        r, t, P = _rigid_poses(rot, tr)
         o = {"n_clash": np.zeros(P, np.int32), "n_contact": np.zeros(P, np.int32), "min_dist": np.zeros(P, np.float64)}
         out = L.StericsOutC()
         out.n_clash, out.n_contact = _p(o["n_clash"], L.I32P), _p(o["n_contact"], L.I32P)
@@ -347,9 +343,10 @@ class Atoms:
         return o
 
 
-class Surface:
+class Surface(_Handle):
     """The heavy atoms of a receptor / ligand pair with their isolated exposure masks resident on the model's GPU (dfm_surface).
     Read-only after creation: `bsa` may be called from several threads at once."""
+    _kind = "surface"
 
     def __init__(self, model: Model, rec_atoms, rec_radius, lig_atoms, lig_radius, center, probe=1.4, points=128):
         from . import surface as SF
@@ -364,28 +361,8 @@ class Surface:
         dirs = SF.sphere_points(self.K)
         prm = L.SurfaceParamsC(float(probe), self.K, _p(dirs), 0)
         self._h = L.lib().dfm_surface_create(model._h, self.Ar, _p(ra), _p(rr), self.Al, _p(la), _p(lr), _p(cen), C.byref(prm))
-        if not self._h:
-            msg = L.lib().dfm_last_error()
-            L.check(-2 if msg.startswith((b"dfm_surface_create", b"hipSetDevice")) else -1, "dfm_surface_create")      # else: bad argument
+        self._created()
         self.class_radius = self.info()["class_radius"]
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib().dfm_surface_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self):
         """{sasa_rec, sasa_lig (A^2 in isolation), rec_exposed [Ar], lig_exposed [Al] (exposed points per atom), class_radius (float32,
@@ -405,10 +382,7 @@ class Surface:
         (int32 [P,2,16])}, with `per_atom` lig_buried [P,Al] / rec_buried [P,Ar] (int32 points, the caller's atom order), and
         bsa_rec / bsa_lig (float64 [P]): the two sides (surface.side_areas)."""
         from . import surface as SF
-        r, t = _f32(rot).reshape(-1, 3), _f32(tr).reshape(-1, 3)
-        if r.shape != t.shape or r.shape[0] < 1:
-            raise ValueError(f"rot and tr must both be [P,3] with P >= 1, got {np.shape(rot)} and {np.shape(tr)}")
-        P = r.shape[0]
+        r, t, P = _rigid_poses(rot, tr)
         o = {"bsa": np.zeros(P, np.float64), "lig_points": np.zeros(P, np.int32), "rec_points": np.zeros(P, np.int32),
              "class_points": np.zeros((P, 2, 16), np.int32)}
         out = L.BsaOutC()
