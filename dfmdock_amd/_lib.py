@@ -39,7 +39,7 @@ EXPORTS = [
     "dfm_last_error", "dfm_config_string", "dfm_device_count", "dfm_set_device", "dfm_default_hparams", "dfm_param_count",
     "dfm_model_create", "dfm_model_destroy", "dfm_complex_create", "dfm_complex_destroy", "dfm_complex_degree",
     "dfm_complex_set_pose", "dfm_complex_set_homomer",
-    "dfm_score", "dfm_sample", "dfm_get_profile", "dfm_diffusion_coef", "dfm_complex_selfcheck", "dfm_trim_cache",
+    "dfm_score", "dfm_sample", "dfm_get_profile", "dfm_diffusion_coef", "dfm_complex_selfcheck", "dfm_trim_cache", "dfm_alloc_diag",
     "dfm_complex_set_restraints", "dfm_restraint_eval", "dfm_pose_rmsd", "dfm_pose_cluster", "dfm_pose_last_timing",
     "dfm_refine", "dfm_forward_marginal", "dfm_igso3_table",
     "dfm_native_create", "dfm_native_destroy", "dfm_native_info", "dfm_pose_metrics", "dfm_metrics_last_timing",
@@ -208,6 +208,7 @@ def lib():
     L.dfm_bsa_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_trim_cache.argtypes = [C.c_int]
     L.dfm_trim_cache.restype = C.c_longlong
+    L.dfm_alloc_diag.argtypes = [C.POINTER(C.c_int64)]
     L.dfm_diffusion_coef.argtypes = [C.POINTER(HParamsC), C.c_int, C.c_double, C.POINTER(C.c_double),
                                      C.POINTER(C.c_double)]
     _lib = L

@@ -2,6 +2,7 @@
 // kernel schedule and the Euler-Maruyama loop.  Everything runs on one HIP stream per complex handle;
 // the host only enqueues (no sync inside the 40-step loop).
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "dfm_device.h"
+#include "dfm_guardscan.h"
 #include "dfm_internal.h"
 #include "dfm_poseprep.h"
 
@@ -119,6 +121,18 @@ static size_t guard_bytes()
     static const size_t g = [] { const char *e = getenv("DFM_ALLOC_GUARD"); return e ? (size_t)atoi(e) * 1024 : (size_t)0; }();
     return g;
 }
+static int alloc_poison()      // DFM_ALLOC_POISON=<byte>: -1 when not set
+{
+    static const int poison = [] { const char *e = getenv("DFM_ALLOC_POISON"); return e ? atoi(e) & 255 : -1; }();
+    return poison;
+}
+// what the two diagnostics did in this process (dfm_alloc_diag): blocks handed out, bytes filled with the poison byte, guard bands
+// checked at release and found damaged, and the first damaged block: its size and the damaged byte's offset from the block's start
+// (negative in the head band, >= size in the tail band)
+struct AllocDiag {
+    std::atomic<int64_t> blocks{0}, poisoned{0}, bands{0}, damaged{0}, first_size{-1}, first_off{-1};
+};
+static AllocDiag g_alloc_diag;
 struct DevPool {
     struct Block { void *p; size_t size; int dev; };
     std::vector<Block> ptrs;
@@ -139,12 +153,16 @@ struct DevPool {
                 unsigned char *base = reinterpret_cast<unsigned char *>(b.p) - G;
                 for (int side = 0; side < 2; ++side) {
                     (void)hipMemcpy(h.data(), side ? base + G + b.size : base, G, hipMemcpyDeviceToHost);
-                    for (size_t k = 0; k < G; ++k)
-                        if (h[k] != 0xA5) {
-                            fprintf(stderr, "DFM_ALLOC_GUARD: block of %zu bytes: %s guard damaged at offset %zu (byte 0x%02x)\n", b.size,
-                                    side ? "TAIL" : "HEAD", k, h[k]);
-                            break;
+                    const size_t k = guard_first_damaged(h.data(), G);
+                    g_alloc_diag.bands.fetch_add(1, std::memory_order_relaxed);
+                    if (k < G) {
+                        fprintf(stderr, "DFM_ALLOC_GUARD: block of %zu bytes: %s guard damaged at offset %zu (byte 0x%02x)\n", b.size,
+                                side ? "TAIL" : "HEAD", k, h[k]);
+                        if (g_alloc_diag.damaged.fetch_add(1, std::memory_order_relaxed) == 0) {
+                            g_alloc_diag.first_size.store((int64_t)b.size, std::memory_order_relaxed);
+                            g_alloc_diag.first_off.store(side ? (int64_t)(b.size + k) : (int64_t)k - (int64_t)G, std::memory_order_relaxed);
                         }
+                    }
                 }
                 (void)hipFree(base);
             }
@@ -178,13 +196,19 @@ struct DevPool {
         int dev = -1;
         (void)hipGetDevice(&dev);
         void *p = nullptr;
+        const int poison = alloc_poison();
         if (const size_t G = guard_bytes()) {
             unsigned char *base = nullptr;
             hipError_t e = hipMalloc(reinterpret_cast<void **>(&base), bytes + 2 * G);
             if (e != hipSuccess) return e;
-            (void)hipMemset(base, 0xA5, G); (void)hipMemset(base + G + bytes, 0xA5, G);
+            (void)hipMemset(base, GUARD_BYTE, G); (void)hipMemset(base + G + bytes, GUARD_BYTE, G);
+            if (poison >= 0) {      // the payload too: a guarded block is exact-size and fresh, its contents whatever the driver left
+                (void)hipMemset(base + G, poison, bytes);
+                g_alloc_diag.poisoned.fetch_add((int64_t)bytes, std::memory_order_relaxed);
+            }
             (void)hipDeviceSynchronize();
             ptrs.push_back({base + G, bytes, dev});
+            g_alloc_diag.blocks.fetch_add(1, std::memory_order_relaxed);
             *out = reinterpret_cast<T *>(base + G);
             return hipSuccess;
         }
@@ -220,13 +244,20 @@ struct DevPool {
             if (e != hipSuccess) return e;
         }
         ptrs.push_back({p, bytes, dev});
+        g_alloc_diag.blocks.fetch_add(1, std::memory_order_relaxed);
         *out = reinterpret_cast<T *>(p);
         // diagnostic: DFM_ALLOC_POISON=<byte> fills every block handed out (fresh or from the cache) with that byte - 255 = NaN
         // patterns in fp32 / fp16 - so that a kernel reading memory nobody wrote shows up as a changed or non-finite result
-        static const int poison = [] { const char *e = getenv("DFM_ALLOC_POISON"); return e ? atoi(e) & 255 : -1; }();
         if (poison >= 0) {
-            hipError_t e = bound ? hipMemsetAsync(p, poison, bytes, owner) : hipMemset(p, poison, bytes);
+            // The fill is waited for, on the pool's own stream or on the null stream.  What is written into the block next need not be
+            // in that stream's order - upload() copies synchronously, upload_async() on whichever (non-blocking) stream the caller
+            // names, and a memset of device memory may return before it has run - and a fill that lands afterwards replaces the data:
+            // the one-byte-per-residue interface flags of dfm_native_create became "every residue" that way.
+            const hipStream_t fs = bound ? owner : nullptr;
+            hipError_t e = hipMemsetAsync(p, poison, bytes, fs);
+            if (e == hipSuccess) e = hipStreamSynchronize(fs);
             if (e != hipSuccess) return e;
+            g_alloc_diag.poisoned.fetch_add((int64_t)bytes, std::memory_order_relaxed);
         }
         return hipSuccess;
     }
@@ -1826,6 +1857,16 @@ extern "C" long long dfm_trim_cache(int device)
 {
     if (device >= MAX_DEVICES) return 0;      // no such device: nothing parked there (a negative index means every device)
     return (long long)g_block_cache.trim(device < 0 ? -1 : device);
+}
+
+extern "C" int dfm_alloc_diag(int64_t out[6])
+{
+    if (!out) return fail(DFM_E_INVALID, "NULL argument");
+    const AllocDiag &d = g_alloc_diag;
+    out[0] = d.blocks.load(std::memory_order_relaxed); out[1] = d.poisoned.load(std::memory_order_relaxed);
+    out[2] = d.bands.load(std::memory_order_relaxed); out[3] = d.damaged.load(std::memory_order_relaxed);
+    out[4] = d.first_size.load(std::memory_order_relaxed); out[5] = d.first_off.load(std::memory_order_relaxed);
+    return DFM_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -65,6 +65,15 @@ def trim_cache(device: int = -1) -> int:
     return int(L.lib().dfm_trim_cache(int(device)))
 
 
+def alloc_diag() -> dict:
+    """What the allocator diagnostics DFM_ALLOC_POISON / DFM_ALLOC_GUARD did in this process (dfm_alloc_diag): {blocks, poisoned_bytes,
+    bands_checked, bands_damaged, first_damaged_size, first_damaged_offset (both -1 while every band is intact)}."""
+    n = (C.c_int64 * 6)()
+    L.check(L.lib().dfm_alloc_diag(n), "dfm_alloc_diag")
+    return dict(zip(("blocks", "poisoned_bytes", "bands_checked", "bands_damaged", "first_damaged_size", "first_damaged_offset"),
+                    (int(v) for v in n)))
+
+
 def device_count() -> int:
     n = C.c_int(0)
     rc = L.lib().dfm_device_count(C.byref(n))

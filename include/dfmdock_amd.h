@@ -525,6 +525,12 @@ int dfm_complex_degree(const dfm_complex *cx);
  * block of `device` (< 0: all devices; an index past the last device: nothing, returns 0) back to the driver - for processes that
  * share a GPU - and returns the bytes freed. */
 long long dfm_trim_cache(int device);
+/* What the allocator's two diagnostics did in this process so far (DFM_ALLOC_POISON=<byte> fills every device block handed out,
+ * DFM_ALLOC_GUARD=<KiB> puts bands of 0xA5 around it and checks them at release): out[0] blocks handed out, out[1] bytes filled
+ * with the poison byte, out[2] guard bands checked, out[3] guard bands found damaged, out[4] / out[5] the size of the first damaged
+ * block and the damaged byte's offset from the block's start (negative: head band; >= size: tail band), both -1 while no band is
+ * damaged.  Without the variables only out[0] counts. */
+int dfm_alloc_diag(int64_t out[6]);
 
 /* B score evaluations of poses lig_pos[B,L,9] at times t[B] */
 int dfm_score(dfm_complex *cx, int B, const float *lig_pos, const float *t, const int32_t *edges_or_null,
