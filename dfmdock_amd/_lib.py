@@ -47,6 +47,8 @@ EXPORTS = [
     "dfm_atoms_create", "dfm_atoms_destroy", "dfm_atoms_info", "dfm_pose_sterics", "dfm_pose_sterics_chunked", "dfm_sterics_last_timing",
     "dfm_sterics_exit_counts",
     "dfm_surface_create", "dfm_surface_destroy", "dfm_surface_info", "dfm_pose_bsa", "dfm_pose_bsa_chunked", "dfm_bsa_last_timing",
+    "dfm_iface_create", "dfm_iface_destroy", "dfm_iface_info", "dfm_pose_iface_energy", "dfm_pose_iface_energy_chunked",
+    "dfm_iface_last_timing",
 ]
 
 
@@ -131,6 +133,10 @@ class BsaOutC(C.Structure):
                 ("bsa", C.POINTER(C.c_double))]
 
 
+class IfaceOutC(C.Structure):
+    _fields_ = [(n, C.POINTER(C.c_int64)) for n in ("rep_q", "att_q", "elec_q", "n_pairs", "lig_vdw_q", "lig_elec_q")]
+
+
 _lib = None
 
 
@@ -206,6 +212,15 @@ def lib():
     L.dfm_pose_bsa.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.POINTER(BsaOutC)]
     L.dfm_pose_bsa_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(BsaOutC)]
     L.dfm_bsa_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_iface_create.argtypes = [C.c_void_p, C.c_int, F32P, F32P, F32P, F32P, C.c_int, F32P, F32P, F32P, F32P, F32P, C.c_float, C.c_float,
+                                   C.c_float, C.c_float]
+    L.dfm_iface_create.restype = C.c_void_p
+    L.dfm_iface_destroy.argtypes = [C.c_void_p]
+    L.dfm_iface_destroy.restype = None
+    L.dfm_iface_info.argtypes = [C.c_void_p, I32P, I32P, F32P, C.POINTER(C.c_double)]
+    L.dfm_pose_iface_energy.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.POINTER(IfaceOutC)]
+    L.dfm_pose_iface_energy_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(IfaceOutC)]
+    L.dfm_iface_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_trim_cache.argtypes = [C.c_int]
     L.dfm_trim_cache.restype = C.c_longlong
     L.dfm_alloc_diag.argtypes = [C.POINTER(C.c_int64)]

@@ -14,6 +14,7 @@
     python -m dfmdock_amd dock|refine ... --consensus [--rank consensus] [--consensus-top 0.5] [--contact-map map.npz]
     python -m dfmdock_amd dock|refine ... --write-restraints consensus.txt --restraint-top 10 [--restraint-upper 8.0]
     python -m dfmdock_amd sweep ... --consensus [--consensus-top 0.5]
+    python -m dfmdock_amd dock|refine ... --interface-energy [--rank interface] [--ie-weights 0.18 1.0 0.5] [--ie-cutoff 8.0] [--energy-residues FILE]
     python -m dfmdock_amd dock|refine ... --clash-screen [--clash-filter] [--clash-cutoff 3.0] [--contact-cutoff 5.0] [--clash-residues FILE]
 
   dock       <- src/inference_single.py:1-12 -> inference() (src/inference_base.py:601-670): num_samples (120) trajectories of
@@ -60,6 +61,14 @@
              --clash-screen` add a `sterics` object for the kept pose (and for every --top-k model) to the result line and a REMARK line
              with the counts to every written model; `--clash-filter` removes the flagged trajectories before the selection, the
              consensus ranking and the clustering; `--clash-residues FILE` lists the kept model's counts per ligand residue.
+  ifenergy   no reference counterpart: the physics rescoring step of docking pipelines on the GPU (dfmdock_amd/ifenergy.py,
+             dfm_pose_iface_energy) - soft Lennard-Jones plus Coulomb with the dielectric 4 r over the heavy-atom pairs of the two chains
+             within --ie-cutoff (8.0 A), element-wise AMBER-style LJ parameters and formal charges, no hydrogens.  `dock / refine
+             --interface-energy` add an `interface_energy` object (rep, att, elec, total in kcal/mol, pairs, rank) for the kept pose and
+             for every --top-k model; `--rank interface` keeps the pose with the lowest total instead of the minimum energy (and makes
+             the totals the clustering key of --top-k; with --clash-filter the flagged poses are out, as under --rank consensus);
+             total = w_rep rep + w_att att + w_elec elec with --ie-weights (default 0.18 1.0 0.5: ZRANK-like starting values, not
+             fitted); `--energy-residues FILE` lists the kept model's unweighted sums per ligand residue.
   selfcheck  no reference counterpart: dfm_complex_selfcheck on the pair (what `dock` and `sweep` run once per complex anyway).
 
 --ckpt takes the Lightning checkpoint the reference loads (src/inference_base.py:611-616; read without Lightning / omegaconf by
@@ -86,8 +95,9 @@ def _add_native(p):
 def _add_consensus(p):
     p.add_argument("--consensus", action="store_true",
                    help="score the trajectories by consensus contacts (adds a `consensus` object to the result line)")
-    p.add_argument("--rank", default="energy", choices=["energy", "consensus"],
-                   help="which trajectory is kept: the minimum energy (default) or the highest consensus score (implies --consensus)")
+    p.add_argument("--rank", default="energy", choices=["energy", "consensus", "interface"],
+                   help="which trajectory is kept: the minimum energy (default), the highest consensus score (implies --consensus) or the "
+                        "lowest interface energy (implies --interface-energy)")
     p.add_argument("--consensus-top", type=float, default=None, metavar="FRAC",
                    help="with --consensus: members of the ensemble are the best FRAC of the trajectories by energy (default 1.0: all)")
     p.add_argument("--contact-map", default=None, metavar="FILE.npz",
@@ -109,6 +119,16 @@ def _add_sterics(p):
                    help="with --clash-screen: heavy-atom distance of an interface contact (default 5.0, >= --clash-cutoff)")
     p.add_argument("--clash-residues", default=None, metavar="FILE",
                    help="write the kept model's clash / contact counts per ligand residue (implies --clash-screen)")
+
+
+def _add_interface(p):
+    p.add_argument("--interface-energy", action="store_true",
+                   help="soft LJ + Coulomb interface energy of every trajectory (adds an `interface_energy` object to the result line and to every model)")
+    p.add_argument("--ie-weights", type=float, nargs=3, default=None, metavar=("REP", "ATT", "ELEC"),
+                   help="with --interface-energy: weights of the total (default 0.18 1.0 0.5, starting values that are not fitted)")
+    p.add_argument("--ie-cutoff", type=float, default=None, metavar="A", help="with --interface-energy: heavy-atom pair cutoff (default 8.0, at most 16)")
+    p.add_argument("--energy-residues", default=None, metavar="FILE",
+                   help="write the kept model's LJ and Coulomb interface energy per ligand residue (implies --interface-energy)")
 
 
 def _add_surface(p):
@@ -162,6 +182,7 @@ def build_parser():
     _add_consensus(d)
     _add_sterics(d)
     _add_surface(d)
+    _add_interface(d)
     _add_common(d)
     r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)")
     r.add_argument("pdb_1", help="receptor PDB")
@@ -177,6 +198,7 @@ def build_parser():
     _add_consensus(r)
     _add_sterics(r)
     _add_surface(r)
+    _add_interface(r)
     _add_common(r)
     s = sub.add_parser("sweep", help="sample every complex of a DB5-style directory (inference_mlsb.py run_sampling)")
     s.add_argument("--db5", required=True, help="directory of <id>.pt files (+ optional test.txt with the ids to run)")
@@ -252,6 +274,16 @@ def parse_args(argv=None):
             ap.error("--sphere-points must be a multiple of 64 in 64 .. 256")
         if args.min_bsa is not None and not np.isfinite(args.min_bsa):
             ap.error("--min-bsa must be finite")
+    if args.cmd in ("dock", "refine"):
+        if args.rank == "interface" or args.energy_residues:
+            args.interface_energy = True
+        if not args.interface_energy and (args.ie_weights is not None or args.ie_cutoff is not None):
+            ap.error("--ie-weights / --ie-cutoff describe --interface-energy: they need it")
+        args.ie_cutoff = 8.0 if args.ie_cutoff is None else args.ie_cutoff
+        if not (np.isfinite(args.ie_cutoff) and 0 < args.ie_cutoff <= 16):
+            ap.error("--ie-cutoff must be in (0, 16]")
+        if args.ie_weights is not None and not np.isfinite(args.ie_weights).all():
+            ap.error("--ie-weights must be finite")
     if args.cmd in ("dock", "refine", "sweep"):
         if args.consensus_top is not None and not args.consensus:
             ap.error("--consensus-top selects the members of the consensus ensemble: it needs --consensus")
@@ -373,6 +405,26 @@ def sterics_outputs(args, model, res, rec, lig, line):
         keys, clash, contact = driver.residue_sterics(model, rec, lig, res["rot_update"], res["tr_update"], args.clash_cutoff, args.contact_cutoff)
         write_clash_residues(args.clash_residues, keys, clash, contact)
         line.update(clash_residues=os.path.abspath(args.clash_residues))
+
+
+def interface_kwargs(args):
+    """Driver keyword arguments of the interface-energy flags of dock / refine: none without them."""
+    if not args.interface_energy:
+        return {}
+    return dict(interface_energy=True, ie_weights=args.ie_weights, ie_cutoff=args.ie_cutoff, rank=args.rank)
+
+
+def interface_outputs(args, model, res, rec, lig, line):
+    """The interface-energy part of a dock / refine result: the `interface_energy` object of the line and --energy-residues."""
+    if not args.interface_energy:
+        return
+    line.update(interface_energy=res["interface_energy"], index=res["index"])
+    if args.energy_residues:
+        from . import driver
+        from .ifenergy import write_energy_residues
+        keys, vdw, elec = driver.residue_interface_energy(model, rec, lig, res["rot_update"], res["tr_update"], args.ie_cutoff)
+        write_energy_residues(args.energy_residues, keys, vdw, elec)
+        line.update(energy_residues=os.path.abspath(args.energy_residues))
 
 
 def surface_kwargs(args):
@@ -508,6 +560,7 @@ def cmd_dock(args):
     kw.update(consensus_kwargs(args))
     kw.update(sterics_kwargs(args))
     kw.update(surface_kwargs(args))
+    kw.update(interface_kwargs(args))
     res = driver.dock_pair(model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                            precision=args.precision, out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
                            on_selfcheck_fail=args.on_selfcheck_fail, **kw)
@@ -527,6 +580,7 @@ def cmd_dock(args):
     consensus_outputs(args, res, rec, lig, line)
     sterics_outputs(args, model, res, rec, lig, line)
     surface_outputs(args, model, res, rec, lig, line)
+    interface_outputs(args, model, res, rec, lig, line)
     print(json.dumps(line), flush=True)
     if args.json:
         extra = {}
@@ -550,6 +604,7 @@ def cmd_refine(args):
     kw.update(consensus_kwargs(args))
     kw.update(sterics_kwargs(args))
     kw.update(surface_kwargs(args))
+    kw.update(interface_kwargs(args))
     res = driver.refine_pair(model, rec, lig, rec_x, lig_x, t_begin=args.t_begin, num_samples=args.num_samples, num_steps=args.num_steps,
                              seed=args.seed, precision=args.precision, out_pdb=args.out, max_batch=args.max_batch,
                              selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, perturb=not args.no_perturb, **kw)
@@ -562,6 +617,7 @@ def cmd_refine(args):
     consensus_outputs(args, res, rec, lig, line)
     sterics_outputs(args, model, res, rec, lig, line)
     surface_outputs(args, model, res, rec, lig, line)
+    interface_outputs(args, model, res, rec, lig, line)
     print(json.dumps(line), flush=True)
     if args.json:
         with open(args.json, "w") as f:

@@ -939,7 +939,7 @@ extern "C" int dfm_restraint_eval(dfm_complex *cx, int B, const float *lig_pos, 
 // several host threads, and next to that model's complex handles, do not share any state.
 // the two millisecond figures of this thread's last call of each kind, behind the dfm_*_last_timing getters: k_pose_dist and the
 // clustering kernels for MS_CLUSTER, host-to-device copies and kernels for the others
-enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_KINDS };
+enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_IFACE, MS_KINDS };
 static thread_local double g_last_ms[MS_KINDS][2] = {};
 
 static void set_last_ms(int kind, double a, double b)
@@ -1015,7 +1015,7 @@ struct PoseCall {
     }
 };
 
-// the chunk loop of the rigid-pose calls (dfm_pose_sterics, dfm_pose_bsa): the chunk's (rot, tr) on the device, their transforms T, and
+// the chunk loop of the rigid-pose calls (dfm_pose_sterics, dfm_pose_bsa, dfm_pose_iface_energy): the chunk's (rot, tr) on the device, their transforms T, and
 // the call's copy / kernel milliseconds from the call's own events.  Per chunk: upload, the caller's memsets and launches, kernels_done,
 // the caller's downloads, finish
 struct PoseChunks {
@@ -1849,6 +1849,167 @@ extern "C" int dfm_pose_bsa(dfm_surface *s, int P, const float *rot, const float
 extern "C" int dfm_bsa_last_timing(double *copy_ms, double *kernel_ms)
 {
     return last_timing(MS_BSA, copy_ms, kernel_ms);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Interface energy (kernels_iface.hip).  A dfm_iface holds what the two atom sets, their parameters, the scalars and the rotation centre
+// fix - the receptor's grid of cells of the cutoff, the ligand in blocks of 64 neighbours, each atom's (rmin_half, sqrt_eps, charge) at
+// its sorted place - and is read-only after creation; every dfm_pose_iface_energy call owns its stream and temporaries.
+constexpr size_t IFACE_CHUNK_BYTES = (size_t)64 << 20;      // per-atom output of one chunk of a call
+constexpr int IFACE_MAX_CHUNK = 32768;                      // poses per launch (gridDim.y)
+
+struct dfm_iface {
+    int device = 0, Ar = 0, Al = 0, n_cells = 0, max_cell_atoms = 0, default_chunk = 0;
+    float cell_edge = 0.f;
+    double sum_bound = 0.0;
+    DevPool pool;      // unbound: released under a device-wide wait, like a model's
+    float *rec = nullptr, *rec_par = nullptr, *lig = nullptr, *lig_par = nullptr, *sphere = nullptr;
+    int32_t *cell_start = nullptr, *lig_index = nullptr;
+    IfaceConst sc = {};
+};
+
+extern "C" void dfm_iface_destroy(dfm_iface *h)
+{
+    if (!h) return;
+    DeviceScope ds(h->device);
+    h->pool.release();
+    delete h;
+}
+
+extern "C" dfm_iface *dfm_iface_create(dfm_model *m, int Ar, const float *rec_atoms, const float *rec_rmin_half, const float *rec_sqrt_eps,
+                                       const float *rec_charge, int Al, const float *lig_atoms, const float *lig_rmin_half,
+                                       const float *lig_sqrt_eps, const float *lig_charge, const float center[3], float cutoff, float soft,
+                                       float elec_min_dist, float dielectric_slope)
+{
+    auto bad = [](int code, const std::string &msg) -> dfm_iface * { (void)fail(code, msg); return nullptr; };
+    if (!m) return bad(DFM_E_INVALID, "m is NULL");
+    if (const std::string msg = check_atom_sets(Ar, rec_atoms, Al, lig_atoms, center); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_iface_atoms("rec", Ar, rec_rmin_half, rec_sqrt_eps, rec_charge); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_iface_atoms("lig", Al, lig_rmin_half, lig_sqrt_eps, lig_charge); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_iface_scalars(cutoff, soft, elec_min_dist, dielectric_slope); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    // the receptor's grid: origin = the bounding box's low corner, edge = the cutoff
+    CellGrid gr;
+    if (!build_cell_grid(Ar, rec_atoms, (double)cutoff, gr))
+        return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells of the cutoff");
+    const IfaceBound bound = iface_sum_bound(Ar, rec_sqrt_eps, rec_charge, Al, lig_sqrt_eps, lig_charge, gr.max_cell, soft, elec_min_dist,
+                                             dielectric_slope);
+    if (!bound.ok) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "the energy sums could reach 2^62 quanta: %.3g pairs of at most %.3g kcal/mol", bound.pairs, bound.term_kcal);
+        return bad(DFM_E_INVALID, buf);
+    }
+    double maxabs = 0.0;
+    for (int k = 0; k < 3; ++k) maxabs = std::max(maxabs, std::max(std::fabs(gr.lo[k]), std::fabs(gr.hi[k])));
+    maxabs += 2.0 * (double)cutoff + 1.0;
+    // the fp32 reject threshold (dfm_posewalk.h): cutoff * 1.0001 + slack
+    const float thr = cutoff * 1.0001f + pose_slack(maxabs);
+    IfaceConst sc = {};
+    sc.g = walk_grid(gr, (double)cutoff, (double)thr, center);
+    sc.cut2 = (double)cutoff * (double)cutoff;
+    sc.soft = (double)soft;
+    sc.min2 = (double)elec_min_dist * (double)elec_min_dist;
+    sc.kc = 332.0637 / (double)dielectric_slope;
+    sc.reject2 = thr * thr;
+    double llo[3] = {(double)lig_atoms[0], (double)lig_atoms[1], (double)lig_atoms[2]};
+    for (int i = 1; i < Al; ++i)
+        for (int k = 0; k < 3; ++k) llo[k] = std::min(llo[k], (double)lig_atoms[(size_t)i * 3 + k]);
+    const LigandBlocks lb = build_ligand_blocks(Al, lig_atoms, llo, sc.g.edge, sc.g.center);
+    if (!lb.finite) return bad(DFM_E_INVALID, "lig_atoms / center: the ligand's extent about the centre overflows fp32");
+    const std::vector<float> rec4 = gather4(gr.order, rec_atoms, nullptr), lig4 = gather4(lb.index, lig_atoms, nullptr);
+    const std::vector<float> recp = gather_iface(gr.order, rec_rmin_half, rec_sqrt_eps, rec_charge);
+    const std::vector<float> ligp = gather_iface(lb.index, lig_rmin_half, lig_sqrt_eps, lig_charge);
+    DeviceScope ds(m->device);
+    if (ds.err != hipSuccess) return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err));
+    dfm_iface *h = new dfm_iface;
+    h->device = m->device; h->Ar = Ar; h->Al = Al; h->sc = sc; h->n_cells = sc.g.nx * sc.g.ny * sc.g.nz; h->max_cell_atoms = gr.max_cell;
+    h->cell_edge = cutoff;
+    h->sum_bound = bound.sum_quanta;
+    h->default_chunk = (int)std::min<size_t>(IFACE_MAX_CHUNK, std::max<size_t>(1, IFACE_CHUNK_BYTES / ((size_t)Al * 2 * sizeof(int64_t))));
+    hipError_t e = hipSuccess;
+    {
+        PoseCall c;
+        e = c.open();
+        if (e == hipSuccess) e = h->pool.upload_async(&h->rec, rec4.data(), rec4.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->rec_par, recp.data(), recp.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->cell_start, gr.start.data(), gr.start.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->lig, lig4.data(), lig4.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->lig_par, ligp.data(), ligp.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->sphere, lb.sphere.data(), lb.sphere.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->lig_index, lb.index.data(), lb.index.size(), c.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
+    }      // the call's stream has drained: the host vectors it read may go
+    if (e != hipSuccess) {
+        h->pool.release();
+        delete h;
+        return bad(e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP, std::string("dfm_iface_create: ") + hipGetErrorString(e));
+    }
+    return h;
+}
+
+extern "C" int dfm_iface_info(const dfm_iface *h, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge, double *sum_bound_q)
+{
+    if (!h) return fail(DFM_E_INVALID, "NULL argument");
+    if (n_cells) *n_cells = h->n_cells;
+    if (max_cell_atoms) *max_cell_atoms = h->max_cell_atoms;
+    if (cell_edge) *cell_edge = h->cell_edge;
+    if (sum_bound_q) *sum_bound_q = h->sum_bound;
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_iface_energy_chunked(dfm_iface *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_iface_out *out)
+{
+    if (!h) return fail(DFM_E_INVALID, "h is NULL");
+    if (!rot) return fail(DFM_E_INVALID, "rot is NULL");
+    if (!tr) return fail(DFM_E_INVALID, "tr is NULL");
+    if (!out) return fail(DFM_E_INVALID, "out is NULL");
+    if (P < 1) return fail(DFM_E_INVALID, "need P >= 1");
+    if (chunk_poses < 0) return fail(DFM_E_INVALID, "chunk_poses must be >= 0");
+    DEVICE_SCOPE(h->device);
+    PoseCall c;
+    HIPCHK(c.open());
+    const bool per_atom = out->lig_vdw_q || out->lig_elec_q;
+    // the call's chunk, else the default: without per-atom output a chunk is bounded by the launch alone
+    const int Pc = std::min(P, chunk_poses > 0 ? std::min(chunk_poses, IFACE_MAX_CHUNK) : (per_atom ? h->default_chunk : IFACE_MAX_CHUNK));
+    const size_t Al = (size_t)h->Al;
+    PoseChunks ch{c, rot, tr};
+    int64_t *d_tot = nullptr, *d_lv = nullptr, *d_le = nullptr;
+    HIPCHK(ch.open(Pc));
+    HIPCHK(c.tmp.alloc(&d_tot, (size_t)Pc * 4));      // rep_q | att_q | elec_q | n_pairs of each pose
+    if (out->lig_vdw_q) HIPCHK(c.tmp.alloc(&d_lv, (size_t)Pc * Al));
+    if (out->lig_elec_q) HIPCHK(c.tmp.alloc(&d_le, (size_t)Pc * Al));
+    const IfaceAtoms at = {h->rec, h->rec_par, h->lig, h->lig_par, h->sphere, h->cell_start, h->lig_index, h->sc, h->Ar, h->Al};
+    std::vector<int64_t> h_tot((size_t)Pc * 4);
+    for (int p0 = 0; p0 < P; p0 += Pc) {
+        const int n = std::min(Pc, P - p0);
+        HIPCHK(ch.upload(p0, n));
+        if (d_lv) HIPCHK(hipMemsetAsync(d_lv, 0, (size_t)n * Al * sizeof(int64_t), c.s));
+        if (d_le) HIPCHK(hipMemsetAsync(d_le, 0, (size_t)n * Al * sizeof(int64_t), c.s));
+        HIPCHK(launch_iface_pose(ch.d_rot, ch.d_tr, n, ch.T, d_tot, c.s));
+        HIPCHK(launch_iface(at, ch.T, n, d_tot, d_lv, d_le, c.s));
+        HIPCHK(ch.kernels_done());
+        HIPCHK(hipMemcpyAsync(h_tot.data(), d_tot, (size_t)n * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
+        if (d_lv) HIPCHK(hipMemcpyAsync(out->lig_vdw_q + (size_t)p0 * Al, d_lv, (size_t)n * Al * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
+        if (d_le) HIPCHK(hipMemcpyAsync(out->lig_elec_q + (size_t)p0 * Al, d_le, (size_t)n * Al * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(ch.finish());
+        for (int p = 0; p < n; ++p) {
+            if (out->rep_q) out->rep_q[p0 + p] = h_tot[(size_t)p * 4];
+            if (out->att_q) out->att_q[p0 + p] = h_tot[(size_t)p * 4 + 1];
+            if (out->elec_q) out->elec_q[p0 + p] = h_tot[(size_t)p * 4 + 2];
+            if (out->n_pairs) out->n_pairs[p0 + p] = h_tot[(size_t)p * 4 + 3];
+        }
+    }
+    set_last_ms(MS_IFACE, ch.copy_ms, ch.kernel_ms);
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_iface_energy(dfm_iface *h, int P, const float *rot, const float *tr, dfm_iface_out *out)
+{
+    return dfm_pose_iface_energy_chunked(h, P, rot, tr, 0, out);
+}
+
+extern "C" int dfm_iface_last_timing(double *copy_ms, double *kernel_ms)
+{
+    return last_timing(MS_IFACE, copy_ms, kernel_ms);
 }
 
 extern "C" int dfm_complex_degree(const dfm_complex *cx) { return cx ? cx->K : -1; }

@@ -469,6 +469,28 @@ hipError_t launch_surface_pose(const float *rot, const float *tr, int n, double 
 // lig_buried is written by the waves that reach the cell walk only, so zero it first.  class_points [n][2][16] is added to.
 hipError_t launch_surface(const SurfaceAtoms &at, const double *T, int n, uint64_t *rec_bur, int32_t *lig_buried, int32_t *rec_buried,
                           int32_t *class_points, hipStream_t s);
+// interface energy (kernels_iface.hip; include/dfmdock_amd.h: dfm_iface_create / dfm_pose_iface_energy).  What the atoms and the scalars
+// fix: the receptor's grid of cells of the cutoff, cut2 = cutoff^2, soft, min2 = elec_min_dist^2 and kc = 332.0637 / dielectric_slope as
+// the definition's doubles, and the fp32 reject threshold squared (g.grow is that threshold as a double, as in StericsConst).
+struct IfaceConst {
+    WalkGrid g;
+    double cut2, soft, min2, kc;
+    float reject2;
+};
+// device arrays of a dfm_iface: rec / lig / sphere / cell_start / lig_index as in StericsAtoms; rec_par [Ar] and lig_par [Al] float4 =
+// (rmin_half, sqrt_eps, charge, 0) of the atom at the same place of rec / lig
+struct IfaceAtoms {
+    const float *rec, *rec_par, *lig, *lig_par, *sphere;
+    const int32_t *cell_start, *lig_index;
+    IfaceConst sc;
+    int Ar, Al;
+};
+// T [n][12]: R(rot) row-major and tr as doubles; also zeroes tot [n][4] = (rep_q, att_q, elec_q, n_pairs) of the n poses
+hipError_t launch_iface_pose(const float *rot, const float *tr, int n, double *T, int64_t *tot, hipStream_t s);
+// n <= 65535 poses.  tot [n][4] is added to.  lig_vdw / lig_elec [n][Al] (caller's atom order) or nullptr: written by the waves that
+// reach the cell walk only, so zero them first
+hipError_t launch_iface(const IfaceAtoms &at, const double *T, int n, int64_t *tot, int64_t *lig_vdw, int64_t *lig_elec, hipStream_t s);
+
 // isolated exposure of one chain on the host, as the definition takes it (kernels_surface.hip)
 void surface_exposure(int n, const float *xyz, const float *radius, double probe, int K, const float *dirs, const double lo[3],
                       const int dims[3], double edge, double pad, const int32_t *start, const int32_t *order, uint64_t *mask);

@@ -1,6 +1,7 @@
-// dfm_poseprep.h - host preparation of the per-pose all-atom calls (api.hip: dfm_atoms_create, dfm_surface_create): argument checks, the
-// cell grid of a chain, the ligand in blocks of 64 neighbours, the rounding slack.  Plain C++ without a HIP call, so that
-// tests/test_pose_prep_cpu.py runs it under the sanitizers without a GPU.
+// dfm_poseprep.h - host preparation of the per-pose all-atom calls (api.hip: dfm_atoms_create, dfm_surface_create, dfm_iface_create):
+// argument checks, the cell grid of a chain, the ligand in blocks of 64 neighbours, the rounding slack, the interface energy's parameter
+// limits and overflow bound.  Plain C++ without a HIP call, so that tests/test_pose_prep_cpu.py and tests/test_ifenergy_cpu.py run it
+// under the sanitizers without a GPU.
 #pragma once
 
 #include <algorithm>
@@ -163,6 +164,83 @@ inline LigandBlocks build_ligand_blocks(int Al, const float *lig_atoms, const do
     }
     for (float v : lb.sphere) lb.finite = lb.finite && std::isfinite(v);
     return lb;
+}
+
+// Interface energy (api.hip: dfm_iface_create; kernels_iface.hip).  The limits of the per-atom parameters [n] of one chain (`who`:
+// "rec" or "lig") and of the call's scalars: the message of the first one that is wrong, or "".
+inline std::string check_iface_atoms(const char *who, int n, const float *rmin_half, const float *sqrt_eps, const float *charge)
+{
+    const std::string w(who);
+    if (!rmin_half) return w + "_rmin_half is NULL";
+    if (!sqrt_eps) return w + "_sqrt_eps is NULL";
+    if (!charge) return w + "_charge is NULL";
+    for (int i = 0; i < n; ++i) {
+        if (!(std::isfinite(rmin_half[i]) && rmin_half[i] > 0.f && rmin_half[i] <= 8.f))
+            return w + "_rmin_half: atom " + std::to_string(i) + " is not in (0, 8]";
+        if (!(std::isfinite(sqrt_eps[i]) && sqrt_eps[i] >= 0.f && sqrt_eps[i] <= 2.f))
+            return w + "_sqrt_eps: atom " + std::to_string(i) + " is not in [0, 2]";
+        if (!(std::isfinite(charge[i]) && std::fabs(charge[i]) <= 4.f)) return w + "_charge: atom " + std::to_string(i) + " is not in [-4, 4]";
+    }
+    return "";
+}
+inline std::string check_iface_scalars(float cutoff, float soft, float elec_min_dist, float dielectric_slope)
+{
+    if (!(std::isfinite(cutoff) && cutoff > 0.f && cutoff <= 16.f)) return "cutoff must be in (0, 16]";
+    if (!(std::isfinite(soft) && soft >= 0.5f && soft <= 1.f)) return "soft must be in [0.5, 1]";
+    if (!(std::isfinite(elec_min_dist) && elec_min_dist >= 1.f)) return "elec_min_dist must be finite and >= 1";
+    if (!(std::isfinite(dielectric_slope) && dielectric_slope > 0.f)) return "dielectric_slope must be finite and > 0";
+    return "";
+}
+
+// The integer sums of the interface energy can not wrap.  One quantum is 2^-20 kcal/mol.  With s2 = Rm^2 / max(r2, (soft Rm)^2) <=
+// soft^-2 a pair has |rep| <= e soft^-12, |att| <= 2 e soft^-6 and |elec| <= (332.0637 / slope) |q_a q_b| / m^2, where e <= E = (largest
+// sqrt_eps of the receptor) (largest of the ligand), |q_a q_b| <= Q likewise and m = elec_min_dist.  At the limits of the checks above
+// (sqrt_eps <= 2, soft >= 0.5, |q| <= 4, m >= 1) that is rep <= 4 * 4096 = 2^14 kcal/mol = 2^34 quanta, att <= 2^9 kcal/mol and
+// elec <= 5313.1 / slope kcal/mol, below 2^14 for slope >= 0.33; a smaller slope is allowed and raises the bound, which is why the bound
+// is taken from the complex's own E, Q, soft, m and slope and not from the limits.  A ligand atom's pairs lie within the cutoff = the
+// cell edge, so in the 27 cells about its own: a pose has at most pairs = Al min(Ar, 27 max_cell_atoms) of them.  Every sum the call forms
+// (rep, att, elec per pose; rep + att and elec per ligand atom) is then at most
+//     pairs * (max(rep + att, elec) * (1 + 2^-30) * 2^20 + 2)     quanta
+// in magnitude: 2^-30 covers the rounding of the few fp64 operations of a term, + 2 the rounding of rep and att to integers.  The
+// creator rejects a complex for which this is not below 2^62 (or not finite), so every partial sum - and every single term's
+// conversion to int64 - is far inside the range.
+struct IfaceBound {
+    double term_kcal, pairs, sum_quanta;
+    bool ok;
+};
+inline IfaceBound iface_sum_bound(int Ar, const float *rec_sqrt_eps, const float *rec_charge, int Al, const float *lig_sqrt_eps,
+                                  const float *lig_charge, int max_cell_atoms, float soft, float elec_min_dist, float dielectric_slope)
+{
+    double er = 0.0, el = 0.0, qr = 0.0, ql = 0.0;
+    for (int i = 0; i < Ar; ++i) {
+        er = std::max(er, (double)rec_sqrt_eps[i]);
+        qr = std::max(qr, std::fabs((double)rec_charge[i]));
+    }
+    for (int i = 0; i < Al; ++i) {
+        el = std::max(el, (double)lig_sqrt_eps[i]);
+        ql = std::max(ql, std::fabs((double)lig_charge[i]));
+    }
+    const double s = 1.0 / (double)soft, s6 = std::pow(s, 6.0), m = (double)elec_min_dist;
+    const double vdw = er * el * (s6 * s6 + 2.0 * s6);
+    const double q = qr * ql, elec = q > 0.0 ? (332.0637 / (double)dielectric_slope) * q / (m * m) : 0.0;
+    IfaceBound b;
+    b.term_kcal = std::max(vdw, elec);
+    b.pairs = (double)Al * std::min((double)Ar, 27.0 * (double)max_cell_atoms);
+    b.sum_quanta = b.pairs * (b.term_kcal * (1.0 + 9.4e-10) * 1048576.0 + 2.0);
+    b.ok = std::isfinite(b.sum_quanta) && b.sum_quanta < 4611686018427387904.0;
+    return b;
+}
+
+// per-atom parameters as the kernel reads them: (rmin_half, sqrt_eps, charge, 0) of atom order[q] at q
+inline std::vector<float> gather_iface(const std::vector<int32_t> &order, const float *rmin_half, const float *sqrt_eps, const float *charge)
+{
+    std::vector<float> v(order.size() * 4, 0.f);
+    for (size_t q = 0; q < order.size(); ++q) {
+        v[q * 4] = rmin_half[order[q]];
+        v[q * 4 + 1] = sqrt_eps[order[q]];
+        v[q * 4 + 2] = charge[order[q]];
+    }
+    return v;
 }
 
 }  // namespace dfm

@@ -1,4 +1,4 @@
-// dfm_posewalk.h - what the per-pose all-atom kernels share (kernels_sterics.hip, kernels_surface.hip): a rigid ligand pose against a
+// dfm_posewalk.h - what the per-pose all-atom kernels share (kernels_sterics.hip, kernels_surface.hip, kernels_iface.hip): a rigid ligand pose against a
 // receptor whose atoms are sorted by cell of a uniform grid (dfm_walkgrid.h).  Device code.
 //
 // A pose is 24 bytes: (rot, tr) of the sampler.  Pose p of ligand atom a is (a - center) R(rot_p)^T + center + tr_p in fp64.  One wave
@@ -12,16 +12,17 @@
 //      range) are staged in LDS, 64 at a time by one coalesced load, and read back as broadcasts (every lane reads the same address: no
 //      bank conflict, one ds_read_b128 per receptor atom for 64 pairs).  Letting each lane walk its own 27 cells instead would test about
 //      a sixth of the pairs, but with 64 different cell ranges per wave: every load a scattered gather, every loop as long as the wave's
-//      longest lane.  The staged form keeps the wave converged up to the kernel's fp64 branch, which few pairs take.
+//      longest lane.  The staged form keeps the wave converged up to the kernel's fp64 part: a per-lane branch that few pairs take in
+//      k_sterics and k_surface, the whole wave's converged evaluation behind one wave-uniform test in k_iface, where many pairs pass.
 //
 // The fp32 reject of the kernels: a pair is dropped without the fp64 arithmetic only when d2 > (reach * 1.0001f + slack)^2 with d2 taken
-// in fp32 from the fp32 copy of the ligand atom (reach: the contact cutoff, or R_a + R_b); written as !(d2 > ...) for the pairs that go
+// in fp32 from the fp32 copy of the ligand atom (reach: the contact cutoff, R_a + R_b, or the energy cutoff, at most 16 A); written as !(d2 > ...) for the pairs that go
 // on, so a NaN goes on.  Why that is conservative: a pair within reach has its ligand atom inside the receptor's box grown by the reach,
 // so every coordinate involved is at most `maxabs` = the largest |coordinate| of that grown box.  The fp32 copy is off by at most 2^-24
 // maxabs per axis, the three differences and d2 add relative errors of a few 2^-24, so the fp32 distance is off by at most sqrt(3) 2^-24
-// maxabs + 4e-7 d < 1.04e-7 maxabs + 2e-6 (d <= 5).  slack = max(1e-3, 2.5e-7 maxabs) A (dfm_poseprep.h: pose_slack) is above the first
-// term at any scale (it stays 1e-3 A up to maxabs = 4000 A, which holds every PDB file), and the factor 1.0001 (5e-4 A at 5 A) is above
-// the second.  The same threshold is `grow` of the box tests of steps 2 and 3, which are taken in fp64; the cell of a coordinate is
+// maxabs + 4e-7 d < 1.04e-7 maxabs + 6.4e-6 (d <= 16, the largest reach of any caller).  slack = max(1e-3, 2.5e-7 maxabs) A (dfm_poseprep.h: pose_slack) is above the first
+// term at any scale (it stays 1e-3 A up to maxabs = 4000 A, which holds every PDB file), and the factor 1.0001 (1e-4 d: 5e-4 A at 5 A, 1.6e-3 A
+// at 16 A, against 4e-7 d) is above the second at any reach.  The same threshold is `grow` of the box tests of steps 2 and 3, which are taken in fp64; the cell of a coordinate is
 // cell_of (dfm_walkgrid.h) in fp64 here and on the host, a monotone function of x, so a receptor atom within reach of the block's box can not lie in
 // a cell below or above the block's range.
 #pragma once
@@ -146,6 +147,32 @@ __device__ __forceinline__ void walk_rows(const WalkGrid &g, const WalkBlock &w,
                 if (lane < cnt) s_rec[lane] = rec[base + lane];
                 __syncthreads();
                 for (int j = 0; j < cnt; ++j) f(base + j, s_rec[j]);
+            }
+        }
+}
+
+// step 4 for a kernel whose receptor atoms carry a second float4 (rec2 [Ar], sorted like rec): f(index, atom, its second float4), both
+// staged by the same two barriers.  s_rec, s_rec2: 64 float4 of LDS each.  An overload of its own, so that the kernels of the
+// one-array walk above compile to what they were.
+template <class F>
+__device__ __forceinline__ void walk_rows(const WalkGrid &g, const WalkBlock &w, const int32_t *__restrict__ cell_start,
+                                          const float4 *__restrict__ rec, const float4 *__restrict__ rec2, float4 *s_rec, float4 *s_rec2,
+                                          F &&f)
+{
+    const int lane = threadIdx.x;
+    for (int cz = w.cz0; cz <= w.cz1; ++cz)
+        for (int cy = w.cy0; cy <= w.cy1; ++cy) {
+            const int row = (cz * g.ny + cy) * g.nx;
+            const int b0 = cell_start[row + w.cx0], b1 = cell_start[row + w.cx1 + 1];
+            for (int base = b0; base < b1; base += 64) {
+                const int cnt = b1 - base < 64 ? b1 - base : 64;
+                __syncthreads();      // the previous batch has been read
+                if (lane < cnt) {
+                    s_rec[lane] = rec[base + lane];
+                    s_rec2[lane] = rec2[base + lane];
+                }
+                __syncthreads();
+                for (int j = 0; j < cnt; ++j) f(base + j, s_rec[j], s_rec2[j]);
             }
         }
 }

@@ -171,6 +171,80 @@ def _surface_result(bd, k, opts):
     return out
 
 
+def iface_inputs(rec, lig, family):
+    """What the interface-energy call takes from two pdbio.backbone_from_atoms dicts: sterics_inputs plus the (rmin_half, sqrt_eps,
+    charge) row of every heavy atom (ifenergy.atom_parameters, float32 [n,3])."""
+    from . import ifenergy as IE
+    ra, la, cen = sterics_inputs(rec, lig, family)
+    return ra, IE.atom_parameters(rec["atoms"]), la, IE.atom_parameters(lig["atoms"]), cen
+
+
+def ensemble_interface_energy(model: engine.Model, rec, lig, rot_update, tr_update, cutoff=8.0, weights=None, per_atom=False):
+    """Interface energy of trajectories on the GPU (dfm_pose_iface_energy) from their final (rot_update, tr_update) alone: soft
+    Lennard-Jones plus Coulomb (eps = 4 r) over the heavy-atom pairs of the two parsed PDB chains within `cutoff` A.  Returns the dict of
+    Interface.energy plus total (float64 [P], ifenergy.total with `weights`: None = ifenergy.WEIGHTS, starting values that are not
+    fitted), weights and cutoff."""
+    from . import ifenergy as IE
+    w = IE.WEIGHTS if weights is None else tuple(float(v) for v in weights)
+    ra, rp, la, lp, cen = iface_inputs(rec, lig, model.hp.family)
+    with model.interface(ra, rp, la, lp, cen, cutoff=cutoff) as h:
+        out = h.energy(np.asarray(rot_update, np.float32).reshape(-1, 3), np.asarray(tr_update, np.float32).reshape(-1, 3), per_atom=per_atom)
+        out.update(total=IE.total(out["rep"], out["att"], out["elec"], w), weights=w, cutoff=h.cutoff)
+    return out
+
+
+def residue_interface_energy(model: engine.Model, rec, lig, rot, tr, cutoff=8.0):
+    """Per ligand residue of ONE pose: (keys, vdw, elec) - the per-atom sums of the interface energy in quanta of 2^-20 kcal/mol summed
+    over each residue's heavy atoms (sterics.residue_of_atoms, ifenergy.residue_energy)."""
+    from . import ifenergy as IE
+    from . import sterics as ST
+    ed = ensemble_interface_energy(model, rec, lig, np.asarray(rot).reshape(1, 3), np.asarray(tr).reshape(1, 3), cutoff, per_atom=True)
+    keys, res = ST.residue_of_atoms(lig["atoms"], ST.heavy_atoms(lig["atoms"]))
+    return keys, IE.residue_energy(ed["lig_vdw_q"][0], res, len(keys)), IE.residue_energy(ed["lig_elec_q"][0], res, len(keys))
+
+
+def _check_interface(interface_energy, rank, ie_weights, ie_cutoff):
+    """None (off) or (rank by it, weights, cutoff) of a pair driver's interface-energy options; rank "interface" implies them."""
+    if not interface_energy and rank != "interface":
+        return None
+    from . import ifenergy as IE
+    w = IE.WEIGHTS if ie_weights is None else tuple(float(v) for v in ie_weights)
+    IE.total(0.0, 0.0, 0.0, w)      # three finite numbers
+    return rank == "interface", w, IE.check_scalars(cutoff=ie_cutoff)[0]
+
+
+def _pose_interface(ed, k):
+    return {"rep": float(ed["rep"][k]), "att": float(ed["att"][k]), "elec": float(ed["elec"][k]), "total": float(ed["total"][k]),
+            "n_pairs": int(ed["n_pairs"][k])}
+
+
+def _interface_pick(model, rec, lig, cols, k, key, opts, bad=None):
+    """The selecting half of the interface-energy part of a pair driver, run BEFORE any per-pose summary is built.  opts = None (off) or
+    _check_interface's; k / key: the pose and the clustering key the driver's own rule gives.  Returns (k, key, data or None): under rank
+    "interface" k is the pose of the lowest total among those the clash filter left (ties: the lower index) and key the totals, NaN on
+    the removed poses; otherwise k and key stay."""
+    if opts is None:
+        return k, key, None
+    by_it, weights, cutoff = opts
+    ed = ensemble_interface_energy(model, rec, lig, cols["rot_update"], cols["tr_update"], cutoff, weights)
+    if by_it:
+        k, key = _kept(np.argmin, bad, ed["total"]), _nan_key(ed["total"], bad)
+    return k, key, ed
+
+
+def _interface_result(ed, k, opts, bad=None, ranked_by="energy"):
+    """The `interface_energy` entries of a pair driver's result for the FINAL kept pose k (none without the option): its terms, its
+    rank by total among the poses the clash filter left, and `ranked_by` - the rule that chose k."""
+    if ed is None:
+        return {}
+    from .cluster import rank_order
+    by_it, weights, cutoff = opts
+    tot = _nan_key(ed["total"], bad)
+    summary = dict(_pose_interface(ed, k), rank=int(np.nonzero(rank_order(tot, len(tot)) == k)[0][0]) + 1, weights=list(weights),
+                   cutoff=float(cutoff), ranked_by="interface" if by_it else ranked_by)
+    return {"interface_energy": summary, "interface_data": ed, "index": int(k)}
+
+
 def _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff):
     """None (off) or (filter, clash cutoff, contact cutoff) of a pair driver's screen options."""
     if not (clash_screen or clash_filter):
@@ -231,15 +305,15 @@ def _remarks(sd, k):
 
 
 def _check_rank(rank, consensus_top):
-    if rank not in ("energy", "consensus"):
-        raise ValueError(f"rank must be 'energy' or 'consensus', got {rank!r}")
+    if rank not in ("energy", "consensus", "interface"):
+        raise ValueError(f"rank must be 'energy', 'consensus' or 'interface', got {rank!r}")
     if not (0.0 < float(consensus_top) <= 1.0):
         raise ValueError(f"consensus_top must be in (0, 1], got {consensus_top}")
 
 
-def _with_consensus(model, rec, lig0, cols, k, key, opts, bad=None):
-    """The consensus part of a pair driver.  opts = None (off) or (rank, cutoff, top); k / key: the pose and the clustering key the
-    driver's own rule gives.  Returns (k, key, extra result entries): under rank "consensus" k is the pose consensus.pick keeps and key
+def _with_consensus(model, rec, lig0, cols, k, key, opts, bad=None, ranked_by="energy"):
+    """The consensus part of a pair driver.  opts = None (off) or (rank, cutoff, top); k / key: the pose and the clustering key chosen so
+    far, `ranked_by` the rule that chose them ("energy": the driver's own; "interface": _interface_pick).  Returns (k, key, extra result entries): under rank "consensus" k is the pose consensus.pick keeps and key
     its order (consensus.rank_positions) - unless no pose has any contact, when both stay and `fallback` says so."""
     if opts is None:
         return k, key, {}
@@ -249,7 +323,6 @@ def _with_consensus(model, rec, lig0, cols, k, key, opts, bad=None):
     cd = ensemble_consensus(model, rec["bb_coords"], lig0, cols["rot_update"], cols["tr_update"], cols["energy"], cutoff, top)
     if bad is not None:      # poses the clash filter removed: no score, so never picked and last in consensus order
         cd["consensus"] = np.where(bad, np.nan, cd["consensus"])
-    ranked_by = "energy"
     if rank == "consensus":
         k2 = CS.pick(cd["consensus"], cols["energy"])
         if k2 is not None:
@@ -654,19 +727,24 @@ def _center(model):
 
 
 def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native=None, cons=None, ster=None, clu=None, refine=None,
-            surf=None):
+            surf=None, ie=None):
     """What every pair driver does with its sampled trajectories: the kept pose, its files and the result.  cols: every trajectory's
     energy, rot_update, tr_update (and the driver's own columns).  pick = (rule, *column names): the driver's own choice, rule(*columns) ->
     index; key: the clustering key that goes with it.  entries(k): the driver's own result entries for the kept pose k.  cons / ster / clu:
-    None or the options of _with_consensus / _screen / _top_models; surf: None or the options of _check_surface; refine: None or the keyword arguments of refine_models - only then
+    None or the options of _with_consensus / _screen / _top_models; surf: None or the options of _check_surface; ie: None or the options of
+    _check_interface; refine: None or the keyword arguments of refine_models - only then
     does the handle outlive the sampling."""
     lig0 = gx.lig_pos0
     if refine is None:      # the columns are host arrays: the handle (and its ~GB of device workspace) goes before any post-processing
         gx.close()
     sd, bad = _screen(model, rec, lig, cols, ster)
     k = _kept(pick[0], bad, *(cols[c] for c in pick[1:]))
-    k, key, extra = _with_consensus(model, rec, lig0, cols, k, _nan_key(key, bad), cons, bad)
+    # the kept pose is settled first - the driver's rule, then rank "interface", then rank "consensus" (one rank is given, so at most one
+    # of the two moves k) - and only then does anything describe it
+    k, key, ed = _interface_pick(model, rec, lig, cols, k, _nan_key(key, bad), ie, bad)
+    k, key, extra = _with_consensus(model, rec, lig0, cols, k, key, cons, bad, "interface" if ie is not None and ie[0] else "energy")
     key = _nan_key(key, bad)      # again: rank "consensus" has replaced the key by consensus.rank_positions
+    extra.update(_interface_result(ed, k, ie, bad, extra["consensus"]["ranked_by"] if "consensus" in extra else "energy"))
     extra.update(_sterics_result(sd, k))
     bd = None if surf is None else ensemble_surface(model, rec, lig, cols["rot_update"], cols["tr_update"], surf[1], surf[2])
     extra.update(_surface_result(bd, k, surf))
@@ -676,11 +754,11 @@ def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_p
     res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, **entries(k)}
     res.update(extra)
-    if cons is not None or ster is not None or surf is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
+    if cons is not None or ster is not None or surf is not None or ie is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
         res.setdefault("trajectories", {c: cols[c] for c in ("energy", "rot_update", "tr_update")})
     _selected_metrics(model, native, rec, lig0, res)
     if clu is not None:
-        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad, bd, None if surf is None else surf[0]))
+        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad, bd, None if surf is None else surf[0], ed))
         if refine is not None:
             refine_models(model, gx, rec, lig, lig0, cols, res["models"], precision=precision, out_pdb=out_pdb, native=native, **refine)
             gx.close()
@@ -691,7 +769,8 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
               out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", restraints=None,
               restraint_rank="satisfied", restraint_params=None, top_k=None, cluster_radius=4.0, cluster_rule="energy", refine_t=None,
               refine_samples=8, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
-              clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, bsa=False, min_bsa=None, probe=1.4, sphere_points=128, **sampler_kw):
+              clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, bsa=False, min_bsa=None, probe=1.4, sphere_points=128,
+              interface_energy=False, ie_weights=None, ie_cutoff=8.0, **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
     pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
     the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
@@ -733,11 +812,20 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     heavy atom and a probe of `probe` A).  The result gains `bsa`, `bsa_rec`, `bsa_lig` (A^2 of the kept pose: both sides, each side),
     `bsa_data` (the arrays), `probe`, `sphere_points`, `index` and `trajectories`; every model of `top_k` gains the three areas.  `min_bsa`
     (implies bsa): cluster centres that bury less than min_bsa A^2 do not become a model of `top_k`; `bsa_dropped` counts them.  It
-    composes with `clash_filter`; the kept pose is not affected."""
+    composes with `clash_filter`; the kept pose is not affected.
+
+    `interface_energy`: the soft Lennard-Jones + Coulomb interface energy of every trajectory (ensemble_interface_energy: heavy-atom
+    pairs within `ie_cutoff` A).  The result gains `interface_energy` ({rep, att, elec, total, n_pairs} of the kept pose in kcal/mol, its
+    rank by total, weights, cutoff, ranked_by), `interface_data` (the arrays), `index` and `trajectories`; every model of `top_k` gains
+    `interface_energy`.  total = ifenergy.total with `ie_weights` (rep, att, elec; None: ifenergy.WEIGHTS - starting values, not
+    fitted).  rank="interface" (implies interface_energy) keeps the pose with the lowest total instead (ties: lower index; it overrides
+    restraint_rank) and makes the totals the clustering key of `top_k`; poses `clash_filter` removed get a NaN key as under rank
+    "consensus"."""
     _check_rank(rank, consensus_top)
     cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
     ster = _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff)
     surf = _check_surface(bsa, min_bsa, probe, sphere_points)
+    ie = _check_interface(interface_energy, rank, ie_weights, ie_cutoff)
     if native is not None:
         _check_native(native, rec, lig)
     if refine_t is not None and top_k is None:
@@ -778,7 +866,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     cols = {c: np.concatenate(v, 0) for c, v in cols.items()}
     if not restrained:
         # the loop's own minimum; consensus and the screen choose among all trajectories at once (the first minimum: the same pose)
-        pick = (np.argmin if cons is not None or ster is not None or surf is not None else (lambda energy: k0), "energy")
+        pick = (np.argmin if cons is not None or ster is not None or surf is not None or ie is not None else (lambda energy: k0), "energy")
         key, entries = cols["energy"], lambda k: {}
     else:
         from . import restraints as RS
@@ -789,14 +877,14 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         entries = lambda k: {"index": k, "restraints": len(restraints), "restraint_rank": restraint_rank,
                              "restraint_energy": float(cols["restraint_energy"][k]), "restraints_satisfied": int(cols["restraints_satisfied"][k]),
                              "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
-    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine, surf)
+    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine, surf, ie)
 
 
 def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
                 out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", perturb=True, restraints=None,
                 restraint_params=None, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
                 clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, start_shift=None, bsa=False, min_bsa=None, probe=1.4,
-                sphere_points=128, **sampler_kw):
+                sphere_points=128, interface_energy=False, ie_weights=None, ie_cutoff=8.0, **sampler_kw):
     """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories
     start from that pose noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps
     down from t_begin; like dock_pair the minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns
@@ -805,12 +893,14 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
     `metrics` of the kept pose and `start_metrics` of the pose the refinement started from.  `consensus` / `rank` / `consensus_top` /
     `consensus_cutoff`: as for dock_pair.  `clash_screen` / `clash_filter` / `clash_cutoff` / `contact_cutoff`: as for dock_pair.
     `bsa` / `min_bsa` / `probe` / `sphere_points`: as for dock_pair (there are no models here, so min_bsa only turns bsa on).
+    `interface_energy` / `ie_weights` / `ie_cutoff` and rank="interface": as for dock_pair.
     `start_shift` ([num_samples,3]): trajectory i starts from the input pose translated by start_shift[i] (the engine's start_pos); the
     shift is added to its tr_update, so (rot_update, tr_update) keep mapping the INPUT pose onto the final one."""
     _check_rank(rank, consensus_top)
     cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
     ster = _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff)
     surf = _check_surface(bsa, min_bsa, probe, sphere_points)
+    ie = _check_interface(interface_energy, rank, ie_weights, ie_cutoff)
     if native is not None:
         _check_native(native, rec, lig)
     if start_shift is not None:
@@ -837,7 +927,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
         done += b
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
     res = _finish(model, gx, rec, lig, cols, (np.argmin, "energy"), None,      # the first minimum wins, as in dock_pair
-                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster, surf=surf)
+                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster, surf=surf, ie=ie)
     if native is not None:
         res["start_metrics"] = native_metrics(model, native, rec["bb_coords"], gx.lig_pos0[None])[0]
     return res
@@ -869,11 +959,12 @@ def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps
     return models
 
 
-def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=None, bad=None, bd=None, min_bsa=None):
+def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=None, bad=None, bd=None, min_bsa=None, ed=None):
     """dock_pair's `models`: the centres of up to top_k clusters in cluster order, each written as <out_pdb stem>_<rank>.pdb.  sd: the
     screen's data (every model gains `sterics`, every file a REMARK line); bad: poses the clash filter removed - their key is NaN, so they
     come last, and a cluster one of them would lead is left out.  bd: the surface data (every model gains bsa, bsa_rec, bsa_lig); min_bsa:
-    a centre that buries less is left out as well, and `bsa_dropped` counts those."""
+    a centre that buries less is left out as well, and `bsa_dropped` counts those.  ed: the interface-energy data (every model gains
+    `interface_energy`)."""
     top_k, radius, rule = clu
     cl = cluster_trajectories(model, lig0, cols["rot_update"], cols["tr_update"], key, radius, rule, top_k)
     models, dropped = [], 0
@@ -890,6 +981,8 @@ def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=
             models[-1]["sterics"] = _pose_sterics(sd, c)
         if bd is not None:
             models[-1].update(_pose_bsa(bd, c))
+        if ed is not None:
+            models[-1]["interface_energy"] = _pose_interface(ed, c)
         if out_pdb:
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c], center=_center(model))
             pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa, remarks=_remarks(sd, c))

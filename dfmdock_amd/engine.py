@@ -226,9 +226,15 @@ class Model:
         `.bsa(rot, tr)` takes P poses in one call."""
         return Surface(self, rec_atoms, rec_radius, lig_atoms, lig_radius, center, probe, points)
 
+    def interface(self, rec_atoms, rec_params, lig_atoms, lig_params, center, cutoff=8.0, soft=0.6, elec_min_dist=3.0, dielectric_slope=4.0):
+        """The heavy atoms of a pair and their (rmin_half, sqrt_eps, charge) rows ([n,3], ifenergy.atom_parameters) prepared for the
+        interface-energy call on the GPU (dfm_iface_create): soft Lennard-Jones plus Coulomb with eps = dielectric_slope r over the pairs
+        within `cutoff` A.  Returns an Interface whose `.energy(rot, tr)` takes P poses in one call."""
+        return Interface(self, rec_atoms, rec_params, lig_atoms, lig_params, center, cutoff, soft, elec_min_dist, dielectric_slope)
+
 
 class _Handle:
-    """What Native, Atoms and Surface share: a handle `_h` made by dfm_<_kind>_create and freed by dfm_<_kind>_destroy - close(), a context
+    """What Native, Atoms, Surface and Interface share: a handle `_h` made by dfm_<_kind>_create and freed by dfm_<_kind>_destroy - close(), a context
     manager, closed when collected."""
     _kind = None
 
@@ -403,6 +409,59 @@ class Surface(_Handle):
         L.check(L.lib().dfm_pose_bsa_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_bsa")
         o["bsa_rec"], o["bsa_lig"] = SF.side_areas(o["class_points"], self.class_radius, self.probe, self.K)
         return o
+
+
+class Interface(_Handle):
+    """The heavy atoms of a receptor / ligand pair with their Lennard-Jones parameters and charges resident on the model's GPU
+    (dfm_iface).  Read-only after creation: `energy` may be called from several threads at once."""
+    _kind = "iface"
+
+    def __init__(self, model: Model, rec_atoms, rec_params, lig_atoms, lig_params, center, cutoff=8.0, soft=0.6, elec_min_dist=3.0,
+                 dielectric_slope=4.0):
+        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _f32(center).reshape(-1)
+        rp, lp = _f32(rec_params), _f32(lig_params)
+        if cen.size != 3:
+            raise ValueError(f"center must have 3 entries, got {np.shape(center)}")
+        if rp.shape != (ra.shape[0], 3) or lp.shape != (la.shape[0], 3):
+            raise ValueError(f"one (rmin_half, sqrt_eps, charge) row per atom: receptor {ra.shape[0]} / {rp.shape}, ligand {la.shape[0]} / {lp.shape}")
+        self.model, self.Ar, self.Al = model, ra.shape[0], la.shape[0]
+        self.cutoff, self.soft, self.elec_min_dist, self.dielectric_slope = (float(np.float32(v)) for v in
+                                                                             (cutoff, soft, elec_min_dist, dielectric_slope))
+        rc, lc = (tuple(np.ascontiguousarray(p[:, k]) for k in range(3)) for p in (rp, lp))
+        self._h = L.lib().dfm_iface_create(model._h, self.Ar, _p(ra), _p(rc[0]), _p(rc[1]), _p(rc[2]), self.Al, _p(la), _p(lc[0]), _p(lc[1]),
+                                           _p(lc[2]), _p(cen), float(cutoff), float(soft), float(elec_min_dist), float(dielectric_slope))
+        self._created()
+
+    def info(self):
+        """{n_cells, max_cell_atoms, cell_edge} of the receptor's grid and sum_bound_q, the creator's bound on the magnitude of every
+        integer sum of a call in quanta (dfm_iface_info)."""
+        n, mx, e, b = C.c_int32(0), C.c_int32(0), C.c_float(0), C.c_double(0)
+        L.check(L.lib().dfm_iface_info(self._h, C.byref(n), C.byref(mx), C.byref(e), C.byref(b)), "dfm_iface_info")
+        return {"n_cells": n.value, "max_cell_atoms": mx.value, "cell_edge": e.value, "sum_bound_q": b.value}
+
+    def energy(self, rot, tr, per_atom=False, chunk_poses=0):
+        """Interface energy of P poses (dfm_pose_iface_energy; the float64 definition is ifenergy.interface_energy): rot [P,3] axis-angle
+        and tr [P,3] as rot_update / tr_update hold them.  Returns {rep_q, att_q, elec_q, n_pairs (int64 [P]; quanta of 2^-20
+        kcal/mol)}, with `per_atom` lig_vdw_q / lig_elec_q (int64 [P,Al], the caller's atom order), and rep, att, elec (float64 [P],
+        kcal/mol = q * 2^-20)."""
+        from . import ifenergy as IE
+        r, t, P = _rigid_poses(rot, tr)
+        o = {k: np.zeros(P, np.int64) for k in ("rep_q", "att_q", "elec_q", "n_pairs")}
+        if per_atom:
+            o["lig_vdw_q"], o["lig_elec_q"] = np.zeros((P, self.Al), np.int64), np.zeros((P, self.Al), np.int64)
+        out = L.IfaceOutC()
+        for k, v in o.items():
+            setattr(out, k, v.ctypes.data_as(C.POINTER(C.c_int64)))
+        L.check(L.lib().dfm_pose_iface_energy_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_iface_energy")
+        o["rep"], o["att"], o["elec"] = IE.kcal(o["rep_q"]), IE.kcal(o["att_q"]), IE.kcal(o["elec_q"])
+        return o
+
+
+def iface_last_timing():
+    """(host-to-device copy ms, kernel ms) of this thread's last Interface.energy call (dfm_iface_last_timing)."""
+    a, b = C.c_double(0), C.c_double(0)
+    L.check(L.lib().dfm_iface_last_timing(C.byref(a), C.byref(b)), "dfm_iface_last_timing")
+    return a.value, b.value
 
 
 def bsa_last_timing():

@@ -517,6 +517,47 @@ int dfm_pose_bsa_chunked(dfm_surface *s, int P, const float *rot, const float *t
 /* GPU milliseconds of the calling thread's last dfm_pose_bsa, summed over its chunks: the host-to-device copies of the poses and the
  * kernels (k_surface_pose, k_surface, k_surface_finish, the memsets of the masks and of the per-atom output) - tools/surface_bench.py */
 int dfm_bsa_last_timing(double *copy_ms, double *kernel_ms);
+/* Interface energy of P rigid poses of one ligand: soft Lennard-Jones plus Coulomb with the dielectric eps = dielectric_slope r over the
+ * heavy-atom pairs of the two chains within a cutoff - the physics rescoring step of docking pipelines.  dfmdock_amd/ifenergy.py is the
+ * float64 definition these calls are tested against.  Atoms, centre and poses as for dfm_atoms_create / dfm_pose_sterics.  Per atom:
+ * rmin_half (A, in (0, 8]), sqrt_eps (sqrt(kcal/mol), in [0, 2]), charge (e, |q| <= 4).  Scalars: cutoff (A, in (0, 16]; 8.0 is usual),
+ * soft (in [0.5, 1]; 0.6), elec_min_dist (A, >= 1; 3.0), dielectric_slope (> 0; 4.0).  The cutoff is a plain truncation, no switching.
+ *   per pair, fp64 on the widened fp32 inputs, in this order of operations (no square root, one division per term):
+ *     r2 = (dx*dx + dy*dy) + dz*dz; the pair counts iff r2 < cutoff*cutoff (strict; a NaN is no pair)
+ *     Rm = rh_a + rh_b; f = soft*Rm; r2v = r2 < f*f ? f*f : r2; s2 = (Rm*Rm)/r2v; s6 = (s2*s2)*s2; e = se_a*se_b
+ *     rep = e*(s6*s6); att = -2.0*(e*s6); m = elec_min_dist; r2c = r2 < m*m ? m*m : r2
+ *     elec = ((332.0637/dielectric_slope)*(q_a*q_b))/r2c
+ *   each term is rounded on its own to quanta of 2^-20 kcal/mol: Q(x) = (int64) rint(x * 2^20), ties to even.
+ *   rep_q, att_q, elec_q [P]: int64 sums of the rounded terms over the pose's pairs; n_pairs [P]: their number; lig_vdw_q (rep + att) and
+ *     lig_elec_q [P,Al]: the same sums per ligand atom, in the caller's atom order.  kcal/mol = q * 2^-20.
+ *   A pose with a NaN or infinite rot / tr gets zeros and disturbs no other pose (not an error).
+ * Every output pointer may be NULL.  The sums are integer sums: the results equal the definition's, and none depends on P, on a pose's
+ * index, on the order of the poses or on the chunks of a call.  dfm_iface_create bins the receptor into cells of the cutoff and rejects
+ * a complex whose sums could reach 2^62 quanta: pairs of one pose <= Al min(Ar, 27 max_cell_atoms), times the largest term its own
+ * parameters allow (dfm_poseprep.h: iface_sum_bound); dfm_iface_info reports cells, the most atoms in one cell, the cell edge and that
+ * bound in quanta.  Per-atom output is produced chunk_poses poses at a time (0: as many as fill 64 MiB of it; without it 32768).
+ * DFM_E_INVALID / NULL, nothing enqueued: a NULL pointer among the inputs, Ar or Al < 1 or > 2^24, a non-finite atom, centre or
+ * parameter, a parameter or scalar outside the limits above, a receptor bounding box of more than 2^24 cells, the sum bound,
+ * chunk_poses < 0, P < 1.  DFM_E_OOM when the atoms or a chunk's per-atom output do not fit.
+ * Takes the MODEL handle for its device only.  The handle is read-only after creation; every call owns a non-blocking stream and its
+ * device temporaries, so calls on one handle may run from several host threads at once.  No reference call has a counterpart. */
+typedef struct dfm_iface dfm_iface;
+typedef struct {
+    int64_t *rep_q, *att_q, *elec_q;   /* [P]    or NULL */
+    int64_t *n_pairs;                  /* [P]    or NULL */
+    int64_t *lig_vdw_q, *lig_elec_q;   /* [P,Al] or NULL */
+} dfm_iface_out;
+dfm_iface *dfm_iface_create(dfm_model *m, int Ar, const float *rec_atoms, const float *rec_rmin_half, const float *rec_sqrt_eps,
+                            const float *rec_charge, int Al, const float *lig_atoms, const float *lig_rmin_half, const float *lig_sqrt_eps,
+                            const float *lig_charge, const float center[3], float cutoff, float soft, float elec_min_dist,
+                            float dielectric_slope);
+void dfm_iface_destroy(dfm_iface *h);
+int dfm_iface_info(const dfm_iface *h, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge, double *sum_bound_q);
+int dfm_pose_iface_energy(dfm_iface *h, int P, const float *rot, const float *tr, dfm_iface_out *out);
+int dfm_pose_iface_energy_chunked(dfm_iface *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_iface_out *out);
+/* GPU milliseconds of the calling thread's last dfm_pose_iface_energy, summed over its chunks: the host-to-device copies of the poses
+ * and the kernels (k_iface_pose, k_iface, the memsets of the per-atom output) - tools/iface_bench.py */
+int dfm_iface_last_timing(double *copy_ms, double *kernel_ms);
 /* edges per node for this complex: min(N,20) + min(40, N-20) */
 int dfm_complex_degree(const dfm_complex *cx);
 /* Device blocks released by destroyed handles are parked per device for the next handle (a set driver creates and destroys a
