@@ -49,6 +49,8 @@ EXPORTS = [
     "dfm_surface_create", "dfm_surface_destroy", "dfm_surface_info", "dfm_pose_bsa", "dfm_pose_bsa_chunked", "dfm_bsa_last_timing",
     "dfm_iface_create", "dfm_iface_destroy", "dfm_iface_info", "dfm_pose_iface_energy", "dfm_pose_iface_energy_chunked",
     "dfm_iface_last_timing",
+    "dfm_rescon_create", "dfm_rescon_destroy", "dfm_rescon_info", "dfm_pose_rescon", "dfm_pose_rescon_chunked", "dfm_rescon_last_timing",
+    "dfm_rescon_last_phases",
 ]
 
 
@@ -137,6 +139,10 @@ class IfaceOutC(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_int64)) for n in ("rep_q", "att_q", "elec_q", "n_pairs", "lig_vdw_q", "lig_elec_q")]
 
 
+class ResconOutC(C.Structure):
+    _fields_ = [(n, I32P) for n in ("ic", "n_pairs", "n_rec_res", "n_lig_res", "rec_degree", "lig_degree")] + [("contact_bits", U32P)]
+
+
 _lib = None
 
 
@@ -221,6 +227,16 @@ def lib():
     L.dfm_pose_iface_energy.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.POINTER(IfaceOutC)]
     L.dfm_pose_iface_energy_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(IfaceOutC)]
     L.dfm_iface_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_rescon_create.argtypes = [C.c_void_p, C.c_int, F32P, I32P, C.c_int, C.POINTER(C.c_uint8), C.c_int, F32P, I32P, C.c_int,
+                                    C.POINTER(C.c_uint8), F32P, C.c_float]
+    L.dfm_rescon_create.restype = C.c_void_p
+    L.dfm_rescon_destroy.argtypes = [C.c_void_p]
+    L.dfm_rescon_destroy.restype = None
+    L.dfm_rescon_info.argtypes = [C.c_void_p, I32P, I32P, F32P, I32P, I32P]
+    L.dfm_pose_rescon.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.POINTER(ResconOutC)]
+    L.dfm_pose_rescon_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(ResconOutC)]
+    L.dfm_rescon_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_rescon_last_phases.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_trim_cache.argtypes = [C.c_int]
     L.dfm_trim_cache.restype = C.c_longlong
     L.dfm_alloc_diag.argtypes = [C.POINTER(C.c_int64)]

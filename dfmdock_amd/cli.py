@@ -15,6 +15,7 @@
     python -m dfmdock_amd dock|refine ... --write-restraints consensus.txt --restraint-top 10 [--restraint-upper 8.0]
     python -m dfmdock_amd sweep ... --consensus [--consensus-top 0.5]
     python -m dfmdock_amd dock|refine ... --interface-energy [--rank interface] [--ie-weights 0.18 1.0 0.5] [--ie-cutoff 8.0] [--energy-residues FILE]
+    python -m dfmdock_amd dock|refine ... --affinity [--affinity-cutoff 5.5] [--contact-residues FILE]
     python -m dfmdock_amd dock|refine ... --clash-screen [--clash-filter] [--clash-cutoff 3.0] [--contact-cutoff 5.0] [--clash-residues FILE]
 
   dock       <- src/inference_single.py:1-12 -> inference() (src/inference_base.py:601-670): num_samples (120) trajectories of
@@ -69,6 +70,13 @@
              the totals the clustering key of --top-k; with --clash-filter the flagged poses are out, as under --rank consensus);
              total = w_rep rep + w_att att + w_elec elec with --ie-weights (default 0.18 1.0 0.5: ZRANK-like starting values, not
              fitted); `--energy-residues FILE` lists the kept model's unweighted sums per ligand residue.
+  affinity   no reference counterpart: which residues touch which over all heavy atoms, on the GPU (dfmdock_amd/affinity.py,
+             dfm_pose_rescon) - the residue pairs with two heavy atoms closer than --affinity-cutoff (5.5 A), counted by residue class -
+             and the contacts-based affinity estimate IC-NIS over them and the non-interacting surface.  `dock / refine --affinity` add an
+             `affinity` object (ic = AA AP AC PP PC CC, n_pairs, n_rec_res, n_lig_res, nis_apolar, nis_charged, dg in kcal/mol, kd in M)
+             for the kept pose and for every --top-k model; `--contact-residues FILE` lists the kept model's residue pairs.  The
+             coefficients, class tables and reference areas are starting values that are not verified or calibrated, the surface is this
+             project's own Shrake-Rupley, and no agreement with the PRODIGY server is claimed.  Nothing is ranked by it.
   selfcheck  no reference counterpart: dfm_complex_selfcheck on the pair (what `dock` and `sweep` run once per complex anyway).
 
 --ckpt takes the Lightning checkpoint the reference loads (src/inference_base.py:611-616; read without Lightning / omegaconf by
@@ -131,6 +139,16 @@ def _add_interface(p):
                    help="write the kept model's LJ and Coulomb interface energy per ligand residue (implies --interface-energy)")
 
 
+def _add_affinity(p):
+    p.add_argument("--affinity", action="store_true",
+                   help="residue contacts by class and the contacts-based affinity estimate of every trajectory (adds an `affinity` object "
+                        "to the result line and to every model; IC-NIS with starting values that are not calibrated)")
+    p.add_argument("--affinity-cutoff", type=float, default=None, metavar="A",
+                   help="with --affinity: heavy-atom distance of a residue contact (default 5.5, at most 16)")
+    p.add_argument("--contact-residues", default=None, metavar="FILE",
+                   help="write the kept model's residue pairs in contact, one per line (implies --affinity)")
+
+
 def _add_surface(p):
     p.add_argument("--bsa", action="store_true",
                    help="buried solvent-accessible surface area of every trajectory (adds bsa, bsa_rec, bsa_lig in A^2 to the result line and to every model)")
@@ -183,6 +201,7 @@ def build_parser():
     _add_sterics(d)
     _add_surface(d)
     _add_interface(d)
+    _add_affinity(d)
     _add_common(d)
     r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)")
     r.add_argument("pdb_1", help="receptor PDB")
@@ -199,6 +218,7 @@ def build_parser():
     _add_sterics(r)
     _add_surface(r)
     _add_interface(r)
+    _add_affinity(r)
     _add_common(r)
     s = sub.add_parser("sweep", help="sample every complex of a DB5-style directory (inference_mlsb.py run_sampling)")
     s.add_argument("--db5", required=True, help="directory of <id>.pt files (+ optional test.txt with the ids to run)")
@@ -284,6 +304,14 @@ def parse_args(argv=None):
             ap.error("--ie-cutoff must be in (0, 16]")
         if args.ie_weights is not None and not np.isfinite(args.ie_weights).all():
             ap.error("--ie-weights must be finite")
+    if args.cmd in ("dock", "refine"):
+        if args.contact_residues:
+            args.affinity = True
+        if not args.affinity and args.affinity_cutoff is not None:
+            ap.error("--affinity-cutoff is the cutoff of --affinity: it needs it")
+        args.affinity_cutoff = 5.5 if args.affinity_cutoff is None else args.affinity_cutoff
+        if not (np.isfinite(args.affinity_cutoff) and 0 < args.affinity_cutoff <= 16):
+            ap.error("--affinity-cutoff must be in (0, 16]")
     if args.cmd in ("dock", "refine", "sweep"):
         if args.consensus_top is not None and not args.consensus:
             ap.error("--consensus-top selects the members of the consensus ensemble: it needs --consensus")
@@ -427,6 +455,28 @@ def interface_outputs(args, model, res, rec, lig, line):
         line.update(energy_residues=os.path.abspath(args.energy_residues))
 
 
+def affinity_kwargs(args):
+    """Driver keyword arguments of the affinity flags of dock / refine: none without them."""
+    if not args.affinity:
+        return {}
+    return dict(affinity=True, affinity_cutoff=args.affinity_cutoff)
+
+
+def affinity_outputs(args, model, res, rec, lig, line):
+    """The affinity part of a dock / refine result: the `affinity` object of the line and --contact-residues."""
+    if not args.affinity:
+        return
+    line.update(affinity=res["affinity"], index=res["index"])
+    if "affinity_data" in res and sum(res["affinity_data"]["unclassified"]):      # residue names outside the 20: counted as apolar
+        line.update(affinity_unclassified=[int(v) for v in res["affinity_data"]["unclassified"]])
+    if args.contact_residues:
+        from . import driver
+        from .affinity import pairs_of, write_contact_residues
+        cd = driver.ensemble_contacts(model, rec, lig, res["rot_update"], res["tr_update"], args.affinity_cutoff, bits=True)
+        write_contact_residues(args.contact_residues, cd["rec_keys"], cd["lig_keys"], pairs_of(cd["contact_bits"][0]))
+        line.update(contact_residues=os.path.abspath(args.contact_residues))
+
+
 def surface_kwargs(args):
     """Driver keyword arguments of the surface flags of dock / refine: none without them."""
     if not args.bsa:
@@ -561,6 +611,7 @@ def cmd_dock(args):
     kw.update(sterics_kwargs(args))
     kw.update(surface_kwargs(args))
     kw.update(interface_kwargs(args))
+    kw.update(affinity_kwargs(args))
     res = driver.dock_pair(model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                            precision=args.precision, out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
                            on_selfcheck_fail=args.on_selfcheck_fail, **kw)
@@ -581,6 +632,7 @@ def cmd_dock(args):
     sterics_outputs(args, model, res, rec, lig, line)
     surface_outputs(args, model, res, rec, lig, line)
     interface_outputs(args, model, res, rec, lig, line)
+    affinity_outputs(args, model, res, rec, lig, line)
     print(json.dumps(line), flush=True)
     if args.json:
         extra = {}
@@ -605,6 +657,7 @@ def cmd_refine(args):
     kw.update(sterics_kwargs(args))
     kw.update(surface_kwargs(args))
     kw.update(interface_kwargs(args))
+    kw.update(affinity_kwargs(args))
     res = driver.refine_pair(model, rec, lig, rec_x, lig_x, t_begin=args.t_begin, num_samples=args.num_samples, num_steps=args.num_steps,
                              seed=args.seed, precision=args.precision, out_pdb=args.out, max_batch=args.max_batch,
                              selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, perturb=not args.no_perturb, **kw)
@@ -618,6 +671,7 @@ def cmd_refine(args):
     sterics_outputs(args, model, res, rec, lig, line)
     surface_outputs(args, model, res, rec, lig, line)
     interface_outputs(args, model, res, rec, lig, line)
+    affinity_outputs(args, model, res, rec, lig, line)
     print(json.dumps(line), flush=True)
     if args.json:
         with open(args.json, "w") as f:

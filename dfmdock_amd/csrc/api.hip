@@ -939,7 +939,7 @@ extern "C" int dfm_restraint_eval(dfm_complex *cx, int B, const float *lig_pos, 
 // several host threads, and next to that model's complex handles, do not share any state.
 // the two millisecond figures of this thread's last call of each kind, behind the dfm_*_last_timing getters: k_pose_dist and the
 // clustering kernels for MS_CLUSTER, host-to-device copies and kernels for the others
-enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_IFACE, MS_KINDS };
+enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_IFACE, MS_RESCON, MS_KINDS };
 static thread_local double g_last_ms[MS_KINDS][2] = {};
 
 static void set_last_ms(int kind, double a, double b)
@@ -1015,7 +1015,7 @@ struct PoseCall {
     }
 };
 
-// the chunk loop of the rigid-pose calls (dfm_pose_sterics, dfm_pose_bsa, dfm_pose_iface_energy): the chunk's (rot, tr) on the device, their transforms T, and
+// the chunk loop of the rigid-pose calls (dfm_pose_sterics, dfm_pose_bsa, dfm_pose_iface_energy, dfm_pose_rescon): the chunk's (rot, tr) on the device, their transforms T, and
 // the call's copy / kernel milliseconds from the call's own events.  Per chunk: upload, the caller's memsets and launches, kernels_done,
 // the caller's downloads, finish
 struct PoseChunks {
@@ -2010,6 +2010,184 @@ extern "C" int dfm_pose_iface_energy(dfm_iface *h, int P, const float *rot, cons
 extern "C" int dfm_iface_last_timing(double *copy_ms, double *kernel_ms)
 {
     return last_timing(MS_IFACE, copy_ms, kernel_ms);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Residue contacts (kernels_rescon.hip).  A dfm_rescon holds what the two atom sets, their residues, the classes, the cutoff and the
+// rotation centre fix - the receptor's grid of cells of the cutoff, the ligand in blocks of 64 neighbours, each atom's residue index in
+// its float4, the receptor's class masks - and is read-only after creation; every dfm_pose_rescon call owns its stream, its bitmap
+// and its other temporaries.
+struct dfm_rescon {
+    int device = 0, Ar = 0, Al = 0, Rr = 0, Lr = 0, W = 0, n_cells = 0, max_cell_atoms = 0, default_chunk = 0;
+    float cell_edge = 0.f;
+    DevPool pool;      // unbound: released under a device-wide wait, like a model's
+    float *rec = nullptr, *lig = nullptr, *sphere = nullptr;
+    int32_t *cell_start = nullptr, *lig_class = nullptr;
+    uint32_t *class_mask = nullptr;
+    ResconConst sc = {};
+};
+
+// zeroing the bitmap, k_rescon_pose + k_rescon, k_rescon_finish of this thread's last dfm_pose_rescon, summed over its chunks
+static thread_local double g_rescon_phase_ms[3] = {};
+
+extern "C" void dfm_rescon_destroy(dfm_rescon *h)
+{
+    if (!h) return;
+    DeviceScope ds(h->device);
+    h->pool.release();
+    delete h;
+}
+
+extern "C" dfm_rescon *dfm_rescon_create(dfm_model *m, int Ar, const float *rec_atoms, const int32_t *rec_res, int Rr, const uint8_t *rec_class,
+                                         int Al, const float *lig_atoms, const int32_t *lig_res, int Lr, const uint8_t *lig_class,
+                                         const float center[3], float cutoff)
+{
+    auto bad = [](int code, const std::string &msg) -> dfm_rescon * { (void)fail(code, msg); return nullptr; };
+    if (!m) return bad(DFM_E_INVALID, "m is NULL");
+    if (const std::string msg = check_atom_sets(Ar, rec_atoms, Al, lig_atoms, center); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_rescon_chain("rec", Ar, rec_res, Rr, rec_class); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_rescon_chain("lig", Al, lig_res, Lr, lig_class); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_rescon_cutoff(cutoff); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    // the receptor's grid: origin = the bounding box's low corner, edge = the cutoff
+    CellGrid gr;
+    if (!build_cell_grid(Ar, rec_atoms, (double)cutoff, gr))
+        return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells of the cutoff");
+    double maxabs = 0.0;
+    for (int k = 0; k < 3; ++k) maxabs = std::max(maxabs, std::max(std::fabs(gr.lo[k]), std::fabs(gr.hi[k])));
+    maxabs += 2.0 * (double)cutoff + 1.0;
+    // the fp32 reject threshold (dfm_posewalk.h): cutoff * 1.0001 + slack
+    const float thr = cutoff * 1.0001f + pose_slack(maxabs);
+    ResconConst sc = {};
+    sc.g = walk_grid(gr, (double)cutoff, (double)thr, center);
+    sc.cutoff = (double)cutoff;
+    sc.reject2 = thr * thr;
+    double llo[3] = {(double)lig_atoms[0], (double)lig_atoms[1], (double)lig_atoms[2]};
+    for (int i = 1; i < Al; ++i)
+        for (int k = 0; k < 3; ++k) llo[k] = std::min(llo[k], (double)lig_atoms[(size_t)i * 3 + k]);
+    const LigandBlocks lb = build_ligand_blocks(Al, lig_atoms, llo, sc.g.edge, sc.g.center);
+    if (!lb.finite) return bad(DFM_E_INVALID, "lig_atoms / center: the ligand's extent about the centre overflows fp32");
+    const std::vector<float> rec4 = gather4_res(gr.order, rec_atoms, rec_res), lig4 = gather4_res(lb.index, lig_atoms, lig_res);
+    const std::vector<uint32_t> masks = rescon_class_masks(Rr, rec_class);
+    const std::vector<int32_t> lcls(lig_class, lig_class + Lr);
+    DeviceScope ds(m->device);
+    if (ds.err != hipSuccess) return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err));
+    dfm_rescon *h = new dfm_rescon;
+    h->device = m->device; h->Ar = Ar; h->Al = Al; h->Rr = Rr; h->Lr = Lr; h->W = rescon_words(Rr); h->sc = sc;
+    h->n_cells = sc.g.nx * sc.g.ny * sc.g.nz; h->max_cell_atoms = gr.max_cell; h->cell_edge = cutoff;
+    h->default_chunk = rescon_chunk_poses(Lr, Rr);
+    hipError_t e = hipSuccess;
+    {
+        PoseCall c;
+        e = c.open();
+        if (e == hipSuccess) e = h->pool.upload_async(&h->rec, rec4.data(), rec4.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->cell_start, gr.start.data(), gr.start.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->lig, lig4.data(), lig4.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->sphere, lb.sphere.data(), lb.sphere.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->class_mask, masks.data(), masks.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->lig_class, lcls.data(), lcls.size(), c.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
+    }      // the call's stream has drained: the host vectors it read may go
+    if (e != hipSuccess) {
+        h->pool.release();
+        delete h;
+        return bad(e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP, std::string("dfm_rescon_create: ") + hipGetErrorString(e));
+    }
+    return h;
+}
+
+extern "C" int dfm_rescon_info(const dfm_rescon *h, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge, int32_t *row_words,
+                               int32_t *chunk_poses)
+{
+    if (!h) return fail(DFM_E_INVALID, "NULL argument");
+    if (n_cells) *n_cells = h->n_cells;
+    if (max_cell_atoms) *max_cell_atoms = h->max_cell_atoms;
+    if (cell_edge) *cell_edge = h->cell_edge;
+    if (row_words) *row_words = h->W;
+    if (chunk_poses) *chunk_poses = h->default_chunk;
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_rescon_chunked(dfm_rescon *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_rescon_out *out)
+{
+    if (!h) return fail(DFM_E_INVALID, "h is NULL");
+    if (!rot) return fail(DFM_E_INVALID, "rot is NULL");
+    if (!tr) return fail(DFM_E_INVALID, "tr is NULL");
+    if (!out) return fail(DFM_E_INVALID, "out is NULL");
+    if (P < 1 || P > RESCON_MAX_POSES) return fail(DFM_E_INVALID, "need 1 <= P <= " + std::to_string(RESCON_MAX_POSES));
+    if (chunk_poses < 0) return fail(DFM_E_INVALID, "chunk_poses must be >= 0");
+    DEVICE_SCOPE(h->device);
+    PoseCall c;
+    HIPCHK(c.open());
+    // the call's chunk, else as many poses as fill RESCON_SCRATCH_BYTES of bitmap
+    const int Pc = std::min(P, chunk_poses > 0 ? std::min(chunk_poses, RESCON_MAX_CHUNK) : h->default_chunk);
+    const size_t Rr = (size_t)h->Rr, Lr = (size_t)h->Lr, row = Lr * (size_t)h->W;
+    PoseChunks ch{c, rot, tr};
+    uint32_t *d_bits = nullptr;
+    int32_t *d_tot = nullptr, *d_rd = nullptr, *d_ld = nullptr;
+    HIPCHK(ch.open(Pc));
+    HIPCHK(c.tmp.alloc(&d_bits, (size_t)Pc * row));
+    HIPCHK(c.tmp.alloc(&d_tot, (size_t)Pc * 9));
+    if (out->rec_degree) HIPCHK(c.tmp.alloc(&d_rd, (size_t)Pc * Rr));
+    if (out->lig_degree) HIPCHK(c.tmp.alloc(&d_ld, (size_t)Pc * Lr));
+    const ResconAtoms at = {h->rec, h->lig, h->sphere, h->cell_start, h->lig_class, h->class_mask, h->sc, h->Ar, h->Al, h->Rr, h->Lr, h->W};
+    std::vector<int32_t> h_tot((size_t)Pc * 9);
+    // the call's own events split the kernel time into its three phases: ev[1] .. zeroed .. c.ev[3] (walked) .. ev[2]
+    struct Ev {
+        hipEvent_t e = nullptr;
+        ~Ev() { if (e) (void)hipEventDestroy(e); }
+    } zeroed;
+    HIPCHK(hipEventCreate(&zeroed.e));
+    double phase[3] = {0.0, 0.0, 0.0};
+    for (int p0 = 0; p0 < P; p0 += Pc) {
+        const int n = std::min(Pc, P - p0);
+        HIPCHK(ch.upload(p0, n));
+        HIPCHK(hipMemsetAsync(d_bits, 0, (size_t)n * row * sizeof(uint32_t), c.s));
+        HIPCHK(hipEventRecord(zeroed.e, c.s));
+        HIPCHK(launch_rescon_pose(ch.d_rot, ch.d_tr, n, ch.T, c.s));
+        HIPCHK(launch_rescon(at, ch.T, n, d_bits, c.s));
+        HIPCHK(hipEventRecord(c.ev[3], c.s));
+        HIPCHK(launch_rescon_finish(at, d_bits, n, d_tot, d_rd, d_ld, c.s));
+        HIPCHK(ch.kernels_done());
+        HIPCHK(hipMemcpyAsync(h_tot.data(), d_tot, (size_t)n * 9 * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        if (d_rd) HIPCHK(hipMemcpyAsync(out->rec_degree + (size_t)p0 * Rr, d_rd, (size_t)n * Rr * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        if (d_ld) HIPCHK(hipMemcpyAsync(out->lig_degree + (size_t)p0 * Lr, d_ld, (size_t)n * Lr * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        if (out->contact_bits)
+            HIPCHK(hipMemcpyAsync(out->contact_bits + (size_t)p0 * row, d_bits, (size_t)n * row * sizeof(uint32_t), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(ch.finish());
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, c.ev[1], zeroed.e) == hipSuccess) phase[0] += ms;
+        if (hipEventElapsedTime(&ms, zeroed.e, c.ev[3]) == hipSuccess) phase[1] += ms;
+        if (hipEventElapsedTime(&ms, c.ev[3], c.ev[2]) == hipSuccess) phase[2] += ms;
+        for (int p = 0; p < n; ++p) {
+            const int32_t *t = h_tot.data() + (size_t)p * 9;
+            if (out->ic) std::memcpy(out->ic + (size_t)(p0 + p) * 6, t, 6 * sizeof(int32_t));
+            if (out->n_pairs) out->n_pairs[p0 + p] = t[6];
+            if (out->n_rec_res) out->n_rec_res[p0 + p] = t[7];
+            if (out->n_lig_res) out->n_lig_res[p0 + p] = t[8];
+        }
+    }
+    set_last_ms(MS_RESCON, ch.copy_ms, ch.kernel_ms);
+    for (int k = 0; k < 3; ++k) g_rescon_phase_ms[k] = phase[k];
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_rescon(dfm_rescon *h, int P, const float *rot, const float *tr, dfm_rescon_out *out)
+{
+    return dfm_pose_rescon_chunked(h, P, rot, tr, 0, out);
+}
+
+extern "C" int dfm_rescon_last_timing(double *copy_ms, double *kernel_ms)
+{
+    return last_timing(MS_RESCON, copy_ms, kernel_ms);
+}
+
+extern "C" int dfm_rescon_last_phases(double *zero_ms, double *walk_ms, double *finish_ms)
+{
+    if (!zero_ms || !walk_ms || !finish_ms) return fail(DFM_E_INVALID, "NULL argument");
+    *zero_ms = g_rescon_phase_ms[0];
+    *walk_ms = g_rescon_phase_ms[1];
+    *finish_ms = g_rescon_phase_ms[2];
+    return DFM_OK;
 }
 
 extern "C" int dfm_complex_degree(const dfm_complex *cx) { return cx ? cx->K : -1; }

@@ -490,6 +490,32 @@ hipError_t launch_iface_pose(const float *rot, const float *tr, int n, double *T
 // n <= 65535 poses.  tot [n][4] is added to.  lig_vdw / lig_elec [n][Al] (caller's atom order) or nullptr: written by the waves that
 // reach the cell walk only, so zero them first
 hipError_t launch_iface(const IfaceAtoms &at, const double *T, int n, int64_t *tot, int64_t *lig_vdw, int64_t *lig_elec, hipStream_t s);
+// residue contacts (kernels_rescon.hip; include/dfmdock_amd.h: dfm_rescon_create / dfm_pose_rescon).  What the atoms and the cutoff fix:
+// the receptor's grid of cells of the cutoff, the cutoff as the definition's double and the fp32 reject threshold squared (g.grow is
+// that threshold as a double, as in StericsConst).
+struct ResconConst {
+    WalkGrid g;
+    double cutoff;
+    float reject2;
+};
+// device arrays of a dfm_rescon: rec / lig / sphere / cell_start as in StericsAtoms, except that the fourth component of every rec / lig
+// float4 holds the bits of the atom's residue index; class_mask [3][W] = the receptor residues of each class as bits; lig_class [Lr].
+// Rr / Lr residues, W = ceil(Rr / 32) words per bitmap row
+struct ResconAtoms {
+    const float *rec, *lig, *sphere;
+    const int32_t *cell_start, *lig_class;
+    const uint32_t *class_mask;
+    ResconConst sc;
+    int Ar, Al, Rr, Lr, W;
+};
+// T [n][12]: R(rot) row-major and tr as doubles
+hipError_t launch_rescon_pose(const float *rot, const float *tr, int n, double *T, hipStream_t s);
+// n <= 65535 poses.  bits [n][Lr][W]: zero it first; bit i & 31 of word i >> 5 of row j is set for every residue pair (i, j) in contact
+hipError_t launch_rescon(const ResconAtoms &at, const double *T, int n, uint32_t *bits, hipStream_t s);
+// tot [n][9] = ic [6] (AA, AP, AC, PP, PC, CC), n_pairs, n_rec_res, n_lig_res of each pose, every entry written; rec_degree [n][Rr] /
+// lig_degree [n][Lr] or nullptr
+hipError_t launch_rescon_finish(const ResconAtoms &at, const uint32_t *bits, int n, int32_t *tot, int32_t *rec_degree, int32_t *lig_degree,
+                                hipStream_t s);
 
 // isolated exposure of one chain on the host, as the definition takes it (kernels_surface.hip)
 void surface_exposure(int n, const float *xyz, const float *radius, double probe, int K, const float *dirs, const double lo[3],

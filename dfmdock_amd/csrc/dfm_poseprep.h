@@ -1,11 +1,14 @@
-// dfm_poseprep.h - host preparation of the per-pose all-atom calls (api.hip: dfm_atoms_create, dfm_surface_create, dfm_iface_create):
-// argument checks, the cell grid of a chain, the ligand in blocks of 64 neighbours, the rounding slack, the interface energy's parameter
-// limits and overflow bound.  Plain C++ without a HIP call, so that tests/test_pose_prep_cpu.py and tests/test_ifenergy_cpu.py run it
-// under the sanitizers without a GPU.
+// dfm_poseprep.h - host preparation of the per-pose all-atom calls (api.hip: dfm_atoms_create, dfm_surface_create, dfm_iface_create,
+// dfm_rescon_create): argument checks, the cell grid of a chain, the ligand in blocks of 64 neighbours, the rounding slack, the interface
+// energy's parameter limits and overflow bound, the residue contacts' limits, residue bits, class masks and chunk size.  Plain C++ without
+// a HIP call, so that tests/test_pose_prep_cpu.py, tests/test_ifenergy_cpu.py and tests/test_affinity_cpu.py run it under the
+// sanitizers without a GPU.
 #pragma once
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
@@ -241,6 +244,64 @@ inline std::vector<float> gather_iface(const std::vector<int32_t> &order, const 
         v[q * 4 + 2] = charge[order[q]];
     }
     return v;
+}
+
+// Residue contacts (api.hip: dfm_rescon_create; kernels_rescon.hip).  The limits: residues per chain, poses per call, and the bytes of
+// bitmap [poses of a chunk][Lr][W] a call may hold, which fix the chunk.
+constexpr int RESCON_MAX_RES = 4096, RESCON_MAX_POSES = 65536, RESCON_MAX_CHUNK = 32768;
+constexpr size_t RESCON_SCRATCH_BYTES = (size_t)64 << 20;
+
+// words of one bitmap row: one bit per receptor residue
+inline int rescon_words(int Rr) { return (Rr + 31) / 32; }
+
+// the residue index of every atom [n] and the class of every residue [n_res] of one chain (`who`: "rec" or "lig"): the message of the
+// first thing that is wrong, or ""
+inline std::string check_rescon_chain(const char *who, int n, const int32_t *res, int n_res, const uint8_t *cls)
+{
+    const std::string w(who);
+    if (!res) return w + "_res is NULL";
+    if (!cls) return w + "_class is NULL";
+    if (n_res < 1 || n_res > RESCON_MAX_RES) return w + ": need 1 <= residues <= " + std::to_string(RESCON_MAX_RES);
+    for (int i = 0; i < n; ++i)
+        if (res[i] < 0 || res[i] >= n_res)
+            return w + "_res: atom " + std::to_string(i) + " has residue " + std::to_string(res[i]) + " outside [0, " + std::to_string(n_res) + ")";
+    for (int i = 0; i < n_res; ++i)
+        if (cls[i] > 2) return w + "_class: residue " + std::to_string(i) + " has class " + std::to_string((int)cls[i]) + ", not 0, 1 or 2";
+    return "";
+}
+inline std::string check_rescon_cutoff(float cutoff)
+{
+    if (!(std::isfinite(cutoff) && cutoff > 0.f && cutoff <= 16.f)) return "cutoff must be in (0, 16]";
+    return "";
+}
+
+// atoms as k_rescon reads them: (x, y, z, the BITS of the residue index) of atom order[q] at q.  The fourth component is never used as a
+// number: it travels through the staging as 32 bits
+inline std::vector<float> gather4_res(const std::vector<int32_t> &order, const float *xyz, const int32_t *res)
+{
+    std::vector<float> v(order.size() * 4, 0.f);
+    for (size_t q = 0; q < order.size(); ++q) {
+        for (int k = 0; k < 3; ++k) v[q * 4 + k] = xyz[(size_t)order[q] * 3 + k];
+        static_assert(sizeof(float) == sizeof(int32_t), "bits");
+        std::memcpy(&v[q * 4 + 3], &res[order[q]], sizeof(int32_t));
+    }
+    return v;
+}
+
+// mask [3][W]: bit i & 31 of word i >> 5 of mask c is set iff receptor residue i has class c
+inline std::vector<uint32_t> rescon_class_masks(int Rr, const uint8_t *cls)
+{
+    const int W = rescon_words(Rr);
+    std::vector<uint32_t> m((size_t)3 * W, 0u);
+    for (int i = 0; i < Rr; ++i) m[(size_t)cls[i] * W + (i >> 5)] |= 1u << (i & 31);
+    return m;
+}
+
+// poses of one chunk of a call: as many bitmaps [Lr][W] of 32-bit words as fit `budget` bytes, at least 1, at most RESCON_MAX_CHUNK
+inline int rescon_chunk_poses(int Lr, int Rr, size_t budget = RESCON_SCRATCH_BYTES)
+{
+    const size_t per_pose = (size_t)Lr * (size_t)rescon_words(Rr) * sizeof(uint32_t);
+    return (int)std::min<size_t>((size_t)RESCON_MAX_CHUNK, std::max<size_t>(1, budget / per_pose));
 }
 
 }  // namespace dfm

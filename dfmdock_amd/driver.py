@@ -125,11 +125,15 @@ def surface_inputs(rec, lig, family):
 def ensemble_surface(model: engine.Model, rec, lig, rot_update, tr_update, probe=1.4, sphere_points=128, per_atom=False):
     """Buried solvent-accessible surface area of trajectories on the GPU (dfm_pose_bsa) from their final (rot_update, tr_update) alone:
     the heavy atoms of the two parsed PDB chains with their element radii, the ligand moved as pdbio.apply_pose_all_atom moves it.
-    Returns the dict of Surface.bsa plus probe, sphere_points and the two radius arrays."""
+    Returns the dict of Surface.bsa plus probe, sphere_points and the two radius arrays and, with `per_atom`, rec_exposed / lig_exposed
+    (the points of every atom that are exposed in isolation, Surface.info)."""
     ra, rr, la, lr, cen = surface_inputs(rec, lig, model.hp.family)
     with model.surface(ra, rr, la, lr, cen, probe, sphere_points) as sf:
         out = sf.bsa(np.asarray(rot_update, np.float32).reshape(-1, 3), np.asarray(tr_update, np.float32).reshape(-1, 3), per_atom=per_atom)
         out.update(probe=sf.probe, sphere_points=sf.K, rec_radius=rr, lig_radius=lr)
+        if per_atom:
+            info = sf.info()
+            out.update(rec_exposed=info["rec_exposed"], lig_exposed=info["lig_exposed"])
     return out
 
 
@@ -243,6 +247,87 @@ def _interface_result(ed, k, opts, bad=None, ranked_by="energy"):
     summary = dict(_pose_interface(ed, k), rank=int(np.nonzero(rank_order(tot, len(tot)) == k)[0][0]) + 1, weights=list(weights),
                    cutoff=float(cutoff), ranked_by="interface" if by_it else ranked_by)
     return {"interface_energy": summary, "interface_data": ed, "index": int(k)}
+
+
+def rescon_inputs(rec, lig, family):
+    """What the residue-contact call takes from two pdbio.backbone_from_atoms dicts: sterics_inputs plus, per chain, the residue index of
+    every heavy atom (sterics.residue_of_atoms) and the class of every residue by its name (affinity.IC_CLASS; a name outside the table is
+    apolar).  Returns (rec_atoms, rec_res, rec_class, lig_atoms, lig_res, lig_class, center, rec_keys, lig_keys, unclassified):
+    unclassified = the number of residues of (receptor, ligand) whose name is outside the table."""
+    from . import affinity as AF
+    from . import sterics as ST
+    ra, la, cen = sterics_inputs(rec, lig, family)
+    rk, rres = ST.residue_of_atoms(rec["atoms"], ST.heavy_atoms(rec["atoms"]))
+    lk, lres = ST.residue_of_atoms(lig["atoms"], ST.heavy_atoms(lig["atoms"]))
+    (rcls, rmiss), (lcls, lmiss) = AF.residue_classes([k[3] for k in rk], AF.IC_CLASS), AF.residue_classes([k[3] for k in lk], AF.IC_CLASS)
+    return ra, rres.astype(np.int32), rcls, la, lres.astype(np.int32), lcls, cen, rk, lk, (int(rmiss), int(lmiss))
+
+
+def ensemble_contacts(model: engine.Model, rec, lig, rot_update, tr_update, cutoff=5.5, per_residue=False, bits=False):
+    """Residue contacts by class of trajectories on the GPU (dfm_pose_rescon) from their final (rot_update, tr_update) alone: the residue
+    pairs of the two parsed PDB chains with two heavy atoms closer than `cutoff` A.  Returns the dict of Contacts.count plus cutoff,
+    rec_keys and lig_keys (the residues the indices of the degree arrays and of contact_bits mean) and unclassified: the residues of
+    (receptor, ligand) whose name is not one of the 20 and that count as apolar."""
+    inp = rescon_inputs(rec, lig, model.hp.family)
+    with model.contacts(*inp[:7], cutoff=cutoff) as h:
+        out = h.count(np.asarray(rot_update, np.float32).reshape(-1, 3), np.asarray(tr_update, np.float32).reshape(-1, 3),
+                      per_residue=per_residue, bits=bits)
+        out.update(cutoff=h.cutoff, rec_keys=inp[7], lig_keys=inp[8], unclassified=inp[9])
+    return out
+
+
+def pose_affinity(model: engine.Model, rec, lig, rot, tr, cutoff=5.5, probe=1.4, sphere_points=128, coef=None, temp_c=25.0, pairs=False,
+                  surface=None):
+    """The contacts-based affinity estimate (IC-NIS; affinity.dg - coefficients, class tables and reference areas there are starting
+    values that are not verified or calibrated, and the surface is this project's own) of the given poses: ensemble_contacts for ic, ONE
+    Surface.bsa(per_atom=True) call for every residue's accessible area inside each complex (affinity.complex_residue_sasa) and from it
+    the composition of the non-interacting surface (affinity.nis_percent).  Returns the dict of ensemble_contacts plus nis [P,3] (percent
+    apolar, polar, charged), nis_apolar, nis_charged, dg_contacts, dg (kcal/mol), kd (M at temp_c) and, with `pairs`, pairs: per pose the
+    [n,2] residue pairs (receptor, ligand) as indices into rec_keys / lig_keys.  `surface`: what ensemble_surface(per_atom=True) returned
+    for these poses, to be used instead of the surface call (its probe and sphere points then hold)."""
+    from . import affinity as AF
+    from . import sterics as ST
+    c = AF.COEF if coef is None else tuple(float(v) for v in coef)
+    rot, tr = np.asarray(rot, np.float32).reshape(-1, 3), np.asarray(tr, np.float32).reshape(-1, 3)
+    out = ensemble_contacts(model, rec, lig, rot, tr, cutoff, bits=pairs)
+    bd = ensemble_surface(model, rec, lig, rot, tr, probe, sphere_points, per_atom=True) if surface is None else surface
+    pr, K = bd["probe"], bd["sphere_points"]
+    sasa = []
+    for chain, side, keys in ((rec, "rec", out["rec_keys"]), (lig, "lig", out["lig_keys"])):
+        res = ST.residue_of_atoms(chain["atoms"], ST.heavy_atoms(chain["atoms"]))[1]
+        sasa.append(AF.complex_residue_sasa(bd[side + "_exposed"], bd[side + "_buried"], bd[side + "_radius"], res, len(keys), pr, K))
+    nis = AF.nis_percent(sasa[0], sasa[1], [k[3] for k in out["rec_keys"]], [k[3] for k in out["lig_keys"]])
+    dgv = AF.dg(out["ic"], nis[:, 0], nis[:, 2], c)
+    out.update(nis=nis, nis_apolar=nis[:, 0], nis_charged=nis[:, 2], dg_contacts=AF.dg_contacts(out["ic"], c), dg=dgv, kd=AF.kd(dgv, temp_c),
+               coef=c, probe=pr, sphere_points=K)
+    if pairs:
+        out["pairs"] = [AF.pairs_of(b) for b in out.pop("contact_bits")]
+    return out
+
+
+AFFINITY_SURFACE = (1.4, 128)      # probe and sphere points of the surface behind the affinity estimate of the pair drivers
+
+
+def _check_affinity(affinity, affinity_cutoff):
+    """None (off) or (cutoff,) of a pair driver's affinity options."""
+    if not affinity:
+        return None
+    from . import affinity as AF
+    return (AF.check_cutoff(affinity_cutoff),)
+
+
+def _pose_affinity(ad, k):
+    fin = lambda v: float(v) if np.isfinite(v) else None
+    return {"ic": [int(v) for v in ad["ic"][k]], "n_pairs": int(ad["n_pairs"][k]), "n_rec_res": int(ad["n_rec_res"][k]),
+            "n_lig_res": int(ad["n_lig_res"][k]), "nis_apolar": fin(ad["nis_apolar"][k]), "nis_charged": fin(ad["nis_charged"][k]),
+            "dg": fin(ad["dg"][k]), "kd": fin(ad["kd"][k]), "cutoff": float(ad["cutoff"])}
+
+
+def _affinity_result(ad, k):
+    """The `affinity` entries of a pair driver's result for the kept pose k: none without the option."""
+    if ad is None:
+        return {}
+    return {"affinity": _pose_affinity(ad, k), "affinity_data": ad, "index": int(k)}
 
 
 def _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff):
@@ -727,12 +812,12 @@ def _center(model):
 
 
 def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native=None, cons=None, ster=None, clu=None, refine=None,
-            surf=None, ie=None):
+            surf=None, ie=None, aff=None):
     """What every pair driver does with its sampled trajectories: the kept pose, its files and the result.  cols: every trajectory's
     energy, rot_update, tr_update (and the driver's own columns).  pick = (rule, *column names): the driver's own choice, rule(*columns) ->
     index; key: the clustering key that goes with it.  entries(k): the driver's own result entries for the kept pose k.  cons / ster / clu:
     None or the options of _with_consensus / _screen / _top_models; surf: None or the options of _check_surface; ie: None or the options of
-    _check_interface; refine: None or the keyword arguments of refine_models - only then
+    _check_interface; aff: None or the options of _check_affinity; refine: None or the keyword arguments of refine_models - only then
     does the handle outlive the sampling."""
     lig0 = gx.lig_pos0
     if refine is None:      # the columns are host arrays: the handle (and its ~GB of device workspace) goes before any post-processing
@@ -746,19 +831,24 @@ def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_p
     key = _nan_key(key, bad)      # again: rank "consensus" has replaced the key by consensus.rank_positions
     extra.update(_interface_result(ed, k, ie, bad, extra["consensus"]["ranked_by"] if "consensus" in extra else "energy"))
     extra.update(_sterics_result(sd, k))
-    bd = None if surf is None else ensemble_surface(model, rec, lig, cols["rot_update"], cols["tr_update"], surf[1], surf[2])
+    # one surface call serves both when the surface options are the ones the affinity estimate takes (probe 1.4 A, 128 points)
+    shared = surf is not None and aff is not None and (surf[1], surf[2]) == _check_surface(True, None, *AFFINITY_SURFACE)[1:]
+    bd = None if surf is None else ensemble_surface(model, rec, lig, cols["rot_update"], cols["tr_update"], surf[1], surf[2], per_atom=shared)
     extra.update(_surface_result(bd, k, surf))
+    ad = None if aff is None else pose_affinity(model, rec, lig, cols["rot_update"], cols["tr_update"], aff[0], *AFFINITY_SURFACE,
+                                                surface=bd if shared else None)
+    extra.update(_affinity_result(ad, k))
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k], center=_center(model))
     if out_pdb:
         pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa, remarks=_remarks(sd, k))
     res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, **entries(k)}
     res.update(extra)
-    if cons is not None or ster is not None or surf is not None or ie is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
+    if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
         res.setdefault("trajectories", {c: cols[c] for c in ("energy", "rot_update", "tr_update")})
     _selected_metrics(model, native, rec, lig0, res)
     if clu is not None:
-        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad, bd, None if surf is None else surf[0], ed))
+        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad, bd, None if surf is None else surf[0], ed, ad))
         if refine is not None:
             refine_models(model, gx, rec, lig, lig0, cols, res["models"], precision=precision, out_pdb=out_pdb, native=native, **refine)
             gx.close()
@@ -770,7 +860,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
               restraint_rank="satisfied", restraint_params=None, top_k=None, cluster_radius=4.0, cluster_rule="energy", refine_t=None,
               refine_samples=8, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
               clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, bsa=False, min_bsa=None, probe=1.4, sphere_points=128,
-              interface_energy=False, ie_weights=None, ie_cutoff=8.0, **sampler_kw):
+              interface_energy=False, ie_weights=None, ie_cutoff=8.0, affinity=False, affinity_cutoff=5.5, **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
     pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
     the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
@@ -820,12 +910,19 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     `interface_energy`.  total = ifenergy.total with `ie_weights` (rep, att, elec; None: ifenergy.WEIGHTS - starting values, not
     fitted).  rank="interface" (implies interface_energy) keeps the pose with the lowest total instead (ties: lower index; it overrides
     restraint_rank) and makes the totals the clustering key of `top_k`; poses `clash_filter` removed get a NaN key as under rank
-    "consensus"."""
+    "consensus".
+
+    `affinity`: the residue contacts by class (heavy atoms within `affinity_cutoff` A) and the contacts-based affinity estimate of every
+    trajectory (pose_affinity: IC-NIS with starting values that are not verified or calibrated, on this project's own surface).  The
+    result gains `affinity` ({ic, n_pairs, n_rec_res, n_lig_res, nis_apolar, nis_charged, dg, kd, cutoff} of the kept pose; dg in
+    kcal/mol, kd in M, None where there is no surface residue), `affinity_data` (the arrays of every trajectory, with dg_contacts),
+    `index` and `trajectories`; every model of `top_k` gains `affinity`.  Nothing is ranked by it."""
     _check_rank(rank, consensus_top)
     cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
     ster = _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff)
     surf = _check_surface(bsa, min_bsa, probe, sphere_points)
     ie = _check_interface(interface_energy, rank, ie_weights, ie_cutoff)
+    aff = _check_affinity(affinity, affinity_cutoff)
     if native is not None:
         _check_native(native, rec, lig)
     if refine_t is not None and top_k is None:
@@ -866,7 +963,8 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     cols = {c: np.concatenate(v, 0) for c, v in cols.items()}
     if not restrained:
         # the loop's own minimum; consensus and the screen choose among all trajectories at once (the first minimum: the same pose)
-        pick = (np.argmin if cons is not None or ster is not None or surf is not None or ie is not None else (lambda energy: k0), "energy")
+        pick = (np.argmin if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None
+                else (lambda energy: k0), "energy")
         key, entries = cols["energy"], lambda k: {}
     else:
         from . import restraints as RS
@@ -877,14 +975,14 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         entries = lambda k: {"index": k, "restraints": len(restraints), "restraint_rank": restraint_rank,
                              "restraint_energy": float(cols["restraint_energy"][k]), "restraints_satisfied": int(cols["restraints_satisfied"][k]),
                              "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
-    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine, surf, ie)
+    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine, surf, ie, aff)
 
 
 def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
                 out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", perturb=True, restraints=None,
                 restraint_params=None, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
                 clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, start_shift=None, bsa=False, min_bsa=None, probe=1.4,
-                sphere_points=128, interface_energy=False, ie_weights=None, ie_cutoff=8.0, **sampler_kw):
+                sphere_points=128, interface_energy=False, ie_weights=None, ie_cutoff=8.0, affinity=False, affinity_cutoff=5.5, **sampler_kw):
     """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories
     start from that pose noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps
     down from t_begin; like dock_pair the minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns
@@ -894,6 +992,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
     `consensus_cutoff`: as for dock_pair.  `clash_screen` / `clash_filter` / `clash_cutoff` / `contact_cutoff`: as for dock_pair.
     `bsa` / `min_bsa` / `probe` / `sphere_points`: as for dock_pair (there are no models here, so min_bsa only turns bsa on).
     `interface_energy` / `ie_weights` / `ie_cutoff` and rank="interface": as for dock_pair.
+    `affinity` / `affinity_cutoff`: as for dock_pair.
     `start_shift` ([num_samples,3]): trajectory i starts from the input pose translated by start_shift[i] (the engine's start_pos); the
     shift is added to its tr_update, so (rot_update, tr_update) keep mapping the INPUT pose onto the final one."""
     _check_rank(rank, consensus_top)
@@ -901,6 +1000,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
     ster = _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff)
     surf = _check_surface(bsa, min_bsa, probe, sphere_points)
     ie = _check_interface(interface_energy, rank, ie_weights, ie_cutoff)
+    aff = _check_affinity(affinity, affinity_cutoff)
     if native is not None:
         _check_native(native, rec, lig)
     if start_shift is not None:
@@ -927,7 +1027,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
         done += b
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
     res = _finish(model, gx, rec, lig, cols, (np.argmin, "energy"), None,      # the first minimum wins, as in dock_pair
-                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster, surf=surf, ie=ie)
+                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster, surf=surf, ie=ie, aff=aff)
     if native is not None:
         res["start_metrics"] = native_metrics(model, native, rec["bb_coords"], gx.lig_pos0[None])[0]
     return res
@@ -959,12 +1059,12 @@ def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps
     return models
 
 
-def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=None, bad=None, bd=None, min_bsa=None, ed=None):
+def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=None, bad=None, bd=None, min_bsa=None, ed=None, ad=None):
     """dock_pair's `models`: the centres of up to top_k clusters in cluster order, each written as <out_pdb stem>_<rank>.pdb.  sd: the
     screen's data (every model gains `sterics`, every file a REMARK line); bad: poses the clash filter removed - their key is NaN, so they
     come last, and a cluster one of them would lead is left out.  bd: the surface data (every model gains bsa, bsa_rec, bsa_lig); min_bsa:
     a centre that buries less is left out as well, and `bsa_dropped` counts those.  ed: the interface-energy data (every model gains
-    `interface_energy`)."""
+    `interface_energy`); ad: the affinity data (every model gains `affinity`)."""
     top_k, radius, rule = clu
     cl = cluster_trajectories(model, lig0, cols["rot_update"], cols["tr_update"], key, radius, rule, top_k)
     models, dropped = [], 0
@@ -983,6 +1083,8 @@ def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=
             models[-1].update(_pose_bsa(bd, c))
         if ed is not None:
             models[-1]["interface_energy"] = _pose_interface(ed, c)
+        if ad is not None:
+            models[-1]["affinity"] = _pose_affinity(ad, c)
         if out_pdb:
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c], center=_center(model))
             pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa, remarks=_remarks(sd, c))

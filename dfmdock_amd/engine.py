@@ -232,9 +232,15 @@ class Model:
         within `cutoff` A.  Returns an Interface whose `.energy(rot, tr)` takes P poses in one call."""
         return Interface(self, rec_atoms, rec_params, lig_atoms, lig_params, center, cutoff, soft, elec_min_dist, dielectric_slope)
 
+    def contacts(self, rec_atoms, rec_res, rec_class, lig_atoms, lig_res, lig_class, center, cutoff=5.5):
+        """The heavy atoms of a pair with the residue index of every atom ([n] in [0, n_res)) and the class of every residue ([n_res]: 0
+        apolar, 1 polar, 2 charged; affinity.residue_classes) prepared for the residue-contact call on the GPU (dfm_rescon_create):
+        residue pairs with two heavy atoms closer than `cutoff` A.  Returns a Contacts whose `.count(rot, tr)` takes P poses in one call."""
+        return Contacts(self, rec_atoms, rec_res, rec_class, lig_atoms, lig_res, lig_class, center, cutoff)
+
 
 class _Handle:
-    """What Native, Atoms, Surface and Interface share: a handle `_h` made by dfm_<_kind>_create and freed by dfm_<_kind>_destroy - close(), a context
+    """What Native, Atoms, Surface, Interface and Contacts share: a handle `_h` made by dfm_<_kind>_create and freed by dfm_<_kind>_destroy - close(), a context
     manager, closed when collected."""
     _kind = None
 
@@ -455,6 +461,68 @@ class Interface(_Handle):
         L.check(L.lib().dfm_pose_iface_energy_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_iface_energy")
         o["rep"], o["att"], o["elec"] = IE.kcal(o["rep_q"]), IE.kcal(o["att_q"]), IE.kcal(o["elec_q"])
         return o
+
+
+class Contacts(_Handle):
+    """The heavy atoms of a receptor / ligand pair with their residue indices and the residue classes resident on the model's GPU
+    (dfm_rescon).  Read-only after creation: `count` may be called from several threads at once."""
+    _kind = "rescon"
+
+    def __init__(self, model: Model, rec_atoms, rec_res, rec_class, lig_atoms, lig_res, lig_class, center, cutoff=5.5):
+        from . import affinity as AF
+        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _f32(center).reshape(-1)
+        if cen.size != 3:
+            raise ValueError(f"center must have 3 entries, got {np.shape(center)}")
+        rr, rc = AF.check_residues(rec_res, ra.shape[0], rec_class, "rec")
+        lr, lc = AF.check_residues(lig_res, la.shape[0], lig_class, "lig")
+        rr, rc, lr, lc = (np.ascontiguousarray(a) for a in (rr, rc, lr, lc))
+        self.model, self.Ar, self.Al, self.Rr, self.Lr = model, ra.shape[0], la.shape[0], rc.size, lc.size
+        self.W, self.cutoff = (self.Rr + 31) // 32, float(np.float32(cutoff))
+        u8 = C.POINTER(C.c_uint8)
+        self._h = L.lib().dfm_rescon_create(model._h, self.Ar, _p(ra), _p(rr, L.I32P), self.Rr, rc.ctypes.data_as(u8), self.Al, _p(la),
+                                            _p(lr, L.I32P), self.Lr, lc.ctypes.data_as(u8), _p(cen), float(cutoff))
+        self._created()
+
+    def info(self):
+        """{n_cells, max_cell_atoms, cell_edge} of the receptor's grid, row_words = W and chunk_poses, the poses one chunk of a call
+        holds a bitmap for (dfm_rescon_info)."""
+        n, mx, e, w, ch = C.c_int32(0), C.c_int32(0), C.c_float(0), C.c_int32(0), C.c_int32(0)
+        L.check(L.lib().dfm_rescon_info(self._h, C.byref(n), C.byref(mx), C.byref(e), C.byref(w), C.byref(ch)), "dfm_rescon_info")
+        return {"n_cells": n.value, "max_cell_atoms": mx.value, "cell_edge": e.value, "row_words": w.value, "chunk_poses": ch.value}
+
+    def count(self, rot, tr, per_residue=False, bits=False, chunk_poses=0):
+        """Residue contacts of P poses (dfm_pose_rescon; the float64 definition is affinity.residue_contacts): rot [P,3] axis-angle and
+        tr [P,3] as rot_update / tr_update hold them.  Returns {ic [P,6] (AA, AP, AC, PP, PC, CC), n_pairs, n_rec_res, n_lig_res [P]}
+        int32, with `per_residue` rec_degree [P,Rr] / lig_degree [P,Lr] int32, with `bits` contact_bits [P,Lr,W] uint32
+        (affinity.pairs_of turns one pose's block into residue pairs)."""
+        r, t, P = _rigid_poses(rot, tr)
+        o = {"ic": np.zeros((P, 6), np.int32), "n_pairs": np.zeros(P, np.int32), "n_rec_res": np.zeros(P, np.int32),
+             "n_lig_res": np.zeros(P, np.int32)}
+        if per_residue:
+            o["rec_degree"], o["lig_degree"] = np.zeros((P, self.Rr), np.int32), np.zeros((P, self.Lr), np.int32)
+        out = L.ResconOutC()
+        for k, v in o.items():
+            setattr(out, k, _p(v, L.I32P))
+        if bits:
+            o["contact_bits"] = np.zeros((P, self.Lr, self.W), np.uint32)
+            out.contact_bits = _p(o["contact_bits"], L.U32P)
+        L.check(L.lib().dfm_pose_rescon_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_rescon")
+        return o
+
+
+def rescon_last_timing():
+    """(host-to-device copy ms, kernel ms) of this thread's last Contacts.count call (dfm_rescon_last_timing)."""
+    a, b = C.c_double(0), C.c_double(0)
+    L.check(L.lib().dfm_rescon_last_timing(C.byref(a), C.byref(b)), "dfm_rescon_last_timing")
+    return a.value, b.value
+
+
+def rescon_last_phases():
+    """(zeroing the bitmap ms, walk ms, finish ms) of this thread's last Contacts.count call: its kernel time by phase
+    (dfm_rescon_last_phases)."""
+    a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+    L.check(L.lib().dfm_rescon_last_phases(C.byref(a), C.byref(b), C.byref(c)), "dfm_rescon_last_phases")
+    return a.value, b.value, c.value
 
 
 def iface_last_timing():

@@ -558,6 +558,50 @@ int dfm_pose_iface_energy_chunked(dfm_iface *h, int P, const float *rot, const f
 /* GPU milliseconds of the calling thread's last dfm_pose_iface_energy, summed over its chunks: the host-to-device copies of the poses
  * and the kernels (k_iface_pose, k_iface, the memsets of the per-atom output) - tools/iface_bench.py */
 int dfm_iface_last_timing(double *copy_ms, double *kernel_ms);
+/* Residue contacts of P rigid poses of one ligand over all heavy atoms, counted by residue class - which residues touch which, and the
+ * input of the contacts-based affinity estimate (IC-NIS).  dfmdock_amd/affinity.py is the float64 definition these calls are tested
+ * against.  Atoms, centre and poses as for dfm_atoms_create / dfm_pose_sterics.  rec_res [Ar] / lig_res [Al]: the residue index of each
+ * atom, in [0, Rr) / [0, Lr); a residue without atoms is legal and never in contact.  rec_class [Rr] / lig_class [Lr]: 0 apolar, 1
+ * polar, 2 charged.  cutoff (A, in (0, 16]; 5.5 is usual).
+ *   an atom pair counts iff d = sqrt((dx*dx + dy*dy) + dz*dz) < cutoff (strict), fp64 on the widened fp32 receptor atom and the fp64
+ *     ligand atom of the pose; a NaN is no pair.
+ *   C_p = the SET of (receptor residue i, ligand residue j) with at least one counting atom pair.
+ *   ic [P,6]: |C_p| split by the unordered pair of classes in the order AA, AP, AC, PP, PC, CC (index a (5 - a) / 2 + b, a <= b);
+ *     n_pairs [P] = |C_p| = the sum of the six; n_rec_res / n_lig_res [P]: residues with at least one contact; rec_degree [P,Rr] /
+ *     lig_degree [P,Lr]: the number of partner residues; contact_bits [P,Lr,W], W = ceil(Rr / 32): bit i & 31 of word i >> 5 of row j
+ *     is set iff (i, j) is in C_p.
+ *   A pose with a NaN or infinite rot / tr gets zeros and disturbs no other pose (not an error).
+ * Every output pointer may be NULL.  Everything is an integer and a set does not depend on the order its members were found in: the
+ * results equal the definition's, and none depends on P, on a pose's index, on the order of the poses or on the chunks of a call.  A
+ * call works through chunk_poses poses at a time (0: as many as fill 64 MiB of bitmap - Lr W 4 bytes per pose - at most 32768);
+ * dfm_rescon_info reports the receptor grid's cells, the most atoms in one cell, the cell edge, W and that default chunk.
+ * DFM_E_INVALID / NULL, nothing enqueued: a NULL pointer among the inputs, Ar or Al < 1 or > 2^24, a non-finite atom or centre, Rr or Lr
+ * < 1 or > 4096, a residue index out of range, a class above 2, a cutoff outside (0, 16], a receptor bounding box of more than 2^24
+ * cells, chunk_poses < 0, P < 1 or > 65536.  DFM_E_OOM when the atoms or a chunk do not fit.
+ * Takes the MODEL handle for its device only.  The handle is read-only after creation; every call owns a non-blocking stream and its
+ * device temporaries, so calls on one handle may run from several host threads at once.  No reference call has a counterpart. */
+typedef struct dfm_rescon dfm_rescon;
+typedef struct {
+    int32_t *ic;                        /* [P,6]    or NULL */
+    int32_t *n_pairs;                   /* [P]      or NULL */
+    int32_t *n_rec_res, *n_lig_res;     /* [P]      or NULL */
+    int32_t *rec_degree;                /* [P,Rr]   or NULL */
+    int32_t *lig_degree;                /* [P,Lr]   or NULL */
+    uint32_t *contact_bits;             /* [P,Lr,W] or NULL */
+} dfm_rescon_out;
+dfm_rescon *dfm_rescon_create(dfm_model *m, int Ar, const float *rec_atoms, const int32_t *rec_res, int Rr, const uint8_t *rec_class, int Al,
+                              const float *lig_atoms, const int32_t *lig_res, int Lr, const uint8_t *lig_class, const float center[3],
+                              float cutoff);
+void dfm_rescon_destroy(dfm_rescon *h);
+int dfm_rescon_info(const dfm_rescon *h, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge, int32_t *row_words, int32_t *chunk_poses);
+int dfm_pose_rescon(dfm_rescon *h, int P, const float *rot, const float *tr, dfm_rescon_out *out);
+int dfm_pose_rescon_chunked(dfm_rescon *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_rescon_out *out);
+/* GPU milliseconds of the calling thread's last dfm_pose_rescon, summed over its chunks: the host-to-device copies of the poses and the
+ * kernels (the memset of the bitmap, k_rescon_pose, k_rescon, k_rescon_finish) - tools/affinity_bench.py */
+int dfm_rescon_last_timing(double *copy_ms, double *kernel_ms);
+/* The kernel milliseconds of that call by phase, from the call's own events: zeroing the bitmap, the walk (k_rescon_pose, k_rescon) and
+ * k_rescon_finish; their sum is kernel_ms */
+int dfm_rescon_last_phases(double *zero_ms, double *walk_ms, double *finish_ms);
 /* edges per node for this complex: min(N,20) + min(40, N-20) */
 int dfm_complex_degree(const dfm_complex *cx);
 /* Device blocks released by destroyed handles are parked per device for the next handle (a set driver creates and destroys a
