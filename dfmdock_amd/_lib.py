@@ -51,6 +51,7 @@ EXPORTS = [
     "dfm_iface_last_timing",
     "dfm_rescon_create", "dfm_rescon_destroy", "dfm_rescon_info", "dfm_pose_rescon", "dfm_pose_rescon_chunked", "dfm_rescon_last_timing",
     "dfm_rescon_last_phases",
+    "dfm_score_distogram", "dfm_distogram_last_timing",
 ]
 
 
@@ -141,6 +142,15 @@ class IfaceOutC(C.Structure):
 
 class ResconOutC(C.Structure):
     _fields_ = [(n, I32P) for n in ("ic", "n_pairs", "n_rec_res", "n_lig_res", "rec_degree", "lig_degree")] + [("contact_bits", U32P)]
+
+
+class DistogramParamsC(C.Structure):
+    _fields_ = [("contact_bins", C.c_int32), ("near_cutoff", C.c_float)]
+
+
+class DistogramOutC(C.Structure):
+    _fields_ = [("nll", F32P), ("nll_near", F32P), ("n_near", I32P), ("exp_contacts", F32P), ("pair_nll", F32P), ("pcontact", F32P),
+                ("edist", F32P), ("pcontact_mean", F32P)]
 
 
 _lib = None
@@ -237,6 +247,9 @@ def lib():
     L.dfm_pose_rescon_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(ResconOutC)]
     L.dfm_rescon_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_rescon_last_phases.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_score_distogram.argtypes = [C.c_void_p, C.c_int, F32P, F32P, I32P, C.c_uint64, C.c_uint32, C.POINTER(DistogramParamsC),
+                                      C.POINTER(DistogramOutC)]
+    L.dfm_distogram_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_trim_cache.argtypes = [C.c_int]
     L.dfm_trim_cache.restype = C.c_longlong
     L.dfm_alloc_diag.argtypes = [C.POINTER(C.c_int64)]

@@ -16,6 +16,7 @@
     python -m dfmdock_amd sweep ... --consensus [--consensus-top 0.5]
     python -m dfmdock_amd dock|refine ... --interface-energy [--rank interface] [--ie-weights 0.18 1.0 0.5] [--ie-cutoff 8.0] [--energy-residues FILE]
     python -m dfmdock_amd dock|refine ... --affinity [--affinity-cutoff 5.5] [--contact-residues FILE]
+    python -m dfmdock_amd dock|refine ... --distogram [--rank distogram] [--distogram-map map.npz] [--distogram-restraints FILE] [--distogram-t 1e-3]
     python -m dfmdock_amd dock|refine ... --clash-screen [--clash-filter] [--clash-cutoff 3.0] [--contact-cutoff 5.0] [--clash-residues FILE]
 
   dock       <- src/inference_single.py:1-12 -> inference() (src/inference_base.py:601-670): num_samples (120) trajectories of
@@ -77,6 +78,17 @@
              for the kept pose and for every --top-k model; `--contact-residues FILE` lists the kept model's residue pairs.  The
              coefficients, class tables and reference areas are starting values that are not verified or calibrated, the surface is this
              project's own Shrake-Rupley, and no agreement with the PRODIGY server is claimed.  Nothing is ranked by it.
+  distogram  the model's own distogram head (second model family only: EGNN_Net.to_dist, 64 distance bins per residue pair) evaluated at
+             every final pose and reduced on the GPU (dfmdock_amd/distogram.py, dfm_score_distogram).  `dock / refine --distogram` add
+             dist_nll (the reference's distogram_loss of the pose's own CA-CA distances under the prediction made at that pose: lower =
+             the pose agrees better with what the model expects), dist_nll_near (the same over pairs closer than the model's cut-off) and
+             exp_contacts (expected number of residue pairs within 7.85 A) for the kept pose and for every --top-k model; `--rank
+             distogram` keeps the pose with the lowest dist_nll (and makes it the clustering key of --top-k; with --clash-filter the
+             flagged poses are out); `--distogram-map FILE.npz` writes the predicted contact probabilities averaged over all
+             trajectories and the expected-distance map of every written model; `--distogram-restraints FILE` writes the --restraint-top
+             most probable contacts as a restraint file (upper bound --restraint-upper, weight = probability) for a second, guided run;
+             `--distogram-t T` (default 1e-3) is the diffusion time of the evaluation.  A first-family checkpoint is refused before
+             sampling.
   selfcheck  no reference counterpart: dfm_complex_selfcheck on the pair (what `dock` and `sweep` run once per complex anyway).
 
 --ckpt takes the Lightning checkpoint the reference loads (src/inference_base.py:611-616; read without Lightning / omegaconf by
@@ -103,18 +115,30 @@ def _add_native(p):
 def _add_consensus(p):
     p.add_argument("--consensus", action="store_true",
                    help="score the trajectories by consensus contacts (adds a `consensus` object to the result line)")
-    p.add_argument("--rank", default="energy", choices=["energy", "consensus", "interface"],
-                   help="which trajectory is kept: the minimum energy (default), the highest consensus score (implies --consensus) or the "
-                        "lowest interface energy (implies --interface-energy)")
+    p.add_argument("--rank", default="energy", choices=["energy", "consensus", "interface", "distogram"],
+                   help="which trajectory is kept: the minimum energy (default), the highest consensus score (implies --consensus), the "
+                        "lowest interface energy (implies --interface-energy) or the lowest distogram nll (implies --distogram)")
     p.add_argument("--consensus-top", type=float, default=None, metavar="FRAC",
                    help="with --consensus: members of the ensemble are the best FRAC of the trajectories by energy (default 1.0: all)")
     p.add_argument("--contact-map", default=None, metavar="FILE.npz",
                    help="write the consensus contact map: count, freq, rec_count, lig_count, M, cutoff, residue labels (implies --consensus)")
     p.add_argument("--write-restraints", default=None, metavar="FILE",
                    help="write the --restraint-top most frequent consensus contacts as a restraint file (implies --consensus)")
-    p.add_argument("--restraint-top", type=int, default=None, metavar="N", help="with --write-restraints: number of contacts (default 10)")
+    p.add_argument("--restraint-top", type=int, default=None, metavar="N",
+                   help="with --write-restraints / --distogram-restraints: number of contacts (default 10)")
     p.add_argument("--restraint-upper", type=float, default=None, metavar="U",
-                   help="with --write-restraints: upper bound on the CA-CA distance of every written contact (A, default 8.0)")
+                   help="with --write-restraints / --distogram-restraints: upper bound on the CA-CA distance of every written contact (A, default 8.0)")
+
+
+def _add_distogram(p):
+    p.add_argument("--distogram", action="store_true",
+                   help="evaluate the model's distogram head at every final pose (family-1 checkpoints): adds dist_nll, dist_nll_near, "
+                        "exp_contacts to the result line and to every model")
+    p.add_argument("--distogram-map", default=None, metavar="FILE.npz",
+                   help="write pcontact_mean [R,L] over all trajectories and the expected-distance map of every written model (implies --distogram)")
+    p.add_argument("--distogram-restraints", default=None, metavar="FILE",
+                   help="write the --restraint-top most probable predicted contacts as a restraint file (implies --distogram)")
+    p.add_argument("--distogram-t", type=float, default=None, metavar="T", help="with --distogram: diffusion time of the evaluation (default 1e-3)")
 
 
 def _add_sterics(p):
@@ -198,6 +222,7 @@ def build_parser():
     d.add_argument("--refine-samples", type=int, default=8, metavar="n", help="with --refine-t: trajectories per cluster centre")
     _add_native(d)
     _add_consensus(d)
+    _add_distogram(d)
     _add_sterics(d)
     _add_surface(d)
     _add_interface(d)
@@ -215,6 +240,7 @@ def build_parser():
     r.add_argument("--restraints", default=None, help="interface restraint file (as for dock)")
     _add_native(r)
     _add_consensus(r)
+    _add_distogram(r)
     _add_sterics(r)
     _add_surface(r)
     _add_interface(r)
@@ -264,8 +290,15 @@ def parse_args(argv=None):
     if args.cmd in ("dock", "refine"):
         if args.rank == "consensus" or args.contact_map or args.write_restraints:
             args.consensus = True
-        if not args.write_restraints and (args.restraint_top is not None or args.restraint_upper is not None):
-            ap.error("--restraint-top / --restraint-upper describe the file of --write-restraints: they need it")
+        if args.rank == "distogram" or args.distogram_map or args.distogram_restraints:
+            args.distogram = True
+        if not args.distogram and args.distogram_t is not None:
+            ap.error("--distogram-t is the time of the --distogram evaluation: it needs it")
+        args.distogram_t = 1e-3 if args.distogram_t is None else args.distogram_t
+        if not (0.0 < args.distogram_t <= 1.0):
+            ap.error("--distogram-t must be in (0, 1]")
+        if not (args.write_restraints or args.distogram_restraints) and (args.restraint_top is not None or args.restraint_upper is not None):
+            ap.error("--restraint-top / --restraint-upper describe the file of --write-restraints / --distogram-restraints: they need one")
         args.restraint_top = 10 if args.restraint_top is None else args.restraint_top
         args.restraint_upper = 8.0 if args.restraint_upper is None else args.restraint_upper
         if args.restraint_top < 1:
@@ -413,6 +446,42 @@ def consensus_outputs(args, res, rec, lig, line):
                             header=f"top {len(groups)} consensus contacts of {len(cd['consensus'])} trajectories ({cd['M']} members, "
                                    f"contact cutoff {cd['cutoff']:g} A): REC LIG UPPER WEIGHT(= contact frequency)")
         line.update(restraints_written=os.path.abspath(args.write_restraints), restraints_written_n=len(groups))
+
+
+def distogram_kwargs(args, model):
+    """Driver keyword arguments of the distogram flags of dock / refine: none without them.  The head exists in the second model
+    family only: a first-family checkpoint with any of the flags ends the command here, before anything is sampled."""
+    if not args.distogram:
+        return {}
+    if model.hp.family != 1:
+        raise SystemExit("--distogram / --rank distogram / --distogram-map / --distogram-restraints need a family-1 checkpoint (EGNN_Net "
+                         "has the distogram head to_dist, Score_Net does not); this checkpoint is family 0")
+    return dict(distogram=True, rank=args.rank, distogram_t=args.distogram_t,
+                distogram_maps=bool(args.distogram_map or args.distogram_restraints))
+
+
+def distogram_outputs(args, res, rec, lig, line):
+    """The distogram part of a dock / refine result: dist_nll, dist_nll_near, exp_contacts of the line (the models carry theirs),
+    --distogram-map and --distogram-restraints."""
+    if not args.distogram:
+        return
+    from . import consensus as CS
+    from . import distogram as DG
+    dd, d = res["distogram_data"], res["distogram"]
+    line.update(dist_nll=d["dist_nll"], dist_nll_near=d["dist_nll_near"], exp_contacts=d["exp_contacts"], dist_rank=d["rank"],
+                distogram_t=d["t"], index=res["index"])
+    if args.distogram_map:
+        idx = [int(res["index"])] + [int(m["index"]) for m in res.get("models", [])]
+        np.savez(args.distogram_map, pcontact_mean=dd["pcontact_mean"], edist=dd["edist"][idx].astype(np.float32), edist_index=np.array(idx, np.int64),
+                 nll=dd["nll"], contact_bins=np.int64(dd["contact_bins"]), t=np.float64(dd["t"]), rec_residues=residue_labels(rec),
+                 lig_residues=residue_labels(lig))
+        line.update(distogram_map=os.path.abspath(args.distogram_map))
+    if args.distogram_restraints:
+        groups = DG.contact_groups(dd["pcontact_mean"], args.restraint_top, upper=args.restraint_upper)
+        CS.write_restraints(args.distogram_restraints, groups, rec, lig,
+                            header=f"top {len(groups)} predicted contacts (distogram head, bins below {DG.BOUNDS[dd['contact_bins'] - 1]:.2f} A, "
+                                   f"mean over {len(dd['nll'])} trajectories at t = {dd['t']:g}): REC LIG UPPER WEIGHT(= contact probability)")
+        line.update(distogram_restraints=os.path.abspath(args.distogram_restraints), distogram_restraints_n=len(groups))
 
 
 def sterics_kwargs(args):
@@ -608,6 +677,7 @@ def cmd_dock(args):
     if args.native:
         kw.update(native=load_native(args.native))
     kw.update(consensus_kwargs(args))
+    kw.update(distogram_kwargs(args, model))
     kw.update(sterics_kwargs(args))
     kw.update(surface_kwargs(args))
     kw.update(interface_kwargs(args))
@@ -629,6 +699,7 @@ def cmd_dock(args):
     if args.native:
         line.update(metrics=res["metrics"])
     consensus_outputs(args, res, rec, lig, line)
+    distogram_outputs(args, res, rec, lig, line)
     sterics_outputs(args, model, res, rec, lig, line)
     surface_outputs(args, model, res, rec, lig, line)
     interface_outputs(args, model, res, rec, lig, line)
@@ -654,6 +725,7 @@ def cmd_refine(args):
     if args.native:
         kw.update(native=load_native(args.native))
     kw.update(consensus_kwargs(args))
+    kw.update(distogram_kwargs(args, model))
     kw.update(sterics_kwargs(args))
     kw.update(surface_kwargs(args))
     kw.update(interface_kwargs(args))
@@ -668,6 +740,7 @@ def cmd_refine(args):
     if args.native:
         line.update(metrics=res["metrics"], start_metrics=res["start_metrics"])
     consensus_outputs(args, res, rec, lig, line)
+    distogram_outputs(args, res, rec, lig, line)
     sterics_outputs(args, model, res, rec, lig, line)
     surface_outputs(args, model, res, rec, lig, line)
     interface_outputs(args, model, res, rec, lig, line)

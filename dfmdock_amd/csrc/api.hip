@@ -286,6 +286,7 @@ struct dfm_model {
     float *en0_w = nullptr;          // [256][512]
     PairHeadDev pair[3];             // family 1: 0 to_force, 1 to_energy, 2 to_confidence
     PairHeadDev dist;                // family 1: to_dist (fp32 only; w3 = [256][64], transposed)
+    float *dist_w3f = nullptr;       // family 1: to_dist.3 in the fragment order of k_pair_dist_sum (PairDistSumArgs::w3f)
     float *ir0_w = nullptr, *ir0_b = nullptr, *ir2_w = nullptr, *ir2_b = nullptr, *ir4_w = nullptr, *ir4_b = nullptr;   // to_ires
     float tab_max[8][2] = {};        // per layer: largest |entry| of the two merged lookup tables as stored (log2e-scaled; before the fp16 clamp)    // local refinement: IGSO(3) cdf tables by sigma index (k_igso3_cdf, 8 KB each in `pool`), built on first use and never changed
     std::mutex ig_m;
@@ -675,6 +676,13 @@ extern "C" dfm_model *dfm_model_create(const float *blob, size_t n_floats, const
             std::memset(&D, 0, sizeof(D));
             up(&D.wab, wab.data(), wab.size()); up(&D.w_d, wd.data(), H); up(&D.ln_w, src.ln_w, H); up(&D.ln_b, src.ln_b, H);
             up(&D.w3, w3t.data(), w3t.size());
+            std::vector<float> w3f((size_t)64 * H);      // A operands of the 256 -> 64 projection: [out block][channel quad][out row][4]
+            for (int ob = 0; ob < 2; ++ob)
+                for (int c4 = 0; c4 < H / 4; ++c4)
+                    for (int mrow = 0; mrow < 32; ++mrow)
+                        for (int e = 0; e < 4; ++e)
+                            w3f[(((size_t)ob * (H / 4) + c4) * 32 + mrow) * 4 + e] = src.w3[(size_t)(ob * 32 + mrow) * H + c4 * 4 + e] * (1.0f / SILU_S);
+            up(&m->dist_w3f, w3f.data(), w3f.size());
         }
     } else {
         up(&m->en0_w, w.en0_w, (size_t)H * 2 * H);
@@ -2866,6 +2874,116 @@ extern "C" int dfm_score(dfm_complex *cx, int B, const float *lig_pos, const flo
     }
     if (rc != DFM_OK) (void)hipStreamSynchronize(s);   // nothing may still read the per-call buffers when they are released
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The distogram head of the second family reduced on the device (kernels_pair.hip: k_pair_dist_sum).  The forward is dfm_score's: same
+// uploads, time embedding, graph, layers and stream; then to_dist.0's projection GEMM into W.A / W.Bm as under DFM_F_DIST, and the fused
+// pair kernel in place of k_pair_dist - the [B,R,L,64] logits are never stored.
+static thread_local double g_distogram_ms[2] = {};
+
+extern "C" int dfm_score_distogram(dfm_complex *cx, int B, const float *lig_pos, const float *t, const int32_t *edges, uint64_t seed,
+                                   uint32_t flags, const dfm_distogram_params *prm, dfm_distogram_out *out)
+{
+    if (!cx || !lig_pos || !t || !prm || !out || !out->nll || !out->nll_near || !out->n_near || !out->exp_contacts)
+        return fail(DFM_E_INVALID, "NULL argument");
+    if (B < 1) return fail(DFM_E_INVALID, "B must be >= 1");
+    if (cx->m->hp.family != 1) return fail(DFM_E_INVALID, "dfm_score_distogram needs a family-1 model (EGNN_Net has to_dist, Score_Net does not)");
+    if (prm->contact_bins < 1 || prm->contact_bins > 63) return fail(DFM_E_INVALID, "contact_bins must be in 1..63");
+    if (prm->near_cutoff != prm->near_cutoff) return fail(DFM_E_INVALID, "near_cutoff is NaN");
+    if (flags & (DFM_F_L0_TABLE | DFM_F_PROFILE | DFM_F_DIST | DFM_F_IRES))
+        return fail(DFM_E_INVALID, "dfm_score_distogram takes the engine flags only (DFM_F_MFMA16, DFM_F_F16, DFM_F_BF16_OPS)");
+    const float near_cut = prm->near_cutoff > 0.f ? prm->near_cutoff : cx->m->hp.cut_off;
+    const bool f16 = flags & DFM_F_F16, bf16 = (flags & DFM_F_MFMA16) || f16;
+    DEVICE_SCOPE(cx->device);
+    int rc = ensure_workspace(cx, B, bf16, false);
+    if (rc) return rc;
+    Workspace &W = cx->ws;
+    hipStream_t s = cx->stream;
+    const size_t N = cx->N, L = cx->L, K = cx->K, RL = (size_t)cx->R * L;
+    cx->prof = dfm_profile{};
+    cx->ev_used = 0; cx->ev_l0_used = 0;
+    cx->fwd_counter = 0;
+    struct Ev {
+        hipEvent_t e = nullptr;
+        ~Ev() { if (e) (void)hipEventDestroy(e); }
+    } ev_begin, ev_end;
+    HIPCHK(hipEventCreate(&ev_begin.e)); HIPCHK(hipEventCreate(&ev_end.e));
+    HIPCHK(hipEventRecord(ev_begin.e, s));
+    HIPCHK(hipMemcpyAsync(W.lig_cur, lig_pos, (size_t)B * L * 9 * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(W.t_dev, t, (size_t)B * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(launch_time_embed(W.t_dev, B, &cx->m->heads, W.hid_base, s));
+    DevPool tmp;
+    tmp.bind(cx->stream);
+    int32_t *edges_dev = nullptr;
+    if (edges) {
+        HIPCHK(tmp.alloc(&edges_dev, (size_t)B * N * K));
+        HIPCHK(hipMemcpyAsync(edges_dev, edges, (size_t)B * N * K * 4, hipMemcpyHostToDevice, s));
+    }
+    const int n_part = pair_dist_sum_parts(cx->R, (int)L);
+    double *part = nullptr, *res = nullptr;
+    float *d_nll = nullptr, *d_pc = nullptr, *d_ed = nullptr, *d_mean = nullptr;
+    HIPCHK(tmp.alloc(&part, (size_t)B * n_part * 4));
+    HIPCHK(tmp.alloc(&res, (size_t)B * 4));
+    if (out->pair_nll) HIPCHK(tmp.alloc(&d_nll, (size_t)B * RL));
+    if (out->pcontact || out->pcontact_mean) HIPCHK(tmp.alloc(&d_pc, (size_t)B * RL));
+    if (out->edist) HIPCHK(tmp.alloc(&d_ed, (size_t)B * RL));
+    if (out->pcontact_mean) HIPCHK(tmp.alloc(&d_mean, RL));
+    FwdOpts o;
+    o.bf16 = bf16; o.f16 = f16; o.bf16_ops = bf16 && !f16 && (flags & DFM_F_BF16_OPS); o.want_energy = false; o.profile = false; o.edges_dev = edges_dev;
+    o.edges_pitch = (int64_t)N * K; o.seed = seed; o.h_first_out = nullptr; o.l0_table = false;
+    o.need_node_out = true;
+    HIPCHK(hipEventRecord(cx->ev_total[0], s));
+    rc = enqueue_forward(cx, B, o);
+    if (rc == DFM_OK) {
+        const dfm_model *m = cx->m;
+        GemmArgs g;
+        std::memset(&g, 0, sizeof(g));
+        g.A0 = W.h; g.lda = H; g.K = H; g.W = m->dist.wab; g.ldw = H; g.M = (int)(B * N); g.Nout = 2 * H; g.epi = 2; g.C = W.A; g.ldc = H;
+        g.C2 = W.Bm;
+        hipError_t e = launch_gemm_f32(g, s);
+        PairDistSumArgs a;
+        a.P = W.A; a.Q = W.Bm; a.ca4 = W.ca4; a.B = B; a.R = cx->R; a.L = (int)L;
+        a.w_d = m->dist.w_d; a.ln_w = m->dist.ln_w; a.ln_b = m->dist.ln_b; a.w3f = m->dist_w3f;
+        a.contact_bins = prm->contact_bins; a.near_cut = near_cut;
+        a.pair_nll = d_nll; a.pcontact = d_pc; a.edist = d_ed; a.pcontact_mean = d_mean; a.part = part; a.res = res;
+        if (e == hipSuccess) e = launch_pair_dist_sum(a, s);
+        if (e != hipSuccess) rc = fail(DFM_E_HIP, hipGetErrorString(e));
+    }
+    if (rc == DFM_OK) {
+        std::vector<double> hres((size_t)B * 4);
+        hipError_t e = hipEventRecord(cx->ev_total[1], s);
+        if (e == hipSuccess) e = hipMemcpyAsync(hres.data(), res, hres.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && out->pair_nll) e = hipMemcpyAsync(out->pair_nll, d_nll, (size_t)B * RL * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && out->pcontact) e = hipMemcpyAsync(out->pcontact, d_pc, (size_t)B * RL * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && out->edist) e = hipMemcpyAsync(out->edist, d_ed, (size_t)B * RL * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && out->pcontact_mean) e = hipMemcpyAsync(out->pcontact_mean, d_mean, RL * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipEventRecord(ev_end.e, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) rc = fail(DFM_E_HIP, hipGetErrorString(e));
+        else {
+            for (int b = 0; b < B; ++b) {
+                out->nll[b] = (float)hres[(size_t)b * 4]; out->nll_near[b] = (float)hres[(size_t)b * 4 + 1];
+                out->n_near[b] = (int32_t)hres[(size_t)b * 4 + 2]; out->exp_contacts[b] = (float)hres[(size_t)b * 4 + 3];
+            }
+            float up_ms = 0.f, k_ms = 0.f, down_ms = 0.f;
+            (void)hipEventElapsedTime(&up_ms, ev_begin.e, cx->ev_total[0]);
+            (void)hipEventElapsedTime(&k_ms, cx->ev_total[0], cx->ev_total[1]);
+            (void)hipEventElapsedTime(&down_ms, cx->ev_total[1], ev_end.e);
+            g_distogram_ms[0] = (double)up_ms + (double)down_ms;
+            g_distogram_ms[1] = (double)k_ms;
+        }
+    }
+    if (rc != DFM_OK) (void)hipStreamSynchronize(s);   // nothing may still read the per-call buffers when they are released
+    return rc;
+}
+
+extern "C" int dfm_distogram_last_timing(double *copy_ms, double *kernel_ms)
+{
+    if (!copy_ms || !kernel_ms) return fail(DFM_E_INVALID, "NULL argument");
+    *copy_ms = g_distogram_ms[0];
+    *kernel_ms = g_distogram_ms[1];
+    return DFM_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -259,6 +259,21 @@ hipError_t launch_pair_finish_s(const PairArgs &a, int n_part, float inv_pool, f
 // dist_logits [B][R][L][64] = Linear(256 -> 64)(SiLU(LayerNorm(P_r + Q_l + w_d D)))  (egnn_net.py:347-352,:447); exact fp32
 hipError_t launch_pair_dist(const float *P, const float *Q, const float4 *ca4, int B, int R, int L, const float *w_d, const float *ln_w,
                             const float *ln_b, const float *w3t /*[256][64]*/, float *out, hipStream_t s);
+// The distogram head reduced inside the pair kernel (k_pair_dist_sum + k_dist_finish + k_dist_mean): per-pose sums in res[B][4] =
+// {mean nll, mean nll over D < near_cut, count of those, sum of pcontact}; per-pair maps [B][R][L] only where a pointer is given
+// (pcontact_mean [R][L] needs pcontact).  part: pair_dist_sum_parts(R, L) * 4 doubles per trajectory.
+struct PairDistSumArgs {
+    const float *P, *Q;
+    const float4 *ca4;
+    int B, R, L;
+    const float *w_d, *ln_w, *ln_b, *w3f;      // w3f: to_dist.3 in MFMA fragment order, 1 / SILU_S folded in (pack_dist_w3f in api.hip)
+    int contact_bins;
+    float near_cut;
+    float *pair_nll, *pcontact, *edist, *pcontact_mean;
+    double *part, *res;
+};
+inline int pair_dist_sum_parts(int R, int L) { return ((R + 31) / 32) * ((L + 63) / 64) * 4; }
+hipError_t launch_pair_dist_sum(const PairDistSumArgs &a, hipStream_t s);
 hipError_t launch_pair_finish(const float *fpart, int B, int R, int L, float inv_pool, float *fvec, const float *cpart,
                               float *conf, hipStream_t s);
 

@@ -473,6 +473,311 @@ hipError_t launch_pair_dist(const float *P, const float *Q, const float4 *ca4, i
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The distogram head reduced in place (dfm_score_distogram): to_dist's 64 logits of every pair never leave the registers.
+// k_pair_head_m's workgroup (32 receptor residues x a 64-residue ligand chunk x trajectory; staged P tile, LayerNorm statistics from row
+// moments and the P.Q MFMA pass, rank-4 outer product for the pre-activation) with to_dist's own weights, then
+//   * the 256 -> 64 projection on the matrix pipe.  After the SiLU the lane (hh, r32) holds, for ITS receptor residue, the channels
+//     cb 32 + 8 g + 4 hh + e: exactly the B operand of v_mfma_f32_32x32x2_f32 (lane = (k = hh, n = residue)) when k = 0 / 1 is paired
+//     with the channels the hh = 0 / 1 lanes hold (any pairing of k with channels is a valid contraction order, as in the dot pass).  The
+//     A operand is W3[o = ob 32 + r32][that channel], read from LDS in that fragment order (packed on the host, 1 / SILU_S folded in): no
+//     transposition, no LDS round trip of the activations, no barrier inside the pair loop.  Two accumulators (ob = 0, 1) leave lane
+//     (hh, r32) with logits o = ob 32 + 8 (i / 4) + 4 hh + i % 4 of pair (r32, l); the partner lane (xor 32) holds the other 32.
+//   * log-softmax, the bin of the pose's own CA-CA distance (fp32 d^2 against fp32 bounds^2), contact probability and expected distance:
+//     in-lane over 32 logits + one __shfl_xor(.., 32) each.
+// Per-pair maps are written only where asked ([B][R][L]); the per-pose sums leave as one double[4] per wave (nll, nll over D < near,
+// count of those, sum of pcontact) that k_dist_finish adds in a fixed order: no atomics, batch-invariant.
+// LDS: the P tile (32 KiB), W3 fragments (64 KiB, dynamic), dots, moments, bin tables: one workgroup per CU.
+constexpr int PD_W3_BYTES = 64 * H * 4;
+constexpr float PD_BIN0 = 3.25f, PD_STEP = (50.75f - 3.25f) / 62.0f;
+
+struct PairDArgs {
+    const float *P, *Q;
+    const float4 *ca4;
+    int R, L;
+    const float *w_d, *ln_w, *ln_b;
+    const float *w3f;          // [2][64][32][4]: w3f[((ob 64 + c4) 32 + m) 4 + e] = W3[ob 32 + m][c4 4 + e] / SILU_S
+    int contact_bins;
+    float near_cut;
+    float *pair_nll, *pcontact, *edist;      // [B][R][L] each, or nullptr
+    double *part;              // [B][gridDim.x * gridDim.y][4 waves][4]
+};
+
+__global__ __launch_bounds__(256) void k_pair_dist_sum(PairDArgs p)
+{
+    constexpr float SS = -1.44269504088896340736f;      // SILU_S
+    extern __shared__ __attribute__((aligned(16))) float W3s[];       // fragment order, see PairDArgs::w3f
+    __shared__ __attribute__((aligned(16))) float Pl[H * PM_RT];      // [c / 4][r][4]
+    __shared__ float dots[4][PM_LW][PM_RT];
+    __shared__ float momp[8][3][PM_RT];
+    __shared__ __attribute__((aligned(16))) float b2s[64], cens[64];  // bounds^2 (b2s[63] = +inf), bin centres
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int hh = lane >> 5, r32 = lane & 31;
+    const int rt = blockIdx.x, lc = blockIdx.y, b = blockIdx.z, N = p.R + p.L;
+    const int l_begin = lc * PM_LC, l_end = l_begin + PM_LC < p.L ? l_begin + PM_LC : p.L;
+    const int r = rt * PM_RT + r32;
+    const bool valid = r < p.R;
+
+    // ---- stage the raw tile, row moments on the way (k_pair_head_m); W3 fragments and the bin tables next to it
+    {
+        const int grp = tid >> 5;
+        const float *prow = p.P + ((size_t)b * N + (valid ? r : 0)) * H;
+        float s1 = 0.f, s2 = 0.f, sw = 0.f;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int c4 = grp + 8 * q;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (valid) v = *reinterpret_cast<const float4 *>(prow + c4 * 4);
+            const float4 wd = *reinterpret_cast<const float4 *>(p.w_d + c4 * 4);
+            *reinterpret_cast<float4 *>(&Pl[(c4 * PM_RT + r32) * 4]) = v;
+            s1 += (v.x + v.y) + (v.z + v.w);
+            s2 += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+            sw += (v.x * wd.x + v.y * wd.y) + (v.z * wd.z + v.w * wd.w);
+        }
+        momp[grp][0][r32] = s1; momp[grp][1][r32] = s2; momp[grp][2][r32] = sw;
+        for (int q = tid; q < 64 * H / 4; q += 256)
+            reinterpret_cast<float4 *>(W3s)[q] = reinterpret_cast<const float4 *>(p.w3f)[q];
+        if (tid < 64) {
+            const float bd = PD_BIN0 + PD_STEP * (float)tid;
+            b2s[tid] = tid < 63 ? bd * bd : __builtin_inff();
+            cens[tid] = PD_BIN0 + PD_STEP * ((float)tid - 0.5f);
+        }
+    }
+    __syncthreads();
+    float mP = 0.f, mP2 = 0.f, mPw = 0.f;
+#pragma unroll
+    for (int g = 0; g < 8; ++g) { mP += momp[g][0][r32]; mP2 += momp[g][1][r32]; mPw += momp[g][2][r32]; }
+    float sum_w, sum_w2;
+    {
+        const float4 wd4 = *reinterpret_cast<const float4 *>(p.w_d + lane * 4);
+        sum_w = wave_sum((wd4.x + wd4.y) + (wd4.z + wd4.w));
+        sum_w2 = wave_sum((wd4.x * wd4.x + wd4.y * wd4.y) + (wd4.z * wd4.z + wd4.w * wd4.w));
+    }
+
+    // ---- dot products P_r . Q_l of the wave's 16 ligand residues + the moments of those rows (k_pair_head_m)
+    float sQv, sQ2v, sQwv;
+    {
+        const int lrow = l_begin + wave + 4 * r32;
+        const bool lv = r32 < PM_LW && lrow < l_end;
+        const float *qrow = p.Q + ((size_t)b * N + p.R + (lv ? lrow : 0)) * H;
+        f32x16 dacc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) dacc[i] = 0.f;
+        float s1 = 0.f, s2 = 0.f, sw = 0.f;
+#pragma unroll 4
+        for (int pg = 0; pg < 32; ++pg) {
+            const int c4 = pg * 2 + hh;
+            float4 q4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (lv) q4 = *reinterpret_cast<const float4 *>(qrow + c4 * 4);
+            const float4 wd = *reinterpret_cast<const float4 *>(p.w_d + c4 * 4);
+            const float4 p4 = *reinterpret_cast<const float4 *>(&Pl[(c4 * PM_RT + r32) * 4]);
+            s1 += (q4.x + q4.y) + (q4.z + q4.w);
+            s2 += (q4.x * q4.x + q4.y * q4.y) + (q4.z * q4.z + q4.w * q4.w);
+            sw += (q4.x * wd.x + q4.y * wd.y) + (q4.z * wd.z + q4.w * wd.w);
+            dacc = __builtin_amdgcn_mfma_f32_32x32x2f32(q4.x, p4.x, dacc, 0, 0, 0);
+            dacc = __builtin_amdgcn_mfma_f32_32x32x2f32(q4.y, p4.y, dacc, 0, 0, 0);
+            dacc = __builtin_amdgcn_mfma_f32_32x32x2f32(q4.z, p4.z, dacc, 0, 0, 0);
+            dacc = __builtin_amdgcn_mfma_f32_32x32x2f32(q4.w, p4.w, dacc, 0, 0, 0);
+        }
+        sQv = s1 + __shfl_xor(s1, 32); sQ2v = s2 + __shfl_xor(s2, 32); sQwv = sw + __shfl_xor(sw, 32);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) dots[wave][8 * (i >> 2) + 4 * hh + (i & 3)][r32] = dacc[i];
+    }
+    __syncthreads();
+    // ---- scale the tile in place: P'' = S ln_w P
+    {
+        const int grp = tid >> 5;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int c4 = grp + 8 * q;
+            const float4 w = *reinterpret_cast<const float4 *>(p.ln_w + c4 * 4);
+            float4 *dst = reinterpret_cast<float4 *>(&Pl[(c4 * PM_RT + r32) * 4]);
+            float4 v = *dst;
+            v.x *= SS * w.x; v.y *= SS * w.y; v.z *= SS * w.z; v.w *= SS * w.w;
+            *dst = v;
+        }
+    }
+    float A2[8], aux[8];
+#pragma unroll
+    for (int cb = 0; cb < 8; ++cb) {
+        const int c = cb * 32 + r32;
+        const float lw = SS * p.ln_w[c];
+        A2[cb] = hh ? SS * p.ln_b[c] : lw;
+        aux[cb] = hh ? lw : lw * p.w_d[c];
+    }
+    __syncthreads();
+
+    const float4 xr = p.ca4[(size_t)b * N + (valid ? r : 0)];
+    const float4 *Pl4 = reinterpret_cast<const float4 *>(Pl);
+    const float4 *W3s4 = reinterpret_cast<const float4 *>(W3s);
+    const float4 *b2s4 = reinterpret_cast<const float4 *>(b2s), *cens4 = reinterpret_cast<const float4 *>(cens);
+    const int cbins = p.contact_bins - 4 * hh;      // logit o = (constant of (ob, i)) + 4 hh: compare the constant
+    float qn[8];
+    {
+        const int l0 = l_begin + wave < l_end ? l_begin + wave : l_end - 1;
+        const float *Ql = p.Q + ((size_t)b * N + p.R + l0) * H;
+#pragma unroll
+        for (int cb = 0; cb < 8; ++cb) qn[cb] = Ql[cb * 32 + r32];
+    }
+    double a_nll = 0, a_near = 0, a_pc = 0, a_cnt = 0;
+    for (int it = 0; it < PM_LW; ++it) {
+        const int l = l_begin + wave + 4 * it;
+        if (l >= l_end) break;
+        float A1[8];
+#pragma unroll
+        for (int cb = 0; cb < 8; ++cb) A1[cb] = hh ? qn[cb] * aux[cb] : aux[cb];
+        {
+            const int ln = l + 4 < l_end ? l + 4 : l;
+            const float *Ql = p.Q + ((size_t)b * N + p.R + ln) * H;
+#pragma unroll
+            for (int cb = 0; cb < 8; ++cb) qn[cb] = Ql[cb * 32 + r32];
+        }
+        const float4 xl = p.ca4[(size_t)b * N + p.R + l];
+        const float dx = xr.x - xl.x, dy = xr.y - xl.y, dz = xr.z - xl.z;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        const float D = sqrtf(d2);
+        const float sq = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sQv), it));
+        const float sq2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sQ2v), it));
+        const float sqw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sQwv), it));
+        const float dot = dots[wave][it][r32];
+        const float mean = ((mP + sq) + D * sum_w) * (1.0f / H);
+        const float ez2 = (((mP2 + sq2) + 2.0f * dot) + D * (2.0f * (mPw + sqw) + D * sum_w2)) * (1.0f / H);
+        const float rstd = __builtin_amdgcn_rsqf(fmaxf(ez2 - mean * mean, 0.f) + 1e-5f);
+        const float B1 = hh ? rstd : rstd * D, B2 = hh ? 1.0f : -mean * rstd;
+        f32x16 acc[2], z[2];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; z[0][i] = 0.f; z[1][i] = 0.f; }
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(A2[0], B2, acc[0], 0, 0, 0);
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(A1[0], B1, acc[0], 0, 0, 0);
+#pragma unroll
+        for (int cb = 0; cb < 8; ++cb) {
+            if (cb + 1 < 8) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[(cb + 1) & 1][i] = 0.f;
+                acc[(cb + 1) & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(A2[cb + 1], B2, acc[(cb + 1) & 1], 0, 0, 0);
+                acc[(cb + 1) & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(A1[cb + 1], B1, acc[(cb + 1) & 1], 0, 0, 0);
+            }
+            const f32x16 &a = acc[cb & 1];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int c4 = (cb * 4 + g) * 2 + hh;
+                const float4 p4 = Pl4[c4 * PM_RT + r32];
+                const float4 wa = W3s4[c4 * PM_RT + r32], wb = W3s4[(64 + c4) * PM_RT + r32];
+                const float y0 = fmaf(p4.x, rstd, a[g * 4 + 0]), y1 = fmaf(p4.y, rstd, a[g * 4 + 1]);
+                const float y2 = fmaf(p4.z, rstd, a[g * 4 + 2]), y3 = fmaf(p4.w, rstd, a[g * 4 + 3]);
+                const float u0 = y0 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y0)), u1 = y1 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y1));
+                const float u2 = y2 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y2)), u3 = y3 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y3));
+                z[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa.x, u0, z[0], 0, 0, 0);
+                z[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wb.x, u0, z[1], 0, 0, 0);
+                z[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa.y, u1, z[0], 0, 0, 0);
+                z[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wb.y, u1, z[1], 0, 0, 0);
+                z[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa.z, u2, z[0], 0, 0, 0);
+                z[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wb.z, u2, z[1], 0, 0, 0);
+                z[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa.w, u3, z[0], 0, 0, 0);
+                z[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wb.w, u3, z[1], 0, 0, 0);
+            }
+        }
+        // ---- the 64 bins of this pair: 32 in this lane, 32 in lane ^ 32
+        int cnt = 0;
+        float zm = z[0][0];
+#pragma unroll
+        for (int ob = 0; ob < 2; ++ob)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 b4 = b2s4[ob * 8 + g * 2 + hh];
+                cnt += (d2 > b4.x ? 1 : 0) + (d2 > b4.y ? 1 : 0) + (d2 > b4.z ? 1 : 0) + (d2 > b4.w ? 1 : 0);
+                zm = fmaxf(fmaxf(zm, fmaxf(z[ob][g * 4], z[ob][g * 4 + 1])), fmaxf(z[ob][g * 4 + 2], z[ob][g * 4 + 3]));
+            }
+        cnt += __shfl_xor(cnt, 32);
+        zm = fmaxf(zm, __shfl_xor(zm, 32));
+        const int bin_c = cnt - 4 * hh;
+        float es = 0.f, pc = 0.f, ed = 0.f, zt = 0.f;
+#pragma unroll
+        for (int ob = 0; ob < 2; ++ob)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 c4v = cens4[ob * 8 + g * 2 + hh];
+                const float cen[4] = {c4v.x, c4v.y, c4v.z, c4v.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int oc = ob * 32 + g * 8 + e;      // + 4 hh = the logit's index
+                    const float zv = z[ob][g * 4 + e];
+                    const float ev = __builtin_amdgcn_exp2f((zv - zm) * 1.44269504088896340736f);
+                    es += ev;
+                    pc += oc < cbins ? ev : 0.f;
+                    ed = fmaf(ev, cen[e], ed);
+                    zt += oc == bin_c ? zv : 0.f;
+                }
+            }
+        es += __shfl_xor(es, 32); pc += __shfl_xor(pc, 32); ed += __shfl_xor(ed, 32); zt += __shfl_xor(zt, 32);
+        const float nll = (zm - zt) + logf(es);
+        const float pcon = pc / es, edv = ed / es;
+        if (hh == 0 && valid) {
+            const size_t o = ((size_t)b * p.R + r) * p.L + l;
+            if (p.pair_nll) p.pair_nll[o] = nll;
+            if (p.pcontact) p.pcontact[o] = pcon;
+            if (p.edist) p.edist[o] = edv;
+            a_nll += (double)nll; a_pc += (double)pcon;
+            if (D < p.near_cut) { a_near += (double)nll; a_cnt += 1.0; }
+        }
+    }
+    a_nll = wave_sum_d(a_nll); a_near = wave_sum_d(a_near); a_cnt = wave_sum_d(a_cnt); a_pc = wave_sum_d(a_pc);
+    if (lane == 0) {
+        double *po = p.part + ((((size_t)b * gridDim.x + rt) * gridDim.y + lc) * 4 + wave) * 4;
+        po[0] = a_nll; po[1] = a_near; po[2] = a_cnt; po[3] = a_pc;
+    }
+}
+
+// res[b] = {mean nll, mean nll over the near pairs (0 / 0 = NaN without any), their count, sum of pcontact}: the n_part wave partials
+// of trajectory b added in index order in double, one thread per quantity
+__global__ __launch_bounds__(64) void k_dist_finish(const double *__restrict__ part, int n_part, double pairs, double *__restrict__ res)
+{
+    __shared__ double red[4];
+    const int b = blockIdx.x, k = threadIdx.x;
+    if (k < 4) {
+        double s = 0;
+        for (int t = 0; t < n_part; ++t) s += part[((size_t)b * n_part + t) * 4 + k];
+        red[k] = s;
+    }
+    __syncthreads();
+    if (k == 0) {
+        double *o = res + (size_t)b * 4;
+        o[0] = red[0] / pairs; o[1] = red[1] / red[2]; o[2] = red[2]; o[3] = red[3];
+    }
+}
+
+// pcontact_mean[q] = mean over the B poses of pc[b][q], added in index order in double
+__global__ __launch_bounds__(256) void k_dist_mean(const float *__restrict__ pc, int B, size_t n, float *__restrict__ out)
+{
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    double s = 0;
+    for (int b = 0; b < B; ++b) s += (double)pc[(size_t)b * n + q];
+    out[q] = (float)(s / (double)B);
+}
+
+hipError_t launch_pair_dist_sum(const PairDistSumArgs &a, hipStream_t s)
+{
+    static std::atomic<bool> attr_done[MAX_DEVICES];
+    {
+        hipError_t e = ensure_lds_attr(reinterpret_cast<const void *>(k_pair_dist_sum), PD_W3_BYTES, attr_done);
+        if (e != hipSuccess) return e;
+    }
+    PairDArgs k;
+    k.P = a.P; k.Q = a.Q; k.ca4 = a.ca4; k.R = a.R; k.L = a.L; k.w_d = a.w_d; k.ln_w = a.ln_w; k.ln_b = a.ln_b; k.w3f = a.w3f;
+    k.contact_bins = a.contact_bins; k.near_cut = a.near_cut; k.pair_nll = a.pair_nll; k.pcontact = a.pcontact; k.edist = a.edist; k.part = a.part;
+    const dim3 grid((a.R + PM_RT - 1) / PM_RT, (a.L + PM_LC - 1) / PM_LC, a.B);
+    hipLaunchKernelGGL(k_pair_dist_sum, grid, dim3(256), PD_W3_BYTES, s, k);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_dist_finish, dim3(a.B), dim3(64), 0, s, a.part, pair_dist_sum_parts(a.R, a.L), (double)a.R * (double)a.L, a.res);
+    e = hipGetLastError();
+    if (e != hipSuccess || !a.pcontact_mean) return e;
+    const size_t n = (size_t)a.R * a.L;
+    hipLaunchKernelGGL(k_dist_mean, dim3((unsigned)((n + 255) / 256)), dim3(256), token_lds(), s, a.pcontact, a.B, n, a.pcontact_mean);
+    return hipGetLastError();
+}
+
 hipError_t launch_pair_head(const PairArgs &a, hipStream_t s)
 {
     static std::atomic<bool> attr_done[MAX_DEVICES];

@@ -389,9 +389,83 @@ def _remarks(sd, k):
             f"(heavy-atom pairs below {sd['clash_cutoff']:g} / {sd['contact_cutoff']:g} A)"]
 
 
+DISTOGRAM_T = 1e-3      # time of the distogram evaluation of final poses: the end of the sampler's grid
+
+
+def ensemble_distogram(gx: engine.Complex, rot_update, tr_update, t=DISTOGRAM_T, precision="mfma16", max_batch=256, contact_bins=7,
+                       near_cutoff=None, maps=False, seed=0):
+    """The distogram head (family 1) of trajectories from their final (rot_update, tr_update) alone, on the open handle `gx`
+    (Complex.distogram, dfm_score_distogram): the poses are rebuilt from the input backbone (cluster.rebuild_backbone) and evaluated at
+    time `t` in chunks of max_batch.  Returns nll, nll_near, exp_contacts (float64 [P]), n_near (int [P]), t, contact_bins and, with
+    `maps`, pcontact_mean [R,L] (the mean over ALL P poses, added in index order in double across the chunks) and edist [P,R,L]."""
+    from .cluster import rebuild_backbone
+    rot, tr = np.asarray(rot_update, np.float32).reshape(-1, 3), np.asarray(tr_update, np.float32).reshape(-1, 3)
+    P, mb = rot.shape[0], max(1, int(max_batch))
+    out = {k: [] for k in ("nll", "nll_near", "n_near", "exp_contacts")}
+    psum, ed = np.zeros((gx.R, gx.L), np.float64), []
+    for p0 in range(0, P, mb):
+        poses = rebuild_backbone(gx.lig_pos0, rot[p0:p0 + mb], tr[p0:p0 + mb], gx.model.hp.family)
+        r = gx.distogram(poses, t, seed=seed + p0, maps=("pcontact", "edist") if maps else (), contact_bins=contact_bins,
+                         near_cutoff=near_cutoff, **engine.precision_kwargs(precision))
+        for k in out:
+            out[k].append(r[k])
+        if maps:
+            for b in range(poses.shape[0]):
+                psum += r["pcontact"][b]
+            ed.append(r["edist"])
+    res = {k: np.concatenate(v).astype(np.int64 if k == "n_near" else np.float64) for k, v in out.items()}
+    res.update(t=float(t), contact_bins=int(contact_bins))
+    if maps:
+        res.update(pcontact_mean=psum / P, edist=np.concatenate(ed, 0))
+    return res
+
+
+def _check_distogram(model, distogram, rank, distogram_t, distogram_maps, max_batch):
+    """None (off) or (rank by it, t, maps, max_batch) of a pair driver's distogram options; rank "distogram" implies them.  The head
+    exists in the second model family only: anything else is refused here, before a trajectory is sampled."""
+    if not distogram and rank != "distogram" and not distogram_maps:
+        return None
+    if model.hp.family != 1:
+        raise ValueError("the distogram head (distogram / rank 'distogram') needs a family-1 checkpoint: EGNN_Net has to_dist, Score_Net "
+                         "does not")
+    t = float(distogram_t)
+    if not (0.0 < t <= 1.0):
+        raise ValueError(f"distogram_t must be in (0, 1], got {distogram_t}")
+    return rank == "distogram", t, bool(distogram_maps), int(max_batch)
+
+
+def _distogram_pick(gx, cols, k, key, opts, bad, precision, seed=0):
+    """The distogram part of a pair driver, run while the handle is still open and BEFORE any per-pose summary is built.  opts = None
+    (off) or _check_distogram's.  Returns (k, key, data or None): under rank "distogram" k is the pose of the lowest nll among those the
+    clash filter left (ties: the lower index; NaN never wins) and key the nll values, NaN on the removed poses; otherwise k and key stay."""
+    if opts is None:
+        return k, key, None
+    by_it, t, maps, mb = opts
+    dd = ensemble_distogram(gx, cols["rot_update"], cols["tr_update"], t, precision, mb, maps=maps, seed=seed)
+    if by_it and not np.isnan(_nan_key(dd["nll"], bad)).all():
+        k, key = _kept(np.nanargmin, bad, dd["nll"]), _nan_key(dd["nll"], bad)
+    return k, key, dd
+
+
+def _pose_distogram(dd, k):
+    fin = lambda v: float(v) if np.isfinite(v) else None
+    return {"dist_nll": fin(dd["nll"][k]), "dist_nll_near": fin(dd["nll_near"][k]), "exp_contacts": fin(dd["exp_contacts"][k])}
+
+
+def _distogram_result(dd, k, opts, bad=None):
+    """The distogram entries of a pair driver's result for the FINAL kept pose k (none without the option)."""
+    if dd is None:
+        return {}
+    from .cluster import rank_order
+    nll = _nan_key(dd["nll"], bad)
+    summary = dict(_pose_distogram(dd, k), n_near=int(dd["n_near"][k]), rank=int(np.nonzero(rank_order(nll, len(nll)) == k)[0][0]) + 1,
+                   t=dd["t"], contact_bins=dd["contact_bins"], ranked_by_distogram=bool(opts[0]))
+    return {"distogram": summary, "distogram_data": dd, "index": int(k)}
+
+
 def _check_rank(rank, consensus_top):
-    if rank not in ("energy", "consensus", "interface"):
-        raise ValueError(f"rank must be 'energy', 'consensus' or 'interface', got {rank!r}")
+    if rank not in ("energy", "consensus", "interface", "distogram"):
+        raise ValueError(f"rank must be 'energy', 'consensus', 'interface' or 'distogram', got {rank!r}")
     if not (0.0 < float(consensus_top) <= 1.0):
         raise ValueError(f"consensus_top must be in (0, 1], got {consensus_top}")
 
@@ -812,7 +886,7 @@ def _center(model):
 
 
 def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native=None, cons=None, ster=None, clu=None, refine=None,
-            surf=None, ie=None, aff=None):
+            surf=None, ie=None, aff=None, dg=None, seed=0):
     """What every pair driver does with its sampled trajectories: the kept pose, its files and the result.  cols: every trajectory's
     energy, rot_update, tr_update (and the driver's own columns).  pick = (rule, *column names): the driver's own choice, rule(*columns) ->
     index; key: the clustering key that goes with it.  entries(k): the driver's own result entries for the kept pose k.  cons / ster / clu:
@@ -820,16 +894,22 @@ def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_p
     _check_interface; aff: None or the options of _check_affinity; refine: None or the keyword arguments of refine_models - only then
     does the handle outlive the sampling."""
     lig0 = gx.lig_pos0
-    if refine is None:      # the columns are host arrays: the handle (and its ~GB of device workspace) goes before any post-processing
+    if refine is None and dg is None:      # the columns are host arrays: the handle (and its ~GB of device workspace) goes before any post-processing
         gx.close()
     sd, bad = _screen(model, rec, lig, cols, ster)
     k = _kept(pick[0], bad, *(cols[c] for c in pick[1:]))
+    # the model's own distogram needs the open handle (a forward per pose): evaluated here, the handle goes right after it
+    k, key, dd = _distogram_pick(gx, cols, k, _nan_key(key, bad), dg, bad, precision, seed)
+    if refine is None and dg is not None:
+        gx.close()
     # the kept pose is settled first - the driver's rule, then rank "interface", then rank "consensus" (one rank is given, so at most one
     # of the two moves k) - and only then does anything describe it
     k, key, ed = _interface_pick(model, rec, lig, cols, k, _nan_key(key, bad), ie, bad)
-    k, key, extra = _with_consensus(model, rec, lig0, cols, k, key, cons, bad, "interface" if ie is not None and ie[0] else "energy")
+    k, key, extra = _with_consensus(model, rec, lig0, cols, k, key, cons, bad,
+                                    "interface" if ie is not None and ie[0] else "distogram" if dg is not None and dg[0] else "energy")
     key = _nan_key(key, bad)      # again: rank "consensus" has replaced the key by consensus.rank_positions
     extra.update(_interface_result(ed, k, ie, bad, extra["consensus"]["ranked_by"] if "consensus" in extra else "energy"))
+    extra.update(_distogram_result(dd, k, dg, bad))
     extra.update(_sterics_result(sd, k))
     # one surface call serves both when the surface options are the ones the affinity estimate takes (probe 1.4 A, 128 points)
     shared = surf is not None and aff is not None and (surf[1], surf[2]) == _check_surface(True, None, *AFFINITY_SURFACE)[1:]
@@ -844,11 +924,11 @@ def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_p
     res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, **entries(k)}
     res.update(extra)
-    if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
+    if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None or dg is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
         res.setdefault("trajectories", {c: cols[c] for c in ("energy", "rot_update", "tr_update")})
     _selected_metrics(model, native, rec, lig0, res)
     if clu is not None:
-        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad, bd, None if surf is None else surf[0], ed, ad))
+        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad, bd, None if surf is None else surf[0], ed, ad, dd))
         if refine is not None:
             refine_models(model, gx, rec, lig, lig0, cols, res["models"], precision=precision, out_pdb=out_pdb, native=native, **refine)
             gx.close()
@@ -860,7 +940,8 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
               restraint_rank="satisfied", restraint_params=None, top_k=None, cluster_radius=4.0, cluster_rule="energy", refine_t=None,
               refine_samples=8, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
               clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, bsa=False, min_bsa=None, probe=1.4, sphere_points=128,
-              interface_energy=False, ie_weights=None, ie_cutoff=8.0, affinity=False, affinity_cutoff=5.5, **sampler_kw):
+              interface_energy=False, ie_weights=None, ie_cutoff=8.0, affinity=False, affinity_cutoff=5.5, distogram=False,
+              distogram_t=DISTOGRAM_T, distogram_maps=False, **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
     pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
     the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
@@ -916,8 +997,17 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     trajectory (pose_affinity: IC-NIS with starting values that are not verified or calibrated, on this project's own surface).  The
     result gains `affinity` ({ic, n_pairs, n_rec_res, n_lig_res, nis_apolar, nis_charged, dg, kd, cutoff} of the kept pose; dg in
     kcal/mol, kd in M, None where there is no surface residue), `affinity_data` (the arrays of every trajectory, with dg_contacts),
-    `index` and `trajectories`; every model of `top_k` gains `affinity`.  Nothing is ranked by it."""
+    `index` and `trajectories`; every model of `top_k` gains `affinity`.  Nothing is ranked by it.
+
+    `distogram` (family-1 models only; anything else raises before sampling): the model's own distogram head at every final pose
+    (ensemble_distogram: one forward per pose at time `distogram_t`, in chunks of max_batch, reduced on the GPU).  The result gains
+    `distogram` ({dist_nll, dist_nll_near, exp_contacts, n_near} of the kept pose, its rank by nll, t, contact_bins), `distogram_data`
+    (the arrays; with `distogram_maps` also pcontact_mean [R,L] and edist [P,R,L]), `index` and `trajectories`; every model of `top_k`
+    gains dist_nll, dist_nll_near and exp_contacts.  rank="distogram" (implies distogram) keeps the pose with the lowest nll instead
+    (ties: lower index; it overrides restraint_rank) and makes the nll values the clustering key of `top_k`; poses `clash_filter` removed
+    get a NaN key as under rank "consensus"."""
     _check_rank(rank, consensus_top)
+    dg = _check_distogram(model, distogram, rank, distogram_t, distogram_maps, max_batch)
     cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
     ster = _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff)
     surf = _check_surface(bsa, min_bsa, probe, sphere_points)
@@ -963,7 +1053,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     cols = {c: np.concatenate(v, 0) for c, v in cols.items()}
     if not restrained:
         # the loop's own minimum; consensus and the screen choose among all trajectories at once (the first minimum: the same pose)
-        pick = (np.argmin if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None
+        pick = (np.argmin if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None or dg is not None
                 else (lambda energy: k0), "energy")
         key, entries = cols["energy"], lambda k: {}
     else:
@@ -975,14 +1065,15 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         entries = lambda k: {"index": k, "restraints": len(restraints), "restraint_rank": restraint_rank,
                              "restraint_energy": float(cols["restraint_energy"][k]), "restraints_satisfied": int(cols["restraints_satisfied"][k]),
                              "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
-    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine, surf, ie, aff)
+    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine, surf, ie, aff, dg, seed)
 
 
 def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
                 out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", perturb=True, restraints=None,
                 restraint_params=None, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
                 clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, start_shift=None, bsa=False, min_bsa=None, probe=1.4,
-                sphere_points=128, interface_energy=False, ie_weights=None, ie_cutoff=8.0, affinity=False, affinity_cutoff=5.5, **sampler_kw):
+                sphere_points=128, interface_energy=False, ie_weights=None, ie_cutoff=8.0, affinity=False, affinity_cutoff=5.5, distogram=False,
+                distogram_t=DISTOGRAM_T, distogram_maps=False, **sampler_kw):
     """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories
     start from that pose noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps
     down from t_begin; like dock_pair the minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns
@@ -993,9 +1084,11 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
     `bsa` / `min_bsa` / `probe` / `sphere_points`: as for dock_pair (there are no models here, so min_bsa only turns bsa on).
     `interface_energy` / `ie_weights` / `ie_cutoff` and rank="interface": as for dock_pair.
     `affinity` / `affinity_cutoff`: as for dock_pair.
+    `distogram` / `distogram_t` / `distogram_maps` and rank="distogram": as for dock_pair.
     `start_shift` ([num_samples,3]): trajectory i starts from the input pose translated by start_shift[i] (the engine's start_pos); the
     shift is added to its tr_update, so (rot_update, tr_update) keep mapping the INPUT pose onto the final one."""
     _check_rank(rank, consensus_top)
+    dg = _check_distogram(model, distogram, rank, distogram_t, distogram_maps, max_batch)
     cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
     ster = _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff)
     surf = _check_surface(bsa, min_bsa, probe, sphere_points)
@@ -1027,7 +1120,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
         done += b
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
     res = _finish(model, gx, rec, lig, cols, (np.argmin, "energy"), None,      # the first minimum wins, as in dock_pair
-                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster, surf=surf, ie=ie, aff=aff)
+                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster, surf=surf, ie=ie, aff=aff, dg=dg, seed=seed)
     if native is not None:
         res["start_metrics"] = native_metrics(model, native, rec["bb_coords"], gx.lig_pos0[None])[0]
     return res
@@ -1059,12 +1152,14 @@ def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps
     return models
 
 
-def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=None, bad=None, bd=None, min_bsa=None, ed=None, ad=None):
+def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=None, bad=None, bd=None, min_bsa=None, ed=None, ad=None,
+                dd=None):
     """dock_pair's `models`: the centres of up to top_k clusters in cluster order, each written as <out_pdb stem>_<rank>.pdb.  sd: the
     screen's data (every model gains `sterics`, every file a REMARK line); bad: poses the clash filter removed - their key is NaN, so they
     come last, and a cluster one of them would lead is left out.  bd: the surface data (every model gains bsa, bsa_rec, bsa_lig); min_bsa:
     a centre that buries less is left out as well, and `bsa_dropped` counts those.  ed: the interface-energy data (every model gains
-    `interface_energy`); ad: the affinity data (every model gains `affinity`)."""
+    `interface_energy`); ad: the affinity data (every model gains `affinity`); dd: the distogram data (every model gains dist_nll,
+    dist_nll_near, exp_contacts)."""
     top_k, radius, rule = clu
     cl = cluster_trajectories(model, lig0, cols["rot_update"], cols["tr_update"], key, radius, rule, top_k)
     models, dropped = [], 0
@@ -1085,6 +1180,8 @@ def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=
             models[-1]["interface_energy"] = _pose_interface(ed, c)
         if ad is not None:
             models[-1]["affinity"] = _pose_affinity(ad, c)
+        if dd is not None:
+            models[-1].update(_pose_distogram(dd, c))
         if out_pdb:
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c], center=_center(model))
             pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa, remarks=_remarks(sd, c))

@@ -702,6 +702,45 @@ class Complex:
             o["relpos"] = ((c >> 20) & 127).astype(np.int8)
         return o
 
+    def distogram(self, lig_pos, t, edges=None, seed=0, mfma16=False, f16=False, maps=(), contact_bins=7, near_cutoff=None):
+        """The distogram head (family 1) of B poses reduced on the GPU - dfm_score_distogram, definition: dfmdock_amd/distogram.py.
+        lig_pos [B,L,3,3] (or [L,3,3]), t [B] (or scalar); mfma16 / f16 choose the engine of the forward as in `score`.
+        Returns {nll [B], nll_near [B], n_near [B] int32, exp_contacts [B]} and, for every name in `maps` out of "pair_nll",
+        "pcontact", "edist" ([B,R,L] each) and "pcontact_mean" ([R,L], mean over the B poses), that map.  near_cutoff None: the
+        model's cut_off.  The [B,R,L,64] logits are never materialised (score(dist=True) returns them)."""
+        lig_pos = _f32(lig_pos)
+        if lig_pos.ndim == 3:
+            lig_pos = lig_pos[None]
+        B = lig_pos.shape[0]
+        if lig_pos.shape[1:] != (self.L, 3, 3):
+            raise ValueError(f"lig_pos must be [B,{self.L},3,3]")
+        t = np.broadcast_to(_f32(t).reshape(-1), (B,)).copy()
+        maps = (maps,) if isinstance(maps, str) else tuple(maps)
+        known = ("pair_nll", "pcontact", "edist", "pcontact_mean")
+        for m in maps:
+            if m not in known:
+                raise ValueError(f"unknown map {m!r}: one of {known}")
+        N, K = self.N, self.K
+        o = dict(nll=np.zeros(B, np.float32), nll_near=np.zeros(B, np.float32), n_near=np.zeros(B, np.int32),
+                 exp_contacts=np.zeros(B, np.float32))
+        out = L.DistogramOutC()
+        out.nll, out.nll_near, out.n_near, out.exp_contacts = _p(o["nll"]), _p(o["nll_near"]), _p(o["n_near"], L.I32P), _p(o["exp_contacts"])
+        for m in maps:
+            o[m] = np.zeros((self.R, self.L) if m == "pcontact_mean" else (B, self.R, self.L), np.float32)
+            setattr(out, m, _p(o[m]))
+        e = None
+        if edges is not None:
+            e = np.ascontiguousarray(edges, dtype=np.int32)
+            if e.ndim == 2:
+                e = e[None]
+            if e.shape != (B, N, K):
+                raise ValueError(f"edges must be [B,N,K] = {(B, N, K)}, got {e.shape}")
+        par = L.DistogramParamsC(int(contact_bins), 0.0 if near_cutoff is None else float(near_cutoff))
+        flags = (L.DFM_F_MFMA16 if mfma16 else 0) | (L.DFM_F_F16 if f16 else 0)
+        rc = L.lib().dfm_score_distogram(self._h, B, _p(lig_pos), _p(t), _p(e, L.I32P), int(seed), flags, C.byref(par), C.byref(out))
+        L.check(rc, "dfm_score_distogram")
+        return o
+
     def sample(self, B=1, num_steps=40, eps=1e-3, tr_noise_scale=0.5, rot_noise_scale=0.5, noise_annealing=False,
                use_clash_force=False, ode=False, seed=0, mfma16=False, inject=None, trace=False, profile=False, f16=False, bf16_ops=False,
                bf16=False, l0_table=True, graph=False, step_energy=None, restraints=False):

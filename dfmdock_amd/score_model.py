@@ -202,19 +202,21 @@ class DFMDock(Score_Model):
 
     Output keys follow egnn_net.py:486-495: tr_score [1,3], rot_score [1,3], energy [], f [L,3], num_clashes [],
     confidence_logits [], ires_logits [N,1]; ``dist_logits`` [R,L,64] - a training-loss input (DFMDock.py:196-215) - with
-    ``with_dist=True`` (off by default: 64 floats per residue pair).  With a 67-channel checkpoint (configs/model/DFMDock.yaml:5) ``batch['is_homomer']`` selects the
+    ``with_dist=True`` (off by default: 64 floats per residue pair); ``with_distogram=True`` adds the head's reductions at the batch's own
+    pose instead - dist_nll, dist_nll_near, dist_n_near, exp_contacts (dfmdock_amd/distogram.py) - without the tensor.  With a 67-channel checkpoint (configs/model/DFMDock.yaml:5) ``batch['is_homomer']`` selects the
     value of the sym channel (default False).  The sampler of this family rotates about the all-backbone-atom centroids
     (src/inference.py:220-254); the engine does the same for ``family=1`` models.  The diffusers and the Euler-Maruyama sampler are shared with
     Score_Model, so ``Euler_Maruyama_sampler(model, batch)`` / ``sample_trajectories`` accept this class too.
     """
 
     def __init__(self, weights, hp: HParams | None = None, precision: str = "mfma16", device_index: int = 0, seed: int = 0,
-                 with_ires: bool = True, with_dist: bool = False):
+                 with_ires: bool = True, with_dist: bool = False, with_distogram: bool = False):
         hp = hp or HParams(family=1, mask_dist=20.0)
         if hp.family != 1:
             raise ValueError("DFMDock needs HParams(family=1)")
         super().__init__(weights, hp=hp, precision=precision, device_index=device_index, seed=seed, with_ires=with_ires)
         self.with_dist = bool(with_dist)      # dist_logits [R,L,64] (egnn_net.py:447,:500): 64 floats per residue pair, off by default
+        self.with_distogram = bool(with_distogram)      # the head reduced on the GPU (engine.Complex.distogram): four scalars per pose
 
     _ires_key = "ires_logits"       # egnn_net.py:486-495
 
@@ -224,6 +226,11 @@ class DFMDock(Score_Model):
         out["confidence_logits"] = torch.tensor(float(r["confidence"][0]), dtype=torch.float32)
         if self.with_dist:
             out["dist_logits"] = torch.from_numpy(r["dist_logits"][0].copy())
+        if self.with_distogram:      # a second evaluation on the graph draw of the first (same seed): the logits are never materialised
+            d = self.complex_for(batch).distogram(_np(batch["lig_pos"]), _np(batch["t"]).reshape(-1), seed=self.seed + self._calls,
+                                                  **{k: v for k, v in engine.precision_kwargs(self.precision).items() if k in ("mfma16", "f16")})
+            out.update(dist_nll=torch.tensor(float(d["nll"][0])), dist_nll_near=torch.tensor(float(d["nll_near"][0])),
+                       dist_n_near=torch.tensor(int(d["n_near"][0]), dtype=torch.int64), exp_contacts=torch.tensor(float(d["exp_contacts"][0])))
         return out
 
     __call__ = forward

@@ -621,6 +621,37 @@ int dfm_alloc_diag(int64_t out[6]);
 int dfm_score(dfm_complex *cx, int B, const float *lig_pos, const float *t, const int32_t *edges_or_null,
               uint64_t seed, uint32_t flags, dfm_score_out *out);
 
+/* The distogram head of the second family (EGNN_Net.to_dist, egnn_net.py:347-352,:447) reduced on the device: for every pose the
+ * 64-bin logits z of each receptor / ligand residue pair are turned, inside the pair kernel, into
+ *   pair_nll = -log_softmax(z)[bin(D)]      D: the pose's own CA-CA distance; bin(d) = #{k : d^2 > bounds[k]^2},
+ *                                           bounds = linspace(3.25, 50.75, 63) (utils/loss.py:65-93, distogram_loss)
+ *   pcontact = sum_{k < contact_bins} softmax(z)[k]        edist = sum_k softmax(z)[k] centre[k],  centre[k] = 3.25 + (k - 0.5) step
+ * and per pose nll = mean over the R L pairs (the reference's distogram_loss of the pose against its own prediction), nll_near / n_near
+ * = mean / count over pairs with D < near_cutoff (n_near = 0: NaN), exp_contacts = sum of pcontact.  pcontact_mean[R,L] is the mean of
+ * pcontact over the B poses, added in index order in double.  The logits are never stored (DFM_F_DIST returns them).  fp32 throughout in
+ * every engine; fixed-order reductions, no atomics: a pose's numbers do not depend on B, on its index or on which maps are asked for.
+ * The forward is dfm_score's (same arguments; flags: the engine flags DFM_F_MFMA16 / DFM_F_F16 / DFM_F_BF16_OPS only).
+ * DFM_E_INVALID, nothing enqueued: a NULL required pointer, B < 1, a family-0 model, contact_bins outside 1..63, any other flag. */
+typedef struct {
+    int32_t contact_bins;   /* bins 0 .. contact_bins - 1 count as contact: 7 <-> d <= 7.85 A */
+    float near_cutoff;      /* <= 0: the model's cut_off */
+} dfm_distogram_params;
+typedef struct {
+    float *nll;             /* [B]      required */
+    float *nll_near;        /* [B]      required */
+    int32_t *n_near;        /* [B]      required */
+    float *exp_contacts;    /* [B]      required */
+    float *pair_nll;        /* [B,R,L]  or NULL */
+    float *pcontact;        /* [B,R,L]  or NULL */
+    float *edist;           /* [B,R,L]  or NULL */
+    float *pcontact_mean;   /* [R,L]    or NULL */
+} dfm_distogram_out;
+int dfm_score_distogram(dfm_complex *cx, int B, const float *lig_pos, const float *t, const int32_t *edges_or_null,
+                        uint64_t seed, uint32_t flags, const dfm_distogram_params *params, dfm_distogram_out *out);
+/* GPU milliseconds of the calling thread's last dfm_score_distogram: the copies (poses and times up, results down) and everything
+ * between them (forward, to_dist.0 projection, k_pair_dist_sum, k_dist_finish, k_dist_mean) - tools/distogram_bench.py */
+int dfm_distogram_last_timing(double *copy_ms, double *kernel_ms);
+
 /* B independent trajectories of the Euler-Maruyama sampler */
 int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, float tr_noise_scale, float rot_noise_scale,
                uint32_t flags, uint64_t seed, const dfm_inject *inj_or_null, dfm_traj_out *out);
