@@ -51,6 +51,8 @@ EXPORTS = [
     "dfm_iface_last_timing",
     "dfm_rescon_create", "dfm_rescon_destroy", "dfm_rescon_info", "dfm_pose_rescon", "dfm_pose_rescon_chunked", "dfm_rescon_last_timing",
     "dfm_rescon_last_phases",
+    "dfm_hbond_create", "dfm_hbond_destroy", "dfm_hbond_info", "dfm_pose_hbonds", "dfm_pose_hbonds_chunked", "dfm_hbond_last_timing",
+    "dfm_hbond_last_phases",
     "dfm_score_distogram", "dfm_distogram_last_timing",
 ]
 
@@ -142,6 +144,10 @@ class IfaceOutC(C.Structure):
 
 class ResconOutC(C.Structure):
     _fields_ = [(n, I32P) for n in ("ic", "n_pairs", "n_rec_res", "n_lig_res", "rec_degree", "lig_degree")] + [("contact_bits", U32P)]
+
+
+class HbondOutC(C.Structure):
+    _fields_ = [(n, I32P) for n in ("n_hbond", "hb_kind", "n_salt", "n_salt_atoms", "rec_hb", "lig_hb", "rec_sb", "lig_sb")]
 
 
 class DistogramParamsC(C.Structure):
@@ -247,6 +253,17 @@ def lib():
     L.dfm_pose_rescon_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(ResconOutC)]
     L.dfm_rescon_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_rescon_last_phases.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    U8P = C.POINTER(C.c_uint8)
+    L.dfm_hbond_create.argtypes = [C.c_void_p, C.c_int, F32P, F32P, U8P, I32P, C.c_int, C.c_int, F32P, F32P, U8P, I32P, C.c_int, F32P,
+                                   C.c_float, C.c_double, C.c_float, C.POINTER(C.c_int)]
+    L.dfm_hbond_create.restype = C.c_void_p
+    L.dfm_hbond_destroy.argtypes = [C.c_void_p]
+    L.dfm_hbond_destroy.restype = None
+    L.dfm_hbond_info.argtypes = [C.c_void_p, I32P, I32P, F32P, I32P, I32P, I32P]
+    L.dfm_pose_hbonds.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.POINTER(HbondOutC)]
+    L.dfm_pose_hbonds_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(HbondOutC)]
+    L.dfm_hbond_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_hbond_last_phases.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_score_distogram.argtypes = [C.c_void_p, C.c_int, F32P, F32P, I32P, C.c_uint64, C.c_uint32, C.POINTER(DistogramParamsC),
                                       C.POINTER(DistogramOutC)]
     L.dfm_distogram_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]

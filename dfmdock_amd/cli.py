@@ -16,6 +16,7 @@
     python -m dfmdock_amd sweep ... --consensus [--consensus-top 0.5]
     python -m dfmdock_amd dock|refine ... --interface-energy [--rank interface] [--ie-weights 0.18 1.0 0.5] [--ie-cutoff 8.0] [--energy-residues FILE]
     python -m dfmdock_amd dock|refine ... --affinity [--affinity-cutoff 5.5] [--contact-residues FILE]
+    python -m dfmdock_amd dock|refine ... --hbonds [--bsa] [--hbond-cutoff 3.5] [--hbond-angle 90] [--salt-cutoff 4.0] [--hbond-residues FILE]
     python -m dfmdock_amd dock|refine ... --distogram [--rank distogram] [--distogram-map map.npz] [--distogram-restraints FILE] [--distogram-t 1e-3]
     python -m dfmdock_amd dock|refine ... --clash-screen [--clash-filter] [--clash-cutoff 3.0] [--contact-cutoff 5.0] [--clash-residues FILE]
 
@@ -78,6 +79,14 @@
              for the kept pose and for every --top-k model; `--contact-residues FILE` lists the kept model's residue pairs.  The
              coefficients, class tables and reference areas are starting values that are not verified or calibrated, the surface is this
              project's own Shrake-Rupley, and no agreement with the PRODIGY server is claimed.  Nothing is ranked by it.
+  hbonds     no reference counterpart: the interface hydrogen bonds and salt bridges of every trajectory on the GPU (dfmdock_amd/hbonds.py,
+             dfm_pose_hbonds).  The files carry no hydrogens, so the criteria are on heavy atoms only: a donor and an acceptor closer than
+             --hbond-cutoff (3.5 A) with both antecedent angles at least --hbond-angle (90 degrees); a cation and an anion closer than
+             --salt-cutoff (4.0 A), counted as residue pairs.  HIS is donor, acceptor and cation.  `dock / refine --hbonds` add n_hbond,
+             hb_bb_bb, hb_bb_sc, hb_sc_sc and n_salt for the kept pose and for every --top-k model, and with --bsa in the same run n_unsat:
+             the donors and acceptors the pose buries completely and leaves without a bond.  `--hbond-residues FILE` lists the kept
+             model's counts per residue of both chains (and <FILE stem>_<rank> those of every --top-k model).  No agreement with the
+             counts of PISA or HBPLUS is claimed.  Nothing is ranked or filtered by them.
   distogram  the model's own distogram head (second model family only: EGNN_Net.to_dist, 64 distance bins per residue pair) evaluated at
              every final pose and reduced on the GPU (dfmdock_amd/distogram.py, dfm_score_distogram).  `dock / refine --distogram` add
              dist_nll (the reference's distogram_loss of the pose's own CA-CA distances under the prediction made at that pose: lower =
@@ -173,6 +182,18 @@ def _add_affinity(p):
                    help="write the kept model's residue pairs in contact, one per line (implies --affinity)")
 
 
+def _add_hbonds(p):
+    p.add_argument("--hbonds", action="store_true",
+                   help="interface hydrogen bonds and salt bridges of every trajectory, heavy-atom criteria (adds n_hbond, hb_bb_bb, hb_bb_sc, "
+                        "hb_sc_sc, n_salt - with --bsa also n_unsat - to the result line and to every model)")
+    p.add_argument("--hbond-cutoff", type=float, default=None, metavar="A", help="with --hbonds: donor - acceptor distance (default 3.5, at most 8)")
+    p.add_argument("--hbond-angle", type=float, default=None, metavar="DEG",
+                   help="with --hbonds: smallest angle at the donor and at the acceptor, taken to their antecedents (default 90, in [90, 180))")
+    p.add_argument("--salt-cutoff", type=float, default=None, metavar="A", help="with --hbonds: cation - anion distance (default 4.0, at most 8)")
+    p.add_argument("--hbond-residues", default=None, metavar="FILE",
+                   help="write the kept model's hydrogen bonds and salt-bridge atom pairs per residue of both chains (implies --hbonds)")
+
+
 def _add_surface(p):
     p.add_argument("--bsa", action="store_true",
                    help="buried solvent-accessible surface area of every trajectory (adds bsa, bsa_rec, bsa_lig in A^2 to the result line and to every model)")
@@ -227,6 +248,7 @@ def build_parser():
     _add_surface(d)
     _add_interface(d)
     _add_affinity(d)
+    _add_hbonds(d)
     _add_common(d)
     r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)")
     r.add_argument("pdb_1", help="receptor PDB")
@@ -245,6 +267,7 @@ def build_parser():
     _add_surface(r)
     _add_interface(r)
     _add_affinity(r)
+    _add_hbonds(r)
     _add_common(r)
     s = sub.add_parser("sweep", help="sample every complex of a DB5-style directory (inference_mlsb.py run_sampling)")
     s.add_argument("--db5", required=True, help="directory of <id>.pt files (+ optional test.txt with the ids to run)")
@@ -345,6 +368,18 @@ def parse_args(argv=None):
         args.affinity_cutoff = 5.5 if args.affinity_cutoff is None else args.affinity_cutoff
         if not (np.isfinite(args.affinity_cutoff) and 0 < args.affinity_cutoff <= 16):
             ap.error("--affinity-cutoff must be in (0, 16]")
+    if args.cmd in ("dock", "refine"):
+        if args.hbond_residues:
+            args.hbonds = True
+        if not args.hbonds and (args.hbond_cutoff is not None or args.hbond_angle is not None or args.salt_cutoff is not None):
+            ap.error("--hbond-cutoff / --hbond-angle / --salt-cutoff describe --hbonds: they need it")
+        args.hbond_cutoff = 3.5 if args.hbond_cutoff is None else args.hbond_cutoff
+        args.hbond_angle = 90.0 if args.hbond_angle is None else args.hbond_angle
+        args.salt_cutoff = 4.0 if args.salt_cutoff is None else args.salt_cutoff
+        if not (np.isfinite(args.hbond_cutoff) and 0 < args.hbond_cutoff <= 8 and np.isfinite(args.salt_cutoff) and 0 < args.salt_cutoff <= 8):
+            ap.error("--hbond-cutoff and --salt-cutoff must be in (0, 8]")
+        if not (90.0 <= args.hbond_angle < 180.0):
+            ap.error("--hbond-angle must be in [90, 180)")
     if args.cmd in ("dock", "refine", "sweep"):
         if args.consensus_top is not None and not args.consensus:
             ap.error("--consensus-top selects the members of the consensus ensemble: it needs --consensus")
@@ -546,6 +581,39 @@ def affinity_outputs(args, model, res, rec, lig, line):
         line.update(contact_residues=os.path.abspath(args.contact_residues))
 
 
+def hbonds_kwargs(args):
+    """Driver keyword arguments of the hydrogen-bond flags of dock / refine: none without them."""
+    if not args.hbonds:
+        return {}
+    return dict(hbonds=True, hbond_cutoff=args.hbond_cutoff, hbond_angle=args.hbond_angle, salt_cutoff=args.salt_cutoff)
+
+
+def hbonds_outputs(args, model, res, rec, lig, line):
+    """The hydrogen-bond part of a dock / refine result: the counts of the line (the models carry theirs already), one note on stderr
+    when polar atoms could not be typed, and --hbond-residues."""
+    if not args.hbonds:
+        return
+    line.update({k: res[k] for k in ("n_hbond", "hb_bb_bb", "hb_bb_sc", "hb_sc_sc", "n_salt", "n_unsat") if k in res}, index=res["index"])
+    untyped = res["hbond_data"]["untyped"] if "hbond_data" in res else (0, 0)
+    if sum(untyped):
+        line.update(hbond_untyped=[int(v) for v in untyped])
+        print(f"hbonds: {untyped[0]} receptor and {untyped[1]} ligand polar atoms have no antecedent in the file and take no part",
+              file=sys.stderr, flush=True)
+    if args.hbond_residues:
+        from . import driver
+        from .hbonds import write_hbond_residues
+
+        def write(path, rot, tr):
+            keys, hb, sb = driver.residue_hbonds(model, rec, lig, rot, tr, args.hbond_cutoff, args.hbond_angle, args.salt_cutoff)
+            write_hbond_residues(path, keys[0], hb[0], sb[0], keys[1], hb[1], sb[1])
+        write(args.hbond_residues, res["rot_update"], res["tr_update"])
+        line.update(hbond_residues=os.path.abspath(args.hbond_residues))
+        stem, ext = os.path.splitext(args.hbond_residues)
+        for m in res.get("models", ()):      # every --top-k model: <stem>_<rank><ext>
+            t = res["hbond_data"]
+            write(f"{stem}_{m['rank']}{ext}", t["rot_update"][m["index"]], t["tr_update"][m["index"]])
+
+
 def surface_kwargs(args):
     """Driver keyword arguments of the surface flags of dock / refine: none without them."""
     if not args.bsa:
@@ -682,6 +750,7 @@ def cmd_dock(args):
     kw.update(surface_kwargs(args))
     kw.update(interface_kwargs(args))
     kw.update(affinity_kwargs(args))
+    kw.update(hbonds_kwargs(args))
     res = driver.dock_pair(model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
                            precision=args.precision, out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
                            on_selfcheck_fail=args.on_selfcheck_fail, **kw)
@@ -704,6 +773,7 @@ def cmd_dock(args):
     surface_outputs(args, model, res, rec, lig, line)
     interface_outputs(args, model, res, rec, lig, line)
     affinity_outputs(args, model, res, rec, lig, line)
+    hbonds_outputs(args, model, res, rec, lig, line)
     print(json.dumps(line), flush=True)
     if args.json:
         extra = {}
@@ -730,6 +800,7 @@ def cmd_refine(args):
     kw.update(surface_kwargs(args))
     kw.update(interface_kwargs(args))
     kw.update(affinity_kwargs(args))
+    kw.update(hbonds_kwargs(args))
     res = driver.refine_pair(model, rec, lig, rec_x, lig_x, t_begin=args.t_begin, num_samples=args.num_samples, num_steps=args.num_steps,
                              seed=args.seed, precision=args.precision, out_pdb=args.out, max_batch=args.max_batch,
                              selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, perturb=not args.no_perturb, **kw)
@@ -745,6 +816,7 @@ def cmd_refine(args):
     surface_outputs(args, model, res, rec, lig, line)
     interface_outputs(args, model, res, rec, lig, line)
     affinity_outputs(args, model, res, rec, lig, line)
+    hbonds_outputs(args, model, res, rec, lig, line)
     print(json.dumps(line), flush=True)
     if args.json:
         with open(args.json, "w") as f:

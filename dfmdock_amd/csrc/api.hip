@@ -947,7 +947,7 @@ extern "C" int dfm_restraint_eval(dfm_complex *cx, int B, const float *lig_pos, 
 // several host threads, and next to that model's complex handles, do not share any state.
 // the two millisecond figures of this thread's last call of each kind, behind the dfm_*_last_timing getters: k_pose_dist and the
 // clustering kernels for MS_CLUSTER, host-to-device copies and kernels for the others
-enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_IFACE, MS_RESCON, MS_KINDS };
+enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_IFACE, MS_RESCON, MS_HBOND, MS_KINDS };
 static thread_local double g_last_ms[MS_KINDS][2] = {};
 
 static void set_last_ms(int kind, double a, double b)
@@ -1023,7 +1023,7 @@ struct PoseCall {
     }
 };
 
-// the chunk loop of the rigid-pose calls (dfm_pose_sterics, dfm_pose_bsa, dfm_pose_iface_energy, dfm_pose_rescon): the chunk's (rot, tr) on the device, their transforms T, and
+// the chunk loop of the rigid-pose calls (dfm_pose_sterics, dfm_pose_bsa, dfm_pose_iface_energy, dfm_pose_rescon, dfm_pose_hbonds): the chunk's (rot, tr) on the device, their transforms T, and
 // the call's copy / kernel milliseconds from the call's own events.  Per chunk: upload, the caller's memsets and launches, kernels_done,
 // the caller's downloads, finish
 struct PoseChunks {
@@ -2195,6 +2195,208 @@ extern "C" int dfm_rescon_last_phases(double *zero_ms, double *walk_ms, double *
     *zero_ms = g_rescon_phase_ms[0];
     *walk_ms = g_rescon_phase_ms[1];
     *finish_ms = g_rescon_phase_ms[2];
+    return DFM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Hydrogen bonds and salt bridges (kernels_hbond.hip).  A dfm_hbond holds what the polar atoms of the two chains, their antecedents,
+// roles and residues, the scalars and the rotation centre fix - the receptor's grid of cells of the larger cutoff with each atom's
+// antecedent beside it, the ligand in blocks of 64 neighbours, each atom's role and charged-residue number in its float4 - and is
+// read-only after creation; every dfm_pose_hbonds call owns its stream, its bitmap and its other temporaries.
+struct dfm_hbond {
+    int device = 0, Nr = 0, Nl = 0, Rc = 0, Lc = 0, Wc = 0, n_cells = 0, max_cell_atoms = 0, default_chunk = 0;
+    float cell_edge = 0.f;
+    DevPool pool;      // unbound: released under a device-wide wait, like a model's
+    float *rec = nullptr, *rec_ante = nullptr, *lig = nullptr, *lig_ante = nullptr, *sphere = nullptr;
+    int32_t *cell_start = nullptr, *rec_index = nullptr, *lig_index = nullptr;
+    HbondConst sc = {};
+};
+
+// the memsets, k_hbond_pose + k_hbond, k_hbond_finish of this thread's last dfm_pose_hbonds, summed over its chunks
+static thread_local double g_hbond_phase_ms[3] = {};
+
+extern "C" void dfm_hbond_destroy(dfm_hbond *h)
+{
+    if (!h) return;
+    DeviceScope ds(h->device);
+    h->pool.release();
+    delete h;
+}
+
+extern "C" dfm_hbond *dfm_hbond_create(dfm_model *m, int Nr, const float *rec_xyz, const float *rec_ante, const uint8_t *rec_role,
+                                       const int32_t *rec_res, int n_rec_res, int Nl, const float *lig_xyz, const float *lig_ante,
+                                       const uint8_t *lig_role, const int32_t *lig_res, int n_lig_res, const float center[3], float hb_cutoff,
+                                       double min_cos2, float salt_cutoff, int *status)
+{
+    auto bad = [status](int code, const std::string &msg) -> dfm_hbond * {
+        (void)fail(code, msg);
+        if (status) *status = code;
+        return nullptr;
+    };
+    if (status) *status = DFM_OK;
+    if (!m) return bad(DFM_E_INVALID, "m is NULL");
+    if (const std::string msg = check_atom_sets(Nr, rec_xyz, Nl, lig_xyz, center); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_hbond_chain("rec", Nr, rec_ante, rec_role, rec_res, n_rec_res); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_hbond_chain("lig", Nl, lig_ante, lig_role, lig_res, n_lig_res); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_hbond_scalars(hb_cutoff, min_cos2, salt_cutoff); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    // the receptor's grid: origin = the bounding box's low corner, edge = the larger cutoff
+    const float reach = std::max(hb_cutoff, salt_cutoff);
+    CellGrid gr;
+    if (!build_cell_grid(Nr, rec_xyz, (double)reach, gr))
+        return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells of the larger cutoff");
+    double maxabs = 0.0;
+    for (int k = 0; k < 3; ++k) maxabs = std::max(maxabs, std::max(std::fabs(gr.lo[k]), std::fabs(gr.hi[k])));
+    maxabs += 2.0 * (double)reach + 1.0;
+    // the fp32 reject threshold (dfm_posewalk.h): reach * 1.0001 + slack
+    const float thr = reach * 1.0001f + pose_slack(maxabs);
+    HbondConst sc = {};
+    sc.g = walk_grid(gr, (double)reach, (double)thr, center);
+    sc.hb2 = (double)hb_cutoff * (double)hb_cutoff;
+    sc.salt2 = (double)salt_cutoff * (double)salt_cutoff;
+    sc.c2 = min_cos2;
+    sc.reject2 = thr * thr;
+    double llo[3] = {(double)lig_xyz[0], (double)lig_xyz[1], (double)lig_xyz[2]};
+    for (int i = 1; i < Nl; ++i)
+        for (int k = 0; k < 3; ++k) llo[k] = std::min(llo[k], (double)lig_xyz[(size_t)i * 3 + k]);
+    const LigandBlocks lb = build_ligand_blocks(Nl, lig_xyz, llo, sc.g.edge, sc.g.center);
+    if (!lb.finite) return bad(DFM_E_INVALID, "lig_xyz / center: the ligand's extent about the centre overflows fp32");
+    std::vector<int32_t> rcomp, lcomp;
+    const int Rc = hbond_charged_residues(Nr, rec_role, rec_res, n_rec_res, rcomp);
+    const int Lc = hbond_charged_residues(Nl, lig_role, lig_res, n_lig_res, lcomp);
+    const std::vector<float> rec4 = gather4_hbond(gr.order, rec_xyz, rec_role, rec_res, rcomp), ra4 = gather4(gr.order, rec_ante, nullptr);
+    const std::vector<float> lig4 = gather4_hbond(lb.index, lig_xyz, lig_role, lig_res, lcomp), la4 = gather4(lb.index, lig_ante, nullptr);
+    DeviceScope ds(m->device);
+    if (ds.err != hipSuccess) return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err));
+    dfm_hbond *h = new dfm_hbond;
+    h->device = m->device; h->Nr = Nr; h->Nl = Nl; h->Rc = Rc; h->Lc = Lc; h->Wc = rescon_words(Rc); h->sc = sc;
+    h->n_cells = sc.g.nx * sc.g.ny * sc.g.nz; h->max_cell_atoms = gr.max_cell; h->cell_edge = reach;
+    h->default_chunk = hbond_chunk_poses(Lc, Rc);
+    hipError_t e = hipSuccess;
+    {
+        PoseCall c;
+        e = c.open();
+        if (e == hipSuccess) e = h->pool.upload_async(&h->rec, rec4.data(), rec4.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->rec_ante, ra4.data(), ra4.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->cell_start, gr.start.data(), gr.start.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->rec_index, gr.order.data(), gr.order.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->lig, lig4.data(), lig4.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->lig_ante, la4.data(), la4.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->lig_index, lb.index.data(), lb.index.size(), c.s);
+        if (e == hipSuccess) e = h->pool.upload_async(&h->sphere, lb.sphere.data(), lb.sphere.size(), c.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
+    }      // the call's stream has drained: the host vectors it read may go
+    if (e != hipSuccess) {
+        h->pool.release();
+        delete h;
+        return bad(e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP, std::string("dfm_hbond_create: ") + hipGetErrorString(e));
+    }
+    return h;
+}
+
+extern "C" int dfm_hbond_info(const dfm_hbond *h, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge, int32_t *n_rec_charged,
+                              int32_t *n_lig_charged, int32_t *chunk_poses)
+{
+    if (!h) return fail(DFM_E_INVALID, "NULL argument");
+    if (n_cells) *n_cells = h->n_cells;
+    if (max_cell_atoms) *max_cell_atoms = h->max_cell_atoms;
+    if (cell_edge) *cell_edge = h->cell_edge;
+    if (n_rec_charged) *n_rec_charged = h->Rc;
+    if (n_lig_charged) *n_lig_charged = h->Lc;
+    if (chunk_poses) *chunk_poses = h->default_chunk;
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_hbonds_chunked(dfm_hbond *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_hbond_out *out)
+{
+    if (!h) return fail(DFM_E_INVALID, "h is NULL");
+    if (!rot) return fail(DFM_E_INVALID, "rot is NULL");
+    if (!tr) return fail(DFM_E_INVALID, "tr is NULL");
+    if (!out) return fail(DFM_E_INVALID, "out is NULL");
+    if (P < 1 || P > HBOND_MAX_POSES) return fail(DFM_E_INVALID, "need 1 <= P <= " + std::to_string(HBOND_MAX_POSES));
+    if (chunk_poses < 0) return fail(DFM_E_INVALID, "chunk_poses must be >= 0");
+    DEVICE_SCOPE(h->device);
+    PoseCall c;
+    HIPCHK(c.open());
+    // the call's chunk, else as many poses as fill RESCON_SCRATCH_BYTES of bitmap
+    const int Pc = std::min(P, chunk_poses > 0 ? std::min(chunk_poses, RESCON_MAX_CHUNK) : h->default_chunk);
+    const size_t Nr = (size_t)h->Nr, Nl = (size_t)h->Nl, words = (size_t)h->Lc * (size_t)h->Wc;
+    PoseChunks ch{c, rot, tr};
+    uint32_t *d_bits = nullptr;
+    int32_t *d_tot = nullptr;
+    // the per-atom outputs asked for, in one block so that one memset zeroes them: rec_hb, rec_sb [Pc][Nr], lig_hb, lig_sb [Pc][Nl]
+    int32_t *d_atom = nullptr, *d_rh = nullptr, *d_rs = nullptr, *d_lh = nullptr, *d_ls = nullptr;
+    const size_t n_atom = (size_t)Pc * ((out->rec_hb ? Nr : 0) + (out->rec_sb ? Nr : 0) + (out->lig_hb ? Nl : 0) + (out->lig_sb ? Nl : 0));
+    HIPCHK(ch.open(Pc));
+    HIPCHK(c.tmp.alloc(&d_bits, std::max<size_t>(1, (size_t)Pc * words)));      // never empty: the kernel forms a row pointer into it
+    HIPCHK(c.tmp.alloc(&d_tot, (size_t)Pc * 5));
+    if (n_atom) {
+        HIPCHK(c.tmp.alloc(&d_atom, n_atom));
+        int32_t *q = d_atom;
+        if (out->rec_hb) { d_rh = q; q += (size_t)Pc * Nr; }
+        if (out->rec_sb) { d_rs = q; q += (size_t)Pc * Nr; }
+        if (out->lig_hb) { d_lh = q; q += (size_t)Pc * Nl; }
+        if (out->lig_sb) { d_ls = q; q += (size_t)Pc * Nl; }
+    }
+    const HbondAtoms at = {h->rec, h->rec_ante, h->lig, h->lig_ante, h->sphere, h->cell_start, h->rec_index, h->lig_index, h->sc,
+                           h->Nr, h->Nl, h->Rc, h->Lc, h->Wc};
+    std::vector<int32_t> h_tot((size_t)Pc * 5);
+    // the call's own events split the kernel time into its three phases: ev[1] .. zeroed .. c.ev[3] (walked) .. ev[2]
+    struct Ev {
+        hipEvent_t e = nullptr;
+        ~Ev() { if (e) (void)hipEventDestroy(e); }
+    } zeroed;
+    HIPCHK(hipEventCreate(&zeroed.e));
+    double phase[3] = {0.0, 0.0, 0.0};
+    for (int p0 = 0; p0 < P; p0 += Pc) {
+        const int n = std::min(Pc, P - p0);
+        HIPCHK(ch.upload(p0, n));
+        if (words) HIPCHK(hipMemsetAsync(d_bits, 0, (size_t)n * words * sizeof(uint32_t), c.s));
+        if (n_atom) HIPCHK(hipMemsetAsync(d_atom, 0, n_atom * sizeof(int32_t), c.s));
+        HIPCHK(hipEventRecord(zeroed.e, c.s));
+        HIPCHK(launch_hbond_pose(ch.d_rot, ch.d_tr, n, ch.T, d_tot, c.s));
+        HIPCHK(launch_hbond(at, ch.T, n, d_tot, d_bits, d_rh, d_rs, d_lh, d_ls, c.s));
+        HIPCHK(hipEventRecord(c.ev[3], c.s));
+        HIPCHK(launch_hbond_finish(at, d_bits, n, d_tot, c.s));
+        HIPCHK(ch.kernels_done());
+        HIPCHK(hipMemcpyAsync(h_tot.data(), d_tot, (size_t)n * 5 * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        if (d_rh) HIPCHK(hipMemcpyAsync(out->rec_hb + (size_t)p0 * Nr, d_rh, (size_t)n * Nr * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        if (d_rs) HIPCHK(hipMemcpyAsync(out->rec_sb + (size_t)p0 * Nr, d_rs, (size_t)n * Nr * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        if (d_lh) HIPCHK(hipMemcpyAsync(out->lig_hb + (size_t)p0 * Nl, d_lh, (size_t)n * Nl * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        if (d_ls) HIPCHK(hipMemcpyAsync(out->lig_sb + (size_t)p0 * Nl, d_ls, (size_t)n * Nl * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(ch.finish());
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, c.ev[1], zeroed.e) == hipSuccess) phase[0] += ms;
+        if (hipEventElapsedTime(&ms, zeroed.e, c.ev[3]) == hipSuccess) phase[1] += ms;
+        if (hipEventElapsedTime(&ms, c.ev[3], c.ev[2]) == hipSuccess) phase[2] += ms;
+        for (int p = 0; p < n; ++p) {
+            const int32_t *t = h_tot.data() + (size_t)p * 5;
+            if (out->n_hbond) out->n_hbond[p0 + p] = (t[0] + t[1]) + t[2];
+            if (out->hb_kind) std::memcpy(out->hb_kind + (size_t)(p0 + p) * 3, t, 3 * sizeof(int32_t));
+            if (out->n_salt_atoms) out->n_salt_atoms[p0 + p] = t[3];
+            if (out->n_salt) out->n_salt[p0 + p] = t[4];
+        }
+    }
+    set_last_ms(MS_HBOND, ch.copy_ms, ch.kernel_ms);
+    for (int k = 0; k < 3; ++k) g_hbond_phase_ms[k] = phase[k];
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_hbonds(dfm_hbond *h, int P, const float *rot, const float *tr, dfm_hbond_out *out)
+{
+    return dfm_pose_hbonds_chunked(h, P, rot, tr, 0, out);
+}
+
+extern "C" int dfm_hbond_last_timing(double *copy_ms, double *kernel_ms)
+{
+    return last_timing(MS_HBOND, copy_ms, kernel_ms);
+}
+
+extern "C" int dfm_hbond_last_phases(double *zero_ms, double *walk_ms, double *finish_ms)
+{
+    if (!zero_ms || !walk_ms || !finish_ms) return fail(DFM_E_INVALID, "NULL argument");
+    *zero_ms = g_hbond_phase_ms[0];
+    *walk_ms = g_hbond_phase_ms[1];
+    *finish_ms = g_hbond_phase_ms[2];
     return DFM_OK;
 }
 

@@ -532,6 +532,36 @@ hipError_t launch_rescon(const ResconAtoms &at, const double *T, int n, uint32_t
 hipError_t launch_rescon_finish(const ResconAtoms &at, const uint32_t *bits, int n, int32_t *tot, int32_t *rec_degree, int32_t *lig_degree,
                                 hipStream_t s);
 
+// hydrogen bonds and salt bridges (kernels_hbond.hip; include/dfmdock_amd.h: dfm_hbond_create / dfm_pose_hbonds).  What the atoms and the
+// scalars fix: the receptor's grid of cells of max(hb_cutoff, salt_cutoff), hb2 / salt2 = the cutoffs squared and c2 = min_cos2 as the
+// definition's doubles, and the fp32 reject threshold squared at the larger cutoff (g.grow is that threshold as a double, as in
+// StericsConst).
+struct HbondConst {
+    WalkGrid g;
+    double hb2, salt2, c2;
+    float reject2;
+};
+// device arrays of a dfm_hbond over the POLAR atoms of the two chains: rec / lig / sphere / cell_start as in StericsAtoms, except that the
+// fourth component of every rec / lig float4 holds the atom's bits (dfm_walkgrid.h: role | compact charged-residue index << 8); rec_ante
+// [Nr] / lig_ante [Nl] float4 = the antecedent of the atom at the same place of rec / lig (w unused); rec_index [Nr] / lig_index [Nl] =
+// each sorted atom's index in the caller's order.  Rc / Lc charged residues, Wc = ceil(Rc / 32) words per bitmap row
+struct HbondAtoms {
+    const float *rec, *rec_ante, *lig, *lig_ante, *sphere;
+    const int32_t *cell_start, *rec_index, *lig_index;
+    HbondConst sc;
+    int Nr, Nl, Rc, Lc, Wc;
+};
+// T [n][12]: R(rot) row-major and tr as doubles; also zeroes tot [n][5] = (bonds with 0, 1, 2 side-chain atoms, salt-bridge atom pairs,
+// salt bridges) of the n poses
+hipError_t launch_hbond_pose(const float *rot, const float *tr, int n, double *T, int32_t *tot, hipStream_t s);
+// n <= 65535 poses.  tot [n][5]: entries 0 .. 3 are added to.  bits [n][Lc][Wc]: zero it first.  rec_hb / rec_sb [n][Nr], lig_hb / lig_sb
+// [n][Nl] (the caller's atom order) or nullptr: zero them first (the receptor's are added to, the ligand's written by the waves that
+// reach the cell walk only)
+hipError_t launch_hbond(const HbondAtoms &at, const double *T, int n, int32_t *tot, uint32_t *bits, int32_t *rec_hb, int32_t *rec_sb,
+                        int32_t *lig_hb, int32_t *lig_sb, hipStream_t s);
+// tot [n][5]: entry 4 = the set bits of the pose's bitmap
+hipError_t launch_hbond_finish(const HbondAtoms &at, const uint32_t *bits, int n, int32_t *tot, hipStream_t s);
+
 // isolated exposure of one chain on the host, as the definition takes it (kernels_surface.hip)
 void surface_exposure(int n, const float *xyz, const float *radius, double probe, int K, const float *dirs, const double lo[3],
                       const int dims[3], double edge, double pad, const int32_t *start, const int32_t *order, uint64_t *mask);

@@ -1,8 +1,8 @@
 // dfm_poseprep.h - host preparation of the per-pose all-atom calls (api.hip: dfm_atoms_create, dfm_surface_create, dfm_iface_create,
-// dfm_rescon_create): argument checks, the cell grid of a chain, the ligand in blocks of 64 neighbours, the rounding slack, the interface
-// energy's parameter limits and overflow bound, the residue contacts' limits, residue bits, class masks and chunk size.  Plain C++ without
-// a HIP call, so that tests/test_pose_prep_cpu.py, tests/test_ifenergy_cpu.py and tests/test_affinity_cpu.py run it under the
-// sanitizers without a GPU.
+// dfm_rescon_create, dfm_hbond_create): argument checks, the cell grid of a chain, the ligand in blocks of 64 neighbours, the rounding
+// slack, the interface energy's parameter limits and overflow bound, the residue contacts' limits, residue bits, class masks and chunk
+// size, the hydrogen bonds' limits, role bits and charged residues.  Plain C++ without a HIP call, so that tests/test_pose_prep_cpu.py,
+// tests/test_ifenergy_cpu.py, tests/test_affinity_cpu.py and tests/test_hbonds_cpu.py run it under the sanitizers without a GPU.
 #pragma once
 
 #include <algorithm>
@@ -303,5 +303,69 @@ inline int rescon_chunk_poses(int Lr, int Rr, size_t budget = RESCON_SCRATCH_BYT
     const size_t per_pose = (size_t)Lr * (size_t)rescon_words(Rr) * sizeof(uint32_t);
     return (int)std::min<size_t>((size_t)RESCON_MAX_CHUNK, std::max<size_t>(1, budget / per_pose));
 }
+
+// Hydrogen bonds and salt bridges (api.hip: dfm_hbond_create; kernels_hbond.hip).  The atoms of a chain are its POLAR atoms only.  The
+// limits: residues per chain, poses per call, the largest cutoff (the role bits: dfm_walkgrid.h).
+constexpr int HBOND_MAX_RES = RESCON_MAX_RES, HBOND_MAX_POSES = RESCON_MAX_POSES;
+constexpr float HBOND_MAX_CUTOFF = 8.f;
+
+// the antecedent [n][3], role [n] and residue index [n] of every polar atom of one chain (`who`: "rec" or "lig"): the message of the
+// first thing that is wrong, or ""
+inline std::string check_hbond_chain(const char *who, int n, const float *ante, const uint8_t *role, const int32_t *res, int n_res)
+{
+    const std::string w(who);
+    if (!ante) return w + "_ante is NULL";
+    if (!role) return w + "_role is NULL";
+    if (!res) return w + "_res is NULL";
+    if (n_res < 1 || n_res > HBOND_MAX_RES) return w + ": need 1 <= residues <= " + std::to_string(HBOND_MAX_RES);
+    for (size_t i = 0; i < (size_t)n * 3; ++i)
+        if (!std::isfinite(ante[i])) return w + "_ante: atom " + std::to_string(i / 3) + " is not finite";
+    for (int i = 0; i < n; ++i) {
+        if (role[i] & ~HB_ROLE_MASK) return w + "_role: atom " + std::to_string(i) + " has role " + std::to_string((int)role[i]) + " outside the five bits";
+        if (res[i] < 0 || res[i] >= n_res)
+            return w + "_res: atom " + std::to_string(i) + " has residue " + std::to_string(res[i]) + " outside [0, " + std::to_string(n_res) + ")";
+    }
+    return "";
+}
+inline std::string check_hbond_scalars(float hb_cutoff, double min_cos2, float salt_cutoff)
+{
+    if (!(std::isfinite(hb_cutoff) && hb_cutoff > 0.f && hb_cutoff <= HBOND_MAX_CUTOFF)) return "hb_cutoff must be in (0, 8]";
+    if (!(std::isfinite(salt_cutoff) && salt_cutoff > 0.f && salt_cutoff <= HBOND_MAX_CUTOFF)) return "salt_cutoff must be in (0, 8]";
+    if (!(min_cos2 >= 0.0 && min_cos2 < 1.0)) return "min_cos2 must be in [0, 1): the squared cosine of an angle in [90, 180)";
+    return "";
+}
+
+// the charged residues of one chain - those with at least one CATION or ANION atom - numbered in residue order: compact [n_res] = that
+// number or -1; returns how many there are (0 is legal)
+inline int hbond_charged_residues(int n, const uint8_t *role, const int32_t *res, int n_res, std::vector<int32_t> &compact)
+{
+    compact.assign((size_t)n_res, -1);
+    for (int i = 0; i < n; ++i)
+        if (role[i] & (HB_CATION | HB_ANION)) compact[(size_t)res[i]] = 0;
+    int count = 0;
+    for (int r = 0; r < n_res; ++r)
+        if (compact[(size_t)r] == 0) compact[(size_t)r] = count++;
+    return count;
+}
+
+// atoms as k_hbond reads them: (x, y, z, the BITS role | compact charged-residue index << 8) of atom order[q] at q; an atom that is
+// neither cation nor anion carries index 0, which is never read
+inline std::vector<float> gather4_hbond(const std::vector<int32_t> &order, const float *xyz, const uint8_t *role, const int32_t *res,
+                                        const std::vector<int32_t> &compact)
+{
+    std::vector<float> v(order.size() * 4, 0.f);
+    for (size_t q = 0; q < order.size(); ++q) {
+        const int32_t a = order[q];
+        for (int k = 0; k < 3; ++k) v[q * 4 + k] = xyz[(size_t)a * 3 + k];
+        const bool charged = (role[a] & (HB_CATION | HB_ANION)) != 0;
+        const uint32_t b = (uint32_t)role[a] | (charged ? (uint32_t)compact[(size_t)res[a]] << HB_RES_SHIFT : 0u);
+        std::memcpy(&v[q * 4 + 3], &b, sizeof(b));
+    }
+    return v;
+}
+
+// poses of one chunk of a call: the bitmap of a pose is [Lc][ceil(Rc / 32)] words over the CHARGED residues of the two chains; a chain
+// without one leaves a bitmap of one word that nothing reads
+inline int hbond_chunk_poses(int Lc, int Rc, size_t budget = RESCON_SCRATCH_BYTES) { return rescon_chunk_poses(std::max(Lc, 1), std::max(Rc, 1), budget); }
 
 }  // namespace dfm

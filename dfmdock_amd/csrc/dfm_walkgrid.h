@@ -1,5 +1,6 @@
 // dfm_walkgrid.h - the receptor's cell grid of the per-pose all-atom calls and its binning formula, in plain C++: the host builds the
-// grid with them (dfm_poseprep.h), the kernels walk it (dfm_posewalk.h).
+// grid with them (dfm_poseprep.h), the kernels walk it (dfm_posewalk.h).  Also the bits a polar atom of the hydrogen-bond call carries
+// in its float4, which the host packs and kernels_hbond.hip reads.
 #pragma once
 
 #include <math.h>
@@ -29,5 +30,10 @@ DFM_HOST_DEVICE inline int cell_of(double x, double origin, double edge, int n)
     c = c < 0.0 ? 0.0 : (c > (double)(n - 1) ? (double)(n - 1) : c);
     return (int)c;
 }
+
+// hydrogen bonds and salt bridges: the role bits of dfmdock_amd/hbonds.py; an atom's bits are role | compact charged-residue index <<
+// HB_RES_SHIFT
+constexpr uint32_t HB_DONOR = 1, HB_ACCEPTOR = 2, HB_CATION = 4, HB_ANION = 8, HB_SIDECHAIN = 16, HB_ROLE_MASK = 31;
+constexpr int HB_RES_SHIFT = 8;
 
 }  // namespace dfm

@@ -330,6 +330,80 @@ def _affinity_result(ad, k):
     return {"affinity": _pose_affinity(ad, k), "affinity_data": ad, "index": int(k)}
 
 
+def hbond_inputs(rec, lig, family):
+    """What the hydrogen-bond call takes from two pdbio.backbone_from_atoms dicts: the polar atoms of both chains (hbonds.polar_atoms over
+    sterics.heavy_atoms: coordinates, antecedents, roles, residues) and the centre of sterics_inputs.  Returns (rec_polar, lig_polar,
+    center)."""
+    from . import hbonds as HB
+    return HB.polar_atoms(rec["atoms"]), HB.polar_atoms(lig["atoms"]), sterics_inputs(rec, lig, family)[2]
+
+
+def ensemble_hbonds(model: engine.Model, rec, lig, rot_update, tr_update, hb_cutoff=3.5, min_angle=90.0, salt_cutoff=4.0, per_atom=False):
+    """Interface hydrogen bonds and salt bridges of trajectories on the GPU (dfm_pose_hbonds) from their final (rot_update, tr_update)
+    alone: heavy-atom criteria over the polar atoms of the two parsed PDB chains (hbonds.py; HIS is donor, acceptor and cation; no
+    agreement with any published tool is claimed).  Returns the dict of HBonds.count plus hb_cutoff, min_angle, salt_cutoff, rec_polar /
+    lig_polar (the polar_atoms dicts the per-atom arrays are in the order of) and untyped: the polar atoms of (receptor, ligand) whose
+    antecedent is missing from the file and that therefore take no part."""
+    rp, lp, cen = hbond_inputs(rec, lig, model.hp.family)
+    with model.hbonds(rp, lp, cen, hb_cutoff, min_angle, salt_cutoff) as h:
+        out = h.count(np.asarray(rot_update, np.float32).reshape(-1, 3), np.asarray(tr_update, np.float32).reshape(-1, 3), per_atom=per_atom)
+        out.update(hb_cutoff=h.hb_cutoff, min_angle=h.min_angle, salt_cutoff=h.salt_cutoff, rec_polar=rp, lig_polar=lp,
+                   untyped=(int(rp["untyped"]), int(lp["untyped"])))
+    return out
+
+
+def unsatisfied_polar(hd, bd, percent=100):
+    """n_unsat [P] int32: the donors and acceptors of both chains that each pose buries completely (`percent` of the points exposed in
+    isolation) and leaves without a hydrogen bond (hbonds.unsatisfied).  hd: ensemble_hbonds(per_atom=True); bd:
+    ensemble_surface(per_atom=True) of the same poses."""
+    from . import hbonds as HB
+    n = 0
+    for side in ("rec", "lig"):
+        pa = hd[side + "_polar"]
+        n = n + HB.unsatisfied(pa["role"], bd[side + "_exposed"][pa["index"]], bd[side + "_buried"][:, pa["index"]], hd[side + "_hb"],
+                               percent)["n_unsat"]
+    return n
+
+
+def residue_hbonds(model: engine.Model, rec, lig, rot, tr, hb_cutoff=3.5, min_angle=90.0, salt_cutoff=4.0):
+    """Per residue of ONE pose: ((receptor keys, ligand keys), (receptor bonds, ligand bonds), (receptor salt-bridge atom pairs,
+    ligand ...)) - the per-atom counts summed over each residue's polar atoms (hbonds.residue_bonds)."""
+    from . import hbonds as HB
+    hd = ensemble_hbonds(model, rec, lig, np.asarray(rot).reshape(1, 3), np.asarray(tr).reshape(1, 3), hb_cutoff, min_angle, salt_cutoff,
+                         per_atom=True)
+    keys, hb, sb = [], [], []
+    for side in ("rec", "lig"):
+        pa = hd[side + "_polar"]
+        keys.append(pa["keys"])
+        hb.append(HB.residue_bonds(hd[side + "_hb"][0], pa["res"], pa["n_res"]))
+        sb.append(HB.residue_bonds(hd[side + "_sb"][0], pa["res"], pa["n_res"]))
+    return keys, hb, sb
+
+
+def _check_hbonds(hbonds, hbond_cutoff, hbond_angle, salt_cutoff):
+    """None (off) or (hb_cutoff, min_angle, salt_cutoff) of a pair driver's hydrogen-bond options."""
+    if not hbonds:
+        return None
+    from . import hbonds as HB
+    HB.min_cos2(hbond_angle)
+    return HB.check_cutoffs(hbond_cutoff, salt_cutoff)[0], float(hbond_angle), HB.check_cutoffs(hbond_cutoff, salt_cutoff)[1]
+
+
+def _pose_hbonds(hd, k):
+    out = {"n_hbond": int(hd["n_hbond"][k]), "hb_bb_bb": int(hd["hb_kind"][k, 0]), "hb_bb_sc": int(hd["hb_kind"][k, 1]),
+           "hb_sc_sc": int(hd["hb_kind"][k, 2]), "n_salt": int(hd["n_salt"][k])}
+    if "n_unsat" in hd:
+        out["n_unsat"] = int(hd["n_unsat"][k])
+    return out
+
+
+def _hbonds_result(hd, k):
+    """The hydrogen-bond entries of a pair driver's result for the kept pose k: none without the option."""
+    if hd is None:
+        return {}
+    return dict(_pose_hbonds(hd, k), hbond_data=hd, index=int(k))
+
+
 def _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff):
     """None (off) or (filter, clash cutoff, contact cutoff) of a pair driver's screen options."""
     if not (clash_screen or clash_filter):
@@ -886,12 +960,12 @@ def _center(model):
 
 
 def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native=None, cons=None, ster=None, clu=None, refine=None,
-            surf=None, ie=None, aff=None, dg=None, seed=0):
+            surf=None, ie=None, aff=None, dg=None, seed=0, hb=None):
     """What every pair driver does with its sampled trajectories: the kept pose, its files and the result.  cols: every trajectory's
     energy, rot_update, tr_update (and the driver's own columns).  pick = (rule, *column names): the driver's own choice, rule(*columns) ->
     index; key: the clustering key that goes with it.  entries(k): the driver's own result entries for the kept pose k.  cons / ster / clu:
     None or the options of _with_consensus / _screen / _top_models; surf: None or the options of _check_surface; ie: None or the options of
-    _check_interface; aff: None or the options of _check_affinity; refine: None or the keyword arguments of refine_models - only then
+    _check_interface; aff: None or the options of _check_affinity; hb: None or the options of _check_hbonds; refine: None or the keyword arguments of refine_models - only then
     does the handle outlive the sampling."""
     lig0 = gx.lig_pos0
     if refine is None and dg is None:      # the columns are host arrays: the handle (and its ~GB of device workspace) goes before any post-processing
@@ -913,22 +987,30 @@ def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_p
     extra.update(_sterics_result(sd, k))
     # one surface call serves both when the surface options are the ones the affinity estimate takes (probe 1.4 A, 128 points)
     shared = surf is not None and aff is not None and (surf[1], surf[2]) == _check_surface(True, None, *AFFINITY_SURFACE)[1:]
-    bd = None if surf is None else ensemble_surface(model, rec, lig, cols["rot_update"], cols["tr_update"], surf[1], surf[2], per_atom=shared)
+    bd = None if surf is None else ensemble_surface(model, rec, lig, cols["rot_update"], cols["tr_update"], surf[1], surf[2],
+                                                    per_atom=shared or hb is not None)
     extra.update(_surface_result(bd, k, surf))
     ad = None if aff is None else pose_affinity(model, rec, lig, cols["rot_update"], cols["tr_update"], aff[0], *AFFINITY_SURFACE,
                                                 surface=bd if shared else None)
     extra.update(_affinity_result(ad, k))
+    # reported, never ranked by; with the surface in the same run also the buried donors and acceptors without a bond
+    hd = None if hb is None else ensemble_hbonds(model, rec, lig, cols["rot_update"], cols["tr_update"], *hb, per_atom=bd is not None)
+    if hd is not None:
+        hd.update(rot_update=cols["rot_update"], tr_update=cols["tr_update"])      # the poses the arrays are of
+        if bd is not None:
+            hd["n_unsat"] = unsatisfied_polar(hd, bd)
+    extra.update(_hbonds_result(hd, k))
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k], center=_center(model))
     if out_pdb:
         pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa, remarks=_remarks(sd, k))
     res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, **entries(k)}
     res.update(extra)
-    if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None or dg is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
+    if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None or dg is not None or hb is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
         res.setdefault("trajectories", {c: cols[c] for c in ("energy", "rot_update", "tr_update")})
     _selected_metrics(model, native, rec, lig0, res)
     if clu is not None:
-        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad, bd, None if surf is None else surf[0], ed, ad, dd))
+        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad, bd, None if surf is None else surf[0], ed, ad, dd, hd))
         if refine is not None:
             refine_models(model, gx, rec, lig, lig0, cols, res["models"], precision=precision, out_pdb=out_pdb, native=native, **refine)
             gx.close()
@@ -941,7 +1023,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
               refine_samples=8, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
               clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, bsa=False, min_bsa=None, probe=1.4, sphere_points=128,
               interface_energy=False, ie_weights=None, ie_cutoff=8.0, affinity=False, affinity_cutoff=5.5, distogram=False,
-              distogram_t=DISTOGRAM_T, distogram_maps=False, **sampler_kw):
+              distogram_t=DISTOGRAM_T, distogram_maps=False, hbonds=False, hbond_cutoff=3.5, hbond_angle=90.0, salt_cutoff=4.0, **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
     pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
     the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
@@ -1005,7 +1087,14 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     (the arrays; with `distogram_maps` also pcontact_mean [R,L] and edist [P,R,L]), `index` and `trajectories`; every model of `top_k`
     gains dist_nll, dist_nll_near and exp_contacts.  rank="distogram" (implies distogram) keeps the pose with the lowest nll instead
     (ties: lower index; it overrides restraint_rank) and makes the nll values the clustering key of `top_k`; poses `clash_filter` removed
-    get a NaN key as under rank "consensus"."""
+    get a NaN key as under rank "consensus".
+
+    `hbonds`: the interface hydrogen bonds and salt bridges of every trajectory (ensemble_hbonds: heavy-atom criteria - a distance below
+    `hbond_cutoff` A and both antecedent angles at least `hbond_angle` degrees; cation / anion pairs below `salt_cutoff` A; HIS is donor,
+    acceptor and cation; no agreement with any published tool is claimed).  The result gains n_hbond, hb_bb_bb, hb_bb_sc, hb_sc_sc, n_salt
+    of the kept pose, `hbond_data` (the arrays), `index` and `trajectories`; with `bsa` in the same run also n_unsat, the donors and
+    acceptors the pose buries completely and leaves without a bond; every model of `top_k` gains the same numbers.  Nothing is ranked or
+    filtered by them."""
     _check_rank(rank, consensus_top)
     dg = _check_distogram(model, distogram, rank, distogram_t, distogram_maps, max_batch)
     cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
@@ -1013,6 +1102,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     surf = _check_surface(bsa, min_bsa, probe, sphere_points)
     ie = _check_interface(interface_energy, rank, ie_weights, ie_cutoff)
     aff = _check_affinity(affinity, affinity_cutoff)
+    hb = _check_hbonds(hbonds, hbond_cutoff, hbond_angle, salt_cutoff)
     if native is not None:
         _check_native(native, rec, lig)
     if refine_t is not None and top_k is None:
@@ -1054,6 +1144,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     if not restrained:
         # the loop's own minimum; consensus and the screen choose among all trajectories at once (the first minimum: the same pose)
         pick = (np.argmin if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None or dg is not None
+                or hb is not None
                 else (lambda energy: k0), "energy")
         key, entries = cols["energy"], lambda k: {}
     else:
@@ -1065,7 +1156,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         entries = lambda k: {"index": k, "restraints": len(restraints), "restraint_rank": restraint_rank,
                              "restraint_energy": float(cols["restraint_energy"][k]), "restraints_satisfied": int(cols["restraints_satisfied"][k]),
                              "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
-    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine, surf, ie, aff, dg, seed)
+    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine, surf, ie, aff, dg, seed, hb)
 
 
 def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
@@ -1073,7 +1164,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
                 restraint_params=None, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
                 clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, start_shift=None, bsa=False, min_bsa=None, probe=1.4,
                 sphere_points=128, interface_energy=False, ie_weights=None, ie_cutoff=8.0, affinity=False, affinity_cutoff=5.5, distogram=False,
-                distogram_t=DISTOGRAM_T, distogram_maps=False, **sampler_kw):
+                distogram_t=DISTOGRAM_T, distogram_maps=False, hbonds=False, hbond_cutoff=3.5, hbond_angle=90.0, salt_cutoff=4.0, **sampler_kw):
     """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories
     start from that pose noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps
     down from t_begin; like dock_pair the minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns
@@ -1085,6 +1176,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
     `interface_energy` / `ie_weights` / `ie_cutoff` and rank="interface": as for dock_pair.
     `affinity` / `affinity_cutoff`: as for dock_pair.
     `distogram` / `distogram_t` / `distogram_maps` and rank="distogram": as for dock_pair.
+    `hbonds` / `hbond_cutoff` / `hbond_angle` / `salt_cutoff`: as for dock_pair.
     `start_shift` ([num_samples,3]): trajectory i starts from the input pose translated by start_shift[i] (the engine's start_pos); the
     shift is added to its tr_update, so (rot_update, tr_update) keep mapping the INPUT pose onto the final one."""
     _check_rank(rank, consensus_top)
@@ -1094,6 +1186,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
     surf = _check_surface(bsa, min_bsa, probe, sphere_points)
     ie = _check_interface(interface_energy, rank, ie_weights, ie_cutoff)
     aff = _check_affinity(affinity, affinity_cutoff)
+    hb = _check_hbonds(hbonds, hbond_cutoff, hbond_angle, salt_cutoff)
     if native is not None:
         _check_native(native, rec, lig)
     if start_shift is not None:
@@ -1120,7 +1213,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
         done += b
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
     res = _finish(model, gx, rec, lig, cols, (np.argmin, "energy"), None,      # the first minimum wins, as in dock_pair
-                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster, surf=surf, ie=ie, aff=aff, dg=dg, seed=seed)
+                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster, surf=surf, ie=ie, aff=aff, dg=dg, seed=seed, hb=hb)
     if native is not None:
         res["start_metrics"] = native_metrics(model, native, rec["bb_coords"], gx.lig_pos0[None])[0]
     return res
@@ -1153,13 +1246,14 @@ def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps
 
 
 def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=None, bad=None, bd=None, min_bsa=None, ed=None, ad=None,
-                dd=None):
+                dd=None, hd=None):
     """dock_pair's `models`: the centres of up to top_k clusters in cluster order, each written as <out_pdb stem>_<rank>.pdb.  sd: the
     screen's data (every model gains `sterics`, every file a REMARK line); bad: poses the clash filter removed - their key is NaN, so they
     come last, and a cluster one of them would lead is left out.  bd: the surface data (every model gains bsa, bsa_rec, bsa_lig); min_bsa:
     a centre that buries less is left out as well, and `bsa_dropped` counts those.  ed: the interface-energy data (every model gains
     `interface_energy`); ad: the affinity data (every model gains `affinity`); dd: the distogram data (every model gains dist_nll,
-    dist_nll_near, exp_contacts)."""
+    dist_nll_near, exp_contacts); hd: the hydrogen-bond data (every model gains n_hbond, hb_bb_bb, hb_bb_sc, hb_sc_sc, n_salt and, with the
+    surface, n_unsat)."""
     top_k, radius, rule = clu
     cl = cluster_trajectories(model, lig0, cols["rot_update"], cols["tr_update"], key, radius, rule, top_k)
     models, dropped = [], 0
@@ -1182,6 +1276,8 @@ def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=
             models[-1]["affinity"] = _pose_affinity(ad, c)
         if dd is not None:
             models[-1].update(_pose_distogram(dd, c))
+        if hd is not None:
+            models[-1].update(_pose_hbonds(hd, c))
         if out_pdb:
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c], center=_center(model))
             pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa, remarks=_remarks(sd, c))

@@ -238,9 +238,16 @@ class Model:
         residue pairs with two heavy atoms closer than `cutoff` A.  Returns a Contacts whose `.count(rot, tr)` takes P poses in one call."""
         return Contacts(self, rec_atoms, rec_res, rec_class, lig_atoms, lig_res, lig_class, center, cutoff)
 
+    def hbonds(self, rec, lig, center, hb_cutoff=3.5, min_angle=90.0, salt_cutoff=4.0):
+        """The polar atoms of a pair (rec, lig: the dicts of hbonds.polar_atoms - xyz, ante, role, res, n_res) prepared for the hydrogen-bond
+        and salt-bridge call on the GPU (dfm_hbond_create): heavy-atom criteria, a distance below `hb_cutoff` A and both antecedent angles
+        at least `min_angle` degrees; cation / anion pairs below `salt_cutoff` A.  Returns an HBonds whose `.count(rot, tr)` takes P poses
+        in one call."""
+        return HBonds(self, rec, lig, center, hb_cutoff, min_angle, salt_cutoff)
+
 
 class _Handle:
-    """What Native, Atoms, Surface, Interface and Contacts share: a handle `_h` made by dfm_<_kind>_create and freed by dfm_<_kind>_destroy - close(), a context
+    """What Native, Atoms, Surface, Interface, Contacts and HBonds share: a handle `_h` made by dfm_<_kind>_create and freed by dfm_<_kind>_destroy - close(), a context
     manager, closed when collected."""
     _kind = None
 
@@ -508,6 +515,68 @@ class Contacts(_Handle):
             out.contact_bits = _p(o["contact_bits"], L.U32P)
         L.check(L.lib().dfm_pose_rescon_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_rescon")
         return o
+
+
+class HBonds(_Handle):
+    """The polar atoms of a receptor / ligand pair with their antecedents, roles and residues resident on the model's GPU (dfm_hbond).
+    Read-only after creation: `count` may be called from several threads at once."""
+    _kind = "hbond"
+
+    def __init__(self, model: Model, rec, lig, center, hb_cutoff=3.5, min_angle=90.0, salt_cutoff=4.0):
+        from . import hbonds as HB
+        cen = _f32(center).reshape(-1)
+        if cen.size != 3:
+            raise ValueError(f"center must have 3 entries, got {np.shape(center)}")
+        self.hb_cutoff, self.salt_cutoff = HB.check_cutoffs(hb_cutoff, salt_cutoff)
+        self.min_angle, self.min_cos2 = float(min_angle), HB.min_cos2(min_angle)
+        rx, ra, rro, rre, self.n_rec_res = (np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a for a in HB.check_chain(rec, "rec"))
+        lx, la, lro, lre, self.n_lig_res = (np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a for a in HB.check_chain(lig, "lig"))
+        self.model, self.Nr, self.Nl = model, rx.shape[0], lx.shape[0]
+        u8, status = C.POINTER(C.c_uint8), C.c_int(0)
+        self._h = L.lib().dfm_hbond_create(model._h, self.Nr, _p(rx), _p(ra), rro.ctypes.data_as(u8), _p(rre, L.I32P), self.n_rec_res,
+                                           self.Nl, _p(lx), _p(la), lro.ctypes.data_as(u8), _p(lre, L.I32P), self.n_lig_res, _p(cen),
+                                           float(hb_cutoff), self.min_cos2, float(salt_cutoff), C.byref(status))
+        if not self._h:
+            L.check(status.value or -1, "dfm_hbond_create")
+
+    def info(self):
+        """{n_cells, max_cell_atoms, cell_edge} of the receptor's grid, n_rec_charged / n_lig_charged = the residues with a cation or an
+        anion, and chunk_poses, the poses one chunk of a call holds a bitmap for (dfm_hbond_info)."""
+        n, mx, e, rc, lc, ch = C.c_int32(0), C.c_int32(0), C.c_float(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        L.check(L.lib().dfm_hbond_info(self._h, C.byref(n), C.byref(mx), C.byref(e), C.byref(rc), C.byref(lc), C.byref(ch)), "dfm_hbond_info")
+        return {"n_cells": n.value, "max_cell_atoms": mx.value, "cell_edge": e.value, "n_rec_charged": rc.value, "n_lig_charged": lc.value,
+                "chunk_poses": ch.value}
+
+    def count(self, rot, tr, per_atom=False, chunk_poses=0):
+        """Hydrogen bonds and salt bridges of P poses (dfm_pose_hbonds; the float64 definition is hbonds.hbonds): rot [P,3] axis-angle and
+        tr [P,3] as rot_update / tr_update hold them.  Returns {n_hbond [P], hb_kind [P,3] (backbone-backbone, mixed, side chain-side
+        chain), n_salt [P] (residue pairs), n_salt_atoms [P]} int32 and, with `per_atom`, rec_hb / rec_sb [P,Nr] and lig_hb / lig_sb
+        [P,Nl] int32 in the caller's polar-atom order."""
+        r, t, P = _rigid_poses(rot, tr)
+        o = {"n_hbond": np.zeros(P, np.int32), "hb_kind": np.zeros((P, 3), np.int32), "n_salt": np.zeros(P, np.int32),
+             "n_salt_atoms": np.zeros(P, np.int32)}
+        if per_atom:
+            o.update(rec_hb=np.zeros((P, self.Nr), np.int32), lig_hb=np.zeros((P, self.Nl), np.int32),
+                     rec_sb=np.zeros((P, self.Nr), np.int32), lig_sb=np.zeros((P, self.Nl), np.int32))
+        out = L.HbondOutC()
+        for k, v in o.items():
+            setattr(out, k, _p(v, L.I32P))
+        L.check(L.lib().dfm_pose_hbonds_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_hbonds")
+        return o
+
+
+def hbond_last_timing():
+    """(host-to-device copy ms, kernel ms) of this thread's last HBonds.count call (dfm_hbond_last_timing)."""
+    a, b = C.c_double(0), C.c_double(0)
+    L.check(L.lib().dfm_hbond_last_timing(C.byref(a), C.byref(b)), "dfm_hbond_last_timing")
+    return a.value, b.value
+
+
+def hbond_last_phases():
+    """(memsets ms, walk ms, finish ms) of this thread's last HBonds.count call: its kernel time by phase (dfm_hbond_last_phases)."""
+    a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+    L.check(L.lib().dfm_hbond_last_phases(C.byref(a), C.byref(b), C.byref(c)), "dfm_hbond_last_phases")
+    return a.value, b.value, c.value
 
 
 def rescon_last_timing():

@@ -602,6 +602,57 @@ int dfm_rescon_last_timing(double *copy_ms, double *kernel_ms);
 /* The kernel milliseconds of that call by phase, from the call's own events: zeroing the bitmap, the walk (k_rescon_pose, k_rescon) and
  * k_rescon_finish; their sum is kernel_ms */
 int dfm_rescon_last_phases(double *zero_ms, double *walk_ms, double *finish_ms);
+/* Interface hydrogen bonds and salt bridges of P rigid poses of one ligand over the POLAR atoms of the two chains - what an interface
+ * report prints next to the contacts.  dfmdock_amd/hbonds.py is the float64 definition these calls are tested against and types the
+ * atoms (polar_atoms).  Heavy atoms only: the files carry no hydrogens; HIS counts as donor, acceptor and cation; no agreement with the
+ * counts of any published tool is claimed.  Centre and poses as for dfm_atoms_create / dfm_pose_sterics.  Per chain: xyz [N,3] the polar
+ * atoms, ante [N,3] the antecedent of each (the bonded heavy atom its angle is taken at; the ligand's rides with the pose), role [N] bits
+ * DONOR 1, ACCEPTOR 2, CATION 4, ANION 8, SIDECHAIN 16, res [N] the residue index of each atom in [0, n_res); a residue without polar
+ * atoms is legal.  hb_cutoff, salt_cutoff (A, in (0, 8]; 3.5 and 4.0 are usual); min_cos2 = cos^2 of the smallest angle, in [0, 1) -
+ * exactly 0 for 90 degrees - as the double the definition uses.
+ *   posed ligand atom X with antecedent XA, receptor atom Y with antecedent YA, fp64 on the widened fp32 receptor and the fp64 pose:
+ *     d = Y - X, r2 = (dx*dx + dy*dy) + dz*dz;  u = XA - X, uu = |u|^2, du = u.d;  w = YA - Y, ww = |w|^2, dw = -(w.d)
+ *   hydrogen bond iff one atom is a DONOR and the other an ACCEPTOR, r2 < hb_cutoff^2 (strict), du <= 0 and du*du >= min_cos2 (uu r2),
+ *     dw <= 0 and dw*dw >= min_cos2 (ww r2); a pair that is complementary in both directions is one bond.  Salt-bridge atom pair iff
+ *     one is a CATION and the other an ANION and r2 < salt_cutoff^2; a pair may be both.  A NaN is neither.
+ *   n_hbond [P]; hb_kind [P,3]: the bonds by the number of SIDECHAIN atoms among the two (0, 1, 2), summing to n_hbond; n_salt_atoms [P]:
+ *     the salt-bridge atom pairs; n_salt [P]: the DISTINCT (receptor residue, ligand residue) pairs with at least one; rec_hb [P,Nr] /
+ *     lig_hb [P,Nl]: the bonds each polar atom takes part in, rec_sb / lig_sb: its salt-bridge partners, in the caller's atom order.
+ *   A pose with a NaN or infinite rot / tr gets zeros and disturbs no other pose (not an error).
+ * Every output pointer may be NULL.  Everything is an integer: the results equal the definition's, and none depends on P, on a pose's
+ * index, on the order of the poses or on the chunks of a call.  The salt bridges are found in a bitmap per pose over the charged residues
+ * of the two chains (those with a CATION or ANION atom; a chain without one is legal); a call works through chunk_poses poses at a time
+ * (0: as many as fill 64 MiB of bitmap, at most 32768).  dfm_hbond_info reports the receptor grid's cells, the most atoms in one cell,
+ * the cell edge = max(hb_cutoff, salt_cutoff), the charged residues of the two chains and that default chunk.
+ * dfm_hbond_create returns NULL on failure and, with `status` not NULL, stores DFM_OK or the error code there.  DFM_E_INVALID / NULL,
+ * nothing enqueued: a NULL pointer among the inputs, Nr or Nl < 1 or > 2^24, a non-finite atom, antecedent or centre, n_rec_res or
+ * n_lig_res < 1 or > 4096, a role outside the five bits, a residue index out of range, a cutoff outside (0, 8], min_cos2 outside [0, 1),
+ * a receptor bounding box of more than 2^24 cells, chunk_poses < 0, P < 1 or > 65536.  DFM_E_OOM when the atoms or a chunk do not fit.
+ * Takes the MODEL handle for its device only.  The handle is read-only after creation; every call owns a non-blocking stream and its
+ * device temporaries, so calls on one handle may run from several host threads at once.  No reference call has a counterpart. */
+typedef struct dfm_hbond dfm_hbond;
+typedef struct {
+    int32_t *n_hbond;                   /* [P]      or NULL */
+    int32_t *hb_kind;                   /* [P,3]    or NULL */
+    int32_t *n_salt, *n_salt_atoms;     /* [P]      or NULL */
+    int32_t *rec_hb, *lig_hb;           /* [P,Nr], [P,Nl] or NULL */
+    int32_t *rec_sb, *lig_sb;           /* [P,Nr], [P,Nl] or NULL */
+} dfm_hbond_out;
+dfm_hbond *dfm_hbond_create(dfm_model *m, int Nr, const float *rec_xyz, const float *rec_ante, const uint8_t *rec_role, const int32_t *rec_res,
+                            int n_rec_res, int Nl, const float *lig_xyz, const float *lig_ante, const uint8_t *lig_role,
+                            const int32_t *lig_res, int n_lig_res, const float center[3], float hb_cutoff, double min_cos2,
+                            float salt_cutoff, int *status);
+void dfm_hbond_destroy(dfm_hbond *h);
+int dfm_hbond_info(const dfm_hbond *h, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge, int32_t *n_rec_charged,
+                   int32_t *n_lig_charged, int32_t *chunk_poses);
+int dfm_pose_hbonds(dfm_hbond *h, int P, const float *rot, const float *tr, dfm_hbond_out *out);
+int dfm_pose_hbonds_chunked(dfm_hbond *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_hbond_out *out);
+/* GPU milliseconds of the calling thread's last dfm_pose_hbonds, summed over its chunks: the host-to-device copies of the poses and the
+ * kernels (the memsets of the bitmap and of the per-atom output, k_hbond_pose, k_hbond, k_hbond_finish) - tools/hbonds_bench.py */
+int dfm_hbond_last_timing(double *copy_ms, double *kernel_ms);
+/* The kernel milliseconds of that call by phase, from the call's own events: the memsets, the walk (k_hbond_pose, k_hbond) and
+ * k_hbond_finish; their sum is kernel_ms */
+int dfm_hbond_last_phases(double *zero_ms, double *walk_ms, double *finish_ms);
 /* edges per node for this complex: min(N,20) + min(40, N-20) */
 int dfm_complex_degree(const dfm_complex *cx);
 /* Device blocks released by destroyed handles are parked per device for the next handle (a set driver creates and destroys a
