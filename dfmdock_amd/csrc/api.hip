@@ -1,6 +1,7 @@
 // api.hip - C ABI of the engine (include/dfmdock_amd.h): handles, weight packing, the per-evaluation
 // kernel schedule and the Euler-Maruyama loop.  Everything runs on one HIP stream per complex handle;
-// the host only enqueues (no sync inside the 40-step loop).
+// the host only enqueues (no sync inside the 40-step loop).  The pose calls (clustering, metrics, consensus,
+// the five rigid-pose families) are in api_pose.hip; what both files need is in dfm_host.h.
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -14,284 +15,17 @@
 #include <vector>
 
 #include "dfm_device.h"
-#include "dfm_guardscan.h"
-#include "dfm_internal.h"
-#include "dfm_poseprep.h"
+#include "dfm_host.h"
 
 using namespace dfm;
 
 // ------------------------------------------------------------------------------------------------
-static thread_local std::string g_err;
+// the single definitions of what dfm_host.h declares
+thread_local std::string dfm::g_err;
 extern "C" const char *dfm_last_error(void) { return g_err.c_str(); }
+BlockCache &dfm::g_block_cache = *new BlockCache;
+AllocDiag dfm::g_alloc_diag;
 
-static int fail(int code, const std::string &msg)
-{
-    g_err = msg;
-    return code;
-}
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess) {                                                                   \
-            return fail(_e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP,                         \
-                        std::string(#expr) + ": " + hipGetErrorString(_e));                       \
-        }                                                                                         \
-    } while (0)
-
-// Every handle belongs to one device (dfm_model: the device current at creation; dfm_complex: its model's).  Entry points
-// run under a DeviceScope: switch to the handle's device, restore the caller's on the way out.
-struct DeviceScope {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceScope(int dev)
-    {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess; }
-    }
-    ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
-};
-#define DEVICE_SCOPE(dev)                                                                          \
-    DeviceScope _ds(dev);                                                                          \
-    if (_ds.err != hipSuccess) return fail(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_ds.err))
-
-// ------------------------------------------------------------------------------------------------
-// Device blocks released by one handle and wanted by the next: a set driver creates and destroys a complex (about forty buffers, some of them
-// gigabytes) every few hundred milliseconds, and hipMalloc / hipFree of that size cost milliseconds each (hipFree also drains the device).
-// Released blocks are kept per device, up to a quarter of its memory, and handed out again to requests of at most twice-smaller size;
-// DFM_ALLOC_CACHE=0 turns the cache off.
-struct BlockCache {
-    std::mutex m;
-    std::multimap<size_t, void *> free_blocks[MAX_DEVICES];
-    size_t bytes[MAX_DEVICES] = {};
-    size_t cap[MAX_DEVICES] = {};
-    static bool enabled()
-    {
-        static const bool on = [] { const char *e = getenv("DFM_ALLOC_CACHE"); return !(e && atoi(e) == 0); }();
-        return on;
-    }
-    static double fraction()      // share of a device's memory the cache may park (DFM_ALLOC_CACHE_FRAC, default 0.25)
-    {
-        static const double f = [] {
-            const char *e = getenv("DFM_ALLOC_CACHE_FRAC");
-            const double v = e ? atof(e) : 0.25;
-            return v < 0.0 ? 0.0 : (v > 0.9 ? 0.9 : v);
-        }();
-        return f;
-    }
-    bool give(int dev, void *p, size_t size)
-    {
-        std::lock_guard<std::mutex> g(m);
-        if (!cap[dev]) {
-            size_t fr = 0, tot = 0;
-            DeviceScope ds(dev);      // the memory of the block's OWN device, whatever the calling thread's current device is
-            if (ds.err != hipSuccess || hipMemGetInfo(&fr, &tot) != hipSuccess) tot = 0;
-            cap[dev] = (size_t)((double)tot * fraction()) + 1;
-        }
-        if (bytes[dev] + size > cap[dev]) return false;
-        free_blocks[dev].emplace(size, p);
-        bytes[dev] += size;
-        return true;
-    }
-    // hand every parked block of `dev` (all devices: dev < 0) back to the driver; returns the bytes freed
-    size_t trim(int dev)
-    {
-        std::vector<std::pair<int, void *>> drop;
-        size_t freed = 0;
-        {
-            std::lock_guard<std::mutex> g(m);
-            for (int d = 0; d < MAX_DEVICES; ++d) {
-                if (dev >= 0 && d != dev) continue;
-                for (auto &kv : free_blocks[d]) drop.emplace_back(d, kv.second);
-                freed += bytes[d];
-                free_blocks[d].clear();
-                bytes[d] = 0;
-            }
-        }
-        for (auto &dp : drop) { DeviceScope ds(dp.first); (void)hipFree(dp.second); }
-        return freed;
-    }
-};
-static BlockCache &g_block_cache = *new BlockCache;      // never destroyed: a handle may outlive static destruction at process exit
-
-// diagnostic: DFM_ALLOC_GUARD=<KiB> puts that many KiB of 0xA5 before and after every block (cache off) and checks them at release:
-// a kernel writing outside its buffers is reported on stderr with the block's size and the first damaged offset
-static size_t guard_bytes()
-{
-    static const size_t g = [] { const char *e = getenv("DFM_ALLOC_GUARD"); return e ? (size_t)atoi(e) * 1024 : (size_t)0; }();
-    return g;
-}
-static int alloc_poison()      // DFM_ALLOC_POISON=<byte>: -1 when not set
-{
-    static const int poison = [] { const char *e = getenv("DFM_ALLOC_POISON"); return e ? atoi(e) & 255 : -1; }();
-    return poison;
-}
-// what the two diagnostics did in this process (dfm_alloc_diag): blocks handed out, bytes filled with the poison byte, guard bands
-// checked at release and found damaged, and the first damaged block: its size and the damaged byte's offset from the block's start
-// (negative in the head band, >= size in the tail band)
-struct AllocDiag {
-    std::atomic<int64_t> blocks{0}, poisoned{0}, bands{0}, damaged{0}, first_size{-1}, first_off{-1};
-};
-static AllocDiag g_alloc_diag;
-struct DevPool {
-    struct Block { void *p; size_t size; int dev; };
-    std::vector<Block> ptrs;
-    hipStream_t owner = nullptr;      // bind(): the one stream that ever touches this pool's blocks
-    bool bound = false;
-    void bind(hipStream_t s) { owner = s; bound = true; }
-    ~DevPool() { release(); }
-    // `drained`: the caller has synchronised the ONE stream that ever touched these blocks (a complex handle's own stream), so
-    // nothing in flight reads them and the device-wide wait - which would also wait for every OTHER handle's queued work, e.g. a
-    // whole dfm_sample call of the next complex of a set run - is not needed.
-    void release(bool drained = false)
-    {
-        if (ptrs.empty()) return;
-        if (const size_t G = guard_bytes()) {
-            (void)hipDeviceSynchronize();
-            std::vector<unsigned char> h(G);
-            for (const Block &b : ptrs) {
-                unsigned char *base = reinterpret_cast<unsigned char *>(b.p) - G;
-                for (int side = 0; side < 2; ++side) {
-                    (void)hipMemcpy(h.data(), side ? base + G + b.size : base, G, hipMemcpyDeviceToHost);
-                    const size_t k = guard_first_damaged(h.data(), G);
-                    g_alloc_diag.bands.fetch_add(1, std::memory_order_relaxed);
-                    if (k < G) {
-                        fprintf(stderr, "DFM_ALLOC_GUARD: block of %zu bytes: %s guard damaged at offset %zu (byte 0x%02x)\n", b.size,
-                                side ? "TAIL" : "HEAD", k, h[k]);
-                        if (g_alloc_diag.damaged.fetch_add(1, std::memory_order_relaxed) == 0) {
-                            g_alloc_diag.first_size.store((int64_t)b.size, std::memory_order_relaxed);
-                            g_alloc_diag.first_off.store(side ? (int64_t)(b.size + k) : (int64_t)k - (int64_t)G, std::memory_order_relaxed);
-                        }
-                    }
-                }
-                (void)hipFree(base);
-            }
-            ptrs.clear();
-            return;
-        }
-        if (BlockCache::enabled()) {
-            // what hipFree would have done: nothing in flight reads these blocks when the next owner gets them (a bound pool waits
-            // for its own stream only)
-            if (!drained) { if (bound) (void)hipStreamSynchronize(owner); else (void)hipDeviceSynchronize(); }
-            for (const Block &b : ptrs)
-                if (b.dev < 0 || b.dev >= MAX_DEVICES || !g_block_cache.give(b.dev, b.p, b.size)) (void)hipFree(b.p);
-        } else {
-            for (const Block &b : ptrs) (void)hipFree(b.p);
-        }
-        ptrs.clear();
-    }
-    // hand back the blocks allocated after `mark` (= ptrs.size() before a group of allocations that failed half way); the caller has
-    // synchronised the owning stream
-    void release_tail(size_t mark)
-    {
-        if (mark >= ptrs.size()) return;
-        std::vector<Block> tail(ptrs.begin() + mark, ptrs.end()), head(ptrs.begin(), ptrs.begin() + mark);
-        ptrs.swap(tail);
-        release(true);
-        ptrs.swap(head);
-    }
-    template <typename T> hipError_t alloc(T **out, size_t n)
-    {
-        size_t bytes = (n ? n : 1) * sizeof(T);
-        int dev = -1;
-        (void)hipGetDevice(&dev);
-        void *p = nullptr;
-        const int poison = alloc_poison();
-        if (const size_t G = guard_bytes()) {
-            unsigned char *base = nullptr;
-            hipError_t e = hipMalloc(reinterpret_cast<void **>(&base), bytes + 2 * G);
-            if (e != hipSuccess) return e;
-            (void)hipMemset(base, GUARD_BYTE, G); (void)hipMemset(base + G + bytes, GUARD_BYTE, G);
-            if (poison >= 0) {      // the payload too: a guarded block is exact-size and fresh, its contents whatever the driver left
-                (void)hipMemset(base + G, poison, bytes);
-                g_alloc_diag.poisoned.fetch_add((int64_t)bytes, std::memory_order_relaxed);
-            }
-            (void)hipDeviceSynchronize();
-            ptrs.push_back({base + G, bytes, dev});
-            g_alloc_diag.blocks.fetch_add(1, std::memory_order_relaxed);
-            *out = reinterpret_cast<T *>(base + G);
-            return hipSuccess;
-        }
-        if (BlockCache::enabled() && dev >= 0 && dev < MAX_DEVICES) {
-            bytes = (bytes + 65535) & ~(size_t)65535;      // 64 KiB granules: neighbouring sizes share blocks
-            // the block's true size travels with it: look it up by taking from the cache under the lock
-            {
-                std::lock_guard<std::mutex> g(g_block_cache.m);
-                auto &fb = g_block_cache.free_blocks[dev];
-                auto it = fb.lower_bound(bytes);
-                if (it != fb.end() && it->first <= 2 * bytes + (1u << 20)) {
-                    p = it->second;
-                    bytes = it->first;
-                    g_block_cache.bytes[dev] -= it->first;
-                    fb.erase(it);
-                }
-            }
-        }
-        if (!p) {
-            hipError_t e = hipMalloc(&p, bytes);
-            if (e != hipSuccess && BlockCache::enabled() && dev >= 0 && dev < MAX_DEVICES) {      // out of memory with blocks parked in the cache: drop them and retry
-                std::vector<void *> drop;
-                {
-                    std::lock_guard<std::mutex> g(g_block_cache.m);
-                    for (auto &kv : g_block_cache.free_blocks[dev]) drop.push_back(kv.second);
-                    g_block_cache.free_blocks[dev].clear();
-                    g_block_cache.bytes[dev] = 0;
-                }
-                for (void *q : drop) (void)hipFree(q);
-                (void)hipGetLastError();
-                e = hipMalloc(&p, bytes);
-            }
-            if (e != hipSuccess) return e;
-        }
-        ptrs.push_back({p, bytes, dev});
-        g_alloc_diag.blocks.fetch_add(1, std::memory_order_relaxed);
-        *out = reinterpret_cast<T *>(p);
-        // diagnostic: DFM_ALLOC_POISON=<byte> fills every block handed out (fresh or from the cache) with that byte - 255 = NaN
-        // patterns in fp32 / fp16 - so that a kernel reading memory nobody wrote shows up as a changed or non-finite result
-        if (poison >= 0) {
-            // The fill is waited for, on the pool's own stream or on the null stream.  What is written into the block next need not be
-            // in that stream's order - upload() copies synchronously, upload_async() on whichever (non-blocking) stream the caller
-            // names, and a memset of device memory may return before it has run - and a fill that lands afterwards replaces the data:
-            // the one-byte-per-residue interface flags of dfm_native_create became "every residue" that way.
-            const hipStream_t fs = bound ? owner : nullptr;
-            hipError_t e = hipMemsetAsync(p, poison, bytes, fs);
-            if (e == hipSuccess) e = hipStreamSynchronize(fs);
-            if (e != hipSuccess) return e;
-            g_alloc_diag.poisoned.fetch_add((int64_t)bytes, std::memory_order_relaxed);
-        }
-        return hipSuccess;
-    }
-    template <typename T> hipError_t upload(T **out, const T *host, size_t n)
-    {
-        hipError_t e = alloc(out, n);
-        if (e != hipSuccess) return e;
-        return hipMemcpy(*out, host, n * sizeof(T), hipMemcpyHostToDevice);
-    }
-    // the same on a handle's own (non-blocking) stream: the caller synchronises it before `host` may change
-    template <typename T> hipError_t upload_async(T **out, const T *host, size_t n, hipStream_t s)
-    {
-        hipError_t e = alloc(out, n);
-        if (e != hipSuccess) return e;
-        return hipMemcpyAsync(*out, host, n * sizeof(T), hipMemcpyHostToDevice, s);
-    }
-};
-
-struct dfm_model {
-    dfm_hparams hp;
-    int device = 0;
-    DevPool pool;
-    float *single_embed = nullptr;   // [256][lm]
-    LayerDev layers[8];
-    HeadsDev heads;
-    float *en0_w = nullptr;          // [256][512]
-    PairHeadDev pair[3];             // family 1: 0 to_force, 1 to_energy, 2 to_confidence
-    PairHeadDev dist;                // family 1: to_dist (fp32 only; w3 = [256][64], transposed)
-    float *dist_w3f = nullptr;       // family 1: to_dist.3 in the fragment order of k_pair_dist_sum (PairDistSumArgs::w3f)
-    float *ir0_w = nullptr, *ir0_b = nullptr, *ir2_w = nullptr, *ir2_b = nullptr, *ir4_w = nullptr, *ir4_b = nullptr;   // to_ires
-    float tab_max[8][2] = {};        // per layer: largest |entry| of the two merged lookup tables as stored (log2e-scaled; before the fp16 clamp)    // local refinement: IGSO(3) cdf tables by sigma index (k_igso3_cdf, 8 KB each in `pool`), built on first use and never changed
-    std::mutex ig_m;
-    std::map<int, double *> ig_tab;
-};
 
 struct Workspace {
     int Bcap = 0;
@@ -938,1465 +672,6 @@ extern "C" int dfm_restraint_eval(dfm_complex *cx, int B, const float *lig_pos, 
         n_satisfied[b] = (int32_t)h[(size_t)b * 8 + 1];
         if (step) std::memcpy(step + (size_t)b * 6, &h[(size_t)b * 8 + 2], 6 * sizeof(float));
     }
-    return DFM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Pose clustering (kernels_cluster.hip).  Bound to the model handle: the drivers close a complex right after sampling, and clustering
-// runs later, on the post-processing thread.  Every call owns a non-blocking stream and its temporaries (block cache), so calls from
-// several host threads, and next to that model's complex handles, do not share any state.
-// the two millisecond figures of this thread's last call of each kind, behind the dfm_*_last_timing getters: k_pose_dist and the
-// clustering kernels for MS_CLUSTER, host-to-device copies and kernels for the others
-enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_IFACE, MS_RESCON, MS_HBOND, MS_KINDS };
-static thread_local double g_last_ms[MS_KINDS][2] = {};
-
-static void set_last_ms(int kind, double a, double b)
-{
-    g_last_ms[kind][0] = a;
-    g_last_ms[kind][1] = b;
-}
-
-static int last_timing(int kind, double *a, double *b)
-{
-    if (!a || !b) return fail(DFM_E_INVALID, "NULL argument");
-    *a = g_last_ms[kind][0];
-    *b = g_last_ms[kind][1];
-    return DFM_OK;
-}
-
-static int check_pose_args(int B, int L, const float *lig_pos, const int32_t *residues, int n_res, std::vector<int32_t> *res_out)
-{
-    if (!lig_pos) return fail(DFM_E_INVALID, "lig_pos is NULL");
-    if (B < 1 || L < 1) return fail(DFM_E_INVALID, "need B >= 1 and L >= 1");
-    if (B > CL_MAX_POSES) return fail(DFM_E_INVALID, "at most " + std::to_string(CL_MAX_POSES) + " poses per call");
-    if ((int64_t)L * 9 > INT32_MAX / 2) return fail(DFM_E_INVALID, "L too large");
-    res_out->clear();
-    if (residues) {
-        if (n_res < 1 || n_res > L) return fail(DFM_E_INVALID, "need 1 <= n_res <= L");
-        std::vector<char> seen((size_t)L, 0);
-        for (int i = 0; i < n_res; ++i) {
-            const int r = residues[i];
-            if (r < 0 || r >= L) return fail(DFM_E_INVALID, "residue " + std::to_string(r) + " outside [0, " + std::to_string(L) + ")");
-            if (seen[(size_t)r]) return fail(DFM_E_INVALID, "residue " + std::to_string(r) + " listed twice");
-            seen[(size_t)r] = 1;
-        }
-        res_out->assign(residues, residues + n_res);
-    }
-    return DFM_OK;
-}
-
-// the call's stream and temporaries; the pool goes back to the block cache after the stream has drained
-struct PoseCall {
-    hipStream_t s = nullptr;
-    DevPool tmp;
-    hipEvent_t ev[4] = {};
-    ~PoseCall()
-    {
-        if (s) (void)hipStreamSynchronize(s);
-        tmp.release(true);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (s) (void)hipStreamDestroy(s);
-    }
-    hipError_t open()
-    {
-        hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-        if (e != hipSuccess) { s = nullptr; return e; }
-        tmp.bind(s);
-        for (hipEvent_t &v : ev)
-            if ((e = hipEventCreate(&v)) != hipSuccess) { v = nullptr; return e; }
-        return hipSuccess;
-    }
-    // uploads lig_pos and the subset; radius > 0 with rmsd == nullptr: the bitmask
-    hipError_t dist(int B, int L, const float *lig_pos, const std::vector<int32_t> &res, float radius, float *rmsd, uint32_t **mask)
-    {
-        float *X = nullptr;
-        int32_t *r = nullptr;
-        hipError_t e = tmp.upload_async(&X, lig_pos, (size_t)B * L * 9, s);
-        if (e == hipSuccess && !res.empty()) e = tmp.upload_async(&r, res.data(), res.size(), s);
-        const int W = (B + 31) / 32;
-        if (e == hipSuccess && !rmsd) e = tmp.alloc(mask, (size_t)B * W);
-        if (e == hipSuccess) e = hipEventRecord(ev[0], s);
-        if (e == hipSuccess) e = launch_pose_dist(X, B, L * 9, r, res.empty() ? L : (int)res.size(), radius, rmsd, rmsd ? nullptr : *mask, s);
-        if (e == hipSuccess) e = hipEventRecord(ev[1], s);
-        return e;
-    }
-};
-
-// the chunk loop of the rigid-pose calls (dfm_pose_sterics, dfm_pose_bsa, dfm_pose_iface_energy, dfm_pose_rescon, dfm_pose_hbonds): the chunk's (rot, tr) on the device, their transforms T, and
-// the call's copy / kernel milliseconds from the call's own events.  Per chunk: upload, the caller's memsets and launches, kernels_done,
-// the caller's downloads, finish
-struct PoseChunks {
-    PoseCall &c;
-    const float *rot, *tr;
-    float *d_rot = nullptr, *d_tr = nullptr;
-    double *T = nullptr;
-    double copy_ms = 0.0, kernel_ms = 0.0;
-    hipError_t open(int Pc)
-    {
-        hipError_t e = c.tmp.alloc(&d_rot, (size_t)Pc * 3);
-        if (e == hipSuccess) e = c.tmp.alloc(&d_tr, (size_t)Pc * 3);
-        if (e == hipSuccess) e = c.tmp.alloc(&T, (size_t)Pc * 12);
-        return e;
-    }
-    hipError_t upload(int p0, int n)
-    {
-        hipError_t e = hipEventRecord(c.ev[0], c.s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_rot, rot + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_tr, tr + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s);
-        if (e == hipSuccess) e = hipEventRecord(c.ev[1], c.s);
-        return e;
-    }
-    hipError_t kernels_done() { return hipEventRecord(c.ev[2], c.s); }
-    hipError_t finish()
-    {
-        const hipError_t e = hipStreamSynchronize(c.s);
-        float ms = 0.f;
-        if (e == hipSuccess && hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) copy_ms += ms;
-        if (e == hipSuccess && hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess) kernel_ms += ms;
-        return e;
-    }
-};
-
-extern "C" int dfm_pose_rmsd(dfm_model *m, int B, int L, const float *lig_pos, const int32_t *residues, int n_res, float *rmsd)
-{
-    if (!m || !rmsd) return fail(DFM_E_INVALID, "NULL argument");
-    std::vector<int32_t> res;
-    if (int rc = check_pose_args(B, L, lig_pos, residues, n_res, &res)) return rc;
-    DEVICE_SCOPE(m->device);
-    PoseCall c;
-    HIPCHK(c.open());
-    float *d = nullptr;
-    HIPCHK(c.tmp.alloc(&d, (size_t)B * B));
-    HIPCHK(c.dist(B, L, lig_pos, res, 1.0f, d, nullptr));
-    HIPCHK(hipMemcpyAsync(rmsd, d, (size_t)B * B * sizeof(float), hipMemcpyDeviceToHost, c.s));
-    HIPCHK(hipStreamSynchronize(c.s));
-    float ms = 0.f;
-    set_last_ms(MS_CLUSTER, hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess ? ms : -1.0, 0.0);
-    return DFM_OK;
-}
-
-extern "C" int dfm_pose_cluster(dfm_model *m, int B, int L, const float *lig_pos, const int32_t *residues, int n_res, const float *key,
-                                float radius, int rule, int max_clusters, int32_t *n_clusters, int32_t *center, int32_t *size,
-                                int32_t *cluster_of)
-{
-    if (!m || !n_clusters || !center || !size || !cluster_of) return fail(DFM_E_INVALID, "NULL argument");
-    std::vector<int32_t> res;
-    if (int rc = check_pose_args(B, L, lig_pos, residues, n_res, &res)) return rc;
-    if (!(radius > 0.f) || !std::isfinite(radius)) return fail(DFM_E_INVALID, "radius must be finite and > 0");
-    if (rule != DFM_CLUSTER_ENERGY && rule != DFM_CLUSTER_SIZE) return fail(DFM_E_INVALID, "rule must be 0 (energy) or 1 (size)");
-    if (max_clusters < 1) return fail(DFM_E_INVALID, "max_clusters must be >= 1");
-    const int maxc = max_clusters < B ? max_clusters : B;
-    // key order on the host: lower key first, ties to the lower index, NaN last (dfmdock_amd/cluster.py: rank_order)
-    std::vector<int32_t> order((size_t)B), pos((size_t)B);
-    for (int i = 0; i < B; ++i) order[(size_t)i] = i;
-    if (key) {
-        std::stable_sort(order.begin(), order.end(), [key](int32_t a, int32_t b) {
-            const bool na = std::isnan(key[a]), nb = std::isnan(key[b]);
-            if (na != nb) return nb;
-            return !na && key[a] < key[b];
-        });
-    }
-    for (int i = 0; i < B; ++i) pos[(size_t)order[(size_t)i]] = i;
-    DEVICE_SCOPE(m->device);
-    PoseCall c;
-    HIPCHK(c.open());
-    uint32_t *mask = nullptr;
-    int32_t *d_order = nullptr, *d_out = nullptr;
-    const size_t out_n = (size_t)B + 2 * (size_t)maxc + 4;      // cluster_of | center | size | state
-    HIPCHK(c.tmp.upload_async(&d_order, order.data(), order.size(), c.s));
-    HIPCHK(c.tmp.alloc(&d_out, out_n));
-    HIPCHK(c.dist(B, L, lig_pos, res, radius, nullptr, &mask));
-    int32_t *d_of = d_out, *d_center = d_out + B, *d_size = d_center + maxc, *d_state = d_size + maxc;
-    if (rule == DFM_CLUSTER_ENERGY) {
-        HIPCHK(launch_cluster_leader(mask, B, d_order, maxc, d_of, d_center, d_size, d_state, c.s));
-    } else {
-        int32_t *d_pos = nullptr, *counts = nullptr, *mlist = nullptr;
-        uint32_t *U = nullptr;
-        HIPCHK(c.tmp.upload_async(&d_pos, pos.data(), pos.size(), c.s));
-        HIPCHK(c.tmp.alloc(&counts, (size_t)B));
-        HIPCHK(c.tmp.alloc(&mlist, (size_t)B));
-        HIPCHK(c.tmp.alloc(&U, (size_t)(B + 31) / 32));
-        HIPCHK(launch_cluster_count(mask, B, counts, U, d_of, d_state, c.s));
-        // one pick + decrement per cluster; the steps after the last pose is assigned return at once.  Every 64 clusters the host
-        // looks at the done flag, so a run that ends early does not enqueue max_clusters steps.
-        int32_t st[3] = {0, 0, 0};
-        for (int k = 0; k < maxc; ++k) {
-            HIPCHK(launch_cluster_step(mask, B, counts, d_pos, d_order, U, d_of, d_center, d_size, mlist, d_state, c.s));
-            if ((k & 63) == 63 && k + 1 < maxc) {
-                HIPCHK(hipMemcpyAsync(st, d_state, sizeof(st), hipMemcpyDeviceToHost, c.s));
-                HIPCHK(hipStreamSynchronize(c.s));
-                if (st[1]) break;
-            }
-        }
-    }
-    HIPCHK(hipEventRecord(c.ev[2], c.s));
-    std::vector<int32_t> h(out_n);
-    HIPCHK(hipMemcpyAsync(h.data(), d_out, out_n * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-    HIPCHK(hipStreamSynchronize(c.s));
-    const int n = h[(size_t)B + 2 * maxc];
-    if (n < 0 || n > maxc) return fail(DFM_E_HIP, "clustering kernel returned " + std::to_string(n) + " clusters");
-    *n_clusters = n;
-    std::memcpy(cluster_of, h.data(), (size_t)B * sizeof(int32_t));
-    std::memcpy(center, h.data() + B, (size_t)n * sizeof(int32_t));
-    std::memcpy(size, h.data() + B + maxc, (size_t)n * sizeof(int32_t));
-    float ms = 0.f;
-    const double dist_ms = hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess ? ms : -1.0;
-    set_last_ms(MS_CLUSTER, dist_ms, hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess ? ms : -1.0);
-    return DFM_OK;
-}
-
-extern "C" int dfm_pose_last_timing(double *dist_ms, double *cluster_ms)
-{
-    return last_timing(MS_CLUSTER, dist_ms, cluster_ms);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Docking metrics (kernels_metrics.hip).  A dfm_native holds what the native alone fixes and is read-only after creation; like the
-// clustering calls it is bound to the model handle's device only, and every dfm_pose_metrics call owns its stream and temporaries.
-constexpr size_t METRICS_CHUNK_BYTES = (size_t)64 << 20;      // poses uploaded and evaluated per chunk of a call
-
-struct dfm_native {
-    int device = 0, R = 0, L = 0;
-    DevPool pool;      // unbound: released under a device-wide wait, like a model's
-    float *rec = nullptr, *lig = nullptr;
-    uint8_t *frec = nullptr, *flig = nullptr;
-    int32_t *contacts = nullptr;
-    double *rec_const = nullptr;      // the receptor's sums with the native receptor as its own model (k_metrics_reduce)
-    MetricsConst mc = {};
-    std::vector<int32_t> iface_rec, iface_lig, pairs;
-};
-
-extern "C" void dfm_native_destroy(dfm_native *nat)
-{
-    if (!nat) return;
-    DeviceScope ds(nat->device);
-    nat->pool.release();
-    delete nat;
-}
-
-extern "C" dfm_native *dfm_native_create(dfm_model *m, const float *rec_pos, const float *lig_pos, int R, int L, float iface_cutoff,
-                                         float contact_cutoff)
-{
-    auto bad = [](int code, const std::string &msg) -> dfm_native * { (void)fail(code, msg); return nullptr; };
-    if (!m || !rec_pos || !lig_pos) return bad(DFM_E_INVALID, "NULL argument");
-    if (R < 1 || L < 1) return bad(DFM_E_INVALID, "need R >= 1 and L >= 1");
-    if ((int64_t)R * L > ((int64_t)1 << 27)) return bad(DFM_E_INVALID, "R x L exceeds 2^27 residue pairs");
-    if (!std::isfinite(iface_cutoff) || !std::isfinite(contact_cutoff)) return bad(DFM_E_INVALID, "cutoffs must be finite");
-    DeviceScope ds(m->device);
-    if (ds.err != hipSuccess) return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err));
-    dfm_native *nat = new dfm_native;
-    nat->device = m->device; nat->R = R; nat->L = L;
-    hipError_t e = hipSuccess;
-    {
-        PoseCall c;
-        uint8_t *d_pairs = nullptr;
-        std::vector<uint8_t> pm((size_t)R * L);
-        e = c.open();
-        if (e == hipSuccess) e = nat->pool.upload_async(&nat->rec, rec_pos, (size_t)R * 9, c.s);
-        if (e == hipSuccess) e = nat->pool.upload_async(&nat->lig, lig_pos, (size_t)L * 9, c.s);
-        if (e == hipSuccess) e = c.tmp.alloc(&d_pairs, pm.size());
-        if (e == hipSuccess) e = launch_native_pairs(nat->rec, nat->lig, R, L, (double)iface_cutoff, (double)contact_cutoff, d_pairs, c.s);
-        if (e == hipSuccess) e = hipMemcpyAsync(pm.data(), d_pairs, pm.size(), hipMemcpyDeviceToHost, c.s);
-        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
-        std::vector<uint8_t> fr((size_t)R, 0), fl((size_t)L, 0);
-        MetricsConst &mc = nat->mc;
-        if (e == hipSuccess) {
-            for (int i = 0; i < R; ++i)
-                for (int j = 0; j < L; ++j) {
-                    const uint8_t b = pm[(size_t)i * L + j];
-                    if (b & 1) { fr[(size_t)i] = 1; fl[(size_t)j] = 1; }
-                    if (b & 2) { nat->pairs.push_back(i); nat->pairs.push_back(j); }
-                }
-            for (int i = 0; i < R; ++i) if (fr[(size_t)i]) nat->iface_rec.push_back(i);
-            for (int j = 0; j < L; ++j) if (fl[(size_t)j]) nat->iface_lig.push_back(j);
-            // the shift: the all-atom centroid rounded to fp32 (p - o is then exact in fp64 for every fp32 coordinate near the complex)
-            double cen[3] = {0.0, 0.0, 0.0};
-            for (int i = 0; i < R * 9; ++i) cen[i % 3] += (double)rec_pos[i];
-            for (int i = 0; i < L * 9; ++i) cen[i % 3] += (double)lig_pos[i];
-            for (int k = 0; k < 3; ++k) {
-                const float of = (float)(cen[k] / (3.0 * ((double)R + (double)L)));
-                mc.o[k] = std::isfinite(of) ? (double)of : 0.0;
-            }
-            for (int i = 0; i < R; ++i)
-                for (int k = 0; k < 9; ++k) {
-                    const double q = (double)rec_pos[(size_t)i * 9 + k] - mc.o[k % 3];
-                    mc.T_rec[k % 3] += q;
-                    if (fr[(size_t)i]) mc.T_rec_iface[k % 3] += q;
-                }
-            for (int j = 0; j < L; ++j)
-                for (int k = 0; k < 9; ++k) {
-                    const double q = (double)lig_pos[(size_t)j * 9 + k] - mc.o[k % 3];
-                    mc.T_lig[k % 3] += q;
-                    if (fl[(size_t)j]) mc.T_lig_iface[k % 3] += q;
-                }
-            mc.n_rec = R; mc.n_lig = L;
-            mc.n_rec_iface = (int)nat->iface_rec.size(); mc.n_lig_iface = (int)nat->iface_lig.size();
-            mc.n_contacts = (int)(nat->pairs.size() / 2);
-            mc.rec_moves = 0;
-            mc.contact_cutoff = (double)contact_cutoff;
-            e = nat->pool.upload_async(&nat->frec, fr.data(), fr.size(), c.s);
-        }
-        if (e == hipSuccess) e = nat->pool.upload_async(&nat->flig, fl.data(), fl.size(), c.s);
-        if (e == hipSuccess) e = nat->pool.upload_async(&nat->contacts, nat->pairs.data(), nat->pairs.size(), c.s);
-        if (e == hipSuccess) e = nat->pool.alloc(&nat->rec_const, 24);
-        if (e == hipSuccess) {
-            const MetricsChain rc = {nat->rec, nat->rec, nat->frec, R};
-            e = launch_metrics_reduce(rc, rc, 1, 1, mc, nat->rec_const, c.s);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
-    }      // the call's stream has drained: the host vectors it read may go
-    if (e != hipSuccess) {
-        nat->pool.release();
-        delete nat;
-        return bad(e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP, std::string("dfm_native_create: ") + hipGetErrorString(e));
-    }
-    return nat;
-}
-
-extern "C" int dfm_native_info(const dfm_native *nat, int32_t *n_iface_rec, int32_t *n_iface_lig, int32_t *n_contacts, int32_t *iface_rec,
-                               int32_t *iface_lig, int32_t *contacts)
-{
-    if (!nat) return fail(DFM_E_INVALID, "NULL argument");
-    if (n_iface_rec) *n_iface_rec = (int32_t)nat->iface_rec.size();
-    if (n_iface_lig) *n_iface_lig = (int32_t)nat->iface_lig.size();
-    if (n_contacts) *n_contacts = (int32_t)(nat->pairs.size() / 2);
-    if (iface_rec && !nat->iface_rec.empty()) std::memcpy(iface_rec, nat->iface_rec.data(), nat->iface_rec.size() * sizeof(int32_t));
-    if (iface_lig && !nat->iface_lig.empty()) std::memcpy(iface_lig, nat->iface_lig.data(), nat->iface_lig.size() * sizeof(int32_t));
-    if (contacts && !nat->pairs.empty()) std::memcpy(contacts, nat->pairs.data(), nat->pairs.size() * sizeof(int32_t));
-    return DFM_OK;
-}
-
-// Python's round(x, 6): the correctly rounded six-decimal string, read back
-static double round6(double x)
-{
-    if (!std::isfinite(x)) return x;
-    char buf[64];
-    snprintf(buf, sizeof(buf), "%.6f", x);
-    return strtod(buf, nullptr);
-}
-// libm's pow through a pointer the compiler cannot fold: metrics.py's `** 2` is that call, and the results are compared bit for bit
-static double (*volatile g_pow)(double, double) = static_cast<double (*)(double, double)>(std::pow);
-
-extern "C" int dfm_pose_metrics(dfm_native *nat, int P, const float *lig_pos, const float *rec_pos, dfm_metrics_out *out)
-{
-    if (!nat || !out) return fail(DFM_E_INVALID, "NULL argument");
-    if (!lig_pos) return fail(DFM_E_INVALID, "lig_pos is NULL");
-    if (P < 1) return fail(DFM_E_INVALID, "need P >= 1");
-    DEVICE_SCOPE(nat->device);
-    PoseCall c;
-    HIPCHK(c.open());
-    const int R = nat->R, L = nat->L, chains = rec_pos ? 2 : 1;
-    const size_t lig_n = (size_t)L * 9, rec_n = (size_t)R * 9, per_pose = (lig_n + (rec_pos ? rec_n : 0)) * sizeof(float);
-    const int Pc = (int)std::min<size_t>((size_t)P, std::max<size_t>(1, METRICS_CHUNK_BYTES / per_pose));
-    float *X = nullptr, *Xr = nullptr;
-    double *sums = nullptr, *xf = nullptr, *d_rmsd = nullptr;
-    int32_t *d_cnt = nullptr;
-    HIPCHK(c.tmp.alloc(&X, (size_t)Pc * lig_n));
-    if (rec_pos) HIPCHK(c.tmp.alloc(&Xr, (size_t)Pc * rec_n));
-    HIPCHK(c.tmp.alloc(&sums, (size_t)Pc * chains * 24));
-    HIPCHK(c.tmp.alloc(&xf, (size_t)Pc * 36));
-    HIPCHK(c.tmp.alloc(&d_rmsd, (size_t)Pc * 3));
-    HIPCHK(c.tmp.alloc(&d_cnt, (size_t)Pc));
-    MetricsConst mc = nat->mc;
-    mc.rec_moves = rec_pos ? 1 : 0;
-    const MetricsChain lig = {X, nat->lig, nat->flig, L}, rec = {rec_pos ? Xr : nat->rec, nat->rec, nat->frec, R};
-    std::vector<double> h_rmsd((size_t)P * 3);
-    std::vector<int32_t> h_cnt((size_t)P);
-    double copy_ms = 0.0, kernel_ms = 0.0;
-    for (int p0 = 0; p0 < P; p0 += Pc) {
-        const int n = std::min(Pc, P - p0);
-        HIPCHK(hipEventRecord(c.ev[0], c.s));
-        HIPCHK(hipMemcpyAsync(X, lig_pos + (size_t)p0 * lig_n, (size_t)n * lig_n * sizeof(float), hipMemcpyHostToDevice, c.s));
-        if (rec_pos) HIPCHK(hipMemcpyAsync(Xr, rec_pos + (size_t)p0 * rec_n, (size_t)n * rec_n * sizeof(float), hipMemcpyHostToDevice, c.s));
-        HIPCHK(hipEventRecord(c.ev[1], c.s));
-        HIPCHK(launch_metrics_reduce(lig, rec, chains, n, mc, sums, c.s));
-        HIPCHK(launch_metrics_finish(lig, rec, sums, chains, nat->rec_const, mc, nat->contacts, n, xf, d_rmsd, d_cnt, c.s));
-        HIPCHK(hipEventRecord(c.ev[2], c.s));
-        HIPCHK(hipMemcpyAsync(h_rmsd.data() + (size_t)p0 * 3, d_rmsd, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, c.s));
-        HIPCHK(hipMemcpyAsync(h_cnt.data() + p0, d_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        HIPCHK(hipStreamSynchronize(c.s));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) copy_ms += ms;
-        if (hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess) kernel_ms += ms;
-    }
-    set_last_ms(MS_METRICS, copy_ms, kernel_ms);
-    const double nc = (double)mc.n_contacts;
-    for (int p = 0; p < P; ++p) {
-        const double cr = h_rmsd[(size_t)p * 3], ir = h_rmsd[(size_t)p * 3 + 1], lr = h_rmsd[(size_t)p * 3 + 2];
-        const double fnat = round6((double)h_cnt[(size_t)p] / (nc + 1e-6));
-        if (out->c_rmsd) out->c_rmsd[p] = cr;
-        if (out->i_rmsd) out->i_rmsd[p] = ir;
-        if (out->l_rmsd) out->l_rmsd[p] = lr;
-        if (out->fnat) out->fnat[p] = fnat;
-        if (out->dockq) out->dockq[p] = (fnat + 1.0 / (1.0 + g_pow(ir / 1.5, 2.0)) + 1.0 / (1.0 + g_pow(lr / 8.5, 2.0))) / 3.0;
-        if (out->n_recovered) out->n_recovered[p] = h_cnt[(size_t)p];
-    }
-    return DFM_OK;
-}
-
-extern "C" int dfm_metrics_last_timing(double *copy_ms, double *kernel_ms)
-{
-    return last_timing(MS_METRICS, copy_ms, kernel_ms);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Consensus contact scoring (kernels_consensus.hip).  Bound to the model handle's device only, like the clustering calls; every call owns
-// its stream and temporaries.  A chunk holds its poses and their contact bits; a call of one chunk keeps the bits between the counting
-// and the scoring pass, a longer call uploads and evaluates every chunk again in the scoring pass.
-constexpr size_t CONSENSUS_CHUNK_BYTES = (size_t)256 << 20;
-constexpr int CONSENSUS_MAX_POSES = 65536;
-
-extern "C" int dfm_consensus_chunk_poses(int R, int L)
-{
-    if (R < 1 || L < 1) return 0;
-    const size_t per_pose = (size_t)L * 9 * sizeof(float) + (size_t)R * (size_t)((L + 63) / 64) * sizeof(uint64_t);
-    return (int)std::min<size_t>(32768, std::max<size_t>(1, CONSENSUS_CHUNK_BYTES / per_pose));      // (a launch takes 65535 poses)
-}
-
-extern "C" int dfm_pose_consensus(dfm_model *m, int P, int R, int L, const float *rec_pos, const float *lig_pos, const uint8_t *member,
-                                  float cutoff, dfm_consensus_out *out)
-{
-    if (!m) return fail(DFM_E_INVALID, "m is NULL");
-    if (!rec_pos) return fail(DFM_E_INVALID, "rec_pos is NULL");
-    if (!lig_pos) return fail(DFM_E_INVALID, "lig_pos is NULL");
-    if (!out) return fail(DFM_E_INVALID, "out is NULL");
-    if (P < 1 || P > CONSENSUS_MAX_POSES) return fail(DFM_E_INVALID, "P must be in 1 .. " + std::to_string(CONSENSUS_MAX_POSES));
-    if (R < 1 || L < 1) return fail(DFM_E_INVALID, "need R >= 1 and L >= 1");
-    if ((int64_t)R * L > ((int64_t)1 << 27)) return fail(DFM_E_INVALID, "R x L exceeds 2^27 residue pairs");
-    if (!std::isfinite(cutoff) || !(cutoff > 0.f)) return fail(DFM_E_INVALID, "cutoff must be finite and > 0");
-    std::vector<uint8_t> mem((size_t)P, 1);
-    if (member) {
-        size_t M = 0;
-        for (int p = 0; p < P; ++p) M += (mem[(size_t)p] = member[p] ? 1 : 0);
-        if (M == 0) return fail(DFM_E_INVALID, "member: no pose is a member");
-    }
-    DEVICE_SCOPE(m->device);
-    PoseCall c;
-    HIPCHK(c.open());
-    const int W = (L + 63) / 64, Pc = std::min(P, dfm_consensus_chunk_poses(R, L));
-    const size_t lig_n = (size_t)L * 9, words = (size_t)W * R, RL = (size_t)R * L;
-    const bool one_chunk = Pc >= P, want_count = out->count || out->rec_count || out->lig_count || out->score_sum;
-    const bool want_pose = out->n_contacts || out->score_sum;
-    float *d_rec = nullptr, *X = nullptr;
-    uint8_t *d_mem = nullptr;
-    uint64_t *d_bits = nullptr;
-    int32_t *d_count = nullptr, *d_marg = nullptr, *d_n = nullptr;
-    int64_t *d_sum = nullptr;
-    HIPCHK(c.tmp.upload_async(&d_rec, rec_pos, (size_t)R * 9, c.s));
-    HIPCHK(c.tmp.upload_async(&d_mem, mem.data(), mem.size(), c.s));
-    HIPCHK(c.tmp.alloc(&X, (size_t)Pc * lig_n));
-    HIPCHK(c.tmp.alloc(&d_bits, (size_t)Pc * words));
-    HIPCHK(c.tmp.alloc(&d_count, RL));
-    HIPCHK(c.tmp.alloc(&d_marg, (size_t)R + L));      // rec_count | lig_count
-    HIPCHK(c.tmp.alloc(&d_n, (size_t)Pc));
-    HIPCHK(c.tmp.alloc(&d_sum, (size_t)Pc));
-    HIPCHK(hipMemsetAsync(d_count, 0, RL * sizeof(int32_t), c.s));
-    HIPCHK(hipMemsetAsync(d_marg, 0, ((size_t)R + L) * sizeof(int32_t), c.s));
-    std::vector<uint64_t> h_bits(out->bits ? (size_t)Pc * words : 0);
-    double copy_ms = 0.0, kernel_ms = 0.0;
-    // pass 0: bits and counts of every chunk; pass 1: per-pose sums against the finished counts
-    for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 1 && !want_pose) break;
-        for (int p0 = 0; p0 < P; p0 += Pc) {
-            const int n = std::min(Pc, P - p0);
-            HIPCHK(hipEventRecord(c.ev[0], c.s));
-            if (pass == 0 || !one_chunk)
-                HIPCHK(hipMemcpyAsync(X, lig_pos + (size_t)p0 * lig_n, (size_t)n * lig_n * sizeof(float), hipMemcpyHostToDevice, c.s));
-            HIPCHK(hipEventRecord(c.ev[1], c.s));
-            if (pass == 0 || !one_chunk) HIPCHK(launch_contact_bits(d_rec, X, n, R, L, cutoff, d_bits, c.s));
-            if (pass == 0 && want_count) HIPCHK(launch_contact_count(d_bits, d_mem + p0, n, R, L, d_count, d_marg, d_marg + R, c.s));
-            if (pass == 1) HIPCHK(launch_contact_score(d_bits, d_count, n, R, L, d_n, d_sum, c.s));
-            HIPCHK(hipEventRecord(c.ev[2], c.s));
-            if (pass == 0 && out->bits)
-                HIPCHK(hipMemcpyAsync(h_bits.data(), d_bits, (size_t)n * words * sizeof(uint64_t), hipMemcpyDeviceToHost, c.s));
-            if (pass == 1 && out->n_contacts)
-                HIPCHK(hipMemcpyAsync(out->n_contacts + p0, d_n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-            if (pass == 1 && out->score_sum)
-                HIPCHK(hipMemcpyAsync(out->score_sum + p0, d_sum, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
-            HIPCHK(hipStreamSynchronize(c.s));
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess) copy_ms += ms;
-            if (hipEventElapsedTime(&ms, c.ev[1], c.ev[2]) == hipSuccess) kernel_ms += ms;
-            if (pass == 0 && out->bits)      // device [n][W][R] -> the ABI's [P][R][W]
-                for (int p = 0; p < n; ++p)
-                    for (int w = 0; w < W; ++w) {
-                        const uint64_t *src = h_bits.data() + ((size_t)p * W + w) * R;
-                        uint64_t *dst = out->bits + (size_t)(p0 + p) * words + w;
-                        for (int i = 0; i < R; ++i) dst[(size_t)i * W] = src[i];
-                    }
-        }
-    }
-    if (out->count) HIPCHK(hipMemcpyAsync(out->count, d_count, RL * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-    if (out->rec_count) HIPCHK(hipMemcpyAsync(out->rec_count, d_marg, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-    if (out->lig_count) HIPCHK(hipMemcpyAsync(out->lig_count, d_marg + R, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-    HIPCHK(hipStreamSynchronize(c.s));
-    set_last_ms(MS_CONSENSUS, copy_ms, kernel_ms);
-    return DFM_OK;
-}
-
-extern "C" int dfm_consensus_last_timing(double *copy_ms, double *kernel_ms)
-{
-    return last_timing(MS_CONSENSUS, copy_ms, kernel_ms);
-}
-
-// ------------------------------------------------------------------------------------------------
-// All-atom clash / contact screen (kernels_sterics.hip).  A dfm_atoms holds what the two atom sets and the rotation centre fix - the
-// receptor's cell grid, the ligand in blocks of 64 neighbours - and is read-only after creation; like a dfm_native it is bound to the
-// model handle's device only, and every dfm_pose_sterics call owns its stream and temporaries.
-constexpr size_t STERICS_CHUNK_BYTES = (size_t)64 << 20;      // per-atom output of one chunk of a call
-constexpr int STERICS_MAX_CHUNK = 32768;                      // poses per launch (gridDim.y)
-static thread_local int g_sterics_count = 0;                  // dfm_sterics_exit_counts: count the early exits of this thread's calls
-static thread_local uint64_t g_sterics_exits[3] = {0, 0, 0};  // waves, left at the sphere test, left at the box test
-
-struct dfm_atoms {
-    int device = 0, Ar = 0, Al = 0, n_cells = 0, max_cell_atoms = 0;
-    int chunk_poses = 0, default_chunk = 0;      // the creator's chunk (0: none given); poses whose per-atom output fills STERICS_CHUNK_BYTES
-    float cell_edge = 0.f;
-    DevPool pool;      // unbound: released under a device-wide wait, like a model's
-    float *rec = nullptr, *lig = nullptr, *sphere = nullptr;
-    int32_t *cell_start = nullptr, *lig_index = nullptr;
-    StericsConst sc = {};
-};
-
-extern "C" void dfm_atoms_destroy(dfm_atoms *a)
-{
-    if (!a) return;
-    DeviceScope ds(a->device);
-    a->pool.release();
-    delete a;
-}
-
-extern "C" dfm_atoms *dfm_atoms_create(dfm_model *m, int Ar, const float *rec_atoms, int Al, const float *lig_atoms, const float center[3],
-                                       const dfm_sterics_params *p_or_null)
-{
-    auto bad = [](int code, const std::string &msg) -> dfm_atoms * { (void)fail(code, msg); return nullptr; };
-    if (!m) return bad(DFM_E_INVALID, "m is NULL");
-    if (const std::string msg = check_atom_sets(Ar, rec_atoms, Al, lig_atoms, center); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    dfm_sterics_params prm = {3.0f, 5.0f, 0};
-    if (p_or_null) prm = *p_or_null;
-    if (!std::isfinite(prm.clash_cutoff) || !std::isfinite(prm.contact_cutoff) || !(prm.clash_cutoff > 0.f) || !(prm.contact_cutoff > 0.f))
-        return bad(DFM_E_INVALID, "cutoffs must be finite and > 0");
-    if (prm.contact_cutoff < prm.clash_cutoff) return bad(DFM_E_INVALID, "contact_cutoff must be >= clash_cutoff");
-    if (prm.chunk_poses < 0) return bad(DFM_E_INVALID, "chunk_poses must be >= 0");
-    // the receptor's grid: origin = the bounding box's low corner, edge = the contact cutoff
-    CellGrid gr;
-    if (!build_cell_grid(Ar, rec_atoms, (double)prm.contact_cutoff, gr))
-        return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells of the contact cutoff");
-    double maxabs = 0.0;
-    for (int k = 0; k < 3; ++k) maxabs = std::max(maxabs, std::max(std::fabs(gr.lo[k]), std::fabs(gr.hi[k])));
-    maxabs += 2.0 * (double)prm.contact_cutoff + 1.0;
-    // the fp32 reject threshold (dfm_posewalk.h): contact * 1.0001 + slack
-    const float thr = prm.contact_cutoff * 1.0001f + pose_slack(maxabs);
-    StericsConst sc = {};
-    sc.g = walk_grid(gr, (double)prm.contact_cutoff, (double)thr, center);
-    sc.contact = (double)prm.contact_cutoff;
-    sc.clash = (double)prm.clash_cutoff;
-    sc.reject2 = thr * thr;
-    if (!std::isfinite(sc.reject2)) return bad(DFM_E_INVALID, "cutoffs must be finite and > 0");
-    double llo[3] = {(double)lig_atoms[0], (double)lig_atoms[1], (double)lig_atoms[2]};
-    for (int i = 1; i < Al; ++i)
-        for (int k = 0; k < 3; ++k) llo[k] = std::min(llo[k], (double)lig_atoms[(size_t)i * 3 + k]);
-    const LigandBlocks lb = build_ligand_blocks(Al, lig_atoms, llo, sc.g.edge, sc.g.center);
-    if (!lb.finite) return bad(DFM_E_INVALID, "lig_atoms / center: the ligand's extent about the centre overflows fp32");
-    const std::vector<float> rec4 = gather4(gr.order, rec_atoms, nullptr), lig4 = gather4(lb.index, lig_atoms, nullptr);
-    DeviceScope ds(m->device);
-    if (ds.err != hipSuccess) return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err));
-    dfm_atoms *a = new dfm_atoms;
-    a->device = m->device; a->Ar = Ar; a->Al = Al; a->sc = sc; a->n_cells = sc.g.nx * sc.g.ny * sc.g.nz; a->max_cell_atoms = gr.max_cell;
-    a->cell_edge = prm.contact_cutoff;
-    a->chunk_poses = prm.chunk_poses;
-    a->default_chunk = (int)std::min<size_t>(STERICS_MAX_CHUNK, std::max<size_t>(1, STERICS_CHUNK_BYTES / ((size_t)Al * 2 * sizeof(int32_t))));
-    hipError_t e = hipSuccess;
-    {
-        PoseCall c;
-        e = c.open();
-        if (e == hipSuccess) e = a->pool.upload_async(&a->rec, rec4.data(), rec4.size(), c.s);
-        if (e == hipSuccess) e = a->pool.upload_async(&a->cell_start, gr.start.data(), gr.start.size(), c.s);
-        if (e == hipSuccess) e = a->pool.upload_async(&a->lig, lig4.data(), lig4.size(), c.s);
-        if (e == hipSuccess) e = a->pool.upload_async(&a->sphere, lb.sphere.data(), lb.sphere.size(), c.s);
-        if (e == hipSuccess) e = a->pool.upload_async(&a->lig_index, lb.index.data(), lb.index.size(), c.s);
-        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
-    }      // the call's stream has drained: the host vectors it read may go
-    if (e != hipSuccess) {
-        a->pool.release();
-        delete a;
-        return bad(e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP, std::string("dfm_atoms_create: ") + hipGetErrorString(e));
-    }
-    return a;
-}
-
-extern "C" int dfm_atoms_info(const dfm_atoms *a, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge)
-{
-    if (!a) return fail(DFM_E_INVALID, "NULL argument");
-    if (n_cells) *n_cells = a->n_cells;
-    if (max_cell_atoms) *max_cell_atoms = a->max_cell_atoms;
-    if (cell_edge) *cell_edge = a->cell_edge;
-    return DFM_OK;
-}
-
-extern "C" int dfm_pose_sterics_chunked(dfm_atoms *a, int P, const float *rot, const float *tr, int chunk_poses, dfm_sterics_out *out)
-{
-    if (!a) return fail(DFM_E_INVALID, "a is NULL");
-    if (!rot) return fail(DFM_E_INVALID, "rot is NULL");
-    if (!tr) return fail(DFM_E_INVALID, "tr is NULL");
-    if (!out) return fail(DFM_E_INVALID, "out is NULL");
-    if (P < 1) return fail(DFM_E_INVALID, "need P >= 1");
-    if (chunk_poses < 0) return fail(DFM_E_INVALID, "chunk_poses must be >= 0");
-    DEVICE_SCOPE(a->device);
-    PoseCall c;
-    HIPCHK(c.open());
-    const bool per_atom = out->lig_clash || out->lig_contact;
-    // the call's chunk, else the creator's, else the default: without per-atom output a chunk is bounded by the launch alone
-    const int want = chunk_poses > 0 ? chunk_poses : a->chunk_poses;
-    const int Pc = std::min(P, want > 0 ? std::min(want, STERICS_MAX_CHUNK) : (per_atom ? a->default_chunk : STERICS_MAX_CHUNK));
-    const size_t Al = (size_t)a->Al;
-    PoseChunks ch{c, rot, tr};
-    int32_t *d_cnt = nullptr, *d_lc = nullptr, *d_lt = nullptr;
-    uint64_t *d_min = nullptr, *d_exits = nullptr;
-    HIPCHK(ch.open(Pc));
-    HIPCHK(c.tmp.alloc(&d_cnt, (size_t)Pc * 2));      // n_clash | n_contact
-    HIPCHK(c.tmp.alloc(&d_min, (size_t)Pc));
-    if (out->lig_clash) HIPCHK(c.tmp.alloc(&d_lc, (size_t)Pc * Al));
-    if (out->lig_contact) HIPCHK(c.tmp.alloc(&d_lt, (size_t)Pc * Al));
-    if (g_sterics_count) {
-        HIPCHK(c.tmp.alloc(&d_exits, 2));
-        HIPCHK(hipMemsetAsync(d_exits, 0, 2 * sizeof(uint64_t), c.s));
-    }
-    const StericsAtoms at = {a->rec, a->lig, a->sphere, a->cell_start, a->lig_index, a->sc, a->Ar, a->Al};
-    std::vector<int32_t> h_cnt((size_t)Pc * 2);
-    std::vector<uint64_t> h_min((size_t)Pc);
-    for (int p0 = 0; p0 < P; p0 += Pc) {
-        const int n = std::min(Pc, P - p0);
-        HIPCHK(ch.upload(p0, n));
-        if (d_lc) HIPCHK(hipMemsetAsync(d_lc, 0, (size_t)n * Al * sizeof(int32_t), c.s));
-        if (d_lt) HIPCHK(hipMemsetAsync(d_lt, 0, (size_t)n * Al * sizeof(int32_t), c.s));
-        HIPCHK(launch_sterics_pose(ch.d_rot, ch.d_tr, n, ch.T, d_cnt, d_cnt + Pc, d_min, c.s));
-        HIPCHK(launch_sterics(at, ch.T, n, d_cnt, d_cnt + Pc, d_min, d_lc, d_lt, d_exits, c.s));
-        HIPCHK(ch.kernels_done());
-        HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)Pc * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        HIPCHK(hipMemcpyAsync(h_min.data(), d_min, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, c.s));
-        if (d_lc) HIPCHK(hipMemcpyAsync(out->lig_clash + (size_t)p0 * Al, d_lc, (size_t)n * Al * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        if (d_lt) HIPCHK(hipMemcpyAsync(out->lig_contact + (size_t)p0 * Al, d_lt, (size_t)n * Al * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        HIPCHK(ch.finish());
-        for (int p = 0; p < n; ++p) {
-            if (out->n_clash) out->n_clash[p0 + p] = h_cnt[(size_t)p];
-            if (out->n_contact) out->n_contact[p0 + p] = h_cnt[(size_t)Pc + p];
-            if (out->min_dist) std::memcpy(out->min_dist + p0 + p, &h_min[(size_t)p], sizeof(double));
-        }
-    }
-    if (d_exits) {
-        uint64_t h[2] = {0, 0};
-        HIPCHK(hipMemcpyAsync(h, d_exits, sizeof(h), hipMemcpyDeviceToHost, c.s));
-        HIPCHK(hipStreamSynchronize(c.s));
-        g_sterics_exits[0] = (uint64_t)P * (uint64_t)((a->Al + 63) / 64);
-        g_sterics_exits[1] = h[0];
-        g_sterics_exits[2] = h[1];
-    }
-    set_last_ms(MS_STERICS, ch.copy_ms, ch.kernel_ms);
-    return DFM_OK;
-}
-
-extern "C" int dfm_pose_sterics(dfm_atoms *a, int P, const float *rot, const float *tr, dfm_sterics_out *out)
-{
-    return dfm_pose_sterics_chunked(a, P, rot, tr, 0, out);
-}
-
-extern "C" int dfm_sterics_last_timing(double *copy_ms, double *kernel_ms)
-{
-    return last_timing(MS_STERICS, copy_ms, kernel_ms);
-}
-
-extern "C" int dfm_sterics_exit_counts(int enable, uint64_t *counts_or_null)
-{
-    if (counts_or_null) std::memcpy(counts_or_null, g_sterics_exits, sizeof(g_sterics_exits));
-    g_sterics_count = enable ? 1 : 0;
-    return DFM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Buried surface area (kernels_surface.hip).  A dfm_surface holds what the two atom sets, their radii, the probe, the sphere points and
-// the rotation centre fix - the receptor's cell grid, the ligand in blocks of 64 neighbours, every atom's isolated exposure mask - and is
-// read-only after creation; every dfm_pose_bsa call owns its stream and temporaries.
-constexpr size_t SURFACE_CHUNK_BYTES = (size_t)64 << 20;      // receptor masks and per-atom output of one chunk of a call
-
-struct dfm_surface {
-    int device = 0, Ar = 0, Al = 0, K = 0, n_classes = 0, n_cells = 0, max_cell_atoms = 0, chunk_poses = 0;
-    float probe = 0.f, cell_edge = 0.f, class_radius[16] = {};
-    double sasa[2] = {0.0, 0.0};
-    std::vector<int32_t> exposed[2];      // exposed points per atom, caller's order: receptor, ligand
-    DevPool pool;
-    float *rec = nullptr, *lig = nullptr, *sphere = nullptr, *dirs = nullptr;
-    int32_t *cell_start = nullptr, *rec_index = nullptr, *lig_index = nullptr, *rec_class = nullptr, *lig_class = nullptr;
-    uint64_t *rec_exp = nullptr, *lig_exp = nullptr;
-    SurfaceConst sc = {};
-};
-
-extern "C" void dfm_surface_destroy(dfm_surface *s)
-{
-    if (!s) return;
-    DeviceScope ds(s->device);
-    s->pool.release();
-    delete s;
-}
-
-extern "C" dfm_surface *dfm_surface_create(dfm_model *m, int Ar, const float *rec_atoms, const float *rec_radius, int Al,
-                                           const float *lig_atoms, const float *lig_radius, const float center[3],
-                                           const dfm_surface_params *p_or_null)
-{
-    auto bad = [](int code, const std::string &msg) -> dfm_surface * { (void)fail(code, msg); return nullptr; };
-    if (!m) return bad(DFM_E_INVALID, "m is NULL");
-    if (const std::string msg = check_atom_sets(Ar, rec_atoms, Al, lig_atoms, center); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    if (!rec_radius) return bad(DFM_E_INVALID, "rec_radius is NULL");
-    if (!lig_radius) return bad(DFM_E_INVALID, "lig_radius is NULL");
-    dfm_surface_params prm = {1.4f, 128, nullptr, 0};
-    if (p_or_null) prm = *p_or_null;
-    if (!std::isfinite(prm.probe) || !(prm.probe > 0.f)) return bad(DFM_E_INVALID, "probe must be finite and > 0");
-    if (prm.K < 64 || prm.K > 256 || prm.K % 64) return bad(DFM_E_INVALID, "K must be a multiple of 64 in 64 .. 256");
-    if (prm.chunk_poses < 0) return bad(DFM_E_INVALID, "chunk_poses must be >= 0");
-    const int K = prm.K, G = K / 64;
-    std::vector<float> dirs((size_t)K * 3);
-    for (int k = 0; k < K; ++k) {
-        if (prm.dirs) {
-            for (int c = 0; c < 3; ++c) dirs[(size_t)k * 3 + c] = prm.dirs[(size_t)k * 3 + c];
-        } else {
-            const double z = 1.0 - (2.0 * k + 1.0) / K, r = std::sqrt(1.0 - z * z), phi = k * (M_PI * (3.0 - std::sqrt(5.0)));
-            dirs[(size_t)k * 3] = (float)(r * std::cos(phi)); dirs[(size_t)k * 3 + 1] = (float)(r * std::sin(phi)); dirs[(size_t)k * 3 + 2] = (float)z;
-        }
-    }
-    for (float v : dirs)
-        if (!std::isfinite(v)) return bad(DFM_E_INVALID, "dirs is not finite");
-    // the radius classes: the distinct fp32 values of both chains in ascending order (positive floats order like their bit patterns)
-    std::vector<float> values;
-    for (int side = 0; side < 2; ++side) {
-        const float *rad = side ? lig_radius : rec_radius;
-        for (int i = 0; i < (side ? Al : Ar); ++i) {
-            if (!std::isfinite(rad[i]) || !(rad[i] > 0.f))
-                return bad(DFM_E_INVALID, std::string(side ? "lig_radius" : "rec_radius") + ": atom " + std::to_string(i) + " is not finite and > 0");
-            if (std::find(values.begin(), values.end(), rad[i]) == values.end()) {
-                if (values.size() == 16) return bad(DFM_E_INVALID, "more than 16 radius classes");
-                values.push_back(rad[i]);
-            }
-        }
-    }
-    std::sort(values.begin(), values.end());
-    auto class_of = [&](float v) { return (int32_t)(std::lower_bound(values.begin(), values.end(), v) - values.begin()); };
-    const double probe = (double)prm.probe, Rmax = (double)values.back() + probe;
-    // one grid edge for the receptor's device grid and both host exposure grids: at least 2 Rmax, grown as dfm_posewalk.h grows a
-    // reach - by the factor 1.0001 and the slack - which is also the fp32 pair test's allowance
-    double maxabs = 0.0;
-    for (size_t i = 0; i < (size_t)Ar * 3; ++i) maxabs = std::max(maxabs, std::fabs((double)rec_atoms[i]));
-    for (size_t i = 0; i < (size_t)Al * 3; ++i) maxabs = std::max(maxabs, std::fabs((double)lig_atoms[i]));
-    maxabs += 4.0 * Rmax + 1.0;
-    const float slack = pose_slack(maxabs), thr = (float)(2.0 * Rmax) * 1.0001f + slack;
-    if (!std::isfinite(thr)) return bad(DFM_E_INVALID, "radii and probe must be finite and > 0");
-    const double edge = (double)thr, pad = 1e-6 + 1e-12 * maxabs;
-    CellGrid gr, gl;
-    if (!build_cell_grid(Ar, rec_atoms, edge, gr)) return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells");
-    if (!build_cell_grid(Al, lig_atoms, edge, gl)) return bad(DFM_E_INVALID, "the ligand's bounding box needs more than 2^24 cells");
-    std::vector<uint64_t> rexp((size_t)Ar * G), lexp((size_t)Al * G);
-    surface_exposure(Ar, rec_atoms, rec_radius, probe, K, dirs.data(), gr.lo, gr.dims, edge, pad, gr.start.data(), gr.order.data(), rexp.data());
-    surface_exposure(Al, lig_atoms, lig_radius, probe, K, dirs.data(), gl.lo, gl.dims, edge, pad, gl.start.data(), gl.order.data(), lexp.data());
-    dfm_surface *sf = new dfm_surface;
-    sf->device = m->device; sf->Ar = Ar; sf->Al = Al; sf->K = K; sf->probe = prm.probe; sf->chunk_poses = prm.chunk_poses;
-    sf->n_classes = (int)values.size();
-    for (size_t c = 0; c < values.size(); ++c) sf->class_radius[c] = values[c];
-    sf->n_cells = gr.dims[0] * gr.dims[1] * gr.dims[2]; sf->max_cell_atoms = gr.max_cell; sf->cell_edge = thr;
-    // exposed points per atom and the isolated SASA: class sums in ascending order, left to right
-    for (int side = 0; side < 2; ++side) {
-        const int n = side ? Al : Ar;
-        const float *rad = side ? lig_radius : rec_radius;
-        const std::vector<uint64_t> &ex = side ? lexp : rexp;
-        int64_t per_class[16] = {};
-        sf->exposed[side].resize((size_t)n);
-        for (int i = 0; i < n; ++i) {
-            int c = 0;
-            for (int g = 0; g < G; ++g) c += __builtin_popcountll(ex[(size_t)i * G + g]);
-            sf->exposed[side][(size_t)i] = c;
-            per_class[class_of(rad[i])] += c;
-        }
-        double s = 0.0;
-        for (size_t c = 0; c < values.size(); ++c) {
-            const double R = (double)values[c] + probe;
-            s = s + (double)per_class[c] * (4.0 * M_PI * R * R / K);
-        }
-        sf->sasa[side] = s;
-    }
-    SurfaceConst sc = {};
-    sc.g = walk_grid(gr, edge, edge, center);
-    sc.probe = probe; sc.slack = slack; sc.G = G;
-    sf->sc = sc;
-    // the ligand in blocks of 64 neighbours; both chains' per-atom arrays in their device order
-    const LigandBlocks lb = build_ligand_blocks(Al, lig_atoms, gl.lo, edge, sc.g.center);
-    if (!lb.finite) { delete sf; return bad(DFM_E_INVALID, "lig_atoms / center: the ligand's extent about the centre overflows fp32"); }
-    const std::vector<float> rec4 = gather4(gr.order, rec_atoms, rec_radius), lig4 = gather4(lb.index, lig_atoms, lig_radius);
-    std::vector<int32_t> rec_class((size_t)Ar), lig_class((size_t)Al);
-    std::vector<uint64_t> rexp_s((size_t)Ar * G), lexp_s((size_t)Al * G);
-    for (int q = 0; q < Ar; ++q) {
-        const int32_t src = gr.order[(size_t)q];
-        rec_class[(size_t)q] = class_of(rec_radius[src]);
-        for (int g = 0; g < G; ++g) rexp_s[(size_t)q * G + g] = rexp[(size_t)src * G + g];
-    }
-    for (int q = 0; q < Al; ++q) {
-        const int32_t src = lb.index[(size_t)q];
-        lig_class[(size_t)q] = class_of(lig_radius[src]);
-        for (int g = 0; g < G; ++g) lexp_s[(size_t)q * G + g] = lexp[(size_t)src * G + g];
-    }
-    DeviceScope ds(m->device);
-    if (ds.err != hipSuccess) { delete sf; return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err)); }
-    hipError_t e = hipSuccess;
-    {
-        PoseCall c;
-        e = c.open();
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->rec, rec4.data(), rec4.size(), c.s);
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->cell_start, gr.start.data(), gr.start.size(), c.s);
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->rec_index, gr.order.data(), gr.order.size(), c.s);
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->rec_class, rec_class.data(), rec_class.size(), c.s);
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->rec_exp, rexp_s.data(), rexp_s.size(), c.s);
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig, lig4.data(), lig4.size(), c.s);
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->sphere, lb.sphere.data(), lb.sphere.size(), c.s);
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig_index, lb.index.data(), lb.index.size(), c.s);
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig_class, lig_class.data(), lig_class.size(), c.s);
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->lig_exp, lexp_s.data(), lexp_s.size(), c.s);
-        if (e == hipSuccess) e = sf->pool.upload_async(&sf->dirs, dirs.data(), dirs.size(), c.s);
-        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
-    }      // the call's stream has drained: the host vectors it read may go
-    if (e != hipSuccess) {
-        sf->pool.release();
-        delete sf;
-        return bad(e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP, std::string("dfm_surface_create: ") + hipGetErrorString(e));
-    }
-    return sf;
-}
-
-extern "C" int dfm_surface_info(const dfm_surface *s, double *sasa_rec, double *sasa_lig, int32_t *rec_exposed, int32_t *lig_exposed,
-                                int32_t *n_classes, float *class_radius, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge)
-{
-    if (!s) return fail(DFM_E_INVALID, "NULL argument");
-    if (sasa_rec) *sasa_rec = s->sasa[0];
-    if (sasa_lig) *sasa_lig = s->sasa[1];
-    if (rec_exposed) std::memcpy(rec_exposed, s->exposed[0].data(), (size_t)s->Ar * sizeof(int32_t));
-    if (lig_exposed) std::memcpy(lig_exposed, s->exposed[1].data(), (size_t)s->Al * sizeof(int32_t));
-    if (n_classes) *n_classes = s->n_classes;
-    if (class_radius) std::memcpy(class_radius, s->class_radius, sizeof(s->class_radius));
-    if (n_cells) *n_cells = s->n_cells;
-    if (max_cell_atoms) *max_cell_atoms = s->max_cell_atoms;
-    if (cell_edge) *cell_edge = s->cell_edge;
-    return DFM_OK;
-}
-
-extern "C" int dfm_pose_bsa_chunked(dfm_surface *sf, int P, const float *rot, const float *tr, int chunk_poses, dfm_bsa_out *out)
-{
-    if (!sf) return fail(DFM_E_INVALID, "s is NULL");
-    if (!rot) return fail(DFM_E_INVALID, "rot is NULL");
-    if (!tr) return fail(DFM_E_INVALID, "tr is NULL");
-    if (!out) return fail(DFM_E_INVALID, "out is NULL");
-    if (P < 1) return fail(DFM_E_INVALID, "need P >= 1");
-    if (chunk_poses < 0) return fail(DFM_E_INVALID, "chunk_poses must be >= 0");
-    DEVICE_SCOPE(sf->device);
-    PoseCall c;
-    HIPCHK(c.open());
-    const size_t Ar = (size_t)sf->Ar, Al = (size_t)sf->Al, G = (size_t)sf->sc.G;
-    // the call's chunk, else the creator's, else as many poses as fill SURFACE_CHUNK_BYTES of masks and per-atom output
-    const size_t per_pose = Ar * G * sizeof(uint64_t) + (out->lig_buried ? Al * sizeof(int32_t) : 0) + (out->rec_buried ? Ar * sizeof(int32_t) : 0);
-    const int want = chunk_poses > 0 ? chunk_poses : sf->chunk_poses;
-    const int fill = (int)std::min<size_t>(STERICS_MAX_CHUNK, std::max<size_t>(1, SURFACE_CHUNK_BYTES / per_pose));
-    const int Pc = std::min(P, want > 0 ? std::min(want, STERICS_MAX_CHUNK) : fill);
-    PoseChunks ch{c, rot, tr};
-    int32_t *d_cls = nullptr, *d_lb = nullptr, *d_rb = nullptr;
-    uint64_t *d_mask = nullptr;
-    HIPCHK(ch.open(Pc));
-    HIPCHK(c.tmp.alloc(&d_cls, (size_t)Pc * 32));
-    HIPCHK(c.tmp.alloc(&d_mask, (size_t)Pc * Ar * G));
-    if (out->lig_buried) HIPCHK(c.tmp.alloc(&d_lb, (size_t)Pc * Al));
-    if (out->rec_buried) HIPCHK(c.tmp.alloc(&d_rb, (size_t)Pc * Ar));
-    const SurfaceAtoms at = {sf->rec, sf->lig, sf->sphere, sf->dirs, sf->cell_start, sf->rec_index, sf->lig_index, sf->rec_class, sf->lig_class,
-                             sf->rec_exp, sf->lig_exp, sf->sc, sf->Ar, sf->Al};
-    std::vector<int32_t> h_cls((size_t)Pc * 32);
-    double area[16] = {};
-    for (int k = 0; k < sf->n_classes; ++k) {
-        const double R = (double)sf->class_radius[k] + (double)sf->probe;
-        area[k] = 4.0 * M_PI * R * R / sf->K;
-    }
-    for (int p0 = 0; p0 < P; p0 += Pc) {
-        const int n = std::min(Pc, P - p0);
-        HIPCHK(ch.upload(p0, n));
-        HIPCHK(hipMemsetAsync(d_mask, 0, (size_t)n * Ar * G * sizeof(uint64_t), c.s));
-        if (d_lb) HIPCHK(hipMemsetAsync(d_lb, 0, (size_t)n * Al * sizeof(int32_t), c.s));
-        HIPCHK(launch_surface_pose(ch.d_rot, ch.d_tr, n, ch.T, d_cls, c.s));
-        HIPCHK(launch_surface(at, ch.T, n, d_mask, d_lb, d_rb, d_cls, c.s));
-        HIPCHK(ch.kernels_done());
-        HIPCHK(hipMemcpyAsync(h_cls.data(), d_cls, (size_t)n * 32 * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        if (d_lb) HIPCHK(hipMemcpyAsync(out->lig_buried + (size_t)p0 * Al, d_lb, (size_t)n * Al * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        if (d_rb) HIPCHK(hipMemcpyAsync(out->rec_buried + (size_t)p0 * Ar, d_rb, (size_t)n * Ar * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        HIPCHK(ch.finish());
-        for (int p = 0; p < n; ++p) {
-            const int32_t *cp = h_cls.data() + (size_t)p * 32;
-            int32_t side[2] = {0, 0};
-            double s = 0.0;
-            for (int ch = 0; ch < 2; ++ch)
-                for (int k = 0; k < sf->n_classes; ++k) {
-                    side[ch] += cp[ch * 16 + k];
-                    s = s + (double)cp[ch * 16 + k] * area[k];
-                }
-            if (out->rec_points) out->rec_points[p0 + p] = side[0];
-            if (out->lig_points) out->lig_points[p0 + p] = side[1];
-            if (out->class_points) std::memcpy(out->class_points + (size_t)(p0 + p) * 32, cp, 32 * sizeof(int32_t));
-            if (out->bsa) out->bsa[p0 + p] = s;
-        }
-    }
-    set_last_ms(MS_BSA, ch.copy_ms, ch.kernel_ms);
-    return DFM_OK;
-}
-
-extern "C" int dfm_pose_bsa(dfm_surface *s, int P, const float *rot, const float *tr, dfm_bsa_out *out)
-{
-    return dfm_pose_bsa_chunked(s, P, rot, tr, 0, out);
-}
-
-extern "C" int dfm_bsa_last_timing(double *copy_ms, double *kernel_ms)
-{
-    return last_timing(MS_BSA, copy_ms, kernel_ms);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Interface energy (kernels_iface.hip).  A dfm_iface holds what the two atom sets, their parameters, the scalars and the rotation centre
-// fix - the receptor's grid of cells of the cutoff, the ligand in blocks of 64 neighbours, each atom's (rmin_half, sqrt_eps, charge) at
-// its sorted place - and is read-only after creation; every dfm_pose_iface_energy call owns its stream and temporaries.
-constexpr size_t IFACE_CHUNK_BYTES = (size_t)64 << 20;      // per-atom output of one chunk of a call
-constexpr int IFACE_MAX_CHUNK = 32768;                      // poses per launch (gridDim.y)
-
-struct dfm_iface {
-    int device = 0, Ar = 0, Al = 0, n_cells = 0, max_cell_atoms = 0, default_chunk = 0;
-    float cell_edge = 0.f;
-    double sum_bound = 0.0;
-    DevPool pool;      // unbound: released under a device-wide wait, like a model's
-    float *rec = nullptr, *rec_par = nullptr, *lig = nullptr, *lig_par = nullptr, *sphere = nullptr;
-    int32_t *cell_start = nullptr, *lig_index = nullptr;
-    IfaceConst sc = {};
-};
-
-extern "C" void dfm_iface_destroy(dfm_iface *h)
-{
-    if (!h) return;
-    DeviceScope ds(h->device);
-    h->pool.release();
-    delete h;
-}
-
-extern "C" dfm_iface *dfm_iface_create(dfm_model *m, int Ar, const float *rec_atoms, const float *rec_rmin_half, const float *rec_sqrt_eps,
-                                       const float *rec_charge, int Al, const float *lig_atoms, const float *lig_rmin_half,
-                                       const float *lig_sqrt_eps, const float *lig_charge, const float center[3], float cutoff, float soft,
-                                       float elec_min_dist, float dielectric_slope)
-{
-    auto bad = [](int code, const std::string &msg) -> dfm_iface * { (void)fail(code, msg); return nullptr; };
-    if (!m) return bad(DFM_E_INVALID, "m is NULL");
-    if (const std::string msg = check_atom_sets(Ar, rec_atoms, Al, lig_atoms, center); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    if (const std::string msg = check_iface_atoms("rec", Ar, rec_rmin_half, rec_sqrt_eps, rec_charge); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    if (const std::string msg = check_iface_atoms("lig", Al, lig_rmin_half, lig_sqrt_eps, lig_charge); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    if (const std::string msg = check_iface_scalars(cutoff, soft, elec_min_dist, dielectric_slope); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    // the receptor's grid: origin = the bounding box's low corner, edge = the cutoff
-    CellGrid gr;
-    if (!build_cell_grid(Ar, rec_atoms, (double)cutoff, gr))
-        return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells of the cutoff");
-    const IfaceBound bound = iface_sum_bound(Ar, rec_sqrt_eps, rec_charge, Al, lig_sqrt_eps, lig_charge, gr.max_cell, soft, elec_min_dist,
-                                             dielectric_slope);
-    if (!bound.ok) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "the energy sums could reach 2^62 quanta: %.3g pairs of at most %.3g kcal/mol", bound.pairs, bound.term_kcal);
-        return bad(DFM_E_INVALID, buf);
-    }
-    double maxabs = 0.0;
-    for (int k = 0; k < 3; ++k) maxabs = std::max(maxabs, std::max(std::fabs(gr.lo[k]), std::fabs(gr.hi[k])));
-    maxabs += 2.0 * (double)cutoff + 1.0;
-    // the fp32 reject threshold (dfm_posewalk.h): cutoff * 1.0001 + slack
-    const float thr = cutoff * 1.0001f + pose_slack(maxabs);
-    IfaceConst sc = {};
-    sc.g = walk_grid(gr, (double)cutoff, (double)thr, center);
-    sc.cut2 = (double)cutoff * (double)cutoff;
-    sc.soft = (double)soft;
-    sc.min2 = (double)elec_min_dist * (double)elec_min_dist;
-    sc.kc = 332.0637 / (double)dielectric_slope;
-    sc.reject2 = thr * thr;
-    double llo[3] = {(double)lig_atoms[0], (double)lig_atoms[1], (double)lig_atoms[2]};
-    for (int i = 1; i < Al; ++i)
-        for (int k = 0; k < 3; ++k) llo[k] = std::min(llo[k], (double)lig_atoms[(size_t)i * 3 + k]);
-    const LigandBlocks lb = build_ligand_blocks(Al, lig_atoms, llo, sc.g.edge, sc.g.center);
-    if (!lb.finite) return bad(DFM_E_INVALID, "lig_atoms / center: the ligand's extent about the centre overflows fp32");
-    const std::vector<float> rec4 = gather4(gr.order, rec_atoms, nullptr), lig4 = gather4(lb.index, lig_atoms, nullptr);
-    const std::vector<float> recp = gather_iface(gr.order, rec_rmin_half, rec_sqrt_eps, rec_charge);
-    const std::vector<float> ligp = gather_iface(lb.index, lig_rmin_half, lig_sqrt_eps, lig_charge);
-    DeviceScope ds(m->device);
-    if (ds.err != hipSuccess) return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err));
-    dfm_iface *h = new dfm_iface;
-    h->device = m->device; h->Ar = Ar; h->Al = Al; h->sc = sc; h->n_cells = sc.g.nx * sc.g.ny * sc.g.nz; h->max_cell_atoms = gr.max_cell;
-    h->cell_edge = cutoff;
-    h->sum_bound = bound.sum_quanta;
-    h->default_chunk = (int)std::min<size_t>(IFACE_MAX_CHUNK, std::max<size_t>(1, IFACE_CHUNK_BYTES / ((size_t)Al * 2 * sizeof(int64_t))));
-    hipError_t e = hipSuccess;
-    {
-        PoseCall c;
-        e = c.open();
-        if (e == hipSuccess) e = h->pool.upload_async(&h->rec, rec4.data(), rec4.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->rec_par, recp.data(), recp.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->cell_start, gr.start.data(), gr.start.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->lig, lig4.data(), lig4.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->lig_par, ligp.data(), ligp.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->sphere, lb.sphere.data(), lb.sphere.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->lig_index, lb.index.data(), lb.index.size(), c.s);
-        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
-    }      // the call's stream has drained: the host vectors it read may go
-    if (e != hipSuccess) {
-        h->pool.release();
-        delete h;
-        return bad(e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP, std::string("dfm_iface_create: ") + hipGetErrorString(e));
-    }
-    return h;
-}
-
-extern "C" int dfm_iface_info(const dfm_iface *h, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge, double *sum_bound_q)
-{
-    if (!h) return fail(DFM_E_INVALID, "NULL argument");
-    if (n_cells) *n_cells = h->n_cells;
-    if (max_cell_atoms) *max_cell_atoms = h->max_cell_atoms;
-    if (cell_edge) *cell_edge = h->cell_edge;
-    if (sum_bound_q) *sum_bound_q = h->sum_bound;
-    return DFM_OK;
-}
-
-extern "C" int dfm_pose_iface_energy_chunked(dfm_iface *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_iface_out *out)
-{
-    if (!h) return fail(DFM_E_INVALID, "h is NULL");
-    if (!rot) return fail(DFM_E_INVALID, "rot is NULL");
-    if (!tr) return fail(DFM_E_INVALID, "tr is NULL");
-    if (!out) return fail(DFM_E_INVALID, "out is NULL");
-    if (P < 1) return fail(DFM_E_INVALID, "need P >= 1");
-    if (chunk_poses < 0) return fail(DFM_E_INVALID, "chunk_poses must be >= 0");
-    DEVICE_SCOPE(h->device);
-    PoseCall c;
-    HIPCHK(c.open());
-    const bool per_atom = out->lig_vdw_q || out->lig_elec_q;
-    // the call's chunk, else the default: without per-atom output a chunk is bounded by the launch alone
-    const int Pc = std::min(P, chunk_poses > 0 ? std::min(chunk_poses, IFACE_MAX_CHUNK) : (per_atom ? h->default_chunk : IFACE_MAX_CHUNK));
-    const size_t Al = (size_t)h->Al;
-    PoseChunks ch{c, rot, tr};
-    int64_t *d_tot = nullptr, *d_lv = nullptr, *d_le = nullptr;
-    HIPCHK(ch.open(Pc));
-    HIPCHK(c.tmp.alloc(&d_tot, (size_t)Pc * 4));      // rep_q | att_q | elec_q | n_pairs of each pose
-    if (out->lig_vdw_q) HIPCHK(c.tmp.alloc(&d_lv, (size_t)Pc * Al));
-    if (out->lig_elec_q) HIPCHK(c.tmp.alloc(&d_le, (size_t)Pc * Al));
-    const IfaceAtoms at = {h->rec, h->rec_par, h->lig, h->lig_par, h->sphere, h->cell_start, h->lig_index, h->sc, h->Ar, h->Al};
-    std::vector<int64_t> h_tot((size_t)Pc * 4);
-    for (int p0 = 0; p0 < P; p0 += Pc) {
-        const int n = std::min(Pc, P - p0);
-        HIPCHK(ch.upload(p0, n));
-        if (d_lv) HIPCHK(hipMemsetAsync(d_lv, 0, (size_t)n * Al * sizeof(int64_t), c.s));
-        if (d_le) HIPCHK(hipMemsetAsync(d_le, 0, (size_t)n * Al * sizeof(int64_t), c.s));
-        HIPCHK(launch_iface_pose(ch.d_rot, ch.d_tr, n, ch.T, d_tot, c.s));
-        HIPCHK(launch_iface(at, ch.T, n, d_tot, d_lv, d_le, c.s));
-        HIPCHK(ch.kernels_done());
-        HIPCHK(hipMemcpyAsync(h_tot.data(), d_tot, (size_t)n * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
-        if (d_lv) HIPCHK(hipMemcpyAsync(out->lig_vdw_q + (size_t)p0 * Al, d_lv, (size_t)n * Al * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
-        if (d_le) HIPCHK(hipMemcpyAsync(out->lig_elec_q + (size_t)p0 * Al, d_le, (size_t)n * Al * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
-        HIPCHK(ch.finish());
-        for (int p = 0; p < n; ++p) {
-            if (out->rep_q) out->rep_q[p0 + p] = h_tot[(size_t)p * 4];
-            if (out->att_q) out->att_q[p0 + p] = h_tot[(size_t)p * 4 + 1];
-            if (out->elec_q) out->elec_q[p0 + p] = h_tot[(size_t)p * 4 + 2];
-            if (out->n_pairs) out->n_pairs[p0 + p] = h_tot[(size_t)p * 4 + 3];
-        }
-    }
-    set_last_ms(MS_IFACE, ch.copy_ms, ch.kernel_ms);
-    return DFM_OK;
-}
-
-extern "C" int dfm_pose_iface_energy(dfm_iface *h, int P, const float *rot, const float *tr, dfm_iface_out *out)
-{
-    return dfm_pose_iface_energy_chunked(h, P, rot, tr, 0, out);
-}
-
-extern "C" int dfm_iface_last_timing(double *copy_ms, double *kernel_ms)
-{
-    return last_timing(MS_IFACE, copy_ms, kernel_ms);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Residue contacts (kernels_rescon.hip).  A dfm_rescon holds what the two atom sets, their residues, the classes, the cutoff and the
-// rotation centre fix - the receptor's grid of cells of the cutoff, the ligand in blocks of 64 neighbours, each atom's residue index in
-// its float4, the receptor's class masks - and is read-only after creation; every dfm_pose_rescon call owns its stream, its bitmap
-// and its other temporaries.
-struct dfm_rescon {
-    int device = 0, Ar = 0, Al = 0, Rr = 0, Lr = 0, W = 0, n_cells = 0, max_cell_atoms = 0, default_chunk = 0;
-    float cell_edge = 0.f;
-    DevPool pool;      // unbound: released under a device-wide wait, like a model's
-    float *rec = nullptr, *lig = nullptr, *sphere = nullptr;
-    int32_t *cell_start = nullptr, *lig_class = nullptr;
-    uint32_t *class_mask = nullptr;
-    ResconConst sc = {};
-};
-
-// zeroing the bitmap, k_rescon_pose + k_rescon, k_rescon_finish of this thread's last dfm_pose_rescon, summed over its chunks
-static thread_local double g_rescon_phase_ms[3] = {};
-
-extern "C" void dfm_rescon_destroy(dfm_rescon *h)
-{
-    if (!h) return;
-    DeviceScope ds(h->device);
-    h->pool.release();
-    delete h;
-}
-
-extern "C" dfm_rescon *dfm_rescon_create(dfm_model *m, int Ar, const float *rec_atoms, const int32_t *rec_res, int Rr, const uint8_t *rec_class,
-                                         int Al, const float *lig_atoms, const int32_t *lig_res, int Lr, const uint8_t *lig_class,
-                                         const float center[3], float cutoff)
-{
-    auto bad = [](int code, const std::string &msg) -> dfm_rescon * { (void)fail(code, msg); return nullptr; };
-    if (!m) return bad(DFM_E_INVALID, "m is NULL");
-    if (const std::string msg = check_atom_sets(Ar, rec_atoms, Al, lig_atoms, center); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    if (const std::string msg = check_rescon_chain("rec", Ar, rec_res, Rr, rec_class); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    if (const std::string msg = check_rescon_chain("lig", Al, lig_res, Lr, lig_class); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    if (const std::string msg = check_rescon_cutoff(cutoff); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    // the receptor's grid: origin = the bounding box's low corner, edge = the cutoff
-    CellGrid gr;
-    if (!build_cell_grid(Ar, rec_atoms, (double)cutoff, gr))
-        return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells of the cutoff");
-    double maxabs = 0.0;
-    for (int k = 0; k < 3; ++k) maxabs = std::max(maxabs, std::max(std::fabs(gr.lo[k]), std::fabs(gr.hi[k])));
-    maxabs += 2.0 * (double)cutoff + 1.0;
-    // the fp32 reject threshold (dfm_posewalk.h): cutoff * 1.0001 + slack
-    const float thr = cutoff * 1.0001f + pose_slack(maxabs);
-    ResconConst sc = {};
-    sc.g = walk_grid(gr, (double)cutoff, (double)thr, center);
-    sc.cutoff = (double)cutoff;
-    sc.reject2 = thr * thr;
-    double llo[3] = {(double)lig_atoms[0], (double)lig_atoms[1], (double)lig_atoms[2]};
-    for (int i = 1; i < Al; ++i)
-        for (int k = 0; k < 3; ++k) llo[k] = std::min(llo[k], (double)lig_atoms[(size_t)i * 3 + k]);
-    const LigandBlocks lb = build_ligand_blocks(Al, lig_atoms, llo, sc.g.edge, sc.g.center);
-    if (!lb.finite) return bad(DFM_E_INVALID, "lig_atoms / center: the ligand's extent about the centre overflows fp32");
-    const std::vector<float> rec4 = gather4_res(gr.order, rec_atoms, rec_res), lig4 = gather4_res(lb.index, lig_atoms, lig_res);
-    const std::vector<uint32_t> masks = rescon_class_masks(Rr, rec_class);
-    const std::vector<int32_t> lcls(lig_class, lig_class + Lr);
-    DeviceScope ds(m->device);
-    if (ds.err != hipSuccess) return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err));
-    dfm_rescon *h = new dfm_rescon;
-    h->device = m->device; h->Ar = Ar; h->Al = Al; h->Rr = Rr; h->Lr = Lr; h->W = rescon_words(Rr); h->sc = sc;
-    h->n_cells = sc.g.nx * sc.g.ny * sc.g.nz; h->max_cell_atoms = gr.max_cell; h->cell_edge = cutoff;
-    h->default_chunk = rescon_chunk_poses(Lr, Rr);
-    hipError_t e = hipSuccess;
-    {
-        PoseCall c;
-        e = c.open();
-        if (e == hipSuccess) e = h->pool.upload_async(&h->rec, rec4.data(), rec4.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->cell_start, gr.start.data(), gr.start.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->lig, lig4.data(), lig4.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->sphere, lb.sphere.data(), lb.sphere.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->class_mask, masks.data(), masks.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->lig_class, lcls.data(), lcls.size(), c.s);
-        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
-    }      // the call's stream has drained: the host vectors it read may go
-    if (e != hipSuccess) {
-        h->pool.release();
-        delete h;
-        return bad(e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP, std::string("dfm_rescon_create: ") + hipGetErrorString(e));
-    }
-    return h;
-}
-
-extern "C" int dfm_rescon_info(const dfm_rescon *h, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge, int32_t *row_words,
-                               int32_t *chunk_poses)
-{
-    if (!h) return fail(DFM_E_INVALID, "NULL argument");
-    if (n_cells) *n_cells = h->n_cells;
-    if (max_cell_atoms) *max_cell_atoms = h->max_cell_atoms;
-    if (cell_edge) *cell_edge = h->cell_edge;
-    if (row_words) *row_words = h->W;
-    if (chunk_poses) *chunk_poses = h->default_chunk;
-    return DFM_OK;
-}
-
-extern "C" int dfm_pose_rescon_chunked(dfm_rescon *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_rescon_out *out)
-{
-    if (!h) return fail(DFM_E_INVALID, "h is NULL");
-    if (!rot) return fail(DFM_E_INVALID, "rot is NULL");
-    if (!tr) return fail(DFM_E_INVALID, "tr is NULL");
-    if (!out) return fail(DFM_E_INVALID, "out is NULL");
-    if (P < 1 || P > RESCON_MAX_POSES) return fail(DFM_E_INVALID, "need 1 <= P <= " + std::to_string(RESCON_MAX_POSES));
-    if (chunk_poses < 0) return fail(DFM_E_INVALID, "chunk_poses must be >= 0");
-    DEVICE_SCOPE(h->device);
-    PoseCall c;
-    HIPCHK(c.open());
-    // the call's chunk, else as many poses as fill RESCON_SCRATCH_BYTES of bitmap
-    const int Pc = std::min(P, chunk_poses > 0 ? std::min(chunk_poses, RESCON_MAX_CHUNK) : h->default_chunk);
-    const size_t Rr = (size_t)h->Rr, Lr = (size_t)h->Lr, row = Lr * (size_t)h->W;
-    PoseChunks ch{c, rot, tr};
-    uint32_t *d_bits = nullptr;
-    int32_t *d_tot = nullptr, *d_rd = nullptr, *d_ld = nullptr;
-    HIPCHK(ch.open(Pc));
-    HIPCHK(c.tmp.alloc(&d_bits, (size_t)Pc * row));
-    HIPCHK(c.tmp.alloc(&d_tot, (size_t)Pc * 9));
-    if (out->rec_degree) HIPCHK(c.tmp.alloc(&d_rd, (size_t)Pc * Rr));
-    if (out->lig_degree) HIPCHK(c.tmp.alloc(&d_ld, (size_t)Pc * Lr));
-    const ResconAtoms at = {h->rec, h->lig, h->sphere, h->cell_start, h->lig_class, h->class_mask, h->sc, h->Ar, h->Al, h->Rr, h->Lr, h->W};
-    std::vector<int32_t> h_tot((size_t)Pc * 9);
-    // the call's own events split the kernel time into its three phases: ev[1] .. zeroed .. c.ev[3] (walked) .. ev[2]
-    struct Ev {
-        hipEvent_t e = nullptr;
-        ~Ev() { if (e) (void)hipEventDestroy(e); }
-    } zeroed;
-    HIPCHK(hipEventCreate(&zeroed.e));
-    double phase[3] = {0.0, 0.0, 0.0};
-    for (int p0 = 0; p0 < P; p0 += Pc) {
-        const int n = std::min(Pc, P - p0);
-        HIPCHK(ch.upload(p0, n));
-        HIPCHK(hipMemsetAsync(d_bits, 0, (size_t)n * row * sizeof(uint32_t), c.s));
-        HIPCHK(hipEventRecord(zeroed.e, c.s));
-        HIPCHK(launch_rescon_pose(ch.d_rot, ch.d_tr, n, ch.T, c.s));
-        HIPCHK(launch_rescon(at, ch.T, n, d_bits, c.s));
-        HIPCHK(hipEventRecord(c.ev[3], c.s));
-        HIPCHK(launch_rescon_finish(at, d_bits, n, d_tot, d_rd, d_ld, c.s));
-        HIPCHK(ch.kernels_done());
-        HIPCHK(hipMemcpyAsync(h_tot.data(), d_tot, (size_t)n * 9 * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        if (d_rd) HIPCHK(hipMemcpyAsync(out->rec_degree + (size_t)p0 * Rr, d_rd, (size_t)n * Rr * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        if (d_ld) HIPCHK(hipMemcpyAsync(out->lig_degree + (size_t)p0 * Lr, d_ld, (size_t)n * Lr * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        if (out->contact_bits)
-            HIPCHK(hipMemcpyAsync(out->contact_bits + (size_t)p0 * row, d_bits, (size_t)n * row * sizeof(uint32_t), hipMemcpyDeviceToHost, c.s));
-        HIPCHK(ch.finish());
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c.ev[1], zeroed.e) == hipSuccess) phase[0] += ms;
-        if (hipEventElapsedTime(&ms, zeroed.e, c.ev[3]) == hipSuccess) phase[1] += ms;
-        if (hipEventElapsedTime(&ms, c.ev[3], c.ev[2]) == hipSuccess) phase[2] += ms;
-        for (int p = 0; p < n; ++p) {
-            const int32_t *t = h_tot.data() + (size_t)p * 9;
-            if (out->ic) std::memcpy(out->ic + (size_t)(p0 + p) * 6, t, 6 * sizeof(int32_t));
-            if (out->n_pairs) out->n_pairs[p0 + p] = t[6];
-            if (out->n_rec_res) out->n_rec_res[p0 + p] = t[7];
-            if (out->n_lig_res) out->n_lig_res[p0 + p] = t[8];
-        }
-    }
-    set_last_ms(MS_RESCON, ch.copy_ms, ch.kernel_ms);
-    for (int k = 0; k < 3; ++k) g_rescon_phase_ms[k] = phase[k];
-    return DFM_OK;
-}
-
-extern "C" int dfm_pose_rescon(dfm_rescon *h, int P, const float *rot, const float *tr, dfm_rescon_out *out)
-{
-    return dfm_pose_rescon_chunked(h, P, rot, tr, 0, out);
-}
-
-extern "C" int dfm_rescon_last_timing(double *copy_ms, double *kernel_ms)
-{
-    return last_timing(MS_RESCON, copy_ms, kernel_ms);
-}
-
-extern "C" int dfm_rescon_last_phases(double *zero_ms, double *walk_ms, double *finish_ms)
-{
-    if (!zero_ms || !walk_ms || !finish_ms) return fail(DFM_E_INVALID, "NULL argument");
-    *zero_ms = g_rescon_phase_ms[0];
-    *walk_ms = g_rescon_phase_ms[1];
-    *finish_ms = g_rescon_phase_ms[2];
-    return DFM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Hydrogen bonds and salt bridges (kernels_hbond.hip).  A dfm_hbond holds what the polar atoms of the two chains, their antecedents,
-// roles and residues, the scalars and the rotation centre fix - the receptor's grid of cells of the larger cutoff with each atom's
-// antecedent beside it, the ligand in blocks of 64 neighbours, each atom's role and charged-residue number in its float4 - and is
-// read-only after creation; every dfm_pose_hbonds call owns its stream, its bitmap and its other temporaries.
-struct dfm_hbond {
-    int device = 0, Nr = 0, Nl = 0, Rc = 0, Lc = 0, Wc = 0, n_cells = 0, max_cell_atoms = 0, default_chunk = 0;
-    float cell_edge = 0.f;
-    DevPool pool;      // unbound: released under a device-wide wait, like a model's
-    float *rec = nullptr, *rec_ante = nullptr, *lig = nullptr, *lig_ante = nullptr, *sphere = nullptr;
-    int32_t *cell_start = nullptr, *rec_index = nullptr, *lig_index = nullptr;
-    HbondConst sc = {};
-};
-
-// the memsets, k_hbond_pose + k_hbond, k_hbond_finish of this thread's last dfm_pose_hbonds, summed over its chunks
-static thread_local double g_hbond_phase_ms[3] = {};
-
-extern "C" void dfm_hbond_destroy(dfm_hbond *h)
-{
-    if (!h) return;
-    DeviceScope ds(h->device);
-    h->pool.release();
-    delete h;
-}
-
-extern "C" dfm_hbond *dfm_hbond_create(dfm_model *m, int Nr, const float *rec_xyz, const float *rec_ante, const uint8_t *rec_role,
-                                       const int32_t *rec_res, int n_rec_res, int Nl, const float *lig_xyz, const float *lig_ante,
-                                       const uint8_t *lig_role, const int32_t *lig_res, int n_lig_res, const float center[3], float hb_cutoff,
-                                       double min_cos2, float salt_cutoff, int *status)
-{
-    auto bad = [status](int code, const std::string &msg) -> dfm_hbond * {
-        (void)fail(code, msg);
-        if (status) *status = code;
-        return nullptr;
-    };
-    if (status) *status = DFM_OK;
-    if (!m) return bad(DFM_E_INVALID, "m is NULL");
-    if (const std::string msg = check_atom_sets(Nr, rec_xyz, Nl, lig_xyz, center); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    if (const std::string msg = check_hbond_chain("rec", Nr, rec_ante, rec_role, rec_res, n_rec_res); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    if (const std::string msg = check_hbond_chain("lig", Nl, lig_ante, lig_role, lig_res, n_lig_res); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    if (const std::string msg = check_hbond_scalars(hb_cutoff, min_cos2, salt_cutoff); !msg.empty()) return bad(DFM_E_INVALID, msg);
-    // the receptor's grid: origin = the bounding box's low corner, edge = the larger cutoff
-    const float reach = std::max(hb_cutoff, salt_cutoff);
-    CellGrid gr;
-    if (!build_cell_grid(Nr, rec_xyz, (double)reach, gr))
-        return bad(DFM_E_INVALID, "the receptor's bounding box needs more than 2^24 cells of the larger cutoff");
-    double maxabs = 0.0;
-    for (int k = 0; k < 3; ++k) maxabs = std::max(maxabs, std::max(std::fabs(gr.lo[k]), std::fabs(gr.hi[k])));
-    maxabs += 2.0 * (double)reach + 1.0;
-    // the fp32 reject threshold (dfm_posewalk.h): reach * 1.0001 + slack
-    const float thr = reach * 1.0001f + pose_slack(maxabs);
-    HbondConst sc = {};
-    sc.g = walk_grid(gr, (double)reach, (double)thr, center);
-    sc.hb2 = (double)hb_cutoff * (double)hb_cutoff;
-    sc.salt2 = (double)salt_cutoff * (double)salt_cutoff;
-    sc.c2 = min_cos2;
-    sc.reject2 = thr * thr;
-    double llo[3] = {(double)lig_xyz[0], (double)lig_xyz[1], (double)lig_xyz[2]};
-    for (int i = 1; i < Nl; ++i)
-        for (int k = 0; k < 3; ++k) llo[k] = std::min(llo[k], (double)lig_xyz[(size_t)i * 3 + k]);
-    const LigandBlocks lb = build_ligand_blocks(Nl, lig_xyz, llo, sc.g.edge, sc.g.center);
-    if (!lb.finite) return bad(DFM_E_INVALID, "lig_xyz / center: the ligand's extent about the centre overflows fp32");
-    std::vector<int32_t> rcomp, lcomp;
-    const int Rc = hbond_charged_residues(Nr, rec_role, rec_res, n_rec_res, rcomp);
-    const int Lc = hbond_charged_residues(Nl, lig_role, lig_res, n_lig_res, lcomp);
-    const std::vector<float> rec4 = gather4_hbond(gr.order, rec_xyz, rec_role, rec_res, rcomp), ra4 = gather4(gr.order, rec_ante, nullptr);
-    const std::vector<float> lig4 = gather4_hbond(lb.index, lig_xyz, lig_role, lig_res, lcomp), la4 = gather4(lb.index, lig_ante, nullptr);
-    DeviceScope ds(m->device);
-    if (ds.err != hipSuccess) return bad(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err));
-    dfm_hbond *h = new dfm_hbond;
-    h->device = m->device; h->Nr = Nr; h->Nl = Nl; h->Rc = Rc; h->Lc = Lc; h->Wc = rescon_words(Rc); h->sc = sc;
-    h->n_cells = sc.g.nx * sc.g.ny * sc.g.nz; h->max_cell_atoms = gr.max_cell; h->cell_edge = reach;
-    h->default_chunk = hbond_chunk_poses(Lc, Rc);
-    hipError_t e = hipSuccess;
-    {
-        PoseCall c;
-        e = c.open();
-        if (e == hipSuccess) e = h->pool.upload_async(&h->rec, rec4.data(), rec4.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->rec_ante, ra4.data(), ra4.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->cell_start, gr.start.data(), gr.start.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->rec_index, gr.order.data(), gr.order.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->lig, lig4.data(), lig4.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->lig_ante, la4.data(), la4.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->lig_index, lb.index.data(), lb.index.size(), c.s);
-        if (e == hipSuccess) e = h->pool.upload_async(&h->sphere, lb.sphere.data(), lb.sphere.size(), c.s);
-        if (e == hipSuccess) e = hipStreamSynchronize(c.s);
-    }      // the call's stream has drained: the host vectors it read may go
-    if (e != hipSuccess) {
-        h->pool.release();
-        delete h;
-        return bad(e == hipErrorOutOfMemory ? DFM_E_OOM : DFM_E_HIP, std::string("dfm_hbond_create: ") + hipGetErrorString(e));
-    }
-    return h;
-}
-
-extern "C" int dfm_hbond_info(const dfm_hbond *h, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge, int32_t *n_rec_charged,
-                              int32_t *n_lig_charged, int32_t *chunk_poses)
-{
-    if (!h) return fail(DFM_E_INVALID, "NULL argument");
-    if (n_cells) *n_cells = h->n_cells;
-    if (max_cell_atoms) *max_cell_atoms = h->max_cell_atoms;
-    if (cell_edge) *cell_edge = h->cell_edge;
-    if (n_rec_charged) *n_rec_charged = h->Rc;
-    if (n_lig_charged) *n_lig_charged = h->Lc;
-    if (chunk_poses) *chunk_poses = h->default_chunk;
-    return DFM_OK;
-}
-
-extern "C" int dfm_pose_hbonds_chunked(dfm_hbond *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_hbond_out *out)
-{
-    if (!h) return fail(DFM_E_INVALID, "h is NULL");
-    if (!rot) return fail(DFM_E_INVALID, "rot is NULL");
-    if (!tr) return fail(DFM_E_INVALID, "tr is NULL");
-    if (!out) return fail(DFM_E_INVALID, "out is NULL");
-    if (P < 1 || P > HBOND_MAX_POSES) return fail(DFM_E_INVALID, "need 1 <= P <= " + std::to_string(HBOND_MAX_POSES));
-    if (chunk_poses < 0) return fail(DFM_E_INVALID, "chunk_poses must be >= 0");
-    DEVICE_SCOPE(h->device);
-    PoseCall c;
-    HIPCHK(c.open());
-    // the call's chunk, else as many poses as fill RESCON_SCRATCH_BYTES of bitmap
-    const int Pc = std::min(P, chunk_poses > 0 ? std::min(chunk_poses, RESCON_MAX_CHUNK) : h->default_chunk);
-    const size_t Nr = (size_t)h->Nr, Nl = (size_t)h->Nl, words = (size_t)h->Lc * (size_t)h->Wc;
-    PoseChunks ch{c, rot, tr};
-    uint32_t *d_bits = nullptr;
-    int32_t *d_tot = nullptr;
-    // the per-atom outputs asked for, in one block so that one memset zeroes them: rec_hb, rec_sb [Pc][Nr], lig_hb, lig_sb [Pc][Nl]
-    int32_t *d_atom = nullptr, *d_rh = nullptr, *d_rs = nullptr, *d_lh = nullptr, *d_ls = nullptr;
-    const size_t n_atom = (size_t)Pc * ((out->rec_hb ? Nr : 0) + (out->rec_sb ? Nr : 0) + (out->lig_hb ? Nl : 0) + (out->lig_sb ? Nl : 0));
-    HIPCHK(ch.open(Pc));
-    HIPCHK(c.tmp.alloc(&d_bits, std::max<size_t>(1, (size_t)Pc * words)));      // never empty: the kernel forms a row pointer into it
-    HIPCHK(c.tmp.alloc(&d_tot, (size_t)Pc * 5));
-    if (n_atom) {
-        HIPCHK(c.tmp.alloc(&d_atom, n_atom));
-        int32_t *q = d_atom;
-        if (out->rec_hb) { d_rh = q; q += (size_t)Pc * Nr; }
-        if (out->rec_sb) { d_rs = q; q += (size_t)Pc * Nr; }
-        if (out->lig_hb) { d_lh = q; q += (size_t)Pc * Nl; }
-        if (out->lig_sb) { d_ls = q; q += (size_t)Pc * Nl; }
-    }
-    const HbondAtoms at = {h->rec, h->rec_ante, h->lig, h->lig_ante, h->sphere, h->cell_start, h->rec_index, h->lig_index, h->sc,
-                           h->Nr, h->Nl, h->Rc, h->Lc, h->Wc};
-    std::vector<int32_t> h_tot((size_t)Pc * 5);
-    // the call's own events split the kernel time into its three phases: ev[1] .. zeroed .. c.ev[3] (walked) .. ev[2]
-    struct Ev {
-        hipEvent_t e = nullptr;
-        ~Ev() { if (e) (void)hipEventDestroy(e); }
-    } zeroed;
-    HIPCHK(hipEventCreate(&zeroed.e));
-    double phase[3] = {0.0, 0.0, 0.0};
-    for (int p0 = 0; p0 < P; p0 += Pc) {
-        const int n = std::min(Pc, P - p0);
-        HIPCHK(ch.upload(p0, n));
-        if (words) HIPCHK(hipMemsetAsync(d_bits, 0, (size_t)n * words * sizeof(uint32_t), c.s));
-        if (n_atom) HIPCHK(hipMemsetAsync(d_atom, 0, n_atom * sizeof(int32_t), c.s));
-        HIPCHK(hipEventRecord(zeroed.e, c.s));
-        HIPCHK(launch_hbond_pose(ch.d_rot, ch.d_tr, n, ch.T, d_tot, c.s));
-        HIPCHK(launch_hbond(at, ch.T, n, d_tot, d_bits, d_rh, d_rs, d_lh, d_ls, c.s));
-        HIPCHK(hipEventRecord(c.ev[3], c.s));
-        HIPCHK(launch_hbond_finish(at, d_bits, n, d_tot, c.s));
-        HIPCHK(ch.kernels_done());
-        HIPCHK(hipMemcpyAsync(h_tot.data(), d_tot, (size_t)n * 5 * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        if (d_rh) HIPCHK(hipMemcpyAsync(out->rec_hb + (size_t)p0 * Nr, d_rh, (size_t)n * Nr * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        if (d_rs) HIPCHK(hipMemcpyAsync(out->rec_sb + (size_t)p0 * Nr, d_rs, (size_t)n * Nr * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        if (d_lh) HIPCHK(hipMemcpyAsync(out->lig_hb + (size_t)p0 * Nl, d_lh, (size_t)n * Nl * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        if (d_ls) HIPCHK(hipMemcpyAsync(out->lig_sb + (size_t)p0 * Nl, d_ls, (size_t)n * Nl * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-        HIPCHK(ch.finish());
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c.ev[1], zeroed.e) == hipSuccess) phase[0] += ms;
-        if (hipEventElapsedTime(&ms, zeroed.e, c.ev[3]) == hipSuccess) phase[1] += ms;
-        if (hipEventElapsedTime(&ms, c.ev[3], c.ev[2]) == hipSuccess) phase[2] += ms;
-        for (int p = 0; p < n; ++p) {
-            const int32_t *t = h_tot.data() + (size_t)p * 5;
-            if (out->n_hbond) out->n_hbond[p0 + p] = (t[0] + t[1]) + t[2];
-            if (out->hb_kind) std::memcpy(out->hb_kind + (size_t)(p0 + p) * 3, t, 3 * sizeof(int32_t));
-            if (out->n_salt_atoms) out->n_salt_atoms[p0 + p] = t[3];
-            if (out->n_salt) out->n_salt[p0 + p] = t[4];
-        }
-    }
-    set_last_ms(MS_HBOND, ch.copy_ms, ch.kernel_ms);
-    for (int k = 0; k < 3; ++k) g_hbond_phase_ms[k] = phase[k];
-    return DFM_OK;
-}
-
-extern "C" int dfm_pose_hbonds(dfm_hbond *h, int P, const float *rot, const float *tr, dfm_hbond_out *out)
-{
-    return dfm_pose_hbonds_chunked(h, P, rot, tr, 0, out);
-}
-
-extern "C" int dfm_hbond_last_timing(double *copy_ms, double *kernel_ms)
-{
-    return last_timing(MS_HBOND, copy_ms, kernel_ms);
-}
-
-extern "C" int dfm_hbond_last_phases(double *zero_ms, double *walk_ms, double *finish_ms)
-{
-    if (!zero_ms || !walk_ms || !finish_ms) return fail(DFM_E_INVALID, "NULL argument");
-    *zero_ms = g_hbond_phase_ms[0];
-    *walk_ms = g_hbond_phase_ms[1];
-    *finish_ms = g_hbond_phase_ms[2];
     return DFM_OK;
 }
 

@@ -1,4 +1,4 @@
-// dfm_guardscan.h - the scan of one guard band of the diagnostic allocator (api.hip: DFM_ALLOC_GUARD), in plain C++: the library runs
+// dfm_guardscan.h - the scan of one guard band of the diagnostic allocator (dfm_host.h: DFM_ALLOC_GUARD), in plain C++: the library runs
 // it over the host copy of every band at release, tests/guard_scan_main.cpp calls it without a GPU.
 #pragma once
 

@@ -1,6 +1,6 @@
-// dfm_poseprep.h - host preparation of the per-pose all-atom calls (api.hip: dfm_atoms_create, dfm_surface_create, dfm_iface_create,
+// dfm_poseprep.h - host preparation of the per-pose all-atom calls (api_pose.hip: dfm_atoms_create, dfm_surface_create, dfm_iface_create,
 // dfm_rescon_create, dfm_hbond_create): argument checks, the cell grid of a chain, the ligand in blocks of 64 neighbours, the rounding
-// slack, the interface energy's parameter limits and overflow bound, the residue contacts' limits, residue bits, class masks and chunk
+// slack, the frame of the cutoff-based creators, the interface energy's parameter limits and overflow bound, the residue contacts' limits, residue bits, class masks and chunk
 // size, the hydrogen bonds' limits, role bits and charged residues.  Plain C++ without a HIP call, so that tests/test_pose_prep_cpu.py,
 // tests/test_ifenergy_cpu.py, tests/test_affinity_cpu.py and tests/test_hbonds_cpu.py run it under the sanitizers without a GPU.
 #pragma once
@@ -169,7 +169,40 @@ inline LigandBlocks build_ligand_blocks(int Al, const float *lig_atoms, const do
     return lb;
 }
 
-// Interface energy (api.hip: dfm_iface_create; kernels_iface.hip).  The limits of the per-atom parameters [n] of one chain (`who`:
+// The frame of a rigid-pose creator whose reach is a cutoff (dfm_atoms_create, dfm_iface_create, dfm_rescon_create, dfm_hbond_create):
+// the receptor's grid of cells of the reach, the grid as the kernels take it, the fp32 reject threshold thr = reach * 1.0001 + slack
+// (dfm_posewalk.h) with reject2 = thr^2, the ligand's low corner and the ligand in blocks.  maxabs = the largest coordinate of the
+// receptor's box + 2 reach + 1.  These numbers decide which pairs the fp32 early reject may skip.
+struct PoseFrame {
+    CellGrid gr;
+    WalkGrid g = {};
+    float thr = 0.f, reject2 = 0.f;
+    double lig_lo[3] = {0.0, 0.0, 0.0};
+    LigandBlocks lb;
+};
+// `reach_name` names the reach in the refusal ("contact cutoff", "cutoff", "larger cutoff"), `lig_name` the ligand's argument; returns
+// the message of the first thing that is wrong, or ""
+inline std::string build_pose_frame(int Ar, const float *rec_atoms, int Al, const float *lig_atoms, const float center[3], float reach,
+                                    const char *reach_name, PoseFrame &f, const char *lig_name = "lig_atoms")
+{
+    if (!build_cell_grid(Ar, rec_atoms, (double)reach, f.gr))
+        return std::string("the receptor's bounding box needs more than 2^24 cells of the ") + reach_name;
+    double maxabs = 0.0;
+    for (int k = 0; k < 3; ++k) maxabs = std::max(maxabs, std::max(std::fabs(f.gr.lo[k]), std::fabs(f.gr.hi[k])));
+    maxabs += 2.0 * (double)reach + 1.0;
+    f.thr = reach * 1.0001f + pose_slack(maxabs);
+    f.g = walk_grid(f.gr, (double)reach, (double)f.thr, center);
+    f.reject2 = f.thr * f.thr;
+    if (!std::isfinite(f.reject2)) return "cutoffs must be finite and > 0";
+    for (int k = 0; k < 3; ++k) f.lig_lo[k] = (double)lig_atoms[k];
+    for (int i = 1; i < Al; ++i)
+        for (int k = 0; k < 3; ++k) f.lig_lo[k] = std::min(f.lig_lo[k], (double)lig_atoms[(size_t)i * 3 + k]);
+    f.lb = build_ligand_blocks(Al, lig_atoms, f.lig_lo, f.g.edge, f.g.center);
+    if (!f.lb.finite) return std::string(lig_name) + " / center: the ligand's extent about the centre overflows fp32";
+    return "";
+}
+
+// Interface energy (api_pose.hip: dfm_iface_create; kernels_iface.hip).  The limits of the per-atom parameters [n] of one chain (`who`:
 // "rec" or "lig") and of the call's scalars: the message of the first one that is wrong, or "".
 inline std::string check_iface_atoms(const char *who, int n, const float *rmin_half, const float *sqrt_eps, const float *charge)
 {
@@ -246,7 +279,7 @@ inline std::vector<float> gather_iface(const std::vector<int32_t> &order, const 
     return v;
 }
 
-// Residue contacts (api.hip: dfm_rescon_create; kernels_rescon.hip).  The limits: residues per chain, poses per call, and the bytes of
+// Residue contacts (api_pose.hip: dfm_rescon_create; kernels_rescon.hip).  The limits: residues per chain, poses per call, and the bytes of
 // bitmap [poses of a chunk][Lr][W] a call may hold, which fix the chunk.
 constexpr int RESCON_MAX_RES = 4096, RESCON_MAX_POSES = 65536, RESCON_MAX_CHUNK = 32768;
 constexpr size_t RESCON_SCRATCH_BYTES = (size_t)64 << 20;
@@ -304,7 +337,7 @@ inline int rescon_chunk_poses(int Lr, int Rr, size_t budget = RESCON_SCRATCH_BYT
     return (int)std::min<size_t>((size_t)RESCON_MAX_CHUNK, std::max<size_t>(1, budget / per_pose));
 }
 
-// Hydrogen bonds and salt bridges (api.hip: dfm_hbond_create; kernels_hbond.hip).  The atoms of a chain are its POLAR atoms only.  The
+// Hydrogen bonds and salt bridges (api_pose.hip: dfm_hbond_create; kernels_hbond.hip).  The atoms of a chain are its POLAR atoms only.  The
 // limits: residues per chain, poses per call, the largest cutoff (the role bits: dfm_walkgrid.h).
 constexpr int HBOND_MAX_RES = RESCON_MAX_RES, HBOND_MAX_POSES = RESCON_MAX_POSES;
 constexpr float HBOND_MAX_CUTOFF = 8.f;

@@ -275,6 +275,26 @@ class _Handle:
             pass
 
 
+def _center(center):
+    """center as float32 [3]: the rotation centre of a rigid-pose handle."""
+    cen = _f32(center).reshape(-1)
+    if cen.size != 3:
+        raise ValueError(f"center must have 3 entries, got {np.shape(center)}")
+    return cen
+
+
+def _grid_info(n, mx, e):
+    """The first three fields of every rigid-pose handle's info(): the receptor's grid."""
+    return {"n_cells": n.value, "max_cell_atoms": mx.value, "cell_edge": e.value}
+
+
+def _last_ms(getter, k):
+    """The k millisecond figures that `getter` (a dfm_*_last_timing or dfm_*_last_phases) returns for this thread's last call."""
+    v = [C.c_double(0) for _ in range(k)]
+    L.check(getattr(L.lib(), getter)(*(C.byref(x) for x in v)), getter)
+    return tuple(x.value for x in v)
+
+
 def _rigid_poses(rot, tr):
     """rot, tr as float32 [P,3] and P: the poses of Atoms.sterics and Surface.bsa."""
     r, t = _f32(rot).reshape(-1, 3), _f32(tr).reshape(-1, 3)
@@ -337,9 +357,7 @@ class Atoms(_Handle):
     _kind = "atoms"
 
     def __init__(self, model: Model, rec_atoms, lig_atoms, center, clash_cutoff=3.0, contact_cutoff=5.0):
-        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _f32(center).reshape(-1)
-        if cen.size != 3:
-            raise ValueError(f"center must have 3 entries, got {np.shape(center)}")
+        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _center(center)
         self.model, self.Ar, self.Al = model, ra.shape[0], la.shape[0]
         self.clash_cutoff, self.contact_cutoff = float(np.float32(clash_cutoff)), float(np.float32(contact_cutoff))
         prm = L.StericsParamsC(float(clash_cutoff), float(contact_cutoff), 0)
@@ -350,7 +368,7 @@ class Atoms(_Handle):
         """{n_cells, max_cell_atoms, cell_edge} of the receptor's grid (dfm_atoms_info)."""
         n, mx, e = C.c_int32(0), C.c_int32(0), C.c_float(0)
         L.check(L.lib().dfm_atoms_info(self._h, C.byref(n), C.byref(mx), C.byref(e)), "dfm_atoms_info")
-        return {"n_cells": n.value, "max_cell_atoms": mx.value, "cell_edge": e.value}
+        return _grid_info(n, mx, e)
 
     def sterics(self, rot, tr, per_atom=False, chunk_poses=0, members=None):
         """Clash / contact screen of P poses (dfm_pose_sterics; the float64 definition is sterics.sterics): rot [P,3] axis-angle and tr
@@ -378,10 +396,8 @@ class Surface(_Handle):
 
     def __init__(self, model: Model, rec_atoms, rec_radius, lig_atoms, lig_radius, center, probe=1.4, points=128):
         from . import surface as SF
-        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _f32(center).reshape(-1)
+        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _center(center)
         rr, lr = _f32(rec_radius).reshape(-1), _f32(lig_radius).reshape(-1)
-        if cen.size != 3:
-            raise ValueError(f"center must have 3 entries, got {np.shape(center)}")
         if rr.size != ra.shape[0] or lr.size != la.shape[0]:
             raise ValueError(f"one radius per atom: {ra.shape[0]} / {rr.size} receptor, {la.shape[0]} / {lr.size} ligand")
         self.model, self.Ar, self.Al = model, ra.shape[0], la.shape[0]
@@ -402,7 +418,7 @@ class Surface(_Handle):
         L.check(L.lib().dfm_surface_info(self._h, C.byref(sr), C.byref(sl), _p(re, L.I32P), _p(le, L.I32P), C.byref(nc), _p(cr), C.byref(n),
                                          C.byref(mx), C.byref(e)), "dfm_surface_info")
         return {"sasa_rec": sr.value, "sasa_lig": sl.value, "rec_exposed": re, "lig_exposed": le, "class_radius": cr[:nc.value].copy(),
-                "n_cells": n.value, "max_cell_atoms": mx.value, "cell_edge": e.value}
+                **_grid_info(n, mx, e)}
 
     def bsa(self, rot, tr, per_atom=False, chunk_poses=0):
         """Buried surface of P poses (dfm_pose_bsa; the float64 definition is surface.bsa): rot [P,3] axis-angle and tr [P,3] as
@@ -431,10 +447,8 @@ class Interface(_Handle):
 
     def __init__(self, model: Model, rec_atoms, rec_params, lig_atoms, lig_params, center, cutoff=8.0, soft=0.6, elec_min_dist=3.0,
                  dielectric_slope=4.0):
-        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _f32(center).reshape(-1)
+        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _center(center)
         rp, lp = _f32(rec_params), _f32(lig_params)
-        if cen.size != 3:
-            raise ValueError(f"center must have 3 entries, got {np.shape(center)}")
         if rp.shape != (ra.shape[0], 3) or lp.shape != (la.shape[0], 3):
             raise ValueError(f"one (rmin_half, sqrt_eps, charge) row per atom: receptor {ra.shape[0]} / {rp.shape}, ligand {la.shape[0]} / {lp.shape}")
         self.model, self.Ar, self.Al = model, ra.shape[0], la.shape[0]
@@ -450,7 +464,7 @@ class Interface(_Handle):
         integer sum of a call in quanta (dfm_iface_info)."""
         n, mx, e, b = C.c_int32(0), C.c_int32(0), C.c_float(0), C.c_double(0)
         L.check(L.lib().dfm_iface_info(self._h, C.byref(n), C.byref(mx), C.byref(e), C.byref(b)), "dfm_iface_info")
-        return {"n_cells": n.value, "max_cell_atoms": mx.value, "cell_edge": e.value, "sum_bound_q": b.value}
+        return {**_grid_info(n, mx, e), "sum_bound_q": b.value}
 
     def energy(self, rot, tr, per_atom=False, chunk_poses=0):
         """Interface energy of P poses (dfm_pose_iface_energy; the float64 definition is ifenergy.interface_energy): rot [P,3] axis-angle
@@ -477,9 +491,7 @@ class Contacts(_Handle):
 
     def __init__(self, model: Model, rec_atoms, rec_res, rec_class, lig_atoms, lig_res, lig_class, center, cutoff=5.5):
         from . import affinity as AF
-        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _f32(center).reshape(-1)
-        if cen.size != 3:
-            raise ValueError(f"center must have 3 entries, got {np.shape(center)}")
+        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _center(center)
         rr, rc = AF.check_residues(rec_res, ra.shape[0], rec_class, "rec")
         lr, lc = AF.check_residues(lig_res, la.shape[0], lig_class, "lig")
         rr, rc, lr, lc = (np.ascontiguousarray(a) for a in (rr, rc, lr, lc))
@@ -495,7 +507,7 @@ class Contacts(_Handle):
         holds a bitmap for (dfm_rescon_info)."""
         n, mx, e, w, ch = C.c_int32(0), C.c_int32(0), C.c_float(0), C.c_int32(0), C.c_int32(0)
         L.check(L.lib().dfm_rescon_info(self._h, C.byref(n), C.byref(mx), C.byref(e), C.byref(w), C.byref(ch)), "dfm_rescon_info")
-        return {"n_cells": n.value, "max_cell_atoms": mx.value, "cell_edge": e.value, "row_words": w.value, "chunk_poses": ch.value}
+        return {**_grid_info(n, mx, e), "row_words": w.value, "chunk_poses": ch.value}
 
     def count(self, rot, tr, per_residue=False, bits=False, chunk_poses=0):
         """Residue contacts of P poses (dfm_pose_rescon; the float64 definition is affinity.residue_contacts): rot [P,3] axis-angle and
@@ -524,9 +536,7 @@ class HBonds(_Handle):
 
     def __init__(self, model: Model, rec, lig, center, hb_cutoff=3.5, min_angle=90.0, salt_cutoff=4.0):
         from . import hbonds as HB
-        cen = _f32(center).reshape(-1)
-        if cen.size != 3:
-            raise ValueError(f"center must have 3 entries, got {np.shape(center)}")
+        cen = _center(center)
         self.hb_cutoff, self.salt_cutoff = HB.check_cutoffs(hb_cutoff, salt_cutoff)
         self.min_angle, self.min_cos2 = float(min_angle), HB.min_cos2(min_angle)
         rx, ra, rro, rre, self.n_rec_res = (np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a for a in HB.check_chain(rec, "rec"))
@@ -544,7 +554,7 @@ class HBonds(_Handle):
         anion, and chunk_poses, the poses one chunk of a call holds a bitmap for (dfm_hbond_info)."""
         n, mx, e, rc, lc, ch = C.c_int32(0), C.c_int32(0), C.c_float(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
         L.check(L.lib().dfm_hbond_info(self._h, C.byref(n), C.byref(mx), C.byref(e), C.byref(rc), C.byref(lc), C.byref(ch)), "dfm_hbond_info")
-        return {"n_cells": n.value, "max_cell_atoms": mx.value, "cell_edge": e.value, "n_rec_charged": rc.value, "n_lig_charged": lc.value,
+        return {**_grid_info(n, mx, e), "n_rec_charged": rc.value, "n_lig_charged": lc.value,
                 "chunk_poses": ch.value}
 
     def count(self, rot, tr, per_atom=False, chunk_poses=0):
@@ -567,52 +577,38 @@ class HBonds(_Handle):
 
 def hbond_last_timing():
     """(host-to-device copy ms, kernel ms) of this thread's last HBonds.count call (dfm_hbond_last_timing)."""
-    a, b = C.c_double(0), C.c_double(0)
-    L.check(L.lib().dfm_hbond_last_timing(C.byref(a), C.byref(b)), "dfm_hbond_last_timing")
-    return a.value, b.value
+    return _last_ms("dfm_hbond_last_timing", 2)
 
 
 def hbond_last_phases():
     """(memsets ms, walk ms, finish ms) of this thread's last HBonds.count call: its kernel time by phase (dfm_hbond_last_phases)."""
-    a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
-    L.check(L.lib().dfm_hbond_last_phases(C.byref(a), C.byref(b), C.byref(c)), "dfm_hbond_last_phases")
-    return a.value, b.value, c.value
+    return _last_ms("dfm_hbond_last_phases", 3)
 
 
 def rescon_last_timing():
     """(host-to-device copy ms, kernel ms) of this thread's last Contacts.count call (dfm_rescon_last_timing)."""
-    a, b = C.c_double(0), C.c_double(0)
-    L.check(L.lib().dfm_rescon_last_timing(C.byref(a), C.byref(b)), "dfm_rescon_last_timing")
-    return a.value, b.value
+    return _last_ms("dfm_rescon_last_timing", 2)
 
 
 def rescon_last_phases():
     """(zeroing the bitmap ms, walk ms, finish ms) of this thread's last Contacts.count call: its kernel time by phase
     (dfm_rescon_last_phases)."""
-    a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
-    L.check(L.lib().dfm_rescon_last_phases(C.byref(a), C.byref(b), C.byref(c)), "dfm_rescon_last_phases")
-    return a.value, b.value, c.value
+    return _last_ms("dfm_rescon_last_phases", 3)
 
 
 def iface_last_timing():
     """(host-to-device copy ms, kernel ms) of this thread's last Interface.energy call (dfm_iface_last_timing)."""
-    a, b = C.c_double(0), C.c_double(0)
-    L.check(L.lib().dfm_iface_last_timing(C.byref(a), C.byref(b)), "dfm_iface_last_timing")
-    return a.value, b.value
+    return _last_ms("dfm_iface_last_timing", 2)
 
 
 def bsa_last_timing():
     """(host-to-device copy ms, kernel ms) of this thread's last Surface.bsa call (dfm_bsa_last_timing)."""
-    a, b = C.c_double(0), C.c_double(0)
-    L.check(L.lib().dfm_bsa_last_timing(C.byref(a), C.byref(b)), "dfm_bsa_last_timing")
-    return a.value, b.value
+    return _last_ms("dfm_bsa_last_timing", 2)
 
 
 def sterics_last_timing():
     """(host-to-device copy ms, kernel ms) of this thread's last Atoms.sterics call (dfm_sterics_last_timing)."""
-    a, b = C.c_double(0), C.c_double(0)
-    L.check(L.lib().dfm_sterics_last_timing(C.byref(a), C.byref(b)), "dfm_sterics_last_timing")
-    return a.value, b.value
+    return _last_ms("dfm_sterics_last_timing", 2)
 
 
 def sterics_exit_counts(enable):
@@ -625,16 +621,12 @@ def sterics_exit_counts(enable):
 
 def metrics_last_timing():
     """(host-to-device copy ms, kernel ms) of this thread's last Native.metrics call (dfm_metrics_last_timing)."""
-    a, b = C.c_double(0), C.c_double(0)
-    L.check(L.lib().dfm_metrics_last_timing(C.byref(a), C.byref(b)), "dfm_metrics_last_timing")
-    return a.value, b.value
+    return _last_ms("dfm_metrics_last_timing", 2)
 
 
 def consensus_last_timing():
     """(host-to-device copy ms, kernel ms) of this thread's last Model.consensus call (dfm_consensus_last_timing)."""
-    a, b = C.c_double(0), C.c_double(0)
-    L.check(L.lib().dfm_consensus_last_timing(C.byref(a), C.byref(b)), "dfm_consensus_last_timing")
-    return a.value, b.value
+    return _last_ms("dfm_consensus_last_timing", 2)
 
 
 def consensus_chunk_poses(R: int, Lg: int) -> int:
@@ -644,9 +636,7 @@ def consensus_chunk_poses(R: int, Lg: int) -> int:
 
 def pose_last_timing():
     """(k_pose_dist ms, clustering kernels ms) of this thread's last pose_rmsd / pose_cluster call (dfm_pose_last_timing)."""
-    a, b = C.c_double(0), C.c_double(0)
-    L.check(L.lib().dfm_pose_last_timing(C.byref(a), C.byref(b)), "dfm_pose_last_timing")
-    return a.value, b.value
+    return _last_ms("dfm_pose_last_timing", 2)
 
 
 class Complex:
