@@ -53,6 +53,8 @@ EXPORTS = [
     "dfm_rescon_last_phases",
     "dfm_hbond_create", "dfm_hbond_destroy", "dfm_hbond_info", "dfm_pose_hbonds", "dfm_pose_hbonds_chunked", "dfm_hbond_last_timing",
     "dfm_hbond_last_phases",
+    "dfm_pairpot_create", "dfm_pairpot_destroy", "dfm_pairpot_info", "dfm_pose_pairpot", "dfm_pose_pairpot_chunked",
+    "dfm_pairpot_last_timing", "dfm_pairpot_last_phases",
     "dfm_score_distogram", "dfm_distogram_last_timing",
 ]
 
@@ -148,6 +150,10 @@ class ResconOutC(C.Structure):
 
 class HbondOutC(C.Structure):
     _fields_ = [(n, I32P) for n in ("n_hbond", "hb_kind", "n_salt", "n_salt_atoms", "rec_hb", "lig_hb", "rec_sb", "lig_sb")]
+
+
+class PairpotOutC(C.Structure):
+    _fields_ = [(n, C.POINTER(C.c_int64)) for n in ("energy_q", "n_pairs", "lig_q")] + [("counts", I32P)]
 
 
 class DistogramParamsC(C.Structure):
@@ -264,6 +270,15 @@ def lib():
     L.dfm_pose_hbonds_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(HbondOutC)]
     L.dfm_hbond_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_hbond_last_phases.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_pairpot_create.argtypes = [C.c_void_p, C.c_int, F32P, I32P, C.c_int, F32P, I32P, F32P, C.c_int, C.c_int, F32P, F32P, C.c_int]
+    L.dfm_pairpot_create.restype = C.c_void_p
+    L.dfm_pairpot_destroy.argtypes = [C.c_void_p]
+    L.dfm_pairpot_destroy.restype = None
+    L.dfm_pairpot_info.argtypes = [C.c_void_p, I32P, I32P, F32P, C.POINTER(C.c_double), I32P, I32P]
+    L.dfm_pose_pairpot.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.POINTER(PairpotOutC)]
+    L.dfm_pose_pairpot_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(PairpotOutC)]
+    L.dfm_pairpot_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_pairpot_last_phases.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_score_distogram.argtypes = [C.c_void_p, C.c_int, F32P, F32P, I32P, C.c_uint64, C.c_uint32, C.POINTER(DistogramParamsC),
                                       C.POINTER(DistogramOutC)]
     L.dfm_distogram_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]

@@ -15,6 +15,7 @@
     python -m dfmdock_amd dock|refine ... --write-restraints consensus.txt --restraint-top 10 [--restraint-upper 8.0]
     python -m dfmdock_amd sweep ... --consensus [--consensus-top 0.5]
     python -m dfmdock_amd dock|refine ... --interface-energy [--rank interface] [--ie-weights 0.18 1.0 0.5] [--ie-cutoff 8.0] [--energy-residues FILE]
+    python -m dfmdock_amd dock|refine ... --pair-potential FILE.npz [--rank pairpot] [--pairpot-residues FILE] [--pair-counts FILE.npz]
     python -m dfmdock_amd dock|refine ... --affinity [--affinity-cutoff 5.5] [--contact-residues FILE]
     python -m dfmdock_amd dock|refine ... --hbonds [--bsa] [--hbond-cutoff 3.5] [--hbond-angle 90] [--salt-cutoff 4.0] [--hbond-residues FILE]
     python -m dfmdock_amd dock|refine ... --distogram [--rank distogram] [--distogram-map map.npz] [--distogram-restraints FILE] [--distogram-t 1e-3]
@@ -87,6 +88,15 @@
              the donors and acceptors the pose buries completely and leaves without a bond.  `--hbond-residues FILE` lists the kept
              model's counts per residue of both chains (and <FILE stem>_<rank> those of every --top-k model).  No agreement with the
              counts of PISA or HBPLUS is claimed.  Nothing is ranked or filtered by them.
+  pairpot    no reference counterpart: a tabulated, distance-binned, type-pair potential of every trajectory on the GPU
+             (dfmdock_amd/pairpot.py, dfm_pose_pairpot) - E = the sum over heavy-atom pairs of table[type_a][type_b][bin(r)], the shape of
+             DFIRE, DOPE, ITScore-PP or a table fitted to one's own decoys.  The project ships NO table and claims nothing about any
+             potential's ranking quality: `--pair-potential FILE.npz` names the user's file (edges [NB+1] in A, table [T,T,NB] in kcal/mol
+             indexed ligand type, receptor type, bin, type_names [T]: RES:ATOM, RES:*, *:ATOM, @ELEMENT or *, the first that fits an atom
+             in that order; an atom none fits is left out and counted in n_untyped) and adds a `pair_potential` object (energy, n_pairs,
+             n_untyped, T, NB, cutoff) for the kept pose and for every --top-k model; `--rank pairpot` keeps the pose with the lowest
+             energy (ties: the lower index); `--pairpot-residues FILE` lists the kept model's energy per ligand residue; `--pair-counts
+             FILE.npz` writes the pair counts [T,T,NB] of every written model - what a potential of this shape is fitted from.
   distogram  the model's own distogram head (second model family only: EGNN_Net.to_dist, 64 distance bins per residue pair) evaluated at
              every final pose and reduced on the GPU (dfmdock_amd/distogram.py, dfm_score_distogram).  `dock / refine --distogram` add
              dist_nll (the reference's distogram_loss of the pose's own CA-CA distances under the prediction made at that pose: lower =
@@ -124,9 +134,10 @@ def _add_native(p):
 def _add_consensus(p):
     p.add_argument("--consensus", action="store_true",
                    help="score the trajectories by consensus contacts (adds a `consensus` object to the result line)")
-    p.add_argument("--rank", default="energy", choices=["energy", "consensus", "interface", "distogram"],
+    p.add_argument("--rank", default="energy", choices=["energy", "consensus", "interface", "distogram", "pairpot"],
                    help="which trajectory is kept: the minimum energy (default), the highest consensus score (implies --consensus), the "
-                        "lowest interface energy (implies --interface-energy) or the lowest distogram nll (implies --distogram)")
+                        "lowest interface energy (implies --interface-energy), the lowest distogram nll (implies --distogram) or the lowest "
+                        "tabulated pair potential (dock / refine only; needs --pair-potential)")
     p.add_argument("--consensus-top", type=float, default=None, metavar="FRAC",
                    help="with --consensus: members of the ensemble are the best FRAC of the trajectories by energy (default 1.0: all)")
     p.add_argument("--contact-map", default=None, metavar="FILE.npz",
@@ -170,6 +181,16 @@ def _add_interface(p):
     p.add_argument("--ie-cutoff", type=float, default=None, metavar="A", help="with --interface-energy: heavy-atom pair cutoff (default 8.0, at most 16)")
     p.add_argument("--energy-residues", default=None, metavar="FILE",
                    help="write the kept model's LJ and Coulomb interface energy per ligand residue (implies --interface-energy)")
+
+
+def _add_pairpot(p):
+    p.add_argument("--pair-potential", default=None, metavar="FILE.npz",
+                   help="tabulated pair potential of every trajectory from the user's table (edges, table, type_names; no table is shipped): "
+                        "adds a `pair_potential` object to the result line and to every model")
+    p.add_argument("--pairpot-residues", default=None, metavar="FILE",
+                   help="with --pair-potential: write the kept model's pair potential per ligand residue")
+    p.add_argument("--pair-counts", default=None, metavar="FILE.npz",
+                   help="with --pair-potential: write the pair counts [T,T,NB] of every written model with type_names and edges")
 
 
 def _add_affinity(p):
@@ -247,6 +268,7 @@ def build_parser():
     _add_sterics(d)
     _add_surface(d)
     _add_interface(d)
+    _add_pairpot(d)
     _add_affinity(d)
     _add_hbonds(d)
     _add_common(d)
@@ -266,6 +288,7 @@ def build_parser():
     _add_sterics(r)
     _add_surface(r)
     _add_interface(r)
+    _add_pairpot(r)
     _add_affinity(r)
     _add_hbonds(r)
     _add_common(r)
@@ -360,6 +383,11 @@ def parse_args(argv=None):
             ap.error("--ie-cutoff must be in (0, 16]")
         if args.ie_weights is not None and not np.isfinite(args.ie_weights).all():
             ap.error("--ie-weights must be finite")
+    if args.cmd in ("dock", "refine"):
+        if args.pair_potential is None and (args.rank == "pairpot" or args.pairpot_residues or args.pair_counts):
+            ap.error("--rank pairpot / --pairpot-residues / --pair-counts need --pair-potential FILE.npz: no table is shipped")
+    elif getattr(args, "rank", None) == "pairpot":
+        ap.error("--rank pairpot is offered by dock and refine")
     if args.cmd in ("dock", "refine"):
         if args.contact_residues:
             args.affinity = True
@@ -544,6 +572,37 @@ def interface_kwargs(args):
     if not args.interface_energy:
         return {}
     return dict(interface_energy=True, ie_weights=args.ie_weights, ie_cutoff=args.ie_cutoff, rank=args.rank)
+
+
+def pairpot_kwargs(args):
+    """Driver keyword arguments of the pair-potential flags of dock / refine: none without them.  The file is read here, once."""
+    if args.pair_potential is None:
+        return {}
+    from .pairpot import load
+    return dict(pair_potential=load(args.pair_potential), rank=args.rank)
+
+
+def pairpot_outputs(args, model, res, rec, lig, line, pot):
+    """The pair-potential part of a dock / refine result: the `pair_potential` object of the line, --pairpot-residues and --pair-counts
+    (the kept pose first, then the models in their order)."""
+    if args.pair_potential is None:
+        return
+    line.update(pair_potential=res["pair_potential"], index=res["index"])
+    if args.pairpot_residues:
+        from . import driver
+        from .pairpot import write_pairpot_residues
+        keys, q = driver.residue_pairpot(model, rec, lig, res["rot_update"], res["tr_update"], pot)
+        write_pairpot_residues(args.pairpot_residues, keys, q)
+        line.update(pairpot_residues=os.path.abspath(args.pairpot_residues))
+    if args.pair_counts:
+        from . import driver
+        idx = [int(res["index"])] + [int(m["index"]) for m in res.get("models", [])]
+        tj = res["pairpot_data"]      # the pair-potential path's own poses: `trajectories` of a restrained run holds no transforms
+        cd = driver.ensemble_pairpot(model, rec, lig, np.asarray(tj["rot_update"])[idx], np.asarray(tj["tr_update"])[idx], pot, counts=True)
+        with open(args.pair_counts, "wb") as f:
+            np.savez(f, counts=cd["counts"], index=np.asarray(idx, np.int64), n_pairs=cd["n_pairs"], energy_q=cd["energy_q"],
+                     type_names=np.asarray([str(n) for n in pot["type_names"]]), edges=np.asarray(pot["edges"], np.float32))
+        line.update(pair_counts=os.path.abspath(args.pair_counts))
 
 
 def interface_outputs(args, model, res, rec, lig, line):
@@ -749,6 +808,7 @@ def cmd_dock(args):
     kw.update(sterics_kwargs(args))
     kw.update(surface_kwargs(args))
     kw.update(interface_kwargs(args))
+    kw.update(pairpot_kwargs(args))
     kw.update(affinity_kwargs(args))
     kw.update(hbonds_kwargs(args))
     res = driver.dock_pair(model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
@@ -772,6 +832,7 @@ def cmd_dock(args):
     sterics_outputs(args, model, res, rec, lig, line)
     surface_outputs(args, model, res, rec, lig, line)
     interface_outputs(args, model, res, rec, lig, line)
+    pairpot_outputs(args, model, res, rec, lig, line, kw.get("pair_potential"))
     affinity_outputs(args, model, res, rec, lig, line)
     hbonds_outputs(args, model, res, rec, lig, line)
     print(json.dumps(line), flush=True)
@@ -799,6 +860,7 @@ def cmd_refine(args):
     kw.update(sterics_kwargs(args))
     kw.update(surface_kwargs(args))
     kw.update(interface_kwargs(args))
+    kw.update(pairpot_kwargs(args))
     kw.update(affinity_kwargs(args))
     kw.update(hbonds_kwargs(args))
     res = driver.refine_pair(model, rec, lig, rec_x, lig_x, t_begin=args.t_begin, num_samples=args.num_samples, num_steps=args.num_steps,
@@ -815,6 +877,7 @@ def cmd_refine(args):
     sterics_outputs(args, model, res, rec, lig, line)
     surface_outputs(args, model, res, rec, lig, line)
     interface_outputs(args, model, res, rec, lig, line)
+    pairpot_outputs(args, model, res, rec, lig, line, kw.get("pair_potential"))
     affinity_outputs(args, model, res, rec, lig, line)
     hbonds_outputs(args, model, res, rec, lig, line)
     print(json.dumps(line), flush=True)

@@ -1,5 +1,5 @@
-// api_pose.hip - the pose calls of the C ABI (include/dfmdock_amd.h): pose clustering, docking metrics, consensus contacts and the five
-// rigid-pose families (sterics, buried surface, interface energy, residue contacts, hydrogen bonds).  Every call owns a non-blocking
+// api_pose.hip - the pose calls of the C ABI (include/dfmdock_amd.h): pose clustering, docking metrics, consensus contacts and the six
+// rigid-pose families (sterics, buried surface, interface energy, residue contacts, hydrogen bonds, tabulated pair potential).  Every call owns a non-blocking
 // stream and its temporaries; the handles are bound to the model handle's device only.
 #include <algorithm>
 #include <climits>
@@ -21,7 +21,7 @@ using namespace dfm;
 // several host threads, and next to that model's complex handles, do not share any state.
 // the two millisecond figures of this thread's last call of each kind, behind the dfm_*_last_timing getters: k_pose_dist and the
 // clustering kernels for MS_CLUSTER, host-to-device copies and kernels for the others
-enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_IFACE, MS_RESCON, MS_HBOND, MS_KINDS };
+enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_IFACE, MS_RESCON, MS_HBOND, MS_PAIRPOT, MS_KINDS };
 static thread_local double g_last_ms[MS_KINDS][2] = {};
 
 static void set_last_ms(int kind, double a, double b)
@@ -97,7 +97,7 @@ struct PoseCall {
     }
 };
 
-// the per-phase kernel milliseconds of this thread's last call of the kinds that split them (MS_RESCON, MS_HBOND), summed over the call's
+// the per-phase kernel milliseconds of this thread's last call of the kinds that split them (MS_RESCON, MS_HBOND, MS_PAIRPOT), summed over the call's
 // chunks: the memsets | the pose kernel and the cell walk | the finishing kernel
 static thread_local double g_phase_ms[MS_KINDS][3] = {};
 
@@ -113,10 +113,10 @@ static int last_phases(int kind, double *zero_ms, double *walk_ms, double *finis
     extern "C" int name(double *copy_ms, double *kernel_ms) { return last_timing(kind, copy_ms, kernel_ms); }
 
 // ------------------------------------------------------------------------------------------------
-// The rigid-pose calls (sterics, buried surface, interface energy, residue contacts, hydrogen bonds).  A handle holds what the two atom
+// The rigid-pose calls (sterics, buried surface, interface energy, residue contacts, hydrogen bonds, pair potential).  A handle holds what the two atom
 // sets and the rotation centre fix - the receptor's cell grid, the ligand in blocks of 64 neighbours, that family's per-atom arrays -
 // and is read-only after creation; like a dfm_native it is bound to the model handle's device only, and every call owns its stream and
-// temporaries.  What the five handles share:
+// temporaries.  What the six handles share:
 struct PoseHandle {
     int device = 0, n_cells = 0, max_cell_atoms = 0;
     int default_chunk = 0;      // poses of a chunk when neither the call nor the creator names one (the surface works it out per call)
@@ -1305,4 +1305,139 @@ DFM_LAST_TIMING(dfm_hbond_last_timing, MS_HBOND)
 extern "C" int dfm_hbond_last_phases(double *zero_ms, double *walk_ms, double *finish_ms)
 {
     return last_phases(MS_HBOND, zero_ms, walk_ms, finish_ms);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Tabulated pair potential (kernels_pairpot.hip): the receptor's grid of cells of the last bin edge, each receptor atom's type and slab
+// offset beside it, the ligand's types at their sorted places, the squared edges and the quantised table in (receptor type, ligand
+// type, bin) order.
+// dfm_pairpot_create refuses in this order: m; the atom sets (check_atom_sets); rec_type / lig_type NULL; T; NB and the edges
+// (check_pairpot_edges); the table (check_pairpot_table); a type out of range, receptor first; chunk_poses; the receptor's box of more
+// than 2^24 cells; the pair bound; the ligand's extent about the centre.
+struct dfm_pairpot : PoseHandle {
+    int Ar = 0, Al = 0, T = 0, NB = 0;
+    int chunk_poses = 0;      // the creator's chunk (0: none given)
+    double pair_bound = 0.0;
+    float *rec_par = nullptr;
+    int32_t *lig_index = nullptr, *lig_type = nullptr, *table_q = nullptr;
+    double *e2 = nullptr;
+    PairpotConst sc = {};
+};
+
+extern "C" void dfm_pairpot_destroy(dfm_pairpot *h) { pose_destroy(h); }
+
+extern "C" dfm_pairpot *dfm_pairpot_create(dfm_model *m, int Ar, const float *rec_atoms, const int32_t *rec_type, int Al, const float *lig_atoms,
+                                           const int32_t *lig_type, const float center[3], int T, int NB, const float *edges,
+                                           const float *table, int chunk_poses)
+{
+    auto bad = [](int code, const std::string &msg) -> dfm_pairpot * { (void)fail(code, msg); return nullptr; };
+    if (!m) return bad(DFM_E_INVALID, "m is NULL");
+    if (const std::string msg = check_atom_sets(Ar, rec_atoms, Al, lig_atoms, center); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (!rec_type) return bad(DFM_E_INVALID, "rec_type is NULL");
+    if (!lig_type) return bad(DFM_E_INVALID, "lig_type is NULL");
+    if (T < 1 || T > PAIRPOT_MAX_TYPES) return bad(DFM_E_INVALID, "need 1 <= T <= " + std::to_string(PAIRPOT_MAX_TYPES));
+    if (const std::string msg = check_pairpot_edges(NB, edges); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_pairpot_table(T, NB, table); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_pairpot_types("rec", Ar, rec_type, T); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_pairpot_types("lig", Al, lig_type, T); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (chunk_poses < 0) return bad(DFM_E_INVALID, "chunk_poses must be >= 0");
+    const float cutoff = edges[NB];
+    PoseFrame f;
+    const std::string frame_msg = build_pose_frame(Ar, rec_atoms, Al, lig_atoms, center, cutoff, "last edge", f);
+    if (f.gr.order.empty()) return bad(DFM_E_INVALID, frame_msg);      // no grid: the bound below needs its fullest cell
+    const PairpotBound bound = pairpot_pair_bound(Ar, Al, f.gr.max_cell);
+    if (!bound.ok) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "a pose could have %.4g atom pairs in range, more than 2^31 - 1", bound.pairs);
+        return bad(DFM_E_INVALID, buf);
+    }
+    if (!frame_msg.empty()) return bad(DFM_E_INVALID, frame_msg);
+    const std::vector<float> rec4 = gather4(f.gr.order, rec_atoms, nullptr), lig4 = gather4(f.lb.index, lig_atoms, nullptr);
+    const std::vector<float> recp = gather4_pairpot(f.gr.order, rec_type, T, NB);
+    std::vector<int32_t> ltype((size_t)Al);
+    for (int i = 0; i < Al; ++i) ltype[(size_t)i] = lig_type[f.lb.index[(size_t)i]];
+    const std::vector<int32_t> tq = quantise_pairpot(T, NB, table);
+    const std::vector<double> e2 = pairpot_edges2(NB, edges);
+    dfm_pairpot *h = new dfm_pairpot;
+    h->set_grid(m->device, f.g, f.gr.max_cell, cutoff);
+    h->Ar = Ar; h->Al = Al; h->T = T; h->NB = NB;
+    h->chunk_poses = chunk_poses;
+    h->pair_bound = bound.pairs;
+    h->sc.g = f.g;
+    h->sc.lo2 = e2[0];
+    h->sc.cut2 = e2[(size_t)NB];
+    h->sc.reject2 = f.reject2;
+    h->sc.T = T; h->sc.NB = NB;
+    h->sc.top = 1;
+    while (h->sc.top * 2 <= NB) h->sc.top *= 2;
+    return pose_finish_create(h, "dfm_pairpot_create", bad, [&](PoseUploads &up) {
+        up(&h->rec, rec4)(&h->rec_par, recp)(&h->cell_start, f.gr.start)(&h->lig, lig4)(&h->sphere, f.lb.sphere);
+        up(&h->lig_index, f.lb.index)(&h->lig_type, ltype)(&h->table_q, tq)(&h->e2, e2);
+    });
+}
+
+extern "C" int dfm_pairpot_info(const dfm_pairpot *h, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge, double *pair_bound,
+                                int32_t *T, int32_t *NB)
+{
+    if (!h) return fail(DFM_E_INVALID, "NULL argument");
+    h->grid_info(n_cells, max_cell_atoms, cell_edge);
+    if (pair_bound) *pair_bound = h->pair_bound;
+    if (T) *T = h->T;
+    if (NB) *NB = h->NB;
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_pairpot_chunked(dfm_pairpot *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_pairpot_out *out)
+{
+    PoseChunks ch;
+    if (int rc = ch.begin(h, "h", P, 0, rot, tr, out, chunk_poses)) return rc;
+    PoseCall &c = ch.c;
+    // the call's chunk, else the creator's, else as many poses as fill PAIRPOT_CHUNK_BYTES of counts plus per-atom output
+    if (int rc = ch.alloc(chunk_poses > 0 ? chunk_poses : h->chunk_poses,
+                          pairpot_chunk_poses(h->Al, h->T, h->NB, out->lig_q != nullptr, out->counts != nullptr), PAIRPOT_MAX_CHUNK))
+        return rc;
+    const int Pc = ch.Pc;
+    const size_t Al = (size_t)h->Al, hist = (size_t)h->T * h->T * h->NB;
+    int64_t *d_tot = nullptr, *d_lq = nullptr;
+    int32_t *d_cnt = nullptr;
+    HIPCHK(c.tmp.alloc(&d_tot, (size_t)Pc * 2));      // energy_q | n_pairs of each pose
+    if (out->lig_q) HIPCHK(c.tmp.alloc(&d_lq, (size_t)Pc * Al));
+    if (out->counts) HIPCHK(c.tmp.alloc(&d_cnt, (size_t)Pc * hist));
+    const PairpotAtoms at = {h->rec, h->rec_par, h->lig, h->sphere, h->cell_start, h->lig_index, h->lig_type, h->table_q, h->e2, h->sc,
+                             h->Ar, h->Al};
+    std::vector<int64_t> h_tot((size_t)Pc * 2);
+    for (int p0 = 0; p0 < P; p0 += Pc) {
+        const int n = std::min(Pc, P - p0);
+        HIPCHK(ch.upload(p0, n));
+        if (d_lq) HIPCHK(hipMemsetAsync(d_lq, 0, (size_t)n * Al * sizeof(int64_t), c.s));
+        if (d_cnt) HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)n * hist * sizeof(int32_t), c.s));
+        HIPCHK(ch.mark_zeroed());
+        HIPCHK(launch_pairpot_pose(ch.d_rot, ch.d_tr, n, ch.T, d_tot, c.s));
+        HIPCHK(launch_pairpot(at, ch.T, n, d_tot, d_lq, d_cnt, c.s));
+        HIPCHK(ch.mark_walked());
+        HIPCHK(ch.kernels_done());      // no finishing kernel: the third phase is empty
+        HIPCHK(hipMemcpyAsync(h_tot.data(), d_tot, (size_t)n * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
+        if (d_lq) HIPCHK(hipMemcpyAsync(out->lig_q + (size_t)p0 * Al, d_lq, (size_t)n * Al * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
+        if (d_cnt) HIPCHK(hipMemcpyAsync(out->counts + (size_t)p0 * hist, d_cnt, (size_t)n * hist * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(ch.finish());
+        for (int p = 0; p < n; ++p) {
+            if (out->energy_q) out->energy_q[p0 + p] = h_tot[(size_t)p * 2];
+            if (out->n_pairs) out->n_pairs[p0 + p] = h_tot[(size_t)p * 2 + 1];
+        }
+    }
+    return ch.done(MS_PAIRPOT);
+}
+
+extern "C" int dfm_pose_pairpot(dfm_pairpot *h, int P, const float *rot, const float *tr, dfm_pairpot_out *out)
+{
+    return dfm_pose_pairpot_chunked(h, P, rot, tr, 0, out);
+}
+
+DFM_LAST_TIMING(dfm_pairpot_last_timing, MS_PAIRPOT)
+
+// the memsets of the per-atom output and of counts, k_pairpot_pose + k_pairpot, and nothing (the call has no finishing kernel) of this
+// thread's last dfm_pose_pairpot, summed over its chunks
+extern "C" int dfm_pairpot_last_phases(double *zero_ms, double *walk_ms, double *finish_ms)
+{
+    return last_phases(MS_PAIRPOT, zero_ms, walk_ms, finish_ms);
 }

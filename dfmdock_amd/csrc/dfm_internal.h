@@ -562,6 +562,33 @@ hipError_t launch_hbond(const HbondAtoms &at, const double *T, int n, int32_t *t
 // tot [n][5]: entry 4 = the set bits of the pose's bitmap
 hipError_t launch_hbond_finish(const HbondAtoms &at, const uint32_t *bits, int n, int32_t *tot, hipStream_t s);
 
+// tabulated pair potential (kernels_pairpot.hip; include/dfmdock_amd.h: dfm_pairpot_create / dfm_pose_pairpot).  What the atoms, the edges
+// and the table fix: the receptor's grid of cells of the last edge, lo2 = e2[0] and cut2 = e2[NB] as the definition's doubles, the fp32
+// reject threshold squared (g.grow is that threshold as a double, as in StericsConst), T types, NB bins and top = the largest power of
+// two <= NB, the first step of the bin search.
+struct PairpotConst {
+    WalkGrid g;
+    double lo2, cut2;
+    float reject2;
+    int T, NB, top;
+};
+// device arrays of a dfm_pairpot: rec / lig / sphere / cell_start / lig_index as in StericsAtoms; rec_par [Ar] float4 = (bits of the type,
+// bits of type T NB, 0, 0) of the atom at the same place of rec; lig_type [Al] of the atom at the same place of lig; e2 [128] = the
+// squared edges, then +inf; table_q [T][T][NB] int32 in the order (receptor type, ligand type, bin)
+struct PairpotAtoms {
+    const float *rec, *rec_par, *lig, *sphere;
+    const int32_t *cell_start, *lig_index, *lig_type, *table_q;
+    const double *e2;
+    PairpotConst sc;
+    int Ar, Al;
+};
+// T [n][12]: R(rot) row-major and tr as doubles; also zeroes tot [n][2] = (energy_q, n_pairs) of the n poses
+hipError_t launch_pairpot_pose(const float *rot, const float *tr, int n, double *T, int64_t *tot, hipStream_t s);
+// n <= 65535 poses.  tot [n][2] is added to.  lig_q [n][Al] (caller's atom order) or nullptr: written by the waves that reach the cell
+// walk only, so zero it first.  counts [n][T][T][NB] in the order (ligand type, receptor type, bin) or nullptr: added to, so zero it
+// first; nullptr launches the instantiation that holds no counting code
+hipError_t launch_pairpot(const PairpotAtoms &at, const double *T, int n, int64_t *tot, int64_t *lig_q, int32_t *counts, hipStream_t s);
+
 // isolated exposure of one chain on the host, as the definition takes it (kernels_surface.hip)
 void surface_exposure(int n, const float *xyz, const float *radius, double probe, int K, const float *dirs, const double lo[3],
                       const int dims[3], double edge, double pad, const int32_t *start, const int32_t *order, uint64_t *mask);

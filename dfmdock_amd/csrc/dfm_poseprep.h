@@ -1,8 +1,9 @@
 // dfm_poseprep.h - host preparation of the per-pose all-atom calls (api_pose.hip: dfm_atoms_create, dfm_surface_create, dfm_iface_create,
-// dfm_rescon_create, dfm_hbond_create): argument checks, the cell grid of a chain, the ligand in blocks of 64 neighbours, the rounding
+// dfm_rescon_create, dfm_hbond_create, dfm_pairpot_create): argument checks, the cell grid of a chain, the ligand in blocks of 64 neighbours, the rounding
 // slack, the frame of the cutoff-based creators, the interface energy's parameter limits and overflow bound, the residue contacts' limits, residue bits, class masks and chunk
-// size, the hydrogen bonds' limits, role bits and charged residues.  Plain C++ without a HIP call, so that tests/test_pose_prep_cpu.py,
-// tests/test_ifenergy_cpu.py, tests/test_affinity_cpu.py and tests/test_hbonds_cpu.py run it under the sanitizers without a GPU.
+// size, the hydrogen bonds' limits, role bits and charged residues, the pair potential's limits, quantised table, squared edges, pair
+// bound and chunk size.  Plain C++ without a HIP call, so that tests/test_pose_prep_cpu.py, tests/test_ifenergy_cpu.py,
+// tests/test_affinity_cpu.py, tests/test_hbonds_cpu.py and tests/test_pairpot_cpu.py run it under the sanitizers without a GPU.
 #pragma once
 
 #include <algorithm>
@@ -400,5 +401,105 @@ inline std::vector<float> gather4_hbond(const std::vector<int32_t> &order, const
 // poses of one chunk of a call: the bitmap of a pose is [Lc][ceil(Rc / 32)] words over the CHARGED residues of the two chains; a chain
 // without one leaves a bitmap of one word that nothing reads
 inline int hbond_chunk_poses(int Lc, int Rc, size_t budget = RESCON_SCRATCH_BYTES) { return rescon_chunk_poses(std::max(Lc, 1), std::max(Rc, 1), budget); }
+
+// Tabulated pair potential (api_pose.hip: dfm_pairpot_create; kernels_pairpot.hip).  The limits: atom types, distance bins, the largest
+// table entry in kcal/mol, poses per launch, and the bytes of counts plus per-atom output a chunk of a call may hold.
+constexpr int PAIRPOT_MAX_TYPES = 256, PAIRPOT_MAX_BINS = 64, PAIRPOT_MAX_CHUNK = 32768;
+constexpr float PAIRPOT_MAX_ENTRY = 1024.f, PAIRPOT_MAX_CUTOFF = 16.f;
+constexpr size_t PAIRPOT_CHUNK_BYTES = (size_t)64 << 20;
+
+// the bin edges [NB + 1]: the message of the first thing that is wrong, or ""
+inline std::string check_pairpot_edges(int NB, const float *edges)
+{
+    if (NB < 1 || NB > PAIRPOT_MAX_BINS) return "need 1 <= NB <= " + std::to_string(PAIRPOT_MAX_BINS);
+    if (!edges) return "edges is NULL";
+    for (int k = 0; k <= NB; ++k)
+        if (!std::isfinite(edges[k])) return "edges: edge " + std::to_string(k) + " is not finite";
+    for (int k = 0; k < NB; ++k)
+        if (!(edges[k] < edges[k + 1])) return "edges: edge " + std::to_string(k + 1) + " is not above edge " + std::to_string(k);
+    if (!(edges[0] >= 0.f)) return "edges: edge 0 is below 0";
+    if (!(edges[NB] <= PAIRPOT_MAX_CUTOFF)) return "edges: the last edge is above 16";
+    return "";
+}
+// the table [T][T][NB], kcal/mol
+inline std::string check_pairpot_table(int T, int NB, const float *table)
+{
+    if (T < 1 || T > PAIRPOT_MAX_TYPES) return "need 1 <= T <= " + std::to_string(PAIRPOT_MAX_TYPES);
+    if (NB < 1 || NB > PAIRPOT_MAX_BINS) return "need 1 <= NB <= " + std::to_string(PAIRPOT_MAX_BINS);
+    if (!table) return "table is NULL";
+    const size_t n = (size_t)T * T * NB;
+    for (size_t i = 0; i < n; ++i)
+        if (!(std::isfinite(table[i]) && std::fabs(table[i]) <= PAIRPOT_MAX_ENTRY))
+            return "table: entry " + std::to_string(i) + " is not in [-1024, 1024]";
+    return "";
+}
+// the type [n] of every atom of one chain (`who`: "rec" or "lig")
+inline std::string check_pairpot_types(const char *who, int n, const int32_t *type, int T)
+{
+    const std::string w(who);
+    if (!type) return w + "_type is NULL";
+    for (int i = 0; i < n; ++i)
+        if (type[i] < 0 || type[i] >= T)
+            return w + "_type: atom " + std::to_string(i) + " has type " + std::to_string(type[i]) + " outside [0, " + std::to_string(T) + ")";
+    return "";
+}
+
+// table_q as the kernel reads it: (int32) rint((double) table * 2^20), ties to even, |q| <= 2^30, TRANSPOSED from the caller's [ligand
+// type ta][receptor type tb][bin] to [tb][ta][bin] - the staged receptor atom is a broadcast, so the 64 gathers of one iteration fall
+// inside the one slab of T NB entries of its type
+inline std::vector<int32_t> quantise_pairpot(int T, int NB, const float *table)
+{
+    std::vector<int32_t> q((size_t)T * T * NB);
+    for (int ta = 0; ta < T; ++ta)
+        for (int tb = 0; tb < T; ++tb)
+            for (int k = 0; k < NB; ++k)
+                q[((size_t)tb * T + ta) * NB + k] = (int32_t)std::nearbyint((double)table[((size_t)ta * T + tb) * NB + k] * 1048576.0);
+    return q;
+}
+
+// e2 [PAIRPOT_E2_SLOTS]: (double) edges[k] * (double) edges[k] - exact, 24 bits times 24 bits - then +inf
+inline std::vector<double> pairpot_edges2(int NB, const float *edges)
+{
+    std::vector<double> e2((size_t)PAIRPOT_E2_SLOTS, (double)INFINITY);
+    for (int k = 0; k <= NB; ++k) e2[(size_t)k] = (double)edges[k] * (double)edges[k];
+    return e2;
+}
+
+// The integer results of the pair potential can not wrap.  A ligand atom's pairs lie within the cutoff = the cell edge, so in the 27 cells
+// about its own: a pose has at most pairs = Al min(Ar, 27 max_cell_atoms) of them.  The creator refuses a complex for which that exceeds
+// 2^31 - 1: under it every entry of counts (and their sum) fits int32, and |energy_q| <= pairs 2^30 < 2^61.
+struct PairpotBound {
+    double pairs;
+    bool ok;
+};
+inline PairpotBound pairpot_pair_bound(int Ar, int Al, int max_cell_atoms)
+{
+    PairpotBound b;
+    b.pairs = (double)Al * std::min((double)Ar, 27.0 * (double)max_cell_atoms);
+    b.ok = b.pairs <= 2147483647.0;
+    return b;
+}
+
+// what rides next to each receptor atom: (the BITS of its type, the BITS of its slab's offset type T NB in table_q, 0, 0) of atom
+// order[q] at q
+inline std::vector<float> gather4_pairpot(const std::vector<int32_t> &order, const int32_t *type, int T, int NB)
+{
+    std::vector<float> v(order.size() * 4, 0.f);
+    for (size_t q = 0; q < order.size(); ++q) {
+        const int32_t t = type[order[q]], slab = t * T * NB;
+        std::memcpy(&v[q * 4], &t, sizeof(t));
+        std::memcpy(&v[q * 4 + 1], &slab, sizeof(slab));
+    }
+    return v;
+}
+
+// poses of one chunk of a call: as many as fill `budget` bytes of counts [T][T][NB] int32 plus per-atom output [Al] int64, whichever of
+// the two the call asks for; without either the launch alone bounds it
+inline int pairpot_chunk_poses(int Al, int T, int NB, bool per_atom, bool counts, size_t budget = PAIRPOT_CHUNK_BYTES)
+{
+    const size_t per_pose = (counts ? (size_t)T * T * NB * sizeof(int32_t) : 0) + (per_atom ? (size_t)Al * sizeof(int64_t) : 0);
+    if (!per_pose) return PAIRPOT_MAX_CHUNK;
+    return (int)std::min<size_t>((size_t)PAIRPOT_MAX_CHUNK, std::max<size_t>(1, budget / per_pose));
+}
 
 }  // namespace dfm

@@ -1,6 +1,6 @@
 // dfm_walkgrid.h - the receptor's cell grid of the per-pose all-atom calls and its binning formula, in plain C++: the host builds the
 // grid with them (dfm_poseprep.h), the kernels walk it (dfm_posewalk.h).  Also the bits a polar atom of the hydrogen-bond call carries
-// in its float4, which the host packs and kernels_hbond.hip reads.
+// in its float4, which the host packs and kernels_hbond.hip reads, and the padded length of the pair potential's squared edges.
 #pragma once
 
 #include <math.h>
@@ -35,5 +35,9 @@ DFM_HOST_DEVICE inline int cell_of(double x, double origin, double edge, int n)
 // HB_RES_SHIFT
 constexpr uint32_t HB_DONOR = 1, HB_ACCEPTOR = 2, HB_CATION = 4, HB_ANION = 8, HB_SIDECHAIN = 16, HB_ROLE_MASK = 31;
 constexpr int HB_RES_SHIFT = 8;
+
+// slots of the pair potential's squared bin edges as the host pads them with +inf (dfm_poseprep.h: pairpot_edges2) and the bin search of
+// kernels_pairpot.hip reads them: twice the largest step of the search over at most 65 edges
+constexpr int PAIRPOT_E2_SLOTS = 128;
 
 }  // namespace dfm

@@ -249,6 +249,86 @@ def _interface_result(ed, k, opts, bad=None, ranked_by="energy"):
     return {"interface_energy": summary, "interface_data": ed, "index": int(k)}
 
 
+def pairpot_inputs(rec, lig, family, pot):
+    """What the pair-potential call takes from two pdbio.backbone_from_atoms dicts and a potential (pairpot.load's dict): the heavy
+    atoms of both chains that the file's type names give a type (pairpot.atom_types; float32 [n,3] and int32 [n]), the centre of
+    sterics_inputs, the indices of the ligand's typed atoms among lig["atoms"] and the number of heavy atoms of both chains that no name
+    fits - those are left out of every sum."""
+    from . import pairpot as PP
+    _, _, cen = sterics_inputs(rec, lig, family)
+    rt, rk, ru = PP.atom_types(rec["atoms"], pot["type_names"])
+    lt, lk, lu = PP.atom_types(lig["atoms"], pot["type_names"])
+    if not rk.size or not lk.size:
+        raise ValueError("the potential's type names fit no heavy atom of " + ("the receptor" if not rk.size else "the ligand"))
+    return np.asarray(rec["aa_coords"], np.float32)[rk], rt, np.asarray(lig["aa_coords"], np.float32)[lk], lt, cen, lk, ru + lu
+
+
+def ensemble_pairpot(model: engine.Model, rec, lig, rot_update, tr_update, pot, per_atom=False, counts=False):
+    """Tabulated pair potential of trajectories on the GPU (dfm_pose_pairpot) from their final (rot_update, tr_update) alone, over the
+    typed heavy atoms of the two parsed PDB chains (pairpot_inputs); pot: pairpot.load's dict - the project ships no table.  Returns the
+    dict of PairPotential.energy plus n_untyped, T, NB, cutoff and lig_kept (the ligand's typed atoms as indices into lig["atoms"])."""
+    ra, rt, la, lt, cen, lk, nu = pairpot_inputs(rec, lig, model.hp.family, pot)
+    with model.pairpot(ra, rt, la, lt, cen, pot["edges"], pot["table"]) as h:
+        out = h.energy(np.asarray(rot_update, np.float32).reshape(-1, 3), np.asarray(tr_update, np.float32).reshape(-1, 3), per_atom=per_atom,
+                       counts=counts)
+        out.update(n_untyped=int(nu), T=h.T, NB=h.NB, cutoff=h.cutoff, lig_kept=lk)
+    return out
+
+
+def residue_pairpot(model: engine.Model, rec, lig, rot, tr, pot):
+    """Per ligand residue of ONE pose: (keys, q) - the per-atom sums of the pair potential in quanta of 2^-20 kcal/mol summed over each
+    residue's typed heavy atoms (sterics.residue_of_atoms over the heavy atoms, pairpot.residue_energy)."""
+    from . import pairpot as PP
+    from . import sterics as ST
+    pd = ensemble_pairpot(model, rec, lig, np.asarray(rot).reshape(1, 3), np.asarray(tr).reshape(1, 3), pot, per_atom=True)
+    heavy = ST.heavy_atoms(lig["atoms"])
+    keys, res = ST.residue_of_atoms(lig["atoms"], heavy)
+    of_atom = dict(zip(heavy.tolist(), res.tolist()))
+    return keys, PP.residue_energy(pd["lig_q"][0], np.array([of_atom[int(i)] for i in pd["lig_kept"]], np.int64), len(keys))
+
+
+def _check_pairpot(pair_potential, rank):
+    """None (off) or (rank by it, the potential) of a pair driver's pair-potential options: pair_potential is pairpot.load's dict or the
+    path of such a file; rank "pairpot" needs one."""
+    if pair_potential is None:
+        if rank == "pairpot":
+            raise ValueError("rank 'pairpot' needs a pair_potential: the project ships no table")
+        return None
+    from . import pairpot as PP
+    pot = PP.load(pair_potential) if isinstance(pair_potential, (str, os.PathLike)) else dict(pair_potential)
+    pot["edges"] = PP.check_edges(pot["edges"])
+    pot["table"] = PP.check_table(pot["table"], pot["edges"].size - 1)
+    if len(pot["type_names"]) != pot["table"].shape[0]:
+        raise ValueError(f"pair_potential: {len(pot['type_names'])} type names for {pot['table'].shape[0]} types")
+    return rank == "pairpot", pot
+
+
+def _pose_pairpot(pd, k):
+    return {"energy": float(pd["energy"][k]), "n_pairs": int(pd["n_pairs"][k]), "n_untyped": int(pd["n_untyped"]), "T": int(pd["T"]),
+            "NB": int(pd["NB"]), "cutoff": float(pd["cutoff"])}
+
+
+def _pairpot_pick(model, rec, lig, cols, k, key, opts, bad=None):
+    """The selecting half of the pair-potential part of a pair driver, run BEFORE any per-pose summary is built, next to _interface_pick.
+    opts = None (off) or _check_pairpot's.  Returns (k, key, data or None): under rank "pairpot" k is the pose of the lowest energy among
+    those the clash filter left (ties: the lower index) and key the energies, NaN on the removed poses; otherwise k and key stay."""
+    if opts is None:
+        return k, key, None
+    by_it, pot = opts
+    pd = ensemble_pairpot(model, rec, lig, cols["rot_update"], cols["tr_update"], pot)
+    pd.update(rot_update=cols["rot_update"], tr_update=cols["tr_update"])      # the poses the arrays are of (a restrained run's `trajectories` hold none)
+    if by_it:
+        k, key = _kept(np.argmin, bad, pd["energy"]), _nan_key(pd["energy"], bad)
+    return k, key, pd
+
+
+def _pairpot_result(pd, k):
+    """The `pair_potential` entries of a pair driver's result for the FINAL kept pose k: none without the option."""
+    if pd is None:
+        return {}
+    return {"pair_potential": _pose_pairpot(pd, k), "pairpot_data": pd, "index": int(k)}
+
+
 def rescon_inputs(rec, lig, family):
     """What the residue-contact call takes from two pdbio.backbone_from_atoms dicts: sterics_inputs plus, per chain, the residue index of
     every heavy atom (sterics.residue_of_atoms) and the class of every residue by its name (affinity.IC_CLASS; a name outside the table is
@@ -538,8 +618,8 @@ def _distogram_result(dd, k, opts, bad=None):
 
 
 def _check_rank(rank, consensus_top):
-    if rank not in ("energy", "consensus", "interface", "distogram"):
-        raise ValueError(f"rank must be 'energy', 'consensus', 'interface' or 'distogram', got {rank!r}")
+    if rank not in ("energy", "consensus", "interface", "distogram", "pairpot"):
+        raise ValueError(f"rank must be 'energy', 'consensus', 'interface', 'distogram' or 'pairpot', got {rank!r}")
     if not (0.0 < float(consensus_top) <= 1.0):
         raise ValueError(f"consensus_top must be in (0, 1], got {consensus_top}")
 
@@ -960,12 +1040,12 @@ def _center(model):
 
 
 def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native=None, cons=None, ster=None, clu=None, refine=None,
-            surf=None, ie=None, aff=None, dg=None, seed=0, hb=None):
+            surf=None, ie=None, aff=None, dg=None, seed=0, hb=None, pp=None):
     """What every pair driver does with its sampled trajectories: the kept pose, its files and the result.  cols: every trajectory's
     energy, rot_update, tr_update (and the driver's own columns).  pick = (rule, *column names): the driver's own choice, rule(*columns) ->
     index; key: the clustering key that goes with it.  entries(k): the driver's own result entries for the kept pose k.  cons / ster / clu:
     None or the options of _with_consensus / _screen / _top_models; surf: None or the options of _check_surface; ie: None or the options of
-    _check_interface; aff: None or the options of _check_affinity; hb: None or the options of _check_hbonds; refine: None or the keyword arguments of refine_models - only then
+    _check_interface; aff: None or the options of _check_affinity; hb: None or the options of _check_hbonds; pp: None or the options of _check_pairpot; refine: None or the keyword arguments of refine_models - only then
     does the handle outlive the sampling."""
     lig0 = gx.lig_pos0
     if refine is None and dg is None:      # the columns are host arrays: the handle (and its ~GB of device workspace) goes before any post-processing
@@ -976,13 +1056,16 @@ def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_p
     k, key, dd = _distogram_pick(gx, cols, k, _nan_key(key, bad), dg, bad, precision, seed)
     if refine is None and dg is not None:
         gx.close()
-    # the kept pose is settled first - the driver's rule, then rank "interface", then rank "consensus" (one rank is given, so at most one
-    # of the two moves k) - and only then does anything describe it
+    # the kept pose is settled first - the driver's rule, then rank "interface", rank "pairpot", then rank "consensus" (one rank is given, so
+    # at most one of them moves k) - and only then does anything describe it
     k, key, ed = _interface_pick(model, rec, lig, cols, k, _nan_key(key, bad), ie, bad)
+    k, key, pd = _pairpot_pick(model, rec, lig, cols, k, key, pp, bad)
+    by_pp = pp is not None and pp[0]
     k, key, extra = _with_consensus(model, rec, lig0, cols, k, key, cons, bad,
-                                    "interface" if ie is not None and ie[0] else "distogram" if dg is not None and dg[0] else "energy")
+                                    "interface" if ie is not None and ie[0] else "pairpot" if by_pp else "distogram" if dg is not None and dg[0] else "energy")
     key = _nan_key(key, bad)      # again: rank "consensus" has replaced the key by consensus.rank_positions
-    extra.update(_interface_result(ed, k, ie, bad, extra["consensus"]["ranked_by"] if "consensus" in extra else "energy"))
+    extra.update(_interface_result(ed, k, ie, bad, extra["consensus"]["ranked_by"] if "consensus" in extra else "pairpot" if by_pp else "energy"))
+    extra.update(_pairpot_result(pd, k))
     extra.update(_distogram_result(dd, k, dg, bad))
     extra.update(_sterics_result(sd, k))
     # one surface call serves both when the surface options are the ones the affinity estimate takes (probe 1.4 A, 128 points)
@@ -1006,11 +1089,11 @@ def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_p
     res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
            "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, **entries(k)}
     res.update(extra)
-    if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None or dg is not None or hb is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
+    if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None or dg is not None or hb is not None or pp is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
         res.setdefault("trajectories", {c: cols[c] for c in ("energy", "rot_update", "tr_update")})
     _selected_metrics(model, native, rec, lig0, res)
     if clu is not None:
-        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad, bd, None if surf is None else surf[0], ed, ad, dd, hd))
+        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad, bd, None if surf is None else surf[0], ed, ad, dd, hd, pd))
         if refine is not None:
             refine_models(model, gx, rec, lig, lig0, cols, res["models"], precision=precision, out_pdb=out_pdb, native=native, **refine)
             gx.close()
@@ -1023,7 +1106,8 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
               refine_samples=8, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
               clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, bsa=False, min_bsa=None, probe=1.4, sphere_points=128,
               interface_energy=False, ie_weights=None, ie_cutoff=8.0, affinity=False, affinity_cutoff=5.5, distogram=False,
-              distogram_t=DISTOGRAM_T, distogram_maps=False, hbonds=False, hbond_cutoff=3.5, hbond_angle=90.0, salt_cutoff=4.0, **sampler_kw):
+              distogram_t=DISTOGRAM_T, distogram_maps=False, hbonds=False, hbond_cutoff=3.5, hbond_angle=90.0, salt_cutoff=4.0, pair_potential=None,
+              **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
     pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
     the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
@@ -1094,7 +1178,12 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     acceptor and cation; no agreement with any published tool is claimed).  The result gains n_hbond, hb_bb_bb, hb_bb_sc, hb_sc_sc, n_salt
     of the kept pose, `hbond_data` (the arrays), `index` and `trajectories`; with `bsa` in the same run also n_unsat, the donors and
     acceptors the pose buries completely and leaves without a bond; every model of `top_k` gains the same numbers.  Nothing is ranked or
-    filtered by them."""
+    filtered by them.
+    `pair_potential` (pairpot.load's dict, or the path of such a file - the project ships no table): the tabulated pair potential of
+    every trajectory (ensemble_pairpot: the heavy atoms the file's type names fit).  The result gains `pair_potential` ({energy in
+    kcal/mol, n_pairs, n_untyped, T, NB, cutoff} of the kept pose), `pairpot_data` (the arrays and the rot_update / tr_update they are of), `index` and `trajectories`; every model
+    of `top_k` gains `pair_potential`.  rank="pairpot" (needs pair_potential) keeps the pose with the lowest energy instead (ties: lower
+    index; it overrides restraint_rank and becomes the clustering key of top_k)."""
     _check_rank(rank, consensus_top)
     dg = _check_distogram(model, distogram, rank, distogram_t, distogram_maps, max_batch)
     cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
@@ -1103,6 +1192,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     ie = _check_interface(interface_energy, rank, ie_weights, ie_cutoff)
     aff = _check_affinity(affinity, affinity_cutoff)
     hb = _check_hbonds(hbonds, hbond_cutoff, hbond_angle, salt_cutoff)
+    pp = _check_pairpot(pair_potential, rank)
     if native is not None:
         _check_native(native, rec, lig)
     if refine_t is not None and top_k is None:
@@ -1144,7 +1234,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     if not restrained:
         # the loop's own minimum; consensus and the screen choose among all trajectories at once (the first minimum: the same pose)
         pick = (np.argmin if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None or dg is not None
-                or hb is not None
+                or hb is not None or pp is not None
                 else (lambda energy: k0), "energy")
         key, entries = cols["energy"], lambda k: {}
     else:
@@ -1156,7 +1246,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         entries = lambda k: {"index": k, "restraints": len(restraints), "restraint_rank": restraint_rank,
                              "restraint_energy": float(cols["restraint_energy"][k]), "restraints_satisfied": int(cols["restraints_satisfied"][k]),
                              "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
-    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine, surf, ie, aff, dg, seed, hb)
+    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine, surf, ie, aff, dg, seed, hb, pp)
 
 
 def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
@@ -1164,7 +1254,8 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
                 restraint_params=None, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
                 clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, start_shift=None, bsa=False, min_bsa=None, probe=1.4,
                 sphere_points=128, interface_energy=False, ie_weights=None, ie_cutoff=8.0, affinity=False, affinity_cutoff=5.5, distogram=False,
-                distogram_t=DISTOGRAM_T, distogram_maps=False, hbonds=False, hbond_cutoff=3.5, hbond_angle=90.0, salt_cutoff=4.0, **sampler_kw):
+                distogram_t=DISTOGRAM_T, distogram_maps=False, hbonds=False, hbond_cutoff=3.5, hbond_angle=90.0, salt_cutoff=4.0, pair_potential=None,
+              **sampler_kw):
     """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories
     start from that pose noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps
     down from t_begin; like dock_pair the minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns
@@ -1177,6 +1268,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
     `affinity` / `affinity_cutoff`: as for dock_pair.
     `distogram` / `distogram_t` / `distogram_maps` and rank="distogram": as for dock_pair.
     `hbonds` / `hbond_cutoff` / `hbond_angle` / `salt_cutoff`: as for dock_pair.
+    `pair_potential` and rank="pairpot": as for dock_pair.
     `start_shift` ([num_samples,3]): trajectory i starts from the input pose translated by start_shift[i] (the engine's start_pos); the
     shift is added to its tr_update, so (rot_update, tr_update) keep mapping the INPUT pose onto the final one."""
     _check_rank(rank, consensus_top)
@@ -1187,6 +1279,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
     ie = _check_interface(interface_energy, rank, ie_weights, ie_cutoff)
     aff = _check_affinity(affinity, affinity_cutoff)
     hb = _check_hbonds(hbonds, hbond_cutoff, hbond_angle, salt_cutoff)
+    pp = _check_pairpot(pair_potential, rank)
     if native is not None:
         _check_native(native, rec, lig)
     if start_shift is not None:
@@ -1213,7 +1306,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
         done += b
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
     res = _finish(model, gx, rec, lig, cols, (np.argmin, "energy"), None,      # the first minimum wins, as in dock_pair
-                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster, surf=surf, ie=ie, aff=aff, dg=dg, seed=seed, hb=hb)
+                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster, surf=surf, ie=ie, aff=aff, dg=dg, seed=seed, hb=hb, pp=pp)
     if native is not None:
         res["start_metrics"] = native_metrics(model, native, rec["bb_coords"], gx.lig_pos0[None])[0]
     return res
@@ -1246,14 +1339,14 @@ def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps
 
 
 def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=None, bad=None, bd=None, min_bsa=None, ed=None, ad=None,
-                dd=None, hd=None):
+                dd=None, hd=None, pd=None):
     """dock_pair's `models`: the centres of up to top_k clusters in cluster order, each written as <out_pdb stem>_<rank>.pdb.  sd: the
     screen's data (every model gains `sterics`, every file a REMARK line); bad: poses the clash filter removed - their key is NaN, so they
     come last, and a cluster one of them would lead is left out.  bd: the surface data (every model gains bsa, bsa_rec, bsa_lig); min_bsa:
     a centre that buries less is left out as well, and `bsa_dropped` counts those.  ed: the interface-energy data (every model gains
     `interface_energy`); ad: the affinity data (every model gains `affinity`); dd: the distogram data (every model gains dist_nll,
     dist_nll_near, exp_contacts); hd: the hydrogen-bond data (every model gains n_hbond, hb_bb_bb, hb_bb_sc, hb_sc_sc, n_salt and, with the
-    surface, n_unsat)."""
+    surface, n_unsat); pd: the pair-potential data (every model gains `pair_potential`)."""
     top_k, radius, rule = clu
     cl = cluster_trajectories(model, lig0, cols["rot_update"], cols["tr_update"], key, radius, rule, top_k)
     models, dropped = [], 0
@@ -1278,6 +1371,8 @@ def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=
             models[-1].update(_pose_distogram(dd, c))
         if hd is not None:
             models[-1].update(_pose_hbonds(hd, c))
+        if pd is not None:
+            models[-1]["pair_potential"] = _pose_pairpot(pd, c)
         if out_pdb:
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c], center=_center(model))
             pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa, remarks=_remarks(sd, c))

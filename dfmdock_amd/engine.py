@@ -245,9 +245,16 @@ class Model:
         in one call."""
         return HBonds(self, rec, lig, center, hb_cutoff, min_angle, salt_cutoff)
 
+    def pairpot(self, rec_atoms, rec_type, lig_atoms, lig_type, center, edges, table):
+        """The heavy atoms of a pair with the type of every atom ([n] in [0, T); pairpot.atom_types) and a tabulated pair potential -
+        edges [NB+1] in A, table [T,T,NB] in kcal/mol indexed (ligand type, receptor type, bin); pairpot.load reads both from a file -
+        prepared for the pair-potential call on the GPU (dfm_pairpot_create).  The project ships no table.  Returns a PairPotential
+        whose `.energy(rot, tr)` takes P poses in one call."""
+        return PairPotential(self, rec_atoms, rec_type, lig_atoms, lig_type, center, edges, table)
+
 
 class _Handle:
-    """What Native, Atoms, Surface, Interface, Contacts and HBonds share: a handle `_h` made by dfm_<_kind>_create and freed by dfm_<_kind>_destroy - close(), a context
+    """What Native, Atoms, Surface, Interface, Contacts, HBonds and PairPotential share: a handle `_h` made by dfm_<_kind>_create and freed by dfm_<_kind>_destroy - close(), a context
     manager, closed when collected."""
     _kind = None
 
@@ -573,6 +580,63 @@ class HBonds(_Handle):
             setattr(out, k, _p(v, L.I32P))
         L.check(L.lib().dfm_pose_hbonds_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_hbonds")
         return o
+
+
+class PairPotential(_Handle):
+    """The heavy atoms of a receptor / ligand pair with their types, the squared bin edges and the quantised table resident on the
+    model's GPU (dfm_pairpot).  Read-only after creation: `energy` may be called from several threads at once."""
+    _kind = "pairpot"
+
+    def __init__(self, model: Model, rec_atoms, rec_type, lig_atoms, lig_type, center, edges, table):
+        from . import pairpot as PP
+        ra, la, cen = _f32(rec_atoms).reshape(-1, 3), _f32(lig_atoms).reshape(-1, 3), _center(center)
+        e = np.ascontiguousarray(PP.check_edges(edges))
+        tb = np.ascontiguousarray(PP.check_table(table, e.size - 1))
+        self.model, self.Ar, self.Al, self.T, self.NB = model, ra.shape[0], la.shape[0], tb.shape[0], e.size - 1
+        rt = np.ascontiguousarray(PP.check_types(rec_type, self.Ar, self.T, "rec_type"))
+        lt = np.ascontiguousarray(PP.check_types(lig_type, self.Al, self.T, "lig_type"))
+        self.cutoff = float(e[-1])
+        self._h = L.lib().dfm_pairpot_create(model._h, self.Ar, _p(ra), _p(rt, L.I32P), self.Al, _p(la), _p(lt, L.I32P), _p(cen), self.T,
+                                             self.NB, _p(e), _p(tb), 0)
+        self._created()
+
+    def info(self):
+        """{n_cells, max_cell_atoms, cell_edge} of the receptor's grid, pair_bound = the creator's bound on the pairs of one pose, T and
+        NB (dfm_pairpot_info)."""
+        n, mx, e, b, T, NB = C.c_int32(0), C.c_int32(0), C.c_float(0), C.c_double(0), C.c_int32(0), C.c_int32(0)
+        L.check(L.lib().dfm_pairpot_info(self._h, C.byref(n), C.byref(mx), C.byref(e), C.byref(b), C.byref(T), C.byref(NB)), "dfm_pairpot_info")
+        return {**_grid_info(n, mx, e), "pair_bound": b.value, "T": T.value, "NB": NB.value}
+
+    def energy(self, rot, tr, per_atom=False, counts=False, chunk_poses=0):
+        """Pair potential of P poses (dfm_pose_pairpot; the float64 definition is pairpot.pair_potential): rot [P,3] axis-angle and tr
+        [P,3] as rot_update / tr_update hold them.  Returns {energy_q, n_pairs (int64 [P]; quanta of 2^-20 kcal/mol)}, with `per_atom`
+        lig_q (int64 [P,Al], the caller's atom order), with `counts` counts (int32 [P,T,T,NB]: ligand type, receptor type, bin - one
+        global atomic per pair, the slow path), and energy (float64 [P], kcal/mol = energy_q * 2^-20)."""
+        from . import pairpot as PP
+        r, t, P = _rigid_poses(rot, tr)
+        o = {"energy_q": np.zeros(P, np.int64), "n_pairs": np.zeros(P, np.int64)}
+        if per_atom:
+            o["lig_q"] = np.zeros((P, self.Al), np.int64)
+        out = L.PairpotOutC()
+        for k, v in o.items():
+            setattr(out, k, v.ctypes.data_as(C.POINTER(C.c_int64)))
+        if counts:
+            o["counts"] = np.zeros((P, self.T, self.T, self.NB), np.int32)
+            out.counts = _p(o["counts"], L.I32P)
+        L.check(L.lib().dfm_pose_pairpot_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_pairpot")
+        o["energy"] = PP.kcal(o["energy_q"])
+        return o
+
+
+def pairpot_last_timing():
+    """(host-to-device copy ms, kernel ms) of this thread's last PairPotential.energy call (dfm_pairpot_last_timing)."""
+    return _last_ms("dfm_pairpot_last_timing", 2)
+
+
+def pairpot_last_phases():
+    """(memsets ms, walk ms, finish ms - the call has no finishing kernel) of this thread's last PairPotential.energy call: its kernel
+    time by phase (dfm_pairpot_last_phases)."""
+    return _last_ms("dfm_pairpot_last_phases", 3)
 
 
 def hbond_last_timing():

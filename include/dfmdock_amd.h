@@ -653,6 +653,58 @@ int dfm_hbond_last_timing(double *copy_ms, double *kernel_ms);
 /* The kernel milliseconds of that call by phase, from the call's own events: the memsets, the walk (k_hbond_pose, k_hbond) and
  * k_hbond_finish; their sum is kernel_ms */
 int dfm_hbond_last_phases(double *zero_ms, double *walk_ms, double *finish_ms);
+/* Tabulated pair potential of P rigid poses of one ligand, E = the sum over heavy-atom pairs of table[type_a][type_b][bin(r)] - the
+ * shape of DFIRE, DOPE, ITScore-PP, ZRANK's ACE term or a table fitted to one's own decoys - and, optionally, the pair counts
+ * N[type_a][type_b][bin] such a potential is a linear function of.  The library ships NO table: the table, its edges and the types come
+ * from the caller, and nothing is claimed about the ranking quality of any potential.  dfmdock_amd/pairpot.py is the float64 definition
+ * these calls are tested against.  Atoms, centre and poses as for dfm_atoms_create / dfm_pose_sterics.  rec_type [Ar] / lig_type [Al]:
+ * the type of each atom, in [0, T), 1 <= T <= 256.  edges [NB+1]: 1 <= NB <= 64, finite, strictly ascending, edges[0] >= 0, edges[NB] <=
+ * 16 (A); the cutoff is edges[NB].  table [T,T,NB]: kcal/mol, indexed (LIGAND type, RECEPTOR type, bin), finite, |x| <= 1024; it need
+ * not be symmetric.
+ *   table_q = (int64) rint((double) table * 2^20), ties to even: quanta of 2^-20 kcal/mol, |q| <= 2^30.
+ *   e2[k] = (double) edges[k] * (double) edges[k], which is exact.  Per pair, fp64 on the widened fp32 receptor atom and the fp64 ligand
+ *     atom of the pose: r2 = (dx*dx + dy*dy) + dz*dz; the pair counts iff e2[0] <= r2 < e2[NB] (a NaN is no pair); its bin is
+ *     k = #{j : e2[j] <= r2} - 1.  No square root is taken anywhere.
+ *   energy_q [P]: the int64 sum of table_q[ta][tb][k] over the pose's pairs; n_pairs [P]: their number, also where the table holds 0;
+ *     lig_q [P,Al]: the same sum per ligand atom, in the caller's atom order; counts [P,T,T,NB]: the pairs by (ligand type, receptor
+ *     type, bin), so that sum(counts) = n_pairs and <counts, table_q> = energy_q.  kcal/mol = q * 2^-20.
+ *   A pose with a NaN or infinite rot / tr gets zeros and disturbs no other pose (not an error).
+ * Every output pointer may be NULL.  Everything is an integer sum: the results equal the definition's, and none depends on P, on a
+ * pose's index, on the order of the poses or on the chunks of a call.  counts costs one global atomic per pair and is the slow path; a
+ * call without it runs a kernel that holds none of that code.  dfm_pairpot_create bins the receptor into cells of edges[NB] and refuses
+ * a complex whose poses could have more than 2^31 - 1 pairs in range - pairs of one pose <= Al min(Ar, 27 max_cell_atoms)
+ * (dfm_poseprep.h: pairpot_pair_bound) - so that counts fits int32 and |energy_q| < 2^61; dfm_pairpot_info reports cells, the most
+ * atoms in one cell, the cell edge, that bound, T and NB.  A call works through chunk_poses poses at a time (0: the creator's, and if
+ * that is 0 too as many as fill 64 MiB of counts plus lig_q, whichever the call asks for; without either 32768).
+ * DFM_E_INVALID / NULL, nothing enqueued, the first of these in this order: a NULL m; a NULL atom set or centre, Ar or Al < 1 or > 2^24,
+ * a non-finite atom or centre; a NULL rec_type or lig_type; T outside 1 .. 256; NB outside 1 .. 64, NULL edges, an edge that is not
+ * finite, not above its predecessor, below 0 or above 16; a NULL table, an entry that is not finite or above 1024 in magnitude; a type
+ * out of range (receptor first); chunk_poses < 0; a receptor bounding box of more than 2^24 cells; the pair bound; a ligand whose
+ * extent about the centre overflows fp32.  For a call: a NULL h, rot, tr or out, P < 1, chunk_poses < 0.  DFM_E_OOM when the atoms, the
+ * table or a chunk's output do not fit.
+ * Takes the MODEL handle for its device only.  The handle is read-only after creation; every call owns a non-blocking stream and its
+ * device temporaries, so calls on one handle may run from several host threads at once.  No reference call has a counterpart. */
+typedef struct dfm_pairpot dfm_pairpot;
+typedef struct {
+    int64_t *energy_q;                  /* [P]        or NULL */
+    int64_t *n_pairs;                   /* [P]        or NULL */
+    int64_t *lig_q;                     /* [P,Al]     or NULL */
+    int32_t *counts;                    /* [P,T,T,NB] or NULL */
+} dfm_pairpot_out;
+dfm_pairpot *dfm_pairpot_create(dfm_model *m, int Ar, const float *rec_atoms, const int32_t *rec_type, int Al, const float *lig_atoms,
+                                const int32_t *lig_type, const float center[3], int T, int NB, const float *edges, const float *table,
+                                int chunk_poses);
+void dfm_pairpot_destroy(dfm_pairpot *h);
+int dfm_pairpot_info(const dfm_pairpot *h, int32_t *n_cells, int32_t *max_cell_atoms, float *cell_edge, double *pair_bound, int32_t *T,
+                     int32_t *NB);
+int dfm_pose_pairpot(dfm_pairpot *h, int P, const float *rot, const float *tr, dfm_pairpot_out *out);
+int dfm_pose_pairpot_chunked(dfm_pairpot *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_pairpot_out *out);
+/* GPU milliseconds of the calling thread's last dfm_pose_pairpot, summed over its chunks: the host-to-device copies of the poses and the
+ * kernels (the memsets of lig_q and counts, k_pairpot_pose, k_pairpot) - tools/pairpot_bench.py */
+int dfm_pairpot_last_timing(double *copy_ms, double *kernel_ms);
+/* The kernel milliseconds of that call by phase, from the call's own events: the memsets, the walk (k_pairpot_pose, k_pairpot) and the
+ * finish, which this call does not have (about 0); their sum is kernel_ms */
+int dfm_pairpot_last_phases(double *zero_ms, double *walk_ms, double *finish_ms);
 /* edges per node for this complex: min(N,20) + min(40, N-20) */
 int dfm_complex_degree(const dfm_complex *cx);
 /* Device blocks released by destroyed handles are parked per device for the next handle (a set driver creates and destroys a
