@@ -37,7 +37,7 @@ __device__ inline double wave_sum(double v)
 template <int p, int q> __device__ inline void jacobi_rot(double (&a)[4][4], double (&v)[4][4])
 {
     const double apq = a[p][q];
-    if (!(fabs(apq) > 0.0)) return;      // also NaN: nothing to do, the NaN reaches the outputs through the residuals
+    if (!(fabs(apq) > 0.0)) return;      // also NaN: nothing to do, k_metrics_solve makes the whole fit NaN
     const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
     const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
     const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
@@ -189,6 +189,17 @@ __global__ __launch_bounds__(64) void k_metrics_solve(const double *__restrict__
                 M[i][j] = c - S[i] * (T[j] * inv);
             }
         horn_rotation(M, r);
+        // a NaN or an infinity in M: the Jacobi sweeps skip what they cannot order and would hand back a finite rotation; the fit is
+        // undefined, so all of it is NaN (0 x M is 0 for every finite entry: finite fits keep their bits)
+        double undefined = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) undefined += 0.0 * M[i][j];
+        if (!(undefined == 0.0)) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) r[k] = __longlong_as_double(0x7ff8000000000000LL);
+        }
 #pragma unroll
         for (int k = 0; k < 9; ++k) dst[k] = r[k];
 #pragma unroll
