@@ -1,5 +1,7 @@
-// dfm_posewalk.h - what the per-pose all-atom kernels share (kernels_sterics.hip, kernels_surface.hip, kernels_iface.hip): a rigid ligand pose against a
-// receptor whose atoms are sorted by cell of a uniform grid (dfm_walkgrid.h).  Device code.
+// dfm_posewalk.h - what the six per-pose all-atom kernels share (kernels_sterics.hip, kernels_surface.hip, kernels_iface.hip,
+// kernels_rescon.hip, kernels_hbond.hip, kernels_pairpot.hip): a rigid ligand pose against a receptor whose atoms are sorted by cell
+// of a uniform grid (dfm_walkgrid.h).  Device code.  tests/test_gpu_pose_kernels.py holds every step below to a float64 restatement,
+// bitwise.
 //
 // A pose is 24 bytes: (rot, tr) of the sampler.  Pose p of ligand atom a is (a - center) R(rot_p)^T + center + tr_p in fp64.  One wave
 // takes a (pose, block of 64 ligand atoms).  In this order:
@@ -13,7 +15,8 @@
 //      bank conflict, one ds_read_b128 per receptor atom for 64 pairs).  Letting each lane walk its own 27 cells instead would test about
 //      a sixth of the pairs, but with 64 different cell ranges per wave: every load a scattered gather, every loop as long as the wave's
 //      longest lane.  The staged form keeps the wave converged up to the kernel's fp64 part: a per-lane branch that few pairs take in
-//      k_sterics and k_surface, the whole wave's converged evaluation behind one wave-uniform test in k_iface, where many pairs pass.
+//      k_sterics, k_surface, k_rescon and k_hbond, the whole wave's converged evaluation behind one wave-uniform test in k_iface and
+//      k_pairpot, where many pairs pass.
 //
 // The fp32 reject of the kernels: a pair is dropped without the fp64 arithmetic only when d2 > (reach * 1.0001f + slack)^2 with d2 taken
 // in fp32 from the fp32 copy of the ligand atom (reach: the contact cutoff, R_a + R_b, or the energy cutoff, at most 16 A); written as !(d2 > ...) for the pairs that go
