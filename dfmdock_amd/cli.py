@@ -120,6 +120,7 @@ import argparse
 import json
 import os
 import sys
+from typing import Callable, NamedTuple
 
 import numpy as np
 
@@ -263,14 +264,8 @@ def build_parser():
                    help="with --top-k: refine every cluster centre locally from t_begin = T (one batched call)")
     d.add_argument("--refine-samples", type=int, default=8, metavar="n", help="with --refine-t: trajectories per cluster centre")
     _add_native(d)
-    _add_consensus(d)
-    _add_distogram(d)
-    _add_sterics(d)
-    _add_surface(d)
-    _add_interface(d)
-    _add_pairpot(d)
-    _add_affinity(d)
-    _add_hbonds(d)
+    for a in ANALYSES:
+        a.add(d)
     _add_common(d)
     r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)")
     r.add_argument("pdb_1", help="receptor PDB")
@@ -283,14 +278,8 @@ def build_parser():
     r.add_argument("--json", default=None, help="also write the result line to this file")
     r.add_argument("--restraints", default=None, help="interface restraint file (as for dock)")
     _add_native(r)
-    _add_consensus(r)
-    _add_distogram(r)
-    _add_sterics(r)
-    _add_surface(r)
-    _add_interface(r)
-    _add_pairpot(r)
-    _add_affinity(r)
-    _add_hbonds(r)
+    for a in ANALYSES:
+        a.add(r)
     _add_common(r)
     s = sub.add_parser("sweep", help="sample every complex of a DB5-style directory (inference_mlsb.py run_sampling)")
     s.add_argument("--db5", required=True, help="directory of <id>.pt files (+ optional test.txt with the ids to run)")
@@ -334,80 +323,10 @@ def parse_args(argv=None):
     if args.cmd == "sweep" and args.step_metrics is not None:
         args.metrics = "gpu"
     if args.cmd in ("dock", "refine"):
-        if args.rank == "consensus" or args.contact_map or args.write_restraints:
-            args.consensus = True
-        if args.rank == "distogram" or args.distogram_map or args.distogram_restraints:
-            args.distogram = True
-        if not args.distogram and args.distogram_t is not None:
-            ap.error("--distogram-t is the time of the --distogram evaluation: it needs it")
-        args.distogram_t = 1e-3 if args.distogram_t is None else args.distogram_t
-        if not (0.0 < args.distogram_t <= 1.0):
-            ap.error("--distogram-t must be in (0, 1]")
-        if not (args.write_restraints or args.distogram_restraints) and (args.restraint_top is not None or args.restraint_upper is not None):
-            ap.error("--restraint-top / --restraint-upper describe the file of --write-restraints / --distogram-restraints: they need one")
-        args.restraint_top = 10 if args.restraint_top is None else args.restraint_top
-        args.restraint_upper = 8.0 if args.restraint_upper is None else args.restraint_upper
-        if args.restraint_top < 1:
-            ap.error("--restraint-top must be >= 1")
-        if not (args.restraint_upper > 0 and np.isfinite(args.restraint_upper)):
-            ap.error("--restraint-upper must be finite and > 0")
-    if args.cmd in ("dock", "refine"):
-        if args.clash_filter or args.clash_residues:
-            args.clash_screen = True
-        if not args.clash_screen and (args.clash_cutoff is not None or args.contact_cutoff is not None):
-            ap.error("--clash-cutoff / --contact-cutoff are the cutoffs of --clash-screen: they need it")
-        args.clash_cutoff = 3.0 if args.clash_cutoff is None else args.clash_cutoff
-        args.contact_cutoff = 5.0 if args.contact_cutoff is None else args.contact_cutoff
-        if not (np.isfinite(args.clash_cutoff) and np.isfinite(args.contact_cutoff) and 0 < args.clash_cutoff <= args.contact_cutoff):
-            ap.error("need 0 < --clash-cutoff <= --contact-cutoff, both finite")
-    if args.cmd in ("dock", "refine"):
-        if args.min_bsa is not None or args.interface_residues:
-            args.bsa = True
-        if not args.bsa and (args.probe is not None or args.sphere_points is not None):
-            ap.error("--probe / --sphere-points describe the surface of --bsa: they need it")
-        args.probe = 1.4 if args.probe is None else args.probe
-        args.sphere_points = 128 if args.sphere_points is None else args.sphere_points
-        if not (np.isfinite(args.probe) and args.probe > 0):
-            ap.error("--probe must be finite and > 0")
-        if args.sphere_points < 64 or args.sphere_points > 256 or args.sphere_points % 64:
-            ap.error("--sphere-points must be a multiple of 64 in 64 .. 256")
-        if args.min_bsa is not None and not np.isfinite(args.min_bsa):
-            ap.error("--min-bsa must be finite")
-    if args.cmd in ("dock", "refine"):
-        if args.rank == "interface" or args.energy_residues:
-            args.interface_energy = True
-        if not args.interface_energy and (args.ie_weights is not None or args.ie_cutoff is not None):
-            ap.error("--ie-weights / --ie-cutoff describe --interface-energy: they need it")
-        args.ie_cutoff = 8.0 if args.ie_cutoff is None else args.ie_cutoff
-        if not (np.isfinite(args.ie_cutoff) and 0 < args.ie_cutoff <= 16):
-            ap.error("--ie-cutoff must be in (0, 16]")
-        if args.ie_weights is not None and not np.isfinite(args.ie_weights).all():
-            ap.error("--ie-weights must be finite")
-    if args.cmd in ("dock", "refine"):
-        if args.pair_potential is None and (args.rank == "pairpot" or args.pairpot_residues or args.pair_counts):
-            ap.error("--rank pairpot / --pairpot-residues / --pair-counts need --pair-potential FILE.npz: no table is shipped")
+        for a in ANALYSES:
+            a.check(ap, args)
     elif getattr(args, "rank", None) == "pairpot":
         ap.error("--rank pairpot is offered by dock and refine")
-    if args.cmd in ("dock", "refine"):
-        if args.contact_residues:
-            args.affinity = True
-        if not args.affinity and args.affinity_cutoff is not None:
-            ap.error("--affinity-cutoff is the cutoff of --affinity: it needs it")
-        args.affinity_cutoff = 5.5 if args.affinity_cutoff is None else args.affinity_cutoff
-        if not (np.isfinite(args.affinity_cutoff) and 0 < args.affinity_cutoff <= 16):
-            ap.error("--affinity-cutoff must be in (0, 16]")
-    if args.cmd in ("dock", "refine"):
-        if args.hbond_residues:
-            args.hbonds = True
-        if not args.hbonds and (args.hbond_cutoff is not None or args.hbond_angle is not None or args.salt_cutoff is not None):
-            ap.error("--hbond-cutoff / --hbond-angle / --salt-cutoff describe --hbonds: they need it")
-        args.hbond_cutoff = 3.5 if args.hbond_cutoff is None else args.hbond_cutoff
-        args.hbond_angle = 90.0 if args.hbond_angle is None else args.hbond_angle
-        args.salt_cutoff = 4.0 if args.salt_cutoff is None else args.salt_cutoff
-        if not (np.isfinite(args.hbond_cutoff) and 0 < args.hbond_cutoff <= 8 and np.isfinite(args.salt_cutoff) and 0 < args.salt_cutoff <= 8):
-            ap.error("--hbond-cutoff and --salt-cutoff must be in (0, 8]")
-        if not (90.0 <= args.hbond_angle < 180.0):
-            ap.error("--hbond-angle must be in [90, 180)")
     if args.cmd in ("dock", "refine", "sweep"):
         if args.consensus_top is not None and not args.consensus:
             ap.error("--consensus-top selects the members of the consensus ensemble: it needs --consensus")
@@ -485,14 +404,19 @@ def residue_labels(chain):
     return np.array([f"{k[0]}:{int(k[1])}{k[2] if k[2] != ' ' else ''}" for k in chain["residues"]])
 
 
-def consensus_kwargs(args):
+def check_consensus(ap, args):
+    if args.rank == "consensus" or args.contact_map or args.write_restraints:
+        args.consensus = True
+
+
+def consensus_kwargs(args, model=None):
     """Driver keyword arguments of the consensus flags of dock / refine: none without them."""
     if not args.consensus:
         return {}
     return dict(consensus=True, rank=args.rank, consensus_top=args.consensus_top)
 
 
-def consensus_outputs(args, res, rec, lig, line):
+def consensus_outputs(args, model, res, rec, lig, line, kw):
     """The consensus part of a dock / refine result: the `consensus` object of the line, --contact-map and --write-restraints."""
     if not args.consensus:
         return
@@ -511,7 +435,26 @@ def consensus_outputs(args, res, rec, lig, line):
         line.update(restraints_written=os.path.abspath(args.write_restraints), restraints_written_n=len(groups))
 
 
-def distogram_kwargs(args, model):
+def check_distogram(ap, args):
+    if args.rank == "distogram" or args.distogram_map or args.distogram_restraints:
+        args.distogram = True
+    if not args.distogram and args.distogram_t is not None:
+        ap.error("--distogram-t is the time of the --distogram evaluation: it needs it")
+    args.distogram_t = 1e-3 if args.distogram_t is None else args.distogram_t
+    if not (0.0 < args.distogram_t <= 1.0):
+        ap.error("--distogram-t must be in (0, 1]")
+    # the file of --write-restraints / --distogram-restraints: checked here, once both have been implied
+    if not (args.write_restraints or args.distogram_restraints) and (args.restraint_top is not None or args.restraint_upper is not None):
+        ap.error("--restraint-top / --restraint-upper describe the file of --write-restraints / --distogram-restraints: they need one")
+    args.restraint_top = 10 if args.restraint_top is None else args.restraint_top
+    args.restraint_upper = 8.0 if args.restraint_upper is None else args.restraint_upper
+    if args.restraint_top < 1:
+        ap.error("--restraint-top must be >= 1")
+    if not (args.restraint_upper > 0 and np.isfinite(args.restraint_upper)):
+        ap.error("--restraint-upper must be finite and > 0")
+
+
+def distogram_kwargs(args, model=None):
     """Driver keyword arguments of the distogram flags of dock / refine: none without them.  The head exists in the second model
     family only: a first-family checkpoint with any of the flags ends the command here, before anything is sampled."""
     if not args.distogram:
@@ -523,7 +466,7 @@ def distogram_kwargs(args, model):
                 distogram_maps=bool(args.distogram_map or args.distogram_restraints))
 
 
-def distogram_outputs(args, res, rec, lig, line):
+def distogram_outputs(args, model, res, rec, lig, line, kw):
     """The distogram part of a dock / refine result: dist_nll, dist_nll_near, exp_contacts of the line (the models carry theirs),
     --distogram-map and --distogram-restraints."""
     if not args.distogram:
@@ -547,14 +490,25 @@ def distogram_outputs(args, res, rec, lig, line):
         line.update(distogram_restraints=os.path.abspath(args.distogram_restraints), distogram_restraints_n=len(groups))
 
 
-def sterics_kwargs(args):
+def check_sterics(ap, args):
+    if args.clash_filter or args.clash_residues:
+        args.clash_screen = True
+    if not args.clash_screen and (args.clash_cutoff is not None or args.contact_cutoff is not None):
+        ap.error("--clash-cutoff / --contact-cutoff are the cutoffs of --clash-screen: they need it")
+    args.clash_cutoff = 3.0 if args.clash_cutoff is None else args.clash_cutoff
+    args.contact_cutoff = 5.0 if args.contact_cutoff is None else args.contact_cutoff
+    if not (np.isfinite(args.clash_cutoff) and np.isfinite(args.contact_cutoff) and 0 < args.clash_cutoff <= args.contact_cutoff):
+        ap.error("need 0 < --clash-cutoff <= --contact-cutoff, both finite")
+
+
+def sterics_kwargs(args, model=None):
     """Driver keyword arguments of the screen flags of dock / refine: none without them."""
     if not args.clash_screen:
         return {}
     return dict(clash_screen=True, clash_filter=args.clash_filter, clash_cutoff=args.clash_cutoff, contact_cutoff=args.contact_cutoff)
 
 
-def sterics_outputs(args, model, res, rec, lig, line):
+def sterics_outputs(args, model, res, rec, lig, line, kw):
     """The screen's part of a dock / refine result: the `sterics` object of the line and --clash-residues."""
     if not args.clash_screen:
         return
@@ -567,14 +521,31 @@ def sterics_outputs(args, model, res, rec, lig, line):
         line.update(clash_residues=os.path.abspath(args.clash_residues))
 
 
-def interface_kwargs(args):
+def check_interface(ap, args):
+    if args.rank == "interface" or args.energy_residues:
+        args.interface_energy = True
+    if not args.interface_energy and (args.ie_weights is not None or args.ie_cutoff is not None):
+        ap.error("--ie-weights / --ie-cutoff describe --interface-energy: they need it")
+    args.ie_cutoff = 8.0 if args.ie_cutoff is None else args.ie_cutoff
+    if not (np.isfinite(args.ie_cutoff) and 0 < args.ie_cutoff <= 16):
+        ap.error("--ie-cutoff must be in (0, 16]")
+    if args.ie_weights is not None and not np.isfinite(args.ie_weights).all():
+        ap.error("--ie-weights must be finite")
+
+
+def interface_kwargs(args, model=None):
     """Driver keyword arguments of the interface-energy flags of dock / refine: none without them."""
     if not args.interface_energy:
         return {}
     return dict(interface_energy=True, ie_weights=args.ie_weights, ie_cutoff=args.ie_cutoff, rank=args.rank)
 
 
-def pairpot_kwargs(args):
+def check_pairpot(ap, args):
+    if args.pair_potential is None and (args.rank == "pairpot" or args.pairpot_residues or args.pair_counts):
+        ap.error("--rank pairpot / --pairpot-residues / --pair-counts need --pair-potential FILE.npz: no table is shipped")
+
+
+def pairpot_kwargs(args, model=None):
     """Driver keyword arguments of the pair-potential flags of dock / refine: none without them.  The file is read here, once."""
     if args.pair_potential is None:
         return {}
@@ -582,12 +553,13 @@ def pairpot_kwargs(args):
     return dict(pair_potential=load(args.pair_potential), rank=args.rank)
 
 
-def pairpot_outputs(args, model, res, rec, lig, line, pot):
+def pairpot_outputs(args, model, res, rec, lig, line, kw):
     """The pair-potential part of a dock / refine result: the `pair_potential` object of the line, --pairpot-residues and --pair-counts
     (the kept pose first, then the models in their order)."""
     if args.pair_potential is None:
         return
     line.update(pair_potential=res["pair_potential"], index=res["index"])
+    pot = kw["pair_potential"]      # as pairpot_kwargs read it
     if args.pairpot_residues:
         from . import driver
         from .pairpot import write_pairpot_residues
@@ -605,7 +577,7 @@ def pairpot_outputs(args, model, res, rec, lig, line, pot):
         line.update(pair_counts=os.path.abspath(args.pair_counts))
 
 
-def interface_outputs(args, model, res, rec, lig, line):
+def interface_outputs(args, model, res, rec, lig, line, kw):
     """The interface-energy part of a dock / refine result: the `interface_energy` object of the line and --energy-residues."""
     if not args.interface_energy:
         return
@@ -618,14 +590,24 @@ def interface_outputs(args, model, res, rec, lig, line):
         line.update(energy_residues=os.path.abspath(args.energy_residues))
 
 
-def affinity_kwargs(args):
+def check_affinity(ap, args):
+    if args.contact_residues:
+        args.affinity = True
+    if not args.affinity and args.affinity_cutoff is not None:
+        ap.error("--affinity-cutoff is the cutoff of --affinity: it needs it")
+    args.affinity_cutoff = 5.5 if args.affinity_cutoff is None else args.affinity_cutoff
+    if not (np.isfinite(args.affinity_cutoff) and 0 < args.affinity_cutoff <= 16):
+        ap.error("--affinity-cutoff must be in (0, 16]")
+
+
+def affinity_kwargs(args, model=None):
     """Driver keyword arguments of the affinity flags of dock / refine: none without them."""
     if not args.affinity:
         return {}
     return dict(affinity=True, affinity_cutoff=args.affinity_cutoff)
 
 
-def affinity_outputs(args, model, res, rec, lig, line):
+def affinity_outputs(args, model, res, rec, lig, line, kw):
     """The affinity part of a dock / refine result: the `affinity` object of the line and --contact-residues."""
     if not args.affinity:
         return
@@ -640,14 +622,28 @@ def affinity_outputs(args, model, res, rec, lig, line):
         line.update(contact_residues=os.path.abspath(args.contact_residues))
 
 
-def hbonds_kwargs(args):
+def check_hbonds(ap, args):
+    if args.hbond_residues:
+        args.hbonds = True
+    if not args.hbonds and (args.hbond_cutoff is not None or args.hbond_angle is not None or args.salt_cutoff is not None):
+        ap.error("--hbond-cutoff / --hbond-angle / --salt-cutoff describe --hbonds: they need it")
+    args.hbond_cutoff = 3.5 if args.hbond_cutoff is None else args.hbond_cutoff
+    args.hbond_angle = 90.0 if args.hbond_angle is None else args.hbond_angle
+    args.salt_cutoff = 4.0 if args.salt_cutoff is None else args.salt_cutoff
+    if not (np.isfinite(args.hbond_cutoff) and 0 < args.hbond_cutoff <= 8 and np.isfinite(args.salt_cutoff) and 0 < args.salt_cutoff <= 8):
+        ap.error("--hbond-cutoff and --salt-cutoff must be in (0, 8]")
+    if not (90.0 <= args.hbond_angle < 180.0):
+        ap.error("--hbond-angle must be in [90, 180)")
+
+
+def hbonds_kwargs(args, model=None):
     """Driver keyword arguments of the hydrogen-bond flags of dock / refine: none without them."""
     if not args.hbonds:
         return {}
     return dict(hbonds=True, hbond_cutoff=args.hbond_cutoff, hbond_angle=args.hbond_angle, salt_cutoff=args.salt_cutoff)
 
 
-def hbonds_outputs(args, model, res, rec, lig, line):
+def hbonds_outputs(args, model, res, rec, lig, line, kw):
     """The hydrogen-bond part of a dock / refine result: the counts of the line (the models carry theirs already), one note on stderr
     when polar atoms could not be typed, and --hbond-residues."""
     if not args.hbonds:
@@ -673,14 +669,29 @@ def hbonds_outputs(args, model, res, rec, lig, line):
             write(f"{stem}_{m['rank']}{ext}", t["rot_update"][m["index"]], t["tr_update"][m["index"]])
 
 
-def surface_kwargs(args):
+def check_surface(ap, args):
+    if args.min_bsa is not None or args.interface_residues:
+        args.bsa = True
+    if not args.bsa and (args.probe is not None or args.sphere_points is not None):
+        ap.error("--probe / --sphere-points describe the surface of --bsa: they need it")
+    args.probe = 1.4 if args.probe is None else args.probe
+    args.sphere_points = 128 if args.sphere_points is None else args.sphere_points
+    if not (np.isfinite(args.probe) and args.probe > 0):
+        ap.error("--probe must be finite and > 0")
+    if args.sphere_points < 64 or args.sphere_points > 256 or args.sphere_points % 64:
+        ap.error("--sphere-points must be a multiple of 64 in 64 .. 256")
+    if args.min_bsa is not None and not np.isfinite(args.min_bsa):
+        ap.error("--min-bsa must be finite")
+
+
+def surface_kwargs(args, model=None):
     """Driver keyword arguments of the surface flags of dock / refine: none without them."""
     if not args.bsa:
         return {}
     return dict(bsa=True, min_bsa=args.min_bsa, probe=args.probe, sphere_points=args.sphere_points)
 
 
-def surface_outputs(args, model, res, rec, lig, line):
+def surface_outputs(args, model, res, rec, lig, line, kw):
     """The surface part of a dock / refine result: the areas of the line and --interface-residues."""
     if not args.bsa:
         return
@@ -789,101 +800,73 @@ def _format_table_clustered(per, table, top_k):
     return "\n".join(lines)
 
 
-def cmd_dock(args):
+class _Flags(NamedTuple):
+    """The command-line side of one per-pose analysis of dock / refine."""
+    add: Callable          # (subparser): its flags
+    check: Callable        # (ap, args): what its flags imply, their defaults and their errors
+    kwargs: Callable       # (args, model) -> its driver keyword arguments: none without its flags
+    outputs: Callable      # (args, model, res, rec, lig, line, kw): its entries of the result line and its files
+
+
+# in the order of the flags in --help and of the entries in the result line
+ANALYSES = (
+    _Flags(_add_consensus, check_consensus, consensus_kwargs, consensus_outputs),
+    _Flags(_add_distogram, check_distogram, distogram_kwargs, distogram_outputs),
+    _Flags(_add_sterics, check_sterics, sterics_kwargs, sterics_outputs),
+    _Flags(_add_surface, check_surface, surface_kwargs, surface_outputs),
+    _Flags(_add_interface, check_interface, interface_kwargs, interface_outputs),
+    _Flags(_add_pairpot, check_pairpot, pairpot_kwargs, pairpot_outputs),
+    _Flags(_add_affinity, check_affinity, affinity_kwargs, affinity_outputs),
+    _Flags(_add_hbonds, check_hbonds, hbonds_kwargs, hbonds_outputs),
+)
+
+
+def cmd_pair(args):
+    """dock and refine: one body; they differ in their own driver keywords, their own entries of the line and what --json adds."""
     from . import driver
+    dock = args.cmd == "dock"
     model, _ = load_model(args)
     rec, lig, rec_x, lig_x = load_pair(args.pdb_1, args.pdb_2, args.features, model.hp.lm_embed_dim)
-    kw = {}
+    kw = {} if dock else dict(t_begin=args.t_begin, perturb=not args.no_perturb)
     if args.restraints:
         from .restraints import read_restraints
-        kw = dict(restraints=read_restraints(args.restraints, rec, lig), restraint_rank=args.restraint_rank)
-    if args.top_k is not None:
+        kw.update(restraints=read_restraints(args.restraints, rec, lig), **({"restraint_rank": args.restraint_rank} if dock else {}))
+    if dock and args.top_k is not None:
         kw.update(top_k=args.top_k, cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule)
-    if args.refine_t is not None:
+    if dock and args.refine_t is not None:
         kw.update(refine_t=args.refine_t, refine_samples=args.refine_samples)
     if args.native:
         kw.update(native=load_native(args.native))
-    kw.update(consensus_kwargs(args))
-    kw.update(distogram_kwargs(args, model))
-    kw.update(sterics_kwargs(args))
-    kw.update(surface_kwargs(args))
-    kw.update(interface_kwargs(args))
-    kw.update(pairpot_kwargs(args))
-    kw.update(affinity_kwargs(args))
-    kw.update(hbonds_kwargs(args))
-    res = driver.dock_pair(model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed,
-                           precision=args.precision, out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck,
-                           on_selfcheck_fail=args.on_selfcheck_fail, **kw)
-    line = {"energy": res["energy"], "output": os.path.abspath(args.out), "num_samples": args.num_samples, "precision": res["precision"],
-            "rot_update": [float(v) for v in res["rot_update"]], "tr_update": [float(v) for v in res["tr_update"]],
-            "selfcheck_ok": None if res["selfcheck"] is None else bool(res["selfcheck"]["ok"])}
-    if args.restraints:
+    for a in ANALYSES:
+        kw.update(a.kwargs(args, model))
+    res = (driver.dock_pair if dock else driver.refine_pair)(
+        model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed, precision=args.precision,
+        out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, **kw)
+    line = {"energy": res["energy"], "output": os.path.abspath(args.out), "num_samples": args.num_samples, "precision": res["precision"]}
+    if not dock:
+        line.update(t_begin=res["t_begin"], perturb=not args.no_perturb, index=res["index"])
+    line.update(rot_update=[float(v) for v in res["rot_update"]], tr_update=[float(v) for v in res["tr_update"]],
+                selfcheck_ok=None if res["selfcheck"] is None else bool(res["selfcheck"]["ok"]))
+    if dock and args.restraints:
         line.update(restraints=res["restraints"], restraints_satisfied=res["restraints_satisfied"],
                     restraint_energy=res["restraint_energy"], restraint_rank=res["restraint_rank"], index=res["index"])
-    if args.top_k is not None:
+    if dock and args.top_k is not None:
         line.update(models=[dict(m, path=os.path.abspath(driver.model_path(args.out, m["rank"]))) for m in res["models"]],
                     cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule)
-    if args.refine_t is not None:
+    if dock and args.refine_t is not None:
         line.update(refine_t=args.refine_t, refine_samples=args.refine_samples)
     if args.native:
-        line.update(metrics=res["metrics"])
-    consensus_outputs(args, res, rec, lig, line)
-    distogram_outputs(args, res, rec, lig, line)
-    sterics_outputs(args, model, res, rec, lig, line)
-    surface_outputs(args, model, res, rec, lig, line)
-    interface_outputs(args, model, res, rec, lig, line)
-    pairpot_outputs(args, model, res, rec, lig, line, kw.get("pair_potential"))
-    affinity_outputs(args, model, res, rec, lig, line)
-    hbonds_outputs(args, model, res, rec, lig, line)
+        line.update(metrics=res["metrics"], **({} if dock else {"start_metrics": res["start_metrics"]}))
+    for a in ANALYSES:
+        a.outputs(args, model, res, rec, lig, line, kw)
     print(json.dumps(line), flush=True)
     if args.json:
-        extra = {}
-        if args.restraints:
-            extra["trajectories"] = {k: [float(x) for x in v] for k, v in res["trajectories"].items()}
+        if dock:
+            extra = {"trajectories": {k: [float(x) for x in v] for k, v in res["trajectories"].items()}} if args.restraints else {}
+        else:
+            extra = {"energies": [float(e) for e in res["trajectories"]["energy"]]}
         with open(args.json, "w") as f:
             json.dump(dict(line, selfcheck=res["selfcheck"], **extra), f, default=float)
-    return 0
-
-
-def cmd_refine(args):
-    from . import driver
-    model, _ = load_model(args)
-    rec, lig, rec_x, lig_x = load_pair(args.pdb_1, args.pdb_2, args.features, model.hp.lm_embed_dim)
-    kw = {}
-    if args.restraints:
-        from .restraints import read_restraints
-        kw = dict(restraints=read_restraints(args.restraints, rec, lig))
-    if args.native:
-        kw.update(native=load_native(args.native))
-    kw.update(consensus_kwargs(args))
-    kw.update(distogram_kwargs(args, model))
-    kw.update(sterics_kwargs(args))
-    kw.update(surface_kwargs(args))
-    kw.update(interface_kwargs(args))
-    kw.update(pairpot_kwargs(args))
-    kw.update(affinity_kwargs(args))
-    kw.update(hbonds_kwargs(args))
-    res = driver.refine_pair(model, rec, lig, rec_x, lig_x, t_begin=args.t_begin, num_samples=args.num_samples, num_steps=args.num_steps,
-                             seed=args.seed, precision=args.precision, out_pdb=args.out, max_batch=args.max_batch,
-                             selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, perturb=not args.no_perturb, **kw)
-    line = {"energy": res["energy"], "output": os.path.abspath(args.out), "num_samples": args.num_samples, "precision": res["precision"],
-            "t_begin": res["t_begin"], "perturb": not args.no_perturb, "index": res["index"],
-            "rot_update": [float(v) for v in res["rot_update"]], "tr_update": [float(v) for v in res["tr_update"]],
-            "selfcheck_ok": None if res["selfcheck"] is None else bool(res["selfcheck"]["ok"])}
-    if args.native:
-        line.update(metrics=res["metrics"], start_metrics=res["start_metrics"])
-    consensus_outputs(args, res, rec, lig, line)
-    distogram_outputs(args, res, rec, lig, line)
-    sterics_outputs(args, model, res, rec, lig, line)
-    surface_outputs(args, model, res, rec, lig, line)
-    interface_outputs(args, model, res, rec, lig, line)
-    pairpot_outputs(args, model, res, rec, lig, line, kw.get("pair_potential"))
-    affinity_outputs(args, model, res, rec, lig, line)
-    hbonds_outputs(args, model, res, rec, lig, line)
-    print(json.dumps(line), flush=True)
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(dict(line, selfcheck=res["selfcheck"], energies=[float(e) for e in res["trajectories"]["energy"]]), f, default=float)
     return 0
 
 
@@ -975,4 +958,4 @@ def cmd_selfcheck(args):
 
 def main(argv=None):
     args = parse_args(argv)
-    return {"dock": cmd_dock, "sweep": cmd_sweep, "selfcheck": cmd_selfcheck, "refine": cmd_refine}[args.cmd](args)
+    return {"dock": cmd_pair, "sweep": cmd_sweep, "selfcheck": cmd_selfcheck, "refine": cmd_pair}[args.cmd](args)

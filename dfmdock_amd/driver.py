@@ -18,11 +18,13 @@ from __future__ import annotations
 
 import csv
 import os
+from typing import Callable, NamedTuple
 
 import numpy as np
 
 from . import distributed as D
 from . import engine, pdbio
+from .cluster import rank_order, rebuild_backbone
 from .metrics import NativeContext, compute_metrics
 
 CSV_FIELDS = ["id", "index", "c_rmsd", "i_rmsd", "l_rmsd", "fnat", "DockQ", "energy", "num_clashes"]
@@ -65,7 +67,6 @@ def cluster_trajectories(model: engine.Model, lig_pos0, rot_update, tr_update, k
     """Cluster trajectories on the GPU (dfm_pose_cluster) by the ligand backbone rebuilt from their final (rot_update, tr_update) on
     the input backbone lig_pos0 (cluster.rebuild_backbone): a function of those records alone, so every world size and sharding gives
     the same clusters.  `key` [n]: lower = better.  Returns the dict of Model.pose_cluster."""
-    from .cluster import rebuild_backbone
     poses = rebuild_backbone(lig_pos0, rot_update, tr_update, model.hp.family)
     return model.pose_cluster(poses, radius, key=key, rule=rule, max_clusters=max_clusters)
 
@@ -75,7 +76,6 @@ def ensemble_consensus(model: engine.Model, rec_bb, lig0, rot_update, tr_update,
     (rot_update, tr_update) on the input backbone lig0 (cluster.rebuild_backbone, as cluster_trajectories does).  Members: the best `top`
     fraction by energy (consensus.energy_members); every trajectory is scored.  Returns the dict of Model.consensus plus `members`."""
     from . import consensus as CS
-    from .cluster import rebuild_backbone
     poses = rebuild_backbone(lig0, rot_update, tr_update, model.hp.family)
     members = CS.energy_members(energy, top)
     out = model.consensus(rec_bb, poses, cutoff=cutoff, members=members)
@@ -222,30 +222,15 @@ def _pose_interface(ed, k):
             "n_pairs": int(ed["n_pairs"][k])}
 
 
-def _interface_pick(model, rec, lig, cols, k, key, opts, bad=None):
-    """The selecting half of the interface-energy part of a pair driver, run BEFORE any per-pose summary is built.  opts = None (off) or
-    _check_interface's; k / key: the pose and the clustering key the driver's own rule gives.  Returns (k, key, data or None): under rank
-    "interface" k is the pose of the lowest total among those the clash filter left (ties: the lower index) and key the totals, NaN on
-    the removed poses; otherwise k and key stay."""
-    if opts is None:
-        return k, key, None
-    by_it, weights, cutoff = opts
-    ed = ensemble_interface_energy(model, rec, lig, cols["rot_update"], cols["tr_update"], cutoff, weights)
-    if by_it:
-        k, key = _kept(np.argmin, bad, ed["total"]), _nan_key(ed["total"], bad)
-    return k, key, ed
-
-
 def _interface_result(ed, k, opts, bad=None, ranked_by="energy"):
     """The `interface_energy` entries of a pair driver's result for the FINAL kept pose k (none without the option): its terms, its
     rank by total among the poses the clash filter left, and `ranked_by` - the rule that chose k."""
     if ed is None:
         return {}
-    from .cluster import rank_order
-    by_it, weights, cutoff = opts
+    _, weights, cutoff = opts
     tot = _nan_key(ed["total"], bad)
     summary = dict(_pose_interface(ed, k), rank=int(np.nonzero(rank_order(tot, len(tot)) == k)[0][0]) + 1, weights=list(weights),
-                   cutoff=float(cutoff), ranked_by="interface" if by_it else ranked_by)
+                   cutoff=float(cutoff), ranked_by=ranked_by)
     return {"interface_energy": summary, "interface_data": ed, "index": int(k)}
 
 
@@ -306,20 +291,6 @@ def _check_pairpot(pair_potential, rank):
 def _pose_pairpot(pd, k):
     return {"energy": float(pd["energy"][k]), "n_pairs": int(pd["n_pairs"][k]), "n_untyped": int(pd["n_untyped"]), "T": int(pd["T"]),
             "NB": int(pd["NB"]), "cutoff": float(pd["cutoff"])}
-
-
-def _pairpot_pick(model, rec, lig, cols, k, key, opts, bad=None):
-    """The selecting half of the pair-potential part of a pair driver, run BEFORE any per-pose summary is built, next to _interface_pick.
-    opts = None (off) or _check_pairpot's.  Returns (k, key, data or None): under rank "pairpot" k is the pose of the lowest energy among
-    those the clash filter left (ties: the lower index) and key the energies, NaN on the removed poses; otherwise k and key stay."""
-    if opts is None:
-        return k, key, None
-    by_it, pot = opts
-    pd = ensemble_pairpot(model, rec, lig, cols["rot_update"], cols["tr_update"], pot)
-    pd.update(rot_update=cols["rot_update"], tr_update=cols["tr_update"])      # the poses the arrays are of (a restrained run's `trajectories` hold none)
-    if by_it:
-        k, key = _kept(np.argmin, bad, pd["energy"]), _nan_key(pd["energy"], bad)
-    return k, key, pd
 
 
 def _pairpot_result(pd, k):
@@ -478,9 +449,7 @@ def _pose_hbonds(hd, k):
 
 
 def _hbonds_result(hd, k):
-    """The hydrogen-bond entries of a pair driver's result for the kept pose k: none without the option."""
-    if hd is None:
-        return {}
+    """The hydrogen-bond entries of a pair driver's result for the kept pose k."""
     return dict(_pose_hbonds(hd, k), hbond_data=hd, index=int(k))
 
 
@@ -494,10 +463,8 @@ def _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff):
 
 
 def _screen(model, rec, lig, cols, opts):
-    """The screen of a pair driver's trajectories.  Returns (sterics data or None, bad): bad [n] bool = the poses --clash-filter removes
+    """The screen of a pair driver's trajectories.  Returns (sterics data, bad): bad [n] bool = the poses --clash-filter removes
     (CAPRI's flags), or None when nothing is removed - the filter is off, nothing is flagged, or every pose would go (`fallback`)."""
-    if opts is None:
-        return None, None
     filtered, clash_cutoff, contact_cutoff = opts
     sd = ensemble_sterics(model, rec, lig, cols["rot_update"], cols["tr_update"], clash_cutoff, contact_cutoff)
     sd["filtered"], sd["fallback"] = filtered, bool(filtered and sd["flags"].all())
@@ -552,7 +519,6 @@ def ensemble_distogram(gx: engine.Complex, rot_update, tr_update, t=DISTOGRAM_T,
     (Complex.distogram, dfm_score_distogram): the poses are rebuilt from the input backbone (cluster.rebuild_backbone) and evaluated at
     time `t` in chunks of max_batch.  Returns nll, nll_near, exp_contacts (float64 [P]), n_near (int [P]), t, contact_bins and, with
     `maps`, pcontact_mean [R,L] (the mean over ALL P poses, added in index order in double across the chunks) and edist [P,R,L]."""
-    from .cluster import rebuild_backbone
     rot, tr = np.asarray(rot_update, np.float32).reshape(-1, 3), np.asarray(tr_update, np.float32).reshape(-1, 3)
     P, mb = rot.shape[0], max(1, int(max_batch))
     out = {k: [] for k in ("nll", "nll_near", "n_near", "exp_contacts")}
@@ -588,29 +554,13 @@ def _check_distogram(model, distogram, rank, distogram_t, distogram_maps, max_ba
     return rank == "distogram", t, bool(distogram_maps), int(max_batch)
 
 
-def _distogram_pick(gx, cols, k, key, opts, bad, precision, seed=0):
-    """The distogram part of a pair driver, run while the handle is still open and BEFORE any per-pose summary is built.  opts = None
-    (off) or _check_distogram's.  Returns (k, key, data or None): under rank "distogram" k is the pose of the lowest nll among those the
-    clash filter left (ties: the lower index; NaN never wins) and key the nll values, NaN on the removed poses; otherwise k and key stay."""
-    if opts is None:
-        return k, key, None
-    by_it, t, maps, mb = opts
-    dd = ensemble_distogram(gx, cols["rot_update"], cols["tr_update"], t, precision, mb, maps=maps, seed=seed)
-    if by_it and not np.isnan(_nan_key(dd["nll"], bad)).all():
-        k, key = _kept(np.nanargmin, bad, dd["nll"]), _nan_key(dd["nll"], bad)
-    return k, key, dd
-
-
 def _pose_distogram(dd, k):
     fin = lambda v: float(v) if np.isfinite(v) else None
     return {"dist_nll": fin(dd["nll"][k]), "dist_nll_near": fin(dd["nll_near"][k]), "exp_contacts": fin(dd["exp_contacts"][k])}
 
 
 def _distogram_result(dd, k, opts, bad=None):
-    """The distogram entries of a pair driver's result for the FINAL kept pose k (none without the option)."""
-    if dd is None:
-        return {}
-    from .cluster import rank_order
+    """The distogram entries of a pair driver's result for the FINAL kept pose k."""
     nll = _nan_key(dd["nll"], bad)
     summary = dict(_pose_distogram(dd, k), n_near=int(dd["n_near"][k]), rank=int(np.nonzero(rank_order(nll, len(nll)) == k)[0][0]) + 1,
                    t=dd["t"], contact_bins=dd["contact_bins"], ranked_by_distogram=bool(opts[0]))
@@ -624,28 +574,13 @@ def _check_rank(rank, consensus_top):
         raise ValueError(f"consensus_top must be in (0, 1], got {consensus_top}")
 
 
-def _with_consensus(model, rec, lig0, cols, k, key, opts, bad=None, ranked_by="energy"):
-    """The consensus part of a pair driver.  opts = None (off) or (rank, cutoff, top); k / key: the pose and the clustering key chosen so
-    far, `ranked_by` the rule that chose them ("energy": the driver's own; "interface": _interface_pick).  Returns (k, key, extra result entries): under rank "consensus" k is the pose consensus.pick keeps and key
-    its order (consensus.rank_positions) - unless no pose has any contact, when both stay and `fallback` says so."""
-    if opts is None:
-        return k, key, {}
-    from . import consensus as CS
-    from .cluster import rank_order
-    rank, cutoff, top = opts
-    cd = ensemble_consensus(model, rec["bb_coords"], lig0, cols["rot_update"], cols["tr_update"], cols["energy"], cutoff, top)
-    if bad is not None:      # poses the clash filter removed: no score, so never picked and last in consensus order
-        cd["consensus"] = np.where(bad, np.nan, cd["consensus"])
-    if rank == "consensus":
-        k2 = CS.pick(cd["consensus"], cols["energy"])
-        if k2 is not None:
-            k, key, ranked_by = k2, CS.rank_positions(cd["consensus"], cols["energy"]), "consensus"
-    n = len(cd["consensus"])
+def _consensus_result(cd, k, opts, ranked_by="energy"):
+    """The `consensus` entries of a pair driver's result for the FINAL kept pose k; `ranked_by`: the rule that chose it (`fallback`: not rank "consensus" itself)."""
     s = float(cd["consensus"][k])
-    summary = {"score": None if np.isnan(s) else s, "rank": int(np.nonzero(rank_order(-cd["consensus"], n) == k)[0][0]) + 1,
+    summary = {"score": None if np.isnan(s) else s, "rank": int(np.nonzero(rank_order(-cd["consensus"], len(cd["consensus"])) == k)[0][0]) + 1,
                "n_contacts": int(cd["n_contacts"][k]), "M": int(cd["M"]), "cutoff": float(cd["cutoff"]), "ranked_by": ranked_by,
-               "fallback": rank == "consensus" and ranked_by != "consensus"}
-    return k, key, {"consensus": summary, "consensus_data": cd, "index": int(k)}
+               "fallback": opts[0] == "consensus" and ranked_by != "consensus"}
+    return {"consensus": summary, "consensus_data": cd, "index": int(k)}
 
 
 def checked_precision(gx: engine.Complex, precision: str, name: str, selfcheck=True, on_fail="fp32", log=None, seed=0):
@@ -1009,29 +944,17 @@ def native_metrics(model: engine.Model, native, rec_bb, lig_poses):
     nr, nl = (np.asarray(x, np.float32).reshape(-1, 3, 3) for x in native)
     rec_bb, lig_poses = np.asarray(rec_bb, np.float32).reshape(-1, 3, 3), np.asarray(lig_poses, np.float32)
     lig_poses = lig_poses.reshape(lig_poses.shape[0], -1, 3, 3)
-    if nr.shape[0] != rec_bb.shape[0] or nl.shape[0] != lig_poses.shape[1]:
-        raise ValueError(f"the native has {nr.shape[0]} receptor / {nl.shape[0]} ligand residues, the input pair "
-                         f"{rec_bb.shape[0]} / {lig_poses.shape[1]}: they must match residue by residue")
+    _check_native((nr, nl), rec_bb.shape[0], lig_poses.shape[1])
     with model.native(nr, nl) as nat:
         m = nat.metrics(lig_poses, np.repeat(rec_bb[None], lig_poses.shape[0], 0))
     return [{k: float(m[k][p]) for k in METRIC_FIELDS} for p in range(lig_poses.shape[0])]
 
 
-def _check_native(native, rec, lig):
-    """Before any sampling: the native must have the input's residue counts."""
+def _check_native(native, n_rec, n_lig):
+    """The native must have the input's residue counts (the pair drivers ask before any sampling)."""
     nr, nl = (np.asarray(x).reshape(-1, 3, 3) for x in native)
-    if nr.shape[0] != len(rec["bb_coords"]) or nl.shape[0] != len(lig["bb_coords"]):
-        raise ValueError(f"the native has {nr.shape[0]} receptor / {nl.shape[0]} ligand residues, the input pair "
-                         f"{len(rec['bb_coords'])} / {len(lig['bb_coords'])}: they must match residue by residue")
-
-
-def _selected_metrics(model, native, rec, lig0, res):
-    """`metrics` of the pose a pair driver keeps (its rot_update / tr_update on the input backbone), when a native is given."""
-    if native is not None:
-        from .cluster import rebuild_backbone
-        res["metrics"] = native_metrics(model, native, rec["bb_coords"],
-                                        rebuild_backbone(lig0, res["rot_update"][None], res["tr_update"][None], model.hp.family))[0]
-    return res
+    if nr.shape[0] != n_rec or nl.shape[0] != n_lig:
+        raise ValueError(f"the native has {nr.shape[0]} receptor / {nl.shape[0]} ligand residues, the input pair {n_rec} / {n_lig}: they must match residue by residue")
 
 
 def _center(model):
@@ -1039,63 +962,180 @@ def _center(model):
     return "all_atoms" if model.hp.family == 1 else "ca"
 
 
-def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native=None, cons=None, ster=None, clu=None, refine=None,
-            surf=None, ie=None, aff=None, dg=None, seed=0, hb=None, pp=None):
-    """What every pair driver does with its sampled trajectories: the kept pose, its files and the result.  cols: every trajectory's
-    energy, rot_update, tr_update (and the driver's own columns).  pick = (rule, *column names): the driver's own choice, rule(*columns) ->
-    index; key: the clustering key that goes with it.  entries(k): the driver's own result entries for the kept pose k.  cons / ster / clu:
-    None or the options of _with_consensus / _screen / _top_models; surf: None or the options of _check_surface; ie: None or the options of
-    _check_interface; aff: None or the options of _check_affinity; hb: None or the options of _check_hbonds; pp: None or the options of _check_pairpot; refine: None or the keyword arguments of refine_models - only then
-    does the handle outlive the sampling."""
-    lig0 = gx.lig_pos0
-    if refine is None and dg is None:      # the columns are host arrays: the handle (and its ~GB of device workspace) goes before any post-processing
-        gx.close()
-    sd, bad = _screen(model, rec, lig, cols, ster)
-    k = _kept(pick[0], bad, *(cols[c] for c in pick[1:]))
-    # the model's own distogram needs the open handle (a forward per pose): evaluated here, the handle goes right after it
-    k, key, dd = _distogram_pick(gx, cols, k, _nan_key(key, bad), dg, bad, precision, seed)
-    if refine is None and dg is not None:
-        gx.close()
-    # the kept pose is settled first - the driver's rule, then rank "interface", rank "pairpot", then rank "consensus" (one rank is given, so
-    # at most one of them moves k) - and only then does anything describe it
-    k, key, ed = _interface_pick(model, rec, lig, cols, k, _nan_key(key, bad), ie, bad)
-    k, key, pd = _pairpot_pick(model, rec, lig, cols, k, key, pp, bad)
-    by_pp = pp is not None and pp[0]
-    k, key, extra = _with_consensus(model, rec, lig0, cols, k, key, cons, bad,
-                                    "interface" if ie is not None and ie[0] else "pairpot" if by_pp else "distogram" if dg is not None and dg[0] else "energy")
-    key = _nan_key(key, bad)      # again: rank "consensus" has replaced the key by consensus.rank_positions
-    extra.update(_interface_result(ed, k, ie, bad, extra["consensus"]["ranked_by"] if "consensus" in extra else "pairpot" if by_pp else "energy"))
-    extra.update(_pairpot_result(pd, k))
-    extra.update(_distogram_result(dd, k, dg, bad))
-    extra.update(_sterics_result(sd, k))
-    # one surface call serves both when the surface options are the ones the affinity estimate takes (probe 1.4 A, 128 points)
-    shared = surf is not None and aff is not None and (surf[1], surf[2]) == _check_surface(True, None, *AFFINITY_SURFACE)[1:]
-    bd = None if surf is None else ensemble_surface(model, rec, lig, cols["rot_update"], cols["tr_update"], surf[1], surf[2],
-                                                    per_atom=shared or hb is not None)
-    extra.update(_surface_result(bd, k, surf))
-    ad = None if aff is None else pose_affinity(model, rec, lig, cols["rot_update"], cols["tr_update"], aff[0], *AFFINITY_SURFACE,
-                                                surface=bd if shared else None)
-    extra.update(_affinity_result(ad, k))
+class _Run:
+    """One pair-driver call after its sampling: what _finish, the analyses and _top_models pass around.  cols: every trajectory's energy, rot_update,
+    tr_update (and the driver's own columns); opts[name]: the checked options of every analysis of ANALYSES that is on; data[name]: the arrays it produced;
+    k, key, bad, ranked_by: the kept pose, the clustering key, the poses the clash filter removed (or None) and the rule that chose k, as they stand."""
+
+    def __init__(self, model, gx, rec, lig, cols, precision, opts=None, selfcheck=None, out_pdb=None, native=None, seed=0):
+        self.model, self.gx, self.rec, self.lig, self.lig0, self.cols = model, gx, rec, lig, gx.lig_pos0, cols
+        self.precision, self.selfcheck, self.out_pdb, self.native, self.seed = precision, selfcheck, out_pdb, native, seed
+        self.opts, self.data = {name: o for name, o in (opts or {}).items() if o is not None}, {}
+        self.k, self.key, self.bad, self.ranked_by = None, None, None, "energy"
+
+    def any(self):      # is any analysis on?  Then the result also carries `index` and every trajectory, and dock_pair picks among all of them at once
+        return bool(self.opts)
+
+    def poses(self):
+        return self.cols["rot_update"], self.cols["tr_update"]
+
+
+def _ranked(run, name, data, column, pick=np.argmin):
+    """Keeps the arrays of analysis `name` and, when its options say that the run ranks by it, makes the pose of the lowest `column` among those the clash filter
+    left the kept one (ties: the lower index) and the column the clustering key, NaN on the removed poses.  With np.nanargmin a NaN never wins, and a column of NaN alone moves nothing."""
+    run.data[name] = data
+    if run.opts[name][0]:
+        key = _nan_key(data[column], run.bad)
+        run.ranked_by = name
+        if pick is not np.nanargmin or not np.isnan(key).all():
+            run.k, run.key = _kept(pick, run.bad, data[column]), key
+
+
+def _sterics_screen(run):
+    run.data["sterics"], run.bad = _screen(run.model, run.rec, run.lig, run.cols, run.opts["sterics"])
+
+
+def _distogram_select(run):
+    _, t, maps, mb = run.opts["distogram"]
+    _ranked(run, "distogram", ensemble_distogram(run.gx, *run.poses(), t, run.precision, mb, maps=maps, seed=run.seed), "nll", np.nanargmin)
+
+
+def _interface_select(run):
+    _, weights, cutoff = run.opts["interface"]
+    _ranked(run, "interface", ensemble_interface_energy(run.model, run.rec, run.lig, *run.poses(), cutoff, weights), "total")
+
+
+def _pairpot_select(run):
+    pd = ensemble_pairpot(run.model, run.rec, run.lig, *run.poses(), run.opts["pairpot"][1])
+    pd.update(rot_update=run.cols["rot_update"], tr_update=run.cols["tr_update"])      # the poses the arrays are of (a restrained run's `trajectories` hold none)
+    _ranked(run, "pairpot", pd, "energy")
+
+
+def _consensus_select(run):
+    """Under rank "consensus" the kept pose becomes the one consensus.pick keeps and the key its order - unless no pose has any contact, when both stay."""
+    from . import consensus as CS
+    rank, cutoff, top = run.opts["consensus"]
+    cd = run.data["consensus"] = ensemble_consensus(run.model, run.rec["bb_coords"], run.lig0, *run.poses(), run.cols["energy"], cutoff, top)
+    if run.bad is not None:      # poses the clash filter removed: no score, so never picked and last in consensus order
+        cd["consensus"] = np.where(run.bad, np.nan, cd["consensus"])
+    if rank == "consensus":
+        k = CS.pick(cd["consensus"], run.cols["energy"])
+        if k is not None:
+            run.k, run.key, run.ranked_by = k, CS.rank_positions(cd["consensus"], run.cols["energy"]), "consensus"
+
+
+def _shared_surface(run):      # one surface call serves the affinity estimate too when its options are the ones that takes (probe 1.4 A, 128 points)
+    surf = run.opts.get("surface")
+    return surf is not None and "affinity" in run.opts and surf[1:] == _check_surface(True, None, *AFFINITY_SURFACE)[1:]
+
+
+def _surface_describe(run):
+    _, probe, points = run.opts["surface"]
+    run.data["surface"] = ensemble_surface(run.model, run.rec, run.lig, *run.poses(), probe, points, per_atom=_shared_surface(run) or "hbonds" in run.opts)
+
+
+def _affinity_describe(run):
+    shared = run.data["surface"] if _shared_surface(run) else None
+    run.data["affinity"] = pose_affinity(run.model, run.rec, run.lig, *run.poses(), run.opts["affinity"][0], *AFFINITY_SURFACE, surface=shared)
+
+
+def _hbonds_describe(run):
     # reported, never ranked by; with the surface in the same run also the buried donors and acceptors without a bond
-    hd = None if hb is None else ensemble_hbonds(model, rec, lig, cols["rot_update"], cols["tr_update"], *hb, per_atom=bd is not None)
-    if hd is not None:
-        hd.update(rot_update=cols["rot_update"], tr_update=cols["tr_update"])      # the poses the arrays are of
-        if bd is not None:
-            hd["n_unsat"] = unsatisfied_polar(hd, bd)
-    extra.update(_hbonds_result(hd, k))
+    bd = run.data.get("surface")
+    hd = run.data["hbonds"] = ensemble_hbonds(run.model, run.rec, run.lig, *run.poses(), *run.opts["hbonds"], per_atom=bd is not None)
+    hd.update(rot_update=run.cols["rot_update"], tr_update=run.cols["tr_update"])      # the poses the arrays are of
+    if bd is not None:
+        hd["n_unsat"] = unsatisfied_polar(hd, bd)
+
+
+class _Analysis(NamedTuple):
+    """One per-pose analysis of the pair drivers."""
+    name: str
+    defaults: dict                # its keywords of dock_pair / refine_pair
+    check: Callable               # (model, rank, max_batch, **its keywords) -> its options, None: off; raises before anything is sampled
+    stage: str                    # where _finish runs it: "screen", "handle", "select" or "describe"
+    run: Callable                 # run -> None: fills run.data[name]; may set run.bad ("screen") or run.k, run.key, run.ranked_by ("handle", "select")
+    result: Callable              # run -> its entries of the result, for the kept pose run.k
+    pose: Callable = None         # (data, k) -> its summary of pose k: what every model of top_k gains ...
+    model_key: str = None         # ... under this key (None: merged into the model)
+
+
+# In the order a model of top_k lists them, which within a stage is also the order of the calls: interface, pairpot, then consensus (one
+# rank is given, so at most one of them moves the kept pose); surface before affinity and hbonds, which use it.
+ANALYSES = (
+    _Analysis("sterics", dict(clash_screen=False, clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0), lambda model, rank, max_batch, **kw: _check_sterics(**kw),
+              "screen", _sterics_screen, lambda run: _sterics_result(run.data["sterics"], run.k), _pose_sterics, "sterics"),
+    _Analysis("surface", dict(bsa=False, min_bsa=None, probe=1.4, sphere_points=128), lambda model, rank, max_batch, **kw: _check_surface(**kw),
+              "describe", _surface_describe, lambda run: _surface_result(run.data["surface"], run.k, run.opts["surface"]), _pose_bsa),
+    # its `ranked_by`: the rule that kept the pose - but rank "distogram" is named only when the consensus object names it as well
+    _Analysis("interface", dict(interface_energy=False, ie_weights=None, ie_cutoff=8.0), lambda model, rank, max_batch, **kw: _check_interface(rank=rank, **kw),
+              "select", _interface_select, lambda run: _interface_result(
+                  run.data["interface"], run.k, run.opts["interface"], run.bad, run.ranked_by if "consensus" in run.opts or run.ranked_by != "distogram" else "energy"),
+              _pose_interface, "interface_energy"),
+    _Analysis("affinity", dict(affinity=False, affinity_cutoff=5.5), lambda model, rank, max_batch, **kw: _check_affinity(**kw),
+              "describe", _affinity_describe, lambda run: _affinity_result(run.data["affinity"], run.k), _pose_affinity, "affinity"),
+    _Analysis("distogram", dict(distogram=False, distogram_t=DISTOGRAM_T, distogram_maps=False),
+              lambda model, rank, max_batch, **kw: _check_distogram(model, rank=rank, max_batch=max_batch, **kw),
+              "handle", _distogram_select, lambda run: _distogram_result(run.data["distogram"], run.k, run.opts["distogram"], run.bad), _pose_distogram),
+    _Analysis("hbonds", dict(hbonds=False, hbond_cutoff=3.5, hbond_angle=90.0, salt_cutoff=4.0), lambda model, rank, max_batch, **kw: _check_hbonds(**kw),
+              "describe", _hbonds_describe, lambda run: _hbonds_result(run.data["hbonds"], run.k), _pose_hbonds),
+    _Analysis("pairpot", dict(pair_potential=None), lambda model, rank, max_batch, **kw: _check_pairpot(rank=rank, **kw),
+              "select", _pairpot_select, lambda run: _pairpot_result(run.data["pairpot"], run.k), _pose_pairpot, "pair_potential"),
+    _Analysis("consensus", dict(consensus=False, consensus_top=1.0, consensus_cutoff=5.5), lambda model, rank, max_batch, consensus, consensus_top, consensus_cutoff:
+              (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None,      # rank "consensus" implies it
+              "select", _consensus_select, lambda run: _consensus_result(run.data["consensus"], run.k, run.opts["consensus"], run.ranked_by)),
+)
+
+
+def _analysis_options(model, max_batch, kw):
+    """{analysis name: its checked options, None when it is off} of a dock_pair / refine_pair call, before anything is sampled.  kw: what the call gave beyond
+    the driver's own parameters; `rank` and the keywords of ANALYSES (their defaults where absent) are taken OUT of it - what stays goes to the sampler."""
+    rank = kw.pop("rank", "energy")
+    given = {a.name: {name: kw.pop(name, default) for name, default in a.defaults.items()} for a in ANALYSES}
+    _check_rank(rank, given["consensus"]["consensus_top"])
+    return {a.name: a.check(model, rank, max_batch, **given[a.name]) for a in ANALYSES}
+
+
+def _finish(run, pick, entries, clu=None, refine=None):
+    """What every pair driver does with its sampled trajectories: the kept pose, its files and the result.  pick = (rule, *column names): the driver's
+    own choice, rule(*columns) -> index; run.key: the clustering key that goes with it.  entries(k): the driver's own result entries for the kept pose k.
+    clu: None or the options of _top_models; refine: None or the keyword arguments of refine_models - only then does the handle outlive the post-processing."""
+    model, gx, rec, lig, cols = run.model, run.gx, run.rec, run.lig, run.cols
+    on = [a for a in ANALYSES if a.name in run.opts]
+
+    def stage(name):
+        for a in on:
+            if a.stage == name:
+                a.run(run)
+    handle = refine is not None or any(a.stage == "handle" for a in on)
+    if not handle:      # the columns are host arrays: the handle (and its ~GB of device workspace) goes before any post-processing
+        gx.close()
+    stage("screen")
+    run.k = _kept(pick[0], run.bad, *(cols[c] for c in pick[1:]))
+    run.key = _nan_key(run.key, run.bad)
+    stage("handle")      # the model's own distogram needs the open handle (a forward per pose): the handle goes right after it
+    if handle and refine is None:
+        gx.close()
+    stage("select")      # the kept pose is settled first - the driver's rule, then the rank that is given - and only then does anything describe it
+    run.key = _nan_key(run.key, run.bad)      # again: rank "consensus" has replaced the key by consensus.rank_positions
+    stage("describe")
+    k = run.k
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k], center=_center(model))
-    if out_pdb:
-        pdbio.write_complex_pdb(out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa, remarks=_remarks(sd, k))
+    if run.out_pdb:
+        pdbio.write_complex_pdb(run.out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa, remarks=_remarks(run.data.get("sterics"), k))
     res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
-           "lig_aa_coords": lig_aa, "precision": precision, "selfcheck": chk, **entries(k)}
-    res.update(extra)
-    if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None or dg is not None or hb is not None or pp is not None:      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
+           "lig_aa_coords": lig_aa, "precision": run.precision, "selfcheck": run.selfcheck, **entries(k)}
+    for a in on:
+        res.update(a.result(run))
+    if run.any():      # these also return `index` and every trajectory - the driver's own `trajectories` if it has them
         res.setdefault("trajectories", {c: cols[c] for c in ("energy", "rot_update", "tr_update")})
-    _selected_metrics(model, native, rec, lig0, res)
+    if run.native is not None:      # of the kept pose: its rot_update / tr_update on the input backbone
+        pose = rebuild_backbone(run.lig0, res["rot_update"][None], res["tr_update"][None], model.hp.family)
+        res["metrics"] = native_metrics(model, run.native, rec["bb_coords"], pose)[0]
     if clu is not None:
-        res.update(_top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native, sd, bad, bd, None if surf is None else surf[0], ed, ad, dd, hd, pd))
+        res.update(_top_models(run, clu))
         if refine is not None:
-            refine_models(model, gx, rec, lig, lig0, cols, res["models"], precision=precision, out_pdb=out_pdb, native=native, **refine)
+            refine_models(run, res["models"], **refine)
             gx.close()
     return res
 
@@ -1103,15 +1143,11 @@ def _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_p
 def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_steps=40, seed=0, precision="mfma16",
               out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", restraints=None,
               restraint_rank="satisfied", restraint_params=None, top_k=None, cluster_radius=4.0, cluster_rule="energy", refine_t=None,
-              refine_samples=8, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
-              clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, bsa=False, min_bsa=None, probe=1.4, sphere_points=128,
-              interface_energy=False, ie_weights=None, ie_cutoff=8.0, affinity=False, affinity_cutoff=5.5, distogram=False,
-              distogram_t=DISTOGRAM_T, distogram_maps=False, hbonds=False, hbond_cutoff=3.5, hbond_angle=90.0, salt_cutoff=4.0, pair_potential=None,
-              **sampler_kw):
-    """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their
-    pre-computed node features; returns {'energy': min energy} and writes the best pose.  `sampler_kw` are the sampler options
-    the reference's pair loop passes (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale,
-    rot_noise_scale, ode).
+              refine_samples=8, native=None, **sampler_kw):
+    """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their pre-computed node features; returns
+    {'energy': min energy} and writes the best pose.  `sampler_kw`: `rank` and the analysis keywords described below (their names and defaults:
+    ANALYSES; checked by _analysis_options before anything is sampled) and, beyond those, the sampler options the reference's pair loop passes
+    (src/inference_base.py:483-491: use_clash_force, noise_annealing, tr_noise_scale, rot_noise_scale, ode).
 
     `restraints` ([restraints.RestraintGroup]): sample with the interface restraint step (DFM_F_RESTRAINTS, `restraint_params` or the
     defaults) and keep, by `restraint_rank`, the minimum-energy trajectory among those satisfying the most groups ("satisfied") or the
@@ -1184,17 +1220,9 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     kcal/mol, n_pairs, n_untyped, T, NB, cutoff} of the kept pose), `pairpot_data` (the arrays and the rot_update / tr_update they are of), `index` and `trajectories`; every model
     of `top_k` gains `pair_potential`.  rank="pairpot" (needs pair_potential) keeps the pose with the lowest energy instead (ties: lower
     index; it overrides restraint_rank and becomes the clustering key of top_k)."""
-    _check_rank(rank, consensus_top)
-    dg = _check_distogram(model, distogram, rank, distogram_t, distogram_maps, max_batch)
-    cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
-    ster = _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff)
-    surf = _check_surface(bsa, min_bsa, probe, sphere_points)
-    ie = _check_interface(interface_energy, rank, ie_weights, ie_cutoff)
-    aff = _check_affinity(affinity, affinity_cutoff)
-    hb = _check_hbonds(hbonds, hbond_cutoff, hbond_angle, salt_cutoff)
-    pp = _check_pairpot(pair_potential, rank)
+    opts = _analysis_options(model, max_batch, sampler_kw)
     if native is not None:
-        _check_native(native, rec, lig)
+        _check_native(native, len(rec["bb_coords"]), len(lig["bb_coords"]))
     if refine_t is not None and top_k is None:
         raise ValueError("refine_t refines the cluster centres: it needs top_k")
     if refine_t is not None and int(refine_samples) < 1:
@@ -1209,7 +1237,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         if not (np.isfinite(cluster_radius) and cluster_radius > 0):
             raise ValueError("cluster_radius must be finite and > 0")
     clu = None if top_k is None else (int(top_k), float(cluster_radius), cluster_rule)
-    refine = None if refine_t is None else dict(t_begin=float(refine_t), n=int(refine_samples), num_steps=num_steps, seed=seed,
+    refine = None if refine_t is None else dict(t_begin=float(refine_t), n=int(refine_samples), num_steps=num_steps,
                                                 restraints=restraints is not None, **sampler_kw)
     gx = engine.Complex(model, rec_x, lig_x, rec["bb_coords"], lig["bb_coords"])
     precision, chk = checked_precision(gx, precision, "pair", selfcheck, on_selfcheck_fail, seed=seed)
@@ -1231,57 +1259,37 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
             cols[c].append(r[c])
         done += b
     cols = {c: np.concatenate(v, 0) for c, v in cols.items()}
+    run = _Run(model, gx, rec, lig, cols, precision, opts, chk, out_pdb, native, seed)
     if not restrained:
-        # the loop's own minimum; consensus and the screen choose among all trajectories at once (the first minimum: the same pose)
-        pick = (np.argmin if cons is not None or ster is not None or surf is not None or ie is not None or aff is not None or dg is not None
-                or hb is not None or pp is not None
-                else (lambda energy: k0), "energy")
-        key, entries = cols["energy"], lambda k: {}
+        # the loop's own minimum; with any analysis on, the pick is among all trajectories at once (the first minimum: the same pose)
+        pick = (np.argmin if run.any() else (lambda energy: k0), "energy")
+        run.key, entries = cols["energy"], lambda k: {}
     else:
         from . import restraints as RS
         from .cluster import satisfied_key
         by_satisfied = restraint_rank == "satisfied"
         pick = (RS.rank_key, "energy", "restraints_satisfied") if by_satisfied else (np.argmin, "energy")
-        key = satisfied_key(cols["energy"], cols["restraints_satisfied"]) if by_satisfied else cols["energy"]
+        run.key = satisfied_key(cols["energy"], cols["restraints_satisfied"]) if by_satisfied else cols["energy"]
         entries = lambda k: {"index": k, "restraints": len(restraints), "restraint_rank": restraint_rank,
                              "restraint_energy": float(cols["restraint_energy"][k]), "restraints_satisfied": int(cols["restraints_satisfied"][k]),
                              "trajectories": {c: cols[c] for c in ("energy", "restraint_energy", "restraints_satisfied")}}
-    return _finish(model, gx, rec, lig, cols, pick, key, entries, precision, chk, out_pdb, native, cons, ster, clu, refine, surf, ie, aff, dg, seed, hb, pp)
+    return _finish(run, pick, entries, clu, refine)
 
 
 def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
                 out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", perturb=True, restraints=None,
-                restraint_params=None, native=None, consensus=False, rank="energy", consensus_top=1.0, consensus_cutoff=5.5, clash_screen=False,
-                clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0, start_shift=None, bsa=False, min_bsa=None, probe=1.4,
-                sphere_points=128, interface_energy=False, ie_weights=None, ie_cutoff=8.0, affinity=False, affinity_cutoff=5.5, distogram=False,
-                distogram_t=DISTOGRAM_T, distogram_maps=False, hbonds=False, hbond_cutoff=3.5, hbond_angle=90.0, salt_cutoff=4.0, pair_potential=None,
-              **sampler_kw):
-    """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories
-    start from that pose noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps
-    down from t_begin; like dock_pair the minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns
-    dock_pair's dict plus `t_begin`, `index` and `trajectories` (every trajectory's energy, rot_update, tr_update).  `restraints`
-    ([restraints.RestraintGroup]) turns the restraint step on (DFM_F_RESTRAINTS).  `native` (as for dock_pair): the result gains
-    `metrics` of the kept pose and `start_metrics` of the pose the refinement started from.  `consensus` / `rank` / `consensus_top` /
-    `consensus_cutoff`: as for dock_pair.  `clash_screen` / `clash_filter` / `clash_cutoff` / `contact_cutoff`: as for dock_pair.
-    `bsa` / `min_bsa` / `probe` / `sphere_points`: as for dock_pair (there are no models here, so min_bsa only turns bsa on).
-    `interface_energy` / `ie_weights` / `ie_cutoff` and rank="interface": as for dock_pair.
-    `affinity` / `affinity_cutoff`: as for dock_pair.
-    `distogram` / `distogram_t` / `distogram_maps` and rank="distogram": as for dock_pair.
-    `hbonds` / `hbond_cutoff` / `hbond_angle` / `salt_cutoff`: as for dock_pair.
-    `pair_potential` and rank="pairpot": as for dock_pair.
+                restraint_params=None, native=None, start_shift=None, **sampler_kw):
+    """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories start from that pose
+    noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps down from t_begin; like dock_pair the
+    minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns dock_pair's dict plus `t_begin`, `index` and `trajectories`
+    (every trajectory's energy, rot_update, tr_update).  `restraints` ([restraints.RestraintGroup]) turns the restraint step on (DFM_F_RESTRAINTS).
+    `native`, `rank` and every analysis keyword: as for dock_pair (there are no models here, so min_bsa only turns bsa on); with `native` the result also
+    gains `start_metrics` of the pose the refinement started from.
     `start_shift` ([num_samples,3]): trajectory i starts from the input pose translated by start_shift[i] (the engine's start_pos); the
     shift is added to its tr_update, so (rot_update, tr_update) keep mapping the INPUT pose onto the final one."""
-    _check_rank(rank, consensus_top)
-    dg = _check_distogram(model, distogram, rank, distogram_t, distogram_maps, max_batch)
-    cons = (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None
-    ster = _check_sterics(clash_screen, clash_filter, clash_cutoff, contact_cutoff)
-    surf = _check_surface(bsa, min_bsa, probe, sphere_points)
-    ie = _check_interface(interface_energy, rank, ie_weights, ie_cutoff)
-    aff = _check_affinity(affinity, affinity_cutoff)
-    hb = _check_hbonds(hbonds, hbond_cutoff, hbond_angle, salt_cutoff)
-    pp = _check_pairpot(pair_potential, rank)
+    opts = _analysis_options(model, max_batch, sampler_kw)
     if native is not None:
-        _check_native(native, rec, lig)
+        _check_native(native, len(rec["bb_coords"]), len(lig["bb_coords"]))
     if start_shift is not None:
         start_shift = np.asarray(start_shift, np.float32).reshape(-1, 3)
         if start_shift.shape[0] != num_samples:
@@ -1305,84 +1313,70 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
             cols[c].append(r[c])
         done += b
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
-    res = _finish(model, gx, rec, lig, cols, (np.argmin, "energy"), None,      # the first minimum wins, as in dock_pair
-                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols}, precision, chk, out_pdb, native, cons, ster, surf=surf, ie=ie, aff=aff, dg=dg, seed=seed, hb=hb, pp=pp)
+    run = _Run(model, gx, rec, lig, cols, precision, opts, chk, out_pdb, native, seed)
+    res = _finish(run, (np.argmin, "energy"),      # the first minimum wins, as in dock_pair
+                  lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols})
     if native is not None:
-        res["start_metrics"] = native_metrics(model, native, rec["bb_coords"], gx.lig_pos0[None])[0]
+        res["start_metrics"] = native_metrics(model, native, rec["bb_coords"], run.lig0[None])[0]
     return res
 
 
-def refine_models(model, gx, rec, lig, lig0, cols, models, t_begin, n, num_steps, seed, precision, out_pdb, restraints=False, native=None,
-                  **sampler_kw):
+def refine_models(run, models, t_begin, n, num_steps, restraints=False, **sampler_kw):
     """dock_pair's second stage (`refine_t`): the K cluster centres of `models` refined in ONE dfm_refine call - B = K n trajectories,
     start_pos = each centre's backbone n times.  Every model gains `refined_energy` (the minimum over its n trajectories) and
     `refined_index`; <out_pdb stem>_<rank>.pdb becomes that refined pose (the centre's rigid motion, then the refinement's)."""
-    from .cluster import rebuild_backbone
+    model, rec, lig, cols = run.model, run.rec, run.lig, run.cols
     K = len(models)
     cen = [m["index"] for m in models]
-    start = rebuild_backbone(lig0, cols["rot_update"][cen], cols["tr_update"][cen], model.hp.family)      # [K,L,3,3]
-    r = gx.refine(B=K * n, t_begin=t_begin, start_pos=np.repeat(start, n, 0), num_steps=num_steps, seed=seed, restraints=restraints,
-                  **engine.precision_kwargs(precision), **sampler_kw)
+    start = rebuild_backbone(run.lig0, cols["rot_update"][cen], cols["tr_update"][cen], model.hp.family)      # [K,L,3,3]
+    r = run.gx.refine(B=K * n, t_begin=t_begin, start_pos=np.repeat(start, n, 0), num_steps=num_steps, seed=run.seed, restraints=restraints,
+                      **engine.precision_kwargs(run.precision), **sampler_kw)
     center = _center(model)
     kept = [k * n + int(np.argmin(r["energy"][k * n:(k + 1) * n])) for k in range(K)]
-    if native is not None:      # every centre after its refinement (before: the model's `metrics`, _top_models)
-        for m, rm in zip(models, native_metrics(model, native, rec["bb_coords"], r["lig_pos"][kept])):
+    if run.native is not None:      # every centre after its refinement (before: the model's `metrics`, _top_models)
+        for m, rm in zip(models, native_metrics(model, run.native, rec["bb_coords"], r["lig_pos"][kept])):
             m["refined_metrics"] = rm
     for k, m in enumerate(models):
         j = kept[k]
         m.update(refined_energy=float(r["energy"][j]), refined_index=j - k * n)
-        if out_pdb:
+        if run.out_pdb:
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][cen[k]], cols["tr_update"][cen[k]], center=center)
             aa = pdbio.apply_pose_all_atom(aa, start[k], r["rot_update"][j], r["tr_update"][j], center=center)
-            pdbio.write_complex_pdb(model_path(out_pdb, m["rank"]), list(rec["atoms"]), lig["atoms"], aa)
+            pdbio.write_complex_pdb(model_path(run.out_pdb, m["rank"]), list(rec["atoms"]), lig["atoms"], aa)
     return models
 
 
-def _top_models(model, rec, lig, lig0, cols, key, clu, out_pdb, native=None, sd=None, bad=None, bd=None, min_bsa=None, ed=None, ad=None,
-                dd=None, hd=None, pd=None):
-    """dock_pair's `models`: the centres of up to top_k clusters in cluster order, each written as <out_pdb stem>_<rank>.pdb.  sd: the
-    screen's data (every model gains `sterics`, every file a REMARK line); bad: poses the clash filter removed - their key is NaN, so they
-    come last, and a cluster one of them would lead is left out.  bd: the surface data (every model gains bsa, bsa_rec, bsa_lig); min_bsa:
-    a centre that buries less is left out as well, and `bsa_dropped` counts those.  ed: the interface-energy data (every model gains
-    `interface_energy`); ad: the affinity data (every model gains `affinity`); dd: the distogram data (every model gains dist_nll,
-    dist_nll_near, exp_contacts); hd: the hydrogen-bond data (every model gains n_hbond, hb_bb_bb, hb_bb_sc, hb_sc_sc, n_salt and, with the
-    surface, n_unsat); pd: the pair-potential data (every model gains `pair_potential`)."""
+def _top_models(run, clu):
+    """dock_pair's `models`: the centres of up to top_k clusters in cluster order, each written as <out_pdb stem>_<rank>.pdb with the screen's REMARK line.
+    Every model gains the per-pose summary of every analysis that is on (ANALYSES: pose, model_key).  run.bad: poses the clash filter removed - their key is
+    NaN, so they come last, and a cluster one of them would lead is left out.  With min_bsa a centre that buries less is left out as well (`bsa_dropped`)."""
     top_k, radius, rule = clu
-    cl = cluster_trajectories(model, lig0, cols["rot_update"], cols["tr_update"], key, radius, rule, top_k)
+    model, rec, lig, cols, bad, sd = run.model, run.rec, run.lig, run.cols, run.bad, run.data.get("sterics")
+    min_bsa = run.opts["surface"][0] if "surface" in run.opts else None
+    cl = cluster_trajectories(model, run.lig0, cols["rot_update"], cols["tr_update"], run.key, radius, rule, top_k)
     models, dropped = [], 0
     for c, n in zip(cl["center"], cl["size"]):
         c = int(c)
         if bad is not None and bad[c]:
             continue
-        if bd is not None and min_bsa is not None and bd["bsa"][c] < min_bsa:
+        if min_bsa is not None and run.data["surface"]["bsa"][c] < min_bsa:
             dropped += 1
             continue
         k = len(models)
         models.append({"rank": k + 1, "index": c, "energy": float(cols["energy"][c]), "cluster_size": int(n)})
-        if sd is not None:
-            models[-1]["sterics"] = _pose_sterics(sd, c)
-        if bd is not None:
-            models[-1].update(_pose_bsa(bd, c))
-        if ed is not None:
-            models[-1]["interface_energy"] = _pose_interface(ed, c)
-        if ad is not None:
-            models[-1]["affinity"] = _pose_affinity(ad, c)
-        if dd is not None:
-            models[-1].update(_pose_distogram(dd, c))
-        if hd is not None:
-            models[-1].update(_pose_hbonds(hd, c))
-        if pd is not None:
-            models[-1]["pair_potential"] = _pose_pairpot(pd, c)
-        if out_pdb:
+        for a in ANALYSES:
+            if a.pose and a.name in run.opts:
+                summary = a.pose(run.data[a.name], c)
+                models[-1].update(summary if a.model_key is None else {a.model_key: summary})
+        if run.out_pdb:
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c], center=_center(model))
-            pdbio.write_complex_pdb(model_path(out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa, remarks=_remarks(sd, c))
-    if native is not None and models:
-        from .cluster import rebuild_backbone
+            pdbio.write_complex_pdb(model_path(run.out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa, remarks=_remarks(sd, c))
+    if run.native is not None and models:
         cen = [m["index"] for m in models]
-        poses = rebuild_backbone(lig0, cols["rot_update"][cen], cols["tr_update"][cen], model.hp.family)
-        for m, pm in zip(models, native_metrics(model, native, rec["bb_coords"], poses)):
+        poses = rebuild_backbone(run.lig0, cols["rot_update"][cen], cols["tr_update"][cen], model.hp.family)
+        for m, pm in zip(models, native_metrics(model, run.native, rec["bb_coords"], poses)):
             m["metrics"] = pm
-    return {"models": models, "cluster_of": cl["cluster_of"], **({"bsa_dropped": dropped} if bd is not None and min_bsa is not None else {})}
+    return {"models": models, "cluster_of": cl["cluster_of"], **({"bsa_dropped": dropped} if min_bsa is not None else {})}
 
 
 def model_path(out_pdb, rank):

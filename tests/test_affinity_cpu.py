@@ -411,10 +411,13 @@ def test_pair_drivers_share_one_path(tmp_path, monkeypatch):
         def close(self):
             pass
     model = type("M", (), {"hp": type("Hp", (), {"family": 0})})()
-    fin = lambda **kw: driver._finish(model, Gx(), rec, lig, cols, (np.argmin, "energy"), energy, lambda k: {}, "fp32", None, None, **kw)
+    def fin(clu=None, **opts):
+        run = driver._Run(model, Gx(), rec, lig, cols, "fp32", opts)
+        run.key = energy
+        return driver._finish(run, (np.argmin, "energy"), lambda k: {}, clu)
     r = fin()
     assert "affinity" not in r and "affinity_data" not in r and "index" not in r and "args" not in seen
-    r = fin(aff=driver._check_affinity(True, 6.0), clu=(2, 4.0, "energy"))
+    r = fin(affinity=driver._check_affinity(True, 6.0), clu=(2, 4.0, "energy"))
     assert seen["args"] == ((n, 3), (n, 3), 6.0) and r["index"] == 1 and r["affinity"] == driver._pose_affinity(ad, 1)
     assert r["affinity_data"]["dg_contacts"].tolist() == ad["dg_contacts"].tolist() and set(r["trajectories"]) == {"energy", "rot_update", "tr_update"}
     assert [m["index"] for m in r["models"]] == [1, 3] and all(m["affinity"] == driver._pose_affinity(ad, m["index"]) for m in r["models"])
@@ -428,10 +431,10 @@ def test_pair_drivers_share_one_path(tmp_path, monkeypatch):
         return {"bsa": np.arange(n) * 100.0, "bsa_rec": np.arange(n) * 50.0, "bsa_lig": np.arange(n) * 50.0, "probe": probe, "sphere_points": points,
                 "tag": len(calls)}
     monkeypatch.setattr(driver, "ensemble_surface", ensemble_surface)
-    r = fin(aff=driver._check_affinity(True, 5.5), surf=driver._check_surface(True, None, 1.4, 128))
+    r = fin(affinity=driver._check_affinity(True, 5.5), surface=driver._check_surface(True, None, 1.4, 128))
     assert calls == [(float(np.float32(1.4)), 128, True)] and seen["surface"]["tag"] == 1 and r["bsa"] == 100.0 and r["affinity"]["n_pairs"] == int(ad["n_pairs"][1])
     calls.clear()
-    r = fin(aff=driver._check_affinity(True, 5.5), surf=driver._check_surface(True, None, 1.2, 64))
+    r = fin(affinity=driver._check_affinity(True, 5.5), surface=driver._check_surface(True, None, 1.2, 64))
     assert calls == [(float(np.float32(1.2)), 64, False)] and seen["surface"] is None and r["sphere_points"] == 64
 
 

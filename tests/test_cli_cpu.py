@@ -23,6 +23,26 @@ def test_parser_and_defaults():
         cli.build_parser().parse_args(["dock", "r.pdb", "l.pdb", "--features", "f.npz"])      # --ckpt is required
 
 
+ANALYSIS_FLAGS = ["--native", "--consensus", "--rank", "--consensus-top", "--contact-map", "--write-restraints", "--restraint-top", "--restraint-upper",
+                  "--distogram", "--distogram-map", "--distogram-restraints", "--distogram-t", "--clash-screen", "--clash-filter", "--clash-cutoff",
+                  "--contact-cutoff", "--clash-residues", "--bsa", "--min-bsa", "--interface-residues", "--probe", "--sphere-points", "--interface-energy",
+                  "--ie-weights", "--ie-cutoff", "--energy-residues", "--pair-potential", "--pairpot-residues", "--pair-counts", "--affinity",
+                  "--affinity-cutoff", "--contact-residues", "--hbonds", "--hbond-cutoff", "--hbond-angle", "--salt-cutoff", "--hbond-residues"]
+COMMON_FLAGS = ["--ckpt", "--num-steps", "--precision", "--seed", "--device", "--max-batch", "--no-selfcheck", "--on-selfcheck-fail"]
+OWN_FLAGS = {"dock": ["--features", "--num-samples", "--out", "--json", "--restraints", "--restraint-rank", "--top-k", "--cluster-radius", "--cluster-rule",
+                      "--refine-t", "--refine-samples"],
+             "refine": ["--features", "--t-begin", "--num-samples", "--no-perturb", "--out", "--json", "--restraints"]}
+
+
+@pytest.mark.parametrize("cmd", ["dock", "refine"])
+def test_every_flag_of_dock_and_refine_is_offered(cmd):
+    """The option strings of the built parser, as a literal list: an analysis that falls out of the parser's loop takes its flags along."""
+    from dfmdock_amd import cli
+    sub = [a for a in cli.build_parser()._actions if a.dest == "cmd"][0].choices[cmd]
+    flags = [s for a in sub._actions for s in a.option_strings]
+    assert flags == ["-h", "--help"] + OWN_FLAGS[cmd] + ANALYSIS_FLAGS + COMMON_FLAGS
+
+
 def test_checkpoint_written_by_the_test_reads_back(tmp_path):
     from dfmdock_amd.weights import HParams, load_lightning_checkpoint, pack_blob
     for lightning in (True, False):

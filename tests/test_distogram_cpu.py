@@ -179,13 +179,20 @@ def test_distogram_pick_and_result():
     driver.ensemble_distogram = lambda *a, **k: dd
     try:
         cols = dict(rot_update=np.zeros((4, 3)), tr_update=np.zeros((4, 3)))
-        assert driver._distogram_pick(None, cols, 0, None, None, None, "fp32") == (0, None, None)
-        k, key, d = driver._distogram_pick(None, cols, 0, np.arange(4.0), (True, 1e-3, False, 2), None, "fp32")
+        def pick(k, key, opts, bad):      # the selecting stages of driver._finish, from the pose and key the driver's own rule gave
+            run = driver._Run(None, type("G", (), {"lig_pos0": None}), None, None, cols, "fp32", {"distogram": opts})
+            run.k, run.key, run.bad = k, key, bad
+            for a in driver.ANALYSES:
+                if a.stage in ("handle", "select") and a.name in run.opts:
+                    a.run(run)
+            return run.k, run.key, run.data.get("distogram")
+        assert pick(0, None, None, None) == (0, None, None)
+        k, key, d = pick(0, np.arange(4.0), (True, 1e-3, False, 2), None)
         assert k == 2 and np.array_equal(key, dd["nll"], equal_nan=True)
         bad = np.array([False, False, True, False])
-        k, key, d = driver._distogram_pick(None, cols, 0, np.arange(4.0), (True, 1e-3, False, 2), bad, "fp32")
+        k, key, d = pick(0, np.arange(4.0), (True, 1e-3, False, 2), bad)
         assert k == 3 and np.isnan(key[2])
-        k, key, d = driver._distogram_pick(None, cols, 1, np.arange(4.0), (False, 1e-3, False, 2), None, "fp32")
+        k, key, d = pick(1, np.arange(4.0), (False, 1e-3, False, 2), None)
         assert k == 1 and np.array_equal(key, np.arange(4.0))
         r = driver._distogram_result(dd, 3, (True, 1e-3, False, 2), bad)
         assert r["distogram"] == dict(dist_nll=4.1, dist_nll_near=None, exp_contacts=11.0, n_near=0, rank=1, t=1e-3, contact_bins=7,

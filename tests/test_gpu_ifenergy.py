@@ -428,9 +428,10 @@ def test_drivers_and_cli(model, tmp_path):
     # the models come in ascending total and model 1 is the kept pose
     gx = type("G", (), {"lig_pos0": lig0, "close": lambda self: None})()
     tj = fil["trajectories"]
-    res = driver._finish(model, gx, rec, lig, {c: tj[c] for c in ("energy", "rot_update", "tr_update")}, (np.argmin, "energy"), tj["energy"],
-                         lambda k: {}, "fp32", None, None, ster=driver._check_sterics(False, True, 3.0, 5.0), clu=(24, 4.0, "energy"),
-                         ie=driver._check_interface(True, "interface", (0.0, 1.0, 0.0), 8.0))
+    run = driver._Run(model, gx, rec, lig, {c: tj[c] for c in ("energy", "rot_update", "tr_update")}, "fp32",
+                      dict(sterics=driver._check_sterics(False, True, 3.0, 5.0), interface=driver._check_interface(True, "interface", (0.0, 1.0, 0.0), 8.0)))
+    run.key = tj["energy"]
+    res = driver._finish(run, (np.argmin, "energy"), lambda k: {}, clu=(24, 4.0, "energy"))
     idx = [m["index"] for m in res["models"]]
     totals = [m["interface_energy"]["total"] for m in res["models"]]
     print("models", idx, totals)

@@ -570,10 +570,13 @@ def test_driver_inputs_and_the_shared_finish(tmp_path, monkeypatch):
         def close(self):
             pass
     model = type("M", (), {"hp": type("Hp", (), {"family": 0})})()
-    fin = lambda **kw: driver._finish(model, Gx(), rec, lig, cols, (np.argmin, "energy"), energy, lambda k: {}, "fp32", None, None, **kw)
+    def fin(clu=None, **opts):
+        run = driver._Run(model, Gx(), rec, lig, cols, "fp32", opts)
+        run.key = energy
+        return driver._finish(run, (np.argmin, "energy"), lambda k: {}, clu)
     r = fin()
     assert not any(k in r for k in ("n_hbond", "hbond_data", "index", "n_salt")) and "args" not in seen
-    r = fin(hb=driver._check_hbonds(True, 3.5, 90.0, 4.0), clu=(2, 4.0, "energy"))
+    r = fin(hbonds=driver._check_hbonds(True, 3.5, 90.0, 4.0), clu=(2, 4.0, "energy"))
     want = lambda k: {"n_hbond": int(kind[k].sum()), "hb_bb_bb": int(kind[k, 0]), "hb_bb_sc": int(kind[k, 1]), "hb_sc_sc": int(kind[k, 2]), "n_salt": k + 2}
     assert seen["args"] == ((n, 3), 3.5, 90.0, 4.0, False) and r["index"] == 1 and {k: r[k] for k in want(1)} == want(1) and "n_unsat" not in r
     assert set(r["trajectories"]) == {"energy", "rot_update", "tr_update"} and r["hbond_data"]["n_salt_atoms"].tolist() == list(range(3, 3 + n))
@@ -581,7 +584,7 @@ def test_driver_inputs_and_the_shared_finish(tmp_path, monkeypatch):
     json.dumps({k: r[k] for k in want(1)})
     # with the surface in the same run: one per-atom surface call, and n_unsat = receptor atom 0 (fully buried, no bond) plus the ligand's
     # atom in the poses where it has no bond; the receptor's acceptor buries 5 of 6 points only
-    r = fin(hb=driver._check_hbonds(True, 3.5, 90.0, 4.0), surf=driver._check_surface(True, None, 1.4, 128), clu=(2, 4.0, "energy"))
+    r = fin(hbonds=driver._check_hbonds(True, 3.5, 90.0, 4.0), surface=driver._check_surface(True, None, 1.4, 128), clu=(2, 4.0, "energy"))
     assert calls == [True] and seen["args"][4] is True and r["hbond_data"]["n_unsat"].tolist() == [2, 1, 2, 1, 2] and r["n_unsat"] == 1 and r["bsa"] == 100.0
     assert [m["n_unsat"] for m in r["models"]] == [1, 1]
 

@@ -352,7 +352,10 @@ def test_driver_inputs_and_selection_helpers(tmp_path):
     ed = {"rep": np.array([1.0, 2.0]), "att": np.array([-3.0, -1.0]), "elec": np.array([0.5, 0.0]), "total": np.array([-2.5, -0.5]), "n_pairs": np.array([40, 9])}
     assert driver._pose_interface(ed, 1) == {"rep": 2.0, "att": -1.0, "elec": 0.0, "total": -0.5, "n_pairs": 9}
     json.dumps(driver._pose_interface(ed, 0))
-    assert driver._interface_pick(None, None, None, None, 3, None, None) == (3, None, None) and driver._interface_result(None, 3, None) == {}
+    off = driver._Run(None, type("G", (), {"lig_pos0": None}), None, None, None, "fp32", {"interface": None})      # off: no stage of _finish runs it
+    off.k = 3
+    [a.run(off) for a in driver.ANALYSES if a.name in off.opts]
+    assert (off.k, off.key, off.data) == (3, None, {}) and not off.any() and driver._interface_result(None, 3, None) == {}
 
 
 def test_every_summary_describes_the_kept_pose(tmp_path, monkeypatch):
@@ -390,8 +393,9 @@ def test_every_summary_describes_the_kept_pose(tmp_path, monkeypatch):
             monkeypatch.setattr(driver, "_screen", lambda *a: ({"flags": bad, "n_clash": np.zeros(n, int), "n_contact": np.ones(n, int), "min_dist": np.ones(n),
                                                               "threshold": 1.0, "ensemble_mean": 0.0, "ensemble_std": 0.0, "clash_cutoff": 3.0,
                                                               "contact_cutoff": 5.0, "filtered": True, "fallback": False}, bad))
-        return driver._finish(model, Gx(), rec, lig, cols, (np.argmin, "energy"), energy, lambda k: {}, "fp32", None, None, cons=cons,
-                              ster=(True, 3.0, 5.0) if bad is not None else None, ie=ie)
+        run = driver._Run(model, Gx(), rec, lig, cols, "fp32", dict(consensus=cons, sterics=(True, 3.0, 5.0) if bad is not None else None, interface=ie))
+        run.key = energy
+        return driver._finish(run, (np.argmin, "energy"), lambda k: {})
     for rank, want, by in (("energy", 0, "energy"), ("consensus", 2, "consensus"), ("interface", 3, "interface")):
         r = finish(rank, True, True)
         assert r["index"] == want and np.array_equal(r["rot_update"], cols["rot_update"][want]) and r["energy"] == float(energy[want])

@@ -364,3 +364,151 @@ def test_plain_dock_pair_keeps_the_batchwise_minimum(monkeypatch, tmp_path, pair
     k = batchwise_minimum(e)
     assert k == OVERLAP and int(np.argmin(e)) == N_TRAJ - 1 and int(np.nanargmin(e)) == N_TRAJ - 2
     assert res["energy"] == float(e[k]) and np.array_equal(res["tr_update"], gx.columns()["tr_update"][k]) and "index" not in res
+
+
+RANKS = ("energy", "consensus", "interface", "distogram", "pairpot")
+EVERY = dict(consensus=True, clash_filter=True, bsa=True, min_bsa=150.0, interface_energy=True, affinity=True, hbonds=True, native=True, top_k=3,
+             refine_t=0.1, refine_samples=2)
+MODEL_KEYS = ["rank", "index", "energy", "cluster_size", "sterics", "bsa", "bsa_rec", "bsa_lig", "interface_energy", "affinity", "dist_nll",
+              "dist_nll_near", "exp_contacts", "n_hbond", "hb_bb_bb", "hb_bb_sc", "hb_sc_sc", "n_salt", "n_unsat", "pair_potential", "metrics",
+              "refined_metrics", "refined_energy", "refined_index"]      # in the order the result line prints them
+DISTOGRAM_KEYS = {"dist_nll", "dist_nll_near", "exp_contacts"}
+
+
+def stub_analyses(monkeypatch, seen):
+    """Every analysis of the pair drivers that would need the device, answered by fixed seeded arrays of N_TRAJ poses; each call appends its
+    name to the model's log and its arguments of interest to `seen`."""
+    from dfmdock_amd import driver
+    rng = np.random.default_rng(77)
+    n = N_TRAJ
+    draw = lambda: rng.permutation(n).astype(np.float64) - 4.5      # no ties; the minimum is somewhere else every time
+    total, ppe, nll = draw(), draw(), draw()
+    kind = rng.integers(0, 5, (n, 3))
+
+    def ensemble_surface(model, rec, lig, rot, tr, probe, points, per_atom=False):
+        model.log.append("surface")
+        seen.setdefault("surface", []).append((probe, points, per_atom))
+        bd = {"bsa": np.arange(n) * 100.0, "bsa_rec": np.arange(n) * 60.0, "bsa_lig": np.arange(n) * 40.0, "probe": probe, "sphere_points": points}
+        if per_atom:
+            bd.update(rec_exposed=np.int32([4, 0, 0, 6]), lig_exposed=np.int32([0, 5]), rec_buried=np.int32([[4, 0, 0, 5]] * n), lig_buried=np.int32([[0, 5]] * n))
+        return bd
+
+    def ensemble_interface_energy(model, rec, lig, rot, tr, cutoff, weights):
+        model.log.append("interface")
+        return {"rep": np.arange(n) + 0.5, "att": -np.arange(n) - 0.25, "elec": np.zeros(n), "total": total.copy(), "n_pairs": np.arange(100, 100 + n)}
+
+    def ensemble_pairpot(model, rec, lig, rot, tr, pot):
+        model.log.append("pairpot")
+        return {"energy": ppe.copy(), "n_pairs": np.arange(200, 200 + n), "n_untyped": 2, "T": 3, "NB": 30, "cutoff": 15.0}
+
+    def pose_affinity(model, rec, lig, rot, tr, cutoff, probe, points, surface=None):
+        model.log.append("affinity")
+        seen["affinity_surface"] = surface
+        ic = np.arange(6 * n).reshape(n, 6)
+        return {"ic": ic, "n_pairs": ic.sum(1), "n_rec_res": np.arange(n), "n_lig_res": np.arange(n) + 1, "nis_apolar": np.linspace(30, 40, n),
+                "nis_charged": np.linspace(20, 25, n), "dg": -np.arange(n) - 7.0, "kd": np.full(n, 1e-6), "cutoff": cutoff}
+
+    def ensemble_hbonds(model, rec, lig, rot, tr, hb_cutoff, min_angle, salt_cutoff, per_atom=False):
+        model.log.append("hbonds")
+        seen["hbonds_per_atom"] = per_atom
+        hd = {"n_hbond": kind.sum(1), "hb_kind": kind, "n_salt": np.arange(n) + 2, "untyped": (0, 0),
+              "rec_polar": {"role": np.uint8([1, 2]), "index": np.array([0, 3])}, "lig_polar": {"role": np.uint8([3]), "index": np.array([1])}}
+        if per_atom:
+            hd.update(rec_hb=np.zeros((n, 2), np.int32), lig_hb=(np.arange(n)[:, None] % 2).astype(np.int32))
+        return hd
+
+    def ensemble_distogram(gx, rot, tr, t, precision, max_batch, maps=False, seed=0):
+        gx.model.log.append("distogram")
+        assert gx.calls["close"] == 0, "the distogram needs the open handle"
+        return {"nll": nll.copy(), "nll_near": nll + 0.5, "n_near": np.arange(n), "exp_contacts": np.arange(n) + 10.0, "t": float(t), "contact_bins": 7}
+    for f in (ensemble_surface, ensemble_interface_energy, ensemble_pairpot, pose_affinity, ensemble_hbonds, ensemble_distogram):
+        monkeypatch.setattr(driver, f.__name__, f)
+    return {"interface": total, "pairpot": ppe, "distogram": nll}
+
+
+def seeded_table():
+    rng = np.random.default_rng(3)
+    return {"edges": np.linspace(0.0, 15.0, 31).astype(np.float32), "table": rng.uniform(-1.0, 1.0, (3, 3, 30)).astype(np.float32),
+            "type_names": ["@C", "@N", "*"]}
+
+
+@pytest.mark.parametrize("rank", RANKS)
+@pytest.mark.parametrize("kind", DRIVERS)
+def test_every_analysis_at_once(monkeypatch, tmp_path, pair, kind, rank):
+    """Every analysis switched on together, under every rank: the order of the calls, the entries of the result and of every model, which
+    pose is kept, who says it ranked, and that every summary describes that one pose."""
+    from dfmdock_amd import driver
+    rec, lig = pair
+    for family in (0, 1):
+        seen = {}
+        column = stub_analyses(monkeypatch, seen)
+        opts = dict(EVERY, rank=rank, pair_potential=seeded_table(), **({"distogram": True} if family == 1 else {}))
+        if rank == "distogram" and family == 0:      # the head exists in the second family only: refused before a handle is made
+            monkeypatch.setattr(driver.engine, "Complex", FakeComplex)
+            with pytest.raises(ValueError, match="family-1"):
+                (driver.refine_pair if kind == "refine" else driver.dock_pair)(FakeModel(0), rec, lig, None, None, **{k: v for k, v in opts.items() if k != "native"})
+            continue
+        res, gx, model, out, kw = run(monkeypatch, tmp_path, pair, kind, opts, family)
+        cols, log, models = gx.columns(), list(model.log), res.get("models", [])
+        dock, dg = kind != "refine", family == 1
+        # the order of events
+        want = ["draw"] * 3 + (["close"] if not dock and not dg else []) + ["sterics"] + (["distogram"] if dg else []) + \
+               (["close"] if not dock and dg else []) + ["interface", "pairpot", "consensus", "surface", "affinity", "hbonds", "write", "metrics"]
+        if dock:
+            want += ["cluster"] + ["write"] * len(models) + ["metrics", "draw", "metrics"] + ["write"] * len(models) + ["close"]
+        else:
+            want += ["metrics"]      # start_metrics
+        assert log == want, (kind, rank, family, log)
+        assert seen["surface"] == [(float(np.float32(1.4)), 128, True)] and seen["affinity_surface"] is res["bsa_data"] and seen["hbonds_per_atom"] is True
+        # the entries of the result and of every model
+        keys = expected_keys(kind, {k: v for k, v in kw.items() if k in ("consensus", "rank", "clash_filter", "native", "top_k")}) | {
+            "index", "trajectories", "bsa", "bsa_rec", "bsa_lig", "bsa_data", "probe", "sphere_points", "min_bsa", "interface_energy", "interface_data",
+            "pair_potential", "pairpot_data", "affinity", "affinity_data", "n_hbond", "hb_bb_bb", "hb_bb_sc", "hb_sc_sc", "n_salt", "n_unsat", "hbond_data"}
+        keys |= ({"distogram", "distogram_data"} if dg else set()) | ({"bsa_dropped"} if dock else set())
+        assert set(res) == keys, (kind, rank, family, sorted(set(res) ^ keys))
+        assert list(res["trajectories"]) == (list(COLUMNS) if kind in ("dock", "refine") else ["energy", "restraint_energy", "restraints_satisfied"])
+        assert len(models) >= 1 if dock else "models" not in res
+        for m in models:
+            assert list(m) == [k for k in MODEL_KEYS if dg or k not in DISTOGRAM_KEYS], list(m)
+        # the kept pose: the lowest value of the rank's column among the poses the filter left
+        flags = screen_flags(rec, lig, cols, family)
+        assert np.nonzero(flags)[0].tolist() == [OVERLAP]
+        if rank in column:
+            k = int(np.argmin(np.where(flags, np.inf, column[rank])))
+        else:
+            k = expected_index(kind, {k: v for k, v in kw.items() if k in ("rank", "clash_filter")}, rec, lig, cols, family)
+        assert res["index"] == k and res["energy"] == float(cols["energy"][k]) and np.array_equal(res["rot_update"], cols["rot_update"][k])
+        if dock:
+            assert res["bsa_dropped"] + len(models) <= 3 and all(m["bsa"] >= 150.0 and not flags[m["index"]] for m in models)
+            if k >= 2:
+                assert models[0]["index"] == k      # under rule "energy" model 1 is the kept pose, unless min_bsa drops it
+        # who ranked
+        assert res["consensus"]["ranked_by"] == rank and res["consensus"]["fallback"] is False
+        assert res["interface_energy"]["ranked_by"] == rank
+        if dg:
+            assert res["distogram"]["ranked_by_distogram"] is (rank == "distogram")
+        assert res["sterics"]["filtered"] is True and res["sterics"]["fallback"] is False and res["min_bsa"] == 150.0
+        # every summary is that of the kept pose, every model's that of its own
+        has = lambda whole, part: {key: whole[key] for key in part} == part
+        for at, into in [(k, res)] + [(m["index"], m) for m in models]:
+            assert has(into["sterics"], driver._pose_sterics(res["sterics_data"], at)) and has(into, driver._pose_bsa(res["bsa_data"], at))
+            assert has(into["interface_energy"], driver._pose_interface(res["interface_data"], at))
+            assert into["pair_potential"] == driver._pose_pairpot(res["pairpot_data"], at) and into["affinity"] == driver._pose_affinity(res["affinity_data"], at)
+            assert has(into, driver._pose_hbonds(res["hbond_data"], at)) and "n_unsat" in driver._pose_hbonds(res["hbond_data"], at)
+            if dg:
+                assert has(into["distogram"] if into is res else into, driver._pose_distogram(res["distogram_data"], at))
+        assert res["consensus"]["n_contacts"] == int(res["consensus_data"]["n_contacts"][k])
+        for name in ("pairpot_data", "hbond_data"):      # they carry the poses their arrays are of
+            assert np.array_equal(res[name]["rot_update"], cols["rot_update"]) and np.array_equal(res[name]["tr_update"], cols["tr_update"])
+        assert gx.calls["close"] == 1
+
+
+@pytest.mark.parametrize("rank", ("energy", "interface", "distogram", "pairpot"))
+def test_ranked_by_without_consensus(monkeypatch, tmp_path, pair, rank):
+    """Without the consensus option `interface_energy` names the rule that kept the pose - except rank "distogram", which it reports as
+    "energy" (the distogram object says ranked_by_distogram)."""
+    column = stub_analyses(monkeypatch, {})
+    res, gx, _, _, _ = run(monkeypatch, tmp_path, pair, "refine", dict(rank=rank, interface_energy=True, distogram=True, pair_potential=seeded_table()), 1)
+    want = int(np.argmin(column[rank])) if rank in column else int(np.argmin(gx.columns()["energy"]))
+    assert res["index"] == want and "consensus" not in res
+    assert res["interface_energy"]["ranked_by"] == {"distogram": "energy"}.get(rank, rank) and res["distogram"]["ranked_by_distogram"] is (rank == "distogram")

@@ -235,7 +235,7 @@ def test_cli_flags_parse_default_off_and_reach_the_driver(tmp_path, monkeypatch,
                 cli.parse_args([cmd] + base + bad)
     with pytest.raises(SystemExit):
         cli.parse_args(["sweep", "--db5", "d", "--ckpt", "c", "--clash-screen"])      # sweep is left alone: the DB5 files hold backbones only
-    # cmd_dock with the engine stubbed: what reaches dock_pair, what the line and the residue file hold
+    # cmd_pair (dock) with the engine stubbed: what reaches dock_pair, what the line and the residue file hold
     cx, rs, ls = golden_7cei()
     rec_pdb, lig_pdb, feat = write_pair(str(tmp_path), cx, rs, ls)
     seen = {}
