@@ -1,30 +1,27 @@
 """Kernel-level harness of the node-model GEMMs and GraphNorm statistics (tests/kernels/dense_harness.hip), and their float64 references.
 
-The shim is host code that drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so (dfm::launch_gemm_split, launch_gemm_f32,
-launch_gn_stats) on host arrays, with sentinel guard bands around every device block.  This module compiles it, binds it with ctypes
-and restates, in numpy, what the engine does on the host for these kernels: the split-bf16 weight tiles of api.hip's split_bf16
-([K/32][4][Nout][8] bf16 hi / lo) and the fp16 conversion f2h of dfm_device.h.
+The shim drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so (dfm::launch_gemm_split, launch_gemm_f32, launch_gn_stats)
+under the guard-band protocol of tests/kernel_harness.py.  This module binds it and restates, in numpy, what the engine does on the
+host for these kernels: the split-bf16 weight tiles of api.hip's split_bf16 ([K/32][4][Nout][8] bf16 hi / lo) and the fp16 conversion
+f2h of dfm_device.h.
 
 Run as a script (`python dense_harness.py child SHIM IN.npz OUT.npz`) it replays a list of launches stored in IN.npz and writes every
 output to OUT.npz: the tile-shape tests run it in child processes, because the launcher reads its shape overrides once per process.
 """
 import ctypes as C
-import os
-import shutil
-import subprocess
+import functools
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "dfmdock_amd")
-SHIM_SRC = os.path.join(ROOT, "tests", "kernels", "dense_harness.hip")
+import kernel_harness as kh
+from kernel_harness import HIP_INVALID_VALUE, HIP_SUCCESS, LIBDIR, ROOT, Out, guards_intact, hipcc, replay, save_launches      # noqa: F401 (re-exported)
+
 LAUNCHERS = ("_ZN3dfm17launch_gemm_splitERKNS_8GemmArgsEPKtS4_P12ihipStream_t",
              "_ZN3dfm15launch_gemm_f32ERKNS_8GemmArgsEP12ihipStream_t",
              "_ZN3dfm15launch_gn_statsEPKfiiS1_PfS2_S1_S1_P12ihipStream_t")
 H = 256
 U32 = 2.0 ** -24                  # unit roundoff of fp32
-HIP_SUCCESS, HIP_INVALID_VALUE = 0, 1
 
 # Bound of the three-term split GEMM relative to |A| |W|^T (derivation: the docstring of test_gpu_dense_kernels.py)
 C_SPLIT = 2.0 ** -15
@@ -32,43 +29,22 @@ C_SPLIT = 2.0 ** -15
 SLOTS = ("A0", "A1", "W", "Whi", "Wlo", "bias", "gn_shift", "gn_den", "gn_w", "gn_b", "gn_part", "gn_ms", "R",
          "C", "C2", "C2b", "Cb", "stat_part", "zbuf")
 INTS = ("M", "K", "Nout", "lda", "ldw", "ldc", "pro", "epi", "rows_per_graph", "a0_period", "r_period", "a0_offset", "gn_B", "gn_N")
+OPS = ("split", "f32", "gn_stats")
 
 
-class DhBuf(C.Structure):
-    _fields_ = [("host", C.c_void_p), ("bytes", C.c_longlong), ("out", C.c_int)]
+class Call(C.Structure):
+    _fields_ = [("buf", kh.Buf * len(SLOTS))] + [(n, C.c_int) for n in INTS]
 
 
-class DhCall(C.Structure):
-    _fields_ = [("buf", DhBuf * len(SLOTS))] + [(n, C.c_int) for n in INTS]
+compile_shim = functools.partial(kh.compile_shim, "dense")
 
 
-def hipcc():
-    return os.environ.get("HIPCC") or "/opt/rocm/bin/hipcc"
-
-
-def compile_shim(outdir):
-    """hipcc --offload-arch=gfx950 -shared -fPIC, linked against the built library with an rpath.  Raises if the compiler is missing."""
-    cc = hipcc()
-    if not (os.path.isfile(cc) or shutil.which(cc)):
-        raise RuntimeError(f"hipcc not found ({cc}): the kernel harness cannot be built")
-    out = os.path.join(str(outdir), "libdense_harness.so")
-    subprocess.run([cc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", SHIM_SRC, "-o", out,
-                    "-L", LIBDIR, "-ldfmdock_amd", "-Wl,-rpath," + LIBDIR], check=True, capture_output=True, text=True)
-    return out
-
-
-class Harness:
+class Harness(kh.KernelHarness):
     def __init__(self, path):
-        self.path = path
-        self.lib = C.CDLL(path)
-        for f in ("dh_gemm_split", "dh_gemm_f32", "dh_gn_stats"):
-            getattr(self.lib, f).argtypes = [C.POINTER(DhCall)]
-            getattr(self.lib, f).restype = C.c_int
+        super().__init__(path, Call, SLOTS, OPS)
         self.lib.dh_validate_split.argtypes = [C.c_int] * 10
         self.lib.dh_validate_split.restype = C.c_int
         self.lib.dh_device_cus.argtypes = [C.POINTER(C.c_int)]
-        self.lib.dh_guard_bytes.restype = C.c_longlong
-        self.guard = int(self.lib.dh_guard_bytes())
 
     def cus(self):
         n = C.c_int(0)
@@ -78,39 +54,6 @@ class Harness:
 
     def validate_split(self, M, K, Nout, lda, ldc, pro=0, epi=0, rows_per_graph=0, stats=False, zbuf=False):
         return self.lib.dh_validate_split(M, K, Nout, lda, ldc, pro, epi, rows_per_graph, int(stats), int(zbuf))
-
-    def run(self, op, ins, outs, **ints):
-        """op: 'split' | 'f32' | 'gn_stats'.  ins: slot -> array (uploaded as is); outs: slot -> (dtype, element count).
-        Returns {slot: interior array, slot + '_guard': (before, after) raw bytes}."""
-        call = DhCall()
-        keep = []
-        for k, v in ints.items():
-            setattr(call, k, int(v))
-        for k, v in ins.items():
-            if v is None:
-                continue
-            a = np.ascontiguousarray(v)
-            keep.append(a)
-            b = call.buf[SLOTS.index(k)]
-            b.host, b.bytes, b.out = a.ctypes.data, a.nbytes, 0
-        host = {}
-        for k, (dt, n) in outs.items():
-            nbytes = np.dtype(dt).itemsize * int(n)
-            raw = np.zeros(self.guard * 2 + nbytes, np.uint8)
-            host[k] = (raw, dt, nbytes)
-            b = call.buf[SLOTS.index(k)]
-            b.host, b.bytes, b.out = raw.ctypes.data, nbytes, 1
-        e = {"split": self.lib.dh_gemm_split, "f32": self.lib.dh_gemm_f32, "gn_stats": self.lib.dh_gn_stats}[op](C.byref(call))
-        res = {"err": e}
-        for k, (raw, dt, nbytes) in host.items():
-            res[k] = raw[self.guard:self.guard + nbytes].view(dt).copy()
-            res[k + "_guard"] = (raw[:self.guard], raw[self.guard + nbytes:])
-        return res
-
-
-def guards_intact(res, slot):
-    a, b = res[slot + "_guard"]
-    return bool((a == 0xff).all() and (b == 0xff).all())
 
 
 # ---- host restatements --------------------------------------------------------------------------------------------------------
@@ -256,40 +199,5 @@ FORCE_ENV = {"nj2": {"DFM_GEMM_NARROW_MAXWG": "0"},
              "qt": {"DFM_GEMM_NARROW_MAXWG": "1000000000", "DFM_GEMM_QUARTER_MAXWG": "1000000000"}}
 
 
-# ---- replay of stored launches (child processes) ---------------------------------------------------------------------------
-def save_launches(path, launches):
-    """launches: list of dicts {op, ins: {slot: array}, outs: {slot: (dtype, n)}, ints: {...}} -> one npz."""
-    flat = {"n": np.array(len(launches))}
-    for i, L in enumerate(launches):
-        flat[f"{i}/op"] = np.array(L["op"])
-        for k, v in L["ins"].items():
-            if v is not None:
-                flat[f"{i}/in/{k}"] = np.asarray(v)
-        for k, (dt, n) in L["outs"].items():
-            flat[f"{i}/out/{k}"] = np.array([np.dtype(dt).str, str(int(n))])
-        for k, v in L["ints"].items():
-            flat[f"{i}/int/{k}"] = np.array(int(v))
-    np.savez(path, **flat)
-
-
-def replay(h, path_in, path_out):
-    d = np.load(path_in)
-    res = {}
-    for i in range(int(d["n"])):
-        op = str(d[f"{i}/op"])
-        ins = {k.split("/")[2]: d[k] for k in d.files if k.startswith(f"{i}/in/")}
-        outs = {k.split("/")[2]: (np.dtype(str(d[k][0])), int(d[k][1])) for k in d.files if k.startswith(f"{i}/out/")}
-        ints = {k.split("/")[2]: int(d[k]) for k in d.files if k.startswith(f"{i}/int/")}
-        r = h.run(op, ins, outs, **ints)
-        if r["err"] != HIP_SUCCESS:
-            raise RuntimeError(f"launch {i} ({op}): hipError {r['err']}")
-        for k in outs:
-            res[f"{i}/{k}"] = r[k]
-    np.savez(path_out, **res)
-
-
 if __name__ == "__main__":
-    if len(sys.argv) == 5 and sys.argv[1] == "child":
-        replay(Harness(sys.argv[2]), sys.argv[3], sys.argv[4])
-    else:
-        sys.exit("usage: dense_harness.py child SHIM IN.npz OUT.npz")
+    kh.child_main(Harness, sys.argv)

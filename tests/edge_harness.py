@@ -1,9 +1,8 @@
 """Kernel-level harness of the message kernels (tests/kernels/edge_harness.hip) and their float64 references and error bounds.
 
-The shim is host code that drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so (dfm::launch_edge_bf16, launch_coord_bf16,
-launch_edge_f32, launch_edge_rows, launch_edge_rows32, launch_l0_gather, launch_l0_gather32) on host arrays, with sentinel guard bands
-around every device block.  This module compiles it, binds it with ctypes and restates in numpy what api.hip's dfm_model_create does
-for one layer: the float64 table Td, the merged fp16 table T2b (scaled by SILU_S), the 16-bit weight fragments (pack_frags), the packed
+The shim drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so (dfm::launch_edge_bf16, launch_coord_bf16, launch_edge_f32,
+launch_edge_rows, launch_edge_rows32, launch_l0_gather, launch_l0_gather32) under the guard-band protocol of tests/kernel_harness.py.
+This module binds it and restates in numpy what api.hip's dfm_model_create does for one layer: the float64 table Td, the merged fp16 table T2b (scaled by SILU_S), the 16-bit weight fragments (pack_frags), the packed
 bias pairs (pack_bias), the SILU_S scalings of w_r, att_b and wc2, and pack_code.  The error bounds are derived in the docstring of
 tests/test_gpu_edge_kernels.py; edge_rows / coord_ref / f32m_rows below compute them per element.
 
@@ -12,17 +11,15 @@ output to OUT.npz: the task-form tests run it in child processes, because the la
 per process.
 """
 import ctypes as C
-import os
-import subprocess
+import functools
 import sys
 
 import numpy as np
 
 import dense_harness as dh
+import kernel_harness as kh
+from kernel_harness import HIP_INVALID_VALUE, HIP_SUCCESS, LIBDIR, ROOT, Out, guards_intact, replay, save_launches      # noqa: F401 (re-exported)
 
-ROOT = dh.ROOT
-LIBDIR = dh.LIBDIR
-SHIM_SRC = os.path.join(ROOT, "tests", "kernels", "edge_harness.hip")
 LAUNCHERS = ("_ZN3dfm16launch_edge_bf16ERKNS_8EdgeArgsEP12ihipStream_t",
              "_ZN3dfm17launch_coord_bf16ERKNS_8EdgeArgsEP12ihipStream_t",
              "_ZN3dfm15launch_edge_f32ERKNS_8EdgeArgsEP12ihipStream_t",
@@ -38,8 +35,7 @@ NTAB2 = 6912 + 2640
 TASK_CTR_WGS = 1024
 EDGE_WAVES = 8
 L0_MISS = 0x80000000
-HIP_SUCCESS, HIP_INVALID_VALUE = dh.HIP_SUCCESS, dh.HIP_INVALID_VALUE
-OPS = {"edge_bf16": 0, "coord_bf16": 1, "edge_f32": 2, "edge_rows": 3, "edge_rows32": 4, "l0_gather": 5, "l0_gather32": 6}
+OPS = ("edge_bf16", "coord_bf16", "edge_f32", "edge_rows", "edge_rows32", "l0_gather", "l0_gather32")
 
 SLOTS = ("A", "Bm", "Bmb", "Ah", "edges", "codes", "radial", "ca4",
          "T", "T2b", "W2t", "W2f", "W2f16", "b2", "b2p", "b2p16", "att_w", "w_r", "w_r_s",
@@ -49,37 +45,22 @@ SLOTS = ("A", "Bm", "Bmb", "Ah", "edges", "codes", "radial", "ca4",
 INTS = ("B", "N", "R", "K", "last", "f16", "lig_only", "agg_is_zero", "n_rows_cap", "repeat")
 
 
-class EhBuf(C.Structure):
-    _fields_ = [("host", C.c_void_p), ("bytes", C.c_longlong), ("out", C.c_int)]
+class Call(C.Structure):
+    _fields_ = [("buf", kh.Buf * len(SLOTS)), ("ab_bstride", C.c_longlong), ("att_b", C.c_float)] + [(n, C.c_int) for n in INTS]
 
 
-class EhCall(C.Structure):
-    _fields_ = [("buf", EhBuf * len(SLOTS)), ("ab_bstride", C.c_longlong), ("att_b", C.c_float)] + [(n, C.c_int) for n in INTS]
+compile_shim = functools.partial(kh.compile_shim, "edge")
 
 
-def compile_shim(outdir):
-    """hipcc --offload-arch=gfx950 -shared -fPIC, linked against the built library with an rpath.  Raises if the compiler is missing."""
-    cc = dh.hipcc()
-    out = os.path.join(str(outdir), "libedge_harness.so")
-    subprocess.run([cc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", SHIM_SRC, "-o", out,
-                    "-L", LIBDIR, "-ldfmdock_amd", "-Wl,-rpath," + LIBDIR], check=True, capture_output=True, text=True)
-    return out
-
-
-class Harness:
+class Harness(kh.KernelHarness):
     def __init__(self, path):
-        self.path = path
-        self.lib = C.CDLL(path)
-        self.lib.eh_run.argtypes = [C.POINTER(EhCall), C.c_int]
-        self.lib.eh_run.restype = C.c_int
+        super().__init__(path, Call, SLOTS, OPS)
         self.lib.eh_validate.argtypes = [C.c_int] * 7
         self.lib.eh_validate.restype = C.c_int
         self.lib.eh_tile_tasks.argtypes = [C.c_int] * 3
         self.lib.eh_tile_tasks.restype = C.c_int
         self.lib.eh_device_cus.restype = C.c_int
-        self.lib.eh_guard_bytes.restype = C.c_longlong
         self.lib.eh_last_ms.restype = C.c_float
-        self.guard = int(self.lib.eh_guard_bytes())
 
     def cus(self):
         return int(self.lib.eh_device_cus())
@@ -92,47 +73,7 @@ class Harness:
         return bool(self.lib.eh_tile_tasks(B, N, K))
 
     def validate(self, op, B, N, R, K, last=0, lig_only=0):
-        return self.lib.eh_validate(OPS[op], B, N, R, K, last, lig_only)
-
-    def run(self, op, ins, outs, ints):
-        """ins: slot -> array (uploaded as is); outs: slot -> (dtype, element count) or (initial interior array,) for an in-out block.
-        ints: INTS / ab_bstride / att_b.  Returns {slot: interior, slot + '_guard': (before, after) raw bytes, 'err': hipError}."""
-        call = EhCall()
-        keep = []
-        for k, v in ints.items():
-            setattr(call, k, float(v) if k == "att_b" else int(v))
-        for k, v in ins.items():
-            if v is None:
-                continue
-            a = np.ascontiguousarray(v)
-            keep.append(a)
-            b = call.buf[SLOTS.index(k)]
-            b.host, b.bytes, b.out = a.ctypes.data, a.nbytes, 0
-        host = {}
-        for k, spec in outs.items():
-            if len(spec) == 1:
-                init = np.ascontiguousarray(spec[0])
-                dt, nbytes = init.dtype, init.nbytes
-                raw = np.full(self.guard * 2 + nbytes, 0xff, np.uint8)
-                raw[self.guard:self.guard + nbytes] = init.view(np.uint8).ravel()
-                mode = 2
-            else:
-                dt, n = spec
-                nbytes = np.dtype(dt).itemsize * int(n)
-                raw = np.zeros(self.guard * 2 + nbytes, np.uint8)
-                mode = 1
-            host[k] = (raw, dt, nbytes)
-            b = call.buf[SLOTS.index(k)]
-            b.host, b.bytes, b.out = raw.ctypes.data, nbytes, mode
-        e = self.lib.eh_run(C.byref(call), OPS[op])
-        res = {"err": e}
-        for k, (raw, dt, nbytes) in host.items():
-            res[k] = raw[self.guard:self.guard + nbytes].view(dt).copy()
-            res[k + "_guard"] = (raw[:self.guard], raw[self.guard + nbytes:])
-        return res
-
-
-guards_intact = dh.guards_intact
+        return self.lib.eh_validate(OPS.index(op), B, N, R, K, last, lig_only)
 
 
 # ---- host restatements of api.hip ---------------------------------------------------------------------------------------------
@@ -456,45 +397,5 @@ def f32m_coord(L, gm, e_gm, xi, xj, K):
     return _coord_tail(w, e_w, xi, xj, K)
 
 
-# ---- replay of stored launches (child processes) ---------------------------------------------------------------------------
-def save_launches(path, launches):
-    """launches: list of dicts {op, ins: {slot: array}, outs: {slot: spec}, ints: {...}} -> one npz."""
-    flat = {"n": np.array(len(launches))}
-    for i, Lc in enumerate(launches):
-        flat[f"{i}/op"] = np.array(Lc["op"])
-        for k, v in Lc["ins"].items():
-            if v is not None:
-                flat[f"{i}/in/{k}"] = np.asarray(v)
-        for k, spec in Lc["outs"].items():
-            if len(spec) == 1:
-                flat[f"{i}/io/{k}"] = np.asarray(spec[0])
-            else:
-                flat[f"{i}/out/{k}"] = np.array([np.dtype(spec[0]).str, str(int(spec[1]))])
-        for k, v in Lc["ints"].items():
-            flat[f"{i}/int/{k}"] = np.array(v)
-    np.savez(path, **flat)
-
-
-def replay(h, path_in, path_out):
-    d = np.load(path_in)
-    res = {}
-    for i in range(int(d["n"])):
-        op = str(d[f"{i}/op"])
-        ins = {k.split("/")[2]: d[k] for k in d.files if k.startswith(f"{i}/in/")}
-        outs = {k.split("/")[2]: (np.dtype(str(d[k][0])), int(d[k][1])) for k in d.files if k.startswith(f"{i}/out/")}
-        outs.update({k.split("/")[2]: (d[k],) for k in d.files if k.startswith(f"{i}/io/")})
-        ints = {k.split("/")[2]: d[k].item() for k in d.files if k.startswith(f"{i}/int/")}
-        r = h.run(op, ins, outs, ints)
-        if r["err"] != HIP_SUCCESS:
-            raise RuntimeError(f"launch {i} ({op}): hipError {r['err']}")
-        for k in outs:
-            res[f"{i}/{k}"] = r[k]
-            res[f"{i}/{k}_guard_ok"] = np.array(guards_intact(r, k))
-    np.savez(path_out, **res)
-
-
 if __name__ == "__main__":
-    if len(sys.argv) == 5 and sys.argv[1] == "child":
-        replay(Harness(sys.argv[2]), sys.argv[3], sys.argv[4])
-    else:
-        sys.exit("usage: edge_harness.py child SHIM IN.npz OUT.npz")
+    kh.child_main(Harness, sys.argv)

@@ -1,9 +1,9 @@
 """Kernel-level harness of the graph front end and the pose kernels (tests/kernels/geom_harness.hip): everything upstream of the trunk.
 
 The shim drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so (dfm::launch_knn_sample, launch_edge_feat with and without the
-table classification, launch_l0_pairs, launch_init_pose, launch_clash_force) on host arrays, with sentinel guard bands around every
-device block; it exports the host versions of philox4x32 / u01 / pack_code and holds one test-only kernel that evaluates the hardware
-log2 of the sampling race on a given array.  This module compiles it, binds it with ctypes and holds
+table classification, launch_l0_pairs, launch_init_pose, launch_clash_force) under the guard-band protocol of tests/kernel_harness.py;
+it exports the host versions of philox4x32 / u01 / pack_code and holds one test-only kernel that evaluates the hardware log2 of the
+sampling race on a given array.  This module binds it and holds
   * the references, written from the model definition (score_net_mlsb.py:30-135, coords6d.py, inference_base.py:255-384), not from the
     kernels: kernels_geom.hip is compiled with -ffp-contract=off, so subtraction, product, sum, sqrt and division are correctly rounded
     fp32 in the order written and a numpy float32 restatement gives the same bits - kNN slots and order, distance bin, relpos, radial
@@ -21,25 +21,19 @@ b N + i: trajectory b of a batch draws the stream a B = 1 launch would draw for 
 holding the same pose get different graphs, and a trajectory's graph depends on its place in the batch.
 """
 import ctypes as C
-import os
-import shutil
-import subprocess
+import functools
 
 import numpy as np
 
-from heads_harness import Out, guards_intact, is_sentinel      # noqa: F401 (re-exported)
+import kernel_harness as kh
+from kernel_harness import HIP_INVALID_VALUE, HIP_SUCCESS, LIBDIR, ROOT, Out, guards_intact, is_sentinel      # noqa: F401 (re-exported)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "dfmdock_amd")
-SHIM_SRC = os.path.join(ROOT, "tests", "kernels", "geom_harness.hip")
 LAUNCHERS = ("_ZN3dfm17launch_knn_sampleEPK15HIP_vector_typeIfLj4EEiiiimjPiPKjP12ihipStream_t",
              "_ZN3dfm16launch_edge_featEPK15HIP_vector_typeIfLj4EES3_S3_PKiiiiifPjPfRKNS_10L0ClassifyES6_P12ihipStream_t",
              "_ZN3dfm15launch_l0_pairsEPK15HIP_vector_typeIfLj4EES3_S3_iifPS0_IjLj2EEPS0_IjLj4EEP12ihipStream_t",
              "_ZN3dfm16launch_init_poseEPKfS1_iiiiS1_S1_mPfS2_S2_P12ihipStream_t",
              "_ZN3dfm18launch_clash_forceEPKfiiiPfS2_P12ihipStream_t")
 U = 2.0 ** -24                    # unit roundoff of fp32
-HIP_SUCCESS = 0
-HIP_INVALID_VALUE = 1
 RNG_EDGES, RNG_INIT = 1, 3
 MISS = 0x80000000
 
@@ -54,41 +48,19 @@ LOG2_PROVISIONAL = (2.0 ** -20, 2.0 ** -24)      # |hw - log2 u| <= rel |log2 u|
 LOG2_ENVELOPE = (2.0 ** -22, 2.0 ** -26)         # measured: 2^-23.01 relative over all u < 1, no absolute excess near 1; twice that, the term kept
 
 
-class GhBuf(C.Structure):
-    _fields_ = [("host", C.c_void_p), ("bytes", C.c_longlong), ("out", C.c_int)]
-
-
-class GhCall(C.Structure):
-    _fields_ = ([("buf", GhBuf * len(SLOTS)), ("n", C.c_longlong), ("seed", C.c_ulonglong), ("mask_dist", C.c_float),
+class Call(C.Structure):
+    _fields_ = ([("buf", kh.Buf * len(SLOTS)), ("n", C.c_longlong), ("seed", C.c_ulonglong), ("mask_dist", C.c_float),
                  ("stream_id", C.c_uint)] + [(n, C.c_int) for n in INTS])
 
 
-def hipcc():
-    return os.environ.get("HIPCC") or "/opt/rocm/bin/hipcc"
-
-
-def compile_shim(outdir):
-    """hipcc --offload-arch=gfx950 -shared -fPIC, linked against the built library with an rpath.  Raises if the compiler is missing."""
-    cc = hipcc()
-    if not (os.path.isfile(cc) or shutil.which(cc)):
-        raise RuntimeError(f"hipcc not found ({cc}): the kernel harness cannot be built")
-    out = os.path.join(str(outdir), "libgeom_harness.so")
-    subprocess.run([cc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", SHIM_SRC, "-o", out,
-                    "-L", LIBDIR, "-ldfmdock_amd", "-Wl,-rpath," + LIBDIR], check=True, capture_output=True, text=True)
-    return out
-
-
+compile_shim = functools.partial(kh.compile_shim, "geom")
 U32P = C.POINTER(C.c_uint)
 
 
-class Harness:
+class Harness(kh.KernelHarness):
     def __init__(self, path):
-        self.path = path
-        self.lib = L = C.CDLL(path)
-        L.gh_run.argtypes = [C.POINTER(GhCall), C.c_int]
-        L.gh_run.restype = C.c_int
-        for f in ("gh_guard_bytes", "gh_call_bytes"):
-            getattr(L, f).restype = C.c_longlong
+        super().__init__(path, Call, SLOTS, OPS)
+        L = self.lib
         L.gh_philox.argtypes = [C.c_longlong, U32P, C.c_uint, C.c_uint, U32P]
         L.gh_u01.argtypes = [C.c_longlong, U32P, C.POINTER(C.c_float)]
         L.gh_u01_scan.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -96,8 +68,6 @@ class Harness:
         L.gh_pack_code.restype = C.c_uint
         L.gh_rng_edges.restype = L.gh_rng_init.restype = C.c_uint
         L.gh_find_top_uniform.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_uint, C.c_ulonglong, C.c_longlong, U32P]
-        self.guard = int(L.gh_guard_bytes())
-        assert int(L.gh_call_bytes()) == C.sizeof(GhCall), "GhCall: the ctypes layout differs from the shim's"
 
     # ---- host functions of the library's headers
     def philox(self, ctr, k0, k1):
@@ -121,33 +91,6 @@ class Harness:
         found = np.zeros(4, np.uint32)
         ok = self.lib.gh_find_top_uniform(n0, n1, c1_mul, n2, int(vary_seed), c3, seed, max_blocks, found.ctypes.data_as(U32P))
         return tuple(int(x) for x in found) if ok else None
-
-    def run(self, op, bufs, **scalars):
-        """bufs: slot -> array (input, uploaded as is) or Out.  Returns {slot: interior array, slot + '_guard': (before, after) bytes}."""
-        call = GhCall()
-        keep, host = [], {}
-        for k, v in scalars.items():
-            setattr(call, k, float(v) if k == "mask_dist" else int(v))
-        for k, v in bufs.items():
-            if v is None:
-                continue
-            b = call.buf[SLOTS.index(k)]
-            if isinstance(v, Out):
-                nbytes = v.dtype.itemsize * v.n
-                raw = np.zeros(self.guard * 2 + nbytes, np.uint8)
-                if v.init is not None:
-                    raw[self.guard:self.guard + nbytes] = v.init.reshape(-1).view(np.uint8)
-                host[k] = (raw, v.dtype, nbytes)
-                b.host, b.bytes, b.out = raw.ctypes.data, nbytes, 1 if v.init is None else 2
-            else:
-                a = np.ascontiguousarray(v)
-                keep.append(a)
-                b.host, b.bytes, b.out = a.ctypes.data, a.nbytes, 0
-        res = {"err": self.lib.gh_run(C.byref(call), OPS.index(op))}
-        for k, (raw, dt, nbytes) in host.items():
-            res[k] = raw[self.guard:self.guard + nbytes].view(dt).copy()
-            res[k + "_guard"] = (raw[:self.guard], raw[self.guard + nbytes:])
-        return res
 
 
 f32 = np.float32

@@ -1,8 +1,8 @@
 """Kernel-level harness of the pair heads and score heads (tests/kernels/heads_harness.hip): everything downstream of the trunk.
 
-The shim is host code that drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so (dfm::launch_pair_head, launch_pair_head_m,
-launch_pair_finish_s, launch_pair_finish, launch_pair_dist, launch_energy_pairs, launch_time_embed, launch_heads, launch_prep_pose) on
-host arrays, with sentinel guard bands around every device block.  This module compiles it, binds it with ctypes and holds
+The shim drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so (dfm::launch_pair_head, launch_pair_head_m,
+launch_pair_finish_s, launch_pair_finish, launch_pair_dist, launch_energy_pairs, launch_time_embed, launch_heads, launch_prep_pose)
+under the guard-band protocol of tests/kernel_harness.py.  This module binds it and holds
   * float64 numpy references of each operation, written from the model definition (egnn_net.py:329-358, :413-470; score_net_mlsb.py
     :162-172, :386-411; inference_base.py:342-352, :439-456), not from the kernels;
   * the error bounds of each kernel relative to those references (derivations: the docstring of tests/test_gpu_head_kernels.py);
@@ -11,15 +11,13 @@ host arrays, with sentinel guard bands around every device block.  This module c
   * the inputs of the GPU tests, so that the CPU tests can check conditions on them (threshold safety, the restatement under the bound).
 """
 import ctypes as C
-import os
-import shutil
-import subprocess
+import functools
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "dfmdock_amd")
-SHIM_SRC = os.path.join(ROOT, "tests", "kernels", "heads_harness.hip")
+import kernel_harness as kh
+from kernel_harness import HIP_SUCCESS, LIBDIR, ROOT, Out, guards_intact, is_sentinel      # noqa: F401 (re-exported)
+
 LAUNCHERS = ("_ZN3dfm16launch_pair_headERKNS_8PairArgsEP12ihipStream_t",
              "_ZN3dfm18launch_pair_head_mERKNS_8PairArgsEP12ihipStream_t",
              "_ZN3dfm20launch_pair_finish_sERKNS_8PairArgsEifPfS3_P12ihipStream_t",
@@ -33,7 +31,6 @@ H, HI = 256, 128
 U = 2.0 ** -24                    # unit roundoff of fp32
 LN_EPS = 1e-5
 SILU_S = np.float32(-1.44269504088896340736)
-HIP_SUCCESS = 0
 PM_RT, PM_LC = 32, 64             # k_pair_head_m: receptor x ligand residues of a workgroup
 
 SLOTS = ("P", "Q", "ca4", "w_d", "ln_w", "ln_b", "w3", "S", "fpart", "spart", "clash", "fvec", "conf", "dist",
@@ -49,86 +46,19 @@ STEP_FIELDS = ("g2_r", "g_r", "hg2_r", "g2_t", "g_t", "hg2_t", "dt", "sqrt_dt", 
 HEAD_W = ("t_W", "t_lin", "trs0", "trs_ln_w", "trs_ln_b", "trs4", "rots0", "rots_ln_w", "rots_ln_b", "rots4")
 
 
-class HhBuf(C.Structure):
-    _fields_ = [("host", C.c_void_p), ("bytes", C.c_longlong), ("out", C.c_int)]
-
-
-class HhCall(C.Structure):
-    _fields_ = ([("buf", HhBuf * len(SLOTS))] + [(n, C.c_longlong) for n in LONGS] + [("seed", C.c_ulonglong)]
+class Call(C.Structure):
+    _fields_ = ([("buf", kh.Buf * len(SLOTS))] + [(n, C.c_longlong) for n in LONGS] + [("seed", C.c_ulonglong)]
                 + [(n, C.c_float) for n in FLOATS] + [(n, C.c_int) for n in INTS])
 
 
-def hipcc():
-    return os.environ.get("HIPCC") or "/opt/rocm/bin/hipcc"
+compile_shim = functools.partial(kh.compile_shim, "heads")
 
 
-def compile_shim(outdir):
-    """hipcc --offload-arch=gfx950 -shared -fPIC, linked against the built library with an rpath.  Raises if the compiler is missing."""
-    cc = hipcc()
-    if not (os.path.isfile(cc) or shutil.which(cc)):
-        raise RuntimeError(f"hipcc not found ({cc}): the kernel harness cannot be built")
-    out = os.path.join(str(outdir), "libheads_harness.so")
-    subprocess.run([cc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", SHIM_SRC, "-o", out,
-                    "-L", LIBDIR, "-ldfmdock_amd", "-Wl,-rpath," + LIBDIR], check=True, capture_output=True, text=True)
-    return out
-
-
-class Out:
-    """An output buffer: dtype and element count; init = None (sentinel interior) or an array the interior starts as (in / out)."""
-    def __init__(self, dtype, n=None, init=None):
-        self.dtype = np.dtype(dtype)
-        self.init = None if init is None else np.ascontiguousarray(init, self.dtype)
-        self.n = int(n if init is None else self.init.size)
-
-
-class Harness:
+class Harness(kh.KernelHarness):
     def __init__(self, path):
-        self.path = path
-        self.lib = C.CDLL(path)
-        self.lib.hh_run.argtypes = [C.POINTER(HhCall), C.c_int]
-        self.lib.hh_run.restype = C.c_int
-        for f in ("hh_guard_bytes", "hh_call_bytes", "hh_step_params_bytes"):
-            getattr(self.lib, f).restype = C.c_longlong
-        self.guard = int(self.lib.hh_guard_bytes())
-        assert int(self.lib.hh_call_bytes()) == C.sizeof(HhCall), "HhCall: the ctypes layout differs from the shim's"
+        super().__init__(path, Call, SLOTS, OPS)
+        self.lib.hh_step_params_bytes.restype = C.c_longlong
         assert int(self.lib.hh_step_params_bytes()) == 48
-
-    def run(self, op, bufs, **scalars):
-        """bufs: slot -> array (input, uploaded as is) or Out.  Returns {slot: interior array, slot + '_guard': (before, after) bytes}."""
-        call = HhCall()
-        keep, host = [], {}
-        for k, v in scalars.items():
-            setattr(call, k, v if k in FLOATS else int(v))
-        for k, v in bufs.items():
-            if v is None:
-                continue
-            b = call.buf[SLOTS.index(k)]
-            if isinstance(v, Out):
-                nbytes = v.dtype.itemsize * v.n
-                raw = np.zeros(self.guard * 2 + nbytes, np.uint8)
-                if v.init is not None:
-                    raw[self.guard:self.guard + nbytes] = v.init.reshape(-1).view(np.uint8)
-                host[k] = (raw, v.dtype, nbytes)
-                b.host, b.bytes, b.out = raw.ctypes.data, nbytes, 1 if v.init is None else 2
-            else:
-                a = np.ascontiguousarray(v)
-                keep.append(a)
-                b.host, b.bytes, b.out = a.ctypes.data, a.nbytes, 0
-        res = {"err": self.lib.hh_run(C.byref(call), OPS.index(op))}
-        for k, (raw, dt, nbytes) in host.items():
-            res[k] = raw[self.guard:self.guard + nbytes].view(dt).copy()
-            res[k + "_guard"] = (raw[:self.guard], raw[self.guard + nbytes:])
-        return res
-
-
-def guards_intact(res, slot):
-    a, b = res[slot + "_guard"]
-    return bool((a == 0xff).all() and (b == 0xff).all())
-
-
-def is_sentinel(x):
-    """Elementwise: does a 4-byte element still hold the 0xff fill?"""
-    return np.ascontiguousarray(x).view(np.uint32) == 0xffffffff
 
 
 def step_params(entries):

@@ -1,20 +1,16 @@
-// dense_harness.hip - test-only host shim around the node-model launchers of libdfmdock_amd.so (tests/dense_harness.py builds it).
+// dense_harness.hip - test-only host shim around the node-model launchers of libdfmdock_amd.so (tests/dense_harness.py builds it):
+// dfm::launch_gemm_split, launch_gemm_f32 and launch_gn_stats.
 //
-// Host code only: no kernels here.  Every entry point takes host arrays, uploads each into a device block with GUARD bytes of
-// sentinel (0xff: a NaN as fp32 and as fp16) before and after it, fills a dfm::GemmArgs, calls the SHIPPED launcher on a stream of its
-// own, synchronises and copies the outputs back WITH their guard bands.  The interior of every output block starts as the sentinel too,
-// so an element the kernel should have written and did not is visible as well.  Each entry point returns the hipError_t.
+// Host code only: no kernels here.  The guard-band protocol is harness_common.h's; this file fills a dfm::GemmArgs from the call record.
+// Every output is out = 1: its interior starts as the sentinel.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <vector>
 
 #include "../../dfmdock_amd/csrc/dfm_internal.h"
+#include "harness_common.h"
 
 namespace {
-
-constexpr size_t GUARD = 4096;      // bytes of sentinel on each side of a block
-constexpr unsigned char SENTINEL = 0xff;
 
 // buffer slots of one call (the GemmArgs pointer each one becomes)
 enum Slot {
@@ -22,27 +18,21 @@ enum Slot {
     S_C, S_C2, S_C2B, S_CB, S_STAT, S_ZBUF, N_SLOTS
 };
 
+enum Op { OP_SPLIT, OP_F32, OP_GN_STATS };
+
 }  // namespace
 
 extern "C" {
 
-// One host buffer.  Inputs: `bytes` bytes at host.  Outputs (out != 0): host holds GUARD + bytes + GUARD bytes and receives the whole
-// device block, guards included.  host == nullptr: the slot is unused (nullptr in GemmArgs).
-struct DhBuf {
-    void *host;
-    long long bytes;
-    int out;
-};
-
-struct DhCall {
-    DhBuf buf[N_SLOTS];
+struct Call {
+    harness::HarnessBuf buf[N_SLOTS];
     int M, K, Nout, lda, ldw, ldc, pro, epi, rows_per_graph, a0_period, r_period;
     int a0_offset;      // bytes added to the A0 device pointer (4: an unaligned launch of launch_gemm_f32)
     int gn_B, gn_N;     // launch_gn_stats: trajectories, rows per trajectory (u = A0, mean_scale = GN_MS, fold = GN_W / GN_B,
                         // shift -> C, den -> C2)
 };
 
-long long dh_guard_bytes() { return (long long)GUARD; }
+HARNESS_EXPORTS(Call)
 
 int dh_device_cus(int *cus)
 {
@@ -79,28 +69,19 @@ int dh_validate_split(int M, int K, int Nout, int lda, int ldc, int pro, int epi
     return (int)r;
 }
 
-static int run(const DhCall *c, int op)
+int kh_run(const Call *c, int op)
 {
-    void *dev[N_SLOTS] = {};
-    hipError_t e = hipSuccess;
+    harness::Blocks<N_SLOTS> blk(c->buf);
+    auto P = [&](int i) { return blk.ptr(i); };
     hipStream_t s = nullptr;
-    dfm::GemmArgs a;
-    std::memset(&a, 0, sizeof(a));
-    for (int i = 0; i < N_SLOTS && e == hipSuccess; ++i) {
-        const DhBuf &b = c->buf[i];
-        if (!b.host) continue;
-        const size_t total = GUARD + (size_t)b.bytes + GUARD;
-        if ((e = hipMalloc(&dev[i], total)) != hipSuccess) break;
-        if ((e = hipMemset(dev[i], SENTINEL, total)) != hipSuccess) break;
-        if (!b.out) e = hipMemcpy((char *)dev[i] + GUARD, b.host, (size_t)b.bytes, hipMemcpyHostToDevice);
-    }
-    auto P = [&](int i) -> void * { return dev[i] ? (char *)dev[i] + GUARD : nullptr; };
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    hipError_t e = blk.begin(&s);
     if (e == hipSuccess) {
-        if (op == 2) {
+        if (op == OP_GN_STATS) {
             e = dfm::launch_gn_stats((const float *)P(S_A0), c->gn_B, c->gn_N, (const float *)P(S_GN_MS), (float *)P(S_C),
                                      (float *)P(S_C2), (const float *)P(S_GN_W), (const float *)P(S_GN_B), s);
-        } else {
+        } else if (op == OP_SPLIT || op == OP_F32) {
+            dfm::GemmArgs a;
+            std::memset(&a, 0, sizeof(a));
             a.A0 = (const float *)((char *)P(S_A0) + c->a0_offset);
             a.A1 = (const float *)P(S_A1);
             a.lda = c->lda; a.K = c->K; a.W = (const float *)P(S_W); a.ldw = c->ldw; a.bias = (const float *)P(S_BIAS);
@@ -111,25 +92,13 @@ static int run(const DhCall *c, int op)
             a.C2b = (uint16_t *)P(S_C2B); a.Cb = (uint16_t *)P(S_CB); a.stat_part = (float *)P(S_STAT);
             a.gn_part = (const float *)P(S_GN_PART); a.gn_ms = (const float *)P(S_GN_MS); a.zbuf = (float *)P(S_ZBUF);
             a.a0_period = c->a0_period; a.r_period = c->r_period;
-            e = op == 0 ? dfm::launch_gemm_split(a, (const uint16_t *)P(S_WHI), (const uint16_t *)P(S_WLO), s)
-                        : dfm::launch_gemm_f32(a, s);
+            e = op == OP_SPLIT ? dfm::launch_gemm_split(a, (const uint16_t *)P(S_WHI), (const uint16_t *)P(S_WLO), s)
+                               : dfm::launch_gemm_f32(a, s);
+        } else {
+            e = hipErrorInvalidValue;
         }
     }
-    if (s) {
-        const hipError_t e2 = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = e2;
-        (void)hipStreamDestroy(s);
-    }
-    for (int i = 0; i < N_SLOTS && e == hipSuccess; ++i)
-        if (dev[i] && c->buf[i].out)
-            e = hipMemcpy(c->buf[i].host, dev[i], GUARD + (size_t)c->buf[i].bytes + GUARD, hipMemcpyDeviceToHost);
-    for (int i = 0; i < N_SLOTS; ++i)
-        if (dev[i]) (void)hipFree(dev[i]);
-    return (int)e;
+    return (int)blk.finish(e);
 }
-
-int dh_gemm_split(const DhCall *c) { return run(c, 0); }
-int dh_gemm_f32(const DhCall *c) { return run(c, 1); }
-int dh_gn_stats(const DhCall *c) { return run(c, 2); }
 
 }  // extern "C"

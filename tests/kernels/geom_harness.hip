@@ -3,22 +3,16 @@
 // launch_clash_force (tests/geom_harness.py builds it).
 //
 // Host code, plus ONE test-only kernel (k_hw_log2: the hardware log2 the sampling race uses, evaluated on a given array, so that its
-// error is measured on the instruction itself and not on the kernel under test).  Every entry point takes host arrays, uploads each into
-// a device block with GUARD bytes of sentinel (0xff) before and after it, calls the SHIPPED launcher on a stream of its own,
-// synchronises and copies the outputs back WITH their guard bands.  An output block's interior starts as the sentinel (out = 1) or as
-// the caller's contents (out = 2: the pose and the accumulated update k_clash_force changes in place, the row counter).
+// error is measured on the instruction itself and not on the kernel under test).  The guard-band protocol is harness_common.h's.  The
+// in / out blocks (out = 2) are the pose and the accumulated update k_clash_force changes in place, and the row counter.
 // The host versions of philox4x32, u01 and pack_code (they are __host__ __device__) are exported for the CPU tests.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-
 #include "../../dfmdock_amd/csrc/dfm_device.h"
 #include "../../dfmdock_amd/csrc/dfm_internal.h"
+#include "harness_common.h"
 
 namespace {
-
-constexpr size_t GUARD = 4096;      // bytes of sentinel on each side of a block
-constexpr unsigned char SENTINEL = 0xff;
 
 // buffer slots of one call (tests/geom_harness.py SLOTS lists the same names in the same order)
 enum Slot {
@@ -38,14 +32,8 @@ __global__ __launch_bounds__(256) void k_hw_log2(const float *__restrict__ x, fl
 
 extern "C" {
 
-struct GhBuf {
-    void *host;
-    long long bytes;
-    int out;
-};
-
-struct GhCall {
-    GhBuf buf[N_SLOTS];
+struct Call {
+    harness::HarnessBuf buf[N_SLOTS];
     long long n;
     unsigned long long seed;
     float mask_dist;
@@ -53,8 +41,7 @@ struct GhCall {
     int B, N, R, L, K, knn, nsamp, all_atoms;
 };
 
-long long gh_guard_bytes() { return (long long)GUARD; }
-long long gh_call_bytes() { return (long long)sizeof(GhCall); }
+HARNESS_EXPORTS(Call)
 
 // ---- host versions of the device helpers ----------------------------------------------------------------------------------------
 // n Philox blocks: counter words c[4 n], key (k0, k1) -> out[4 n]
@@ -111,27 +98,15 @@ int gh_find_top_uniform(unsigned n0, unsigned n1, unsigned c1_mul, unsigned n2, 
 }
 
 // ---- one launch -----------------------------------------------------------------------------------------------------------------
-int gh_run(const GhCall *c, int op)
+int kh_run(const Call *c, int op)
 {
-    void *dev[N_SLOTS] = {};
-    hipError_t e = hipSuccess;
-    hipStream_t s = nullptr;
-    for (int i = 0; i < N_SLOTS && e == hipSuccess; ++i) {
-        const GhBuf &b = c->buf[i];
-        if (!b.host) continue;
-        const size_t total = GUARD + (size_t)b.bytes + GUARD;
-        if ((e = hipMalloc(&dev[i], total)) != hipSuccess) break;
-        if ((e = hipMemset(dev[i], SENTINEL, total)) != hipSuccess) break;
-        if (b.out == 0) e = hipMemcpy((char *)dev[i] + GUARD, b.host, (size_t)b.bytes, hipMemcpyHostToDevice);
-        else if (b.out == 2) e = hipMemcpy((char *)dev[i] + GUARD, (const char *)b.host + GUARD, (size_t)b.bytes, hipMemcpyHostToDevice);
-    }
-    auto P = [&](int i) -> void * { return dev[i] ? (char *)dev[i] + GUARD : nullptr; };
+    harness::Blocks<N_SLOTS> blk(c->buf);
+    auto P = [&](int i) { return blk.ptr(i); };
     auto F = [&](int i) -> float * { return (float *)P(i); };
     auto F4 = [&](int i) -> const float4 * { return (const float4 *)P(i); };
 
-    // the fills and uploads above went through the null stream, which a non-blocking stream does not wait for
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    hipStream_t s = nullptr;
+    hipError_t e = blk.begin(&s);
     if (e == hipSuccess) {
         switch (op) {
         case OP_KNN_SAMPLE:
@@ -161,21 +136,7 @@ int gh_run(const GhCall *c, int op)
         default: e = hipErrorInvalidValue;
         }
     }
-    // a launcher that refuses its arguments starts nothing: the blocks are still copied back, so that a test can see them untouched
-    const hipError_t refused = s && e == hipErrorInvalidValue ? e : hipSuccess;
-    if (refused != hipSuccess) e = hipSuccess;
-    if (s) {
-        const hipError_t e2 = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = e2;
-        (void)hipStreamDestroy(s);
-    }
-    for (int i = 0; i < N_SLOTS && e == hipSuccess; ++i)
-        if (dev[i] && c->buf[i].out)
-            e = hipMemcpy(c->buf[i].host, dev[i], GUARD + (size_t)c->buf[i].bytes + GUARD, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = refused;
-    for (int i = 0; i < N_SLOTS; ++i)
-        if (dev[i]) (void)hipFree(dev[i]);
-    return (int)e;
+    return (int)blk.finish(e);
 }
 
 }  // extern "C"

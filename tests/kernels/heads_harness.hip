@@ -1,21 +1,17 @@
 // heads_harness.hip - test-only host shim around the pair-head and score-head launchers of libdfmdock_amd.so (tests/heads_harness.py
 // builds it).
 //
-// Host code only: no kernels here.  Every entry point takes host arrays, uploads each into a device block with GUARD bytes of
-// sentinel (0xff: a NaN as fp32, -1 as int32) before and after it, fills a host dfm::PairArgs / dfm::HeadsDev / dfm::HeadArgs whose
-// pointers are those blocks, calls the SHIPPED launcher on a stream of its own, synchronises and copies the outputs back WITH their
-// guard bands.  An output block's interior starts as the sentinel (out = 1) or as the caller's own contents (out = 2: the pose and
-// the accumulated updates k_heads changes in place).  Each entry point returns the hipError_t.
+// Host code only: no kernels here.  The guard-band protocol is harness_common.h's; this file fills a host dfm::PairArgs / dfm::HeadsDev
+// / dfm::HeadArgs whose pointers are the blocks.  The in / out blocks (out = 2) are the pose and the accumulated updates k_heads
+// changes in place.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include "../../dfmdock_amd/csrc/dfm_internal.h"
+#include "harness_common.h"
 
 namespace {
-
-constexpr size_t GUARD = 4096;      // bytes of sentinel on each side of a block
-constexpr unsigned char SENTINEL = 0xff;
 
 // buffer slots of one call (tests/heads_harness.py SLOTS lists the same names in the same order)
 enum Slot {
@@ -32,16 +28,8 @@ enum Op { OP_PAIR_HEAD, OP_PAIR_HEAD_M, OP_PAIR_FINISH_S, OP_PAIR_FINISH, OP_PAI
 
 extern "C" {
 
-// One host buffer.  out 0: input, `bytes` bytes at host.  out 1 / 2: host holds GUARD + bytes + GUARD bytes and receives the whole
-// device block, guards included; out 2 also uploads the interior host[GUARD .. GUARD + bytes) first.  host == nullptr: unused (nullptr).
-struct HhBuf {
-    void *host;
-    long long bytes;
-    int out;
-};
-
-struct HhCall {
-    HhBuf buf[N_SLOTS];
+struct Call {
+    harness::HarnessBuf buf[N_SLOTS];
     long long hid_bstride, z_bstride, trace_bstride, trace_s_bstride;
     unsigned long long seed;
     float cut_off, inv_pool, pool_div;
@@ -49,25 +37,13 @@ struct HhCall {
     int B, R, L, Rp, mode, n_part, want_energy, en_mode, do_update, ode, all_atoms, prep_next, step, n_times;
 };
 
-long long hh_guard_bytes() { return (long long)GUARD; }
-long long hh_call_bytes() { return (long long)sizeof(HhCall); }
+HARNESS_EXPORTS(Call)
 long long hh_step_params_bytes() { return (long long)sizeof(dfm::StepParams); }
 
-int hh_run(const HhCall *c, int op)
+int kh_run(const Call *c, int op)
 {
-    void *dev[N_SLOTS] = {};
-    hipError_t e = hipSuccess;
-    hipStream_t s = nullptr;
-    for (int i = 0; i < N_SLOTS && e == hipSuccess; ++i) {
-        const HhBuf &b = c->buf[i];
-        if (!b.host) continue;
-        const size_t total = GUARD + (size_t)b.bytes + GUARD;
-        if ((e = hipMalloc(&dev[i], total)) != hipSuccess) break;
-        if ((e = hipMemset(dev[i], SENTINEL, total)) != hipSuccess) break;
-        if (b.out == 0) e = hipMemcpy((char *)dev[i] + GUARD, b.host, (size_t)b.bytes, hipMemcpyHostToDevice);
-        else if (b.out == 2) e = hipMemcpy((char *)dev[i] + GUARD, (const char *)b.host + GUARD, (size_t)b.bytes, hipMemcpyHostToDevice);
-    }
-    auto P = [&](int i) -> void * { return dev[i] ? (char *)dev[i] + GUARD : nullptr; };
+    harness::Blocks<N_SLOTS> blk(c->buf);
+    auto P = [&](int i) { return blk.ptr(i); };
     auto F = [&](int i) -> float * { return (float *)P(i); };
 
     dfm::PairArgs pa;
@@ -99,9 +75,8 @@ int hh_run(const HhCall *c, int op)
     ha.prep_next = c->prep_next; ha.rec_pos = F(S_REC_POS);
     ha.prep_pos = (float4 *)P(S_PREP_POS); ha.prep_ca4 = (float4 *)P(S_PREP_CA4); ha.prep_cb4 = (float4 *)P(S_PREP_CB4);
 
-    // the fills and uploads above went through the null stream, which a non-blocking stream does not wait for
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    hipStream_t s = nullptr;
+    hipError_t e = blk.begin(&s);
     if (e == hipSuccess) {
         switch (op) {
         case OP_PAIR_HEAD: e = dfm::launch_pair_head(pa, s); break;
@@ -124,17 +99,7 @@ int hh_run(const HhCall *c, int op)
         default: e = hipErrorInvalidValue;
         }
     }
-    if (s) {
-        const hipError_t e2 = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = e2;
-        (void)hipStreamDestroy(s);
-    }
-    for (int i = 0; i < N_SLOTS && e == hipSuccess; ++i)
-        if (dev[i] && c->buf[i].out)
-            e = hipMemcpy(c->buf[i].host, dev[i], GUARD + (size_t)c->buf[i].bytes + GUARD, hipMemcpyDeviceToHost);
-    for (int i = 0; i < N_SLOTS; ++i)
-        if (dev[i]) (void)hipFree(dev[i]);
-    return (int)e;
+    return (int)blk.finish(e);
 }
 
 }  // extern "C"

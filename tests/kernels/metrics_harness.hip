@@ -1,21 +1,18 @@
 // metrics_harness.hip - test-only host shim around the docking-metrics launchers of libdfmdock_amd.so (tests/metrics_harness.py builds
 // it): dfm::launch_native_pairs, launch_metrics_reduce, launch_metrics_finish.
 //
-// Host code only: no kernels here.  Every entry point takes host arrays, checks that each is large enough for the launch it feeds (a
-// short one is hipErrorInvalidValue and nothing is launched), uploads each into a device block with GUARD bytes of sentinel (0xff) before
-// and after it, fills dfm::MetricsChain / dfm::MetricsConst from the call record, calls the SHIPPED launcher on a stream of its own,
-// synchronises and copies the outputs back WITH their guard bands.  An output block's interior starts as the sentinel.
+// Host code only: no kernels here.  The guard-band protocol is harness_common.h's.  BEFORE anything is uploaded this file checks that
+// every array is large enough for the launch it feeds and that the contact indices are in range (a failure is hipErrorInvalidValue
+// and no device is touched); then it fills dfm::MetricsChain / dfm::MetricsConst from the call record.  Every output is out = 1.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
 
 #include "../../dfmdock_amd/csrc/dfm_internal.h"
+#include "harness_common.h"
 
 namespace {
-
-constexpr size_t GUARD = 4096;      // bytes of sentinel on each side of a block
-constexpr unsigned char SENTINEL = 0xff;
 
 // buffer slots of one call (tests/metrics_harness.py SLOTS lists the same names in the same order)
 enum Slot {
@@ -29,26 +26,17 @@ enum Op { OP_NATIVE_PAIRS, OP_REDUCE, OP_FINISH, OP_FULL };
 
 extern "C" {
 
-// One host buffer.  out 0: input, `bytes` bytes at host.  out 1: host holds GUARD + bytes + GUARD bytes and receives the whole device
-// block, guards included.  host == nullptr: unused.
-struct MhBuf {
-    void *host;
-    long long bytes;
-    int out;
-};
-
-struct MhCall {
-    MhBuf buf[N_SLOTS];
+struct Call {
+    harness::HarnessBuf buf[N_SLOTS];
     double iface_cutoff, contact_cutoff;
     double T_rec[3], T_lig[3], T_rec_iface[3], T_lig_iface[3], o[3];
     // R, L: the chain lengths of the arrays; n_*: the counts k_metrics_solve / k_metrics_resid divide by (the test may set them apart)
     int P, R, L, chains, n_rec, n_lig, n_rec_iface, n_lig_iface, n_contacts, rec_moves;
 };
 
-long long mh_guard_bytes() { return (long long)GUARD; }
-long long mh_call_bytes() { return (long long)sizeof(MhCall); }
+HARNESS_EXPORTS(Call)
 
-int mh_run(const MhCall *c, int op)
+int kh_run(const Call *c, int op)
 {
     const long long P = c->P, R = c->R, L = c->L, ch = c->chains;
     auto has = [&](int i, long long bytes) { return c->buf[i].host && c->buf[i].bytes >= bytes; };
@@ -75,18 +63,8 @@ int mh_run(const MhCall *c, int op)
     }
     if (!ok) return (int)hipErrorInvalidValue;
 
-    void *dev[N_SLOTS] = {};
-    hipError_t e = hipSuccess;
-    hipStream_t s = nullptr;
-    for (int i = 0; i < N_SLOTS && e == hipSuccess; ++i) {
-        const MhBuf &b = c->buf[i];
-        if (!b.host) continue;
-        const size_t total = GUARD + (size_t)b.bytes + GUARD;
-        if ((e = hipMalloc(&dev[i], total)) != hipSuccess) break;
-        if ((e = hipMemset(dev[i], SENTINEL, total)) != hipSuccess) break;
-        if (b.out == 0 && b.bytes > 0) e = hipMemcpy((char *)dev[i] + GUARD, b.host, (size_t)b.bytes, hipMemcpyHostToDevice);
-    }
-    auto D = [&](int i) -> void * { return dev[i] ? (char *)dev[i] + GUARD : nullptr; };
+    harness::Blocks<N_SLOTS> blk(c->buf);
+    auto D = [&](int i) { return blk.ptr(i); };
 
     const dfm::MetricsChain lig = {(const float *)D(S_LIG_MODEL), (const float *)D(S_LIG_NAT), (const uint8_t *)D(S_FLIG), c->L};
     const dfm::MetricsChain rec = {(const float *)D(S_REC_MODEL), (const float *)D(S_REC_NAT), (const uint8_t *)D(S_FREC), c->R};
@@ -99,26 +77,15 @@ int mh_run(const MhCall *c, int op)
         mc.o[k] = c->o[k];
     }
 
-    // the fills and uploads above went through the null stream, which a non-blocking stream does not wait for
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    hipStream_t s = nullptr;
+    hipError_t e = blk.begin(&s);
     if (e == hipSuccess && op == OP_NATIVE_PAIRS)
         e = dfm::launch_native_pairs(rec.native, lig.native, c->R, c->L, c->iface_cutoff, c->contact_cutoff, (uint8_t *)D(S_PAIRS), s);
     if (e == hipSuccess && (op == OP_REDUCE || op == OP_FULL)) e = dfm::launch_metrics_reduce(lig, rec, c->chains, c->P, mc, (double *)D(S_SUMS), s);
     if (e == hipSuccess && (op == OP_FINISH || op == OP_FULL))
         e = dfm::launch_metrics_finish(lig, rec, (const double *)D(S_SUMS), c->chains, (const double *)D(S_REC_CONST), mc,
                                        (const int32_t *)D(S_CONTACTS), c->P, (double *)D(S_XF), (double *)D(S_RMSD), (int32_t *)D(S_RECOVERED), s);
-    if (s) {
-        const hipError_t e2 = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = e2;
-        (void)hipStreamDestroy(s);
-    }
-    for (int i = 0; i < N_SLOTS && e == hipSuccess; ++i)
-        if (dev[i] && c->buf[i].out)
-            e = hipMemcpy(c->buf[i].host, dev[i], GUARD + (size_t)c->buf[i].bytes + GUARD, hipMemcpyDeviceToHost);
-    for (int i = 0; i < N_SLOTS; ++i)
-        if (dev[i]) (void)hipFree(dev[i]);
-    return (int)e;
+    return (int)blk.finish(e);
 }
 
 }  // extern "C"

@@ -6,25 +6,22 @@
 // uploaded it checks everything a kernel would follow as an index - every array long enough for the launch it feeds, cell_start of
 // nx ny nz + 1 entries, monotone, from 0 to Ar, lig_index a permutation, residue bits below Rr / Lr, W = ceil(Rr / 32), types below
 // T, slab offsets type * T * NB, NB in 1 .. 64 with its `top`, e2 of 128 slots that end in +inf - and answers
-// hipErrorInvalidValue without a launch when one fails: no call makes a kernel read outside its blocks.  Then every buffer is uploaded
-// into a device block of its own with GUARD bytes of sentinel (0xff) before and after it, the shipped structs (WalkGrid, StericsConst /
-// StericsAtoms, IfaceConst / IfaceAtoms, PairpotConst / PairpotAtoms, ResconConst / ResconAtoms, HbondAtoms) are filled from the record,
-// the SHIPPED launcher runs on a stream of its own, and the outputs are copied back WITH their guard bands.  The interior of an output block starts as the sentinel (out 1) or as what
-// the caller put there (out 2): zero where the contract says "zero it first", a base where it says "added to", a marker where it says
-// "written by the waves that reach the cell walk only".  A per-atom output the caller leaves out is passed as nullptr.
+// hipErrorInvalidValue without a launch when one fails: no call makes a kernel read outside its blocks.  Then the guard-band protocol of
+// harness_common.h runs, with the shipped structs (WalkGrid, StericsConst / StericsAtoms, IfaceConst / IfaceAtoms, PairpotConst /
+// PairpotAtoms, ResconConst / ResconAtoms, HbondAtoms, SurfaceAtoms) filled from the record.  A per-atom output the caller leaves out is
+// passed as nullptr.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 #include <vector>
 
 #include "../../dfmdock_amd/csrc/dfm_internal.h"
+#include "harness_common.h"
 
 namespace {
 
-constexpr size_t GUARD = 4096;      // bytes of sentinel on each side of a block
-constexpr unsigned char SENTINEL = 0xff;
+using harness::GUARD;
 
 // buffer slots of one call (tests/pose_harness.py SLOTS lists the same names in the same order)
 enum Slot {
@@ -45,17 +42,8 @@ enum Op {
 
 extern "C" {
 
-// One host buffer.  out 0: input, `bytes` bytes at host.  out 1 / 2: host holds GUARD + bytes + GUARD bytes and receives the whole device
-// block, guards included; 2: the interior starts as the host's interior, 1: as the sentinel.  host == nullptr: unused (nullptr to the
-// launcher where the contract allows it).
-struct PhBuf {
-    void *host;
-    long long bytes;
-    int out;
-};
-
-struct PhCall {
-    PhBuf buf[N_SLOTS];
+struct Call {
+    harness::HarnessBuf buf[N_SLOTS];
     double lo[3], hi[3], center[3], edge, grow, clash, contact;
     double cut2, soft, min2, kc, lo2;      // IfaceConst; PairpotConst (cut2 is shared)
     double hb2, salt2, c2;                 // HbondConst
@@ -66,11 +54,10 @@ struct PhCall {
     int nx, ny, nz, n, Ar, Al, Rr, Lr, W, Lc, Wc, NT, NB, top, Rc, G;
 };
 
-long long ph_guard_bytes() { return (long long)GUARD; }
-long long ph_call_bytes() { return (long long)sizeof(PhCall); }
+HARNESS_EXPORTS(Call)
 
-// the checks alone (what ph_run does first): hipSuccess or hipErrorInvalidValue.  Touches no device.
-int ph_check(const PhCall *c, int op)
+// the checks alone (what kh_run does first): hipSuccess or hipErrorInvalidValue.  Touches no device.
+int ph_check(const Call *c, int op)
 {
     const long long n = c->n < 0 ? 0 : c->n, Ar = c->Ar, Al = c->Al;
     auto has = [&](int i, long long bytes) { return c->buf[i].host && c->buf[i].bytes >= bytes; };
@@ -216,23 +203,12 @@ int ph_check(const PhCall *c, int op)
     return ok ? (int)hipSuccess : (int)hipErrorInvalidValue;
 }
 
-int ph_run(const PhCall *c, int op)
+int kh_run(const Call *c, int op)
 {
     if (ph_check(c, op) != (int)hipSuccess) return (int)hipErrorInvalidValue;
 
-    void *dev[N_SLOTS] = {};
-    hipError_t e = hipSuccess;
-    hipStream_t s = nullptr;
-    for (int i = 0; i < N_SLOTS && e == hipSuccess; ++i) {
-        const PhBuf &b = c->buf[i];
-        if (!b.host) continue;
-        const size_t total = GUARD + (size_t)b.bytes + GUARD;
-        if ((e = hipMalloc(&dev[i], total)) != hipSuccess) break;
-        if ((e = hipMemset(dev[i], SENTINEL, total)) != hipSuccess) break;
-        if (b.out != 1 && b.bytes > 0)
-            e = hipMemcpy((char *)dev[i] + GUARD, (const char *)b.host + (b.out ? GUARD : 0), (size_t)b.bytes, hipMemcpyHostToDevice);
-    }
-    auto D = [&](int i) -> void * { return dev[i] ? (char *)dev[i] + GUARD : nullptr; };
+    harness::Blocks<N_SLOTS> blk(c->buf);
+    auto D = [&](int i) { return blk.ptr(i); };
 
     dfm::WalkGrid g = {};
     for (int k = 0; k < 3; ++k) { g.lo[k] = c->lo[k]; g.hi[k] = c->hi[k]; g.center[k] = c->center[k]; }
@@ -276,9 +252,8 @@ int ph_run(const PhCall *c, int op)
     int32_t *n_clash = (int32_t *)D(S_N_CLASH), *n_contact = (int32_t *)D(S_N_CONTACT);
     uint64_t *min_bits = (uint64_t *)D(S_MIN_BITS);
 
-    // the fills and uploads above went through the null stream, which a non-blocking stream does not wait for
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    hipStream_t s = nullptr;
+    hipError_t e = blk.begin(&s);
     if (e == hipSuccess) switch (op) {
         case OP_POSE_STERICS: e = dfm::launch_sterics_pose(rot, tr, c->n, T, n_clash, n_contact, min_bits, s); break;
         case OP_POSE_SURFACE: e = dfm::launch_surface_pose(rot, tr, c->n, T, (int32_t *)D(S_TOT), s); break;
@@ -317,20 +292,7 @@ int ph_run(const PhCall *c, int op)
             break;
         default: e = hipErrorInvalidValue;
     }
-    if (s) {
-        const hipError_t e2 = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = e2;
-        (void)hipStreamDestroy(s);
-    }
-    // a launcher's refusal still returns the blocks: they must be the prefill
-    const bool refused = e == hipErrorInvalidValue;
-    hipError_t ec = hipSuccess;
-    for (int i = 0; i < N_SLOTS && ec == hipSuccess && (e == hipSuccess || refused); ++i)
-        if (dev[i] && c->buf[i].out)
-            ec = hipMemcpy(c->buf[i].host, dev[i], GUARD + (size_t)c->buf[i].bytes + GUARD, hipMemcpyDeviceToHost);
-    for (int i = 0; i < N_SLOTS; ++i)
-        if (dev[i]) (void)hipFree(dev[i]);
-    return (int)(e != hipSuccess ? e : ec);
+    return (int)blk.finish(e);      // (a launcher's refusal still returns the blocks: they must be the prefill)
 }
 
 }  // extern "C"

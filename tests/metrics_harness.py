@@ -2,8 +2,8 @@
 k_metrics_solve and k_metrics_resid of kernels_metrics.hip, launch by launch.
 
 The shim drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so (dfm::launch_native_pairs, launch_metrics_reduce,
-launch_metrics_finish) on host arrays, with sentinel guard bands around every device block.  This module compiles it, binds it with
-ctypes and holds
+launch_metrics_finish) under the guard-band protocol of tests/kernel_harness.py, after checking that every array is large enough for
+the launch it feeds.  This module binds it and holds
   * the float64 references, written from dfmdock_amd/metrics.py (SVD Kabsch with the reflection fix: find_rigid_alignment; the contact
     distance: _min_dist / _min_dist_pairs), not from the kernels, and the exactly rounded sums (math.fsum) the reduction is held to;
   * an extended-precision evaluation of the same definition (np.longdouble sums and residuals, the 3 x 3 SVD in mpmath at 50 digits),
@@ -27,23 +27,16 @@ Gates.
 import ctypes as C
 import functools
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 
-from heads_harness import Out, guards_intact      # noqa: F401 (re-exported)
+import kernel_harness as kh
+from kernel_harness import HIP_INVALID_VALUE, HIP_SUCCESS, LIBDIR, ROOT, Out, guards_intact      # noqa: F401 (re-exported)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "dfmdock_amd")
-SHIM_SRC = os.path.join(ROOT, "tests", "kernels", "metrics_harness.hip")
 LAUNCHERS = ("_ZN3dfm19launch_native_pairsEPKfS1_iiddPhP12ihipStream_t",
              "_ZN3dfm21launch_metrics_reduceERKNS_12MetricsChainES2_iiRKNS_12MetricsConstEPdP12ihipStream_t",
              "_ZN3dfm21launch_metrics_finishERKNS_12MetricsChainES2_PKdiS4_RKNS_12MetricsConstEPKiiPdSA_PiP12ihipStream_t")
-HIP_SUCCESS = 0
-HIP_INVALID_VALUE = 1
-U64 = 2.0 ** -53                  # unit roundoff of fp64
+U64 = 2.0 ** -53                 # unit roundoff of fp64
 BORDER = 1e-3                     # A: a contact decision this close to its cutoff may go either way (generic coordinates only)
 BORDER_CAP = 0.005                # at most this share of a generator's decisions may be that close
 RMSD_ABS, RMSD_REL = 1e-9, 1e-9
@@ -62,28 +55,12 @@ def f64(x):
     return np.asarray(x, np.float64)
 
 
-class MhBuf(C.Structure):
-    _fields_ = [("host", C.c_void_p), ("bytes", C.c_longlong), ("out", C.c_int)]
-
-
-class MhCall(C.Structure):
-    _fields_ = ([("buf", MhBuf * len(SLOTS)), ("iface_cutoff", C.c_double), ("contact_cutoff", C.c_double)] +
+class Call(C.Structure):
+    _fields_ = ([("buf", kh.Buf * len(SLOTS)), ("iface_cutoff", C.c_double), ("contact_cutoff", C.c_double)] +
                 [(n, C.c_double * 3) for n in VECS] + [(n, C.c_int) for n in INTS])
 
 
-def hipcc():
-    return os.environ.get("HIPCC") or "/opt/rocm/bin/hipcc"
-
-
-def compile_shim(outdir):
-    """hipcc --offload-arch=gfx950 -shared -fPIC, linked against the built library with an rpath.  Raises if the compiler is missing."""
-    cc = hipcc()
-    if not (os.path.isfile(cc) or shutil.which(cc)):
-        raise RuntimeError(f"hipcc not found ({cc}): the kernel harness cannot be built")
-    out = os.path.join(str(outdir), "libmetrics_harness.so")
-    subprocess.run([cc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", SHIM_SRC, "-o", out,
-                    "-L", LIBDIR, "-ldfmdock_amd", "-Wl,-rpath," + LIBDIR], check=True, capture_output=True, text=True)
-    return out
+compile_shim = functools.partial(kh.compile_shim, "metrics")
 
 
 # ---- cases -------------------------------------------------------------------------------------------------------------------------
@@ -128,54 +105,11 @@ def consts(case):
 
 
 # ---- binding -----------------------------------------------------------------------------------------------------------------------
-class Harness:
-    def __init__(self, path):
-        self.path = path
-        self.lib = L = C.CDLL(path)
-        L.mh_run.argtypes = [C.POINTER(MhCall), C.c_int]
-        L.mh_run.restype = C.c_int
-        for f in ("mh_guard_bytes", "mh_call_bytes"):
-            getattr(L, f).restype = C.c_longlong
-        self.guard = int(L.mh_guard_bytes())
-        assert int(L.mh_call_bytes()) == C.sizeof(MhCall), "MhCall: the ctypes layout differs from the shim's"
+class Harness(kh.KernelHarness):
+    check = True      # run() asserts success unless told check=False
 
-    def run(self, op, bufs, check=True, **scalars):
-        """bufs: slot -> array (input, uploaded as is) or Out.  Returns {slot: interior array, slot + '_guard': (before, after) bytes}.
-        check: the launch succeeded and no byte outside an output block changed."""
-        call = MhCall()
-        keep, host = [], {}
-        for k, v in scalars.items():
-            if k in VECS:
-                setattr(call, k, (C.c_double * 3)(*[float(x) for x in v]))
-            else:
-                setattr(call, k, int(v) if k in INTS else float(v))
-        for k, v in bufs.items():
-            if v is None:
-                continue
-            b = call.buf[SLOTS.index(k)]
-            if isinstance(v, Out):
-                nbytes = v.dtype.itemsize * v.n
-                raw = np.zeros(self.guard * 2 + nbytes, np.uint8)
-                host[k] = (raw, v.dtype, nbytes)
-                b.host, b.bytes, b.out = raw.ctypes.data, nbytes, 1
-            else:
-                a = np.ascontiguousarray(v)
-                if a.size == 0:      # an empty list still needs an address
-                    a = np.zeros(1, a.dtype)
-                    keep.append(a)
-                    b.host, b.bytes, b.out = a.ctypes.data, 0, 0
-                    continue
-                keep.append(a)
-                b.host, b.bytes, b.out = a.ctypes.data, a.nbytes, 0
-        res = {"err": self.lib.mh_run(C.byref(call), OPS.index(op))}
-        for k, (raw, dt, nbytes) in host.items():
-            res[k] = raw[self.guard:self.guard + nbytes].view(dt).copy()
-            res[k + "_guard"] = (raw[:self.guard], raw[self.guard + nbytes:])
-        if check:
-            assert res["err"] == HIP_SUCCESS, f"{op}: hipError {res['err']}"
-            for k in host:
-                assert guards_intact(res, k), f"{op}: bytes outside the {k} block changed"
-        return res
+    def __init__(self, path):
+        super().__init__(path, Call, SLOTS, OPS)
 
     # ---- the four operations on a Case
     def native_pairs(self, rec, lig, iface_cutoff, contact_cutoff):

@@ -2,8 +2,8 @@
 dfm_posewalk.h - launch_{sterics,surface,iface,rescon,hbond,pairpot}{_pose,}, launch_rescon_finish, launch_hbond_finish and
 k_surface_finish inside launch_surface - launch by launch.
 
-The shim drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so on host arrays, with sentinel guard bands around every device
-block, after checking everything a kernel would follow as an index.  This module compiles it, binds it with ctypes and holds
+The shim drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so under the guard-band protocol of tests/kernel_harness.py, after
+checking everything a kernel would follow as an index.  This module binds it and holds
   * a frame built in numpy from the comments of dfm_poseprep.h, not by calling it (cell grid, sorted receptor, Morton-ordered ligand
     blocks, spheres, thr, reject2, grow), with knobs the host never turns: an edge that is not the reach, a padded box, a ligand in
     any order, spheres larger than needed;
@@ -27,20 +27,13 @@ operations in the same order as the restatement, so every comparison is bitwise 
 import copy
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 
-from heads_harness import Out, guards_intact, is_sentinel      # noqa: F401 (re-exported)
+import kernel_harness as kh
+from kernel_harness import HIP_INVALID_VALUE, HIP_SUCCESS, LIBDIR, ROOT, Out, guards_intact, is_sentinel      # noqa: F401 (re-exported)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "dfmdock_amd")
-SHIM_SRC = os.path.join(ROOT, "tests", "kernels", "pose_harness.hip")
-HIP_SUCCESS = 0
-HIP_INVALID_VALUE = 1
 INF_BITS = 0x7FF0000000000000
 MARKER = -77      # prefill of the per-atom outputs "written by the waves that reach the cell walk only"
 POSE_GATE_FACTOR = 8.0
@@ -66,91 +59,27 @@ def f64(x):
     return np.asarray(x, np.float64)
 
 
-class PhBuf(C.Structure):
-    _fields_ = [("host", C.c_void_p), ("bytes", C.c_longlong), ("out", C.c_int)]
-
-
-class PhCall(C.Structure):
-    _fields_ = ([("buf", PhBuf * len(SLOTS))] + [(n, C.c_double * 3) for n in VECS] + [(n, C.c_double) for n in DOUBLES] +
+class Call(C.Structure):
+    _fields_ = ([("buf", kh.Buf * len(SLOTS))] + [(n, C.c_double * 3) for n in VECS] + [(n, C.c_double) for n in DOUBLES] +
                 [("reject2", C.c_float), ("slack", C.c_float)] + [(n, C.c_int) for n in INTS])
 
 
-def hipcc():
-    return os.environ.get("HIPCC") or "/opt/rocm/bin/hipcc"
-
-
-def compile_shim(outdir):
-    """hipcc --offload-arch=gfx950 -shared -fPIC, linked against the built library with an rpath.  Raises if the compiler is missing."""
-    cc = hipcc()
-    if not (os.path.isfile(cc) or shutil.which(cc)):
-        raise RuntimeError(f"hipcc not found ({cc}): the kernel harness cannot be built")
-    out = os.path.join(str(outdir), "libpose_harness.so")
-    subprocess.run([cc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", SHIM_SRC, "-o", out,
-                    "-L", LIBDIR, "-ldfmdock_amd", "-Wl,-rpath," + LIBDIR], check=True, capture_output=True, text=True)
-    return out
+compile_shim = functools.partial(kh.compile_shim, "pose")
 
 
 # ---- binding -----------------------------------------------------------------------------------------------------------------------
-def fill_call(bufs, scalars, guard):
-    """The ctypes record of one call.  bufs: slot -> array (input) or Out (init = the prefill).  Returns (call, host, keep)."""
-    call = PhCall()
-    keep, host = [], {}
-    for k, v in scalars.items():
-        if k in VECS:
-            setattr(call, k, (C.c_double * 3)(*[float(x) for x in v]))
-        else:
-            setattr(call, k, int(v) if k in INTS else float(v))      # (reject2 and slack are c_float fields: float32 values pass unchanged)
-    for k, v in bufs.items():
-        if v is None:
-            continue
-        b = call.buf[SLOTS.index(k)]
-        if isinstance(v, Out):
-            nbytes = v.dtype.itemsize * v.n
-            raw = np.zeros(guard * 2 + nbytes, np.uint8)
-            if v.init is not None:
-                raw[guard:guard + nbytes] = v.init.reshape(-1).view(np.uint8)
-            host[k] = (raw, v.dtype, nbytes)
-            b.host, b.bytes, b.out = raw.ctypes.data, nbytes, 1 if v.init is None else 2
-        else:
-            a = np.ascontiguousarray(v)
-            nbytes = a.nbytes
-            if a.size == 0:      # an empty array still needs an address
-                a = np.zeros(1, a.dtype)
-            keep.append(a)
-            b.host, b.bytes, b.out = a.ctypes.data, nbytes, 0
-    return call, host, keep
+class Harness(kh.KernelHarness):
+    check = True      # run() asserts success unless told check=False
 
-
-class Harness:
     def __init__(self, path):
-        self.path = path
-        self.lib = L = C.CDLL(path)
-        for f in (L.ph_run, L.ph_check):
-            f.argtypes = [C.POINTER(PhCall), C.c_int]
-            f.restype = C.c_int
-        for f in ("ph_guard_bytes", "ph_call_bytes"):
-            getattr(L, f).restype = C.c_longlong
-        self.guard = int(L.ph_guard_bytes())
-        assert int(L.ph_call_bytes()) == C.sizeof(PhCall), "PhCall: the ctypes layout differs from the shim's"
+        super().__init__(path, Call, SLOTS, OPS)
+        self.lib.ph_check.argtypes = [C.POINTER(Call), C.c_int]
+        self.lib.ph_check.restype = C.c_int
 
     def check_only(self, op, bufs, **scalars):
         """The shim's range checks alone: no device is touched."""
-        call, _, keep = fill_call(bufs, scalars, self.guard)
+        call, _, keep = self.fill_call(bufs, scalars)
         return int(self.lib.ph_check(C.byref(call), OPS.index(op)))
-
-    def run(self, op, bufs, check=True, **scalars):
-        """Returns {slot: interior array, slot + '_guard': (before, after) bytes, 'err'}.  check: the launch succeeded; always: no byte
-        outside a block that came back changed."""
-        call, host, keep = fill_call(bufs, scalars, self.guard)
-        res = {"err": int(self.lib.ph_run(C.byref(call), OPS.index(op)))}
-        for k, (raw, dt, nbytes) in host.items():
-            res[k] = raw[self.guard:self.guard + nbytes].view(dt).copy()
-            res[k + "_guard"] = (raw[:self.guard], raw[self.guard + nbytes:])
-        if check:
-            assert res["err"] == HIP_SUCCESS, f"{op}: hipError {res['err']}"
-        for k, (raw, _, _) in host.items():      # (a call the shim itself refuses copies nothing back: the guards are still zero)
-            assert not raw[:self.guard].any() or guards_intact(res, k), f"{op}: bytes outside the {k} block changed"
-        return res
 
     # ---- the operations
     def pose(self, op, rot, tr, extra=3):

@@ -1,12 +1,12 @@
 """The kernel harness of the node-model GEMMs without a GPU (tests/dense_harness.py, tests/kernels/dense_harness.hip): it builds and
 links against the library, the launcher refuses bad shapes before any device work, the float64 restatements agree with numpy, and
 the GEMM bound of tests/test_gpu_dense_kernels.py is tight enough to catch a kernel that drops precision."""
-import subprocess
 
 import numpy as np
 import pytest
 
 import dense_harness as dh
+import kernel_harness as kh
 
 
 @pytest.fixture(scope="module")
@@ -21,15 +21,14 @@ def harness(shim):
 
 def test_library_exports_the_launchers():
     """The harness links against dfm::launch_* by name: a build with hidden visibility would break it silently."""
-    out = subprocess.run(["nm", "-D", "--defined-only", dh.LIBDIR + "/libdfmdock_amd.so"], check=True, capture_output=True,
-                         text=True).stdout
+    out = kh.exported_symbols(dh.LIBDIR + "/libdfmdock_amd.so", True)
     syms = {line.split()[-1] for line in out.splitlines() if line.strip()}
     for s in dh.LAUNCHERS:
         assert s in syms, s
 
 
 def test_shim_links(shim, harness):
-    out = subprocess.run(["nm", "-D", "--undefined-only", shim], check=True, capture_output=True, text=True).stdout
+    out = kh.exported_symbols(shim, False)
     for s in dh.LAUNCHERS:
         assert s in out, s
     assert harness.guard >= 1024

@@ -10,6 +10,7 @@ import pytest
 
 import dense_harness as dh
 import edge_harness as eh
+import kernel_harness as kh
 
 H = eh.H
 S = eh.S
@@ -32,15 +33,14 @@ def layer():
 
 def test_library_exports_the_launchers():
     """The harness links against the launchers by name: a build with hidden visibility would break it silently."""
-    out = subprocess.run(["nm", "-D", "--defined-only", eh.LIBDIR + "/libdfmdock_amd.so"], check=True, capture_output=True,
-                         text=True).stdout
+    out = kh.exported_symbols(eh.LIBDIR + "/libdfmdock_amd.so", True)
     syms = {line.split()[-1] for line in out.splitlines() if line.strip()}
     for s in eh.LAUNCHERS:
         assert s in syms, s
 
 
 def test_shim_links(shim, harness):
-    out = subprocess.run(["nm", "-D", "--undefined-only", shim], check=True, capture_output=True, text=True).stdout
+    out = kh.exported_symbols(shim, False)
     for s in eh.LAUNCHERS:
         assert s in out, s
     assert harness.guard >= 1024

@@ -3,12 +3,12 @@ the shim builds and links against the library's launchers; the numpy Philox and 
 references agree with the project's CPU oracle on a small complex; each seeded mutant of a reference is rejected by the very comparison
 the GPU tests use; the exclusion caps (undecided nodes <= 2 %, undecided edges <= 1 %) hold on the GPU tests' own inputs; u01 is
 monotone with smallest value 2^-25 and largest value exactly 1.0f."""
-import subprocess
 
 import numpy as np
 import pytest
 
 import geom_harness as gh
+import kernel_harness as kh
 
 
 @pytest.fixture(scope="module")
@@ -22,14 +22,14 @@ def h(shim):
 
 
 def test_library_exports_the_launchers():
-    out = subprocess.run(["nm", "-D", "--defined-only", gh.LIBDIR + "/libdfmdock_amd.so"], check=True, capture_output=True, text=True).stdout
+    out = kh.exported_symbols(gh.LIBDIR + "/libdfmdock_amd.so", True)
     syms = {line.split()[-1] for line in out.splitlines() if line.strip()}
     for s in gh.LAUNCHERS:
         assert s in syms, s
 
 
 def test_shim_links(shim, h):
-    out = subprocess.run(["nm", "-D", "--undefined-only", shim], check=True, capture_output=True, text=True).stdout
+    out = kh.exported_symbols(shim, False)
     for s in gh.LAUNCHERS:
         assert s in out, s
     assert h.guard >= 1024

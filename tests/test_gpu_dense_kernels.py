@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import dense_harness as dh
+from dense_harness import Out
 
 pytestmark = pytest.mark.gpu
 
@@ -48,34 +49,34 @@ def cus(h):
 # ---- launch descriptions ------------------------------------------------------------------------------------------------------
 def split_launch(M, K, Nout, A0, W, *, A1=None, bias=None, pro=0, epi=0, R=None, rpg=0, a0_period=0, r_period=0, stats=False,
                  zbuf=False, outs=("C",), ldc=None, gn=None, op="split", a0_offset=0):
-    """One launch as {op, ins, outs, ints}.  gn: dict of gn_shift / gn_den / gn_w / gn_b / gn_part / gn_ms arrays."""
+    """One launch as {op, bufs, scalars}: inputs are arrays, outputs Out.  gn: dict of gn_shift / gn_den / gn_w / gn_b / gn_part / gn_ms arrays."""
     ldc = ldc or (256 if epi == 2 else Nout)
-    ins = {"A0": A0, "A1": A1, "bias": bias, "R": R}
+    bufs = {"A0": A0, "A1": A1, "bias": bias, "R": R}
     if op == "split":
-        ins["Whi"], ins["Wlo"] = dh.split_bf16(W)
+        bufs["Whi"], bufs["Wlo"] = dh.split_bf16(W)
     else:
-        ins["W"] = np.ascontiguousarray(W, np.float32)
+        bufs["W"] = np.ascontiguousarray(W, np.float32)
         if a0_offset:
-            ins["A0"] = np.concatenate([np.zeros(a0_offset // 4, np.float32), np.ravel(A0)])
-    ins.update(gn or {})
-    o = {}
+            bufs["A0"] = np.concatenate([np.zeros(a0_offset // 4, np.float32), np.ravel(A0)])
+    bufs.update(gn or {})
     for s in outs:
         n = M * ldc if s == "C" else M * 256
-        o[s] = (np.uint16 if s in ("C2b", "Cb") else np.float32, n)
+        bufs[s] = Out(np.uint16 if s in ("C2b", "Cb") else np.float32, n)
     if stats:
-        o["stat_part"] = (np.float32, (M // rpg) * ((rpg + 31) // 32) * 256 * 2)
+        bufs["stat_part"] = Out(np.float32, (M // rpg) * ((rpg + 31) // 32) * 256 * 2)
     if zbuf:
-        o["zbuf"] = (np.float32, M * 256)
-    ints = dict(M=M, K=K, Nout=Nout, lda=A0.shape[-1], ldw=K, ldc=ldc, pro=pro, epi=epi, rows_per_graph=rpg, a0_period=a0_period,
-                r_period=r_period, a0_offset=a0_offset)
-    return {"op": op, "ins": ins, "outs": o, "ints": ints}
+        bufs["zbuf"] = Out(np.float32, M * 256)
+    scalars = dict(M=M, K=K, Nout=Nout, lda=A0.shape[-1], ldw=K, ldc=ldc, pro=pro, epi=epi, rows_per_graph=rpg, a0_period=a0_period,
+                   r_period=r_period, a0_offset=a0_offset)
+    return {"op": op, "bufs": bufs, "scalars": scalars}
 
 
 def run(h, L):
-    r = h.run(L["op"], L["ins"], L["outs"], **L["ints"])
+    r = h.run(L["op"], L["bufs"], **L["scalars"])
     assert r["err"] == dh.HIP_SUCCESS, f"hipError {r['err']}"
-    for s in L["outs"]:
-        assert dh.guards_intact(r, s), f"{s}: bytes outside the output block changed"
+    for s, v in L["bufs"].items():
+        if isinstance(v, Out):
+            assert dh.guards_intact(r, s), f"{s}: bytes outside the output block changed"
     return r
 
 
@@ -138,24 +139,24 @@ def worst_ratio(got, ref, S):
 
 def check_gemm(r, L, A_eff, W, *, act_err=None, report=None, fracs=None):
     """Every output of launch L against float64 of A_eff (the prologue's output, [M][K]) times W^T + bias (+ R)."""
-    M, Nout, epi, ldc = L["ints"]["M"], L["ints"]["Nout"], L["ints"]["epi"], L["ints"]["ldc"]
+    M, Nout, epi, ldc = L["scalars"]["M"], L["scalars"]["Nout"], L["scalars"]["epi"], L["scalars"]["ldc"]
     W64 = np.asarray(W, np.float64)
     acc = A_eff @ W64.T
     S = np.abs(A_eff) @ np.abs(W64).T
-    err = dh.C_SPLIT * S if L["op"] == "split" else (L["ints"]["K"] + 4) * U * S
+    err = dh.C_SPLIT * S if L["op"] == "split" else (L["scalars"]["K"] + 4) * U * S
     if act_err is not None:
         err = err + act_err @ np.abs(W64).T
-    bias = L["ins"]["bias"]
+    bias = L["bufs"]["bias"]
     b64 = np.zeros(Nout) if bias is None else np.asarray(bias, np.float64)
     ref = acc + b64
     Rf = 0.0
     if epi == 1:
-        R = L["ins"]["R"].astype(np.float64)
-        Rf = a_rows(R, M, L["ints"]["r_period"])
+        R = L["bufs"]["R"].astype(np.float64)
+        Rf = a_rows(R, M, L["scalars"]["r_period"])
         ref = ref + Rf
     b32 = err + 2 * U * (np.abs(ref) + np.abs(b64) + np.abs(Rf))
     b16 = b32 * (1 + 2.0 ** -11) + 2.0 ** -11 * np.abs(ref) + 2.0 ** -25
-    outs = L["outs"]
+    outs = L["bufs"]      # (the output slots: no input has one of their names)
     if "C" in outs:
         C = r["C"].reshape(M, ldc)
         if epi == 2:
@@ -180,7 +181,7 @@ def check_gemm(r, L, A_eff, W, *, act_err=None, report=None, fracs=None):
 def check_stat_part(r, L, C):
     """stat_part = (mean, M2) per 32-row half of every trajectory, against float64 of the kernel's own fp32 C (bound: the fused
     per-half terms of den_rel_bound, from the fp32 shifted sums and the Chan merges of the kernel)."""
-    N = L["ints"]["rows_per_graph"]
+    N = L["scalars"]["rows_per_graph"]
     sp = r["stat_part"].reshape(-1, (N + 31) // 32, 256, 2).astype(np.float64)
     assert np.isfinite(sp).all(), "stat_part: a slot was not written (sentinel left) or is not finite"
     ref = dh.half_stats64(C, N)
@@ -202,8 +203,8 @@ def gn_params(rng):
 
 
 def gn_stats_launch(u, B, N, ms, w=None, b=None):
-    return {"op": "gn_stats", "ins": {"A0": u, "gn_ms": ms, "gn_w": w, "gn_b": b},
-            "outs": {"C": (np.float32, B * 256), "C2": (np.float32, B * 256)}, "ints": dict(gn_B=B, gn_N=N)}
+    return {"op": "gn_stats", "bufs": {"A0": u, "gn_ms": ms, "gn_w": w, "gn_b": b, "C": Out(np.float32, B * 256), "C2": Out(np.float32, B * 256)},
+            "scalars": dict(gn_B=B, gn_N=N)}
 
 
 # ---- the node model's launch chain at one size --------------------------------------------------------------------------------

@@ -41,6 +41,7 @@ import pytest
 
 import dense_harness as dh
 import edge_harness as eh
+from edge_harness import Out
 
 pytestmark = pytest.mark.gpu
 
@@ -111,41 +112,48 @@ def ints(inp, **kw):
 
 def agg_init(inp, zero):
     n = inp["B"] * inp["N"] * H
-    return (np.zeros(n, np.float32) if zero else np.full(n, SENT_F32, np.float32),)
+    return io(np.zeros(n, np.float32) if zero else np.full(n, SENT_F32, np.float32))
+
+
+def io(a):
+    """An in / out block that starts as array a."""
+    a = np.asarray(a)
+    return Out(a.dtype, init=a)
 
 
 def msg_launch(L, inp, *, f16, aw16, last=0, lig_only=0, agg_zero=True, task_ctr=True, repeat=1, mbuf=None, A_s=None):
     A_s = inp["A_s"] if A_s is None else A_s
     Lig = inp["N"] - inp["R"]
-    ins = {"A": A_s, "Bmb": dh.f2h(inp["Bm_s"]), "Ah": dh.f2h(A_s) if aw16 else None, "edges": inp["edges"], "codes": inp["codes"],
-           "radial": inp["rad"], "ca4": inp["ca4"]}
-    ins.update({k: v for k, v in L["slots"].items()})
-    outs = {"agg": agg_init(inp, agg_zero)}
+    bufs = {"A": A_s, "Bmb": dh.f2h(inp["Bm_s"]), "Ah": dh.f2h(A_s) if aw16 else None, "edges": inp["edges"], "codes": inp["codes"],
+            "radial": inp["rad"], "ca4": inp["ca4"]}
+    bufs.update({k: v for k, v in L["slots"].items()})
+    bufs["agg"] = agg_init(inp, agg_zero)
     if task_ctr:
-        outs["task_ctr"] = (np.zeros(2 * eh.TASK_CTR_WGS, np.uint32),)
+        bufs["task_ctr"] = io(np.zeros(2 * eh.TASK_CTR_WGS, np.uint32))
     if last:
-        outs["mbuf"] = (mbuf,) if mbuf is not None else (np.uint16, inp["B"] * Lig * 64 * H)
-        outs["fout"] = (np.float32, inp["B"] * Lig * 3)
-    return {"op": "edge_bf16", "ins": ins, "outs": outs,
-            "ints": ints(inp, last=last, f16=f16, lig_only=lig_only, agg_is_zero=int(agg_zero), repeat=repeat, att_b=L["att_b"])}
+        bufs["mbuf"] = io(mbuf) if mbuf is not None else Out(np.uint16, inp["B"] * Lig * 64 * H)
+        bufs["fout"] = Out(np.float32, inp["B"] * Lig * 3)
+    return {"op": "edge_bf16", "bufs": bufs,
+            "scalars": ints(inp, last=last, f16=f16, lig_only=lig_only, agg_is_zero=int(agg_zero), repeat=repeat, att_b=L["att_b"])}
 
 
 def f32_launch(L, inp, *, last=0, lig_only=0, A=None):
     Lig = inp["N"] - inp["R"]
-    ins = {"A": inp["A"] if A is None else A, "Bm": inp["Bm"], "edges": inp["edges"], "codes": inp["codes"], "radial": inp["rad"],
-           "ca4": inp["ca4"]}
-    ins.update(L["slots"])
-    outs = {"agg": agg_init(inp, False), "range": (np.zeros(2, np.uint32),)}
+    bufs = {"A": inp["A"] if A is None else A, "Bm": inp["Bm"], "edges": inp["edges"], "codes": inp["codes"], "radial": inp["rad"],
+            "ca4": inp["ca4"]}
+    bufs.update(L["slots"])
+    bufs.update(agg=agg_init(inp, False), range=io(np.zeros(2, np.uint32)))
     if last:
-        outs["fout"] = (np.float32, inp["B"] * Lig * 3)
-    return {"op": "edge_f32", "ins": ins, "outs": outs, "ints": ints(inp, last=last, lig_only=lig_only, att_b=L["att_b"])}
+        bufs["fout"] = Out(np.float32, inp["B"] * Lig * 3)
+    return {"op": "edge_f32", "bufs": bufs, "scalars": ints(inp, last=last, lig_only=lig_only, att_b=L["att_b"])}
 
 
 def run(h, Lc):
-    r = h.run(Lc["op"], Lc["ins"], Lc["outs"], Lc["ints"])
+    r = h.run(Lc["op"], Lc["bufs"], **Lc["scalars"])
     assert r["err"] == dh.HIP_SUCCESS, f"hipError {r['err']}"
-    for s in Lc["outs"]:
-        assert eh.guards_intact(r, s), f"{s}: bytes outside the output block changed"
+    for s, v in Lc["bufs"].items():
+        if isinstance(v, Out):
+            assert eh.guards_intact(r, s), f"{s}: bytes outside the output block changed"
     if "task_ctr" in r:
         assert not r["task_ctr"].any(), "task counters not zero after the launch"
     return r
@@ -261,12 +269,12 @@ def rows_launch(h, layer, inp, rows, cnt, fp32):
     """launch_edge_rows (fp16) / launch_edge_rows32 over the list `rows` (capacity len(rows), device count cnt) -> [ceil32(cap)][256]."""
     cap = len(rows)
     cap32 = (cap + 31) // 32 * 32
-    ins = {"A": inp["A"] if fp32 else inp["A_s"], "Bm": inp["Bm"], "Bmb": dh.f2h(inp["Bm_s"]), "Ah": dh.f2h(inp["A_s"]),
-           "rows": rows, "n_rows": np.array([cnt], np.uint32)}
-    ins.update(layer["slots"])
-    outs = {"rows_out": (np.float32, cap32 * H) if fp32 else (np.uint16, cap32 * H)}
-    Lc = {"op": "edge_rows32" if fp32 else "edge_rows", "ins": ins, "outs": outs,
-          "ints": dict(B=1, N=inp["N"], R=0, K=1, f16=1, n_rows_cap=cap, ab_bstride=0, att_b=layer["att_b"])}
+    bufs = {"A": inp["A"] if fp32 else inp["A_s"], "Bm": inp["Bm"], "Bmb": dh.f2h(inp["Bm_s"]), "Ah": dh.f2h(inp["A_s"]),
+            "rows": rows, "n_rows": np.array([cnt], np.uint32)}
+    bufs.update(layer["slots"])
+    bufs["rows_out"] = Out(np.float32 if fp32 else np.uint16, cap32 * H)
+    Lc = {"op": "edge_rows32" if fp32 else "edge_rows", "bufs": bufs,
+          "scalars": dict(B=1, N=inp["N"], R=0, K=1, f16=1, n_rows_cap=cap, ab_bstride=0, att_b=layer["att_b"])}
     return run(h, Lc)["rows_out"].reshape(cap32, H)
 
 
@@ -329,9 +337,10 @@ def test_last_layer(h, cus, layer, f16, K):
     fouts = []
     assert eh.coord_form(B, Lig, cus) == "static"
     for lig_only in (0, 1):
-        Lc = {"op": "coord_bf16", "ins": {**Lw["slots"], "edges": inp["edges"], "ca4": inp["ca4"]},
-              "outs": {"mbuf": (res[lig_only]["mbuf"],), "fout": (np.float32, B * Lig * 3), "task_ctr": (np.zeros(2 * eh.TASK_CTR_WGS, np.uint32),)},
-              "ints": ints(inp, last=1, f16=f16, lig_only=lig_only)}
+        Lc = {"op": "coord_bf16",
+              "bufs": {**Lw["slots"], "edges": inp["edges"], "ca4": inp["ca4"], "mbuf": io(res[lig_only]["mbuf"]),
+                       "fout": Out(np.float32, B * Lig * 3), "task_ctr": io(np.zeros(2 * eh.TASK_CTR_WGS, np.uint32))},
+              "scalars": ints(inp, last=1, f16=f16, lig_only=lig_only)}
         rc = run(h, Lc)
         assert np.array_equal(rc["mbuf"], res[lig_only]["mbuf"]), "the coordinate kernel wrote its input"
         fouts.append(rc["fout"])
@@ -382,10 +391,10 @@ def test_coord_task_forms(h, shim, cus, layer, tmp_path):
     inp = dict(B=B, N=N, R=R, K=K, Ab=1)
 
     def launch(repeat):
-        return {"op": "coord_bf16", "ins": {**layer["slots"], "edges": edges, "ca4": ca4},
-                "outs": {"mbuf": (eh.encode_mbuf(bits),), "fout": (np.float32, B * Lig * 3),
-                         "task_ctr": (np.zeros(2 * eh.TASK_CTR_WGS, np.uint32),)},
-                "ints": ints(inp, last=1, f16=1, repeat=repeat)}
+        return {"op": "coord_bf16",
+                "bufs": {**layer["slots"], "edges": edges, "ca4": ca4, "mbuf": io(eh.encode_mbuf(bits)), "fout": Out(np.float32, B * Lig * 3),
+                         "task_ctr": io(np.zeros(2 * eh.TASK_CTR_WGS, np.uint32))},
+                "scalars": ints(inp, last=1, f16=1, repeat=repeat)}
 
     r1 = run(h, launch(1))
     r2 = run(h, launch(2))
@@ -523,12 +532,12 @@ def test_edge_rows(h, layer, fp32):
     cap32 = (cap + 31) // 32 * 32
 
     def launch(rw):
-        ins = {"A": inp["A"] if fp32 else inp["A_s"], "Bm": inp["Bm"], "Bmb": dh.f2h(inp["Bm_s"]), "Ah": dh.f2h(inp["A_s"]),
-               "rows": rw, "n_rows": np.array([cnt], np.uint32)}
-        ins.update(layer["slots"])
-        outs = {"rows_out": (np.float32, cap32 * H) if fp32 else (np.uint16, cap32 * H)}
-        Lc = {"op": "edge_rows32" if fp32 else "edge_rows", "ins": ins, "outs": outs,
-              "ints": dict(B=1, N=inp["N"], R=0, K=1, f16=1, n_rows_cap=cap, ab_bstride=0, att_b=layer["att_b"])}
+        bufs = {"A": inp["A"] if fp32 else inp["A_s"], "Bm": inp["Bm"], "Bmb": dh.f2h(inp["Bm_s"]), "Ah": dh.f2h(inp["A_s"]),
+                "rows": rw, "n_rows": np.array([cnt], np.uint32)}
+        bufs.update(layer["slots"])
+        bufs["rows_out"] = Out(np.float32 if fp32 else np.uint16, cap32 * H)
+        Lc = {"op": "edge_rows32" if fp32 else "edge_rows", "bufs": bufs,
+              "scalars": dict(B=1, N=inp["N"], R=0, K=1, f16=1, n_rows_cap=cap, ab_bstride=0, att_b=layer["att_b"])}
         return run(h, Lc)["rows_out"].reshape(cap32, H)
 
     out = launch(rows)
@@ -565,10 +574,10 @@ def test_l0_gather(h, fp32, K):
     xv = dh.h_to_f64(X) if not fp32 else X.astype(np.float64)
 
     def launch(B, src):
-        Lc = {"op": "l0_gather32" if fp32 else "l0_gather", "ins": {"table": tab, "X": X, "src": src},
-              "outs": {"agg": (np.float32, B * N * H), "counter": (np.array([7], np.uint32),),
-                       "miss_total": (np.array([100], np.uint64),)},
-              "ints": dict(B=B, N=N, K=K)}
+        Lc = {"op": "l0_gather32" if fp32 else "l0_gather",
+              "bufs": {"table": tab, "X": X, "src": src, "agg": Out(np.float32, B * N * H), "counter": io(np.array([7], np.uint32)),
+                       "miss_total": io(np.array([100], np.uint64))},
+              "scalars": dict(B=B, N=N, K=K)}
         r = run(h, Lc)
         assert r["counter"][0] == 0 and r["miss_total"][0] == 107
         return r["agg"].reshape(B, N, H)
@@ -611,8 +620,8 @@ def test_nan_reaches_every_output(h, layer, kernel):
         mask = np.ones(val.shape[:2], bool)
         mask[1, i0 - R] = False
         assert np.isfinite(val[mask][:, :K]).all()
-        Lc = {"op": "coord_bf16", "ins": {**layer["slots"], "edges": inp["edges"], "ca4": inp["ca4"]},
-              "outs": {"mbuf": (r["mbuf"],), "fout": (np.float32, B * Lig * 3)}, "ints": ints(inp, last=1, f16=f16)}
+        Lc = {"op": "coord_bf16", "bufs": {**layer["slots"], "edges": inp["edges"], "ca4": inp["ca4"], "mbuf": io(r["mbuf"]),
+                                           "fout": Out(np.float32, B * Lig * 3)}, "scalars": ints(inp, last=1, f16=f16)}
         fout = run(h, Lc)["fout"].reshape(B, Lig, 3)
     agg = r["agg"].reshape(B, N, H)
     assert np.isnan(agg[1, i0]).all(), "NaN lost in agg"
@@ -634,11 +643,11 @@ def test_nan_reaches_row_outputs(h, layer):
     for fp32 in (0, 1):
         A = inp["A"].copy()
         A[0, i0, 3] = np.nan
-        ins = {"A": A if fp32 else A_s, "Bm": inp["Bm"], "Bmb": dh.f2h(inp["Bm_s"]), "Ah": dh.f2h(A_s), "rows": rows}
-        ins.update(layer["slots"])
-        Lc = {"op": "edge_rows32" if fp32 else "edge_rows", "ins": ins,
-              "outs": {"rows_out": (np.float32, 64 * H) if fp32 else (np.uint16, 64 * H)},
-              "ints": dict(B=1, N=inp["N"], R=0, K=1, f16=1, n_rows_cap=64, ab_bstride=0, att_b=layer["att_b"])}
+        bufs = {"A": A if fp32 else A_s, "Bm": inp["Bm"], "Bmb": dh.f2h(inp["Bm_s"]), "Ah": dh.f2h(A_s), "rows": rows}
+        bufs.update(layer["slots"])
+        bufs["rows_out"] = Out(np.float32 if fp32 else np.uint16, 64 * H)
+        Lc = {"op": "edge_rows32" if fp32 else "edge_rows", "bufs": bufs,
+              "scalars": dict(B=1, N=inp["N"], R=0, K=1, f16=1, n_rows_cap=64, ab_bstride=0, att_b=layer["att_b"])}
         out = run(h, Lc)["rows_out"].reshape(64, H)
         v = out.astype(np.float64) if fp32 else dh.h_to_f64(out)
         hit = rows[:, 0] == i0

@@ -4,12 +4,12 @@ tests/test_gpu_head_kernels.py holds for an fp32 restatement of the kernel and i
 test sits within rounding of a threshold, and the LayerNorm conditioning kappa of the committed golden cases is where the moment form
 of the variance is harmless."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import heads_harness as hh
+import kernel_harness as kh
 from conftest import complex_for, load_golden, pair_hparams
 
 H = hh.H
@@ -22,15 +22,14 @@ def shim(tmp_path_factory):
 
 def test_library_exports_the_launchers():
     """The harness links against the launchers by name: a build with hidden visibility would break it silently."""
-    out = subprocess.run(["nm", "-D", "--defined-only", hh.LIBDIR + "/libdfmdock_amd.so"], check=True, capture_output=True,
-                         text=True).stdout
+    out = kh.exported_symbols(hh.LIBDIR + "/libdfmdock_amd.so", True)
     syms = {line.split()[-1] for line in out.splitlines() if line.strip()}
     for s in hh.LAUNCHERS:
         assert s in syms, s
 
 
 def test_shim_links(shim):
-    out = subprocess.run(["nm", "-D", "--undefined-only", shim], check=True, capture_output=True, text=True).stdout
+    out = kh.exported_symbols(shim, False)
     for s in hh.LAUNCHERS:
         assert s in out, s
     h = hh.Harness(shim)      # also checks that the ctypes call record has the shim's size

@@ -3,12 +3,12 @@ shim builds and links against the library's launchers; the float64 definition is
 GPU case's inputs (against its extended-precision evaluation); a numpy restatement of the kernels passes every comparison the GPU
 tests use and each of its ten seeded mutants is rejected by them on the GPU tests' own inputs; the generators keep the pairs within
 1e-3 A of a cutoff under the cap, and the lattice cases hold the planted pairs they claim."""
-import subprocess
 
 import numpy as np
 import pytest
 
 import metrics_harness as mh
+import kernel_harness as kh
 
 
 def all_cases():
@@ -22,18 +22,18 @@ def shim(tmp_path_factory):
 
 
 def test_library_exports_the_launchers():
-    out = subprocess.run(["nm", "-D", "--defined-only", mh.LIBDIR + "/libdfmdock_amd.so"], check=True, capture_output=True, text=True).stdout
+    out = kh.exported_symbols(mh.LIBDIR + "/libdfmdock_amd.so", True)
     syms = {line.split()[-1] for line in out.splitlines() if line.strip()}
     for s in mh.LAUNCHERS:
         assert s in syms, s
 
 
 def test_shim_links(shim):
-    out = subprocess.run(["nm", "-D", "--undefined-only", shim], check=True, capture_output=True, text=True).stdout
+    out = kh.exported_symbols(shim, False)
     for s in mh.LAUNCHERS:
         assert s in out, s
-    kernels = subprocess.run(["nm", "-D", "--defined-only", shim], check=True, capture_output=True, text=True).stdout
-    assert "mh_run" in kernels and "__device_stub__" not in kernels, "the shim adds no kernel of its own"
+    kernels = kh.exported_symbols(shim, True)
+    assert "kh_run" in kernels and "__device_stub__" not in kernels, "the shim adds no kernel of its own"
     h = mh.Harness(shim)      # also checks that the ctypes call record has the shim's size
     assert h.guard >= 1024
 

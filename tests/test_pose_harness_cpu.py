@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import pose_harness as ph
+import kernel_harness as kh
 
 ROOT = ph.ROOT
 BORDER, BORDER_CAP = 1e-3, 0.005      # the border rule of the API tests: a decision this close to its cutoff, for at most this share
@@ -26,12 +27,12 @@ def shim(tmp_path_factory):
 
 
 def test_shim_links_and_adds_no_kernel(shim):
-    und = subprocess.run(["nm", "-D", "--undefined-only", shim.path], check=True, capture_output=True, text=True).stdout
+    und = kh.exported_symbols(shim.path, False)
     for name in ("launch_sterics_pose", "launch_surface_pose", "launch_iface_pose", "launch_rescon_pose", "launch_hbond_pose",
                  "launch_pairpot_pose", "launch_stericsERK", "launch_resconERK", "launch_rescon_finish", "launch_hbond_finish"):
         assert name in und, name
-    defined = subprocess.run(["nm", "-D", "--defined-only", shim.path], check=True, capture_output=True, text=True).stdout
-    assert "ph_run" in defined and "__device_stub__" not in defined, "the shim adds no kernel of its own"
+    defined = kh.exported_symbols(shim.path, True)
+    assert "kh_run" in defined and "__device_stub__" not in defined, "the shim adds no kernel of its own"
     assert shim.guard >= 1024
 
 
@@ -47,7 +48,7 @@ def _sterics_call(h, case, **change):
 
 
 def test_shim_refuses_every_bad_index(shim):
-    """Everything a kernel would follow as an index, wrong in turn: hipErrorInvalidValue from the check that ph_run makes before it touches
+    """Everything a kernel would follow as an index, wrong in turn: hipErrorInvalidValue from the check that kh_run makes before it touches
     the device (ph_check is that check alone; this runs without a GPU)."""
     c = ph.generic_case(0)
     fr, P = c.fr, len(c.T)
