@@ -7,12 +7,15 @@ ligand-residue subset S (default: all L residues):
     rmsd_ab = sqrt( mean over the 3 |S| atoms of S of |x_a - x_b|^2 )      (no superposition: the receptor frame is the same in every
                                                                            trajectory, so this is the pairwise L-RMSD of CAPRI / DockQ)
     a ~ b  <=>  rmsd_ab <= radius                                         (a pose is its own neighbour)
+A pose with a non-finite coordinate among the compared residues has a non-finite rmsd to every pose, itself included (NaN for a NaN
+coordinate): it is no pose's neighbour, not even its own, never opens a cluster under either rule and keeps cluster_of = -1.
 
 Ranking: a per-pose key, lower is better, ties to the lower index, NaN last (`rank_order`).
   rule "energy" (leader clustering): walk the poses in key order; an unassigned pose opens a cluster that its unassigned neighbours join.
   rule "size" (ClusPro-style greedy): repeatedly the unassigned pose with the most unassigned neighbours (ties: better key, then lower
       index) and its unassigned neighbours form the next cluster.
-Both stop after max_clusters clusters; poses still unassigned then belong to cluster -1.  Clusters are numbered in the order they formed.
+Both stop after max_clusters clusters, or when no pose that is its own neighbour is left (every cluster has size >= 1); poses still
+unassigned then belong to cluster -1.  Clusters are numbered in the order they formed.
 """
 from __future__ import annotations
 
@@ -54,8 +57,9 @@ def pose_rmsd(lig_pos, residues=None):
     x = x.reshape(x.shape[0], -1, 3).astype(np.float64)
     B, n = x.shape[0], x.shape[1]
     out = np.empty((B, B), np.float64)
-    for a in range(B):      # direct differences (the Gram form cancels: |x|^2 ~ 1e6 A^2 against 1e1 for a close pair)
-        out[a] = np.sqrt(((x - x[a]) ** 2).sum(-1).sum(-1) / n)
+    with np.errstate(invalid="ignore", over="ignore"):      # a non-finite coordinate makes its pose's row and column non-finite
+        for a in range(B):      # direct differences (the Gram form cancels: |x|^2 ~ 1e6 A^2 against 1e1 for a close pair)
+            out[a] = np.sqrt(((x - x[a]) ** 2).sum(-1).sum(-1) / n)
     return out
 
 
@@ -71,8 +75,8 @@ def rank_order(key, B):
 
 
 def cluster_adjacency(adj, key=None, rule="energy", max_clusters=None):
-    """The two rules on a boolean neighbour matrix adj [B, B] (symmetric, True diagonal).  Returns {n_clusters, center, size,
-    cluster_of} as int32 arrays (center / size have n_clusters entries)."""
+    """The two rules on a boolean neighbour matrix adj [B, B] (symmetric; the diagonal True but for poses with a non-finite coordinate).
+    Returns {n_clusters, center, size, cluster_of} as int32 arrays (center / size have n_clusters entries)."""
     if rule not in RULES:
         raise ValueError(f"rule must be one of {RULES}, got {rule!r}")
     adj = np.asarray(adj, bool)
@@ -83,7 +87,7 @@ def cluster_adjacency(adj, key=None, rule="energy", max_clusters=None):
     order = rank_order(key, B)
     pos = np.empty(B, np.int64)
     pos[order] = np.arange(B)
-    free = np.ones(B, bool)
+    free = adj.diagonal().copy()      # a pose that is not its own neighbour (a non-finite coordinate) opens no cluster and joins none
     cluster_of = np.full(B, -1, np.int32)
     center, size = [], []
     if rule == "energy":

@@ -157,7 +157,16 @@ struct MinOp { __device__ int operator()(int a, int b) const { return a < b ? a 
 struct SumOp { __device__ int operator()(int a, int b) const { return a + b; } };
 struct MaxOp64 { __device__ unsigned long long operator()(unsigned long long a, unsigned long long b) const { return a > b ? a : b; } };
 
-__device__ inline uint32_t valid_bits(int w, int B) { const int n = B - w * 32; return n >= 32 ? 0xffffffffu : ((1u << n) - 1u); }
+// word w of the candidate set every rule starts from: the poses that are their own neighbour (the diagonal of the bitmask).  A pose
+// with a non-finite coordinate among the compared residues is nobody's neighbour, itself included (sqrtf(NaN) <= radius is false): it
+// never opens a cluster and never joins one.  Bits at or beyond B stay clear.
+__device__ inline uint32_t self_bits(const uint32_t *__restrict__ mask, int w, int W, int B)
+{
+    const int n = B - w * 32 < 32 ? B - w * 32 : 32;
+    uint32_t u = 0;
+    for (int b = 0; b < n; ++b) u |= ((mask[(int64_t)(w * 32 + b) * W + w] >> b) & 1u) << b;
+    return u;
+}
 
 }  // namespace
 
@@ -173,7 +182,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_cluster_leader(const uint32_t *_
     __shared__ uint32_t U[CL_MAX_WORDS];
     __shared__ int scr[16];
     const int tid = threadIdx.x;
-    for (int w = tid; w < W; w += CL_THREADS) U[w] = valid_bits(w, B);
+    for (int w = tid; w < W; w += CL_THREADS) U[w] = self_bits(mask, w, W, B);
     for (int i = tid; i < B; i += CL_THREADS) cluster_of[i] = -1;
     __syncthreads();
     int pos = 0, k = 0;
@@ -209,7 +218,8 @@ __global__ __launch_bounds__(CL_THREADS) void k_cluster_leader(const uint32_t *_
     if (tid == 0) n_out[0] = k;
 }
 
-// rule 1, step 0: counts[i] = neighbours of i (all poses unassigned), U = every pose, cluster_of = -1, state = {clusters, done, members}
+// rule 1, step 0: counts[i] = neighbours of i (all poses unassigned), U = every pose that is its own neighbour, cluster_of = -1,
+// state = {clusters, done, members}
 __global__ __launch_bounds__(256) void k_cluster_count(const uint32_t *__restrict__ mask, int B, int W, int32_t *__restrict__ counts,
                                                        uint32_t *__restrict__ U, int32_t *__restrict__ cluster_of, int32_t *__restrict__ state)
 {
@@ -221,7 +231,7 @@ __global__ __launch_bounds__(256) void k_cluster_count(const uint32_t *__restric
         if (lane == 0) { counts[r] = c; cluster_of[r] = -1; }
     }
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    for (int w = g; w < W; w += gridDim.x * blockDim.x) U[w] = valid_bits(w, B);
+    for (int w = g; w < W; w += gridDim.x * blockDim.x) U[w] = self_bits(mask, w, W, B);
     if (g < 3) state[g] = 0;
 }
 
@@ -247,7 +257,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_cluster_pick(const uint32_t *__r
     }
     best = block_reduce(best, scr64, MaxOp64());
     const int k = state[0];
-    if (best == 0) {      // every pose assigned (an unassigned pose counts at least itself)
+    if (best == 0) {      // every pose assigned (a pose in U is its own neighbour, so it counts at least itself)
         if (tid == 0) state[1] = 1;
         return;
     }

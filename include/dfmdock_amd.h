@@ -326,11 +326,16 @@ int dfm_restraint_eval(dfm_complex *cx, int B, const float *lig_pos, float *ener
  * Each pair sums direct differences in a fixed order over the coordinates: the matrix is bitwise symmetric, and a pair's value does
  * not depend on B or on the order of the poses.  Neighbours: rmsd_ab <= radius (a pose is its own neighbour).  Key order: key_or_null
  * ascending (lower = better; NULL: index order), ties to the lower index, NaN last.
+ * A pose with a non-finite coordinate among the compared residues: its whole row and column of the dfm_pose_rmsd matrix, the diagonal
+ * included, are not finite (NaN for a NaN coordinate; +-inf off the diagonal for an infinite one) and every other entry keeps its bits;
+ * a coordinate outside the compared residues is never read.  Such a pose is no pose's neighbour, ITSELF INCLUDED: it never opens a
+ * cluster under either rule, joins none and keeps cluster_of = -1.
  *   rule DFM_CLUSTER_ENERGY (leader clustering): walk the poses in key order; an unassigned pose opens a cluster and its unassigned
  *     neighbours join it.
  *   rule DFM_CLUSTER_SIZE (greedy, ClusPro style): repeatedly the unassigned pose with the most unassigned neighbours (ties: better key,
  *     then lower index) and its unassigned neighbours form the next cluster.
- * Both stop after max_clusters clusters.  Out: *n_clusters, center[k] and size[k] for k < n_clusters (the arrays hold at least
+ * Both stop after max_clusters clusters or when no pose that is its own neighbour is left, so every cluster formed has size >= 1 and
+ * B poses that are all non-finite give *n_clusters = 0.  Out: *n_clusters, center[k] and size[k] for k < n_clusters (the arrays hold at least
  * min(max_clusters, B) entries), cluster_of[B] (-1: not in any of the clusters formed); clusters are numbered in the order they formed.
  * Results equal the float64 definition dfmdock_amd/cluster.py exactly wherever no pair lies within float32 rounding of the radius.
  * Limits: 1 <= B <= 65536, L >= 1, residues in [0, L) without repeats, radius finite and > 0, rule 0 or 1, max_clusters >= 1 - else

@@ -29,7 +29,7 @@ def _brute(lig_pos, radius, key=None, rule="energy", max_clusters=None, residues
         return i < j
 
     maxc = B if max_clusters is None else max_clusters
-    free, of, center, size = set(range(B)), [-1] * B, [], []
+    free, of, center, size = {i for i in range(B) if nb[i][i]}, [-1] * B, [], []      # (a pose with a NaN is not its own neighbour)
     if rule == "energy":
         order = list(range(B))
         for i in range(B):      # selection sort with `better`
@@ -137,6 +137,40 @@ def test_max_clusters_leaves_the_rest_unassigned(rule):
     got = cluster_poses(x, 2.5, rule=rule, max_clusters=2)
     assert got["n_clusters"] == 2 and (got["cluster_of"] == -1).sum() == 9 - got["size"].sum()
     _same(got, _brute(x, 2.5, rule=rule, max_clusters=2))
+
+
+@pytest.mark.filterwarnings("ignore:invalid value")
+@pytest.mark.parametrize("max_clusters", [None, 2, 6])
+@pytest.mark.parametrize("rule", ["energy", "size"])
+def test_a_non_finite_pose_opens_no_cluster(rule, max_clusters):
+    """A pose with a non-finite coordinate is no pose's neighbour, itself included: it never opens a cluster, keeps cluster_of = -1,
+    every cluster formed has a member, and the run ends when no pose that is its own neighbour is left - keyed first, keyed last, and
+    when every pose is such a pose."""
+    from dfmdock_amd.cluster import cluster_poses
+    x = _chain(6, 2.0)
+    x[3:] += np.float32(100.0)      # two chains of three
+    kw = {} if max_clusters is None else {"max_clusters": max_clusters}
+    for bad, value in ((0, np.nan), (5, np.nan), (2, np.inf)):
+        y = x.copy()
+        y[bad, 1, 2, 0] = value
+        for key in (None, np.where(np.arange(6) == bad, -9.0, np.arange(6)).astype(np.float32),      # keyed first
+                    np.where(np.arange(6) == bad, 99.0, np.arange(6)).astype(np.float32)):           # keyed last
+            got = cluster_poses(y, 2.5, key=key, rule=rule, **kw)
+            _same(got, _brute(y, 2.5, key=key, rule=rule, **kw))
+            assert got["cluster_of"][bad] == -1 and bad not in list(got["center"]) and (got["size"] >= 1).all()
+            if max_clusters != 2:
+                assert got["size"].sum() == 5 and (np.delete(got["cluster_of"], bad) >= 0).all()
+        sub = cluster_poses(y, 2.5, rule=rule, residues=[0, 2], **kw)      # the non-finite coordinate is in residue 1: not compared
+        _same(sub, cluster_poses(x, 2.5, rule=rule, residues=[0, 2], **kw))
+    allbad = x.copy()
+    allbad[:, 0, 0, 0] = np.nan
+    got = cluster_poses(allbad, 2.5, key=np.arange(6, dtype=np.float32), rule=rule, **kw)
+    assert got["n_clusters"] == 0 and got["center"].size == 0 and got["size"].size == 0 and (got["cluster_of"] == -1).all()
+    # the case of the record: 6 poses, one with a NaN, one cluster of the five others
+    far = _chain(6, 1.0)
+    far[3, 0, 0, 0] = np.nan
+    got = cluster_poses(far, 50.0, rule=rule, **kw)
+    assert got["n_clusters"] == 1 and list(got["center"]) == [0] and list(got["size"]) == [5] and list(got["cluster_of"]) == [0, 0, 0, -1, 0, 0]
 
 
 @pytest.mark.parametrize("seed", range(6))

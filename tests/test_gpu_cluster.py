@@ -121,6 +121,42 @@ def test_cluster_equals_the_definition(rule, B, L, model):
         assert want["n_clusters"] > 1
 
 
+@pytest.mark.parametrize("rule", ["energy", "size"])
+def test_a_non_finite_pose_opens_no_cluster(rule, model):
+    """A pose with a NaN or an infinite coordinate among the compared residues is no pose's neighbour, itself included: keyed first or
+    keyed last it opens no cluster and keeps cluster_of = -1, every cluster has a member, and when every pose is such a pose no cluster
+    forms - with and without max_clusters, equal to the definition."""
+    from dfmdock_amd.cluster import cluster_poses
+    rng = np.random.default_rng(5)
+    B, L = 70, 12
+    basins = _rigid(_ligand(L), 4, rng, spread=25.0)
+    x = np.stack([basins[rng.integers(4)] + rng.integers(-2, 3, 3).astype(np.float64) for _ in range(B)]).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        for bad, value in ((0, np.nan), (B - 1, np.nan), (37, np.inf)):
+            y = x.copy()
+            y[bad, 5, 1, 2] = value
+            first = np.where(np.arange(B) == bad, -1e9, rng.normal(size=B)).astype(np.float32)
+            last = np.where(np.arange(B) == bad, 1e9, first).astype(np.float32)
+            for key in (None, first, last):
+                for kw in ({}, {"max_clusters": 3}):
+                    want = cluster_poses(y, 2.55, key=key, rule=rule, **kw)
+                    got = model.pose_cluster(y, 2.55, key=key, rule=rule, **kw)
+                    for k in ("n_clusters", "center", "size", "cluster_of"):
+                        assert np.array_equal(got[k], want[k]), (bad, k)
+                    assert got["cluster_of"][bad] == -1 and bad not in got["center"] and (got["size"] >= 1).all()
+                    if not kw:
+                        assert got["size"].sum() == B - 1
+            r = model.pose_rmsd(y)
+            assert not np.isfinite(r[bad]).any() and not np.isfinite(r[:, bad]).any() and np.isfinite(np.delete(np.delete(r, bad, 0), bad, 1)).all()
+            sub = [0, 1, 2, 3]      # the non-finite coordinate is in residue 5: not compared
+            assert np.array_equal(model.pose_rmsd(y, residues=sub), model.pose_rmsd(x, residues=sub))
+        y = x.copy()
+        y[:, 0, 0, 0] = np.nan
+        for kw in ({}, {"max_clusters": 3}):
+            got = model.pose_cluster(y, 2.55, key=rng.normal(size=B).astype(np.float32), rule=rule, **kw)
+            assert got["n_clusters"] == 0 and got["center"].size == 0 and got["size"].size == 0 and (got["cluster_of"] == -1).all()
+
+
 def test_two_calls_are_bitwise_the_same(model):
     rng = np.random.default_rng(11)
     x = _rigid(_ligand(80), 700, rng)

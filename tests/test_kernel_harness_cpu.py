@@ -12,6 +12,7 @@ import pytest
 
 import dense_harness
 import edge_harness
+import ensemble_harness
 import geom_harness
 import heads_harness
 import kernel_harness as kh
@@ -20,16 +21,16 @@ import pose_harness
 from kernel_harness import HIP_INVALID_VALUE, HIP_SUCCESS, Out
 
 MODULES = {"dense": dense_harness, "edge": edge_harness, "heads": heads_harness, "geom": geom_harness, "metrics": metrics_harness,
-           "pose": pose_harness}
+           "pose": pose_harness, "ensemble": ensemble_harness}
 
 
 @pytest.mark.parametrize("name", sorted(MODULES))
 def test_call_record_layout(name, tmp_path_factory):
-    """Constructing the Harness asserts kh_call_bytes() == sizeof(Call): a field added on one side only is caught in all six."""
+    """Constructing the Harness asserts kh_call_bytes() == sizeof(Call): a field added on one side only is caught in all seven."""
     m = MODULES[name]
     h = m.Harness(m.compile_shim(tmp_path_factory.mktemp(name + "_layout")))
     assert h.guard >= 1024 and C.sizeof(m.Call) > len(m.SLOTS) * C.sizeof(kh.Buf)
-    assert h.check == (name in ("metrics", "pose"))
+    assert h.check == (name in ("metrics", "pose", "ensemble"))
 
 
 @pytest.fixture(scope="module")
