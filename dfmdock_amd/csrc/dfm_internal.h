@@ -262,6 +262,9 @@ hipError_t launch_pair_dist(const float *P, const float *Q, const float4 *ca4, i
 // The distogram head reduced inside the pair kernel (k_pair_dist_sum + k_dist_finish + k_dist_mean): per-pose sums in res[B][4] =
 // {mean nll, mean nll over D < near_cut, count of those, sum of pcontact}; per-pair maps [B][R][L] only where a pointer is given
 // (pcontact_mean [R][L] needs pcontact).  part: pair_dist_sum_parts(R, L) * 4 doubles per trajectory.
+// Non-finite input (a NaN or an infinity in a P row, a Q row or a CA coordinate): every map entry and pose sum that the float64
+// definition (dfmdock_amd/distogram.py) makes non-finite is non-finite - although fmaxf(ez2 - mean^2, 0) turns a NaN variance into 0,
+// the mean term carries it into every channel - and every other entry and every other trajectory keeps its bits.
 struct PairDistSumArgs {
     const float *P, *Q;
     const float4 *ca4;
@@ -359,6 +362,10 @@ hipError_t launch_start_pose(const StartArgs &a, int B, hipStream_t s);
 constexpr int RS_MAX_GROUPS = 4096;       // per-group arg-min in LDS (12 B per group)
 constexpr int RS_MAX_PAIRS = 1 << 20;
 constexpr int RS_SMALL = 16;              // groups of up to RS_SMALL pairs: one lane each; larger ones (listed in `big`): one wave each
+// Non-finite coordinates: restraints.evaluate is the contract.  A pair whose d^2 is NaN wins its group's arg-min wherever it stands in
+// the list (the first such pair, as np.argmin keeps it), so the group's distance is NaN and with it the energy and the step of that
+// trajectory (under `apply`: its pose and updates); the group does not count as satisfied.  Other trajectories are unaffected, and
+// finite inputs take the comparisons they always took.
 struct RestraintArgs {
     const float *rec_pos;       // [R][9]  the receptor as the sampler sees it (the clash force's coordinates)
     int R, L, all_atoms;        // all_atoms: rotate about the all-backbone-atom centroid (second family, as k_heads)

@@ -710,7 +710,8 @@ hipError_t launch_clash_force(const float *rec_pos, int B, int R, int L, float *
 // One 256-thread workgroup per trajectory (the shape of k_prep_pose, so that this kernel can prepare the pose it produces for the next
 // evaluation with the same code and the same bits).  Phase 1: groups of at most RS_SMALL pairs are one lane each (serial loop: a
 // restraint set is mostly single pairs), larger groups one wave each (pairs strided over the lanes, lane-local then butterfly arg-min,
-// ties to the lower pair index); each group's (d^2, arg-min pair) goes to LDS.  Phase 2: lane t folds groups t, t + 256, ... in order,
+// ties to the lower pair index; a NaN d^2 wins wherever it stands, the first one in list order, as np.argmin has it: the group's
+// distance, the energy and the step are then NaN); each group's (d^2, arg-min pair) goes to LDS.  Phase 2: lane t folds groups t, t + 256, ... in order,
 // then the block sums the lanes in a fixed order - a trajectory's bits do not depend on B or on its place in the batch.  d^2 and every
 // sum are float64 (a group near its bound cancels d - u); the pose update is float32 with k_heads' expressions.
 __global__ __launch_bounds__(256) void k_restraint(RestraintArgs p)
@@ -746,7 +747,7 @@ __global__ __launch_bounds__(256) void k_restraint(RestraintArgs p)
                 const double dy = (double)lig[j * 9 + 4] - (double)p.rec_pos[i * 9 + 4];
                 const double dz = (double)lig[j * 9 + 5] - (double)p.rec_pos[i * 9 + 5];
                 const double d2 = dx * dx + dy * dy + dz * dz;
-                if (arg < 0 || d2 < best) { best = d2; arg = q; }
+                if (arg < 0 || d2 < best || (d2 != d2 && best == best)) { best = d2; arg = q; }      // (the first NaN wins and stays)
             }
             s_d2[g] = best; s_arg[g] = arg;
         }
@@ -760,14 +761,17 @@ __global__ __launch_bounds__(256) void k_restraint(RestraintArgs p)
                 const double dy = (double)lig[j * 9 + 4] - (double)p.rec_pos[i * 9 + 4];
                 const double dz = (double)lig[j * 9 + 5] - (double)p.rec_pos[i * 9 + 5];
                 const double d2 = dx * dx + dy * dy + dz * dz;
-                if (arg == 0x7fffffff || d2 < best) { best = d2; arg = q; }
+                if (arg == 0x7fffffff || d2 < best || (d2 != d2 && best == best)) { best = d2; arg = q; }
             }
 #pragma unroll
             for (int m = 32; m >= 1; m >>= 1) {
                 const double ob = __shfl_xor(best, m, 64);
                 const int oa = __shfl_xor(arg, m, 64);
-                // lexicographic (d^2, pair index) minimum; a lane without pairs (arg = INT_MAX) loses to any lane with one
-                if (oa != 0x7fffffff && (arg == 0x7fffffff || ob < best || (ob == best && oa < arg))) { best = ob; arg = oa; }
+                // lexicographic (d^2, pair index) minimum with NaN below every number; a lane without pairs (arg = INT_MAX) loses to
+                // any lane with one.  Finite values: ob < best || (ob == best && oa < arg), as before.
+                const bool on = ob != ob, bn = best != best;
+                const bool lower = on ? (!bn || oa < arg) : (!bn && (ob < best || (ob == best && oa < arg)));
+                if (oa != 0x7fffffff && (arg == 0x7fffffff || lower)) { best = ob; arg = oa; }
             }
             if (lane == 0) { s_d2[g] = best; s_arg[g] = arg; }
         }

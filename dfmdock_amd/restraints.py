@@ -97,7 +97,7 @@ def evaluate(groups, rec_pos, lig_pos, params: RestraintParams | None = None, ce
         pr = np.asarray(grp.pairs, np.int64).reshape(-1, 2)
         diff = x[pr[:, 1]] - y[pr[:, 0]]
         d2 = (diff[:, 0] * diff[:, 0] + diff[:, 1] * diff[:, 1]) + diff[:, 2] * diff[:, 2]
-        k = int(np.argmin(d2))      # first minimal pair
+        k = int(np.argmin(d2))      # first minimal pair; a NaN distance wins (the first one): the group's d, U and the step are then NaN
         d = float(np.sqrt(d2[k]))
         d_all.append(d)
         arg_all.append(k)

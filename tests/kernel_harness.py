@@ -1,4 +1,4 @@
-"""The binding every kernel harness shares (tests/{dense,edge,heads,geom,metrics,pose,ensemble}_harness.py over tests/kernels/harness_common.h).
+"""The binding every kernel harness shares (tests/{dense,edge,heads,geom,metrics,pose,ensemble,aux}_harness.py over tests/kernels/harness_common.h).
 
 The guard-band protocol.  A shim (tests/kernels/<name>_harness.hip) is host code that drives the shipped launchers of
 dfmdock_amd/libdfmdock_amd.so on host arrays.  One call is a ctypes record: SLOTS named buffers first, then the shim's scalars.  Every

@@ -4,6 +4,7 @@ the CPU oracle.  Every test prints the figure it asserts on."""
 import numpy as np
 import pytest
 
+import aux_harness as ah
 from conftest import complex_for, load_golden, pair_hparams
 from refine_replay import CONTACT_CUTOFF, oracle_refine_replay
 
@@ -64,6 +65,11 @@ def test_igso3_table_vs_reference(model, ref):
         assert r["sigma"] == float(ref[f"t{n}/sigma"])
         worst = max(worst, dev)
         assert dev < 1e-10, (t, dev)
+        # the derived gate of k_igso3_cdf (tests/test_gpu_aux_kernels.py; 1.5e-13 .. 2e-11, entry by entry) against the table in extended
+        # precision, and twice it against the recorded float64 table, which the same count of roundings bounds
+        ext, gate = ah.igso3_ref(r["sigma"])
+        assert (np.abs(r["cdf"] - ext) <= gate).all(), (t, float((np.abs(r["cdf"] - ext) / gate).max()))
+        assert (np.abs(r["cdf"] - ref[f"t{n}/cdf"]) <= 2 * gate).all(), (t, float((np.abs(r["cdf"] - ref[f"t{n}/cdf"]) / gate).max()))
     print(f"igso3 max cdf deviation over the 8 t: {worst:.3e}")
     again = model.igso3_table(0.1)      # cached: the same bits
     np.testing.assert_array_equal(again["cdf"], model.igso3_table(0.1)["cdf"])
@@ -93,6 +99,14 @@ def test_injected_start_vs_reference_and_oracle(prec, model, ref):
         np.testing.assert_allclose(r["init_pose"][0], ref[f"t{n}/fm_pose"], atol=3e-5)
         np.testing.assert_allclose(fm["rot"][0], rot[0], atol=2e-4)
         np.testing.assert_allclose(fm["tr"][0], tr[0], atol=2e-3)
+        # the updates are ONE fp32 rounding of float64 values a few roundings from the mirror's (tests/test_gpu_aux_kernels.py): an fp32
+        # ulp, 2 u |x|, where the float64 difference crosses a rounding boundary; the angle also moves by (table difference) / pdf, the
+        # tables within twice the gate of k_igso3_cdf and pdf >= 1e-3 at the fixture's uniforms (make_golden_igso3.py).  The mirror
+        # takes the draws as the kernel receives them: rounded to fp32
+        rot32, tr32 = RF.forward_marginal(np.float32(t), *(np.asarray(rinj[k], np.float32) for k in ("u_angle", "axis_draw", "tr_draw")))
+        dang = 2 * float(ah.igso3_ref(RF.sigma_index(np.float32(t))[1])[1].max()) / 1e-3
+        assert (np.abs(fm["rot"][0] - rot32[0]) <= 2 * ah.U * np.abs(rot32[0]) + dang).all(), (t, fm["rot"][0], rot32[0])
+        assert (np.abs(fm["tr"][0] - tr32[0]) <= 2 * ah.U * np.abs(tr32[0]) + 1e-12).all(), (t, fm["tr"][0], tr32[0])
     gx.close()
 
 
