@@ -1,4 +1,4 @@
-// dfm_host.h - private host-side plumbing shared by api.hip and api_pose.hip: the thread's last error, the HIP error and device-scope
+// dfm_host.h - private host-side plumbing shared by the api_*.hip files (the engine's: dfm_engine.h) and api_pose.hip: the thread's last error, the HIP error and device-scope
 // macros, the device block cache and the pools that draw on it, the allocator diagnostics, and the model handle.  The objects
 // behind the `extern` declarations are defined once, in api.hip.
 #pragma once

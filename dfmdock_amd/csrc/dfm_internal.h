@@ -8,6 +8,7 @@
 #include <atomic>
 
 #include "../../include/dfmdock_amd.h"
+#include "dfm_schedule.h"
 #include "dfm_walkgrid.h"
 
 namespace dfm {
@@ -158,7 +159,7 @@ struct GemmArgs {
 };
 hipError_t launch_gemm_f32(const GemmArgs &a, hipStream_t s);
 // split-bf16 (hi/lo) variant: three bf16 MFMA terms a_hi w_hi + a_hi w_lo + a_lo w_hi, ~1e-5 relative error (bound 2^-15 |A||W|^T:
-// tests/test_gpu_dense_kernels.py); Whi / Wlo = the pre-split weights as bf16 tiles [K/32][4][Nout][8] (split_bf16 in api.hip), a.W
+// tests/test_gpu_dense_kernels.py); Whi / Wlo = the pre-split weights as bf16 tiles [K/32][4][Nout][8] (split_bf16 in api_model.hip), a.W
 // and a.ldw unused.  Needs K % 32 == 0, Nout % 256 == 0, lda and ldc multiples of 4 (else hipErrorInvalidValue before any launch)
 hipError_t launch_gemm_split(const GemmArgs &a, const uint16_t *Whi, const uint16_t *Wlo, hipStream_t s);
 int gemm_rows_per_tile();   // 64: the row tile of k_gemm_split (tiles of the fused GraphNorm statistics)
@@ -269,7 +270,7 @@ struct PairDistSumArgs {
     const float *P, *Q;
     const float4 *ca4;
     int B, R, L;
-    const float *w_d, *ln_w, *ln_b, *w3f;      // w3f: to_dist.3 in MFMA fragment order, 1 / SILU_S folded in (pack_dist_w3f in api.hip)
+    const float *w_d, *ln_w, *ln_b, *w3f;      // w3f: to_dist.3 in MFMA fragment order, 1 / SILU_S folded in (dfm_model_create in api_model.hip)
     int contact_bins;
     float near_cut;
     float *pair_nll, *pcontact, *edist, *pcontact_mean;
@@ -280,9 +281,8 @@ hipError_t launch_pair_dist_sum(const PairDistSumArgs &a, hipStream_t s);
 hipError_t launch_pair_finish(const float *fpart, int B, int R, int L, float inv_pool, float *fvec, const float *cpart,
                               float *conf, hipStream_t s);
 
-// per-step scalars of the Euler-Maruyama update as k_heads reads them from device memory when the step loop is a replayed graph
-struct StepParams { float g2_r, g_r, hg2_r, g2_t, g_t, hg2_t, dt, sqrt_dt, rot_noise, tr_noise; uint32_t step, pad; };
-
+// (StepParams, the per-step scalars of the Euler-Maruyama update as k_heads reads them from device memory when the step loop is a
+// replayed graph: dfm_schedule.h)
 struct HeadArgs {
     const float *fvec;       // [B][L][3]
     const float4 *ca4;       // [B][N]

@@ -325,7 +325,7 @@ constexpr int SK = 32, SLD = 40;   // K per stage; LDS row stride in bf16
 
 struct GemmSplitArgs {
     GemmArgs g;
-    const uint16_t *Whi, *Wlo;   // [K/32][4][Nout][8] bf16 hi / lo (split_bf16 in api.hip)
+    const uint16_t *Whi, *Wlo;   // [K/32][4][Nout][8] bf16 hi / lo (split_bf16 in api_model.hip)
 };
 
 __device__ inline uint32_t pack2(__bf16 a, __bf16 b)

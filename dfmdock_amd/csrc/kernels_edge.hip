@@ -216,7 +216,7 @@ __device__ inline uint16_t bf16_bits(float x) { return __builtin_bit_cast(uint16
 // x' = SILU_S * x is (x' / SILU_S) / (1 + exp2(x')), i.e. exp2 -> +1 -> rcp -> mul on x' and a constant factor 1 / SILU_S
 // that the next linear stage absorbs:
 //   producer   pre' = S * (A_i + Bm_j + w_r r^2 + table rows)   (tables, w_r, [Wa|Wb] and b1 are scaled on the host / in the
-//              producing GEMM: api.hip)                          m' = pre' / (1 + exp2(pre')) = S * m
+//              producing GEMM: api_model.hip)                   m' = pre' / (1 + exp2(pre')) = S * m
 //   contraction acc' = W2 m' + S b2 = S * (W2 m + b2)            (the weights are untouched)
 //   epilogue   m2' = acc' / (1 + exp2(acc')) = S * m2 ;  gate = 1 / (1 + exp2(att_w . m2' + S att_b)) ;
 //              agg = (1 / S) * sum_rows gate * m2' ;  stored messages = gate * m2' = S * (gated message)
@@ -1407,11 +1407,11 @@ static EdgeKArgs to_kargs(const EdgeArgs &a)
     k.Wc1t = w->Wc1t; k.bc1 = w->bc1; k.wc2 = w->wc2;
     k.agg = a.agg; k.last = a.last; k.fout = a.fout; k.mbuf = a.mbuf; k.stamp = a.stamp; k.split = 0;
     k.node0 = a.lig_only ? a.R : 0; k.nodes = a.lig_only ? a.N - a.R : a.N;
-    k.no_agg = a.lig_only ? 1 : 0;      // the ligand-only last layer feeds the coordinate update alone (api.hip: no node model follows)
+    k.no_agg = a.lig_only ? 1 : 0;      // the ligand-only last layer feeds the coordinate update alone (api_forward.hip: no node model follows)
     k.Ah = a.Ah; k.range = a.range; k.task_ctr = nullptr;
     return k;
 }
-// the 16-bit MFMA kernels take the -log2(e)-scaled operands (SILU_S, api.hip)
+// the 16-bit MFMA kernels take the -log2(e)-scaled operands (SILU_S, api_model.hip)
 static EdgeKArgs to_kargs_mfma(const EdgeArgs &a, int mode)
 {
     EdgeKArgs k = to_kargs(a);

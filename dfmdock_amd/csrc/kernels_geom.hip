@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void k_knn_sample(const float4 *__restrict__ c
                                                     uint32_t seed_lo, uint32_t seed_hi, uint32_t stream_id,
                                                     int32_t *__restrict__ edges, const uint32_t *__restrict__ ctl)
 {
-    // ctl (replayed step graph, api.hip: StepCtl): the evaluation index and the call's seed come from device memory, so that the
+    // ctl (replayed step graph, api_sample.hip: ws.step_ctl): the evaluation index and the call's seed come from device memory, so that the
     // captured launch is the same node in every step and every call
     if (ctl) { stream_id = ctl[0]; seed_lo = ctl[1]; seed_hi = ctl[2]; }
     __shared__ uint32_t sh_key[4][64], sh_j[4][64];

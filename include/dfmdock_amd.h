@@ -117,7 +117,7 @@ enum {
        intra-chain residue pair instead of once per edge, trajectory and step - in layer 0 the node features are the pose-independent
        embedding, and the geometry of two residues of one chain does not change under the rigid motion of the ligand).  dfm_sample
        uses the table whenever the complex is eligible (depth >= 2, (R^2 + L^2) * 516 B and the per-batch row buffers within the
-       budgets in api.hip), whatever the batch size; dfm_score is a pure function of its arguments and uses it only on request.
+       budgets in api_complex.hip), whatever the batch size; dfm_score is a pure function of its arguments and uses it only on request.
        Inter-chain edges, and intra-chain edges whose feature bins in the pose at hand differ from the table's, go through the edge
        model as before.  Against the direct evaluation the only difference is the fp16 rounding of each stored message before the
        K-row sum (fp32 engine: fp32 rows of 1 KiB, only the ORDER of the K-row sum differs, <= 2e-5; measured: tests/test_gpu_l0_table.py).                                                                  */

@@ -1,5 +1,5 @@
 """A fixed list of calls over the whole public surface of the engine, for runs under the allocator diagnostics (DFM_ALLOC_POISON,
-DFM_ALLOC_GUARD: dfmdock_amd/csrc/api.hip).  Every call stores ALL of its outputs under a stable key; the only things left out are
+DFM_ALLOC_GUARD: dfmdock_amd/csrc/dfm_host.h).  Every call stores ALL of its outputs under a stable key; the only things left out are
 clocks (`*_last_timing`, the millisecond / cycle fields of `profile()`).
 
 Three groups - trunk, start, analysis - one child process each (`python tests/alloc_recipe.py GROUP OUT.npz`; the diagnostic switches are

@@ -2,7 +2,7 @@
 
 The shim drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so (dfm::launch_gemm_split, launch_gemm_f32, launch_gn_stats)
 under the guard-band protocol of tests/kernel_harness.py.  This module binds it and restates, in numpy, what the engine does on the
-host for these kernels: the split-bf16 weight tiles of api.hip's split_bf16 ([K/32][4][Nout][8] bf16 hi / lo) and the fp16 conversion
+host for these kernels: the split-bf16 weight tiles of api_model.hip's split_bf16 ([K/32][4][Nout][8] bf16 hi / lo) and the fp16 conversion
 f2h of dfm_device.h.
 
 Run as a script (`python dense_harness.py child SHIM IN.npz OUT.npz`) it replays a list of launches stored in IN.npz and writes every
@@ -76,7 +76,7 @@ def split_hi_lo(x):
 
 
 def split_bf16(W):
-    """api.hip split_bf16: W [Nout][K] fp32 -> (hi, lo) bf16 bits in the tile order [K/32][4][Nout][8]."""
+    """api_model.hip split_bf16: W [Nout][K] fp32 -> (hi, lo) bf16 bits in the tile order [K/32][4][Nout][8]."""
     W = np.asarray(W, np.float32)
     Nout, K = W.shape
     assert K % 32 == 0

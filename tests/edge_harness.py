@@ -2,7 +2,7 @@
 
 The shim drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so (dfm::launch_edge_bf16, launch_coord_bf16, launch_edge_f32,
 launch_edge_rows, launch_edge_rows32, launch_l0_gather, launch_l0_gather32) under the guard-band protocol of tests/kernel_harness.py.
-This module binds it and restates in numpy what api.hip's dfm_model_create does for one layer: the float64 table Td, the merged fp16 table T2b (scaled by SILU_S), the 16-bit weight fragments (pack_frags), the packed
+This module binds it and restates in numpy what api_model.hip's dfm_model_create does for one layer: the float64 table Td, the merged fp16 table T2b (scaled by SILU_S), the 16-bit weight fragments (pack_frags), the packed
 bias pairs (pack_bias), the SILU_S scalings of w_r, att_b and wc2, and pack_code.  The error bounds are derived in the docstring of
 tests/test_gpu_edge_kernels.py; edge_rows / coord_ref / f32m_rows below compute them per element.
 
@@ -76,7 +76,7 @@ class Harness(kh.KernelHarness):
         return self.lib.eh_validate(OPS.index(op), B, N, R, K, last, lig_only)
 
 
-# ---- host restatements of api.hip ---------------------------------------------------------------------------------------------
+# ---- host restatements of api_model.hip ---------------------------------------------------------------------------------------------
 def pack_code(d, om, th, ph, rp):
     d, om, th, ph, rp = (np.asarray(x, np.uint32) for x in (d, om, th, ph, rp))
     return d | (om << 6) | (th << 11) | (ph << 16) | (rp << 20)
@@ -95,7 +95,7 @@ def frag_order(W):
 
 
 def pack_frags(W, f16):
-    """api.hip pack_frags: 16-bit B-operand fragments of W [256 out][256 in], bits [16][8][64][8]."""
+    """api_model.hip pack_frags: 16-bit B-operand fragments of W [256 out][256 in], bits [16][8][64][8]."""
     f = frag_order(np.asarray(W, np.float32))
     return np.ascontiguousarray(dh.f2h(f) if f16 else dh.to_bf16_bits(f))
 
@@ -111,7 +111,7 @@ def unpack_frags(bits, f16):
 
 
 def pack_bias(bias, f16):
-    """api.hip pack_bias: SILU_S * bias as (hi | lo << 16) pairs, [8 n-tiles][64 lanes], lanes 32..63 zero."""
+    """api_model.hip pack_bias: SILU_S * bias as (hi | lo << 16) pairs, [8 n-tiles][64 lanes], lanes 32..63 zero."""
     x = (np.float32(S) * np.asarray(bias, np.float32)).astype(np.float32)
     if f16:
         hi = dh.f2h(x)
@@ -131,7 +131,7 @@ def unpack_bias(v, f16):
 
 
 def merged_tables(Td):
-    """api.hip T2b: fp16 of fp32(SILU_S * (row sums)) - [0, 6912): (om*24 + th)*12 + ph; 6912 + rp*40 + d.  Also the float64 sums."""
+    """api_model.hip T2b: fp16 of fp32(SILU_S * (row sums)) - [0, 6912): (om*24 + th)*12 + ph; 6912 + rp*40 + d.  Also the float64 sums."""
     om, th, ph = np.meshgrid(np.arange(24), np.arange(24), np.arange(12), indexing="ij")
     t0 = Td[40 + om.ravel()] + Td[64 + th.ravel()] + Td[88 + ph.ravel()]
     rp, d = np.meshgrid(np.arange(66), np.arange(40), indexing="ij")

@@ -1,5 +1,5 @@
 """The kernel harness of the message kernels without a GPU (tests/edge_harness.py, tests/kernels/edge_harness.hip): it builds and links
-against the library, the launchers refuse shapes their kernels cannot run before any device work, the numpy restatements of api.hip
+against the library, the launchers refuse shapes their kernels cannot run before any device work, the numpy restatements of api_model.hip
 round-trip, the task-form restatement equals edge_msg_tile_tasks, and the bound of tests/test_gpu_edge_kernels.py is tight enough to
 catch a kernel that is subtly wrong."""
 import subprocess

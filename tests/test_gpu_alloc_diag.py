@@ -1,4 +1,4 @@
-"""Every public call under the allocator's poison fills and guard bands (DFM_ALLOC_POISON, DFM_ALLOC_GUARD: dfmdock_amd/csrc/api.hip).
+"""Every public call under the allocator's poison fills and guard bands (DFM_ALLOC_POISON, DFM_ALLOC_GUARD: dfmdock_amd/csrc/dfm_host.h).
 
 By default DevPool::alloc rounds a request up to 64 KiB granules and hands out blocks that destroyed handles parked, with their old
 contents: a write a few elements past a buffer, or a read of memory that no launch of the call wrote, changes nothing that a whole-call

@@ -147,7 +147,7 @@ def main():
     os.makedirs(os.path.join(ROOT, "tools", "variants"), exist_ok=True)
     so = os.path.join(ROOT, "tools", "variants", name + ".so")
     run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, os.path.join(td, "kernels_geom.o")] +
-        [os.path.join(SRC, f) for f in ("api.o", "api_pose.o", "kernels_heads.o", "kernels_dense.o", "kernels_edge.o", "kernels_pair.o")])
+        [os.path.join(SRC, f) for f in ("api.o", "api_model.o", "api_complex.o", "api_forward.o", "api_score.o", "api_sample.o", "api_pose.o", "kernels_heads.o", "kernels_dense.o", "kernels_edge.o", "kernels_pair.o")])
     print(f"{name}: transform {transform}{'' if what is None else '=' + what}{'' if rng is None else rng} on {lines[start][:40]}: {n_pk} packed instructions in the kernel, {edits} edits -> {so}")
 
 
