@@ -191,18 +191,56 @@ def make_sticky_weights(seed: int = 4, hp: HParams = HParams(), tr_scale: float 
     Measured on syn_64_48 (48 CPU free runs, tests/): P(final energy != 0) = 1.00, energy quartiles 0.080 / 0.094 / 0.112, 26 clashes on average.
     (score_net_mlsb.py:396-411: tr_score = unit(mean f) * tr_scale(|mean f|, t); egnn.py:118-137: the coordinate update.)"""
     w = make_random_weights(seed, hp)
-
-    def const_head(prefix, target):
-        w[prefix + ".1.weight"] = np.zeros_like(w[prefix + ".1.weight"])
-        w[prefix + ".1.bias"] = np.ones_like(w[prefix + ".1.bias"])
-        silu1 = 1.0 / (1.0 + np.exp(-1.0))
-        w[prefix + ".4.weight"] = np.full_like(w[prefix + ".4.weight"], np.log(np.expm1(target)) / (hp.inner_dim * silu1))
-
-    const_head("tr_scale", tr_scale)
-    const_head("rot_scale", rot_scale)
+    _constant_scale_heads(w, hp, tr_scale, rot_scale)
     last = f"network.EGNN_{hp.depth - 1}.egcl."
     w[last + "coord_mlp.0.bias"] = np.full_like(w[last + "coord_mlp.0.bias"], coord_bias)
     w[last + "coord_mlp.2.weight"] = np.full_like(w[last + "coord_mlp.2.weight"], coord_w)
+    return w
+
+
+def _constant_scale_heads(w, hp, tr_scale, rot_scale):
+    """tr_scale / rot_scale as constant heads: LayerNorm weight 0, bias 1 -> SiLU(1) in every channel, last Linear chosen so that
+    Softplus gives the target."""
+    silu1 = 1.0 / (1.0 + np.exp(-1.0))
+    for prefix, target in (("tr_scale", tr_scale), ("rot_scale", rot_scale)):
+        w[prefix + ".1.weight"] = np.zeros_like(w[prefix + ".1.weight"])
+        w[prefix + ".1.bias"] = np.ones_like(w[prefix + ".1.bias"])
+        w[prefix + ".4.weight"] = np.full_like(w[prefix + ".4.weight"], np.log(np.expm1(target)) / (hp.inner_dim * silu1))
+
+
+def make_contact_weights(seed: int = 4, hp: HParams = HParams(), head_seed: int = 11, coord_gain: float = 4.0, coord_w: float = -0.004,
+                         coord_sd: float = 0.004, node_gain: float = 2.0, force_w: float = 0.005, force_sd: float = 0.02) -> "OrderedDict[str, np.ndarray]":
+    """A weight draw for the IN-CONTACT rollout fixtures (tests/golden/make_golden_contact.py): like the sticky draw it keeps the
+    chains together over all 40 steps, but its force head follows the network instead of a constant.  make_sticky_weights' coordinate
+    head is clamp-saturated or bias-dominated on every last-layer edge, so a 2 % error in a message weight moves f by 1e-4 at most
+    and a whole rollout by milli-Angstroms; here
+      * family 0: the sticky draw at coord_w = -0.004 with, in the last layer, coord_mlp.0.bias = 0, coord_mlp.0.weight times
+        coord_gain and coord_mlp.2.weight = coord_w + coord_sd N(0,1) (PCG64(head_seed)): the per-edge coordinate weight is a
+        zero-bias function of the edge message, negative on average (every edge still pulls its node towards the neighbour) and
+        well inside the +-2 clamp;
+      * family 1 (no coordinate update; f_j = mean_i unit(rec_i - lig_j) * to_force[i,j], egnn_net.py:465-467): the same constant
+        tr_scale / rot_scale heads and to_force.3.weight = force_w + force_sd N(0,1), i.e. a pair force that is attractive on
+        average and varies with both residues' embeddings (at force_w = 0.02 the constant part hides the defect: 4e-4 to 6e-4 on f);
+      * both: node_mlp.3.weight of every layer times node_gain.  make_random_weights keeps the residual branch at 0.5 / sqrt(H), so
+        h is dominated by the embedding and a 2 % defect in EGNN_2's edge weights moved f by only 6e-4 on syn_64_48 at coord_gain 8,
+        node_gain 1 (whatever the seed); with gains 4 and 2 it moves f by >= 1.2e-3 on every complex of the fixtures and at most
+        1.2 % of the last-layer edges reach the clamp."""
+    rng = np.random.Generator(np.random.PCG64(head_seed))
+    if hp.family == 0:
+        w = make_sticky_weights(seed, hp, coord_w=coord_w)
+        last = f"network.EGNN_{hp.depth - 1}.egcl."
+        w[last + "coord_mlp.0.bias"] = np.zeros_like(w[last + "coord_mlp.0.bias"])
+        w[last + "coord_mlp.0.weight"] = (w[last + "coord_mlp.0.weight"] * np.float32(coord_gain)).astype(np.float32)
+        shape = w[last + "coord_mlp.2.weight"].shape
+        w[last + "coord_mlp.2.weight"] = (coord_w + coord_sd * rng.standard_normal(shape)).astype(np.float32)
+    else:
+        w = make_random_weights(seed, hp)
+        _constant_scale_heads(w, hp, 0.1, 0.2)
+        shape = w["to_force.3.weight"].shape
+        w["to_force.3.weight"] = (force_w + force_sd * rng.standard_normal(shape)).astype(np.float32)
+    for name in w:
+        if name.endswith("node_mlp.3.weight"):
+            w[name] = (w[name] * np.float32(node_gain)).astype(np.float32)
     return w
 
 
