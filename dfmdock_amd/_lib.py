@@ -56,6 +56,7 @@ EXPORTS = [
     "dfm_pairpot_create", "dfm_pairpot_destroy", "dfm_pairpot_info", "dfm_pose_pairpot", "dfm_pose_pairpot_chunked",
     "dfm_pairpot_last_timing", "dfm_pairpot_last_phases",
     "dfm_score_distogram", "dfm_distogram_last_timing",
+    "dfm_pose_fit", "dfm_pose_fit_chunked", "dfm_fit_last_timing",
 ]
 
 
@@ -154,6 +155,10 @@ class HbondOutC(C.Structure):
 
 class PairpotOutC(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_int64)) for n in ("energy_q", "n_pairs", "lig_q")] + [("counts", I32P)]
+
+
+class FitOutC(C.Structure):
+    _fields_ = [("rot", F32P), ("tr", F32P), ("rmsd", C.POINTER(C.c_double)), ("rec_rmsd_or_null", C.POINTER(C.c_double))]
 
 
 class DistogramParamsC(C.Structure):
@@ -282,6 +287,9 @@ def lib():
     L.dfm_score_distogram.argtypes = [C.c_void_p, C.c_int, F32P, F32P, I32P, C.c_uint64, C.c_uint32, C.POINTER(DistogramParamsC),
                                       C.POINTER(DistogramOutC)]
     L.dfm_distogram_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_pose_fit.argtypes = [C.c_void_p, C.c_int, C.c_int, F32P, F32P, C.c_int, F32P, F32P, F32P, C.POINTER(FitOutC)]
+    L.dfm_pose_fit_chunked.argtypes = [C.c_void_p, C.c_int, C.c_int, F32P, F32P, C.c_int, F32P, F32P, F32P, C.c_int, C.POINTER(FitOutC)]
+    L.dfm_fit_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_trim_cache.argtypes = [C.c_int]
     L.dfm_trim_cache.restype = C.c_longlong
     L.dfm_alloc_diag.argtypes = [C.POINTER(C.c_int64)]

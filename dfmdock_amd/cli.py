@@ -20,6 +20,8 @@
     python -m dfmdock_amd dock|refine ... --hbonds [--bsa] [--hbond-cutoff 3.5] [--hbond-angle 90] [--salt-cutoff 4.0] [--hbond-residues FILE]
     python -m dfmdock_amd dock|refine ... --distogram [--rank distogram] [--distogram-map map.npz] [--distogram-restraints FILE] [--distogram-t 1e-3]
     python -m dfmdock_amd dock|refine ... --clash-screen [--clash-filter] [--clash-cutoff 3.0] [--contact-cutoff 5.0] [--clash-residues FILE]
+    python -m dfmdock_amd rescore REC.pdb LIG.pdb --ckpt model_0.ckpt --features F.npz --decoys D.pdb [D2.pdb ...] | --coords C.npz | --poses P.npz
+                                  [--decoy-chains A B] [--fit-tolerance 0.1] [--score-t 1e-3] [--scores scores.csv] [--top-k K [--refine-t T]] [every dock analysis]
 
   dock       <- src/inference_single.py:1-12 -> inference() (src/inference_base.py:601-670): num_samples (120) trajectories of
                 num_steps (40), the minimum-energy one applied to the all-atom ligand, `output.pdb` written, {"energy": E} printed.
@@ -108,6 +110,14 @@
              most probable contacts as a restraint file (upper bound --restraint-upper, weight = probability) for a second, guided run;
              `--distogram-t T` (default 1e-3) is the diffusion time of the evaluation.  A first-family checkpoint is refused before
              sampling.
+  rescore    no reference counterpart as a command: decoys made elsewhere (another docking program, an earlier run) ranked with the model's
+             energy head and screened, clustered and described with every analysis of `dock`.  The decoys are rigid images of the ligand
+             PDB: `--decoys` (PDB files, every MODEL; matched to the input residue by residue, `--decoy-chains` when the chain ids
+             differ; a model that carries the receptor may sit in any frame), `--coords` (backbones) or `--poses` (rot_update /
+             tr_update as they are).  Coordinates are fitted on the GPU (dfmdock_amd/fit.py, dfm_pose_fit); a decoy whose fit leaves more
+             than --fit-tolerance (0.1 A) backbone RMSD is rejected: no energy, never kept, never a model.  The energy is the model's at
+             --score-t (default: the end of the sampler's grid).  Same output contract as `dock`, plus `fit` and `num_decoys`;
+             `--scores FILE.csv` lists every decoy; `--top-k K --refine-t T` hands the cluster centres to the local refinement.
   selfcheck  no reference counterpart: dfm_complex_selfcheck on the pair (what `dock` and `sweep` run once per complex anyway).
 
 --ckpt takes the Lightning checkpoint the reference loads (src/inference_base.py:611-616; read without Lightning / omegaconf by
@@ -117,6 +127,7 @@ Everything computes on the MI355X through the C ABI; without a GPU the commands 
 from __future__ import annotations
 
 import argparse
+import csv
 import json
 import os
 import sys
@@ -228,6 +239,18 @@ def _add_surface(p):
                    help="with --bsa: sphere points per atom, a multiple of 64 in 64 .. 256 (default 128)")
 
 
+def _add_models(p, what):
+    """--top-k and what goes with it, for dock and rescore."""
+    p.add_argument("--top-k", type=int, default=None, metavar="K",
+                   help=f"cluster the {what} and write the first K cluster centres as <out stem>_1.pdb ... _K.pdb")
+    p.add_argument("--cluster-radius", type=float, default=4.0, help="with --top-k: ligand RMSD radius of a cluster (A)")
+    p.add_argument("--cluster-rule", default="energy", choices=["energy", "size"],
+                   help="with --top-k: leader clustering in key order (default) or greedy by cluster size")
+    p.add_argument("--refine-t", type=float, default=None, metavar="T",
+                   help="with --top-k: refine every cluster centre locally from t_begin = T (one batched call)")
+    p.add_argument("--refine-samples", type=int, default=8, metavar="n", help="with --refine-t: trajectories per cluster centre")
+
+
 def _add_common(p):
     p.add_argument("--ckpt", required=True, help="Lightning checkpoint or bare state_dict (torch.save)")
     p.add_argument("--num-steps", type=int, default=40)
@@ -255,14 +278,7 @@ def build_parser():
     d.add_argument("--restraint-rank", default="satisfied", choices=["satisfied", "energy"],
                    help="with --restraints: keep the minimum energy among the trajectories satisfying the most groups (default) "
                         "or the plain minimum energy")
-    d.add_argument("--top-k", type=int, default=None, metavar="K",
-                   help="cluster the trajectories and write the first K cluster centres as <out stem>_1.pdb ... _K.pdb")
-    d.add_argument("--cluster-radius", type=float, default=4.0, help="with --top-k: ligand RMSD radius of a cluster (A)")
-    d.add_argument("--cluster-rule", default="energy", choices=["energy", "size"],
-                   help="with --top-k: leader clustering in key order (default) or greedy by cluster size")
-    d.add_argument("--refine-t", type=float, default=None, metavar="T",
-                   help="with --top-k: refine every cluster centre locally from t_begin = T (one batched call)")
-    d.add_argument("--refine-samples", type=int, default=8, metavar="n", help="with --refine-t: trajectories per cluster centre")
+    _add_models(d, "trajectories")
     _add_native(d)
     for a in ANALYSES:
         a.add(d)
@@ -281,6 +297,28 @@ def build_parser():
     for a in ANALYSES:
         a.add(r)
     _add_common(r)
+    x = sub.add_parser("rescore", help="rank, screen and describe decoys made elsewhere with the model's energy and every analysis of dock")
+    x.add_argument("pdb_1", help="receptor PDB")
+    x.add_argument("pdb_2", help="ligand PDB: the conformation the decoys are rigid images of")
+    x.add_argument("--features", required=True, help=".npz with rec_esm / lig_esm [n,1280] (or rec_x / lig_x [n,1301])")
+    src = x.add_mutually_exclusive_group(required=True)
+    src.add_argument("--decoys", nargs="+", default=None, metavar="FILE.pdb", help="decoy files: every MODEL of every file, in order")
+    src.add_argument("--coords", default=None, metavar="FILE.npz", help="decoy backbones: lig_pos [P,L,3,3] and optionally rec_pos [P,R,3,3]")
+    src.add_argument("--poses", default=None, metavar="FILE.npz", help="decoys as poses: rot_update [P,3] and tr_update [P,3], taken as they are")
+    x.add_argument("--decoy-chains", nargs=2, default=None, metavar=("RCHAINS", "LCHAINS"),
+                   help="with --decoys: the chain ids of the receptor and of the ligand in the decoy files (default: those of the input files)")
+    x.add_argument("--fit-tolerance", type=float, default=0.1, metavar="A",
+                   help="a decoy whose rigid fit leaves a larger backbone RMSD is rejected (default 0.1)")
+    x.add_argument("--score-t", type=float, default=None, metavar="T", help="time of the energy evaluation (default: the end of the sampler's grid)")
+    x.add_argument("--out", default="output.pdb")
+    x.add_argument("--json", default=None, help="also write the result line to this file")
+    x.add_argument("--scores", default=None, metavar="FILE.csv",
+                   help="one row per decoy: source, model, fit_rmsd, rec_rmsd, rejected, energy, rank")
+    _add_models(x, "decoys")
+    _add_native(x)
+    for a in ANALYSES:
+        a.add(x)
+    _add_common(x)
     s = sub.add_parser("sweep", help="sample every complex of a DB5-style directory (inference_mlsb.py run_sampling)")
     s.add_argument("--db5", required=True, help="directory of <id>.pt files (+ optional test.txt with the ids to run)")
     s.add_argument("--num-samples", type=int, default=40)
@@ -318,16 +356,24 @@ def build_parser():
 def parse_args(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
-    if args.cmd == "dock" and args.refine_t is not None and args.top_k is None:
+    if args.cmd in ("dock", "rescore") and args.refine_t is not None and args.top_k is None:
         ap.error("--refine-t refines the cluster centres: it needs --top-k")
+    if args.cmd == "rescore":
+        if args.decoy_chains is not None and args.decoys is None:
+            ap.error("--decoy-chains names the chains of --decoys files")
+        if not (args.fit_tolerance >= 0.0):
+            ap.error("--fit-tolerance must be >= 0")
+        for path in (args.decoys or []) + [p for p in (args.coords, args.poses) if p]:
+            if not os.path.isfile(path):
+                ap.error(f"{path}: no such file")
     if args.cmd == "sweep" and args.step_metrics is not None:
         args.metrics = "gpu"
-    if args.cmd in ("dock", "refine"):
+    if args.cmd in ("dock", "refine", "rescore"):
         for a in ANALYSES:
             a.check(ap, args)
     elif getattr(args, "rank", None) == "pairpot":
         ap.error("--rank pairpot is offered by dock and refine")
-    if args.cmd in ("dock", "refine", "sweep"):
+    if args.cmd in ("dock", "refine", "rescore", "sweep"):
         if args.consensus_top is not None and not args.consensus:
             ap.error("--consensus-top selects the members of the consensus ensemble: it needs --consensus")
         args.consensus_top = 1.0 if args.consensus_top is None else args.consensus_top
@@ -821,6 +867,42 @@ ANALYSES = (
 )
 
 
+def _pair_kwargs(args, model, kw, models):
+    """What dock, refine and rescore give their driver alike, added to kw: the model / refinement options (`models`: the command has
+    them), --native and the keywords of every analysis."""
+    if models and args.top_k is not None:
+        kw.update(top_k=args.top_k, cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule)
+    if models and args.refine_t is not None:
+        kw.update(refine_t=args.refine_t, refine_samples=args.refine_samples)
+    if args.native:
+        kw.update(native=load_native(args.native))
+    for a in ANALYSES:
+        kw.update(a.kwargs(args, model))
+    return kw
+
+
+def _pose_entries(res):
+    """The kept pose's entries of a result line."""
+    return dict(rot_update=[float(v) for v in res["rot_update"]], tr_update=[float(v) for v in res["tr_update"]],
+                selfcheck_ok=None if res["selfcheck"] is None else bool(res["selfcheck"]["ok"]))
+
+
+def _finish_line(args, model, res, rec, lig, line, kw, models, native_extra=()):
+    """The tail of a result line - models, refinement, --native metrics (and the command's own `native_extra` entries of res), every
+    analysis' entries and files - and the line itself on stdout."""
+    from . import driver
+    if models and args.top_k is not None:
+        line.update(models=[dict(m, path=os.path.abspath(driver.model_path(args.out, m["rank"]))) for m in res["models"]],
+                    cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule)
+    if models and args.refine_t is not None:
+        line.update(refine_t=args.refine_t, refine_samples=args.refine_samples)
+    if args.native:
+        line.update(metrics=res["metrics"], **{k: res[k] for k in native_extra})
+    for a in ANALYSES:
+        a.outputs(args, model, res, rec, lig, line, kw)
+    print(json.dumps(line), flush=True)
+
+
 def cmd_pair(args):
     """dock and refine: one body; they differ in their own driver keywords, their own entries of the line and what --json adds."""
     from . import driver
@@ -831,35 +913,18 @@ def cmd_pair(args):
     if args.restraints:
         from .restraints import read_restraints
         kw.update(restraints=read_restraints(args.restraints, rec, lig), **({"restraint_rank": args.restraint_rank} if dock else {}))
-    if dock and args.top_k is not None:
-        kw.update(top_k=args.top_k, cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule)
-    if dock and args.refine_t is not None:
-        kw.update(refine_t=args.refine_t, refine_samples=args.refine_samples)
-    if args.native:
-        kw.update(native=load_native(args.native))
-    for a in ANALYSES:
-        kw.update(a.kwargs(args, model))
+    _pair_kwargs(args, model, kw, models=dock)
     res = (driver.dock_pair if dock else driver.refine_pair)(
         model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed, precision=args.precision,
         out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, **kw)
     line = {"energy": res["energy"], "output": os.path.abspath(args.out), "num_samples": args.num_samples, "precision": res["precision"]}
     if not dock:
         line.update(t_begin=res["t_begin"], perturb=not args.no_perturb, index=res["index"])
-    line.update(rot_update=[float(v) for v in res["rot_update"]], tr_update=[float(v) for v in res["tr_update"]],
-                selfcheck_ok=None if res["selfcheck"] is None else bool(res["selfcheck"]["ok"]))
+    line.update(_pose_entries(res))
     if dock and args.restraints:
         line.update(restraints=res["restraints"], restraints_satisfied=res["restraints_satisfied"],
                     restraint_energy=res["restraint_energy"], restraint_rank=res["restraint_rank"], index=res["index"])
-    if dock and args.top_k is not None:
-        line.update(models=[dict(m, path=os.path.abspath(driver.model_path(args.out, m["rank"]))) for m in res["models"]],
-                    cluster_radius=args.cluster_radius, cluster_rule=args.cluster_rule)
-    if dock and args.refine_t is not None:
-        line.update(refine_t=args.refine_t, refine_samples=args.refine_samples)
-    if args.native:
-        line.update(metrics=res["metrics"], **({} if dock else {"start_metrics": res["start_metrics"]}))
-    for a in ANALYSES:
-        a.outputs(args, model, res, rec, lig, line, kw)
-    print(json.dumps(line), flush=True)
+    _finish_line(args, model, res, rec, lig, line, kw, models=dock, native_extra=() if dock else ("start_metrics",))
     if args.json:
         if dock:
             extra = {"trajectories": {k: [float(x) for x in v] for k, v in res["trajectories"].items()}} if args.restraints else {}
@@ -867,6 +932,96 @@ def cmd_pair(args):
             extra = {"energies": [float(e) for e in res["trajectories"]["energy"]]}
         with open(args.json, "w") as f:
             json.dump(dict(line, selfcheck=res["selfcheck"], **extra), f, default=float)
+    return 0
+
+
+def load_decoys(args, rec, lig):
+    """The decoys of `rescore` -> (decoys of driver.rescore_pair, [(source, model number)] per decoy)."""
+    from . import pdbio
+    if args.poses:
+        f = np.load(args.poses, allow_pickle=False)
+        for k in ("rot_update", "tr_update"):
+            if k not in f:
+                raise ValueError(f"{args.poses}: need rot_update [P,3] and tr_update [P,3]")
+        dec = {"rot_update": np.asarray(f["rot_update"], np.float32), "tr_update": np.asarray(f["tr_update"], np.float32)}
+        return dec, [(args.poses, i + 1) for i in range(dec["rot_update"].reshape(-1, 3).shape[0])]
+    L, R = len(lig["bb_coords"]), len(rec["bb_coords"])
+    if args.coords:
+        f = np.load(args.coords, allow_pickle=False)
+        if "lig_pos" not in f:
+            raise ValueError(f"{args.coords}: need lig_pos [P,{L},3,3] (and optionally rec_pos [P,{R},3,3])")
+        lp = np.asarray(f["lig_pos"], np.float32)
+        if lp.size == 0 or lp.size % (L * 9):
+            raise ValueError(f"{args.coords}: lig_pos is {lp.shape}, the ligand PDB has {L} residues with N, CA and C")
+        dec = {"lig_pos": lp.reshape(-1, L, 3, 3)}
+        if "rec_pos" in f:
+            rp = np.asarray(f["rec_pos"], np.float32)
+            if rp.size != dec["lig_pos"].shape[0] * R * 9:
+                raise ValueError(f"{args.coords}: rec_pos is {rp.shape}, expected ({dec['lig_pos'].shape[0]}, {R}, 3, 3)")
+            dec["rec_pos"] = rp.reshape(-1, R, 3, 3)
+        return dec, [(args.coords, i + 1) for i in range(dec["lig_pos"].shape[0])]
+    chains = args.decoy_chains or (None, None)
+    ligs, recs, names = [], [], []
+    for path in args.decoys:
+        models = pdbio.read_models(path)
+        if not models:
+            raise ValueError(f"{path}: no ATOM records")
+        for i, atoms in enumerate(models):
+            lb, rb = pdbio.match_model(atoms, rec, lig, chains[0], chains[1], source=path, model=i + 1)
+            ligs.append(lb)
+            recs.append(rb)
+            names.append((path, i + 1))
+    dec = {"lig_pos": np.asarray(ligs, np.float32)}
+    if any(r is not None for r in recs):      # a model without a receptor is in the input's frame: it travels with the input's receptor
+        dec["rec_pos"] = np.asarray([rec["bb_coords"] if r is None else r for r in recs], np.float32)
+    return dec, names
+
+
+def write_scores(path, names, res):
+    """--scores: one row per decoy, in input order; rank: its place by the key the run clustered by (1 = best), empty when rejected."""
+    from .cluster import rank_order
+    fd, energy = res["fit_data"], res["trajectories"]["energy"]
+    key = np.asarray(res["key"], np.float64)
+    rank = np.empty(len(names), np.int64)
+    rank[rank_order(key, len(names))] = np.arange(1, len(names) + 1)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["source", "model", "fit_rmsd", "rec_rmsd", "rejected", "energy", "rank"])
+        for i, (src, m) in enumerate(names):
+            rej = bool(fd["rejected"][i])
+            w.writerow([src, m, repr(float(fd["rmsd"][i])), "" if fd["rec_rmsd"] is None else repr(float(fd["rec_rmsd"][i])), int(rej),
+                        "" if rej else repr(float(energy[i])), "" if rej or np.isnan(key[i]) else int(rank[i])])
+
+
+def cmd_rescore(args):
+    """rescore: cmd_pair's line for decoys that were made elsewhere, plus `fit` and `num_decoys`.  What is wrong with the decoys - a
+    file that does not match the pair, an array of the wrong shape, no rigid image among them - is one line on stderr and status 1."""
+    from . import driver
+    model, _ = load_model(args)
+    rec, lig, rec_x, lig_x = load_pair(args.pdb_1, args.pdb_2, args.features, model.hp.lm_embed_dim)
+    try:
+        decoys, names = load_decoys(args, rec, lig)
+    except ValueError as e:
+        print(f"rescore: {e}", file=sys.stderr)
+        return 1
+    kw = _pair_kwargs(args, model, {} if args.score_t is None else dict(t=args.score_t), models=True)
+    try:
+        res = driver.rescore_pair(model, rec, lig, rec_x, lig_x, decoys, fit_tolerance=args.fit_tolerance, num_steps=args.num_steps,
+                                  seed=args.seed, precision=args.precision, out_pdb=args.out, max_batch=args.max_batch,
+                                  selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, **kw)
+    except driver.AllRejected as e:
+        print(f"rescore: {e}", file=sys.stderr)
+        return 1
+    k = res["index"]
+    line = {"energy": res["energy"], "output": os.path.abspath(args.out), "num_decoys": len(names), "precision": res["precision"],
+            "t": res["t"], "index": k, "source": names[k][0], "model": names[k][1], "fit": res["fit"]}
+    line.update(_pose_entries(res))
+    _finish_line(args, model, res, rec, lig, line, kw, models=True)
+    if args.scores:
+        write_scores(args.scores, names, res)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(dict(line, selfcheck=res["selfcheck"], energies=[float(e) for e in res["trajectories"]["energy"]]), f, default=float)
     return 0
 
 
@@ -958,4 +1113,4 @@ def cmd_selfcheck(args):
 
 def main(argv=None):
     args = parse_args(argv)
-    return {"dock": cmd_pair, "sweep": cmd_sweep, "selfcheck": cmd_selfcheck, "refine": cmd_pair}[args.cmd](args)
+    return {"dock": cmd_pair, "sweep": cmd_sweep, "selfcheck": cmd_selfcheck, "refine": cmd_pair, "rescore": cmd_rescore}[args.cmd](args)

@@ -1,5 +1,5 @@
 // api_pose.hip - the pose calls of the C ABI (include/dfmdock_amd.h): pose clustering, docking metrics, consensus contacts and the six
-// rigid-pose families (sterics, buried surface, interface energy, residue contacts, hydrogen bonds, tabulated pair potential).  Every call owns a non-blocking
+// rigid-pose families (sterics, buried surface, interface energy, residue contacts, hydrogen bonds, tabulated pair potential) and the rigid pose fit.  Every call owns a non-blocking
 // stream and its temporaries; the handles are bound to the model handle's device only.
 #include <algorithm>
 #include <climits>
@@ -21,7 +21,7 @@ using namespace dfm;
 // several host threads, and next to that model's complex handles, do not share any state.
 // the two millisecond figures of this thread's last call of each kind, behind the dfm_*_last_timing getters: k_pose_dist and the
 // clustering kernels for MS_CLUSTER, host-to-device copies and kernels for the others
-enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_IFACE, MS_RESCON, MS_HBOND, MS_PAIRPOT, MS_KINDS };
+enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_IFACE, MS_RESCON, MS_HBOND, MS_PAIRPOT, MS_FIT, MS_KINDS };
 static thread_local double g_last_ms[MS_KINDS][2] = {};
 
 static void set_last_ms(int kind, double a, double b)
@@ -203,12 +203,22 @@ struct PoseChunks {
         if (!out) return fail(DFM_E_INVALID, "out is NULL");
         if (P_ < 1 || (max_P && P_ > max_P)) return fail(DFM_E_INVALID, max_P ? "need 1 <= P <= " + std::to_string(max_P) : std::string("need P >= 1"));
         if (chunk_poses < 0) return fail(DFM_E_INVALID, "chunk_poses must be >= 0");
-        ds.emplace(h->device);
-        if (ds->err != hipSuccess) return fail(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds->err));
-        HIPCHK(c.open());
-        P = P_; rot = rot_; tr = tr_;
+        if (int rc = open(h->device, P_)) return rc;
+        rot = rot_; tr = tr_;
         return DFM_OK;
     }
+    // the device scope, stream and temporaries alone, for a call whose poses are not (rot, tr) (dfm_pose_fit): it uploads between
+    // copies_begin and copies_done, and from kernels_done on the chunk runs as every other
+    int open(int device, int P_)
+    {
+        ds.emplace(device);
+        if (ds->err != hipSuccess) return fail(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds->err));
+        HIPCHK(c.open());
+        P = P_;
+        return DFM_OK;
+    }
+    hipError_t copies_begin() { return hipEventRecord(c.ev[0], c.s); }
+    hipError_t copies_done() { return hipEventRecord(c.ev[1], c.s); }
     // the chunk: `want` poses if one was asked for (at most the launch's `cap`), else `fallback`
     int alloc(int want, int fallback, int cap)
     {
@@ -220,10 +230,10 @@ struct PoseChunks {
     }
     hipError_t upload(int p0, int n)
     {
-        hipError_t e = hipEventRecord(c.ev[0], c.s);
+        hipError_t e = copies_begin();
         if (e == hipSuccess) e = hipMemcpyAsync(d_rot, rot + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s);
         if (e == hipSuccess) e = hipMemcpyAsync(d_tr, tr + (size_t)p0 * 3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c.s);
-        if (e == hipSuccess) e = hipEventRecord(c.ev[1], c.s);
+        if (e == hipSuccess) e = copies_done();
         return e;
     }
     hipError_t mark_zeroed()
@@ -1441,3 +1451,73 @@ extern "C" int dfm_pairpot_last_phases(double *zero_ms, double *walk_ms, double 
 {
     return last_phases(MS_PAIRPOT, zero_ms, walk_ms, finish_ms);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Rigid pose fit (kernels_fit.hip): from decoy coordinates back to the sampler's (rot_update, tr_update).  Bound to the model handle's
+// device only, like the clustering calls; the call's scaffold and chunk loop are PoseChunks', its poses are coordinates.
+constexpr size_t FIT_CHUNK_BYTES = (size_t)64 << 20;      // poses uploaded and fitted per chunk of a call
+constexpr int FIT_MAX_CHUNK = 1 << 20;                    // poses per launch
+
+extern "C" int dfm_pose_fit_chunked(dfm_model *m, int P, int L, const float *lig_ref, const float *lig_pos, int R, const float *rec_ref,
+                                    const float *rec_pos, const float center[3], int chunk_poses, dfm_fit_out *out)
+{
+    if (!m) return fail(DFM_E_INVALID, "m is NULL");
+    if (!lig_ref) return fail(DFM_E_INVALID, "lig_ref is NULL");
+    if (!lig_pos) return fail(DFM_E_INVALID, "lig_pos is NULL");
+    if (!center) return fail(DFM_E_INVALID, "center is NULL");
+    if (!out || !out->rot || !out->tr || !out->rmsd) return fail(DFM_E_INVALID, "out, out->rot, out->tr or out->rmsd is NULL");
+    if (P < 1) return fail(DFM_E_INVALID, "need P >= 1");
+    if (L < 1) return fail(DFM_E_INVALID, "need L >= 1");
+    if ((rec_ref == nullptr) != (rec_pos == nullptr)) return fail(DFM_E_INVALID, "rec_ref and rec_pos must be given together");
+    const bool with_rec = rec_ref != nullptr;
+    if (with_rec && R < 1) return fail(DFM_E_INVALID, "need R >= 1 with a receptor");
+    if (with_rec && !out->rec_rmsd_or_null) return fail(DFM_E_INVALID, "out->rec_rmsd_or_null is NULL with a receptor");
+    if (chunk_poses < 0) return fail(DFM_E_INVALID, "chunk_poses must be >= 0");
+    if ((int64_t)L * 9 > INT32_MAX / 2 || (with_rec && (int64_t)R * 9 > INT32_MAX / 2)) return fail(DFM_E_INVALID, "L or R too large");
+    const int Rn = with_rec ? R : 0, chains = with_rec ? 2 : 1;
+    PoseChunks ch;
+    if (int rc = ch.open(m->device, P)) return rc;
+    PoseCall &c = ch.c;
+    const size_t lig_n = (size_t)L * 9, rec_n = (size_t)Rn * 9, per_pose = (lig_n + rec_n) * sizeof(float);
+    const int by_memory = (int)std::min<size_t>(FIT_MAX_CHUNK, std::max<size_t>(1, FIT_CHUNK_BYTES / per_pose));
+    const int Pc = std::min(P, chunk_poses > 0 ? std::min(chunk_poses, FIT_MAX_CHUNK) : by_memory);
+    // the shift is the rotation centre itself: an fp32 triple, so p - o is exact in fp64, and tr is the shifted frame's t
+    const double o[3] = {(double)center[0], (double)center[1], (double)center[2]};
+    float *d_lref = nullptr, *d_rref = nullptr, *X = nullptr, *Xr = nullptr, *d_rot = nullptr, *d_tr = nullptr;
+    double *sums = nullptr, *xf = nullptr, *d_rmsd = nullptr;      // d_rmsd: rmsd [Pc] | rec_rmsd [Pc]
+    HIPCHK(c.tmp.upload_async(&d_lref, lig_ref, lig_n, c.s));
+    if (with_rec) HIPCHK(c.tmp.upload_async(&d_rref, rec_ref, rec_n, c.s));
+    HIPCHK(c.tmp.alloc(&X, (size_t)Pc * lig_n));
+    if (with_rec) HIPCHK(c.tmp.alloc(&Xr, (size_t)Pc * rec_n));
+    HIPCHK(c.tmp.alloc(&sums, (size_t)Pc * chains * 15));
+    HIPCHK(c.tmp.alloc(&xf, (size_t)Pc * 24));
+    HIPCHK(c.tmp.alloc(&d_rot, (size_t)Pc * 3));
+    HIPCHK(c.tmp.alloc(&d_tr, (size_t)Pc * 3));
+    HIPCHK(c.tmp.alloc(&d_rmsd, (size_t)Pc * 2));
+    const FitChain lig = {X, d_lref, L}, rec = {Xr, d_rref, Rn};
+    for (int p0 = 0; p0 < P; p0 += Pc) {
+        const int n = std::min(Pc, P - p0);
+        HIPCHK(ch.copies_begin());
+        HIPCHK(hipMemcpyAsync(X, lig_pos + (size_t)p0 * lig_n, (size_t)n * lig_n * sizeof(float), hipMemcpyHostToDevice, c.s));
+        if (with_rec) HIPCHK(hipMemcpyAsync(Xr, rec_pos + (size_t)p0 * rec_n, (size_t)n * rec_n * sizeof(float), hipMemcpyHostToDevice, c.s));
+        HIPCHK(ch.copies_done());
+        HIPCHK(launch_fit_reduce(lig, rec, n, o, sums, c.s));
+        HIPCHK(launch_fit_solve(sums, L, Rn, n, xf, d_rot, d_tr, c.s));
+        HIPCHK(launch_fit_resid(lig, rec, xf, n, o, d_rmsd, d_rmsd + Pc, c.s));
+        HIPCHK(ch.kernels_done());
+        HIPCHK(hipMemcpyAsync(out->rot + (size_t)p0 * 3, d_rot, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(hipMemcpyAsync(out->tr + (size_t)p0 * 3, d_tr, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(hipMemcpyAsync(out->rmsd + p0, d_rmsd, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c.s));
+        if (with_rec) HIPCHK(hipMemcpyAsync(out->rec_rmsd_or_null + p0, d_rmsd + Pc, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(ch.finish());
+    }
+    return ch.done(MS_FIT);
+}
+
+extern "C" int dfm_pose_fit(dfm_model *m, int P, int L, const float *lig_ref, const float *lig_pos, int R, const float *rec_ref,
+                            const float *rec_pos, const float center[3], dfm_fit_out *out)
+{
+    return dfm_pose_fit_chunked(m, P, L, lig_ref, lig_pos, R, rec_ref, rec_pos, center, 0, out);
+}
+
+DFM_LAST_TIMING(dfm_fit_last_timing, MS_FIT)

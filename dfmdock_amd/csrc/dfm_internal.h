@@ -429,6 +429,23 @@ hipError_t launch_metrics_finish(const MetricsChain &lig, const MetricsChain &re
                                  const MetricsConst &mc, const int32_t *contacts, int P, double *xf, double *rmsd, int32_t *recovered,
                                  hipStream_t s);
 
+// rigid pose fit (kernels_fit.hip; include/dfmdock_amd.h: dfm_pose_fit).  One chain of a batch of decoys: pos [P][n][9] (pose stride
+// n * 9), ref [n][9] the same chain of the input; n = 0 (receptor only): the decoys bring no receptor
+struct FitChain {
+    const float *pos;
+    const float *ref;
+    int n;
+};
+// sums [P][chains][15] = S_pos [3] | C = sum pos ref^T [9] | S_ref [3] in coordinates shifted by o; chain 0 the ligand, chain 1 the
+// receptor (chains = 2 when rec.n > 0)
+hipError_t launch_fit_reduce(const FitChain &lig, const FitChain &rec, int P, const double o[3], double *sums, hipStream_t s);
+// xf [P][24] = R, t of the ligand fit | Q, s of the receptor fit (identity, 0 without one) in the shifted coordinates; rot / tr [P][3] =
+// the pose in the sampler's convention about the centre o
+hipError_t launch_fit_solve(const double *sums, int n_lig, int n_rec, int P, double *xf, float *rot, float *tr, hipStream_t s);
+// rmsd [P]; rec_rmsd [P] written when rec.n > 0 (else never read: may be nullptr)
+hipError_t launch_fit_resid(const FitChain &lig, const FitChain &rec, const double *xf, int P, const double o[3], double *rmsd,
+                            double *rec_rmsd, hipStream_t s);
+
 // consensus contact scoring (kernels_consensus.hip; include/dfmdock_amd.h: dfm_pose_consensus).  n poses of one chunk: rec [R][9],
 // lig [n][L][9]; bits [n][W][R] uint64 with W = ceil(L / 64): bit j % 64 of word (p, j / 64, i) = contact (i, j) of pose p, unused high
 // bits 0 (the transpose of the C ABI's [P][R][W]).  member [n]: 1 = the pose counts.  count [R][L], rec_count [R], lig_count [L] are

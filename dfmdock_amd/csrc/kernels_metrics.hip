@@ -19,6 +19,7 @@
 //
 // Built with -ffp-contract=off: the distance arithmetic rounds like numpy's; the sums use explicit fma.
 #include "dfm_contact.h"      // min_dist9
+#include "dfm_horn.h"         // wave_sum, horn_rotation
 #include "dfm_internal.h"
 
 namespace dfm {
@@ -26,74 +27,6 @@ namespace dfm {
 namespace {
 
 constexpr int MW = 4;      // waves (poses) per workgroup
-
-__device__ inline double wave_sum(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// one Jacobi rotation of the symmetric 4 x 4 matrix a in the (p, q) plane; v collects the eigenvectors as columns
-template <int p, int q> __device__ inline void jacobi_rot(double (&a)[4][4], double (&v)[4][4])
-{
-    const double apq = a[p][q];
-    if (!(fabs(apq) > 0.0)) return;      // also NaN: nothing to do, k_metrics_solve makes the whole fit NaN
-    const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    a[p][p] -= t * apq;
-    a[q][q] += t * apq;
-    a[p][q] = 0.0;
-    a[q][p] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (k != p && k != q) {
-            const double akp = a[k][p], akq = a[k][q];
-            a[k][p] = c * akp - s * akq; a[p][k] = a[k][p];
-            a[k][q] = s * akp + c * akq; a[q][k] = a[k][q];
-        }
-        const double vkp = v[k][p], vkq = v[k][q];
-        v[k][p] = c * vkp - s * vkq;
-        v[k][q] = s * vkp + c * vkq;
-    }
-}
-
-// M[a][b] = sum (p - pm)_a (q - qm)_b  ->  row-major proper rotation r with sum |r p - q|^2 minimal (Horn 1987)
-__device__ inline void horn_rotation(const double (&M)[3][3], double (&r)[9])
-{
-    double a[4][4], v[4][4];
-    a[0][0] = M[0][0] + M[1][1] + M[2][2];
-    a[1][1] = M[0][0] - M[1][1] - M[2][2];
-    a[2][2] = -M[0][0] + M[1][1] - M[2][2];
-    a[3][3] = -M[0][0] - M[1][1] + M[2][2];
-    a[0][1] = a[1][0] = M[1][2] - M[2][1];
-    a[0][2] = a[2][0] = M[2][0] - M[0][2];
-    a[0][3] = a[3][0] = M[0][1] - M[1][0];
-    a[1][2] = a[2][1] = M[0][1] + M[1][0];
-    a[1][3] = a[3][1] = M[2][0] + M[0][2];
-    a[2][3] = a[3][2] = M[1][2] + M[2][1];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[i][j] = i == j ? 1.0 : 0.0;
-#pragma unroll 1
-    for (int sweep = 0; sweep < 12; ++sweep) {
-        const double off = fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[0][3]) + fabs(a[1][2]) + fabs(a[1][3]) + fabs(a[2][3]);
-        if (!(off > 0.0)) break;
-        jacobi_rot<0, 1>(a, v); jacobi_rot<0, 2>(a, v); jacobi_rot<0, 3>(a, v);
-        jacobi_rot<1, 2>(a, v); jacobi_rot<1, 3>(a, v); jacobi_rot<2, 3>(a, v);
-    }
-    // the eigenvector of the largest eigenvalue (first one on ties)
-    double best = a[0][0], w = v[0][0], x = v[1][0], y = v[2][0], z = v[3][0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k)
-        if (a[k][k] > best) { best = a[k][k]; w = v[0][k]; x = v[1][k]; y = v[2][k]; z = v[3][k]; }
-    const double n = 1.0 / sqrt(w * w + x * x + y * y + z * z);
-    w *= n; x *= n; y *= n; z *= n;
-    r[0] = w * w + x * x - y * y - z * z; r[1] = 2.0 * (x * y - w * z);         r[2] = 2.0 * (x * z + w * y);
-    r[3] = 2.0 * (x * y + w * z);         r[4] = w * w - x * x + y * y - z * z; r[5] = 2.0 * (y * z - w * x);
-    r[6] = 2.0 * (x * z - w * y);         r[7] = 2.0 * (y * z + w * x);         r[8] = w * w - x * x - y * y + z * z;
-}
 
 }  // namespace
 

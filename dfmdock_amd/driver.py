@@ -992,7 +992,12 @@ def _ranked(run, name, data, column, pick=np.argmin):
 
 
 def _sterics_screen(run):
-    run.data["sterics"], run.bad = _screen(run.model, run.rec, run.lig, run.cols, run.opts["sterics"])
+    sd, bad = _screen(run.model, run.rec, run.lig, run.cols, run.opts["sterics"])
+    if run.bad is not None and bad is not None:      # poses the driver removed itself (rescore_pair's rejected decoys): both masks hold
+        bad = run.bad | bad
+        if bad.all():      # the filter would take what the driver left: nothing more is removed
+            sd["fallback"], bad = True, run.bad
+    run.data["sterics"], run.bad = sd, run.bad if bad is None else bad
 
 
 def _distogram_select(run):
@@ -1094,6 +1099,27 @@ def _analysis_options(model, max_batch, kw):
     given = {a.name: {name: kw.pop(name, default) for name, default in a.defaults.items()} for a in ANALYSES}
     _check_rank(rank, given["consensus"]["consensus_top"])
     return {a.name: a.check(model, rank, max_batch, **given[a.name]) for a in ANALYSES}
+
+
+def _check_refine(top_k, refine_t, refine_samples):
+    """refine_t of dock_pair / rescore_pair: it needs top_k and at least one trajectory per centre."""
+    if refine_t is not None and top_k is None:
+        raise ValueError("refine_t refines the cluster centres: it needs top_k")
+    if refine_t is not None and int(refine_samples) < 1:
+        raise ValueError("refine_samples must be >= 1")
+
+
+def _check_models(top_k, cluster_radius, cluster_rule):
+    """None (no models) or the options of _top_models: (top_k, cluster radius, cluster rule), checked."""
+    if top_k is None:
+        return None
+    if int(top_k) < 1:
+        raise ValueError("top_k must be >= 1")
+    if cluster_rule not in ("energy", "size"):
+        raise ValueError(f"cluster_rule must be 'energy' or 'size', got {cluster_rule!r}")
+    if not (np.isfinite(cluster_radius) and cluster_radius > 0):
+        raise ValueError("cluster_radius must be finite and > 0")
+    return int(top_k), float(cluster_radius), cluster_rule
 
 
 def _finish(run, pick, entries, clu=None, refine=None):
@@ -1223,20 +1249,10 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     opts = _analysis_options(model, max_batch, sampler_kw)
     if native is not None:
         _check_native(native, len(rec["bb_coords"]), len(lig["bb_coords"]))
-    if refine_t is not None and top_k is None:
-        raise ValueError("refine_t refines the cluster centres: it needs top_k")
-    if refine_t is not None and int(refine_samples) < 1:
-        raise ValueError("refine_samples must be >= 1")
+    _check_refine(top_k, refine_t, refine_samples)
     if restraints is not None and restraint_rank not in ("satisfied", "energy"):
         raise ValueError(f"restraint_rank must be 'satisfied' or 'energy', got {restraint_rank!r}")
-    if top_k is not None:
-        if int(top_k) < 1:
-            raise ValueError("top_k must be >= 1")
-        if cluster_rule not in ("energy", "size"):
-            raise ValueError(f"cluster_rule must be 'energy' or 'size', got {cluster_rule!r}")
-        if not (np.isfinite(cluster_radius) and cluster_radius > 0):
-            raise ValueError("cluster_radius must be finite and > 0")
-    clu = None if top_k is None else (int(top_k), float(cluster_radius), cluster_rule)
+    clu = _check_models(top_k, cluster_radius, cluster_rule)
     refine = None if refine_t is None else dict(t_begin=float(refine_t), n=int(refine_samples), num_steps=num_steps,
                                                 restraints=restraints is not None, **sampler_kw)
     gx = engine.Complex(model, rec_x, lig_x, rec["bb_coords"], lig["bb_coords"])
@@ -1318,6 +1334,87 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
                   lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols})
     if native is not None:
         res["start_metrics"] = native_metrics(model, native, rec["bb_coords"], run.lig0[None])[0]
+    return res
+
+
+class AllRejected(ValueError):
+    """rescore_pair: no decoy is a rigid image of the input pair."""
+
+
+RESCORE_T = 1e-3      # time of rescore_pair's energy evaluation: the last entry of the sampler's default grid, where dfm_sample takes its final energy
+
+
+def fit_decoys(model: engine.Model, lig0, decoys, rec_bb=None):
+    """The decoys of rescore_pair as (rot_update [P,3], tr_update [P,3] float32, rmsd [P], rec_rmsd [P] or None): coordinates
+    ({"lig_pos": [P,L,3,3], "rec_pos": optional [P,R,3,3]}) fitted on the GPU (Model.pose_fit) about the backbone centre
+    cluster.rebuild_backbone uses for the model's family; poses ({"rot_update", "tr_update"}) taken as they are, with an rmsd of 0."""
+    if "lig_pos" in decoys:
+        if "rot_update" in decoys or "tr_update" in decoys:
+            raise ValueError("decoys must hold either lig_pos (and rec_pos) or rot_update and tr_update, not both")
+        x0 = np.asarray(lig0, np.float32).reshape(-1, 3, 3).astype(np.float64)
+        center = x0.reshape(-1, 3).mean(0) if model.hp.family == 1 else x0[:, 1].mean(0)
+        rec_pos = decoys.get("rec_pos")
+        if rec_pos is not None and rec_bb is None:
+            raise ValueError("decoys with rec_pos need the input receptor's backbone")
+        f = model.pose_fit(lig0, decoys["lig_pos"], center, None if rec_pos is None else rec_bb, rec_pos)
+        return f["rot"], f["tr"], f["rmsd"], f["rec_rmsd"]
+    if "rot_update" not in decoys or "tr_update" not in decoys:
+        raise ValueError("decoys must hold lig_pos (and optionally rec_pos) or rot_update and tr_update")
+    rot, tr = (np.array(decoys[k], np.float32).reshape(-1, 3) for k in ("rot_update", "tr_update"))
+    if rot.shape != tr.shape or rot.shape[0] < 1:
+        raise ValueError(f"rot_update and tr_update must both be [P,3] with P >= 1, got {rot.shape} and {tr.shape}")
+    return rot, tr, np.zeros(rot.shape[0]), None
+
+
+def rescore_pair(model: engine.Model, rec, lig, rec_x, lig_x, decoys, fit_tolerance=0.1, t=RESCORE_T, seed=0, precision="mfma16",
+                 out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", top_k=None, cluster_radius=4.0,
+                 cluster_rule="energy", refine_t=None, refine_samples=8, num_steps=40, native=None, **kw):
+    """Rescoring of decoys this engine did not sample: every decoy of the two parsed PDB chains becomes a pose (rot_update, tr_update)
+    (fit_decoys), gets the model's energy at time `t` - Complex.score on cluster.rebuild_backbone of its pose, in chunks of max_batch, the
+    chunk that starts at decoy p0 with seed + p0 as dock_pair's batches and ensemble_distogram's chunks take theirs: the energy column
+    equals that call made by hand chunk by chunk, and with P <= max_batch the one call with `seed` - and
+    the minimum-energy one is kept, written and described exactly as dock_pair does it (_finish): `rank`, every analysis keyword,
+    `top_k` / `cluster_radius` / `cluster_rule`, `refine_t` / `refine_samples` and `native` are dock_pair's.  `num_steps` and what is
+    left of `kw` go to the sampler of `refine_t`.
+    A decoy whose fit leaves an rmsd (or rec_rmsd) above `fit_tolerance` A, or NaN, is no rigid image of the input: it is REJECTED - a
+    NaN energy and key, never kept and never a model, like a pose the clash filter removed (the two masks add up); its pose columns hold
+    the fit where that is finite and the identity where it is not, so every analysis still sees P poses.  With every decoy rejected
+    the call raises AllRejected before any analysis runs.
+    Returns refine_pair's dict (energy, index, trajectories, ...) plus `t`, `fit` ({rmsd, rec_rmsd, tolerance, n_rejected}, the first two
+    of the kept pose) and `fit_data` ({rot_update, tr_update, rmsd, rec_rmsd, rejected}: the fit's own arrays).
+    Family 1: cluster.rebuild_backbone rotates about the backbone centroid, pdbio.apply_pose_all_atom about the all-atom mean, and one
+    (rot_update, tr_update) goes to both, as it always has in dock_pair."""
+    opts = _analysis_options(model, max_batch, kw)
+    if native is not None:
+        _check_native(native, len(rec["bb_coords"]), len(lig["bb_coords"]))
+    if not (np.isfinite(fit_tolerance) and fit_tolerance >= 0):
+        raise ValueError("fit_tolerance must be finite and >= 0")
+    _check_refine(top_k, refine_t, refine_samples)
+    clu = _check_models(top_k, cluster_radius, cluster_rule)
+    refine = None if refine_t is None else dict(t_begin=float(refine_t), n=int(refine_samples), num_steps=num_steps, **kw)
+    lig0 = np.asarray(lig["bb_coords"], np.float32)
+    rot, tr, rmsd, rec_rmsd = fit_decoys(model, lig0, decoys, np.asarray(rec["bb_coords"], np.float32))
+    with np.errstate(invalid="ignore"):
+        rejected = ~(rmsd <= fit_tolerance) | (False if rec_rmsd is None else ~(rec_rmsd <= fit_tolerance))
+    fit_data = {"rot_update": rot.copy(), "tr_update": tr.copy(), "rmsd": rmsd, "rec_rmsd": rec_rmsd, "rejected": rejected}
+    if rejected.all():
+        raise AllRejected(f"every one of the {rejected.size} decoys is rejected: no fit is within fit_tolerance = {fit_tolerance} A "
+                         f"(smallest rmsd {np.nanmin(rmsd) if not np.isnan(rmsd).all() else float('nan'):.3g} A) - are these decoys of this pair?")
+    finite = np.isfinite(rot).all(1) & np.isfinite(tr).all(1)
+    rot, tr = np.where(finite[:, None], rot, np.float32(0)), np.where(finite[:, None], tr, np.float32(0))
+    gx = engine.Complex(model, rec_x, lig_x, rec["bb_coords"], lig["bb_coords"])
+    precision, chk = checked_precision(gx, precision, "pair", selfcheck, on_selfcheck_fail, seed=seed)
+    P, mb = rot.shape[0], max(1, int(max_batch))
+    energy = np.concatenate([gx.score(rebuild_backbone(gx.lig_pos0, rot[p0:p0 + mb], tr[p0:p0 + mb], model.hp.family), t, seed=seed + p0,
+                                      energy=True, **engine.precision_kwargs(precision))["energy"] for p0 in range(0, P, mb)])
+    cols = {"energy": np.where(rejected, np.float32(np.nan), energy), "rot_update": rot, "tr_update": tr}
+    run = _Run(model, gx, rec, lig, cols, precision, opts, chk, out_pdb, native, seed)
+    run.key, run.bad = cols["energy"], rejected if rejected.any() else None
+    res = _finish(run, (np.nanargmin, "energy"), lambda k: {"index": k, "t": float(t), "trajectories": cols}, clu, refine)
+    k = res["index"]
+    res["fit"] = {"rmsd": float(rmsd[k]), "rec_rmsd": None if rec_rmsd is None else float(rec_rmsd[k]), "tolerance": float(fit_tolerance),
+                  "n_rejected": int(rejected.sum())}
+    res["fit_data"], res["key"] = fit_data, run.key      # key: what the clustering ranked by, NaN on the removed poses
     return res
 
 

@@ -213,6 +213,37 @@ class Model:
         o["consensus"] = CS.finish(o["score_sum"], o["n_contacts"], o["M"])
         return o
 
+    def pose_fit(self, lig_ref, lig_pos, center, rec_ref=None, rec_pos=None, chunk_poses=0):
+        """Rigid pose fit of P decoys on the GPU (dfm_pose_fit; the float64 definition is fit.fit_poses): lig_ref [L,3,3] the input
+        ligand, lig_pos [P,L,3,3] the decoys' ligands, center [3] the sampler's rotation centre; rec_ref [R,3,3] and rec_pos [P,R,3,3],
+        both or neither, for decoys in a frame of their own.  Returns {rot [P,3], tr [P,3] float32 - the sampler's (rot_update,
+        tr_update) -, rmsd [P] float64 and rec_rmsd [P] float64 or None}."""
+        lr = _f32(lig_ref).reshape(-1, 9)
+        Lg = lr.shape[0]
+        lp = _f32(lig_pos)
+        if Lg < 1 or lp.size == 0 or lp.size % (Lg * 9):
+            raise ValueError(f"lig_pos must be [P,{Lg},3,3] with P >= 1, got {np.shape(lig_pos)}")
+        P = lp.size // (Lg * 9)
+        if (rec_ref is None) != (rec_pos is None):
+            raise ValueError("rec_ref and rec_pos must be given together")
+        rr = rp = None
+        R = 0
+        if rec_ref is not None:
+            rr, rp = _f32(rec_ref).reshape(-1, 9), _f32(rec_pos)
+            R = rr.shape[0]
+            if R < 1 or rp.size != P * R * 9:
+                raise ValueError(f"rec_pos must be [{P},{R},3,3], got {np.shape(rec_pos)}")
+        cen = _center(center)
+        o = {"rot": np.zeros((P, 3), np.float32), "tr": np.zeros((P, 3), np.float32), "rmsd": np.zeros(P, np.float64),
+             "rec_rmsd": None if rr is None else np.zeros(P, np.float64)}
+        out = L.FitOutC()
+        dp = C.POINTER(C.c_double)
+        out.rot, out.tr, out.rmsd = _p(o["rot"]), _p(o["tr"]), o["rmsd"].ctypes.data_as(dp)
+        if rr is not None:
+            out.rec_rmsd_or_null = o["rec_rmsd"].ctypes.data_as(dp)
+        L.check(L.lib().dfm_pose_fit_chunked(self._h, P, Lg, _p(lr), _p(lp), R, _p(rr), _p(rp), _p(cen), int(chunk_poses), C.byref(out)),
+                "dfm_pose_fit")
+        return o
 
     def atoms(self, rec_atoms, lig_atoms, center, clash_cutoff=3.0, contact_cutoff=5.0):
         """The heavy atoms of a pair prepared for the all-atom clash / contact screen on the GPU (dfm_atoms_create): rec_atoms [Ar,3],
@@ -626,6 +657,11 @@ class PairPotential(_Handle):
         L.check(L.lib().dfm_pose_pairpot_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_pairpot")
         o["energy"] = PP.kcal(o["energy_q"])
         return o
+
+
+def fit_last_timing():
+    """(copy_ms, kernel_ms) of this thread's last Model.pose_fit, from the call's own events."""
+    return _last_ms("dfm_fit_last_timing", 2)
 
 
 def pairpot_last_timing():

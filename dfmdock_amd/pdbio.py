@@ -1,6 +1,7 @@
 """PDB front / back end of the docking drivers without biotite.  Host side only.
 
   read_pdb / backbone_from_atoms   <- get_info_from_pdb            (src/inference_base.py:72-126)
+  read_models / match_model        every model of a decoy file, matched to the input pair residue by residue (no reference counterpart)
   apply_pose_all_atom              <- modify_aa_coords             (src/inference_base.py:354-364)
   write_complex_pdb                <- combine_atom_arrays + PDBFile.write (src/inference_base.py:37-66,:659-668)
   place_fourth_atom, full_backbone <- utils/pdb.py:31-56, inference_mlsb.py:68-85 (O / virtual-CB placement)
@@ -27,18 +28,106 @@ def read_pdb(path):
             rec = line[:6]
             if rec.startswith("ENDMDL"):
                 break
-            if rec not in ("ATOM  ", "HETATM"):
-                continue
-            alt = line[16]
-            if alt not in (" ", "A"):
-                continue
-            atoms.append({
-                "hetero": rec == "HETATM", "name": line[12:16].strip(), "res_name": line[17:20].strip(),
-                "chain": line[21], "res_id": int(line[22:26]), "ins": line[26],
-                "coord": (float(line[30:38]), float(line[38:46]), float(line[46:54])),
-                "element": line[76:78].strip() if len(line) >= 78 else "",
-            })
+            a = _atom_record(line)
+            if a is not None:
+                atoms.append(a)
     return atoms
+
+
+def _atom_record(line):
+    """One ATOM / HETATM line as read_pdb's dict, or None for any other record and for an alternate location past the first
+    (read_pdb's rule: blank or A)."""
+    rec = line[:6]
+    if rec not in ("ATOM  ", "HETATM") or line[16] not in (" ", "A"):
+        return None
+    return {
+        "hetero": rec == "HETATM", "name": line[12:16].strip(), "res_name": line[17:20].strip(),
+        "chain": line[21], "res_id": int(line[22:26]), "ins": line[26],
+        "coord": (float(line[30:38]), float(line[38:46]), float(line[46:54])),
+        "element": line[76:78].strip() if len(line) >= 78 else "",
+    }
+
+
+def read_models(path):
+    """The atom records of EVERY model of a PDB file, as a list (one entry per MODEL ... ENDMDL block, in file order) of read_pdb's
+    lists of dicts, under read_pdb's alternate-location rule.  A MODEL record opens a block and closes the one before it (files of
+    write_trajectory_pdb hold no ENDMDL); a file without MODEL records is one model.  A MODEL record followed at once by another, or
+    by ENDMDL, is a model without atoms: it keeps its place in the list, and match_model reports its first ligand residue missing."""
+    models, cur, in_model = [], [], False
+    with open(path) as f:
+        for line in f:
+            rec = line[:6]
+            if rec.startswith("MODEL"):
+                if in_model or cur:
+                    models.append(cur)
+                cur, in_model = [], True
+            elif rec.startswith("ENDMDL"):
+                models.append(cur)
+                cur, in_model = [], False
+            else:
+                a = _atom_record(line)
+                if a is not None:
+                    cur.append(a)
+    if in_model or cur:
+        models.append(cur)
+    return models
+
+
+def _chain_ids(residues):
+    out = []
+    for key in residues:
+        if key[0] not in out:
+            out.append(key[0])
+    return out
+
+
+def match_model(atoms, rec, lig, rec_chains=None, lig_chains=None, source="decoy", model=1):
+    """The backbone of one decoy model (`atoms`: one entry of read_models) in the residue order of the input pair (rec, lig: the dicts
+    of backbone_from_atoms): (lig_bb [L,3,3], rec_bb [R,3,3] or None) float64.  The model's residues are matched to the inputs'
+    `residues` keys - chain, number, insertion code and name.  The ligand must be complete and in the input's order; the receptor is
+    used when the model holds any atom of a receptor chain, and must then be complete and in order as well; atoms of other residues
+    (and HETATM records) are ignored.  rec_chains / lig_chains: the chain ids the two sides have IN THE DECOY FILE, one per chain id
+    of the input file in its order of appearance (default: the input files' own ids).  Raises ValueError naming `source`, `model` and
+    the first residue that is missing or out of place; and, when the two inputs share a chain id and no chains are given, asking for
+    them."""
+    ids = {"rec": _chain_ids(rec["residues"]), "lig": _chain_ids(lig["residues"])}
+    given = {"rec": rec_chains, "lig": lig_chains}
+    if rec_chains is None and lig_chains is None and set(ids["rec"]) & set(ids["lig"]):
+        raise ValueError(f"receptor and ligand input share the chain id(s) {sorted(set(ids['rec']) & set(ids['lig']))}: "
+                         "name the chains the two sides have in the decoys (rec_chains / lig_chains, --decoy-chains RCHAINS LCHAINS)")
+    maps = {}
+    for side in ("rec", "lig"):
+        g = ids[side] if given[side] is None else list(given[side])
+        if len(g) != len(ids[side]):
+            raise ValueError(f"{side}_chains {''.join(g)!r} must name one chain per chain of the input ({''.join(ids[side])!r})")
+        maps[side] = dict(zip(ids[side], g))
+    if set(maps["rec"].values()) & set(maps["lig"].values()):
+        raise ValueError("rec_chains and lig_chains must not share a chain id")
+    found, order = {}, {}
+    for a in atoms:
+        if a["hetero"] or a["name"] not in ("N", "CA", "C"):
+            continue
+        key = (a["chain"], a["res_id"], a["ins"], a["res_name"])
+        order.setdefault(key, len(order))
+        found.setdefault(key, {}).setdefault(a["name"], a["coord"])
+
+    def side_bb(side, chain):
+        bb, last = np.empty((len(chain["residues"]), 3, 3), np.float64), -1
+        for i, key in enumerate(chain["residues"]):
+            k = (maps[side][key[0]],) + tuple(key[1:])
+            label = f"{k[3]} {k[0]}{k[1]}{k[2].strip()}"
+            if k not in found or len(found[k]) < 3:
+                raise ValueError(f"{source}, model {model}: {'ligand' if side == 'lig' else 'receptor'} residue {label} is missing"
+                                 + ("" if k not in found else " an N, CA or C atom"))
+            if order[k] < last:
+                raise ValueError(f"{source}, model {model}: {'ligand' if side == 'lig' else 'receptor'} residue {label} is out of place")
+            last = order[k]
+            bb[i] = [found[k]["N"], found[k]["CA"], found[k]["C"]]
+        return bb
+    lig_bb = side_bb("lig", lig)
+    rec_here = set(maps["rec"].values())
+    rec_bb = side_bb("rec", rec) if any(a["chain"] in rec_here and not a["hetero"] for a in atoms) else None
+    return lig_bb, rec_bb
 
 
 def backbone_from_atoms(atoms):

@@ -710,6 +710,39 @@ int dfm_pairpot_last_timing(double *copy_ms, double *kernel_ms);
 /* The kernel milliseconds of that call by phase, from the call's own events: the memsets, the walk (k_pairpot_pose, k_pairpot) and the
  * finish, which this call does not have (about 0); their sum is kernel_ms */
 int dfm_pairpot_last_phases(double *zero_ms, double *walk_ms, double *finish_ms);
+/* Rigid pose fit of P decoys of one complex: from the backbone coordinates of a rigidly placed ligand back to the pose
+ * (rot_update, tr_update) of dfm_traj_out, the one form every dfm_pose_* call, dfm_refine's start and the drivers' output path take -
+ * the door for decoys this engine did not sample.  dfmdock_amd/fit.py (fit_poses) is the float64 definition this call is tested
+ * against.  Backbones are [n,9] = (N, CA, C) per residue; the points of a fit are all 3 n atoms with equal weights.
+ *   lig_ref [L,9]: the input ligand, lig_pos [P,L,9]: the decoys' ligands, center: the point the sampler rotates the ligand about
+ *   (CA centroid of lig_ref for family 0, backbone centroid for family 1).  rec_ref_or_null [R,9] and rec_pos_or_null [P,R,9], both or
+ *   neither: the input receptor and the decoys' receptors, for decoys that sit in a frame of their own.
+ *   With a receptor, (Q, s) is the Kabsch fit of rec_pos[p] onto rec_ref (the proper rotation the SVD gives with its reflection fix),
+ *   rec_rmsd the root mean square of |Q y + s - y_ref|, and the decoy's ligand becomes x' = Q x + s; without one x' = x.  (R, t) is the
+ *   Kabsch fit of lig_ref onto x' and rmsd the root mean square of the explicit residuals |R x0 + t - x'| - above a tolerance of the
+ *   caller's the decoy is no rigid image of the input.  rot = the axis-angle of R, angle in [0, pi], taken from Horn's quaternion
+ *   (exactly zero for the identity); tr = t + R c - c, so that x = (x0 - c) R(rot)^T + c + tr.
+ *   Everything is fp64 on the fp32 inputs; rot and tr are rounded to fp32 at the end.  A pose with a non-finite coordinate has rot, tr,
+ *   rmsd and rec_rmsd NaN and leaves the other poses alone.  A pose's outputs depend on that pose and the references alone - not on P,
+ *   its index, or how the call splits P into chunks (64 MiB of decoys each; dfm_pose_fit_chunked: chunk_poses > 0 poses each).
+ * DFM_E_INVALID: a NULL m / lig_ref / lig_pos / center / out / out->rot / out->tr / out->rmsd, P < 1, L < 1, exactly one of the two
+ * receptor pointers, R < 1 or a NULL out->rec_rmsd_or_null with a receptor, chunk_poses < 0.  Takes the MODEL handle for its device
+ * only; every call owns a non-blocking stream and its device temporaries, so calls may run from several host threads at once.  The
+ * reference has no such call: it replaces the host-side Kabsch fit a user of the reference would write around the rot_update /
+ * tr_update bookkeeping of src/inference_base.py to bring outside decoys into its convention. */
+typedef struct {
+    float *rot;                 /* [P,3] */
+    float *tr;                  /* [P,3] */
+    double *rmsd;               /* [P]   */
+    double *rec_rmsd_or_null;   /* [P], needed with a receptor */
+} dfm_fit_out;
+int dfm_pose_fit(dfm_model *m, int P, int L, const float *lig_ref /*[L,9]*/, const float *lig_pos /*[P,L,9]*/, int R,
+                 const float *rec_ref_or_null /*[R,9]*/, const float *rec_pos_or_null /*[P,R,9]*/, const float center[3], dfm_fit_out *out);
+int dfm_pose_fit_chunked(dfm_model *m, int P, int L, const float *lig_ref, const float *lig_pos, int R, const float *rec_ref_or_null,
+                         const float *rec_pos_or_null, const float center[3], int chunk_poses, dfm_fit_out *out);
+/* GPU milliseconds of the calling thread's last dfm_pose_fit, summed over its chunks: the host-to-device copies of the decoys and the
+ * three kernels (k_fit_reduce, k_fit_solve, k_fit_resid) - tools/fit_bench.py */
+int dfm_fit_last_timing(double *copy_ms, double *kernel_ms);
 /* edges per node for this complex: min(N,20) + min(40, N-20) */
 int dfm_complex_degree(const dfm_complex *cx);
 /* Device blocks released by destroyed handles are parked per device for the next handle (a set driver creates and destroys a
