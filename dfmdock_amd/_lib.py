@@ -31,6 +31,7 @@ DFM_F_L0_TABLE = 1 << 11       # dfm_score: layer 0 through the per-complex mess
 DFM_F_NO_L0_TABLE = 1 << 12    # dfm_sample: layer 0 evaluated directly
 DFM_F_GRAPH = 1 << 13          # dfm_sample: replay one captured step as a hipGraph (opt-in)
 DFM_F_RESTRAINTS = 1 << 14     # dfm_sample: the interface restraint step (dfm_complex_set_restraints)
+DFM_F_SYMMETRY = 1 << 15       # dfm_sample / dfm_refine: the Cn symmetry step (dfm_complex_set_symmetry)
 
 DFM_CLUSTER_ENERGY = 0         # dfm_pose_cluster rules
 DFM_CLUSTER_SIZE = 1
@@ -40,7 +41,7 @@ EXPORTS = [
     "dfm_model_create", "dfm_model_destroy", "dfm_complex_create", "dfm_complex_destroy", "dfm_complex_degree",
     "dfm_complex_set_pose", "dfm_complex_set_homomer",
     "dfm_score", "dfm_sample", "dfm_get_profile", "dfm_diffusion_coef", "dfm_complex_selfcheck", "dfm_trim_cache", "dfm_alloc_diag",
-    "dfm_complex_set_restraints", "dfm_restraint_eval", "dfm_pose_rmsd", "dfm_pose_cluster", "dfm_pose_last_timing",
+    "dfm_complex_set_restraints", "dfm_restraint_eval", "dfm_complex_set_symmetry", "dfm_symmetry_eval", "dfm_pose_rmsd", "dfm_pose_cluster", "dfm_pose_last_timing",
     "dfm_refine", "dfm_forward_marginal", "dfm_igso3_table",
     "dfm_native_create", "dfm_native_destroy", "dfm_native_info", "dfm_pose_metrics", "dfm_metrics_last_timing",
     "dfm_pose_consensus", "dfm_consensus_chunk_poses", "dfm_consensus_last_timing",
@@ -113,6 +114,15 @@ class SelfcheckC(C.Structure):
 
 class RestraintParamsC(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("k_tr", "k_rot", "max_tr", "max_rot", "t_start")]
+
+
+class SymmetryParamsC(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("gain_rot", "gain_tr", "max_rot", "max_tr", "t_start")] + [("snap_last", C.c_int32)]
+
+
+class SymmetryOutC(C.Structure):
+    _fields_ = [(n, C.POINTER(C.c_double)) for n in ("theta", "screw", "axis", "axis_point", "fit_rmsd", "sym_rmsd")] + \
+               [("order_m", C.POINTER(C.c_int32)), ("step", C.POINTER(C.c_float))]
 
 
 class MetricsOutC(C.Structure):
@@ -213,6 +223,8 @@ def lib():
     L.dfm_complex_selfcheck.argtypes = [C.c_void_p, C.c_int, F32P, C.c_uint64, C.c_uint32, C.POINTER(SelfcheckC)]
     L.dfm_complex_set_restraints.argtypes = [C.c_void_p, C.c_int, I32P, I32P, F32P, F32P, C.POINTER(RestraintParamsC)]
     L.dfm_restraint_eval.argtypes = [C.c_void_p, C.c_int, F32P, F32P, I32P, F32P]
+    L.dfm_complex_set_symmetry.argtypes = [C.c_void_p, C.c_int, C.POINTER(SymmetryParamsC)]
+    L.dfm_symmetry_eval.argtypes = [C.c_void_p, C.c_int, F32P, C.POINTER(SymmetryOutC)]
     L.dfm_pose_rmsd.argtypes = [C.c_void_p, C.c_int, C.c_int, F32P, I32P, C.c_int, F32P]
     L.dfm_pose_cluster.argtypes = [C.c_void_p, C.c_int, C.c_int, F32P, I32P, C.c_int, F32P, C.c_float, C.c_int, C.c_int, I32P, I32P, I32P,
                                    I32P]

@@ -20,6 +20,7 @@
     python -m dfmdock_amd dock|refine ... --hbonds [--bsa] [--hbond-cutoff 3.5] [--hbond-angle 90] [--salt-cutoff 4.0] [--hbond-residues FILE]
     python -m dfmdock_amd dock|refine ... --distogram [--rank distogram] [--distogram-map map.npz] [--distogram-restraints FILE] [--distogram-t 1e-3]
     python -m dfmdock_amd dock|refine ... --clash-screen [--clash-filter] [--clash-cutoff 3.0] [--contact-cutoff 5.0] [--clash-residues FILE]
+    python -m dfmdock_amd dock|refine A.pdb A2.pdb ... --symmetry C3 [--symmetry-gain 0.5] [--symmetry-t-start 1] [--symmetry-tolerance 0.1] [--no-symmetry-snap]
     python -m dfmdock_amd rescore REC.pdb LIG.pdb --ckpt model_0.ckpt --features F.npz --decoys D.pdb [D2.pdb ...] | --coords C.npz | --poses P.npz
                                   [--decoy-chains A B] [--fit-tolerance 0.1] [--score-t 1e-3] [--scores scores.csv] [--top-k K [--refine-t T]] [every dock analysis]
 
@@ -36,6 +37,11 @@
              format there and in INTEGRATION.md).  `dock --restraints` keeps the minimum-energy trajectory among those satisfying the
              most groups (`--restraint-rank energy`: the plain minimum-energy rule); `sweep --native-restraints K` restrains every
              complex with K seeded native CA-CA contacts (< --restraint-cutoff A), the usual evaluation of guided docking.
+  symmetry   no reference counterpart: Cn symmetric docking of a homo-oligomer (dfmdock_amd/symmetry.py, dfm_complex_set_symmetry).
+             Both inputs are the same single chain (same sequence, rigid images of each other within --symmetry-tolerance A); the
+             sampler's symmetry step keeps the monomer-to-monomer transform on a pure rotation by 2 pi m / n, the last step projects
+             exactly (--no-symmetry-snap: it does not), the result line gains a `symmetry` object (n, m, theta, screw, sym_rmsd,
+             closure, axis, axis_point; n >= 4: ring_clashes) and every written file holds all n chains.
   clustering no reference counterpart: trajectories grouped by ligand RMSD on the GPU (dfmdock_amd/cluster.py, dfm_pose_cluster).
              `dock --top-k K` writes the centres of the first K clusters as <out stem>_1.pdb ... <out stem>_K.pdb (model 1 of rule
              energy is output.pdb) and lists them under `models`; `sweep --cluster-radius R` adds `cluster` / `is_center` to the CSV and
@@ -251,6 +257,66 @@ def _add_models(p, what):
     p.add_argument("--refine-samples", type=int, default=8, metavar="n", help="with --refine-t: trajectories per cluster centre")
 
 
+def _add_symmetry(p):
+    p.add_argument("--symmetry", default=None, metavar="Cn",
+                   help="Cn symmetric docking of a homo-oligomer (C3 or 3; n in 2 .. 24): both inputs are the same single chain; the "
+                        "sampler keeps every pose on a closed n-mer and the written files hold all n chains")
+    p.add_argument("--symmetry-gain", type=float, default=None, metavar="G",
+                   help="with --symmetry: fraction of the angle error and of the screw translation one step removes, in (0, 1] (default 0.5)")
+    p.add_argument("--symmetry-t-start", type=float, default=None, metavar="T",
+                   help="with --symmetry: the symmetry step runs on the steps with t <= T (default 1: every step)")
+    p.add_argument("--symmetry-tolerance", type=float, default=None, metavar="A",
+                   help="with --symmetry: largest Kabsch rmsd (A) of the two input monomers' backbones (default 0.1)")
+    p.add_argument("--no-symmetry-snap", action="store_true",
+                   help="with --symmetry: the last step follows the gains like every other one instead of projecting exactly")
+
+
+def symmetry_parser():
+    """The options of --symmetry as a parser of their own: parse_args takes them out of the command line of dock and refine before the
+    command's parser reads the rest (the command's own option list stays what it was; its help shows these in the epilog)."""
+    p = argparse.ArgumentParser(prog="python -m dfmdock_amd dock|refine", add_help=False, allow_abbrev=False, usage=argparse.SUPPRESS)
+    _add_symmetry(p.add_argument_group("Cn symmetric docking (dock and refine)"))
+    return p
+
+
+def _symmetry_epilog():
+    return symmetry_parser().format_help().strip()
+
+
+SYMMETRY_DESTS = ("symmetry", "symmetry_gain", "symmetry_t_start", "symmetry_tolerance", "no_symmetry_snap")
+
+
+def symmetry_kwargs(args, ap=None):
+    """The driver keywords of --symmetry and its options (none without it); the options alone are an error."""
+    def bad(msg):
+        if ap is not None:
+            ap.error(msg)
+        raise SystemExit(msg)
+    if not hasattr(args, "symmetry"):      # a namespace of the command's parser alone (parse_args adds these): no symmetry
+        return {}
+    given = [o for o, v in (("--symmetry-gain", args.symmetry_gain), ("--symmetry-t-start", args.symmetry_t_start),
+                            ("--symmetry-tolerance", args.symmetry_tolerance), ("--no-symmetry-snap", args.no_symmetry_snap or None))
+             if v is not None]
+    if args.symmetry is None:
+        if given:
+            bad(f"{', '.join(given)} need(s) --symmetry")
+        return {}
+    from .symmetry import SymmetryParams, parse_symmetry
+    try:
+        n = parse_symmetry(args.symmetry)
+        par = SymmetryParams(**({} if args.symmetry_gain is None else {"gain_rot": args.symmetry_gain, "gain_tr": args.symmetry_gain}),
+                             **({} if args.symmetry_t_start is None else {"t_start": args.symmetry_t_start}),
+                             snap_last=0 if args.no_symmetry_snap else 1)
+    except ValueError as e:
+        bad(str(e))
+    kw = {"symmetry": n, "symmetry_params": par}
+    if args.symmetry_tolerance is not None:
+        if not (np.isfinite(args.symmetry_tolerance) and args.symmetry_tolerance >= 0):
+            bad("--symmetry-tolerance must be finite and >= 0")
+        kw["symmetry_tolerance"] = args.symmetry_tolerance
+    return kw
+
+
 def _add_common(p):
     p.add_argument("--ckpt", required=True, help="Lightning checkpoint or bare state_dict (torch.save)")
     p.add_argument("--num-steps", type=int, default=40)
@@ -267,7 +333,8 @@ def _add_common(p):
 def build_parser():
     ap = argparse.ArgumentParser(prog="python -m dfmdock_amd", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
-    d = sub.add_parser("dock", help="dock one receptor / ligand PDB pair (inference_single.py)")
+    d = sub.add_parser("dock", help="dock one receptor / ligand PDB pair (inference_single.py)", epilog=_symmetry_epilog(),
+                       formatter_class=argparse.RawDescriptionHelpFormatter)
     d.add_argument("pdb_1", help="receptor PDB")
     d.add_argument("pdb_2", help="ligand PDB")
     d.add_argument("--features", required=True, help=".npz with rec_esm / lig_esm [n,1280] (or rec_x / lig_x [n,1301])")
@@ -283,7 +350,8 @@ def build_parser():
     for a in ANALYSES:
         a.add(d)
     _add_common(d)
-    r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)")
+    r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)", epilog=_symmetry_epilog(),
+                       formatter_class=argparse.RawDescriptionHelpFormatter)
     r.add_argument("pdb_1", help="receptor PDB")
     r.add_argument("pdb_2", help="ligand PDB, in the pose to refine")
     r.add_argument("--features", required=True, help=".npz with rec_esm / lig_esm [n,1280] (or rec_x / lig_x [n,1301])")
@@ -355,7 +423,14 @@ def build_parser():
 
 def parse_args(argv=None):
     ap = build_parser()
+    argv = list(sys.argv[1:] if argv is None else argv)
+    sym = None
+    if argv and argv[0] in ("dock", "refine"):      # the symmetry options: their own parser first, the command's parser reads the rest
+        sym, argv = symmetry_parser().parse_known_args(argv)
     args = ap.parse_args(argv)
+    for dest in SYMMETRY_DESTS:
+        setattr(args, dest, getattr(sym, dest) if sym is not None else (False if dest == "no_symmetry_snap" else None))
+    symmetry_kwargs(args, ap)      # (checked here, before anything is loaded)
     if args.cmd in ("dock", "rescore") and args.refine_t is not None and args.top_k is None:
         ap.error("--refine-t refines the cluster centres: it needs --top-k")
     if args.cmd == "rescore":
@@ -907,16 +982,23 @@ def cmd_pair(args):
     """dock and refine: one body; they differ in their own driver keywords, their own entries of the line and what --json adds."""
     from . import driver
     dock = args.cmd == "dock"
+    sym_kw = symmetry_kwargs(args)      # (checked before the checkpoint is read)
     model, _ = load_model(args)
     rec, lig, rec_x, lig_x = load_pair(args.pdb_1, args.pdb_2, args.features, model.hp.lm_embed_dim)
     kw = {} if dock else dict(t_begin=args.t_begin, perturb=not args.no_perturb)
+    kw.update(sym_kw)
     if args.restraints:
         from .restraints import read_restraints
         kw.update(restraints=read_restraints(args.restraints, rec, lig), **({"restraint_rank": args.restraint_rank} if dock else {}))
     _pair_kwargs(args, model, kw, models=dock)
-    res = (driver.dock_pair if dock else driver.refine_pair)(
-        model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed, precision=args.precision,
-        out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, **kw)
+    try:
+        res = (driver.dock_pair if dock else driver.refine_pair)(
+            model, rec, lig, rec_x, lig_x, num_samples=args.num_samples, num_steps=args.num_steps, seed=args.seed, precision=args.precision,
+            out_pdb=args.out, max_batch=args.max_batch, selfcheck=not args.no_selfcheck, on_selfcheck_fail=args.on_selfcheck_fail, **kw)
+    except ValueError as e:
+        if sym_kw and str(e).startswith("symmetry"):      # the inputs are no homo-oligomer: the cause, not a traceback
+            raise SystemExit(str(e)) from None
+        raise
     line = {"energy": res["energy"], "output": os.path.abspath(args.out), "num_samples": args.num_samples, "precision": res["precision"]}
     if not dock:
         line.update(t_begin=res["t_begin"], perturb=not args.no_perturb, index=res["index"])
@@ -924,12 +1006,16 @@ def cmd_pair(args):
     if dock and args.restraints:
         line.update(restraints=res["restraints"], restraints_satisfied=res["restraints_satisfied"],
                     restraint_energy=res["restraint_energy"], restraint_rank=res["restraint_rank"], index=res["index"])
+    if sym_kw:
+        line.update(symmetry=res["symmetry"], index=res["index"])
     _finish_line(args, model, res, rec, lig, line, kw, models=dock, native_extra=() if dock else ("start_metrics",))
     if args.json:
         if dock:
             extra = {"trajectories": {k: [float(x) for x in v] for k, v in res["trajectories"].items()}} if args.restraints else {}
         else:
             extra = {"energies": [float(e) for e in res["trajectories"]["energy"]]}
+        if sym_kw:      # every trajectory's m, theta, screw, sym_rmsd, closure
+            extra["symmetry_data"] = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in res["symmetry_data"].items()}
         with open(args.json, "w") as f:
             json.dump(dict(line, selfcheck=res["selfcheck"], **extra), f, default=float)
     return 0

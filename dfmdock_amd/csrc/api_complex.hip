@@ -258,6 +258,91 @@ extern "C" int dfm_restraint_eval(dfm_complex *cx, int B, const float *lig_pos, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// defaults of dfm_symmetry_params: starting values, not measured against a trained checkpoint
+static dfm_symmetry_params default_symmetry_params() { return dfm_symmetry_params{0.5f, 0.5f, 0.3f, 10.0f, 1.0f, 1}; }
+
+extern "C" int dfm_complex_set_symmetry(dfm_complex *cx, int n, const dfm_symmetry_params *par)
+{
+    if (!cx) return fail(DFM_E_INVALID, "NULL argument");
+    dfm_symmetry_params pr = par ? *par : default_symmetry_params();
+    if (n != 0) {
+        if (n < SYM_MIN_ORDER || n > SYM_MAX_ORDER)
+            return fail(DFM_E_INVALID, "symmetry: need n = 0 or " + std::to_string(SYM_MIN_ORDER) + " <= n <= " + std::to_string(SYM_MAX_ORDER));
+        if (cx->R != cx->L)
+            return fail(DFM_E_INVALID, "symmetry: receptor and ligand must be the same chain (R = " + std::to_string(cx->R) + ", L = " +
+                                           std::to_string(cx->L) + ")");
+    }
+    if (n == 0) pr = default_symmetry_params();      // a clear takes no parameters: whatever p points at is ignored
+    if (!(pr.gain_rot > 0.f && pr.gain_rot <= 1.f) || !(pr.gain_tr > 0.f && pr.gain_tr <= 1.f))
+        return fail(DFM_E_INVALID, "symmetry: gain_rot and gain_tr must lie in (0, 1]");
+    if (!(pr.max_rot > 0.f) || !(pr.max_tr > 0.f) || !std::isfinite(pr.max_rot) || !std::isfinite(pr.max_tr) || std::isnan(pr.t_start))
+        return fail(DFM_E_INVALID, "symmetry: max_rot and max_tr must be finite and > 0, t_start a number");
+    DEVICE_SCOPE(cx->device);
+    HIPCHK(hipStreamSynchronize(cx->stream));
+    cx->sym_n = n; cx->sym_par = pr;
+    // the captured step graph holds the order and the parameters by value (or no symmetry step at all): capture again on the next call
+    if (cx->step_exec) { (void)hipGraphExecDestroy(cx->step_exec); cx->step_exec = nullptr; }
+    return DFM_OK;
+}
+
+SymmetryArgs dfm::symmetry_args(const dfm_complex *cx, float *lig)
+{
+    SymmetryArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.rec_pos = cx->rec_pos; a.R = cx->R; a.L = cx->L; a.all_atoms = cx->m->hp.family == 1;
+    a.n = cx->sym_n;
+    a.gain_rot = cx->sym_par.gain_rot; a.gain_tr = cx->sym_par.gain_tr; a.max_rot = cx->sym_par.max_rot; a.max_tr = cx->sym_par.max_tr;
+    a.t_start = cx->sym_par.t_start; a.snap_last = cx->sym_par.snap_last ? 1 : 0;
+    a.lig = lig;
+    return a;
+}
+
+extern "C" int dfm_symmetry_eval(dfm_complex *cx, int B, const float *lig_pos, dfm_symmetry_out *out)
+{
+    if (!cx || !lig_pos || !out || !out->step) return fail(DFM_E_INVALID, "NULL argument");
+    if (B < 1) return fail(DFM_E_INVALID, "need B >= 1");
+    const size_t nb = (size_t)B;
+    if (cx->sym_n == 0) {      // nothing stored: zeros, as dfm_restraint_eval
+        if (out->theta) std::memset(out->theta, 0, nb * sizeof(double));
+        if (out->screw) std::memset(out->screw, 0, nb * sizeof(double));
+        if (out->axis) std::memset(out->axis, 0, nb * 3 * sizeof(double));
+        if (out->axis_point) std::memset(out->axis_point, 0, nb * 3 * sizeof(double));
+        if (out->fit_rmsd) std::memset(out->fit_rmsd, 0, nb * sizeof(double));
+        if (out->sym_rmsd) std::memset(out->sym_rmsd, 0, nb * sizeof(double));
+        if (out->order_m) std::memset(out->order_m, 0, nb * sizeof(int32_t));
+        std::memset(out->step, 0, nb * 6 * sizeof(float));
+        return DFM_OK;
+    }
+    DEVICE_SCOPE(cx->device);
+    CallGuard guard(cx->stream);
+    DevPool tmp;
+    tmp.bind(cx->stream);
+    float *lig = nullptr, *st = nullptr;
+    double *o = nullptr;
+    HIPCHK(tmp.upload_async(&lig, lig_pos, nb * cx->L * 9, cx->stream));
+    HIPCHK(tmp.alloc(&o, nb * SYM_OUT));
+    HIPCHK(tmp.alloc(&st, nb * 6));
+    SymmetryArgs a = symmetry_args(cx, lig);
+    a.out = o; a.step_out = st;
+    HIPCHK(launch_symmetry(a, B, cx->stream));
+    std::vector<double> h(nb * SYM_OUT);
+    HIPCHK(hipMemcpyAsync(h.data(), o, h.size() * sizeof(double), hipMemcpyDeviceToHost, cx->stream));
+    HIPCHK(hipMemcpyAsync(out->step, st, nb * 6 * sizeof(float), hipMemcpyDeviceToHost, cx->stream));
+    HIPCHK(hipStreamSynchronize(cx->stream));
+    for (size_t b = 0; b < nb; ++b) {
+        const double *r = &h[b * SYM_OUT];
+        if (out->theta) out->theta[b] = r[0];
+        if (out->screw) out->screw[b] = r[1];
+        if (out->axis) std::memcpy(out->axis + b * 3, r + 2, 3 * sizeof(double));
+        if (out->axis_point) std::memcpy(out->axis_point + b * 3, r + 5, 3 * sizeof(double));
+        if (out->fit_rmsd) out->fit_rmsd[b] = r[8];
+        if (out->sym_rmsd) out->sym_rmsd[b] = r[9];
+        if (out->order_m) out->order_m[b] = (int32_t)r[10];
+    }
+    return guard.done(DFM_OK);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Layer 0 behind the message table: budgets.  The table costs 516 B per intra-chain ordered pair (8 M pairs = 4.1 GB: 2000 + 2000
 // residues); beyond it layer 0 is evaluated directly (DFM_L0_TABLE=0 in the environment: always).  Eligibility is a property of the
 // COMPLEX alone (r04 also switched to the direct evaluation above 32 M edges per batched evaluation, so a trajectory's bits

@@ -13,7 +13,7 @@ using namespace dfm;
 
 // The sampler behind dfm_sample and dfm_refine: the time grid linspace(t_first, eps, num_steps) and `start`, which fills ws.lig_cur /
 // tr_update / rot_update with the start poses on the handle's stream (per-call device buffers from `tmp`).  Everything after the
-// start - noise scales, last step without noise, annealing, ODE, clash force, restraint step, final evaluation - is shared.
+// start - noise scales, last step without noise, annealing, ODE, clash force, restraint step, symmetry step, final evaluation - is shared.
 using StartFn = std::function<int(DevPool &tmp)>;
 
 // one sampler call: its arguments, its time grid, its per-call device buffers and what they decide
@@ -34,6 +34,9 @@ struct SampleCall {
     // the restraint step (DFM_F_RESTRAINTS with a set stored): after k_heads, before the clash force.  Without the clash force it is the
     // last kernel that moves the pose and takes over k_heads' preparation of it - the flag adds no dependent launch per step
     bool restr = false;
+    // the symmetry step (DFM_F_SYMMETRY with a symmetry stored): the last thing that moves the pose in a step, after the clash force, so
+    // a snapped final pose stays snapped.  Under fuse_prep it is the kernel that prepares the pose (k_heads and k_restraint then do not)
+    bool sym = false;
 };
 
 // the by-value arguments of step i's k_heads launch
@@ -60,8 +63,18 @@ static hipError_t restraint_step(const SampleCall &c, int i, const uint32_t *ctl
     RestraintArgs ra = restraint_args(c.cx, W.lig_cur);
     ra.apply = 1; ra.tr_update = W.tr_update; ra.rot_update = W.rot_update;
     ra.t_dev = W.t_dev; ra.step = (uint32_t)i; ra.ctl = ctl;
-    if (c.fuse_prep) { ra.prep_next = 1; ra.prep_pos = W.pos; ra.prep_ca4 = W.ca4; ra.prep_cb4 = W.cb4; }
+    if (c.fuse_prep && !c.sym) { ra.prep_next = 1; ra.prep_pos = W.pos; ra.prep_ca4 = W.ca4; ra.prep_cb4 = W.cb4; }
     return launch_restraint(ra, c.B, c.cx->stream);
+}
+
+static hipError_t symmetry_step(const SampleCall &c, int i, const uint32_t *ctl)
+{
+    Workspace &W = c.cx->ws;
+    SymmetryArgs sa = symmetry_args(c.cx, W.lig_cur);
+    sa.apply = 1; sa.tr_update = W.tr_update; sa.rot_update = W.rot_update;
+    sa.t_dev = W.t_dev; sa.step = (uint32_t)i; sa.num_steps = (uint32_t)c.num_steps; sa.ctl = ctl;
+    if (c.fuse_prep) { sa.prep_next = 1; sa.prep_pos = W.pos; sa.prep_ca4 = W.ca4; sa.prep_cb4 = W.cb4; }
+    return launch_symmetry(sa, c.B, c.cx->stream);
 }
 
 // the per-call device buffers: injections, traces
@@ -78,7 +91,7 @@ static int sample_buffers(SampleCall &c, const dfm_inject *inj, const dfm_traj_o
     return DFM_OK;
 }
 
-// captures one step (evaluation, k_heads on the device-side scalars, restraint step, clash force) into cx->step_exec
+// captures one step (evaluation, k_heads on the device-side scalars, restraint step, clash force, symmetry step) into cx->step_exec
 static int capture_step_graph(const SampleCall &c, FwdOpts o, uint64_t key)
 {
     dfm_complex *cx = c.cx;
@@ -96,6 +109,7 @@ static int capture_step_graph(const SampleCall &c, FwdOpts o, uint64_t key)
         hipError_t e = launch_heads(ha, s);
         if (e == hipSuccess && c.restr) e = restraint_step(c, 0, W.step_ctl);
         if (e == hipSuccess && (c.flags & DFM_F_CLASH_FORCE)) e = launch_clash_force(cx->rec_pos, c.B, cx->R, cx->L, W.lig_cur, W.tr_update, s);
+        if (e == hipSuccess && c.sym) e = symmetry_step(c, 0, W.step_ctl);
         if (e != hipSuccess) crc = fail(DFM_E_HIP, hipGetErrorString(e));
     }
     const std::string keep = g_err;
@@ -119,11 +133,11 @@ static int run_steps_graph(const SampleCall &c, const FwdOpts &o, bool l0)
     const size_t S = c.num_steps;
     std::vector<StepParams> sp(S);
     for (int i = 0; i < c.num_steps; ++i) sp[i] = step_params(c.grid, i, c.flags, c.tr_noise_scale, c.rot_noise_scale, c.num_steps);
-    const uint32_t ctl_h[4] = {0u, (uint32_t)c.seed, (uint32_t)(c.seed >> 32), 0u};
+    const uint32_t ctl_h[4] = {0u, (uint32_t)c.seed, (uint32_t)(c.seed >> 32), (uint32_t)c.num_steps};      // ([3]: the symmetry step's "last step")
     HIPCHK(hipMemcpyAsync(W.step_params, sp.data(), S * sizeof(StepParams), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(W.step_ctl, ctl_h, sizeof(ctl_h), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));      // (pageable sources: the copies have read them)
-    const uint64_t key = graph_key(c.B, c.flags, l0, c.restr);
+    const uint64_t key = graph_key(c.B, c.flags, l0, c.restr, c.sym);
     if (!cx->step_exec || cx->step_key != key || cx->step_gen != cx->buf_gen) {
         const int rc = capture_step_graph(c, o, key);
         if (rc) return rc;
@@ -133,7 +147,7 @@ static int run_steps_graph(const SampleCall &c, const FwdOpts &o, bool l0)
     return DFM_OK;
 }
 
-// the plain step loop: evaluation, k_heads with the step's scalars by value, restraint step, clash force
+// the plain step loop: evaluation, k_heads with the step's scalars by value, restraint step, clash force, symmetry step
 static int run_steps(const SampleCall &c, FwdOpts o)
 {
     dfm_complex *cx = c.cx;
@@ -148,12 +162,13 @@ static int run_steps(const SampleCall &c, FwdOpts o)
         if (rc) return rc;
         HeadArgs ha;
         step_head_args(c, i, ha);
-        if (c.fuse_prep && !c.restr) { ha.prep_next = 1; ha.rec_pos = cx->rec_pos; ha.prep_pos = W.pos; ha.prep_ca4 = W.ca4; ha.prep_cb4 = W.cb4; }
+        if (c.fuse_prep && !c.restr && !c.sym) { ha.prep_next = 1; ha.rec_pos = cx->rec_pos; ha.prep_pos = W.pos; ha.prep_ca4 = W.ca4; ha.prep_cb4 = W.cb4; }
         HIPCHK(launch_heads(ha, s));
         if (c.restr) HIPCHK(restraint_step(c, i, nullptr));
         if (c.flags & DFM_F_CLASH_FORCE)   // inference_base.py:458-461
             HIPCHK(launch_clash_force(cx->rec_pos, c.B, cx->R, cx->L, W.lig_cur, W.tr_update, s));
-        if (c.tp_d && (c.restr || (c.flags & DFM_F_CLASH_FORCE)))      // the trace holds the pose after the whole step
+        if (c.sym) HIPCHK(symmetry_step(c, i, nullptr));
+        if (c.tp_d && (c.restr || c.sym || (c.flags & DFM_F_CLASH_FORCE)))      // the trace holds the pose after the whole step
             HIPCHK(hipMemcpy2DAsync(c.tp_d + (size_t)i * L * 9, S * L * 9 * 4, W.lig_cur, L * 9 * 4, L * 9 * 4, c.B, hipMemcpyDeviceToDevice, s));
     }
     return DFM_OK;
@@ -230,6 +245,7 @@ static int sample_impl(dfm_complex *cx, int B, int num_steps, float eps, float t
     c.use_graph = (graph_env_on || (flags & DFM_F_GRAPH)) && !(flags & (DFM_F_PROFILE | DFM_F_STEP_ENERGY)) && !inj && !c.tp_d && !c.tsc_d;
     c.fuse_prep = !c.use_graph && !(flags & DFM_F_CLASH_FORCE);
     c.restr = (flags & DFM_F_RESTRAINTS) && cx->rs_G > 0;
+    c.sym = (flags & DFM_F_SYMMETRY) && cx->sym_n > 0;
     if ((rc = c.use_graph ? run_steps_graph(c, o, l0) : run_steps(c, o)) != DFM_OK) return rc;
     if ((rc = finish_sample(c, o, out)) != DFM_OK) return rc;
     if (o.profile && (rc = finish_profile(cx)) != DFM_OK) return rc;

@@ -2,7 +2,7 @@
 // handle, the options of one score evaluation, and the helpers that cross files.
 //   api.hip          globals, device, hyper-parameters, diffusion coefficients, configuration string, cache and diagnostics calls
 //   api_model.hip    the weight blob's map, the packers, dfm_model_create / destroy
-//   api_complex.hip  the complex handle: lifecycle, pose, homomer flag, restraints, workspace, time grid, layer-0 message table
+//   api_complex.hip  the complex handle: lifecycle, pose, homomer flag, restraints, symmetry, workspace, time grid, layer-0 message table
 //   api_forward.hip  one batched score evaluation (enqueue_forward), the scaffold of a public call, the profile read-out
 //   api_score.hip    dfm_score, dfm_score_distogram, dfm_complex_selfcheck
 //   api_sample.hip   the sampler behind dfm_sample and dfm_refine, the IGSO(3) tables, dfm_forward_marginal
@@ -37,7 +37,7 @@ struct Workspace {
     uint32_t *l0_src = nullptr; uint4 *l0_rows = nullptr; uint16_t *l0_x = nullptr; uint32_t *l0_counter = nullptr;
     float *l0_x32 = nullptr;      // fp32 engine: the row list's messages (1 KiB per row)
     unsigned long long *l0_miss_total = nullptr;
-    // replayed step graph: {evaluations started, seed lo, seed hi, -} and the per-step scalars of the call's time grid
+    // replayed step graph: {evaluations started, seed lo, seed hi, num_steps} and the per-step scalars of the call's time grid
     uint32_t *step_ctl = nullptr; StepParams *step_params = nullptr;
     // t_dev / hid_base / step_params live in their own pool, sized for max(Bcap, the longest time grid asked for so far)
     DevPool tpool;
@@ -86,6 +86,9 @@ struct dfm_complex {
     float *rs_upper = nullptr, *rs_weight = nullptr;
     int rs_G = 0, rs_nbig = 0;
     dfm_restraint_params rs_par = {};
+    // Cn symmetry (dfm_complex_set_symmetry): the order (0: none stored) and the step's parameters
+    int sym_n = 0;
+    dfm_symmetry_params sym_par = {};
 };
 
 namespace dfm {
@@ -151,6 +154,7 @@ int ensure_time_grid(dfm_complex *cx, size_t n);
 int ensure_workspace(dfm_complex *cx, int B, bool bf16, bool l0);
 int build_l0_table(dfm_complex *cx, float *build_ms, bool fp32);
 RestraintArgs restraint_args(const dfm_complex *cx, float *lig);
+SymmetryArgs symmetry_args(const dfm_complex *cx, float *lig);
 
 // ---- api_forward.hip
 // start of a public call: the workspace for B trajectories of this engine (with the layer-0 buffers when l0), the profile, the event

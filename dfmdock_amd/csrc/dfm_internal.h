@@ -388,6 +388,30 @@ struct RestraintArgs {
 };
 hipError_t launch_restraint(const RestraintArgs &a, int B, hipStream_t s);
 
+// Cn symmetry step (kernels_symmetry.hip: k_symmetry; include/dfmdock_amd.h: dfm_complex_set_symmetry)
+constexpr int SYM_MIN_ORDER = 2, SYM_MAX_ORDER = 24;
+constexpr int SYM_OUT = 12;      // doubles per pose of the evaluation mode: theta, screw, axis[3], axis_point[3], fit_rmsd, sym_rmsd, m, -
+struct SymmetryArgs {
+    const float *rec_pos;       // [R][9]  the receptor as the sampler sees it; R == L
+    int R, L, all_atoms;        // all_atoms: rotate about the all-backbone-atom centroid (second family, as k_heads)
+    int n;                      // order of the cyclic group
+    float gain_rot, gain_tr, max_rot, max_tr, t_start;
+    int snap_last;
+    float *lig;                 // [B][L][9]  pose (moved in place when apply)
+    int apply;                  // sampler: move the pose and the bookkeeping; 0: evaluation only (dfm_symmetry_eval)
+    float *tr_update, *rot_update;   // [B][3] (apply)
+    // sampler: step i runs only when t_dev[i] <= t_start, and is the last one when i + 1 == num_steps; i = step, or ctl[0] - 1 with
+    // num_steps = ctl[3] in the replayed step graph.  t_dev == nullptr: always, never the last
+    const float *t_dev;
+    uint32_t step, num_steps;
+    const uint32_t *ctl;
+    double *out;                // [B][SYM_OUT] (or nullptr)
+    float *step_out;            // [B][6] dtau, domega (or nullptr)
+    int prep_next;              // prepare the pose for the next evaluation (what k_prep_pose writes), as k_heads' prep_next
+    float4 *prep_pos, *prep_ca4, *prep_cb4;
+};
+hipError_t launch_symmetry(const SymmetryArgs &a, int B, hipStream_t s);
+
 // pose clustering (kernels_cluster.hip; include/dfmdock_amd.h: dfm_pose_rmsd / dfm_pose_cluster).  X [B][L9] pose rows, res [n_res] the
 // residue subset or nullptr (n_res = L); rmsd [B][B] (evaluation) or, when rmsd is nullptr, mask [B][ceil(B/32)] (bit: rmsd <= radius)
 constexpr int CL_MAX_POSES = 65536;

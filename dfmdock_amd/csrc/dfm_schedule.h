@@ -90,11 +90,11 @@ inline EngineSel engine_sel(uint32_t flags)
 inline bool table_by_default(const EngineSel &s, uint32_t flags) { return s.has_table && !(flags & DFM_F_NO_L0_TABLE); }
 
 // what the captured step graph of a handle was captured for: the batch, the flags that change its nodes, whether layer 0 goes through
-// the table and whether the restraint step is part of it
-inline uint64_t graph_key(int B, uint32_t flags, bool l0, bool restr)
+// the table and whether the restraint step and the symmetry step are part of it
+inline uint64_t graph_key(int B, uint32_t flags, bool l0, bool restr, bool sym = false)
 {
     return ((uint64_t)(uint32_t)B << 32) | (uint64_t)(flags & (DFM_F_MFMA16 | DFM_F_F16 | DFM_F_BF16_OPS | DFM_F_CLASH_FORCE | DFM_F_ODE | DFM_F_NO_L0_TABLE))
-           | (l0 ? 1ull << 31 : 0ull) | (restr ? (uint64_t)DFM_F_RESTRAINTS : 0ull);
+           | (l0 ? 1ull << 31 : 0ull) | (restr ? (uint64_t)DFM_F_RESTRAINTS : 0ull) | (sym ? (uint64_t)DFM_F_SYMMETRY : 0ull);
 }
 
 }  // namespace dfm

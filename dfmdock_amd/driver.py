@@ -962,6 +962,111 @@ def _center(model):
     return "all_atoms" if model.hp.family == 1 else "ca"
 
 
+def _check_symmetry(rec, lig, symmetry, symmetry_params, tolerance):
+    """None (no symmetry) or {n, params, tolerance, input_rmsd} of dock_pair / refine_pair's `symmetry`, checked before anything is
+    sampled: the two inputs must be ONE chain each, of one sequence, and rigid images of each other within `tolerance` A (the Kabsch
+    rmsd over all backbone atoms - rescore's --fit-tolerance rule)."""
+    if symmetry is None:
+        if symmetry_params is not None:
+            raise ValueError("symmetry_params needs symmetry (the order n of the assembly)")
+        return None
+    from . import symmetry as SY
+    n = SY.check_order(symmetry)
+    if not (np.isfinite(tolerance) and tolerance >= 0):
+        raise ValueError("symmetry_tolerance must be finite and >= 0")
+    for side, c in (("receptor", rec), ("ligand", lig)):
+        ids = pdbio._chain_ids(c["residues"])
+        if len(ids) > 1:
+            raise ValueError(f"symmetry: the {side} has more than one chain id ({''.join(ids)}): a Cn assembly is built from ONE chain")
+    if rec["seq"] != lig["seq"]:
+        raise ValueError(f"symmetry: receptor and ligand sequences differ ({len(rec['seq'])} and {len(lig['seq'])} residues): "
+                         "a Cn assembly needs two copies of the same chain")
+    _, _, rmsd = SY.fit_transform(rec["bb_coords"], lig["bb_coords"])
+    if not rmsd <= tolerance:
+        raise ValueError(f"symmetry: the two input monomers are no rigid images of each other: Kabsch rmsd {rmsd:.3g} A over the backbone "
+                         f"is above symmetry_tolerance = {tolerance} A")
+    return {"n": n, "params": symmetry_params, "tolerance": float(tolerance), "input_rmsd": float(rmsd)}
+
+
+def _set_symmetry(model, gx, sym):
+    """Stores the symmetry of a checked `sym` on the handle; a model with the 67th position channel gets its homomer flag (a 66-channel
+    model has no such channel: the entry point refuses it)."""
+    if model.hp.positional_embed_dim == 67:
+        gx.set_homomer(True)
+    gx.set_symmetry(sym["n"], sym["params"])
+
+
+def _file_center(model, lig):
+    """The point pdbio.apply_pose_all_atom (and every dfm_pose_* call of the drivers) rotates this ligand about, float64 [3]."""
+    if model.hp.family == 1:
+        return np.asarray(lig["aa_coords"], np.float64).reshape(-1, 3).mean(0)
+    return np.asarray(lig["bb_coords"], np.float64)[:, 1].mean(0)
+
+
+def _pose_bb(run, i):
+    """A symmetric run: the ligand backbone of trajectory i's final pose as the written files hold it (None otherwise)."""
+    if run.sym is None:
+        return None
+    from . import symmetry as SY
+    return SY._pose_backbone(run.lig["bb_coords"], run.cols["rot_update"][i], run.cols["tr_update"][i], _file_center(run.model, run.lig))
+
+
+def _symmetry_columns(run):
+    """The symmetry record of EVERY trajectory's final pose as arrays (run.data["symmetry"]): m, theta, screw, sym_rmsd, closure."""
+    from . import symmetry as SY
+    recs = [SY.record(run.rec["bb_coords"], _pose_bb(run, i), run.sym["n"], _center(run.model)) for i in range(len(run.cols["energy"]))]
+    run.sym["records"] = recs
+    return {k: np.asarray([r[k] for r in recs]) for k in ("m", "theta", "screw", "sym_rmsd", "closure")}
+
+
+def _ring_clashes(run, indices):
+    """n >= 4: the heavy-atom clash count of copy 0 (the receptor) against copies k = 2 .. n // 2 of the poses `indices`, summed over k -
+    one call of the all-atom screen over all of them (copy k placed by symmetry.copy_poses).  Copies 1 and n - 1 are the docked interface
+    itself; a ring that closes on paper can still run copy 2 into copy 0."""
+    from . import symmetry as SY
+    n = run.sym["n"]
+    ks = list(range(2, n // 2 + 1))
+    ra, la, cen = sterics_inputs(run.rec, run.lig, run.model.hp.family)
+    rot, tr = run.poses()
+    rots, trs = [], []
+    for i in indices:
+        rk, tk = SY.copy_poses(run.rec["bb_coords"], run.lig["bb_coords"], rot[i], tr[i], _file_center(run.model, run.lig), n, _center(run.model))
+        rots += [rk[k - 1] for k in ks]
+        trs += [tk[k - 1] for k in ks]
+    with run.model.atoms(ra, la, cen) as at:
+        out = at.sterics(np.asarray(rots, np.float32).reshape(-1, 3), np.asarray(trs, np.float32).reshape(-1, 3))
+    return [int(v) for v in out["n_clash"].reshape(len(indices), len(ks)).sum(1)]
+
+
+def _symmetry_record(run, i, ring=None):
+    return dict(run.sym["records"][i], **({} if ring is None else {"ring_clashes": ring}))
+
+
+def _write_pose(run, path, lig_aa, lig_bb, remarks=None):
+    """One written model: receptor + ligand at lig_aa - or, in a symmetric run, all n chains: the receptor under its own chain id, then
+    the ligand (lig_aa, its backbone lig_bb) and its images under the powers of the projected transform T' (symmetry.evaluate: a pure
+    rotation by theta* about the assembly's axis) under the next unused chain letters."""
+    rec, lig = run.rec, run.lig
+    if run.sym is None:
+        return pdbio.write_complex_pdb(path, list(rec["atoms"]), lig["atoms"], lig_aa, remarks=remarks)
+    from . import symmetry as SY
+    n = run.sym["n"]
+    ev = SY.evaluate(rec["bb_coords"], lig_bb, n, center=_center(run.model))
+    if ev["m"] > 0:
+        Qp = SY.axis_angle_to_matrix(ev["theta_star"] * ev["axis"])
+        taup = ev["axis_point"] - Qp @ ev["axis_point"]
+    else:      # no axis (or a non-finite pose): the fit's own transform
+        Qp, taup = (ev["Q"], ev["tau"]) if ev["Q"] is not None else (np.full((3, 3), np.nan), np.full(3, np.nan))
+    used = set(pdbio._chain_ids(rec["residues"]))
+    letters = [ch for ch in "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789" if ch not in used]
+    atoms, coords = [], []
+    for k in range(1, n):
+        Qk, tk = SY.transform_power(Qp, taup, k - 1)
+        atoms += [dict(a, chain=letters[k - 1]) for a in lig["atoms"]]
+        coords.append(np.asarray(lig_aa, np.float64) @ Qk.T + tk)
+    pdbio.write_complex_pdb(path, list(rec["atoms"]), atoms, np.concatenate(coords, 0), remarks=remarks)
+
+
 class _Run:
     """One pair-driver call after its sampling: what _finish, the analyses and _top_models pass around.  cols: every trajectory's energy, rot_update,
     tr_update (and the driver's own columns); opts[name]: the checked options of every analysis of ANALYSES that is on; data[name]: the arrays it produced;
@@ -972,6 +1077,7 @@ class _Run:
         self.precision, self.selfcheck, self.out_pdb, self.native, self.seed = precision, selfcheck, out_pdb, native, seed
         self.opts, self.data = {name: o for name, o in (opts or {}).items() if o is not None}, {}
         self.k, self.key, self.bad, self.ranked_by = None, None, None, "energy"
+        self.sym = None      # a symmetric run (_check_symmetry's dict): every written model holds all n chains, every pose a `symmetry` record
 
     def any(self):      # is any analysis on?  Then the result also carries `index` and every trajectory, and dock_pair picks among all of them at once
         return bool(self.opts)
@@ -1147,8 +1253,10 @@ def _finish(run, pick, entries, clu=None, refine=None):
     stage("describe")
     k = run.k
     lig_aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][k], cols["tr_update"][k], center=_center(model))
+    if run.sym is not None:
+        run.data["symmetry"] = _symmetry_columns(run)
     if run.out_pdb:
-        pdbio.write_complex_pdb(run.out_pdb, list(rec["atoms"]), lig["atoms"], lig_aa, remarks=_remarks(run.data.get("sterics"), k))
+        _write_pose(run, run.out_pdb, lig_aa, _pose_bb(run, k), remarks=_remarks(run.data.get("sterics"), k))
     res = {"energy": float(cols["energy"][k]), "rot_update": cols["rot_update"][k].copy(), "tr_update": cols["tr_update"][k].copy(),
            "lig_aa_coords": lig_aa, "precision": run.precision, "selfcheck": run.selfcheck, **entries(k)}
     for a in on:
@@ -1160,6 +1268,15 @@ def _finish(run, pick, entries, clu=None, refine=None):
         res["metrics"] = native_metrics(model, run.native, rec["bb_coords"], pose)[0]
     if clu is not None:
         res.update(_top_models(run, clu))
+    if run.sym is not None:      # the kept pose and every model: their record; n >= 4: the ring screen of all of them in one call
+        idx = [k] + [m["index"] for m in res.get("models", [])]
+        ring = _ring_clashes(run, idx) if run.sym["n"] >= 4 else [None] * len(idx)
+        res["symmetry"] = _symmetry_record(run, k, ring[0])
+        for m, rc in zip(res.get("models", []), ring[1:]):
+            m["symmetry"] = _symmetry_record(run, m["index"], rc)
+        res["symmetry_data"] = dict(run.data["symmetry"], n=run.sym["n"], tolerance=run.sym["tolerance"], input_rmsd=run.sym["input_rmsd"])
+        res.setdefault("index", k)
+    if clu is not None:
         if refine is not None:
             refine_models(run, res["models"], **refine)
             gx.close()
@@ -1169,7 +1286,7 @@ def _finish(run, pick, entries, clu=None, refine=None):
 def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_steps=40, seed=0, precision="mfma16",
               out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", restraints=None,
               restraint_rank="satisfied", restraint_params=None, top_k=None, cluster_radius=4.0, cluster_rule="energy", refine_t=None,
-              refine_samples=8, native=None, **sampler_kw):
+              refine_samples=8, native=None, symmetry=None, symmetry_params=None, symmetry_tolerance=0.1, **sampler_kw):
     """inference() of the reference for two parsed PDB chains (pdbio.backbone_from_atoms dicts) and their pre-computed node features; returns
     {'energy': min energy} and writes the best pose.  `sampler_kw`: `rank` and the analysis keywords described below (their names and defaults:
     ANALYSES; checked by _analysis_options before anything is sampled) and, beyond those, the sampler options the reference's pair loop passes
@@ -1245,7 +1362,20 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     every trajectory (ensemble_pairpot: the heavy atoms the file's type names fit).  The result gains `pair_potential` ({energy in
     kcal/mol, n_pairs, n_untyped, T, NB, cutoff} of the kept pose), `pairpot_data` (the arrays and the rot_update / tr_update they are of), `index` and `trajectories`; every model
     of `top_k` gains `pair_potential`.  rank="pairpot" (needs pair_potential) keeps the pose with the lowest energy instead (ties: lower
-    index; it overrides restraint_rank and becomes the clustering key of top_k)."""
+    index; it overrides restraint_rank and becomes the clustering key of top_k).
+
+    `symmetry` (an order n in 2 .. 24): Cn symmetric docking of a homo-oligomer.  Receptor and ligand must be ONE chain each, of the same
+    sequence, and rigid images of each other within `symmetry_tolerance` A (Kabsch rmsd of the backbones); anything else raises a
+    ValueError that names the cause, before anything is sampled.  The sampler runs with the symmetry step (DFM_F_SYMMETRY,
+    `symmetry_params`: symmetry.SymmetryParams or the defaults - starting values, not measured against a trained checkpoint); a model
+    with the 67th position channel gets its homomer flag.  The result gains `symmetry` ({n, m, theta, screw, sym_rmsd, closure, axis,
+    axis_point} of the kept pose; closure: the largest displacement of a receptor atom under T^n, on the host; for n >= 4 also
+    ring_clashes, the heavy-atom clashes of the receptor against copies 2 .. n / 2 from the all-atom screen - reported, nothing is
+    filtered by it), `symmetry_data` (m, theta, screw, sym_rmsd, closure of every trajectory) and `index`; every model of `top_k` gains
+    `symmetry` (of its cluster centre) and, under `refine_t`, `refined_symmetry` (the same record without ring_clashes, of the refined pose
+    its file holds; the refinement samples with the symmetry step too).  out_pdb and the model files hold all n chains: the receptor under its chain id, the copies under the next unused
+    letters."""
+    sym = _check_symmetry(rec, lig, symmetry, symmetry_params, symmetry_tolerance)
     opts = _analysis_options(model, max_batch, sampler_kw)
     if native is not None:
         _check_native(native, len(rec["bb_coords"]), len(lig["bb_coords"]))
@@ -1254,8 +1384,10 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         raise ValueError(f"restraint_rank must be 'satisfied' or 'energy', got {restraint_rank!r}")
     clu = _check_models(top_k, cluster_radius, cluster_rule)
     refine = None if refine_t is None else dict(t_begin=float(refine_t), n=int(refine_samples), num_steps=num_steps,
-                                                restraints=restraints is not None, **sampler_kw)
+                                                restraints=restraints is not None, **({"symmetry": True} if sym else {}), **sampler_kw)
     gx = engine.Complex(model, rec_x, lig_x, rec["bb_coords"], lig["bb_coords"])
+    if sym:      # (before the self-check: the homomer channel changes what the engines compute)
+        _set_symmetry(model, gx, sym)
     precision, chk = checked_precision(gx, precision, "pair", selfcheck, on_selfcheck_fail, seed=seed)
     restrained = restraints is not None
     if restrained:
@@ -1264,7 +1396,8 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     best, k0, done = None, None, 0
     while done < num_samples:
         b = min(max_batch, num_samples - done)
-        r = gx.sample(B=b, num_steps=num_steps, seed=seed + done, restraints=restrained, **engine.precision_kwargs(precision), **sampler_kw)
+        r = gx.sample(B=b, num_steps=num_steps, seed=seed + done, restraints=restrained, symmetry=sym is not None,
+                      **engine.precision_kwargs(precision), **sampler_kw)
         if restrained:      # the restraint terms of the final poses, on the sampler's own kernel
             ev = gx.restraint_eval(r["lig_pos"])
             r["restraint_energy"], r["restraints_satisfied"] = ev["energy"], ev["n_satisfied"]
@@ -1276,6 +1409,7 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
         done += b
     cols = {c: np.concatenate(v, 0) for c, v in cols.items()}
     run = _Run(model, gx, rec, lig, cols, precision, opts, chk, out_pdb, native, seed)
+    run.sym = sym
     if not restrained:
         # the loop's own minimum; with any analysis on, the pick is among all trajectories at once (the first minimum: the same pose)
         pick = (np.argmin if run.any() else (lambda energy: k0), "energy")
@@ -1294,7 +1428,8 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
 
 def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_samples=32, num_steps=40, seed=0, precision="mfma16",
                 out_pdb="output.pdb", max_batch=256, selfcheck=True, on_selfcheck_fail="fp32", perturb=True, restraints=None,
-                restraint_params=None, native=None, start_shift=None, **sampler_kw):
+                restraint_params=None, native=None, start_shift=None, symmetry=None, symmetry_params=None, symmetry_tolerance=0.1,
+                **sampler_kw):
     """Local refinement of the pose the two parsed PDB chains are in (engine.Complex.refine, dfm_refine): num_samples trajectories start from that pose
     noised with the forward process at t_begin (perturb=False: from the pose itself) and run the sampler's steps down from t_begin; like dock_pair the
     minimum-energy one is kept, applied to the all-atom ligand and written to out_pdb.  Returns dock_pair's dict plus `t_begin`, `index` and `trajectories`
@@ -1302,7 +1437,10 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
     `native`, `rank` and every analysis keyword: as for dock_pair (there are no models here, so min_bsa only turns bsa on); with `native` the result also
     gains `start_metrics` of the pose the refinement started from.
     `start_shift` ([num_samples,3]): trajectory i starts from the input pose translated by start_shift[i] (the engine's start_pos); the
-    shift is added to its tr_update, so (rot_update, tr_update) keep mapping the INPUT pose onto the final one."""
+    shift is added to its tr_update, so (rot_update, tr_update) keep mapping the INPUT pose onto the final one.
+    `symmetry`, `symmetry_params`, `symmetry_tolerance`: as for dock_pair (the symmetry step fits the receptor onto every pose itself: it
+    needs no reference ligand, so foreign start poses are fine)."""
+    sym = _check_symmetry(rec, lig, symmetry, symmetry_params, symmetry_tolerance)
     opts = _analysis_options(model, max_batch, sampler_kw)
     if native is not None:
         _check_native(native, len(rec["bb_coords"]), len(lig["bb_coords"]))
@@ -1311,6 +1449,8 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
         if start_shift.shape[0] != num_samples:
             raise ValueError(f"start_shift must be [{num_samples},3], got {start_shift.shape}")
     gx = engine.Complex(model, rec_x, lig_x, rec["bb_coords"], lig["bb_coords"])
+    if sym:
+        _set_symmetry(model, gx, sym)
     precision, chk = checked_precision(gx, precision, "pair", selfcheck, on_selfcheck_fail, seed=seed)
     if restraints is not None:
         gx.set_restraints(restraints, restraint_params)
@@ -1322,7 +1462,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
         if start_shift is not None:      # a translation commutes with the rotation about the (equally translated) centre
             skw["start_pos"] = gx.lig_pos0[None] + start_shift[done:done + b, None, None, :]
         r = gx.refine(B=b, t_begin=t_begin, perturb=perturb, num_steps=num_steps, seed=seed + done, restraints=restraints is not None,
-                      **engine.precision_kwargs(precision), **skw)
+                      symmetry=sym is not None, **engine.precision_kwargs(precision), **skw)
         if start_shift is not None:
             r["tr_update"] = (r["tr_update"] + start_shift[done:done + b]).astype(np.float32)
         for c in cols:
@@ -1330,6 +1470,7 @@ def refine_pair(model: engine.Model, rec, lig, rec_x, lig_x, t_begin=0.1, num_sa
         done += b
     cols = {k: np.concatenate(v, 0) for k, v in cols.items()}
     run = _Run(model, gx, rec, lig, cols, precision, opts, chk, out_pdb, native, seed)
+    run.sym = sym
     res = _finish(run, (np.argmin, "energy"),      # the first minimum wins, as in dock_pair
                   lambda k: {"index": k, "t_begin": float(t_begin), "trajectories": cols})
     if native is not None:
@@ -1436,10 +1577,13 @@ def refine_models(run, models, t_begin, n, num_steps, restraints=False, **sample
     for k, m in enumerate(models):
         j = kept[k]
         m.update(refined_energy=float(r["energy"][j]), refined_index=j - k * n)
+        if run.sym is not None:      # `symmetry` describes the cluster centre; the file written below holds the refined pose: its own record
+            from . import symmetry as SY
+            m["refined_symmetry"] = SY.record(rec["bb_coords"], r["lig_pos"][j], run.sym["n"], _center(model))
         if run.out_pdb:
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][cen[k]], cols["tr_update"][cen[k]], center=center)
             aa = pdbio.apply_pose_all_atom(aa, start[k], r["rot_update"][j], r["tr_update"][j], center=center)
-            pdbio.write_complex_pdb(model_path(run.out_pdb, m["rank"]), list(rec["atoms"]), lig["atoms"], aa)
+            _write_pose(run, model_path(run.out_pdb, m["rank"]), aa, r["lig_pos"][j])
     return models
 
 
@@ -1467,7 +1611,7 @@ def _top_models(run, clu):
                 models[-1].update(summary if a.model_key is None else {a.model_key: summary})
         if run.out_pdb:
             aa = pdbio.apply_pose_all_atom(lig["aa_coords"], lig["bb_coords"], cols["rot_update"][c], cols["tr_update"][c], center=_center(model))
-            pdbio.write_complex_pdb(model_path(run.out_pdb, k + 1), list(rec["atoms"]), lig["atoms"], aa, remarks=_remarks(sd, c))
+            _write_pose(run, model_path(run.out_pdb, k + 1), aa, _pose_bb(run, c), remarks=_remarks(sd, c))
     if run.native is not None and models:
         cen = [m["index"] for m in models]
         poses = rebuild_backbone(run.lig0, cols["rot_update"][cen], cols["tr_update"][cen], model.hp.family)

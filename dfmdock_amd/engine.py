@@ -757,6 +757,7 @@ class Complex:
             L.check(-2, "dfm_complex_create")
         self.K = L.lib().dfm_complex_degree(self._h)
         self.n_restraints = 0
+        self.symmetry = 0
         self.lig_pos0 = lig_pos.reshape(self.L, 3, 3).copy()
 
     def close(self):
@@ -808,6 +809,36 @@ class Complex:
         o = dict(energy=np.zeros(B, np.float32), n_satisfied=np.zeros(B, np.int32), step=np.zeros((B, 6), np.float32))
         L.check(L.lib().dfm_restraint_eval(self._h, B, _p(lp), _p(o["energy"]), _p(o["n_satisfied"], L.I32P), _p(o["step"])),
                 "dfm_restraint_eval")
+        return o
+
+    def set_symmetry(self, n, params=None):
+        """Store the order n of a cyclic assembly (2 .. 24; 0 or None clears it) and the step's parameters (symmetry.SymmetryParams,
+        None: the defaults) - dfm_complex_set_symmetry.  The ligand must be the receptor's own chain (R == L).
+        `sample(symmetry=True)` / `refine(symmetry=True)` apply the symmetry step."""
+        n = int(n or 0)
+        par = None if params is None else params.to_c()
+        rc = L.lib().dfm_complex_set_symmetry(self._h, n, C.byref(par) if par is not None else None)
+        L.check(rc, "dfm_complex_set_symmetry")
+        self.symmetry = n
+
+    def symmetry_eval(self, lig_pos):
+        """The stored symmetry at poses lig_pos [B,L,3,3] (or [L,3,3]) on the GPU, with the sampler's own kernel (dfm_symmetry_eval):
+        float64 theta [B], screw [B], axis [B,3], axis_point [B,3], fit_rmsd [B], sym_rmsd [B]; int32 order_m [B]; float32 step [B,6] =
+        dtau, domega of a non-final step.  The definition: symmetry.evaluate."""
+        lp = _f32(lig_pos)
+        if lp.ndim == 3:
+            lp = lp[None]
+        B = lp.shape[0]
+        if lp.shape[1:] != (self.L, 3, 3):
+            raise ValueError(f"lig_pos must be [B,{self.L},3,3]")
+        o = dict(theta=np.zeros(B), screw=np.zeros(B), axis=np.zeros((B, 3)), axis_point=np.zeros((B, 3)), fit_rmsd=np.zeros(B),
+                 sym_rmsd=np.zeros(B), order_m=np.zeros(B, np.int32), step=np.zeros((B, 6), np.float32))
+        out = L.SymmetryOutC()
+        F64P = C.POINTER(C.c_double)
+        for k in ("theta", "screw", "axis", "axis_point", "fit_rmsd", "sym_rmsd"):
+            setattr(out, k, _p(o[k], F64P))
+        out.order_m, out.step = _p(o["order_m"], L.I32P), _p(o["step"])
+        L.check(L.lib().dfm_symmetry_eval(self._h, B, _p(lp), C.byref(out)), "dfm_symmetry_eval")
         return o
 
     def score(self, lig_pos, t, edges=None, seed=0, mfma16=False, energy=True, debug=False, profile=False, f16=False,
@@ -902,19 +933,21 @@ class Complex:
 
     def sample(self, B=1, num_steps=40, eps=1e-3, tr_noise_scale=0.5, rot_noise_scale=0.5, noise_annealing=False,
                use_clash_force=False, ode=False, seed=0, mfma16=False, inject=None, trace=False, profile=False, f16=False, bf16_ops=False,
-               bf16=False, l0_table=True, graph=False, step_energy=None, restraints=False):
+               bf16=False, l0_table=True, graph=False, step_energy=None, restraints=False, symmetry=False):
         """B independent Euler-Maruyama trajectories (inference_base.py:390-468 batched).  l0_table=False: DFM_F_NO_L0_TABLE
         (layer 0 evaluated edge by edge even where the per-complex message table applies).  graph=True: DFM_F_GRAPH (one captured
         step replayed as a hipGraph instead of every launch enqueued by the host; bitwise the same results, no faster on MI355X).
         trace=True returns the pose after every step and the scores of every evaluation; by default it also asks for the energy
         head on every step (DFM_F_STEP_ENERGY - the step evaluations then run their last layer in full); step_energy=False keeps
         the step evaluations exactly as an untraced call runs them (ligand-only last layer, no energy in trace_scores[:, :-1]).
-        restraints=True: DFM_F_RESTRAINTS (the restraint step of set_restraints after every update; nothing without a stored set)."""
+        restraints=True: DFM_F_RESTRAINTS (the restraint step of set_restraints after every update; nothing without a stored set).
+        symmetry=True: DFM_F_SYMMETRY (the Cn symmetry step of set_symmetry as the last move of every step; nothing without a stored
+        symmetry)."""
         return self._trajectories(None, B, num_steps, eps, tr_noise_scale, rot_noise_scale, noise_annealing, use_clash_force, ode, seed,
-                                  mfma16 or bf16, inject, trace, profile, f16, bf16_ops, l0_table, graph, step_energy, restraints)
+                                  mfma16 or bf16, inject, trace, profile, f16, bf16_ops, l0_table, graph, step_energy, restraints, symmetry)
 
     def _trajectories(self, refine, B, num_steps, eps, tr_noise_scale, rot_noise_scale, noise_annealing, use_clash_force, ode, seed, mfma16,
-                      inject, trace, profile, f16, bf16_ops, l0_table, graph, step_energy, restraints):
+                      inject, trace, profile, f16, bf16_ops, l0_table, graph, step_energy, restraints, symmetry=False):
         """dfm_sample (refine None) or dfm_refine (refine = (RefineParamsC, RefineInjectC or None, arrays to keep alive))."""
         if step_energy is None:
             step_energy = bool(trace)
@@ -947,7 +980,8 @@ class Complex:
                 (L.DFM_F_CLASH_FORCE if use_clash_force else 0) | (L.DFM_F_ODE if ode else 0) | \
                 (L.DFM_F_PROFILE if profile else 0) | (L.DFM_F_STEP_ENERGY if step_energy else 0) | (L.DFM_F_F16 if f16 else 0) | \
                 (L.DFM_F_BF16_OPS if bf16_ops else 0) | (0 if l0_table else L.DFM_F_NO_L0_TABLE) | \
-                (L.DFM_F_GRAPH if graph else 0) | (L.DFM_F_RESTRAINTS if restraints else 0)
+                (L.DFM_F_GRAPH if graph else 0) | (L.DFM_F_RESTRAINTS if restraints else 0) | \
+                (L.DFM_F_SYMMETRY if symmetry else 0)
         if refine is not None:
             par, rinj, _alive = refine
             rc = L.lib().dfm_refine(self._h, int(B), S, float(eps), float(tr_noise_scale), float(rot_noise_scale), flags, int(seed),
@@ -974,7 +1008,8 @@ class Complex:
 
     def refine(self, B=1, t_begin=0.1, start_pos=None, perturb=True, num_steps=40, eps=1e-3, tr_noise_scale=0.5, rot_noise_scale=0.5,
                noise_annealing=False, use_clash_force=False, ode=False, seed=0, mfma16=False, inject=None, refine_inject=None, trace=False,
-               profile=False, f16=False, bf16_ops=False, bf16=False, l0_table=True, graph=False, step_energy=None, restraints=False):
+               profile=False, f16=False, bf16_ops=False, bf16=False, l0_table=True, graph=False, step_energy=None, restraints=False,
+               symmetry=False):
         """Local refinement (dfm_refine; definition: dfmdock_amd/refine.py): B trajectories that start from `start_pos` [B,L,3,3] (one
         pose per trajectory; [L,3,3]: the same for all; None: the stored ligand pose), noised with the reference's forward process at
         `t_begin` (perturb=False: the pose itself), and run `sample`'s steps over linspace(t_begin, eps, num_steps).  Keywords and the
@@ -995,7 +1030,7 @@ class Complex:
         rinj, k2 = self._refine_inject(refine_inject, B)
         return self._trajectories((par, rinj, keep + k2), B, num_steps, eps, tr_noise_scale, rot_noise_scale, noise_annealing,
                                   use_clash_force, ode, seed, mfma16 or bf16, inject, trace, profile, f16, bf16_ops, l0_table, graph,
-                                  step_energy, restraints)
+                                  step_energy, restraints, symmetry)
 
     def forward_marginal(self, B, t, seed=0, refine_inject=None):
         """The draws `refine` starts from at t_begin = t (dfm_forward_marginal, the start kernel in evaluation mode): {rot [B,3]

@@ -132,6 +132,10 @@ enum {
     DFM_F_RESTRAINTS = 1u << 14,     /* dfm_sample: apply the interface restraint step (dfm_complex_set_restraints) after every step's
                                         Euler-Maruyama update with t_i <= t_start, before the clash force.  With no set stored the flag
                                         does nothing: the results are bitwise those of the unflagged call                   */
+    DFM_F_SYMMETRY = 1u << 15,       /* dfm_sample / dfm_refine: apply the Cn symmetry step (dfm_complex_set_symmetry) as the LAST thing
+                                        that moves the pose in every step with t_i <= t_start: evaluation, heads, restraint step, clash
+                                        force, symmetry step.  With no symmetry stored the flag does nothing: the results are bitwise
+                                        those of the unflagged call                                                          */
     DFM_F_GRAPH = 1u << 13           /* dfm_sample: capture ONE step (score evaluation + heads + update) as a hipGraph and replay it
                                         num_steps times instead of enqueueing every launch (ignored when anything is injected,
                                         traced or profiled).  Same kernels and arguments - the per-step / per-call scalars are
@@ -150,6 +154,29 @@ typedef struct {
     float max_rot;    /* rad, largest rotation of one restraint step                                          default 0.3    */
     float t_start;    /* the step runs on step i when t_i <= t_start (1.0: every step)                         default 1.0    */
 } dfm_restraint_params;
+
+/* Parameters of the symmetry step (dfm_complex_set_symmetry).  The defaults (p_or_null = NULL) are starting values: nobody has measured
+ * them against a trained checkpoint. */
+typedef struct {
+    float gain_rot;     /* in (0, 1]: fraction of the angle error one step removes: domega = clip(gain_rot (theta* - theta) u, max_rot)  default 0.5 */
+    float gain_tr;      /* in (0, 1]: fraction of the screw translation one step removes: dtau = clip(-gain_tr s u, max_tr)              default 0.5 */
+    float max_rot;      /* rad, largest rotation of one symmetry step                                                                   default 0.3 */
+    float max_tr;       /* A, largest translation of one symmetry step                                                                  default 10.0 */
+    float t_start;      /* the step runs on step i when t_i <= t_start (1.0: every step)                                                 default 1.0 */
+    int32_t snap_last;  /* non-zero: the LAST step of a sampler call projects exactly (gains 1, nothing clipped)                          default 1 */
+} dfm_symmetry_params;
+
+/* Output of dfm_symmetry_eval.  Required: step.  Any other pointer may be NULL. */
+typedef struct {
+    double *theta;        /* [B]    rad, rotation angle of the monomer-to-monomer transform T, in [0, pi]                 */
+    double *screw;        /* [B]    A, translation of T along its axis                                                   */
+    double *axis;         /* [B,3]  unit axis u of T                                                                     */
+    double *axis_point;   /* [B,3]  a point of the axis of the projected (pure-rotation) transform: the assembly's axis   */
+    double *fit_rmsd;     /* [B]    A, rms residual of the fit of the receptor onto the pose                              */
+    double *sym_rmsd;     /* [B]    A, rms displacement of the pose's atoms under the full projection                     */
+    int32_t *order_m;     /* [B]    m of theta* = 2 pi m / n (0: no axis, or a non-finite pose)                           */
+    float *step;          /* [B,6]  dtau, domega of a non-final step                                                     */
+} dfm_symmetry_out;
 
 /* Output of dfm_score.  Required: tr_score, rot_score.  Any other pointer may be NULL. */
 typedef struct {
@@ -320,6 +347,27 @@ int dfm_complex_set_restraints(dfm_complex *cx, int n_groups, const int32_t *gro
 /* The restraint terms at B poses lig_pos [B,L,9]: energy U [B], the number of groups with v_g = 0 [B] and (step_or_null) the step the
  * sampler would take there [B,6] = dtau, domega.  Runs the sampler's kernel (k_restraint) in its evaluation mode.  No set stored: zeros. */
 int dfm_restraint_eval(dfm_complex *cx, int B, const float *lig_pos, float *energy, int32_t *n_satisfied, float *step_or_null);
+/* Cn symmetric docking of a homo-oligomer: the ligand is a copy of the receptor's own chain (R == L, residue k of one is residue k of the
+ * other) and the assembly wanted is the cyclic n-mer.  With the stored receptor backbone y and a trajectory's pose x: (Q, tau) = the
+ * least-squares fit (proper rotation) of y onto x over all 3 R backbone atoms, the monomer-to-monomer transform T; theta in [0, pi] and u
+ * the angle and unit axis of Q (quaternion with w >= 0; |v| <= 1e-9: no axis, a zero step); c the centroid the sampler rotates about
+ * (ligand CA; all backbone atoms for family 1); g = Q^T (c - tau); s = u . (c - g) the translation along the axis; theta* = 2 pi m / n with
+ * m in 1 .. n / 2, gcd(m, n) = 1, closest to theta (ties: the smaller m).  Rotating x about c by (theta* - theta) u and shifting it by
+ * -s u makes T a pure rotation by theta* about an axis parallel to u: T^n = identity.  The symmetry step of DFM_F_SYMMETRY takes
+ * domega = clip(gain_rot (theta* - theta) u, max_rot), dtau = clip(-gain_tr s u, max_tr) with the restraint step's clip, and on the last
+ * step of a call with snap_last the whole projection, so final poses are symmetric to fp32 rounding.  It is applied as the restraint
+ * step is (modify_coords and the rot_update / tr_update bookkeeping) as the last thing that moves the pose in a step; a step of all zeros
+ * leaves every bit alone.  A pose with a non-finite coordinate gets a NaN step; the other trajectories are unaffected.  The fit needs no
+ * reference ligand, so the step is also right under dfm_refine with foreign start poses.
+ * n = 0 clears the stored symmetry (p_or_null is then ignored); 2 <= n <= 24 otherwise.  DFM_E_INVALID, the stored state kept: R != L, n outside the range, a gain
+ * outside (0, 1], a maximum that is not finite and > 0, a NaN.  A captured step graph (DFM_F_GRAPH) is invalidated: the next call captures
+ * again.  p_or_null = NULL: the defaults (dfm_symmetry_params) - starting values nobody has measured against a trained checkpoint.  No
+ * reference call has a counterpart. */
+int dfm_complex_set_symmetry(dfm_complex *cx, int n, const dfm_symmetry_params *p_or_null);
+/* The symmetry terms at B poses lig_pos [B,L,9] (dfm_symmetry_out; the definition in float64 numpy: dfmdock_amd/symmetry.py).  Runs the
+ * sampler's kernel (k_symmetry) in its evaluation mode; `step` is the step of a non-final iteration.  No axis: theta = 0, order_m = 0, a
+ * zero step, fit_rmsd as fitted and NaN elsewhere.  A non-finite pose: NaN everywhere, order_m = 0.  Nothing stored: zeros. */
+int dfm_symmetry_eval(dfm_complex *cx, int B, const float *lig_pos /*[B,L,9]*/, dfm_symmetry_out *out);
 /* Pose clustering of B ligand poses lig_pos [B,L,9] (N, CA, C per residue, dfm_traj_out's layout) over the ligand residues
  * residues_or_null[n_res] (NULL: all L; n_res is then ignored).  Distance: rmsd_ab = sqrt(mean over the 3 n_res atoms of |x_a - x_b|^2)
  * with NO superposition - the receptor is fixed in every trajectory of a complex, so this is the pairwise L-RMSD of CAPRI / DockQ.
