@@ -58,6 +58,7 @@ EXPORTS = [
     "dfm_pairpot_last_timing", "dfm_pairpot_last_phases",
     "dfm_score_distogram", "dfm_distogram_last_timing",
     "dfm_pose_fit", "dfm_pose_fit_chunked", "dfm_fit_last_timing",
+    "dfm_density_create", "dfm_density_destroy", "dfm_density_info", "dfm_pose_density", "dfm_pose_density_chunked", "dfm_density_last_timing",
 ]
 
 
@@ -165,6 +166,10 @@ class HbondOutC(C.Structure):
 
 class PairpotOutC(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_int64)) for n in ("energy_q", "n_pairs", "lig_q")] + [("counts", I32P)]
+
+
+class DensityOutC(C.Structure):
+    _fields_ = [("sum_q", C.POINTER(C.c_int64)), ("n_inside", I32P), ("n_above", I32P), ("atom_q", C.POINTER(C.c_int64))]
 
 
 class FitOutC(C.Structure):
@@ -302,6 +307,15 @@ def lib():
     L.dfm_pose_fit.argtypes = [C.c_void_p, C.c_int, C.c_int, F32P, F32P, C.c_int, F32P, F32P, F32P, C.POINTER(FitOutC)]
     L.dfm_pose_fit_chunked.argtypes = [C.c_void_p, C.c_int, C.c_int, F32P, F32P, C.c_int, F32P, F32P, F32P, C.c_int, C.POINTER(FitOutC)]
     L.dfm_fit_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.dfm_density_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, F32P, F32P, C.c_int, F32P, C.c_int, F32P, F32P, F32P, C.c_float,
+                                     C.POINTER(C.c_int)]
+    L.dfm_density_create.restype = C.c_void_p
+    L.dfm_density_destroy.argtypes = [C.c_void_p]
+    L.dfm_density_destroy.restype = None
+    L.dfm_density_info.argtypes = [C.c_void_p, I32P, I32P, I32P, I32P, I32P, C.POINTER(C.c_double)]
+    L.dfm_pose_density.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.POINTER(DensityOutC)]
+    L.dfm_pose_density_chunked.argtypes = [C.c_void_p, C.c_int, F32P, F32P, C.c_int, C.POINTER(DensityOutC)]
+    L.dfm_density_last_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dfm_trim_cache.argtypes = [C.c_int]
     L.dfm_trim_cache.restype = C.c_longlong
     L.dfm_alloc_diag.argtypes = [C.POINTER(C.c_int64)]

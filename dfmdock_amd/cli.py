@@ -16,6 +16,8 @@
     python -m dfmdock_amd sweep ... --consensus [--consensus-top 0.5]
     python -m dfmdock_amd dock|refine ... --interface-energy [--rank interface] [--ie-weights 0.18 1.0 0.5] [--ie-cutoff 8.0] [--energy-residues FILE]
     python -m dfmdock_amd dock|refine ... --pair-potential FILE.npz [--rank pairpot] [--pairpot-residues FILE] [--pair-counts FILE.npz]
+    python -m dfmdock_amd dock|refine|rescore ... --density MAP.mrc --density-resolution 8 [--rank density] [--density-threshold 1.0] [--min-density-cc X]
+                                                  [--density-residues FILE] [--write-simulated-map OUT.mrc]
     python -m dfmdock_amd dock|refine ... --affinity [--affinity-cutoff 5.5] [--contact-residues FILE]
     python -m dfmdock_amd dock|refine ... --hbonds [--bsa] [--hbond-cutoff 3.5] [--hbond-angle 90] [--salt-cutoff 4.0] [--hbond-residues FILE]
     python -m dfmdock_amd dock|refine ... --distogram [--rank distogram] [--distogram-map map.npz] [--distogram-restraints FILE] [--distogram-t 1e-3]
@@ -105,6 +107,14 @@
              n_untyped, T, NB, cutoff) for the kept pose and for every --top-k model; `--rank pairpot` keeps the pose with the lowest
              energy (ties: the lower index); `--pairpot-residues FILE` lists the kept model's energy per ligand residue; `--pair-counts
              FILE.npz` writes the pair counts [T,T,NB] of every written model - what a potential of this shape is fitted from.
+  density    no reference counterpart: the fit of every trajectory into a cryo-EM map on the GPU (dfmdock_amd/density.py,
+             dfm_pose_density).  `dock / refine / rescore --density MAP.mrc --density-resolution R` read an MRC map the RECEPTOR already
+             sits in and add a `density` object - density_cc (the overlap correlation of the simulated complex with the map; atoms are
+             Gaussians of sigma = R / (pi sqrt(2)) weighted by atomic number), density_inclusion (the share of the ligand's heavy atoms in
+             density at or above `--density-threshold`, default 1.0, in units of the normalised map) and density_n_outside - for the kept
+             pose and for every --top-k model; `--rank density` keeps the pose with the highest correlation; `--min-density-cc X` keeps
+             cluster centres below X out of the models; `--density-residues FILE` and `--write-simulated-map OUT.mrc` describe the kept
+             model.  Rigid ligand, no density-guided sampling, no local resolution, masks or FSC, no claim about real maps.
   distogram  the model's own distogram head (second model family only: EGNN_Net.to_dist, 64 distance bins per residue pair) evaluated at
              every final pose and reduced on the GPU (dfmdock_amd/distogram.py, dfm_score_distogram).  `dock / refine --distogram` add
              dist_nll (the reference's distogram_loss of the pose's own CA-CA distances under the prediction made at that pose: lower =
@@ -152,10 +162,10 @@ def _add_native(p):
 def _add_consensus(p):
     p.add_argument("--consensus", action="store_true",
                    help="score the trajectories by consensus contacts (adds a `consensus` object to the result line)")
-    p.add_argument("--rank", default="energy", choices=["energy", "consensus", "interface", "distogram", "pairpot"],
+    p.add_argument("--rank", default="energy", choices=["energy", "consensus", "interface", "distogram", "pairpot", "density"],
                    help="which trajectory is kept: the minimum energy (default), the highest consensus score (implies --consensus), the "
-                        "lowest interface energy (implies --interface-energy), the lowest distogram nll (implies --distogram) or the lowest "
-                        "tabulated pair potential (dock / refine only; needs --pair-potential)")
+                        "lowest interface energy (implies --interface-energy), the lowest distogram nll (implies --distogram), the lowest "
+                        "tabulated pair potential (dock / refine only; needs --pair-potential) or the highest map correlation (needs --density)")
     p.add_argument("--consensus-top", type=float, default=None, metavar="FRAC",
                    help="with --consensus: members of the ensemble are the best FRAC of the trajectories by energy (default 1.0: all)")
     p.add_argument("--contact-map", default=None, metavar="FILE.npz",
@@ -317,6 +327,38 @@ def symmetry_kwargs(args, ap=None):
     return kw
 
 
+def _add_density(p):
+    p.add_argument("--density", default=None, metavar="MAP.mrc",
+                   help="cryo-EM density fit of every trajectory against an MRC map the receptor already sits in: adds a `density` object "
+                        "(density_cc, density_inclusion, density_n_outside) to the result line and its three figures to every model; `--rank "
+                        "density` keeps the pose with the highest correlation")
+    p.add_argument("--density-resolution", type=float, default=None, metavar="R",
+                   help="with --density (required): the map's resolution in A; atoms are simulated as Gaussians of sigma = R / (pi sqrt(2))")
+    p.add_argument("--density-threshold", type=float, default=None, metavar="T",
+                   help="with --density: an atom counts as included at or above T, in units of the normalised map (default 1.0)")
+    p.add_argument("--min-density-cc", type=float, default=None, metavar="X",
+                   help="with --density and --top-k: leave a cluster centre whose correlation is below X out of the models")
+    p.add_argument("--density-residues", default=None, metavar="FILE",
+                   help="with --density: write the mean weighted map value per ligand residue over the kept pose and the models")
+    p.add_argument("--write-simulated-map", default=None, metavar="OUT.mrc",
+                   help="with --density: write the kept model simulated on the map's grid, for visual checks")
+
+
+def density_parser():
+    """The options of --density as a parser of their own, as symmetry_parser: parse_args takes them out of the command line of dock,
+    refine and rescore before the command's parser reads the rest; the command's help shows them in the epilog."""
+    p = argparse.ArgumentParser(prog="python -m dfmdock_amd dock|refine|rescore", add_help=False, allow_abbrev=False, usage=argparse.SUPPRESS)
+    _add_density(p.add_argument_group("cryo-EM density fit (dock, refine and rescore)"))
+    return p
+
+
+DENSITY_DESTS = ("density", "density_resolution", "density_threshold", "min_density_cc", "density_residues", "write_simulated_map")
+
+
+def _density_epilog():
+    return density_parser().format_help().strip()
+
+
 def _add_common(p):
     p.add_argument("--ckpt", required=True, help="Lightning checkpoint or bare state_dict (torch.save)")
     p.add_argument("--num-steps", type=int, default=40)
@@ -333,7 +375,7 @@ def _add_common(p):
 def build_parser():
     ap = argparse.ArgumentParser(prog="python -m dfmdock_amd", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
-    d = sub.add_parser("dock", help="dock one receptor / ligand PDB pair (inference_single.py)", epilog=_symmetry_epilog(),
+    d = sub.add_parser("dock", help="dock one receptor / ligand PDB pair (inference_single.py)", epilog=_symmetry_epilog() + "\n\n" + _density_epilog(),
                        formatter_class=argparse.RawDescriptionHelpFormatter)
     d.add_argument("pdb_1", help="receptor PDB")
     d.add_argument("pdb_2", help="ligand PDB")
@@ -350,7 +392,7 @@ def build_parser():
     for a in ANALYSES:
         a.add(d)
     _add_common(d)
-    r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)", epilog=_symmetry_epilog(),
+    r = sub.add_parser("refine", help="refine the pose the two PDB files are in (partial diffusion from --t-begin)", epilog=_symmetry_epilog() + "\n\n" + _density_epilog(),
                        formatter_class=argparse.RawDescriptionHelpFormatter)
     r.add_argument("pdb_1", help="receptor PDB")
     r.add_argument("pdb_2", help="ligand PDB, in the pose to refine")
@@ -365,7 +407,8 @@ def build_parser():
     for a in ANALYSES:
         a.add(r)
     _add_common(r)
-    x = sub.add_parser("rescore", help="rank, screen and describe decoys made elsewhere with the model's energy and every analysis of dock")
+    x = sub.add_parser("rescore", help="rank, screen and describe decoys made elsewhere with the model's energy and every analysis of dock",
+                       epilog=_density_epilog(), formatter_class=argparse.RawDescriptionHelpFormatter)
     x.add_argument("pdb_1", help="receptor PDB")
     x.add_argument("pdb_2", help="ligand PDB: the conformation the decoys are rigid images of")
     x.add_argument("--features", required=True, help=".npz with rec_esm / lig_esm [n,1280] (or rec_x / lig_x [n,1301])")
@@ -427,7 +470,12 @@ def parse_args(argv=None):
     sym = None
     if argv and argv[0] in ("dock", "refine"):      # the symmetry options: their own parser first, the command's parser reads the rest
         sym, argv = symmetry_parser().parse_known_args(argv)
+    den = None
+    if argv and argv[0] in ("dock", "refine", "rescore"):      # the density options likewise
+        den, argv = density_parser().parse_known_args(argv)
     args = ap.parse_args(argv)
+    for dest in DENSITY_DESTS:
+        setattr(args, dest, getattr(den, dest) if den is not None else None)
     for dest in SYMMETRY_DESTS:
         setattr(args, dest, getattr(sym, dest) if sym is not None else (False if dest == "no_symmetry_snap" else None))
     symmetry_kwargs(args, ap)      # (checked here, before anything is loaded)
@@ -446,8 +494,8 @@ def parse_args(argv=None):
     if args.cmd in ("dock", "refine", "rescore"):
         for a in ANALYSES:
             a.check(ap, args)
-    elif getattr(args, "rank", None) == "pairpot":
-        ap.error("--rank pairpot is offered by dock and refine")
+    elif getattr(args, "rank", None) in ("pairpot", "density"):
+        ap.error(f"--rank {args.rank} is offered by dock and refine")
     if args.cmd in ("dock", "refine", "rescore", "sweep"):
         if args.consensus_top is not None and not args.consensus:
             ap.error("--consensus-top selects the members of the consensus ensemble: it needs --consensus")
@@ -698,6 +746,69 @@ def pairpot_outputs(args, model, res, rec, lig, line, kw):
         line.update(pair_counts=os.path.abspath(args.pair_counts))
 
 
+def _density_flags(p):
+    """Nothing: the density flags are density_parser's, which parse_args reads first (the commands' own option lists stay what they were)."""
+
+
+def check_density(ap, args):
+    if getattr(args, "density", None) is None:
+        given = [o for o, d in (("--density-resolution", "density_resolution"), ("--density-threshold", "density_threshold"), ("--min-density-cc", "min_density_cc"),
+                                ("--density-residues", "density_residues"), ("--write-simulated-map", "write_simulated_map")) if getattr(args, d, None) is not None]
+        if given or getattr(args, "rank", None) == "density":
+            ap.error(f"{', '.join(given + (['--rank density'] if args.rank == 'density' else []))} need(s) --density MAP.mrc")
+        return
+    if args.density_resolution is None or not (np.isfinite(args.density_resolution) and args.density_resolution > 0):
+        ap.error("--density needs --density-resolution R, finite and > 0 (A)")
+    if not os.path.isfile(args.density):
+        ap.error(f"{args.density}: no such file")
+    args.density_threshold = 1.0 if args.density_threshold is None else args.density_threshold
+    if not np.isfinite(args.density_threshold):
+        ap.error("--density-threshold must be finite")
+    if args.min_density_cc is not None and (not np.isfinite(args.min_density_cc) or getattr(args, "top_k", None) is None):
+        ap.error("--min-density-cc must be finite and filters the models of --top-k: it needs it")
+
+
+def density_kwargs(args, model=None):
+    """Driver keyword arguments of the density flags: none without --density.  The map is read here, once."""
+    if getattr(args, "density", None) is None:
+        return {}
+    from .density import read_mrc
+    kw = dict(density_map=read_mrc(args.density), density_resolution=args.density_resolution, density_threshold=args.density_threshold, rank=args.rank)
+    if args.min_density_cc is not None:
+        kw["min_density_cc"] = args.min_density_cc
+    return kw
+
+
+def density_outputs(args, model, res, rec, lig, line, kw):
+    """The density part of a result: the `density` object of the line, --density-residues (the kept pose and the models) and
+    --write-simulated-map (the kept model on the map's grid)."""
+    if getattr(args, "density", None) is None:
+        return
+    line.update(density=res["density"], index=res["index"])
+    if "density_dropped" in res:
+        line.update(density_dropped=res["density_dropped"])
+    dmap = kw["density_map"]      # as density_kwargs read it
+    if args.density_residues:
+        from . import driver
+        from .density import write_density_residues
+        idx = [int(res["index"])] + [int(m["index"]) for m in res.get("models", [])]
+        tj = res["density_data"]      # the density path's own poses
+        keys, mean = driver.residue_density(model, rec, lig, np.asarray(tj["rot_update"])[idx], np.asarray(tj["tr_update"])[idx], dmap,
+                                            args.density_resolution, args.density_threshold)
+        write_density_residues(args.density_residues, keys, mean)
+        line.update(density_residues=os.path.abspath(args.density_residues))
+    if args.write_simulated_map:
+        from . import density as DN
+        from . import driver
+        from . import sterics as ST
+        ra, rw, _, lw, _ = driver.density_inputs(rec, lig, model.hp.family)
+        posed = np.asarray(res["lig_aa_coords"], np.float64)[ST.heavy_atoms(lig["atoms"])]
+        sim = DN.simulate_map(np.concatenate([ra.astype(np.float64), posed]), np.concatenate([rw, lw]), res["density"]["sigma"],
+                              np.shape(dmap["grid"]), dmap["origin"], dmap["voxel"])
+        DN.write_mrc(args.write_simulated_map, sim.astype(np.float32), dmap["origin"], dmap["voxel"])
+        line.update(simulated_map=os.path.abspath(args.write_simulated_map))
+
+
 def interface_outputs(args, model, res, rec, lig, line, kw):
     """The interface-energy part of a dock / refine result: the `interface_energy` object of the line and --energy-residues."""
     if not args.interface_energy:
@@ -937,6 +1048,7 @@ ANALYSES = (
     _Flags(_add_surface, check_surface, surface_kwargs, surface_outputs),
     _Flags(_add_interface, check_interface, interface_kwargs, interface_outputs),
     _Flags(_add_pairpot, check_pairpot, pairpot_kwargs, pairpot_outputs),
+    _Flags(_density_flags, check_density, density_kwargs, density_outputs),
     _Flags(_add_affinity, check_affinity, affinity_kwargs, affinity_outputs),
     _Flags(_add_hbonds, check_hbonds, hbonds_kwargs, hbonds_outputs),
 )

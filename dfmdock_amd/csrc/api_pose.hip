@@ -1,5 +1,5 @@
 // api_pose.hip - the pose calls of the C ABI (include/dfmdock_amd.h): pose clustering, docking metrics, consensus contacts and the six
-// rigid-pose families (sterics, buried surface, interface energy, residue contacts, hydrogen bonds, tabulated pair potential) and the rigid pose fit.  Every call owns a non-blocking
+// rigid-pose families (sterics, buried surface, interface energy, residue contacts, hydrogen bonds, tabulated pair potential), the rigid pose fit and the density fit.  Every call owns a non-blocking
 // stream and its temporaries; the handles are bound to the model handle's device only.
 #include <algorithm>
 #include <climits>
@@ -21,7 +21,7 @@ using namespace dfm;
 // several host threads, and next to that model's complex handles, do not share any state.
 // the two millisecond figures of this thread's last call of each kind, behind the dfm_*_last_timing getters: k_pose_dist and the
 // clustering kernels for MS_CLUSTER, host-to-device copies and kernels for the others
-enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_IFACE, MS_RESCON, MS_HBOND, MS_PAIRPOT, MS_FIT, MS_KINDS };
+enum { MS_CLUSTER, MS_METRICS, MS_CONSENSUS, MS_STERICS, MS_BSA, MS_IFACE, MS_RESCON, MS_HBOND, MS_PAIRPOT, MS_FIT, MS_DENSITY, MS_KINDS };
 static thread_local double g_last_ms[MS_KINDS][2] = {};
 
 static void set_last_ms(int kind, double a, double b)
@@ -1451,6 +1451,127 @@ extern "C" int dfm_pairpot_last_phases(double *zero_ms, double *walk_ms, double 
 {
     return last_phases(MS_PAIRPOT, zero_ms, walk_ms, finish_ms);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Density fit (kernels_density.hip): the grid as one float4 per node, the ligand's atoms with their weights in the caller's order and
+// the grid's geometry as doubles.  No receptor and no cell grid: the PoseHandle's grid fields stay 0.
+// The definition (dfmdock_amd/density.py is the float64 numpy statement of it).  The receptor's frame is the map's; pose p of ligand
+// atom a is (a - center) R(rot_p)^T + center + tr_p in fp64, as for every other rigid-pose call.  C channels (1 to 4) of float32 on one
+// orthogonal grid [nz][ny][nx], node (iz, iy, ix) at origin + (ix, iy, iz) * voxel, origin / voxel float32 (x, y, z).  One atom, one
+// channel, everything widened to fp64, in this order, nothing contracted:
+//   ux = (x - ox) / vx ; ix = floor(ux) ; fx = ux - ix        (same for y, z)
+//   inside  iff 0 <= ux < nx-1 and 0 <= uy < ny-1 and 0 <= uz < nz-1   (NaN is outside)
+//   c00 = c000 + fx*(c100 - c000) ; c10 = c010 + fx*(c110 - c010)
+//   c01 = c001 + fx*(c101 - c001) ; c11 = c011 + fx*(c111 - c011)
+//   c0  = c00  + fy*(c10 - c00)   ; c1  = c01  + fy*(c11 - c01)
+//   val = c0   + fz*(c1 - c0)
+//   term_q = int64(rint((w_a * val) * 2^20))      ties to even; 0 for an outside atom
+// sum_q [P,C] = the sums of term_q, n_inside [P], n_above [P] = the inside atoms whose channel-0 val >= threshold, atom_q [P,Al] = term_q
+// of channel 0.  A pose with a non-finite transform gets zeros.
+// dfm_density_create refuses in this order: m; C, the axes, NULL origin / voxel / grids, a non-finite origin, a voxel outside (0, 16], a
+// grid value that is not finite or above 2^10 in magnitude (check_density_grid); NULL lig_atoms / lig_w / center, Al, a non-finite atom,
+// a weight that is not finite or above 2^7 in magnitude, a non-finite centre (check_density_atoms); a threshold that is not finite; the
+// sum bound (density_sum_bound).
+struct dfm_density : PoseHandle {
+    int nx = 0, ny = 0, nz = 0, C = 0, Al = 0;
+    double sum_bound = 0.0;
+    float *grid = nullptr;
+    double *geo = nullptr;
+};
+
+extern "C" void dfm_density_destroy(dfm_density *h) { pose_destroy(h); }
+
+extern "C" dfm_density *dfm_density_create(dfm_model *m, int nx, int ny, int nz, const float origin[3], const float voxel[3], int C,
+                                           const float *grids, int Al, const float *lig_atoms, const float *lig_w, const float center[3],
+                                           float threshold, int *err)
+{
+    auto bad = [err](int code, const std::string &msg) -> dfm_density * {
+        (void)fail(code, msg);
+        if (err) *err = code;
+        return nullptr;
+    };
+    if (err) *err = DFM_OK;
+    if (!m) return bad(DFM_E_INVALID, "m is NULL");
+    if (const std::string msg = check_density_grid(nx, ny, nz, origin, voxel, C, grids); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (const std::string msg = check_density_atoms(Al, lig_atoms, lig_w, center); !msg.empty()) return bad(DFM_E_INVALID, msg);
+    if (!std::isfinite(threshold)) return bad(DFM_E_INVALID, "threshold is not finite");
+    const DensityBound bound = density_sum_bound(Al);
+    if (!bound.ok) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "a pose's sums could reach %.4g quanta, 2^62 or more", bound.quanta);
+        return bad(DFM_E_INVALID, buf);
+    }
+    std::vector<float> g4, lig4;
+    try {
+        g4 = interleave_density(nx, ny, nz, C, grids);
+        lig4 = gather4_density(Al, lig_atoms, lig_w);
+    } catch (const std::bad_alloc &) {
+        return bad(DFM_E_OOM, "dfm_density_create: the host copy of the grid does not fit");
+    }
+    const std::vector<double> geo = {(double)origin[0], (double)origin[1], (double)origin[2], (double)voxel[0], (double)voxel[1],
+                                     (double)voxel[2], (double)center[0], (double)center[1], (double)center[2], (double)threshold,
+                                     (double)(nx - 1), (double)(ny - 1), (double)(nz - 1), 0.0, 0.0, 0.0};
+    static_assert(DENSITY_GEO_SLOTS == 16, "geo holds 16 doubles");
+    dfm_density *h = new dfm_density;
+    h->device = m->device;
+    h->nx = nx; h->ny = ny; h->nz = nz; h->C = C; h->Al = Al;
+    h->sum_bound = bound.quanta;
+    return pose_finish_create(h, "dfm_density_create", bad, [&](PoseUploads &up) { up(&h->grid, g4)(&h->lig, lig4)(&h->geo, geo); });
+}
+
+extern "C" int dfm_density_info(const dfm_density *h, int32_t *nx, int32_t *ny, int32_t *nz, int32_t *C, int32_t *chunk_poses,
+                                double *sum_bound)
+{
+    if (!h) return fail(DFM_E_INVALID, "NULL argument");
+    if (nx) *nx = h->nx;
+    if (ny) *ny = h->ny;
+    if (nz) *nz = h->nz;
+    if (C) *C = h->C;
+    if (chunk_poses) *chunk_poses = density_chunk_poses(h->Al, true);
+    if (sum_bound) *sum_bound = h->sum_bound;
+    return DFM_OK;
+}
+
+extern "C" int dfm_pose_density_chunked(dfm_density *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_density_out *out)
+{
+    PoseChunks ch;
+    if (int rc = ch.begin(h, "h", P, 0, rot, tr, out, chunk_poses)) return rc;
+    PoseCall &c = ch.c;
+    // the call's chunk, else as many poses as fill DENSITY_CHUNK_BYTES of per-atom output
+    if (int rc = ch.alloc(chunk_poses, density_chunk_poses(h->Al, out->atom_q != nullptr), DENSITY_MAX_CHUNK)) return rc;
+    const int Pc = ch.Pc, C = h->C;
+    const size_t Al = (size_t)h->Al;
+    int64_t *d_tot = nullptr, *d_aq = nullptr;
+    HIPCHK(c.tmp.alloc(&d_tot, (size_t)Pc * DENSITY_TOT));
+    if (out->atom_q) HIPCHK(c.tmp.alloc(&d_aq, (size_t)Pc * Al));
+    const DensityAtoms at = {h->grid, h->lig, h->geo, h->nx, h->ny, h->nz, h->C, h->Al};
+    std::vector<int64_t> h_tot((size_t)Pc * DENSITY_TOT);
+    for (int p0 = 0; p0 < P; p0 += Pc) {
+        const int n = std::min(Pc, P - p0);
+        HIPCHK(ch.upload(p0, n));
+        HIPCHK(launch_density_pose(ch.d_rot, ch.d_tr, n, ch.T, d_tot, c.s));
+        HIPCHK(launch_density(at, ch.T, n, d_tot, d_aq, c.s));
+        HIPCHK(ch.kernels_done());
+        HIPCHK(hipMemcpyAsync(h_tot.data(), d_tot, (size_t)n * DENSITY_TOT * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
+        if (d_aq) HIPCHK(hipMemcpyAsync(out->atom_q + (size_t)p0 * Al, d_aq, (size_t)n * Al * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
+        HIPCHK(ch.finish());
+        for (int p = 0; p < n; ++p) {
+            const int64_t *t = &h_tot[(size_t)p * DENSITY_TOT];
+            if (out->sum_q)
+                for (int k = 0; k < C; ++k) out->sum_q[(size_t)(p0 + p) * C + k] = t[k];
+            if (out->n_inside) out->n_inside[p0 + p] = (int32_t)t[4];
+            if (out->n_above) out->n_above[p0 + p] = (int32_t)t[5];
+        }
+    }
+    return ch.done(MS_DENSITY);
+}
+
+extern "C" int dfm_pose_density(dfm_density *h, int P, const float *rot, const float *tr, dfm_density_out *out)
+{
+    return dfm_pose_density_chunked(h, P, rot, tr, 0, out);
+}
+
+DFM_LAST_TIMING(dfm_density_last_timing, MS_DENSITY)
 
 // ------------------------------------------------------------------------------------------------
 // Rigid pose fit (kernels_fit.hip): from decoy coordinates back to the sampler's (rot_update, tr_update).  Bound to the model handle's

@@ -637,6 +637,25 @@ hipError_t launch_pairpot_pose(const float *rot, const float *tr, int n, double 
 // first; nullptr launches the instantiation that holds no counting code
 hipError_t launch_pairpot(const PairpotAtoms &at, const double *T, int n, int64_t *tot, int64_t *lig_q, int32_t *counts, hipStream_t s);
 
+// density fit (kernels_density.hip; include/dfmdock_amd.h: dfm_density_create / dfm_pose_density).  geo [DENSITY_GEO_SLOTS] doubles on the
+// device, staged in LDS by every wave: origin x y z, voxel x y z, centre x y z, threshold, then nx - 1, ny - 1, nz - 1 as doubles (the
+// upper bounds of the inside test).
+constexpr int DENSITY_GEO_SLOTS = 16;
+// device arrays of a dfm_density: grid [nz][ny][nx] float4 = the channels of a node, zeros behind the C-th; lig [Al] float4 = (x, y, z,
+// w) in the caller's order
+struct DensityAtoms {
+    const float *grid, *lig;
+    const double *geo;
+    int nx, ny, nz, C, Al;
+};
+// tot [n][DENSITY_TOT] = sum_q of the four channels, n_inside, n_above of each pose
+constexpr int DENSITY_TOT = 6;
+// T [n][12]: R(rot) row-major and tr as doubles; also zeroes tot [n][6]
+hipError_t launch_density_pose(const float *rot, const float *tr, int n, double *T, int64_t *tot, hipStream_t s);
+// n <= 65535 poses.  tot [n][6] is added to.  atom_q [n][Al] or nullptr: every entry is written (0 for an outside atom and for a pose
+// that is not finite); nullptr launches the instantiation that holds no store of it
+hipError_t launch_density(const DensityAtoms &at, const double *T, int n, int64_t *tot, int64_t *atom_q, hipStream_t s);
+
 // isolated exposure of one chain on the host, as the definition takes it (kernels_surface.hip)
 void surface_exposure(int n, const float *xyz, const float *radius, double probe, int K, const float *dirs, const double lo[3],
                       const int dims[3], double edge, double pad, const int32_t *start, const int32_t *order, uint64_t *mask);

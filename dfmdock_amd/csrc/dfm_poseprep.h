@@ -1,9 +1,9 @@
 // dfm_poseprep.h - host preparation of the per-pose all-atom calls (api_pose.hip: dfm_atoms_create, dfm_surface_create, dfm_iface_create,
-// dfm_rescon_create, dfm_hbond_create, dfm_pairpot_create): argument checks, the cell grid of a chain, the ligand in blocks of 64 neighbours, the rounding
+// dfm_rescon_create, dfm_hbond_create, dfm_pairpot_create, dfm_density_create): argument checks, the cell grid of a chain, the ligand in blocks of 64 neighbours, the rounding
 // slack, the frame of the cutoff-based creators, the interface energy's parameter limits and overflow bound, the residue contacts' limits, residue bits, class masks and chunk
 // size, the hydrogen bonds' limits, role bits and charged residues, the pair potential's limits, quantised table, squared edges, pair
-// bound and chunk size.  Plain C++ without a HIP call, so that tests/test_pose_prep_cpu.py, tests/test_ifenergy_cpu.py,
-// tests/test_affinity_cpu.py, tests/test_hbonds_cpu.py and tests/test_pairpot_cpu.py run it under the sanitizers without a GPU.
+// bound and chunk size, the density fit's limits, interleaved grid, sum bound and chunk size.  Plain C++ without a HIP call, so that tests/test_pose_prep_cpu.py, tests/test_ifenergy_cpu.py,
+// tests/test_affinity_cpu.py, tests/test_hbonds_cpu.py, tests/test_pairpot_cpu.py and tests/test_density_cpu.py run it under the sanitizers without a GPU.
 #pragma once
 
 #include <algorithm>
@@ -500,6 +500,96 @@ inline int pairpot_chunk_poses(int Al, int T, int NB, bool per_atom, bool counts
     const size_t per_pose = (counts ? (size_t)T * T * NB * sizeof(int32_t) : 0) + (per_atom ? (size_t)Al * sizeof(int64_t) : 0);
     if (!per_pose) return PAIRPOT_MAX_CHUNK;
     return (int)std::min<size_t>((size_t)PAIRPOT_MAX_CHUNK, std::max<size_t>(1, budget / per_pose));
+}
+
+// Density fit (api_pose.hip: dfm_density_create; kernels_density.hip).  The limits: channels, nodes per axis, the largest grid value,
+// weight and voxel edge, poses per launch, and the bytes of per-atom output a chunk of a call may hold.
+constexpr int DENSITY_MAX_CHANNELS = 4, DENSITY_MIN_AXIS = 2, DENSITY_MAX_AXIS = 1024, DENSITY_MAX_CHUNK = 32768;
+constexpr float DENSITY_MAX_VALUE = 1024.f, DENSITY_MAX_WEIGHT = 128.f, DENSITY_MAX_VOXEL = 16.f;
+constexpr size_t DENSITY_CHUNK_BYTES = (size_t)64 << 20;
+
+// the grid [C][nz][ny][nx], its origin and voxel (x, y, z): the message of the first thing that is wrong, or ""
+inline std::string check_density_grid(int nx, int ny, int nz, const float *origin, const float *voxel, int C, const float *grids)
+{
+    if (C < 1 || C > DENSITY_MAX_CHANNELS) return "need 1 <= C <= " + std::to_string(DENSITY_MAX_CHANNELS);
+    const int n[3] = {nx, ny, nz};
+    for (int k = 0; k < 3; ++k)
+        if (n[k] < DENSITY_MIN_AXIS || n[k] > DENSITY_MAX_AXIS)
+            return std::string("need 2 <= n") + "xyz"[k] + " <= " + std::to_string(DENSITY_MAX_AXIS);
+    if (!origin) return "origin is NULL";
+    if (!voxel) return "voxel is NULL";
+    if (!grids) return "grids is NULL";
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(origin[k])) return "origin is not finite";
+    for (int k = 0; k < 3; ++k)
+        if (!(std::isfinite(voxel[k]) && voxel[k] > 0.f && voxel[k] <= DENSITY_MAX_VOXEL)) return "voxel is not in (0, 16]";
+    const size_t total = (size_t)C * nz * ny * nx;
+    for (size_t i = 0; i < total; ++i)
+        if (!(std::isfinite(grids[i]) && std::fabs(grids[i]) <= DENSITY_MAX_VALUE))
+            return "grids: value " + std::to_string(i) + " is not in [-1024, 1024]";
+    return "";
+}
+
+// the ligand's atoms [Al][3], their weights [Al] and the rotation centre
+inline std::string check_density_atoms(int Al, const float *lig_atoms, const float *lig_w, const float *center)
+{
+    if (!lig_atoms) return "lig_atoms is NULL";
+    if (!lig_w) return "lig_w is NULL";
+    if (!center) return "center is NULL";
+    if (Al < 1) return "need Al >= 1";
+    if (Al > POSE_MAX_ATOMS) return "Al exceeds 2^24 atoms";
+    for (size_t i = 0; i < (size_t)Al * 3; ++i)
+        if (!std::isfinite(lig_atoms[i])) return "lig_atoms: atom " + std::to_string(i / 3) + " is not finite";
+    for (int i = 0; i < Al; ++i)
+        if (!(std::isfinite(lig_w[i]) && std::fabs(lig_w[i]) <= DENSITY_MAX_WEIGHT))
+            return "lig_w: weight " + std::to_string(i) + " is not in [-128, 128]";
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(center[k])) return "center is not finite";
+    return "";
+}
+
+// The integer sums of the density fit can not wrap.  A trilinear value lies between its eight corners up to the rounding of seven
+// lerps, so |w val| 2^20 <= 2^7 2^10 2^20 (1 + 2^-48) and |term_q| <= 2^37: a pose's sums are below quanta = Al 2^37 in magnitude.  The
+// creator refuses a ligand for which that reaches 2^62.
+struct DensityBound {
+    double quanta;
+    bool ok;
+};
+inline DensityBound density_sum_bound(int64_t Al)
+{
+    DensityBound b;
+    b.quanta = (double)Al * 137438953472.0;      // 2^37
+    b.ok = b.quanta < 4611686018427387904.0;     // 2^62
+    return b;
+}
+
+// the grid as the kernel gathers it: [nz][ny][nx][4] floats, the C channels of a node side by side and zeros behind them, so that a
+// corner is one 16-byte load whatever C is
+inline std::vector<float> interleave_density(int nx, int ny, int nz, int C, const float *grids)
+{
+    const size_t nodes = (size_t)nz * ny * nx;
+    std::vector<float> v(nodes * 4, 0.f);
+    for (int c = 0; c < C; ++c)
+        for (size_t i = 0; i < nodes; ++i) v[i * 4 + c] = grids[(size_t)c * nodes + i];
+    return v;
+}
+
+// atoms [Al] as the kernel reads them: (x, y, z, w), in the caller's order
+inline std::vector<float> gather4_density(int Al, const float *xyz, const float *w)
+{
+    std::vector<float> v((size_t)Al * 4);
+    for (int i = 0; i < Al; ++i) {
+        for (int k = 0; k < 3; ++k) v[(size_t)i * 4 + k] = xyz[(size_t)i * 3 + k];
+        v[(size_t)i * 4 + 3] = w[i];
+    }
+    return v;
+}
+
+// poses of one chunk of a call: as many as fill `budget` bytes of per-atom output [Al] int64; without it the launch alone bounds it
+inline int density_chunk_poses(int Al, bool per_atom, size_t budget = DENSITY_CHUNK_BYTES)
+{
+    if (!per_atom) return DENSITY_MAX_CHUNK;
+    return (int)std::min<size_t>((size_t)DENSITY_MAX_CHUNK, std::max<size_t>(1, budget / ((size_t)Al * sizeof(int64_t))));
 }
 
 }  // namespace dfm

@@ -300,6 +300,81 @@ def _pairpot_result(pd, k):
     return {"pair_potential": _pose_pairpot(pd, k), "pairpot_data": pd, "index": int(k)}
 
 
+def density_inputs(rec, lig, family):
+    """What the density fit takes from two pdbio.backbone_from_atoms dicts: sterics_inputs (the heavy atoms of both chains and the
+    centre) plus the weight of every heavy atom - its element's atomic number (density.atom_weights) - receptor first."""
+    from . import density as DN
+    from . import sterics as ST
+    ra, la, cen = sterics_inputs(rec, lig, family)
+    return ra, DN.atom_weights(rec["atoms"], ST.heavy_atoms(rec["atoms"])), la, DN.atom_weights(lig["atoms"], ST.heavy_atoms(lig["atoms"])), cen
+
+
+def ensemble_density(model: engine.Model, rec, lig, rot_update, tr_update, dmap, resolution, threshold=1.0, per_atom=False):
+    """Density fit of trajectories on the GPU (dfm_pose_density) from their final (rot_update, tr_update) alone: the heavy atoms of the
+    two parsed PDB chains, weighted by atomic number, against dmap (density.read_mrc's dict; the receptor is taken to sit in the map's
+    frame) at `resolution` A (sigma = resolution * density.SIGMA_FACTOR).  The three grids of density.channels are gathered in one call.
+    Returns the dict of Density.fit plus cc (density.correlation), neg_cc, inclusion (n_above / Al), n_outside (Al - n_inside), Al,
+    scalars, resolution, sigma and threshold."""
+    from . import density as DN
+    ra, rw, la, lw, cen = density_inputs(rec, lig, model.hp.family)
+    sigma = float(resolution) * DN.SIGMA_FACTOR
+    grids, scalars = DN.channels(dmap, ra, rw, sigma, la, lw)
+    with model.density(grids, dmap["origin"], dmap["voxel"], la, lw, cen, threshold) as h:
+        out = h.fit(np.asarray(rot_update, np.float32).reshape(-1, 3), np.asarray(tr_update, np.float32).reshape(-1, 3), per_atom=per_atom)
+    cc = DN.correlation(out["sum_q"], scalars)
+    out.update(cc=cc, neg_cc=-cc, inclusion=DN.inclusion(out["n_above"], la.shape[0]), n_outside=la.shape[0] - out["n_inside"].astype(np.int64),
+               Al=int(la.shape[0]), scalars=scalars, resolution=float(resolution), sigma=sigma, threshold=float(threshold))
+    return out
+
+
+def residue_density(model: engine.Model, rec, lig, rot, tr, dmap, resolution, threshold=1.0):
+    """Per ligand residue, over the poses (rot, tr) [n,3]: (keys, mean) - the mean over the poses and over the residue's heavy atoms of
+    w * val of the normalised map (channel 0), float64 [n_res] (sterics.residue_of_atoms over the heavy atoms, density.residue_density)."""
+    from . import density as DN
+    from . import sterics as ST
+    dd = ensemble_density(model, rec, lig, np.asarray(rot).reshape(-1, 3), np.asarray(tr).reshape(-1, 3), dmap, resolution, threshold, per_atom=True)
+    keys, res = ST.residue_of_atoms(lig["atoms"], ST.heavy_atoms(lig["atoms"]))
+    q = DN.residue_density(dd["atom_q"], res, len(keys)).sum(0)
+    return keys, DN.units(q) / (np.bincount(res, minlength=len(keys)) * dd["atom_q"].shape[0])
+
+
+def _check_density(density_map, density_resolution, density_threshold, min_density_cc, rank):
+    """None (off) or (rank by it, the map, resolution, threshold, min_density_cc) of a pair driver's density options: density_map is
+    density.read_mrc's dict or the path of an MRC file and needs density_resolution; rank "density" needs a map."""
+    if density_map is None:
+        if rank == "density":
+            raise ValueError("rank 'density' needs a density_map")
+        if min_density_cc is not None:
+            raise ValueError("min_density_cc needs a density_map")
+        return None
+    from . import density as DN
+    dmap = DN.read_mrc(density_map) if isinstance(density_map, (str, os.PathLike)) else dict(density_map)
+    g, o, v = DN.check_grid(np.zeros((1,) + tuple(np.shape(dmap["grid"])), np.float32), dmap["origin"], dmap["voxel"])      # the shape and the geometry
+    if not np.isfinite(np.asarray(dmap["grid"], np.float64)).all():
+        raise ValueError("density_map: the map holds a value that is not finite")
+    if density_resolution is None or not (np.isfinite(density_resolution) and density_resolution > 0):
+        raise ValueError("a density_map needs density_resolution, finite and > 0 (A)")
+    if not np.isfinite(np.float32(density_threshold)):
+        raise ValueError("density_threshold must be finite")
+    if min_density_cc is not None and not np.isfinite(min_density_cc):
+        raise ValueError("min_density_cc must be finite")
+    return rank == "density", dmap, float(density_resolution), float(density_threshold), None if min_density_cc is None else float(min_density_cc)
+
+
+def _pose_density(dd, k):
+    cc = float(dd["cc"][k])
+    return {"density_cc": cc if np.isfinite(cc) else None, "density_inclusion": float(dd["inclusion"][k]), "density_n_outside": int(dd["n_outside"][k])}
+
+
+def _density_result(dd, k, opts, bad=None):
+    """The density entries of a pair driver's result for the FINAL kept pose k: its three figures, its rank by correlation (1: the highest)
+    among the poses the clash filter left, the resolution, sigma and threshold they were taken at."""
+    key = _nan_key(dd["neg_cc"], bad)
+    summary = dict(_pose_density(dd, k), rank=int(np.nonzero(rank_order(key, len(key)) == k)[0][0]) + 1, resolution=dd["resolution"],
+                   sigma=dd["sigma"], threshold=dd["threshold"], ranked_by_density=bool(opts[0]))
+    return {"density": summary, "density_data": dd, "index": int(k)}
+
+
 def rescon_inputs(rec, lig, family):
     """What the residue-contact call takes from two pdbio.backbone_from_atoms dicts: sterics_inputs plus, per chain, the residue index of
     every heavy atom (sterics.residue_of_atoms) and the class of every residue by its name (affinity.IC_CLASS; a name outside the table is
@@ -568,8 +643,8 @@ def _distogram_result(dd, k, opts, bad=None):
 
 
 def _check_rank(rank, consensus_top):
-    if rank not in ("energy", "consensus", "interface", "distogram", "pairpot"):
-        raise ValueError(f"rank must be 'energy', 'consensus', 'interface', 'distogram' or 'pairpot', got {rank!r}")
+    if rank not in ("energy", "consensus", "interface", "distogram", "pairpot", "density"):
+        raise ValueError(f"rank must be 'energy', 'consensus', 'interface', 'distogram', 'pairpot' or 'density', got {rank!r}")
     if not (0.0 < float(consensus_top) <= 1.0):
         raise ValueError(f"consensus_top must be in (0, 1], got {consensus_top}")
 
@@ -1122,6 +1197,13 @@ def _pairpot_select(run):
     _ranked(run, "pairpot", pd, "energy")
 
 
+def _density_select(run):
+    _, dmap, resolution, threshold, _ = run.opts["density"]
+    dd = ensemble_density(run.model, run.rec, run.lig, *run.poses(), dmap, resolution, threshold)
+    dd.update(rot_update=run.cols["rot_update"], tr_update=run.cols["tr_update"])      # the poses the arrays are of
+    _ranked(run, "density", dd, "neg_cc", np.nanargmin)      # the highest correlation; a NaN never wins
+
+
 def _consensus_select(run):
     """Under rank "consensus" the kept pose becomes the one consensus.pick keeps and the key its order - unless no pose has any contact, when both stay."""
     from . import consensus as CS
@@ -1171,7 +1253,7 @@ class _Analysis(NamedTuple):
     model_key: str = None         # ... under this key (None: merged into the model)
 
 
-# In the order a model of top_k lists them, which within a stage is also the order of the calls: interface, pairpot, then consensus (one
+# In the order a model of top_k lists them, which within a stage is also the order of the calls: interface, pairpot, density, then consensus (one
 # rank is given, so at most one of them moves the kept pose); surface before affinity and hbonds, which use it.
 ANALYSES = (
     _Analysis("sterics", dict(clash_screen=False, clash_filter=False, clash_cutoff=3.0, contact_cutoff=5.0), lambda model, rank, max_batch, **kw: _check_sterics(**kw),
@@ -1192,6 +1274,9 @@ ANALYSES = (
               "describe", _hbonds_describe, lambda run: _hbonds_result(run.data["hbonds"], run.k), _pose_hbonds),
     _Analysis("pairpot", dict(pair_potential=None), lambda model, rank, max_batch, **kw: _check_pairpot(rank=rank, **kw),
               "select", _pairpot_select, lambda run: _pairpot_result(run.data["pairpot"], run.k), _pose_pairpot, "pair_potential"),
+    _Analysis("density", dict(density_map=None, density_resolution=None, density_threshold=1.0, min_density_cc=None),
+              lambda model, rank, max_batch, **kw: _check_density(rank=rank, **kw),
+              "select", _density_select, lambda run: _density_result(run.data["density"], run.k, run.opts["density"], run.bad), _pose_density),
     _Analysis("consensus", dict(consensus=False, consensus_top=1.0, consensus_cutoff=5.5), lambda model, rank, max_batch, consensus, consensus_top, consensus_cutoff:
               (rank, float(consensus_cutoff), float(consensus_top)) if consensus or rank == "consensus" else None,      # rank "consensus" implies it
               "select", _consensus_select, lambda run: _consensus_result(run.data["consensus"], run.k, run.opts["consensus"], run.ranked_by)),
@@ -1363,6 +1448,13 @@ def dock_pair(model: engine.Model, rec, lig, rec_x, lig_x, num_samples=120, num_
     kcal/mol, n_pairs, n_untyped, T, NB, cutoff} of the kept pose), `pairpot_data` (the arrays and the rot_update / tr_update they are of), `index` and `trajectories`; every model
     of `top_k` gains `pair_potential`.  rank="pairpot" (needs pair_potential) keeps the pose with the lowest energy instead (ties: lower
     index; it overrides restraint_rank and becomes the clustering key of top_k).
+    `density_map` (density.read_mrc's dict, or the path of an MRC file; the receptor is taken to sit in the map's frame) with
+    `density_resolution` (A; sigma = resolution * density.SIGMA_FACTOR) and `density_threshold` (in units of the normalised map): the
+    density fit of every trajectory (ensemble_density: heavy atoms weighted by atomic number).  The result gains `density` ({density_cc,
+    density_inclusion, density_n_outside, rank, resolution, sigma, threshold} of the kept pose), `density_data`, `index` and
+    `trajectories`; every model of `top_k` gains density_cc, density_inclusion and density_n_outside.  rank="density" (needs density_map)
+    keeps the pose with the highest correlation instead; `min_density_cc` leaves a cluster centre below it out of `models`
+    (`density_dropped`).  The ligand is rigid, nothing guides the sampler, and nothing is claimed about ranking quality on real maps.
 
     `symmetry` (an order n in 2 .. 24): Cn symmetric docking of a homo-oligomer.  Receptor and ligand must be ONE chain each, of the same
     sequence, and rigid images of each other within `symmetry_tolerance` A (Kabsch rmsd of the backbones); anything else raises a
@@ -1594,6 +1686,7 @@ def _top_models(run, clu):
     top_k, radius, rule = clu
     model, rec, lig, cols, bad, sd = run.model, run.rec, run.lig, run.cols, run.bad, run.data.get("sterics")
     min_bsa = run.opts["surface"][0] if "surface" in run.opts else None
+    min_cc, cc_dropped = (run.opts["density"][4] if "density" in run.opts else None), 0
     cl = cluster_trajectories(model, run.lig0, cols["rot_update"], cols["tr_update"], run.key, radius, rule, top_k)
     models, dropped = [], 0
     for c, n in zip(cl["center"], cl["size"]):
@@ -1602,6 +1695,9 @@ def _top_models(run, clu):
             continue
         if min_bsa is not None and run.data["surface"]["bsa"][c] < min_bsa:
             dropped += 1
+            continue
+        if min_cc is not None and not run.data["density"]["cc"][c] >= min_cc:
+            cc_dropped += 1
             continue
         k = len(models)
         models.append({"rank": k + 1, "index": c, "energy": float(cols["energy"][c]), "cluster_size": int(n)})
@@ -1617,7 +1713,8 @@ def _top_models(run, clu):
         poses = rebuild_backbone(run.lig0, cols["rot_update"][cen], cols["tr_update"][cen], model.hp.family)
         for m, pm in zip(models, native_metrics(model, run.native, rec["bb_coords"], poses)):
             m["metrics"] = pm
-    return {"models": models, "cluster_of": cl["cluster_of"], **({"bsa_dropped": dropped} if min_bsa is not None else {})}
+    return {"models": models, "cluster_of": cl["cluster_of"], **({"bsa_dropped": dropped} if min_bsa is not None else {}),
+            **({"density_dropped": cc_dropped} if min_cc is not None else {})}
 
 
 def model_path(out_pdb, rank):

@@ -283,9 +283,16 @@ class Model:
         whose `.energy(rot, tr)` takes P poses in one call."""
         return PairPotential(self, rec_atoms, rec_type, lig_atoms, lig_type, center, edges, table)
 
+    def density(self, grids, origin, voxel, lig_atoms, lig_w, center, threshold=1.0):
+        """A density grid - grids [C,nz,ny,nx] float32, 1 to 4 channels on one orthogonal grid with `origin` and `voxel` [3] in A (x, y,
+        z); density.read_mrc and density.channels make them from a map - and the ligand's atoms with their weights prepared for the
+        density-fit call on the GPU (dfm_density_create); the receptor is taken to be in the map's frame.  Returns a Density whose
+        `.fit(rot, tr)` takes P poses in one call."""
+        return Density(self, grids, origin, voxel, lig_atoms, lig_w, center, threshold)
+
 
 class _Handle:
-    """What Native, Atoms, Surface, Interface, Contacts, HBonds and PairPotential share: a handle `_h` made by dfm_<_kind>_create and freed by dfm_<_kind>_destroy - close(), a context
+    """What Native, Atoms, Surface, Interface, Contacts, HBonds, PairPotential and Density share: a handle `_h` made by dfm_<_kind>_create and freed by dfm_<_kind>_destroy - close(), a context
     manager, closed when collected."""
     _kind = None
 
@@ -657,6 +664,50 @@ class PairPotential(_Handle):
         L.check(L.lib().dfm_pose_pairpot_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_pairpot")
         o["energy"] = PP.kcal(o["energy_q"])
         return o
+
+
+class Density(_Handle):
+    """A density grid, channel-interleaved, and the ligand's atoms with their weights resident on the model's GPU (dfm_density).
+    Read-only after creation: `fit` may be called from several threads at once."""
+    _kind = "density"
+
+    def __init__(self, model: Model, grids, origin, voxel, lig_atoms, lig_w, center, threshold=1.0):
+        from . import density as DN
+        g, o, v = DN.check_grid(grids, origin, voxel)
+        la, cen = _f32(lig_atoms).reshape(-1, 3), _center(center)
+        w = np.ascontiguousarray(DN.check_weights(lig_w, la.shape[0]))
+        o, v = np.ascontiguousarray(o), np.ascontiguousarray(v)
+        self.model, self.Al, self.C, self.shape, self.threshold = model, la.shape[0], g.shape[0], g.shape[1:], float(np.float32(threshold))
+        err = C.c_int(0)
+        self._h = L.lib().dfm_density_create(model._h, g.shape[3], g.shape[2], g.shape[1], _p(o), _p(v), self.C, _p(g), self.Al, _p(la), _p(w),
+                                             _p(cen), self.threshold, C.byref(err))
+        self._created()
+
+    def info(self):
+        """{nx, ny, nz, C, chunk_poses (of a call with atom_q), sum_bound (quanta a pose's sums stay below)} (dfm_density_info)."""
+        v = [C.c_int32(0) for _ in range(5)]
+        b = C.c_double(0)
+        L.check(L.lib().dfm_density_info(self._h, *(C.byref(x) for x in v), C.byref(b)), "dfm_density_info")
+        return dict(zip(("nx", "ny", "nz", "C", "chunk_poses"), (x.value for x in v)), sum_bound=b.value)
+
+    def fit(self, rot, tr, per_atom=False, chunk_poses=0):
+        """Density fit of P poses (dfm_pose_density; the float64 definition is density.density): rot [P,3] axis-angle and tr [P,3] as
+        rot_update / tr_update hold them.  Returns {sum_q (int64 [P,C]; quanta of 2^-20), n_inside, n_above (int32 [P])} and, with
+        `per_atom`, atom_q (int64 [P,Al]: channel 0, the caller's atom order)."""
+        r, t, P = _rigid_poses(rot, tr)
+        o = {"sum_q": np.zeros((P, self.C), np.int64), "n_inside": np.zeros(P, np.int32), "n_above": np.zeros(P, np.int32)}
+        if per_atom:
+            o["atom_q"] = np.zeros((P, self.Al), np.int64)
+        out = L.DensityOutC()
+        for k, a in o.items():
+            setattr(out, k, a.ctypes.data_as(C.POINTER(C.c_int64 if a.dtype == np.int64 else C.c_int32)))
+        L.check(L.lib().dfm_pose_density_chunked(self._h, P, _p(r), _p(t), int(chunk_poses), C.byref(out)), "dfm_pose_density")
+        return o
+
+
+def density_last_timing():
+    """(host-to-device copy ms, kernel ms) of this thread's last Density.fit call (dfm_density_last_timing)."""
+    return _last_ms("dfm_density_last_timing", 2)
 
 
 def fit_last_timing():

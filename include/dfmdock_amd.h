@@ -791,6 +791,55 @@ int dfm_pose_fit_chunked(dfm_model *m, int P, int L, const float *lig_ref, const
 /* GPU milliseconds of the calling thread's last dfm_pose_fit, summed over its chunks: the host-to-device copies of the decoys and the
  * three kernels (k_fit_reduce, k_fit_solve, k_fit_resid) - tools/fit_bench.py */
 int dfm_fit_last_timing(double *copy_ms, double *kernel_ms);
+/* Cryo-EM density fit of P rigid poses of one ligand: which of these models does the map support?  Per pose and channel the sum over
+ * the ligand's atoms of w_a times the trilinear value of a 3-D grid at the posed atom - a gather, not a cell walk - plus the atoms inside
+ * the grid and those in density above a threshold.  dfmdock_amd/density.py is the float64 definition these calls are tested against, and
+ * holds the host finishes (MRC files, simulated maps, the closed-form correlation).  Nothing is claimed about ranking quality on real maps.
+ *   Frame: the receptor's coordinates are taken to be in the map's frame; fitting the receptor into the map is not done.  Centre and
+ *     poses as for dfm_atoms_create / dfm_pose_sterics: pose p of atom a is (a - center) R(rot_p)^T + center + tr_p in fp64.
+ *   Grid: grids [C,nz,ny,nx] float32, 1 <= C <= 4 channels on ONE orthogonal grid, 2 <= n <= 1024 nodes per axis, every value finite and
+ *     at most 2^10 in magnitude; origin [3] and voxel [3] float32 in A, (x, y, z), voxel finite and in (0, 16] and possibly anisotropic;
+ *     node (iz, iy, ix) sits at origin + (ix, iy, iz) * voxel.  lig_w [Al]: the atoms' weights, finite, |w| <= 2^7.
+ *   One atom, one channel, everything widened to fp64, in this order, nothing contracted:
+ *     ux = (x - ox) / vx ; ix = floor(ux) ; fx = ux - ix        (same for y, z)
+ *     inside  iff 0 <= ux < nx-1 and 0 <= uy < ny-1 and 0 <= uz < nz-1   (NaN is outside)
+ *     c00 = c000 + fx*(c100 - c000) ; c10 = c010 + fx*(c110 - c010)      (cXYZ: the node at ix+X, iy+Y, iz+Z)
+ *     c01 = c001 + fx*(c101 - c001) ; c11 = c011 + fx*(c111 - c011)
+ *     c0  = c00  + fy*(c10 - c00)   ; c1  = c01  + fy*(c11 - c01)
+ *     val = c0   + fz*(c1 - c0)
+ *     term_q = (int64) rint((w_a * val) * 2^20), ties to even; 0 for an outside atom.  No square root, no transcendental.
+ *   sum_q [P,C]: the int64 sums of term_q; n_inside [P]: the atoms inside; n_above [P]: the inside atoms whose channel-0 val >= threshold
+ *     (a float32, widened); atom_q [P,Al]: term_q of channel 0, in the caller's atom order.  Values are q * 2^-20.
+ *   A pose with a NaN or infinite rot / tr gets zeros and disturbs no other pose (not an error).
+ * Every output pointer may be NULL.  Everything is an integer sum: the results equal the definition's, and none depends on P, on a
+ * pose's index, on the order of the poses or on the chunks of a call.  |term_q| <= 2^37; dfm_density_create refuses a ligand whose
+ * Al * 2^37 quanta could reach 2^62 (dfm_poseprep.h: density_sum_bound).  The device holds the grid channel-interleaved, 16 bytes per
+ * node.  dfm_density_info reports the grid's shape, C, the poses of a chunk of a call with atom_q and that bound.  A call works through
+ * chunk_poses poses at a time (0: as many as fill 64 MiB of atom_q; without atom_q 32768).
+ * DFM_E_INVALID / NULL (*err, when given, holds the code), nothing enqueued, the first of these in this order: a NULL m; C outside 1 .. 4,
+ * an axis outside 2 .. 1024, a NULL origin, voxel or grids, a non-finite origin, a voxel outside (0, 16], a grid value that is not finite
+ * or above 2^10 in magnitude; a NULL lig_atoms, lig_w or center, Al < 1 or > 2^24, a non-finite atom, a weight that is not finite or
+ * above 2^7 in magnitude, a non-finite centre; a threshold that is not finite; the sum bound.  For a call: a NULL h, rot, tr or out,
+ * P < 1, chunk_poses < 0.  DFM_E_OOM when the grid, the atoms or a chunk's output do not fit.
+ * Takes the MODEL handle for its device only.  The handle is read-only after creation; every call owns a non-blocking stream and its
+ * device temporaries, so calls on one handle may run from several host threads at once.  No reference call has a counterpart. */
+typedef struct dfm_density dfm_density;
+typedef struct {
+    int64_t *sum_q;                     /* [P,C]  or NULL */
+    int32_t *n_inside;                  /* [P]    or NULL */
+    int32_t *n_above;                   /* [P]    or NULL */
+    int64_t *atom_q;                    /* [P,Al] or NULL */
+} dfm_density_out;
+dfm_density *dfm_density_create(dfm_model *m, int nx, int ny, int nz, const float origin[3], const float voxel[3], int C,
+                                const float *grids, int Al, const float *lig_atoms, const float *lig_w, const float center[3],
+                                float threshold, int *err);
+void dfm_density_destroy(dfm_density *h);
+int dfm_density_info(const dfm_density *h, int32_t *nx, int32_t *ny, int32_t *nz, int32_t *C, int32_t *chunk_poses, double *sum_bound);
+int dfm_pose_density(dfm_density *h, int P, const float *rot, const float *tr, dfm_density_out *out);
+int dfm_pose_density_chunked(dfm_density *h, int P, const float *rot, const float *tr, int chunk_poses, dfm_density_out *out);
+/* GPU milliseconds of the calling thread's last dfm_pose_density, summed over its chunks: the host-to-device copies of the poses and the
+ * kernels (k_density_pose, k_density) - tools/density_bench.py */
+int dfm_density_last_timing(double *copy_ms, double *kernel_ms);
 /* edges per node for this complex: min(N,20) + min(40, N-20) */
 int dfm_complex_degree(const dfm_complex *cx);
 /* Device blocks released by destroyed handles are parked per device for the next handle (a set driver creates and destroys a
