@@ -1,5 +1,6 @@
-"""Kernel-level harness of the four launchers the other harnesses leave out (tests/kernels/aux_harness.hip): launch_pair_dist_sum
-(k_pair_dist_sum + k_dist_finish + k_dist_mean), launch_restraint (k_restraint), launch_igso3_cdf and launch_start_pose.
+"""Kernel-level harness of the five launchers the other harnesses leave out (tests/kernels/aux_harness.hip): launch_pair_dist_sum
+(k_pair_dist_sum + k_dist_finish + k_dist_mean), launch_restraint (k_restraint), launch_symmetry (k_symmetry), launch_igso3_cdf and
+launch_start_pose.
 
 The shim drives the shipped launchers of dfmdock_amd/libdfmdock_amd.so under the guard-band protocol of tests/kernel_harness.py, after
 checking everything a kernel would follow as an index.  This module binds it and holds
@@ -25,9 +26,11 @@ from kernel_harness import HIP_INVALID_VALUE, HIP_SUCCESS, LIBDIR, ROOT, Out, gu
 from dfmdock_amd import distogram as DG
 from dfmdock_amd import refine as RF
 from dfmdock_amd import restraints as RS
+from dfmdock_amd import symmetry as SY
 
 LAUNCHERS = ("_ZN3dfm20launch_pair_dist_sumERKNS_15PairDistSumArgsEP12ihipStream_t",
              "_ZN3dfm16launch_restraintERKNS_13RestraintArgsEiP12ihipStream_t",
+             "_ZN3dfm15launch_symmetryERKNS_12SymmetryArgsEiP12ihipStream_t",
              "_ZN3dfm16launch_igso3_cdfEdPdP12ihipStream_t",
              "_ZN3dfm17launch_start_poseERKNS_9StartArgsEiP12ihipStream_t")
 H = hh.H
@@ -42,12 +45,13 @@ RNG_START = 4
 SLOTS = ("P", "Q", "ca4", "w_d", "ln_w", "ln_b", "w3f", "pair_nll", "pcontact", "edist", "pcontact_mean", "part", "res",
          "rec_pos", "gstart", "pairs", "upper", "weight", "big", "lig", "tr_upd", "rot_upd", "t_dev", "ctl", "out",
          "prep_pos", "prep_ca4", "prep_cb4",
-         "cdf", "start", "u_inj", "axis_inj", "tr_inj")
+         "cdf", "start", "u_inj", "axis_inj", "tr_inj", "sym_out", "step_out")
 DOUBLES = ("sigma", "sigma_r3")
-FLOATS = ("near_cut", "k_tr", "k_rot", "max_tr", "max_rot", "t_start")
-INTS = ("B", "R", "L", "contact_bins", "all_atoms", "perturb", "G", "n_big", "n_pairs", "apply", "prep_next", "n_t")
-UINTS = ("step", "seed_lo", "seed_hi")
-OPS = ("pair_dist_sum", "restraint", "igso3_cdf", "start_pose")
+FLOATS = ("near_cut", "k_tr", "k_rot", "max_tr", "max_rot", "t_start", "gain_rot", "gain_tr")
+INTS = ("B", "R", "L", "contact_bins", "all_atoms", "perturb", "G", "n_big", "n_pairs", "apply", "prep_next", "n_t", "n", "snap_last")
+UINTS = ("step", "seed_lo", "seed_hi", "num_steps")
+OPS = ("pair_dist_sum", "restraint", "igso3_cdf", "start_pose", "symmetry")
+SYM_OUT, SYM_MIN_ORDER, SYM_MAX_ORDER = 12, 2, 24
 
 f32 = np.float32
 
@@ -84,6 +88,8 @@ class Harness(kh.KernelHarness):
         self.lib.ax_parts.argtypes = [C.c_int, C.c_int]
         self.lib.ax_parts.restype = C.c_longlong
         assert int(self.lib.ax_rs_small()) == RS_SMALL and int(self.lib.ax_rs_max_groups()) == RS_MAX_GROUPS
+        assert (int(self.lib.ax_sym_out()), int(self.lib.ax_sym_min_order()), int(self.lib.ax_sym_max_order())) == (SYM_OUT, SYM_MIN_ORDER, SYM_MAX_ORDER)
+        assert (SYM_MIN_ORDER, SYM_MAX_ORDER) == (SY.MIN_ORDER, SY.MAX_ORDER)
         assert all(int(self.lib.ax_parts(R, L)) == parts_of(R, L) for R, L in ((1, 1), (33, 65), (65, 129)))
 
     def check_only(self, op, bufs, **scalars):
@@ -125,11 +131,46 @@ class Harness(kh.KernelHarness):
         if prep:
             bufs.update(prep_pos=Out(f32, B * N * 4), prep_ca4=Out(f32, B * N * 4), prep_cb4=Out(f32, B * N * 4))
         sc = dict(B=B, R=R, L=L, all_atoms=c["all_atoms"], G=len(c["upper"]), n_big=len(c["big"]), n_pairs=len(c["pairs"]), apply=apply,
-                  prep_next=int(prep), n_t=0 if t_dev is None else len(t_dev), step=step, **{k: c["params"][k] for k in FLOATS[1:]})
+                  prep_next=int(prep), n_t=0 if t_dev is None else len(t_dev), step=step, **{k: c["params"][k] for k in FLOATS[1:6]})
         sc.update(over)
         r = self.run("restraint", bufs, check=check, **sc)
         if "out" in r:
             r["out"] = r["out"].reshape(B, 8)
+        return r
+
+    def symmetry(self, c, apply=0, out=True, step_out=True, prep=False, t_dev=None, step=0, num_steps=0, ctl=None, sl=slice(None), rot0=None,
+                 tr0=None, check=True, **over):
+        """One launch_symmetry on the case c (sym_case).  The pose is in / out in both modes (evaluation mode must return its bits);
+        apply: tr_upd and rot_upd are in / out (rot0 / tr0 their start).  out / step_out: the two optional outputs; prep: prep_next with
+        its three outputs.  Returns the slots reshaped per trajectory, `ev` (sym_unpack) when `out` was asked for."""
+        lig = np.ascontiguousarray(c["lig"][sl])
+        B, L = len(lig), c["L"]
+        N = 2 * L
+        bufs = dict(rec_pos=c["rec_pos"], lig=Out(f32, init=lig), t_dev=t_dev, ctl=ctl)
+        if apply:
+            bufs.update(tr_upd=Out(f32, init=np.zeros((B, 3), f32) if tr0 is None else tr0),
+                        rot_upd=Out(f32, init=np.zeros((B, 3), f32) if rot0 is None else rot0))
+        if out:
+            bufs["sym_out"] = Out(np.float64, B * SYM_OUT)
+        if step_out:
+            bufs["step_out"] = Out(f32, B * 6)
+        if prep:
+            bufs.update(prep_pos=Out(f32, B * N * 4), prep_ca4=Out(f32, B * N * 4), prep_cb4=Out(f32, B * N * 4))
+        p = c["params"]
+        sc = dict(B=B, R=L, L=L, all_atoms=c["all_atoms"], n=c["n"], apply=apply, prep_next=int(prep), n_t=0 if t_dev is None else len(t_dev),
+                  step=step, num_steps=num_steps, snap_last=p["snap_last"], **{k: p[k] for k in ("gain_rot", "gain_tr", "max_rot", "max_tr", "t_start")})
+        sc.update(over)
+        r = self.run("symmetry", bufs, check=check, **sc)
+        if r["err"] == HIP_SUCCESS:
+            r["lig"] = r["lig"].reshape(B, L * 9)
+            for k in ("tr_upd", "rot_upd"):
+                if k in r:
+                    r[k] = r[k].reshape(B, 3)
+            if step_out:
+                r["step_out"] = r["step_out"].reshape(B, 6)
+            if out:
+                r["sym_out"] = r["sym_out"].reshape(B, SYM_OUT)
+                r["ev"] = sym_unpack(r["sym_out"], r["step_out"] if step_out else np.full((B, 6), np.nan, f32))
         return r
 
     def igso3(self, sigma, extra=24):
@@ -695,6 +736,166 @@ def apply_ref(c, b, step, rot0, tr0):
     dtr, drot = 2 * U * (np.abs(step[:3]).max() + 2.0 ** -126), 2 * U * (np.linalg.norm(step[3:]) + 2.0 ** -126)
     dpose = 2 * rad * (drot + 32 * U) + dtr + 8 * U * (np.abs(x3).max() + np.abs(cen).max() + np.abs(step[:3]).max())
     return new.reshape(-1), tu, ru, dpose, dtr + 2 * U * (np.abs(tr0).max() + np.abs(step[:3]).max()), 2 * drot + 256 * U
+
+
+# =====================================================================================================================================
+# k_symmetry
+# =====================================================================================================================================
+SYM_SIZES = (1, 21, 22, 85, 86, 300)      # residues: 3, 63, 66, 255, 258, 900 atoms - a partial wave, the wave edge, the block stride edge, several strides
+SYM_PARAMS = dict(gain_rot=0.5, gain_tr=0.75, max_rot=0.3, max_tr=10.0, t_start=1.0, snap_last=1)      # (the two gains differ: a swap shows)
+SYM_MIDPOINTS = {5: ((1, 2),), 8: ((1, 3),), 12: ((1, 5),), 24: ((1, 5), (5, 7), (7, 11))}      # neighbouring generators m | m' of each order
+SYM_MUTANTS = {      # name -> the comparison that rejects it
+    "larger_m": "order_m", "no_gcd": "order_m", "no_w_flip": "order_m", "clip_under_snap": "step", "gains_swapped": "step",
+    "centre_all_atoms": "pose", "screw_sign": "step", "compose_order": "rot_update", "last_off_by_one": "step", "last_from_num_steps": "step"}
+
+
+def sym_unpack(out, step):
+    """[B][SYM_OUT] doubles and [B][6] floats -> the dict symmetry_fixtures.check_eval takes."""
+    out = f64(out)
+    m = np.where(np.isnan(out[:, 10]), -1.0, out[:, 10])      # (a slot that was not written holds the sentinel, a NaN)
+    return dict(theta=out[:, 0], screw=out[:, 1], axis=out[:, 2:5], axis_point=out[:, 5:8], fit_rmsd=out[:, 8], sym_rmsd=out[:, 9],
+                order_m=m.astype(np.int64), step=np.asarray(step, f32))
+
+
+def sym_chain(L, seed=0):
+    """A backbone [L][3][3] float32: CA on a random walk of 3.8 A steps, N and C 1.46 / 1.52 A off in independent directions."""
+    rng = np.random.default_rng([31, seed, L])
+    unit = lambda v: v / np.linalg.norm(v, axis=-1, keepdims=True)
+    ca = np.cumsum(3.8 * unit(rng.standard_normal((L, 3))), 0) + rng.standard_normal(3) * 5
+    return np.stack([ca + 1.46 * unit(rng.standard_normal((L, 3))), ca, ca + 1.52 * unit(rng.standard_normal((L, 3)))], 1).astype(f32)
+
+
+def sym_params(**over):
+    return {k: (int(v) if k == "snap_last" else float(f32(v))) for k, v in dict(SYM_PARAMS, **over).items()}
+
+
+def sym_case_of(y, lig, n, all_atoms, params=None):
+    L = len(y)
+    lig = np.asarray(lig, f32).reshape(-1, L, 9)
+    return dict(rec_pos=np.ascontiguousarray(y, f32).reshape(L, 9), lig=np.ascontiguousarray(lig), R=L, L=L, B=len(lig), all_atoms=all_atoms, n=n,
+                params=sym_params(**(params or {})))
+
+
+@functools.lru_cache(maxsize=None)
+def sym_case(L, n, all_atoms, B=8, seed=0):
+    """The special poses of symmetry_fixtures.poses - [0] symmetric, [1] theta = pi, [2] clips, [3] does not, [4] an exact translation (no
+    axis), [5] a NaN - and B - 6 random ones, of a chain of L residues."""
+    import symmetry_fixtures as SF
+    y = sym_chain(L, seed)
+    return sym_case_of(y, SF.poses(y, n, B, np.random.default_rng([32, seed, L, n])), n, all_atoms)
+
+
+@functools.lru_cache(maxsize=None)
+def sym_midpoint_case(n, L=22, all_atoms=0):
+    """Poses 1e-3 rad either side of the midpoint between neighbouring generators, one with theta below the first generator and one above
+    the last.  Returns (case, expected m of each pose)."""
+    import symmetry_fixtures as SF
+    y = sym_chain(L, seed=n)
+    rng = np.random.default_rng([33, n])
+    thetas, want = [], []
+    for m1, m2 in SYM_MIDPOINTS[n]:
+        mid = np.pi * (m1 + m2) / n
+        thetas += [mid - 1e-3, mid + 1e-3]
+        want += [m1, m2]
+    first = 2 * np.pi / n
+    last = max(m for m in range(1, n // 2 + 1) if math.gcd(m, n) == 1)
+    thetas += [0.4 * first, 0.5 * (2 * np.pi * last / n + np.pi)]
+    want += [1, last]
+    lig = [SF.turn(y, th, rng.standard_normal(3), SF.outside_point(y, rng.standard_normal(3), 4.0), rng.standard_normal()).astype(f32) for th in thetas]
+    return sym_case_of(y, np.stack(lig), n, all_atoms), tuple(want)
+
+
+def sym_p32(c):
+    return SY.SymmetryParams(**c["params"])
+
+
+def symmetry_ref(c, b, last=False):
+    """symmetry.evaluate on the kernel's own fp32 coordinates and fp32 parameters at pose b - the definition, never a second run of the
+    kernel - and the margins that make a decision `decided`: m_gap (best against second-best |theta - 2 pi m / n| over the coprime m; inf
+    with one candidate), clip_margin [2] (| |gain v| - max | of translation and rotation), vn (|v| of the fit's quaternion, against
+    symmetry.NO_AXIS) and clipped [2]."""
+    p = sym_p32(c)
+    center = "all_atoms" if c["all_atoms"] else "ca"
+    y, x = c["rec_pos"].reshape(-1, 3, 3), c["lig"][b].reshape(-1, 3, 3)
+    with np.errstate(all="ignore"):
+        ev = SY.evaluate(y, x, c["n"], p, center, last)
+    ref = dict(ev, ev=ev, m_gap=np.inf, clip_margin=np.full(2, np.inf), vn=np.nan, clipped=np.zeros(2, bool))
+    if ev["Q"] is None:
+        return ref
+    q = SY._quaternion(ev["Q"])
+    ref["vn"] = float(np.sqrt(q[1] * q[1] + q[2] * q[2] + q[3] * q[3]))
+    if ev["m"] == 0:
+        return ref
+    d = sorted(abs(ev["theta"] - 2.0 * math.pi * m / c["n"]) for m in range(1, c["n"] // 2 + 1) if math.gcd(m, c["n"]) == 1)
+    if len(d) > 1:
+        ref["m_gap"] = d[1] - d[0]
+    raw = np.array([abs(p.gain_tr * ev["screw"]), abs(p.gain_rot * (ev["theta_star"] - ev["theta"]))])
+    lim = np.array([p.max_tr, p.max_rot])
+    ref["clip_margin"], ref["clipped"] = np.abs(raw - lim), raw > lim
+    return ref
+
+
+def symmetry_restated(c, b, mutant=None, idx=None, num_steps=0, ctl=None, rot0=None, tr0=None):
+    """k_symmetry's decisions restated in float64 on top of the definition's fit (symmetry.fit_transform): the quaternion's sign, the
+    choice of m, `last` from the by-value arguments or the control words, the gains, the clip, the move and the composition.  idx: the
+    step index (None: no t_dev, never the last).  Returns order_m, theta, screw, step [6] and, with rot0 / tr0, pose, tr_update,
+    rot_update.  mutant: one of SYM_MUTANTS -
+      larger_m             of the two generators that bracket theta the larger m, however near the smaller one is
+      no_gcd               m not filtered by gcd(m, n) = 1
+      no_w_flip            the quaternion with w < 0 kept: theta = 2 pi - theta about -u
+      clip_under_snap      the clip applied to the snapped step too
+      gains_swapped        gain_rot on the translation, gain_tr on the rotation
+      centre_all_atoms     the all-atom centroid for the CA family
+      screw_sign           dtau = + gain s u
+      compose_order        rot_update = axis_angle(R(rot_update) R(domega))
+      last_off_by_one      last iff idx == num_steps
+      last_from_num_steps  the by-value num_steps although the control words are given."""
+    p, n = sym_p32(c), c["n"]
+    y, x = f64(c["rec_pos"]).reshape(-1, 3, 3), f64(c["lig"][b]).reshape(-1, 3, 3)
+    center = "all_atoms" if (c["all_atoms"] or mutant == "centre_all_atoms") else "ca"
+    Q, tau, _ = SY.fit_transform(y, x)
+    q = SY._quaternion(Q)
+    w, v = q[0], q[1:]
+    vn = float(np.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]))
+    out = dict(order_m=0, theta=0.0, screw=np.nan, step=np.zeros(6))
+    if vn > SY.NO_AXIS:
+        if mutant == "no_w_flip":
+            w, v = -w, -v
+        theta, u = 2.0 * math.atan2(vn, w), v / vn
+        cen = SY._centroid(x, center)
+        s = float(u @ (cen - Q.T @ (cen - tau)))
+        best = None
+        for m in range(1, n // 2 + 1):
+            if mutant != "no_gcd" and math.gcd(m, n) != 1:
+                continue
+            d = abs(theta - 2.0 * math.pi * m / n)
+            if best is None or d < best[0]:
+                best = (d, 2.0 * math.pi * m / n, m)
+        if mutant == "larger_m":      # the larger of the two generators that bracket theta (or the nearest one's larger neighbour)
+            ms = [m for m in range(1, n // 2 + 1) if math.gcd(m, n) == 1]
+            above = [m for m in ms if 2.0 * math.pi * m / n >= theta]
+            m = above[0] if above else ms[-1]
+            best = (0.0, 2.0 * math.pi * m / n, m)
+        _, ts, m_sel = best
+        last = False
+        if idx is not None:
+            S = num_steps if (ctl is None or mutant == "last_from_num_steps") else int(ctl[3])
+            last = (idx == S) if mutant == "last_off_by_one" else (idx + 1 == S)
+        snap = last and bool(p.snap_last)
+        g_tr, g_rot = (1.0, 1.0) if snap else ((p.gain_rot, p.gain_tr) if mutant == "gains_swapped" else (p.gain_tr, p.gain_rot))
+        st = np.concatenate([(g_tr if mutant == "screw_sign" else -g_tr) * s * u, g_rot * (ts - theta) * u])
+        if not snap or mutant == "clip_under_snap":
+            st = np.concatenate([SY._clip(st[:3], p.max_tr), SY._clip(st[3:], p.max_rot)])
+        out.update(order_m=m_sel, theta=theta, screw=s, step=st)
+    if rot0 is not None:
+        cen = SY._centroid(x, center)
+        st = out["step"]
+        Rm = RS.axis_angle_to_matrix(st[3:])
+        out["pose"] = ((x - cen) @ Rm.T + cen + st[:3]).reshape(-1)
+        out["tr_update"] = f64(tr0) + st[:3]
+        R0 = RS.axis_angle_to_matrix(f64(rot0))
+        out["rot_update"] = RS.matrix_to_axis_angle(R0 @ Rm if mutant == "compose_order" else Rm @ R0)
+    return out
 
 
 # =====================================================================================================================================

@@ -1,14 +1,15 @@
-// aux_harness.hip - test-only host shim around the four launchers of libdfmdock_amd.so that the other seven harnesses leave out
+// aux_harness.hip - test-only host shim around the five launchers of libdfmdock_amd.so that the other eight harnesses leave out
 // (tests/aux_harness.py builds it): dfm::launch_pair_dist_sum (k_pair_dist_sum + k_dist_finish + k_dist_mean), launch_restraint,
-// launch_igso3_cdf and launch_start_pose.
+// launch_symmetry, launch_igso3_cdf and launch_start_pose.
 //
 // Host code only: no kernels here.  The one entry point takes a call record of named host buffers and an op code.  BEFORE anything is
 // uploaded it checks everything a kernel would follow as an index - every array long enough for the launch it feeds, pair indices
 // below R / L, gstart strictly increasing from 0 to P, `big` naming each group of more than RS_SMALL pairs once and no other,
 // G <= RS_MAX_GROUPS, part / res of pair_dist_sum_parts(R, L) slots, contact_bins in 1 .. 63, the index into t_dev (ctl[0] - 1 or step)
-// inside it - and answers hipErrorInvalidValue without a launch when one fails: no call makes a kernel read or write outside its
-// blocks.  Then the guard-band protocol of harness_common.h runs with the shipped structs (PairDistSumArgs, RestraintArgs, StartArgs)
-// filled from the record.  An optional pointer whose slot is unused is passed as nullptr.
+// inside it, for the symmetry step R == L, the order in SYM_MIN_ORDER .. SYM_MAX_ORDER and a control block of 16 bytes (k_symmetry reads
+// ctl[3], k_restraint stops at ctl[0]) - and answers hipErrorInvalidValue without a launch when one fails: no call makes a kernel read
+// or write outside its blocks.  Then the guard-band protocol of harness_common.h runs with the shipped structs (PairDistSumArgs,
+// RestraintArgs, SymmetryArgs, StartArgs) filled from the record.  An optional pointer whose slot is unused is passed as nullptr.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -28,10 +29,11 @@ enum Slot {
     S_REC_POS, S_GSTART, S_PAIRS, S_UPPER, S_WEIGHT, S_BIG, S_LIG, S_TR_UPD, S_ROT_UPD, S_T_DEV, S_CTL, S_OUT,
     S_PREP_POS, S_PREP_CA4, S_PREP_CB4,
     S_CDF, S_START, S_U_INJ, S_AXIS_INJ, S_TR_INJ,
+    S_SYM_OUT, S_STEP_OUT,
     N_SLOTS
 };
 
-enum Op { OP_PAIR_DIST_SUM, OP_RESTRAINT, OP_IGSO3_CDF, OP_START_POSE };
+enum Op { OP_PAIR_DIST_SUM, OP_RESTRAINT, OP_IGSO3_CDF, OP_START_POSE, OP_SYMMETRY };
 
 constexpr long long H = 256;
 
@@ -43,16 +45,19 @@ struct Call {
     harness::HarnessBuf buf[N_SLOTS];
     double sigma, sigma_r3;
     long long start_bstride;
-    float near_cut, k_tr, k_rot, max_tr, max_rot, t_start;
-    // B trajectories; R / L residues; G groups of n_pairs pairs, n_big of them large; n_t entries of t_dev
-    int B, R, L, contact_bins, all_atoms, perturb, G, n_big, n_pairs, apply, prep_next, n_t;
-    unsigned step, seed_lo, seed_hi;
+    float near_cut, k_tr, k_rot, max_tr, max_rot, t_start, gain_rot, gain_tr;
+    // B trajectories; R / L residues; G groups of n_pairs pairs, n_big of them large; n_t entries of t_dev; n the order of the symmetry
+    int B, R, L, contact_bins, all_atoms, perturb, G, n_big, n_pairs, apply, prep_next, n_t, n, snap_last;
+    unsigned step, seed_lo, seed_hi, num_steps;
 };
 
 HARNESS_EXPORTS(Call)
 long long ax_parts(int R, int L) { return (long long)dfm::pair_dist_sum_parts(R, L); }
 int ax_rs_small() { return dfm::RS_SMALL; }
 int ax_rs_max_groups() { return dfm::RS_MAX_GROUPS; }
+int ax_sym_out() { return dfm::SYM_OUT; }
+int ax_sym_min_order() { return dfm::SYM_MIN_ORDER; }
+int ax_sym_max_order() { return dfm::SYM_MAX_ORDER; }
 
 // the checks alone (what kh_run does first): hipSuccess or hipErrorInvalidValue.  Touches no device.
 int ax_check(const Call *c, int op)
@@ -117,6 +122,26 @@ int ax_check(const Call *c, int op)
         }
         return ok ? (int)hipSuccess : (int)hipErrorInvalidValue;
     }
+    if (op == OP_SYMMETRY) {
+        ok = B >= 1 && B <= 65535 && R == L && L >= 1 && L <= (1 << 20) && c->n >= dfm::SYM_MIN_ORDER && c->n <= dfm::SYM_MAX_ORDER &&
+             (c->apply == 0 || c->apply == 1) && (c->prep_next == 0 || c->prep_next == 1) && (c->snap_last == 0 || c->snap_last == 1);
+        if (!ok) return (int)hipErrorInvalidValue;
+        ok = in(S_REC_POS, R * 36) && (c->apply ? io(S_LIG, B * L * 36) : has(S_LIG, B * L * 36) && c->buf[S_LIG].out != 1) &&
+             (c->apply ? io(S_TR_UPD, B * 12) && io(S_ROT_UPD, B * 12) : !c->buf[S_TR_UPD].host && !c->buf[S_ROT_UPD].host) &&
+             opt_out(S_SYM_OUT, B * dfm::SYM_OUT * 8) && opt_out(S_STEP_OUT, B * 24);
+        if (ok && c->prep_next) ok = out(S_PREP_POS, B * N * 16) && out(S_PREP_CA4, B * N * 16) && out(S_PREP_CB4, B * N * 16);
+        if (ok && !c->prep_next) ok = !c->buf[S_PREP_POS].host && !c->buf[S_PREP_CA4].host && !c->buf[S_PREP_CB4].host;
+        if (ok && c->buf[S_T_DEV].host) {
+            ok = c->n_t >= 1 && in(S_T_DEV, (long long)c->n_t * 4) && opt_in(S_CTL, 16);      // (k_symmetry reads ctl[3]: 16 bytes, not k_restraint's 12)
+            if (ok) {
+                const uint32_t idx = c->buf[S_CTL].host ? ((const uint32_t *)c->buf[S_CTL].host)[0] - 1u : c->step;
+                ok = idx < (uint32_t)c->n_t;
+            }
+        } else if (ok) {
+            ok = !c->buf[S_CTL].host;
+        }
+        return ok ? (int)hipSuccess : (int)hipErrorInvalidValue;
+    }
     if (op == OP_IGSO3_CDF) return out(S_CDF, (long long)dfm::IGSO3_N * 8) ? (int)hipSuccess : (int)hipErrorInvalidValue;
     if (op == OP_START_POSE) {
         ok = B >= 1 && B <= 65535 && L >= 1 && L <= (1 << 20) && (c->start_bstride == 0 || c->start_bstride >= L * 9) &&
@@ -157,6 +182,15 @@ int kh_run(const Call *c, int op)
     ra.prep_next = c->prep_next;
     ra.prep_pos = (float4 *)P(S_PREP_POS); ra.prep_ca4 = (float4 *)P(S_PREP_CA4); ra.prep_cb4 = (float4 *)P(S_PREP_CB4);
 
+    dfm::SymmetryArgs sy;
+    std::memset(&sy, 0, sizeof(sy));
+    sy.rec_pos = F(S_REC_POS); sy.R = c->R; sy.L = c->L; sy.all_atoms = c->all_atoms; sy.n = c->n;
+    sy.gain_rot = c->gain_rot; sy.gain_tr = c->gain_tr; sy.max_rot = c->max_rot; sy.max_tr = c->max_tr; sy.t_start = c->t_start;
+    sy.snap_last = c->snap_last; sy.lig = F(S_LIG); sy.apply = c->apply; sy.tr_update = F(S_TR_UPD); sy.rot_update = F(S_ROT_UPD);
+    sy.t_dev = F(S_T_DEV); sy.step = c->step; sy.num_steps = c->num_steps; sy.ctl = (const uint32_t *)P(S_CTL);
+    sy.out = (double *)P(S_SYM_OUT); sy.step_out = F(S_STEP_OUT); sy.prep_next = c->prep_next;
+    sy.prep_pos = (float4 *)P(S_PREP_POS); sy.prep_ca4 = (float4 *)P(S_PREP_CA4); sy.prep_cb4 = (float4 *)P(S_PREP_CB4);
+
     dfm::StartArgs sa;
     std::memset(&sa, 0, sizeof(sa));
     sa.start = F(S_START); sa.start_bstride = c->start_bstride; sa.L = c->L; sa.all_atoms = c->all_atoms; sa.perturb = c->perturb;
@@ -171,6 +205,7 @@ int kh_run(const Call *c, int op)
         case OP_RESTRAINT: e = dfm::launch_restraint(ra, c->B, s); break;
         case OP_IGSO3_CDF: e = dfm::launch_igso3_cdf(c->sigma, (double *)P(S_CDF), s); break;
         case OP_START_POSE: e = dfm::launch_start_pose(sa, c->B, s); break;
+        case OP_SYMMETRY: e = dfm::launch_symmetry(sy, c->B, s); break;
         default: e = hipErrorInvalidValue;
     }
     return (int)blk.finish(e);

@@ -1,6 +1,7 @@
-// pose_harness.hip - test-only host shim around the rigid-pose launchers of libdfmdock_amd.so (tests/pose_harness.py builds it): the six
+// pose_harness.hip - test-only host shim around the rigid-pose launchers of libdfmdock_amd.so (tests/pose_harness.py builds it): the seven
 // dfm::launch_*_pose, launch_sterics (the shared cell walk of dfm_posewalk.h, the one launcher with `exits`), launch_iface,
-// launch_pairpot, launch_hbond, launch_surface (with its finish kernel), launch_rescon, launch_rescon_finish and launch_hbond_finish.
+// launch_pairpot, launch_hbond, launch_surface (with its finish kernel), launch_rescon, launch_rescon_finish, launch_hbond_finish and
+// launch_density (a gather from a grid, no cell walk: it shares the pose kernels' pose_transform and T).
 //
 // Host code only: no kernels here.  The one entry point takes a call record of named host buffers and an op code.  BEFORE anything is
 // uploaded it checks everything a kernel would follow as an index - every array long enough for the launch it feeds, cell_start of
@@ -8,8 +9,10 @@
 // T, slab offsets type * T * NB, NB in 1 .. 64 with its `top`, e2 of 128 slots that end in +inf - and answers
 // hipErrorInvalidValue without a launch when one fails: no call makes a kernel read outside its blocks.  Then the guard-band protocol of
 // harness_common.h runs, with the shipped structs (WalkGrid, StericsConst / StericsAtoms, IfaceConst / IfaceAtoms, PairpotConst /
-// PairpotAtoms, ResconConst / ResconAtoms, HbondAtoms, SurfaceAtoms) filled from the record.  A per-atom output the caller leaves out is
-// passed as nullptr.
+// PairpotAtoms, ResconConst / ResconAtoms, HbondAtoms, SurfaceAtoms, DensityAtoms) filled from the record.  A per-atom output the
+// caller leaves out is passed as nullptr.  The density launch is checked for its array lengths (for max(., 2) nodes per axis,
+// max(Al, 1) atoms and max(n, 0) poses), a finite geo with voxel > 0 and geo[10..12] == nx - 1, ny - 1, nz - 1 (the bounds the kernel
+// turns into corner indices); n, nx / ny / nz < 2 and Al < 1 go through to the launcher, whose refusals they are.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -29,13 +32,14 @@ enum Slot {
     S_EXITS, S_TOT, S_BITS, S_CLASS_MASK, S_LIG_CLASS, S_REC_DEGREE, S_LIG_DEGREE, S_REC_PAR, S_LIG_PAR, S_LIG_VDW, S_LIG_ELEC, S_LIG_TYPE,
     S_TABLE_Q, S_E2, S_LIG_Q, S_COUNTS, S_REC_ANTE, S_LIG_ANTE, S_REC_INDEX, S_REC_HB, S_REC_SB, S_LIG_HB, S_LIG_SB,
     S_DIRS, S_REC_CLASS, S_REC_EXP, S_LIG_EXP, S_REC_BUR, S_LIG_BURIED, S_REC_BURIED,
+    S_GRID, S_GEO, S_ATOM_Q,
     N_SLOTS
 };
 
 // OP_STERICS_CHAIN: launch_sterics_pose, then launch_sterics on the T it wrote, as dfm_pose_sterics chains them
 enum Op {
     OP_POSE_STERICS, OP_POSE_SURFACE, OP_POSE_IFACE, OP_POSE_RESCON, OP_POSE_HBOND, OP_POSE_PAIRPOT, OP_STERICS, OP_STERICS_CHAIN,
-    OP_RESCON, OP_RESCON_FINISH, OP_HBOND_FINISH, OP_IFACE, OP_PAIRPOT, OP_HBOND, OP_SURFACE
+    OP_RESCON, OP_RESCON_FINISH, OP_HBOND_FINISH, OP_IFACE, OP_PAIRPOT, OP_HBOND, OP_SURFACE, OP_POSE_DENSITY, OP_DENSITY
 };
 
 }  // namespace
@@ -50,8 +54,8 @@ struct Call {
     double probe;                          // SurfaceConst (with slack and G)
     float reject2, slack;
     // n poses; Ar / Al atoms; Rr / Lr residues and W words per bitmap row (rescon); Lc rows of Wc words (hbond finish); NT types, NB bins
-    // and top (pairpot); Rc / Lc charged residues (hbond: Ar / Al are its polar atoms)
-    int nx, ny, nz, n, Ar, Al, Rr, Lr, W, Lc, Wc, NT, NB, top, Rc, G;
+    // and top (pairpot); Rc / Lc charged residues (hbond: Ar / Al are its polar atoms); C channels (density: nx / ny / nz are its nodes)
+    int nx, ny, nz, n, Ar, Al, Rr, Lr, W, Lc, Wc, NT, NB, top, Rc, G, C;
 };
 
 HARNESS_EXPORTS(Call)
@@ -68,13 +72,31 @@ int ph_check(const Call *c, int op)
     for (int i = 0; i < N_SLOTS; ++i) ok = ok && c->buf[i].bytes >= 0 && c->buf[i].out >= 0 && c->buf[i].out <= 2;
     if (!ok) return (int)hipErrorInvalidValue;
 
-    if (op >= OP_POSE_STERICS && op <= OP_POSE_PAIRPOT) {
+    if ((op >= OP_POSE_STERICS && op <= OP_POSE_PAIRPOT) || op == OP_POSE_DENSITY) {
         ok = c->n >= 1 && has(S_ROT, n * 12) && has(S_TR, n * 12) && out(S_T, n * 96);
         if (op == OP_POSE_STERICS) ok = ok && out(S_N_CLASH, n * 4) && out(S_N_CONTACT, n * 4) && out(S_MIN_BITS, n * 8);
         if (op == OP_POSE_SURFACE) ok = ok && out(S_TOT, n * 32 * 4);
         if (op == OP_POSE_IFACE) ok = ok && out(S_TOT, n * 4 * 8);
         if (op == OP_POSE_HBOND) ok = ok && out(S_TOT, n * 5 * 4);
         if (op == OP_POSE_PAIRPOT) ok = ok && out(S_TOT, n * 2 * 8);
+        if (op == OP_POSE_DENSITY) ok = ok && out(S_TOT, n * dfm::DENSITY_TOT * 8);
+        return ok ? (int)hipSuccess : (int)hipErrorInvalidValue;
+    }
+    if (op == OP_DENSITY) {
+        // n, nx / ny / nz < 2 and Al < 1 are the launcher's to refuse: the arrays are checked for what a launch could touch whatever they are
+        auto at_least = [](long long v, long long lo) { return v < lo ? lo : v; };
+        ok = c->nx <= 1024 && c->ny <= 1024 && c->nz <= 1024 && Al <= (1 << 24) && c->n <= (1 << 20) && c->C >= 1 && c->C <= 4;
+        if (!ok) return (int)hipErrorInvalidValue;
+        const long long nodes = at_least(c->nx, 2) * at_least(c->ny, 2) * at_least(c->nz, 2), atoms = at_least(Al, 1);
+        ok = has(S_GRID, nodes * 16) && c->buf[S_GRID].out == 0 && has(S_LIG, atoms * 16) && c->buf[S_LIG].out == 0 &&
+             has(S_GEO, dfm::DENSITY_GEO_SLOTS * 8) && c->buf[S_GEO].out == 0 && has(S_T, n * 96) && out(S_TOT, n * dfm::DENSITY_TOT * 8) &&
+             opt(S_ATOM_Q, n * atoms * 8);
+        if (ok) {
+            const double *geo = (const double *)c->buf[S_GEO].host;
+            for (int k = 0; k < dfm::DENSITY_GEO_SLOTS; ++k) ok = ok && std::isfinite(geo[k]);
+            ok = ok && geo[3] > 0.0 && geo[4] > 0.0 && geo[5] > 0.0 && geo[10] == (double)(c->nx - 1) && geo[11] == (double)(c->ny - 1) &&
+                 geo[12] == (double)(c->nz - 1);
+        }
         return ok ? (int)hipSuccess : (int)hipErrorInvalidValue;
     }
     if (op == OP_RESCON_FINISH) {
@@ -247,6 +269,10 @@ int kh_run(const Call *c, int op)
     su.sc.g = g; su.sc.probe = c->probe; su.sc.slack = c->slack; su.sc.G = c->G;
     su.Ar = c->Ar; su.Al = c->Al;
 
+    dfm::DensityAtoms da = {};
+    da.grid = (const float *)D(S_GRID); da.lig = sa.lig; da.geo = (const double *)D(S_GEO);
+    da.nx = c->nx; da.ny = c->ny; da.nz = c->nz; da.C = c->C; da.Al = c->Al;
+
     const float *rot = (const float *)D(S_ROT), *tr = (const float *)D(S_TR);
     double *T = (double *)D(S_T);
     int32_t *n_clash = (int32_t *)D(S_N_CLASH), *n_contact = (int32_t *)D(S_N_CONTACT);
@@ -261,6 +287,8 @@ int kh_run(const Call *c, int op)
         case OP_POSE_RESCON: e = dfm::launch_rescon_pose(rot, tr, c->n, T, s); break;
         case OP_POSE_HBOND: e = dfm::launch_hbond_pose(rot, tr, c->n, T, (int32_t *)D(S_TOT), s); break;
         case OP_POSE_PAIRPOT: e = dfm::launch_pairpot_pose(rot, tr, c->n, T, (int64_t *)D(S_TOT), s); break;
+        case OP_POSE_DENSITY: e = dfm::launch_density_pose(rot, tr, c->n, T, (int64_t *)D(S_TOT), s); break;
+        case OP_DENSITY: e = dfm::launch_density(da, T, c->n, (int64_t *)D(S_TOT), (int64_t *)D(S_ATOM_Q), s); break;
         case OP_STERICS_CHAIN:
             e = dfm::launch_sterics_pose(rot, tr, c->n, T, n_clash, n_contact, min_bits, s);
             if (e != hipSuccess) break;

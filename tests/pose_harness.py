@@ -41,16 +41,16 @@ POSE_GATE_FACTOR = 8.0
 SLOTS = ("rot", "tr", "T", "rec", "lig", "sphere", "cell_start", "lig_index", "n_clash", "n_contact", "min_bits", "lig_clash", "lig_contact",
          "exits", "tot", "bits", "class_mask", "lig_class", "rec_degree", "lig_degree", "rec_par", "lig_par", "lig_vdw", "lig_elec", "lig_type",
          "table_q", "e2", "lig_q", "counts", "rec_ante", "lig_ante", "rec_index", "rec_hb", "rec_sb", "lig_hb", "lig_sb",
-         "dirs", "rec_class", "rec_exp", "lig_exp", "rec_bur", "lig_buried", "rec_buried")
+         "dirs", "rec_class", "rec_exp", "lig_exp", "rec_bur", "lig_buried", "rec_buried", "grid", "geo", "atom_q")
 VECS = ("lo", "hi", "center")
 DOUBLES = ("edge", "grow", "clash", "contact", "cut2", "soft", "min2", "kc", "lo2", "hb2", "salt2", "c2", "probe")
-INTS = ("nx", "ny", "nz", "n", "Ar", "Al", "Rr", "Lr", "W", "Lc", "Wc", "NT", "NB", "top", "Rc", "G")
+INTS = ("nx", "ny", "nz", "n", "Ar", "Al", "Rr", "Lr", "W", "Lc", "Wc", "NT", "NB", "top", "Rc", "G", "C")
 OPS = ("pose_sterics", "pose_surface", "pose_iface", "pose_rescon", "pose_hbond", "pose_pairpot", "sterics", "sterics_chain", "rescon",
-       "rescon_finish", "hbond_finish", "iface", "pairpot", "hbond", "surface")
-POSE_OPS = OPS[:6]
+       "rescon_finish", "hbond_finish", "iface", "pairpot", "hbond", "surface", "pose_density", "density")
+POSE_OPS = OPS[:6] + ("pose_density",)
 # what each pose kernel zeroes next to T: (slot, dtype, entries per pose) - rescon has nothing
 POSE_TOTALS = {"pose_sterics": None, "pose_surface": ("tot", np.int32, 32), "pose_iface": ("tot", np.int64, 4), "pose_rescon": None,
-               "pose_hbond": ("tot", np.int32, 5), "pose_pairpot": ("tot", np.int64, 2)}
+               "pose_hbond": ("tot", np.int32, 5), "pose_pairpot": ("tot", np.int64, 2), "pose_density": ("tot", np.int64, 6)}
 
 f32 = np.float32
 
@@ -224,6 +224,21 @@ class Harness(kh.KernelHarness):
         r = self.run("hbond_finish", dict(bits=np.ascontiguousarray(bits, np.uint32), tot=Out(np.int32, init=np.asarray(base, np.int32))),
                      n=P, Lc=Lc, Wc=Wc)
         return r["tot"].reshape(P, 5)
+
+    def density(self, dc, T, atom_q=True, base=None, extra=2, check=True, **over):
+        """launch_density on the case dc (density_case) and T [P,12] float64.  tot has room for `extra` more poses and starts as `base`
+        ([P + extra][6], default zeros); atom_q ([P][Al] and extra * Al entries behind) starts as MARKER.  over: scalars (n, Al, nx, ny,
+        nz, C) or the geo buffer as a call that the launcher must refuse wants them."""
+        P, Al = len(T), dc["Al"]
+        base = np.zeros((P + extra, 6), np.int64) if base is None else np.asarray(base, np.int64)
+        bufs = dict(grid=dc["grid4"], geo=over.pop("geo", dc["geo"]), lig=dc["lig4"], T=np.ascontiguousarray(T, np.float64), tot=Out(np.int64, init=base))
+        if atom_q:
+            bufs["atom_q"] = Out(np.int64, init=np.full((P + extra) * max(Al, 1), MARKER, np.int64))
+        sc = dict(nx=dc["dims"][0], ny=dc["dims"][1], nz=dc["dims"][2], n=P, Al=Al, C=dc["C"])
+        sc.update(over)
+        r = self.run("density", bufs, check=check, **sc)
+        r["tot"] = r["tot"].reshape(P + extra, 6)
+        return r
 
 
 # ---- the frame, from the comments of dfm_poseprep.h -----------------------------------------------------------------------------------
@@ -1409,3 +1424,311 @@ def surface_cases():
     drot, dtr = touching_poses(drng, 2, 0.3, 0.5)
     out.append(("dense clump", Surface(drec, three(400), dlig, three(70), centre_of(dlig), 1.4, 128, masks(400, 2), masks(70, 2)), pose_T(drot, dtr), drot, dtr))
     return tuple(out)
+
+
+# =====================================================================================================================================
+# k_density_pose / k_density: a gather, no cell walk
+# =====================================================================================================================================
+DENSITY_SHAPES = ((2, 2, 2), (3, 5, 4))      # [nz, ny, nx]
+DENSITY_AL = (1, 63, 64, 65, 130)
+DENSITY_N = (1, 2, 5)
+DENSITY_MUTANTS = {      # name -> the comparison of density_compare that rejects it
+    "le_upper": "n_inside", "trunc": "n_inside", "fx_f32": "atom_q", "y_before_x": "atom_q", "stride_swapped": "atom_q", "half_away": "atom_q",
+    "contracted": "atom_q", "channel1_above": "n_above", "lanes_past_Al": "n_inside", "tot_stored": "sum_q"}
+
+
+def density_case(shape, C, Al, seed=0, origin=(-3.0, 2.0, -5.0), voxel=(1.5, 1.0, 2.0), threshold=0.125, center=None, lig=None, w=None, grid4=None):
+    """Inputs of one launch_density: a grid [nz][ny][nx] of float4 whose FOUR channels are all non-zero whatever C is (the launcher must not
+    add the ones at or above C), anisotropic voxels, a negative origin, atoms from a quarter of the extent outside to a quarter beyond."""
+    rng = np.random.default_rng([71, seed, C, Al] + list(shape))
+    nz, ny, nx = shape
+    o, v = f32(origin), f32(voxel)
+    if grid4 is None:
+        grid4 = rng.uniform(-4.0, 4.0, (nz, ny, nx, 4)).astype(f32)
+    ext = v * (f32([nx, ny, nz]) - 1)
+    if lig is None:
+        lig = (o + ext * rng.uniform(-0.25, 1.25, (max(Al, 1), 3))).astype(f32)
+    if w is None:
+        w = rng.uniform(-8.0, 8.0, len(lig)).astype(f32)
+    cen = f32(lig.mean(0) if center is None else center)
+    geo = np.concatenate([f64(o), f64(v), f64(cen), [float(f32(threshold))], [nx - 1.0, ny - 1.0, nz - 1.0], np.zeros(3)])
+    return dict(grid4=np.ascontiguousarray(grid4, f32), geo=geo, lig4=np.ascontiguousarray(np.concatenate([f32(lig), f32(w)[:, None]], 1), f32),
+                dims=(nx, ny, nz), C=C, Al=Al, origin=o, voxel=v, center=cen, threshold=float(f32(threshold)))
+
+
+def density_poses(dc, n, seed=0, s_rot=0.3, s_tr=0.2):
+    """rot, tr [n,3] float32: rotations of about s_rot rad, translations of about s_tr times the grid's smallest extent."""
+    rng = np.random.default_rng([72, seed, n])
+    ext = float((f64(dc["voxel"]) * dc["geo"][10:13]).min())
+    return (rng.standard_normal((n, 3)) * s_rot).astype(f32), (rng.standard_normal((n, 3)) * s_tr * ext).astype(f32)
+
+
+def density_base(P, extra=2, seed=0):
+    """What tot starts as: values of every size and sign, [P + extra][6]."""
+    rng = np.random.default_rng([73, seed, P])
+    return rng.integers(-(1 << 40), 1 << 40, (P + extra, 6)).astype(np.int64)
+
+
+def _two_product_error(w, val):
+    """The exact error of fl(w val) for w a widened fp32 number (Veltkamp split of val: both partial products are exact)."""
+    p = w * val
+    bits_ = np.ascontiguousarray(val, np.float64).view(np.uint64) & np.uint64(0xFFFFFFFFF8000000)
+    hi = bits_.view(np.float64)
+    lo = val - hi
+    return (w * hi - p) + w * lo
+
+
+def density_ref(grid, geo, lig4, T, C, mutant=None, base=None):
+    """k_density restated in float64 numpy from T as twelve doubles, in the kernel's operation order and parenthesisation:
+    ((qx t0 + qy t1) + qz t2) + c + t9, the division by the voxel, floor, the seven lerps of every channel, rint((w val) 2^20).  grid
+    [nz][ny][nx][4] float32, geo [16], lig4 [Al][4].  Returns integers only: tot [P][6] (= base + the sums where a base is given; the
+    channels at or above C are not added), atom_q [P][Al], inside [P][Al].  mutant: one of DENSITY_MUTANTS -
+      le_upper        u <= n - 1 at the upper face (the corner index runs into the next row, as flat addressing does)
+      trunc           the cell by truncation, the inside test on it: u in (-1, 0) lands in cell 0
+      fx_f32          the fraction along x rounded to fp32
+      y_before_x      the lerps along y before those along x
+      stride_swapped  ny for nx in the row stride
+      half_away       ties away from zero in the quantisation
+      contracted      the product w val not rounded before the scale (decided by its exact error at a tie)
+      channel1_above  n_above from channel 1
+      lanes_past_Al   the idle lanes of the last block counted (they hold the last atom)
+      tot_stored      tot stored, not added to."""
+    grid = np.asarray(grid, f32)
+    nz, ny, nx = grid.shape[:3]
+    G = grid.reshape(-1, 4)
+    geo, lig4, T = f64(geo), np.asarray(lig4, f32).reshape(-1, 4), f64(T).reshape(-1, 12)
+    P, Al = len(T), len(lig4)
+    t = T[:, None, :]
+    with np.errstate(all="ignore"):
+        fin = ~np.isnan((T * 0.0).sum(1))
+        q3 = f64(lig4[:, :3]) - geo[6:9]
+        qx, qy, qz = q3[None, :, 0], q3[None, :, 1], q3[None, :, 2]
+        X = ((qx * t[..., 0] + qy * t[..., 1]) + qz * t[..., 2]) + geo[6] + t[..., 9]
+        Y = ((qx * t[..., 3] + qy * t[..., 4]) + qz * t[..., 5]) + geo[7] + t[..., 10]
+        Z = ((qx * t[..., 6] + qy * t[..., 7]) + qz * t[..., 8]) + geo[8] + t[..., 11]
+        u = np.stack([(X - geo[0]) / geo[3], (Y - geo[1]) / geo[4], (Z - geo[2]) / geo[5]], -1)      # [P][Al][3]
+        n1 = geo[10:13]
+        if mutant == "trunc":
+            cell = np.trunc(u)
+            inside = ((cell >= 0.0) & (cell <= n1 - 1.0)).all(-1)
+        elif mutant == "le_upper":
+            inside = ((u >= 0.0) & (u <= n1)).all(-1)
+        else:
+            inside = ((u >= 0.0) & (u < n1)).all(-1)
+        inside &= fin[:, None]
+        um = np.where(inside[..., None], u, 0.0)
+        fl = np.trunc(um) if mutant == "trunc" else np.floor(um)
+        f = um - fl
+        fx, fy, fz = f[..., 0, None], f[..., 1, None], f[..., 2, None]
+        if mutant == "fx_f32":
+            fx = f64(fx.astype(f32))
+        ix, iy, iz = (fl[..., k].astype(np.int64) for k in range(3))
+        row, slab = (ny if mutant == "stride_swapped" else nx), nx * ny
+        first = (iz * ny + iy) * row + ix
+        c = lambda dz, dy, dx: f64(G[(first + dx + dy * row + dz * slab) % len(G)])      # [P][Al][4]; the wrap is reached by mutants only
+        c000, c100, c010, c110, c001, c101, c011, c111 = c(0, 0, 0), c(0, 0, 1), c(0, 1, 0), c(0, 1, 1), c(1, 0, 0), c(1, 0, 1), c(1, 1, 0), c(1, 1, 1)
+        if mutant == "y_before_x":
+            a00, a10 = c000 + fy * (c010 - c000), c100 + fy * (c110 - c100)
+            a01, a11 = c001 + fy * (c011 - c001), c101 + fy * (c111 - c101)
+            c0, c1 = a00 + fx * (a10 - a00), a01 + fx * (a11 - a01)
+        else:
+            c00, c10 = c000 + fx * (c100 - c000), c010 + fx * (c110 - c010)
+            c01, c11 = c001 + fx * (c101 - c001), c011 + fx * (c111 - c011)
+            c0, c1 = c00 + fy * (c10 - c00), c01 + fy * (c11 - c01)
+        val = c0 + fz * (c1 - c0)
+        w = f64(lig4[:, 3])[None, :, None]
+        s = (w * val) * QUANTA
+        r = np.rint(s)
+        if mutant == "half_away":
+            r = np.sign(s) * np.floor(np.abs(s) + 0.5)
+        elif mutant == "contracted":
+            err = _two_product_error(np.broadcast_to(w, val.shape), val)
+            tie = (s - np.floor(s)) == 0.5
+            r = np.where(tie & (err != 0.0), np.floor(s) + (err > 0.0), r)
+        q = np.where(inside[..., None], r, 0.0).astype(np.int64)
+        above = inside & (val[..., 1 if mutant == "channel1_above" else 0] >= geo[9])
+    tot = np.zeros((P, 6), np.int64)
+    tot[:, :4], tot[:, 4], tot[:, 5] = q.sum(1), inside.sum(1), above.sum(1)
+    if mutant == "lanes_past_Al":
+        pad = (-Al) % 64
+        tot[:, :4] += pad * q[:, -1]
+        tot[:, 4] += pad * inside[:, -1]
+        tot[:, 5] += pad * above[:, -1]
+    tot[:, C:4] = 0
+    if base is not None:
+        b = np.asarray(base, np.int64)[:P]
+        if mutant == "tot_stored":
+            written = np.zeros((P, 6), bool)
+            written[:, :C], written[:, 4], written[:, 5] = True, True, tot[:, 5] != 0
+            written &= inside.any(1)[:, None]
+            tot = np.where(written, tot, b)
+        else:
+            tot = b + tot
+    return dict(tot=tot, atom_q=q[..., 0].copy(), inside=inside)
+
+
+def density_compare(out, ref, P, Al, base=None, atom_q=True):
+    """Every comparison of one launch against density_ref (which holds the base already), as numbers of mismatches: sum_q, n_inside,
+    n_above, atom_q, `past` (a total past pose P that is not the base any more, an atom_q entry past [P][Al] that is not the marker)."""
+    tot = np.asarray(out["tot"]).reshape(-1, 6)
+    cmp = {"sum_q": int((tot[:P, :4] != ref["tot"][:, :4]).sum()), "n_inside": int((tot[:P, 4] != ref["tot"][:, 4]).sum()),
+           "n_above": int((tot[:P, 5] != ref["tot"][:, 5]).sum()), "past": 0}
+    if len(tot) > P:
+        cmp["past"] += int((tot[P:] != (0 if base is None else np.asarray(base, np.int64)[P:])).sum())
+    if atom_q:
+        aq = np.asarray(out["atom_q"]).reshape(-1)
+        cmp["atom_q"] = int((aq[:P * Al] != ref["atom_q"].reshape(-1)).sum())
+        cmp["past"] += int((aq[P * Al:] != MARKER).sum())
+    return cmp
+
+
+def density_definition(dc, rot, tr):
+    """dfmdock_amd.density.density on the case's first C channels: the package's definition."""
+    from dfmdock_amd import density as DN
+    grids = np.ascontiguousarray(np.moveaxis(dc["grid4"][..., :dc["C"]], -1, 0))
+    return DN.density(grids, dc["origin"], dc["voxel"], dc["lig4"][:, :3], dc["lig4"][:, 3], dc["center"], rot, tr, dc["threshold"], per_atom=True)
+
+
+@functools.lru_cache(maxsize=None)
+def density_launches(shape, C):
+    """[(dc, rot, tr, T, base)] of test_density_exact for one grid and one C: every Al of DENSITY_AL with every n of DENSITY_N."""
+    out = []
+    for Al in DENSITY_AL:
+        dc = density_case(shape, C, Al)
+        for n in DENSITY_N:
+            rot, tr = density_poses(dc, n, seed=Al)
+            out.append((dc, rot, tr, pose_T(rot, tr), density_base(n, seed=Al)))
+    return tuple(out)
+
+
+QUARTER_TURNS = {"identity": ((1, 0, 0), (0, 1, 0), (0, 0, 1)), "x90": ((1, 0, 0), (0, 0, -1), (0, 1, 0)), "y90": ((0, 0, 1), (0, 1, 0), (-1, 0, 0)),
+                 "z90": ((0, -1, 0), (1, 0, 0), (0, 0, 1))}
+PLANTED_TR = ((0.0, 0.0, 0.0), (0.25, -0.5, 0.125), (-0.125, 0.25, 0.5), (0.5, 0.125, -0.5))
+PLANTED_KINDS = ("node", "lower", "upper", "neg_half", "far")      # and "<face>+" / "<face>-": one fp32 ulp up / down along the face's axis
+
+
+@functools.lru_cache(maxsize=None)
+def planted_density_case():
+    """(dc, T [4][12], labels) with T of EXACT doubles - the identity and the quarter turns about x, y, z (entries 0, +-1), translations that
+    are small binary fractions - on a grid whose origin and voxels are binary fractions too (voxels 0.5, 1, 2: the division is exact), so
+    every X and u is exact.  For every pose p the atoms x = R^T (Y - t) whose images Y are: nodes (corners of the grid among them), a
+    point on each of the six faces, and that atom moved by one fp32 ulp either way along the axis the face's normal comes from; a point
+    with u = -1/2 on each axis; and, once, atoms at 1e30 and 3e38.  labels [Al] = (pose, kind).  Every atom is seen by all four poses."""
+    shape, o, v = (3, 5, 4), np.array([-1.75, 2.0, -4.25]), np.array([0.5, 1.0, 2.0])      # (no face at 0: an ulp of 0 is a denormal)
+    n1 = np.array([shape[2], shape[1], shape[0]], np.float64) - 1
+    mid = o + 0.75 * v
+    atoms, labels, T = [], [], []
+    for p, (name, R) in enumerate(QUARTER_TURNS.items()):
+        R, t = np.array(R, np.float64), np.array(PLANTED_TR[p])
+        T.append(np.concatenate([R.reshape(-1), t]))
+        pre = lambda Y: R.T @ (np.asarray(Y, np.float64) - t)
+
+        def add(x, kind):
+            assert (f64(f32(x)) == x).all(), (name, kind, x)      # the atom is an fp32 number
+            atoms.append(f32(x))
+            labels.append((p, kind))
+        for node in ((0, 0, 0), (1, 1, 1), (2, 3, 1), (3, 0, 0), (0, 4, 0), (0, 0, 2), (3, 4, 2), (2, 3, 0)):
+            add(pre(o + np.array(node) * v), "node")
+        for k in range(3):
+            j = int(np.nonzero(R[k])[0][0])      # the atom coordinate that moves X_k
+            for kind, uk in (("lower", 0.0), ("upper", n1[k])):
+                Yp = mid.copy()
+                Yp[k] = o[k] + uk * v[k]
+                x = pre(Yp)
+                add(x, kind)
+                for sgn, far in (("+", np.inf), ("-", -np.inf)):
+                    xs = f32(x)
+                    xs[j] = np.nextafter(xs[j], f32(far))
+                    add(f64(xs), kind + sgn)
+            Yp = mid.copy()
+            Yp[k] = o[k] - 0.5 * v[k]
+            add(pre(Yp), "neg_half")
+    for far in ((1e30, 0.0, 0.0), (0.0, -3e38, 0.0), (0.0, 0.0, 3e38)):
+        add(f64(f32(far)), "far")
+    lig = np.asarray(atoms, f32)
+    w = np.random.default_rng(74).uniform(1.0, 8.0, len(lig)).astype(f32)
+    dc = density_case(shape, 2, len(lig), seed=5, origin=o, voxel=v, center=(0.0, 0.0, 0.0), lig=lig, w=w)
+    return dc, np.asarray(T), tuple(labels)
+
+
+def density_inside_exact(dc, T):
+    """The inside decision of every (pose, atom) in exact rational arithmetic: X = R (x - c) + c + t, 0 <= (X - o) / v < n - 1."""
+    geo, lig = dc["geo"], dc["lig4"]
+    F = lambda a: Fraction(float(a))
+    out = np.zeros((len(T), len(lig)), bool)
+    for p, tp in enumerate(T):
+        for a, x in enumerate(lig):
+            q = [F(x[k]) - F(geo[6 + k]) for k in range(3)]
+            ok = True
+            for k in range(3):
+                Xk = sum(q[j] * F(tp[3 * k + j]) for j in range(3)) + F(geo[6 + k]) + F(tp[9 + k])
+                uk = (Xk - F(geo[k])) / F(geo[3 + k])
+                ok = ok and 0 <= uk < F(geo[10 + k])
+            out[p, a] = ok
+    return out
+
+
+def minus_zero_density_case():
+    """(dc, T): u_x = -0.0.  The atom sits on the x = 0 face of a grid whose origin is 0 there, the pose shifts it by -2^-1000 and the voxel
+    is 2^100 wide along x: the quotient -2^-1100 is below half the smallest denormal and rounds to -0.0, which is >= 0: inside, cell 0,
+    fraction 0 (the IEEE operations are the definition; the exact quotient would be outside)."""
+    dc = density_case((2, 2, 2), 1, 1, seed=6, origin=(0.0, 0.0, 0.0), voxel=(2.0 ** 100, 1.0, 1.0), center=(0.0, 0.0, 0.0),
+                      lig=f32([[0.0, 0.25, 0.5]]), w=f32([3.0]))
+    T = np.concatenate([np.eye(3).reshape(-1), [-2.0 ** -1000, 0.0, 0.0]])[None]
+    return dc, T
+
+
+def ties_density_case():
+    """(half, rounded, T): quantisation ties.
+    half     a grid that is 2^-21 on every node, weights 1, 3, 5, -1, -5: (w val) 2^20 = w / 2 exactly; ties to even give 0, 2, 2, -0, -2.
+    rounded  ties that exist only once a product is rounded.  Channel 0 is -1, 1 on the nodes (x = 0, 1) of the row y = 0 and 0, 2 on those
+             of y = 1, the same in both z planes; the atoms sit at fx = 1/2, so the lerps along x give 0 and 1 exactly and val = fy =
+             fl(y / 3) (a voxel of 3 along y) with y = (k + 1/2) 2^-20, k = 2 .. 9, and w = 3: fl(3 fl(y / 3)) = y exactly, a tie, although
+             3 fl(y / 3) != y.  Lerps along y first round -1 + fy and 1 + fy at 2^-53: no tie is left, and half of them fall the other way."""
+    flat = np.full((2, 2, 2, 4), 2.0 ** -21, f32)
+    half = density_case((2, 2, 2), 1, 5, seed=7, origin=(0.0, 0.0, 0.0), voxel=(1.0, 1.0, 1.0), center=(0.0, 0.0, 0.0),
+                        lig=f32([[0.25, 0.5, 0.75], [0.5, 0.5, 0.5], [0.125, 0.25, 0.5], [0.75, 0.25, 0.5], [0.5, 0.75, 0.25]]),
+                        w=f32([1, 3, 5, -1, -5]), grid4=flat)
+    g = np.zeros((2, 2, 2, 4), f32)
+    g[:, 0, :, 0], g[:, 1, :, 0] = (-1.0, 1.0), (0.0, 2.0)
+    g[..., 1] = f32(2.0 ** -21)
+    lig = f32([[0.5, (k + 0.5) * 2.0 ** -20, 0.5] for k in range(2, 10)])
+    rounded = density_case((2, 2, 2), 1, len(lig), seed=8, origin=(0.0, 0.0, 0.0), voxel=(1.0, 3.0, 1.0), center=(0.0, 0.0, 0.0), lig=lig,
+                           w=np.full(len(lig), 3.0, f32), grid4=g)
+    T = np.concatenate([np.eye(3).reshape(-1), np.zeros(3)])[None]
+    return half, rounded, T
+
+
+def nonfinite_density_T(T0, T1):
+    """[38][12]: T0, then T0 with NaN, +inf, -inf in each of its twelve slots, then T1."""
+    out = np.tile(f64(T0), (38, 1))
+    for k in range(12):
+        for j, v in enumerate((np.nan, np.inf, -np.inf)):
+            out[1 + 3 * k + j, k] = v
+    out[37] = T1
+    return out
+
+
+def limit_density_case():
+    """The launcher's largest n: 65535 poses of one atom on a 2 x 2 x 2 grid, pure translations about its centre, a share of them
+    outside."""
+    dc = density_case((2, 2, 2), 3, 1, seed=9, lig=f32([[-2.25, 2.5, -4.0]]), w=f32([5.5]))
+    rng = np.random.default_rng(75)
+    T = np.tile(np.concatenate([np.eye(3).reshape(-1), np.zeros(3)]), (65535, 1))
+    T[:, 9:] = rng.uniform(-1.0, 1.0, (65535, 3)) * f64(dc["voxel"]) * 0.7
+    return dc, T
+
+
+def sum_limit_density_case():
+    """Values of 2^10 on every node and weights of +-2^7 across 130 atoms: terms of exactly +-2^37 (the largest check_density_grid and
+    check_density_atoms admit), every tenth atom's negative; channel 1 holds -2^10."""
+    g = np.full((2, 2, 2, 4), 1024.0, f32)
+    g[..., 1] = -1024.0
+    rng = np.random.default_rng(76)
+    lig = rng.uniform(1.0, 15.0, (130, 3)).astype(f32)
+    w = np.where(np.arange(130) % 10 == 3, -128.0, 128.0).astype(f32)
+    dc = density_case((2, 2, 2), 2, 130, seed=10, origin=(0.0, 0.0, 0.0), voxel=(16.0, 16.0, 16.0), threshold=1024.0, center=(8.0, 8.0, 8.0),
+                      lig=lig, w=w, grid4=g)
+    T = np.tile(np.concatenate([np.eye(3).reshape(-1), np.zeros(3)]), (2, 1))
+    T[1, 9:] = (0.5, -0.25, 0.125)
+    return dc, T

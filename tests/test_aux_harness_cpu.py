@@ -4,7 +4,9 @@ zero; the kernel's fp32 bin table restated in numpy decides every quarter-angstr
 construction separates the 64 bins by far more than the bound; the numpy fp32 restatement of k_pair_dist_sum stays under every bound on
 the GPU tests' own inputs and each of its nine seeded mutants is rejected by the comparison named for it; the references are the
 package's definitions; the restated arg-min and first-crossing rules agree with the definitions on the GPU tests' inputs and their
-mutants do not; the extended-precision IGSO(3) table agrees with mpmath."""
+mutants do not; the extended-precision IGSO(3) table agrees with mpmath; symmetry_ref is symmetry.evaluate, every decision of every
+symmetry pose the GPU file launches has a margin above the gate that could flip it, and each of the ten seeded mutants of the restated
+symmetry step is rejected by the comparison named for it."""
 import math
 
 import mpmath as mp
@@ -13,7 +15,7 @@ import pytest
 
 import aux_harness as ah
 import kernel_harness as kh
-from aux_harness import DG, RF, RS, Out, U, f32, f64
+from aux_harness import DG, RF, RS, SY, Out, U, f32, f64
 
 
 # ---- the shim ------------------------------------------------------------------------------------------------------------------------
@@ -449,3 +451,151 @@ def test_start_reference_is_the_definition():
     assert 0 < u0 < 1 and float(f32(u0)) == u0 and np.isfinite(ax0).all() and (dz < 1e-5).all()
     u1 = ah.start_draws64(3, 77)[0]
     assert u1 != u0
+
+
+# ---- k_symmetry: the reference is the definition, the shim's checks, the margins of every decision, the mutants ------------------------
+def all_sym_cases():
+    """(name, case) of every launch of the GPU file's symmetry tests."""
+    out = [(f"eval L {L} a {aa}", ah.sym_case(L, n, aa)) for L, n in ((1, 2), (21, 3), (22, 4), (85, 5), (86, 7), (300, 24)) for aa in (0, 1)]
+    out += [(f"apply L {L}", ah.sym_case(L, 3, aa)) for L, aa in ((1, 0), (21, 1), (22, 0), (85, 1), (86, 0), (300, 1))]
+    out += [(f"midpoints n {n}", ah.sym_midpoint_case(n)[0]) for n in sorted(ah.SYM_MIDPOINTS)]
+    out.append(("batch", ah.sym_case(85, 5, 1)))
+    return out
+
+
+def test_symmetry_ref_is_the_definition():
+    """symmetry_ref returns symmetry.evaluate's own values (on the fp32 coordinates and fp32 parameters); the restatement without a mutant
+    agrees with it to float64 rounding on every pose, move included."""
+    c = ah.sym_case(22, 4, 0)
+    p = SY.SymmetryParams(**c["params"])
+    for v in c["params"].values():
+        assert float(f32(v)) == v
+    for name, c in all_sym_cases():
+        for b in range(c["B"]):
+            ref = ah.symmetry_ref(c, b)
+            with np.errstate(all="ignore"):
+                ev = SY.evaluate(c["rec_pos"].reshape(-1, 3, 3), c["lig"][b].reshape(-1, 3, 3), c["n"], SY.SymmetryParams(**c["params"]),
+                                 "all_atoms" if c["all_atoms"] else "ca")
+            for k in ("m", "theta", "screw", "fit_rmsd", "sym_rmsd"):
+                assert ref[k] == ev[k] or (np.isnan(ref[k]) and np.isnan(ev[k])), (name, b, k)
+            assert np.array_equal(ref["step"], ev["step"], equal_nan=True) and np.array_equal(ref["axis_point"], ev["axis_point"], equal_nan=True)
+            if not np.isfinite(c["lig"][b]).all():
+                continue
+            rot0, tr0 = np.array([0.3, -0.2, 0.1]), np.array([1.0, -2.0, 0.5])
+            rs = ah.symmetry_restated(c, b, rot0=rot0, tr0=tr0)
+            assert rs["order_m"] == ref["m"] and np.abs(rs["step"] - ref["step"]).max() <= 1e-12, (name, b)
+            pose, tu, ru, *_ = ah.apply_ref(c, b, ref["step"], rot0, tr0)
+            assert np.abs(rs["pose"] - pose).max() <= 1e-9 and np.abs(rs["rot_update"] - ru).max() <= 1e-12 and np.abs(rs["tr_update"] - tu).max() <= 1e-12
+    last = ah.symmetry_ref(ah.sym_case(86, 3, 0), 2, last=True)
+    assert np.linalg.norm(last["step"][:3]) > 10.0 and np.linalg.norm(last["step"][3:]) > 0.3      # the snapped step is not clipped
+
+
+def test_symmetry_decisions_have_margins():
+    """Every decision of every pose the GPU file launches is decided: the gap between the best and the second-best generator exceeds 1e-9
+    rad (the theta gate is 1e-11), both clip margins exceed the bound of the step they decide (gain x the gate of screw / theta:
+    1e-8 A, 1e-11 rad), and |v| is either below 1e-12 or above 1e-6 (NO_AXIS is 1e-9).  No pose is excused; the only planted boundaries
+    are the exactly symmetric pose (delta = 0: a step of zero is far from the clip) and the midpoints, 1e-3 rad off."""
+    n_poses = 0
+    for name, c in all_sym_cases():
+        p = c["params"]
+        for b in range(c["B"]):
+            if not np.isfinite(c["lig"][b]).all():
+                continue
+            ref = ah.symmetry_ref(c, b)
+            assert ref["vn"] < 1e-12 or ref["vn"] > 1e-6, (name, b, ref["vn"])
+            assert (ref["m"] == 0) == (ref["vn"] < 1e-12)
+            assert ref["m_gap"] > 1e-9, (name, b, ref["m_gap"])
+            assert ref["clip_margin"][0] > 1e3 * p["gain_tr"] * 1e-8 and ref["clip_margin"][1] > 1e3 * p["gain_rot"] * 1e-11, (name, b, ref["clip_margin"])
+            n_poses += 1
+    assert n_poses > 150
+    for n in ah.SYM_MIDPOINTS:
+        c, want = ah.sym_midpoint_case(n)
+        got = [ah.symmetry_ref(c, b) for b in range(c["B"])]
+        assert [g["m"] for g in got] == list(want)
+        assert all(5e-4 < g["m_gap"] < 4e-3 for g in got[:-2]), [g["m_gap"] for g in got]      # 2e-3 but for the fp32 rounding of the coordinates
+    for L in (22, 86):      # the zero-step poses
+        import symmetry_fixtures as SF
+        y = ah.sym_chain(L, seed=3)
+        c = ah.sym_case_of(y, np.stack([SF.exact_translation(y), y.copy()]), 3, 0)
+        assert not np.array_equal(c["lig"][0], c["lig"][1])
+        for b in (0, 1):
+            ref = ah.symmetry_ref(c, b)
+            assert ref["vn"] < 1e-12 and ref["m"] == 0 and ref["theta"] == 0.0 and not ref["step"].any() and np.isnan(ref["screw"])
+
+
+SYM_MUTANT_INPUT = {"larger_m": ("midpoints n 24", None), "no_gcd": ("midpoints n 8", None), "no_w_flip": ("batch", None),
+                    "clip_under_snap": ("apply L 86", "last"), "gains_swapped": ("apply L 86", None), "centre_all_atoms": ("apply L 86", None),
+                    "screw_sign": ("apply L 86", None), "compose_order": ("apply L 86", None), "last_off_by_one": ("apply L 86", "last"),
+                    "last_from_num_steps": ("apply L 86", "ctl")}
+
+
+@pytest.mark.parametrize("mutant", sorted(ah.SYM_MUTANTS))
+def test_symmetry_mutants_are_rejected(mutant):
+    """Each seeded mutant of the restatement fails the comparison named for it in SYM_MUTANTS, with the GPU file's own gate and on its
+    own inputs: order_m exact; the step beyond 2 fp32 ulp; the pose and rot_update beyond apply_ref's bounds."""
+    name, mode = SYM_MUTANT_INPUT[mutant]
+    c = dict(all_sym_cases())[name]
+    rot0, tr0 = np.array([0.3, -0.2, 0.1]), np.array([1.0, -2.0, 0.5])
+    # test_symmetry_last_step's arguments: idx 3 of 4 steps; with the control words the by-value num_steps says the opposite
+    kw = {None: {}, "last": dict(idx=3, num_steps=4), "ctl": dict(idx=3, num_steps=5, ctl=(4, 0, 0, 4))}[mode]
+    rejected = 0
+    for b in range(c["B"]):
+        if not np.isfinite(c["lig"][b]).all():
+            continue
+        ref = ah.symmetry_ref(c, b, last=mode is not None)
+        good, bad = ah.symmetry_restated(c, b, rot0=rot0, tr0=tr0, **kw), ah.symmetry_restated(c, b, mutant, rot0=rot0, tr0=tr0, **kw)
+        pose, tu, ru, dpose, dtu, dru = ah.apply_ref(c, b, ref["step"], rot0, tr0)
+        ulp = lambda s: np.repeat([np.spacing(f32(np.abs(s[:3]).max())), np.spacing(f32(np.abs(s[3:]).max()))], 3).astype(np.float64)
+
+        def verdict(r):
+            return {"order_m": r["order_m"] != ref["m"], "step": bool((np.abs(r["step"] - ref["step"]) > 2 * ulp(ref["step"])).any()),
+                    "pose": bool((np.abs(r["pose"] - pose) > dpose).any()), "rot_update": bool((np.abs(r["rot_update"] - ru) > dru).any())}
+        assert not any(verdict(good).values()), (mutant, b, verdict(good))
+        rejected += verdict(bad)[ah.SYM_MUTANTS[mutant]]
+    assert rejected >= 1, mutant
+
+
+def test_shim_checks_of_the_symmetry_launch(shim):
+    """One malformed record per condition, refused before anything is uploaded."""
+    h = ah.Harness(shim)
+    c = ah.sym_case(22, 3, 0)
+    B, L = c["B"], 22
+    good = lambda **k: dict(dict(rec_pos=c["rec_pos"], lig=Out(f32, init=c["lig"]), sym_out=Out(np.float64, B * ah.SYM_OUT), step_out=Out(f32, B * 6)), **k)
+    sc = dict(B=B, R=L, L=L, all_atoms=0, n=3, apply=0, prep_next=0, snap_last=1, **{k: v for k, v in c["params"].items() if k != "snap_last"})
+    assert h.check_only("symmetry", good(), **sc) == ah.HIP_SUCCESS
+    assert h.check_only("symmetry", good(lig=c["lig"]), **sc) == ah.HIP_SUCCESS
+    for change in (dict(R=21), dict(R=23), dict(R=0, L=0), dict(n=1), dict(n=25), dict(n=0), dict(B=0), dict(apply=2), dict(snap_last=2), dict(apply=1), dict(prep_next=1)):
+        assert refused(h, "symmetry", good(), **dict(sc, **change)), change
+    for bufs in (good(rec_pos=c["rec_pos"][:-1]), good(lig=Out(f32, init=c["lig"][:-1])), good(lig=Out(f32, B * L * 9)), good(sym_out=Out(np.float64, B * ah.SYM_OUT - 1)),
+                 good(step_out=Out(f32, B * 6 - 1)), good(step_out=np.zeros(B * 6, f32)), good(tr_upd=Out(f32, init=np.zeros(B * 3, f32))),
+                 good(ctl=np.array([1, 0, 0, 4], np.uint32))):
+        assert refused(h, "symmetry", bufs, **sc)
+    t = np.array([0.5, 0.25], f32)
+    four = lambda a: np.array([a, 0, 0, 2], np.uint32)
+    assert h.check_only("symmetry", good(t_dev=t), step=1, n_t=2, **sc) == ah.HIP_SUCCESS
+    assert h.check_only("symmetry", good(t_dev=t, ctl=four(2)), step=9, n_t=2, **sc) == ah.HIP_SUCCESS
+    assert refused(h, "symmetry", good(t_dev=t), step=2, n_t=2, **sc)                                         # step outside t_dev
+    assert refused(h, "symmetry", good(t_dev=t, ctl=four(0)), step=0, n_t=2, **sc)                            # ctl[0] - 1 wraps
+    assert refused(h, "symmetry", good(t_dev=t, ctl=four(3)), step=0, n_t=2, **sc)
+    assert refused(h, "symmetry", good(t_dev=t, ctl=four(1)[:3]), step=0, n_t=2, **sc)                        # 12 bytes: k_restraint's block, not this kernel's
+    assert h.check_only("restraint", dict(rec_pos=c["rec_pos"]), B=1) == ah.HIP_INVALID_VALUE
+    ap = good(tr_upd=Out(f32, init=np.zeros(B * 3, f32)), rot_upd=Out(f32, init=np.zeros(B * 3, f32)))
+    assert h.check_only("symmetry", ap, **dict(sc, apply=1)) == ah.HIP_SUCCESS
+    assert refused(h, "symmetry", dict(ap, lig=c["lig"]), **dict(sc, apply=1))                                # apply needs the pose in / out
+    N = 2 * L
+    prep = dict(prep_pos=Out(f32, B * N * 4), prep_ca4=Out(f32, B * N * 4), prep_cb4=Out(f32, B * N * 4))
+    assert h.check_only("symmetry", good(**prep), **dict(sc, prep_next=1)) == ah.HIP_SUCCESS
+    assert refused(h, "symmetry", good(**dict(prep, prep_ca4=Out(f32, B * N * 4 - 1))), **dict(sc, prep_next=1))
+    assert refused(h, "symmetry", good(**prep), **sc)                                                         # prep outputs without prep_next
+
+
+def test_every_declared_launcher_is_called_by_a_shim():
+    """Every launch_* that dfm_internal.h declares is called in the source of some shim under tests/kernels/: no launcher is reached
+    through whole public calls only."""
+    import glob
+    import os
+    import re
+    names = set(re.findall(r"\b(launch_\w+)\s*\(", open(os.path.join(ah.LIBDIR, "csrc", "dfm_internal.h")).read()))
+    src = "".join(open(f).read() for f in glob.glob(os.path.join(ah.ROOT, "tests", "kernels", "*_harness.hip")))
+    assert len(names) >= 58 and {"launch_symmetry", "launch_density", "launch_density_pose"} <= names
+    assert not sorted(n for n in names if not re.search(r"\b" + n + r"\s*\(", src))

@@ -1,5 +1,5 @@
-"""The distogram reduction (k_pair_dist_sum + k_dist_finish + k_dist_mean), the restraint step (k_restraint) and the refinement start
-(k_igso3_cdf, k_start_pose), launch by launch between guard bands against float64 computed from the same inputs, through the host shim of
+"""The distogram reduction (k_pair_dist_sum + k_dist_finish + k_dist_mean), the restraint step (k_restraint), the symmetry step
+(k_symmetry) and the refinement start (k_igso3_cdf, k_start_pose), launch by launch between guard bands against float64 computed from the same inputs, through the host shim of
 tests/aux_harness.py.  Every comparison is with the float64 definition, never with another kernel or a second run.  u = 2^-24, e = 2^-53.
 
 k_pair_dist_sum.
@@ -32,6 +32,12 @@ k_restraint (aux_harness.restraint_ref).  d^2, d, v = d - u are the definition's
   summation order on the torque + 6 e for k and the clip + ONE fp32 rounding.  The clip decision is exact wherever | |k F| - max | exceeds
   the bound of the norm - on every case here (CPU file).  Arg-min ties: one group per launch whose tied pairs pull in different
   directions.  NaN: restraints.evaluate (np.argmin) is the specification - a NaN distance wins the arg-min wherever it stands.
+k_symmetry (aux_harness.symmetry_ref = symmetry.evaluate on the kernel's fp32 coordinates and parameters).  No new tolerance: the
+  diagnostics carry symmetry_fixtures.check_eval's gates (theta 1e-11 rad, axis 1e-10, the lengths 1e-8 A, the fp32 step 2 ulp of the step
+  formed from the device's own float64 outputs), order_m is exact, the move carries apply_ref's bounds as k_restraint's does, the last step
+  the sampler tests' closure gates (1e-5 rad, 1e-3 A), and everything else - prep_next against launch_prep_pose, gating, the control words
+  against the by-value arguments, batch invariance, the zero step, non-finite poses - is bitwise.  The CPU file asserts that every decision
+  of every pose used here (the choice of m, both clips, |v| against NO_AXIS) has a margin above the gate that could flip it.
 k_igso3_cdf (aux_harness.igso3_ref): refine.igso3_cdf's formula in numpy.longdouble from the same float64 inputs; the gate counts the
   kernel's roundings term by term (c e sum |terms| with the argument's e |omega (l + 1/2)|; 1000 sequential additions; the 22-addition
   scan).  Its largest entry is 1.5e-13 at sigma = 1.5 and 1.9e-11 at sigma = 0.1 (the argument's rounding, up to 3141 x 2^-53 per term, in
@@ -50,6 +56,8 @@ import pytest
 
 import aux_harness as ah
 import heads_harness as hh
+import symmetry_fixtures as SF
+from aux_harness import SY
 from aux_harness import Out, U, bits, f32, f64
 
 pytestmark = pytest.mark.gpu
@@ -483,3 +491,234 @@ def test_start_pose_native_draws(h):
     assert np.isnan(zr["rot_upd"][2]).all() and np.isnan(zr["lig"][2]).all()
     keep = [0, 1, 3, 4]
     assert np.isfinite(zr["rot_upd"][keep]).all() and np.isfinite(zr["lig"][keep]).all() and np.isfinite(zr["tr_upd"]).all()
+
+
+# ---- k_symmetry ----------------------------------------------------------------------------------------------------------------------
+SYM_GATES = dict(theta=1e-11, axis=1e-10, screw=1e-8, axis_point=1e-8, fit_rmsd=1e-8, sym_rmsd=1e-8)      # symmetry_fixtures.check_eval's own
+SYM_ORDER_OF = {1: 2, 21: 3, 22: 4, 85: 5, 86: 7, 300: 24}
+
+
+def sym_check_eval(name, c, ev, key="k_symmetry eval", sl=None):
+    """symmetry_fixtures.check_eval, unchanged gates, on the evaluation outputs of a launch; records worst / gate of each."""
+    lig = c["lig"] if sl is None else c["lig"][sl]
+    worst, clipped = SF.check_eval(ev, c["rec_pos"].reshape(-1, 3, 3), lig.reshape(len(lig), -1, 3, 3), c["n"], ah.sym_p32(c),
+                                   "all_atoms" if c["all_atoms"] else "ca")
+    print(name, {k: f"{v:.3g}" for k, v in worst.items()})
+    for k, gate in SYM_GATES.items():
+        record(f"{key} {k}", worst[k] / gate)
+    record(f"{key} step (gate 2 ulp)", worst["step_ulp"] / 2.0)
+    return clipped
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and bool((bits(a) == bits(b)).all())
+
+
+def prep_of(heads, c, lig):
+    B, L = len(lig), c["L"]
+    N = 2 * L
+    pp = heads.run("prep_pose", dict(rec_pos=c["rec_pos"], lig=np.ascontiguousarray(lig, f32), prep_pos=Out(f32, B * N * 4), prep_ca4=Out(f32, B * N * 4),
+                                     prep_cb4=Out(f32, B * N * 4)), B=B, R=L, L=L, all_atoms=c["all_atoms"])
+    assert pp["err"] == hh.HIP_SUCCESS
+    return pp
+
+
+def start_updates(B, seed):
+    rng = np.random.default_rng([41, seed])
+    return (rng.standard_normal((B, 3)) * 0.3).astype(f32), (rng.standard_normal((B, 3)) * 3).astype(f32)
+
+
+@pytest.mark.parametrize("all_atoms", [0, 1])
+@pytest.mark.parametrize("L", ah.SYM_SIZES)
+def test_symmetry_eval(h, L, all_atoms):
+    """Evaluation mode against symmetry.evaluate on the special poses of symmetry_fixtures.poses, at 3, 63, 66, 255, 258 and 900 atoms:
+    order_m exact, the diagnostics within check_eval's gates, the fp32 step within 2 ulp of the step formed from the device's own float64
+    outputs; the pose is an input and keeps its bits; step_out alone, out alone and both together give the same bits."""
+    c = ah.sym_case(L, SYM_ORDER_OF[L], all_atoms)
+    r = h.symmetry(c)
+    assert same_bits(r["lig"], c["lig"].reshape(c["B"], -1)), "the evaluation mode wrote the pose"
+    clipped = sym_check_eval(f"k_symmetry eval L {L} all_atoms {all_atoms}", c, r["ev"])
+    assert clipped[2][0] and not clipped[3].any() and r["ev"]["order_m"][4] == 0 and r["ev"]["order_m"][5] == 0
+    only_out, only_step = h.symmetry(c, step_out=False), h.symmetry(c, out=False)
+    assert same_bits(only_out["sym_out"], r["sym_out"]) and same_bits(only_step["step_out"], r["step_out"])
+    assert not ah.is_sentinel(r["step_out"]).any() and not ah.is_sentinel(r["sym_out"][:, :11].view(np.uint32)).any()
+
+
+@pytest.mark.parametrize("n", sorted(ah.SYM_MIDPOINTS))
+def test_symmetry_nearest_generator(h, n):
+    """Poses 1e-3 rad either side of the midpoint between neighbouring generators (n = 5: m 1|2, 8: 1|3, 12: 1|5, 24: 1|5, 5|7, 7|11), one
+    below the first generator and one above the last: order_m is exactly the expected m, and everything else is within the gates."""
+    c, want = ah.sym_midpoint_case(n)
+    r = h.symmetry(c)
+    assert r["ev"]["order_m"].tolist() == list(want)
+    sym_check_eval(f"k_symmetry midpoints n {n}", c, r["ev"], key="k_symmetry midpoints")
+
+
+@pytest.mark.parametrize("L,all_atoms", [(1, 0), (21, 1), (22, 0), (85, 1), (86, 0), (300, 1)])
+def test_symmetry_apply_and_prep(h, heads, L, all_atoms):
+    """Apply mode from a non-zero rot_update / tr_update: the moved pose, tr_update and the composed rot_update against apply_ref of the
+    DEFINITION's step within apply_ref's bounds (the restraint and heads tests' update bound); `out` as in evaluation mode; the NaN pose
+    gets a NaN pose and NaN updates, the pose without an axis keeps its bits; prep_next writes the bits launch_prep_pose writes for the
+    moved pose and leaves no sentinel."""
+    c = ah.sym_case(L, 3, all_atoms)
+    B = c["B"]
+    rot0, tr0 = start_updates(B, L)
+    r = h.symmetry(c, apply=1, prep=True, rot0=rot0, tr0=tr0)
+    sym_check_eval(f"k_symmetry apply L {L}", c, r["ev"])
+    moved = 0
+    for b in range(B):
+        ref = ah.symmetry_ref(c, b)
+        if b == 5:
+            assert np.isnan(r["lig"][b]).all() and np.isnan(r["tr_upd"][b]).all() and np.isnan(r["rot_upd"][b]).all()
+            continue
+        pose, tur, rur, dpose, dtu, dru = ah.apply_ref(c, b, ref["step"], rot0[b], tr0[b])
+        moved += bool(np.any(ref["step"] != 0))
+        within(f"k_symmetry pose [{b}]", r["lig"][b], pose, dpose, "k_symmetry apply pose")
+        within(f"k_symmetry tr_update [{b}]", r["tr_upd"][b], tur, dtu, "k_symmetry apply tr_update")
+        within(f"k_symmetry rot_update [{b}]", r["rot_upd"][b], rur, dru, "k_symmetry apply rot_update")
+    assert moved >= 5
+    assert same_bits(r["lig"][4], c["lig"][4].reshape(-1)) and same_bits(r["tr_upd"][4], tr0[4]) and same_bits(r["rot_upd"][4], rot0[4])
+    pp = prep_of(heads, c, r["lig"])
+    for k in ("prep_pos", "prep_ca4", "prep_cb4"):
+        assert not ah.is_sentinel(r[k]).any(), k
+        assert ((bits(r[k]) == bits(pp[k])) | (np.isnan(r[k]) & np.isnan(pp[k]))).all(), k
+        fin = np.isfinite(pp[k])
+        assert fin.mean() > 0.8 and (bits(r[k])[fin] == bits(pp[k])[fin]).all(), k
+
+
+@pytest.mark.parametrize("L,all_atoms", [(22, 0), (86, 1)])
+def test_symmetry_zero_step(h, L, all_atoms):
+    """A translation that fp32 holds exactly, and a pose bitwise equal to the receptor: no axis.  m = 0, theta = 0, a zero step, NaN where
+    the definition says NaN; under apply the pose and both updates keep their bits."""
+    y = ah.sym_chain(L, seed=3)
+    c = ah.sym_case_of(y, np.stack([SF.exact_translation(y), y.copy()]), 3, all_atoms)
+    assert not same_bits(c["lig"][0], c["lig"][1])
+    rot0, tr0 = start_updates(2, 7)
+    r = h.symmetry(c, apply=1, rot0=rot0, tr0=tr0)
+    sym_check_eval(f"k_symmetry zero step L {L}", c, r["ev"], key="k_symmetry zero step")
+    ev = r["ev"]
+    assert (ev["order_m"] == 0).all() and (ev["theta"] == 0).all() and (bits(r["step_out"]) == 0).all()
+    assert np.isnan(ev["screw"]).all() and np.isnan(ev["axis"]).all() and np.isnan(ev["axis_point"]).all() and np.isnan(ev["sym_rmsd"]).all()
+    assert (ev["fit_rmsd"] <= 1e-12).all()
+    assert same_bits(r["lig"], c["lig"].reshape(2, -1)) and same_bits(r["tr_upd"], tr0) and same_bits(r["rot_upd"], rot0)
+
+
+@pytest.mark.parametrize("via", ["step", "ctl"])
+def test_symmetry_gating(h, heads, via):
+    """t_dev with the by-value `step`, and with the control words (index ctl[0] - 1; the by-value step then points at a NaN time): times
+    just above, equal to and below t_start.  Gated off: the pose, the updates, `out` and `step_out` keep their bits or sentinels and prep_*
+    equals launch_prep_pose of the UNMOVED pose.  Gated on: bitwise the launch without t_dev."""
+    c = dict(ah.sym_case(86, 3, 0))
+    c["params"] = dict(c["params"], t_start=float(f32(0.4)))
+    B = c["B"]
+    t = np.array([np.nan, np.nextafter(f32(0.4), f32(1)), f32(0.4), f32(0.1), np.nan], f32)
+    rot0, tr0 = start_updates(B, 11)
+    free = h.symmetry(c, apply=1, prep=True, rot0=rot0, tr0=tr0)
+    assert not same_bits(free["lig"], c["lig"].reshape(B, -1))
+    pp = prep_of(heads, c, c["lig"])
+    keys = ("lig", "tr_upd", "rot_upd", "sym_out", "step_out", "prep_pos", "prep_ca4", "prep_cb4")
+    for idx, runs in ((1, False), (2, True), (3, True)):
+        kw = dict(t_dev=t, step=idx, num_steps=99) if via == "step" else dict(t_dev=t, step=4 * (idx % 2), num_steps=idx + 1,
+                                                                              ctl=np.array([idx + 1, 7, 9, 99], np.uint32))
+        r = h.symmetry(c, apply=1, prep=True, rot0=rot0, tr0=tr0, **kw)
+        if runs:
+            for k in keys:
+                assert same_bits(r[k], free[k]), (via, idx, k)
+        else:
+            assert same_bits(r["lig"], c["lig"].reshape(B, -1)) and same_bits(r["tr_upd"], tr0) and same_bits(r["rot_upd"], rot0)
+            assert ah.is_sentinel(r["step_out"]).all() and ah.is_sentinel(r["sym_out"].view(np.uint32)).all(), "a gated-off launch wrote its outputs"
+            for k in ("prep_pos", "prep_ca4", "prep_cb4"):
+                assert ((bits(r[k]) == bits(pp[k])) | (np.isnan(r[k]) & np.isnan(pp[k]))).all(), k
+
+
+@pytest.mark.parametrize("via", ["step", "ctl"])
+def test_symmetry_last_step(h, via):
+    """snap_last = 1 at idx + 1 == num_steps: step_out is the unclipped full projection (within 2 ulp of device_step with gains 1 and no
+    clip) on a case whose ordinary step clips, and the moved pose, evaluated by the float64 definition, has |theta - theta*| <= 1e-5 and
+    closure <= 1e-3 A (the sampler tests' gates).  One step earlier, and with snap_last = 0, the step follows the gains: bitwise the launch
+    without t_dev.  With the control words, the by-value num_steps contradicts ctl[3] in both directions."""
+    c = ah.sym_case(86, 3, 0)
+    B, n = c["B"], c["n"]
+    y = c["rec_pos"].reshape(-1, 3, 3)
+    t = np.full(6, 0.5, f32)
+    idx, S = 3, 4
+    rot0, tr0 = start_updates(B, 13)
+
+    def run(snap, last):
+        cc = dict(c, params=dict(c["params"], snap_last=snap))
+        if via == "step":
+            kw = dict(t_dev=t, step=idx, num_steps=S if last else S + 1)
+        else:      # the by-value arguments say the opposite of the control words
+            kw = dict(t_dev=t, step=(0 if last else S - 1), num_steps=(S + 1 if last else S), ctl=np.array([idx + 1, 0, 0, S if last else S + 1], np.uint32))
+        return h.symmetry(cc, apply=1, rot0=rot0, tr0=tr0, **kw)
+    plain = h.symmetry(c, apply=1, rot0=rot0, tr0=tr0)
+    assert ah.symmetry_ref(c, 2)["clipped"].all(), "the case must clip without snap"
+    for snap, last in ((1, False), (0, True), (0, False)):
+        r = run(snap, last)
+        for k in ("lig", "tr_upd", "rot_upd", "sym_out", "step_out"):
+            assert same_bits(r[k], plain[k]), (via, snap, last, k)
+    r = run(1, True)
+    assert same_bits(r["sym_out"], plain["sym_out"])
+    full = SY.SymmetryParams(gain_rot=1.0, gain_tr=1.0, max_rot=1e30, max_tr=1e30, snap_last=1)
+    worst = 0.0
+    for b in range(B):
+        if b == 5:
+            assert np.isnan(r["step_out"][b]).all()
+            continue
+        want = SF.device_step(r["ev"], b, n, full)
+        for hh_ in (0, 1):
+            w3 = want[hh_ * 3:hh_ * 3 + 3]
+            ulp = SF.ulp32(np.abs(w3).max()) if np.abs(w3).max() > 0 else 2.0 ** -149
+            dev = float(np.abs(f64(r["step_out"][b, hh_ * 3:hh_ * 3 + 3]) - w3).max())
+            worst = max(worst, dev / ulp)
+            assert dev <= 2 * ulp, (b, hh_, dev, ulp)
+        if b == 4:
+            continue
+        closure, dtheta, screw = SF.closure(y, r["lig"][b].reshape(-1, 3, 3), n)
+        print(f"k_symmetry last step [{b}]: closure {closure:.3g} A, |theta - theta*| {dtheta:.3g}, screw {screw:.3g}")
+        record("k_symmetry last step closure (gate 1e-3 A)", closure / 1e-3)
+        record("k_symmetry last step theta (gate 1e-5 rad)", dtheta / 1e-5)
+        assert dtheta <= 1e-5 and closure <= 1e-3, (b, dtheta, closure)
+    record("k_symmetry last step step_out (gate 2 ulp)", worst / 2.0)
+    assert np.linalg.norm(r["step_out"][2, :3]) > c["params"]["max_tr"] and np.linalg.norm(r["step_out"][2, 3:]) > c["params"]["max_rot"]
+
+
+def test_symmetry_batch_invariance(h, heads):
+    """Trajectory b of B = 5 has the bits of the same pose alone: pose, updates, out, step_out, prep_*."""
+    c = ah.sym_case(85, 5, 1)
+    rot0, tr0 = start_updates(5, 17)
+    r = h.symmetry(c, apply=1, prep=True, rot0=rot0, tr0=tr0, sl=slice(0, 5))
+    N = 2 * c["L"]
+    for b in (0, 2, 3, 4):
+        one = h.symmetry(c, apply=1, prep=True, rot0=rot0[b:b + 1], tr0=tr0[b:b + 1], sl=slice(b, b + 1))
+        for k in ("lig", "tr_upd", "rot_upd", "sym_out", "step_out"):
+            assert same_bits(one[k][0], r[k][b]), (b, k)
+        for k in ("prep_pos", "prep_ca4", "prep_cb4"):
+            assert same_bits(one[k], r[k].reshape(5, N * 4)[b]), (b, k)
+
+
+@pytest.mark.parametrize("where,value", [("lig", np.nan), ("lig", np.inf), ("rec", np.nan), ("rec", -np.inf)])
+def test_symmetry_nonfinite(h, where, value):
+    """A non-finite coordinate in one ligand pose: that trajectory gets NaN diagnostics, m = 0 and a NaN step and, under apply, a NaN pose
+    and NaN updates, while its finite neighbours are bitwise what they are without it.  In the receptor: every trajectory."""
+    base = ah.sym_case(22, 3, 0)
+    lig = base["lig"][[0, 2, 3, 6, 7]].copy()
+    rec = base["rec_pos"].copy()
+    rot0, tr0 = start_updates(5, 19)
+    clean = h.symmetry(ah.sym_case_of(rec.reshape(-1, 3, 3), lig, 3, 0), apply=1, rot0=rot0, tr0=tr0)
+    if where == "lig":
+        lig[2, 13, 4] = value
+        hit = [2]
+    else:
+        rec[7, 2] = value
+        hit = [0, 1, 2, 3, 4]
+    r = h.symmetry(ah.sym_case_of(rec.reshape(-1, 3, 3), lig, 3, 0), apply=1, rot0=rot0, tr0=tr0)
+    for b in range(5):
+        if b in hit:
+            assert np.isnan(r["sym_out"][b, :10]).all() and r["sym_out"][b, 10] == 0 and np.isnan(r["step_out"][b]).all(), b
+            assert np.isnan(r["lig"][b]).all() and np.isnan(r["tr_upd"][b]).all() and np.isnan(r["rot_upd"][b]).all(), b
+        else:
+            for k in ("lig", "tr_upd", "rot_upd", "sym_out", "step_out"):
+                assert same_bits(r[k][b], clean[k][b]), (b, k)
+    ev = ah.symmetry_ref(ah.sym_case_of(rec.reshape(-1, 3, 3), lig, 3, 0), hit[0])
+    assert ev["m"] == 0 and np.isnan(ev["step"]).all() and np.isnan(ev["theta"])

@@ -3,7 +3,9 @@ walk_front, walk_rows): sterics, buried surface, interface energy, residue conta
 tests/kernels/pose_harness.hip on small host arrays with guard bands around every device block, against the float64 restatements of
 tests/pose_harness.py by brute force over all P x Al x Ar pairs (tests/test_pose_harness_cpu.py shows that the numpy frame is the
 host's, that the restated walk finds exactly the brute force's pairs and that the comparisons used here reject its seeded mutants),
-and the same poses through the public creators and calls.
+and the same poses through the public creators and calls; and the density fit's two launchers (k_density_pose with the other six pose
+kernels, k_density - a gather from a grid, no walk - alone on T of exact doubles, on a prefilled tot and a marked atom_q, against
+pose_harness.density_ref, integer for integer).
 
 What is exact and what carries a gate (pose_harness.py states each):
   exact (bitwise)   every count, per-atom count, bitmap, total, degree and exit counter; the translation entries of T; rot = 0 gives the
@@ -63,8 +65,8 @@ def model(blob):
 # ---- the pose kernels ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [1, 64, 65])
 def test_pose_kernels(h, n):
-    """All six launch_*_pose on every finite rotation of pose_harness.pose_rotations: translation exact, rotation within the gate, rot = 0
-    the identity, the totals zeroed as each header comment promises, nothing past n written, the six T bitwise the same."""
+    """All seven launch_*_pose on every finite rotation of pose_harness.pose_rotations: translation exact, rotation within the gate, rot = 0
+    the identity, the totals zeroed as each header comment promises, nothing past n written, the seven T bitwise the same."""
     rot, tr = ph.pose_inputs(n)
     first = None
     for op in ph.POSE_OPS:
@@ -434,3 +436,114 @@ def test_rescon_chain_and_public_call(h, model):
     assert np.array_equal(api["ic"], fin["tot"][:, :6]) and np.array_equal(api["n_pairs"], fin["tot"][:, 6])
     assert np.array_equal(api["n_rec_res"], fin["tot"][:, 7]) and np.array_equal(api["n_lig_res"], fin["tot"][:, 8])
     assert np.array_equal(api["rec_degree"], fin["rec_degree"]) and np.array_equal(api["lig_degree"], fin["lig_degree"])
+
+
+# ---- density fit: launch_density alone (the public call always zeroes tot through k_density_pose and builds T from fp32 rot / tr) -----------------
+def density_exact(h, dc, T, base=None, atom_q=True, name="k_density"):
+    """One launch_density against density_ref, integer for integer: sum_q, n_inside, n_above, atom_q, nothing written past n or [n][Al]."""
+    P = len(T)
+    base = ph.density_base(P) if base is None else base
+    out = h.density(dc, T, atom_q=atom_q, base=base)
+    ref = ph.density_ref(dc["grid4"], dc["geo"], dc["lig4"], T, dc["C"], base=base)
+    cmp = ph.density_compare(out, ref, P, dc["Al"], base=base, atom_q=atom_q)
+    print(name, "Al", dc["Al"], "n", P, cmp)
+    assert not any(cmp.values()), (name, dc["dims"], dc["C"], dc["Al"], P, cmp)
+    tally(name, P * dc["Al"])
+    return out, ref
+
+
+@pytest.mark.parametrize("C", [1, 2, 3, 4])
+@pytest.mark.parametrize("shape", ph.DENSITY_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_density_exact(h, shape, C):
+    """tot and atom_q against density_ref on T = the float64 restatement of pose_transform: grids 2 x 2 x 2 and [3, 5, 4] with anisotropic
+    voxels and a negative origin, Al = 1, 63, 64, 65, 130, n = 1, 2, 5.  tot starts as a base of large values of both signs and comes back
+    as base + sum on sum_q, n_inside, n_above; the slots of the channels at or above C keep the base although the grid's float4 holds
+    non-zero values there; two more poses of tot and of atom_q behind the launch's keep base and marker; every entry of atom_q [n][Al] is
+    overwritten (the reference has no marker); without atom_q the same totals."""
+    for dc, rot, tr, T, base in ph.density_launches(shape, C):
+        assert dc["grid4"][..., C:].all() or C == 4
+        out, ref = density_exact(h, dc, T, base)
+        bare, _ = density_exact(h, dc, T, base, atom_q=False)
+        assert bare["tot"].tobytes() == out["tot"].tobytes()
+        assert (out["tot"][:len(T), C:4] == base[:len(T), C:4]).all()
+
+
+def test_density_exact_transforms(h):
+    """T of exact doubles - the identity and the quarter turns about x, y, z, translations that are small binary fractions - with atoms
+    planted on nodes, on each face, one fp32 ulp inside and outside each face, at u = -1/2 and at 1e30 / 3e38: the inside decision equals
+    the one of exact rational arithmetic under every rotation; u = -0.0 is inside (the IEEE comparison is the definition)."""
+    dc, T, labels = ph.planted_density_case()
+    out, ref = density_exact(h, dc, T, name="k_density planted")
+    exact = ph.density_inside_exact(dc, T)
+    assert (out["tot"][:4, 4] - ph.density_base(4)[:4, 4] == exact.sum(1)).all()
+    aq = out["atom_q"][:4 * dc["Al"]].reshape(4, dc["Al"])
+    assert (aq[~exact] == 0).all() and (aq[exact] != 0).mean() > 0.9
+    mz, Tz = ph.minus_zero_density_case()
+    out, ref = density_exact(h, mz, Tz, base=np.zeros((3, 6), np.int64), name="k_density u = -0.0")
+    assert out["tot"][0, 4] == 1 and ref["inside"].all()
+
+
+def test_density_ties_to_even(h):
+    """(w val) 2^20 exactly on k + 1/2: to even, for both signs; and ties that exist only because w val is rounded before the scale and
+    because the lerps run along x first."""
+    half, rounded, T = ph.ties_density_case()
+    out, _ = density_exact(h, half, T, name="k_density ties")
+    assert out["atom_q"][:5].tolist() == [0, 2, 2, 0, -2]
+    out, _ = density_exact(h, rounded, T, name="k_density ties")
+    assert out["atom_q"][:8].tolist() == [2, 4, 4, 6, 6, 8, 8, 10]
+
+
+def test_density_non_finite_T(h):
+    """NaN, +inf and -inf in each of the 12 slots of T, 36 poses between two ordinary ones: each adds nothing to tot and gets zeros in atom_q;
+    the two ordinary poses are bitwise what they are in a launch of their own."""
+    dc, rot, tr, T, _ = ph.density_launches((3, 5, 4), 2)[11]      # Al = 65, n = 5
+    T38 = ph.nonfinite_density_T(T[0], T[1])
+    base = ph.density_base(38, seed=3)
+    out, ref = density_exact(h, dc, T38, base, name="k_density non-finite T")
+    assert (out["tot"][1:37] == base[1:37]).all() and (out["atom_q"][65:37 * 65] == 0).all()
+    assert ref["inside"][0].any() and ref["inside"][37].any()
+    alone = h.density(dc, T[:2], base=base[[0, 37, 36, 36]])
+    assert (alone["tot"][:2] == out["tot"][[0, 37]]).all()
+    assert (alone["atom_q"][:130] == np.concatenate([out["atom_q"][:65], out["atom_q"][37 * 65:38 * 65]])).all()
+
+
+def test_density_every_atom_outside(h):
+    """No atom of any block inside (the wave's early return): tot keeps its base, atom_q is zeros."""
+    dc0, rot, tr, T, base = ph.density_launches((3, 5, 4), 3)[14]      # Al = 130, n = 5
+    far = dc0["lig4"][:, :3] + ph.f32([500.0, 0.0, 0.0])
+    dc = ph.density_case((3, 5, 4), 3, 130, lig=far, w=dc0["lig4"][:, 3], center=dc0["center"])
+    out, ref = density_exact(h, dc, T, base, name="k_density all outside")
+    assert not ref["inside"].any() and (out["tot"] == base).all() and (out["atom_q"][:5 * 130] == 0).all()
+
+
+def test_density_largest_n(h):
+    """n = 65535 (gridDim.y's limit) with Al = 1 on 2 x 2 x 2: accepted and exact."""
+    dc, T = ph.limit_density_case()
+    out, ref = density_exact(h, dc, T, name="k_density n 65535")
+    assert 0.2 < ref["inside"].mean() < 0.8
+
+
+@pytest.mark.parametrize("change", [dict(n=65536), dict(n=0), dict(nx=1), dict(ny=1), dict(nz=1), dict(Al=0)], ids=lambda c: "%s=%d" % next(iter(c.items())))
+def test_density_refusals_leave_every_block_alone(h, change):
+    """The launcher's own refusals (the shim lets these through): hipErrorInvalidValue, tot still the base, atom_q still the marker."""
+    dc = ph.density_case((2, 2, 2), 2, 3)
+    P = max(change.get("n", 2), 1)
+    T = np.tile(np.concatenate([np.eye(3).reshape(-1), np.zeros(3)]), (P, 1))
+    over = dict(change)
+    for k, slot in (("nx", 10), ("ny", 11), ("nz", 12)):
+        if k in change:
+            over["geo"] = dc["geo"].copy()
+            over["geo"][slot] = change[k] - 1.0
+    base = ph.density_base(P, seed=4)
+    out = h.density(dc, T, base=base, check=False, **over)
+    assert out["err"] == ph.HIP_INVALID_VALUE
+    assert (out["tot"] == base).all() and (out["atom_q"] == ph.MARKER).all()
+    assert ph.guards_intact(out, "tot") and ph.guards_intact(out, "atom_q")
+
+
+def test_density_limits_of_the_sums(h):
+    """Grid values of 2^10 and weights of +-2^7: every term is +-2^37 exactly, 130 of them per pose."""
+    dc, T = ph.sum_limit_density_case()
+    out, ref = density_exact(h, dc, T, base=np.zeros((4, 6), np.int64), name="k_density limits")
+    assert set(np.abs(out["atom_q"][:260]).tolist()) == {1 << 37} and (out["tot"][:2, 0] == (117 - 13) * (1 << 37)).all()
+    assert (out["tot"][:2, 1] == -out["tot"][:2, 0]).all() and (out["tot"][:2, 4:] == 130).all()

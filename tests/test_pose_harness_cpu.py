@@ -539,3 +539,147 @@ def test_shim_refuses_bad_indices_of_the_other_four_walks(shim):
     for change in (dict(G=5), dict(G=0), dict(G=sf.G + 1), dict(rec_class=cls), dict(lig_class=np.full(sf.fr.Al, -1, np.int32)), dict(dirs=sf.dirs[:-1]),
                    dict(rec_exp=bufs["rec_exp"][:-1]), dict(rec_bur=ph.Out(np.uint64, len(Ts) * sf.fr.Ar * sf.G - 1)), dict(tot=ph.Out(np.int32, 32 * len(Ts) - 1))):
         assert check("surface", **change) == ph.HIP_INVALID_VALUE, list(change)
+
+
+# ---- the density fit: density_ref is the definition, the shim's checks, the power of the comparisons, the conditions on the inputs -------------
+def test_shim_links_the_density_launchers(shim):
+    und = kh.exported_symbols(shim.path, False)
+    assert "launch_density_pose" in und and "launch_densityERK" in und
+
+
+def all_density_launches():
+    return [L for shape in ph.DENSITY_SHAPES for C in (1, 2, 3, 4) for L in ph.density_launches(shape, C)]
+
+
+def test_density_restatement_agrees_with_the_definition():
+    """density_ref on T = pose_T(rot, tr) equals dfmdock_amd.density.density on every array, for every launch of test_density_exact and
+    for the poses of the non-finite, all-outside and limit cases that come from rot / tr; the channels at or above C are left out."""
+    n = 0
+    for dc, rot, tr, T, base in all_density_launches():
+        ref, want = ph.density_ref(dc["grid4"], dc["geo"], dc["lig4"], T, dc["C"]), ph.density_definition(dc, rot, tr)
+        C = dc["C"]
+        assert np.array_equal(ref["tot"][:, :C], want["sum_q"]) and not ref["tot"][:, C:4].any()
+        assert np.array_equal(ref["tot"][:, 4], want["n_inside"]) and np.array_equal(ref["tot"][:, 5], want["n_above"])
+        assert np.array_equal(ref["atom_q"], want["atom_q"])
+        n += ref["inside"].size
+    assert n == 8 * 323 * 8
+    # T as exact doubles: the identity and zero rotation vectors are the same pose to the definition
+    dc, T = ph.sum_limit_density_case()
+    want = ph.density_definition(dc, np.zeros((2, 3), np.float32), T[:, 9:].astype(np.float32))
+    ref = ph.density_ref(dc["grid4"], dc["geo"], dc["lig4"], T, dc["C"])
+    assert np.array_equal(ref["tot"][:, :2], want["sum_q"]) and np.array_equal(ref["atom_q"], want["atom_q"])
+    for dc, T in ((ph.ties_density_case()[0], ph.ties_density_case()[2]), (ph.ties_density_case()[1], ph.ties_density_case()[2])):
+        want = ph.density_definition(dc, np.zeros((1, 3), np.float32), np.zeros((1, 3), np.float32))
+        assert np.array_equal(ph.density_ref(dc["grid4"], dc["geo"], dc["lig4"], T, 1)["atom_q"], want["atom_q"])
+    # a pose that is not finite: zeros in the definition, nothing added in the restatement
+    dc, rot, tr, T, _ = ph.density_launches((3, 5, 4), 2)[11]
+    ref = ph.density_ref(dc["grid4"], dc["geo"], dc["lig4"], ph.nonfinite_density_T(T[0], T[1]), 2)
+    assert not ref["tot"][1:37].any() and not ref["atom_q"][1:37].any() and ref["tot"][0, 4] > 0 and ref["tot"][37, 4] > 0
+
+
+def test_density_inputs_hold_what_they_claim():
+    """The conditions the GPU tests rely on, none excused: the planted transforms are exact (the restatement's inside decision equals the
+    rational one for all 4 x 119 pairs; every face atom has its two fp32 neighbours on either side of the decision; upper faces are
+    outside, lower faces inside, u = -1/2 outside); every generic launch has atoms inside and outside, on both sides of the threshold; the
+    limit case's terms are 2^37."""
+    dc, T, labels = ph.planted_density_case()
+    ref = ph.density_ref(dc["grid4"], dc["geo"], dc["lig4"], T, dc["C"])
+    exact = ph.density_inside_exact(dc, T)
+    assert np.array_equal(ref["inside"], exact)
+    assert set(np.unique(T[:, :9]).tolist()) == {-1.0, 0.0, 1.0}
+    own = {}
+    for a, (p, kind) in enumerate(labels):
+        own.setdefault((p, kind), []).append(bool(exact[p, a]))
+    for p in range(4):
+        assert own[(p, "lower")] == [True] * 3 and own[(p, "upper")] == [False] * 3 and own[(p, "neg_half")] == [False] * 3, p
+        for face, inward in (("lower", True), ("upper", False)):
+            up, down = own[(p, face + "+")], own[(p, face + "-")]
+            assert all(a != b for a, b in zip(up, down)), (p, face)      # one ulp either way decides
+        assert sum(own[(p, "node")]) == 4 and len(own[(p, "node")]) == 8      # the nodes on an upper face are outside
+    assert not exact[:, -3:].any()      # 1e30, 3e38
+    assert exact.sum(1).min() >= 13 and (~exact).sum(1).min() >= 50      # every pose sees the other poses' atoms on both sides too
+    for dc, rot, tr, T, base in all_density_launches():
+        ref = ph.density_ref(dc["grid4"], dc["geo"], dc["lig4"], T, dc["C"])
+        if dc["Al"] >= 63:
+            assert (ref["inside"].sum(1) > 0).all() and (~ref["inside"]).sum(1).min() > 0
+            assert 0 < ref["tot"][:, 5].sum() < ref["tot"][:, 4].sum()
+    mz, Tz = ph.minus_zero_density_case()
+    with np.errstate(all="ignore"):
+        u = (Tz[0, 9] - mz["geo"][0]) / mz["geo"][3]
+    assert u == 0.0 and np.signbit(u) and ph.density_ref(mz["grid4"], mz["geo"], mz["lig4"], Tz, 1)["inside"].all()
+    assert not ph.density_inside_exact(mz, Tz).any()      # the exact quotient is negative: the IEEE comparison is the definition
+    dc, T = ph.limit_density_case()
+    assert len(T) == 65535 and dc["Al"] == 1
+
+
+DENSITY_MUTANT_CASE = {"le_upper": "planted", "trunc": "planted", "fx_f32": "generic 130", "y_before_x": "rounded", "stride_swapped": "generic 130",
+                       "half_away": "half", "contracted": "rounded", "channel1_above": "generic 130", "lanes_past_Al": "generic 65", "tot_stored": "generic 130"}
+
+
+@pytest.mark.parametrize("mutant", sorted(ph.DENSITY_MUTANTS))
+def test_density_mutants_are_rejected(mutant):
+    """Each seeded mutant of density_ref is rejected by the comparison named for it in DENSITY_MUTANTS, on inputs the GPU file launches."""
+    half, rounded, Tt = ph.ties_density_case()
+    L = ph.density_launches((3, 5, 4), 2)
+    planted = ph.planted_density_case()
+    cases = {"planted": (planted[0], planted[1], ph.density_base(4)), "half": (half, Tt, ph.density_base(1)), "rounded": (rounded, Tt, ph.density_base(1)),
+             "generic 65": (L[11][0], L[11][3], L[11][4]), "generic 130": (L[14][0], L[14][3], L[14][4])}
+    dc, T, base = cases[DENSITY_MUTANT_CASE[mutant]]
+    assert (dc["Al"], len(T)) in ((65, 5), (130, 5), (119, 4), (5, 1), (8, 1))
+    ref = ph.density_ref(dc["grid4"], dc["geo"], dc["lig4"], T, dc["C"], base=base)
+    good = ph.density_compare(dict(tot=np.concatenate([ref["tot"], base[len(T):]]), atom_q=ref["atom_q"]), ref, len(T), dc["Al"], base=base)
+    assert not any(good.values())
+    bad = ph.density_ref(dc["grid4"], dc["geo"], dc["lig4"], T, dc["C"], base=base, mutant=mutant)
+    cmp = ph.density_compare(dict(tot=np.concatenate([bad["tot"], base[len(T):]]), atom_q=bad["atom_q"]), ref, len(T), dc["Al"], base=base)
+    assert cmp[ph.DENSITY_MUTANTS[mutant]] > 0, (mutant, cmp)
+
+
+def test_density_compare_sees_writes_past_the_launch():
+    dc, rot, tr, T, base = ph.density_launches((2, 2, 2), 1)[4]
+    ref = ph.density_ref(dc["grid4"], dc["geo"], dc["lig4"], T, 1, base=base)
+    tot, aq = np.concatenate([ref["tot"], base[len(T):]]), np.concatenate([ref["atom_q"].reshape(-1), np.full(2 * dc["Al"], ph.MARKER)])
+    assert ph.density_compare(dict(tot=tot, atom_q=aq), ref, len(T), dc["Al"], base=base)["past"] == 0
+    tot[-1, 4] += 1
+    aq[len(T) * dc["Al"]] = 0
+    assert ph.density_compare(dict(tot=tot, atom_q=aq), ref, len(T), dc["Al"], base=base)["past"] == 2
+
+
+def _density_call(dc, poses, **change):
+    """The record of one density launch on `poses` [P,12], with scalars or buffers replaced by `change`."""
+    P = len(poses)
+    bufs = dict(grid=dc["grid4"], geo=dc["geo"], lig=dc["lig4"], T=poses, tot=ph.Out(np.int64, P * 6), atom_q=ph.Out(np.int64, P * max(dc["Al"], 1)))
+    sc = dict(nx=dc["dims"][0], ny=dc["dims"][1], nz=dc["dims"][2], n=P, Al=dc["Al"], C=dc["C"])
+    for k, v in change.items():
+        (sc if k in sc else bufs)[k] = v
+    return bufs, sc
+
+
+def test_shim_checks_of_the_density_launch(shim):
+    """One malformed record per condition, refused without touching a device; n, nx / ny / nz < 2 and Al < 1 pass the shim (they are the
+    launcher's to refuse) as long as the arrays hold max(., 2) nodes per axis, max(Al, 1) atoms and max(n, 0) poses."""
+    dc, rot, tr, T, _ = ph.density_launches((3, 5, 4), 2)[5]      # Al = 63, n = 5
+    b, s = _density_call(dc, T)
+    assert shim.check_only("density", b, **s) == ph.HIP_SUCCESS
+    geo = lambda k, v: dict(geo=np.concatenate([dc["geo"][:k], [v], dc["geo"][k + 1:]]))
+    bad = [dict(grid=dc["grid4"].reshape(-1)[:-1]), dict(lig=dc["lig4"][:-1]), dict(geo=dc["geo"][:-1]), dict(T=T[:-1]), dict(tot=ph.Out(np.int64, 29)),
+           dict(atom_q=ph.Out(np.int64, 5 * 63 - 1)), dict(tot=np.zeros(30, np.int64)), dict(grid=ph.Out(np.float32, init=dc["grid4"])),
+           geo(0, np.nan), geo(7, np.inf), geo(9, -np.inf), geo(4, 0.0), geo(3, -1.5), geo(10, 4.0), geo(11, 3.0), geo(12, 3.0), geo(13, np.nan),
+           dict(nx=5), dict(ny=4), dict(nz=4), dict(n=6), dict(Al=64), dict(C=0), dict(C=5)]
+    for change in bad:
+        b, s = _density_call(dc, T, **change)
+        assert shim.check_only("density", b, **s) == ph.HIP_INVALID_VALUE, list(change)
+        r = shim.run("density", b, check=False, **s)
+        assert r["err"] == ph.HIP_INVALID_VALUE and all(not r[k + "_guard"][0].any() for k, v in b.items() if isinstance(v, ph.Out)), list(change)
+    small = ph.density_case((2, 2, 2), 2, 3)
+    T2 = T[:2]
+    for change in (dict(n=0), dict(Al=0), dict(nx=1, geo=np.concatenate([small["geo"][:10], [0.0], small["geo"][11:]])),
+                   dict(nz=1, geo=np.concatenate([small["geo"][:12], [0.0], small["geo"][13:]]))):
+        b, s = _density_call(small, T2, **change)
+        assert shim.check_only("density", b, **s) == ph.HIP_SUCCESS, list(change)
+    b, s = _density_call(small, np.tile(T2[:1], (65536, 1)), atom_q=None)
+    assert shim.check_only("density", b, **s) == ph.HIP_SUCCESS
+    rot, tr = ph.pose_inputs(5)
+    ok = dict(rot=rot, tr=tr, T=ph.Out(np.float64, 60), tot=ph.Out(np.int64, 30))
+    assert shim.check_only("pose_density", ok, n=5) == ph.HIP_SUCCESS
+    for change in (dict(tot=ph.Out(np.int64, 29)), dict(tr=tr[:-1]), dict(T=ph.Out(np.float64, 59))):
+        assert shim.check_only("pose_density", dict(ok, **change), n=5) == ph.HIP_INVALID_VALUE, list(change)
