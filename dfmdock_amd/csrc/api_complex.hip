@@ -41,11 +41,23 @@ static hipError_t project_layer0(dfm_complex *cx)
     return hipGetLastError();
 }
 
+// "" when every coordinate of the given arrays (either may be NULL: not given) is a number, else the message of the refusal
+static std::string stored_pose_error(const float *rec_pos, int R, const float *lig_pos, int L)
+{
+    size_t k;
+    if (rec_pos && (k = first_nonfinite(rec_pos, (size_t)R * 9)) < (size_t)R * 9) return "rec_pos: residue " + std::to_string(k / 9) + " is not finite";
+    if (lig_pos && (k = first_nonfinite(lig_pos, (size_t)L * 9)) < (size_t)L * 9) return "lig_pos: residue " + std::to_string(k / 9) + " is not finite";
+    return "";
+}
+
 extern "C" dfm_complex *dfm_complex_create(dfm_model *m, const float *rec_x, const float *lig_x, const float *rec_pos,
                                            const float *lig_pos, int R, int L)
 {
     if (!m || !rec_x || !lig_x || !rec_pos || !lig_pos) { fail(DFM_E_INVALID, "NULL argument"); return nullptr; }
     if (R < 1 || L < 1 || R + L > MAX_NODES) { fail(DFM_E_INVALID, "need 1 <= R, L and R + L <= 4096"); return nullptr; }
+    // the stored pose is what the layer-0 table and the A0 / Bm0 operands are built from: it must be numbers (checked before anything
+    // is created or enqueued)
+    if (const std::string bad = stored_pose_error(rec_pos, R, lig_pos, L); !bad.empty()) { fail(DFM_E_INVALID, bad); return nullptr; }
     DeviceScope ds(m->device);
     if (ds.err != hipSuccess) { fail(DFM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(ds.err)); return nullptr; }
     dfm_complex *cx = new dfm_complex();
@@ -116,6 +128,8 @@ extern "C" int dfm_complex_degree(const dfm_complex *cx) { return cx ? cx->K : -
 extern "C" int dfm_complex_set_pose(dfm_complex *cx, const float *rec_pos, const float *lig_pos)
 {
     if (!cx) return fail(DFM_E_INVALID, "NULL argument");
+    // both arrays are checked before either is copied: a refused call keeps the stored pose and the tables built from it
+    if (const std::string bad = stored_pose_error(rec_pos, cx->R, lig_pos, cx->L); !bad.empty()) return fail(DFM_E_INVALID, bad);
     DEVICE_SCOPE(cx->device);
     // the stream may still read the old poses (an earlier call never returns before its work is done, but stay safe)
     HIPCHK(hipStreamSynchronize(cx->stream));

@@ -154,17 +154,34 @@ __device__ inline void prep_pose_block(const float *__restrict__ rec_pos, const 
 {
     const int N = R + L;
     double s0 = 0, s1 = 0, s2 = 0;
+    // Non-finite poses (include/dfmdock_amd.h): a pose with a NaN or infinite coordinate in ANY backbone atom gets a NaN centre, so
+    // that every prepared coordinate of this trajectory - and with them every floating-point output of it - is NaN, not the finite
+    // values a NaN in an N or C atom alone (angle bins 0) would leave.  A test of the bits in the pass that forms the centroid
+    // (the CA centroid's pass reads the residue's other two atoms for it): finite poses keep theirs.
+    bool bad = false;
+    auto marked = [](float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; };
     if (all_atoms) {
-        for (int q = threadIdx.x; q < L * 3; q += blockDim.x) { s0 += lig[q * 3]; s1 += lig[q * 3 + 1]; s2 += lig[q * 3 + 2]; }
+        for (int q = threadIdx.x; q < L * 3; q += blockDim.x) {
+            const float x = lig[q * 3], y = lig[q * 3 + 1], z = lig[q * 3 + 2];
+            s0 += x; s1 += y; s2 += z;
+            bad = bad || marked(x) || marked(y) || marked(z);
+        }
     } else {
-        for (int q = threadIdx.x; q < L; q += blockDim.x) { s0 += lig[q * 9 + 3]; s1 += lig[q * 9 + 4]; s2 += lig[q * 9 + 5]; }
+        for (int q = threadIdx.x; q < L; q += blockDim.x) {
+            float v[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) { v[k] = lig[q * 9 + k]; bad = bad || marked(v[k]); }
+            s0 += v[3]; s1 += v[4]; s2 += v[5];
+        }
     }
+    if (bad) s0 = __builtin_nan("");
     s0 = block_sum_d(s0, scratch);
     s1 = block_sum_d(s1, scratch);
     s2 = block_sum_d(s2, scratch);
     if (threadIdx.x == 0) {
         const int cnt = all_atoms ? L * 3 : L;
         center[0] = (float)(s0 / cnt); center[1] = (float)(s1 / cnt); center[2] = (float)(s2 / cnt);
+        if (s0 != s0) center[1] = center[2] = center[0];      // marked above (or a NaN sum): NaN on all three axes
     }
     __syncthreads();
     const float cx = center[0], cy = center[1], cz = center[2];

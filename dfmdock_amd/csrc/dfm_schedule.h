@@ -4,12 +4,24 @@
 #pragma once
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
 #include "../../include/dfmdock_amd.h"
 
 namespace dfm {
+
+// index of the first value of x[0 .. n) that is NaN or infinite; n when all are numbers (the stored pose of a complex must be:
+// dfm_complex_create / dfm_complex_set_pose refuse it otherwise, include/dfmdock_amd.h "non-finite poses").  No part of the schedule:
+// it lives here because this is the engine's one header of plain host C++ (no HIP), which tests/schedule_main.cpp already builds under
+// the sanitizers - the scan of a caller's array is what such a build is for
+inline size_t first_nonfinite(const float *x, size_t n)
+{
+    for (size_t k = 0; k < n; ++k)
+        if (!std::isfinite(x[k])) return k;
+    return n;
+}
 
 // g(t) and sigma(t) of the R^3 (which 0) or SO(3) (which 1) diffuser; DFM_E_INVALID for another `which`, or t outside [0,1] on SO(3)
 inline int diffusion_coef(const dfm_hparams &hp, int which, double t, double *g_out, double *sigma_out)

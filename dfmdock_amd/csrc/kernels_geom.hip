@@ -80,12 +80,21 @@ template <int NPL> __device__ inline uint32_t knn_count_lt(const uint32_t (&key)
     return (uint32_t)__builtin_amdgcn_readlane((int)c, 0) + (uint32_t)__builtin_amdgcn_readlane((int)c, 32);      // wave-uniform
 }
 __device__ inline uint32_t knn_cand(int lane, int r) { return 4u * (uint32_t)lane + 256u * (uint32_t)(r >> 2) + (uint32_t)(r & 3); }
+// The selection words (include/dfmdock_amd.h, "non-finite poses": the ordering rule of the graph).  A distance or race key that is a
+// number is >= +0 and keeps its own bits (<= 0x7F800000 = +inf); a NaN of either sign and any payload becomes ONE word above +inf, so
+// NaN candidates tie and go by ascending index; a slot that is no candidate (j >= N, or taken by the kNN stage) lies above every
+// candidate.  All three have bit 31 clear, which knn_select relies on, and k <= candidates: a padding slot is never taken.
+// v is a number >= +0 (a square root; |log2 u| d^3) or a NaN: ONE unsigned minimum leaves the first alone and maps every NaN word
+// (0x7F800001 .. 0x7FFFFFFF and, as unsigned, everything with the sign bit) to KNN_KEY_NAN.  The kernel is VALU-bound: this is the
+// whole cost of the rule in the kNN stage, one instruction per candidate.
+constexpr uint32_t KNN_KEY_NAN = 0x7F800001u, KNN_KEY_PAD = 0x7FFFFFFFu;
+__device__ inline uint32_t knn_key_word(float v) { const uint32_t w = __float_as_uint(v); return w < KNN_KEY_NAN ? w : KNN_KEY_NAN; }
 // bit r of the result: slot r of this lane is among the k smallest (key, candidate index) pairs of the wave (k <= valid keys)
 template <int NPL> __device__ inline uint64_t knn_select(const uint32_t (&key)[NPL], int k, int lane)
 {
     uint32_t prefix = 0, thr = 0;
     bool exact = false;
-    for (int bit = 30; bit >= 0; --bit) {      // keys are non-negative floats: bit 31 is clear
+    for (int bit = 30; bit >= 0; --bit) {      // keys are knn_key_word / KNN_KEY_PAD words: bit 31 is clear
         const uint32_t t = prefix | (1u << bit);
         const uint32_t c = knn_count_lt<NPL>(key, t);
         if (c == (uint32_t)k) { thr = t; exact = true; break; }
@@ -144,13 +153,14 @@ __global__ __launch_bounds__(256) void k_knn_sample(const float4 *__restrict__ c
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int j = 4 * (lane + 64 * q) + e;
-            float d = __builtin_inff();
+            uint32_t kw = KNN_KEY_PAD;
             if (j < N) {
                 const float4 cj = ca[j];
                 const float dx = ci.x - cj.x, dy = ci.y - cj.y, dz = ci.z - cj.z;
-                d = sqrtf((dx * dx + dy * dy) + dz * dz);
+                const float d = sqrtf((dx * dx + dy * dy) + dz * dz);
+                kw = knn_key_word(d);
             }
-            key[q * 4 + e] = __float_as_uint(d);
+            key[q * 4 + e] = kw;
         }
         // (keeps the scheduler from hoisting all NPL coordinate loads - 4 registers each - to the top: at NPL = 32 that alone is 128)
         if ((q & 1) == 1) __builtin_amdgcn_sched_barrier(0);
@@ -179,6 +189,7 @@ __global__ __launch_bounds__(256) void k_knn_sample(const float4 *__restrict__ c
     }
     if (nsamp > 0) {
         // ---- sampling: race keys for every candidate not taken above; the nsamp smallest win
+        const int lim = N - 4 * lane;
 #pragma unroll
         for (int q = 0; q < NPL / 4; ++q) {
             const u32x4 rnd = philox4x32((uint32_t)node, (uint32_t)(node >> 32) ^ ((uint32_t)(lane + 64 * q) << 8),
@@ -187,16 +198,19 @@ __global__ __launch_bounds__(256) void k_knn_sample(const float4 *__restrict__ c
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int r = q * 4 + e;
-                float d = __uint_as_float(key[r]);
-                float k2 = __builtin_inff();
-                if (!((near >> r) & 1) && d != __builtin_inff()) {   // not taken by kNN, j < N
-                    d = d < 1e-10f ? 1e-10f : d;
+                uint32_t kw = KNN_KEY_PAD;
+                // not taken by kNN, and a residue whatever its distance: j = 4 lane + (256 (r / 4) + r % 4) < N, the constant against lim
+                if (!((near >> r) & 1) && 256 * (r >> 2) + (r & 3) < lim) {
+                    // d < 1e-10f ? 1e-10f : d on the words: distances are >= +0, so the unsigned maximum is the float maximum, and
+                    // KNN_KEY_NAN stays - as a float it is a NaN, and its race key is NaN again
+                    const uint32_t dw = key[r], floor = __float_as_uint(1e-10f);
+                    const float d = __uint_as_float(dw > floor ? dw : floor);
                     // v_log_f32 (log2): a common factor ln 2 does not change the race.  |log2 u| and not -log2 u: u01 can return exactly 1.0f, and
                     // -log2(1) d^3 = -0.0f has the sign bit set - as a word it would order ABOVE every key in the selection below, so the
                     // candidate that wins with certainty could never be drawn (and with nsamp = all candidates a slot stayed unwritten)
-                    k2 = fabsf(__builtin_amdgcn_logf(u01(rr[e]))) * ((d * d) * d);
+                    kw = knn_key_word(fabsf(__builtin_amdgcn_logf(u01(rr[e]))) * ((d * d) * d));
                 }
-                key[r] = __float_as_uint(k2);
+                key[r] = kw;
             }
             __builtin_amdgcn_sched_barrier(0);      // one Philox block at a time: its temporaries are not multiplied by NPL / 4
         }
@@ -355,8 +369,11 @@ __global__ __launch_bounds__(CLS ? 1024 : 256) void k_edge_feat(const float4 *__
         // the distance moves by rounding only (|d r2| <= 2 d x ~1e-5 A), a different conformer or a perturbed backbone moves it by
         // >= 2 d x 1e-2 A - such an edge is a miss and goes through the edge model, so DFM_F_L0_TABLE is safe for ANY lig_pos
         // (the rigid-image precondition is now checked instead of assumed)
+        // (r2 = +inf, a residue at infinity, would pass the comparison as inf <= inf with the code of any pair beyond the last distance
+        // bin: a pair whose r2 is no finite number is never a hit; a NaN fails the comparison by itself)
         const uint2 c0 = cls.code0[idx];
-        const bool hit = live && same && c0.x == code && fabsf(__uint_as_float(c0.y) - r2) <= 1e-3f * fmaxf(sqrtf(r2), 1.0f);
+        const bool hit = live && same && c0.x == code && fabsf(__uint_as_float(c0.y) - r2) <= 1e-3f * fmaxf(sqrtf(r2), 1.0f) &&
+                         r2 < __builtin_inff();
         const bool is_miss = live && !hit;
         const unsigned long long miss = __ballot(is_miss);
         const int lane = threadIdx.x & 63;
@@ -649,6 +666,7 @@ hipError_t launch_start_pose(const StartArgs &a, int B, hipStream_t s)
 // form only after a float32 distance test with a margin (d^2 < 16.5: pairs within 4 A are rare) - r01-r04 ran every one of the 810 k pairs of a
 // 300+300 complex through float64 sqrt / division in 256 threads: 0.53 ms per step whatever the batch (+69 % on a B = 8 call,
 // tools/option_costs.py).  Same expressions for the pairs that count; the float64 partial sums group differently (1e-16).
+__device__ inline bool not_a_number_or_inf(float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; }
 __global__ __launch_bounds__(1024) void k_clash_force(const float *__restrict__ rec_pos, int R, int L,
                                                       float *__restrict__ lig_cur, float *__restrict__ tr_update)
 {
@@ -660,11 +678,16 @@ __global__ __launch_bounds__(1024) void k_clash_force(const float *__restrict__ 
     float *lig = lig_cur + (size_t)b * L * 9;
     const int nj = (L * 3 + (int)blockDim.x - 1) / (int)blockDim.x;      // ligand atoms per thread (1 up to 341 residues)
     double g0 = 0, g1 = 0, g2 = 0;
+    bool bad = false;
     for (int jj = 0; jj < nj; ++jj) {
         const int j = threadIdx.x + jj * blockDim.x;
         const bool jv = j < L * 3;
         const float fx = jv ? lig[j * 3] : 0.f, fy = jv ? lig[j * 3 + 1] : 0.f, fz = jv ? lig[j * 3 + 2] : 0.f;
         const double lx = fx, ly = fy, lz = fz;
+        // Non-finite poses (include/dfmdock_amd.h): an atom with a NaN or infinite coordinate passes no `< 16.5f` below and would be
+        // dropped from the force, the rest of the pose moved by a finite shift.  Such a pose gets a NaN shift instead (a test of the
+        // bits: finite poses keep theirs)
+        bad = bad || not_a_number_or_inf(fx) || not_a_number_or_inf(fy) || not_a_number_or_inf(fz);
         for (int c0 = 0; c0 < R * 3; c0 += CH) {      // (per thread the receptor atoms are still visited in ascending order)
             const int cn = R * 3 - c0 < CH ? R * 3 - c0 : CH;
             __syncthreads();
@@ -686,9 +709,11 @@ __global__ __launch_bounds__(1024) void k_clash_force(const float *__restrict__ 
             }
         }
     }
+    if (bad) g0 = __builtin_nan("");
     g0 = block_sum_d(g0, scratch); g1 = block_sum_d(g1, scratch); g2 = block_sum_d(g2, scratch);
     if (threadIdx.x == 0) {
         shift[0] = (float)(g0 / (L * 3)); shift[1] = (float)(g1 / (L * 3)); shift[2] = (float)(g2 / (L * 3));
+        if (g0 != g0) shift[1] = shift[2] = shift[0];      // marked above: the whole pose and tr_update become NaN
         for (int k = 0; k < 3; ++k) tr_update[b * 3 + k] += shift[k];
     }
     __syncthreads();

@@ -244,6 +244,10 @@ __global__ __launch_bounds__(256) void k_heads(HeadKArgs p)
             s_score[6] = p.en_mode == 0 ? (float)a[9] / ((float)a[10] + 1e-6f)
                                         : (p.en_mode == 1 ? (float)a[9] / fmaxf((float)a[10], 1.0f) : (float)a[9]);
             s_score[7] = (float)a[11];
+            // a non-finite pose (prep_pose_block: every prepared coordinate is NaN) passes no `D < cut_off`: without this its energy
+            // would be that of a pose out of contact, 0 / 1e-6.  It is NaN like the pose's other outputs; num_clashes stays 0
+            const float x0 = p.ca4[(size_t)b * N].x;
+            if (x0 != x0) s_score[6] = x0;
         } else {
             s_score[6] = 0.f; s_score[7] = 0.f;
         }

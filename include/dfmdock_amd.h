@@ -314,14 +314,17 @@ int64_t dfm_param_count(const dfm_hparams *hp);
 dfm_model *dfm_model_create(const float *blob, size_t n_floats, const dfm_hparams *hp);
 void dfm_model_destroy(dfm_model *m);
 
+/* NULL with DFM_E_INVALID, nothing created or enqueued: a NULL pointer, R or L < 1, R + L > 4096, a NaN or infinite value in rec_pos
+ * or lig_pos (the stored pose must be numbers: the layer-0 table and operands are built from it). */
 dfm_complex *dfm_complex_create(dfm_model *m, const float *rec_x /*[R,lm]*/, const float *lig_x /*[L,lm]*/,
                                 const float *rec_pos /*[R,9]*/, const float *lig_pos /*[L,9]*/, int R, int L);
 void dfm_complex_destroy(dfm_complex *cx);
 /* Replace the poses stored by dfm_complex_create (either pointer may be NULL = keep): rec_pos [R,9] is what every later
  * dfm_score / dfm_sample call sees as the receptor, lig_pos [L,9] is the start pose of dfm_sample.  The node features and
  * everything derived from them stay resident - a caller that re-centres the complex every step (DFMDock.move_to_lig_center,
- * src/models/DFMDock.py:254-257) or docks several ligand conformations does not pay the feature upload again.  On an error
- * return the stored poses are unspecified (one of the two may have been replaced): call again. */
+ * src/models/DFMDock.py:254-257) or docks several ligand conformations does not pay the feature upload again.  A NaN or infinite
+ * value in either array: DFM_E_INVALID before anything is copied - both stored poses, the tables built from them and every later
+ * result stay as they were.  On a DFM_E_HIP return the stored poses are unspecified (one of the two may have been replaced): call again. */
 int dfm_complex_set_pose(dfm_complex *cx, const float *rec_pos_or_null, const float *lig_pos_or_null);
 /* positional_embed_dim = 67 only: value of the 67th ("sym") position channel for this complex - 1 when receptor and ligand
  * have the same sequence (is_homomer, src/datasets/docking_dataset.py:129), 0 otherwise (the default).  DFM_E_INVALID for a
@@ -855,7 +858,33 @@ long long dfm_trim_cache(int device);
  * damaged.  Without the variables only out[0] counts. */
 int dfm_alloc_diag(int64_t out[6]);
 
-/* B score evaluations of poses lig_pos[B,L,9] at times t[B] */
+/* NON-FINITE POSES IN THE TRUNK CALLS (dfm_score, dfm_score_distogram, dfm_sample, dfm_refine, dfm_complex_selfcheck).
+ * A pose can carry a NaN or an infinite coordinate: dfm_score, dfm_score_distogram and dfm_refine(start_pos) take host poses
+ * unchecked, an injected tr_draw or R0 can be NaN, and the restraint and symmetry steps give a non-finite pose a NaN step.
+ * Such a pose is not an error of the call.  What holds for it (tests/test_gpu_nonfinite.py, launch by launch in
+ * tests/test_gpu_geom_kernels.py and tests/test_gpu_head_kernels.py):
+ *   1. In range.  Whatever the coordinates, every index a kernel forms from them stays inside its array: graph edges are residue
+ *      indices in [0, N), and so are the positions in the row list and the layer-0 table that follow from them.
+ *   2. Contained.  A pose (trajectory) with a non-finite coordinate changes no bit of any other pose's outputs in the same call.
+ *   3. Visible.  The pose preparation marks a pose with a NaN or infinite coordinate in ANY backbone atom: every prepared coordinate
+ *      of it is NaN.  Its tr_score, rot_score, energy and f are NaN - the energy too, although no residue pair of it passes
+ *      D < cut_off - and from dfm_sample / dfm_refine also its lig_pos, rot_update and tr_update, from the first evaluation that
+ *      sees the coordinate on.  num_clashes of such a pose is 0 (no pair passes D <= 3; an integer has no NaN).
+ *      The clash force (DFM_F_CLASH_FORCE) does the same on its own: a pose with a non-finite coordinate in any atom gets a NaN
+ *      shift - its whole pose and tr_update are NaN - instead of a finite shift from the atoms that are numbers.
+ *      dfm_score_distogram: its nll, nll_near and exp_contacts are NaN, n_near is 0, its slices of the per-pair maps are NaN, and
+ *      EVERY entry of pcontact_mean is NaN, since that map is the mean over all B poses.
+ *   4. Stored poses are refused.  The layer-0 message table and the layer-0 operands are built from the stored pose:
+ *      dfm_complex_create and dfm_complex_set_pose return NULL / DFM_E_INVALID for a NaN or infinite value in rec_pos or lig_pos,
+ *      before anything is created, copied or enqueued; dfm_complex_set_pose then keeps BOTH stored poses as they were.  So
+ *      dfm_complex_selfcheck, which runs the stored pose, never sees one.
+ *   5. Ordering rule of the graph.  Of the C-alpha distances of a node, a NaN (either sign, any payload) orders after every
+ *      number, +inf included, and all NaN tie; ties go by ascending residue index.  Only residues are candidates (j < N: no
+ *      padding slot of the selection is ever taken).  In the sampling race a candidate at a NaN distance (NaN race key) is drawn
+ *      only after every candidate with a number key; a residue at +inf has the key +inf.  A node none of whose distances is a
+ *      number (every node of a marked pose) therefore has the kNN slots 0 .. knn-1 and the next nsamp residues. */
+
+/* B score evaluations of poses lig_pos[B,L,9] at times t[B].  Non-finite poses: see above (rules 1-3). */
 int dfm_score(dfm_complex *cx, int B, const float *lig_pos, const float *t, const int32_t *edges_or_null,
               uint64_t seed, uint32_t flags, dfm_score_out *out);
 
@@ -869,7 +898,9 @@ int dfm_score(dfm_complex *cx, int B, const float *lig_pos, const float *t, cons
  * pcontact over the B poses, added in index order in double.  The logits are never stored (DFM_F_DIST returns them).  fp32 throughout in
  * every engine; fixed-order reductions, no atomics: a pose's numbers do not depend on B, on its index or on which maps are asked for.
  * The forward is dfm_score's (same arguments; flags: the engine flags DFM_F_MFMA16 / DFM_F_F16 / DFM_F_BF16_OPS only).
- * DFM_E_INVALID, nothing enqueued: a NULL required pointer, B < 1, a family-0 model, contact_bins outside 1..63, any other flag. */
+ * DFM_E_INVALID, nothing enqueued: a NULL required pointer, B < 1, a family-0 model, contact_bins outside 1..63, any other flag.
+ * A pose with a non-finite coordinate (rules 1-3 above): its per-pose outputs and map slices are NaN (n_near 0), every entry of
+ * pcontact_mean is NaN, and the other poses keep their bits. */
 typedef struct {
     int32_t contact_bins;   /* bins 0 .. contact_bins - 1 count as contact: 7 <-> d <= 7.85 A */
     float near_cutoff;      /* <= 0: the model's cut_off */
@@ -890,7 +921,8 @@ int dfm_score_distogram(dfm_complex *cx, int B, const float *lig_pos, const floa
  * between them (forward, to_dist.0 projection, k_pair_dist_sum, k_dist_finish, k_dist_mean) - tools/distogram_bench.py */
 int dfm_distogram_last_timing(double *copy_ms, double *kernel_ms);
 
-/* B independent trajectories of the Euler-Maruyama sampler */
+/* B independent trajectories of the Euler-Maruyama sampler.  A trajectory whose pose becomes non-finite (an injected NaN draw, a NaN
+ * step) stays NaN to the end and leaves the others alone: rules 1-3 of "non-finite poses" above. */
 int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, float tr_noise_scale, float rot_noise_scale,
                uint32_t flags, uint64_t seed, const dfm_inject *inj_or_null, dfm_traj_out *out);
 
@@ -901,7 +933,9 @@ int dfm_sample(dfm_complex *cx, int B, int num_steps, float eps, float tr_noise_
  * translation and are composed as in dfm_sample: they map the START pose of a trajectory onto its final pose; init_pose is the pose
  * after the start.  A start_pos[b] that is a rigid motion of the stored ligand pose hits the layer-0 message table; any other conformer
  * misses edge by edge and goes through the edge model (the rule of DFM_F_L0_TABLE).  DFM_E_INVALID, nothing enqueued: p NULL, t_begin
- * NaN, <= eps or > 1, num_steps < 2, inj->R0 or inj->tr_draw set (they belong to randomize_pose; the start is injected through rinj). */
+ * NaN, <= eps or > 1, num_steps < 2, inj->R0 or inj->tr_draw set (they belong to randomize_pose; the start is injected through rinj).
+ * start_pos is not checked: a start_pos[b] with a NaN or infinite coordinate gives trajectory b NaN outputs and leaves the others alone
+ * (rules 1-3 of "non-finite poses" above). */
 int dfm_refine(dfm_complex *cx, int B, int num_steps, float eps, float tr_noise_scale, float rot_noise_scale, uint32_t flags,
                uint64_t seed, const dfm_refine_params *p, const dfm_inject *inj_or_null, const dfm_refine_inject *rinj_or_null,
                dfm_traj_out *out);
@@ -918,7 +952,8 @@ int dfm_get_profile(const dfm_complex *cx, dfm_profile *p);
 /* Runs the stored pose of the complex (dfm_complex_create / dfm_complex_set_pose) through the fp32 engine and through the 16-bit
  * engine `flags` selects (DFM_F_MFMA16, the default when neither is given, or DFM_F_F16; DFM_F_BF16_OPS is honoured) on the same
  * n_eval (1..16) engine-drawn graphs at times t[n_eval] (NULL: spread over [1, 0.001]) and fills `out` (see dfm_selfcheck_out).
- * Costs one fp32 + one 16-bit batched evaluation of n_eval poses (about 0.1 s at 300+300); the drivers call it once per complex. */
+ * Costs one fp32 + one 16-bit batched evaluation of n_eval poses (about 0.1 s at 300+300); the drivers call it once per complex.
+ * The stored pose is finite by construction (rule 4 of "non-finite poses" above). */
 int dfm_complex_selfcheck(dfm_complex *cx, int n_eval, const float *t_or_null, uint64_t seed, uint32_t flags, dfm_selfcheck_out *out);
 
 /* which: 0 = R^3 (VE), 1 = SO(3) (logarithmic).  Returns DFM_E_INVALID for t outside [0,1] on SO(3). */

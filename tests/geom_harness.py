@@ -11,7 +11,11 @@ sampling race on a given array.  This module binds it and holds
     (float64 with the measured envelope of the hardware log2) and the native draws of k_init_pose carry a margin;
   * the comparisons the GPU tests use (check_knn, check_sampled, check_edge_codes, check_pairs, check_classification), which
     tests/test_geom_harness_cpu.py also turns on seeded mutants of the references to show that they have power;
-  * the input generators, so that the CPU tests can check the exclusion caps on the inputs the GPU tests use.
+  * the input generators, so that the CPU tests can check the exclusion caps on the inputs the GPU tests use;
+  * non-finite poses (include/dfmdock_amd.h, "non-finite poses in the trunk calls"): the geometries NONFINITE with a NaN or infinite
+    coordinate in one trajectory, the ordering rule of the graph as order_word / knn_ref / sample_ref(near=) / check_sampled, the
+    features and the table-hit predicate with IEEE comparisons, and present_selection - a word-level restatement of the selection
+    as it stood before the rule, kept as a named mutant.
 Out of scope: k_prep_pose is in the heads harness; k_restraint, k_igso3_cdf and k_start_pose each have a direct comparison with numpy
 or the reference (tests/test_gpu_restraints.py, tests/test_gpu_refine.py).
 
@@ -141,41 +145,127 @@ def degree_of(N, knn=20, nsamp=40):
 def dist32(ca):
     """|x_i - x_j| [N][N] in fp32 with the kernel's (and torch's op-by-op) order: sqrt((dx dx + dy dy) + dz dz)."""
     x, y, z = (np.ascontiguousarray(ca[:, k], f32) for k in range(3))
-    dx = x[:, None] - x[None, :]
-    acc = dx * dx
-    dx = y[:, None] - y[None, :]
-    acc += dx * dx
-    dx = z[:, None] - z[None, :]
-    acc += dx * dx
-    return np.sqrt(acc, out=acc)
+    with np.errstate(invalid="ignore"):      # non-finite coordinates: inf - inf and every operation on a NaN give NaN
+        dx = x[:, None] - x[None, :]
+        acc = dx * dx
+        dx = y[:, None] - y[None, :]
+        acc += dx * dx
+        dx = z[:, None] - z[None, :]
+        acc += dx * dx
+        return np.sqrt(acc, out=acc)
+
+
+NAN_WORD = 0x7F800001      # the one word of every NaN in the graph's order: just above +inf (0x7F800000)
+
+
+def order_word(d):
+    """The ordering rule of the graph (include/dfmdock_amd.h, non-finite poses) as one uint32 per distance: a number (>= +0, +inf
+    included) orders like its bit pattern; a NaN - either sign, any payload - orders after every number, and all NaN tie."""
+    d = np.ascontiguousarray(d, f32)
+    return np.where(np.isnan(d), np.uint32(NAN_WORD), d.view(np.uint32))
 
 
 def knn_ref(d, knn, mutant=None):
-    """The knn smallest (d, j) of every row in ascending order, the lowest j first on equal d: non-negative floats order like their bit
-    patterns, so (bits(d) << 32) | j is one sortable word per candidate.  mutant 'tie_high': the highest j first."""
+    """The knn smallest (d, j) of every row in ascending order, the lowest j first on equal d: (order_word(d) << 32) | j is one sortable
+    word per candidate (a NaN distance after every number, ties by ascending j).  Only residues j < N are candidates: there is no
+    padding here, so none can be taken.  mutant 'tie_high': the highest j first."""
     N = d.shape[1]
     j = np.arange(N, dtype=np.uint64)[None, :]
-    word = (np.ascontiguousarray(d, f32).view(np.uint32).astype(np.uint64) << np.uint64(32)) | (np.uint64(N - 1) - j if mutant == "tie_high" else j)
+    word = (order_word(d).astype(np.uint64) << np.uint64(32)) | (np.uint64(N - 1) - j if mutant == "tie_high" else j)
     low = np.sort(np.partition(word, knn - 1, axis=1)[:, :knn], axis=1) & np.uint64(0xFFFFFFFF)
     return (N - 1 - low if mutant == "tie_high" else low).astype(np.int32)
+
+
+def npl_of(N):
+    """Candidate slots per lane of the k_knn_sample instantiation that launch_knn_sample picks for N residues (64 NPL slots per node)."""
+    return 4 if N <= 256 else 8 if N <= 512 else 12 if N <= 768 else 16 if N <= 1024 else 32 if N <= 2048 else 64
+
+
+def present_select(keys, k):
+    """Word-level restatement of knn_select AS IT STOOD before the ordering rule: keys [slots] uint32, slot index = candidate index.  A
+    radix threshold from bit 30 down (bit 31 taken for clear), sel = key < threshold, ties at the k-th word by ascending candidate."""
+    keys = np.asarray(keys, np.uint32)
+    prefix = 0
+    for bit in range(30, -1, -1):
+        t = prefix | (1 << bit)
+        c = int((keys < t).sum())
+        if c == k:
+            return keys < t
+        if c < k:
+            prefix = t
+    sel = keys < prefix
+    tie = np.flatnonzero(keys == prefix)[:max(k - int(sel.sum()), 0)]
+    sel[tie] = True
+    return sel
+
+
+def present_selection(d, knn):
+    """The named mutant of knn_ref: the kNN slots [N][knn] of the selection as it stood, on the raw words of the fp32 distances d [N][N]
+    with +inf in the padding slots j >= N.  A selected padding slot comes out as its index j >= N; a slot that no winner was written to
+    (fewer than knn words below the threshold: the kernel read LDS rows nobody wrote) as -1.  On finite coordinates it IS knn_ref."""
+    N = d.shape[0]
+    slots = 64 * npl_of(N)
+    out = np.full((N, knn), -1, np.int32)
+    pad = np.full(slots - N, 0x7F800000, np.uint32)
+    for i in range(N):
+        keys = np.concatenate([np.ascontiguousarray(d[i], f32).view(np.uint32), pad])
+        win = np.flatnonzero(present_select(keys, knn))
+        win = win[np.lexsort((win, keys[win]))][:knn]      # ranked by (word, j) through LDS
+        out[i, :win.size] = win
+    return out
+
+
+def present_race(d, near, u, nsamp):
+    """The sampled slots [N][nsamp] of the race as it stood, through the same word-level present_select: the word of a slot is +inf when
+    it is a kNN winner, a padding slot OR at a distance whose word is +inf (`d != inf` was the test for "is a residue"), else the fp32
+    word of |log2 u| d^3 (numpy's log2 for the hardware's: the last bits of a key differ, the words that decide here are +inf and NaN).
+    Slots come out in candidate order, a missing one as -1."""
+    N = d.shape[0]
+    slots = 64 * npl_of(N)
+    out = np.full((N, nsamp), -1, np.int32)
+    with np.errstate(invalid="ignore"):
+        dc = np.where(d < f32(1e-10), f32(1e-10), d)
+        k2 = (np.abs(np.log2(f64(u))).astype(f32) * ((dc * dc) * dc)).astype(f32)
+    k2 = np.where(d == f32(np.inf), f32(np.inf), k2)
+    np.put_along_axis(k2, near.astype(np.int64), f32(np.inf), axis=1)
+    pad = np.full(slots - N, 0x7F800000, np.uint32)
+    for i in range(N):
+        win = np.flatnonzero(present_select(np.concatenate([k2[i].view(np.uint32), pad]), nsamp))[:nsamp]
+        out[i, :win.size] = win
+    return out
 
 
 def race_keys(d, near, u, envelope, mutant=None):
     """float64 race keys -log2(u_j) d_j^3 [n][N] (inf: not a candidate) and their error bounds.  d^3 as the kernel forms it, (d d) d in
     fp32 of the distance clamped at 1e-10; the kernel's key differs by the hardware log2 (envelope = (rel, abs)) and one fp32 product:
-    bound = 2 ((rel |log2 u| + abs) d^3 + 2 u key).  mutant 'all_keys': the kNN winners stay in the race."""
-    dc = np.maximum(d, f32(1e-10))
-    d3 = f64((dc * dc) * dc)
-    l2 = np.abs(np.log2(f64(u)))
-    key = l2 * d3
-    bound = 2.0 * ((envelope[0] * l2 + envelope[1]) * d3 + 2 * U * key)
+    bound = 2 ((rel |log2 u| + abs) d^3 + 2 u key).  mutant 'all_keys': the kNN winners stay in the race.
+    Non-finite distances: a NaN distance has a NaN key (the clamp d < 1e-10 ? 1e-10 : d keeps a NaN); a residue at +inf has the key
+    +inf, or NaN = 0 inf when its uniform is exactly 1.  check_sampled tells these from the +inf of a kNN winner by `near`."""
+    with np.errstate(invalid="ignore"):
+        dc = np.where(d < f32(1e-10), f32(1e-10), d)
+        d3 = f64((dc * dc) * dc)
+        l2 = np.abs(np.log2(f64(u)))
+        key = l2 * d3
+        bound = 2.0 * ((envelope[0] * l2 + envelope[1]) * d3 + 2 * U * key)
     if mutant != "all_keys":
         np.put_along_axis(key, near.astype(np.int64), np.inf, axis=1)
     return key, bound
 
 
-def sample_ref(key, nsamp, mutant=None):
-    """The nsamp smallest keys of every row as index lists [n][nsamp] (ascending key).  mutant 'largest': the 40 largest finite keys."""
+def sample_ref(key, nsamp, mutant=None, near=None):
+    """The nsamp smallest keys of every row as index lists [n][nsamp] (ascending key).  mutant 'largest': the 40 largest finite keys.
+    With `near` (the kNN slots: no candidates), by the ordering rule on any keys: the candidates with a number key in ascending
+    (key, j), +inf included; then the candidates with a NaN key in ascending j.  mutant 'nan_first': the NaN keys before the numbers."""
+    if near is not None:
+        n, N = key.shape
+        cls = np.isnan(key).astype(np.int64)
+        if mutant == "nan_first":
+            cls = 1 - cls
+        if near.shape[1]:
+            np.put_along_axis(cls, near.astype(np.int64), 2, axis=1)
+        k = np.where(cls == (1 if mutant == "nan_first" else 0), key, 0.0)
+        jj = np.broadcast_to(np.arange(N), (n, N))
+        return np.lexsort((jj, k, cls), axis=1)[:, :nsamp].astype(np.int32)
     if mutant == "largest":
         k = np.where(np.isfinite(key), -key, np.inf)
         return np.argsort(k, axis=1, kind="stable")[:, :nsamp].astype(np.int32)
@@ -188,15 +278,54 @@ def check_knn(got, ref):
 
 
 def check_sampled(got, near, key, bound, nsamp):
-    """got [n][nsamp]: the sampled slots.  They are distinct, disjoint from the kNN slots `near`, candidates (finite key), and as a set
-    the nsamp smallest keys: exactly at a DECIDED node (its nsamp-th and (nsamp+1)-th keys further apart than the sum of their bounds);
-    at an undecided node the symmetric difference lies within the ambiguous band.  Returns the number of undecided nodes."""
+    """got [n][nsamp]: the sampled slots of n nodes, every one a residue index.  A node all of whose candidates (the residues outside its
+    kNN slots `near`) have finite race keys - every node of a finite trajectory - goes through check_sampled_finite, exactly.  The others:
+      * fewer than nsamp candidates at a number distance (key not NaN): every one of them is among the sampled slots (numbers first);
+        nothing else is asked of the node but the range - the NaN candidates that fill it up may repeat;
+      * at least nsamp of them: the slots are distinct candidates with number keys and, as a set, the nsamp smallest (key, j) - +inf keys
+        (residues at infinity) tie and go by ascending j - exactly when the nsamp-th and the next key are decided, else within the band.
+    Returns the number of undecided nodes."""
     got = np.asarray(got, np.int64)
     n, N = key.shape
     assert got.shape == (n, nsamp)
     if nsamp == 0:
         return 0
     assert ((got >= 0) & (got < N)).all(), "a sampled slot is no residue index"
+    cand = np.ones((n, N), bool)
+    if near.shape[1]:
+        np.put_along_axis(cand, near.astype(np.int64), False, axis=1)
+    plain = (np.isfinite(key) | ~cand).all(1)
+    und = check_sampled_finite(got[plain], near[plain], key[plain], bound[plain], nsamp) if plain.any() else 0
+    jj = np.arange(N)
+    for r in np.flatnonzero(~plain):
+        num = cand[r] & ~np.isnan(key[r])
+        g = got[r]
+        if num.sum() < nsamp:
+            assert np.isin(jj[num], g).all(), f"node {r}: a candidate at a number distance was passed over for one at a NaN distance"
+            continue
+        assert np.unique(g).size == nsamp, f"node {r} has a sampled slot twice"
+        assert num[g].all(), f"node {r}: a sampled slot is a kNN slot or has a NaN key although {int(num.sum())} number keys are left"
+        idx = jj[num]
+        idx = idx[np.lexsort((idx, key[r, idx]))]
+        ref, lo = idx[:nsamp], key[r, idx[nsamp - 1]]
+        hi = key[r, idx[nsamp]] if idx.size > nsamp else np.inf
+        if not np.isfinite(hi) or hi - lo > bound[r, idx[nsamp - 1]] + bound[r, idx[nsamp]]:
+            assert set(g.tolist()) == set(ref.tolist()), f"decided node {r} differs from the nsamp smallest race keys"
+            continue
+        und += 1
+        fin = np.isfinite(key[r]) & num
+        band = fin & (key[r] + bound[r] >= lo - bound[r, idx[nsamp - 1]]) & (key[r] - bound[r] <= hi + bound[r, idx[nsamp]])
+        diff = np.zeros(N, bool)
+        diff[np.setxor1d(g, ref)] = True
+        assert not (diff & ~band).any(), f"undecided node {r}: a slot outside the ambiguous band differs"
+    return und
+
+
+def check_sampled_finite(got, near, key, bound, nsamp):
+    """got [n][nsamp]: the sampled slots.  They are distinct, disjoint from the kNN slots `near`, candidates (finite key), and as a set
+    the nsamp smallest keys: exactly at a DECIDED node (its nsamp-th and (nsamp+1)-th keys further apart than the sum of their bounds);
+    at an undecided node the symmetric difference lies within the ambiguous band.  Returns the number of undecided nodes."""
+    n, N = key.shape
     srt = np.sort(got, axis=1)
     assert (srt[:, 1:] != srt[:, :-1]).all(), "a node has a sampled slot twice"
     if near.shape[1]:
@@ -282,15 +411,18 @@ def pair_index(i, j, R, L, mutant=None):
 def edge_ref(n4, ca4, cb4, i, j, R, mask_dist, mutant=None):
     """Features of the ordered pairs (i, j) of ONE trajectory.  Exact (fp32 restatement): r2, the distance bin `bd`, relpos `rp`, the
     gate d < mask_dist and i != j.  Angles omega / theta / phi in float64 from the same fp32 inputs (`a64`) and in numpy fp32 (`a32`).
-    mutant 'ge': >= instead of > at the distance-bin boundaries."""
+    mutant 'ge': >= instead of > at the distance-bin boundaries.
+    Non-finite coordinates, with IEEE comparisons as the kernel makes them: a NaN distance passes no `>` (distance bin 0) and not the gate
+    (angle bins 0); a distance of +inf passes all 39 and not the gate; relpos is index arithmetic and stays exact; r2 is NaN or +inf."""
     i, j = np.asarray(i, np.int64), np.asarray(j, np.int64)
     n, ca, cb = (np.asarray(x, f32)[:, :3] for x in (n4, ca4, cb4))
-    dv = ca[i] - ca[j]
-    r2 = (dv[:, 0] * dv[:, 0] + dv[:, 1] * dv[:, 1]) + dv[:, 2] * dv[:, 2]
-    d = np.sqrt(r2)
-    cmp = np.greater_equal if mutant == "ge" else np.greater
-    bd = cmp(d[:, None], DIST_BOUNDS[None, :]).sum(1)
-    gate = (d < f32(mask_dist)) & (i != j)
+    with np.errstate(invalid="ignore"):
+        dv = ca[i] - ca[j]
+        r2 = (dv[:, 0] * dv[:, 0] + dv[:, 1] * dv[:, 1]) + dv[:, 2] * dv[:, 2]
+        d = np.sqrt(r2)
+        cmp = np.greater_equal if mutant == "ge" else np.greater
+        bd = cmp(d[:, None], DIST_BOUNDS[None, :]).sum(1)
+        gate = (d < f32(mask_dist)) & (i != j)
     same = (i < R) == (j < R)
     rp = np.where(same, np.clip(i - j + 32, 0, 64), 65)
     out = dict(r2=r2, bd=bd, rp=rp, gate=gate)
@@ -330,12 +462,20 @@ def angle_undecided(ref, m):
     return out
 
 
+def assert_same_f32(got, want):
+    """Bit for bit, +inf / -inf included; where `want` is NaN, `got` is a NaN (sign and payload of a NaN are not part of any contract)."""
+    got, want = np.ascontiguousarray(got, f32), np.ascontiguousarray(want, f32)
+    nan = np.isnan(want)
+    np.testing.assert_array_equal(np.isnan(got), nan)
+    np.testing.assert_array_equal(got.view(np.uint32)[~nan], want.view(np.uint32)[~nan])
+
+
 def check_edge_codes(codes, radial, ref, m):
     """codes / radial of a launch against edge_ref: radial, distance bin and relpos exact; masked pairs have the three angle bins 0; a
     decided angle has the float64 bin (NaN: 0); an undecided one has one of the bins within m of it (across the +-180 wrap for the
     dihedrals).  Returns the number of undecided edges."""
     f = unpack_code(codes)
-    np.testing.assert_array_equal(np.asarray(radial, f32).view(np.uint32), ref["r2"].view(np.uint32))
+    assert_same_f32(radial, ref["r2"])
     np.testing.assert_array_equal(f["bd"], ref["bd"])
     np.testing.assert_array_equal(f["rp"], ref["rp"])
     und = angle_undecided(ref, m)
@@ -377,8 +517,11 @@ def check_pairs(code0, rows, R, L, codes, radial, mutant=None):
 
 def check_graph(edges, ca4, knn, nsamp, seed, stream, envelope, cap=0.02):
     """edges [B][N][knn + nsamp] of one k_knn_sample launch: kNN slots exact (check_knn), sampled slots against the float64 race with the
-    given log2 envelope (check_sampled: decided nodes exactly).  At most cap B N nodes may be undecided; returns their number."""
+    given log2 envelope (check_sampled: decided nodes exactly).  At most cap B N nodes may be undecided; returns their number.
+    Whatever the coordinates, every edge is a residue index, and the order is the ordering rule of the graph (order_word)."""
     B, N = ca4.shape[:2]
+    edges = np.asarray(edges)
+    assert ((edges >= 0) & (edges < N)).all(), "an edge is no residue index"
     und = 0
     for b in range(B):
         d = dist32(ca4[b, :, :3])
@@ -391,6 +534,19 @@ def check_graph(edges, ca4, knn, nsamp, seed, stream, envelope, cap=0.02):
     return und
 
 
+def ref_graph(ca4, knn, nsamp, seed, stream):
+    """The reference's own edges [B][N][knn + nsamp] by the ordering rule, float64 race keys: in-range index lists for the kernels
+    downstream of k_knn_sample that owe nothing to the kernel under test."""
+    B, N = ca4.shape[:2]
+    out = np.zeros((B, N, knn + nsamp), np.int32)
+    for b in range(B):
+        d = dist32(ca4[b, :, :3])
+        near = knn_ref(d, knn)
+        key, _ = race_keys(d, near, edge_stream_u(b * N + np.arange(N), N, stream, seed), LOG2_ENVELOPE)
+        out[b] = np.concatenate([near, sample_ref(key, nsamp, near=near)], 1)
+    return out
+
+
 def hit_ref(i, j, codes, radial, code0, R, L, mutant=None):
     """The table-hit predicate of k_edge_feat<1>: both residues of one chain, the entry's code equal, |r2_entry - r2| <= 1e-3 max(sqrt(r2),
     1) in fp32.  mutant 'no_sqrt': tolerance 1e-3.  Returns (hit, pair index)."""
@@ -399,8 +555,11 @@ def hit_ref(i, j, codes, radial, code0, R, L, mutant=None):
     idx = np.where(same, pair_index(i, j, R, L), 0)
     c0 = np.asarray(code0, np.uint32).reshape(-1, 2)[idx]
     r2 = np.asarray(radial, f32)
-    tol = f32(1e-3) * (f32(1.0) if mutant == "no_sqrt" else np.maximum(np.sqrt(r2), f32(1.0)))
-    hit = same & (c0[:, 0] == np.asarray(codes, np.uint32)) & (np.abs(c0[:, 1].copy().view(f32) - r2) <= tol)
+    with np.errstate(invalid="ignore"):      # a pair whose r2 is NaN or inf is never a hit (mutant 'inf_hits': inf <= inf passes)
+        tol = f32(1e-3) * (f32(1.0) if mutant == "no_sqrt" else np.maximum(np.sqrt(r2), f32(1.0)))
+        hit = same & (c0[:, 0] == np.asarray(codes, np.uint32)) & (np.abs(c0[:, 1].copy().view(f32) - r2) <= tol)
+    if mutant != "inf_hits":
+        hit &= np.isfinite(r2)
     return hit, idx
 
 
@@ -516,7 +675,52 @@ def coincident_coords(B, N, seed=0):
     return ca
 
 
-COORDS = {"chain": chain_coords, "lattice": lattice_coords, "coincident": coincident_coords}
+def _words(*w):
+    return np.array(w, np.uint32).view(f32)
+
+
+def bad_trajectory(B):
+    """The one trajectory of a non-finite geometry that holds the non-finite coordinates: 1 (of B = 3), 0 when there is one only."""
+    return min(1, B - 1)
+
+
+def _nonfinite(fill):
+    def make(B, N, seed=0):
+        ca = chain_coords(B, N, seed)
+        fill(ca[bad_trajectory(B)], N // 2, N)
+        return ca
+    return make
+
+
+def _nan_residue(ca, R, N):
+    ca[R + (N - R) // 3, 1] = np.nan      # one coordinate of one ligand CA
+
+
+def _inf_residue(ca, R, N):
+    ca[R // 2, 0] = np.inf                # one receptor residue at +inf, one ligand residue at -inf
+    ca[N - 1, 2] = -np.inf
+
+
+def _ligand(*words):
+    def fill(ca, R, N):
+        ca[R:, :3] = _words(*words)[(np.arange(N - R)[:, None] + np.arange(3)[None, :]) % len(words)]      # rotated from residue to residue
+    return fill
+
+
+# Non-finite geometries (trajectory bad_trajectory(B) of the random chain; the others stay finite).  R = N // 2 is the receptor.
+NONFINITE = {"nan_residue": _nonfinite(_nan_residue),                             # one CA of the ligand half is NaN
+             "nan_ligand": _nonfinite(_ligand(0x7FC00000)),                       # every coordinate behind R is +NaN
+             "neg_nan_ligand": _nonfinite(_ligand(0xFFC00000)),                   # ... is the NaN with the sign bit set
+             "payload_nan": _nonfinite(_ligand(0x7F800001, 0xFFBFFFFF, 0x7FFFFFFF)),      # signalling, negative, all ones
+             "inf_residue": _nonfinite(_inf_residue)}
+COORDS = {"chain": chain_coords, "lattice": lattice_coords, "coincident": coincident_coords, **NONFINITE}
+NONFINITE_SIZES = (16, 40, 214, 255, 256, 257, 600, 1030)      # 16: the degree clamps; 1030: NPL = 32, the vector-pipe count
+NONFINITE_DEGREES = ((20, 40), (60, 0))
+
+
+def finite_twin(kind, B, N, seed=0):
+    """The same launch with the bad trajectory made finite: the chain the non-finite geometry was cut from."""
+    return chain_coords(B, N, seed)
 
 KNN_SIZES_SMALL = (1, 19, 20, 21, 59, 60, 61)
 KNN_SIZES_LARGE = (256, 257, 512, 513, 768, 769, 1024, 1025, 2048, 2049)
@@ -566,7 +770,8 @@ def backbone(ca4, seed=0, collinear=()):
     def off(r):
         v = rng.standard_normal(ca.shape)
         return (v * (r / np.linalg.norm(v, axis=-1, keepdims=True))).astype(f32)
-    n, c = ca + off(1.46), ca + off(1.52)
+    with np.errstate(invalid="ignore"):      # (a signalling NaN among the coordinates)
+        n, c = ca + off(1.46), ca + off(1.52)
     for k in collinear:
         n[:, k] = ca[:, k] + np.array([-1.5, 0, 0], f32)
         c[:, k] = ca[:, k] + np.array([1.5, 0, 0], f32)
@@ -578,9 +783,10 @@ def backbone_from_pos(pos):
     c = C - Ca, a = b x c (coords6d.py:71-75), in fp32 in the engine's expression order."""
     pos = np.asarray(pos, f32)
     n, ca, c = pos[..., 0, :], pos[..., 1, :], pos[..., 2, :]
-    b, cc = ca - n, c - ca
-    a = _cross(b, cc)
-    cb = ((f32(-0.58273431) * a + f32(0.56802827) * b) - f32(0.54067466) * cc) + ca
+    with np.errstate(invalid="ignore"):
+        b, cc = ca - n, c - ca
+        a = _cross(b, cc)
+        cb = ((f32(-0.58273431) * a + f32(0.56802827) * b) - f32(0.54067466) * cc) + ca
     pad = lambda x: np.concatenate([x, np.zeros(x.shape[:-1] + (1,), f32)], -1).astype(f32)
     return pad(n), pad(ca), pad(cb)
 

@@ -4,6 +4,7 @@
 //       rc, then ts / dt / g / sigma as hex doubles and every StepParams field of every step as bits
 //   schedule_main sel                  EngineSel (and table_by_default) of the 16 combinations of the four engine flags
 //   schedule_main key B FLAGS L0 RESTR [B FLAGS L0 RESTR ...]      graph_key of each
+//   schedule_main finite N [OFFSET:HEXWORD ...]      first_nonfinite of N finite floats with the listed words planted
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -82,6 +83,20 @@ int main(int argc, char **argv)
                                                                atoi(argv[k + 3]) != 0));
         return 0;
     }
-    fprintf(stderr, "usage: %s grid ... | sel | key ...\n", argv[0]);
+    if (argc >= 3 && !strcmp(argv[1], "finite")) {      // its own heap block of exactly N floats: a scan past it is a sanitizer report
+        const size_t n = (size_t)strtoull(argv[2], nullptr, 10);
+        float *x = n ? static_cast<float *>(malloc(n * sizeof(float))) : nullptr;
+        if (n && !x) return 3;
+        for (size_t k = 0; k < n; ++k) x[k] = 1.0f + (float)(k % 7);
+        for (int a = 3; a < argc; ++a) {
+            unsigned long long off = 0; unsigned int word = 0;
+            if (sscanf(argv[a], "%llu:%x", &off, &word) != 2 || off >= n) { free(x); return 2; }
+            std::memcpy(x + off, &word, 4);
+        }
+        printf("%zu\n", dfm::first_nonfinite(x, n));
+        free(x);
+        return 0;
+    }
+    fprintf(stderr, "usage: %s grid ... | sel | key ... | finite N [OFFSET:HEXWORD ...]\n", argv[0]);
     return 2;
 }

@@ -2,7 +2,9 @@
 the shim builds and links against the library's launchers; the numpy Philox and u01 equal the library's host functions bit for bit; the
 references agree with the project's CPU oracle on a small complex; each seeded mutant of a reference is rejected by the very comparison
 the GPU tests use; the exclusion caps (undecided nodes <= 2 %, undecided edges <= 1 %) hold on the GPU tests' own inputs; u01 is
-monotone with smallest value 2^-25 and largest value exactly 1.0f."""
+monotone with smallest value 2^-25 and largest value exactly 1.0f.  Non-finite poses: the ordering rule of the graph against a plain
+Python sort; the selection as it stood before the rule (present_selection) is rejected on every non-finite geometry and accepted on the
+three finite ones; the features and the table-hit predicate on NaN and infinite coordinates."""
 
 import numpy as np
 import pytest
@@ -123,7 +125,7 @@ def graph_ref(ca4, knn, nsamp, seed, stream, tie=None, race=None, pick=None):
         d = gh.dist32(ca4[b, :, :3])
         near = gh.knn_ref(d, knn, tie)
         key, _ = gh.race_keys(d, near, gh.edge_stream_u(b * N + np.arange(N), N, stream, seed), gh.LOG2_PROVISIONAL, race)
-        out[b] = np.concatenate([near, gh.sample_ref(key, nsamp, pick)], 1)
+        out[b] = np.concatenate([near, gh.sample_ref(key, nsamp, pick, near=None if np.isfinite(d).all() else near)], 1)
     return out
 
 
@@ -253,3 +255,154 @@ def test_batches_cover_the_early_wave_exit():
     cls = lambda N: 4 if N <= 256 else 8 if N <= 512 else 12 if N <= 768 else 16 if N <= 1024 else 32 if N <= 2048 else 64
     seen = {cls(c[1]) for c in gh.knn_cases() if (c[1] * c[2]) % 4}
     assert seen == {4, 8, 12, 16, 32, 64}
+
+
+# ---- non-finite poses: the ordering rule of the graph, the selection as it stood as a named mutant ------------------------------------
+MUTANT_SIZES = (40, 214, 257, 600)
+
+
+def rule5_rows(d, knn, rows):
+    """The ordering rule written out with Python's sort, independent of knn_ref's packed word: numbers by (d, j), then NaN by j."""
+    return np.array([sorted(range(d.shape[1]), key=lambda j: (bool(np.isnan(d[i, j])), 0.0 if np.isnan(d[i, j]) else float(d[i, j]), j))[:knn]
+                     for i in rows], np.int32)
+
+
+@pytest.mark.parametrize("N", MUTANT_SIZES)
+@pytest.mark.parametrize("kind", sorted(gh.NONFINITE))
+def test_present_selection_is_rejected_on_non_finite_poses(kind, N):
+    """knn_ref follows the ordering rule (against a plain Python sort, on the nodes that see a non-finite distance and on a sample of the
+    others).  The selection as it stood (gh.present_selection: words of the raw distances, +inf in the padding slots) is rejected by the
+    comparison the GPU tests use, on the trajectory that holds the non-finite coordinates.  Where a node has fewer than knn number
+    distances it takes padding slots (j >= N) or, with the sign bit set in every word, nothing at all - check_knn alone rejects that.
+    inf_residue has ONE NaN per row (inf - inf, the residue at infinity against itself), which orders above the padding just as the
+    rule asks, and the +inf distances tie with the padding by ascending index with the residues first: its kNN slots are right, and the
+    assertion below says so.  Its defect is in the race - `d != inf` took every residue at infinity, and from it every other residue,
+    for no candidate and the kNN winners were drawn a second time - and check_sampled rejects the race as it stood
+    (gh.present_race: the same word-level selection on the old race words)."""
+    B, knn = 3, 20
+    ca4 = gh.COORDS[kind](B, N, seed=N)
+    b = gh.bad_trajectory(B)
+    assert not np.isfinite(ca4[b]).all() and np.isfinite(np.delete(ca4, b, 0)).all()
+    d = gh.dist32(ca4[b, :, :3])
+    ref = gh.knn_ref(d, knn)
+    rows = np.unique(np.concatenate([np.flatnonzero(~np.isfinite(d).all(1))[:40], np.arange(0, N, 37)]))
+    np.testing.assert_array_equal(ref[rows], rule5_rows(d, knn, rows))
+    gh.check_knn(ref, ref)
+    bad = gh.present_selection(d, knn)
+    if kind == "inf_residue":
+        gh.check_knn(bad, ref)
+        nsamp = min(40, N - knn)
+        u = gh.edge_stream_u(b * N + np.arange(N), N, 3, 0x1234567899ABCDEF)
+        key, bound = gh.race_keys(d, ref, u, gh.LOG2_PROVISIONAL)
+        assert gh.check_sampled(gh.sample_ref(key, nsamp, near=ref), ref, key, bound, nsamp) == 0
+        # the race as it stood, word for word through present_select: it is right on the nodes that see the two residues at infinity
+        # from afar, and wrong on those two nodes - every word of their rows is +inf, the ties go by index from slot 0 on, and the
+        # kNN winners are drawn a second time
+        old = gh.present_race(d, ref, u, nsamp)
+        rows = np.flatnonzero(np.isinf(d).sum(1) > 2)
+        assert rows.size == 2 and ((old[rows][:, :, None] == ref[rows][:, None, :]).any(2)).any()
+        with pytest.raises(AssertionError):
+            gh.check_sampled(old, ref, key, bound, nsamp)
+    else:
+        with pytest.raises(AssertionError):
+            gh.check_knn(bad, ref)
+        assert (bad >= N).any() or (bad < 0).any(), "the defect is an index out of range or a slot never written"
+
+
+@pytest.mark.parametrize("N", MUTANT_SIZES + (256,))
+@pytest.mark.parametrize("kind", ("chain", "lattice", "coincident"))
+def test_present_selection_is_accepted_on_finite_poses(kind, N):
+    """On the three finite geometries the selection as it stood IS the reference (ties at the knn-th distance and coincident residues
+    included): the extended comparison sees the defect and nothing else."""
+    ca4 = gh.COORDS[kind](1, N, seed=N)
+    d = gh.dist32(ca4[0, :, :3])
+    gh.check_knn(gh.present_selection(d, 20), gh.knn_ref(d, 20))
+
+
+def test_issue_table_of_the_present_selection():
+    """One NaN node, knn = 20: 20 of 20 picks in the padding at N = 40, 214, 600 (largest j = N + 19) with either sign; at N = 256 (no
+    padding) the picks are in range with a positive NaN and NOTHING is picked with the sign bit set."""
+    for N, neg in ((40, 0), (40, 1), (214, 0), (214, 1), (600, 0), (600, 1), (256, 0), (256, 1)):
+        keys = np.full(64 * gh.npl_of(N), 0x7F800000, np.uint32)
+        keys[:N] = 0xFFC00000 if neg else 0x7FC00000
+        win = np.flatnonzero(gh.present_select(keys, 20))
+        if N == 256:
+            assert (win.size == 0) if neg else (win.tolist() == list(range(20)))
+        else:
+            assert win.tolist() == list(range(N, N + 20))
+
+
+@pytest.mark.parametrize("kind", sorted(gh.NONFINITE))
+def test_graph_reference_and_mutants_on_non_finite_poses(kind):
+    """The reference's own graph passes check_graph on every non-finite geometry (N = 40: fewer than nsamp number candidates on the nodes
+    of the NaN ligand; N = 214: enough of them).  Rejected: NaN candidates drawn before the numbers; an edge out of range; on the
+    finite trajectories, the old mutants still (ties broken high)."""
+    args = (0x1234567899ABCDEF, 3)
+    for N in (40, 214):
+        knn, nsamp = gh.degree_of(N)
+        ca4 = gh.COORDS[kind](3, N, seed=N)
+        good = graph_ref(ca4, knn, nsamp, *args)
+        assert graph_check(good, ca4, knn, nsamp, *args) <= 0.02 * 3 * N
+        b = gh.bad_trajectory(3)
+        d = gh.dist32(ca4[b, :, :3])
+        near = gh.knn_ref(d, knn)
+        key, _ = gh.race_keys(d, near, gh.edge_stream_u(b * N + np.arange(N), N, args[1], args[0]), gh.LOG2_PROVISIONAL)
+        cand_nan = np.isnan(key)
+        np.put_along_axis(cand_nan, near.astype(np.int64), False, axis=1)
+        bad = good.copy()
+        bad[b, :, knn:] = gh.sample_ref(key, nsamp, "nan_first", near=near)
+        differs = (np.sort(bad[b, :, knn:], 1) != np.sort(good[b, :, knn:], 1)).any()
+        # (at N = 40, K = N: every candidate of a node is drawn, in whichever order)
+        assert cand_nan.any() and (differs or N == 40)
+        if differs:
+            with pytest.raises(AssertionError):
+                graph_check(bad, ca4, knn, nsamp, *args)
+        bad = good.copy()
+        bad[b, N - 1, knn + nsamp - 1] = N
+        with pytest.raises(AssertionError):
+            graph_check(bad, ca4, knn, nsamp, *args)
+        bad = good.copy()
+        bad[0] = graph_ref(ca4[:1], knn, nsamp, *args, tie="tie_high")[0]
+        if (bad[0] != good[0]).any():
+            with pytest.raises(AssertionError):
+                graph_check(bad, ca4, knn, nsamp, *args)
+
+
+def test_edge_reference_on_non_finite_poses():
+    """edge_ref and hit_ref with IEEE comparisons: on an edge that touches a NaN residue every `>` count is 0 (distance bin 0, angle bins
+    0: the gate d < mask_dist fails), on one that touches a residue at infinity the distance bin is 39 and the gate fails; relpos is exact;
+    radial is NaN resp. +inf; such a pair is never a table hit - also not against an entry that holds the very same code and r2 bits
+    (mutant 'inf_hits', the comparison inf <= inf: rejected by check_classification)."""
+    N, R, K = 40, 20, 40
+    for kind in sorted(gh.NONFINITE):
+        ca4 = gh.COORDS[kind](1, N, seed=N)
+        n4, ca4, cb4 = gh.backbone(ca4, seed=2)
+        badres = ~np.isfinite(ca4[0, :, :3]).all(1)
+        i, j = np.repeat(np.arange(N), K), np.tile(np.arange(K), N)
+        ref = gh.edge_ref(n4[0], ca4[0], cb4[0], i, j, R, 22.0)
+        touch = badres[i] | badres[j]
+        assert touch.any() and (~touch).any()
+        assert not np.isfinite(ref["r2"][touch]).any() and np.isfinite(ref["r2"][~touch]).all()
+        assert not ref["gate"][touch].any()
+        nan = np.isnan(ref["r2"])
+        assert (ref["bd"][nan] == 0).all() and (ref["bd"][np.isinf(ref["r2"])] == 39).all()
+        same = (i < R) == (j < R)
+        np.testing.assert_array_equal(ref["rp"], np.where(same, np.clip(i - j + 32, 0, 64), 65))
+        codes = (ref["bd"] | ref["rp"] << 20).astype(np.uint32)
+        P = R * R + (N - R) * (N - R)
+        code0 = np.zeros((P, 2), np.uint32)
+        q = gh.pair_index(i[same], j[same], R, N - R)
+        # the entry of every pair IS this pose's record; a pair at infinity has the entry of a finite pair beyond the last bin (100 A)
+        code0[q, 0], code0[q, 1] = codes[same], np.where(np.isinf(ref["r2"][same]), np.float32(1e4), ref["r2"][same]).view(np.uint32)
+        hit, idx = gh.hit_ref(i, j, codes, ref["r2"], code0, R, N - R)
+        assert not hit[touch].any() and hit[same & ~touch].all()
+        if kind == "inf_residue":
+            loose, _ = gh.hit_ref(i, j, codes, ref["r2"], code0, R, N - R, mutant="inf_hits")
+            assert (loose & ~hit).any()
+            src = np.where(loose, idx, 0).astype(np.uint32)
+            at = np.cumsum(~loose) - 1
+            src[~loose] = gh.MISS | at[~loose].astype(np.uint32)
+            rows = np.full((i.size, 4), 0xFFFFFFFF, np.uint32)
+            rows[at[~loose]] = np.stack([i, j, codes, ref["r2"].view(np.uint32)], 1).astype(np.uint32)[~loose]
+            with pytest.raises(AssertionError):
+                gh.check_classification(src, rows, int((~loose).sum()), 0, i, j, codes, ref["r2"], hit, idx)

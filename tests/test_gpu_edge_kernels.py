@@ -595,6 +595,39 @@ def test_l0_gather(h, fp32, K):
     assert np.array_equal(agg1[0].view(np.uint32), agg[0].view(np.uint32))
 
 
+@pytest.mark.parametrize("fp32", [0, 1])
+def test_l0_gather_non_finite_rows(h, fp32):
+    """Rows of the row list whose message is NaN (the rows of edges with a NaN radial: a non-finite pose): exactly the nodes that own
+    such a row become NaN, every other node - of the same and of the other trajectories - keeps its bits, the counter ends at zero."""
+    rng = np.random.default_rng(77 + fp32)
+    B, N, K, P, M = 3, 23, 13, 97, 41
+    tab = (rng.standard_normal((P, H)) * 0.3).astype(np.float32)
+    X = (rng.standard_normal((M, H)) * 0.3).astype(np.float32)
+    Xn = X.copy()
+    nanrows = np.array([0, 7, 40])
+    Xn[nanrows] = np.nan
+    Xn[19, 100] = np.nan      # one channel only
+    nanrows = np.append(nanrows, 19)
+    if not fp32:
+        tab, X, Xn = dh.f2h(tab), dh.f2h(X), dh.f2h(Xn)
+    miss = rng.random((B, N, K)) < 0.3
+    src = np.where(miss, eh.L0_MISS | rng.integers(0, M, (B, N, K)), rng.integers(0, P, (B, N, K))).astype(np.uint32)
+
+    def launch(x):
+        r = run(h, {"op": "l0_gather32" if fp32 else "l0_gather",
+                    "bufs": {"table": tab, "X": x, "src": src, "agg": Out(np.float32, B * N * H), "counter": io(np.array([7], np.uint32)),
+                             "miss_total": io(np.array([100], np.uint64))}, "scalars": dict(B=B, N=N, K=K)})
+        assert r["counter"][0] == 0 and r["miss_total"][0] == 107
+        return r["agg"].reshape(B, N, H)
+
+    good, bad = launch(X), launch(Xn)
+    owns = (miss & np.isin(src & 0x7fffffff, nanrows)).any(2)
+    assert owns.any() and (~owns).any() and np.isfinite(good).all()
+    assert np.isnan(bad[owns]).any(-1).all() and np.array_equal(bad[~owns].view(np.uint32), good[~owns].view(np.uint32))
+    full = (miss & np.isin(src & 0x7fffffff, nanrows[:3])).any(2)
+    assert np.isnan(bad[full]).all()
+
+
 # ---- special values ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kernel", ["bf16_A32", "bf16_A16", "f16_A32", "f16_A16", "f32"])
 def test_nan_reaches_every_output(h, layer, kernel):

@@ -22,6 +22,13 @@ correctly rounded fp32 in the order written, which numpy float32 reproduces bit 
                         normal z = r cos(2 pi u_b), r = sqrt(-2 ln u_a), carries dz = r (4 pi + 4) u + 3 u |z| + 2 u r (logf 1 ulp, sqrtf,
                         two roundings of the argument, cosf 2 ulp, the product); dR = 4 max dz / |q| + 2 u enters the same formulas;
                         trajectories whose first uniform is below 2^-20 are excluded.
+  non-finite poses      five geometries with a NaN or infinite coordinate in one trajectory of three (geom_harness.NONFINITE).  No new
+                        margin: the graph follows the ordering rule of include/dfmdock_amd.h (a NaN distance after every number, ties by
+                        ascending j, numbers first in the race: geom_harness.order_word / check_sampled), every edge is a residue index,
+                        codes / radial / row list / counter are the IEEE restatement (radial NaN by isnan, +inf by its bits), a pair
+                        with a non-finite r2 is no table hit, and the finite trajectories have the bits of the launch on the finite
+                        twin.  tests/test_geom_harness_cpu.py shows that the selection as it stood before the rule is rejected on
+                        these geometries and accepted on the finite ones.
 The largest |error| / bound of every toleranced test and the measured log2 envelope go to $DFM_GEOM_PROFILE/geom_kernels_gpu.txt when that
 variable names a directory (profiles/geom_kernels.txt holds the MI355X figures).
 """
@@ -290,6 +297,113 @@ def test_edge_feat_classification_quiet_first_workgroup_and_all_miss(h):
     assert n == hit.size and not hit.any()
 
 
+# ---- 3b: non-finite poses (include/dfmdock_amd.h: in range, contained, the ordering rule of the graph) -----------------------------------
+# Every launch here gets the arrays the test built and writes only its own guarded blocks: nothing follows an edge as an index.
+@pytest.mark.parametrize("N", gh.NONFINITE_SIZES)
+@pytest.mark.parametrize("kind", sorted(gh.NONFINITE))
+def test_knn_sample_non_finite(h, kind, N):
+    """B = 3 with the non-finite coordinates in trajectory 1 (one NaN CA; a ligand half of +NaN, of NaN with the sign bit, of signalling /
+    negative / all-ones NaN; one residue at +inf and one at -inf), N on both sides of 256 and N = 16 (the degree clamps), 600 and 1030
+    (NPL = 12, and 32: the count on the vector pipe), degrees (20, 40) and (60, 0), seed and evaluation index as arguments and from
+    ctl.  The graph follows the ordering rule (check_graph: a NaN distance after every number, ties by ascending j; numbers first in
+    the race), every edge is a residue index, and trajectories 0 and 2 have the bits of the same launch with trajectory 1 finite."""
+    B = 3
+    ca4 = gh.COORDS[kind](B, N, seed=N)
+    twin = gh.finite_twin(kind, B, N, seed=N)
+    b = gh.bad_trajectory(B)
+    keep = [t for t in range(B) if t != b]
+    assert np.array_equal(ca4[keep], twin[keep]) and not np.isfinite(ca4[b]).all()
+    ctl = np.array([STREAM, SEED & 0xFFFFFFFF, SEED >> 32], np.uint32)
+    for deg in gh.NONFINITE_DEGREES:
+        knn, nsamp = gh.degree_of(N, *deg)
+        edges = knn_launch(h, ca4, knn, nsamp)
+        assert ((edges >= 0) & (edges < N)).all(), f"edges up to {edges.max()} of N = {N}"
+        check_graph(edges, ca4, knn, nsamp)
+        ref = knn_launch(h, twin, knn, nsamp)
+        np.testing.assert_array_equal(edges[keep], ref[keep])
+        np.testing.assert_array_equal(knn_launch(h, ca4, knn, nsamp, seed=99, stream=77, ctl=ctl), edges)
+
+
+def nonfinite_pose(kind, N, B=3):
+    """(n4, ca4, cb4) of a non-finite geometry and of its finite twin (the same backbone offsets), and the bad trajectory."""
+    bad = gh.backbone(gh.COORDS[kind](B, N, seed=N), seed=2)
+    twin = gh.backbone(gh.finite_twin(kind, B, N, seed=N), seed=2)
+    return bad, twin, gh.bad_trajectory(B)
+
+
+@pytest.mark.parametrize("N", (40, 214))
+@pytest.mark.parametrize("kind", sorted(gh.NONFINITE))
+def test_edge_feat_non_finite(h, kind, N):
+    """k_edge_feat<0> on the reference's own graph of a non-finite pose (in-range edges by the ordering rule, not the kernel's): codes and
+    radial are the IEEE restatement (a NaN distance: bin 0 and no angle; +inf: bin 39 and no angle; relpos exact; radial NaN or +inf), and
+    the two finite trajectories have the bits of the launch on the finite twin."""
+    (n4, ca4, cb4), (tn, tca, tcb), b = nonfinite_pose(kind, N)
+    knn, nsamp = gh.degree_of(N)
+    c = dict(n4=n4, ca4=ca4, cb4=cb4, edges=gh.ref_graph(ca4, knn, nsamp, SEED, STREAM), B=3, N=N, R=N // 2, K=knn + nsamp, mask_dist=22.0)
+    r = feat_launch(h, c)
+    ref = gh.edge_case_ref(c)
+    und = gh.check_edge_codes(r["codes"], r["radial"], ref, gh.angle_margin(ref))
+    assert und <= 0.01 * ref["gate"].size
+    _, i, j = gh.edge_ij(c["edges"], N, c["K"])
+    tb = np.repeat(np.arange(3), N * c["K"])
+    badres = ~np.isfinite(ca4[b, :, :3]).all(1)
+    touch = (tb == b) & (badres[i] | badres[j])
+    assert touch.any() and not np.isfinite(r["radial"][touch]).any() and np.isfinite(r["radial"][~touch]).all()
+    f = gh.unpack_code(r["codes"])
+    assert not (f["om"][touch] | f["th"][touch] | f["ph"][touch]).any()
+    t = feat_launch(h, dict(c, n4=tn, ca4=tca, cb4=tcb))
+    for k in ("codes", "radial"):
+        np.testing.assert_array_equal(r[k].view(np.uint32)[tb != b], t[k].view(np.uint32)[tb != b])
+
+
+@pytest.mark.parametrize("N", (40, 600))
+@pytest.mark.parametrize("kind", sorted(gh.NONFINITE))
+def test_edge_feat_classification_non_finite(h, kind, N):
+    """k_edge_feat<1> on the non-finite trajectory against the table entries of the FINITE pose it was cut from (k_l0_pairs on the twin: the
+    stored pose of a complex is always finite): every edge that touches a non-finite residue is a miss - also the pair at +inf whose entry
+    holds the same code, a finite pair beyond the last distance bin (inf <= inf would pass; planted at N = 40) -, every other intra-chain
+    edge a hit; row
+    list, src and counter as the restatement has them, the counter = the number of misses.  And k_l0_pairs on the non-finite pose itself:
+    records of every pair at their index, codes and radial those of k_edge_feat<0>."""
+    (n4, ca4, cb4), (tn, tca, tcb), b = nonfinite_pose(kind, N)
+    R = N // 2
+    knn, nsamp = gh.degree_of(N)
+    K = knn + nsamp
+    edges = gh.ref_graph(ca4[b:b + 1], knn, nsamp, SEED, STREAM)
+    if kind == "inf_residue":      # the ligand residue at -inf against the ligand residue that the finite pose has furthest from it (54 A at N = 600)
+        edges[0, N - 1, K - 1] = R + int(np.argmax(gh.dist32(tca[b, :, :3])[N - 1, R:]))
+    c = dict(n4=n4[b:b + 1], ca4=ca4[b:b + 1], cb4=cb4[b:b + 1], edges=edges, B=1, N=N, R=R, L=N - R, K=K, mask_dist=22.0)
+    code0 = pairs_launch(h, dict(c, n4=tn[b:b + 1], ca4=tca[b:b + 1], cb4=tcb[b:b + 1]))["code0"].reshape(-1, 2)
+    if kind == "inf_residue" and N == 40:
+        # no pair of 20 residues lies beyond the last distance bin (50.75 A): the entry of the planted pair is made that of one at 100 A
+        # (distance bin 39, no angle, the pair's relpos), which is what a larger complex holds there (N = 600 has it by itself)
+        far = int(edges[0, N - 1, K - 1])
+        code0 = code0.copy()
+        code0[gh.pair_index(N - 1, far, R, N - R)] = (39 | int(np.clip(N - 1 - far + 32, 0, 64)) << 20, np.array([1e4], np.float32).view(np.uint32)[0])
+    r = feat_launch(h, c, cls=dict(code0=code0, capacity=N * K, start=0))
+    ref = gh.edge_case_ref(c)
+    gh.check_edge_codes(r["codes"], r["radial"], ref, gh.angle_margin(ref))
+    _, i, j = gh.edge_ij(edges, N, K)
+    hit, idx = gh.hit_ref(i, j, r["codes"], r["radial"], code0, R, N - R)
+    misses = gh.check_classification(r["src"], r["rows"].reshape(-1, 4), r["counter"][0], 0, i, j, r["codes"], r["radial"], hit, idx)
+    badres = ~np.isfinite(ca4[b, :, :3]).all(1)
+    touch = badres[i] | badres[j]
+    same = (i < R) == (j < R)
+    assert touch.any() and not hit[touch].any() and hit[same & ~touch].all()
+    assert misses == int((~hit).sum()) == int(r["counter"][0])
+    if kind == "inf_residue":
+        loose, _ = gh.hit_ref(i, j, r["codes"], r["radial"], code0, R, N - R, mutant="inf_hits")
+        assert (loose & ~hit).any(), "no pair at infinity whose finite entry lies beyond the last bin: inf <= inf was never at stake"
+    # k_l0_pairs on the non-finite pose
+    p = pairs_launch(h, c)
+    ii, jj = gh.all_pairs(R, N - R)
+    full = feat_launch(h, dict(c, K=N, edges=np.tile(np.arange(N, dtype=np.int32), (1, N, 1))))
+    sel = ii * N + jj
+    pref = gh.edge_ref(n4[b], ca4[b], cb4[b], ii, jj, R, 22.0)
+    gh.check_edge_codes(full["codes"][sel], full["radial"][sel], pref, gh.angle_margin(pref))
+    gh.check_pairs(p["code0"], p["rows"], R, N - R, full["codes"][sel], full["radial"][sel])
+
+
 # ---- 4: k_clash_force --------------------------------------------------------------------------------------------------------------
 def clash_launch(h, c):
     B, R, L = c["B"], c["R"], c["L"]
@@ -334,6 +448,24 @@ def test_clash_force_without_contact(h):
     lig_out, tr_out = clash_launch(h, c)
     np.testing.assert_array_equal(lig_out.view(np.uint32).reshape(-1), c["lig"].view(np.uint32).reshape(-1))
     np.testing.assert_array_equal(tr_out.view(np.uint32), c["tr0"].view(np.uint32))
+
+
+@pytest.mark.parametrize("R,L", ((300, 40), (9, 342)))
+@pytest.mark.parametrize("where,value", (((7, 2), np.nan), ((0, 4), np.inf), ((-1, 8), -np.inf)), ids=("nan_in_N", "inf_in_CA", "neg_inf_in_C"))
+def test_clash_force_non_finite(h, R, L, where, value):
+    """One NaN or infinite coordinate in ONE atom of trajectory 1 of B = 3.  That atom passes no d^2 < 16.5 and would be dropped from the
+    force while the rest of the pose is moved by a finite shift: the pose gets a NaN shift instead - every coordinate of it and its
+    tr_update are NaN - and trajectories 0 and 2 have the bits of the launch with trajectory 1 finite (guards: run).  L = 342: the
+    second ligand atom per thread."""
+    c = gh.clash_case(R, L)
+    good_lig, good_tr = clash_launch(h, c)
+    bad = dict(c, lig=c["lig"].copy())
+    bad["lig"][1, where[0], where[1]] = value
+    lig, tr = clash_launch(h, bad)
+    assert np.isfinite(good_lig).all() and np.isfinite(good_tr).all()
+    for got, ref in ((lig, good_lig), (tr, good_tr)):
+        np.testing.assert_array_equal(got[[0, 2]].view(np.uint32), ref[[0, 2]].view(np.uint32))
+    assert np.isnan(lig[1]).all() and np.isnan(tr[1]).all(), "a non-finite pose kept numbers through the clash force"
 
 
 # ---- 5: k_init_pose ----------------------------------------------------------------------------------------------------------------

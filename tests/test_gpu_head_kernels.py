@@ -485,3 +485,157 @@ def test_heads_replayed_step_draws(h):
         assert np.isfinite(rep[k]).all(), k
         assert (rep[k].view(np.uint32) == direct[k].view(np.uint32)).all(), k
         assert (other_step[k] != direct[k]).any() and (swapped[k] != direct[k]).any(), k
+
+
+# ---- non-finite poses (include/dfmdock_amd.h: contained, visible) ------------------------------------------------------------------------
+def same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+
+
+@pytest.mark.parametrize("all_atoms", (0, 1))
+@pytest.mark.parametrize("where,value", [((40, 0), np.nan), ((40, 4), np.nan), ((85, 8), np.inf), ((0, 3), -np.inf)],
+                         ids=["nan_in_N", "nan_in_CA", "inf_in_C", "neg_inf_in_CA"])
+def test_prep_pose_non_finite(h, where, value, all_atoms):
+    """One NaN or infinite coordinate in ANY backbone atom of pose 1 of B = 3 (an N atom: without the mark the CA centroid, every CA and so
+    every distance of the pose stayed finite and only angle bins went to 0): every prepared coordinate of that pose is NaN on all three
+    axes, w stays 0, and poses 0 and 2 have the bits of the launch with pose 1 finite."""
+    B, R, L = 3, 5, 86
+    N = R + L
+    rng = np.random.default_rng([L, 23])
+    rec_pos = (rng.standard_normal((R, 9)) * 6).astype(np.float32)
+    lig = (rng.standard_normal((B, L, 9)) * 6 + 2).astype(np.float32)
+    bad = lig.copy()
+    bad[1, where[0], where[1]] = value
+    out = lambda: dict(prep_pos=Out(np.float32, B * N * 4), prep_ca4=Out(np.float32, B * N * 4), prep_cb4=Out(np.float32, B * N * 4))
+    good = run(h, "prep_pose", dict(rec_pos=rec_pos, lig=lig, **out()), B=B, R=R, L=L, all_atoms=all_atoms)
+    r = run(h, "prep_pose", dict(rec_pos=rec_pos, lig=bad, **out()), B=B, R=R, L=L, all_atoms=all_atoms)
+    for k in ("prep_pos", "prep_ca4", "prep_cb4"):
+        g, x = good[k].reshape(B, N, 4), r[k].reshape(B, N, 4)
+        assert np.isfinite(g).all()
+        assert same_bits(x[[0, 2]], g[[0, 2]]), f"{k}: another pose's bits changed"
+        assert np.isnan(x[1, :, :3]).all() and (x[1, :, 3] == 0).all(), f"{k}: the non-finite pose has numbers among its prepared coordinates"
+
+
+def test_energy_pairs_non_finite(h):
+    """Trajectory 1 of B = 3 as k_prep_pose leaves a non-finite pose (every CA NaN) and NaN activations: no pair passes D < cut_off or
+    D <= 3, so its sums, counts and clash counts are exactly 0 - the kernel alone would report a pose out of contact; k_heads turns that
+    energy into NaN (test_heads_non_finite) and num_clashes is documented as 0.  The other trajectories keep their bits."""
+    R, L = hh.ENERGY_SIZES[-1]
+    c = hh.energy_case(R, L, B=3)
+    bufs = {k: c[k] for k in ("enA", "enB", "ca4", "en_ln_w", "en_ln_b", "en_w3")}
+    out = lambda: dict(spart=Out(np.float32, 3 * R * 2), clash=Out(np.int32, 3 * R))
+    good = run(h, "energy_pairs", dict(bufs, **out()), B=3, R=R, L=L, cut_off=hh.CUT_OFF, want_energy=1)
+    bad = dict(bufs, ca4=bufs["ca4"].copy(), enA=bufs["enA"].copy(), enB=bufs["enB"].copy())
+    bad["ca4"][1, :, :3] = np.nan
+    bad["enA"][1] = np.nan
+    bad["enB"][1] = np.nan
+    r = run(h, "energy_pairs", dict(bad, **out()), B=3, R=R, L=L, cut_off=hh.CUT_OFF, want_energy=1)
+    sp, sg = r["spart"].reshape(3, R, 2), good["spart"].reshape(3, R, 2)
+    assert same_bits(sp[[0, 2]], sg[[0, 2]]) and (r["clash"].reshape(3, R)[[0, 2]] == good["clash"].reshape(3, R)[[0, 2]]).all()
+    assert (sp[1] == 0).all() and (r["clash"].reshape(3, R)[1] == 0).all()
+    assert (sg[1, :, 1] > 0).any(), "the finite pose has pairs inside the cut-off"
+
+
+@pytest.mark.parametrize("en_mode", (0, 1, 2))
+def test_heads_non_finite(h, en_mode):
+    """k_heads on B = 3 with trajectory 1 non-finite as the kernels before it leave it: every prepared CA NaN, the force NaN, the energy
+    parts those of k_energy_pairs / k_pair_finish_s for a pose no pair of which passes the cut-off (sums and counts 0).  Its tr_score,
+    rot_score AND energy are NaN - not 0 / 1e-6, the energy of a pose out of contact -, num_clashes is 0; trajectories 0 and 2 have the
+    bits of the launch with trajectory 1 finite."""
+    L = 86
+    x = heads_inputs(L, n_part=40)
+    B, R = x["B"], x["R"]
+    kw = dict(B=B, R=R, L=L, n_part=40, want_energy=1, en_mode=en_mode, pool_div=float(L), hid_bstride=256, trace_s_bstride=24)
+    out = lambda: dict(scores=Out(np.float32, B * 8), trace_scores=Out(np.float32, B * 24))
+    good = run(h, "heads", dict(heads_bufs(x), **out()), **kw)["scores"].reshape(B, 8)
+    y = dict(x, fvec=x["fvec"].copy(), ca4=x["ca4"].copy(), en=x["en"].copy(), clash=x["clash"].copy())
+    y["fvec"][1] = np.nan
+    y["ca4"][1, :, :3] = np.nan
+    y["en"][1] = 0
+    y["clash"][1] = 0
+    r = run(h, "heads", dict(heads_bufs(y), **out()), **kw)
+    sc = r["scores"].reshape(B, 8)
+    assert np.isfinite(good).all() and same_bits(sc[[0, 2]], good[[0, 2]])
+    assert np.isnan(sc[1, :7]).all(), f"finite outputs of a non-finite pose: {sc[1]}"
+    assert sc[1, 7] == 0
+    assert same_bits(r["trace_scores"].reshape(B, 24)[:, :8][[0, 2]], good[[0, 2]]) and np.isnan(r["trace_scores"].reshape(B, 24)[1, :7]).all()
+
+
+def test_heads_update_non_finite(h):
+    """The update launch (with prep_next) on the same batch: the non-finite trajectory's pose, tr_update, rot_update and prepared
+    coordinates are NaN, the others' bits are those of the launch with trajectory 1 finite."""
+    L = 86
+    x = heads_inputs(L, seed=2)
+    B, R = x["B"], x["R"]
+    lig, rot0, tr0, z, rec_pos = update_inputs(x)
+    good = update_launch(h, x, lig, rot0, tr0, z, 0, 0, rec_pos)
+    y = dict(x, fvec=x["fvec"].copy(), ca4=x["ca4"].copy(), en=x["en"].copy(), clash=x["clash"].copy())
+    y["fvec"][1] = np.nan
+    y["ca4"][1, :, :3] = np.nan
+    y["en"][1] = 0
+    y["clash"][1] = 0
+    lb = lig.copy()
+    lb[1, 40, 4] = np.nan
+    r = update_launch(h, y, lb, rot0, tr0, z, 0, 0, rec_pos)
+    for k, shape in (("lig", (B, L * 9)), ("tr_upd", (B, 3)), ("rot_upd", (B, 3)), ("prep_pos", (B, -1)), ("prep_ca4", (B, -1)), ("prep_cb4", (B, -1)),
+                     ("scores", (B, 8))):
+        a, g = r[k].reshape(shape), good[k].reshape(shape)
+        assert same_bits(a[[0, 2]], g[[0, 2]]), k
+    assert np.isnan(r["lig"].reshape(B, L * 9)[1]).all() and np.isnan(r["tr_upd"].reshape(B, 3)[1]).all() and np.isnan(r["rot_upd"].reshape(B, 3)[1]).all()
+    for k in ("prep_pos", "prep_ca4", "prep_cb4"):
+        assert np.isnan(r[k].reshape(B, R + L, 4)[1, :, :3]).all(), k
+    assert np.isnan(r["scores"].reshape(B, 8)[1, :7]).all()
+
+
+def pair_batch3(c):
+    """A pair-head case as B = 3 (trajectory 0 once more as the third) and the same with trajectory 1 non-finite: CA NaN, P and Q NaN."""
+    pick = [0, 1, 0]
+    good = dict(c, **{k: np.ascontiguousarray(c[k][pick]) for k in ("P", "Q", "ca4")}, B=3)
+    bad = dict(good, **{k: good[k].copy() for k in ("P", "Q", "ca4")})
+    bad["ca4"][1, :, :3] = np.nan
+    bad["P"][1] = np.nan
+    bad["Q"][1] = np.nan
+    return good, bad
+
+
+def test_pair_heads_non_finite(h, m_cases, x_cases):
+    """k_pair_head_m (+ k_pair_finish_s), k_pair_head<1> (+ k_pair_finish) and k_pair_dist with trajectory 1 of B = 3 non-finite: the
+    other two keep their bits in every output; the bad one's S, force and distance logits are NaN; its masked energy sums and counts and
+    its clash count are 0 (no pair passes D < cut_off: k_heads makes the energy NaN)."""
+    R, L = hh.PAIR_M_SIZES[3]      # 33 x 65: a partial 32-row tile and a partial ligand tile
+    good, bad = pair_batch3(m_cases[f"size_{R}_{L}"])
+    Sg, Sb = run_head_m(h, good, B=3), run_head_m(h, bad, B=3)
+    assert same_bits(Sb[[0, 2]], Sg[[0, 2]]) and np.isnan(Sb[1, :, :R]).all()
+    n_part = n_part_of(R)
+    sc = dict(B=3, R=R, L=L, Rp=Sg.shape[2], n_part=n_part, cut_off=hh.CUT_OFF, inv_pool=1.0 / R)
+    for S, ca4, tag in ((Sg, good["ca4"], "good"), (Sb, bad["ca4"], "bad")):
+        r0 = run(h, "pair_finish_s", dict(S=S, ca4=ca4, fvec=Out(np.float32, 3 * L * 3), clash=Out(np.int32, 3 * n_part)), mode=0, **sc)
+        r1 = run(h, "pair_finish_s", dict(S=S, ca4=ca4, spart=Out(np.float32, 3 * n_part * 2)), mode=1, **sc)
+        if tag == "good":
+            f0, c0, s0 = r0["fvec"].reshape(3, L, 3), r0["clash"].reshape(3, n_part), r1["spart"].reshape(3, n_part, 2)
+        else:
+            f1, c1, s1 = r0["fvec"].reshape(3, L, 3), r0["clash"].reshape(3, n_part), r1["spart"].reshape(3, n_part, 2)
+    assert same_bits(f1[[0, 2]], f0[[0, 2]]) and (c1[[0, 2]] == c0[[0, 2]]).all() and same_bits(s1[[0, 2]], s0[[0, 2]])
+    assert np.isnan(f1[1]).all() and (c1[1] == 0).all() and (s1[1] == 0).all()
+    # k_pair_head<1>
+    name = f"size_{hh.PAIR_X_SIZES[3][0]}_{hh.PAIR_X_SIZES[3][1]}"      # 65 x 7: two receptor tiles
+    good, bad = pair_batch3(x_cases[name])
+    R, L = good["R"], good["L"]
+    RT = (R + 63) // 64
+    sc = dict(B=3, R=R, L=L, cut_off=hh.CUT_OFF, inv_pool=1.0 / R)
+    res = {}
+    for tag, c in (("good", good), ("bad", bad)):
+        r0 = run(h, "pair_head", dict(head_bufs(c), fpart=Out(np.float32, 3 * RT * L * 3), clash=Out(np.int32, 3 * RT * 4)), mode=0, **sc)
+        rf = run(h, "pair_finish", dict(fpart=r0["fpart"], fvec=Out(np.float32, 3 * L * 3)), **sc)
+        r1 = run(h, "pair_head", dict(head_bufs(c), spart=Out(np.float32, 3 * RT * 4 * 2)), mode=1, **sc)
+        res[tag] = (rf["fvec"].reshape(3, L, 3), r0["clash"].reshape(3, -1), r1["spart"].reshape(3, -1, 2))
+    (f0, c0, s0), (f1, c1, s1) = res["good"], res["bad"]
+    assert same_bits(f1[[0, 2]], f0[[0, 2]]) and (c1[[0, 2]] == c0[[0, 2]]).all() and same_bits(s1[[0, 2]], s0[[0, 2]])
+    assert np.isnan(f1[1]).all() and (c1[1] == 0).all() and (s1[1] == 0).all()
+    # k_pair_dist
+    c = hh.pair_case(3, 5, seed=5)
+    good, bad = pair_batch3(dict(c, R=3, L=5))
+    w3t = (np.random.default_rng(5).standard_normal((H, 64)) / 16).astype(np.float32)
+    d0 = run(h, "pair_dist", dict(head_bufs(good), w3=w3t, dist=Out(np.float32, 3 * 3 * 5 * 64)), B=3, R=3, L=5)["dist"].reshape(3, -1)
+    d1 = run(h, "pair_dist", dict(head_bufs(bad), w3=w3t, dist=Out(np.float32, 3 * 3 * 5 * 64)), B=3, R=3, L=5)["dist"].reshape(3, -1)
+    assert same_bits(d1[[0, 2]], d0[[0, 2]]) and np.isnan(d1[1]).all() and np.isfinite(d0).all()

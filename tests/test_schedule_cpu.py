@@ -171,3 +171,16 @@ def test_graph_key(exe):
     for i in range(len(inputs)):
         for j in range(len(inputs)):
             assert (keys[i] == keys[j]) == (ident[i] == ident[j]), (inputs[i], inputs[j])
+
+
+@pytest.mark.parametrize("n", [1, 9, 360, 1926])      # one value, one residue, 24 + 16 residues, 7CEI (214 x 9)
+def test_first_nonfinite(exe, n):
+    """The scan behind the refusal of a non-finite stored pose (dfm_complex_create / dfm_complex_set_pose): the index of the FIRST NaN or
+    infinity - either sign, quiet, signalling, any payload - and n for an array of numbers (the largest finite value and denormals
+    included); the block has exactly n floats, so reading past it is a sanitizer report."""
+    one = lambda *planted: int(exe("finite", n, *[f"{o}:{w:x}" for o, w in planted])[0])
+    assert one() == n
+    assert one((n - 1, 0x7F7FFFFF), (0, 0x00000001), (n // 2, 0x80000000), (n // 3, 0xFF7FFFFF)) == n
+    for w in (0x7FC00000, 0xFFC00000, 0x7F800001, 0xFFBFFFFF, 0x7FFFFFFF, 0x7F800000, 0xFF800000):
+        assert one((n - 1, w)) == n - 1 and one((0, w)) == 0 and one((n // 2, w)) == n // 2
+        assert one((n - 1, w), (n // 2, 0x7FC00000)) == n // 2
